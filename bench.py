@@ -1,14 +1,22 @@
 #!/usr/bin/env python3
-"""Headline benchmark: Gemma-4 12B decode tok/s (+ prefill TFLOP/s) on MI355X for the three weight
-policies of BASELINE.json (bf16 / PerChannelFp8 / PerGroupFp4), with the roofline fraction of the
-dominant kernel and the restated reference CPU backend timed beside it.
+"""Headline benchmark: Gemma-4 12B decode tok/s on MI355X for the first weight policy of --policies.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--policies bf16,fp8,fp4] [--no-prefill]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--policies bf16,fp8,fp4] [--no-prefill] [--dump-outputs DIR] [--full]
 
 A "step" is one decode token of the whole model (embedding -> 48 blocks -> final norm -> lm_head, fp32
 logits) at context 2048 with every weight resident in HBM, replayed from one captured hipGraph.  The
 path does not shard: with --gpus N every rank runs an independent replica on its
 own GPU; there is no data-path collective.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: it builds the first policy's model, fills the KV cache with one
+T=2048 prefill, warms up, times the --steps decode steps and prints the line.  --full adds everything else, as
+before: every policy of BASELINE.json (bf16 / PerChannelFp8 / PerGroupFp4) with its timed prefill (W8A8 and
+per-forward staging beside it), the roofline fraction of the dominant kernel, the measured stream-read ceiling and
+launch cost, BASELINE config 2 (GPT-2 124M) and the restated reference CPU backend timed beside them.
+
+--dump-outputs DIR writes what the last timed step computed -- the fp32 logits and the token the device sampler drew
+from them -- as DIR/logits.npy (float32) and DIR/next_token.npy (float64).  The inputs (synthetic weights, prompt,
+first decode token) are fixed, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -182,6 +190,29 @@ def timed_prefill(m):
     return _median(xs), min(xs), max(xs) - min(xs)
 
 
+FIRST_DECODE_TOKEN = 17       # mila_gemma_time_decode feeds this id to the first step; every later step feeds the token the device sampler drew
+
+
+def prompt_tokens(T):
+    """the T-token prompt mila_gemma_time_prefill feeds: (i * 7919 + 13) mod 1000"""
+    import numpy as np
+    return ((np.arange(T, dtype=np.int64) * 7919 + 13) % 1000).astype(np.int32)
+
+
+def dump_outputs(m, out_dir, ctx, steps, warmup, mode):
+    """--dump-outputs: what the last timed decode step computed -- its fp32 logits and the token the device sampler drew from them --
+    as out_dir/logits.npy (float32) and out_dir/next_token.npy (float64).  The runner's timed loop keeps neither, so the same chain is
+    run again on the same path: warmup + steps greedy steps from the context (each writes its own KV row before any later step reads
+    it, so every step sees the caches its timed twin saw), then the last step once more with the token it was fed, for its logits."""
+    import numpy as np
+    n = warmup + steps
+    drawn = m.generate(FIRST_DECODE_TOKEN, ctx, n, mode)
+    logits = m.decode(int(drawn[-2]) if n > 1 else FIRST_DECODE_TOKEN, ctx + n - 1, mode)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), logits.astype(np.float32))
+    np.save(os.path.join(out_dir, "next_token.npy"), drawn[-1:].astype(np.float64))
+
+
 def launch_boundary_us(capi):
     """what one more graph node costs when it does no work: a chain of 64 one-thread launches (advance_position) replayed from a hipGraph, microseconds per launch
     (tools/bench_fixed_cost.py's first case, measured in this process) -- the `fixed_us_per_launch` of the decode design floor"""
@@ -203,6 +234,28 @@ def launch_boundary_us(capi):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / (20 * 64)
+
+
+def stream_read_GBps(capi):
+    """measured streaming ceiling beside the 8 TB/s spec: a read-only pass over 2 GiB with 16-byte loads, GB/s"""
+    import ctypes as C
+    import torch
+    n = 2 << 30
+    src = torch.empty(n, dtype=torch.uint8, device="cuda")
+    sink = torch.zeros(4096, dtype=torch.float32, device="cuda")
+    lib = capi.load()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for _ in range(2):
+        capi.check(lib.mila_cdna4_stream_read(C.c_void_p(sink.data_ptr()), C.c_void_p(src.data_ptr()), C.c_size_t(n), st))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5):
+        capi.check(lib.mila_cdna4_stream_read(C.c_void_p(sink.data_ptr()), C.c_void_p(src.data_ptr()), C.c_size_t(n), st))
+    e1.record()
+    torch.cuda.synchronize()
+    gbps = round(5 * n / e0.elapsed_time(e1) / 1e6, 1)
+    del src
+    return gbps
 
 
 def _free_port():
@@ -287,7 +340,12 @@ def main():
     ap.add_argument("--gemm-schedule", type=int, default=None, help="tuning hook: 0 lockstep, 1 ping-pong (4 phases), 3 ping-pong (2 phases, default)")
     ap.add_argument("--tune", action="append", default=[], metavar="NAME=VALUE", help="named tuning variable (csrc/internal.h: mila_cdna4_tune), repeatable; experiments only")
     ap.add_argument("--bounded-local-kv", type=int, default=0, help="1: SlidingWindowKvCache on the sliding-window layers (bounded ring of window + chunk - 1 rows)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (logits, sampled token) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="beside the headline: every --policies entry with its timed prefill, the dominant kernel's roofline, "
+                                                         "stream-read and launch-cost yardsticks, GPT-2 config 2 and the CPU baseline")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
 
     # N > 1 and no launcher env: this process only starts one child per GPU (it never initialises a GPU itself)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -305,9 +363,11 @@ def main():
     if a.bounded_local_kv:
         cfg["bounded_local_kv"] = 1
     policies = [p for p in a.policies.split(",") if p]
+    if not a.full:
+        policies = policies[:1]                    # a plain run measures the headline policy only
 
     # the CPU baseline FIRST (rank 0 of the single-GPU line only): the GPU phases then run back to back to the end of the process
-    cpu = cpu_baseline(cfg) if (rank == 0 and world == 1 and not a.no_cpu and not a.stub) else None
+    cpu = cpu_baseline(cfg) if (a.full and rank == 0 and world == 1 and not a.no_cpu and not a.stub) else None
 
     if a.stub:
         if os.environ.get("MILA_BENCH_STUB_FAIL_RANK") == str(rank):      # tests: a replica that dies before the barrier must end the whole command, promptly
@@ -341,6 +401,9 @@ def main():
     ctx = a.context if a.context else CONTEXT
     if ctx < CHUNK:
         raise SystemExit("bench.py: --context must be at least %d" % CHUNK)
+    if a.dump_outputs and a.bounded_local_kv and a.warmup + a.steps > (1 if a.no_prefill else CHUNK):
+        # the ring of window + chunk - 1 rows would have evicted prompt rows the first steps read: the last step could not be run again as it was timed
+        raise SystemExit("bench.py: --dump-outputs with --bounded-local-kv needs --warmup + --steps <= %d" % (1 if a.no_prefill else CHUNK))
     for pol in policies:
         m = host.Gemma(pol, cfg, max_seq=ctx + a.steps + a.warmup + 8, max_prefill=1 if a.no_prefill else CHUNK, seed=1234)
         if a.resident is not None:
@@ -351,7 +414,13 @@ def main():
         resident = a.resident is None or bool(a.resident)
         r["resident_prefill_weights_GB"] = round(m.resident_staging_bytes() / 1e9, 3)
         r["total_resident_GB"] = round((info["weight_bytes"] + m.resident_staging_bytes()) / 1e9, 3)      # weights + scales + tied table + the staging above (KV caches / activations aside)
-        if not a.no_prefill:
+        if not a.no_prefill and not a.full:
+            # a plain run only fills the KV cache: the prompt mila_gemma_time_prefill feeds, once, or the chunked prompt up to the context
+            if ctx > CHUNK:
+                m.time_prefill_chunked(ctx)
+            else:
+                m.prefill(prompt_tokens(CHUNK))
+        if not a.no_prefill and a.full:
             ms, ms_min, spread = timed_prefill(m)
             r["prefill_timing"] = "median of %d timed passes (HIP events, one T=2048 prefill each, each behind an untimed pass) after %d untimed; min and max - min beside it" % (PREFILL_TIMED, PREFILL_UNTIMED)
             r["prefill_ms_min"] = round(ms_min, 3)
@@ -402,50 +471,37 @@ def main():
         torch.cuda.synchronize()
         ranks.barrier()
         t["wall_ms_per_step"] = ranks.max_over_ranks(t["wall_ms_per_step"])      # timing only: max over ranks
-        k = m.time_dominant_kernel(3)
+        if a.dump_outputs and rank == 0 and pol == policies[0]:
+            dump_outputs(m, a.dump_outputs, ctx, a.steps, a.warmup, a.mode)
         r["launches_per_token"] = m.graph_node_count() if a.mode == "graph" else None
         r.update({"ms_per_step": round(t["wall_ms_per_step"], 4), "device_ms_per_step": round(t["device_ms_per_step"], 4),
                   "tok_s": round(1e3 / t["wall_ms_per_step"], 2),
-                  "token_roofline_frac": round(info["decode_bytes_per_token"] / (t["wall_ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                  "dominant_kernel": {"name": "matvec_kernel<fmt,R,U,PRO=2,GEGLU> (fc_gate_up)", "avg_us": round(k["avg_us"], 3),
-                                      "bytes": k["bytes"], "GBps": round(k["bytes"] / k["avg_us"] / 1e3, 1)}})
+                  "token_roofline_frac": round(info["decode_bytes_per_token"] / (t["wall_ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)})
+        if a.full:
+            k = m.time_dominant_kernel(3)
+            r["dominant_kernel"] = {"name": "matvec_kernel<fmt,R,U,PRO=2,GEGLU> (fc_gate_up)", "avg_us": round(k["avg_us"], 3),
+                                    "bytes": k["bytes"], "GBps": round(k["bytes"] / k["avg_us"] / 1e3, 1)}
         results[pol] = r
         m.close()
         del m
 
     # BASELINE config 2 beside the headline: GPT-2 124M bf16 forward, B = 8, T = 1024 (tools/bench_gpt2.py; rank 0 of the single-GPU line only)
     gpt2 = None
-    if rank == 0 and world == 1 and not a.no_gpt2:
+    if a.full and rank == 0 and world == 1 and not a.no_gpt2:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_gpt2
         gpt2 = bench_gpt2.run(5)
 
-    # measured streaming ceiling beside the 8 TB/s spec: a read-only pass over 2 GiB with 16-byte loads
-    import ctypes as C
-    n = 2 << 30
-    src = torch.empty(n, dtype=torch.uint8, device="cuda")
-    sink = torch.zeros(4096, dtype=torch.float32, device="cuda")
-    lib = capi.load()
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    for _ in range(2):
-        capi.check(lib.mila_cdna4_stream_read(C.c_void_p(sink.data_ptr()), C.c_void_p(src.data_ptr()), C.c_size_t(n), st))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5):
-        capi.check(lib.mila_cdna4_stream_read(C.c_void_p(sink.data_ptr()), C.c_void_p(src.data_ptr()), C.c_size_t(n), st))
-    e1.record()
-    torch.cuda.synchronize()
-    stream_read_gbps = round(5 * n / e0.elapsed_time(e1) / 1e6, 1)
-    del src
-
-    # the decode design floor: one launch per fused Linear / attention step means every token pays launches_per_token node boundaries on top of its
-    # bytes at the rate a pure stream reaches on this box; what fraction of the 8 TB/s roofline that design can reach at best, per policy
-    fixed_us = round(launch_boundary_us(capi), 3)
-    for pol, r in results.items():
-        if r.get("launches_per_token"):
-            floor_ms = r["bytes_per_token_GB"] / stream_read_gbps * 1e3 + r["launches_per_token"] * fixed_us * 1e-3
-            r["design_floor_ms"] = round(floor_ms, 4)
-            r["design_floor_frac"] = round(r["bytes_per_token_GB"] / HBM_PEAK_GBPS * 1e3 / floor_ms, 4)
+    if a.full:
+        # the decode design floor: one launch per fused Linear / attention step means every token pays launches_per_token node boundaries on top of its
+        # bytes at the rate a pure stream reaches on this box; what fraction of the 8 TB/s roofline that design can reach at best, per policy
+        stream_read_gbps = stream_read_GBps(capi)
+        fixed_us = round(launch_boundary_us(capi), 3)
+        for pol, r in results.items():
+            if r.get("launches_per_token"):
+                floor_ms = r["bytes_per_token_GB"] / stream_read_gbps * 1e3 + r["launches_per_token"] * fixed_us * 1e-3
+                r["design_floor_ms"] = round(floor_ms, 4)
+                r["design_floor_frac"] = round(r["bytes_per_token_GB"] / HBM_PEAK_GBPS * 1e3 / floor_ms, 4)
 
     head = results[policies[0]]
     out = {
@@ -457,24 +513,25 @@ def main():
         "config": {"workload": "Gemma-4 12B, weight policy %s, B=1, prefill T=2048%s then decode at positions %d.." % (policies[0], "" if ctx == CONTEXT else " (chunked to %d)" % ctx, ctx),
                    "decode_mode": a.mode, "replicas": world, "parallelism": "replicas only (no collective)", "bounded_local_kv": int(bool(a.bounded_local_kv)),
                    **({"tune": a.tune} if a.tune else {})},
-        "roofline": {"bound": "hbm", "achieved": head["dominant_kernel"]["GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(head["dominant_kernel"]["GBps"] / HBM_PEAK_GBPS, 4), "traffic": measured_traffic(policies[0])[0],
-                     "traffic_source": measured_traffic(policies[0])[1],
-                     "kernel": head["dominant_kernel"]["name"], "avg_us": head["dominant_kernel"]["avg_us"],
-                     "algorithmic_bytes_per_launch": head["dominant_kernel"]["bytes"],
-                     "whole_token_frac": head["token_roofline_frac"],
-                     # the floor of THIS design (one graph node per fused Linear / attention step): bytes at the measured stream rate + launches x the cost of an empty node
-                     "launches_per_token": head.get("launches_per_token"), "fixed_us_per_launch": fixed_us,
-                     "design_floor_frac": {pol: r.get("design_floor_frac") for pol, r in results.items()},
-                     "design_floor": "bytes_per_token / measured_stream_read + launches_per_token x fixed_us_per_launch, as a fraction of bytes_per_token / 8 TB/s",
-                     # beside the 8 TB/s datasheet figure: what a read-only pass reaches on this box (the matvec's launch shape, non-temporal 16-byte loads,
-                     # 2 GiB: a yardstick measured in the same process) and the guide's float4-copy figure; the whole token against each
-                     "measured_stream_read_GBps": stream_read_gbps,
-                     "frac_of_measured_stream_read": round(head["dominant_kernel"]["GBps"] / stream_read_gbps, 4),
-                     "whole_token_frac_of_measured_stream_read": round(head["token_roofline_frac"] * HBM_PEAK_GBPS / stream_read_gbps, 4),
-                     "whole_token_frac_of_guide_achievable_6300GBps": round(head["token_roofline_frac"] * HBM_PEAK_GBPS / 6300.0, 4)},
-        "policies": results,
     }
+    if a.full:
+        out["roofline"] = {"bound": "hbm", "achieved": head["dominant_kernel"]["GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                           "frac": round(head["dominant_kernel"]["GBps"] / HBM_PEAK_GBPS, 4), "traffic": measured_traffic(policies[0])[0],
+                           "traffic_source": measured_traffic(policies[0])[1],
+                           "kernel": head["dominant_kernel"]["name"], "avg_us": head["dominant_kernel"]["avg_us"],
+                           "algorithmic_bytes_per_launch": head["dominant_kernel"]["bytes"],
+                           "whole_token_frac": head["token_roofline_frac"],
+                           # the floor of THIS design (one graph node per fused Linear / attention step): bytes at the measured stream rate + launches x the cost of an empty node
+                           "launches_per_token": head.get("launches_per_token"), "fixed_us_per_launch": fixed_us,
+                           "design_floor_frac": {pol: r.get("design_floor_frac") for pol, r in results.items()},
+                           "design_floor": "bytes_per_token / measured_stream_read + launches_per_token x fixed_us_per_launch, as a fraction of bytes_per_token / 8 TB/s",
+                           # beside the 8 TB/s datasheet figure: what a read-only pass reaches on this box (the matvec's launch shape, non-temporal 16-byte loads,
+                           # 2 GiB: a yardstick measured in the same process) and the guide's float4-copy figure; the whole token against each
+                           "measured_stream_read_GBps": stream_read_gbps,
+                           "frac_of_measured_stream_read": round(head["dominant_kernel"]["GBps"] / stream_read_gbps, 4),
+                           "whole_token_frac_of_measured_stream_read": round(head["token_roofline_frac"] * HBM_PEAK_GBPS / stream_read_gbps, 4),
+                           "whole_token_frac_of_guide_achievable_6300GBps": round(head["token_roofline_frac"] * HBM_PEAK_GBPS / 6300.0, 4)}
+    out["policies"] = results
     if gpt2 is not None:
         out["gpt2_124M_bf16_B8_T1024"] = gpt2
     if rank == 0:

@@ -1,8 +1,10 @@
-# usage: bash tools/prof_one.sh <tag> <policy>...   -> gpurun_out/prof_<tag>_<policy>/
+# usage: bash tools/prof_one.sh <tag> <policy>...   -> ${OUT_DIR:-build/out}/prof_<tag>_<policy>/
 set -e
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+out=${OUT_DIR:-build/out}
+mkdir -p "$out"
 for pol in "$@"; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag}_$pol -- python3 bench.py --steps 16 --warmup 4 --policies $pol --no-cpu --no-prefill > gpurun_out/prof_${tag}_$pol.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_$pol -- python3 bench.py --full --steps 16 --warmup 4 --policies $pol --no-cpu --no-prefill > $out/prof_${tag}_$pol.log 2>&1
   echo "trace $pol done"
 done
