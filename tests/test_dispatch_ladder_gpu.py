@@ -1,6 +1,8 @@
 """One oracle sweep over the Linear dispatch ladder: RocmLinearOp::forward -- through the host mirror's Linear component (libmila_host) -- at
 M in {1, 2, 16, 17, 32, 33, 64, 65, 255, 256, 300, 511, 512, 576, 1041, 2048, 2049, 2303} x the four Gemma-4 12B Linear shapes x the weight policies (bf16, PerChannelFp8<>
-with its default W8A16 prefill and with the opt-in W8A8 one, PerGroupFp4<128> = W4A8), sampled rows against the oracle of the arithmetic that policy runs at that row count,
+with its default W8A16 prefill and with the opt-in W8A8 one, PerGroupFp4<128> = W4A8), sampled rows against the oracle of the arithmetic that policy runs at that row count
+(gpu_util.sample_rows: every row up to 65, beyond that both ends of every 256-row tile-row, every 32-row band of three tile-rows and ten rows of the remainder; the
+expectation of all row counts in one float64 matmul, tests/ref_matmul.py, the bar elementwise, gpu_util.assert_gemm_close),
 AND the kernel form that served the call (csrc/internal.h: mila_cdna4_last_form) against a committed table (tests/golden/dispatch_ladder.json): a threshold edit in
 csrc/gemm.hip / gemm256.hip cannot silently route a prompt length to another form -- the table changes, and this test says so until the table is regenerated on purpose
 (MILA_RECORD_LADDER=1 python -m pytest tests/test_dispatch_ladder_gpu.py  ->  gpurun_out/dispatch_ladder.json).
@@ -13,8 +15,9 @@ import numpy as np
 import pytest
 
 import orc
+import ref_matmul
 import synth
-from gpu_util import assert_bf16_close
+from gpu_util import assert_bf16_close, assert_gemm_close, sample_rows
 from mila_amd import capi, host
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +26,22 @@ ROWS = [1, 2, 16, 17, 32, 33, 64, 65, 255, 256, 300, 511, 512, 576, 1041, 2048, 
 SHAPES = [("qkv_proj(local)", 3840, 8192), ("o_proj(local)", 4096, 3840), ("fc_gate_up", 3840, 30720), ("fc_down", 15360, 3840)]
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dispatch_ladder.json")
 RECORD = os.environ.get("MILA_RECORD_LADDER") == "1"
+
+
+def _expected_rows(policy, x, Wb, q):
+    """(float64 expectation, magnitude at (m_idx, n_idx)) of the prefill arithmetic (M > 1) of this policy on the stacked sampled rows of every row count: what
+    _expected restates row count by row count, through ref_matmul"""
+    if policy in ("bf16", "fp8"):
+        W = Wb if policy == "bf16" else ref_matmul.dequant_fp8_bf16_bits(*q)                # W8A16: bf16(dequantized weight), bf16 GEMM
+        return ref_matmul.linear_bf16w(x, W), lambda m, n: ref_matmul.abs_products("bf16", x, W, at=(m, n))
+    x8, ts = orc.quantize_act_fp8_per_token(x)
+    if policy == "fp8-w8a8":
+        w8, sc = q
+        return ref_matmul.linear_fp8a_fp8w(x8, ts, w8, sc, 1.0), lambda m, n: ref_matmul.abs_products("fp8a_fp8w", x8, w8, (ts, sc), at=(m, n))
+    q4, s4, ws, w8 = q                                                                       # W4A8: two-step epilogue
+    raw = ref_matmul.linear_fp8a_fp8w(x8, np.ones(len(ts), dtype=np.float32), w8, None, ws)
+    exp = orc.round_bf16(raw.astype(np.float32)).astype(np.float64) * ts.astype(np.float64)[:, None]
+    return exp, lambda m, n: ref_matmul.abs_products("fp8a_fp8w", x8, w8, (ts, np.float32(ws)), at=(m, n))
 
 
 def _expected(policy, M, x, Wb, q):
@@ -66,6 +85,7 @@ def test_every_row_count_reaches_a_tested_form_and_the_oracle(policy, shape):
     golden = json.load(open(GOLDEN)) if os.path.exists(GOLDEN) else {}
     table = {}
     rng = np.random.default_rng(K + N)
+    sampled = []                                                                             # (M, forms, rows, X[rows], Y[rows]) of every row count above 1
     try:
         for M in ROWS:
             X = orc.round_bf16((rng.standard_normal((M, K)) * rng.uniform(0.3, 2.0, (M, 1))).astype(np.float32))
@@ -74,11 +94,22 @@ def test_every_row_count_reaches_a_tested_form_and_the_oracle(policy, shape):
             forms = capi.last_form()
             assert forms, "no kernel form was noted for M = %d" % M
             table["%s/%s/%d" % (policy, name, M)] = forms
-            rows = sorted({0, M - 1})
-            exp = _expected(policy, M, X[rows] if M > 1 else X, Wb, q)
-            assert_bf16_close(Y[rows], exp, 2, 2e-3 * float(np.abs(exp).max()), "%s %s M=%d via %s" % (policy, name, M, "+".join(forms)))
+            if M == 1:                                                                       # the decode matvec: its one row, against its own arithmetic
+                exp = _expected(policy, M, X, Wb, q)
+                assert_bf16_close(Y, exp, 2, 2e-3 * float(np.abs(exp).max()), "%s %s M=%d via %s" % (policy, name, M, "+".join(forms)))
+                continue
+            rows = sample_rows(M, rng)
+            assert rows[0] == 0 and rows[-1] == M - 1
+            sampled.append((M, forms, rows, X[rows], np.ascontiguousarray(Y[rows])))
     finally:
         lin.close()
+    exp, mag = _expected_rows(policy, np.concatenate([s[3] for s in sampled]), Wb, q)
+    at = 0
+    for M, forms, rows, x, y in sampled:
+        e = exp[at:at + len(x)]
+        assert_gemm_close(y.reshape(len(x), N), e, lambda m, n, at=at: mag(m + at, n), 2, "%s %s M=%d via %s" % (policy, name, M, "+".join(forms)),
+                          2e-3 * float(np.abs(e).max()), row_ids=rows)
+        at += len(x)
     if RECORD:
         out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "dispatch_ladder.json")
         have = json.load(open(out)) if os.path.exists(out) else {}

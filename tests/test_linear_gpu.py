@@ -13,8 +13,9 @@ import pytest
 import torch
 
 import orc
+import ref_matmul
 from gpu_util import (assert_bf16_close, bits, dev_f32, dev_u16, dev_u8, empty_f32, empty_u16, empty_u8,
-                      host, rel_err)
+                      host, rel_err, sample_rows)
 from mila_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -355,13 +356,13 @@ def test_gemm_256_tile_kernel_agrees_with_the_128_tile_kernel(M, K, N, bias):
     fa, fc = orc.from_bf16_bits(bits(Y256)), orc.from_bf16_bits(bits(Y128))
     ok = (np.abs(oa - oc) <= 1) | (np.abs(fa - fc) <= 2e-3)
     assert ok.all(), int((~ok).sum())
-    rows = [0, 1, 127, 128, 255, M - 1, M // 2 + 3]
+    rows = sample_rows(M, np.random.default_rng(M + N))       # every 256-row tile-row, every 32-row band of three of them
     Xh = orc.from_bf16_bits(X[rows].view(torch.int16).cpu().numpy().view(np.uint16))
     Wb = W.view(torch.int16).cpu().numpy().view(np.uint16)
-    exp = orc.linear_bf16w(Xh, Wb, None)
+    exp = ref_matmul.linear_bf16w(Xh, Wb, None)
     if bias:
         bb = b.view(torch.int16).cpu().numpy().view(np.uint16)
-        exp = orc.round_bf16(exp).astype(np.float64) + orc.from_bf16_bits(bb).astype(np.float64)
+        exp = orc.round_bf16(exp.astype(np.float32)).astype(np.float64) + orc.from_bf16_bits(bb).astype(np.float64)
     assert_bf16_close(bits(Y256)[rows], exp, 2 if bias else 1, 2e-3, "gemm256 vs oracle")
 
 
@@ -485,8 +486,8 @@ def test_w4a8_prefill_matches_the_restated_reference(M, K, N, bias):
     x8_exp, ts_exp = orc.quantize_act_fp8_per_token(X)
     assert np.array_equal(host(ts_d), ts_exp) and np.array_equal(X8.cpu().numpy(), x8_exp)
     # 4. GEMM + epilogue, stand-alone and through the one-call form
-    rows = [0, 7, 129, M - 1]
-    raw = orc.linear_fp8a_fp8w(x8_exp[rows], np.ones(len(rows), dtype=np.float32), w8_exp, None, ws, None)       # sB * acc
+    rows = sorted(set(sample_rows(M, rng)) | {7})       # every 256-row tile-row, every 32-row band of three of them, the zero token
+    raw = ref_matmul.linear_fp8a_fp8w(x8_exp[rows], np.ones(len(rows), dtype=np.float32), w8_exp, None, ws, None)       # sB * acc
     exp = orc.round_bf16(raw.astype(np.float32)).astype(np.float64) * ts_exp[rows].astype(np.float64)[:, None]
     if bias:
         exp = exp + orc.from_bf16_bits(bb).astype(np.float64)

@@ -485,3 +485,93 @@ def test_gemma4_composition_matches_the_huggingface_fixture():
             # bf16 after every component through 6 random-weight layers: the same 1e-1-of-range bar the GPU path is held to
             # against this composition (tests/test_gemma_host_gpu.py); measured worst 5.7e-2
             assert np.abs(gb - exp).max() <= 1e-1 * np.abs(exp).max(), (pos, np.abs(gb - exp).max())
+
+
+# ---- tests/ref_matmul.py: the float64-BLAS twin of the oracle's Linear loops ------------------------------------------------------------------------------------
+def _twin_operands(K, M=24, N=96):
+    """the GPU tests' operands (test_w8a8_gpu._operands): channel scales over 4 octaves, token scales 0.2 - 3.0, an all-zero token"""
+    rng = np.random.default_rng(K)
+    Wb = orc.to_bf16_bits((rng.standard_normal((N, K)) / np.sqrt(K) * rng.uniform(0.25, 4.0, (N, 1))).astype(np.float32))
+    X = orc.round_bf16((rng.standard_normal((M, K)) * rng.uniform(0.2, 3.0, (M, 1))).astype(np.float32))
+    X[7] = 0.0
+    bb = orc.to_bf16_bits(rng.uniform(-0.1, 0.1, N).astype(np.float32))
+    return rng, Wb, X, bb
+
+
+def _fp32_ulps_apart(a, b):
+    a, b = (np.ascontiguousarray(v, dtype=np.float32).view(np.int32).astype(np.int64) for v in (a, b))
+    a, b = (np.where(v < 0, -(v & 0x7fffffff), v) for v in (a, b))
+    return int(np.abs(a - b).max())
+
+
+def test_ref_matmul_decodes_e4m3_and_bf16_like_the_oracle():
+    import ref_matmul
+    codes = np.arange(256, dtype=np.uint8)
+    mine = ref_matmul.e4m3_to_f64(codes)
+    theirs = np.array([orc.lib.orc_e4m3_to_f32(int(c)) for c in codes], dtype=np.float64)
+    assert np.array_equal(np.isnan(mine), np.isnan(theirs)) and np.array_equal(mine[~np.isnan(mine)], theirs[~np.isnan(theirs)])
+    allbits = np.arange(65536, dtype=np.uint16)
+    allbits = allbits[(allbits & 0x7f80) != 0x7f80]
+    assert np.array_equal(ref_matmul.bf16_bits_to_f64(allbits), orc.from_bf16_bits(allbits).astype(np.float64))
+
+
+@pytest.mark.parametrize("K", [128, 3840, 15360])
+def test_ref_matmul_fp8_x_fp8_is_the_oracle_exactly_and_order_independent(K):
+    """products of two e4m3 values have 8 significant bits and the whole sum fits a double: float64 BLAS gives the oracle's bits, in any order of k"""
+    import ref_matmul
+    rng, Wb, X, bb = _twin_operands(K)
+    w8, sc = orc.quantize_fp8_per_channel(Wb)
+    x8, ts = orc.quantize_act_fp8_per_token(X)
+    for row_scale, tensor_scale, bias in ((sc, 1.0, None), (sc, 1.0, bb), (None, 0.37, None), (None, 0.37, bb)):
+        mine = ref_matmul.linear_fp8a_fp8w(x8, ts, w8, row_scale, tensor_scale, bias)
+        assert mine.dtype == np.float64
+        assert np.array_equal(mine.astype(np.float32), orc.linear_fp8a_fp8w(x8, ts, w8, row_scale, tensor_scale, bias))
+    base = ref_matmul.linear_fp8a_fp8w(x8, ts, w8, sc)
+    perm = rng.permutation(K)
+    assert np.array_equal(base, ref_matmul.linear_fp8a_fp8w(x8[:, ::-1], ts, w8[:, ::-1], sc))
+    assert np.array_equal(base, ref_matmul.linear_fp8a_fp8w(x8[:, perm], ts, w8[:, perm], sc))
+    assert np.all(base[7] == 0.0)
+    # the magnitude: whole matrix and element gather agree, and it bounds the sum
+    mag = ref_matmul.abs_products("fp8a_fp8w", x8, w8, (ts, sc))
+    assert np.all(mag >= np.abs(base) * (1 - 1e-12))
+    m_idx, n_idx = rng.integers(0, x8.shape[0], 50), rng.integers(0, w8.shape[0], 50)
+    np.testing.assert_allclose(ref_matmul.abs_products("fp8a_fp8w", x8, w8, (ts, sc), at=(m_idx, n_idx)), mag[m_idx, n_idx], rtol=1e-12)
+    lut = np.array([orc.lib.orc_e4m3_to_f32(int(c)) for c in range(256)], dtype=np.float64)
+    brute = (np.abs(lut[x8[3]]) * np.abs(lut[w8[5]])).sum() * float(sc[5]) * float(ts[3])
+    assert abs(mag[3, 5] - brute) <= 1e-12 * brute
+
+
+@pytest.mark.parametrize("K", [128, 3840, 15360])
+def test_ref_matmul_bf16_and_w8a16_equal_the_oracle_after_its_float_cast(K):
+    """bf16 products are exact, the double sum is not: BLAS and the oracle's loop differ by summation order at the 2^-53 level -- the same float, or its neighbour when the
+    sum lies at a rounding boundary"""
+    import ref_matmul
+    rng, Wb, X, bb = _twin_operands(K)
+    for bias in (None, bb):
+        assert _fp32_ulps_apart(ref_matmul.linear_bf16w(X, Wb, bias).astype(np.float32), orc.linear_bf16w(X, Wb, bias)) <= 1
+    w8, sc = orc.quantize_fp8_per_channel(Wb)
+    for bias in (None, bb):
+        assert _fp32_ulps_apart(ref_matmul.linear_fp8w(X, w8, sc, bias).astype(np.float32), orc.linear_fp8w(X, w8, sc, bias)) <= 1
+    Wdq = orc.to_bf16_bits(orc.dequant_fp8(w8, sc))
+    assert np.array_equal(ref_matmul.dequant_fp8_bf16_bits(w8, sc), Wdq)
+    assert _fp32_ulps_apart(ref_matmul.linear_fp8w(X, w8, sc, bb, staged=True).astype(np.float32), orc.linear_bf16w(X, Wdq, bb)) <= 1
+    mag = ref_matmul.abs_products("bf16", X, Wb)
+    assert np.all(mag >= np.abs(ref_matmul.linear_bf16w(X, Wb)) * (1 - 1e-12))
+    m_idx, n_idx = rng.integers(0, X.shape[0], 50), rng.integers(0, Wb.shape[0], 50)
+    np.testing.assert_allclose(ref_matmul.abs_products("bf16", X, Wb, at=(m_idx, n_idx)), mag[m_idx, n_idx], rtol=1e-12)
+    np.testing.assert_allclose(ref_matmul.abs_products("fp8w", X, w8, (sc,), at=(m_idx, n_idx)), ref_matmul.abs_products("fp8w", X, w8, (sc,))[m_idx, n_idx], rtol=1e-12)
+
+
+def test_ref_matmul_slabs_do_not_change_a_bit():
+    import ref_matmul
+    rng, Wb, X, bb = _twin_operands(256, M=16, N=700)
+    w8, sc = orc.quantize_fp8_per_channel(Wb)
+    x8, ts = orc.quantize_act_fp8_per_token(X)
+    whole = ref_matmul.linear_fp8a_fp8w(x8, ts, w8, sc, 1.0, bb)
+    keep = ref_matmul.SLAB_BYTES
+    try:
+        ref_matmul.SLAB_BYTES = 1
+        assert len(list(ref_matmul._slabs(700, 256, 16))) == 6
+        assert np.array_equal(whole, ref_matmul.linear_fp8a_fp8w(x8, ts, w8, sc, 1.0, bb))
+    finally:
+        ref_matmul.SLAB_BYTES = keep

@@ -18,7 +18,8 @@ import pytest
 import torch
 
 import orc
-from gpu_util import assert_bf16_close, bits, dev_f32, dev_u16, dev_u8, empty_f32, empty_u16, empty_u8, host
+import ref_matmul
+from gpu_util import assert_bf16_close, bits, dev_f32, dev_u16, dev_u8, empty_f32, empty_u16, empty_u8, host, sample_rows
 from mila_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -35,15 +36,15 @@ def _operands(rng, M, K, N):
 
 
 def _expected(x8, ts, w8, sc, rows, bb):
-    exp = orc.linear_fp8a_fp8w(x8[rows], ts[rows], w8, sc, 1.0, None).astype(np.float64)
+    exp = ref_matmul.linear_fp8a_fp8w(x8[rows], ts[rows], w8, sc, 1.0, None)            # (the oracle's loop in float64 BLAS: exact for fp8 x fp8, test_oracle_kats)
     if bb is not None:
         exp = exp + orc.from_bf16_bits(bb).astype(np.float64)
     return exp
 
 
 def _sample_rows(M):
-    main = M - M % 256
-    return sorted({0, 1, min(7, M - 1), M // 2, M - 1, max(0, main - 1), min(M - 1, main), min(M - 1, main + 127), min(M - 1, main + 128)})
+    """every 256-row tile-row and every 32-row band of three of them (gpu_util.sample_rows), and the zero token"""
+    return sorted(set(sample_rows(M, np.random.default_rng(M))) | {min(7, M - 1)})
 
 
 @pytest.mark.parametrize("M,K,N,bias", [(2048, 256, 8192, False), (512, 384, 30720, True), (2048, 128, 3840, True), (2048, 1280, 3840, False), (2048, 256, 30720, True),
@@ -104,7 +105,7 @@ def test_w8a8_prefill_matches_the_oracle_at_every_row_count(M, K, N, bias):
             big = M - tail if 0 < tail <= 64 else M
         assert np.array_equal(forms[1][:big], bits(Y)[:big]), "the masked LDS-tile kernel and the LDS-DMA fp8 kernels differ"
     # 5. against the policy's reference arithmetic (W8A16: exact activations on the dequantized weights): the reference's bar for an activation-quantized prefill
-    ref16 = orc.linear_fp8w(X[rows], w8, sc).astype(np.float64)
+    ref16 = ref_matmul.linear_fp8w(X[rows], w8, sc)
     if bias:
         ref16 = ref16 + orc.from_bf16_bits(bb).astype(np.float64)
     got = orc.from_bf16_bits(bits(Y)[rows]).astype(np.float64)
@@ -135,7 +136,7 @@ def test_w8a8_geglu_form_is_bit_identical_to_linear_then_geglu(M, K, F):
     assert np.array_equal(bits(Y2), bits(Y1))
     # the float64 composition on sampled rows: gate / up rounded to bf16 as the Linear stores them, GeGLU in double
     rows = _sample_rows(M)
-    gu = orc.round_bf16(orc.linear_fp8a_fp8w(x8[rows], ts[rows], w8, sc, 1.0, None).astype(np.float32))
+    gu = orc.round_bf16(ref_matmul.linear_fp8a_fp8w(x8[rows], ts[rows], w8, sc, 1.0, None).astype(np.float32))
     exp = orc.geglu(gu)
     assert_bf16_close(bits(Y1)[rows], exp, 2, 2e-3 * float(np.abs(exp).max()), "W8A8 Linear + GeGLU vs the float64 composition")
     for form in (1, 2):
