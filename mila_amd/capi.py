@@ -135,6 +135,21 @@ def last_form():
     return [f for f in buf.value.decode().split("+") if f]
 
 
+PLAN_ENTRIES = ["gemm_bf16", "gemm_bf16_ws", "gemm_geglu_bf16", "gemm_fp8_scaled", "gemm_fp8_scaled_ws", "gemm_geglu_fp8_scaled"]
+
+
+def gemm_plan(entry, M, K, N):
+    """the prefill GEMM plan (csrc/gemm_plan.hip) of an entry point -- an index into, or a name of, PLAN_ENTRIES; N = F for the GeGLU entries -- as a list of
+    (form, row0, rows, col0, cols, S): one kernel-form launch per rectangle of the output, S > 0 on split-K steps; the column-split marker comes first, with rows == 0.
+    Needs no GPU."""
+    lib = load()
+    lib.mila_cdna4_gemm_plan_describe.restype = C.c_size_t
+    buf = C.create_string_buffer(8192)
+    need = lib.mila_cdna4_gemm_plan_describe(PLAN_ENTRIES.index(entry) if isinstance(entry, str) else int(entry), int(M), int(K), int(N), buf, C.c_size_t(len(buf)))
+    assert need <= len(buf), "plan text of %d bytes" % need
+    return [(f[0],) + tuple(int(v) for v in f[1:]) for f in (item.split(":") for item in buf.value.decode().split("+") if item)]
+
+
 def check(rc):
     if rc == MILA_OK:
         return
@@ -189,7 +204,7 @@ EXPORTED = [
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI
 INTERNAL = [
-    "tune", "tune_get", "tune_reset", "tune_list", "last_form",
+    "tune", "tune_get", "tune_reset", "tune_list", "last_form", "gemm_plan_describe",
     "decode_engine_debug",
     "selftest_decode", "selftest_wave_reduce", "selftest_mfma_fp8", "stream_copy", "stream_read",
     "attn_decode_split_count", "fused_attn_decode_partials_bf16", "matvec_attn_combine",

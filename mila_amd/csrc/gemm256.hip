@@ -18,6 +18,7 @@
 //     the steady state.  A staged slot is read one phase after the wait + barrier that retires it.
 //   * fragments: ds_read_b128, 12 / 4 / 8 / 4 per phase (the W or X fragments of the previous phase are reused).
 #include "common.h"
+#include "gemm_plan.h"
 #include <type_traits>
 
 namespace mila {
@@ -1296,37 +1297,22 @@ __global__ __launch_bounds__(512) void gemm256x128_kernel(const Gemm256Params p)
     }
 }
 
-// the LDS-DMA kernels address their operands through 32-bit buffer offsets (bytes, signed int arithmetic): both tensors must stay below 2 GiB
-static bool lds_dma_addressable(int M, int K, int w_rows) { return (int64_t)M * K * 2 < 0x7fffffffll && (int64_t)w_rows * K * 2 < 0x7fffffffll; }
-
-int g_ldsdma_loose_tiles = 30;     // the 256 x 128 ring applies from this many tiles on whatever the fill of its last round (tuning "gemm.ldsdma_loose_tiles"; 0 = the fill rule only).
-MILA_TUNE("gemm.ldsdma_loose_tiles", g_ldsdma_loose_tiles);
-                                   // Measured with tools/experiments/bf16_ragged_rules.py (profiles/r03_bf16_ragged.txt): even a 30-tile ring beats the register-staged 128-tile kernel --
-                                   // bf16-policy prefill of 100 / 300 / 511 / 1000 tokens 23.6 / 25.1 / 26.4 / 31.6 -> 16.3 / 17.9 / 21.4 / 26.7 ms
-// taken when the 256 x 256 grid does not apply and the 256 x 128 grid fills most of one round of CUs (or several)
-bool gemm256x128_applicable(int M, int K, int N)
-{
-    if (M <= 0 || N % 128 != 0 || K % 64 != 0 || !lds_dma_addressable(M, K, N)) return false;
-    const int tiles = ((M + 255) / 256) * (N / 128);      // a ragged last tile-row counts (and costs) whole: rows past M re-read row M - 1, their stores are masked
-    const int rounds = (tiles + kNumCU - 1) / kNumCU;
-    if (g_ldsdma_loose_tiles > 0 && tiles >= g_ldsdma_loose_tiles) return true;      // experiment / ragged-M rule: see g_ldsdma_loose_tiles
-    return tiles >= 160 && tiles >= 0.70 * rounds * kNumCU;      // (192 tiles -- GPT-2's 768-wide projections at B T = 8192 -- beat the 128-tile kernel's 384: 18 / 51 vs 29 / 74 us)
-}
-
-// bf16 only: N of any size (ragged last column tile, any row pitch) when the grid is many rounds deep -- GPT-2's lm_head (N = 50257, 12 576 tiles at M = 8192)
-bool gemm256x128_ragged_n_applicable(int M, int K, int N)
-{
-    if (M <= 0 || K % 64 != 0 || N % 128 == 0 || !lds_dma_addressable(M, K, N)) return false;
-    return (int64_t)((M + 255) / 256) * ((N + 127) / 128) >= 4 * kNumCU;
-}
-
-extern int g_gemm_pingpong;
-extern int g_gemm_persistent;
+// ---- host side: the leaf launchers of the LDS-DMA forms (declared in gemm_plan.h).  Which form serves a shape is gemm_plan.hip's; what stays here is how a chosen
+// form is launched: schedule (PP), persistent walk, row-wise epilogue ----
+int g_gemm_rowwise = 1;       // tuning "gemm.rowwise_epilogue": 0 = an output whose row pitch is no multiple of 128 bytes keeps the direct epilogue stores
+MILA_TUNE("gemm.rowwise_epilogue", g_gemm_rowwise);
+int g_gemm_persistent = 1;    // tuning "gemm.persistent": 0 = one workgroup per tile instead of the persistent tile walk
+MILA_TUNE("gemm.persistent", g_gemm_persistent);
+int g_gemm_pingpong = 5;      // tuning "gemm.schedule": 0 = all eight waves in lockstep; 1 = staggered (ping-pong), four phases per
+                              // K-tile in the 256 x 256 kernel; 2 = 1 + prefer the 256 x 128 ring; 3 = staggered, two phases per K-tile in the
+                              // 256 x 256 kernel; 4 = 3 + fp8 x fp8 shapes take the 256 x 256 kernel wherever it applies; 5 (default) = 4 with ONE
+                              // s_setprio 1 for waves 4-7 (the later-dispatched half loses every issue arbitration by age) instead of a raise around
+                              // every MFMA block: 0.5-1 % on each bf16 shape, nothing on fp8; same bits
+MILA_TUNE("gemm.schedule", g_gemm_pingpong);
 // (round 4, with the interior K-tiles in both forms: 576 tiles 45.9 one workgroup per tile / 47.5 walking, 768 tiles 59.8 / 60.4, 544 tiles (N = 8704) 137.0 / 150.2 us,
 // 12 576 tiles equal -- profiles/r04_persistent_walk.txt: the walk starts above three rounds)
 int g_gemm_walk_min_tiles = 3 * kNumCU + 1;      // tuning "gemm.walk_min_tiles": the 256 x 128 ring walks its tiles from this many on
 MILA_TUNE("gemm.walk_min_tiles", g_gemm_walk_min_tiles);
-extern int g_gemm_fp8_tail_form;      // gemm_fp8_tail.hip: != 0 sends every row through the tail kernels
 
 template <bool FP8, bool GEGLU, int PP>
 static int launch_gemm256x128_tt(const Gemm256Params& p, hipStream_t s)
@@ -1371,28 +1357,11 @@ static int launch_gemm256x128_t(const Gemm256Params& p, hipStream_t s)
 }
 int launch_gemm256x128(uint16_t* Y, const uint16_t* X, const uint16_t* W, const uint16_t* bias, int M, int K, int N, hipStream_t s, int act)
 {
-    note_form("gemm256x128");
     Gemm256Params p{Y, X, W, bias, M, K, N, (M + 255) / 256, (N + 127) / 128, nullptr, nullptr, 0, act};
     return launch_gemm256x128_t<false>(p, s);
 }
 
-// ---- split-K (round 3): short prompts and the remainders of long ones.  A 300-row prompt gives fc_down (N = 3840, K = 15360) 60 tiles of 240 K-tiles each: 60 CUs
-// busy for a full-length K loop, 196 idle.  The split form starts S copies of the tile list, copy ks taking 1 / S of K, and a second kernel sums the S fp32 partials in
-// a fixed order and applies the epilogue (bias, GELU, bf16) -- same bits whatever the timing.  The partials live in caller workspace (S M N floats, <= 32 MiB since
-// tiles x S <= 256 CUs): the entry that takes one is mila_cdna4_gemm_bf16_ws, the counterpart of the cuBLASLt workspace CudaLinearOp hands its plans
-// (CudaLinearOp.ixx:637-638, CudaExecutionContext.ixx:337).
-int g_gemm_splitk = 1;            // tuning "gemm.splitk": the split-K forms of gemm_bf16_ws / gemm_fp8_scaled_ws
-MILA_TUNE("gemm.splitk", g_gemm_splitk);
-int gemm_splitk_for(int M, int K, int N)      // S (>= 2), or 0: no split-K form for this shape
-{
-    if (!g_gemm_splitk || g_gemm_pingpong != 5) return 0;
-    if (M <= 0 || N % 128 != 0 || K % 64 != 0 || !lds_dma_addressable(M, K, N)) return 0;
-    const int tiles = ((M + 255) / 256) * (N / 128), nk = K / 64;
-    if (tiles > kNumCU / 2) return 0;
-    const int S = min(min(kNumCU / tiles, nk / 8), 16);      // at least 8 K-tiles per copy: the ring's fill and drain are 3
-    return S >= 2 ? S : 0;
-}
-
+// ---- split-K (the rule and its measurement: gemm_plan.hip): S copies of the ring's tile list write fp32 partials; a second kernel sums them and applies the epilogue ----
 // y = epilogue(sum over s of P[s]), 8 columns per thread; the epilogue is the 256 x 128 kernel's: bf16(acc) [+ bias, rounded again] [-> GELU of the rounded value]
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(uint16_t* __restrict__ Y, const float* __restrict__ P, const uint16_t* __restrict__ bias, int64_t MN, int N, int S,
                                                             int act, int ldy)
@@ -1456,31 +1425,26 @@ __global__ __launch_bounds__(256) void splitk_reduce_fp8_kernel(uint16_t* __rest
     st16(Y + (size_t)m * ldy + n, u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])});
 }
 
-int gemm_fp8_splitk_for(int M, int K, int N)      // S (>= 2), or 0: the fp8 (W4A8) 256 x 128 ring has no split-K form for this shape
-{
-    if (!g_gemm_splitk || g_gemm_pingpong != 5 || g_gemm_fp8_tail_form != 0) return 0;
-    if (M <= 0 || N % 128 != 0 || K % 128 != 0 || !lds_dma_addressable(M, K, N)) return 0;
-    const int tiles = ((M + 255) / 256) * (N / 128), nk = K / 128;
-    if (tiles > kNumCU / 2) return 0;
-    const int S = min(min(kNumCU / tiles, nk / 8), 16);
-    return S >= 2 ? S : 0;
-}
-
-static int launch_gemm256x128_fp8_splitk(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias, int M, int K, int N,
-                                         hipStream_t s, float* partials, int S, int ldy = 0)
+// the ring over S copies of the tile list, writing [S][M][N] fp32 partials
+template <bool FP8>
+static int launch_ring_splitk(uint16_t* Y, const void* X, const void* W, int M, int K, int N, float* partials, int S, hipStream_t s)
 {
     static bool attr_set = false;
     if (!attr_set)
     {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256x128_kernel<true, false, 2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               3 * kStage3Bytes), "hipFuncSetAttribute(gemm256x128 fp8 split-K)");
+        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256x128_kernel<FP8, false, 2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               3 * kStage3Bytes), "hipFuncSetAttribute(gemm256x128 split-K)");
         if (rc) return rc;
         attr_set = true;
     }
-    note_form("fp8_gemm256x128_splitk");
-    Gemm256Params p{nullptr, reinterpret_cast<const uint16_t*>(X8), reinterpret_cast<const uint16_t*>(W8), nullptr, M, K, N, (M + 255) / 256, N / 128, nullptr, nullptr, 0, 0, partials, S};
-    hipLaunchKernelGGL((gemm256x128_kernel<true, false, 2, false, true>), dim3(p.tiles_m * p.tiles_n * S), dim3(512), 3 * kStage3Bytes, s, p);
-    int rc = check_hip(hipGetLastError(), "gemm256x128 (fp8 split-K)");
+    Gemm256Params p{Y, static_cast<const uint16_t*>(X), static_cast<const uint16_t*>(W), nullptr, M, K, N, (M + 255) / 256, N / 128, nullptr, nullptr, 0, 0, partials, S};
+    hipLaunchKernelGGL((gemm256x128_kernel<FP8, false, 2, false, true>), dim3(p.tiles_m * p.tiles_n * S), dim3(512), 3 * kStage3Bytes, s, p);
+    return check_hip(hipGetLastError(), FP8 ? "gemm256x128 (fp8 split-K)" : "gemm256x128 (split-K)");
+}
+int launch_gemm256x128_fp8_splitk(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias, int M, int K, int N,
+                                  hipStream_t s, float* partials, int S, int ldy)
+{
+    int rc = launch_ring_splitk<true>(nullptr, X8, W8, M, K, N, partials, S, s);
     if (rc) return rc;
     const int64_t MN = (int64_t)M * N;
     hipLaunchKernelGGL(splitk_reduce_fp8_kernel, dim3((unsigned)((MN / 8 + 255) / 256)), dim3(256), 0, s, Y, partials, bias, x_scales, w_scale.p, w_scale.per_channel, MN, N, S, ldy ? ldy : N);
@@ -1488,63 +1452,17 @@ static int launch_gemm256x128_fp8_splitk(uint16_t* Y, const uint8_t* X8, const u
 }
 
 // the second kernel on its own (the few-row form of gemm_fewrow_bf16.hip writes the same [S][M][N] partials)
-int launch_splitk_reduce(uint16_t* Y, const float* partials, const uint16_t* bias, int M, int N, int S, int act, hipStream_t s)
+int launch_splitk_reduce(uint16_t* Y, const float* partials, const uint16_t* bias, int M, int N, int S, int act, hipStream_t s, int ldy)
 {
-    const int64_t MN = (int64_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((MN / 8 + 255) / 256)), dim3(256), 0, s, Y, partials, bias, MN, N, S, act, N);
-    return check_hip(hipGetLastError(), "splitk_reduce");
-}
-
-int launch_gemm256x128_splitk(uint16_t* Y, const uint16_t* X, const uint16_t* W, const uint16_t* bias, int M, int K, int N, hipStream_t s, int act, float* partials, int S, int ldy)
-{
-    static bool attr_set = false;
-    if (!attr_set)
-    {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256x128_kernel<false, false, 2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               3 * kStage3Bytes), "hipFuncSetAttribute(gemm256x128 split-K)");
-        if (rc) return rc;
-        attr_set = true;
-    }
-    note_form("gemm256x128_splitk");
-    Gemm256Params p{Y, X, W, nullptr, M, K, N, (M + 255) / 256, N / 128, nullptr, nullptr, 0, 0, partials, S};
-    hipLaunchKernelGGL((gemm256x128_kernel<false, false, 2, false, true>), dim3(p.tiles_m * p.tiles_n * S), dim3(512), 3 * kStage3Bytes, s, p);
-    int rc = check_hip(hipGetLastError(), "gemm256x128 (split-K)");
-    if (rc) return rc;
     const int64_t MN = (int64_t)M * N;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((MN / 8 + 255) / 256)), dim3(256), 0, s, Y, partials, bias, MN, N, S, act, ldy ? ldy : N);
     return check_hip(hipGetLastError(), "splitk_reduce");
 }
-
-// one 512-thread workgroup per CU: worth it only when the tile count fills whole rounds of 256 CUs
-int g_gemm256_min_fill = 80;      // tuning "gemm.tile256_min_fill": the 256 x 256 grid applies when its tiles fill at least this many percent of their rounds of CUs
-MILA_TUNE("gemm.tile256_min_fill", g_gemm256_min_fill);
-bool gemm256_applicable(int M, int K, int N)
+int launch_gemm256x128_splitk(uint16_t* Y, const uint16_t* X, const uint16_t* W, const uint16_t* bias, int M, int K, int N, hipStream_t s, int act, float* partials, int S, int ldy)
 {
-    if (M <= 0 || N % 256 != 0 || K % 64 != 0 || !lds_dma_addressable(M, K, N)) return false;
-    const int tiles = ((M + 255) / 256) * (N / 256);
-    const int rounds = (tiles + kNumCU - 1) / kNumCU;
-    return tiles >= 200 && tiles * 100 >= g_gemm256_min_fill * rounds * kNumCU;      // (80 %: nine tile-rows of fc_gate_up -- 1080 tiles, 4.2 rounds walked as 5 -- stay on the fused kernel)
+    const int rc = launch_ring_splitk<false>(Y, X, W, M, K, N, partials, S, s);
+    return rc ? rc : launch_splitk_reduce(Y, partials, bias, M, N, S, act, s, ldy);
 }
-
-// bf16 only: N of any size (ragged last tile-column, any row pitch) on the PERSISTENT 256 x 256 schedule when the grid is many rounds deep -- GPT-2's lm_head
-// (N = 50257: 6 304 tiles at M = 8192, K = 768).  A tile there is 12 K-tiles, as long as what a one-tile workgroup pays around them (launch, first-load latency, the
-// store drain): the persistent walk overlaps all three with the next tile's K loop
-bool gemm256_ragged_n_applicable(int M, int K, int N)
-{
-    if (M <= 0 || K % 128 != 0 || N % 256 == 0 || !lds_dma_addressable(M, K, N)) return false;
-    return (int64_t)((M + 255) / 256) * ((N + 255) / 256) >= 4 * kNumCU;
-}
-
-int g_gemm_rowwise = 1;       // tuning "gemm.rowwise_epilogue": 0 = an output whose row pitch is no multiple of 128 bytes keeps the direct epilogue stores
-MILA_TUNE("gemm.rowwise_epilogue", g_gemm_rowwise);
-int g_gemm_persistent = 1;    // tuning "gemm.persistent": 0 = one workgroup per tile instead of the persistent tile walk
-MILA_TUNE("gemm.persistent", g_gemm_persistent);
-int g_gemm_pingpong = 5;      // tuning "gemm.schedule": 0 = all eight waves in lockstep; 1 = staggered (ping-pong), four phases per
-                              // K-tile in the 256 x 256 kernel; 2 = 1 + prefer the 256 x 128 ring; 3 = staggered, two phases per K-tile in the
-                              // 256 x 256 kernel; 4 = 3 + fp8 x fp8 shapes take the 256 x 256 kernel wherever it applies; 5 (default) = 4 with ONE
-                              // s_setprio 1 for waves 4-7 (the later-dispatched half loses every issue arbitration by age) instead of a raise around
-                              // every MFMA block: 0.5-1 % on each bf16 shape, nothing on fp8; same bits
-MILA_TUNE("gemm.schedule", g_gemm_pingpong);
 
 template <int MODE, int PP>
 static int launch_gemm256_tt(const Gemm256Params& p, hipStream_t s)
@@ -1582,207 +1500,29 @@ int launch_gemm256(uint16_t* Y, const uint16_t* X, const uint16_t* W, const uint
 {
     // a row pitch that is no multiple of 128 bytes: one workgroup per tile and the row-wise epilogue through LDS (two-phase schedules only)
     const int rowwise = ((N & 63) != 0 && g_gemm_pingpong >= 3 && g_gemm_rowwise) ? 1 : 0;
-    note_form("gemm256");
     Gemm256Params p{Y, X, W, bias, M, K, N, (M + 255) / 256, (N + 255) / 256, nullptr, nullptr, rowwise, act};
     p.ldy = ldy;
     return launch_gemm256_t<G_PLAIN>(p, s);
 }
-
-// ---- column split (round 4): an output whose 256 x 256 tile list ends in a nearly empty round -- Gemma's global qkv_proj, N = 8704 at T = 2048: 272 tiles on 256 CUs (the
-// 256 x 128 ring ran it as 544 tiles in three rounds for 2.1 rounds of work, 165 us = 0.83 PFLOP/s) -- is cut at the last whole round: columns [0, n_main) as whole rounds
-// of 256 x 256 tiles, the few remaining column tiles through the split-K form of the ring (their S copies cover the idle CUs), both writing their column range of Y with
-// the pitch of the whole row.  Needs the caller's workspace (S M (N - n_main) floats).  n_main = 0: no split for this shape.
-int g_gemm_colsplit = 1;
-MILA_TUNE("gemm.colsplit", g_gemm_colsplit);
-int gemm_splitk_for(int M, int K, int N);
-int gemm_colsplit_main(int M, int K, int N, int* S_rest)
-{
-    *S_rest = 0;
-    if (!g_gemm_colsplit || g_gemm_pingpong != 5 || M < 256 || N % 256 != 0 || K % 64 != 0 || !lds_dma_addressable(M, K, N)) return 0;
-    const int tm = (M + 255) / 256, tn = N / 256, tiles = tm * tn;
-    if (tiles <= kNumCU) return 0;
-    const int rounds = (tiles + kNumCU - 1) / kNumCU;
-    if (tiles >= 0.80 * rounds * kNumCU) return 0;                  // the whole list fills its rounds well enough (gemm256_applicable's rule)
-    const int tn_main = ((tiles / kNumCU) * kNumCU) / tm;           // column tiles of the whole rounds
-    if (tn_main <= 0 || tn_main >= tn) return 0;
-    const int n_main = tn_main * 256, rest = N - n_main;
-    const int S = gemm_splitk_for(M, K, rest);
-    if (S < 2) return 0;
-    *S_rest = S;
-    return n_main;
-}
-
 // Y[M, F] = GeGLU(X W^T), W = [gate rows 0 .. F-1 | up rows F .. 2F-1]
-bool gemm256_geglu_applicable(int M, int K, int F)
-{
-    if (M <= 0 || F % 128 != 0 || K % 64 != 0 || !lds_dma_addressable(M, K, 2 * F)) return false;
-    const int tiles = ((M + 255) / 256) * (F / 128);
-    const int rounds = (tiles + kNumCU - 1) / kNumCU;
-    return tiles >= 200 && tiles >= 0.80 * rounds * kNumCU;
-}
 int launch_gemm256_geglu(uint16_t* Y, const uint16_t* X, const uint16_t* W, int M, int K, int F, hipStream_t s)
 {
-    note_form("gemm256_geglu");
     Gemm256Params p{Y, X, W, nullptr, M, K, F, (M + 255) / 256, F / 128, nullptr, nullptr};
     return launch_gemm256_t<G_GEGLU>(p, s);
 }
 
-// gemm_fp8_tail.hip: the same arithmetic for any row count (masked 128-row tiles; skinny weight streaming for <= 64 rows)
-int launch_gemm_fp8_tail(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias,
-                         int M, int K, int N, hipStream_t s);
-int launch_gemm_fp8_geglu_tail(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, int M, int K, int F,
-                               hipStream_t s);
-
-// Row counts of any kind (the fp4 policy's prefill is W4A8 for EVERY M > 1, CudaLinearOp.ixx:646-715):
-//   (short prompts, measured with tools/experiments/short_prompt_rules.py, profiles/r03_short_prompts.txt: below 512 rows the LDS-DMA kernels still win wherever their grid
-//    has >= 120 tiles -- qkv, fc_gate_up -- and lose on the N = 3840 shapes, whose 30-60 tiles leave the chip empty; fp4-policy prefill of 300 / 400 / 511 tokens
-//    14.8 / 17.4 / 18.3 -> 11.8 / 13.0 / 13.6 ms, monotonic in T again)
-//   M >= 512 and N % 128 == 0, K % 128 == 0: the LDS-DMA kernels over ceil(M / 256) tile-rows -- a ragged last tile-row stages row M - 1 for the rows past M
-//     and masks its stores (a 208-row tail costs one tile-row, 1/8 of a T = 2048 chunk; on the masked 128-row tiles it cost 40 % of the chunk) -- except that a
-//     tail of <= 64 rows goes to the skinny weight-streaming kernel instead (a 1-row tail: +11 % of the chunk instead of +12.5 %, and no MFMA work on padding);
-//   everything else: the tail kernels of gemm_fp8_tail.hip alone.
-// Rows are independent and the LDS-DMA kernels and the masked tiles run the same instruction chain per output element.
-constexpr int kSkinnyTailRows = 64;
-// Few rows (tools/experiments/few_row_rules_fp4.sh, profiles/r03_splitk.txt): one 16-row group stays with the skinny kernel -- a weight stream of one byte per weight
-// (fp4-policy prefill of 8 / 16 tokens 4.83 / 4.92 ms, against 4.95 / 5.02 on the tile forms); from 17 rows on the tile grids (>= 120 tiles) and the split-K form are faster
-// (17 / 24 / 32 tokens 5.39 / 5.50 / 5.69 ms skinny, 5.09 / 5.10 / 5.17 here; 64 tokens 7.15 -> 5.66).  A W4A8 form of the few-row kernel (gemm_fewrow_bf16.hip with
-// e4m3 operands; parity-green) was slower than both on every length -- the skinny kernel's fused GeGLU saves fc_gate_up a reduce and an elementwise pass -- and is not kept.
-int g_fp8_splitk_min_rows = 17;      // tuning "gemm_fp8.splitk_min_rows": fewer rows stay with the skinny kernel
-MILA_TUNE("gemm_fp8.splitk_min_rows", g_fp8_splitk_min_rows);
-int g_fp8_big_rule = 3;      // tuning "gemm_fp8.big_rule": 0 = LDS-DMA kernels from 512 rows on (round 3's first rule), 1 = from 128 rows on,
-                             // 2 = from 512 rows on or wherever ceil(M / 256) x (W rows / 128) >= 120 tiles, 3 (default) = 2 without the skinny split of a short prompt's remainder
-MILA_TUNE("gemm_fp8.big_rule", g_fp8_big_rule);
-static int fp8_big_rows(int M, int K, int N_mult, int w_rows)      // rows the LDS-DMA kernels take (0 = none); N_mult: the column granularity the form needs (128, or 64 for 256 x 128 GeGLU)
+// the fp8 x fp8 LDS-DMA forms (W4A8: one weight scale; W8A8: per channel); GeGLU: N = F, Y[M, F] = GeGLU of the Linear over W8 = [gate rows | up rows] (2F x K e4m3)
+int launch_gemm_fp8_ldsdma(GemmForm form, uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias, int M, int K, int N,
+                           hipStream_t s, int ldy)
 {
-    if (!lds_dma_addressable(M, K, w_rows)) return 0;
-    if (g_gemm_fp8_tail_form != 0 || K % 128 != 0 || N_mult == 0) return 0;
-    // below two full tile-rows the LDS-DMA kernels pay only where their grid still covers the chip (tuning variable gemm_fp8.big_rule)
-    const int tiles = ((M + 255) / 256) * (w_rows / 128);
-    const bool big = g_fp8_big_rule == 1 ? M >= 128 : (g_fp8_big_rule >= 2 ? (M >= 512 || (M >= g_fp8_splitk_min_rows && tiles >= 120)) : M >= 512);
-    if (!big) return 0;
-    if (g_fp8_big_rule == 3 && M < 512) return M;        // a short prompt's <= 64-row remainder stays in the ragged tile-row: a skinny pass re-streams every weight, which only a long main part amortises
-    const int tail = M % 256;
-    return (tail > 0 && tail <= kSkinnyTailRows) ? M - tail : M;
+    const bool geglu = form == GF_FP8_GEMM256_GEGLU || form == GF_FP8_GEMM256X128_GEGLU, ring = form == GF_FP8_GEMM256X128 || form == GF_FP8_GEMM256X128_GEGLU;
+    const int tile_n = (ring ? 128 : 256) / (geglu ? 2 : 1);      // output columns per tile: a GeGLU tile holds gate and up rows
+    Gemm256Params p{Y, reinterpret_cast<const uint16_t*>(X8), reinterpret_cast<const uint16_t*>(W8), bias, M, K, N, (M + 255) / 256, N / tile_n, x_scales, w_scale.p};
+    p.w_pc = w_scale.per_channel;
+    p.ldy = ldy;
+    if (form == GF_FP8_GEMM256X128_GEGLU) return launch_gemm256x128_t<true, true>(p, s);
+    if (form == GF_FP8_GEMM256_GEGLU) return launch_gemm256_t<G_FP8_GEGLU>(p, s);
+    return form == GF_FP8_GEMM256 ? launch_gemm256_t<G_FP8>(p, s) : launch_gemm256x128_t<true>(p, s);
 }
-// which LDS-DMA kernel: 2 = 256 x 256 (enough tiles for the chip, N % 256 == 0), 1 = 256 x 128
-static int fp8_pick(int rows, int N)
-{
-    const int tm = (rows + 255) / 256;
-    if (N % 256 == 0 && tm * (N / 256) >= 200) return 2;
-    return 1;
-}
-
-// Y[M, F] = GeGLU of the W4A8 Linear over W8 = [gate rows | up rows] (2F x K e4m3)
-int launch_gemm_fp8_geglu(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, int M, int K, int F,
-                          hipStream_t s)
-{
-    const bool form256 = F % 128 == 0 && ((M + 255) / 256) * (F / 128) >= 200;
-    const int rows = fp8_big_rows(M, K, form256 ? 128 : (F % 64 == 0 ? 64 : 0), 2 * F);
-    if (rows)
-    {
-        int rc;
-        const int tm = (rows + 255) / 256;
-        if (!form256)
-        {
-            Gemm256Params q{Y, reinterpret_cast<const uint16_t*>(X8), reinterpret_cast<const uint16_t*>(W8), nullptr, rows, K, F, tm, F / 64, x_scales, w_scale.p};
-            q.w_pc = w_scale.per_channel;
-            note_form("fp8_gemm256x128_geglu");
-            rc = launch_gemm256x128_t<true, true>(q, s);
-        }
-        else
-        {
-            Gemm256Params p{Y, reinterpret_cast<const uint16_t*>(X8), reinterpret_cast<const uint16_t*>(W8), nullptr, rows, K, F, tm, F / 128, x_scales, w_scale.p};
-            p.w_pc = w_scale.per_channel;
-            note_form("fp8_gemm256_geglu");
-            rc = launch_gemm256_t<G_FP8_GEGLU>(p, s);
-        }
-        if (rc || rows == M) return rc;
-    }
-    return launch_gemm_fp8_geglu_tail(Y + (size_t)rows * F, X8 + (size_t)rows * K, W8, x_scales + rows, w_scale, M - rows, K, F, s);
-}
-int launch_gemm_fp8(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias,
-                    int M, int K, int N, hipStream_t s)
-{
-    const int rows = fp8_big_rows(M, K, N % 128 == 0 ? 128 : 0, N);
-    if (rows)
-    {
-        const int which = fp8_pick(rows, N), tm = (rows + 255) / 256;
-        Gemm256Params p{Y, reinterpret_cast<const uint16_t*>(X8), reinterpret_cast<const uint16_t*>(W8), bias, rows, K, N, tm, which == 2 ? N / 256 : N / 128, x_scales, w_scale.p};
-        p.w_pc = w_scale.per_channel;
-        note_form(which == 2 ? "fp8_gemm256" : "fp8_gemm256x128");
-        const int rc = which == 2 ? launch_gemm256_t<G_FP8>(p, s) : launch_gemm256x128_t<true>(p, s);
-        if (rc || rows == M) return rc;
-    }
-    return launch_gemm_fp8_tail(Y + (size_t)rows * N, X8 + (size_t)rows * K, W8, x_scales + rows, w_scale, bias, M - rows, K, N, s);
-}
-
-
-// ---- the same with a caller workspace (mila_cdna4_gemm_fp8_scaled_ws; mirrors gemm.hip's bf16_ws_plan): a short prompt whose tile list covers at most half the CUs
-// splits K whole; a long prompt's remainder whose ragged tile-row would open another round of the grid (T = 2303 on the N = 3840 shapes) splits K alone ----
-struct Fp8WsPlan { int main_rows, S; int n_main = 0; };      // n_main > 0: the column split (see gemm_colsplit_main): columns [0, n_main) on 256 x 256 fp8 tiles, the rest split-K
-static Fp8WsPlan fp8_ws_plan(int M, int K, int N)
-{
-    if (M < g_fp8_splitk_min_rows) return {M, 0};
-    int S = gemm_fp8_splitk_for(M, K, N);
-    if (S) return {0, S};
-    // the 256 x 256 fp8 tile list of N = 8704 at T = 2048 is 272 tiles: one round and sixteen stragglers, walked as two (fp8_pick: 2).  Whole rounds + a split-K rest instead.
-    if (g_gemm_colsplit && g_gemm_pingpong == 5 && g_gemm_fp8_tail_form == 0 && M >= 512 && N % 256 == 0 && K % 128 == 0 && lds_dma_addressable(M, K, N))
-    {
-        const int tm = (M + 255) / 256, tn = N / 256, tiles = tm * tn;
-        const int rounds = (tiles + kNumCU - 1) / kNumCU;
-        if (tiles > kNumCU && tiles < 0.80 * rounds * kNumCU)
-        {
-            const int tn_main = ((tiles / kNumCU) * kNumCU) / tm;
-            if (tn_main > 0 && tn_main < tn)
-            {
-                const int n_main = tn_main * 256;
-                const int Sr = gemm_fp8_splitk_for(M, K, N - n_main);
-                if (Sr >= 2 && fp8_big_rows(M, K, 128, n_main) == M && fp8_pick(M, n_main) == 2) { Fp8WsPlan cs{0, Sr}; cs.n_main = n_main; return cs; }
-            }
-        }
-    }
-    const int tail = M % 256, main_rows = M - tail;
-    if (M < 512 || tail < g_fp8_splitk_min_rows) return {M, 0};
-    if (fp8_big_rows(main_rows, K, N % 128 == 0 ? 128 : 0, N) != main_rows) return {M, 0};
-    const int per_row = fp8_pick(main_rows, N) == 2 ? N / 256 : N / 128, tm = main_rows / 256;
-    const bool new_round = (tm * per_row + kNumCU - 1) / kNumCU < ((tm + 1) * per_row + kNumCU - 1) / kNumCU;
-    if (!new_round) return {M, 0};
-    S = gemm_fp8_splitk_for(tail, K, N);
-    return S ? Fp8WsPlan{main_rows, S} : Fp8WsPlan{M, 0};
-}
-size_t gemm_fp8_ws_bytes(int M, int K, int N)
-{
-    const Fp8WsPlan pl = fp8_ws_plan(M, K, N);
-    if (pl.n_main) return (size_t)pl.S * M * (N - pl.n_main) * sizeof(float);
-    return pl.S ? (size_t)pl.S * (M - pl.main_rows) * N * sizeof(float) : 0;
-}
-int launch_gemm_fp8_ws(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias, int M, int K, int N, hipStream_t s,
-                       void* ws)
-{
-    const Fp8WsPlan pl = fp8_ws_plan(M, K, N);
-    if (!pl.S) return launch_gemm_fp8(Y, X8, W8, x_scales, w_scale, bias, M, K, N, s);
-    if (pl.n_main)
-    {
-        note_form("fp8_gemm256_colsplit");
-        note_form("fp8_gemm256");
-        Gemm256Params p{Y, reinterpret_cast<const uint16_t*>(X8), reinterpret_cast<const uint16_t*>(W8), bias, M, K, pl.n_main, (M + 255) / 256, pl.n_main / 256, x_scales, w_scale.p};
-        p.w_pc = w_scale.per_channel;
-        p.ldy = N;
-        int rc = launch_gemm256_t<G_FP8>(p, s);
-        if (rc) return rc;
-        const Fp8WScale wr{w_scale.per_channel ? w_scale.p + pl.n_main : w_scale.p, w_scale.per_channel};
-        return launch_gemm256x128_fp8_splitk(Y + pl.n_main, X8, W8 + (size_t)pl.n_main * K, x_scales, wr, bias ? bias + pl.n_main : nullptr, M, K, N - pl.n_main, s,
-                                             static_cast<float*>(ws), pl.S, N);
-    }
-    if (pl.main_rows > 0)
-    {
-        int rc = launch_gemm_fp8(Y, X8, W8, x_scales, w_scale, bias, pl.main_rows, K, N, s);
-        if (rc) return rc;
-    }
-    return launch_gemm256x128_fp8_splitk(Y + (size_t)pl.main_rows * N, X8 + (size_t)pl.main_rows * K, W8, x_scales + pl.main_rows, w_scale, bias, M - pl.main_rows, K, N, s,
-                                         static_cast<float*>(ws), pl.S);
-}
-// the fused GeGLU form steps aside where the plain GEMM over [2F, K] would split K (same reason as gemm.hip's geglu_rows_applicable)
-bool gemm_fp8_geglu_steps_aside(int M, int K, int F) { return fp8_ws_plan(M, K, 2 * F).S != 0; }
 
 }  // namespace mila

@@ -1,4 +1,4 @@
-// bf16 x bf16 GEMM for up to 32 rows with a caller workspace: the few-row form behind mila_cdna4_gemm_bf16_ws (gemm.hip: bf16_ws_plan).
+// bf16 x bf16 GEMM for up to 32 rows with a caller workspace: the few-row form behind mila_cdna4_gemm_bf16_ws (gemm_plan.hip: plan_bf16).
 // A 2 ... 32-token prompt (or chunk tail) is a weight stream: 448 MB per Gemma layer against a few MB of activations.  The forms that served it stream slower than the
 // decode matvec does -- the 256 x 128 ring keeps 2 x 16 KB of weights in flight per CU and stages 240 padding rows per real one (fc_down at 64 rows: 3 TB/s), the skinny
 // kernel (gemm_skinny_bf16.hip) re-reads its X image for every 16 W rows.  Here:
@@ -12,7 +12,7 @@
 //     splitk_reduce_kernel (gemm256.hip) sums the slices in a fixed order and applies the epilogue (bias, GELU, bf16) -- the same second kernel as the tile form.
 #include <algorithm>
 
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace mila {
 

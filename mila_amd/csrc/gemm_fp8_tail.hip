@@ -18,7 +18,7 @@
 // operand at slots g and 4 + g, the conflict-free pattern of gemm256.hip -- XOR-swizzled by (row >> 1) & 7.
 #include <algorithm>
 
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace mila {
 
@@ -463,7 +463,6 @@ template <bool GEGLU>
 static int launch_skinny(const Fp8SkinnyParams& p, hipStream_t s)
 {
     const int groups = (p.M + 15) / 16;
-    note_form(GEGLU ? "fp8_skinny_geglu" : "fp8_skinny");
     if (groups <= 1) launch_skinny_mg<1, GEGLU>(p, s);
     else if (groups == 2) launch_skinny_mg<2, GEGLU>(p, s);
     else launch_skinny_mg<4, GEGLU>(p, s);
@@ -476,7 +475,6 @@ static int launch_tail_t(Fp8TailParams p, hipStream_t s)
     constexpr int BO = (GEGLU ? WN * PT * 8 : WN * PT * 16);
     p.tiles_m = (p.M + 127) / 128;
     p.tiles_n = (p.N + BO - 1) / BO;
-    note_form(GEGLU ? "fp8_tail_geglu" : "fp8_tail");
     hipLaunchKernelGGL((gemm_fp8_tail_kernel<WN, PT, QT, GEGLU>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p);
     MILA_LAUNCH_CHECK("gemm_fp8_tail");
 }
@@ -493,45 +491,14 @@ static int launch_tail(const Fp8TailParams& p, hipStream_t s)
     return launch_tail_t<1, 2, 2, GEGLU>(p, s);
 }
 
-int g_gemm_fp8_tail_form = 0;       // tuning "gemm_fp8.tail_form": 0 = LDS-DMA kernels on the leading rows, the tail kernels by row count on the rest; 1 = EVERY row on the masked 128-row
-                                    // LDS tiles (bit-identical to the LDS-DMA kernels: the test of that statement); 2 = every row as skinny pieces
-MILA_TUNE("gemm_fp8.tail_form", g_gemm_fp8_tail_form);
-constexpr int kSkinnyRows = 64;     // rows one skinny launch takes
-constexpr int kSkinnyMaxTail = 64;  // tails up to here run as ONE skinny launch; longer ones on the 128-row LDS tiles (measured: four skinny pieces of a 208-row tail cost more than two LDS tile rows)
-
-static bool use_skinny(int M) { return g_gemm_fp8_tail_form == 2 || (g_gemm_fp8_tail_form == 0 && M <= kSkinnyMaxTail); }
-
-int launch_gemm_fp8_tail(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias,
-                         int M, int K, int N, hipStream_t s)
+// the leaf (gemm_plan.h; which rows take which form is gemm_plan.hip's: plan_fp8_tail): ONE skinny launch over up to kFp8SkinnyRows rows, or the masked 128-row tiles
+int launch_gemm_fp8_tail(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias, int M, int K, int N, bool skinny,
+                         bool geglu, hipStream_t s)
 {
-    if (use_skinny(M))
-    {
-        for (int r0 = 0; r0 < M; r0 += kSkinnyRows)
-        {
-            Fp8SkinnyParams q{Y + (size_t)r0 * N, X8 + (size_t)r0 * K, W8, bias, x_scales + r0, w_scale.p, std::min(kSkinnyRows, M - r0), K, N, w_scale.per_channel};
-            const int rc = launch_skinny<false>(q, s);
-            if (rc) return rc;
-        }
-        return MILA_OK;
-    }
-    Fp8TailParams p{Y, X8, W8, bias, x_scales, w_scale.p, M, K, N, 0, 0, w_scale.per_channel};
-    return launch_tail<false>(p, s);
-}
-int launch_gemm_fp8_geglu_tail(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, int M, int K, int F,
-                               hipStream_t s)
-{
-    if (use_skinny(M))
-    {
-        for (int r0 = 0; r0 < M; r0 += kSkinnyRows)
-        {
-            Fp8SkinnyParams q{Y + (size_t)r0 * F, X8 + (size_t)r0 * K, W8, nullptr, x_scales + r0, w_scale.p, std::min(kSkinnyRows, M - r0), K, F, w_scale.per_channel};
-            const int rc = launch_skinny<true>(q, s);
-            if (rc) return rc;
-        }
-        return MILA_OK;
-    }
-    Fp8TailParams p{Y, X8, W8, nullptr, x_scales, w_scale.p, M, K, F, 0, 0, w_scale.per_channel};
-    return launch_tail<true>(p, s);
+    const Fp8SkinnyParams q{Y, X8, W8, bias, x_scales, w_scale.p, M, K, N, w_scale.per_channel};
+    const Fp8TailParams p{Y, X8, W8, bias, x_scales, w_scale.p, M, K, N, 0, 0, w_scale.per_channel};
+    if (!geglu) return skinny ? launch_skinny<false>(q, s) : launch_tail<false>(p, s);
+    return skinny ? launch_skinny<true>(q, s) : launch_tail<true>(p, s);
 }
 
 }  // namespace mila

@@ -10,7 +10,7 @@ extern "C" {
 #endif
 /* NAMED tuning variables (round 4): every launch heuristic a test or a tool may override is an int with a dotted name, registered next to the rule it steers
  * (MILA_TUNE in csrc/common.h).  tune(name, value) sets one, tune_get reads it, tune_reset restores every default, tune_list prints "name=value (default d)" lines.
- *   gemm.*        bf16 / staged GEMM dispatch (csrc/gemm.hip, gemm256.hip)      gemm_fp8.*   fp8 x fp8 (W4A8 / W8A8) dispatch (gemm256.hip, gemm_fp8_tail.hip)
+ *   gemm.*        bf16 / staged GEMM dispatch (csrc/gemm_plan.hip; launch: gemm256.hip)      gemm_fp8.*   fp8 x fp8 (W4A8 / W8A8) dispatch (gemm_plan.hip; launch: gemm_fp8_tail.hip)
  *   attn.*        decode attention (csrc/attention.hip)                          flash.*      flash prefill (attention_prefill.hip)
  * last_form: the kernel forms the calling thread's Linear / attention entry points ran since the previous call ("gemm256+skinny_bf16", "fp8_ldsdma_256x128+fp8_skinny", ...),
  * so a test can assert WHICH form a row count was routed to. */
@@ -19,26 +19,30 @@ MILA_API int mila_cdna4_tune_get(const char* name, int* value);
 MILA_API int mila_cdna4_tune_reset(void);
 MILA_API size_t mila_cdna4_tune_list(char* buf, size_t cap);
 MILA_API size_t mila_cdna4_last_form(char* buf, size_t cap);
+/* the prefill GEMM plan (csrc/gemm_plan.hip) of an entry point as text, without running device code: entry 0 = gemm_bf16, 1 = gemm_bf16_ws (and the staged forms),
+ * 2 = gemm_geglu_bf16 (N = F), 3 = gemm_fp8_scaled, 4 = gemm_fp8_scaled_ws (and the W8A8 / scratch forms), 5 = gemm_geglu_fp8_scaled (N = F).  Writes
+ * "form:row0:rows:col0:cols:S" items joined by '+' (one kernel-form launch per rectangle of the output; S > 0: split-K copies), the column-split marker, all zeros, first. */
+MILA_API size_t mila_cdna4_gemm_plan_describe(int entry, int M, int K, int N, char* buf, size_t cap);
 /* The names (tune_list prints them with their values and defaults; each is documented where it is registered):
  *   matvec.rows_per_wave, matvec.chunks_in_flight, matvec.max_workgroups                 0 = the default rule                                         (csrc/matvec.hip)
- *   gemm.force128          1 = always the 128 x 128 register-staged GEMM (A/B against the LDS-DMA kernels)                                           (csrc/gemm.hip)
+ *   gemm.force128          1 = always the 128 x 128 register-staged GEMM (A/B against the LDS-DMA kernels)                                           (csrc/gemm_plan.hip)
  *   gemm.bf16_skinny       the bf16 skinny weight-streaming kernel for <= 64-row prompts and remainders (default 1)
  *   gemm.fewrow            the few-row (<= 32 rows) form of gemm_bf16_ws (default 1)
  *   gemm.skinny_ahead_rows up to this many rows the skinny kernels go ahead of an applicable tile grid (default 1)
  *   gemm.splitk, gemm.splitk_min_rows      the split-K forms of gemm_bf16_ws / gemm_fp8_scaled_ws; row counts below the minimum stay off them (1, 2)
- *   gemm.ldsdma_loose_tiles  the 256 x 128 ring from this many tiles on whatever its last round's fill (30; 0 = the fill rule only)                   (csrc/gemm256.hip)
- *   gemm.rowwise_epilogue  0 = an output whose row pitch is no multiple of 128 bytes keeps the direct epilogue stores (default 1: row-wise through LDS)
+ *   gemm.ldsdma_loose_tiles  the 256 x 128 ring from this many tiles on whatever its last round's fill (30; 0 = the fill rule only)
+ *   gemm.tile256_min_fill  the 256 x 256 grid applies when its tiles fill at least this many percent of their rounds of CUs (default 80; profiles/r04_tile256_fill_rule.txt:
+ *                          at 75 % -- GPT-2's fc_1, 384 tiles -- the 256 x 128 ring is 56 us against 74); the column splits judge the same grid by the same value.  Same bits.
+ *   gemm.colsplit          the column split of a tile list whose last round is nearly empty (default 1)
+ *   gemm.rowwise_epilogue  0 = an output whose row pitch is no multiple of 128 bytes keeps the direct epilogue stores (default 1: row-wise through LDS)     (csrc/gemm256.hip)
  *   gemm.schedule          0 = all eight waves in lockstep; 1 = staggered (ping-pong), four phases per K-tile; 2 = 1, preferring the 256 x 128 ring; 3 = staggered, two
  *                          phases per K-tile; 4 = 3 + the fp8 shapes on the 256 x 256 kernel wherever it applies; 5 (default) = 4 with a static priority for waves 4-7.  Same bits.
  *   gemm.persistent        0 = one workgroup per tile instead of the persistent tile walk (default 1).  Same bits.
- *   gemm.tile256_min_fill  the 256 x 256 grid applies when its tiles fill at least this many percent of their rounds of CUs (default 80; profiles/r04_tile256_fill_rule.txt:
- *                          at 75 % -- GPT-2's fc_1, 384 tiles -- the 256 x 128 ring is 56 us against 74).  Same bits.
  *   gemm.walk_min_tiles    the 256 x 128 ring walks its tiles from this many on (default 3 x 256 + 1: up to three rounds one workgroup per tile is as fast or faster).  Same bits.
- *   gemm.colsplit          the column split of a tile list whose last round is nearly empty (default 1)
- *   gemm_fp8.tail_form     0 (default) = LDS-DMA kernels on the leading multiple of 256 rows, the tail kernels of gemm_fp8_tail.hip on the rest; 1 = EVERY row on the masked
+ *   gemm_fp8.tail_form     (csrc/gemm_plan.hip) 0 (default) = LDS-DMA kernels on the leading multiple of 256 rows, the tail kernels of gemm_fp8_tail.hip on the rest; 1 = EVERY row on the masked
  *                          128-row tiles (bit-identical to the LDS-DMA kernels: the test of that statement); 2 = every row as skinny pieces (fp32-rounding-level differences)
  *   gemm_fp8.skinny_whole_x, gemm_fp8.big_rule, gemm_fp8.splitk_min_rows      the skinny kernel's barrier-free <= 4-row form (1); which row counts below 512 take the LDS-DMA
- *                          kernels (rules 0 .. 3 of gemm256.hip: fp8_big_rows; 3); row counts below this stay off the fp8 split-K form (17)
+ *                          kernels (rules 0 .. 3 of the fp8 plan, csrc/gemm_plan.hip; 3); row counts below this stay off the fp8 split-K form (17)
  *   attn.positions_per_split, attn.max_workgroups, attn.heads_per_group_512, attn.xcd_local, attn.mfma_decode, attn.mfma_min_band      decode attention (csrc/attention.hip)
  *   flash.form             8 (default) = the LDS-DMA forms; 9 = lockstep 8-wave workgroups at HS 256 too; 10 = the ping-pong 8-wave form; 11 = the software-pipelined loop; 2 = HS 512 as 4-wave d-split
  *                          workgroups; 1 = the register-staged kernels.  Same bits.                                                       (csrc/attention_prefill.hip) */

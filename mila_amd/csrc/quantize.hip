@@ -8,7 +8,7 @@
 // exact reduction, so the reduction order does not matter.  The fp8 encode is done in integer
 // arithmetic on the fp32 bits (RNE at mantissa bit 20, saturate to 0x7e) so it does not depend on
 // the FP8 hardware-convert overflow mode.
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace mila {
 
@@ -240,16 +240,16 @@ __global__ __launch_bounds__(256) void quantize_fp8_per_token_kernel(uint8_t* __
     }
 }
 
-int launch_gemm_fp8(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias,
-                    int M, int K, int N, hipStream_t s);
-bool gemm256_geglu_applicable(int M, int K, int F);
-int launch_gemm_fp8_geglu(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, int M, int K, int F,
-                          hipStream_t s);
-// gemm256.hip: the split-K forms behind a caller workspace
-size_t gemm_fp8_ws_bytes(int M, int K, int N);
-int launch_gemm_fp8_ws(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias, int M, int K, int N, hipStream_t s,
-                       void* ws);
-bool gemm_fp8_geglu_steps_aside(int M, int K, int F);
+// the fp8 x fp8 GEMM of an entry point that takes a workspace: the plan is built once, checked against what the caller passed, and run
+static int run_fp8_ws(const char* who, uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, Fp8WScale w_scale, const uint16_t* bias, int M, int K, int N,
+                      void* workspace, size_t workspace_bytes, hipStream_t s)
+{
+    const GemmPlan pl = plan_fp8(M, K, N, true);
+    if (pl.ws_bytes && (!workspace || workspace_bytes < pl.ws_bytes))
+        return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: workspace %zu bytes < required %zu (ask gemm_fp8_workspace_bytes)", who, workspace_bytes, pl.ws_bytes);
+    MILA_REQUIRE(!pl.ws_bytes || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+    return run_gemm_fp8(pl, Y, X8, W8, x_scales, w_scale, bias, K, N, workspace, s);
+}
 
 }  // namespace mila
 
@@ -320,7 +320,7 @@ int mila_cdna4_quantize_fp8_per_token(uint8_t* dst, float* scales, const uint16_
     MILA_LAUNCH_CHECK("quantize_fp8_per_token");
 }
 
-// every M: the LDS-DMA kernels on the leading multiple of 256 rows where one applies, the masked tail kernel on the rest (gemm256.hip: launch_gemm_fp8)
+// every M: the LDS-DMA kernels on the leading multiple of 256 rows where one applies, the masked tail kernel on the rest (gemm_plan.hip: plan_fp8)
 int mila_cdna4_gemm_fp8_applicable(int M, int K, int N) { return (M > 0 && K > 0 && N > 0 && K % 16 == 0) ? 1 : 0; }
 
 int mila_cdna4_gemm_fp8_scaled(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, const float* weight_scale,
@@ -328,12 +328,7 @@ int mila_cdna4_gemm_fp8_scaled(uint16_t* Y, const uint8_t* X8, const uint8_t* W8
 {
     MILA_REQUIRE(Y && X8 && W8 && x_scales && weight_scale, "gemm_fp8_scaled: null pointer");
     MILA_REQUIRE(mila_cdna4_gemm_fp8_applicable(M, K, N), "gemm_fp8_scaled: shape (M=%d, K=%d, N=%d) has no fp8 MFMA kernel (ask gemm_fp8_applicable)", M, K, N);
-    return launch_gemm_fp8(Y, X8, W8, x_scales, Fp8WScale{weight_scale, 0}, bias, M, K, N, as_stream(stream));
-}
-
-size_t mila_cdna4_gemm_fp8_workspace_bytes(int M, int K, int N)
-{
-    return (M > 0 && K > 0 && N > 0 && K % 16 == 0) ? gemm_fp8_ws_bytes(M, K, N) : 0;
+    return run_gemm_fp8(plan_fp8(M, K, N, false), Y, X8, W8, x_scales, Fp8WScale{weight_scale, 0}, bias, K, N, nullptr, as_stream(stream));
 }
 
 int mila_cdna4_gemm_fp8_scaled_ws(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, const float* weight_scale, const uint16_t* bias, int M, int K, int N,
@@ -341,11 +336,7 @@ int mila_cdna4_gemm_fp8_scaled_ws(uint16_t* Y, const uint8_t* X8, const uint8_t*
 {
     MILA_REQUIRE(Y && X8 && W8 && x_scales && weight_scale, "gemm_fp8_scaled_ws: null pointer");
     MILA_REQUIRE(mila_cdna4_gemm_fp8_applicable(M, K, N), "gemm_fp8_scaled_ws: shape (M=%d, K=%d, N=%d) has no fp8 MFMA kernel (ask gemm_fp8_applicable)", M, K, N);
-    const size_t need = gemm_fp8_ws_bytes(M, K, N);
-    if (need && (!workspace || workspace_bytes < need))
-        return set_error(MILA_E_SCRATCH_TOO_SMALL, "gemm_fp8_scaled_ws: workspace %zu bytes < required %zu (ask gemm_fp8_workspace_bytes)", workspace_bytes, need);
-    MILA_REQUIRE(!need || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "gemm_fp8_scaled_ws: the workspace must be 16-byte aligned");
-    return launch_gemm_fp8_ws(Y, X8, W8, x_scales, Fp8WScale{weight_scale, 0}, bias, M, K, N, as_stream(stream), workspace);
+    return run_fp8_ws("gemm_fp8_scaled_ws", Y, X8, W8, x_scales, Fp8WScale{weight_scale, 0}, bias, M, K, N, workspace, workspace_bytes, as_stream(stream));
 }
 
 // [e4m3 weights | e4m3 activations | per-token scales | split-K workspace], each part 16-byte aligned
@@ -357,7 +348,7 @@ static size_t w4a8_ws_offset(int M, int K, int N)
 size_t mila_cdna4_gemm_w4a8_scratch_bytes(int M, int K, int N)
 {
     if (M <= 0 || K <= 0 || N <= 0) return 0;
-    return w4a8_ws_offset(M, K, N) + (K % 16 == 0 ? gemm_fp8_ws_bytes(M, K, N) : 0);
+    return w4a8_ws_offset(M, K, N) + mila_cdna4_gemm_fp8_workspace_bytes(M, K, N);
 }
 
 int mila_cdna4_gemm_bf16_w4a8(uint16_t* Y, const uint16_t* X, const uint8_t* W_packed, const float* scales, const float* weight_fp8_scale,
@@ -365,7 +356,8 @@ int mila_cdna4_gemm_bf16_w4a8(uint16_t* Y, const uint16_t* X, const uint8_t* W_p
 {
     MILA_REQUIRE(Y && X && W_packed && scales && weight_fp8_scale, "gemm_bf16_w4a8: null pointer");
     MILA_REQUIRE(mila_cdna4_gemm_fp8_applicable(M, K, N), "gemm_bf16_w4a8: shape (M=%d, K=%d, N=%d) has no fp8 MFMA kernel (ask gemm_fp8_applicable)", M, K, N);
-    const size_t need = mila_cdna4_gemm_w4a8_scratch_bytes(M, K, N);
+    const GemmPlan pl = plan_fp8(M, K, N, true);
+    const size_t need = w4a8_ws_offset(M, K, N) + pl.ws_bytes;
     if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "gemm_bf16_w4a8: scratch %zu bytes < required %zu", scratch_bytes, need);
     uint8_t* w8 = static_cast<uint8_t*>(scratch);
     uint8_t* x8 = w8 + (((size_t)N * K + 15) & ~(size_t)15);
@@ -375,18 +367,15 @@ int mila_cdna4_gemm_bf16_w4a8(uint16_t* Y, const uint16_t* X, const uint8_t* W_p
     rc = mila_cdna4_quantize_fp8_per_token(x8, ts, X, M, K, stream);
     if (rc) return rc;
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "gemm_bf16_w4a8: the scratch must be 16-byte aligned");
-    return launch_gemm_fp8_ws(Y, x8, w8, ts, Fp8WScale{weight_fp8_scale, 0}, bias, M, K, N, as_stream(stream), w8 + w4a8_ws_offset(M, K, N));
+    return run_gemm_fp8(pl, Y, x8, w8, ts, Fp8WScale{weight_fp8_scale, 0}, bias, K, N, w8 + w4a8_ws_offset(M, K, N), as_stream(stream));
 }
-
-// (0 also where the plain W4A8 GEMM over [2F, K] would split K given a workspace: Linear + GeGLU as two calls is the faster pair there and keeps the bits of the unfused path)
-int mila_cdna4_gemm_geglu_w4a8_applicable(int M, int K, int F) { return (M > 0 && K > 0 && F > 0 && K % 16 == 0 && !gemm_fp8_geglu_steps_aside(M, K, F)) ? 1 : 0; }
 
 int mila_cdna4_gemm_geglu_fp8_scaled(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, const float* weight_scale, int M, int K, int F,
                                      mila_stream_t stream)
 {
     MILA_REQUIRE(Y && X8 && W8 && x_scales && weight_scale, "gemm_geglu_fp8_scaled: null pointer");
     MILA_REQUIRE(mila_cdna4_gemm_geglu_w4a8_applicable(M, K, F), "gemm_geglu_fp8_scaled: shape (M=%d, K=%d, F=%d) is outside the fused kernel", M, K, F);
-    return launch_gemm_fp8_geglu(Y, X8, W8, x_scales, Fp8WScale{weight_scale, 0}, M, K, F, as_stream(stream));
+    return run_gemm_fp8(plan_fp8_geglu(M, K, F), Y, X8, W8, x_scales, Fp8WScale{weight_scale, 0}, nullptr, K, F, nullptr, as_stream(stream));
 }
 
 int mila_cdna4_gemm_geglu_bf16_w4a8(uint16_t* Y, const uint16_t* X, const uint8_t* W_packed, const float* scales, const float* weight_fp8_scale,
@@ -404,7 +393,7 @@ int mila_cdna4_gemm_geglu_bf16_w4a8(uint16_t* Y, const uint16_t* X, const uint8_
     if (rc) return rc;
     rc = mila_cdna4_quantize_fp8_per_token(x8, ts, X, M, K, stream);
     if (rc) return rc;
-    return launch_gemm_fp8_geglu(Y, x8, w8, ts, Fp8WScale{weight_fp8_scale, 0}, M, K, F, as_stream(stream));
+    return run_gemm_fp8(plan_fp8_geglu(M, K, F), Y, x8, w8, ts, Fp8WScale{weight_fp8_scale, 0}, nullptr, K, F, nullptr, as_stream(stream));
 }
 
 /* ---- W8A8: the PerChannelFp8<> policy's own e4m3 [N, K] weights + scale[N] consumed by the fp8 matrix cores as they lie in HBM (Quantization/Weight/Policies.ixx:39-40:
@@ -418,11 +407,7 @@ int mila_cdna4_gemm_fp8_w8a8_ws(uint16_t* Y, const uint8_t* X8, const uint8_t* W
     MILA_REQUIRE(Y && X8 && W8 && x_scales && channel_scales, "gemm_fp8_w8a8_ws: null pointer");
     MILA_REQUIRE(mila_cdna4_gemm_fp8_applicable(M, K, N), "gemm_fp8_w8a8_ws: shape (M=%d, K=%d, N=%d) has no fp8 MFMA kernel (ask gemm_fp8_applicable)", M, K, N);
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(channel_scales) & 15) == 0, "gemm_fp8_w8a8_ws: the per-channel scales must be 16-byte aligned");
-    const size_t need = gemm_fp8_ws_bytes(M, K, N);
-    if (need && (!workspace || workspace_bytes < need))
-        return set_error(MILA_E_SCRATCH_TOO_SMALL, "gemm_fp8_w8a8_ws: workspace %zu bytes < required %zu (ask gemm_fp8_workspace_bytes)", workspace_bytes, need);
-    MILA_REQUIRE(!need || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "gemm_fp8_w8a8_ws: the workspace must be 16-byte aligned");
-    return launch_gemm_fp8_ws(Y, X8, W8, x_scales, Fp8WScale{channel_scales, 1}, bias, M, K, N, as_stream(stream), workspace);
+    return run_fp8_ws("gemm_fp8_w8a8_ws", Y, X8, W8, x_scales, Fp8WScale{channel_scales, 1}, bias, M, K, N, workspace, workspace_bytes, as_stream(stream));
 }
 
 int mila_cdna4_gemm_geglu_fp8_w8a8(uint16_t* Y, const uint8_t* X8, const uint8_t* W8, const float* x_scales, const float* channel_scales, int M, int K, int F, mila_stream_t stream)
@@ -430,7 +415,7 @@ int mila_cdna4_gemm_geglu_fp8_w8a8(uint16_t* Y, const uint8_t* X8, const uint8_t
     MILA_REQUIRE(Y && X8 && W8 && x_scales && channel_scales, "gemm_geglu_fp8_w8a8: null pointer");
     MILA_REQUIRE(mila_cdna4_gemm_geglu_w4a8_applicable(M, K, F), "gemm_geglu_fp8_w8a8: shape (M=%d, K=%d, F=%d) is outside the fused kernel (ask gemm_geglu_w4a8_applicable)", M, K, F);
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(channel_scales) & 15) == 0 && F % 4 == 0, "gemm_geglu_fp8_w8a8: the per-channel scales must be 16-byte aligned and F a multiple of 4");
-    return launch_gemm_fp8_geglu(Y, X8, W8, x_scales, Fp8WScale{channel_scales, 1}, M, K, F, as_stream(stream));
+    return run_gemm_fp8(plan_fp8_geglu(M, K, F), Y, X8, W8, x_scales, Fp8WScale{channel_scales, 1}, nullptr, K, F, nullptr, as_stream(stream));
 }
 
 // [e4m3 activations | per-token scales | split-K workspace], each part 16-byte aligned
@@ -441,7 +426,7 @@ static size_t w8a8_ws_offset(int M, int K)
 size_t mila_cdna4_gemm_w8a8_scratch_bytes(int M, int K, int N)
 {
     if (M <= 0 || K <= 0 || N <= 0) return 0;
-    return w8a8_ws_offset(M, K) + (K % 16 == 0 ? gemm_fp8_ws_bytes(M, K, N) : 0);
+    return w8a8_ws_offset(M, K) + mila_cdna4_gemm_fp8_workspace_bytes(M, K, N);
 }
 
 int mila_cdna4_gemm_bf16_w8a8(uint16_t* Y, const uint16_t* X, const uint8_t* W8, const float* channel_scales, const uint16_t* bias, int M, int K, int N, void* scratch,
@@ -450,14 +435,15 @@ int mila_cdna4_gemm_bf16_w8a8(uint16_t* Y, const uint16_t* X, const uint8_t* W8,
     MILA_REQUIRE(Y && X && W8 && channel_scales, "gemm_bf16_w8a8: null pointer");
     MILA_REQUIRE(mila_cdna4_gemm_fp8_applicable(M, K, N), "gemm_bf16_w8a8: shape (M=%d, K=%d, N=%d) has no fp8 MFMA kernel (ask gemm_fp8_applicable)", M, K, N);
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(channel_scales) & 15) == 0, "gemm_bf16_w8a8: the per-channel scales must be 16-byte aligned");
-    const size_t need = mila_cdna4_gemm_w8a8_scratch_bytes(M, K, N);
+    const GemmPlan pl = plan_fp8(M, K, N, true);
+    const size_t need = w8a8_ws_offset(M, K) + pl.ws_bytes;
     if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "gemm_bf16_w8a8: scratch %zu bytes < required %zu", scratch_bytes, need);
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "gemm_bf16_w8a8: the scratch must be 16-byte aligned");
     uint8_t* x8 = static_cast<uint8_t*>(scratch);
     float* ts = reinterpret_cast<float*>(x8 + (((size_t)M * K + 15) & ~(size_t)15));
     int rc = mila_cdna4_quantize_fp8_per_token(x8, ts, X, M, K, stream);
     if (rc) return rc;
-    return launch_gemm_fp8_ws(Y, x8, W8, ts, Fp8WScale{channel_scales, 1}, bias, M, K, N, as_stream(stream), x8 + w8a8_ws_offset(M, K));
+    return run_gemm_fp8(pl, Y, x8, W8, ts, Fp8WScale{channel_scales, 1}, bias, K, N, x8 + w8a8_ws_offset(M, K), as_stream(stream));
 }
 
 int mila_cdna4_gemm_geglu_bf16_w8a8(uint16_t* Y, const uint16_t* X, const uint8_t* W8, const float* channel_scales, int M, int K, int F, void* scratch, size_t scratch_bytes,
@@ -473,7 +459,7 @@ int mila_cdna4_gemm_geglu_bf16_w8a8(uint16_t* Y, const uint16_t* X, const uint8_
     float* ts = reinterpret_cast<float*>(x8 + (((size_t)M * K + 15) & ~(size_t)15));
     int rc = mila_cdna4_quantize_fp8_per_token(x8, ts, X, M, K, stream);
     if (rc) return rc;
-    return launch_gemm_fp8_geglu(Y, x8, W8, ts, Fp8WScale{channel_scales, 1}, M, K, F, as_stream(stream));
+    return run_gemm_fp8(plan_fp8_geglu(M, K, F), Y, x8, W8, ts, Fp8WScale{channel_scales, 1}, nullptr, K, F, nullptr, as_stream(stream));
 }
 
 }  // extern "C"

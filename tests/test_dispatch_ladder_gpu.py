@@ -4,7 +4,7 @@ with its default W8A16 prefill and with the opt-in W8A8 one, PerGroupFp4<128> = 
 (gpu_util.sample_rows: every row up to 65, beyond that both ends of every 256-row tile-row, every 32-row band of three tile-rows and ten rows of the remainder; the
 expectation of all row counts in one float64 matmul, tests/ref_matmul.py, the bar elementwise, gpu_util.assert_gemm_close),
 AND the kernel form that served the call (csrc/internal.h: mila_cdna4_last_form) against a committed table (tests/golden/dispatch_ladder.json): a threshold edit in
-csrc/gemm.hip / gemm256.hip cannot silently route a prompt length to another form -- the table changes, and this test says so until the table is regenerated on purpose
+csrc/gemm_plan.hip cannot silently route a prompt length to another form -- the table changes, and this test says so until the table is regenerated on purpose
 (MILA_RECORD_LADDER=1 python -m pytest tests/test_dispatch_ladder_gpu.py  ->  gpurun_out/dispatch_ladder.json).
 
 Reference: CudaLinearOp::forward's branches (OPS/Linear/CudaLinearOp.ixx:543-827): M == 1 decode matvecs; M > 1: bf16 cuBLASLt, fp8 weights 2-phase W8A16, fp4 weights W4A8."""

@@ -92,7 +92,7 @@ def test_full_size_gemm_schedules_give_the_same_bits(policy, bf16_run):
     lib = capi.load()
     outs = []
     try:
-        # (the split-K forms -- here the column split of the global qkv_proj, csrc/gemm256.hip: gemm_colsplit_main -- exist under the default schedule only and sum K in
+        # (the split-K forms -- here the column split of the global qkv_proj, csrc/gemm_plan.hip: colsplit_columns -- exist under the default schedule only and sum K in
         # another order: the schedules are compared on ONE decomposition, with the column split off; the default decomposition is compared across its own two forms below)
         capi.tune("gemm.colsplit", 0)
         for sched, persistent in (((0, 1), (3, 1), (5, 0), (5, 1)) if policy == "bf16" else ((1, 1), (3, 1), (5, 0), (5, 1))):

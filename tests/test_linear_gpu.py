@@ -585,7 +585,7 @@ def test_w4a8_serves_every_row_count_like_the_reference(M, K, N, bias, G):
             capi.tune_reset()
         forms[form] = bits(Yf)
         assert_bf16_close(forms[form][rows], exp, 2, 1e-3 * float(np.abs(exp).max()), "fp8 GEMM, tail form %d, vs restated reference" % form)
-    # who serves which rows by default (csrc/gemm256.hip: launch_gemm_fp8): with M >= 512 (and K % 128 == N % 128 == 0) the LDS-DMA kernels take every tile-row,
+    # who serves which rows by default (csrc/gemm_plan.hip: plan_fp8): with M >= 512 (and K % 128 == N % 128 == 0) the LDS-DMA kernels take every tile-row,
     # a ragged last one masked -- unless the tail is <= 64 rows, which goes to the skinny kernel; below 512 rows: skinny up to 16 (64 without a tile grid), masked LDS tiles beyond
     # -- and below 512 rows wherever their grid still has >= 120 tiles (no skinny split there: the remainder stays in the ragged tile-row)
     tail = M % 256
@@ -1031,7 +1031,7 @@ def test_w4a8_gemm_with_a_workspace_splits_k(M, K, N, bias):
 @pytest.mark.parametrize("M,K,N", [(2048, 1024, 8704), (2048 + 100, 1024, 8704)])
 def test_column_split_of_a_tile_list_that_ends_in_a_nearly_empty_round(M, K, N):
     """Gemma's global qkv_proj (N = 8704) at T = 2048 is 272 tiles of 256 x 256 on 256 CUs: with a workspace the first 8192 columns run as whole rounds of 256 x 256 tiles and
-    the last 512 through the split-K ring, both writing their column range of Y with the pitch of the whole row (csrc/gemm256.hip: gemm_colsplit_main).  bf16, W4A8 and W8A8:
+    the last 512 through the split-K ring, both writing their column range of Y with the pitch of the whole row (csrc/gemm_plan.hip: colsplit_columns).  bf16, W4A8 and W8A8:
     sampled rows x ALL columns (both sides of the cut) against the float64 oracle, a guard row behind Y, and the form that ran."""
     lib = capi.load()
     rng = np.random.default_rng(M + N)
