@@ -508,6 +508,9 @@ MILA_API int mila_cdna4_fused_attn_decode_bf16(uint16_t* Y, uint16_t* Kc, uint16
                                                int NKV, int HS, int capacity, int position,
                                                const int32_t* position_dev, int window, float scale, float eps,
                                                mila_stream_t stream);
+/* the live-length bucket of `len` keys on a cache of `capacity` rows, as the decode entry points choose it: what a caller compares to know when a captured launch must
+ * be captured again (0 for capacity <= 0) */
+MILA_API int mila_cdna4_attn_decode_band_bucket(int len, int capacity);
 
 /* fused_attn_decode_bf16 for B rows decoded at ONE position (the reference's decode kernels take the batch in their grid, Gqa.Decode.Bf16.cu:379-387): batch row b reads
  * q_raw / k_raw / v_raw + b * raw_b_stride elements and its own caches [b]; Y [B, NH*HS]; scratch from attn_decode_scratch_bytes(B, NH, HS).  Bit-identical, row by row,

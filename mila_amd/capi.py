@@ -150,6 +150,21 @@ def gemm_plan(entry, M, K, N):
     return [(f[0],) + tuple(int(v) for v in f[1:]) for f in (item.split(":") for item in buf.value.decode().split("+") if item)]
 
 
+PLAN_FIELDS = ("form", "splits", "band_max", "heads_per_group", "head_groups", "flat", "prologue", "partial_floats", "scratch_need")
+
+
+def attn_decode_plan(B, NH, NKV, HS, capacity, window, len_hint=0, fused=False, hooks=False):
+    """the decode-attention plan (csrc/attention.hip: plan_decode) of a shape as a dict of PLAN_FIELDS: len_hint = the live-length bound the launch is for (0 = the capacity),
+    fused = a fused entry, hooks = the entry uses tickets, no_combine or warm ranges.  Needs no GPU."""
+    lib = load()
+    lib.mila_cdna4_attn_decode_plan_describe.restype = C.c_size_t
+    buf = C.create_string_buffer(256)
+    need = lib.mila_cdna4_attn_decode_plan_describe(int(B), int(NH), int(NKV), int(HS), int(capacity), int(window), int(len_hint), int(fused), int(hooks), buf, C.c_size_t(len(buf)))
+    assert 0 < need <= len(buf), "no plan for this shape" if not need else "plan text of %d bytes" % need
+    f = buf.value.decode().split(":")
+    return dict(zip(PLAN_FIELDS, [f[0]] + [int(v) for v in f[1:]]))
+
+
 def check(rc):
     if rc == MILA_OK:
         return
@@ -197,14 +212,14 @@ EXPORTED = [
     "sample_stochastic_scratch_bytes", "sample_stochastic_fp32", "sample_stochastic_bf16",
     "fused_norm_matvec", "fused_qkv_post", "fused_qkv_post_prefill", "fused_tail_norm_bf16", "fused_tail_norm_quant_bf16",
     "attn_decode_bf16_devpos", "fused_qkv_post_devpos", "advance_position", "advance_position_snapshot", "snapshot_token", "sample_argmax_advance_fp32", "sample_argmax_final_advance", "fused_attn_decode_batch_bf16", "fused_attn_decode_bf16",
-    "dequantize_to_bf16", "gemm_geglu_fp8_scaled",
+    "attn_decode_band_bucket", "dequantize_to_bf16", "gemm_geglu_fp8_scaled",
     "gemm_fp8_w8a8_ws", "gemm_geglu_fp8_w8a8", "gemm_w8a8_scratch_bytes", "gemm_bf16_w8a8", "gemm_geglu_bf16_w8a8",
     "matvec_fp32", "gemm_fp32", "mha_fp32", "mha_kv_write_fp32", "mha_decode_fp32", "lpe_fp32", "rope_forward_fp32",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI
 INTERNAL = [
-    "tune", "tune_get", "tune_reset", "tune_list", "last_form", "gemm_plan_describe",
+    "tune", "tune_get", "tune_reset", "tune_list", "last_form", "gemm_plan_describe", "attn_decode_plan_describe",
     "decode_engine_debug",
     "selftest_decode", "selftest_wave_reduce", "selftest_mfma_fp8", "stream_copy", "stream_read",
     "attn_decode_split_count", "fused_attn_decode_partials_bf16", "matvec_attn_combine",

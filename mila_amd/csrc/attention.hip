@@ -27,12 +27,6 @@
 
 namespace mila {
 
-constexpr int kMaxSplits = 64;
-constexpr int kMaxSplitsMfma = 256;      // the long-context MFMA decode (attn_decode_mfma_kernel): one workgroup per CU
-constexpr int kMfmaMinBand = 8192;        // band bucket (keys) from which a 16-head group on one KV head takes the MFMA decode (see band_bucket; profiles/r04_attn_band.txt)
-static int g_mfma_min_band = kMfmaMinBand;      // tuning "attn.mfma_min_band" (keys)
-MILA_TUNE("attn.mfma_min_band", g_mfma_min_band);
-
 // ---- KV append ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void kv_write_bf16_kernel(uint16_t* __restrict__ Kc, uint16_t* __restrict__ Vc,
                                                             const uint16_t* __restrict__ k,
@@ -761,9 +755,59 @@ __global__ __launch_bounds__(256) void attn_combine_many_kernel(uint16_t* __rest
     }
 }
 
+// ---- the decode plan ------------------------------------------------------------------------------------------------------------------------------------
+// Everything one decode call decides before it launches -- kernel form, split count, the band the splits are sized for, grid shape, scratch -- is a DecodePlan, made in
+// ONE place (plan_decode) from the shape alone; run_decode launches from it, the size / split-count queries and mila_cdna4_attn_decode_plan_describe read it.  Each
+// rule stands here once, its tunable beside it.
+enum DecodeForm { DF_SCALAR, DF_MFMA, DF_GENERIC };      // attn_decode_kernel | attn_decode_mfma_kernel | attention_generic.hip (any other head size)
+struct DecodePlan
+{
+    DecodeForm form;
+    int splits, band_max;         // band_max: the most keys a launch of this shape sees (the window, or the live-length bucket)
+    int gh, hgroups;              // query heads per workgroup, workgroups per KV head (scalar form)
+    int flat;                     // AttnParams::flat
+    bool prologue;                // MFMA form of a fused entry: q/k/v norm + RoPE + KV append as a launch of its own, the roped q rows parked behind the partials
+    size_t partial_floats;        // B * NH * splits * (HS + 4)
+    size_t scratch_need;          // bytes; 0 = the launch touches no scratch
+};
+
+constexpr int kMaxSplits = 64;
+constexpr int kMaxSplitsMfma = 256;      // the long-context MFMA decode (attn_decode_mfma_kernel): one workgroup per CU
+static int g_tune_positions_per_split = 64;     // tuning "attn.positions_per_split": positions one split covers
+MILA_TUNE("attn.positions_per_split", g_tune_positions_per_split);
+static int g_attn_max_wgs = 256;                // decode_splits: the split count is capped so that a launch has about this many workgroups
+MILA_TUNE("attn.max_workgroups", g_attn_max_wgs);
+static int g_attn_gh512 = 2;      // query heads per workgroup at HS 512 (experiment: 4 = half the head groups re-reading each K / V row, twice the accumulators per wave)
+MILA_TUNE("attn.heads_per_group_512", g_attn_gh512);
 static int g_tune_decode_mfma = 1;      // tuning "attn.mfma_decode": 0 = never take the MFMA decode
 MILA_TUNE("attn.mfma_decode", g_tune_decode_mfma);
+static int g_mfma_min_band = 8192;      // tuning "attn.mfma_min_band": band bucket (keys) from which a 16-head group on one KV head takes the MFMA decode (profiles/r04_attn_band.txt)
+MILA_TUNE("attn.mfma_min_band", g_mfma_min_band);
+// Experiment (round 4, VERDICT r03 item 2a): every split of a head group and the combine workgroups of its heads on ONE XCD (blockIdx.x % 8 equal), so that the merge
+// reads the partials from that XCD's L2 instead of across the fabric.  Same arithmetic per workgroup: bit-identical.  Result: profiles/r04_attn_pair_experiments.txt
+static int g_attn_xcd_local = 0;
+MILA_TUNE("attn.xcd_local", g_attn_xcd_local);
 
+// The launch geometry of an unwindowed layer (split count, and whether the matrix-core decode serves it) is chosen from a BUCKET of the live length, not from the cache
+// capacity: 4096, 8192, 16384, ... keys (doubling), clipped to the capacity.  (chosen from the capacity alone, a 32K-capacity cache decoding at position 2K
+// ran the matrix-core kernel with 256 splits of 8 keys each -- 28.5 us against the scalar kernel's 23.9; the crossover is at ~8K keys, profiles/r04_attn_band.txt.)  A
+// bucket is a function of the position only, so eager launches and a captured graph agree as long as the graph is re-captured when the position leaves its bucket
+// (GemmaTransformer::ensureGraph asks mila_cdna4_attn_decode_band_bucket); inside a bucket the geometry is static, which is what a graph needs.  Caches of <= 4096 rows
+// (the benchmark's) have one bucket.
+static int band_bucket(int len, int capacity)
+{
+    int b = 4096;
+    while (b < len && b < capacity) b <<= 1;
+    return min(b, capacity);
+}
+static int heads_per_group(int GS, int HS) { return HS >= 512 ? (GS >= g_attn_gh512 && g_attn_gh512 == 4 ? 4 : (GS >= 2 ? 2 : 1)) : (GS >= 4 ? 4 : GS); }
+static int decode_splits(int B, int NKV, int hgroups, int band)
+{
+    // ~256 workgroups of 8 waves, 64 positions (8 per wave) per split
+    const int cap = max(1, g_attn_max_wgs / (NKV * hgroups * B));
+    const int pps = g_tune_positions_per_split >= 8 ? g_tune_positions_per_split : 64;      // (a tuning value below 8 means the default)
+    return max(1, min(min((band + pps - 1) / pps, cap), kMaxSplits));
+}
 static bool mfma_decode_applies(int NH, int NKV, int HS, int band_max)
 {
     return g_tune_decode_mfma && HS == 512 && NKV > 0 && (NH / NKV) % 16 == 0 && band_max >= g_mfma_min_band;
@@ -771,11 +815,44 @@ static bool mfma_decode_applies(int NH, int NKV, int HS, int band_max)
 static int mfma_decode_splits(int B, int NH, int NKV, int band_max)
 {
     const int groups = NKV * ((NH / NKV) / 16) * B;
-    int s = (band_max + 127) / 128;                      // at least four key tiles per split at the full band
-    const int cap = max(1, kNumCU / groups);
-    if (s > cap) s = cap;
-    if (s > kMaxSplitsMfma) s = kMaxSplitsMfma;
-    return max(s, 1);
+    const int s = (band_max + 127) / 128;                      // at least four key tiles per split at the full band
+    return max(1, min(min(s, max(1, kNumCU / groups)), kMaxSplitsMfma));
+}
+// partials [B, NH, splits, HS + 4] floats, + the roped q rows [B, NH, HS] bf16 of a prologue launch
+static size_t decode_scratch_bytes(int B, int NH, int HS, int splits, bool q_rows)
+{
+    return (size_t)B * NH * splits * (HS + 4) * sizeof(float) + (q_rows ? (size_t)B * NH * HS * 2 : 0);
+}
+
+// len_hint: an upper bound on the live length the launch is for -- position + 1 in the eager forms; in the device-position forms what the caller captured the graph for;
+// 0 = the capacity.  The split count depends only on (window, band bucket), never on the current length inside a bucket, so that eager launches and a graph captured
+// once reduce in the same order: bit-identical.  hooks: the entry uses tickets, no_combine or warm ranges, which address the 3-D grid of the scalar kernel.
+static DecodePlan plan_decode(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, bool fused, bool hooks)
+{
+    DecodePlan d{};
+    const int GS = NH / NKV;
+    const bool split_kernel = HS == 64 || HS == 128 || HS == 256 || HS == 512;
+    d.band_max = (window > 0 && window < capacity) ? window : (len_hint > 0 ? band_bucket(len_hint, capacity) : capacity);
+    d.gh = heads_per_group(GS, HS);
+    d.hgroups = GS / d.gh;
+    if (mfma_decode_applies(NH, NKV, HS, d.band_max) && !hooks)
+    {
+        // 16 heads on one KV head over a long band: the matrix-core decode.  The fused form is the CHAIN here: the 4 us its prologue launch costs are nothing against a
+        // band of thousands of keys
+        d.form = DF_MFMA;
+        d.splits = mfma_decode_splits(B, NH, NKV, d.band_max);
+        d.prologue = fused;
+    }
+    else
+    {
+        d.form = split_kernel ? DF_SCALAR : DF_GENERIC;
+        d.splits = decode_splits(B, NKV, d.hgroups, d.band_max);
+        // the XCD-local grid needs the head groups to tile the 8 XCDs (8 groups, or a multiple)
+        d.flat = (g_attn_xcd_local && split_kernel && (NKV * d.hgroups) % 8 == 0 && !hooks) ? 1 : 0;
+    }
+    d.partial_floats = (size_t)B * NH * d.splits * (HS + 4);
+    d.scratch_need = (d.form == DF_MFMA || (d.form == DF_SCALAR && d.splits > 1)) ? decode_scratch_bytes(B, NH, HS, d.splits, d.prologue) : 0;
+    return d;
 }
 static int launch_decode_mfma(const AttnParams& p, int B, hipStream_t s)
 {
@@ -797,10 +874,6 @@ static int launch_decode_mfma(const AttnParams& p, int B, hipStream_t s)
     return check_hip(hipGetLastError(), "attn_combine_many");
 }
 
-static int g_attn_gh512 = 2;      // query heads per workgroup at HS 512 (experiment: 4 = half the head groups re-reading each K / V row, twice the accumulators per wave)
-MILA_TUNE("attn.heads_per_group_512", g_attn_gh512);
-static int heads_per_group(int GS, int HS) { return HS >= 512 ? (GS >= g_attn_gh512 && g_attn_gh512 == 4 ? 4 : (GS >= 2 ? 2 : 1)) : (GS >= 4 ? 4 : GS); }
-
 template <int HS, int GH, bool FUSED>
 static int launch_decode(const AttnParams& p, int B, hipStream_t s)
 {
@@ -810,7 +883,7 @@ static int launch_decode(const AttnParams& p, int B, hipStream_t s)
     const int wa = (p.warm_a && p.warm_a_lines > 0) ? p.warm_a_blocks : 0;
     if (p.flat)
     {
-        // (only taken without warm blocks, tickets or a caller-side combine: run_decode)
+        // (only taken without warm blocks, tickets or a caller-side combine: plan_decode)
         hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED>), dim3(p.NKV * hgroups * p.splits, 1, B), dim3(kDecodeWaves * 64), lds, s, p);
         int rc = check_hip(hipGetLastError(), "attn_decode (xcd-local)");
         if (rc || p.splits <= 1) return rc;
@@ -868,119 +941,92 @@ static int dispatch_hs(int HS, const AttnParams& p, int B, hipStream_t s)
     }
 }
 
-static int g_tune_positions_per_split = 64;     // tuning "attn.positions_per_split": positions one split covers
-MILA_TUNE("attn.positions_per_split", g_tune_positions_per_split);
-// Experiment (round 4, VERDICT r03 item 2a): every split of a head group and the combine workgroups of its heads on ONE XCD (blockIdx.x % 8 equal), so that the merge
-// reads the partials from that XCD's L2 instead of across the fabric.  Same arithmetic per workgroup: bit-identical.  Result: profiles/r04_attn_pair_experiments.txt
-static int g_attn_xcd_local = 0;
-MILA_TUNE("attn.xcd_local", g_attn_xcd_local);
-static int g_attn_max_wgs = 256;                // decode_splits: the split count is capped so that a launch has about this many workgroups
-MILA_TUNE("attn.max_workgroups", g_attn_max_wgs);
-
-static int decode_splits(int B, int NH, int NKV, int HS, int band)
+// The one executor: scratch check against the plan, the prologue launch where the plan has one, the leaf launcher of the plan's form.  A fused call has p.q_raw set.
+static int run_decode(const DecodePlan& d, AttnParams p, int B, int HS, size_t scratch_bytes, const char* who, hipStream_t stream)
 {
-    // ~256 workgroups of 8 waves, 64 positions (8 per wave) per split
-    const int GS = NH / NKV;
-    const int hgroups = GS / heads_per_group(GS, HS);
-    int cap = g_attn_max_wgs / (NKV * hgroups * B);
-    if (cap < 1) cap = 1;
-    const int pps = g_tune_positions_per_split >= 8 ? g_tune_positions_per_split : 64;      // (a tuning value below 8 means the default)
-    int s = (band + pps - 1) / pps;
-    if (s > cap) s = cap;
-    if (s > kMaxSplits) s = kMaxSplits;
-    if (s < 1) s = 1;
-    return s;
-}
-
-// The launch geometry of an unwindowed layer (split count, and whether the matrix-core decode serves it) is chosen from a BUCKET of the live length, not from the cache
-// capacity: 4096, 8192, 16384, ... keys, clipped to the capacity.  (chosen from the capacity alone, a 32K-capacity cache decoding at position 2K ran the
-// matrix-core kernel with 256 splits of 8 keys each -- 28.5 us against the scalar kernel's 23.9; the crossover is at ~8K keys, profiles/r04_attn_band.txt.)  A bucket is a
-// function of the position only, so eager launches and a captured graph agree as long as the graph is re-captured when the position leaves its bucket
-// (GemmaTransformer::ensureGraph does); inside a bucket the geometry is static, which is what a graph needs.  Caches of <= 4096 rows (the benchmark's) have one bucket.
-static int band_bucket(int len, int capacity)
-{
-    int b = 4096;
-    while (b < len && b < capacity) b <<= 1;
-    return min(b, capacity);
-}
-
-// len_hint: an upper bound on the live length this launch is for -- position + 1 in the eager forms; in the device-position forms what the caller captured the graph
-// for (0 = the capacity)
-static int run_decode(uint16_t* Y, const uint16_t* Q, uint16_t* Kc, uint16_t* Vc, void* scratch, size_t scratch_bytes, int B,
-                      int NH, int NKV, int HS, int capacity, int position, const int32_t* pos_dev, int window, float scale,
-                      const AttnParams* fused, const char* who, hipStream_t stream, int len_hint = 0)
-{
-    AttnParams p{};
-    if (fused) p = *fused;
-    p.Y = Y; p.Q = Q; p.K = Kc; p.V = Vc; p.scratch = reinterpret_cast<float*>(scratch);
-    p.NH = NH; p.NKV = NKV; p.capacity = capacity; p.position = position; p.window = window;
-    // the split count depends only on (window, band bucket), never on the current length inside a bucket, so that eager
-    // launches and a graph captured once (the _devpos forms) reduce in the same order: bit-identical
-    const int hint = pos_dev ? len_hint : position + 1;
-    const int band_limit = hint > 0 ? band_bucket(hint, capacity) : capacity;
-    const int band_max = (window > 0 && window < capacity) ? window : band_limit;
-    p.splits = decode_splits(B, NH, NKV, HS, band_max);
-    p.scale = scale;
-    p.pos_dev = pos_dev;
-    if (mfma_decode_applies(NH, NKV, HS, band_max) && !p.tickets && !p.no_combine && !p.warm_a && !p.warm_b)
+    const bool fused = p.q_raw != nullptr;
+    p.splits = d.splits;
+    p.flat = d.flat;
+    if (d.scratch_need && (!p.scratch || scratch_bytes < d.scratch_need))
+        return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, d.scratch_need);
+    if (d.form != DF_MFMA) return fused ? dispatch_hs<true>(HS, p, B, stream) : dispatch_hs<false>(HS, p, B, stream);
+    if (d.prologue)
     {
-        // 16 heads on one KV head over a long band: the matrix-core decode (attn_decode_mfma_kernel).  The fused form is the CHAIN here -- q/k/v norm + RoPE + KV append
-        // as its own launch, the roped q rows parked behind the partials -- the 4 us it costs are nothing against a band of thousands of keys
-        p.splits = mfma_decode_splits(B, NH, NKV, band_max);
-        const size_t part_floats = (size_t)B * NH * p.splits * (HS + 4);
-        const size_t need = part_floats * sizeof(float) + (fused ? (size_t)B * NH * HS * 2 : 0);
-        if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
-        if (fused)
+        uint16_t* q_tmp = reinterpret_cast<uint16_t*>(p.scratch + d.partial_floats);
+        for (int b = 0; b < B; ++b)
         {
-            uint16_t* q_tmp = reinterpret_cast<uint16_t*>(p.scratch + part_floats);
-            for (int b = 0; b < B; ++b)
-            {
-                uint16_t* kc = Kc + (size_t)b * NKV * capacity * HS;
-                uint16_t* vc = Vc + (size_t)b * NKV * capacity * HS;
-                const size_t ro = (size_t)b * p.raw_b_stride;
-                const int rc = pos_dev ? mila_cdna4_fused_qkv_post_devpos(q_tmp + (size_t)b * NH * HS, kc, vc, p.q_raw + ro, p.k_raw + ro, p.v_raw + ro, p.qw, p.kw, p.vw, p.cos_cache,
-                                                                          p.sin_cache, NH, NKV, HS, pos_dev, capacity, p.eps, reinterpret_cast<mila_stream_t>(stream))
-                                       : mila_cdna4_fused_qkv_post(q_tmp + (size_t)b * NH * HS, kc, vc, p.q_raw + ro, p.k_raw + ro, p.v_raw + ro, p.qw, p.kw, p.vw, p.cos_cache,
-                                                                   p.sin_cache, NH, NKV, HS, position, capacity, p.eps, reinterpret_cast<mila_stream_t>(stream));
-                if (rc) return rc;
-            }
-            p.Q = q_tmp;
-            p.q_b_stride = 0;
+            uint16_t* kc = p.K + (size_t)b * p.NKV * p.capacity * HS;
+            uint16_t* vc = p.V + (size_t)b * p.NKV * p.capacity * HS;
+            const size_t ro = (size_t)b * p.raw_b_stride;
+            const int rc = p.pos_dev ? mila_cdna4_fused_qkv_post_devpos(q_tmp + (size_t)b * p.NH * HS, kc, vc, p.q_raw + ro, p.k_raw + ro, p.v_raw + ro, p.qw, p.kw, p.vw, p.cos_cache,
+                                                                        p.sin_cache, p.NH, p.NKV, HS, p.pos_dev, p.capacity, p.eps, reinterpret_cast<mila_stream_t>(stream))
+                                     : mila_cdna4_fused_qkv_post(q_tmp + (size_t)b * p.NH * HS, kc, vc, p.q_raw + ro, p.k_raw + ro, p.v_raw + ro, p.qw, p.kw, p.vw, p.cos_cache,
+                                                                 p.sin_cache, p.NH, p.NKV, HS, p.position, p.capacity, p.eps, reinterpret_cast<mila_stream_t>(stream));
+            if (rc) return rc;
         }
-        return launch_decode_mfma(p, B, stream);
+        p.Q = q_tmp;
+        p.q_b_stride = 0;
     }
-    const bool split_kernel = HS == 64 || HS == 128 || HS == 256 || HS == 512;
-    if (split_kernel && p.splits > 1)
-    {
-        const size_t need = (size_t)B * NH * p.splits * (HS + 4) * sizeof(float);
-        if (!scratch || scratch_bytes < need)
-            return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
-    }
-    {
-        // the XCD-local grid needs the head groups to tile the 8 XCDs (8 groups, or a multiple), and none of the experiment hooks that address the 3-D grid
-        const int GS_ = NH / NKV, ngrp = NKV * (GS_ / heads_per_group(GS_, HS));
-        p.flat = (g_attn_xcd_local && split_kernel && ngrp % 8 == 0 && !p.tickets && !p.no_combine && !p.warm_a && !p.warm_b) ? 1 : 0;
-    }
-    return fused ? dispatch_hs<true>(HS, p, B, stream) : dispatch_hs<false>(HS, p, B, stream);
+    return launch_decode_mfma(p, B, stream);
 }
 
-// unfused decode whose query rows are `q_b_stride` elements apart (a packed [B, 1, 3C] MHA projection)
-static int run_decode_q(uint16_t* Y, const uint16_t* Q, int64_t q_b_stride, uint16_t* Kc, uint16_t* Vc, void* scratch, size_t scratch_bytes, int B,
-                        int NH, int NKV, int HS, int capacity, int position, int window, float scale, const char* who, hipStream_t stream)
+// The unfused entries (attn_decode_bf16, its device-position form, mha_decode_bf16): plan and launch.  q_b_stride as in AttnParams; len_hint as in plan_decode.
+static int unfused_decode(const char* who, uint16_t* Y, const uint16_t* Q, int64_t q_b_stride, const uint16_t* Kc, const uint16_t* Vc, void* scratch, size_t scratch_bytes, int B,
+                          int NH, int NKV, int HS, int capacity, int position, const int32_t* pos_dev, int len_hint, int window, float scale, hipStream_t stream)
 {
     AttnParams p{};
-    p.Y = Y; p.Q = Q; p.q_b_stride = q_b_stride; p.K = Kc; p.V = Vc; p.scratch = reinterpret_cast<float*>(scratch);
-    p.NH = NH; p.NKV = NKV; p.capacity = capacity; p.position = position; p.window = window;
-    const int band_max = (window > 0 && window < capacity) ? window : capacity;
-    p.splits = decode_splits(B, NH, NKV, HS, band_max);
-    p.scale = scale;
-    const bool split_kernel = HS == 64 || HS == 128 || HS == 256 || HS == 512;
-    if (split_kernel && p.splits > 1)
+    p.Y = Y; p.Q = Q; p.q_b_stride = q_b_stride; p.K = const_cast<uint16_t*>(Kc); p.V = const_cast<uint16_t*>(Vc); p.scratch = reinterpret_cast<float*>(scratch);
+    p.NH = NH; p.NKV = NKV; p.capacity = capacity; p.position = position; p.pos_dev = pos_dev; p.window = window; p.scale = scale;
+    return run_decode(plan_decode(B, NH, NKV, HS, capacity, window, len_hint, false, false), p, B, HS, scratch_bytes, who, stream);
+}
+
+// What the fused entry points share: the checks (`who` names the entry in the messages), the prologue fields of AttnParams, the plan and its launch.  The argument
+// block is fused_attn_decode_ex's; the other entries fill it from their parameter lists.
+enum { FD_BATCH = 1, FD_TICKETS = 2, FD_PARTIALS = 4 };      // the batch entry's B / raw_b_stride checks | tickets are required | no Y: the partials stay in scratch
+static int fused_decode(const char* who, const mila_fused_attn_args& a, int B, int64_t raw_b_stride, int flags, hipStream_t stream)
+{
+    MILA_REQUIRE((a.Y || (flags & FD_PARTIALS)) && a.Kc && a.Vc && a.q_raw && a.k_raw && a.v_raw && a.qw && a.kw && a.cos_cache && a.sin_cache &&
+                 (a.tickets || !(flags & FD_TICKETS)), "%s: null pointer", who);
+    if (flags & FD_BATCH)
     {
-        const size_t need = (size_t)B * NH * p.splits * (HS + 4) * sizeof(float);
-        if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
+        MILA_REQUIRE(B > 0 && a.NH > 0 && a.NKV > 0 && a.NH % a.NKV == 0, "%s: bad sizes (B=%d NH=%d NKV=%d)", who, B, a.NH, a.NKV);
+        MILA_REQUIRE(B == 1 || raw_b_stride >= (int64_t)a.NKV * a.HS, "%s: raw_b_stride %lld is shorter than a K row", who, (long long)raw_b_stride);
     }
-    return dispatch_hs<false>(HS, p, B, stream);
+    else
+        MILA_REQUIRE(a.NH > 0 && a.NKV > 0 && a.NH % a.NKV == 0, "%s: bad head counts (NH=%d NKV=%d)", who, a.NH, a.NKV);
+    MILA_REQUIRE(a.capacity > 0 && a.window >= 0 && (a.position_dev || a.position >= 0), "%s: bad sizes", who);
+    MILA_REQUIRE(a.HS % 16 == 0, "%s: HS=%d must be a multiple of 16", who, a.HS);
+    MILA_REQUIRE(a.warm_a_blocks >= 0 && a.warm_a_blocks <= 64 && a.warm_b_blocks >= 0 && a.warm_b_blocks <= 64, "%s: warm block counts must be in [0, 64]", who);
+    if (a.tickets)
+        MILA_REQUIRE(a.ticket_count >= mila_cdna4_attn_decode_ticket_count(1, a.NH), "%s: %zu tickets < required %zu", who, a.ticket_count,
+                     mila_cdna4_attn_decode_ticket_count(1, a.NH));
+    AttnParams p{};
+    p.Y = a.Y; p.K = a.Kc; p.V = a.Vc; p.scratch = reinterpret_cast<float*>(a.scratch);
+    p.NH = a.NH; p.NKV = a.NKV; p.capacity = a.capacity; p.position = a.position; p.pos_dev = a.position_dev; p.window = a.window; p.scale = a.scale;
+    p.q_raw = a.q_raw; p.k_raw = a.k_raw; p.v_raw = a.v_raw; p.raw_b_stride = raw_b_stride; p.qw = a.qw; p.kw = a.kw; p.vw = a.vw;
+    p.cos_cache = a.cos_cache; p.sin_cache = a.sin_cache; p.eps = a.eps;
+    p.tickets = a.tickets;
+    p.no_combine = (flags & FD_PARTIALS) ? 1 : 0;
+    if (a.warm_a && a.warm_a_bytes >= 128 && a.warm_a_blocks > 0) { p.warm_a = (const uint8_t*)a.warm_a; p.warm_a_lines = (int64_t)(a.warm_a_bytes / 128); p.warm_a_blocks = a.warm_a_blocks; }
+    if (a.warm_b && a.warm_b_bytes >= 128 && a.warm_b_blocks > 0) { p.warm_b = (const uint8_t*)a.warm_b; p.warm_b_lines = (int64_t)(a.warm_b_bytes / 128); p.warm_b_blocks = a.warm_b_blocks; p.warm_b_pair = (int64_t)a.warm_b_pair_offset; }
+    // under position_dev, `position` carries the live-length bound the launch is captured for (0 = the capacity)
+    const DecodePlan d = plan_decode(B, a.NH, a.NKV, a.HS, a.capacity, a.window, a.position_dev ? a.position : a.position + 1, true,
+                                     p.tickets || p.no_combine || p.warm_a || p.warm_b);
+    if (flags & FD_PARTIALS) MILA_REQUIRE(d.splits > 1, "%s: this (window, capacity) runs unsplit; use fused_attn_decode_bf16", who);
+    if (!a.position_dev)
+    {
+        const int len = a.position + 1, band = (a.window > 0 && a.window < len) ? a.window : len;
+        MILA_REQUIRE(band <= a.capacity, "%s: live band %d exceeds the cache capacity %d", who, band, a.capacity);
+    }
+    return run_decode(d, p, B, a.HS, a.scratch_bytes, who, stream);
+}
+static mila_fused_attn_args fused_args(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, const uint16_t* q_raw, const uint16_t* k_raw, const uint16_t* v_raw, const uint16_t* qw,
+                                       const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache, void* scratch, size_t scratch_bytes,
+                                       uint32_t* tickets, size_t ticket_count, int NH, int NKV, int HS, int capacity, int position, const int32_t* position_dev, int window,
+                                       float scale, float eps)
+{
+    return mila_fused_attn_args{Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, tickets, ticket_count, nullptr, 0, 0, nullptr, 0, 0, 0,
+                                NH, NKV, HS, capacity, position, position_dev, window, scale, eps};
 }
 
 // packed [B, T, 3C] rows -> K / V rows of a [B, NH, capacity, HS] cache at positions start_pos .. start_pos + T - 1 (the K / V part of the reference's
@@ -1043,14 +1089,14 @@ int mila_cdna4_kv_write_bf16(uint16_t* Kc, uint16_t* Vc, const uint16_t* k, cons
     MILA_LAUNCH_CHECK("kv_write_bf16");
 }
 
+// the largest scratch_need of the plans a (B, NH, HS) can take: kMaxSplits partials per head, or (HS 512) the MFMA decode's kMaxSplitsMfma + the roped q rows of its fused form
 size_t mila_cdna4_attn_decode_scratch_bytes(int B, int NH, int HS)
 {
     if (B <= 0 || NH <= 0 || HS <= 0) return 0;
-    const size_t scalar = (size_t)B * NH * kMaxSplits * (HS + 4) * sizeof(float);
-    // the long-context MFMA decode (HS 512): up to kMaxSplitsMfma partials per head + the roped q rows of its fused form
-    const size_t mfma = (HS == 512) ? (size_t)B * NH * kMaxSplitsMfma * (HS + 4) * sizeof(float) + (size_t)B * NH * HS * 2 : 0;
-    return scalar > mfma ? scalar : mfma;
+    return std::max(decode_scratch_bytes(B, NH, HS, kMaxSplits, false), HS == 512 ? decode_scratch_bytes(B, NH, HS, kMaxSplitsMfma, true) : 0);
 }
+
+int mila_cdna4_attn_decode_band_bucket(int len, int capacity) { return capacity > 0 ? band_bucket(len, capacity) : 0; }
 
 int mila_cdna4_attn_decode_bf16(uint16_t* Y, const uint16_t* Q, const uint16_t* Kc, const uint16_t* Vc, void* scratch,
                                 size_t scratch_bytes, int B, int NH, int NKV, int HS, int capacity, int len, int window,
@@ -1062,8 +1108,7 @@ int mila_cdna4_attn_decode_bf16(uint16_t* Y, const uint16_t* Q, const uint16_t* 
     MILA_REQUIRE(window >= 0, "attn_decode_bf16: negative window");
     const int band = (window > 0 && window < len) ? window : len;
     MILA_REQUIRE(band <= capacity, "attn_decode_bf16: live band %d exceeds the cache capacity %d", band, capacity);
-    return run_decode(Y, Q, const_cast<uint16_t*>(Kc), const_cast<uint16_t*>(Vc), scratch, scratch_bytes, B, NH, NKV, HS, capacity,
-                      len - 1, nullptr, window, scale, nullptr, "attn_decode_bf16", as_stream(stream));
+    return unfused_decode("attn_decode_bf16", Y, Q, 0, Kc, Vc, scratch, scratch_bytes, B, NH, NKV, HS, capacity, len - 1, nullptr, len, window, scale, as_stream(stream));
 }
 
 int mila_cdna4_attn_decode_bf16_devpos(uint16_t* Y, const uint16_t* Q, const uint16_t* Kc, const uint16_t* Vc, void* scratch,
@@ -1076,8 +1121,7 @@ int mila_cdna4_attn_decode_bf16_devpos(uint16_t* Y, const uint16_t* Q, const uin
     MILA_REQUIRE(max_len > 0 && capacity > 0 && window >= 0, "attn_decode_bf16_devpos: bad sizes");
     const int band = (window > 0 && window < max_len) ? window : max_len;
     MILA_REQUIRE(band <= capacity, "attn_decode_bf16_devpos: live band %d exceeds the cache capacity %d", band, capacity);
-    return run_decode(Y, Q, const_cast<uint16_t*>(Kc), const_cast<uint16_t*>(Vc), scratch, scratch_bytes, B, NH, NKV, HS, capacity, 0,
-                      position_dev, window, scale, nullptr, "attn_decode_bf16_devpos", as_stream(stream), max_len);
+    return unfused_decode("attn_decode_bf16_devpos", Y, Q, 0, Kc, Vc, scratch, scratch_bytes, B, NH, NKV, HS, capacity, 0, position_dev, max_len, window, scale, as_stream(stream));
 }
 
 // Fused decode attention for one token (B == 1): per-head q/k/v RMSNorm + RoPE + KV append + flash-decode.
@@ -1088,20 +1132,8 @@ int mila_cdna4_fused_attn_decode_bf16(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, c
                                       int NH, int NKV, int HS, int capacity, int position, const int32_t* position_dev,
                                       int window, float scale, float eps, mila_stream_t stream)
 {
-    MILA_REQUIRE(Y && Kc && Vc && q_raw && k_raw && v_raw && qw && kw && cos_cache && sin_cache, "fused_attn_decode_bf16: null pointer");
-    MILA_REQUIRE(NH > 0 && NKV > 0 && NH % NKV == 0, "fused_attn_decode_bf16: bad head counts (NH=%d NKV=%d)", NH, NKV);
-    MILA_REQUIRE(capacity > 0 && window >= 0 && (position_dev || position >= 0), "fused_attn_decode_bf16: bad sizes");
-    MILA_REQUIRE(HS % 16 == 0, "fused_attn_decode_bf16: HS=%d must be a multiple of 16", HS);
-    if (!position_dev)
-    {
-        const int len = position + 1, band = (window > 0 && window < len) ? window : len;
-        MILA_REQUIRE(band <= capacity, "fused_attn_decode_bf16: live band %d exceeds the cache capacity %d", band, capacity);
-    }
-    AttnParams f{};
-    f.q_raw = q_raw; f.k_raw = k_raw; f.v_raw = v_raw; f.qw = qw; f.kw = kw; f.vw = vw; f.cos_cache = cos_cache; f.sin_cache = sin_cache;
-    f.eps = eps;
-    return run_decode(Y, nullptr, Kc, Vc, scratch, scratch_bytes, 1, NH, NKV, HS, capacity, position, position_dev, window, scale, &f,
-                      "fused_attn_decode_bf16", as_stream(stream), position_dev ? position : 0);
+    return fused_decode("fused_attn_decode_bf16", fused_args(Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, nullptr, 0, NH, NKV, HS,
+                                                             capacity, position, position_dev, window, scale, eps), 1, 0, 0, as_stream(stream));
 }
 
 // The same launch for B rows decoded at one position (Gqa.Decode.Bf16.cu:379-387 takes the batch in its grid): batch row b reads its raw projections at
@@ -1112,23 +1144,9 @@ int mila_cdna4_fused_attn_decode_batch_bf16(uint16_t* Y, uint16_t* Kc, uint16_t*
                                             int NH, int NKV, int HS, int capacity, int position, const int32_t* position_dev,
                                             int window, float scale, float eps, mila_stream_t stream)
 {
-    MILA_REQUIRE(Y && Kc && Vc && q_raw && k_raw && v_raw && qw && kw && cos_cache && sin_cache, "fused_attn_decode_batch_bf16: null pointer");
-    MILA_REQUIRE(B > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "fused_attn_decode_batch_bf16: bad sizes (B=%d NH=%d NKV=%d)", B, NH, NKV);
-    MILA_REQUIRE(B == 1 || raw_b_stride >= (int64_t)NKV * HS, "fused_attn_decode_batch_bf16: raw_b_stride %lld is shorter than a K row", (long long)raw_b_stride);
-    MILA_REQUIRE(capacity > 0 && window >= 0 && (position_dev || position >= 0), "fused_attn_decode_batch_bf16: bad sizes");
-    MILA_REQUIRE(HS % 16 == 0, "fused_attn_decode_batch_bf16: HS=%d must be a multiple of 16", HS);
-    if (!position_dev)
-    {
-        const int len = position + 1, band = (window > 0 && window < len) ? window : len;
-        MILA_REQUIRE(band <= capacity, "fused_attn_decode_batch_bf16: live band %d exceeds the cache capacity %d", band, capacity);
-    }
-    AttnParams f{};
-    f.q_raw = q_raw; f.k_raw = k_raw; f.v_raw = v_raw; f.raw_b_stride = raw_b_stride; f.qw = qw; f.kw = kw; f.vw = vw; f.cos_cache = cos_cache; f.sin_cache = sin_cache;
-    f.eps = eps;
-    return run_decode(Y, nullptr, Kc, Vc, scratch, scratch_bytes, B, NH, NKV, HS, capacity, position, position_dev, window, scale, &f,
-                      "fused_attn_decode_batch_bf16", as_stream(stream), position_dev ? position : 0);
+    return fused_decode("fused_attn_decode_batch_bf16", fused_args(Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, nullptr, 0, NH, NKV,
+                                                                   HS, capacity, position, position_dev, window, scale, eps), B, raw_b_stride, FD_BATCH, as_stream(stream));
 }
-
 // ---- GPT-2 multi-head attention over a KV cache (CudaMhaOp.ixx:137-380: prefill / decode of IPositionalUnaryOp + IKvCacheLifecycle) ----
 // The cache is [B, NH, capacity, HS] like the GQA one (NKV = NH); K / V come from the packed [B, T, 3C] projection.
 int mila_cdna4_mha_kv_write_bf16(uint16_t* Kc, uint16_t* Vc, const uint16_t* QKV, int B, int T, int C, int NH, int start_pos, int capacity,
@@ -1162,15 +1180,16 @@ int mila_cdna4_mha_decode_bf16(uint16_t* Y, const uint16_t* QKV, uint16_t* Kc, u
     const int HS = C / NH;
     int rc = mila_cdna4_mha_kv_write_bf16(Kc, Vc, QKV, B, 1, C, NH, position, capacity, stream);
     if (rc) return rc;
-    return run_decode_q(Y, QKV, 3 * (int64_t)C, Kc, Vc, scratch, scratch_bytes, B, NH, NH, HS, capacity, position, 0, 1.0f / sqrtf((float)HS),
-                        "mha_decode_bf16", as_stream(stream));
+    // the query rows of a packed [B, 1, 3C] projection are 3C elements apart; the geometry is the capacity's (len_hint 0)
+    return unfused_decode("mha_decode_bf16", Y, QKV, 3 * (int64_t)C, Kc, Vc, scratch, scratch_bytes, B, NH, NH, HS, capacity, position, nullptr, 0, 0, 1.0f / sqrtf((float)HS),
+                          as_stream(stream));
 }
 
-int mila_cdna4_attn_decode_split_count(int B, int NH, int NKV, int HS, int capacity, int window)
+// the `splits` of the plan fused_attn_decode_partials_bf16 runs for this shape and len_hint (as in plan_decode: position + 1 of an eager call, 0 = the capacity)
+int mila_cdna4_attn_decode_split_count(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint)
 {
     if (B <= 0 || NH <= 0 || NKV <= 0 || NH % NKV != 0 || capacity <= 0 || window < 0) return 0;
-    const int band_max = (window > 0 && window < capacity) ? window : capacity;
-    return decode_splits(B, NH, NKV, HS, band_max);
+    return plan_decode(B, NH, NKV, HS, capacity, window, len_hint, true, true).splits;
 }
 
 int mila_cdna4_fused_attn_decode_partials_bf16(uint16_t* Kc, uint16_t* Vc, const uint16_t* q_raw, const uint16_t* k_raw,
@@ -1179,23 +1198,8 @@ int mila_cdna4_fused_attn_decode_partials_bf16(uint16_t* Kc, uint16_t* Vc, const
                                                int NH, int NKV, int HS, int capacity, int position, const int32_t* position_dev,
                                                int window, float scale, float eps, mila_stream_t stream)
 {
-    MILA_REQUIRE(Kc && Vc && q_raw && k_raw && v_raw && qw && kw && cos_cache && sin_cache, "fused_attn_decode_partials_bf16: null pointer");
-    MILA_REQUIRE(NH > 0 && NKV > 0 && NH % NKV == 0, "fused_attn_decode_partials_bf16: bad head counts (NH=%d NKV=%d)", NH, NKV);
-    MILA_REQUIRE(capacity > 0 && window >= 0 && (position_dev || position >= 0), "fused_attn_decode_partials_bf16: bad sizes");
-    MILA_REQUIRE(HS % 16 == 0, "fused_attn_decode_partials_bf16: HS=%d must be a multiple of 16", HS);
-    MILA_REQUIRE(mila_cdna4_attn_decode_split_count(1, NH, NKV, HS, capacity, window) > 1,
-                 "fused_attn_decode_partials_bf16: this (window, capacity) runs unsplit; use fused_attn_decode_bf16");
-    if (!position_dev)
-    {
-        const int len = position + 1, band = (window > 0 && window < len) ? window : len;
-        MILA_REQUIRE(band <= capacity, "fused_attn_decode_partials_bf16: live band %d exceeds the cache capacity %d", band, capacity);
-    }
-    AttnParams f{};
-    f.q_raw = q_raw; f.k_raw = k_raw; f.v_raw = v_raw; f.qw = qw; f.kw = kw; f.vw = vw; f.cos_cache = cos_cache; f.sin_cache = sin_cache;
-    f.eps = eps;
-    f.no_combine = 1;
-    return run_decode(nullptr, nullptr, Kc, Vc, scratch, scratch_bytes, 1, NH, NKV, HS, capacity, position, position_dev, window, scale, &f,
-                      "fused_attn_decode_partials_bf16", as_stream(stream));
+    return fused_decode("fused_attn_decode_partials_bf16", fused_args(nullptr, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, nullptr, 0,
+                                                                      NH, NKV, HS, capacity, position, position_dev, window, scale, eps), 1, 0, FD_PARTIALS, as_stream(stream));
 }
 
 size_t mila_cdna4_attn_decode_ticket_count(int B, int NH)
@@ -1213,50 +1217,25 @@ int mila_cdna4_fused_attn_decode_onepass_bf16(uint16_t* Y, uint16_t* Kc, uint16_
                                               uint32_t* tickets, size_t ticket_count, int NH, int NKV, int HS, int capacity, int position,
                                               const int32_t* position_dev, int window, float scale, float eps, mila_stream_t stream)
 {
-    MILA_REQUIRE(Y && Kc && Vc && q_raw && k_raw && v_raw && qw && kw && cos_cache && sin_cache && tickets, "fused_attn_decode_onepass_bf16: null pointer");
-    MILA_REQUIRE(NH > 0 && NKV > 0 && NH % NKV == 0, "fused_attn_decode_onepass_bf16: bad head counts (NH=%d NKV=%d)", NH, NKV);
-    MILA_REQUIRE(capacity > 0 && window >= 0 && (position_dev || position >= 0), "fused_attn_decode_onepass_bf16: bad sizes");
-    MILA_REQUIRE(HS % 16 == 0, "fused_attn_decode_onepass_bf16: HS=%d must be a multiple of 16", HS);
-    MILA_REQUIRE(ticket_count >= mila_cdna4_attn_decode_ticket_count(1, NH), "fused_attn_decode_onepass_bf16: %zu tickets < required %zu",
-                 ticket_count, mila_cdna4_attn_decode_ticket_count(1, NH));
-    if (!position_dev)
-    {
-        const int len = position + 1, band = (window > 0 && window < len) ? window : len;
-        MILA_REQUIRE(band <= capacity, "fused_attn_decode_onepass_bf16: live band %d exceeds the cache capacity %d", band, capacity);
-    }
-    AttnParams f{};
-    f.q_raw = q_raw; f.k_raw = k_raw; f.v_raw = v_raw; f.qw = qw; f.kw = kw; f.vw = vw; f.cos_cache = cos_cache; f.sin_cache = sin_cache;
-    f.eps = eps;
-    f.tickets = tickets;
-    return run_decode(Y, nullptr, Kc, Vc, scratch, scratch_bytes, 1, NH, NKV, HS, capacity, position, position_dev, window, scale, &f,
-                      "fused_attn_decode_onepass_bf16", as_stream(stream));
+    return fused_decode("fused_attn_decode_onepass_bf16", fused_args(Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, tickets, ticket_count,
+                                                                     NH, NKV, HS, capacity, position, position_dev, window, scale, eps), 1, 0, FD_TICKETS, as_stream(stream));
 }
 
 // fused_attn_decode_bf16 (or, with tickets, fused_attn_decode_onepass_bf16) from an argument block, with optional warm ranges
 int mila_cdna4_fused_attn_decode_ex(const mila_fused_attn_args* a, mila_stream_t stream)
 {
     MILA_REQUIRE(a != nullptr, "fused_attn_decode_ex: null arguments");
-    MILA_REQUIRE(a->Y && a->Kc && a->Vc && a->q_raw && a->k_raw && a->v_raw && a->qw && a->kw && a->cos_cache && a->sin_cache, "fused_attn_decode_ex: null pointer");
-    MILA_REQUIRE(a->NH > 0 && a->NKV > 0 && a->NH % a->NKV == 0, "fused_attn_decode_ex: bad head counts (NH=%d NKV=%d)", a->NH, a->NKV);
-    MILA_REQUIRE(a->capacity > 0 && a->window >= 0 && (a->position_dev || a->position >= 0), "fused_attn_decode_ex: bad sizes");
-    MILA_REQUIRE(a->HS % 16 == 0, "fused_attn_decode_ex: HS=%d must be a multiple of 16", a->HS);
-    MILA_REQUIRE(a->warm_a_blocks >= 0 && a->warm_a_blocks <= 64 && a->warm_b_blocks >= 0 && a->warm_b_blocks <= 64, "fused_attn_decode_ex: warm block counts must be in [0, 64]");
-    if (a->tickets)
-        MILA_REQUIRE(a->ticket_count >= mila_cdna4_attn_decode_ticket_count(1, a->NH), "fused_attn_decode_ex: %zu tickets < required %zu",
-                     a->ticket_count, mila_cdna4_attn_decode_ticket_count(1, a->NH));
-    if (!a->position_dev)
-    {
-        const int len = a->position + 1, band = (a->window > 0 && a->window < len) ? a->window : len;
-        MILA_REQUIRE(band <= a->capacity, "fused_attn_decode_ex: live band %d exceeds the cache capacity %d", band, a->capacity);
-    }
-    AttnParams f{};
-    f.q_raw = a->q_raw; f.k_raw = a->k_raw; f.v_raw = a->v_raw; f.qw = a->qw; f.kw = a->kw; f.vw = a->vw; f.cos_cache = a->cos_cache; f.sin_cache = a->sin_cache;
-    f.eps = a->eps;
-    f.tickets = a->tickets;
-    if (a->warm_a && a->warm_a_bytes >= 128 && a->warm_a_blocks > 0) { f.warm_a = (const uint8_t*)a->warm_a; f.warm_a_lines = (int64_t)(a->warm_a_bytes / 128); f.warm_a_blocks = a->warm_a_blocks; }
-    if (a->warm_b && a->warm_b_bytes >= 128 && a->warm_b_blocks > 0) { f.warm_b = (const uint8_t*)a->warm_b; f.warm_b_lines = (int64_t)(a->warm_b_bytes / 128); f.warm_b_blocks = a->warm_b_blocks; f.warm_b_pair = (int64_t)a->warm_b_pair_offset; }
-    return run_decode(a->Y, nullptr, a->Kc, a->Vc, a->scratch, a->scratch_bytes, 1, a->NH, a->NKV, a->HS, a->capacity, a->position, a->position_dev, a->window,
-                      a->scale, &f, "fused_attn_decode_ex", as_stream(stream));
+    return fused_decode("fused_attn_decode_ex", *a, 1, 0, 0, as_stream(stream));
+}
+
+size_t mila_cdna4_attn_decode_plan_describe(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, int fused, int hooks, char* buf, size_t cap)
+{
+    if (buf && cap) buf[0] = 0;
+    if (B <= 0 || NH <= 0 || NKV <= 0 || NH % NKV != 0 || HS <= 0 || capacity <= 0 || window < 0) return 0;
+    const DecodePlan d = plan_decode(B, NH, NKV, HS, capacity, window, len_hint, fused != 0, hooks != 0);
+    static const char* const names[] = {"attn_decode", "attn_decode_mfma", "attn_generic"};
+    return 1 + snprintf(buf, buf ? cap : 0, "%s:%d:%d:%d:%d:%d:%d:%zu:%zu", names[d.form], d.splits, d.band_max, d.gh, d.hgroups, d.flat, (int)d.prologue, d.partial_floats,
+                        d.scratch_need);
 }
 
 }  // extern "C"

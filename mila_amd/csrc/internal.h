@@ -23,6 +23,10 @@ MILA_API size_t mila_cdna4_last_form(char* buf, size_t cap);
  * 2 = gemm_geglu_bf16 (N = F), 3 = gemm_fp8_scaled, 4 = gemm_fp8_scaled_ws (and the W8A8 / scratch forms), 5 = gemm_geglu_fp8_scaled (N = F).  Writes
  * "form:row0:rows:col0:cols:S" items joined by '+' (one kernel-form launch per rectangle of the output; S > 0: split-K copies), the column-split marker, all zeros, first. */
 MILA_API size_t mila_cdna4_gemm_plan_describe(int entry, int M, int K, int N, char* buf, size_t cap);
+/* the decode-attention plan (csrc/attention.hip: plan_decode) of a shape as text, without running device code: len_hint = the live-length bound the launch is for (0 = the
+ * capacity), fused = a fused entry, hooks = the entry uses tickets, no_combine or warm ranges.  Writes "form:splits:band_max:heads_per_group:head_groups:flat:prologue:
+ * partial_floats:scratch_need" (form: attn_decode | attn_decode_mfma | attn_generic); returns the text's size, 0 for a bad shape. */
+MILA_API size_t mila_cdna4_attn_decode_plan_describe(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, int fused, int hooks, char* buf, size_t cap);
 /* The names (tune_list prints them with their values and defaults; each is documented where it is registered):
  *   matvec.rows_per_wave, matvec.chunks_in_flight, matvec.max_workgroups                 0 = the default rule                                         (csrc/matvec.hip)
  *   gemm.force128          1 = always the 128 x 128 register-staged GEMM (A/B against the LDS-DMA kernels)                                           (csrc/gemm_plan.hip)
@@ -71,8 +75,10 @@ MILA_API int mila_cdna4_stream_read(float* sink, const void* src, size_t bytes, 
  * partials in its prologue, element for element the arithmetic of the combine launch, so
  *   fused_attn_decode_partials + matvec_attn_combine  ==  fused_attn_decode + matvec_bf16[_qfp8|_qfp4]   bit for bit,
  * one launch fewer.  Every workgroup re-reads all partials from L2, so callers use it while NH * splits * (HS + 4) * 4 bytes
- * stays small (Gemma sliding-window layers: 266 KB); attn_decode_split_count() gives `splits` for a (window, capacity). */
-MILA_API int mila_cdna4_attn_decode_split_count(int B, int NH, int NKV, int HS, int capacity, int window);
+ * stays small (Gemma sliding-window layers: 266 KB); attn_decode_split_count() gives the `splits` of the launch: len_hint is
+ * position + 1 of an eager call, the `position` passed beside a position_dev, 0 = the capacity (an unwindowed layer's geometry follows
+ * the live-length bucket, mila_cdna4_attn_decode_band_bucket). */
+MILA_API int mila_cdna4_attn_decode_split_count(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint);
 MILA_API int mila_cdna4_fused_attn_decode_partials_bf16(uint16_t* Kc, uint16_t* Vc, const uint16_t* q_raw,
                                                         const uint16_t* k_raw, const uint16_t* v_raw,
                                                         const uint16_t* qw, const uint16_t* kw, const uint16_t* vw,

@@ -241,20 +241,18 @@ namespace Mila::Dnn
         }
         /// capture on first use, and again whenever the captured graph no longer matches what a replay must do: another token
         /// buffer, or a different sampler setting (a graph captured without the sampler node never writes the next token)
-        /// ... or a position outside the band bucket the attention launches were captured for (csrc/attention.hip: band_bucket -- 4096, 8192, 16384, ... keys: an unwindowed
-        /// layer's split geometry and kernel form follow the live length bucket, not the cache capacity).  Cheap: callers invoke it before every replay.
+        /// ... or a position in another band bucket than the attention launches were captured for (an unwindowed layer's split geometry and kernel form follow the live-length
+        /// bucket -- 4096, 8192, 16384, ... keys, clipped to the capacity -- not the cache capacity).  Cheap: callers invoke it before every replay.
         void ensureGraph( const TokenTensor& token, dim_t start_position )
         {
             if ( !graph_exec_ || captured_token_ != token.data() || captured_sample_in_graph_ != sample_in_graph_ || captured_ring_ != token_ring_ ||
-                 start_position + 1 > captured_band_end_ || ( start_position + 1 <= captured_band_end_ / 2 && captured_band_end_ > 4096 ) )
+                 bandBucket( start_position ) != captured_band_end_ )
                 captureGraph( token, start_position );
         }
-        /// the live-length bucket of a position (the rule of csrc/attention.hip: band_bucket)
+        /// the live-length bucket of a position, asked of the device library whose launches follow it
         dim_t bandBucket( dim_t position ) const
         {
-            dim_t b = 4096;
-            while ( b < position + 1 && b < max_seq_ ) b <<= 1;
-            return std::min( b, max_seq_ );
+            return mila_cdna4_attn_decode_band_bucket( static_cast<int>( position + 1 ), static_cast<int>( max_seq_ ) );
         }
         bool graphCaptured() const noexcept { return graph_exec_ != nullptr; }
         /// kernel nodes of the captured decode step (0 before a capture): the launches one token costs on the graph path

@@ -6,6 +6,10 @@ uniform(-1,1) data (:61-75,:611), this build's is <= 1 bf16 ulp + 2e-3 abs vs fl
 Dead zones of the cache are poisoned with NaN (the reference's out-of-tree harness does the same,
 Docs/Discussions/DecodePerformanceCampaign.md:95-106): a kernel that touches a row outside the live
 band produces NaN and fails."""
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -17,6 +21,11 @@ from mila_amd import capi
 pytestmark = pytest.mark.gpu
 
 NAN_BITS = 0x7fc0
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("attn_decode_plan_fixtures", os.path.join(ROOT, "tools", "attn_decode_plan_fixtures.py"))
+plan_fixtures = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(plan_fixtures)
+PLAN_BITS = json.load(open(os.path.join(ROOT, "tests", "golden", "attn_decode_plan_bits.json")))
 
 
 def _bf(x):
@@ -209,3 +218,23 @@ def test_mha_packed_qkv_vs_reference_cpu_op(B, T, Cm, NH):
     assert_bf16_close(bits(Y), exp, 1, 2e-3, "mha")
     got = orc.from_bf16_bits(bits(Y)).reshape(exp.shape)
     assert np.abs(got - exp).max() <= 3e-2          # the reference's BF16 attention bar
+
+
+@pytest.mark.parametrize("setting,geometry", sorted({(st, c[:4]) for st, c in plan_fixtures.bit_cases()}))
+def test_decode_entries_run_the_forms_and_give_the_bits_of_the_recorded_build(setting, geometry):
+    """parity with the build tests/golden/attn_decode_plan_bits.json was recorded from (tools/attn_decode_plan_fixtures.py bits, on an MI355X, BEFORE the decode dispatch
+    became plan_decode): attn_decode_bf16, fused_attn_decode_[batch_]bf16 and mha_decode_bf16 on the tool's seeded inputs note the same kernel forms, write the same
+    output bits and leave the same scratch -- the split partials, so the same split count launch for launch.  Scalar-kernel and generic head sizes at every position class
+    of a 512-row cache, both sides of the 4096-key bucket edge of an 8300-row cache (also at 128 positions per split: 32 and 64 splits), and the matrix-core decode"""
+    cases = [c for st, c in plan_fixtures.bit_cases() if st == setting and c[:4] == geometry]
+    assert cases and set(PLAN_BITS[setting]) >= {plan_fixtures.case_key(c) for c in cases}
+    try:
+        plan_fixtures.apply_setting(setting)
+        diff = []
+        for c in cases:
+            got, want = plan_fixtures.run_bit_case(c), PLAN_BITS[setting][plan_fixtures.case_key(c)]
+            assert sorted(got) == sorted(want), (c, sorted(got), sorted(want))
+            diff += [(c, e, got[e][0], want[e][0]) for e in want if got[e] != want[e]]
+        assert not diff, "%d entries differ from the recorded build, first: %s" % (len(diff), diff[:4])
+    finally:
+        capi.tune_reset()

@@ -371,11 +371,27 @@ def test_tail_norm_with_per_token_fp8_output_equals_tail_norm_then_quantize(D):
 def test_attention_partials_plus_combining_o_proj_equals_attention_plus_o_proj(NH, NKV, HS, rot, base, window, kv_shared, cap, fmt, pos):
     """flash-decode without its combine launch + an o_proj whose prologue combines the split partials == the two-launch
     attention + the plain o_proj Linear, bit for bit (cache rows too)"""
-    pos = min(pos, cap - 1)
+    _partials_plus_combining_o_proj(NH, NKV, HS, rot, base, window, kv_shared, cap, fmt, min(pos, cap - 1), 0)
+
+
+def test_attention_partials_are_sized_by_the_live_length_bucket_the_launch_uses():
+    """ADVICE r04 finding 3: on a cache deeper than 4096 rows the launch follows the live-length bucket, and attn_decode_split_count(..., len_hint = position + 1) is the
+    split count of THAT launch -- with 128 positions per split, 32 at position 100 of an 8192-row cache where the capacity alone says 64 -- so the combining o_proj
+    merges exactly the partials that were written"""
+    lib = capi.load()
+    try:
+        capi.tune("attn.positions_per_split", 128)
+        assert lib.mila_cdna4_attn_decode_split_count(1, 8, 2, 256, 8192, 0, 101) == 32 and lib.mila_cdna4_attn_decode_split_count(1, 8, 2, 256, 8192, 0, 0) == 64
+        _partials_plus_combining_o_proj(8, 2, 256, 0, 1e4, 0, False, 8192, 0, 100, 101)
+    finally:
+        capi.tune_reset()
+
+
+def _partials_plus_combining_o_proj(NH, NKV, HS, rot, base, window, kv_shared, cap, fmt, pos, len_hint):
     rng = np.random.default_rng(HS + NKV + pos + fmt)
     max_seq, D = 2048, 520
     lib = capi.load()
-    splits = lib.mila_cdna4_attn_decode_split_count(1, NH, NKV, HS, cap, window)
+    splits = lib.mila_cdna4_attn_decode_split_count(1, NH, NKV, HS, cap, window, len_hint)
     assert splits > 1
     Kc0 = torch.from_numpy(orc.to_bf16_bits(rng.uniform(-1, 1, (1, NKV, cap, HS)).astype(np.float32) * 0.5).view(np.int16)).cuda()
     Vc0 = torch.from_numpy(orc.to_bf16_bits(rng.uniform(-1, 1, (1, NKV, cap, HS)).astype(np.float32)).view(np.int16)).cuda()
@@ -401,6 +417,14 @@ def test_attention_partials_plus_combining_o_proj_equals_attention_plus_o_proj(N
     capi.call("matvec_attn_combine", y1, scratch, splits, NH, HS, W, s, fmt, D, 128)
     assert np.array_equal(bits(K1), bits(K0)) and np.array_equal(bits(V1), bits(V0)), "cache rows differ"
     assert np.array_equal(bits(y1), bits(y0)), "o_proj output differs"
+    # the same with the position on the device: `position` then carries the live-length bound the split count was asked for
+    K2, V2, y2 = Kc0.clone(), Vc0.clone(), empty_u16(D)
+    scratch.zero_()
+    pd = torch.tensor([pos], dtype=torch.int32, device="cuda")
+    capi.call("fused_attn_decode_partials_bf16", K2, V2, _d(q), _d(k), _d(v), qw, kw, None, cos, sin, scratch, C.c_size_t(nbytes), NH, NKV, HS,
+              cap, len_hint, pd, window, 1.0, 1e-6)
+    capi.call("matvec_attn_combine", y2, scratch, splits, NH, HS, W, s, fmt, D, 128)
+    assert np.array_equal(bits(K2), bits(K0)) and np.array_equal(bits(y2), bits(y0)), "device-position form differs"
 
 
 @pytest.mark.parametrize("NH,NKV,HS,rot,base,window,kv_shared,cap", [(16, 8, 256, 0, 1e4, 1024, False, 2048), (16, 1, 512, 128, 1e6, 0, True, 2048),
@@ -410,11 +434,24 @@ def test_onepass_attention_equals_attention_plus_combine(NH, NKV, HS, rot, base,
     """split flash-decode whose last-arriving workgroup merges its head-group's partials in the same launch == attention + combine
     launches, bit for bit, call after call on the SAME scratch with changing queries (a stale partial from the previous call, or
     a ticket left armed, would show), while another stream keeps the memory system busy"""
-    pos = min(pos, cap - 1)
+    _onepass_equals_attention_plus_combine(NH, NKV, HS, rot, base, window, kv_shared, cap, min(pos, cap - 1), 0)
+
+
+def test_onepass_attention_follows_the_live_length_bucket_in_both_position_forms():
+    """the ADVICE r04 finding 3 case of the partials test: the one-pass form, eager and with the position on the device (`position` then carries the live-length bound),
+    is shaped for the bucket like fused_attn_decode_bf16"""
+    try:
+        capi.tune("attn.positions_per_split", 128)
+        _onepass_equals_attention_plus_combine(8, 2, 256, 0, 1e4, 0, False, 8192, 100, 101)
+    finally:
+        capi.tune_reset()
+
+
+def _onepass_equals_attention_plus_combine(NH, NKV, HS, rot, base, window, kv_shared, cap, pos, len_hint):
     rng = np.random.default_rng(7 * HS + NKV + pos)
     max_seq = 2048
     lib = capi.load()
-    splits = lib.mila_cdna4_attn_decode_split_count(1, NH, NKV, HS, cap, window)
+    splits = lib.mila_cdna4_attn_decode_split_count(1, NH, NKV, HS, cap, window, len_hint)
     assert splits > 1
     Kc0 = torch.from_numpy(orc.to_bf16_bits(rng.uniform(-1, 1, (1, NKV, cap, HS)).astype(np.float32) * 0.5).view(np.int16)).cuda()
     Vc0 = torch.from_numpy(orc.to_bf16_bits(rng.uniform(-1, 1, (1, NKV, cap, HS)).astype(np.float32)).view(np.int16)).cuda()
@@ -457,7 +494,7 @@ def test_onepass_attention_equals_attention_plus_combine(NH, NKV, HS, rot, base,
     pd = torch.tensor([pos], dtype=torch.int32, device="cuda")
     y2 = empty_u16(NH * HS)
     capi.call("fused_attn_decode_onepass_bf16", y2, K1, V1, qs[-1], ks[-1], vs[-1], qw, kw, None, cos, sin, scratch1, C.c_size_t(nbytes),
-              tickets, C.c_size_t(nt), NH, NKV, HS, cap, 0, pd, window, 1.0, 1e-6)
+              tickets, C.c_size_t(nt), NH, NKV, HS, cap, len_hint, pd, window, 1.0, 1e-6)
     assert np.array_equal(bits(y2), bits(y0[-1]))
     with pytest.raises(capi.InvalidArgument):
         capi.call("fused_attn_decode_onepass_bf16", y2, K1, V1, qs[0], ks[0], vs[0], qw, kw, None, cos, sin, scratch1, C.c_size_t(nbytes),

@@ -582,6 +582,33 @@ def test_decode_across_a_live_length_bucket_re_captures_the_graph_and_keeps_the_
         g.close()
 
 
+def test_a_rewind_into_a_lower_bucket_of_a_capacity_that_is_no_power_of_two_re_captures_the_graph():
+    """ADVICE r04 finding 1: with max_seq 12000 the buckets are 4096, 8192, 12000.  A graph captured at position 9000 (bucket 12000) and rewound to 7000 (bucket 8192, which
+    eager launches use: other split counts) must be captured again -- the host asks the device library for the bucket (mila_cdna4_attn_decode_band_bucket) instead of
+    guessing 'half the captured end' -- and reference-order, fused and graph logits stay bit-identical at every step.  A capture goes through the entry points, so it
+    notes kernel forms (mila_cdna4_last_form); a replay launches the graph and notes none."""
+    from mila_amd import capi
+    cfg = dict(vocab_size=1024, embedding_dim=256, num_layers=2, num_heads=16, num_kv_heads=8, head_dim=64, hidden_dim=512,
+               global_head_dim=512, num_global_kv_heads=1, window=8, sliding_window_pattern=2, global_rotary_dim=128)
+    max_seq, start, back = 12000, 9000, 7000
+    toks = [(7 * i + 3) % 1024 for i in range(start + 2)]
+    models = {m: host.Gemma("bf16", cfg, max_seq=max_seq, max_prefill=1024, seed=11) for m in ("reference", "fused", "graph")}
+    for g in models.values():
+        for o in range(0, start, 1024):
+            g.prefill(toks[o:min(o + 1024, start)], o)
+    captured = []
+    for pos in (start, start + 1, back, back + 1):
+        out = {m: models[m].decode(toks[pos], pos, m) for m in ("reference", "fused")}
+        capi.last_form()
+        out["graph"] = models["graph"].decode(toks[pos], pos, "graph")
+        captured.append(bool(capi.last_form()))
+        for m in ("fused", "graph"):
+            assert np.array_equal(out["reference"].view(np.uint32), out[m].view(np.uint32)), "%s != reference-order at %d" % (m, pos)
+    assert captured == [True, False, True, False], captured
+    for g in models.values():
+        g.close()
+
+
 @pytest.mark.parametrize("cfg_name,T", [("MEDIUM", 24), ("WIDE_FFN", 1024)])
 def test_w8a8_opt_in_prefill_of_the_fp8_policy(cfg_name, T):
     """PerChannelFp8<> with setFp8ActivationPrefill(true) (row g1; Policies.ixx:39-40): every layer Linear of a T > 1 forward runs fp8 x fp8 on the policy's own e4m3
