@@ -271,6 +271,32 @@ MILA_API int mila_cdna4_mha_decode_bf16(uint16_t* Y, const uint16_t* QKV, uint16
                                         mila_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Grouped-query attention over an FP8 KV cache: the PerChannelKvFp8<> policy (Quantization/KvCache/QuantPolicy.ixx:56-88: e4m3 storage of K and V, one fp32
+ * scale per KV head per cached token, absmax / 448, dequantized to transient BF16 -- "never written back"; the reference declares the policy and has no kernels
+ * for it, BACKLOG.md "Future": OperationTraits<GqaOp, Cuda, BF16, PerChannelKvFp8<>>).  Launch shapes follow the bf16 entries above (Attention/GQA/Kernels/CudaGqa.cuh).
+ *   cache   K8, V8 [B, NKV, capacity, HS] uint8 (e4m3) + Ks, Vs [B, NKV, capacity] fp32; row = abs_pos % capacity.  HS in {64, 128, 256, 512}.
+ *   kv_write_fp8: quantizing append of k / v [B, chunk, NKV*HS] at rows (start_pos + t) % capacity -- each K / V row of one (batch, token, KV head) exactly as
+ *     quantize_fp8_per_channel quantizes one weight row: bit-identical bytes and scales.  chunk <= capacity (QuantPolicy.ixx:56-88; CudaGqa.cuh: cuda_kvcache_write_kv_bf16).
+ *   A cached value is bf16_rne(float(e4m3) * scale) -- the bits dequantize_to_bf16 (fp8) produces.  The attention arithmetic on those values is the bf16 cache's.
+ *   attn_decode_kvfp8: attn_decode_bf16 over this cache (CudaGqa.cuh: cuda_gqa_decode_attention_bf16): values dequantized in registers; the split count of
+ *     attn_decode_bf16's scalar kernel for the shape; scratch from attn_decode_scratch_bytes(B, NH, HS).
+ *   kv_dequant_fp8_bf16: cache rows of positions [first_pos, first_pos + count) -> the same rows of bf16 caches [B, NKV, capacity, HS]; other rows are not written.
+ *   attn_prefill_kvfp8: attn_prefill_bf16 over this cache (CudaGqa.cuh flash-prefill launchers): the chunk's band [max(0, pos_offset - window + 1), pos_offset + chunk)
+ *     (from 0 when unwindowed; extended down to the 32-key tile boundary the flash kernels start streaming from) is dequantized into two transient bf16 caches in
+ *     `scratch` (attn_prefill_kvfp8_scratch_bytes, 16-byte aligned), then the bf16 kernels run on them.  The cache must already contain the chunk (kv_write_fp8 first).
+ * ------------------------------------------------------------------------------------------- */
+MILA_API int mila_cdna4_kv_write_fp8(uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* k, const uint16_t* v, int B, int chunk, int NKV, int HS,
+                                     int start_pos, int capacity, mila_stream_t stream);
+MILA_API int mila_cdna4_attn_decode_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch,
+                                          size_t scratch_bytes, int B, int NH, int NKV, int HS, int capacity, int len, int window, float scale, mila_stream_t stream);
+MILA_API int mila_cdna4_kv_dequant_fp8_bf16(uint16_t* Kc_bf16, uint16_t* Vc_bf16, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, int B, int NKV,
+                                            int HS, int capacity, int first_pos, int count, mila_stream_t stream);
+MILA_API size_t mila_cdna4_attn_prefill_kvfp8_scratch_bytes(int B, int NKV, int HS, int capacity);
+MILA_API int mila_cdna4_attn_prefill_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch,
+                                           size_t scratch_bytes, int B, int chunk, int NH, int NKV, int HS, int capacity, int pos_offset, int window, float scale,
+                                           mila_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Normalisation / activations.
  * rmsnorm: y = x * rsqrt(mean(x^2) + eps) * (w + w_offset) + b over `dim` strided by `inner`;
  *   rstd (bf16, may be NULL) gets one value per slice.  replaces

@@ -81,6 +81,14 @@ def load():
     main.mila_cdna4_sample_stochastic_scratch_bytes.restype = C.c_size_t
     main.mila_cdna4_attn_decode_ticket_count.restype = C.c_size_t
     main.mila_cdna4_mha_decode_scratch_bytes.restype = C.c_size_t
+    # the FP8 KV cache (PerChannelKvFp8<>, csrc/attention_kvfp8.hip): K8 / V8 [B, NKV, capacity, HS] e4m3 + Ks / Vs [B, NKV, capacity] fp32
+    p, i, f, z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+    main.mila_cdna4_kv_write_fp8.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                               # K8 V8 Ks Vs k v | B chunk NKV HS start_pos capacity | stream
+    main.mila_cdna4_attn_decode_kvfp8.argtypes = [p, p, p, p, p, p, p, z, i, i, i, i, i, i, i, f, p]              # Y Q K8 V8 Ks Vs scratch bytes | B NH NKV HS capacity len window | scale
+    main.mila_cdna4_kv_dequant_fp8_bf16.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                        # Kc Vc K8 V8 Ks Vs | B NKV HS capacity first_pos count
+    main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.argtypes = [i, i, i, i]                                      # B NKV HS capacity
+    main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.restype = z
+    main.mila_cdna4_attn_prefill_kvfp8.argtypes = [p, p, p, p, p, p, p, z, i, i, i, i, i, i, i, i, f, p]          # Y Q K8 V8 Ks Vs scratch bytes | B chunk NH NKV HS capacity pos_offset window | scale
     _lib = _Libs(main)
     return _lib
 
@@ -215,6 +223,7 @@ EXPORTED = [
     "attn_decode_band_bucket", "dequantize_to_bf16", "gemm_geglu_fp8_scaled",
     "gemm_fp8_w8a8_ws", "gemm_geglu_fp8_w8a8", "gemm_w8a8_scratch_bytes", "gemm_bf16_w8a8", "gemm_geglu_bf16_w8a8",
     "matvec_fp32", "gemm_fp32", "mha_fp32", "mha_kv_write_fp32", "mha_decode_fp32", "lpe_fp32", "rope_forward_fp32",
+    "kv_write_fp8", "attn_decode_kvfp8", "kv_dequant_fp8_bf16", "attn_prefill_kvfp8_scratch_bytes", "attn_prefill_kvfp8",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

@@ -24,6 +24,7 @@
 #include "internal.h"
 #include "attention_generic.h"
 #include "attention_tiles.h"
+#include "attention_decode_plan.h"
 
 namespace mila {
 
@@ -827,7 +828,8 @@ static size_t decode_scratch_bytes(int B, int NH, int HS, int splits, bool q_row
 // len_hint: an upper bound on the live length the launch is for -- position + 1 in the eager forms; in the device-position forms what the caller captured the graph for;
 // 0 = the capacity.  The split count depends only on (window, band bucket), never on the current length inside a bucket, so that eager launches and a graph captured
 // once reduce in the same order: bit-identical.  hooks: the entry uses tickets, no_combine or warm ranges, which address the 3-D grid of the scalar kernel.
-static DecodePlan plan_decode(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, bool fused, bool hooks)
+// scalar_only: the caller has no matrix-core form (the fp8 KV cache, attention_kvfp8.hip): the scalar form's plan for the same shape.
+static DecodePlan plan_decode(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, bool fused, bool hooks, bool scalar_only = false)
 {
     DecodePlan d{};
     const int GS = NH / NKV;
@@ -835,7 +837,7 @@ static DecodePlan plan_decode(int B, int NH, int NKV, int HS, int capacity, int 
     d.band_max = (window > 0 && window < capacity) ? window : (len_hint > 0 ? band_bucket(len_hint, capacity) : capacity);
     d.gh = heads_per_group(GS, HS);
     d.hgroups = GS / d.gh;
-    if (mfma_decode_applies(NH, NKV, HS, d.band_max) && !hooks)
+    if (mfma_decode_applies(NH, NKV, HS, d.band_max) && !hooks && !scalar_only)
     {
         // 16 heads on one KV head over a long band: the matrix-core decode.  The fused form is the CHAIN here: the 4 us its prologue launch costs are nothing against a
         // band of thousands of keys
@@ -1027,6 +1029,18 @@ static mila_fused_attn_args fused_args(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, 
 {
     return mila_fused_attn_args{Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, tickets, ticket_count, nullptr, 0, 0, nullptr, 0, 0, 0,
                                 NH, NKV, HS, capacity, position, position_dev, window, scale, eps};
+}
+
+// ---- what attention_kvfp8.hip takes from this file (attention_decode_plan.h) ----
+ScalarDecodeShape plan_decode_scalar(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint)
+{
+    const DecodePlan d = plan_decode(B, NH, NKV, HS, capacity, window, len_hint, false, false, true);
+    return ScalarDecodeShape{d.splits, d.gh, d.hgroups, d.scratch_need};
+}
+int launch_attn_combine(uint16_t* Y, const float* partials, int B, int NH, int HS, int splits, hipStream_t s)
+{
+    hipLaunchKernelGGL(attn_combine_kernel, dim3(NH, B, HS / 64), dim3(64), 0, s, Y, partials, NH, HS, splits, nullptr, 0, 0, 0);
+    return check_hip(hipGetLastError(), "attn_combine");
 }
 
 // packed [B, T, 3C] rows -> K / V rows of a [B, NH, capacity, HS] cache at positions start_pos .. start_pos + T - 1 (the K / V part of the reference's

@@ -1,0 +1,506 @@
+// Grouped-query attention over an FP8 KV cache: the PerChannelKvFp8<> policy of the reference (Quantization/KvCache/QuantPolicy.ixx:56-88 declares it -- e4m3 storage of
+// K and V, one fp32 scale per KV head per cached token, absmax / 448, "dequantized to transient BF16 buffers ... never written back"; BACKLOG.md names the missing
+// OperationTraits<GqaOp, Cuda, BF16, PerChannelKvFp8<>> row -- the reference has the policy type and no kernels).
+//
+//   layout   K8, V8 [B, NKV, capacity, HS] uint8, Ks, Vs [B, NKV, capacity] fp32; row = abs_pos % capacity (the bf16 cache's ring rule, Gqa.Cache.Bf16.cu:86-130)
+//   write    a K / V row of one (batch, token, KV head) is quantized as quantize_fp8_per_channel quantizes a weight row (fp8_quant.h): bit-identical bytes and scales
+//   read     a cached value is bf16_rne(float(e4m3) * scale) -- the bits dequantize_to_bf16 produces -- in the decode kernel's registers, or in a transient bf16
+//            cache for the prefill, which then runs the bf16 flash kernels: both see the same K / V values, the attention arithmetic is the bf16 cache's.
+//
+// Decode (the hot path): the split-K flash decode of attention.hip (Gqa.Decode.Bf16.cu:93-105, :212, :297-351) with the row loads at one byte per element.  A lane
+// loads 4 bytes of a row (8 at HS 512), so a row is HS / 4 lanes wide: one row per wave-instruction at HS 256 / 512, two at HS 128 (half-waves), four at HS 64
+// (16-lane rows).  Each lane segment keeps its own online-softmax state over its own positions; the segments of a wave are merged in registers, the eight waves
+// through LDS, the splits by attention.hip's combine kernel from partials in its layout.  Grid and split count are plan_decode's scalar form for the same shape.
+#include "attention_decode_plan.h"
+#include "attention_tiles.h"      // kKeysPerTile: the flash prefill streams whole key tiles
+#include "fp8_quant.h"
+
+namespace mila {
+
+// ---- quantizing KV append ---------------------------------------------------------------------------------------------------------------------------------------
+// one wave per (K | V, batch, token, KV head) row: lanes below HS / EPL own EPL consecutive elements, the absmax is a wave reduction (exact, any order)
+template <int HS>
+__global__ __launch_bounds__(256) void kv_write_fp8_kernel(uint8_t* __restrict__ K8, uint8_t* __restrict__ V8, float* __restrict__ Ks, float* __restrict__ Vs,
+                                                           const uint16_t* __restrict__ k, const uint16_t* __restrict__ v, int64_t rows, int chunk, int NKV,
+                                                           int start_pos, int capacity)
+{
+    constexpr int EPL = HS >= 512 ? 8 : 4, ACTIVE = HS / EPL;
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // wave-uniform
+    if (w >= 2 * rows) return;
+    const bool is_v = w >= rows;
+    int64_t r = is_v ? w - rows : w;                                     // source order [b, t, nkv]
+    const int n = (int)(r % NKV);
+    r /= NKV;
+    const int t = (int)(r % chunk), b = (int)(r / chunk);
+    const uint16_t* src = (is_v ? v : k) + (((size_t)b * chunk + t) * NKV + n) * HS;
+    const size_t drow = ((size_t)b * NKV + n) * capacity + (size_t)((start_pos + t) % capacity);
+    const bool act = lane < ACTIVE;
+    uint32_t x[EPL / 2];
+#pragma unroll
+    for (int e = 0; e < EPL / 2; ++e) x[e] = 0u;
+    if (act)
+    {
+        if constexpr (EPL == 8)
+        {
+            const u32x4 q = ld16(src + lane * 8);
+            x[0] = q[0]; x[1] = q[1]; x[2] = q[2]; x[3] = q[3];
+        }
+        else
+        {
+            const u32x2 q = *reinterpret_cast<const u32x2*>(src + lane * 4);
+            x[0] = q[0]; x[1] = q[1];
+        }
+    }
+    float m = 0.0f;
+#pragma unroll
+    for (int e = 0; e < EPL / 2; ++e) m = fmaxf(m, fmaxf(fabsf(bf16_lo(x[e])), fabsf(bf16_hi(x[e]))));
+    const float scale = fp8_row_scale(wave_max(m));
+    const float inv = 1.0f / scale;
+    if (lane == 0) (is_v ? Vs : Ks)[drow] = scale;
+    if (act)
+    {
+        uint8_t* dst = (is_v ? V8 : K8) + drow * HS + lane * EPL;
+        if constexpr (EPL == 8)
+            *reinterpret_cast<u32x2*>(dst) = u32x2{bf16x4_to_e4m3x4(x[0], x[1], inv), bf16x4_to_e4m3x4(x[2], x[3], inv)};
+        else
+            *reinterpret_cast<uint32_t*>(dst) = bf16x4_to_e4m3x4(x[0], x[1], inv);
+    }
+}
+
+// ---- band dequant (the prefill's transient bf16 cache) ------------------------------------------------------------------------------------------------------------
+// rows of positions [first_pos, first_pos + count) of every (batch, KV head), K and V: one thread per 16 bytes -> 16 bf16 at the same row index of the destination
+__global__ __launch_bounds__(256) void kv_dequant_fp8_kernel(uint16_t* __restrict__ Kd, uint16_t* __restrict__ Vd, const uint8_t* __restrict__ K8,
+                                                             const uint8_t* __restrict__ V8, const float* __restrict__ Ks, const float* __restrict__ Vs,
+                                                             int64_t total_vec, int HS, int capacity, int first_pos, int count)
+{
+    const int hv = HS / 16;
+    const int64_t stride = (int64_t)gridDim.x * 256, half = total_vec / 2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total_vec; i += stride)
+    {
+        const bool is_v = i >= half;
+        int64_t r = is_v ? i - half : i;
+        const int e = (int)(r % hv);
+        r /= hv;
+        const int t = (int)(r % count);
+        const int64_t head = r / count;                                  // b * NKV + kv head
+        const size_t row = (size_t)head * capacity + (size_t)((first_pos + t) % capacity);
+        const float sc = (is_v ? Vs : Ks)[row];
+        const u32x4 w = ld16((is_v ? V8 : K8) + row * HS + (size_t)e * 16);
+        uint32_t o[8];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) e4m3x4_to_bf16x4(w[d], sc, o[2 * d], o[2 * d + 1]);
+        uint16_t* dst = (is_v ? Vd : Kd) + row * HS + (size_t)e * 16;
+        st16(dst, u32x4{o[0], o[1], o[2], o[3]});
+        st16(dst + 8, u32x4{o[4], o[5], o[6], o[7]});
+    }
+}
+
+// ---- decode attention -----------------------------------------------------------------------------------------------------------------------------------------
+struct KvFp8DecodeParams
+{
+    uint16_t* Y;              // [B, NH*HS]
+    const uint16_t* Q;        // [B, NH*HS]
+    const uint8_t* K8;        // [B, NKV, capacity, HS] e4m3
+    const uint8_t* V8;
+    const float* Ks;          // [B, NKV, capacity]
+    const float* Vs;
+    float* scratch;           // [B, NH, splits, HS+4] partials when splits > 1 (attention.hip's layout)
+    int NH, NKV, capacity, len, window, splits;
+    float scale;
+};
+
+constexpr int kKvFp8Waves = 8;     // 512 threads per workgroup, as attn_decode_kernel
+
+// sum over the LPR-lane segment a lane belongs to (segments are aligned): the leading steps of wave_sum
+template <int LPR>
+__device__ __forceinline__ float segment_sum(float v)
+{
+    if constexpr (LPR == 64) return wave_sum(v);
+    v += dpp_f32<0xB1>(v);
+    v += dpp_f32<0x4E>(v);
+    v += dpp_f32<0x141>(v);
+    v += dpp_f32<0x140>(v);
+    if constexpr (LPR == 32)
+    {
+        const uint32_t u = __float_as_uint(v);
+        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+        v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+    return v;
+}
+
+// GH = query heads per workgroup; grid = (splits, NKV * GS/GH, B).  Wave w, lane segment s own positions begin + (w * RPW + s) + 8 * RPW * j of the split.
+template <int HS, int GH>
+__global__ __launch_bounds__(kKvFp8Waves * 64) void attn_decode_kvfp8_kernel(const KvFp8DecodeParams p)
+{
+    constexpr int NW = kKvFp8Waves;
+    constexpr int EPL = HS >= 512 ? 8 : 4;                 // elements (= cache bytes) of a row per lane
+    constexpr int ND = EPL / 4, NPAIR = EPL / 2;
+    constexpr int LPR = HS / EPL;                          // lanes per row: 64, 64, 32, 16
+    constexpr int RPW = 64 / LPR;                          // rows per wave-instruction: 1, 1, 2, 4
+    constexpr int PG = 8 / RPW;                            // row slots a lane keeps in flight: a workgroup's group is 64 positions at every head size
+    constexpr int FE = HS / 64;                            // output elements per lane in the merge
+    constexpr int STR = HS + 2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_kvfp8[];
+    float* sm = reinterpret_cast<float*>(smem_kvfp8);      // [NW][GH][HS + 2]
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane / LPR, ll = lane % LPR;
+    const int GS = p.NH / p.NKV, hgroups = GS / GH;
+    const int split = blockIdx.x, grp = blockIdx.y;
+    const int kvh = grp / hgroups, hg = grp % hgroups;
+    const int h0 = kvh * GS + hg * GH;                     // first query head of this workgroup
+    const int b = blockIdx.z;
+    const int len = p.len;
+    const int band_begin = (p.window > 0) ? max(0, len - p.window) : 0;
+    const int band = len - band_begin;
+    const int chunk = (band + p.splits - 1) / p.splits;
+    const int begin = band_begin + split * chunk;
+    const int end = min(begin + chunk, len);
+
+    const size_t head = ((size_t)b * p.NKV + kvh) * p.capacity;
+    const uint8_t* kbase = p.K8 + head * HS + ll * EPL;
+    const uint8_t* vbase = p.V8 + head * HS + ll * EPL;
+    const float* ksb = p.Ks + head;
+    const float* vsb = p.Vs + head;
+
+    struct KVG { uint32_t k[PG][ND], v[PG][ND]; float ks[PG], vs[PG]; };
+    // wbase: the wave's first position of the group (wave-uniform); a lane's own rows are wbase + sub + NW * RPW * j
+    auto load_group = [&](KVG& g, int wbase) {
+#pragma unroll
+        for (int j = 0; j < PG; ++j)
+        {
+            const int pp = wbase + sub + NW * RPW * j;
+            if (pp < end)
+            {
+                const size_t r = (size_t)(pp % p.capacity);
+                if constexpr (ND == 2)
+                {
+                    const u32x2 a = *reinterpret_cast<const u32x2*>(kbase + r * HS), c = *reinterpret_cast<const u32x2*>(vbase + r * HS);
+                    g.k[j][0] = a[0]; g.k[j][1] = a[1]; g.v[j][0] = c[0]; g.v[j][1] = c[1];
+                }
+                else
+                {
+                    g.k[j][0] = *reinterpret_cast<const uint32_t*>(kbase + r * HS);
+                    g.v[j][0] = *reinterpret_cast<const uint32_t*>(vbase + r * HS);
+                }
+                g.ks[j] = ksb[r];                          // one address per segment: a broadcast load
+                g.vs[j] = vsb[r];
+            }
+            else
+            {
+#pragma unroll
+                for (int e = 0; e < ND; ++e) { g.k[j][e] = 0u; g.v[j][e] = 0u; }
+                g.ks[j] = 0.0f;
+                g.vs[j] = 0.0f;
+            }
+        }
+    };
+
+    int base = begin + wave * RPW;
+    KVG ga, gb;
+    if (base < end) load_group(ga, base);                  // in flight while q is fetched
+
+    uint32_t q[GH][NPAIR];
+#pragma unroll
+    for (int g = 0; g < GH; ++g)
+    {
+        const uint16_t* qp = p.Q + ((size_t)b * p.NH + h0 + g) * HS + ll * EPL;
+        if constexpr (EPL == 8)
+        {
+            const u32x4 t = ld16(qp);
+            q[g][0] = t[0]; q[g][1] = t[1]; q[g][2] = t[2]; q[g][3] = t[3];
+        }
+        else
+        {
+            const u32x2 t = *reinterpret_cast<const u32x2*>(qp);
+            q[g][0] = t[0]; q[g][1] = t[1];
+        }
+    }
+
+    float m[GH], l[GH], o[GH][EPL];
+#pragma unroll
+    for (int g = 0; g < GH; ++g)
+    {
+        m[g] = -INFINITY;
+        l[g] = 0.0f;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) o[g][e] = 0.0f;
+    }
+
+    auto compute_group = [&](const KVG& gbuf, int wbase) {
+        float sc[PG][GH];
+        uint32_t vp[PG][NPAIR];
+#pragma unroll
+        for (int j = 0; j < PG; ++j)
+        {
+            // the cached values, bf16_rne(float(e4m3) * scale), as packed bf16 pairs
+            uint32_t kp[NPAIR];
+#pragma unroll
+            for (int d = 0; d < ND; ++d)
+            {
+                e4m3x4_to_bf16x4(gbuf.k[j][d], gbuf.ks[j], kp[2 * d], kp[2 * d + 1]);
+                e4m3x4_to_bf16x4(gbuf.v[j][d], gbuf.vs[j], vp[j][2 * d], vp[j][2 * d + 1]);
+            }
+#pragma unroll
+            for (int g = 0; g < GH; ++g)
+            {
+                float a = 0.0f;
+#pragma unroll
+                for (int e = 0; e < NPAIR; ++e) a = dot2_bf16(as_bf16x2(q[g][e]), as_bf16x2(kp[e]), a);
+                sc[j][g] = a;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < PG; ++j)
+#pragma unroll
+            for (int g = 0; g < GH; ++g) sc[j][g] = segment_sum<LPR>(sc[j][g]);
+#pragma unroll
+        for (int g = 0; g < GH; ++g)
+        {
+            float a[PG], mt = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < PG; ++j)
+            {
+                a[j] = (wbase + sub + NW * RPW * j < end) ? sc[j][g] * p.scale : -INFINITY;
+                mt = fmaxf(mt, a[j]);
+            }
+            const float mn = fmaxf(m[g], mt);
+            const float msafe = (mn == -INFINITY) ? 0.0f : mn;
+            const float alpha = __expf(m[g] - msafe);        // m = -inf first time: exp(-inf) = 0
+            float ex[PG], rs = 0.0f;
+#pragma unroll
+            for (int j = 0; j < PG; ++j) { ex[j] = __expf(a[j] - msafe); rs += ex[j]; }
+            l[g] = l[g] * alpha + rs;
+            m[g] = mn;
+#pragma unroll
+            for (int e = 0; e < NPAIR; ++e)
+            {
+                float lo = o[g][2 * e] * alpha, hi = o[g][2 * e + 1] * alpha;
+#pragma unroll
+                for (int j = 0; j < PG; ++j)
+                {
+                    lo = fmaf(ex[j], bf16_lo(vp[j][e]), lo);
+                    hi = fmaf(ex[j], bf16_hi(vp[j][e]), hi);
+                }
+                o[g][2 * e] = lo;
+                o[g][2 * e + 1] = hi;
+            }
+        }
+    };
+    for (;;)                                               // (wave-uniform control: `base` is the wave's, not the lane segment's)
+    {
+        if (base >= end) break;
+        int nb = base + NW * RPW * PG;
+        if (nb < end) load_group(gb, nb);
+        compute_group(ga, base);
+        base = nb;
+        if (base >= end) break;
+        nb = base + NW * RPW * PG;
+        if (nb < end) load_group(ga, nb);
+        compute_group(gb, base);
+        base = nb;
+    }
+
+    // ---- merge the RPW lane segments of the wave in registers: afterwards every segment holds the wave's state ----
+    if constexpr (RPW > 1)
+    {
+#pragma unroll
+        for (int off = LPR; off < 64; off <<= 1)
+        {
+#pragma unroll
+            for (int g = 0; g < GH; ++g)
+            {
+                const float mo = __shfl_xor(m[g], off, 64), lo_ = __shfl_xor(l[g], off, 64);
+                const float M = fmaxf(m[g], mo);
+                const float fa = (m[g] == -INFINITY) ? 0.0f : __expf(m[g] - M), fb = (mo == -INFINITY) ? 0.0f : __expf(mo - M);
+                l[g] = l[g] * fa + lo_ * fb;
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) o[g][e] = o[g][e] * fa + __shfl_xor(o[g][e], off, 64) * fb;
+                m[g] = M;
+            }
+        }
+    }
+
+    // ---- merge the NW waves through LDS; wave w < GH finalises head w ----
+#pragma unroll
+    for (int g = 0; g < GH; ++g)
+    {
+        float* dst = sm + ((size_t)wave * GH + g) * STR;
+        if (sub == 0)
+        {
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) dst[ll * EPL + e] = o[g][e];
+        }
+        if (lane == 0) { dst[HS] = m[g]; dst[HS + 1] = l[g]; }
+    }
+    __syncthreads();
+    if (wave < GH)
+    {
+        const int g = wave;
+        float M = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[((size_t)w * GH + g) * STR + HS]);
+        float L = 0.0f, acc[FE];
+#pragma unroll
+        for (int e = 0; e < FE; ++e) acc[e] = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w)
+        {
+            const float* src = sm + ((size_t)w * GH + g) * STR;
+            const float mw = src[HS];
+            const float f = (mw == -INFINITY) ? 0.0f : __expf(mw - M);
+            L += src[HS + 1] * f;
+#pragma unroll
+            for (int e = 0; e < FE; ++e) acc[e] += src[lane * FE + e] * f;
+        }
+        const int h = h0 + g;
+        if (p.splits == 1)
+        {
+            const float inv = (L > 0.0f) ? 1.0f / L : 0.0f;
+            uint16_t* y = p.Y + ((size_t)b * p.NH + h) * HS + lane * FE;
+            if constexpr (FE == 1)
+                y[0] = f32_to_bf16_bits(acc[0] * inv);
+            else
+            {
+#pragma unroll
+                for (int e = 0; e < FE; e += 2) *reinterpret_cast<uint32_t*>(y + e) = pack_bf16x2(acc[e] * inv, acc[e + 1] * inv);
+            }
+        }
+        else
+        {
+            float* dst = p.scratch + (((size_t)b * p.NH + h) * p.splits + split) * (HS + 4);
+#pragma unroll
+            for (int e = 0; e < FE; ++e) dst[lane * FE + e] = acc[e];
+            if (lane == 0) { dst[HS] = M; dst[HS + 1] = L; }
+        }
+    }
+}
+
+template <int HS, int GH>
+static int launch_decode_kvfp8(const KvFp8DecodeParams& p, int B, int hgroups, hipStream_t s)
+{
+    note_form("attn_decode_kvfp8");
+    const size_t lds = (size_t)kKvFp8Waves * GH * (HS + 2) * sizeof(float);      // <= 33 KB (HS 256 x 4 heads, HS 512 x 2)
+    hipLaunchKernelGGL((attn_decode_kvfp8_kernel<HS, GH>), dim3(p.splits, p.NKV * hgroups, B), dim3(kKvFp8Waves * 64), lds, s, p);
+    int rc = check_hip(hipGetLastError(), "attn_decode_kvfp8");
+    if (rc || p.splits <= 1) return rc;
+    return launch_attn_combine(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
+}
+template <int HS>
+static int dispatch_kvfp8_gh(const KvFp8DecodeParams& p, int B, int gh, int hgroups, hipStream_t s)
+{
+    if (gh == 1) return launch_decode_kvfp8<HS, 1>(p, B, hgroups, s);
+    if (gh == 2) return launch_decode_kvfp8<HS, 2>(p, B, hgroups, s);
+    if constexpr (HS < 512)      // (HS 512 takes 4 heads only under the attn.heads_per_group_512 experiment)
+        if (gh == 4) return launch_decode_kvfp8<HS, 4>(p, B, hgroups, s);
+    return set_error(MILA_E_UNSUPPORTED, "attn_decode_kvfp8: no kernel for %d heads per workgroup at HS=%d", gh, HS);
+}
+
+static bool kvfp8_head_size(int HS) { return HS == 64 || HS == 128 || HS == 256 || HS == 512; }
+static size_t kvfp8_transient_bytes(int B, int NKV, int HS, int capacity) { return 2 * (size_t)B * NKV * capacity * HS * sizeof(uint16_t); }
+
+}  // namespace mila
+
+using namespace mila;
+
+extern "C" {
+
+int mila_cdna4_kv_write_fp8(uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* k, const uint16_t* v, int B, int chunk, int NKV, int HS, int start_pos,
+                            int capacity, mila_stream_t stream)
+{
+    MILA_REQUIRE(K8 && V8 && Ks && Vs && k && v, "kv_write_fp8: null pointer");
+    MILA_REQUIRE(B > 0 && chunk > 0 && NKV > 0 && capacity > 0, "kv_write_fp8: bad sizes");
+    MILA_REQUIRE(kvfp8_head_size(HS), "kv_write_fp8: HS=%d must be 64, 128, 256 or 512", HS);
+    MILA_REQUIRE(start_pos >= 0, "kv_write_fp8: negative start position");
+    MILA_REQUIRE(chunk <= capacity, "kv_write_fp8: chunk %d exceeds the cache capacity %d", chunk, capacity);
+    const int64_t rows = (int64_t)B * chunk * NKV;
+    MILA_REQUIRE((2 * rows + 3) / 4 <= 0x7fffffffLL, "kv_write_fp8: too many rows for one launch");
+    const dim3 grid((unsigned)((2 * rows + 3) / 4));
+    hipStream_t s = as_stream(stream);
+    switch (HS)
+    {
+        case 64: hipLaunchKernelGGL(kv_write_fp8_kernel<64>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, capacity); break;
+        case 128: hipLaunchKernelGGL(kv_write_fp8_kernel<128>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, capacity); break;
+        case 256: hipLaunchKernelGGL(kv_write_fp8_kernel<256>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, capacity); break;
+        default: hipLaunchKernelGGL(kv_write_fp8_kernel<512>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, capacity); break;
+    }
+    MILA_LAUNCH_CHECK("kv_write_fp8");
+}
+
+int mila_cdna4_kv_dequant_fp8_bf16(uint16_t* Kc_bf16, uint16_t* Vc_bf16, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, int B, int NKV, int HS,
+                                   int capacity, int first_pos, int count, mila_stream_t stream)
+{
+    MILA_REQUIRE(Kc_bf16 && Vc_bf16 && K8 && V8 && Ks && Vs, "kv_dequant_fp8_bf16: null pointer");
+    MILA_REQUIRE(B > 0 && NKV > 0 && capacity > 0, "kv_dequant_fp8_bf16: bad sizes");
+    MILA_REQUIRE(kvfp8_head_size(HS), "kv_dequant_fp8_bf16: HS=%d must be 64, 128, 256 or 512", HS);
+    MILA_REQUIRE(first_pos >= 0 && count > 0 && count <= capacity, "kv_dequant_fp8_bf16: positions [%d, %d + %d) do not fit the cache capacity %d", first_pos, first_pos,
+                 count, capacity);
+    const int64_t total_vec = 2 * (int64_t)B * NKV * count * (HS / 16);
+    int blocks = ceil_div(total_vec, 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(kv_dequant_fp8_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), Kc_bf16, Vc_bf16, K8, V8, Ks, Vs, total_vec, HS, capacity, first_pos, count);
+    MILA_LAUNCH_CHECK("kv_dequant_fp8_bf16");
+}
+
+int mila_cdna4_attn_decode_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
+                                 int B, int NH, int NKV, int HS, int capacity, int len, int window, float scale, mila_stream_t stream)
+{
+    MILA_REQUIRE(Y && Q && K8 && V8 && Ks && Vs, "attn_decode_kvfp8: null pointer");
+    MILA_REQUIRE(B > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "attn_decode_kvfp8: bad head counts (NH=%d NKV=%d)", NH, NKV);
+    MILA_REQUIRE(kvfp8_head_size(HS), "attn_decode_kvfp8: HS=%d must be 64, 128, 256 or 512", HS);
+    const int GS = NH / NKV;
+    MILA_REQUIRE(GS == 1 || GS == 2 || GS == 4 || GS == 8 || GS == 16 || GS == 32, "attn_decode_kvfp8: group size %d (NH/NKV) must be 1,2,4,8,16 or 32", GS);
+    MILA_REQUIRE(len > 0 && capacity > 0, "attn_decode_kvfp8: len and capacity must be positive (len=%d capacity=%d)", len, capacity);
+    MILA_REQUIRE(window >= 0, "attn_decode_kvfp8: negative window");
+    const int band = (window > 0 && window < len) ? window : len;
+    MILA_REQUIRE(band <= capacity, "attn_decode_kvfp8: live band %d exceeds the cache capacity %d", band, capacity);
+    const ScalarDecodeShape d = plan_decode_scalar(B, NH, NKV, HS, capacity, window, len);
+    MILA_REQUIRE(!d.scratch_need || (scratch && scratch_bytes >= d.scratch_need), "attn_decode_kvfp8: scratch %zu bytes < required %zu (ask attn_decode_scratch_bytes)",
+                 scratch_bytes, d.scratch_need);
+    KvFp8DecodeParams p{Y, Q, K8, V8, Ks, Vs, reinterpret_cast<float*>(scratch), NH, NKV, capacity, len, window, d.splits, scale};
+    hipStream_t s = as_stream(stream);
+    switch (HS)
+    {
+        case 64: return dispatch_kvfp8_gh<64>(p, B, d.gh, d.hgroups, s);
+        case 128: return dispatch_kvfp8_gh<128>(p, B, d.gh, d.hgroups, s);
+        case 256: return dispatch_kvfp8_gh<256>(p, B, d.gh, d.hgroups, s);
+        default: return dispatch_kvfp8_gh<512>(p, B, d.gh, d.hgroups, s);
+    }
+}
+
+size_t mila_cdna4_attn_prefill_kvfp8_scratch_bytes(int B, int NKV, int HS, int capacity)
+{
+    if (B <= 0 || NKV <= 0 || HS <= 0 || capacity <= 0) return 0;
+    return kvfp8_transient_bytes(B, NKV, HS, capacity);
+}
+
+int mila_cdna4_attn_prefill_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
+                                  int B, int chunk, int NH, int NKV, int HS, int capacity, int pos_offset, int window, float scale, mila_stream_t stream)
+{
+    MILA_REQUIRE(Y && Q && K8 && V8 && Ks && Vs && scratch, "attn_prefill_kvfp8: null pointer");
+    MILA_REQUIRE(B > 0 && chunk > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "attn_prefill_kvfp8: bad sizes");
+    MILA_REQUIRE(kvfp8_head_size(HS), "attn_prefill_kvfp8: HS=%d must be 64, 128, 256 or 512", HS);
+    MILA_REQUIRE(pos_offset >= 0 && capacity > 0 && window >= 0, "attn_prefill_kvfp8: bad positions");
+    // every key a query of this chunk may see must still be resident in the ring: the band [first, pos_offset + chunk)
+    const int first = (window > 0) ? max(0, pos_offset - window + 1) : 0, count = pos_offset + chunk - first;
+    MILA_REQUIRE(count <= capacity, "attn_prefill_kvfp8: keys [%d,%d] do not fit the cache capacity %d", first, pos_offset + chunk - 1, capacity);
+    const size_t need = kvfp8_transient_bytes(B, NKV, HS, capacity);
+    MILA_REQUIRE(scratch_bytes >= need, "attn_prefill_kvfp8: scratch %zu bytes < required %zu (ask attn_prefill_kvfp8_scratch_bytes)", scratch_bytes, need);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "attn_prefill_kvfp8: the scratch must be 16-byte aligned");
+    // The transient bf16 caches, of the cache's own shape.  The flash kernels stream whole tiles of kKeysPerTile keys from the tile boundary at or below the band's
+    // first key (attention_prefill.hip: kt0): the up to 31 rows in front of the band are multiplied by a probability of exactly zero, so they must hold finite
+    // values -- the dequantized older tokens (or, in a ring too short to still hold them, the newer rows that took their place: the whole ring then).  Every other
+    // row stays as it is: the kernels clamp their reads to the chunk's last key.
+    const int end = pos_offset + chunk;
+    int first_d = first & ~(kKeysPerTile - 1);
+    if (end - first_d > capacity) first_d = end - capacity;      // (<= first, >= 0: count <= capacity <= end here)
+    uint16_t* Kt = static_cast<uint16_t*>(scratch);
+    uint16_t* Vt = Kt + (size_t)B * NKV * capacity * HS;
+    int rc = mila_cdna4_kv_dequant_fp8_bf16(Kt, Vt, K8, V8, Ks, Vs, B, NKV, HS, capacity, first_d, end - first_d, stream);
+    if (rc) return rc;
+    return mila_cdna4_attn_prefill_bf16(Y, Q, Kt, Vt, B, chunk, NH, NKV, HS, capacity, pos_offset, window, scale, stream);
+}
+
+}  // extern "C"

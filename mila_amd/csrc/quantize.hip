@@ -9,26 +9,9 @@
 // arithmetic on the fp32 bits (RNE at mantissa bit 20, saturate to 0x7e) so it does not depend on
 // the FP8 hardware-convert overflow mode.
 #include "gemm_plan.h"
+#include "fp8_quant.h"      // the e4m3 encoders and the row-scale rule (shared with the quantizing KV-cache append)
 
 namespace mila {
-
-// OCP E4M3FN <- f32, RNE, saturate-to-finite, NaN -> 0x7f (== __nv_fp8_e4m3(float))
-__device__ __forceinline__ uint32_t f32_to_e4m3_rne_sat(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    const uint32_t sign = (u >> 24) & 0x80u;
-    uint32_t a = u & 0x7fffffffu;
-    if (a > 0x7f800000u) return sign | 0x7fu;
-    if (a >= 0x43e80000u) return sign | 0x7eu;          // >= 464 (midpoint 448/480) or inf
-    if (a < 0x3c800000u)                                 // < 2^-6: subnormal grid, step 2^-9
-    {
-        const float q = __builtin_rintf(__uint_as_float(a) * 512.0f);   // v_rndne_f32, 0..8
-        return sign | (uint32_t)q;                                       // 8 == 0x08 == 2^-6
-    }
-    a += 0x7ffffu + ((a >> 20) & 1u);                    // RNE to 3 mantissa bits
-    const uint32_t code = (((a >> 23) - 120u) << 3) | ((a >> 20) & 7u);
-    return sign | (code > 0x7eu ? 0x7eu : code);
-}
 
 // CudaFp4WeightQuantization.cu:54-70: strict '<' breakpoints, sign from x < 0
 __device__ __forceinline__ uint32_t f32_to_e2m1(float x)
@@ -66,7 +49,7 @@ __global__ __launch_bounds__(256) void quantize_fp8_per_channel_kernel(uint8_t* 
     }
     for (int i = nvec * 8 + threadIdx.x; i < K; i += 256) m = fmaxf(m, fabsf(bf16_bits_to_f32(s[i])));
     const float absmax = block_max<4>(m, red);
-    const float scale = (absmax > 0.0f) ? (absmax / 448.0f) : 1.0f;
+    const float scale = fp8_row_scale(absmax);
     const float inv = 1.0f / scale;
     if (threadIdx.x == 0) scales[row] = scale;
     for (int i = threadIdx.x; i < nvec; i += 256)
@@ -127,17 +110,6 @@ __global__ __launch_bounds__(1024) void fp4_weight_fp8_scale_kernel(float* __res
         for (int w = 1; w < 16; ++w) m = fmaxf(m, red[w]);
         atomicMax(reinterpret_cast<unsigned int*>(out), __float_as_uint(fmaxf(m, 1e-12f) * (6.0f / 448.0f)));
     }
-}
-
-// four finite f32 -> four OCP e4m3 bytes with the hardware convert (v_cvt_pk_fp8_f32: RNE), saturating to +-448 first as
-// f32_to_e4m3_rne_sat does (|v| >= 464 -> 0x7e); inputs here are products of finite weights and scales, never NaN
-__device__ __forceinline__ uint32_t f32x4_to_e4m3x4_hw(float a, float b, float c, float d)
-{
-    a = __builtin_amdgcn_fmed3f(a, -448.0f, 448.0f); b = __builtin_amdgcn_fmed3f(b, -448.0f, 448.0f);
-    c = __builtin_amdgcn_fmed3f(c, -448.0f, 448.0f); d = __builtin_amdgcn_fmed3f(d, -448.0f, 448.0f);
-    int r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    r = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
-    return (uint32_t)r;
 }
 
 // packed fp4 -> e4m3: out[2b], out[2b+1] = e4m3(lut(nibble) * (group scale * (1 / weight_fp8_scale)))  (CudaW4A16Gemm.cu:300-323)

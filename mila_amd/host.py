@@ -642,3 +642,101 @@ class activation_tap:
             lib.mila_linear_tap_get(i, None, x8.ctypes.data, ts.ctypes.data)
             self.records.append((M, K, N, x8, ts))
         return False
+
+
+KV_POLICIES = {"none": 0, "sliding_window": 1, "fp8": 2}
+
+
+class GqaOpConfigC(C.Structure):
+    _fields_ = [("num_heads", C.c_int64), ("num_kv_heads", C.c_int64), ("head_dim", C.c_int64), ("window", C.c_int64), ("attention_scale", C.c_float)]
+
+
+class GqaComponent:
+    """ONE GroupedQueryAttention<Rocm, BF16, kv_policy> of the host mirror (libmila_host: host/src/gqa_runner.cpp) over its op-owned KV cache: kv_policy "none"
+    (NoKvCompression), "sliding_window" (SlidingWindowKvCache) or "fp8" (PerChannelKvFp8<>: e4m3 K / V + one fp32 scale per KV head per cached token).  q / k / v and
+    the outputs are bf16 bit patterns (uint16 numpy)."""
+
+    def __init__(self, kv_policy, num_heads, num_kv_heads, head_dim, window=0, attention_scale=0.0, batch=1, max_seq=1024, prefill_chunk=0, device=0):
+        lib = load()
+        vp, i64 = C.c_void_p, C.c_int64
+        lib.mila_gqa_create.restype = vp
+        lib.mila_gqa_create.argtypes = [C.c_int, C.POINTER(GqaOpConfigC), i64, i64, i64, C.c_int]
+        lib.mila_gqa_destroy.argtypes = [vp]
+        lib.mila_gqa_init_cache.argtypes = [vp]
+        lib.mila_gqa_prefill.argtypes = [vp, vp, vp, vp, i64, i64, vp]
+        lib.mila_gqa_decode.argtypes = [vp, vp, vp, vp, i64, vp]
+        lib.mila_gqa_rewind.argtypes = [vp, i64]
+        lib.mila_gqa_state_bytes.argtypes = [vp, vp]
+        lib.mila_gqa_read_cache.argtypes = [vp, vp, vp, vp, vp]
+        lib.mila_gqa_fused_surface_probe.argtypes = [vp, C.c_int]
+        self.kv_policy, self.B, self.NH, self.NKV, self.HS = kv_policy, batch, num_heads, num_kv_heads, head_dim
+        cfg = GqaOpConfigC(num_heads, num_kv_heads, head_dim, window, attention_scale)
+        self.h = lib.mila_gqa_create(KV_POLICIES[kv_policy], C.byref(cfg), batch, max_seq, prefill_chunk, device)
+        if not self.h:
+            text = lib.mila_host_last_error().decode()
+            raise (ValueError if text.startswith("invalid_argument") else RuntimeError)(text)
+
+    @staticmethod
+    def _check(rc):
+        if rc:
+            text = load().mila_host_last_error().decode()
+            raise (ValueError if rc == capi.MILA_E_INVALID_ARGUMENT else (TypeError if rc == capi.MILA_E_UNSUPPORTED else RuntimeError))(text)
+
+    @staticmethod
+    def _rows(a):
+        return np.ascontiguousarray(a, dtype=np.uint16)
+
+    def init_cache(self):
+        self._check(load().mila_gqa_init_cache(self.h))
+
+    def prefill(self, q, k, v, position):
+        """q [B, T, NH*HS], k / v [B, T, NKV*HS] at absolute positions position .. position + T - 1 -> [B, T, NH*HS]"""
+        q, k, v = self._rows(q), self._rows(k), self._rows(v)
+        T = q.size // (self.B * self.NH * self.HS)
+        y = np.empty((self.B, T, self.NH * self.HS), dtype=np.uint16)
+        self._check(load().mila_gqa_prefill(self.h, q.ctypes.data, k.ctypes.data, v.ctypes.data, T, position, y.ctypes.data))
+        return y
+
+    def decode(self, q, k, v, position):
+        """one token per sequence: q [B, NH*HS], k / v [B, NKV*HS] -> [B, NH*HS]"""
+        q, k, v = self._rows(q), self._rows(k), self._rows(v)
+        y = np.empty((self.B, self.NH * self.HS), dtype=np.uint16)
+        self._check(load().mila_gqa_decode(self.h, q.ctypes.data, k.ctypes.data, v.ctypes.data, position, y.ctypes.data))
+        return y
+
+    def rewind(self, length):
+        self._check(load().mila_gqa_rewind(self.h, length))
+
+    def state(self):
+        """dict: op_state_bytes, op_required_state_bytes, component_state_bytes, component_required_state_bytes, capacity, length"""
+        out = (C.c_int64 * 6)()
+        self._check(load().mila_gqa_state_bytes(self.h, out))
+        return dict(zip(("op_state_bytes", "op_required_state_bytes", "component_state_bytes", "component_required_state_bytes", "capacity", "length"), list(out)))
+
+    def read_cache(self):
+        """fp8 policy: (K8, V8 uint8 [B, NKV, capacity, HS], Ks, Vs float32 [B, NKV, capacity]); bf16 policies: (K, V uint16 [B, NKV, capacity, HS], None, None)"""
+        cap = self.state()["capacity"]
+        shape = (self.B, self.NKV, cap, self.HS)
+        if self.kv_policy == "fp8":
+            k8, v8 = np.empty(shape, dtype=np.uint8), np.empty(shape, dtype=np.uint8)
+            ks, vs = np.empty(shape[:3], dtype=np.float32), np.empty(shape[:3], dtype=np.float32)
+            self._check(load().mila_gqa_read_cache(self.h, k8.ctypes.data, v8.ctypes.data, ks.ctypes.data, vs.ctypes.data))
+            return k8, v8, ks, vs
+        k, v = np.empty(shape, dtype=np.uint16), np.empty(shape, dtype=np.uint16)
+        self._check(load().mila_gqa_read_cache(self.h, k.ctypes.data, v.ctypes.data, None, None))
+        return k, v, None, None
+
+    def fused_surface_probe(self, which):
+        """call prefillFromCache / keyCache / valueCache (the methods the fused q/k/v entries use); raises TypeError (std::logic_error) under the fp8 policy"""
+        self._check(load().mila_gqa_fused_surface_probe(self.h, {"prefillFromCache": 0, "keyCache": 1, "valueCache": 2}[which]))
+
+    def close(self):
+        if self.h:
+            load().mila_gqa_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -200,8 +200,9 @@ namespace Mila::Dnn
             return st;
         }
 
-        uint16_t* keyCache() noexcept { return operation_->keyCache(); }
-        uint16_t* valueCache() noexcept { return operation_->valueCache(); }
+        /// the bf16 caches' raw pointers, for the fused entry points; the FP8 KV policy's op has none and throws std::logic_error
+        uint16_t* keyCache() noexcept( noexcept( std::declval<OpType&>().keyCache() ) ) { return operation_->keyCache(); }
+        uint16_t* valueCache() noexcept( noexcept( std::declval<OpType&>().valueCache() ) ) { return operation_->valueCache(); }
         dim_t cacheCapacity() const noexcept { return operation_->cacheCapacity(); }
         dim_t cacheLength() const noexcept { return operation_->cacheLength(); }
         void noteCacheLength( dim_t length ) { operation_->noteCacheLength( length ); }

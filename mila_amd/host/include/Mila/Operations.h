@@ -823,6 +823,122 @@ namespace Mila::Dnn::Compute
         using type = RocmGqaOp<TKvPolicy::kBoundedRing>;
     };
 
+    /// The op row of Quant::KvCache::PerChannelKvFp8<> (Quantization/KvCache/QuantPolicy.ixx:56-88; the reference's BACKLOG names the row
+    /// OperationTraits<GqaOp, Cuda, BF16, PerChannelKvFp8<>> and has no kernels for it): the public methods of RocmGqaOpBase over an op-owned e4m3 cache with one
+    /// fp32 scale per KV head per cached token (csrc/attention_kvfp8.hip).  The cache is unbounded: capacity = max_seq.  Queries, outputs and the appended K / V
+    /// rows stay BF16; a cached value is read back as bf16( e4m3 * scale ) -- in registers by the decode kernel, in a transient bf16 cache by the prefill.
+    class RocmGqaKvFp8Op : public Operation<DeviceType::Rocm, TensorDataType::BF16>
+    {
+    public:
+        using TensorType = RocmBf16Tensor;
+        using StorageTensor = RocmTensor<TensorDataType::FP8_E4M3>;
+        using ScaleTensor = RocmTensor<TensorDataType::FP32>;
+        RocmGqaKvFp8Op( IExecutionContext* ctx, const GqaOpConfig& cfg ) : Operation( ctx ), cfg_( cfg )
+        {
+            if ( cfg.num_heads <= 0 || cfg.num_kv_heads <= 0 || cfg.num_heads % cfg.num_kv_heads != 0 )
+                throw std::invalid_argument( "RocmGqaKvFp8Op: num_heads must be a positive multiple of num_kv_heads" );
+            if ( cfg.head_dim != 64 && cfg.head_dim != 128 && cfg.head_dim != 256 && cfg.head_dim != 512 )
+                throw std::invalid_argument( "RocmGqaKvFp8Op: head_dim must be 64, 128, 256 or 512" );
+            if ( cfg.window < 0 ) throw std::invalid_argument( "RocmGqaKvFp8Op: window must be >= 0" );
+        }
+        bool boundedRing() const noexcept { return false; }
+        float scale() const noexcept { return cfg_.attention_scale > 0.0f ? cfg_.attention_scale : 1.0f / std::sqrt( static_cast<float>( cfg_.head_dim ) ); }
+        dim_t resolveCacheCapacity( dim_t max_seq, dim_t /*window*/, dim_t /*prefill_chunk*/ ) const { return max_seq; }
+
+        /// four tensors: K8 / V8 [B, NKV, capacity, HS] e4m3, Ks / Vs [B, NKV, capacity] fp32
+        void initializeKvCache( int batch, dim_t max_seq, dim_t /*prefill_chunk*/ )
+        {
+            batch_ = batch;
+            capacity_ = max_seq;
+            const shape_t s8{ batch, cfg_.num_kv_heads, capacity_, cfg_.head_dim }, ss{ batch, cfg_.num_kv_heads, capacity_ };
+            k8_ = std::make_unique<StorageTensor>( context_->getDeviceId(), s8 );
+            v8_ = std::make_unique<StorageTensor>( context_->getDeviceId(), s8 );
+            ks_ = std::make_unique<ScaleTensor>( context_->getDeviceId(), ss );
+            vs_ = std::make_unique<ScaleTensor>( context_->getDeviceId(), ss );
+            length_ = 0;
+        }
+        void resetKvCache() noexcept { length_ = 0; }
+        void rewindKvCache( dim_t length )
+        {
+            if ( length < 0 || length > length_ ) throw std::invalid_argument( "RocmGqaKvFp8Op::rewindKvCache: bad length" );
+            length_ = length;      // unbounded: every earlier row is still there, and a row's bytes and scale do not depend on later rows
+        }
+        dim_t cacheLength() const noexcept { return length_; }
+        void noteCacheLength( dim_t ) { throw std::logic_error( "RocmGqaKvFp8Op::noteCacheLength: " + std::string( kFusedOnly ) ); }
+        dim_t cacheCapacity() const noexcept { return capacity_; }
+
+        /// q [B,chunk,NH*HS], k/v [B,chunk,NKV*HS] at absolute positions [position, position+chunk): quantizing append, then the bf16 flash prefill on the band
+        /// dequantized into the context's scratch
+        void prefill( const TensorType& q, const TensorType& k, const TensorType& v, TensorType& out, int chunk, int position )
+        {
+            requireCache();
+            mila_stream_t st = context_->getStream();
+            const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
+            rocmCheck( mila_cdna4_kv_write_fp8( k8_->data(), v8_->data(), ks_->data(), vs_->data(), q_cast( k ), q_cast( v ), batch_, chunk, NKV, HS, position, cap, st ) );
+            const size_t need = mila_cdna4_attn_prefill_kvfp8_scratch_bytes( batch_, NKV, HS, cap );
+            void* scratch = context_->getScratch( need );   // fetched per call, never cached
+            rocmCheck( mila_cdna4_attn_prefill_kvfp8( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, chunk, NH, NKV, HS,
+                                                      cap, position, (int)cfg_.window, scale(), st ) );
+            length_ = position + chunk;
+        }
+        /// one token per sequence at absolute position `position`
+        void decode( const TensorType& q, const TensorType& k, const TensorType& v, TensorType& out, int position )
+        {
+            requireCache();
+            const int NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
+            rocmCheck( mila_cdna4_kv_write_fp8( k8_->data(), v8_->data(), ks_->data(), vs_->data(), q_cast( k ), q_cast( v ), batch_, 1, NKV, HS, position, cap,
+                                                context_->getStream() ) );
+            attendDecode( q, out, position );
+        }
+        /// attention only, over rows that are already in the cache
+        void attendDecode( const TensorType& q, TensorType& out, int position )
+        {
+            requireCache();
+            const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
+            const size_t need = mila_cdna4_attn_decode_scratch_bytes( batch_, NH, HS );
+            void* scratch = context_->getScratch( need );   // fetched per call, never cached
+            rocmCheck( mila_cdna4_attn_decode_kvfp8( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, NH, NKV, HS, cap,
+                                                     position + 1, (int)cfg_.window, scale(), context_->getStream() ) );
+            length_ = position + 1;
+        }
+
+        /// these three exist for the fused q/k/v post-processing entries (fused_qkv_post, fused_attn_decode), which write a bf16 cache through raw pointers
+        void prefillFromCache( const TensorType&, TensorType&, int, int ) { throw std::logic_error( "RocmGqaKvFp8Op::prefillFromCache: " + std::string( kFusedOnly ) ); }
+        uint16_t* keyCache() { throw std::logic_error( "RocmGqaKvFp8Op::keyCache: " + std::string( kFusedOnly ) ); }
+        uint16_t* valueCache() { throw std::logic_error( "RocmGqaKvFp8Op::valueCache: " + std::string( kFusedOnly ) ); }
+
+        /// 2 * B * NKV * capacity * (HS + 4): one byte per element and one fp32 scale per row, K and V
+        size_t stateBytes() const noexcept { return tensorBytes( k8_ ) + tensorBytes( v8_ ) + tensorBytes( ks_ ) + tensorBytes( vs_ ); }
+        size_t requiredStateBytes( int batch, dim_t max_seq, dim_t /*prefill_chunk*/ ) const
+        {
+            return 2 * static_cast<size_t>( batch ) * static_cast<size_t>( cfg_.num_kv_heads ) * static_cast<size_t>( max_seq ) * ( static_cast<size_t>( cfg_.head_dim ) + 4 );
+        }
+        /// the cache arrays (tests read them back): e4m3 bytes and fp32 scales
+        const StorageTensor* keyStorage() const noexcept { return k8_.get(); }
+        const StorageTensor* valueStorage() const noexcept { return v8_.get(); }
+        const ScaleTensor* keyScales() const noexcept { return ks_.get(); }
+        const ScaleTensor* valueScales() const noexcept { return vs_.get(); }
+        const GqaOpConfig& config() const noexcept { return cfg_; }
+
+    private:
+        static constexpr const char* kFusedOnly = "the fused q/k/v entries write a bf16 cache; the FP8 KV cache is appended to by prefill() / decode() only";
+        static const uint16_t* q_cast( const TensorType& t ) { return static_cast<const uint16_t*>( t.rawData() ); }
+        void requireCache() const { if ( !k8_ ) throw std::runtime_error( "RocmGqaKvFp8Op: initializeKvCache() must be called first" ); }
+        GqaOpConfig cfg_;
+        std::unique_ptr<StorageTensor> k8_, v8_;
+        std::unique_ptr<ScaleTensor> ks_, vs_;
+        int batch_{ 1 };
+        dim_t capacity_{ 0 }, length_{ 0 };
+    };
+    /// more specialised than the TKvPolicy row above; storage other than OCP e4m3 has no kernels
+    template<TensorDataType TStorage>
+    struct OperationTraits<OperationType::GroupedQueryAttentionOp, DeviceType::Rocm, TensorDataType::BF16, Quant::KvCache::PerChannelKvFp8<TStorage>>
+    {
+        static_assert( TStorage == TensorDataType::FP8_E4M3,
+                       "PerChannelKvFp8: the CDNA4 KV-cache kernels store OCP e4m3 (FP8_E4M3); FP8_E5M2 storage has no GroupedQueryAttentionOp row" );
+        using type = RocmGqaKvFp8Op;
+    };
+
     // ---------------------------------------------------------------------------------------
     // Sampling (row f3): counterpart of CudaSamplingOp<FP32> (OPS/Sampling/CudaSamplingOp.ixx; Tests/Dnn/Samplers/Sampling.Cuda.cpp:40-150).
     // forward(): sample on the context's stream into a device token.  enqueueForward() / awaitToken(): the decode-ahead half of the pipelined generation loop --

@@ -1,6 +1,6 @@
 // Compile-time weight / KV-cache quantization policies -- kept verbatim in meaning from
 // /root/reference/Mila/Src/Dnn/Quantization/Weight/Policies.ixx:23-31,46-53,70-79,104-113,125-138
-// and Quantization/KvCache/Policy.ixx:51-54,75-78.  They carry no runtime state: every branch on
+// and Quantization/KvCache/Policy.ixx:51-54,75-78, QuantPolicy.ixx:56-88.  They carry no runtime state: every branch on
 // them is `if constexpr`.
 #pragma once
 
@@ -92,4 +92,34 @@ namespace Mila::Dnn::Quant::KvCache
     struct NoKvCompression { static constexpr bool kBoundedRing = false; };
     /// bounded ring: capacity = min(T, window + prefill_chunk - 1)  (CudaGqaOp.ixx:552-574)
     struct SlidingWindowKvCache { static constexpr bool kBoundedRing = true; };
+
+    /// FP8 storage of K and V (Quantization/KvCache/QuantPolicy.ixx:56-88): one fp32 scale per KV head per cached token, scale = max|row| / 448, symmetric
+    /// (no zero point); values are dequantized to BF16 right before the attention math and never written back.  The cache is unbounded (capacity == context).
+    /// The CDNA4 kernels store OCP e4m3 (csrc/attention_kvfp8.hip); the storage axis exists because the reference's policy has it.
+    template<TensorDataType TStorage = TensorDataType::FP8_E4M3>
+    struct PerChannelKvFp8
+    {
+        static constexpr bool kIsActive = true;
+        static constexpr TensorDataType kStorageDtype = TStorage;
+        static constexpr TensorDataType kScaleDtype = TensorDataType::FP32;
+        static constexpr bool kPerHeadPerToken = true;
+        static constexpr bool kSymmetric = true;
+        static constexpr bool kBoundedRing = false;
+    };
+
+    /// a policy that changes how K / V are STORED (the two ring policies above only change how many rows there are)
+    template<typename T>
+    concept QuantKvPolicy = requires
+    {
+        { T::kIsActive } -> std::convertible_to<bool>;
+        { T::kStorageDtype } -> std::convertible_to<TensorDataType>;
+        { T::kScaleDtype } -> std::convertible_to<TensorDataType>;
+        { T::kPerHeadPerToken } -> std::convertible_to<bool>;
+        { T::kSymmetric } -> std::convertible_to<bool>;
+    };
+
+    static_assert( !QuantKvPolicy<NoKvCompression> );
+    static_assert( !QuantKvPolicy<SlidingWindowKvCache> );
+    static_assert( QuantKvPolicy<PerChannelKvFp8<>> );
+    static_assert( QuantKvPolicy<PerChannelKvFp8<TensorDataType::FP8_E5M2>> );      // a policy type; the op row rejects it (Operations.h)
 }

@@ -47,6 +47,9 @@ namespace
     static_assert( std::is_same_v<ProbeNet::GlobalBlockType::AttentionType::OpType, Mila::Dnn::Compute::RocmGqaOp<false>>, "global (full-attention) layers must never be bounded" );
 }
 
+/// the other runners of this library (gqa_runner.cpp) report through the message mila_host_last_error() returns
+namespace Mila::Host { void setLastError( const std::string& text ) { g_err = text; } }
+
 extern "C" {
 
 #define HOST_API __attribute__((visibility("default")))
