@@ -278,8 +278,15 @@ MILA_API int mila_cdna4_mha_decode_bf16(uint16_t* Y, const uint16_t* QKV, uint16
  *   kv_write_fp8: quantizing append of k / v [B, chunk, NKV*HS] at rows (start_pos + t) % capacity -- each K / V row of one (batch, token, KV head) exactly as
  *     quantize_fp8_per_channel quantizes one weight row: bit-identical bytes and scales.  chunk <= capacity (QuantPolicy.ixx:56-88; CudaGqa.cuh: cuda_kvcache_write_kv_bf16).
  *   A cached value is bf16_rne(float(e4m3) * scale) -- the bits dequantize_to_bf16 (fp8) produces.  The attention arithmetic on those values is the bf16 cache's.
- *   attn_decode_kvfp8: attn_decode_bf16 over this cache (CudaGqa.cuh: cuda_gqa_decode_attention_bf16): values dequantized in registers; the split count of
- *     attn_decode_bf16's scalar kernel for the shape; scratch from attn_decode_scratch_bytes(B, NH, HS).
+ *   attn_decode_kvfp8: attn_decode_bf16 over this cache (CudaGqa.cuh: cuda_gqa_decode_attention_bf16), from attn_decode_bf16's plan for the shape -- the same kernel
+ *     form, split count and scratch need.  16 query heads per KV head at HS 512 from the 8192-key band bucket on: the matrix-core kernel, e4m3 rows dequantized on
+ *     the way into LDS -- bit for bit attn_decode_bf16 on a bf16 cache of the dequantized values.  Every other shape: the wave-per-position kernel, values dequantized
+ *     in registers.  Scratch from attn_decode_scratch_bytes(B, NH, HS).
+ *   kv_write_fp8_devpos / attn_decode_kvfp8_devpos: the graph-replay forms (see attn_decode_bf16_devpos below; CudaGqa.cuh: cuda_kvcache_write_kv_bf16,
+ *     cuda_gqa_decode_attention_bf16 -- the reference passes the position from the host at every step): one token per sequence appended at row *position_dev % capacity
+ *     with kv_write_fp8's bytes and scales; attention over len = *position_dev + 1 keys, read by the kernels.  `max_len` (>= the live length, in its band bucket:
+ *     attn_decode_band_bucket) fixes form and split count at capture time -- any max_len of the bucket gives attn_decode_kvfp8's bits; splits past the live band
+ *     contribute (m = -inf, l = 0) partials.
  *   kv_dequant_fp8_bf16: cache rows of positions [first_pos, first_pos + count) -> the same rows of bf16 caches [B, NKV, capacity, HS]; other rows are not written.
  *   attn_prefill_kvfp8: attn_prefill_bf16 over this cache (CudaGqa.cuh flash-prefill launchers): the chunk's band [max(0, pos_offset - window + 1), pos_offset + chunk)
  *     (from 0 when unwindowed; extended down to the 32-key tile boundary the flash kernels start streaming from) is dequantized into two transient bf16 caches in
@@ -289,6 +296,15 @@ MILA_API int mila_cdna4_kv_write_fp8(uint8_t* K8, uint8_t* V8, float* Ks, float*
                                      int start_pos, int capacity, mila_stream_t stream);
 MILA_API int mila_cdna4_attn_decode_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch,
                                           size_t scratch_bytes, int B, int NH, int NKV, int HS, int capacity, int len, int window, float scale, mila_stream_t stream);
+MILA_API int mila_cdna4_kv_write_fp8_devpos(uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* k, const uint16_t* v, int B, int NKV, int HS,
+                                            const int32_t* position_dev, int capacity, mila_stream_t stream);
+MILA_API int mila_cdna4_attn_decode_kvfp8_devpos(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch,
+                                                 size_t scratch_bytes, int B, int NH, int NKV, int HS, int capacity, const int32_t* position_dev, int max_len, int window,
+                                                 float scale, mila_stream_t stream);
+/* the plan attn_decode_kvfp8 (and its device-position form, len_hint = max_len) launches from, as text, without running device code -- the counterpart of what a caller of
+ * the reference learns from CudaGqa.cuh's launcher (cuda_gqa_decode_attention_bf16 picks its split count from the band): "form:splits:band_max:heads_per_group:
+ * head_groups:flat:prologue:partial_floats:scratch_need", form attn_decode_kvfp8 | attn_decode_kvfp8_mfma; returns the text's size, 0 for a bad shape. */
+MILA_API size_t mila_cdna4_attn_decode_kvfp8_plan_describe(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, char* buf, size_t cap);
 MILA_API int mila_cdna4_kv_dequant_fp8_bf16(uint16_t* Kc_bf16, uint16_t* Vc_bf16, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, int B, int NKV,
                                             int HS, int capacity, int first_pos, int count, mila_stream_t stream);
 MILA_API size_t mila_cdna4_attn_prefill_kvfp8_scratch_bytes(int B, int NKV, int HS, int capacity);

@@ -85,6 +85,10 @@ def load():
     p, i, f, z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
     main.mila_cdna4_kv_write_fp8.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                               # K8 V8 Ks Vs k v | B chunk NKV HS start_pos capacity | stream
     main.mila_cdna4_attn_decode_kvfp8.argtypes = [p, p, p, p, p, p, p, z, i, i, i, i, i, i, i, f, p]              # Y Q K8 V8 Ks Vs scratch bytes | B NH NKV HS capacity len window | scale
+    main.mila_cdna4_kv_write_fp8_devpos.argtypes = [p, p, p, p, p, p, i, i, i, p, i, p]                           # K8 V8 Ks Vs k v | B NKV HS | position_dev | capacity | stream
+    main.mila_cdna4_attn_decode_kvfp8_devpos.argtypes = [p, p, p, p, p, p, p, z, i, i, i, i, i, p, i, i, f, p]    # Y Q K8 V8 Ks Vs scratch bytes | B NH NKV HS capacity | position_dev | max_len window | scale
+    main.mila_cdna4_attn_decode_kvfp8_plan_describe.argtypes = [i, i, i, i, i, i, i, p, z]                        # B NH NKV HS capacity window len_hint | buf cap
+    main.mila_cdna4_attn_decode_kvfp8_plan_describe.restype = z
     main.mila_cdna4_kv_dequant_fp8_bf16.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                        # Kc Vc K8 V8 Ks Vs | B NKV HS capacity first_pos count
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.argtypes = [i, i, i, i]                                      # B NKV HS capacity
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.restype = z
@@ -173,6 +177,16 @@ def attn_decode_plan(B, NH, NKV, HS, capacity, window, len_hint=0, fused=False, 
     return dict(zip(PLAN_FIELDS, [f[0]] + [int(v) for v in f[1:]]))
 
 
+def attn_decode_kvfp8_plan(B, NH, NKV, HS, capacity, window, len_hint=0):
+    """the plan attn_decode_kvfp8 / attn_decode_kvfp8_devpos launch from (csrc/attention.hip: plan_decode for the fp8 KV cache) as a dict of PLAN_FIELDS; form is
+    attn_decode_kvfp8 or attn_decode_kvfp8_mfma.  Needs no GPU."""
+    buf = C.create_string_buffer(256)
+    need = load().mila_cdna4_attn_decode_kvfp8_plan_describe(int(B), int(NH), int(NKV), int(HS), int(capacity), int(window), int(len_hint), buf, C.c_size_t(len(buf)))
+    assert 0 < need <= len(buf), "no plan for this shape" if not need else "plan text of %d bytes" % need
+    f = buf.value.decode().split(":")
+    return dict(zip(PLAN_FIELDS, [f[0]] + [int(v) for v in f[1:]]))
+
+
 def check(rc):
     if rc == MILA_OK:
         return
@@ -224,6 +238,7 @@ EXPORTED = [
     "gemm_fp8_w8a8_ws", "gemm_geglu_fp8_w8a8", "gemm_w8a8_scratch_bytes", "gemm_bf16_w8a8", "gemm_geglu_bf16_w8a8",
     "matvec_fp32", "gemm_fp32", "mha_fp32", "mha_kv_write_fp32", "mha_decode_fp32", "lpe_fp32", "rope_forward_fp32",
     "kv_write_fp8", "attn_decode_kvfp8", "kv_dequant_fp8_bf16", "attn_prefill_kvfp8_scratch_bytes", "attn_prefill_kvfp8",
+    "kv_write_fp8_devpos", "attn_decode_kvfp8_devpos", "attn_decode_kvfp8_plan_describe",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

@@ -24,6 +24,7 @@
 #include "internal.h"
 #include "attention_generic.h"
 #include "attention_tiles.h"
+#include "attention_decode_mfma.h"
 #include "attention_decode_plan.h"
 
 namespace mila {
@@ -539,165 +540,18 @@ __global__ __launch_bounds__(64) void attn_combine_kernel(uint16_t* __restrict__
 // ---- long-context decode on the matrix cores (round 3) ------------------------------------------------------------------------------------------
 // Gemma's global layers put 16 query heads on ONE KV head: at one decode position those 16 heads ARE a 16-row MFMA tile, and K / V rows are shared by all of them.
 // The wave-per-position kernel above costs a 64-lane reduction per (head, key): at 32 768 keys it is vector-ALU-bound, 63.7 us for 67 MB of K / V (1.05 TB/s,
-// profiles/r03_long_context.txt) -- and its 8 head-groups of 2 read every row 8 times from L2.  Here a workgroup takes one split of the keys for all 16 heads:
-// K / V tiles of 32 keys go global -> registers -> LDS (double-buffered images of attention_tiles.h, the next tile's loads in flight during this tile's products),
-// S^T = K Q^T and O^T += V^T P^T run as in the flash prefill (transposed products: a head's keys sit in its lane's registers, the row statistics are in-lane plus two
-// permlane steps, the exponentiated scores ARE the second product's B operand).  The four waves split the OUTPUT dimensions (each computes the whole S^T and softmax
-// of the tile -- identical in all four -- and a quarter of O^T: 32 accumulator registers).  Partials in the layout of the scalar kernel: O (unnormalised, relative
-// to M) | M | L per (head, split); up to 256 splits, merged by attn_combine_many_kernel.  fp32 scores and statistics, P rounded to bf16 for the PV product (as the
-// flash kernels do): within 1 bf16 ulp of the double-precision oracle like them, NOT bit-identical to the scalar kernel -- the choice depends on (window, capacity)
-// only, so every path of a model (reference order, fused, graph replay) takes the same kernel.
+// profiles/r03_long_context.txt) -- and its 8 head-groups of 2 read every row 8 times from L2.  Here a workgroup takes one split of the keys for all 16 heads: the
+// tile body of attention_decode_mfma.h (shared with the fp8 KV cache's kernel, attention_kvfp8.hip) under the bf16 staging policy.  Partials in the layout of the
+// scalar kernel: O (unnormalised, relative to M) | M | L per (head, split); up to 256 splits, merged by attn_combine_many_kernel.  fp32 scores and statistics, P
+// rounded to bf16 for the PV product (as the flash kernels do): within 1 bf16 ulp of the double-precision oracle like them, NOT bit-identical to the scalar kernel --
+// the choice depends on (window, capacity) only, so every path of a model (reference order, fused, graph replay) takes the same kernel.
 template <int HS>
 __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(const AttnParams p)
 {
-    constexpr int KSTEPS = HS / 32, DT = HS / 16, DTW = DT / 4;
-    constexpr int ROWB = HS * 2, TILE_BYTES = kKeysPerTile * ROWB;
-    constexpr int CH = (kKeysPerTile * (ROWB / 16)) / 256;          // 16-byte chunks each thread stages per tile and operand
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_mfma[];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, g = lane >> 4;
-    const int GS = p.NH / p.NKV, n16 = GS / 16;
-    const int split = blockIdx.x, kvh = blockIdx.y / n16, h0 = kvh * GS + (blockIdx.y % n16) * 16, b = blockIdx.z;
     const int pos = p.pos_dev ? *p.pos_dev : p.position;
-    const int len = pos + 1;
-    const int band_begin = (p.window > 0) ? max(0, len - p.window) : 0;
-    const int band = len - band_begin;
-    const int chunk = (band + p.splits - 1) / p.splits;
-    const int begin = band_begin + split * chunk;
-    const int end = min(begin + chunk, len);
-    float* part = p.scratch + (((size_t)b * p.NH + h0 + l15) * p.splits + split) * (HS + 4);      // this lane's head row
-
-    f32x4 o[DTW];
-#pragma unroll
-    for (int d = 0; d < DTW; ++d) o[d] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    float m_run = -INFINITY, l_run = 0.0f;
-
-    if (begin < end)      // workgroup-uniform
-    {
-        // Q: the 16 heads' rows as a 16-row image in LDS (the layout of a K tile's first 16 rows); the fragments of a k-step are read per tile -- held in registers they
-        // cost 64 VGPRs, which buy the second staging set (two tiles of K / V in flight per workgroup instead of one: the kernel is a latency chain of 4-8 tiles)
-        unsigned char* ldsQ = smem_mfma + 4 * TILE_BYTES;
-        {
-            const uint16_t* qb = p.Q + (size_t)b * (p.q_b_stride ? (size_t)p.q_b_stride : (size_t)p.NH * HS) + (size_t)h0 * HS;
-#pragma unroll
-            for (int i = 0; i < (16 * (ROWB / 16)) / 256; ++i)
-            {
-                const int c = tid + 256 * i;
-                const int row = c / (ROWB / 16), ch = c % (ROWB / 16);
-                *reinterpret_cast<u32x4*>(ldsQ + k_off<HS>(row, ch)) = ld16(qb + (size_t)row * HS + ch * 8);
-            }
-        }
-        const uint16_t* kbase = p.K + ((size_t)b * p.NKV + kvh) * p.capacity * HS;
-        const uint16_t* vbase = p.V + ((size_t)b * p.NKV + kvh) * p.capacity * HS;
-        const bool wraps = end > p.capacity;                          // uniform: an unbounded cache (the global layers) needs no modulo per row
-        struct StageRegs { u32x4 k[CH], v[CH]; };
-        const int ntiles = (end - begin + kKeysPerTile - 1) / kKeysPerTile;
-        const int kt_last = begin + (ntiles - 1) * kKeysPerTile;
-        auto stage_load = [&](StageRegs& r, int kt) {
-            kt = min(kt, kt_last);                                    // a load past the last tile re-reads it (never stored): branch-free, the waits stay counted
-#pragma unroll
-            for (int i = 0; i < CH; ++i)
-            {
-                const int c = tid + 256 * i;
-                const int row = c / (ROWB / 16), ch = c % (ROWB / 16);
-                const int key = min(kt + row, end - 1);                 // rows past the split re-read its last key (masked below; a real, finite V row)
-                const size_t off = (size_t)(wraps ? key % p.capacity : key) * HS + ch * 8;
-                r.k[i] = ld16(kbase + off);
-                r.v[i] = ld16(vbase + off);
-            }
-        };
-        auto stage_store = [&](const StageRegs& r, unsigned char* ldsK, unsigned char* ldsV) {
-#pragma unroll
-            for (int i = 0; i < CH; ++i)
-            {
-                const int c = tid + 256 * i;
-                const int row = c / (ROWB / 16), ch = c % (ROWB / 16);
-                *reinterpret_cast<u32x4*>(ldsK + k_off<HS>(row, ch)) = r.k[i];
-                *reinterpret_cast<u32x4*>(ldsV + v_off<HS>(row, ch)) = r.v[i];
-            }
-        };
-        StageRegs ra, rb;
-        stage_load(ra, begin);
-        stage_load(rb, begin + kKeysPerTile);
-        auto tile = [&](int t, StageRegs& regs) {
-            const int kt = begin + t * kKeysPerTile;
-            // two [K | V] buffers: tile t is stored while slower waves may still read tile t - 1 from the other one (the store follows the barrier of tile t - 1,
-            // which every wave reaches only after its reads of tile t - 2): one barrier per tile, which also publishes the Q image before its first read
-            unsigned char* ldsK = smem_mfma + (t & 1) * 2 * TILE_BYTES;
-            unsigned char* ldsV = ldsK + TILE_BYTES;
-            stage_store(regs, ldsK, ldsV);
-            __syncthreads();
-            stage_load(regs, kt + 2 * kKeysPerTile);                  // two tiles ahead, in flight during this tile's and the next one's products
-
-            f32x4 s0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, s1 = s0;
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s)
-            {
-                const s16x8 qf = *reinterpret_cast<const s16x8*>(ldsQ + k_off<HS>(l15, 4 * s + g));
-                const s16x8 ka = *reinterpret_cast<const s16x8*>(ldsK + k_off<HS>(l15, 4 * s + g));
-                const s16x8 kb = *reinterpret_cast<const s16x8*>(ldsK + k_off<HS>(16 + l15, 4 * s + g));
-                s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ka), __builtin_bit_cast(bf16x8, qf), s0, 0, 0, 0);
-                s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kb), __builtin_bit_cast(bf16x8, qf), s1, 0, 0, 0);
-            }
-            // lane holds keys kt + 4 g + r (s0) and kt + 16 + 4 g + r (s1) of head row l15
-            float sv[8], mt = -INFINITY;
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-            {
-                const int key = kt + ((r < 4) ? (4 * g + r) : (16 + 4 * g + (r - 4)));
-                const float raw = (r < 4) ? s0[r] : s1[r - 4];
-                sv[r] = (key < end) ? raw * p.scale : -INFINITY;
-                mt = fmaxf(mt, sv[r]);
-            }
-            mt = quad_rows_max(mt);
-            const float mn = fmaxf(m_run, mt);                      // finite: every tile holds at least one key of the split
-            const float alpha = __expf(m_run - mn);                 // m_run = -inf -> 0
-            float pe[8], rs = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-            {
-                pe[r] = __expf(sv[r] - mn);
-                rs += pe[r];
-            }
-            rs = quad_rows_sum(rs);
-            l_run = l_run * alpha + rs;
-            m_run = mn;
-            u32x4 pb;
-            pb[0] = pack_bf16x2(pe[0], pe[1]);
-            pb[1] = pack_bf16x2(pe[2], pe[3]);
-            pb[2] = pack_bf16x2(pe[4], pe[5]);
-            pb[3] = pack_bf16x2(pe[6], pe[7]);
-            const bf16x8 pfrag = __builtin_bit_cast(bf16x8, pb);
-            const bool rescale = __any(alpha != 1.0f);
-#pragma unroll
-            for (int dd = 0; dd < DTW; ++dd)
-            {
-                const int d = wave * DTW + dd;
-                const int q4 = l15 >> 2, pp = l15 & 3;
-                const int col = 16 * d + 4 * pp;
-                const int r_lo = 4 * g + q4, r_hi = 16 + 4 * g + q4;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) s16x4*)(ldsV + v_off<HS>(r_lo, col >> 3) + ((col & 7) << 1)));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) s16x4*)(ldsV + v_off<HS>(r_hi, col >> 3) + ((col & 7) << 1)));
-                s16x8 va;
-                va[0] = lo[0]; va[1] = lo[1]; va[2] = lo[2]; va[3] = lo[3];
-                va[4] = hi[0]; va[5] = hi[1]; va[6] = hi[2]; va[7] = hi[3];
-                if (rescale) { o[dd][0] *= alpha; o[dd][1] *= alpha; o[dd][2] *= alpha; o[dd][3] *= alpha; }
-                o[dd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, va), pfrag, o[dd], 0, 0, 0);
-            }
-        };
-        for (int t = 0; t < ntiles; t += 2)
-        {
-            tile(t, ra);
-            if (t + 1 < ntiles) tile(t + 1, rb);
-        }
-    }
-    // O^T[dim 16 d + 4 g + r][head l15] -> this head's partial row; (M, L) once per head (an empty split leaves O = 0, M = -inf, L = 0: the merge ignores it)
-#pragma unroll
-    for (int dd = 0; dd < DTW; ++dd) *reinterpret_cast<f32x4*>(part + 16 * (wave * DTW + dd) + 4 * g) = o[dd];
-    if (wave == 0 && g == 0) { part[HS] = m_run; part[HS + 1] = l_run; }
+    const MfmaDecodeArgs a{p.Q, p.q_b_stride, p.scratch, p.NH, p.NKV, p.capacity, pos + 1, p.window, p.splits, p.scale};
+    attn_decode_mfma_body<HS>(a, MfmaStageBf16<HS>{p.K, p.V}, smem_mfma);
 }
 
 // merge of up to kMaxSplitsMfma partials per head: grid (NH, B, HS / 64), 4 waves; wave w merges splits 64 w .. 64 w + 63 as attn_combine_kernel does (lane s holds
@@ -782,6 +636,8 @@ static int g_attn_gh512 = 2;      // query heads per workgroup at HS 512 (experi
 MILA_TUNE("attn.heads_per_group_512", g_attn_gh512);
 static int g_tune_decode_mfma = 1;      // tuning "attn.mfma_decode": 0 = never take the MFMA decode
 MILA_TUNE("attn.mfma_decode", g_tune_decode_mfma);
+static int g_tune_kvfp8_mfma = 1;       // tuning "attn.kvfp8_mfma_decode": 0 = the fp8 KV cache (attention_kvfp8.hip) never takes its matrix-core decode: the scalar plan
+MILA_TUNE("attn.kvfp8_mfma_decode", g_tune_kvfp8_mfma);
 static int g_mfma_min_band = 8192;      // tuning "attn.mfma_min_band": band bucket (keys) from which a 16-head group on one KV head takes the MFMA decode (profiles/r04_attn_band.txt)
 MILA_TUNE("attn.mfma_min_band", g_mfma_min_band);
 // Experiment (round 4): every split of a head group and the combine workgroups of its heads on ONE XCD (blockIdx.x % 8 equal), so that the merge
@@ -828,9 +684,11 @@ static size_t decode_scratch_bytes(int B, int NH, int HS, int splits, bool q_row
 // len_hint: an upper bound on the live length the launch is for -- position + 1 in the eager forms; in the device-position forms what the caller captured the graph for;
 // 0 = the capacity.  The split count depends only on (window, band bucket), never on the current length inside a bucket, so that eager launches and a graph captured
 // once reduce in the same order: bit-identical.  hooks: the entry uses tickets, no_combine or warm ranges, which address the 3-D grid of the scalar kernel.
-// scalar_only: the caller has no matrix-core form (the fp8 KV cache, attention_kvfp8.hip): the scalar form's plan for the same shape.
-static DecodePlan plan_decode(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, bool fused, bool hooks, bool scalar_only = false)
+// kvfp8: the plan is for the fp8 KV cache's entries (attention_kvfp8.hip), whose two kernels take the same forms by the same rules; under attn.kvfp8_mfma_decode 0 they
+// keep to the scalar form's plan for the shape.
+static DecodePlan plan_decode(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, bool fused, bool hooks, bool kvfp8 = false)
 {
+    const bool scalar_only = kvfp8 && !g_tune_kvfp8_mfma;
     DecodePlan d{};
     const int GS = NH / NKV;
     const bool split_kernel = HS == 64 || HS == 128 || HS == 256 || HS == 512;
@@ -856,12 +714,17 @@ static DecodePlan plan_decode(int B, int NH, int NKV, int HS, int capacity, int 
     d.scratch_need = (d.form == DF_MFMA || (d.form == DF_SCALAR && d.splits > 1)) ? decode_scratch_bytes(B, NH, HS, d.splits, d.prologue) : 0;
     return d;
 }
+int launch_attn_combine_many(uint16_t* Y, const float* partials, int B, int NH, int HS, int splits, hipStream_t s)
+{
+    hipLaunchKernelGGL(attn_combine_many_kernel, dim3(NH, B, HS / 64), dim3(256), 0, s, Y, partials, NH, HS, splits);
+    return check_hip(hipGetLastError(), "attn_combine_many");
+}
 static int launch_decode_mfma(const AttnParams& p, int B, hipStream_t s)
 {
     constexpr int HS = 512;
     note_form("attn_decode_mfma");
     static bool attr_set = false;
-    const size_t lds = 4 * (size_t)kKeysPerTile * HS * 2 + 16 * (size_t)HS * 2;      // two [K | V] tile pairs + the 16 heads' Q rows
+    const size_t lds = mfma_decode_lds_bytes<HS>();
     if (!attr_set)
     {
         int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_mfma_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(attn_decode_mfma)");
@@ -872,8 +735,7 @@ static int launch_decode_mfma(const AttnParams& p, int B, hipStream_t s)
     hipLaunchKernelGGL((attn_decode_mfma_kernel<HS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, p);
     int rc = check_hip(hipGetLastError(), "attn_decode_mfma");
     if (rc) return rc;
-    hipLaunchKernelGGL(attn_combine_many_kernel, dim3(p.NH, B, HS / 64), dim3(256), 0, s, p.Y, p.scratch, p.NH, HS, p.splits);
-    return check_hip(hipGetLastError(), "attn_combine_many");
+    return launch_attn_combine_many(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
 }
 
 template <int HS, int GH, bool FUSED>
@@ -1032,10 +894,10 @@ static mila_fused_attn_args fused_args(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, 
 }
 
 // ---- what attention_kvfp8.hip takes from this file (attention_decode_plan.h) ----
-ScalarDecodeShape plan_decode_scalar(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint)
+KvFp8DecodeShape plan_decode_kvfp8(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint)
 {
     const DecodePlan d = plan_decode(B, NH, NKV, HS, capacity, window, len_hint, false, false, true);
-    return ScalarDecodeShape{d.splits, d.gh, d.hgroups, d.scratch_need};
+    return KvFp8DecodeShape{d.form == DF_MFMA, d.splits, d.gh, d.hgroups, d.scratch_need};
 }
 int launch_attn_combine(uint16_t* Y, const float* partials, int B, int NH, int HS, int splits, hipStream_t s)
 {
@@ -1242,14 +1104,25 @@ int mila_cdna4_fused_attn_decode_ex(const mila_fused_attn_args* a, mila_stream_t
     return fused_decode("fused_attn_decode_ex", *a, 1, 0, 0, as_stream(stream));
 }
 
+static size_t describe_plan(const DecodePlan& d, const char* const* names, char* buf, size_t cap)
+{
+    return 1 + snprintf(buf, buf ? cap : 0, "%s:%d:%d:%d:%d:%d:%d:%zu:%zu", names[d.form], d.splits, d.band_max, d.gh, d.hgroups, d.flat, (int)d.prologue, d.partial_floats,
+                        d.scratch_need);
+}
 size_t mila_cdna4_attn_decode_plan_describe(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, int fused, int hooks, char* buf, size_t cap)
 {
     if (buf && cap) buf[0] = 0;
     if (B <= 0 || NH <= 0 || NKV <= 0 || NH % NKV != 0 || HS <= 0 || capacity <= 0 || window < 0) return 0;
-    const DecodePlan d = plan_decode(B, NH, NKV, HS, capacity, window, len_hint, fused != 0, hooks != 0);
     static const char* const names[] = {"attn_decode", "attn_decode_mfma", "attn_generic"};
-    return 1 + snprintf(buf, buf ? cap : 0, "%s:%d:%d:%d:%d:%d:%d:%zu:%zu", names[d.form], d.splits, d.band_max, d.gh, d.hgroups, d.flat, (int)d.prologue, d.partial_floats,
-                        d.scratch_need);
+    return describe_plan(plan_decode(B, NH, NKV, HS, capacity, window, len_hint, fused != 0, hooks != 0), names, buf, cap);
+}
+// the plan attn_decode_kvfp8 and its device-position form launch from; the fp8 KV cache has kernels for the four split-kernel head sizes only
+size_t mila_cdna4_attn_decode_kvfp8_plan_describe(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, char* buf, size_t cap)
+{
+    if (buf && cap) buf[0] = 0;
+    if (B <= 0 || NH <= 0 || NKV <= 0 || NH % NKV != 0 || (HS != 64 && HS != 128 && HS != 256 && HS != 512) || capacity <= 0 || window < 0) return 0;
+    static const char* const names[] = {"attn_decode_kvfp8", "attn_decode_kvfp8_mfma", ""};
+    return describe_plan(plan_decode(B, NH, NKV, HS, capacity, window, len_hint, false, false, true), names, buf, cap);
 }
 
 }  // extern "C"

@@ -7,10 +7,16 @@
 //   read     a cached value is bf16_rne(float(e4m3) * scale) -- the bits dequantize_to_bf16 produces -- in the decode kernel's registers, or in a transient bf16
 //            cache for the prefill, which then runs the bf16 flash kernels: both see the same K / V values, the attention arithmetic is the bf16 cache's.
 //
-// Decode (the hot path): the split-K flash decode of attention.hip (Gqa.Decode.Bf16.cu:93-105, :212, :297-351) with the row loads at one byte per element.  A lane
-// loads 4 bytes of a row (8 at HS 512), so a row is HS / 4 lanes wide: one row per wave-instruction at HS 256 / 512, two at HS 128 (half-waves), four at HS 64
-// (16-lane rows).  Each lane segment keeps its own online-softmax state over its own positions; the segments of a wave are merged in registers, the eight waves
-// through LDS, the splits by attention.hip's combine kernel from partials in its layout.  Grid and split count are plan_decode's scalar form for the same shape.
+// Decode (the hot path), two kernels chosen by attention.hip's plan_decode exactly as it chooses between the bf16 cache's two:
+//   attn_decode_kvfp8_kernel       the split-K flash decode of attention.hip (Gqa.Decode.Bf16.cu:93-105, :212, :297-351) with the row loads at one byte per element.  A
+//     lane loads 4 bytes of a row (8 at HS 512), so a row is HS / 4 lanes wide: one row per wave-instruction at HS 256 / 512, two at HS 128 (half-waves), four at
+//     HS 64 (16-lane rows).  Each lane segment keeps its own online-softmax state over its own positions; the segments of a wave are merged in registers, the eight
+//     waves through LDS, the splits by attention.hip's combine kernel from partials in its layout.
+//   attn_decode_kvfp8_mfma_kernel  16 query heads on one KV head at HS 512 over a long band (from the 8192-key bucket): the matrix-core decode -- the tile body of
+//     attention_decode_mfma.h under the e4m3 staging policy (16-byte e4m3 chunks + row scales -> registers -> bf16 values in the bf16 kernel's LDS images), up to 256
+//     splits merged by attn_combine_many_kernel.  From LDS on it IS attn_decode_mfma_kernel: the same bits as attn_decode_bf16 on the dequantized cache.
+// Both take the live length either as a launch argument or (the device-position entries, for graph replay) from device memory.
+#include "attention_decode_mfma.h"
 #include "attention_decode_plan.h"
 #include "attention_tiles.h"      // kKeysPerTile: the flash prefill streams whole key tiles
 #include "fp8_quant.h"
@@ -22,7 +28,7 @@ namespace mila {
 template <int HS>
 __global__ __launch_bounds__(256) void kv_write_fp8_kernel(uint8_t* __restrict__ K8, uint8_t* __restrict__ V8, float* __restrict__ Ks, float* __restrict__ Vs,
                                                            const uint16_t* __restrict__ k, const uint16_t* __restrict__ v, int64_t rows, int chunk, int NKV,
-                                                           int start_pos, int capacity)
+                                                           int start_pos, const int32_t* __restrict__ pos_dev, int capacity)
 {
     constexpr int EPL = HS >= 512 ? 8 : 4, ACTIVE = HS / EPL;
     const int lane = threadIdx.x & 63;
@@ -34,7 +40,8 @@ __global__ __launch_bounds__(256) void kv_write_fp8_kernel(uint8_t* __restrict__
     r /= NKV;
     const int t = (int)(r % chunk), b = (int)(r / chunk);
     const uint16_t* src = (is_v ? v : k) + (((size_t)b * chunk + t) * NKV + n) * HS;
-    const size_t drow = ((size_t)b * NKV + n) * capacity + (size_t)((start_pos + t) % capacity);
+    const int first = pos_dev ? *pos_dev : start_pos;                    // (the device-position form appends one token at *pos_dev)
+    const size_t drow = ((size_t)b * NKV + n) * capacity + (size_t)((first + t) % capacity);
     const bool act = lane < ACTIVE;
     uint32_t x[EPL / 2];
 #pragma unroll
@@ -108,6 +115,7 @@ struct KvFp8DecodeParams
     float* scratch;           // [B, NH, splits, HS+4] partials when splits > 1 (attention.hip's layout)
     int NH, NKV, capacity, len, window, splits;
     float scale;
+    const int32_t* pos_dev;   // when set: len = *pos_dev + 1, read by the kernels (graph replay); null in the eager form
 };
 
 constexpr int kKvFp8Waves = 8;     // 512 threads per workgroup, as attn_decode_kernel
@@ -152,12 +160,12 @@ __global__ __launch_bounds__(kKvFp8Waves * 64) void attn_decode_kvfp8_kernel(con
     const int kvh = grp / hgroups, hg = grp % hgroups;
     const int h0 = kvh * GS + hg * GH;                     // first query head of this workgroup
     const int b = blockIdx.z;
-    const int len = p.len;
+    const int len = p.pos_dev ? *p.pos_dev + 1 : p.len;
     const int band_begin = (p.window > 0) ? max(0, len - p.window) : 0;
     const int band = len - band_begin;
     const int chunk = (band + p.splits - 1) / p.splits;
     const int begin = band_begin + split * chunk;
-    const int end = min(begin + chunk, len);
+    const int end = min(begin + chunk, len);      // (a split past the live band: begin >= end, nothing is loaded, its partial is O = 0, M = -inf, L = 0)
 
     const size_t head = ((size_t)b * p.NKV + kvh) * p.capacity;
     const uint8_t* kbase = p.K8 + head * HS + ll * EPL;
@@ -398,6 +406,35 @@ static int dispatch_kvfp8_gh(const KvFp8DecodeParams& p, int B, int gh, int hgro
     return set_error(MILA_E_UNSUPPORTED, "attn_decode_kvfp8: no kernel for %d heads per workgroup at HS=%d", gh, HS);
 }
 
+// ---- the matrix-core decode (attention_decode_mfma.h): grid (splits, NKV * GS / 16, B), 256 threads ----
+template <int HS>
+__global__ __launch_bounds__(256) void attn_decode_kvfp8_mfma_kernel(const KvFp8DecodeParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_kvfp8_mfma[];
+    const int len = p.pos_dev ? *p.pos_dev + 1 : p.len;
+    const MfmaDecodeArgs a{p.Q, 0, p.scratch, p.NH, p.NKV, p.capacity, len, p.window, p.splits, p.scale};
+    attn_decode_mfma_body<HS>(a, MfmaStageKvFp8<HS>{p.K8, p.V8, p.Ks, p.Vs}, smem_kvfp8_mfma);
+}
+static int launch_decode_kvfp8_mfma(const KvFp8DecodeParams& p, int B, hipStream_t s)
+{
+    constexpr int HS = 512;
+    note_form("attn_decode_kvfp8_mfma");
+    static bool attr_set = false;
+    const size_t lds = mfma_decode_lds_bytes<HS>();      // what attn_decode_mfma_kernel asks for: the images are the same
+    if (!attr_set)
+    {
+        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_kvfp8_mfma_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                           "hipFuncSetAttribute(attn_decode_kvfp8_mfma)");
+        if (rc) return rc;
+        attr_set = true;
+    }
+    const int n16 = (p.NH / p.NKV) / 16;
+    hipLaunchKernelGGL((attn_decode_kvfp8_mfma_kernel<HS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, p);
+    int rc = check_hip(hipGetLastError(), "attn_decode_kvfp8_mfma");
+    if (rc) return rc;
+    return launch_attn_combine_many(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
+}
+
 static bool kvfp8_head_size(int HS) { return HS == 64 || HS == 128 || HS == 256 || HS == 512; }
 static size_t kvfp8_transient_bytes(int B, int NKV, int HS, int capacity) { return 2 * (size_t)B * NKV * capacity * HS * sizeof(uint16_t); }
 
@@ -407,6 +444,24 @@ using namespace mila;
 
 extern "C" {
 
+// the append launch of both write entries: `chunk` tokens from start_pos, or (pos_dev) one token at *pos_dev
+static int launch_kv_write_fp8(const char* who, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* k, const uint16_t* v, int B, int chunk, int NKV, int HS, int start_pos,
+                               const int32_t* pos_dev, int capacity, mila_stream_t stream)
+{
+    const int64_t rows = (int64_t)B * chunk * NKV;
+    MILA_REQUIRE((2 * rows + 3) / 4 <= 0x7fffffffLL, "%s: too many rows for one launch", who);
+    const dim3 grid((unsigned)((2 * rows + 3) / 4));
+    hipStream_t s = as_stream(stream);
+    switch (HS)
+    {
+        case 64: hipLaunchKernelGGL(kv_write_fp8_kernel<64>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, pos_dev, capacity); break;
+        case 128: hipLaunchKernelGGL(kv_write_fp8_kernel<128>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, pos_dev, capacity); break;
+        case 256: hipLaunchKernelGGL(kv_write_fp8_kernel<256>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, pos_dev, capacity); break;
+        default: hipLaunchKernelGGL(kv_write_fp8_kernel<512>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, pos_dev, capacity); break;
+    }
+    return check_hip(hipGetLastError(), who);
+}
+
 int mila_cdna4_kv_write_fp8(uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* k, const uint16_t* v, int B, int chunk, int NKV, int HS, int start_pos,
                             int capacity, mila_stream_t stream)
 {
@@ -415,18 +470,16 @@ int mila_cdna4_kv_write_fp8(uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, cons
     MILA_REQUIRE(kvfp8_head_size(HS), "kv_write_fp8: HS=%d must be 64, 128, 256 or 512", HS);
     MILA_REQUIRE(start_pos >= 0, "kv_write_fp8: negative start position");
     MILA_REQUIRE(chunk <= capacity, "kv_write_fp8: chunk %d exceeds the cache capacity %d", chunk, capacity);
-    const int64_t rows = (int64_t)B * chunk * NKV;
-    MILA_REQUIRE((2 * rows + 3) / 4 <= 0x7fffffffLL, "kv_write_fp8: too many rows for one launch");
-    const dim3 grid((unsigned)((2 * rows + 3) / 4));
-    hipStream_t s = as_stream(stream);
-    switch (HS)
-    {
-        case 64: hipLaunchKernelGGL(kv_write_fp8_kernel<64>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, capacity); break;
-        case 128: hipLaunchKernelGGL(kv_write_fp8_kernel<128>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, capacity); break;
-        case 256: hipLaunchKernelGGL(kv_write_fp8_kernel<256>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, capacity); break;
-        default: hipLaunchKernelGGL(kv_write_fp8_kernel<512>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, capacity); break;
-    }
-    MILA_LAUNCH_CHECK("kv_write_fp8");
+    return launch_kv_write_fp8("kv_write_fp8", K8, V8, Ks, Vs, k, v, B, chunk, NKV, HS, start_pos, nullptr, capacity, stream);
+}
+
+int mila_cdna4_kv_write_fp8_devpos(uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* k, const uint16_t* v, int B, int NKV, int HS, const int32_t* position_dev,
+                                   int capacity, mila_stream_t stream)
+{
+    MILA_REQUIRE(K8 && V8 && Ks && Vs && k && v && position_dev, "kv_write_fp8_devpos: null pointer");
+    MILA_REQUIRE(B > 0 && NKV > 0 && capacity > 0, "kv_write_fp8_devpos: bad sizes");
+    MILA_REQUIRE(kvfp8_head_size(HS), "kv_write_fp8_devpos: HS=%d must be 64, 128, 256 or 512", HS);
+    return launch_kv_write_fp8("kv_write_fp8_devpos", K8, V8, Ks, Vs, k, v, B, 1, NKV, HS, 0, position_dev, capacity, stream);
 }
 
 int mila_cdna4_kv_dequant_fp8_bf16(uint16_t* Kc_bf16, uint16_t* Vc_bf16, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, int B, int NKV, int HS,
@@ -444,23 +497,25 @@ int mila_cdna4_kv_dequant_fp8_bf16(uint16_t* Kc_bf16, uint16_t* Vc_bf16, const u
     MILA_LAUNCH_CHECK("kv_dequant_fp8_bf16");
 }
 
-int mila_cdna4_attn_decode_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
-                                 int B, int NH, int NKV, int HS, int capacity, int len, int window, float scale, mila_stream_t stream)
+// what the two decode entries share: the checks (`who` names the entry in the messages; `len` is the live length of the eager entry, the captured bound max_len of
+// the device-position one), the plan for that length's band bucket, the launch of the plan's form
+static int kvfp8_decode(const char* who, uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
+                        int B, int NH, int NKV, int HS, int capacity, int len, const int32_t* pos_dev, int window, float scale, mila_stream_t stream)
 {
-    MILA_REQUIRE(Y && Q && K8 && V8 && Ks && Vs, "attn_decode_kvfp8: null pointer");
-    MILA_REQUIRE(B > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "attn_decode_kvfp8: bad head counts (NH=%d NKV=%d)", NH, NKV);
-    MILA_REQUIRE(kvfp8_head_size(HS), "attn_decode_kvfp8: HS=%d must be 64, 128, 256 or 512", HS);
+    MILA_REQUIRE(B > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "%s: bad head counts (NH=%d NKV=%d)", who, NH, NKV);
+    MILA_REQUIRE(kvfp8_head_size(HS), "%s: HS=%d must be 64, 128, 256 or 512", who, HS);
     const int GS = NH / NKV;
-    MILA_REQUIRE(GS == 1 || GS == 2 || GS == 4 || GS == 8 || GS == 16 || GS == 32, "attn_decode_kvfp8: group size %d (NH/NKV) must be 1,2,4,8,16 or 32", GS);
-    MILA_REQUIRE(len > 0 && capacity > 0, "attn_decode_kvfp8: len and capacity must be positive (len=%d capacity=%d)", len, capacity);
-    MILA_REQUIRE(window >= 0, "attn_decode_kvfp8: negative window");
+    MILA_REQUIRE(GS == 1 || GS == 2 || GS == 4 || GS == 8 || GS == 16 || GS == 32, "%s: group size %d (NH/NKV) must be 1,2,4,8,16 or 32", who, GS);
+    MILA_REQUIRE(len > 0 && capacity > 0, "%s: %s and capacity must be positive (%s=%d capacity=%d)", who, pos_dev ? "max_len" : "len", pos_dev ? "max_len" : "len", len, capacity);
+    MILA_REQUIRE(window >= 0, "%s: negative window", who);
     const int band = (window > 0 && window < len) ? window : len;
-    MILA_REQUIRE(band <= capacity, "attn_decode_kvfp8: live band %d exceeds the cache capacity %d", band, capacity);
-    const ScalarDecodeShape d = plan_decode_scalar(B, NH, NKV, HS, capacity, window, len);
-    MILA_REQUIRE(!d.scratch_need || (scratch && scratch_bytes >= d.scratch_need), "attn_decode_kvfp8: scratch %zu bytes < required %zu (ask attn_decode_scratch_bytes)",
-                 scratch_bytes, d.scratch_need);
-    KvFp8DecodeParams p{Y, Q, K8, V8, Ks, Vs, reinterpret_cast<float*>(scratch), NH, NKV, capacity, len, window, d.splits, scale};
+    MILA_REQUIRE(band <= capacity, "%s: live band %d exceeds the cache capacity %d", who, band, capacity);
+    const KvFp8DecodeShape d = plan_decode_kvfp8(B, NH, NKV, HS, capacity, window, len);
+    MILA_REQUIRE(!d.scratch_need || (scratch && scratch_bytes >= d.scratch_need), "%s: scratch %zu bytes < required %zu (ask attn_decode_scratch_bytes)", who, scratch_bytes,
+                 d.scratch_need);
+    KvFp8DecodeParams p{Y, Q, K8, V8, Ks, Vs, reinterpret_cast<float*>(scratch), NH, NKV, capacity, len, window, d.splits, scale, pos_dev};
     hipStream_t s = as_stream(stream);
+    if (d.mfma) return launch_decode_kvfp8_mfma(p, B, s);      // (HS 512 by the plan's rule)
     switch (HS)
     {
         case 64: return dispatch_kvfp8_gh<64>(p, B, d.gh, d.hgroups, s);
@@ -468,6 +523,20 @@ int mila_cdna4_attn_decode_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* 
         case 256: return dispatch_kvfp8_gh<256>(p, B, d.gh, d.hgroups, s);
         default: return dispatch_kvfp8_gh<512>(p, B, d.gh, d.hgroups, s);
     }
+}
+
+int mila_cdna4_attn_decode_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
+                                 int B, int NH, int NKV, int HS, int capacity, int len, int window, float scale, mila_stream_t stream)
+{
+    MILA_REQUIRE(Y && Q && K8 && V8 && Ks && Vs, "attn_decode_kvfp8: null pointer");
+    return kvfp8_decode("attn_decode_kvfp8", Y, Q, K8, V8, Ks, Vs, scratch, scratch_bytes, B, NH, NKV, HS, capacity, len, nullptr, window, scale, stream);
+}
+
+int mila_cdna4_attn_decode_kvfp8_devpos(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
+                                        int B, int NH, int NKV, int HS, int capacity, const int32_t* position_dev, int max_len, int window, float scale, mila_stream_t stream)
+{
+    MILA_REQUIRE(Y && Q && K8 && V8 && Ks && Vs && position_dev, "attn_decode_kvfp8_devpos: null pointer");
+    return kvfp8_decode("attn_decode_kvfp8_devpos", Y, Q, K8, V8, Ks, Vs, scratch, scratch_bytes, B, NH, NKV, HS, capacity, max_len, position_dev, window, scale, stream);
 }
 
 size_t mila_cdna4_attn_prefill_kvfp8_scratch_bytes(int B, int NKV, int HS, int capacity)

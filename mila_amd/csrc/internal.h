@@ -48,6 +48,7 @@ MILA_API size_t mila_cdna4_attn_decode_plan_describe(int B, int NH, int NKV, int
  *   gemm_fp8.skinny_whole_x, gemm_fp8.big_rule, gemm_fp8.splitk_min_rows      the skinny kernel's barrier-free <= 4-row form (1); which row counts below 512 take the LDS-DMA
  *                          kernels (rules 0 .. 3 of the fp8 plan, csrc/gemm_plan.hip; 3); row counts below this stay off the fp8 split-K form (17)
  *   attn.positions_per_split, attn.max_workgroups, attn.heads_per_group_512, attn.xcd_local, attn.mfma_decode, attn.mfma_min_band      decode attention (csrc/attention.hip)
+ *   attn.kvfp8_mfma_decode 0 = the fp8 KV cache's decode (csrc/attention_kvfp8.hip) keeps to the wave-per-position kernel where the plan would take the matrix-core one (default 1)
  *   flash.form             8 (default) = the LDS-DMA forms; 9 = lockstep 8-wave workgroups at HS 256 too; 10 = the ping-pong 8-wave form; 11 = the software-pipelined loop; 2 = HS 512 as 4-wave d-split
  *                          workgroups; 1 = the register-staged kernels.  Same bits.                                                       (csrc/attention_prefill.hip) */
 /* engine diagnostics: the next decode_engine launches write wall-clock stamps (100 MHz) of the first 8 workgroups' 8 waves, 16 slots each */

@@ -665,6 +665,8 @@ class GqaComponent:
         lib.mila_gqa_init_cache.argtypes = [vp]
         lib.mila_gqa_prefill.argtypes = [vp, vp, vp, vp, i64, i64, vp]
         lib.mila_gqa_decode.argtypes = [vp, vp, vp, vp, i64, vp]
+        lib.mila_gqa_decode_at.argtypes = [vp, vp, vp, vp, i64, i64, vp]
+        lib.mila_gqa_note_cache_length.argtypes = [vp, i64]
         lib.mila_gqa_rewind.argtypes = [vp, i64]
         lib.mila_gqa_state_bytes.argtypes = [vp, vp]
         lib.mila_gqa_read_cache.argtypes = [vp, vp, vp, vp, vp]
@@ -703,6 +705,17 @@ class GqaComponent:
         y = np.empty((self.B, self.NH * self.HS), dtype=np.uint16)
         self._check(load().mila_gqa_decode(self.h, q.ctypes.data, k.ctypes.data, v.ctypes.data, position, y.ctypes.data))
         return y
+
+    def decode_at(self, q, k, v, position, max_len):
+        """decode() with the position read from DEVICE memory by the kernels (the op's decodeAt; fp8 policy only): max_len bounds the live length inside its band
+        bucket.  state()["length"] does not move: follow up with note_cache_length(position + 1)"""
+        q, k, v = self._rows(q), self._rows(k), self._rows(v)
+        y = np.empty((self.B, self.NH * self.HS), dtype=np.uint16)
+        self._check(load().mila_gqa_decode_at(self.h, q.ctypes.data, k.ctypes.data, v.ctypes.data, position, max_len, y.ctypes.data))
+        return y
+
+    def note_cache_length(self, length):
+        self._check(load().mila_gqa_note_cache_length(self.h, length))
 
     def rewind(self, length):
         self._check(load().mila_gqa_rewind(self.h, length))

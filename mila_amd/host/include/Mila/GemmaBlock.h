@@ -161,6 +161,18 @@ namespace Mila::Dnn
             decode_active_ = true;
             return *view_;
         }
+        /// decode() at the position held in device memory (the ops that have a device-position form: the FP8 KV policy's); max_len bounds the live length inside its
+        /// band bucket.  The cache length is the caller's to report afterwards: noteCacheLength( position + 1 )
+        TensorType& decodeAt( const TensorType& q, const TensorType& k, const TensorType& v, const int32_t* position_dev, dim_t max_len )
+        {
+            requireBuilt( "decodeAt" );
+            const dim_t B = q.shape()[ 0 ];
+            checkOperands( q, k, v, B, 1 );
+            view_ = std::make_unique<TensorType>( output_->view( shape_t{ B, 1, config_.getModelDim() } ) );
+            operation_->decodeAt( q, k, v, *view_, position_dev, static_cast<int>( max_len ) );
+            decode_active_ = true;
+            return *view_;
+        }
         /// the chunk's K/V rows were already appended by the fused q/k/v post-processing kernel: attention only, into a caller tensor
         void prefillFromCache( const TensorType& q, TensorType& out, int chunk, int position ) { operation_->prefillFromCache( q, out, chunk, position ); }
 

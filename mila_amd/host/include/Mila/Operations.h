@@ -826,7 +826,8 @@ namespace Mila::Dnn::Compute
     /// The op row of Quant::KvCache::PerChannelKvFp8<> (Quantization/KvCache/QuantPolicy.ixx:56-88; the reference's BACKLOG names the row
     /// OperationTraits<GqaOp, Cuda, BF16, PerChannelKvFp8<>> and has no kernels for it): the public methods of RocmGqaOpBase over an op-owned e4m3 cache with one
     /// fp32 scale per KV head per cached token (csrc/attention_kvfp8.hip).  The cache is unbounded: capacity = max_seq.  Queries, outputs and the appended K / V
-    /// rows stay BF16; a cached value is read back as bf16( e4m3 * scale ) -- in registers by the decode kernel, in a transient bf16 cache by the prefill.
+    /// rows stay BF16; a cached value is read back as bf16( e4m3 * scale ) -- by the decode kernels in registers (on the way into LDS in the matrix-core form a 16-head
+    /// group takes from the 8192-key bucket on), in a transient bf16 cache by the prefill.
     class RocmGqaKvFp8Op : public Operation<DeviceType::Rocm, TensorDataType::BF16>
     {
     public:
@@ -864,7 +865,12 @@ namespace Mila::Dnn::Compute
             length_ = length;      // unbounded: every earlier row is still there, and a row's bytes and scale do not depend on later rows
         }
         dim_t cacheLength() const noexcept { return length_; }
-        void noteCacheLength( dim_t ) { throw std::logic_error( "RocmGqaKvFp8Op::noteCacheLength: " + std::string( kFusedOnly ) ); }
+        /// a caller that appended through decodeAt() (whose position lives on the device) reports how far it wrote
+        void noteCacheLength( dim_t length )
+        {
+            if ( length < 0 || length > capacity_ ) throw std::invalid_argument( "RocmGqaKvFp8Op::noteCacheLength: length outside [0, capacity]" );
+            length_ = length;
+        }
         dim_t cacheCapacity() const noexcept { return capacity_; }
 
         /// q [B,chunk,NH*HS], k/v [B,chunk,NKV*HS] at absolute positions [position, position+chunk): quantizing append, then the bf16 flash prefill on the band
@@ -900,6 +906,23 @@ namespace Mila::Dnn::Compute
             rocmCheck( mila_cdna4_attn_decode_kvfp8( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, NH, NKV, HS, cap,
                                                      position + 1, (int)cfg_.window, scale(), context_->getStream() ) );
             length_ = position + 1;
+        }
+
+        /// decode() with the position in DEVICE memory (graph replay: one captured launch sequence serves every step): appends the token at row *position_dev and
+        /// attends over *position_dev + 1 keys.  max_len: an upper bound of the live length inside its band bucket (mila_cdna4_attn_decode_band_bucket), which fixes
+        /// the kernel form and split count -- any bound of the bucket gives decode()'s bits.  The op cannot see the device value: cacheLength() is unchanged, the
+        /// caller follows up with noteCacheLength( position + 1 ) once it knows the position on the host.
+        void decodeAt( const TensorType& q, const TensorType& k, const TensorType& v, TensorType& out, const int32_t* position_dev, int max_len )
+        {
+            requireCache();
+            if ( !position_dev ) throw std::invalid_argument( "RocmGqaKvFp8Op::decodeAt: null device position" );
+            mila_stream_t st = context_->getStream();
+            const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
+            rocmCheck( mila_cdna4_kv_write_fp8_devpos( k8_->data(), v8_->data(), ks_->data(), vs_->data(), q_cast( k ), q_cast( v ), batch_, NKV, HS, position_dev, cap, st ) );
+            const size_t need = mila_cdna4_attn_decode_scratch_bytes( batch_, NH, HS );
+            void* scratch = context_->getScratch( need );   // fetched per call, never cached
+            rocmCheck( mila_cdna4_attn_decode_kvfp8_devpos( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, NH, NKV, HS, cap,
+                                                            position_dev, max_len, (int)cfg_.window, scale(), st ) );
         }
 
         /// these three exist for the fused q/k/v post-processing entries (fused_qkv_post, fused_attn_decode), which write a bf16 cache through raw pointers

@@ -1,6 +1,6 @@
 // C entry points for ONE GroupedQueryAttention<Rocm, BF16, TKvPolicy> component of the host mirror, for the three KV-cache policies
-// (Quantization/KvCache: NoKvCompression, SlidingWindowKvCache, PerChannelKvFp8<>): build, chunked prefill, decode, rewind, state bytes and a read-back of the
-// cache arrays (tests/test_kvfp8_host_gpu.py).  Errors go to the message mila_host_last_error() returns.
+// (Quantization/KvCache: NoKvCompression, SlidingWindowKvCache, PerChannelKvFp8<>): build, chunked prefill, decode, the device-position decode of the FP8 policy,
+// rewind, state bytes and a read-back of the cache arrays (tests/test_kvfp8_host_gpu.py, tests/test_kvfp8_decode_at_host_gpu.py).  Errors go to the message mila_host_last_error() returns.
 #include <cstring>
 #include <memory>
 #include <string>
@@ -27,6 +27,7 @@ namespace
         std::variant<std::unique_ptr<Plain>, std::unique_ptr<Ring>, std::unique_ptr<Fp8>> gqa;
         dim_t B, NH, NKV, HS, max_seq, chunk;
         std::unique_ptr<TensorType> q, k, v;
+        std::unique_ptr<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>> position;      ///< decodeAt's device position
     };
     template<typename F> int guarded( F&& f )
     {
@@ -83,6 +84,7 @@ HOST_API void* mila_gqa_create( int kv_policy, const mila_gqa_op_config* cfg, in
         r->q = std::make_unique<TensorType>( r->ctx->getDeviceId(), shape_t{ batch, r->chunk, c.num_heads * c.head_dim } );
         r->k = std::make_unique<TensorType>( r->ctx->getDeviceId(), shape_t{ batch, r->chunk, c.num_kv_heads * c.head_dim } );
         r->v = std::make_unique<TensorType>( r->ctx->getDeviceId(), shape_t{ batch, r->chunk, c.num_kv_heads * c.head_dim } );
+        r->position = std::make_unique<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>>( r->ctx->getDeviceId(), shape_t{ 1 } );
         out = r.release();
     } );
     return rc == 0 ? out : nullptr;
@@ -127,6 +129,38 @@ HOST_API int mila_gqa_decode( void* h, const uint16_t* q, const uint16_t* k, con
             rocm( r )->synchronize();
         }, r->gqa );
     } );
+}
+
+/// GroupedQueryAttention::decodeAt: the same step with the position in device memory (`position` is copied there first) and the live-length bound max_len; the
+/// component's cache length is NOT advanced (mila_gqa_note_cache_length).  PerChannelKvFp8<> only: the bf16 policies answer MILA_E_UNSUPPORTED
+HOST_API int mila_gqa_decode_at( void* h, const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t position, int64_t max_len, uint16_t* y )
+{
+    auto* r = static_cast<GqaRunner*>( h );
+    return guarded( [&]
+    {
+        if ( position < 0 || position > INT32_MAX || max_len <= 0 || max_len > INT32_MAX ) throw std::invalid_argument( "mila_gqa_decode_at: position or max_len out of range" );
+        auto qv = upload( r, *r->q, q, 1, r->NH * r->HS ), kv = upload( r, *r->k, k, 1, r->NKV * r->HS ), vv = upload( r, *r->v, v, 1, r->NKV * r->HS );
+        const int32_t pos = static_cast<int32_t>( position );
+        Compute::rocmCheck( mila_cdna4_memcpy_h2d( r->position->rawData(), &pos, sizeof( pos ), rocm( r )->getStream() ) );
+        std::visit( [&]( auto& g )
+        {
+            if constexpr ( std::is_same_v<typename std::decay_t<decltype( *g )>::OpType, Compute::RocmGqaKvFp8Op> )
+            {
+                auto& out = g->decodeAt( qv, kv, vv, static_cast<const int32_t*>( r->position->rawData() ), max_len );
+                copyToHost( y, out, static_cast<size_t>( r->B * r->NH * r->HS ) * 2, rocm( r ) );
+                rocm( r )->synchronize();
+            }
+            else
+                throw std::logic_error( "mila_gqa_decode_at: only the PerChannelKvFp8<> op has a device-position decode" );
+        }, r->gqa );
+    } );
+}
+
+/// the component's noteCacheLength( length ): what a caller of decodeAt reports once it knows the position
+HOST_API int mila_gqa_note_cache_length( void* h, int64_t length )
+{
+    auto* r = static_cast<GqaRunner*>( h );
+    return guarded( [&] { std::visit( [&]( auto& g ) { g->noteCacheLength( length ); }, r->gqa ); } );
 }
 
 /// the op's rewindKvCache( length ): throws where the component's bool-returning form would return false

@@ -1,10 +1,12 @@
 """Decode attention over the FP8 KV cache (attn_decode_kvfp8, csrc/attention_kvfp8.hip) against the bf16 cache (attn_decode_bf16) on the same box in the same
 process, at Gemma's two layer geometries:
     local   NH 16, NKV 8, HS 256, window 1024, len 2048
-    global  NH 16, NKV 1, HS 512, unwindowed, len 2048 / 8192 / 32768      (from 8192 keys on the bf16 side runs its matrix-core form: the honest competitor)
+    global  NH 16, NKV 1, HS 512, unwindowed, len 2048 / 8192 / 16384 / 32768      (from 8192 keys on both caches run their matrix-core forms)
+Three legs: attn_decode_bf16, attn_decode_kvfp8 as planned, and attn_decode_kvfp8 under attn.kvfp8_mfma_decode 0 (the wave-per-position kernel at every length: what the
+fp8 cache ran before it had a matrix-core form) -- the tuning is set before that leg's pass and reset after it.
 Method: a pair of HIP events around every launch (attention + combine), the launches of a pass walking a ROTATION of cache copies whose total size exceeds the
-256 MiB Infinity Cache, so every launch streams its K / V from HBM.  Both entries are warmed up, then timed in alternating passes; the figure is the median over all
-timed launches (passes x copies), the minimum beside it.  Both caches hold the same random K / V (the fp8 one through kv_write_fp8).  Bytes are the live band's: band x NKV x 2 x HS x 2 for bf16,
+256 MiB Infinity Cache, so every launch streams its K / V from HBM.  The entries are warmed up, then timed in alternating passes; the figure is the median over all
+timed launches (passes x copies), the minimum beside it, and the spread of the per-pass medians (what a difference between two legs has to exceed).  Both caches hold the same random K / V (the fp8 one through kv_write_fp8).  Bytes are the live band's: band x NKV x 2 x HS x 2 for bf16,
 band x NKV x 2 x (HS + 4) for fp8.
     python tools/bench_attn_kvfp8.py [--passes 15] [--out FILE]  ->  one JSON line per case"""
 import os
@@ -25,6 +27,7 @@ CASES = [
     ("gemma_local", 16, 8, 256, 1024, 2048),
     ("gemma_global", 16, 1, 512, 0, 2048),
     ("gemma_global", 16, 1, 512, 0, 8192),
+    ("gemma_global", 16, 1, 512, 0, 16384),
     ("gemma_global", 16, 1, 512, 0, 32768),
 ]
 ROTATION_BYTES = 320 << 20      # > the 256 MiB Infinity Cache
@@ -59,11 +62,21 @@ def bench(name, NH, NKV, HS, window, length, passes):
     run16 = lambda s: capi.call("attn_decode_bf16", Y16, q, s[0], s[1], scratch, C.c_size_t(nb), B, NH, NKV, HS, cap, length, window, 1.0)
     run8 = lambda s: capi.call("attn_decode_kvfp8", Y8, q, s[0], s[1], s[2], s[3], scratch, C.c_size_t(nb), B, NH, NKV, HS, cap, length, window, 1.0)
 
+    def scalar_leg(fn):
+        """fn() under attn.kvfp8_mfma_decode 0"""
+        capi.tune("attn.kvfp8_mfma_decode", 0)
+        try:
+            return fn()
+        finally:
+            capi.tune_reset()
+
     capi.last_form()
     run16(sets16[0])
     form16 = "+".join(capi.last_form())
     run8(sets8[0])
     form8 = "+".join(capi.last_form())
+    scalar_leg(lambda: run8(sets8[0]))
+    form8s = "+".join(capi.last_form())
     torch.cuda.synchronize()
     # the two caches hold the same K / V up to the fp8 rounding: the outputs must agree to that rounding (a faster, different answer is no answer)
     diff = (Y16.view(torch.bfloat16).float() - Y8.view(torch.bfloat16).float()).abs().max().item()
@@ -81,14 +94,25 @@ def bench(name, NH, NKV, HS, window, length, passes):
     for _ in range(3):      # warm-up: code objects, clocks, both rotations
         one_pass(run16, sets16)
         one_pass(run8, sets8)
-    t16, t8 = [], []
+        scalar_leg(lambda: one_pass(run8, sets8))
+    t16, t8, t8s = [], [], []      # one list of launches per pass
     for _ in range(passes):
-        t16 += one_pass(run16, sets16)
-        t8 += one_pass(run8, sets8)
-    m16, m8 = statistics.median(t16), statistics.median(t8)
+        t16.append(one_pass(run16, sets16))
+        t8.append(one_pass(run8, sets8))
+        t8s.append(scalar_leg(lambda: one_pass(run8, sets8)))
+    flat = lambda t: [x for p in t for x in p]
+    med = lambda t: statistics.median(flat(t))
+    spread = lambda t: round(max(statistics.median(p) for p in t) - min(statistics.median(p) for p in t), 2)      # between the passes' own medians
+    m16, m8, m8s = med(t16), med(t8), med(t8s)
     return {"case": name, "NH": NH, "NKV": NKV, "HS": HS, "window": window, "len": length, "band": band,
-            "bf16_form": form16, "fp8_form": form8, "bf16_us": round(m16, 2), "bf16_min_us": round(min(t16), 2), "fp8_us": round(m8, 2), "fp8_min_us": round(min(t8), 2),
-            "fp8_over_bf16": round(m8 / m16, 3), "bf16_band_bytes": bytes16, "fp8_band_bytes": bytes8,
+            "bf16_form": form16, "fp8_form": form8, "fp8_scalar_form": form8s,
+            "bf16_us": round(m16, 2), "bf16_min_us": round(min(flat(t16)), 2), "bf16_pass_spread_us": spread(t16),
+            "fp8_us": round(m8, 2), "fp8_min_us": round(min(flat(t8)), 2), "fp8_pass_spread_us": spread(t8),
+            "fp8_scalar_us": round(m8s, 2), "fp8_scalar_min_us": round(min(flat(t8s)), 2), "fp8_scalar_pass_spread_us": spread(t8s),
+            "fp8_over_bf16": round(m8 / m16, 3), "fp8_scalar_over_bf16": round(m8s / m16, 3), "fp8_over_fp8_scalar": round(m8 / m8s, 3),
+            "pass_medians_us": {"bf16": [round(statistics.median(p), 2) for p in t16], "fp8": [round(statistics.median(p), 2) for p in t8],
+                                "fp8_scalar": [round(statistics.median(p), 2) for p in t8s]},
+            "bf16_band_bytes": bytes16, "fp8_band_bytes": bytes8,
             "bf16_GBps": round(bytes16 / m16 / 1e3, 1), "fp8_GBps": round(bytes8 / m8 / 1e3, 1),
             "copies": [len(sets16), len(sets8)], "passes": passes, "max_abs_output_diff": diff}
 
