@@ -196,7 +196,9 @@ def test_fused_attn_decode_takes_a_batch_like_the_reference_kernels(B, NH, NKV, 
               scratch, C.c_size_t(nbytes), B, NH, NKV, HS, cap, pos, None, window, 1.0, 1e-6)
     assert np.array_equal(bits(K1), bits(K0)) and np.array_equal(bits(V1), bits(V0)), "cache rows differ"
     assert np.array_equal(bits(y1), bits(y0)), "attention output differs"
-    # and against the oracle on one row: norm -> rope -> attention over that row's history
+    # (against the oracle -- norm -> rope -> attention over each batch row's OWN history, dead cache rows NaN -- the chain is held by
+    # tests/test_attn_decode_classes_gpu.py::test_fused_prologue_equals_the_chain_and_the_oracle_in_every_class: the caches here are random and alike in kind for every
+    # row, so a batch stride that is wrong in the chain and in the one-launch form alike would not show in this test)
     with pytest.raises(capi.InvalidArgument):
         capi.call("fused_attn_decode_batch_bf16", y1, K1, V1, rows_d[0, q_off:], rows_d[0, k_off:], rows_d[0, v_off:], C.c_int64(8), qw, kw, None, cos, sin,
                   scratch, C.c_size_t(nbytes), B, NH, NKV, HS, cap, pos, None, window, 1.0, 1e-6)
