@@ -291,6 +291,13 @@ MILA_API int mila_cdna4_mha_decode_bf16(uint16_t* Y, const uint16_t* QKV, uint16
  *   attn_prefill_kvfp8: attn_prefill_bf16 over this cache (CudaGqa.cuh flash-prefill launchers): the chunk's band [max(0, pos_offset - window + 1), pos_offset + chunk)
  *     (from 0 when unwindowed; extended down to the 32-key tile boundary the flash kernels start streaming from) is dequantized into two transient bf16 caches in
  *     `scratch` (attn_prefill_kvfp8_scratch_bytes, 16-byte aligned), then the bf16 kernels run on them.  The cache must already contain the chunk (kv_write_fp8 first).
+ *   fused_qkv_post_kvfp8 / _prefill / _devpos: fused_qkv_post / fused_qkv_post_prefill / fused_qkv_post_devpos (below) with a quantizing append, B == 1:
+ *     q_out <- rope(rmsnorm(q; qw)) as there; k' = rope(rmsnorm(k; kw)) and v' = rmsnorm(v_src; vw or ones), rounded to bf16 as the bf16 cache would hold them, are
+ *     quantized row by row as kv_write_fp8 quantizes them and stored at row pos % capacity of K8 / V8 / Ks / Vs.  q_out, bytes and scales are bit-identical to
+ *     the bf16 entry into scratch caches followed by kv_write_fp8 on the rows it wrote; no other cache row is written.  One launch instead of the six of the unfused
+ *     chain (Gemma.Block.ixx:315-337: q_norm, k_norm, rope.decode, v_norm, kvcache_write); the prefill form takes T <= capacity rows of the packed qkv_proj output at
+ *     + t * src_row_stride elements (a multiple of 8) for positions pos_offset + t (Gemma.Block.ixx:215-262); the device-position form reads the position from
+ *     *position_dev, for graph replay (the reference passes it from the host at every step, SPEC/Gemma4InferenceReview.md:71-84).  HS in {64, 128, 256, 512}.
  * ------------------------------------------------------------------------------------------- */
 MILA_API int mila_cdna4_kv_write_fp8(uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* k, const uint16_t* v, int B, int chunk, int NKV, int HS,
                                      int start_pos, int capacity, mila_stream_t stream);
@@ -311,6 +318,17 @@ MILA_API size_t mila_cdna4_attn_prefill_kvfp8_scratch_bytes(int B, int NKV, int 
 MILA_API int mila_cdna4_attn_prefill_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch,
                                            size_t scratch_bytes, int B, int chunk, int NH, int NKV, int HS, int capacity, int pos_offset, int window, float scale,
                                            mila_stream_t stream);
+MILA_API int mila_cdna4_fused_qkv_post_kvfp8(uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k, const uint16_t* v_src,
+                                             const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache, int NH, int NKV,
+                                             int HS, int position, int capacity, float eps, mila_stream_t stream);
+MILA_API int mila_cdna4_fused_qkv_post_kvfp8_prefill(uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k,
+                                                     const uint16_t* v_src, int64_t src_row_stride, const uint16_t* qw, const uint16_t* kw, const uint16_t* vw,
+                                                     const float* cos_cache, const float* sin_cache, int T, int NH, int NKV, int HS, int pos_offset, int capacity,
+                                                     float eps, mila_stream_t stream);
+MILA_API int mila_cdna4_fused_qkv_post_kvfp8_devpos(uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k,
+                                                    const uint16_t* v_src, const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache,
+                                                    const float* sin_cache, int NH, int NKV, int HS, const int32_t* position_dev, int capacity, float eps,
+                                                    mila_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Normalisation / activations.

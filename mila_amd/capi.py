@@ -93,6 +93,10 @@ def load():
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.argtypes = [i, i, i, i]                                      # B NKV HS capacity
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.restype = z
     main.mila_cdna4_attn_prefill_kvfp8.argtypes = [p, p, p, p, p, p, p, z, i, i, i, i, i, i, i, i, f, p]          # Y Q K8 V8 Ks Vs scratch bytes | B chunk NH NKV HS capacity pos_offset window | scale
+    i64 = C.c_int64
+    main.mila_cdna4_fused_qkv_post_kvfp8.argtypes = [p] * 13 + [i, i, i, i, i, f, p]                              # q_out K8 V8 Ks Vs q k v_src qw kw vw cos sin | NH NKV HS position capacity | eps
+    main.mila_cdna4_fused_qkv_post_kvfp8_prefill.argtypes = [p] * 8 + [i64] + [p] * 5 + [i, i, i, i, i, i, f, p]  # q_out K8 V8 Ks Vs q k v_src | stride | qw kw vw cos sin | T NH NKV HS pos_offset capacity | eps
+    main.mila_cdna4_fused_qkv_post_kvfp8_devpos.argtypes = [p] * 13 + [i, i, i, p, i, f, p]                       # ... | NH NKV HS | position_dev | capacity | eps
     _lib = _Libs(main)
     return _lib
 
@@ -239,6 +243,7 @@ EXPORTED = [
     "matvec_fp32", "gemm_fp32", "mha_fp32", "mha_kv_write_fp32", "mha_decode_fp32", "lpe_fp32", "rope_forward_fp32",
     "kv_write_fp8", "attn_decode_kvfp8", "kv_dequant_fp8_bf16", "attn_prefill_kvfp8_scratch_bytes", "attn_prefill_kvfp8",
     "kv_write_fp8_devpos", "attn_decode_kvfp8_devpos", "attn_decode_kvfp8_plan_describe",
+    "fused_qkv_post_kvfp8", "fused_qkv_post_kvfp8_prefill", "fused_qkv_post_kvfp8_devpos",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

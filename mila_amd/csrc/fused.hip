@@ -6,6 +6,7 @@
 // with the same lane->element assignment as the standalone kernels, so each intermediate bf16
 // rounding of the unfused chain is reproduced and the results are bit-identical.
 #include "common.h"
+#include "fp8_quant.h"
 #include "rms_common.h"
 #include "rope_common.h"
 
@@ -29,6 +30,15 @@ struct QkvPostParams
     float eps;
     // prefill form: token t = blockIdx.y at position + t reads its q/k/v at + t * src_row_stride and writes q_out at + t * NH * HS
     int64_t src_row_stride;
+};
+
+// the FP8 KV cache (PerChannelKvFp8<>, attention_kvfp8.hip) as the append's destination: K8 / V8 [NKV, capacity, HS] e4m3, Ks / Vs [NKV, capacity] fp32
+struct KvFp8Rows
+{
+    uint8_t* K8;
+    uint8_t* V8;
+    float* Ks;
+    float* Vs;
 };
 
 __global__ void advance_position_kernel(int32_t* pos) { *pos += 1; }
@@ -63,11 +73,30 @@ __device__ __forceinline__ float group_tree_sum(float v, int hv)
     return v;
 }
 
+// max over the hv lanes of a lane group: group_tree_sum's steps with fmaxf (exact in any order)
+__device__ __forceinline__ float group_tree_max(float v, int hv)
+{
+    if (hv >= 2) v = fmaxf(v, dpp_f32<0xB1>(v));
+    if (hv >= 4) v = fmaxf(v, dpp_f32<0x4E>(v));
+    if (hv >= 8) v = fmaxf(v, dpp_f32<0x141>(v));
+    if (hv >= 16) v = fmaxf(v, dpp_f32<0x140>(v));
+    if (hv >= 32)
+    {
+        const uint32_t u = __float_as_uint(v);
+        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+        v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    }
+    return v;
+}
+
 // Head rows [0,NH) = q, [NH,NH+NKV) = k, [NH+NKV, NH+2NKV) = v of token blockIdx.y.  HS <= 512: a row is handled by the hv = HS / 16
 // lanes that also apply the result (lane g holds the rotation pair of chunks g and g + hv), 64 / hv rows per wave, every lane busy.
 // The sum of squares is tree(lo chunks) + tree(hi chunks) over those hv lanes -- exactly what rms_rstd_wave's 64-lane butterfly
 // computes for a row of 2 hv chunks (its remaining steps add zeros), so the bits match the standalone RMSNorm kernel.
-__global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostParams p)
+// kQuant: the K / V rows, rounded to bf16 as the bf16 cache would hold them, are quantized the way kv_write_fp8_kernel quantizes a row (row absmax over the row's hv
+// lanes -> fp8_row_scale -> bf16x4_to_e4m3x4) and go to the FP8 KV cache `d` (HS <= 512): two 8-byte e4m3 groups per lane, the scale from the row's first lane.
+template <bool kQuant>
+__device__ __forceinline__ void qkv_post_body(const QkvPostParams& p, const KvFp8Rows& d)
 {
     const int HS = p.HS, half = HS / 2, hv = half / 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -85,7 +114,9 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostParams p)
     const float* sin_row = p.sin_cache + (size_t)position * half;
     const uint16_t* src;
     const uint16_t* w;
-    uint16_t* dst;
+    uint16_t* dst = nullptr;
+    uint8_t* dst8 = nullptr;      // kQuant: the K / V row's bytes and its scale
+    float* dsts = nullptr;
     bool rotate;
     if (rr < p.NH)
     {
@@ -94,12 +125,18 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostParams p)
     else if (rr < p.NH + p.NKV)
     {
         const int n = rr - p.NH;
-        src = p.k + src_t + (size_t)n * HS; w = p.kw; dst = p.Kc + ((size_t)n * p.capacity + row) * HS; rotate = true;
+        const size_t crow = (size_t)n * p.capacity + row;
+        src = p.k + src_t + (size_t)n * HS; w = p.kw; rotate = true;
+        if constexpr (kQuant) { dst8 = d.K8 + crow * HS; dsts = d.Ks + crow; }
+        else dst = p.Kc + crow * HS;
     }
     else
     {
         const int n = rr - p.NH - p.NKV;
-        src = p.v_src + src_t + (size_t)n * HS; w = p.vw; dst = p.Vc + ((size_t)n * p.capacity + row) * HS; rotate = false;
+        const size_t crow = (size_t)n * p.capacity + row;
+        src = p.v_src + src_t + (size_t)n * HS; w = p.vw; rotate = false;
+        if constexpr (kQuant) { dst8 = d.V8 + crow * HS; dsts = d.Vs + crow; }
+        else dst = p.Vc + crow * HS;
     }
     float rstd;
     u32x4 xlo, xhi;
@@ -127,7 +164,7 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostParams p)
         xhi = ld16(src + (size_t)(gl + hv) * 8);
         rstd = rms_rstd_wave(src, HS, p.eps);
     }
-    if (!valid) return;
+    if constexpr (!kQuant) { if (!valid) return; }
     u32x4 lo, hi;
     if (w)
     {
@@ -140,9 +177,32 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostParams p)
         hi = rms_apply8_now(xhi, rstd);
     }
     if (rotate) rope_rotate8_regs(lo, hi, c0, c1, s0, s1);
+    if constexpr (kQuant)
+    {
+        // every lane of the wave takes part in the group reduction (rows past the last one recompute the last row and return after it)
+        float m = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            m = fmaxf(m, fmaxf(fmaxf(fabsf(bf16_lo(lo[e])), fabsf(bf16_hi(lo[e]))), fmaxf(fabsf(bf16_lo(hi[e])), fabsf(bf16_hi(hi[e])))));
+        m = group_tree_max(m, hv);
+        if (!valid) return;
+        if (dst8)
+        {
+            const float scale = fp8_row_scale(m);
+            const float inv = 1.0f / scale;
+            if (gl == 0) *dsts = scale;
+            *reinterpret_cast<u32x2*>(dst8 + (size_t)gl * 8) = u32x2{bf16x4_to_e4m3x4(lo[0], lo[1], inv), bf16x4_to_e4m3x4(lo[2], lo[3], inv)};
+            *reinterpret_cast<u32x2*>(dst8 + (size_t)(gl + hv) * 8) = u32x2{bf16x4_to_e4m3x4(hi[0], hi[1], inv), bf16x4_to_e4m3x4(hi[2], hi[3], inv)};
+            return;
+        }
+    }
     st16(dst + (size_t)gl * 8, lo);
     st16(dst + (size_t)(gl + hv) * 8, hi);
 }
+
+__global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostParams p) { qkv_post_body<false>(p, KvFp8Rows{}); }
+// the same launch shape; Kc / Vc of `p` are unused
+__global__ __launch_bounds__(256) void qkv_post_kvfp8_kernel(const QkvPostParams p, const KvFp8Rows d) { qkv_post_body<true>(p, d); }
 
 static int qkv_post_rows_per_wave(int HS)
 {
@@ -199,6 +259,47 @@ int mila_cdna4_fused_qkv_post_devpos(uint16_t* q_out, uint16_t* Kc, uint16_t* Vc
     const int rows = NH + 2 * NKV;
     hipLaunchKernelGGL(qkv_post_kernel, dim3(ceil_div(rows, 4 * qkv_post_rows_per_wave(HS))), dim3(256), 0, as_stream(stream), p);
     MILA_LAUNCH_CHECK("fused_qkv_post_devpos");
+}
+
+// ---- the same three entries over the FP8 KV cache (PerChannelKvFp8<>): q_out as above, the K / V rows quantized into K8 / V8 / Ks / Vs --------------------------
+// what the three share: every check (`who` names the entry), then the launch of T tokens from `position` (or one token at *pos_dev)
+static int qkv_post_kvfp8(const char* who, uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k, const uint16_t* v_src,
+                          int64_t src_row_stride, const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache, int T, int NH, int NKV,
+                          int HS, int position, const int32_t* pos_dev, bool devpos, bool strided, int capacity, float eps, mila_stream_t stream)
+{
+    MILA_REQUIRE(q_out && K8 && V8 && Ks && Vs && q && k && v_src && qw && kw && cos_cache && sin_cache && (!devpos || pos_dev), "%s: null pointer", who);
+    MILA_REQUIRE(HS == 64 || HS == 128 || HS == 256 || HS == 512, "%s: HS=%d must be 64, 128, 256 or 512", who, HS);
+    MILA_REQUIRE(T > 0 && T <= 65535 && NH > 0 && NKV > 0 && capacity > 0 && position >= 0, "%s: bad sizes", who);
+    MILA_REQUIRE(T <= capacity, "%s: %d tokens do not fit the cache capacity %d", who, T, capacity);
+    MILA_REQUIRE(!strided || (src_row_stride % 8 == 0 && src_row_stride >= (int64_t)HS), "%s: row stride %lld must be a multiple of 8", who, (long long)src_row_stride);
+    QkvPostParams p{q_out, nullptr, nullptr, q, k, v_src, qw, kw, vw, cos_cache, sin_cache, pos_dev, NH, NKV, HS, position, capacity, eps, src_row_stride};
+    const int rows = NH + 2 * NKV;
+    hipLaunchKernelGGL(qkv_post_kvfp8_kernel, dim3(ceil_div(rows, 4 * qkv_post_rows_per_wave(HS)), T), dim3(256), 0, as_stream(stream), p, KvFp8Rows{K8, V8, Ks, Vs});
+    return check_hip(hipGetLastError(), who);
+}
+
+int mila_cdna4_fused_qkv_post_kvfp8(uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k, const uint16_t* v_src,
+                                    const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache, int NH, int NKV, int HS,
+                                    int position, int capacity, float eps, mila_stream_t stream)
+{
+    return qkv_post_kvfp8("fused_qkv_post_kvfp8", q_out, K8, V8, Ks, Vs, q, k, v_src, 0, qw, kw, vw, cos_cache, sin_cache, 1, NH, NKV, HS, position, nullptr, false, false, capacity, eps,
+                          stream);
+}
+
+int mila_cdna4_fused_qkv_post_kvfp8_prefill(uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k, const uint16_t* v_src,
+                                            int64_t src_row_stride, const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache,
+                                            int T, int NH, int NKV, int HS, int pos_offset, int capacity, float eps, mila_stream_t stream)
+{
+    return qkv_post_kvfp8("fused_qkv_post_kvfp8_prefill", q_out, K8, V8, Ks, Vs, q, k, v_src, src_row_stride, qw, kw, vw, cos_cache, sin_cache, T, NH, NKV, HS, pos_offset, nullptr,
+                          false, true, capacity, eps, stream);
+}
+
+int mila_cdna4_fused_qkv_post_kvfp8_devpos(uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k, const uint16_t* v_src,
+                                           const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache, int NH, int NKV, int HS,
+                                           const int32_t* position_dev, int capacity, float eps, mila_stream_t stream)
+{
+    return qkv_post_kvfp8("fused_qkv_post_kvfp8_devpos", q_out, K8, V8, Ks, Vs, q, k, v_src, 0, qw, kw, vw, cos_cache, sin_cache, 1, NH, NKV, HS, 0, position_dev, true, false, capacity, eps,
+                          stream);
 }
 
 int mila_cdna4_advance_position(int32_t* position_dev, mila_stream_t stream)

@@ -17,7 +17,7 @@ _lib = None
 class GemmaConfigC(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("vocab_size", "embedding_dim", "num_layers", "num_heads", "num_kv_heads",
                                          "head_dim", "hidden_dim", "global_head_dim", "num_global_kv_heads", "window",
-                                         "sliding_window_pattern", "global_rotary_dim", "bounded_local_kv")]
+                                         "sliding_window_pattern", "global_rotary_dim", "bounded_local_kv", "kv_fp8")]
 
 
 GEMMA4_12B = dict(vocab_size=262144, embedding_dim=3840, num_layers=48, num_heads=16, num_kv_heads=8, head_dim=256,
@@ -84,10 +84,11 @@ class Gemma:
 
     MODES = {"reference": 0, "fused": 1, "graph": 2}
 
-    def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None):
+    def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None, kv_fp8=False):
         """device: HIP device ordinal; default = this process's LOCAL_RANK (one replica per GPU under torch.distributed.run).
         profile: synthetic-parameter multipliers {linear_gain, qk_norm_center, post_norm_center, layer_scalar, table_gain}
-        (GemmaTransformer::SyntheticProfile; None = the unit-scale generator of SURVEY.md section 8d)"""
+        (GemmaTransformer::SyntheticProfile; None = the unit-scale generator of SURVEY.md section 8d)
+        kv_fp8: PerChannelKvFp8<> on every layer -- e4m3 K / V + one fp32 scale per KV head per cached token (also: config["kv_fp8"] = 1)"""
         lib = load()
         if device is None:
             from .replicas import local_device
@@ -95,6 +96,9 @@ class Gemma:
         self.device = device
         self.cfg = dict(GEMMA4_12B if config is None else config)
         self.cfg.setdefault("bounded_local_kv", 0)      # 1: SlidingWindowKvCache on the sliding-window layers
+        self.cfg.setdefault("kv_fp8", 0)                # 1: the FP8 KV cache (GemmaConfig::kv_fp8)
+        if kv_fp8:
+            self.cfg["kv_fp8"] = 1
         c = GemmaConfigC(**self.cfg)
         self.vocab = self.cfg["vocab_size"]
         self.h = lib.mila_gemma_create(POLICIES[policy], C.byref(c), max_seq, max_prefill, seed, device)
@@ -177,6 +181,14 @@ class Gemma:
         lib.mila_gemma_graph_node_count.argtypes = [C.c_void_p, C.c_void_p]
         out = C.c_int64()
         _check(lib.mila_gemma_graph_node_count(self.h, C.byref(out)))
+        return out.value
+
+    def graph_capture_count(self):
+        """captures of the decode graph so far: the first graph-mode step, and one for every re-capture (a position in another live-length bucket, another sampler setting)"""
+        lib = load()
+        lib.mila_gemma_graph_capture_count.argtypes = [C.c_void_p, C.c_void_p]
+        out = C.c_int64()
+        _check(lib.mila_gemma_graph_capture_count(self.h, C.byref(out)))
         return out.value
 
     def resident_staging_bytes(self):
@@ -277,6 +289,8 @@ class GemmaModel:
         lib = load()
         lib.mila_gemma_model_from_pretrained.restype = C.c_void_p
         lib.mila_gemma_model_from_pretrained.argtypes = [C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]
+        lib.mila_gemma_model_from_pretrained_kv.restype = C.c_void_p
+        lib.mila_gemma_model_from_pretrained_kv.argtypes = [C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]
         lib.mila_gemma_model_synthetic.restype = C.c_void_p
         lib.mila_gemma_model_synthetic.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_int]
         lib.mila_gemma_model_destroy.argtypes = [C.c_void_p]
@@ -290,19 +304,22 @@ class GemmaModel:
         raise (ValueError if text.startswith("invalid_argument") else RuntimeError)(what + ": " + text)
 
     @classmethod
-    def from_pretrained(cls, path, policy="bf16", context=4096, prefill_chunk=0, bounded_local_kv=False, device=0):
+    def from_pretrained(cls, path, policy="bf16", context=4096, prefill_chunk=0, bounded_local_kv=False, device=0, kv_fp8=False):
         """GemmaModel::fromPretrained(path, GemmaModelConfig(context).withWeightQuantization(policy)): the geometry comes from the artifact"""
         lib = cls._bind()
-        h = lib.mila_gemma_model_from_pretrained(str(path).encode(), POLICIES[policy], context, prefill_chunk, int(bool(bounded_local_kv)), device)
+        h = lib.mila_gemma_model_from_pretrained_kv(str(path).encode(), POLICIES[policy], context, prefill_chunk, int(bool(bounded_local_kv)), int(bool(kv_fp8)), device)
         if not h:
             cls._raise(lib, "GemmaModel.from_pretrained")
         return cls(h, device)
 
     @classmethod
-    def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0):
+    def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0, kv_fp8=False):
         lib = cls._bind()
         cfg = dict(GEMMA4_12B if config is None else config)
         cfg.setdefault("bounded_local_kv", 0)
+        cfg.setdefault("kv_fp8", 0)
+        if kv_fp8:
+            cfg["kv_fp8"] = 1
         c = GemmaConfigC(**cfg)
         p = None
         if profile is not None:

@@ -3,7 +3,7 @@
 //     forward, exactly the sequence of GemmaBlock::decode / ::prefill,
 //     /root/reference/Mila/Src/Dnn/Components/Transformers/Gemma/Gemma.Block.ixx:197-356, and
 //     GemmaTransformer::decode, Gemma.ixx:281-297), and
-//   * decodeFused(): the same arithmetic as 6 launches per layer, and
+//   * decodeFused(): the same arithmetic as 6 launches per layer (7 with GemmaConfig::kv_fp8, the FP8 KV cache), and
 //   * a hipGraph of the fused step with the position in device memory (one replay per token).
 // The three paths produce bit-identical logits (tests/test_gemma_host_gpu.py).
 //
@@ -34,6 +34,7 @@ namespace Mila::Dnn
               global_rotary_dim = 128;
         float rms_norm_eps = 1e-6f, rope_theta_local = 10000.0f, rope_theta_global = 1000000.0f, final_logit_softcapping = 30.0f;
         bool bounded_local_kv = false;   ///< SlidingWindowKvCache on the sliding-window layers (ring of window + chunk - 1 rows)
+        bool kv_fp8 = false;             ///< PerChannelKvFp8<> on every layer: e4m3 K / V + one fp32 scale per KV head per cached token, (HS + 4) / (2 HS) of the bf16 bytes
 
         bool isGlobalLayer( dim_t i ) const { return ( i + 1 ) % sliding_window_pattern == 0; }   // Gemma.Config.ixx:504-507
         dim_t headDim( bool g ) const { return g ? global_head_dim : head_dim; }
@@ -52,6 +53,14 @@ namespace Mila::Dnn
                 throw std::invalid_argument( "GemmaConfig: num_heads must be a multiple of the KV head counts" );
             if ( embedding_dim % 128 != 0 || hidden_dim % 128 != 0 || qWidth( false ) % 128 != 0 || qWidth( true ) % 128 != 0 )
                 throw std::invalid_argument( "GemmaConfig: feature widths must be multiples of 128 (FP4 group size)" );
+            if ( kv_fp8 )
+            {
+                if ( bounded_local_kv ) throw std::invalid_argument( "GemmaConfig: kv_fp8 cannot be combined with bounded_local_kv (the FP8 KV cache is unbounded)" );
+                for ( dim_t hs : { head_dim, global_head_dim } )
+                    if ( hs != 64 && hs != 128 && hs != 256 && hs != 512 )
+                        throw std::invalid_argument( "GemmaConfig: kv_fp8 needs head dimensions of 64, 128, 256 or 512 (head_dim " + std::to_string( head_dim ) + ", global_head_dim " +
+                                                     std::to_string( global_head_dim ) + ")" );
+            }
         }
 
         /// weight parameters streamed per decode token (Linear body, tied table) -- SURVEY.md section 8d
@@ -84,6 +93,9 @@ namespace Mila::Dnn
         using LocalBlockType = GemmaBlock<kDevice, kPrecision, false, TWeightQuant, Quant::KvCache::NoKvCompression>;
         using BoundedLocalBlockType = GemmaBlock<kDevice, kPrecision, false, TWeightQuant, Quant::KvCache::SlidingWindowKvCache>;
         using GlobalBlockType = GemmaBlock<kDevice, kPrecision, true, TWeightQuant, Quant::KvCache::NoKvCompression>;
+        // ... and with GemmaConfig::kv_fp8 every block keeps its K / V in the FP8 KV cache (unbounded on both kinds)
+        using KvFp8LocalBlockType = GemmaBlock<kDevice, kPrecision, false, TWeightQuant, Quant::KvCache::PerChannelKvFp8<>>;
+        using KvFp8GlobalBlockType = GemmaBlock<kDevice, kPrecision, true, TWeightQuant, Quant::KvCache::PerChannelKvFp8<>>;
         static constexpr int kFmt = Quant::Weight::abiWeightFormat<TWeightQuant>();
         static constexpr int kTableFmt = Quant::Weight::abiWeightFormat<TableQuantizationPolicy>();
 
@@ -191,7 +203,7 @@ namespace Mila::Dnn
         }
 
         // ------------------------------------------------------------------------------------
-        // fused decode: embedding + 6 launches per layer + head
+        // fused decode: embedding + 6 launches per layer (7 over the FP8 KV cache) + head
         // ------------------------------------------------------------------------------------
         LogitsTensor& decodeFused( const TokenTensor& token, dim_t position )
         {
@@ -238,6 +250,7 @@ namespace Mila::Dnn
             captured_token_ = token.data();
             captured_sample_in_graph_ = sample_in_graph_;
             captured_ring_ = token_ring_;
+            ++graph_captures_;
         }
         /// capture on first use, and again whenever the captured graph no longer matches what a replay must do: another token
         /// buffer, or a different sampler setting (a graph captured without the sampler node never writes the next token)
@@ -263,6 +276,8 @@ namespace Mila::Dnn
             hipCheck( hipGraphGetNodes( graph_, nullptr, &n ), "hipGraphGetNodes" );
             return n;
         }
+        /// captures so far: the first use, and one more for every change ensureGraph() answered (another token buffer, sampler setting, ring, or band bucket)
+        size_t graphCaptureCount() const noexcept { return graph_captures_; }
         bool graphSamples() const noexcept { return graph_exec_ != nullptr && captured_sample_in_graph_; }
         /// when set, every replay ends with the greedy sampler writing the next token into the token buffer the graph reads from:
         /// a closed autoregressive loop with no host round trip.  Takes effect at the next ensureGraph() / captureGraph().
@@ -351,7 +366,7 @@ namespace Mila::Dnn
             {
                 b += L.qkv_proj->getParameterBytes() + L.o_proj->getParameterBytes() + L.fc_gate_up->getParameterBytes() + L.fc_down->getParameterBytes();
                 const dim_t band = L.global ? context : std::min<dim_t>( context, cfg_.window );
-                b += 2.0 * band * cfg_.kvWidth( L.global ) * 2;
+                b += cfg_.kv_fp8 ? 2.0 * band * cfg_.numKvHeads( L.global ) * ( cfg_.headDim( L.global ) + 4 ) : 2.0 * band * cfg_.kvWidth( L.global ) * 2;
                 b += 2.0 * ( 4 * cfg_.embedding_dim + 2 * cfg_.headDim( L.global ) );
             }
             b += lm_head_->getParameterBytes();
@@ -483,7 +498,9 @@ namespace Mila::Dnn
                     block->build( BuildContext( shape_t{ 1, P, D }, RuntimeMode::Inference ) );
                     layers_.push_back( block );
                 };
-                if ( g ) wire( std::make_shared<GlobalBlockType>( n, bc ) );
+                if ( cfg_.kv_fp8 && g ) wire( std::make_shared<KvFp8GlobalBlockType>( n, bc ) );
+                else if ( cfg_.kv_fp8 ) wire( std::make_shared<KvFp8LocalBlockType>( n, bc ) );
+                else if ( g ) wire( std::make_shared<GlobalBlockType>( n, bc ) );
                 else if ( cfg_.bounded_local_kv ) wire( std::make_shared<BoundedLocalBlockType>( n, bc ) );
                 else wire( std::make_shared<LocalBlockType>( n, bc ) );
             }
@@ -657,10 +674,16 @@ namespace Mila::Dnn
             const uint16_t* qp = static_cast<const uint16_t*>( qkv.rawData() );
             const uint16_t* kp = qp + (size_t)( NH * HD );
             const uint16_t* vp = g ? kp : kp + (size_t)( NKV * HD );
-            Compute::rocmCheck( mila_cdna4_fused_qkv_post_prefill( q.data(), L.keyCache(), L.valueCache(), qp, kp, vp, (int64_t)cfg_.packedQkvWidth( g ),
-                                                                   L.q_norm->getWeight()->data(), L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(),
-                                                                   L.rope->cosCache(), L.rope->sinCache(), T, (int)NH, (int)NKV, (int)HD, position_offset,
-                                                                   (int)L.cacheCapacity(), cfg_.rms_norm_eps, st ) );
+            if ( L.kvFp8() )      // the same launch with the quantizing append; prefillFromCache() is then the policy's attention-only prefill (band dequant + the bf16 flash kernels)
+                Compute::rocmCheck( mila_cdna4_fused_qkv_post_kvfp8_prefill( q.data(), L.keyCacheFp8(), L.valueCacheFp8(), L.keyScales(), L.valueScales(), qp, kp, vp,
+                                                                             (int64_t)cfg_.packedQkvWidth( g ), L.q_norm->getWeight()->data(), L.k_norm->getWeight()->data(),
+                                                                             L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(), T, (int)NH, (int)NKV, (int)HD,
+                                                                             position_offset, (int)L.cacheCapacity(), cfg_.rms_norm_eps, st ) );
+            else
+                Compute::rocmCheck( mila_cdna4_fused_qkv_post_prefill( q.data(), L.keyCache(), L.valueCache(), qp, kp, vp, (int64_t)cfg_.packedQkvWidth( g ),
+                                                                       L.q_norm->getWeight()->data(), L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(),
+                                                                       L.rope->cosCache(), L.rope->sinCache(), T, (int)NH, (int)NKV, (int)HD, position_offset,
+                                                                       (int)L.cacheCapacity(), cfg_.rms_norm_eps, st ) );
             auto attn = attn_out_->view( shape_t{ 1, T, NH * HD } );
             L.prefillFromCache( q, attn, T, position_offset );
             auto& o = L.o_proj->forward( attn );
@@ -802,7 +825,12 @@ namespace Mila::Dnn
 
     public:
         /// two half-chunks on two streams (see halfBlock): off by default until measured per deployment; same bits either way
-        void setPrefillOverlap( bool on ) { prefill_overlap_ = on; }
+        void setPrefillOverlap( bool on )
+        {
+            if ( on && cfg_.kv_fp8 )
+                throw std::invalid_argument( "GemmaTransformer::setPrefillOverlap: not available with kv_fp8 (both halves would dequantize their band into the one context scratch)" );
+            prefill_overlap_ = on;
+        }
         /// the fused prefill glue serves 1024 < D <= 8192 (workgroup-per-row canonical RMS reduction)
         bool fusedPrefillApplicable() const { return cfg_.embedding_dim > 1024 && cfg_.embedding_dim <= 8192 && cfg_.embedding_dim % 8 == 0; }
         /// on (default): prefill runs the fused glue when the configuration fits; off: one launch per reference op.  Same bits.
@@ -883,10 +911,32 @@ namespace Mila::Dnn
                 const uint16_t* vp = g ? kp : kp + (size_t)NKV * HD;
                 const size_t need = attnScratchBytes();
                 void* scratch = attn_partials_->data();
-                Compute::rocmCheck( mila_cdna4_fused_attn_decode_bf16( attn_out_->data(), L.keyCache(), L.valueCache(), qp, kp, vp, L.q_norm->getWeight()->data(),
-                                                                       L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(),
-                                                                       scratch, need, NH, NKV, HD, (int)L.cacheCapacity(), position, pos_dev,
-                                                                       (int)cfg_.windowFor( g ), L.attentionScale(), cfg_.rms_norm_eps, st ) );
+                if ( L.kvFp8() )
+                {
+                    // the FP8 KV cache: two launches (+ combine) -- the quantizing append into a model-owned q buffer, then the policy's decode attention on the
+                    // model-owned partials.  Under pos_dev, `position` is the live-length bound of the captured band bucket (as for the bf16 launch below)
+                    const uint16_t *qw = L.q_norm->getWeight()->data(), *kw = L.k_norm->getWeight()->data(), *vw = L.v_norm->getWeight()->data();
+                    const int cap = (int)L.cacheCapacity(), window = (int)cfg_.windowFor( g );
+                    if ( pos_dev )
+                    {
+                        Compute::rocmCheck( mila_cdna4_fused_qkv_post_kvfp8_devpos( f_q_->data(), L.keyCacheFp8(), L.valueCacheFp8(), L.keyScales(), L.valueScales(), qp, kp, vp, qw, kw, vw,
+                                                                                    L.rope->cosCache(), L.rope->sinCache(), NH, NKV, HD, pos_dev, cap, cfg_.rms_norm_eps, st ) );
+                        Compute::rocmCheck( mila_cdna4_attn_decode_kvfp8_devpos( attn_out_->data(), f_q_->data(), L.keyCacheFp8(), L.valueCacheFp8(), L.keyScales(), L.valueScales(), scratch,
+                                                                                 need, 1, NH, NKV, HD, cap, pos_dev, position, window, L.attentionScale(), st ) );
+                    }
+                    else
+                    {
+                        Compute::rocmCheck( mila_cdna4_fused_qkv_post_kvfp8( f_q_->data(), L.keyCacheFp8(), L.valueCacheFp8(), L.keyScales(), L.valueScales(), qp, kp, vp, qw, kw, vw,
+                                                                             L.rope->cosCache(), L.rope->sinCache(), NH, NKV, HD, position, cap, cfg_.rms_norm_eps, st ) );
+                        Compute::rocmCheck( mila_cdna4_attn_decode_kvfp8( attn_out_->data(), f_q_->data(), L.keyCacheFp8(), L.valueCacheFp8(), L.keyScales(), L.valueScales(), scratch, need,
+                                                                          1, NH, NKV, HD, cap, position + 1, window, L.attentionScale(), st ) );
+                    }
+                }
+                else
+                    Compute::rocmCheck( mila_cdna4_fused_attn_decode_bf16( attn_out_->data(), L.keyCache(), L.valueCache(), qp, kp, vp, L.q_norm->getWeight()->data(),
+                                                                           L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(),
+                                                                           scratch, need, NH, NKV, HD, (int)L.cacheCapacity(), position, pos_dev,
+                                                                           (int)cfg_.windowFor( g ), L.attentionScale(), cfg_.rms_norm_eps, st ) );
                 // 4. o_proj
                 plainMatvec( *L.o_proj, f_o_->data(), attn_out_->data() );
                 // 5. post_attn_norm + residual + pre_ffn_norm + gate_up + GeGLU
@@ -1235,6 +1285,7 @@ namespace Mila::Dnn
         const int32_t* captured_token_{ nullptr };      // what the captured graph was built for: ensureGraph() re-captures on a mismatch
         dim_t captured_band_end_{ 0 };                  // ... and the live-length bucket (exclusive end) its attention launches were shaped for
         bool captured_sample_in_graph_{ false };
+        size_t graph_captures_{ 0 };
         unsigned long long* token_ring_{ nullptr };
         unsigned long long* token_seq_{ nullptr };
         const unsigned long long* captured_ring_{ nullptr };

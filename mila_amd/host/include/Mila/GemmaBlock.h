@@ -607,6 +607,13 @@ namespace Mila::Dnn
         virtual dim_t cacheCapacity() const noexcept = 0;
         virtual float attentionScale() const noexcept = 0;
         virtual void prefillFromCache( const TensorType& q, TensorType& out, int chunk, int position ) = 0;
+        // ... and the FP8 KV policy's (PerChannelKvFp8<>): the four cache arrays the quantizing fused entries append to (null on a bf16-cache block, whose
+        // keyCache() / valueCache() are null on an fp8 one); prefillFromCache() above runs the policy's attention-only prefill on either
+        virtual bool kvFp8() const noexcept = 0;
+        virtual uint8_t* keyCacheFp8() noexcept = 0;
+        virtual uint8_t* valueCacheFp8() noexcept = 0;
+        virtual float* keyScales() noexcept = 0;
+        virtual float* valueScales() noexcept = 0;
         /// drop everything from `position` on, given that `written` positions were appended (the fused schedules append behind the op's back); false = refused
         virtual bool rewindKvCache( dim_t position, dim_t written ) = 0;
 
@@ -737,11 +744,21 @@ namespace Mila::Dnn
         }
         void resetKVCache() override { attn->resetKVCache(); }
 
-        uint16_t* keyCache() noexcept override { return attn->keyCache(); }
-        uint16_t* valueCache() noexcept override { return attn->valueCache(); }
+        static constexpr bool kKvFp8 = Quant::KvCache::QuantKvPolicy<TKvPolicy>;
+        uint16_t* keyCache() noexcept override { if constexpr ( kKvFp8 ) return nullptr; else return attn->keyCache(); }
+        uint16_t* valueCache() noexcept override { if constexpr ( kKvFp8 ) return nullptr; else return attn->valueCache(); }
         dim_t cacheCapacity() const noexcept override { return attn->cacheCapacity(); }
         float attentionScale() const noexcept override { return attn->scale(); }
-        void prefillFromCache( const TensorType& q, TensorType& out, int chunk, int position ) override { attn->prefillFromCache( q, out, chunk, position ); }
+        void prefillFromCache( const TensorType& q, TensorType& out, int chunk, int position ) override
+        {
+            if constexpr ( kKvFp8 ) attn->getOperation().attendPrefill( q, out, chunk, position );
+            else attn->prefillFromCache( q, out, chunk, position );
+        }
+        bool kvFp8() const noexcept override { return kKvFp8; }
+        uint8_t* keyCacheFp8() noexcept override { if constexpr ( kKvFp8 ) return attn->getOperation().keyBytes(); else return nullptr; }
+        uint8_t* valueCacheFp8() noexcept override { if constexpr ( kKvFp8 ) return attn->getOperation().valueBytes(); else return nullptr; }
+        float* keyScales() noexcept override { if constexpr ( kKvFp8 ) return attn->getOperation().keyScaleData(); else return nullptr; }
+        float* valueScales() noexcept override { if constexpr ( kKvFp8 ) return attn->getOperation().valueScaleData(); else return nullptr; }
         bool rewindKvCache( dim_t position, dim_t written ) override { attn->noteCacheLength( written ); return attn->rewindKvCache( position ); }
 
         /// Gemma.Block.ixx:433-440 / :464-490: the children's stats + the block's own workspace (unless the owner of a pooled one installed it)

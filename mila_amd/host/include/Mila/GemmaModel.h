@@ -70,16 +70,18 @@ namespace Mila::Dnn
         /// MI355X deployment knobs (no reference counterpart: a 12 GB card always chunks and always bounds the ring)
         GemmaModelConfig& withPrefillChunk( dim_t chunk ) { prefill_chunk_ = chunk; return *this; }          ///< 0 = min(context, 2048)
         GemmaModelConfig& withBoundedLocalKv( bool on ) { bounded_local_kv_ = on; return *this; }            ///< SlidingWindowKvCache on the sliding-window layers
+        GemmaModelConfig& withKvFp8( bool on ) { kv_fp8_ = on; return *this; }                               ///< PerChannelKvFp8<> on every layer (GemmaConfig::kv_fp8), under any weight policy
         dim_t getContextLength() const noexcept { return context_length_; }
         WeightQuantization getWeightQuantization() const noexcept { return weight_quantization_; }
         KvCacheCompression getKvCacheCompression() const noexcept { return kv_cache_compression_; }
         dim_t getPrefillChunk() const noexcept { return prefill_chunk_ > 0 ? std::min( prefill_chunk_, context_length_ ) : std::min<dim_t>( context_length_, 2048 ); }
         bool boundedLocalKv() const noexcept { return bounded_local_kv_; }
+        bool kvFp8() const noexcept { return kv_fp8_; }
     private:
         dim_t context_length_{ 0 }, prefill_chunk_{ 0 };
         WeightQuantization weight_quantization_{ WeightQuantization::None };
         KvCacheCompression kv_cache_compression_{ KvCacheCompression::None };
-        bool bounded_local_kv_{ false };
+        bool bounded_local_kv_{ false }, kv_fp8_{ false };
     };
 
     /// Models/QuantizationDispatch.ixx: the runtime deployment choice picks the compile-time policy
@@ -135,6 +137,7 @@ namespace Mila::Dnn
                     if ( md.max_seq_length != 0 && model_config.getContextLength() > static_cast<dim_t>( md.max_seq_length ) )
                         throw std::invalid_argument( "GemmaModel::fromPretrained: context_length " + std::to_string( model_config.getContextLength() ) + " exceeds trained max_seq_len " + std::to_string( md.max_seq_length ) );
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
+                    cfg.kv_fp8 = model_config.kvFp8();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
                     net->loadPretrained( path );
                     return std::unique_ptr<GemmaModel>( new GemmaModel( Network( std::move( net ) ), cfg, model_config, md ) );
@@ -149,6 +152,7 @@ namespace Mila::Dnn
                 {
                     GemmaConfig cfg = network_config;
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
+                    cfg.kv_fp8 = model_config.kvFp8();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
                     typename Net<TWeightQuantization>::SyntheticProfile p;
                     p.linear_gain = profile.linear_gain; p.qk_norm_center = profile.qk_norm_center; p.post_norm_center = profile.post_norm_center; p.layer_scalar = profile.layer_scalar; p.table_gain = profile.table_gain;

@@ -925,6 +925,31 @@ namespace Mila::Dnn::Compute
                                                             position_dev, max_len, (int)cfg_.window, scale(), st ) );
         }
 
+        /// attention only, over rows the quantizing fused append (fused_qkv_post_kvfp8_prefill) has already written: q [B,chunk,NH*HS] at absolute positions
+        /// [position, position+chunk); the band is dequantized into the context's scratch, then the bf16 flash prefill runs on it
+        void attendPrefill( const TensorType& q, TensorType& out, int chunk, int position )
+        {
+            requireCache();
+            const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
+            const size_t need = mila_cdna4_attn_prefill_kvfp8_scratch_bytes( batch_, NKV, HS, cap );
+            void* scratch = context_->getScratch( need );   // fetched per call, never cached
+            rocmCheck( mila_cdna4_attn_prefill_kvfp8( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, chunk, NH, NKV, HS,
+                                                      cap, position, (int)cfg_.window, scale(), context_->getStream() ) );
+            length_ = position + chunk;
+        }
+        /// attendDecode() at the position held in device memory: attention over *position_dev + 1 keys, rows already appended (fused_qkv_post_kvfp8_devpos); max_len as
+        /// in decodeAt().  cacheLength() is unchanged: noteCacheLength( position + 1 ) once the host knows the position
+        void attendDecodeAt( const TensorType& q, TensorType& out, const int32_t* position_dev, int max_len )
+        {
+            requireCache();
+            if ( !position_dev ) throw std::invalid_argument( "RocmGqaKvFp8Op::attendDecodeAt: null device position" );
+            const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
+            const size_t need = mila_cdna4_attn_decode_scratch_bytes( batch_, NH, HS );
+            void* scratch = context_->getScratch( need );   // fetched per call, never cached
+            rocmCheck( mila_cdna4_attn_decode_kvfp8_devpos( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, NH, NKV, HS, cap,
+                                                            position_dev, max_len, (int)cfg_.window, scale(), context_->getStream() ) );
+        }
+
         /// these three exist for the fused q/k/v post-processing entries (fused_qkv_post, fused_attn_decode), which write a bf16 cache through raw pointers
         void prefillFromCache( const TensorType&, TensorType&, int, int ) { throw std::logic_error( "RocmGqaKvFp8Op::prefillFromCache: " + std::string( kFusedOnly ) ); }
         uint16_t* keyCache() { throw std::logic_error( "RocmGqaKvFp8Op::keyCache: " + std::string( kFusedOnly ) ); }
@@ -941,6 +966,11 @@ namespace Mila::Dnn::Compute
         const StorageTensor* valueStorage() const noexcept { return v8_.get(); }
         const ScaleTensor* keyScales() const noexcept { return ks_.get(); }
         const ScaleTensor* valueScales() const noexcept { return vs_.get(); }
+        /// ... and their device arrays, for the quantizing fused entries (fused_qkv_post_kvfp8*), which append through raw pointers; null before initializeKvCache()
+        uint8_t* keyBytes() noexcept { return k8_ ? static_cast<uint8_t*>( k8_->rawData() ) : nullptr; }
+        uint8_t* valueBytes() noexcept { return v8_ ? static_cast<uint8_t*>( v8_->rawData() ) : nullptr; }
+        float* keyScaleData() noexcept { return ks_ ? ks_->data() : nullptr; }
+        float* valueScaleData() noexcept { return vs_ ? vs_->data() : nullptr; }
         const GqaOpConfig& config() const noexcept { return cfg_; }
 
     private:

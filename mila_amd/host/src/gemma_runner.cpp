@@ -45,6 +45,8 @@ namespace
     static_assert( std::is_same_v<ProbeNet::BoundedLocalBlockType::AttentionType::OpType, Mila::Dnn::Compute::RocmGqaOp<true>>, "SlidingWindowKvCache must reach the local (sliding) layers" );
     static_assert( std::is_same_v<ProbeNet::LocalBlockType::AttentionType::OpType, Mila::Dnn::Compute::RocmGqaOp<false>>, "the default policy keeps local layers unbounded" );
     static_assert( std::is_same_v<ProbeNet::GlobalBlockType::AttentionType::OpType, Mila::Dnn::Compute::RocmGqaOp<false>>, "global (full-attention) layers must never be bounded" );
+    static_assert( std::is_same_v<ProbeNet::KvFp8LocalBlockType::AttentionType::OpType, Mila::Dnn::Compute::RocmGqaKvFp8Op> &&
+                   std::is_same_v<ProbeNet::KvFp8GlobalBlockType::AttentionType::OpType, Mila::Dnn::Compute::RocmGqaKvFp8Op>, "kv_fp8 puts the FP8 KV cache op on both kinds of layer" );
 }
 
 /// the other runners of this library (gqa_runner.cpp) report through the message mila_host_last_error() returns
@@ -59,6 +61,7 @@ struct mila_gemma_config
     int64_t vocab_size, embedding_dim, num_layers, num_heads, num_kv_heads, head_dim, hidden_dim, global_head_dim,
             num_global_kv_heads, window, sliding_window_pattern, global_rotary_dim;
     int64_t bounded_local_kv;   ///< != 0: SlidingWindowKvCache (ring of window + chunk - 1 rows) on the sliding-window layers
+    int64_t kv_fp8;             ///< != 0: PerChannelKvFp8<> (e4m3 K / V + one fp32 scale per KV head per cached token) on every layer
 };
 
 HOST_API const char* mila_host_last_error( void ) { return g_err.c_str(); }
@@ -78,6 +81,7 @@ HOST_API void* mila_gemma_create( int policy, const mila_gemma_config* c, int64_
             cfg.num_global_kv_heads = c->num_global_kv_heads; cfg.window = c->window; cfg.sliding_window_pattern = c->sliding_window_pattern;
             cfg.global_rotary_dim = c->global_rotary_dim;
             cfg.bounded_local_kv = c->bounded_local_kv != 0;
+            cfg.kv_fp8 = c->kv_fp8 != 0;
         }
         auto rr = std::make_unique<Runner>();
         rr->max_prefill = max_prefill;
@@ -567,6 +571,13 @@ HOST_API int mila_gemma_graph_node_count( void* h, int64_t* out )
     return guarded( [&] { std::visit( [&]( auto& m ) { *out = static_cast<int64_t>( m->graphNodeCount() ); }, r->model ); } );
 }
 
+/// how often the decode graph has been captured (first use + every re-capture ensureGraph() decided on, e.g. a position in another band bucket)
+HOST_API int mila_gemma_graph_capture_count( void* h, int64_t* out )
+{
+    auto* r = static_cast<Runner*>( h );
+    return guarded( [&] { std::visit( [&]( auto& m ) { *out = static_cast<int64_t>( m->graphCaptureCount() ); }, r->model ); } );
+}
+
 /// bytes of op-owned resident prefill staging held by the layer Linears at this moment
 HOST_API int mila_gemma_resident_staging_bytes( void* h, double* out )
 {
@@ -838,12 +849,12 @@ HOST_API int mila_component_scenarios( int device )
 // ---- L6: GemmaModel (Models/GemmaModel.ixx): fromPretrained / generate -------------------------------------------------------------
 using RocmGemmaModel = GemmaModel<DeviceType::Rocm, TensorDataType::BF16>;
 
-static GemmaModelConfig model_config_of( int policy, int64_t context, int64_t chunk, int bounded )
+static GemmaModelConfig model_config_of( int policy, int64_t context, int64_t chunk, int bounded, int kv_fp8 )
 {
     if ( policy < 0 || policy > 2 ) throw std::invalid_argument( "unknown weight policy" );
     GemmaModelConfig mc;
     mc.withContextLength( context ).withWeightQuantization( policy == 0 ? WeightQuantization::None : ( policy == 1 ? WeightQuantization::FP8 : WeightQuantization::FP4 ) );
-    mc.withPrefillChunk( chunk ).withBoundedLocalKv( bounded != 0 );
+    mc.withPrefillChunk( chunk ).withBoundedLocalKv( bounded != 0 ).withKvFp8( kv_fp8 != 0 );
     return mc;
 }
 
@@ -851,7 +862,14 @@ static GemmaModelConfig model_config_of( int policy, int64_t context, int64_t ch
 HOST_API void* mila_gemma_model_from_pretrained( const char* path, int policy, int64_t context, int64_t prefill_chunk, int bounded_local_kv, int device )
 {
     RocmGemmaModel* m = nullptr;
-    int rc = guarded( [&] { m = RocmGemmaModel::fromPretrained( path, model_config_of( policy, context, prefill_chunk, bounded_local_kv ), Compute::Device::Rocm( device ) ).release(); } );
+    int rc = guarded( [&] { m = RocmGemmaModel::fromPretrained( path, model_config_of( policy, context, prefill_chunk, bounded_local_kv, 0 ), Compute::Device::Rocm( device ) ).release(); } );
+    return rc == 0 ? m : nullptr;
+}
+/// ... with the KV policy switch: kv_fp8 != 0 = GemmaModelConfig::withKvFp8( true )
+HOST_API void* mila_gemma_model_from_pretrained_kv( const char* path, int policy, int64_t context, int64_t prefill_chunk, int bounded_local_kv, int kv_fp8, int device )
+{
+    RocmGemmaModel* m = nullptr;
+    int rc = guarded( [&] { m = RocmGemmaModel::fromPretrained( path, model_config_of( policy, context, prefill_chunk, bounded_local_kv, kv_fp8 ), Compute::Device::Rocm( device ) ).release(); } );
     return rc == 0 ? m : nullptr;
 }
 
@@ -862,7 +880,7 @@ HOST_API void* mila_gemma_model_synthetic( int policy, const mila_gemma_config* 
     int rc = guarded( [&]
     {
         GemmaConfig cfg;
-        int bounded = 0;
+        int bounded = 0, kv_fp8 = 0;
         if ( c )
         {
             cfg.vocab_size = c->vocab_size; cfg.embedding_dim = c->embedding_dim; cfg.num_layers = c->num_layers; cfg.num_heads = c->num_heads;
@@ -870,10 +888,11 @@ HOST_API void* mila_gemma_model_synthetic( int policy, const mila_gemma_config* 
             cfg.num_global_kv_heads = c->num_global_kv_heads; cfg.window = c->window; cfg.sliding_window_pattern = c->sliding_window_pattern;
             cfg.global_rotary_dim = c->global_rotary_dim;
             bounded = c->bounded_local_kv != 0;
+            kv_fp8 = c->kv_fp8 != 0;
         }
         GemmaTransformer<NoWeightQuant>::SyntheticProfile pr;
         if ( p ) { pr.linear_gain = p[ 0 ]; pr.qk_norm_center = p[ 1 ]; pr.post_norm_center = p[ 2 ]; pr.layer_scalar = p[ 3 ]; pr.table_gain = p[ 4 ]; }
-        m = RocmGemmaModel::fromSynthetic( cfg, model_config_of( policy, context, prefill_chunk, bounded ), seed, pr, Compute::Device::Rocm( device ) ).release();
+        m = RocmGemmaModel::fromSynthetic( cfg, model_config_of( policy, context, prefill_chunk, bounded, kv_fp8 ), seed, pr, Compute::Device::Rocm( device ) ).release();
     } );
     return rc == 0 ? m : nullptr;
 }
