@@ -9,15 +9,15 @@
 //   * score = dot(q,k) * scale BEFORE max/exp                        (Gqa.Decode.Bf16.cu:212)
 //   * fp32 scores / probabilities / accumulators, bf16 only at the final store.
 //
-// CDNA4 design of the decode kernel (HBM/latency bound: 4-8 MB of K/V per layer):
-//   grid (splits, NKV, B*Tq), 256 threads = 4 waves.  A wave owns every 4th position of its
-//   split; a lane owns HS/64 contiguous elements of every row (16-byte loads at HS = 512), so one
-//   wave-instruction fetches one whole K (or V) row; q is kept packed (bf16 pairs) in registers
-//   and multiplied with v_dot2_f32_bf16; the 64-lane score reduction is a xor butterfly; online
-//   softmax state (m, l, O) lives in registers per wave and is merged across the 4 waves through
-//   LDS four heads at a time; split partials (m, l, O) go to caller-provided scratch and are
-//   merged by a second tiny kernel (a kernel boundary is cheaper than an in-kernel agent-scope
-//   acquire on this chip, MI355X_MICROARCH "boundary" vs "barrier-xcd").
+// CDNA4 design of the decode (HBM/latency bound: 4-8 MB of K/V per layer): grid (splits, NKV * head groups, B), 512 threads = 8 waves.  A wave owns every 8th
+// position of its split and one wave-instruction fetches one whole K (or V) row; online-softmax state (m, l, O) lives in registers per wave and is merged across the
+// waves through LDS; split partials (m, l, O) go to caller-provided scratch and are merged by a second tiny kernel (a kernel boundary is cheaper than an in-kernel
+// agent-scope acquire on this chip, MI355X_MICROARCH "boundary" vs "barrier-xcd").  From the scores on -- softmax step, both merges, finaliser, the two stores --
+// the kernel is attention_decode_scalar.h, shared with the fp8 cache's kernel (attention_kvfp8.hip).
+//
+// What this file owns: the bf16 append; attn_decode_kernel = its own row loop (bf16 rows used as loaded) around those shared phases, plus the parts only this cache
+// has (fused norm + RoPE + append prologue, warm blocks, one-pass ticket tail, XCD-local grid); the combine kernels; the matrix-core decode's bf16 kernel; plan_decode -- the one place that
+// chooses form, heads per workgroup and split count for BOTH caches -- and the bf16 entry points that launch from it.
 #include "common.h"
 #include "rms_common.h"
 #include "rope_common.h"
@@ -26,6 +26,7 @@
 #include "attention_tiles.h"
 #include "attention_decode_mfma.h"
 #include "attention_decode_plan.h"
+#include "attention_decode_scalar.h"
 
 namespace mila {
 
@@ -86,27 +87,6 @@ struct AttnParams
     const float* sin_cache;
     float eps;
 };
-
-template <int EPL>
-__device__ __forceinline__ void load_row(uint32_t (&dst)[EPL / 2], const uint16_t* p)
-{
-    if constexpr (EPL == 8)
-    {
-        const u32x4 v = ld16(p);
-        dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
-    }
-    else if constexpr (EPL == 4)
-    {
-        const u32x2 v = *reinterpret_cast<const u32x2*>(p);
-        dst[0] = v[0]; dst[1] = v[1];
-    }
-    else
-    {
-        dst[0] = *reinterpret_cast<const uint32_t*>(p);
-    }
-}
-
-constexpr int kDecodeWaves = 8;     // 512 threads per workgroup
 
 // norm (+ RoPE) of one head row by one wave, canonical helpers => bit-identical to the standalone
 // rmsnorm / rope kernels and to qkv_post_kernel.  dst_lds / dst_glb may be NULL.
@@ -177,10 +157,6 @@ __device__ __forceinline__ uint16_t combine_dim(const float* __restrict__ base, 
     }
     return f32_to_bf16_bits(L > 0.0f ? acc / L : 0.0f);
 }
-__device__ __forceinline__ void partial_st_sc1(float* p, float v)
-{
-    __hip_atomic_store((__attribute__((address_space(1))) float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // one dword per 128-byte line of [base, base + 128 nlines), lines strided over `nthreads` threads; nothing is written
 // pair != 0: the range is the head of TWO streams `pair` bytes apart (the gate and up halves the fused gate_up kernel reads in
@@ -210,11 +186,8 @@ __device__ __forceinline__ void warm_lines(const uint8_t* __restrict__ base, int
 template <int HS, int GH, bool FUSED>
 __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(const AttnParams p)
 {
-    constexpr int NW = kDecodeWaves;
-    constexpr int EPL = (HS >= 128) ? HS / 64 : 2;
-    constexpr int NPAIR = EPL / 2;
-    constexpr int ACTIVE = HS / EPL;                       // lanes that own data (64, or 32 for HS = 64)
-    constexpr int STR = HS + 2;
+    using Row = DecodeGeomBf16<HS>;
+    constexpr int NW = kDecodeWaves, EPL = Row::EPL, NPAIR = Row::NPAIR, ACTIVE = Row::ACTIVE, PG = Row::PG, STR = HS + 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float* sm = reinterpret_cast<float*>(smem_raw);        // [NW][GH][HS + 2]
     uint16_t* qs = reinterpret_cast<uint16_t*>(smem_raw + (size_t)NW * GH * STR * sizeof(float));   // [GH][HS], then k_new, v_new
@@ -246,7 +219,6 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(const At
     uint16_t* kbase = p.K + ((size_t)b * p.NKV + kvh) * p.capacity * HS;
     uint16_t* vbase = p.V + ((size_t)b * p.NKV + kvh) * p.capacity * HS;
 
-    constexpr int PG = (HS >= 512) ? 4 : 8;
     struct KVG { uint32_t k[PG][NPAIR], v[PG][NPAIR]; };
     auto load_group = [&](KVG& gbuf, int base) {
 #pragma unroll
@@ -355,42 +327,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(const At
                 for (int e = 0; e < NPAIR; ++e) a = dot2_bf16(as_bf16x2(q[g][e]), as_bf16x2(gbuf.k[j][e]), a);
                 sc[j][g] = a;
             }
-#pragma unroll
-        for (int j = 0; j < PG; ++j)
-#pragma unroll
-            for (int g = 0; g < GH; ++g) sc[j][g] = wave_sum(sc[j][g]);
-#pragma unroll
-        for (int g = 0; g < GH; ++g)
-        {
-            float a[PG], mt = -INFINITY;
-#pragma unroll
-            for (int j = 0; j < PG; ++j)
-            {
-                a[j] = (base_ + NW * j < end) ? sc[j][g] * p.scale : -INFINITY;
-                mt = fmaxf(mt, a[j]);
-            }
-            const float mn = fmaxf(m[g], mt);
-            const float msafe = (mn == -INFINITY) ? 0.0f : mn;
-            const float alpha = __expf(m[g] - msafe);        // m = -inf first time: exp(-inf) = 0
-            float ex[PG], rs = 0.0f;
-#pragma unroll
-            for (int j = 0; j < PG; ++j) { ex[j] = __expf(a[j] - msafe); rs += ex[j]; }
-            l[g] = l[g] * alpha + rs;
-            m[g] = mn;
-#pragma unroll
-            for (int e = 0; e < NPAIR; ++e)
-            {
-                float lo = o[g][2 * e] * alpha, hi = o[g][2 * e + 1] * alpha;
-#pragma unroll
-                for (int j = 0; j < PG; ++j)
-                {
-                    lo = fmaf(ex[j], bf16_lo(gbuf.v[j][e]), lo);
-                    hi = fmaf(ex[j], bf16_hi(gbuf.v[j][e]), hi);
-                }
-                o[g][2 * e] = lo;
-                o[g][2 * e + 1] = hi;
-            }
-        }
+        decode_softmax_step<GH, Row>(sc, gbuf.v, m, l, o, base_, end, p.scale);
     };
     for (;;)
     {
@@ -408,76 +345,8 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(const At
         base = nb;
     }
 
-    // ---- merge the NW waves through LDS; wave w < GH finalises head w ----
-#pragma unroll
-    for (int g = 0; g < GH; ++g)
-    {
-        float* dst = sm + ((size_t)wave * GH + g) * STR;
-        if (owner)
-        {
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) dst[lane * EPL + e] = o[g][e];
-        }
-        if (lane == 0) { dst[HS] = m[g]; dst[HS + 1] = l[g]; }
-    }
-    __syncthreads();
-    if (wave < GH)
-    {
-        const int g = wave;
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[((size_t)w * GH + g) * STR + HS]);
-        float L = 0.0f, acc[EPL];
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] = 0.0f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-        {
-            const float* src = sm + ((size_t)w * GH + g) * STR;
-            const float mw = src[HS];
-            const float f = (mw == -INFINITY) ? 0.0f : __expf(mw - M);
-            L += src[HS + 1] * f;
-            if (owner)
-            {
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) acc[e] += src[lane * EPL + e] * f;
-            }
-        }
-        const int h = h0 + g;
-        if (p.splits == 1)
-        {
-            const float inv = (L > 0.0f) ? 1.0f / L : 0.0f;
-            uint16_t* y = p.Y + ((size_t)b * p.NH + h) * HS + lane * EPL;
-            if (owner)
-            {
-#pragma unroll
-                for (int e = 0; e < EPL; e += 2)
-                    *reinterpret_cast<uint32_t*>(y + e) = pack_bf16x2(acc[e] * inv, acc[e + 1] * inv);
-            }
-        }
-        else if (p.tickets == nullptr)
-        {
-            float* dst = p.scratch + (((size_t)b * p.NH + h) * p.splits + split) * (HS + 4);
-            if (owner)
-            {
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) dst[lane * EPL + e] = acc[e];
-            }
-            if (lane == 0) { dst[HS] = M; dst[HS + 1] = L; }
-        }
-        else
-        {
-            // one-pass form: write-through (sc1) stores, drained by this wave before the workgroup's arrival is counted
-            float* dst = p.scratch + (((size_t)b * p.NH + h) * p.splits + split) * (HS + 4);
-            if (owner)
-            {
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) partial_st_sc1(dst + lane * EPL + e, acc[e]);
-            }
-            if (lane == 0) { partial_st_sc1(dst + HS, M); partial_st_sc1(dst + HS + 1, L); }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
+    const DecodeFinishArgs a{p.Y, p.scratch, p.NH, p.splits, split, b, h0, p.tickets != nullptr};
+    decode_finish<HS, GH, Row>(a, m, l, o, sm);
     if (p.splits > 1 && p.tickets != nullptr)
     {
         // Arrival ticket per (batch row, head-group): MI355X_MICROARCH.md hand-off table, row 1 (sc1 payload stores drained by
@@ -691,7 +560,7 @@ static DecodePlan plan_decode(int B, int NH, int NKV, int HS, int capacity, int 
     const bool scalar_only = kvfp8 && !g_tune_kvfp8_mfma;
     DecodePlan d{};
     const int GS = NH / NKV;
-    const bool split_kernel = HS == 64 || HS == 128 || HS == 256 || HS == 512;
+    const bool split_kernel = decode_scalar_head_size(HS);
     d.band_max = (window > 0 && window < capacity) ? window : (len_hint > 0 ? band_bucket(len_hint, capacity) : capacity);
     d.gh = heads_per_group(GS, HS);
     d.hgroups = GS / d.gh;
@@ -767,42 +636,29 @@ static int launch_decode(const AttnParams& p, int B, hipStream_t s)
     return rc;
 }
 
-template <int HS, bool FUSED>
-static int dispatch_gs(const AttnParams& p, int B, hipStream_t s)
-{
-    const int GS = p.NH / p.NKV;
-    if (GS != 1 && GS != 2 && GS != 4 && GS != 8 && GS != 16 && GS != 32)
-        return set_error(MILA_E_UNSUPPORTED, "attention: group size %d (NH/NKV) must be 1,2,4,8,16 or 32", GS);
-    switch (heads_per_group(GS, HS))
-    {
-        case 1: return launch_decode<HS, 1, FUSED>(p, B, s);
-        case 2: return launch_decode<HS, 2, FUSED>(p, B, s);
-        default: return launch_decode<HS, 4, FUSED>(p, B, s);
-    }
-}
-
+// the scalar form of a plan: the plan's heads per workgroup at one of the four head sizes (attention_decode_plan.h), the generic kernel at any other
 template <bool FUSED>
-static int dispatch_hs(int HS, const AttnParams& p, int B, hipStream_t s)
+static int dispatch_hs(int HS, int gh, const AttnParams& p, int B, hipStream_t s)
 {
-    switch (HS)
+    if (decode_scalar_head_size(HS))
     {
-        case 64: return dispatch_gs<64, FUSED>(p, B, s);
-        case 128: return dispatch_gs<128, FUSED>(p, B, s);
-        case 256: return dispatch_gs<256, FUSED>(p, B, s);
-        case 512: return dispatch_gs<512, FUSED>(p, B, s);
-        default:
-            if constexpr (!FUSED)
-            {
-                // any other head size: one wave per (batch, head) row on the generic kernel (attention_generic.hip); the position may live on the device only in the
-                // captured forms, which the benchmarked head sizes alone use
-                if (p.pos_dev) return set_error(MILA_E_UNSUPPORTED, "attention: the device-position form needs a head size of 64, 128, 256 or 512 (got %d)", HS);
-                const int64_t qbs = p.q_b_stride ? p.q_b_stride : (int64_t)p.NH * HS;
-                GenericAttnParams g{p.Y, p.Q, p.K, p.V, qbs, qbs, (int64_t)p.NKV * p.capacity * HS, (int64_t)p.capacity * HS, HS,
-                                    B, 1, p.NH, p.NKV, HS, p.capacity, p.position, p.window, p.scale};
-                return launch_attn_generic(g, s);
-            }
-            return set_error(MILA_E_UNSUPPORTED, "attention: head size %d must be 64, 128, 256 or 512", HS);
+        const int GS = p.NH / p.NKV;
+        if (!decode_group_size_ok(GS)) return set_error(MILA_E_UNSUPPORTED, "attention: group size %d (NH/NKV) must be 1,2,4,8,16 or 32", GS);
+        const int rc = dispatch_decode_scalar<true>(HS, gh, [&](auto hs, auto g) { return launch_decode<decltype(hs)::value, decltype(g)::value, FUSED>(p, B, s); });
+        if (rc == kNoDecodeKernel) return set_error(MILA_E_UNSUPPORTED, "attention: no kernel for %d heads per workgroup at HS=%d", gh, HS);
+        return rc;
     }
+    if constexpr (!FUSED)
+    {
+        // any other head size: one wave per (batch, head) row on the generic kernel (attention_generic.hip); the position may live on the device only in the
+        // captured forms, which the benchmarked head sizes alone use
+        if (p.pos_dev) return set_error(MILA_E_UNSUPPORTED, "attention: the device-position form needs a head size of 64, 128, 256 or 512 (got %d)", HS);
+        const int64_t qbs = p.q_b_stride ? p.q_b_stride : (int64_t)p.NH * HS;
+        GenericAttnParams g{p.Y, p.Q, p.K, p.V, qbs, qbs, (int64_t)p.NKV * p.capacity * HS, (int64_t)p.capacity * HS, HS,
+                            B, 1, p.NH, p.NKV, HS, p.capacity, p.position, p.window, p.scale};
+        return launch_attn_generic(g, s);
+    }
+    return set_error(MILA_E_UNSUPPORTED, "attention: head size %d must be 64, 128, 256 or 512", HS);
 }
 
 // The one executor: scratch check against the plan, the prologue launch where the plan has one, the leaf launcher of the plan's form.  A fused call has p.q_raw set.
@@ -813,7 +669,7 @@ static int run_decode(const DecodePlan& d, AttnParams p, int B, int HS, size_t s
     p.flat = d.flat;
     if (d.scratch_need && (!p.scratch || scratch_bytes < d.scratch_need))
         return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, d.scratch_need);
-    if (d.form != DF_MFMA) return fused ? dispatch_hs<true>(HS, p, B, stream) : dispatch_hs<false>(HS, p, B, stream);
+    if (d.form != DF_MFMA) return fused ? dispatch_hs<true>(HS, d.gh, p, B, stream) : dispatch_hs<false>(HS, d.gh, p, B, stream);
     if (d.prologue)
     {
         uint16_t* q_tmp = reinterpret_cast<uint16_t*>(p.scratch + d.partial_floats);
@@ -879,7 +735,7 @@ static int fused_decode(const char* who, const mila_fused_attn_args& a, int B, i
     if (flags & FD_PARTIALS) MILA_REQUIRE(d.splits > 1, "%s: this (window, capacity) runs unsplit; use fused_attn_decode_bf16", who);
     if (!a.position_dev)
     {
-        const int len = a.position + 1, band = (a.window > 0 && a.window < len) ? a.window : len;
+        const int band = live_band(a.position + 1, a.window);
         MILA_REQUIRE(band <= a.capacity, "%s: live band %d exceeds the cache capacity %d", who, band, a.capacity);
     }
     return run_decode(d, p, B, a.HS, a.scratch_bytes, who, stream);
@@ -982,7 +838,7 @@ int mila_cdna4_attn_decode_bf16(uint16_t* Y, const uint16_t* Q, const uint16_t* 
     MILA_REQUIRE(B > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "attn_decode_bf16: bad head counts (NH=%d NKV=%d)", NH, NKV);
     MILA_REQUIRE(len > 0 && capacity > 0, "attn_decode_bf16: len and capacity must be positive (len=%d capacity=%d)", len, capacity);
     MILA_REQUIRE(window >= 0, "attn_decode_bf16: negative window");
-    const int band = (window > 0 && window < len) ? window : len;
+    const int band = live_band(len, window);
     MILA_REQUIRE(band <= capacity, "attn_decode_bf16: live band %d exceeds the cache capacity %d", band, capacity);
     return unfused_decode("attn_decode_bf16", Y, Q, 0, Kc, Vc, scratch, scratch_bytes, B, NH, NKV, HS, capacity, len - 1, nullptr, len, window, scale, as_stream(stream));
 }
@@ -995,7 +851,7 @@ int mila_cdna4_attn_decode_bf16_devpos(uint16_t* Y, const uint16_t* Q, const uin
     MILA_REQUIRE(Y && Q && Kc && Vc && position_dev, "attn_decode_bf16_devpos: null pointer");
     MILA_REQUIRE(B > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "attn_decode_bf16_devpos: bad head counts (NH=%d NKV=%d)", NH, NKV);
     MILA_REQUIRE(max_len > 0 && capacity > 0 && window >= 0, "attn_decode_bf16_devpos: bad sizes");
-    const int band = (window > 0 && window < max_len) ? window : max_len;
+    const int band = live_band(max_len, window);
     MILA_REQUIRE(band <= capacity, "attn_decode_bf16_devpos: live band %d exceeds the cache capacity %d", band, capacity);
     return unfused_decode("attn_decode_bf16_devpos", Y, Q, 0, Kc, Vc, scratch, scratch_bytes, B, NH, NKV, HS, capacity, 0, position_dev, max_len, window, scale, as_stream(stream));
 }

@@ -8,16 +8,21 @@
 //            cache for the prefill, which then runs the bf16 flash kernels: both see the same K / V values, the attention arithmetic is the bf16 cache's.
 //
 // Decode (the hot path), two kernels chosen by attention.hip's plan_decode exactly as it chooses between the bf16 cache's two:
-//   attn_decode_kvfp8_kernel       the split-K flash decode of attention.hip (Gqa.Decode.Bf16.cu:93-105, :212, :297-351) with the row loads at one byte per element.  A
-//     lane loads 4 bytes of a row (8 at HS 512), so a row is HS / 4 lanes wide: one row per wave-instruction at HS 256 / 512, two at HS 128 (half-waves), four at
-//     HS 64 (16-lane rows).  Each lane segment keeps its own online-softmax state over its own positions; the segments of a wave are merged in registers, the eight
-//     waves through LDS, the splits by attention.hip's combine kernel from partials in its layout.
+//   attn_decode_kvfp8_kernel       the split-K wave-per-position decode (Gqa.Decode.Bf16.cu:93-105, :212, :297-351): its own row loop (one byte per element + the row's
+//     scale, dequantized in registers; a row is HS / 4 lanes wide, so a wave-instruction fetches 1, 2 or 4 rows: DecodeGeomKvFp8) around the phases of
+//     attention_decode_scalar.h that attention.hip's attn_decode_kernel runs too: softmax step, both merges, finaliser, stores.  The splits are merged by attention.hip's combine kernel from partials in its layout.
 //   attn_decode_kvfp8_mfma_kernel  16 query heads on one KV head at HS 512 over a long band (from the 8192-key bucket): the matrix-core decode -- the tile body of
 //     attention_decode_mfma.h under the e4m3 staging policy (16-byte e4m3 chunks + row scales -> registers -> bf16 values in the bf16 kernel's LDS images), up to 256
 //     splits merged by attn_combine_many_kernel.  From LDS on it IS attn_decode_mfma_kernel: the same bits as attn_decode_bf16 on the dequantized cache.
 // Both take the live length either as a launch argument or (the device-position entries, for graph replay) from device memory.
+//
+// What this file owns: the quantizing append, the band dequant and the prefill over a transient bf16 cache; the two kernels above (the scalar one's row loop, the matrix-core one's wrapper)
+// with their parameter block and launches; the fp8 entry points and their checks.  The arithmetic from the scores on (attention_decode_scalar.h), the matrix-core tile
+// body (attention_decode_mfma.h), the plan and the
+// (HS, heads per workgroup) dispatch (attention_decode_plan.h) are shared with the bf16 cache.
 #include "attention_decode_mfma.h"
 #include "attention_decode_plan.h"
+#include "attention_decode_scalar.h"
 #include "attention_tiles.h"      // kKeysPerTile: the flash prefill streams whole key tiles
 #include "fp8_quant.h"
 
@@ -118,38 +123,12 @@ struct KvFp8DecodeParams
     const int32_t* pos_dev;   // when set: len = *pos_dev + 1, read by the kernels (graph replay); null in the eager form
 };
 
-constexpr int kKvFp8Waves = 8;     // 512 threads per workgroup, as attn_decode_kernel
-
-// sum over the LPR-lane segment a lane belongs to (segments are aligned): the leading steps of wave_sum
-template <int LPR>
-__device__ __forceinline__ float segment_sum(float v)
-{
-    if constexpr (LPR == 64) return wave_sum(v);
-    v += dpp_f32<0xB1>(v);
-    v += dpp_f32<0x4E>(v);
-    v += dpp_f32<0x141>(v);
-    v += dpp_f32<0x140>(v);
-    if constexpr (LPR == 32)
-    {
-        const uint32_t u = __float_as_uint(v);
-        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-        v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-    return v;
-}
-
 // GH = query heads per workgroup; grid = (splits, NKV * GS/GH, B).  Wave w, lane segment s own positions begin + (w * RPW + s) + 8 * RPW * j of the split.
 template <int HS, int GH>
-__global__ __launch_bounds__(kKvFp8Waves * 64) void attn_decode_kvfp8_kernel(const KvFp8DecodeParams p)
+__global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kvfp8_kernel(const KvFp8DecodeParams p)
 {
-    constexpr int NW = kKvFp8Waves;
-    constexpr int EPL = HS >= 512 ? 8 : 4;                 // elements (= cache bytes) of a row per lane
-    constexpr int ND = EPL / 4, NPAIR = EPL / 2;
-    constexpr int LPR = HS / EPL;                          // lanes per row: 64, 64, 32, 16
-    constexpr int RPW = 64 / LPR;                          // rows per wave-instruction: 1, 1, 2, 4
-    constexpr int PG = 8 / RPW;                            // row slots a lane keeps in flight: a workgroup's group is 64 positions at every head size
-    constexpr int FE = HS / 64;                            // output elements per lane in the merge
-    constexpr int STR = HS + 2;
+    using Row = DecodeGeomKvFp8<HS>;
+    constexpr int NW = kDecodeWaves, EPL = Row::EPL, ND = Row::ND, NPAIR = Row::NPAIR, LPR = Row::LPR, RPW = Row::RPW, PG = Row::PG;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_kvfp8[];
     float* sm = reinterpret_cast<float*>(smem_kvfp8);      // [NW][GH][HS + 2]
 
@@ -260,42 +239,7 @@ __global__ __launch_bounds__(kKvFp8Waves * 64) void attn_decode_kvfp8_kernel(con
                 sc[j][g] = a;
             }
         }
-#pragma unroll
-        for (int j = 0; j < PG; ++j)
-#pragma unroll
-            for (int g = 0; g < GH; ++g) sc[j][g] = segment_sum<LPR>(sc[j][g]);
-#pragma unroll
-        for (int g = 0; g < GH; ++g)
-        {
-            float a[PG], mt = -INFINITY;
-#pragma unroll
-            for (int j = 0; j < PG; ++j)
-            {
-                a[j] = (wbase + sub + NW * RPW * j < end) ? sc[j][g] * p.scale : -INFINITY;
-                mt = fmaxf(mt, a[j]);
-            }
-            const float mn = fmaxf(m[g], mt);
-            const float msafe = (mn == -INFINITY) ? 0.0f : mn;
-            const float alpha = __expf(m[g] - msafe);        // m = -inf first time: exp(-inf) = 0
-            float ex[PG], rs = 0.0f;
-#pragma unroll
-            for (int j = 0; j < PG; ++j) { ex[j] = __expf(a[j] - msafe); rs += ex[j]; }
-            l[g] = l[g] * alpha + rs;
-            m[g] = mn;
-#pragma unroll
-            for (int e = 0; e < NPAIR; ++e)
-            {
-                float lo = o[g][2 * e] * alpha, hi = o[g][2 * e + 1] * alpha;
-#pragma unroll
-                for (int j = 0; j < PG; ++j)
-                {
-                    lo = fmaf(ex[j], bf16_lo(vp[j][e]), lo);
-                    hi = fmaf(ex[j], bf16_hi(vp[j][e]), hi);
-                }
-                o[g][2 * e] = lo;
-                o[g][2 * e + 1] = hi;
-            }
-        }
+        decode_softmax_step<GH, Row>(sc, vp, m, l, o, wbase + sub, end, p.scale);
     };
     for (;;)                                               // (wave-uniform control: `base` is the wave's, not the lane segment's)
     {
@@ -311,99 +255,19 @@ __global__ __launch_bounds__(kKvFp8Waves * 64) void attn_decode_kvfp8_kernel(con
         base = nb;
     }
 
-    // ---- merge the RPW lane segments of the wave in registers: afterwards every segment holds the wave's state ----
-    if constexpr (RPW > 1)
-    {
-#pragma unroll
-        for (int off = LPR; off < 64; off <<= 1)
-        {
-#pragma unroll
-            for (int g = 0; g < GH; ++g)
-            {
-                const float mo = __shfl_xor(m[g], off, 64), lo_ = __shfl_xor(l[g], off, 64);
-                const float M = fmaxf(m[g], mo);
-                const float fa = (m[g] == -INFINITY) ? 0.0f : __expf(m[g] - M), fb = (mo == -INFINITY) ? 0.0f : __expf(mo - M);
-                l[g] = l[g] * fa + lo_ * fb;
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) o[g][e] = o[g][e] * fa + __shfl_xor(o[g][e], off, 64) * fb;
-                m[g] = M;
-            }
-        }
-    }
-
-    // ---- merge the NW waves through LDS; wave w < GH finalises head w ----
-#pragma unroll
-    for (int g = 0; g < GH; ++g)
-    {
-        float* dst = sm + ((size_t)wave * GH + g) * STR;
-        if (sub == 0)
-        {
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) dst[ll * EPL + e] = o[g][e];
-        }
-        if (lane == 0) { dst[HS] = m[g]; dst[HS + 1] = l[g]; }
-    }
-    __syncthreads();
-    if (wave < GH)
-    {
-        const int g = wave;
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[((size_t)w * GH + g) * STR + HS]);
-        float L = 0.0f, acc[FE];
-#pragma unroll
-        for (int e = 0; e < FE; ++e) acc[e] = 0.0f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-        {
-            const float* src = sm + ((size_t)w * GH + g) * STR;
-            const float mw = src[HS];
-            const float f = (mw == -INFINITY) ? 0.0f : __expf(mw - M);
-            L += src[HS + 1] * f;
-#pragma unroll
-            for (int e = 0; e < FE; ++e) acc[e] += src[lane * FE + e] * f;
-        }
-        const int h = h0 + g;
-        if (p.splits == 1)
-        {
-            const float inv = (L > 0.0f) ? 1.0f / L : 0.0f;
-            uint16_t* y = p.Y + ((size_t)b * p.NH + h) * HS + lane * FE;
-            if constexpr (FE == 1)
-                y[0] = f32_to_bf16_bits(acc[0] * inv);
-            else
-            {
-#pragma unroll
-                for (int e = 0; e < FE; e += 2) *reinterpret_cast<uint32_t*>(y + e) = pack_bf16x2(acc[e] * inv, acc[e + 1] * inv);
-            }
-        }
-        else
-        {
-            float* dst = p.scratch + (((size_t)b * p.NH + h) * p.splits + split) * (HS + 4);
-#pragma unroll
-            for (int e = 0; e < FE; ++e) dst[lane * FE + e] = acc[e];
-            if (lane == 0) { dst[HS] = M; dst[HS + 1] = L; }
-        }
-    }
+    const DecodeFinishArgs a{p.Y, p.scratch, p.NH, p.splits, split, b, h0, false};
+    decode_finish<HS, GH, Row>(a, m, l, o, sm);
 }
 
 template <int HS, int GH>
 static int launch_decode_kvfp8(const KvFp8DecodeParams& p, int B, int hgroups, hipStream_t s)
 {
     note_form("attn_decode_kvfp8");
-    const size_t lds = (size_t)kKvFp8Waves * GH * (HS + 2) * sizeof(float);      // <= 33 KB (HS 256 x 4 heads, HS 512 x 2)
-    hipLaunchKernelGGL((attn_decode_kvfp8_kernel<HS, GH>), dim3(p.splits, p.NKV * hgroups, B), dim3(kKvFp8Waves * 64), lds, s, p);
+    const size_t lds = (size_t)kDecodeWaves * GH * (HS + 2) * sizeof(float);      // <= 33 KB (HS 256 x 4 heads, HS 512 x 2)
+    hipLaunchKernelGGL((attn_decode_kvfp8_kernel<HS, GH>), dim3(p.splits, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, p);
     int rc = check_hip(hipGetLastError(), "attn_decode_kvfp8");
     if (rc || p.splits <= 1) return rc;
     return launch_attn_combine(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
-}
-template <int HS>
-static int dispatch_kvfp8_gh(const KvFp8DecodeParams& p, int B, int gh, int hgroups, hipStream_t s)
-{
-    if (gh == 1) return launch_decode_kvfp8<HS, 1>(p, B, hgroups, s);
-    if (gh == 2) return launch_decode_kvfp8<HS, 2>(p, B, hgroups, s);
-    if constexpr (HS < 512)      // (HS 512 takes 4 heads only under the attn.heads_per_group_512 experiment)
-        if (gh == 4) return launch_decode_kvfp8<HS, 4>(p, B, hgroups, s);
-    return set_error(MILA_E_UNSUPPORTED, "attn_decode_kvfp8: no kernel for %d heads per workgroup at HS=%d", gh, HS);
 }
 
 // ---- the matrix-core decode (attention_decode_mfma.h): grid (splits, NKV * GS / 16, B), 256 threads ----
@@ -435,7 +299,6 @@ static int launch_decode_kvfp8_mfma(const KvFp8DecodeParams& p, int B, hipStream
     return launch_attn_combine_many(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
 }
 
-static bool kvfp8_head_size(int HS) { return HS == 64 || HS == 128 || HS == 256 || HS == 512; }
 static size_t kvfp8_transient_bytes(int B, int NKV, int HS, int capacity) { return 2 * (size_t)B * NKV * capacity * HS * sizeof(uint16_t); }
 
 }  // namespace mila
@@ -467,7 +330,7 @@ int mila_cdna4_kv_write_fp8(uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, cons
 {
     MILA_REQUIRE(K8 && V8 && Ks && Vs && k && v, "kv_write_fp8: null pointer");
     MILA_REQUIRE(B > 0 && chunk > 0 && NKV > 0 && capacity > 0, "kv_write_fp8: bad sizes");
-    MILA_REQUIRE(kvfp8_head_size(HS), "kv_write_fp8: HS=%d must be 64, 128, 256 or 512", HS);
+    MILA_REQUIRE(decode_scalar_head_size(HS), "kv_write_fp8: HS=%d must be 64, 128, 256 or 512", HS);
     MILA_REQUIRE(start_pos >= 0, "kv_write_fp8: negative start position");
     MILA_REQUIRE(chunk <= capacity, "kv_write_fp8: chunk %d exceeds the cache capacity %d", chunk, capacity);
     return launch_kv_write_fp8("kv_write_fp8", K8, V8, Ks, Vs, k, v, B, chunk, NKV, HS, start_pos, nullptr, capacity, stream);
@@ -478,7 +341,7 @@ int mila_cdna4_kv_write_fp8_devpos(uint8_t* K8, uint8_t* V8, float* Ks, float* V
 {
     MILA_REQUIRE(K8 && V8 && Ks && Vs && k && v && position_dev, "kv_write_fp8_devpos: null pointer");
     MILA_REQUIRE(B > 0 && NKV > 0 && capacity > 0, "kv_write_fp8_devpos: bad sizes");
-    MILA_REQUIRE(kvfp8_head_size(HS), "kv_write_fp8_devpos: HS=%d must be 64, 128, 256 or 512", HS);
+    MILA_REQUIRE(decode_scalar_head_size(HS), "kv_write_fp8_devpos: HS=%d must be 64, 128, 256 or 512", HS);
     return launch_kv_write_fp8("kv_write_fp8_devpos", K8, V8, Ks, Vs, k, v, B, 1, NKV, HS, 0, position_dev, capacity, stream);
 }
 
@@ -487,7 +350,7 @@ int mila_cdna4_kv_dequant_fp8_bf16(uint16_t* Kc_bf16, uint16_t* Vc_bf16, const u
 {
     MILA_REQUIRE(Kc_bf16 && Vc_bf16 && K8 && V8 && Ks && Vs, "kv_dequant_fp8_bf16: null pointer");
     MILA_REQUIRE(B > 0 && NKV > 0 && capacity > 0, "kv_dequant_fp8_bf16: bad sizes");
-    MILA_REQUIRE(kvfp8_head_size(HS), "kv_dequant_fp8_bf16: HS=%d must be 64, 128, 256 or 512", HS);
+    MILA_REQUIRE(decode_scalar_head_size(HS), "kv_dequant_fp8_bf16: HS=%d must be 64, 128, 256 or 512", HS);
     MILA_REQUIRE(first_pos >= 0 && count > 0 && count <= capacity, "kv_dequant_fp8_bf16: positions [%d, %d + %d) do not fit the cache capacity %d", first_pos, first_pos,
                  count, capacity);
     const int64_t total_vec = 2 * (int64_t)B * NKV * count * (HS / 16);
@@ -503,12 +366,12 @@ static int kvfp8_decode(const char* who, uint16_t* Y, const uint16_t* Q, const u
                         int B, int NH, int NKV, int HS, int capacity, int len, const int32_t* pos_dev, int window, float scale, mila_stream_t stream)
 {
     MILA_REQUIRE(B > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "%s: bad head counts (NH=%d NKV=%d)", who, NH, NKV);
-    MILA_REQUIRE(kvfp8_head_size(HS), "%s: HS=%d must be 64, 128, 256 or 512", who, HS);
+    MILA_REQUIRE(decode_scalar_head_size(HS), "%s: HS=%d must be 64, 128, 256 or 512", who, HS);
     const int GS = NH / NKV;
-    MILA_REQUIRE(GS == 1 || GS == 2 || GS == 4 || GS == 8 || GS == 16 || GS == 32, "%s: group size %d (NH/NKV) must be 1,2,4,8,16 or 32", who, GS);
+    MILA_REQUIRE(decode_group_size_ok(GS), "%s: group size %d (NH/NKV) must be 1,2,4,8,16 or 32", who, GS);
     MILA_REQUIRE(len > 0 && capacity > 0, "%s: %s and capacity must be positive (%s=%d capacity=%d)", who, pos_dev ? "max_len" : "len", pos_dev ? "max_len" : "len", len, capacity);
     MILA_REQUIRE(window >= 0, "%s: negative window", who);
-    const int band = (window > 0 && window < len) ? window : len;
+    const int band = live_band(len, window);
     MILA_REQUIRE(band <= capacity, "%s: live band %d exceeds the cache capacity %d", who, band, capacity);
     const KvFp8DecodeShape d = plan_decode_kvfp8(B, NH, NKV, HS, capacity, window, len);
     MILA_REQUIRE(!d.scratch_need || (scratch && scratch_bytes >= d.scratch_need), "%s: scratch %zu bytes < required %zu (ask attn_decode_scratch_bytes)", who, scratch_bytes,
@@ -516,13 +379,10 @@ static int kvfp8_decode(const char* who, uint16_t* Y, const uint16_t* Q, const u
     KvFp8DecodeParams p{Y, Q, K8, V8, Ks, Vs, reinterpret_cast<float*>(scratch), NH, NKV, capacity, len, window, d.splits, scale, pos_dev};
     hipStream_t s = as_stream(stream);
     if (d.mfma) return launch_decode_kvfp8_mfma(p, B, s);      // (HS 512 by the plan's rule)
-    switch (HS)
-    {
-        case 64: return dispatch_kvfp8_gh<64>(p, B, d.gh, d.hgroups, s);
-        case 128: return dispatch_kvfp8_gh<128>(p, B, d.gh, d.hgroups, s);
-        case 256: return dispatch_kvfp8_gh<256>(p, B, d.gh, d.hgroups, s);
-        default: return dispatch_kvfp8_gh<512>(p, B, d.gh, d.hgroups, s);
-    }
+    // (<512, 4> runs only under the attn.heads_per_group_512 experiment, on the bf16 cache)
+    const int rc = dispatch_decode_scalar<false>(HS, d.gh, [&](auto hs, auto g) { return launch_decode_kvfp8<decltype(hs)::value, decltype(g)::value>(p, B, d.hgroups, s); });
+    if (rc == kNoDecodeKernel) return set_error(MILA_E_UNSUPPORTED, "attn_decode_kvfp8: no kernel for %d heads per workgroup at HS=%d", d.gh, HS);
+    return rc;
 }
 
 int mila_cdna4_attn_decode_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
@@ -550,7 +410,7 @@ int mila_cdna4_attn_prefill_kvfp8(uint16_t* Y, const uint16_t* Q, const uint8_t*
 {
     MILA_REQUIRE(Y && Q && K8 && V8 && Ks && Vs && scratch, "attn_prefill_kvfp8: null pointer");
     MILA_REQUIRE(B > 0 && chunk > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "attn_prefill_kvfp8: bad sizes");
-    MILA_REQUIRE(kvfp8_head_size(HS), "attn_prefill_kvfp8: HS=%d must be 64, 128, 256 or 512", HS);
+    MILA_REQUIRE(decode_scalar_head_size(HS), "attn_prefill_kvfp8: HS=%d must be 64, 128, 256 or 512", HS);
     MILA_REQUIRE(pos_offset >= 0 && capacity > 0 && window >= 0, "attn_prefill_kvfp8: bad positions");
     // every key a query of this chunk may see must still be resident in the ring: the band [first, pos_offset + chunk)
     const int first = (window > 0) ? max(0, pos_offset - window + 1) : 0, count = pos_offset + chunk - first;
