@@ -253,6 +253,10 @@ MILA_API int mila_cdna4_attn_prefill_bf16(uint16_t* Y, const uint16_t* Q, const 
                                           const uint16_t* Vc, int B, int chunk, int NH, int NKV, int HS,
                                           int capacity, int pos_offset, int window, float scale,
                                           mila_stream_t stream);
+/* the plan attn_prefill_bf16 launches a chunk from (mha_bf16: NKV = NH, pos_offset 0, window 0), as text, without running device code: "form:HB:DS:NW:QROWS:n_qtiles:
+ * n_hblk:n_items" -- form flash | flash_dma | flash_dma_pipe | flash_pp | attn_generic; HB heads x DS d-shares on NW waves per workgroup, which holds QROWS query rows;
+ * n_items = n_qtiles * n_hblk workgroups per batch row.  Returns the text's size, 0 for a bad shape. */
+MILA_API size_t mila_cdna4_attn_prefill_plan_describe(int HS, int NH, int NKV, int chunk, int pos_offset, int window, char* buf, size_t cap);
 /* GPT-2 multi-head attention on packed QKV [B,T,3C] -> [B,T,C], causal, scale 1/sqrt(HS).
  * replaces Attention/MHA/CudaMhaOp.ixx:456-553 (permute + 2 batched GEMMs + softmax + unpermute). */
 MILA_API int mila_cdna4_mha_bf16(uint16_t* Y, const uint16_t* QKV, int B, int T, int C, int NH,

@@ -89,6 +89,8 @@ def load():
     main.mila_cdna4_attn_decode_kvfp8_devpos.argtypes = [p, p, p, p, p, p, p, z, i, i, i, i, i, p, i, i, f, p]    # Y Q K8 V8 Ks Vs scratch bytes | B NH NKV HS capacity | position_dev | max_len window | scale
     main.mila_cdna4_attn_decode_kvfp8_plan_describe.argtypes = [i, i, i, i, i, i, i, p, z]                        # B NH NKV HS capacity window len_hint | buf cap
     main.mila_cdna4_attn_decode_kvfp8_plan_describe.restype = z
+    main.mila_cdna4_attn_prefill_plan_describe.argtypes = [i, i, i, i, i, i, p, z]                                # HS NH NKV chunk pos_offset window | buf cap
+    main.mila_cdna4_attn_prefill_plan_describe.restype = z
     main.mila_cdna4_kv_dequant_fp8_bf16.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                        # Kc Vc K8 V8 Ks Vs | B NKV HS capacity first_pos count
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.argtypes = [i, i, i, i]                                      # B NKV HS capacity
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.restype = z
@@ -191,6 +193,24 @@ def attn_decode_kvfp8_plan(B, NH, NKV, HS, capacity, window, len_hint=0):
     return dict(zip(PLAN_FIELDS, [f[0]] + [int(v) for v in f[1:]]))
 
 
+PREFILL_PLAN_FIELDS = ("form", "HB", "DS", "NW", "QROWS", "n_qtiles", "n_hblk", "n_items")
+
+
+def attn_prefill_plan(HS, NH, NKV, chunk, pos_offset=0, window=0):
+    """the plan attn_prefill_bf16 launches a chunk from (csrc/attention_prefill.hip: plan_prefill, under the current flash.form) as a dict of PREFILL_PLAN_FIELDS: HB heads x
+    DS d-shares on NW waves per workgroup of QROWS query rows, n_items = n_qtiles * n_hblk workgroups per batch row.  Needs no GPU."""
+    buf = C.create_string_buffer(256)
+    need = load().mila_cdna4_attn_prefill_plan_describe(int(HS), int(NH), int(NKV), int(chunk), int(pos_offset), int(window), buf, C.c_size_t(len(buf)))
+    assert 0 < need <= len(buf), "no plan for this shape" if not need else "plan text of %d bytes" % need
+    f = buf.value.decode().split(":")
+    return dict(zip(PREFILL_PLAN_FIELDS, [f[0]] + [int(v) for v in f[1:]]))
+
+
+def prefill_form_name(plan, HS):
+    """what last_form() reports for a launch from this plan: the form and its instantiation"""
+    return plan["form"] if plan["form"] == "attn_generic" else "%s_hs%d_hb%d_ds%d_nw%d" % (plan["form"], HS, plan["HB"], plan["DS"], plan["NW"])
+
+
 def check(rc):
     if rc == MILA_OK:
         return
@@ -228,7 +248,7 @@ EXPORTED = [
     "gemm_w4a8_scratch_bytes", "gemm_bf16_w4a8", "gemm_geglu_w4a8_applicable", "gemm_geglu_bf16_w4a8",
     "gemm_geglu_applicable", "gemm_geglu_preferred", "gemm_geglu_bf16", "gemm_geglu_bf16_w8a16_staged", "gemm_geglu_bf16_w4a16_staged",
     "quantize_fp8_per_channel", "quantize_fp4_per_group",
-    "kv_write_bf16", "attn_decode_scratch_bytes", "attn_decode_bf16", "attn_prefill_bf16", "mha_bf16", "mha_kv_write_bf16", "mha_decode_scratch_bytes", "mha_decode_bf16",
+    "kv_write_bf16", "attn_decode_scratch_bytes", "attn_decode_bf16", "attn_prefill_bf16", "attn_prefill_plan_describe", "mha_bf16", "mha_kv_write_bf16", "mha_decode_scratch_bytes", "mha_decode_bf16",
     "rmsnorm_bf16", "rmsnorm_fp32", "layernorm_bf16", "layernorm_fp32", "softmax_fp32", "softmax_bf16",
     "gelu_bf16", "gelu_fp32", "geglu_bf16", "residual_bf16", "residual_fp32",
     "rope_build_cache", "rope_forward_bf16",

@@ -21,6 +21,7 @@
 //   * a workgroup = 4 waves = (query heads sharing one KV head) x (16-row query sub-tiles): all four
 //     waves consume the same K/V tiles (GQA/MQA reuse in LDS); the heaviest (latest) query tiles are
 //     dispatched first.
+#include <cstdio>
 #include <cstdlib>
 
 #include "common.h"
@@ -28,6 +29,7 @@
 #include <utility>
 #include "internal.h"
 #include "attention_generic.h"
+#include "attention_prefill_plan.h"
 #include "attention_tiles.h"
 
 namespace mila {
@@ -1236,16 +1238,78 @@ static int g_tune_flash_form = 8;      // tuning "flash.form": 8 (default) = the
                                        // d-split workgroups; 1 = the register-staged kernels.  All give the same bits.
 MILA_TUNE("flash.form", g_tune_flash_form);
 
+// ---- the prefill plan --------------------------------------------------------------------------------------------------------------------------------------
+// Which kernel, which workgroup shape and which grid serve a shape is decided HERE, once, from the shape and flash.form; flash_dispatch launches from the plan and
+// mila_cdna4_attn_prefill_plan_describe prints it.  Heads per workgroup follow the group size GS = NH / NKV (all heads of a workgroup share one KV head: HB | GS).
+PrefillPlan plan_prefill(int HS, int NH, int NKV, int chunk, int pos_offset, int window)
+{
+    const int GS = NH / NKV, form = g_tune_flash_form;
+    PrefillPlan pl{};
+    pl.HS = HS;
+    auto shaped = [&](PrefillForm f, int HB, int DS, int NW) {
+        pl.form = f; pl.HB = HB; pl.DS = DS; pl.NW = NW;
+        pl.QROWS = 16 * (NW / (HB * DS));
+        pl.n_qtiles = (chunk + pl.QROWS - 1) / pl.QROWS;
+        pl.n_hblk = NH / HB;
+        pl.n_items = pl.n_qtiles * pl.n_hblk;
+        return pl;
+    };
+    if (HS != 64 && HS != 128 && HS != 256 && HS != 512)
+    {
+        // any other head size (the reference tests' own HS = 4 / 8 geometries): the one-wave-per-row kernel of attention_generic.hip, four (head, row) pairs per workgroup
+        pl.form = PF_GENERIC; pl.HB = 1; pl.DS = 1; pl.NW = 4; pl.QROWS = 4;
+        pl.n_qtiles = (chunk + 3) / 4; pl.n_hblk = NH; pl.n_items = pl.n_qtiles * pl.n_hblk;
+        return pl;
+    }
+    if (HS == 512)
+    {
+        if (form == 10 && GS % 4 == 0) return shaped(PF_FLASH_PP, 4, 2, 8);
+        if (form == 11 && GS % 4 == 0) return shaped(PF_FLASH_DMA_PIPE, 4, 2, 8);
+        if (form >= 8 && GS % 4 == 0) return shaped(PF_FLASH_DMA, 4, 2, 8);      // four heads x two d-halves, double-buffered tiles
+        if (form >= 2) return shaped(PF_FLASH_DMA, GS % 2 == 0 ? 2 : 1, 2, 4);
+    }
+    if (HS == 256)
+    {
+        if (form == 10 && GS % 2 == 0) return shaped(PF_FLASH_PP, 2, 1, 8);
+        if (form == 11 && GS % 2 == 0) return shaped(PF_FLASH_DMA_PIPE, 2, 1, 4);
+        // Double-buffered 4-wave workgroups, two per CU (their phases drift apart, so one's softmax runs under the other's products): 58 us on Gemma's
+        // sliding-window shape at T = 2048.  The 8-wave form (2 heads x 4 row blocks on one tile stream, one workgroup per CU: 1.4x the work per tile load, but
+        // its eight waves move in lockstep) was the faster one -- 76 vs 82 us -- while the tile body was bound by its vector ALU work; with the lean body it
+        // is the slower one (62 us) and stays behind tuning form 9 where at least half the chunk's rows see a full window.  (A d-split does not pay at this
+        // head size: 92.7 us.)
+        if (form == 9 && GS % 2 == 0 && window > 0 && pos_offset + chunk / 2 >= window) return shaped(PF_FLASH_DMA, 2, 1, 8);
+        if (form >= 8) return shaped(PF_FLASH_DMA, GS % 4 == 0 ? 4 : GS % 2 == 0 ? 2 : 1, 1, 4);
+    }
+    // the register-staged kernels (HS <= 256; every head size under form 1)
+    return shaped(PF_FLASH, GS % 4 == 0 ? 4 : GS % 2 == 0 ? 2 : 1, 1, 4);
+}
+
+// the name mila_cdna4_last_form reports for a planned launch: the form and its instantiation, "flash_dma_hs256_hb4_ds1_nw4"
+static void note_prefill_form(const PrefillPlan& pl)
+{
+    char name[64];
+    if (pl.form == PF_GENERIC) snprintf(name, sizeof(name), "%s", kPrefillFormNames[pl.form]);
+    else snprintf(name, sizeof(name), "%s_hs%d_hb%d_ds%d_nw%d", kPrefillFormNames[pl.form], pl.HS, pl.HB, pl.DS, pl.NW);
+    note_form(name);
+}
+
+// the launch parameters of a plan: the caller's, with the plan's grid
+static FlashParams planned_params(const FlashParams& p, const PrefillPlan& pl)
+{
+    FlashParams q = p;
+    q.n_qtiles = pl.n_qtiles;
+    q.n_hblk = pl.n_hblk;
+    return q;
+}
+
 // the register-staged kernels (HS <= 256; every head size under form 1)
 template <int HS, int HB>
-static int launch_flash(const FlashParams& p, int B, hipStream_t s)
+static int launch_flash(const FlashParams& p, const PrefillPlan& pl, int B, hipStream_t s)
 {
-    constexpr int QROWS = 16 * (4 / HB);
     const size_t lds = (size_t)(HS >= 512 ? 2 : 4) * kKeysPerTile * HS * 2;      // HS <= 256: two [K | V] buffers (HS = 512 here: one wave per head, no exchange area)
-    FlashParams q = p;
-    q.n_qtiles = (p.Tq + QROWS - 1) / QROWS;
-    q.n_hblk = p.NH / HB;
-    const dim3 grid(q.n_qtiles * q.n_hblk, 1, B);
+    const FlashParams q = planned_params(p, pl);
+    const dim3 grid(pl.n_items, 1, B);
+    note_prefill_form(pl);
     if constexpr (HS >= 512) hipLaunchKernelGGL((flash_prefill_kernel_s1<HS, HB, 1, 4>), grid, dim3(256), lds, s, q);
     else hipLaunchKernelGGL((flash_prefill_kernel<HS, HB>), grid, dim3(256), lds, s, q);
     MILA_LAUNCH_CHECK("flash_prefill");
@@ -1253,89 +1317,90 @@ static int launch_flash(const FlashParams& p, int B, hipStream_t s)
 
 // the LDS-DMA kernel (HS = 256 or 512): HB heads x DS d-shares x (NW / (HB DS)) row blocks per workgroup of NW waves
 template <int HS, int HB, int DS, int NW, bool PIPE = false>
-static int launch_flash_dma(const FlashParams& p, int B, hipStream_t s)
+static int launch_flash_dma(const FlashParams& p, const PrefillPlan& pl, int B, hipStream_t s)
 {
-    constexpr int QROWS = 16 * (NW / (HB * DS));
     constexpr bool DB = (NW == 8) || (HS <= 256);
     const size_t lds = (size_t)(DB ? 4 : 2) * kKeysPerTile * HS * 2 + ((HS >= 512 && DS == 2) ? (size_t)NW * 2048 * (PIPE ? 2 : 1) : 0);      // + the score-exchange area(s)
-    FlashParams q = p;
-    q.n_qtiles = (p.Tq + QROWS - 1) / QROWS;
-    q.n_hblk = p.NH / HB;
-    const dim3 grid(q.n_qtiles * q.n_hblk, 1, B);
+    const FlashParams q = planned_params(p, pl);
+    const dim3 grid(pl.n_items, 1, B);
     if (lds > 65536)
     {
         // more than 64 KB of dynamic LDS must be allowed once per process (never inside a stream capture: the first prefill of a model is eager)
         static const hipError_t allowed = hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_prefill_kernel_s1<HS, HB, DS, NW, PIPE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (allowed != hipSuccess) return check_hip(allowed, "flash_prefill: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     }
+    note_prefill_form(pl);
     hipLaunchKernelGGL((flash_prefill_kernel_s1<HS, HB, DS, NW, PIPE>), grid, dim3(64 * NW), lds, s, q);
     MILA_LAUNCH_CHECK("flash_prefill");
 }
 
 template <int HS, int HB, int DS>
-static int launch_flash_pp(const FlashParams& p, int B, hipStream_t s)
+static int launch_flash_pp(const FlashParams& p, const PrefillPlan& pl, int B, hipStream_t s)
 {
-    constexpr int QROWS = 16 * (8 / (HB * DS));
     const size_t lds = (size_t)4 * kKeysPerTile * HS * 2;
-    FlashParams q = p;
-    q.n_qtiles = (p.Tq + QROWS - 1) / QROWS;
-    q.n_hblk = p.NH / HB;
-    const dim3 grid(q.n_qtiles * q.n_hblk, 1, B);
+    const FlashParams q = planned_params(p, pl);
+    const dim3 grid(pl.n_items, 1, B);
     if (lds > 65536)
     {
         static const hipError_t allowed = hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_prefill_pp_kernel<HS, HB, DS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (allowed != hipSuccess) return check_hip(allowed, "flash_prefill: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     }
+    note_prefill_form(pl);
     hipLaunchKernelGGL((flash_prefill_pp_kernel<HS, HB, DS>), grid, dim3(512), lds, s, q);
     MILA_LAUNCH_CHECK("flash_prefill");
 }
 
+// plan -> instantiation.  The plan holds the rules; this only maps (form, HB, DS, NW) to the kernels that exist for the head size, and says so where none does.
 template <int HS>
-static int dispatch_hb(const FlashParams& p, int B, hipStream_t s)
+static int dispatch_hb(const FlashParams& p, const PrefillPlan& pl, int B, hipStream_t s)
 {
-    const int GS = p.NH / p.NKV;
-    if constexpr (HS == 512) { if (g_tune_flash_form == 10 && GS % 4 == 0) return launch_flash_pp<HS, 4, 2>(p, B, s); }
-    if constexpr (HS == 256) { if (g_tune_flash_form == 10 && GS % 2 == 0) return launch_flash_pp<HS, 2, 1>(p, B, s); }
-    if constexpr (HS == 512) { if (g_tune_flash_form == 11 && GS % 4 == 0) return launch_flash_dma<HS, 4, 2, 8, true>(p, B, s); }
-    if constexpr (HS == 256) { if (g_tune_flash_form == 11 && GS % 2 == 0) return launch_flash_dma<HS, 2, 1, 4, true>(p, B, s); }
+    const int shape = pl.HB * 100 + pl.DS * 10 + pl.NW;
+    if (pl.form == PF_FLASH)
+    {
+        if (shape == 414) return launch_flash<HS, 4>(p, pl, B, s);
+        if (shape == 214) return launch_flash<HS, 2>(p, pl, B, s);
+        if (shape == 114) return launch_flash<HS, 1>(p, pl, B, s);
+    }
     if constexpr (HS == 512)
     {
-        if (g_tune_flash_form >= 8 && GS % 4 == 0) return launch_flash_dma<HS, 4, 2, 8>(p, B, s);      // four heads x two d-halves, double-buffered tiles
-        if (g_tune_flash_form >= 2) return GS % 2 == 0 ? launch_flash_dma<HS, 2, 2, 4>(p, B, s) : launch_flash_dma<HS, 1, 2, 4>(p, B, s);
+        if (pl.form == PF_FLASH_PP && shape == 428) return launch_flash_pp<HS, 4, 2>(p, pl, B, s);
+        if (pl.form == PF_FLASH_DMA_PIPE && shape == 428) return launch_flash_dma<HS, 4, 2, 8, true>(p, pl, B, s);
+        if (pl.form == PF_FLASH_DMA)
+        {
+            if (shape == 428) return launch_flash_dma<HS, 4, 2, 8>(p, pl, B, s);
+            if (shape == 224) return launch_flash_dma<HS, 2, 2, 4>(p, pl, B, s);
+            if (shape == 124) return launch_flash_dma<HS, 1, 2, 4>(p, pl, B, s);
+        }
     }
     if constexpr (HS == 256)
     {
-        // Double-buffered 4-wave workgroups, two per CU (their phases drift apart, so one's softmax runs under the other's products): 58 us on Gemma's
-        // sliding-window shape at T = 2048.  The 8-wave form (2 heads x 4 row blocks on one tile stream, one workgroup per CU: 1.4x the work per tile load, but
-        // its eight waves move in lockstep) was the faster one -- 76 vs 82 us -- while the tile body was bound by its vector ALU work; with the lean body it
-        // is the slower one (62 us) and stays behind tuning form 9 where at least half the chunk's rows see a full window.  (A d-split does not pay at this
-        // head size: 92.7 us.)
-        if (g_tune_flash_form == 9 && GS % 2 == 0 && p.window > 0 && p.pos_offset + p.Tq / 2 >= p.window) return launch_flash_dma<HS, 2, 1, 8>(p, B, s);
-        if (g_tune_flash_form >= 8)
+        if (pl.form == PF_FLASH_PP && shape == 218) return launch_flash_pp<HS, 2, 1>(p, pl, B, s);
+        if (pl.form == PF_FLASH_DMA_PIPE && shape == 214) return launch_flash_dma<HS, 2, 1, 4, true>(p, pl, B, s);
+        if (pl.form == PF_FLASH_DMA)
         {
-            if (GS % 4 == 0) return launch_flash_dma<HS, 4, 1, 4>(p, B, s);
-            if (GS % 2 == 0) return launch_flash_dma<HS, 2, 1, 4>(p, B, s);
-            return launch_flash_dma<HS, 1, 1, 4>(p, B, s);
+            if (shape == 218) return launch_flash_dma<HS, 2, 1, 8>(p, pl, B, s);
+            if (shape == 414) return launch_flash_dma<HS, 4, 1, 4>(p, pl, B, s);
+            if (shape == 214) return launch_flash_dma<HS, 2, 1, 4>(p, pl, B, s);
+            if (shape == 114) return launch_flash_dma<HS, 1, 1, 4>(p, pl, B, s);
         }
     }
-    if (GS % 4 == 0) return launch_flash<HS, 4>(p, B, s);
-    if (GS % 2 == 0) return launch_flash<HS, 2>(p, B, s);
-    return launch_flash<HS, 1>(p, B, s);
+    return set_error(MILA_E_UNSUPPORTED, "flash_prefill: no %s kernel for HS %d with %d heads x %d d-shares on %d waves", kPrefillFormNames[pl.form], HS, pl.HB, pl.DS, pl.NW);
 }
 
 int flash_dispatch(int HS, const FlashParams& p, int B, hipStream_t s)
 {
-    switch (HS)
+    const PrefillPlan pl = plan_prefill(HS, p.NH, p.NKV, p.Tq, p.pos_offset, p.window);
+    switch (pl.form == PF_GENERIC ? 0 : HS)
     {
-        case 64: return dispatch_hb<64>(p, B, s);
-        case 128: return dispatch_hb<128>(p, B, s);
-        case 256: return dispatch_hb<256>(p, B, s);
-        case 512: return dispatch_hb<512>(p, B, s);
+        case 64: return dispatch_hb<64>(p, pl, B, s);
+        case 128: return dispatch_hb<128>(p, pl, B, s);
+        case 256: return dispatch_hb<256>(p, pl, B, s);
+        case 512: return dispatch_hb<512>(p, pl, B, s);
         default:
         {
-            // any other head size (the reference tests' own HS = 4 / 8 geometries): the one-wave-per-row kernel of attention_generic.hip
             GenericAttnParams g{p.Y, p.Q, p.K, p.V, (int64_t)p.Tq * p.q_row_stride, p.q_row_stride, p.kv_b_stride, p.kv_h_stride, p.kv_r_stride,
                                 B, p.Tq, p.NH, p.NKV, HS, p.capacity, p.pos_offset, p.window, p.scale};
+            note_prefill_form(pl);
             return launch_attn_generic(g, s);
         }
     }
@@ -1386,6 +1451,15 @@ int mila_cdna4_mha_bf16(uint16_t* Y, const uint16_t* QKV, int B, int T, int C, i
     p.Tq = T; p.NH = NH; p.NKV = NH; p.capacity = T; p.pos_offset = 0; p.window = 0;
     p.scale = 1.0f / sqrtf((float)HS);
     return flash_dispatch(HS, p, B, as_stream(stream));
+}
+
+// the plan attn_prefill_bf16 launches from (mha_bf16: NKV = NH, pos_offset 0, window 0) as text, under the current flash.form; no device code runs
+size_t mila_cdna4_attn_prefill_plan_describe(int HS, int NH, int NKV, int chunk, int pos_offset, int window, char* buf, size_t cap)
+{
+    if (buf && cap) buf[0] = 0;
+    if (HS <= 0 || NH <= 0 || NKV <= 0 || NH % NKV != 0 || chunk <= 0 || pos_offset < 0 || window < 0) return 0;
+    const PrefillPlan pl = plan_prefill(HS, NH, NKV, chunk, pos_offset, window);
+    return 1 + snprintf(buf, buf ? cap : 0, "%s:%d:%d:%d:%d:%d:%d:%d", kPrefillFormNames[pl.form], pl.HB, pl.DS, pl.NW, pl.QROWS, pl.n_qtiles, pl.n_hblk, pl.n_items);
 }
 
 }  // extern "C"
