@@ -558,6 +558,31 @@ MILA_API int mila_cdna4_sample_argmax_advance_fp32(const float* logits, int32_t*
 MILA_API int mila_cdna4_sample_argmax_final_advance(int32_t* token_out, const void* scratch, size_t scratch_bytes, int blocks, int32_t* position_dev,
                                                     unsigned long long* seq_dev, unsigned long long* ring, int ring_size, mila_stream_t stream);
 
+/* The stochastic sampler as a pipeline that can sit in a captured decode step ("radix"): the semantics of sample_stochastic_* above, in the same order (softcap, then
+ * temperature; top-k survivors strictly above the (k+1)-th largest; the smallest nucleus whose mass exceeds top_p * total, a tie entering whole; the first index with
+ * e > 0 and cumulative >= r * total, else vocab - 1), from at most 9 launches over fixed buffers instead of 21.  replaces Sampling/Kernels/Sampling.cuh:
+ * cuda_sample_stochastic_fp32 / _bf16 (Sampling.cu:655-714; semantics of the single-block kernel :760-905).  Both thresholds come from digit selection over the 32-bit
+ * key (11 + 11 + 10 bits): integer counts for top-k (the threshold of sample_stochastic_* exactly), 64-bit fixed-point masses (scale 2^40) for top-p, summed with integer
+ * atomics, so a call is deterministic run to run.  The nucleus may differ from sample_stochastic_*'s where top_p * total lies within float rounding of a boundary, and
+ * in one more way: an entry with 0 < e < 2^-40 (2^-40 of the largest probability) adds nothing to the fixed-point total or the histograms, so with top_p < 1 it is never
+ * in the nucleus here, even for a top_p within 2^-22 of 1 at which sample_stochastic_* would keep it.  With top_p >= 1 such entries stay, as there.
+ *   sample_radix_fp32 / _bf16: the draw r in [0, 1] by value; nothing is advanced.
+ *   sample_radix_advance_fp32: the last node of a captured stochastic step, the twin of sample_argmax_final_advance -- the draw is draws[(*seq_dev + 1) % draws_size]
+ *     (host-visible memory the host rewrites between replays; read with one system-scope load), then *position_dev += 1, *seq_dev += 1 and, when ring != NULL,
+ *     ring[seq % ring_size] = seq << 32 | token with one system-scope release store.  seq_dev is required (the draw slot follows it), the ring is optional.
+ *   scratch: sample_radix_scratch_bytes(vocab) bytes, 8-byte aligned, the caller's for the duration of the call; the first launch clears what the others accumulate into.
+ *   sample_radix_plan_describe: "launches:k_passes:p_passes:scratch_need" of a call, from the host function the entries launch from (no device work): one launch fewer
+ *     per digit pass of a truncation that is off (top_k 0 or >= vocab; top_p >= 1), the first nucleus pass riding in the probability launch.  Returns the text's size. */
+MILA_API size_t mila_cdna4_sample_radix_scratch_bytes(int vocab);
+MILA_API int mila_cdna4_sample_radix_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                          void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_bf16(const uint16_t* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                          void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
+                                                  const float* draws, int draws_size, void* scratch, size_t scratch_bytes, int32_t* position_dev,
+                                                  unsigned long long* seq_dev, unsigned long long* ring, int ring_size, mila_stream_t stream);
+MILA_API size_t mila_cdna4_sample_radix_plan_describe(int vocab, int top_k, float top_p, char* buf, size_t cap);
+
 /* One-launch decode attention for one token (B == 1): q/k/v per-head RMSNorm + RoPE + KV append (the
  * work of fused_qkv_post) folded into the flash-decode kernel's prologue, where it overlaps the first
  * K/V round trip.  q_raw [NH*HS], k_raw / v_raw [NKV*HS] are the raw projections (v_raw == k_raw on Gemma

@@ -91,6 +91,14 @@ def load():
     main.mila_cdna4_attn_decode_kvfp8_plan_describe.restype = z
     main.mila_cdna4_attn_prefill_plan_describe.argtypes = [i, i, i, i, i, i, p, z]                                # HS NH NKV chunk pos_offset window | buf cap
     main.mila_cdna4_attn_prefill_plan_describe.restype = z
+    # the stochastic sampler's radix pipeline (csrc/sampling.hip: run_radix)
+    main.mila_cdna4_sample_radix_scratch_bytes.argtypes = [i]
+    main.mila_cdna4_sample_radix_scratch_bytes.restype = z
+    main.mila_cdna4_sample_radix_fp32.argtypes = [p, p, i, f, f, i, f, f, p, z, p]                                # logits token_out | vocab softcap temperature top_k top_p r | scratch bytes
+    main.mila_cdna4_sample_radix_bf16.argtypes = [p, p, i, f, f, i, f, f, p, z, p]
+    main.mila_cdna4_sample_radix_advance_fp32.argtypes = [p, p, i, f, f, i, f, p, i, p, z, p, p, p, i, p]         # ... top_p | draws draws_size | scratch bytes | position_dev seq_dev ring ring_size
+    main.mila_cdna4_sample_radix_plan_describe.argtypes = [i, i, f, p, z]                                         # vocab top_k top_p | buf cap
+    main.mila_cdna4_sample_radix_plan_describe.restype = z
     main.mila_cdna4_kv_dequant_fp8_bf16.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                        # Kc Vc K8 V8 Ks Vs | B NKV HS capacity first_pos count
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.argtypes = [i, i, i, i]                                      # B NKV HS capacity
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.restype = z
@@ -206,6 +214,34 @@ def attn_prefill_plan(HS, NH, NKV, chunk, pos_offset=0, window=0):
     return dict(zip(PREFILL_PLAN_FIELDS, [f[0]] + [int(v) for v in f[1:]]))
 
 
+RADIX_PLAN_FIELDS = ("launches", "k_passes", "p_passes", "scratch_need")
+
+
+def sample_radix_plan(vocab, top_k, top_p):
+    """what a sample_radix_* call launches (csrc/sampling.hip: plan_radix) as a dict of RADIX_PLAN_FIELDS: kernel launches, digit passes of the top-k and of the
+    nucleus search (0 = that truncation is off), scratch bytes.  Needs no GPU."""
+    buf = C.create_string_buffer(128)
+    need = load().mila_cdna4_sample_radix_plan_describe(int(vocab), int(top_k), float(top_p), buf, C.c_size_t(len(buf)))
+    assert 0 < need <= len(buf), "no plan for these arguments" if not need else "plan text of %d bytes" % need
+    return dict(zip(RADIX_PLAN_FIELDS, [int(v) for v in buf.value.decode().split(":")]))
+
+
+def sample_radix_scratch_bytes(vocab):
+    return int(load().mila_cdna4_sample_radix_scratch_bytes(int(vocab)))
+
+
+def sample_radix(logits, token_out, softcap, temperature, top_k, top_p, r, scratch, bf16=False):
+    """token_out[0] <- the radix pipeline's sample from `logits` (fp32, or bf16 bits with bf16=True) at the draw r, on the current torch stream"""
+    call("sample_radix_bf16" if bf16 else "sample_radix_fp32", logits, token_out, int(logits.numel()), float(softcap), float(temperature), int(top_k), float(top_p), float(r),
+         scratch, C.c_size_t(scratch.numel() * scratch.element_size()))
+
+
+def sample_radix_advance(logits, token_out, softcap, temperature, top_k, top_p, draws, scratch, position_dev, seq_dev, ring=None):
+    """the graph form's call: the draw is draws[(*seq_dev + 1) % len(draws)]; bumps *position_dev and *seq_dev, publishes seq << 32 | token into `ring` when given"""
+    call("sample_radix_advance_fp32", logits, token_out, int(logits.numel()), float(softcap), float(temperature), int(top_k), float(top_p), draws, int(draws.numel()),
+         scratch, C.c_size_t(scratch.numel() * scratch.element_size()), position_dev, seq_dev, ring, 0 if ring is None else int(ring.numel()))
+
+
 def prefill_form_name(plan, HS):
     """what last_form() reports for a launch from this plan: the form and its instantiation"""
     return plan["form"] if plan["form"] == "attn_generic" else "%s_hs%d_hb%d_ds%d_nw%d" % (plan["form"], HS, plan["HB"], plan["DS"], plan["NW"])
@@ -256,6 +292,7 @@ EXPORTED = [
     "convert_f32_to_bf16", "convert_bf16_to_f32", "fill_uniform_bf16",
     "sample_scratch_bytes", "sample_argmax_fp32", "sample_argmax_bf16",
     "sample_stochastic_scratch_bytes", "sample_stochastic_fp32", "sample_stochastic_bf16",
+    "sample_radix_scratch_bytes", "sample_radix_fp32", "sample_radix_bf16", "sample_radix_advance_fp32", "sample_radix_plan_describe",
     "fused_norm_matvec", "fused_qkv_post", "fused_qkv_post_prefill", "fused_tail_norm_bf16", "fused_tail_norm_quant_bf16",
     "attn_decode_bf16_devpos", "fused_qkv_post_devpos", "advance_position", "advance_position_snapshot", "snapshot_token", "sample_argmax_advance_fp32", "sample_argmax_final_advance", "fused_attn_decode_batch_bf16", "fused_attn_decode_bf16",
     "attn_decode_band_bucket", "dequantize_to_bf16", "gemm_geglu_fp8_scaled",

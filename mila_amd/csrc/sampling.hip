@@ -394,6 +394,434 @@ static int run_stochastic(const T* logits, int32_t* token_out, int vocab, float 
     return check_hip(hipGetLastError(), who);
 }
 
+// ================================================================================================
+// The radix pipeline: the same sampler (softcap + temperature, top-k, top-p, inverse CDF in token-index order -- the semantics stated above) in at most 9 launches
+// instead of 21, every buffer fixed, so that it can sit in a captured decode step.  Both thresholds are found by DIGIT SELECTION over the 32-bit key (11 + 11 + 10 bits):
+// a launch builds the histogram of the next digit over the elements that share the digits found so far -- per workgroup in LDS, flushed with integer atomics into a
+// global histogram the first launch cleared -- and the NEXT launch's prologue picks the digit by a suffix scan of that histogram, every workgroup the same way (what
+// advance_search does for the 16-ary search).  Every dependency is a kernel boundary.
+//   top-k: the histogram counts keys; the threshold is the largest t with count(key >= t) >= k + 1 -- integers, the 16-ary search's threshold exactly.
+//   top-p: the histogram sums e = expf(x - max) as unsigned 64-bit fixed point (scale 2^40: e <= 1, 2^18 entries sum below 2^59; the truncation is below 2^-22 of the
+//          total, which is >= 2^40 because the maximum contributes e = 1).  Integer sums do not depend on the order of the atomics: run to run the same bits.
+// The per-element e, the survivor tests (ordered_key(x) > kthr, bits(e) >= pthr) and the final walk in index order are the first pipeline's.
+constexpr int kRadixPasses = 3;
+constexpr int kRadixBins = 2048;                    // bins of a pass (the last one uses 1024 of them)
+constexpr int kRadixBlocks = 128;                   // workgroups of the pass / prob launches: each flushes its histogram, and adds to one word serialize
+constexpr double kRadixFixedScale = 1099511627776.0;      // 2^40
+__host__ __device__ constexpr int radix_shift(int pass) { return pass == 0 ? 21 : (pass == 1 ? 10 : 0); }
+__host__ __device__ constexpr int radix_bins(int pass) { return pass == 2 ? 1024 : 2048; }
+
+struct RadixState                   // what i digit passes of a search have fixed
+{
+    unsigned long long above;       // count / fixed-point mass of the keys above the prefix's range
+    uint32_t prefix;                // the digits found so far (lower bits zero)
+    uint32_t pad;
+};
+struct RadixHeader                  // 256 bytes, cleared with the histograms by the first launch
+{
+    unsigned long long total;       // fixed-point sum of e over the top-k survivors
+    RadixState k[kRadixPasses + 1], p[kRadixPasses + 1];      // [i]: the state after i passes ([0] stays zero); [3].prefix is the threshold
+    unsigned long long pad[32 - 1 - 4 * (kRadixPasses + 1)];
+};
+static_assert(sizeof(RadixHeader) == 256, "RadixHeader");
+
+struct RadixParams
+{
+    RadixHeader* hdr;
+    uint32_t* khist;                // [kRadixPasses][kRadixBins] key counts
+    unsigned long long* phist;      // [kRadixPasses][kRadixBins] fixed-point masses
+    float* red;                     // [kSampBlocks] per-workgroup max, then [kSampBlocks] chunk sums of the masked probabilities
+    float* w;                       // [vocab] scaled logits, then probabilities, then the masked probabilities
+    int32_t* token_out;
+    int vocab, top_k;
+    float softcap, temperature, top_p, r;
+    // the graph form's tail (radix_cdf_kernel<true>)
+    const float* draws;
+    int draws_size, ring_size;
+    int32_t* pos;
+    unsigned long long* seq_dev;
+    unsigned long long* ring;
+};
+
+__device__ __forceinline__ unsigned long long radix_fixed(float e) { return (unsigned long long)((double)e * kRadixFixedScale); }
+
+// the digit of a finished histogram pass: the largest d with above + sum(hist[d ..]) >= need (STRICT: > need); `above_out` = above + sum(hist[d + 1 ..]).
+// All 256 threads of the workgroup call it; thread t owns bins [t * per, (t + 1) * per).  No bin satisfies the condition (NaN input): digit 0.
+template <typename T, bool STRICT>
+__device__ void radix_pick(const T* __restrict__ hist, int bins, unsigned long long above, unsigned long long need, uint32_t& digit, unsigned long long& above_out,
+                           unsigned long long* sh /* [8] */)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int per = bins >> 8;      // 8 or 4
+    unsigned long long v[8], mine = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { v[j] = j < per ? (unsigned long long)hist[t * per + j] : 0ull; mine += v[j]; }
+    unsigned long long inc = mine;      // sum over this wave's lanes >= lane
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1)
+    {
+        const unsigned long long o = __shfl_down(inc, off, 64);
+        if (lane + off < 64) inc += o;
+    }
+    if (lane == 0) sh[wave] = inc;
+    if (t == 0) { sh[4] = 0ull; sh[5] = 0ull; }
+    __syncthreads();
+    unsigned long long run = above + inc - mine;      // everything above this thread's bins
+    for (int w = wave + 1; w < 4; ++w) run += sh[w];
+    auto ok = [&](unsigned long long x) { return STRICT ? x > need : x >= need; };
+    if (!ok(run) && ok(run + mine))                   // the sums are monotone: at most one thread
+    {
+#pragma unroll
+        for (int j = 7; j >= 0; --j)
+        {
+            if (j >= per) continue;
+            if (ok(run + v[j])) { sh[4] = (unsigned long long)(t * per + j); sh[5] = run; break; }
+            run += v[j];
+        }
+    }
+    __syncthreads();
+    digit = (uint32_t)sh[4];
+    above_out = sh[5];
+    __syncthreads();
+}
+
+// A thread's strided walk over the vector, its first kRadixPre elements requested BEFORE the prologue that picks the previous pass's digit (a chain of dependent
+// loads, a scan and three barriers): the prologue's latency hides theirs.  At 2^18 entries and kRadixBlocks workgroups that is the whole walk.
+constexpr int kRadixPre = 8;
+__device__ __forceinline__ void radix_preload(const float* w, int first, int stride, int end, float (&pre)[kRadixPre])
+{
+#pragma unroll
+    for (int j = 0; j < kRadixPre; ++j)
+    {
+        const int i = first + j * stride;
+        pre[j] = i < end ? w[i] : 0.0f;
+    }
+}
+template <typename F>
+__device__ __forceinline__ void radix_walk(const float* w, int first, int stride, int end, const float (&pre)[kRadixPre], F&& body)
+{
+#pragma unroll
+    for (int j = 0; j < kRadixPre; ++j)
+    {
+        const int i = first + j * stride;
+        if (i < end) body(i, pre[j]);
+    }
+    for (int i = first + kRadixPre * stride; i < end; i += stride) body(i, w[i]);
+}
+
+// launch 1: x = softcap / temperature, per-workgroup max; clears the header and both histograms for the launches behind it
+template <typename T>
+__global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ logits, const RadixParams p, int clear_words)
+{
+    __shared__ float sv[4];
+    uint32_t* z = reinterpret_cast<uint32_t*>(p.hdr);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < clear_words; i += gridDim.x * 256) z[i] = 0u;
+    float mx = -FLT_MAX;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < p.vocab; i += gridDim.x * 256)
+    {
+        float x = to_f32(logits[i]);
+        if (p.softcap > 0.0f) x = p.softcap * tanhf(x / p.softcap);
+        x = x / p.temperature;
+        p.w[i] = x;
+        mx = fmaxf(mx, x);
+    }
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) p.red[blockIdx.x] = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
+}
+
+// top-k digit pass: pick the previous pass's digit, then count this pass's digit over the keys that share the prefix
+__global__ __launch_bounds__(256) void radix_kpass_kernel(const RadixParams p, int pass)
+{
+    __shared__ uint32_t lh[kRadixBins];
+    __shared__ unsigned long long sh[8];
+    const int first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    float pre[kRadixPre];
+    radix_preload(p.w, first, stride, p.vocab, pre);
+    RadixState st{0ull, 0u, 0u};
+    if (pass > 0)
+    {
+        const RadixState prev = p.hdr->k[pass - 1];
+        uint32_t digit;
+        radix_pick<uint32_t, false>(p.khist + (size_t)(pass - 1) * kRadixBins, radix_bins(pass - 1), prev.above, (unsigned long long)p.top_k + 1ull, digit, st.above, sh);
+        st.prefix = prev.prefix | (digit << radix_shift(pass - 1));
+        if (blockIdx.x == 0 && threadIdx.x == 0) p.hdr->k[pass] = st;
+    }
+    const int bins = radix_bins(pass), shift = radix_shift(pass);
+    const int hshift = pass > 0 ? radix_shift(pass - 1) : 0;      // the bits above it are the prefix
+    for (int b = threadIdx.x; b < bins; b += 256) lh[b] = 0u;
+    __syncthreads();
+    radix_walk(p.w, first, stride, p.vocab, pre, [&](int, float x)
+    {
+        const uint32_t key = ordered_key(x);
+        if (pass == 0 || (key >> hshift) == (st.prefix >> hshift)) atomicAdd(&lh[(key >> shift) & (uint32_t)(bins - 1)], 1u);
+    });
+    __syncthreads();
+    uint32_t* gh = p.khist + (size_t)pass * kRadixBins;
+    for (int b = threadIdx.x; b < bins; b += 256)
+        if (lh[b]) atomicAdd(&gh[b], lh[b]);
+}
+
+// probabilities of the top-k survivors (samp_prob_kernel's expression), their fixed-point total, and the first digit pass of the nucleus search over bits(e)
+__global__ __launch_bounds__(256) void radix_prob_kernel(const RadixParams p, int use_k, int use_p, int nblocks_scale)
+{
+    __shared__ unsigned long long lh[kRadixBins];
+    __shared__ unsigned long long sh[8];
+    __shared__ float sv[4];
+    const int lane = threadIdx.x & 63;
+    const int first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    float pre[kRadixPre];
+    radix_preload(p.w, first, stride, p.vocab, pre);
+    float mx = -FLT_MAX;
+    for (int b = threadIdx.x; b < nblocks_scale; b += 256) mx = fmaxf(mx, p.red[b]);
+    mx = wave_max(mx);
+    if (lane == 0) sv[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
+    uint32_t kthr = 0u;
+    if (use_k)
+    {
+        const RadixState prev = p.hdr->k[kRadixPasses - 1];
+        RadixState st{0ull, 0u, 0u};
+        uint32_t digit;
+        radix_pick<uint32_t, false>(p.khist + (size_t)(kRadixPasses - 1) * kRadixBins, radix_bins(kRadixPasses - 1), prev.above, (unsigned long long)p.top_k + 1ull, digit,
+                                    st.above, sh);
+        kthr = prev.prefix | digit;       // key of the (k+1)-th largest value
+        st.prefix = kthr;
+        if (blockIdx.x == 0 && threadIdx.x == 0) p.hdr->k[kRadixPasses] = st;
+    }
+    if (use_p)
+        for (int b = threadIdx.x; b < kRadixBins; b += 256) lh[b] = 0ull;
+    __syncthreads();
+    unsigned long long sum = 0ull;
+    radix_walk(p.w, first, stride, p.vocab, pre, [&](int i, float x)
+    {
+        const float e = (!use_k || ordered_key(x) > kthr) ? expf(x - mx) : 0.0f;
+        p.w[i] = e;
+        const unsigned long long f = (use_p && e > 0.0f) ? radix_fixed(e) : 0ull;
+        sum += f;
+        if (f) atomicAdd(&lh[(__float_as_uint(e) >> radix_shift(0)) & (uint32_t)(kRadixBins - 1)], f);
+    });
+    if (!use_p) return;      // only the nucleus search reads the total and the histogram
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    if (lane == 0) sh[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(&p.hdr->total, (sh[0] + sh[1]) + (sh[2] + sh[3]));      // one add per workgroup
+    for (int b = threadIdx.x; b < kRadixBins; b += 256)
+        if (lh[b]) atomicAdd(&p.phist[b], lh[b]);
+}
+
+__device__ __forceinline__ unsigned long long radix_mass_target(float top_p, unsigned long long total)
+{
+    return (unsigned long long)((double)top_p * (double)total);      // the nucleus holds the keys whose mass EXCEEDS it
+}
+
+// nucleus digit pass 1 / 2: pick the previous pass's digit, then sum this pass's digit over the probabilities that share the prefix
+__global__ __launch_bounds__(256) void radix_ppass_kernel(const RadixParams p, int pass)
+{
+    __shared__ unsigned long long lh[kRadixBins];
+    __shared__ unsigned long long sh[8];
+    const int first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    float pre[kRadixPre];
+    radix_preload(p.w, first, stride, p.vocab, pre);
+    const RadixState prev = p.hdr->p[pass - 1];
+    RadixState st{0ull, 0u, 0u};
+    uint32_t digit;
+    radix_pick<unsigned long long, true>(p.phist + (size_t)(pass - 1) * kRadixBins, radix_bins(pass - 1), prev.above, radix_mass_target(p.top_p, p.hdr->total), digit, st.above, sh);
+    st.prefix = prev.prefix | (digit << radix_shift(pass - 1));
+    if (blockIdx.x == 0 && threadIdx.x == 0) p.hdr->p[pass] = st;
+    const int bins = radix_bins(pass), shift = radix_shift(pass), hshift = radix_shift(pass - 1);
+    for (int b = threadIdx.x; b < bins; b += 256) lh[b] = 0ull;
+    __syncthreads();
+    radix_walk(p.w, first, stride, p.vocab, pre, [&](int, float e)
+    {
+        const uint32_t key = __float_as_uint(e);       // e >= 0: the bits are ordered
+        if (e > 0.0f && (key >> hshift) == (st.prefix >> hshift))
+        {
+            const unsigned long long f = radix_fixed(e);
+            if (f) atomicAdd(&lh[(key >> shift) & (uint32_t)(bins - 1)], f);
+        }
+    });
+    __syncthreads();
+    unsigned long long* gh = p.phist + (size_t)pass * kRadixBins;
+    for (int b = threadIdx.x; b < bins; b += 256)
+        if (lh[b]) atomicAdd(&gh[b], lh[b]);
+}
+
+// nucleus mask + contiguous-chunk sums for the index-order CDF (samp_mask_kernel with the radix search's threshold)
+__global__ __launch_bounds__(256) void radix_mask_kernel(const RadixParams p, int use_p, int chunk)
+{
+    __shared__ unsigned long long sh[8];
+    __shared__ float sv[4];
+    const int i0 = blockIdx.x * chunk, i1 = min(p.vocab, i0 + chunk);
+    float pre[kRadixPre];
+    radix_preload(p.w, i0 + threadIdx.x, 256, i1, pre);
+    uint32_t pthr = 0u;
+    if (use_p)
+    {
+        const RadixState prev = p.hdr->p[kRadixPasses - 1];
+        RadixState st{0ull, 0u, 0u};
+        uint32_t digit;
+        radix_pick<unsigned long long, true>(p.phist + (size_t)(kRadixPasses - 1) * kRadixBins, radix_bins(kRadixPasses - 1), prev.above,
+                                             radix_mass_target(p.top_p, p.hdr->total), digit, st.above, sh);
+        pthr = prev.prefix | digit;       // bits of the nucleus boundary probability
+        st.prefix = pthr;
+        if (blockIdx.x == 0 && threadIdx.x == 0) p.hdr->p[kRadixPasses] = st;
+    }
+    float sum = 0.0f;
+    radix_walk(p.w, i0 + threadIdx.x, 256, i1, pre, [&](int i, float e)
+    {
+        if (use_p && __float_as_uint(e) < pthr) { e = 0.0f; p.w[i] = 0.0f; }
+        sum += e;
+    });
+    sum = wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) p.red[kSampBlocks + blockIdx.x] = ((sv[0] + sv[1]) + sv[2]) + sv[3];
+}
+
+__device__ __forceinline__ float lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+// inverse CDF in token-index order: samp_cdf_kernel's sums and walk, value for value (the same additions in the same order), by one wave that holds the chunk sums in
+// registers and steps over the zeros of the walk: adding 0 leaves the cumulative sum as it is, and after the truncations nearly every entry is 0.
+// ADVANCE: the stochastic twin of argmax_final_advance_kernel -- the draw is slot (*seq_dev + 1) % draws_size of a host-written ring (system-scope load: the host
+// rewrites the slots between replays), and the tail bumps the position, stores the sequence number and (ring != NULL) publishes seq << 32 | token.
+template <bool ADVANCE>
+__global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int nchunks, int chunk)
+{
+    const int lane = threadIdx.x;
+    float r = p.r;
+    unsigned long long seq = 0ull;
+    if (ADVANCE)
+    {
+        seq = *p.seq_dev + 1ull;
+        const uint32_t* slot = reinterpret_cast<const uint32_t*>(p.draws) + (seq % (unsigned long long)p.draws_size);
+        r = __uint_as_float(__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+    }
+    const float* cs = p.red + kSampBlocks;
+    float c[4];      // chunk sums: lane l holds chunks l, 64 + l, 128 + l, 192 + l
+#pragma unroll
+    for (int q = 0; q < 4; ++q) c[q] = (q * 64 + lane) < nchunks ? cs[q * 64 + lane] : 0.0f;
+    float total = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        for (int l = 0; l < 64; ++l)
+            if (q * 64 + l < nchunks) total += lane_value(c[q], l);
+    const float target = r * total;
+    float before = 0.0f;
+    int b = 0;
+    bool located = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        for (int l = 0; l < 64; ++l)
+        {
+            if (located || q * 64 + l >= nchunks - 1) continue;
+            const float v = lane_value(c[q], l);
+            if (before + v < target) { before += v; b = q * 64 + l + 1; }
+            else located = true;
+        }
+    int result = p.vocab - 1;
+    float cum = before;
+    bool found = false;
+    // kCdfBatch x 64 entries are requested together (a chunk of a 2^18-entry vocabulary in one round trip), then walked in index order
+    constexpr int kCdfBatch = 16;
+    for (int base = b * chunk; base < p.vocab && !found; base += kCdfBatch * 64)
+    {
+        float e[kCdfBatch];
+#pragma unroll
+        for (int q = 0; q < kCdfBatch; ++q) e[q] = (base + q * 64 + lane) < p.vocab ? p.w[base + q * 64 + lane] : 0.0f;
+#pragma unroll
+        for (int q = 0; q < kCdfBatch; ++q)
+        {
+            unsigned long long m = found ? 0ull : __ballot(e[q] > 0.0f);
+            while (m)
+            {
+                const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
+                m &= m - 1ull;
+                cum += lane_value(e[q], l);
+                if (cum >= target) { result = base + q * 64 + l; found = true; break; }
+            }
+        }
+    }
+    if (lane == 0)
+    {
+        p.token_out[0] = result;
+        if (ADVANCE)
+        {
+            *p.pos += 1;
+            *p.seq_dev = seq;
+            if (p.ring != nullptr)
+                __hip_atomic_store(p.ring + (seq % (unsigned long long)p.ring_size), (seq << 32) | (unsigned long long)(uint32_t)result, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// the one place that decides what a radix call launches: the entries below and sample_radix_plan_describe read it
+struct RadixPlan
+{
+    int launches;            // kernel nodes of one call: scale + k_passes + prob + (p_passes - 1: the first nucleus pass rides in prob) + mask + cdf
+    int k_passes, p_passes;  // digit passes of the two searches (0 = that truncation is off)
+    int scale_blocks;        // workgroups of the scale launch (a plain stream: as many as the partial-maximum array holds)
+    int blocks;              // workgroups of the pass / prob launches
+    int chunk, nchunks;      // the mask launch's contiguous chunks
+    size_t scratch_need;
+};
+constexpr size_t kRadixHistBytes = (size_t)kRadixPasses * kRadixBins * (sizeof(uint32_t) + sizeof(unsigned long long));
+static RadixPlan plan_radix(int vocab, int top_k, float top_p)
+{
+    RadixPlan d{};
+    d.k_passes = (top_k > 0 && top_k < vocab) ? kRadixPasses : 0;
+    d.p_passes = top_p < 1.0f ? kRadixPasses : 0;
+    d.launches = 1 + d.k_passes + 1 + (d.p_passes ? d.p_passes - 1 : 0) + 2;
+    d.blocks = d.scale_blocks = (vocab + 255) / 256;
+    if (d.blocks > kRadixBlocks) d.blocks = kRadixBlocks;
+    if (d.scale_blocks > kSampBlocks) d.scale_blocks = kSampBlocks;
+    d.chunk = (vocab + kSampBlocks - 1) / kSampBlocks;
+    d.nchunks = (vocab + d.chunk - 1) / d.chunk;
+    d.scratch_need = sizeof(RadixHeader) + kRadixHistBytes + (size_t)2 * kSampBlocks * 4 + (size_t)vocab * 4;
+    return d;
+}
+
+struct RadixAdvance { const float* draws; int draws_size; int32_t* pos; unsigned long long* seq_dev; unsigned long long* ring; int ring_size; };
+
+// adv == nullptr: the draw is `r` and nothing is advanced
+template <typename T>
+static int run_radix(const T* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r, const RadixAdvance* adv,
+                     void* scratch, size_t scratch_bytes, hipStream_t s, const char* who)
+{
+    MILA_REQUIRE(logits && token_out, "%s: null pointer", who);
+    MILA_REQUIRE(!adv || (adv->draws && adv->pos && adv->seq_dev), "%s: null pointer", who);
+    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
+    MILA_REQUIRE(temperature > 0.0f, "%s: temperature must be > 0 (temperature <= 0 is the greedy sampler: sample_argmax)", who);
+    MILA_REQUIRE(top_k >= 0 && top_p > 0.0f && r >= 0.0f && r <= 1.0f, "%s: need top_k >= 0, top_p > 0, 0 <= r <= 1", who);
+    MILA_REQUIRE(!adv || adv->draws_size > 0, "%s: draws_size must be positive", who);
+    MILA_REQUIRE(!adv || (adv->ring ? adv->ring_size > 0 : adv->ring_size == 0), "%s: ring and ring_size go together", who);
+    const RadixPlan d = plan_radix(vocab, top_k, top_p);
+    if (!scratch || scratch_bytes < d.scratch_need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, d.scratch_need);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, "%s: scratch must be 8-byte aligned", who);
+    RadixParams p{};
+    char* base = reinterpret_cast<char*>(scratch);
+    p.hdr = reinterpret_cast<RadixHeader*>(base);
+    p.khist = reinterpret_cast<uint32_t*>(base + sizeof(RadixHeader));
+    p.phist = reinterpret_cast<unsigned long long*>(p.khist + (size_t)kRadixPasses * kRadixBins);
+    p.red = reinterpret_cast<float*>(base + sizeof(RadixHeader) + kRadixHistBytes);
+    p.w = p.red + 2 * kSampBlocks;
+    p.token_out = token_out; p.vocab = vocab; p.top_k = top_k;
+    p.softcap = softcap; p.temperature = temperature; p.top_p = top_p; p.r = r;
+    if (adv) { p.draws = adv->draws; p.draws_size = adv->draws_size; p.pos = adv->pos; p.seq_dev = adv->seq_dev; p.ring = adv->ring; p.ring_size = adv->ring_size; }
+    const int clear_words = (int)((sizeof(RadixHeader) + kRadixHistBytes) / 4);
+    hipLaunchKernelGGL(radix_scale_kernel<T>, dim3(d.scale_blocks), dim3(256), 0, s, logits, p, clear_words);
+    for (int pass = 0; pass < d.k_passes; ++pass) hipLaunchKernelGGL(radix_kpass_kernel, dim3(d.blocks), dim3(256), 0, s, p, pass);
+    hipLaunchKernelGGL(radix_prob_kernel, dim3(d.blocks), dim3(256), 0, s, p, d.k_passes ? 1 : 0, d.p_passes ? 1 : 0, d.scale_blocks);
+    for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_kernel, dim3(d.blocks), dim3(256), 0, s, p, pass);
+    hipLaunchKernelGGL(radix_mask_kernel, dim3(d.nchunks), dim3(256), 0, s, p, d.p_passes ? 1 : 0, d.chunk);
+    if (adv) hipLaunchKernelGGL(radix_cdf_kernel<true>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
+    else hipLaunchKernelGGL(radix_cdf_kernel<false>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
+    return check_hip(hipGetLastError(), who);
+}
+
 }  // namespace mila
 
 using namespace mila;
@@ -461,6 +889,37 @@ int mila_cdna4_sample_stochastic_bf16(const uint16_t* logits, int32_t* token_out
 {
     return run_stochastic<uint16_t>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, scratch, scratch_bytes,
                                     as_stream(stream), "sample_stochastic_bf16");
+}
+
+size_t mila_cdna4_sample_radix_scratch_bytes(int vocab) { return vocab > 0 ? plan_radix(vocab, 0, 1.0f).scratch_need : 0; }
+
+int mila_cdna4_sample_radix_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                 void* scratch, size_t scratch_bytes, mila_stream_t stream)
+{
+    return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_fp32");
+}
+
+int mila_cdna4_sample_radix_bf16(const uint16_t* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                 void* scratch, size_t scratch_bytes, mila_stream_t stream)
+{
+    return run_radix<uint16_t>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_bf16");
+}
+
+int mila_cdna4_sample_radix_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
+                                         const float* draws, int draws_size, void* scratch, size_t scratch_bytes, int32_t* position_dev,
+                                         unsigned long long* seq_dev, unsigned long long* ring, int ring_size, mila_stream_t stream)
+{
+    const RadixAdvance adv{draws, draws_size, position_dev, seq_dev, ring, ring_size};
+    return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream),
+                            "sample_radix_advance_fp32");
+}
+
+size_t mila_cdna4_sample_radix_plan_describe(int vocab, int top_k, float top_p, char* buf, size_t cap)
+{
+    if (buf && cap) buf[0] = 0;
+    if (vocab <= 0 || top_k < 0 || !(top_p > 0.0f)) return 0;
+    const RadixPlan d = plan_radix(vocab, top_k, top_p);
+    return 1 + snprintf(buf, buf ? cap : 0, "%d:%d:%d:%zu", d.launches, d.k_passes, d.p_passes, d.scratch_need);
 }
 
 }  // extern "C"

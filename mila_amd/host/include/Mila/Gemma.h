@@ -15,6 +15,7 @@
 #pragma once
 #include <functional>
 #include <map>
+#include <optional>
 
 #include <hip/hip_runtime_api.h>
 
@@ -214,6 +215,10 @@ namespace Mila::Dnn
             return *logits_;
         }
 
+        /// SamplingParams (Components/Transformers/SamplingParams.ixx): temperature <= 0 is greedy; top_k 0 / top_p >= 1 disable
+        /// the truncations.  The uniform r in [0, 1) is drawn by the caller, as in the reference (host RNG, GemmaModel.ixx:568).
+        struct SamplingParams { float temperature = 1.0f; int top_k = 0; float top_p = 1.0f; };
+
         /// capture the fused step once; afterwards replayGraph() advances one token per call.
         /// The token is read from `token` (device) and the position from an internal device counter.
         /// Every device pointer the captured nodes hold is model-owned and fixed for the model's lifetime (the split-attention partials
@@ -234,8 +239,18 @@ namespace Mila::Dnn
                 // workgroup leaves its best logit and index in the sampler scratch), its final reduction does the other three: one launch behind the head, not three
                 int sampler_partials = 0;
                 captured_band_end_ = bandBucket( start_position );
-                enqueueFusedStep( token.data(), static_cast<int>( captured_band_end_ ), pos_dev_->data(), sample_in_graph_ ? &sampler_partials : nullptr );
-                if ( sample_in_graph_ )
+                const bool stochastic = graph_sampling_.has_value();
+                if ( stochastic && ( !draw_ring_ || !token_seq_ ) )
+                    throw std::invalid_argument( "GemmaTransformer::captureGraph: a stochastic step needs setDrawRing() and the sequence counter of setTokenRing()" );
+                enqueueFusedStep( token.data(), static_cast<int>( captured_band_end_ ), pos_dev_->data(), ( sample_in_graph_ && !stochastic ) ? &sampler_partials : nullptr );
+                // stochastic: the step ends at the logits like the sampler-less one, then the radix pipeline on the model-owned workspace; its last node draws from the
+                // ring, writes the next token, bumps the position and publishes -- in the place of the advance_position node.  One linear chain on one stream.
+                if ( stochastic )
+                    Compute::rocmCheck( mila_cdna4_sample_radix_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping,
+                                                                              graph_sampling_->temperature, graph_sampling_->top_k, graph_sampling_->top_p, draw_ring_, draw_ring_size_,
+                                                                              radix_scratch_->data(), radix_scratch_->sizeInBytes(), pos_dev_->data(), token_seq_, token_ring_,
+                                                                              token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
+                else if ( sample_in_graph_ )
                     Compute::rocmCheck( mila_cdna4_sample_argmax_final_advance( const_cast<TokenTensor&>( token ).data(), sample_scratch_->data(), sample_scratch_->sizeInBytes(), sampler_partials,
                                                                                 pos_dev_->data(), token_ring_ ? token_seq_ : nullptr, token_ring_, token_ring_ ? token_ring_size_ : 0,
                                                                                 ctx_->getStream() ) );
@@ -250,6 +265,8 @@ namespace Mila::Dnn
             captured_token_ = token.data();
             captured_sample_in_graph_ = sample_in_graph_;
             captured_ring_ = token_ring_;
+            captured_sampling_ = graph_sampling_;
+            captured_draw_ring_ = graph_sampling_ ? draw_ring_ : nullptr;
             ++graph_captures_;
         }
         /// capture on first use, and again whenever the captured graph no longer matches what a replay must do: another token
@@ -259,6 +276,7 @@ namespace Mila::Dnn
         void ensureGraph( const TokenTensor& token, dim_t start_position )
         {
             if ( !graph_exec_ || captured_token_ != token.data() || captured_sample_in_graph_ != sample_in_graph_ || captured_ring_ != token_ring_ ||
+                 !sameSampling( captured_sampling_, graph_sampling_ ) || ( graph_sampling_ && captured_draw_ring_ != draw_ring_ ) ||
                  bandBucket( start_position ) != captured_band_end_ )
                 captureGraph( token, start_position );
         }
@@ -289,6 +307,22 @@ namespace Mila::Dnn
             if ( ring && ( size <= 0 || !seq_dev ) ) throw std::invalid_argument( "GemmaTransformer::setTokenRing: a ring needs a positive size and a sequence counter" );
             token_ring_ = ring; token_ring_size_ = ring ? size : 0; token_seq_ = ring ? seq_dev : nullptr;
         }
+        /// the stochastic sampler as the tail of the captured step (the radix pipeline, mila_cdna4_sample_radix_advance_fp32): with `sp` set, a capture ends at the
+        /// logits and runs the sampler's launches behind them, the last of which takes the place of the position bump; nullopt = off (the greedy / sampler-less
+        /// capture that setSampleInGraph() chooses).  Needs setDrawRing() and setTokenRing()'s sequence counter.  ensureGraph() re-captures when temperature, top_k or
+        /// top_p differ from what was captured.  sp.temperature must be > 0.
+        void setGraphSampling( const std::optional<SamplingParams>& sp )
+        {
+            if ( sp && !( sp->temperature > 0.0f ) ) throw std::invalid_argument( "GemmaTransformer::setGraphSampling: temperature must be > 0 (greedy: setSampleInGraph)" );
+            graph_sampling_ = sp;
+        }
+        /// the uniform draws of the captured stochastic step: `size` floats of host-visible memory (device address); sample number n (the sequence counter's value after
+        /// it) reads slot n % size, which the host fills before it launches the replay that consumes it
+        void setDrawRing( const float* draws, int size )
+        {
+            if ( draws && size <= 0 ) throw std::invalid_argument( "GemmaTransformer::setDrawRing: a ring needs a positive size" );
+            draw_ring_ = draws; draw_ring_size_ = draws ? size : 0;
+        }
         void setDevicePosition( dim_t position )
         {
             checkPosition( position, 1 );
@@ -313,9 +347,6 @@ namespace Mila::Dnn
                                                                sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
         }
 
-        /// SamplingParams (Components/Transformers/SamplingParams.ixx): temperature <= 0 is greedy; top_k 0 / top_p >= 1 disable
-        /// the truncations.  The uniform r in [0, 1) is drawn by the caller, as in the reference (host RNG, GemmaModel.ixx:568).
-        struct SamplingParams { float temperature = 1.0f; int top_k = 0; float top_p = 1.0f; };
         /// token <- a draw from softmax(softcap(logits) / temperature) restricted by top-k / top-p; the Gemma final logit
         /// softcap (cfg.final_logit_softcapping) is applied here, at the sampler (Gemma.ixx:30-32)
         void sampleStochastic( TokenTensor& token_out, const SamplingParams& sp, float r )
@@ -326,6 +357,15 @@ namespace Mila::Dnn
             void* scratch = ctx_->getScratch( need );
             Compute::rocmCheck( mila_cdna4_sample_stochastic_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature,
                                                                    sp.top_k, sp.top_p, r, scratch, need, ctx_->getStream() ) );
+        }
+
+        /// sampleStochastic through the radix pipeline (fewer launches, a model-owned workspace): the eager form of what a stochastic captured step ends with
+        void sampleStochasticRadix( TokenTensor& token_out, const SamplingParams& sp, float r )
+        {
+            if ( sp.temperature <= 0.0f ) { sampleGreedy( token_out ); return; }
+            Compute::TraceRange tr( "gemma.sample(stochastic, radix)" );
+            Compute::rocmCheck( mila_cdna4_sample_radix_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r,
+                                                              radix_scratch_->data(), radix_scratch_->sizeInBytes(), ctx_->getStream() ) );
         }
 
         // ------------------------------------------------------------------------------------
@@ -534,6 +574,8 @@ namespace Mila::Dnn
             sample_scratch_ = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( mila_cdna4_sample_scratch_bytes() / 4 ) } );
             // split-attention partials of the fused / graph decode step: model-owned and never re-allocated (see captureGraph)
             attn_partials_ = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( ( attnScratchBytes() + 3 ) / 4 ) } );
+            // the radix sampler's workspace: model-owned for the same reason (a captured stochastic step's nodes point into it)
+            radix_scratch_ = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( ( mila_cdna4_sample_radix_scratch_bytes( (int)cfg_.vocab_size ) + 3 ) / 4 ) } );
             ctx_->synchronize();
         }
 
@@ -1218,7 +1260,7 @@ namespace Mila::Dnn
                                     ws_k_normed_, ws_v_normed_, ws_qkv_, ws_o_, ws_gate_up_, ws_down_ } ) b += tensorBytes( t );
             for ( const auto* t : { hidden_[ 0 ].get(), hidden_[ 1 ].get(), hidden_[ 2 ].get(), pf_x_[ 0 ].get(), pf_x_[ 1 ].get(), pf_norm_.get(), pf_norm2_.get(), pf_q8_[ 0 ].get(),
                                     pf_q8_[ 1 ].get(), f_qkv_.get(), f_q_.get(), f_o_.get(), f_down_.get(), f_act_.get(), ov_qkv_.get(), ov_o_.get(), ov_gate_up_.get() } ) b += tensorBytes( t );
-            for ( const auto* t : { logits_.get(), sample_scratch_.get(), attn_partials_.get(), pf_ts_[ 0 ].get(), pf_ts_[ 1 ].get() } ) b += tensorBytes( t );
+            for ( const auto* t : { logits_.get(), sample_scratch_.get(), attn_partials_.get(), radix_scratch_.get(), pf_ts_[ 0 ].get(), pf_ts_[ 1 ].get() } ) b += tensorBytes( t );
             b += tensorBytes( pos_dev_.get() );
             return b;
         }
@@ -1236,6 +1278,7 @@ namespace Mila::Dnn
             size_t b = e * 2;
             if ( ov_qkv_ ) b += P * ( maxpacked + D + 2 * F ) * 2;                                           // the two-stream prefill's buffers, once that path has run
             b += static_cast<size_t>( cfg_.vocab_size ) * 4 + ( ( mila_cdna4_sample_scratch_bytes() / 4 ) * 4 ) + ( ( attnScratchBytes() + 3 ) / 4 ) * 4;
+            b += ( ( mila_cdna4_sample_radix_scratch_bytes( (int)cfg_.vocab_size ) + 3 ) / 4 ) * 4;      // the radix sampler's workspace
             if ( kFmt != 0 ) b += 2 * P * 4;
             b += 4;                                                                                          // the device position word
             return b;
@@ -1272,7 +1315,7 @@ namespace Mila::Dnn
         std::unique_ptr<TensorType> ov_qkv_, ov_o_, ov_gate_up_;
         hipStream_t ov_stream_{ nullptr };
         hipEvent_t ov_ev_[ 8 ]{};
-        std::unique_ptr<LogitsTensor> attn_partials_;
+        std::unique_ptr<LogitsTensor> attn_partials_, radix_scratch_;
         std::unique_ptr<TensorType> pf_norm_, pf_norm2_;
         // W4A8 policy: the sandwich tails also write their normalised rows as per-token e4m3 + scales for the Linear that follows ([0]: pre_ffn_norm -> fc_gate_up,
         // [1]: the next block's input_norm -> its qkv_proj); model-owned like every prefill workspace
@@ -1290,5 +1333,14 @@ namespace Mila::Dnn
         unsigned long long* token_seq_{ nullptr };
         const unsigned long long* captured_ring_{ nullptr };
         int token_ring_size_{ 0 };
+        std::optional<SamplingParams> graph_sampling_, captured_sampling_;      // the stochastic tail asked for / captured (nullopt: none)
+        const float* draw_ring_{ nullptr };
+        const float* captured_draw_ring_{ nullptr };
+        int draw_ring_size_{ 0 };
+        static bool sameSampling( const std::optional<SamplingParams>& a, const std::optional<SamplingParams>& b ) noexcept
+        {
+            if ( a.has_value() != b.has_value() ) return false;
+            return !a || ( a->temperature == b->temperature && a->top_k == b->top_k && a->top_p == b->top_p );
+        }
     };
 }

@@ -5,7 +5,8 @@
 //   Models/QuantizationDispatch.ixx:34-95; Core/LanguageModelConfig.ixx:88-230; Core/GenerateStatus.ixx; Components/Transformers/{GenerateParams,SamplingParams}.ixx.
 // MI355X form of the decode-ahead pipeline: a greedy request runs the captured hipGraph whose last node is the device sampler (the next
 // token never leaves the device) and publishes it into a host-visible ring (sequence number << 32 | token, one system-scope store); the host
-// polls its slot while the next step is already running: no event, no copy, no stream wait on the decode path.  A stochastic request enqueues fused step + sampler per token (the uniform draw is a host scalar).
+// polls its slot while the next step is already running: no event, no copy, no stream wait on the decode path.  A stochastic request runs the same loop: its captured
+// step ends with the radix sampler (mila_cdna4_sample_radix_advance_fp32), whose uniform draw the host writes into a second host-visible ring before each replay.
 #pragma once
 
 #include <atomic>
@@ -116,6 +117,7 @@ namespace Mila::Dnn
         ~GemmaModel()
         {
             if ( ring_host_ ) (void)hipHostFree( ring_host_ );
+            if ( draws_host_ ) (void)hipHostFree( draws_host_ );
         }
 
         /// every architectural parameter comes from the artifact's metadata; `model_config` carries the deployment decisions
@@ -224,6 +226,11 @@ namespace Mila::Dnn
             void* dptr = nullptr;
             hipCheck( hipHostGetDevicePointer( &dptr, ring_host_, 0 ), "hipHostGetDevicePointer" );
             ring_dev_ = static_cast<unsigned long long*>( dptr );
+            // the uniform draws of the captured stochastic step, the other way round: the host writes slot n % kSnapshots before it launches the replay that takes sample n
+            hipCheck( hipHostMalloc( reinterpret_cast<void**>( &draws_host_ ), kSnapshots * sizeof( float ), hipHostMallocMapped | hipHostMallocCoherent ), "hipHostMalloc (mapped, coherent draw ring)" );
+            std::memset( draws_host_, 0, kSnapshots * sizeof( float ) );
+            hipCheck( hipHostGetDevicePointer( &dptr, draws_host_, 0 ), "hipHostGetDevicePointer" );
+            draws_dev_ = static_cast<const float*>( dptr );
             ctx->synchronize();
         }
 
@@ -239,7 +246,7 @@ namespace Mila::Dnn
             else
             {
                 typename TNet::SamplingParams p; p.temperature = sp.temperature; p.top_k = sp.top_k; p.top_p = sp.top_p;
-                net.sampleStochastic( *decode_token_device_, p, std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng_ ) );
+                net.sampleStochasticRadix( *decode_token_device_, p, std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng_ ) );
             }
             Compute::rocmCheck( mila_cdna4_snapshot_token( decode_token_device_->data(), seqCounter(), ring_dev_, static_cast<int>( kSnapshots ), net.context()->getStream() ) );
             ++published_;
@@ -305,15 +312,25 @@ namespace Mila::Dnn
             const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
             if ( position < contextLength() )
             {
-                // greedy: the captured step ends with the sampler and the publish; stochastic: the captured step ends at the logits and the sampler (its uniform
-                // draw is a host scalar) follows eagerly.  Switching between the two kinds of request re-captures (a few ms, once per switch)
+                // greedy: the captured step ends with the argmax sampler and the publish; stochastic: it ends with the radix sampler, whose last node takes its draw from
+                // the draw ring and publishes the same way.  Another kind of request, or other sampling parameters, re-capture (a few ms, once per change)
                 net.setSampleInGraph( greedy );
                 net.setTokenRing( ring_dev_, static_cast<int>( kSnapshots ), seqCounter() );
+                if ( greedy ) net.setGraphSampling( std::nullopt );
+                else
+                {
+                    typename TNet::SamplingParams p; p.temperature = params.sampling.temperature; p.top_k = params.sampling.top_k; p.top_p = params.sampling.top_p;
+                    net.setGraphSampling( p );
+                    net.setDrawRing( draws_dev_, static_cast<int>( kSnapshots ) );
+                }
                 net.ensureGraph( *decode_token_device_, position );
                 net.setDevicePosition( position );
             }
+            std::mt19937_64 rng_before_ahead = rng_;
             while ( true )
             {
+                // (a cancel seen here needs no draw put back: the replay of the previous iteration drew for the sample the eager loop drew at that iteration's end --
+                // one draw per sample enqueued, on both loops)
                 if ( stop && stop->load( std::memory_order_relaxed ) ) { ctx->synchronize(); return GenerateStatus::ClientCancelled; }
                 // decode ahead only when another step could consume its logits: within the token budget and with KV-cache room
                 const bool more_steps_allowed = emitted + 1 < max_new;
@@ -323,16 +340,35 @@ namespace Mila::Dnn
                 if ( ahead )
                 {
                     net.ensureGraph( *decode_token_device_, position );      // (re-captures only when the position leaves the captured live-length bucket)
+                    if ( !greedy )
+                    {
+                        // the replay samples the NEXT token before this one is known: one draw per sample, in the order of the eager loop this replaces, and taken
+                        // back below when this token ends the request (that loop would not have drawn it: a request leaves the generator where it always did)
+                        rng_before_ahead = rng_;
+                        const float r = std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng_ );
+                        uint32_t bits;
+                        std::memcpy( &bits, &r, 4 );
+                        __atomic_store_n( reinterpret_cast<uint32_t*>( draws_host_ ) + ( ( published_ + 1 ) % kSnapshots ), bits, __ATOMIC_RELEASE );
+                    }
                     net.replayGraph();
-                    if ( greedy ) ++published_;      // the captured step ends with sampler + publish: the NEXT token
+                    ++published_;      // the captured step ends with sampler + publish: the NEXT token
                 }
                 const int32_t token = awaitSampledToken( mine );
                 if ( ahead ) { kv_token_history_.push_back( token ); ++position; }     // the ahead-decode entered it into the caches, whatever it is
-                if ( stop_ids.contains( token ) ) { ctx->synchronize(); return GenerateStatus::Success; }
-                on_token( token );
+                if ( stop_ids.contains( token ) )
+                {
+                    if ( ahead && !greedy ) rng_ = rng_before_ahead;
+                    ctx->synchronize();
+                    return GenerateStatus::Success;
+                }
+                try { on_token( token ); }
+                catch ( ... )
+                {
+                    if ( ahead && !greedy ) rng_ = rng_before_ahead;      // the eager loop drew only after on_token returned
+                    throw;
+                }
                 ++emitted;
                 if ( !ahead ) return more_steps_allowed ? GenerateStatus::ContextOverflow : GenerateStatus::MaxNewTokensReached;
-                if ( !greedy ) enqueueSampleNext( net, params.sampling );
             }
         }
 
@@ -347,6 +383,8 @@ namespace Mila::Dnn
         std::mt19937_64 rng_{ 0x4d494c41ull };
         unsigned long long* ring_host_{ nullptr };      // pinned + mapped: the device writes, the host polls
         unsigned long long* ring_dev_{ nullptr };       // the same memory through its device address
+        float* draws_host_{ nullptr };                  // pinned + mapped: the host writes a draw, the captured stochastic step's last node reads it
+        const float* draws_dev_{ nullptr };
         uint64_t published_{ 0 };                       // samples enqueued so far (their sequence numbers are 1 .. published_)
     };
 }

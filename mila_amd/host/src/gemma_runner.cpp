@@ -27,6 +27,20 @@ namespace
                      std::unique_ptr<GemmaTransformer<PerGroupFp4<128>>>> model;
         std::unique_ptr<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>> tokens;
         dim_t max_prefill{ 1 };
+        // generate_sampled's graph mode: the draw ring the captured stochastic step reads, the token ring it publishes into, and the device sequence counter --
+        // allocated at the first such call and kept, so that a later call with the same sampling parameters finds its capture still valid
+        static constexpr int kRing = 8;
+        float* draws_host{ nullptr };
+        unsigned long long* ring_host{ nullptr };
+        const float* draws_dev{ nullptr };
+        unsigned long long* ring_dev{ nullptr };
+        std::unique_ptr<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>> seq_dev;      // one 64-bit counter
+        uint64_t samples{ 0 };                                                                       // its value
+        ~Runner()
+        {
+            if ( draws_host ) (void)hipHostFree( draws_host );
+            if ( ring_host ) (void)hipHostFree( ring_host );
+        }
     };
 
     template<typename F> int guarded( F&& f )
@@ -499,15 +513,19 @@ HOST_API int mila_gemma_generate( void* h, int32_t first_token, int64_t start_po
     } );
 }
 
-/// Stochastic generation: like mila_gemma_generate (mode 0 or 1) with the multinomial device sampler; the per-step uniform
-/// comes from a host mt19937( seed ) as in the reference's generate loop.  temperature <= 0 degenerates to greedy.
-HOST_API int mila_gemma_generate_sampled( void* h, int32_t first_token, int64_t start_position, int n_tokens, int mode, float temperature, int top_k,
+/// Stochastic generation: like mila_gemma_generate with the multinomial device sampler; the per-step uniform comes from a host mt19937( seed ) as in the
+/// reference's generate loop.  pipeline 0: sample_stochastic_* (the 16-ary search), eager, modes 0 and 1; pipeline 1: the radix pipeline -- eager behind the step in
+/// modes 0 and 1, as the tail of the captured step in mode 2 (the draw travels through a host-visible ring, the token comes back through another).
+/// temperature <= 0 degenerates to greedy in modes 0 and 1.
+HOST_API int mila_gemma_generate_sampled( void* h, int32_t first_token, int64_t start_position, int n_tokens, int mode, int pipeline, float temperature, int top_k,
                                           float top_p, uint32_t seed, int32_t* host_out )
 {
     auto* r = static_cast<Runner*>( h );
     return guarded( [&]
     {
-        if ( mode != 0 && mode != 1 ) throw std::invalid_argument( "generate_sampled: mode must be 0 (reference order) or 1 (fused)" );
+        if ( pipeline != 0 && pipeline != 1 ) throw std::invalid_argument( "generate_sampled: pipeline must be 0 (16-ary search) or 1 (radix)" );
+        if ( mode != 0 && mode != 1 && !( mode == 2 && pipeline == 1 ) )
+            throw std::invalid_argument( "generate_sampled: mode must be 0 (reference order) or 1 (fused), or 2 (graph) with the radix pipeline" );
         upload_tokens( r, &first_token, 1 );
         std::mt19937 rng( seed );
         std::uniform_real_distribution<float> uni( 0.0f, 1.0f );
@@ -516,13 +534,58 @@ HOST_API int mila_gemma_generate_sampled( void* h, int32_t first_token, int64_t 
             auto* ctx = m->context();
             typename std::remove_reference_t<decltype( *m )>::SamplingParams sp;
             sp.temperature = temperature; sp.top_k = top_k; sp.top_p = top_p;
+            if ( mode != 2 )
+            {
+                for ( int i = 0; i < n_tokens; ++i )
+                {
+                    const int64_t pos = start_position + i;
+                    if ( mode == 0 ) m->decode( *r->tokens, pos ); else m->decodeFused( *r->tokens, pos );
+                    if ( pipeline == 1 ) m->sampleStochasticRadix( *r->tokens, sp, uni( rng ) ); else m->sampleStochastic( *r->tokens, sp, uni( rng ) );
+                    Compute::rocmCheck( mila_cdna4_memcpy_d2h( host_out + i, r->tokens->data(), 4, ctx->getStream() ) );
+                    ctx->synchronize();
+                }
+                return;
+            }
+            if ( !r->seq_dev )
+            {
+                hipCheck( hipHostMalloc( reinterpret_cast<void**>( &r->draws_host ), Runner::kRing * sizeof( float ), hipHostMallocMapped | hipHostMallocCoherent ), "hipHostMalloc (draw ring)" );
+                hipCheck( hipHostMalloc( reinterpret_cast<void**>( &r->ring_host ), Runner::kRing * sizeof( unsigned long long ), hipHostMallocMapped | hipHostMallocCoherent ), "hipHostMalloc (token ring)" );
+                std::memset( r->draws_host, 0, Runner::kRing * sizeof( float ) );
+                std::memset( r->ring_host, 0, Runner::kRing * sizeof( unsigned long long ) );
+                void* d = nullptr;
+                hipCheck( hipHostGetDevicePointer( &d, r->draws_host, 0 ), "hipHostGetDevicePointer" );
+                r->draws_dev = static_cast<const float*>( d );
+                hipCheck( hipHostGetDevicePointer( &d, r->ring_host, 0 ), "hipHostGetDevicePointer" );
+                r->ring_dev = static_cast<unsigned long long*>( d );
+                r->seq_dev = std::make_unique<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>>( ctx->getDeviceId(), shape_t{ 2 } );
+                Compute::rocmCheck( mila_cdna4_memset_zero( r->seq_dev->rawData(), 8, ctx->getStream() ) );
+                ctx->synchronize();
+            }
+            // the settings are this call's: whatever happens, a later greedy or sampler-less capture must not inherit them (the capture itself stays valid)
+            struct Reset { decltype( m )& net; ~Reset() { net->setGraphSampling( std::nullopt ); net->setDrawRing( nullptr, 0 ); net->setTokenRing( nullptr, 0, nullptr ); } } reset{ m };
+            m->setSampleInGraph( false );
+            m->setTokenRing( r->ring_dev, Runner::kRing, reinterpret_cast<unsigned long long*>( r->seq_dev->rawData() ) );
+            m->setDrawRing( r->draws_dev, Runner::kRing );
+            m->setGraphSampling( sp );
+            m->ensureGraph( *r->tokens, start_position );
+            m->setDevicePosition( start_position );
+            // the device counter is the truth: an earlier call that threw between a replay and its bookkeeping must not leave this one reading the wrong slots
+            Compute::rocmCheck( mila_cdna4_memcpy_d2h( &r->samples, r->seq_dev->rawData(), 8, ctx->getStream() ) );
+            ctx->synchronize();
             for ( int i = 0; i < n_tokens; ++i )
             {
-                const int64_t pos = start_position + i;
-                if ( mode == 0 ) m->decode( *r->tokens, pos ); else m->decodeFused( *r->tokens, pos );
-                m->sampleStochastic( *r->tokens, sp, uni( rng ) );
-                Compute::rocmCheck( mila_cdna4_memcpy_d2h( host_out + i, r->tokens->data(), 4, ctx->getStream() ) );
+                m->ensureGraph( *r->tokens, start_position + i );
+                const uint64_t seq = r->samples + 1;
+                const float u = uni( rng );
+                uint32_t bits;
+                std::memcpy( &bits, &u, 4 );
+                __atomic_store_n( reinterpret_cast<uint32_t*>( r->draws_host ) + ( seq % Runner::kRing ), bits, __ATOMIC_RELEASE );
+                m->replayGraph();
+                r->samples = seq;
                 ctx->synchronize();
+                const unsigned long long v = __atomic_load_n( r->ring_host + ( seq % Runner::kRing ), __ATOMIC_ACQUIRE );
+                if ( ( v >> 32 ) != ( seq & 0xffffffffull ) ) throw std::runtime_error( "generate_sampled: the captured step did not publish its token" );
+                host_out[ i ] = static_cast<int32_t>( static_cast<uint32_t>( v ) );
             }
         }, r->model );
     } );
