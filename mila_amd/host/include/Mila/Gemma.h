@@ -381,15 +381,20 @@ namespace Mila::Dnn
             const dim_t D = cfg_.embedding_dim;
             embed( tokens.data(), static_cast<int>( T ), *pf_x_[ 0 ] );
             TensorType* x = pf_x_[ 0 ].get();
-            int flip = 0;
             const bool fused = fused_prefill_ && fusedPrefillApplicable();
             if ( fused && prefill_overlap_ && overlapApplicable( T ) ) return prefillOverlapped( tokens, T, position_offset );
+            int flip = 0;
+            bool q8_normed = false;
             for ( size_t i = 0; i < layers_.size(); ++i )
             {
-                if ( !fused ) { x = &layers_[ i ].prefill( x->view( shape_t{ 1, T, D } ), position_offset ); continue; }   // GemmaBlock::prefill, one component per step
-                TensorType* out = pf_x_[ 1 - flip ].get();
-                blockPrefillFused( layers_[ i ], *x, i > 0, *out, i + 1 < layers_.size() ? &layers_[ i + 1 ] : nullptr, static_cast<int>( T ), static_cast<int>( position_offset ) );
-                x = out;
+                Layer& L = layers_[ i ];
+                if ( !fused ) { x = &L.prefill( x->view( shape_t{ 1, T, D } ), position_offset ); continue; }   // GemmaBlock::prefill, one component per step
+                // one call over rows [0, T), the Linears writing their components' pooled outputs; the first block's input norm is its component's forward, every later
+                // one was written into pf_norm_ by the tail before it
+                BlockRows r{ 0, static_cast<int>( T ), x, pf_x_[ 1 - flip ].get(), i ? pf_norm_.get() : &L.input_norm->forward( x->view( shape_t{ 1, T, D } ) ),
+                             ws_qkv_.get(), ws_o_.get(), ws_gate_up_.get(), ws_down_.get(), q8_normed };
+                q8_normed = blockPrefillFused( L, i + 1 < layers_.size() ? &layers_[ i + 1 ] : nullptr, r, static_cast<int>( position_offset ) );
+                x = r.out;
                 flip = 1 - flip;
             }
             auto last = x->slice( static_cast<size_t>( ( T - 1 ) * D ), shape_t{ 1, 1, D } );
@@ -451,11 +456,9 @@ namespace Mila::Dnn
         RmsNormType& finalNorm() { return *final_norm_; }
         TokenEmbeddingType& tokenEmbedding() { return *temb_; }
 
-        /// launch only the dominant kernel (fc_gate_up fused matvec) of layer `i` -- used by the bench to
-        /// time that kernel with HIP events on the model stream
-        void launchGateUp( size_t i ) { fusedGateUp( layers_[ i ] ); }
         double gateUpBytes( size_t i ) const { return static_cast<double>( layers_[ i ].fc_gate_up->getParameterBytes() ); }
-        /// the dominant decode kernel of the schedule: the fc_gate_up fused matvec of layer i
+        /// launch only the dominant decode kernel of the schedule, the fc_gate_up fused matvec of layer i -- used by the bench to time that kernel with HIP events on
+        /// the model stream
         void launchDominant( size_t i )
         {
             if ( !cur_hidden_ ) cur_hidden_ = hidden_[ 0 ]->data();   // no fused step has run yet (reference-order timing)
@@ -602,161 +605,87 @@ namespace Mila::Dnn
         }
 
         // ---- fused-glue prefill (the reference-order path is GemmaBlock::prefill) -----------------------
-        /// act[T, F] = GeGLU(fc_gate_up(ffn_in)): one kernel when the fused GEMM serves the shape, else Linear + GeGLU
-        /// `x8` / `ts` (W4A8 policy): ffn_in's rows already quantized per token by the tail that produced them -- the quantization launch is then skipped
-        void gateUpGeglu( Layer& L, TensorType& ffn_in, TensorType& act, int T, TensorType* private_gate_up = nullptr, const uint8_t* x8_in = nullptr, const float* ts_in = nullptr )
+        /// What one call of blockPrefillFused() works on: rows [row0, row0 + rows) of the chunk.  The one-stream prefill passes the whole chunk and the components'
+        /// pooled outputs; the two-stream form passes each half, buffers of its own, and the event that orders the halves' attention.
+        struct BlockRows
         {
-            const dim_t D = cfg_.embedding_dim;
-            mila_stream_t st = ctx_->getStream();
-            bool w4a8 = false;
-            if constexpr ( kFmt == 2 )
-                w4a8 = L.fc_gate_up->getOperation().fp8ActivationPrefill() && mila_cdna4_gemm_fp8_applicable( T, (int)D, 2 * (int)cfg_.hidden_dim );
-            if constexpr ( kFmt == 1 )
-            {
-                // W8A8 (opt-in): the policy's e4m3 [2F, D] weights and per-channel scales straight into the fused fp8 x fp8 Linear + GeGLU kernel
-                auto& op = L.fc_gate_up->getOperation();
-                if ( op.fp8ActivationPrefill() && mila_cdna4_gemm_fp8_applicable( T, (int)D, 2 * (int)cfg_.hidden_dim ) )
-                {
-                    w4a8 = true;      // (below: never the bf16 fused form)
-                    if ( mila_cdna4_gemm_geglu_w4a8_applicable( T, (int)D, (int)cfg_.hidden_dim ) )
-                    {
-                        const auto* W8 = static_cast<const uint8_t*>( L.fc_gate_up->getWeight().rawData() );
-                        const float* sc = L.fc_gate_up->getWeightScale()->data();
-                        if ( x8_in && ts_in )
-                        {
-                            Compute::rocmCheck( mila_cdna4_gemm_geglu_fp8_w8a8( act.data(), x8_in, W8, ts_in, sc, T, (int)D, (int)cfg_.hidden_dim, st ) );
-                            return;
-                        }
-                        uint8_t* x8; float* ts;
-                        op.activationScratch( T, (int)D, x8, ts );
-                        Compute::rocmCheck( mila_cdna4_quantize_fp8_per_token( x8, ts, ffn_in.data(), T, (int)D, st ) );
-                        Compute::rocmCheck( mila_cdna4_gemm_geglu_fp8_w8a8( act.data(), x8, W8, ts, sc, T, (int)D, (int)cfg_.hidden_dim, st ) );
-                        return;
-                    }
-                }
-            }
-            if constexpr ( kFmt == 2 )
-            {
-                if ( w4a8 && mila_cdna4_gemm_geglu_w4a8_applicable( T, (int)D, (int)cfg_.hidden_dim ) && L.fc_gate_up->getOperation().weightFp8Scale() &&
-                     L.fc_gate_up->getOperation().residentE4m3() )
-                {
-                    // resident e4m3 weights (staged once at load): only the activations are quantized per forward
-                    auto& op = L.fc_gate_up->getOperation();
-                    if ( x8_in && ts_in )
-                    {
-                        Compute::rocmCheck( mila_cdna4_gemm_geglu_fp8_scaled( act.data(), x8_in, op.residentE4m3(), ts_in, op.weightFp8Scale(), T, (int)D, (int)cfg_.hidden_dim, st ) );
-                        return;
-                    }
-                    uint8_t* x8; float* ts;
-                    op.activationScratch( T, (int)D, x8, ts );
-                    Compute::rocmCheck( mila_cdna4_quantize_fp8_per_token( x8, ts, ffn_in.data(), T, (int)D, st ) );
-                    Compute::rocmCheck( mila_cdna4_gemm_geglu_fp8_scaled( act.data(), x8, op.residentE4m3(), ts, op.weightFp8Scale(), T, (int)D, (int)cfg_.hidden_dim, st ) );
-                    return;
-                }
-                if ( w4a8 && mila_cdna4_gemm_geglu_w4a8_applicable( T, (int)D, (int)cfg_.hidden_dim ) && L.fc_gate_up->getOperation().weightFp8Scale() )
-                {
-                    const int F = (int)cfg_.hidden_dim;
-                    const size_t need = mila_cdna4_gemm_w4a8_scratch_bytes( T, (int)D, 2 * F );
-                    void* scratch = ctx_->getScratch( need );
-                    Compute::rocmCheck( mila_cdna4_gemm_geglu_bf16_w4a8( act.data(), ffn_in.data(), static_cast<const uint8_t*>( L.fc_gate_up->getWeight().rawData() ),
-                                                                         L.fc_gate_up->getWeightScale()->data(), L.fc_gate_up->getOperation().weightFp8Scale(), T, (int)D, F,
-                                                                         Quant::Weight::groupSizeOf<TWeightQuant>(), scratch, need, st ) );
-                    return;
-                }
-            }
-            if ( !w4a8 && mila_cdna4_gemm_geglu_preferred( T, (int)D, (int)cfg_.hidden_dim ) )      // (this caller holds the split-K workspace)
-            {
-                // Linear + GeGLU in one kernel: the [T, 2F] gate|up intermediate never reaches memory (bit-identical to the pair)
-                const int F = (int)cfg_.hidden_dim;
-                const void* W = L.fc_gate_up->getWeight().rawData();
-                if constexpr ( kFmt == 0 )
-                    Compute::rocmCheck( mila_cdna4_gemm_geglu_bf16( act.data(), ffn_in.data(), static_cast<const uint16_t*>( W ), T, (int)D, F, st ) );
-                else if ( kFmt == 1 && L.fc_gate_up->getOperation().residentBf16() )
-                    Compute::rocmCheck( mila_cdna4_gemm_geglu_bf16( act.data(), ffn_in.data(), L.fc_gate_up->getOperation().residentBf16(), T, (int)D, F, st ) );
-                else
-                {
-                    const size_t need = (size_t)2 * F * D * 2;
-                    void* scratch = ctx_->getScratch( need );
-                    if constexpr ( kFmt == 1 )
-                        Compute::rocmCheck( mila_cdna4_gemm_geglu_bf16_w8a16_staged( act.data(), ffn_in.data(), static_cast<const uint8_t*>( W ), L.fc_gate_up->getWeightScale()->data(),
-                                                                                     T, (int)D, F, scratch, need, st ) );
-                    else
-                        Compute::rocmCheck( mila_cdna4_gemm_geglu_bf16_w4a16_staged( act.data(), ffn_in.data(), static_cast<const uint8_t*>( W ), L.fc_gate_up->getWeightScale()->data(),
-                                                                                     T, (int)D, F, Quant::Weight::groupSizeOf<TWeightQuant>(), scratch, need, st ) );
-                }
-            }
-            else
-            {
-                // the unfused pair; a caller running two calls at once (halfBlock) hands each its own [T, 2F] rows instead of the component's output
-                if ( private_gate_up ) L.fc_gate_up->getOperation().forward( ffn_in, *private_gate_up );
-                auto& gate_up = private_gate_up ? *private_gate_up : L.fc_gate_up->forward( ffn_in );
-                Compute::rocmCheck( mila_cdna4_geglu_bf16( act.data(), gate_up.data(), T, (int)cfg_.hidden_dim, st ) );
-            }
-        }
+            int row0, rows;
+            TensorType *x, *out;                      ///< the block's input and output rows (the two pf_x_ buffers, alternating)
+            TensorType* normed;                       ///< input_norm( x )
+            TensorType *qkv, *o, *gate_up, *ffn;      ///< where qkv_proj, o_proj, fc_gate_up (when it runs unfused) and fc_down write
+            bool q8_normed = false;                   ///< the tail before this block left `normed`'s rows in pf_q8_[ 1 ] / pf_ts_[ 1 ] as well, quantized per token
+            hipEvent_t kv_record = nullptr;           ///< recorded once this call's K / V rows are in the cache ...
+            hipEvent_t kv_wait = nullptr;             ///< ... and what its attention waits for: the K / V rows of the chunk's earlier rows, written on another stream
+        };
 
-        /// GemmaBlock::forward with the glue fused (bit-identical to GemmaBlock::prefill): the packed qkv rows go straight through
-        /// q/k/v norm + RoPE into q and the KV cache (no split3 / kv_write), and each sandwich tail (RmsNorm + Residual
-        /// (+ layer scalar) + the next RmsNorm) is one launch.  `have_normed`: the previous block's tail already wrote
-        /// input_norm(input) into pf_norm_; `nextL`: the block whose input_norm the second tail applies.
-        void blockPrefillFused( Layer& L, TensorType& input, bool have_normed, TensorType& output, Layer* nextL, int T, int position_offset )
+        /// GemmaBlock::forward with the glue fused (bit-identical to GemmaBlock::prefill): the packed qkv rows go straight through q/k/v norm + RoPE into q and the
+        /// KV cache (no split3 / kv_write), and each sandwich tail (RmsNorm + Residual (+ layer scalar) + the next RmsNorm) is one launch.  `nextL`: the block whose
+        /// input_norm the second tail applies, into pf_norm_.  Returns whether that tail wrote those rows quantized per token as well: the next call's q8_normed.
+        bool blockPrefillFused( Layer& L, Layer* nextL, const BlockRows& r, int position_offset )
         {
             const bool g = L.global;
-            const dim_t NH = cfg_.num_heads, NKV = cfg_.numKvHeads( g ), HD = cfg_.headDim( g ), D = cfg_.embedding_dim;
+            const dim_t NH = cfg_.num_heads, NKV = cfg_.numKvHeads( g ), HD = cfg_.headDim( g ), D = cfg_.embedding_dim, F = cfg_.hidden_dim;
+            const int T = r.rows, position = position_offset + r.row0;
             mila_stream_t st = ctx_->getStream();
-            auto x3 = input.view( shape_t{ 1, T, D } );
-            auto normed_view = pf_norm_->view( shape_t{ 1, T, D } );
-            TensorType* normed = &normed_view;
-            if ( !have_normed ) { normed = &L.input_norm->forward( x3 ); pf_q8_normed_ = false; }
-            // W4A8 policy: the previous block's second tail wrote these rows quantized as well -- the Linear's own quantization launch is skipped (same bits)
-            bool q8_in = false;
-            if constexpr ( kFmt != 0 ) q8_in = have_normed && pf_q8_normed_ && L.qkv_proj->getOperation().acceptsFp8Activations( T );
-            auto& qkv = q8_in ? L.qkv_proj->forwardFp8Activations( static_cast<const uint8_t*>( pf_q8_[ 1 ]->rawData() ), pf_ts_[ 1 ]->data(), normed->shape() )
-                              : L.qkv_proj->forward( *normed );
-            auto q = q_->view( shape_t{ 1, T, NH * HD } );
-            const uint16_t* qp = static_cast<const uint16_t*>( qkv.rawData() );
+            // a call's region of a buffer starts at its first row in the buffer's OWN (widest) row pitch: the first half of a chunk may run a layer of the other kind
+            // (wider q / qkv rows) ahead of the second half, and the regions of the two must not meet whatever the widths
+            auto rows = [&]( TensorType& t, dim_t width ) { return t.slice( static_cast<size_t>( r.row0 ) * static_cast<size_t>( t.shape().back() ), shape_t{ 1, T, width } ); };
+            auto x3 = rows( *r.x, D ), out = rows( *r.out, D ), normed = rows( *r.normed, D ), next_normed = rows( *pf_norm_, D );
+            // per-token e4m3 rows + scales a tail hands to the Linear behind it: [ 0 ] pre_ffn_norm's for fc_gate_up, [ 1 ] the next block's input_norm's for its qkv_proj
+            uint8_t* q8[ 2 ] = { nullptr, nullptr };
+            float* ts8[ 2 ] = { nullptr, nullptr };
+            if constexpr ( kFmt != 0 )
+                for ( int i = 0; i < 2; ++i )
+                {
+                    q8[ i ] = static_cast<uint8_t*>( pf_q8_[ i ]->rawData() ) + static_cast<size_t>( r.row0 ) * static_cast<size_t>( D );
+                    ts8[ i ] = pf_ts_[ i ]->data() + r.row0;
+                }
+            auto qkv = rows( *r.qkv, cfg_.packedQkvWidth( g ) );
+            // the tail before this block wrote `normed` quantized as well -- the Linear's own quantization launch is skipped (same bits)
+            if ( r.q8_normed ) L.qkv_proj->getOperation().forwardFp8Activations( q8[ 1 ], ts8[ 1 ], qkv.data(), T );
+            else L.qkv_proj->getOperation().forward( normed, qkv );
+            auto q = rows( *q_, NH * HD );
+            const uint16_t* qp = qkv.data();
             const uint16_t* kp = qp + (size_t)( NH * HD );
             const uint16_t* vp = g ? kp : kp + (size_t)( NKV * HD );
             if ( L.kvFp8() )      // the same launch with the quantizing append; prefillFromCache() is then the policy's attention-only prefill (band dequant + the bf16 flash kernels)
                 Compute::rocmCheck( mila_cdna4_fused_qkv_post_kvfp8_prefill( q.data(), L.keyCacheFp8(), L.valueCacheFp8(), L.keyScales(), L.valueScales(), qp, kp, vp,
                                                                              (int64_t)cfg_.packedQkvWidth( g ), L.q_norm->getWeight()->data(), L.k_norm->getWeight()->data(),
                                                                              L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(), T, (int)NH, (int)NKV, (int)HD,
-                                                                             position_offset, (int)L.cacheCapacity(), cfg_.rms_norm_eps, st ) );
+                                                                             position, (int)L.cacheCapacity(), cfg_.rms_norm_eps, st ) );
             else
                 Compute::rocmCheck( mila_cdna4_fused_qkv_post_prefill( q.data(), L.keyCache(), L.valueCache(), qp, kp, vp, (int64_t)cfg_.packedQkvWidth( g ),
                                                                        L.q_norm->getWeight()->data(), L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(),
-                                                                       L.rope->cosCache(), L.rope->sinCache(), T, (int)NH, (int)NKV, (int)HD, position_offset,
+                                                                       L.rope->cosCache(), L.rope->sinCache(), T, (int)NH, (int)NKV, (int)HD, position,
                                                                        (int)L.cacheCapacity(), cfg_.rms_norm_eps, st ) );
-            auto attn = attn_out_->view( shape_t{ 1, T, NH * HD } );
-            L.prefillFromCache( q, attn, T, position_offset );
-            auto& o = L.o_proj->forward( attn );
-            auto res1 = res1_->view( shape_t{ 1, T, D } );
-            auto ffn_in = pf_norm2_->view( shape_t{ 1, T, D } );
+            if ( r.kv_record ) hipCheck( hipEventRecord( r.kv_record, reinterpret_cast<hipStream_t>( st ) ), "hipEventRecord" );
+            if ( r.kv_wait ) hipCheck( hipStreamWaitEvent( reinterpret_cast<hipStream_t>( st ), r.kv_wait, 0 ), "hipStreamWaitEvent" );
+            auto attn = rows( *attn_out_, NH * HD );
+            L.prefillFromCache( q, attn, T, position );
+            auto o = rows( *r.o, D );
+            L.o_proj->getOperation().forward( attn, o );
+            auto res1 = rows( *res1_, D ), ffn_in = rows( *pf_norm2_, D );
             // W4A8 / W8A8: a tail whose normalised rows feed a Linear on the fp8 x fp8 path writes them quantized per token as well (fused_tail_norm_quant)
-            bool q8_ffn = false, q8_next = false;
-            if constexpr ( kFmt != 0 )
-            {
-                auto& gu = L.fc_gate_up->getOperation();
-                q8_ffn = gu.acceptsFp8Activations( T ) && mila_cdna4_gemm_geglu_w4a8_applicable( T, (int)D, (int)cfg_.hidden_dim ) != 0;
-                q8_next = nextL && nextL->qkv_proj->getOperation().acceptsFp8Activations( T );
-            }
+            auto& gate_up_op = L.fc_gate_up->getOperation();
+            const bool q8_ffn = gate_up_op.gegluWantsFp8Rows( T ), q8_next = nextL && nextL->qkv_proj->getOperation().acceptsFp8Activations( T );
             if ( q8_ffn )
-                Compute::rocmCheck( mila_cdna4_fused_tail_norm_quant_bf16( res1.data(), ffn_in.data(), static_cast<uint8_t*>( pf_q8_[ 0 ]->rawData() ), pf_ts_[ 0 ]->data(), o.data(), x3.data(),
-                                                                           L.post_attn_norm->getWeight()->data(), L.pre_ffn_norm->getWeight()->data(), T, (int)D, 1.0f, cfg_.rms_norm_eps, st ) );
+                Compute::rocmCheck( mila_cdna4_fused_tail_norm_quant_bf16( res1.data(), ffn_in.data(), q8[ 0 ], ts8[ 0 ], o.data(), x3.data(), L.post_attn_norm->getWeight()->data(),
+                                                                           L.pre_ffn_norm->getWeight()->data(), T, (int)D, 1.0f, cfg_.rms_norm_eps, st ) );
             else
                 Compute::rocmCheck( mila_cdna4_fused_tail_norm_bf16( res1.data(), ffn_in.data(), o.data(), x3.data(), L.post_attn_norm->getWeight()->data(),
                                                                      L.pre_ffn_norm->getWeight()->data(), T, (int)D, 1.0f, cfg_.rms_norm_eps, st ) );
-            auto act = geglu_->view( shape_t{ 1, T, cfg_.hidden_dim } );
-            if ( q8_ffn ) gateUpGeglu( L, ffn_in, act, T, nullptr, static_cast<const uint8_t*>( pf_q8_[ 0 ]->rawData() ), pf_ts_[ 0 ]->data() );
-            else gateUpGeglu( L, ffn_in, act, T );
-            auto& ffn = L.fc_down->forward( act );
+            auto act = rows( *geglu_, F );
+            auto gate_up = rows( *r.gate_up, 2 * F );         // only written where no fused Linear + GeGLU serves this [T, D, F]
+            gate_up_op.forwardGeglu( ffn_in, act, gate_up, q8_ffn ? q8[ 0 ] : nullptr, q8_ffn ? ts8[ 0 ] : nullptr );
+            auto ffn = rows( *r.ffn, D );
+            L.fc_down->getOperation().forward( act, ffn );
             if ( q8_next )
-                Compute::rocmCheck( mila_cdna4_fused_tail_norm_quant_bf16( output.data(), pf_norm_->data(), static_cast<uint8_t*>( pf_q8_[ 1 ]->rawData() ), pf_ts_[ 1 ]->data(), ffn.data(), res1.data(),
-                                                                           L.post_ffn_norm->getWeight()->data(), nextL->input_norm->getWeight()->data(), T, (int)D, L.layer_scalar,
-                                                                           cfg_.rms_norm_eps, st ) );
+                Compute::rocmCheck( mila_cdna4_fused_tail_norm_quant_bf16( out.data(), next_normed.data(), q8[ 1 ], ts8[ 1 ], ffn.data(), res1.data(), L.post_ffn_norm->getWeight()->data(),
+                                                                           nextL->input_norm->getWeight()->data(), T, (int)D, L.layer_scalar, cfg_.rms_norm_eps, st ) );
             else
-                Compute::rocmCheck( mila_cdna4_fused_tail_norm_bf16( output.data(), nextL ? pf_norm_->data() : nullptr, ffn.data(), res1.data(), L.post_ffn_norm->getWeight()->data(),
+                Compute::rocmCheck( mila_cdna4_fused_tail_norm_bf16( out.data(), nextL ? next_normed.data() : nullptr, ffn.data(), res1.data(), L.post_ffn_norm->getWeight()->data(),
                                                                      nextL ? nextL->input_norm->getWeight()->data() : nullptr, T, (int)D, L.layer_scalar, cfg_.rms_norm_eps, st ) );
-            pf_q8_normed_ = q8_next;
+            return q8_next;
         }
 
         // ---- two halves of a chunk on two streams -------------------------------------------------------------------------------------------
@@ -764,63 +693,20 @@ namespace Mila::Dnn
         // but for attention, so the chunk's two halves run as two kernel sequences on two streams -- each on its own rows of every buffer -- and the second
         // half's attention of a layer waits (an event) for the first half's K / V rows of that layer.  The idle CUs of one stream's tails take the other
         // stream's workgroups.  Same kernels on the same rows: bit-identical to the one-stream form.
+        // Not where any Linear of the chunk takes something from the context scratch -- staging, per-token activation rows (the fp8 x fp8 paths), a split-K workspace
+        // (short tile lists: the same idle CUs this form is after): the two halves' calls would share it.  A split also depends on the row count, so the whole chunk's
+        // row count is asked beside the half's: the halves carry the whole chunk's bits.  An op that stages per forward counts as taking scratch whatever these two
+        // row counts need (usesContextScratch), so the form serves unquantized weights and the fp8 policy's resident bf16 copies, and never the fp4 policy, W8A8 or
+        // per-forward staging.  (The FP8 KV cache dequantizes its band into the same scratch: setPrefillOverlap() refuses it.)
         bool overlapApplicable( dim_t T ) const
         {
-            if constexpr ( kFmt == 2 ) return false;       // the W4A8 path quantizes activations into per-op scratch sized for one call at a time
-            if constexpr ( kFmt == 1 ) { for ( auto& L : layers_ ) if ( L.fc_down->getOperation().fp8ActivationPrefill() || !L.fc_down->getOperation().residentBf16() ) return false; }
             if ( !( T >= 1024 && T % 512 == 0 ) ) return false;
-            // ... and so does a GEMM that splits K through the context's workspace (short tile lists: the same idle CUs this form is after); the split also depends on
-            // the row count, so the halves would not carry the whole chunk's bits
             for ( auto& L : layers_ )
-            {
-                const Compute::LinearOpConfig* cfgs[ 4 ] = { &L.qkv_proj->getOperation().config(), &L.o_proj->getOperation().config(), &L.fc_gate_up->getOperation().config(),
-                                                             &L.fc_down->getOperation().config() };
-                for ( const auto* c : cfgs )
-                    for ( dim_t rows : { T, T / 2 } )
-                        if ( mila_cdna4_gemm_workspace_bytes( static_cast<int>( rows ), static_cast<int>( c->in_features ), static_cast<int>( c->out_features ) ) != 0 ) return false;
-            }
+                for ( int rows : { static_cast<int>( T ), static_cast<int>( T / 2 ) } )
+                    if ( L.qkv_proj->getOperation().usesContextScratch( rows ) || L.o_proj->getOperation().usesContextScratch( rows ) ||
+                         L.fc_gate_up->getOperation().gegluUsesContextScratch( rows ) || L.fc_down->getOperation().usesContextScratch( rows ) )
+                        return false;
             return true;
-        }
-        void halfBlock( Layer& L, int h, bool first_layer, Layer* nextL, int H, int position_offset, int flip, hipEvent_t kv_ready, bool wait_kv )
-        {
-            const bool g = L.global;
-            const dim_t NH = cfg_.num_heads, NKV = cfg_.numKvHeads( g ), HD = cfg_.headDim( g ), D = cfg_.embedding_dim, F = cfg_.hidden_dim;
-            const size_t r0 = static_cast<size_t>( h ) * static_cast<size_t>( H );
-            mila_stream_t st = ctx_->getStream();
-            // a half's region of a buffer starts at its first row in the buffer's OWN (widest) row pitch: the first half may run a layer of the other kind
-            // (wider q / qkv rows) ahead of the second half, and the regions of the two must not meet whatever the widths
-            auto rows = [&]( TensorType& t, dim_t width ) { return t.slice( r0 * static_cast<size_t>( t.shape().back() ), shape_t{ 1, H, width } ); };
-            auto x3 = rows( *pf_x_[ flip ], D );
-            auto out = rows( *pf_x_[ 1 - flip ], D );
-            auto normed = rows( *pf_norm_, D );
-            (void)first_layer;
-            auto qkv = rows( *ov_qkv_, cfg_.packedQkvWidth( g ) );
-            L.qkv_proj->getOperation().forward( normed, qkv );
-            auto q = rows( *q_, NH * HD );
-            const uint16_t* qp = qkv.data();
-            const uint16_t* kp = qp + (size_t)( NH * HD );
-            const uint16_t* vp = g ? kp : kp + (size_t)( NKV * HD );
-            Compute::rocmCheck( mila_cdna4_fused_qkv_post_prefill( q.data(), L.keyCache(), L.valueCache(), qp, kp, vp, (int64_t)cfg_.packedQkvWidth( g ),
-                                                                   L.q_norm->getWeight()->data(), L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(),
-                                                                   L.rope->cosCache(), L.rope->sinCache(), H, (int)NH, (int)NKV, (int)HD, position_offset + h * H,
-                                                                   (int)L.cacheCapacity(), cfg_.rms_norm_eps, st ) );
-            if ( h == 0 ) hipCheck( hipEventRecord( kv_ready, reinterpret_cast<hipStream_t>( st ) ), "hipEventRecord" );
-            else if ( wait_kv ) hipCheck( hipStreamWaitEvent( reinterpret_cast<hipStream_t>( st ), kv_ready, 0 ), "hipStreamWaitEvent" );
-            auto attn = rows( *attn_out_, NH * HD );
-            L.prefillFromCache( q, attn, H, position_offset + h * H );
-            auto o = rows( *ov_o_, D );
-            L.o_proj->getOperation().forward( attn, o );
-            auto res1 = rows( *res1_, D );
-            auto ffn_in = rows( *pf_norm2_, D );
-            Compute::rocmCheck( mila_cdna4_fused_tail_norm_bf16( res1.data(), ffn_in.data(), o.data(), x3.data(), L.post_attn_norm->getWeight()->data(),
-                                                                 L.pre_ffn_norm->getWeight()->data(), H, (int)D, 1.0f, cfg_.rms_norm_eps, st ) );
-            auto act = rows( *geglu_, F );
-            auto gate_up = rows( *ov_gate_up_, 2 * F );        // only written when the fused Linear + GeGLU does not serve this [H, D, F]
-            gateUpGeglu( L, ffn_in, act, H, &gate_up );
-            auto ffn = rows( *ov_o_, D );                      // o is dead after the first tail
-            L.fc_down->getOperation().forward( act, ffn );
-            Compute::rocmCheck( mila_cdna4_fused_tail_norm_bf16( out.data(), nextL ? normed.data() : nullptr, ffn.data(), res1.data(), L.post_ffn_norm->getWeight()->data(),
-                                                                 nextL ? nextL->input_norm->getWeight()->data() : nullptr, H, (int)D, L.layer_scalar, cfg_.rms_norm_eps, st ) );
         }
         LogitsTensor& prefillOverlapped( const TokenTensor& tokens, dim_t T, dim_t position_offset )
         {
@@ -850,10 +736,13 @@ namespace Mila::Dnn
             {
                 Layer* nextL = i + 1 < layers_.size() ? &layers_[ i + 1 ] : nullptr;
                 hipEvent_t kv = ov_ev_[ 1 + ( i % 6 ) ];
-                halfBlock( layers_[ i ], 0, i == 0, nextL, H, static_cast<int>( position_offset ), flip, kv, false );
+                // each half's Linears write the two-stream form's own buffers (o is dead after the first tail: fc_down's rows go there too)
+                BlockRows r{ 0, H, pf_x_[ flip ].get(), pf_x_[ 1 - flip ].get(), pf_norm_.get(), ov_qkv_.get(), ov_o_.get(), ov_gate_up_.get(), ov_o_.get(), false, kv, nullptr };
+                blockPrefillFused( layers_[ i ], nextL, r, static_cast<int>( position_offset ) );
                 {
                     struct Scope { Compute::RocmExecutionContext* c; mila_stream_t old; ~Scope() { c->swapStream( old ); } } scope{ ctx_, ctx_->swapStream( reinterpret_cast<mila_stream_t>( ov_stream_ ) ) };
-                    halfBlock( layers_[ i ], 1, i == 0, nextL, H, static_cast<int>( position_offset ), flip, kv, true );
+                    r.row0 = H; r.kv_record = nullptr; r.kv_wait = kv;
+                    blockPrefillFused( layers_[ i ], nextL, r, static_cast<int>( position_offset ) );
                 }
                 flip = 1 - flip;
             }
@@ -866,7 +755,7 @@ namespace Mila::Dnn
         }
 
     public:
-        /// two half-chunks on two streams (see halfBlock): off by default until measured per deployment; same bits either way
+        /// two half-chunks on two streams (see prefillOverlapped): off by default until measured per deployment; same bits either way
         void setPrefillOverlap( bool on )
         {
             if ( on && cfg_.kv_fp8 )
@@ -902,17 +791,6 @@ namespace Mila::Dnn
             a.post_scale = 1.0f; a.eps = cfg_.rms_norm_eps; a.fmt = kFmt; a.K = (int)lin.getConfig().getInputFeatures();
             a.N = (int)lin.getConfig().getOutputFeatures(); a.group = Quant::Weight::groupSizeOf<TWeightQuant>(); a.geglu = 0;
             return a;
-        }
-        void plainMatvec( LinearType& lin, uint16_t* y, const uint16_t* x )
-        {
-            auto in = TensorType();   // route through the op so the launch is the same C-ABI call as Linear::forward
-            (void)in;
-            const int K = (int)lin.getConfig().getInputFeatures(), N = (int)lin.getConfig().getOutputFeatures();
-            mila_stream_t st = ctx_->getStream();
-            if constexpr ( kFmt == 0 ) Compute::rocmCheck( mila_cdna4_matvec_bf16( y, x, static_cast<const uint16_t*>( lin.getWeight().rawData() ), nullptr, K, N, st ) );
-            else if constexpr ( kFmt == 1 ) Compute::rocmCheck( mila_cdna4_matvec_bf16_qfp8( y, x, static_cast<const uint8_t*>( lin.getWeight().rawData() ), lin.getWeightScale()->data(), nullptr, K, N, st ) );
-            else Compute::rocmCheck( mila_cdna4_matvec_bf16_qfp4( y, x, static_cast<const uint8_t*>( lin.getWeight().rawData() ), lin.getWeightScale()->data(), nullptr, K, N,
-                                                                  Quant::Weight::groupSizeOf<TWeightQuant>(), st ) );
         }
         void fusedGateUp( Layer& L )
         {
@@ -980,11 +858,11 @@ namespace Mila::Dnn
                                                                            scratch, need, NH, NKV, HD, (int)L.cacheCapacity(), position, pos_dev,
                                                                            (int)cfg_.windowFor( g ), L.attentionScale(), cfg_.rms_norm_eps, st ) );
                 // 4. o_proj
-                plainMatvec( *L.o_proj, f_o_->data(), attn_out_->data() );
+                L.o_proj->getOperation().matvec( f_o_->data(), attn_out_->data() );      // (the C-ABI call of Linear::forward on one row; these Linears carry no bias)
                 // 5. post_attn_norm + residual + pre_ffn_norm + gate_up + GeGLU
                 fusedGateUp( L );
                 // 6. fc_down
-                plainMatvec( *L.fc_down, f_down_->data(), f_act_->data() );
+                L.fc_down->getOperation().matvec( f_down_->data(), f_act_->data() );
                 prev = &L;
             }
             // tail of the last layer + final norm + lm_head (fp32 logits) in one launch
@@ -1321,7 +1199,6 @@ namespace Mila::Dnn
         // [1]: the next block's input_norm -> its qkv_proj); model-owned like every prefill workspace
         std::unique_ptr<TensorType> pf_q8_[ 2 ];          // [1, P, D / 2] bf16 elements = P * D bytes of e4m3
         std::unique_ptr<LogitsTensor> pf_ts_[ 2 ];        // [P] fp32 per-token scales
-        bool pf_q8_normed_{ false };       // pf_q8_[1] / pf_ts_[1] hold the rows of pf_norm_ (written by the previous block's second tail in this prefill)
         const uint16_t* cur_hidden_{ nullptr };
         hipGraph_t graph_{ nullptr };
         hipGraphExec_t graph_exec_{ nullptr };

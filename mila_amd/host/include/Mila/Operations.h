@@ -7,7 +7,9 @@
 // std::make_shared<OpType>(IExecutionContext*, const Config&); they cache RAW pointers handed over by
 // setParameters()/setWeightScales() and never own parameters; build() validates shapes and throws;
 // forward() only enqueues work on the context's stream; scratch is fetched from the context on every
-// forward.  Every forward() ends in exactly one C-ABI call (include/mila_cdna4.h).
+// forward.  A forward() is the C-ABI calls (include/mila_cdna4.h) of ONE route through its op, chosen in one place per op -- for a Linear of more than
+// one row RocmLinearOp::route() / gegluRoute() -- and fails where no kernel serves the call: usually a single call; two where the route feeds the fp8
+// matrix cores from bf16 rows (the per-token quantization launch, then the GEMM) or is the unfused Linear + GeGLU pair.
 #pragma once
 
 #include <chrono>
@@ -79,6 +81,20 @@ namespace Mila::Dnn::Compute
     };
     inline ActivationTap*& activationTap() { static ActivationTap* tap = nullptr; return tap; }
 
+    /// What serves a Linear call of more than one row.  RocmLinearOp::route() is the only place that decides it: forward(), acceptsFp8Activations(),
+    /// forwardFp8Activations() and usesContextScratch() read the answer.
+    enum class PrefillRoute
+    {
+        Bf16,            ///< the bf16 GEMM on the op's own weights, the context scratch as its split-K workspace (unquantized weights)
+        ResidentBf16,    ///< the same GEMM on the bf16 copy staged at load (fp8 policy)
+        Staged,          ///< the _staged entry: dequantize into scratch, then the bf16 GEMM; a scratch need of 0 is the in-register dequantizing kernel
+        Fp8Rows,         ///< fp8 x fp8 on per-token e4m3 rows: W8A8 on the policy's own weights (fp8 policy), W4A8 on the resident e4m3 copy (fp4 policy)
+        W4a8OneCall,     ///< gemm_bf16_w4a8: the weights and the rows staged into scratch inside the one call (fp4 policy without the resident copy)
+    };
+    /// ... and what serves Linear + GeGLU (RocmLinearOp::gegluRoute(), read by forwardGeglu(), gegluWantsFp8Rows() and gegluUsesContextScratch()): one fused kernel
+    /// on the weights the matching PrefillRoute reads, or the pair forward() + geglu_bf16
+    enum class GegluRoute { FusedBf16, FusedResidentBf16, FusedStaged, FusedFp8Rows, FusedW4a8OneCall, Pair };
+
     /// counterpart of CudaLinearOp<Prec, TWeightQuant> (OPS/Linear/CudaLinearOp.ixx:107-1287)
     template<TensorDataType TPrecision, Quant::Weight::WeightQuantPolicy TWeightQuant>
     class RocmLinearOp : public Operation<DeviceType::Rocm, TPrecision>
@@ -125,7 +141,42 @@ namespace Mila::Dnn::Compute
             built_ = true;
         }
 
-        /// M == 1 -> decode matvec; M > 1 -> MFMA GEMM (CudaLinearOp.ixx:535-827)
+        /// The one decision of a call of M > 1 rows.
+        /// fp8 policy: W8A8 when opted in (setFp8ActivationPrefill) -- "FP8 matmul consumes weights and scales natively" (Quantization/Weight/Policies.ixx:39-40) --, else
+        /// the resident bf16 copy where the staged call would dequantize (the LDS-DMA GEMM applies), else the staged entry.
+        /// fp4 policy: W4A8, the reference's default prefill for it (kUseFp8ActivationPrefillPath, CudaLinearOp.ixx:646-715), on the resident e4m3 copy or staged inside
+        /// the one call; it needs the per-tensor weight scale, else the staged W4A16 entry.
+        PrefillRoute route( int M ) const
+        {
+            if constexpr ( kFmt == 0 ) return PrefillRoute::Bf16;
+            if ( fp8Serves( M ) && ( kFmt == 1 || weight_fp8_scale_ ) ) return ( kFmt == 1 || resident_e4m3_ ) ? PrefillRoute::Fp8Rows : PrefillRoute::W4a8OneCall;
+            if ( resident_bf16_ && mila_cdna4_gemm_staging_bytes( M, (int)cfg_.in_features, (int)cfg_.out_features ) != 0 ) return PrefillRoute::ResidentBf16;
+            return PrefillRoute::Staged;
+        }
+        /// bytes of context scratch forward() of M > 1 rows takes on route r: staging, per-token activation rows, a split-K workspace
+        size_t scratchBytes( PrefillRoute r, int M ) const
+        {
+            const int K = (int)cfg_.in_features, N = (int)cfg_.out_features;
+            switch ( r )
+            {
+            case PrefillRoute::Staged: return mila_cdna4_gemm_staging_bytes( M, K, N );
+            case PrefillRoute::Fp8Rows: return activationBytes( M, K ) + mila_cdna4_gemm_fp8_workspace_bytes( M, K, N );
+            case PrefillRoute::W4a8OneCall: return mila_cdna4_gemm_w4a8_scratch_bytes( M, K, N );
+            default: return mila_cdna4_gemm_workspace_bytes( M, K, N );
+            }
+        }
+        /// true when forward() of M rows takes anything from the context scratch (one call at a time may: two calls on two streams would share it).  The staged entry
+        /// of an op without a resident copy counts whatever the shape: it dequantizes into scratch wherever the plan streams bf16 weights, and only a plan of 128-tile
+        /// kernels alone needs no bytes -- a caller that asks for some row counts must not conclude from those that the op never stages.  (With the resident copy the
+        /// route is Staged only where that need is 0.)
+        bool usesContextScratch( int M ) const
+        {
+            if ( M <= 1 ) return false;
+            const PrefillRoute r = route( M );
+            return ( r == PrefillRoute::Staged && !resident_bf16_ ) || scratchBytes( r, M ) != 0;
+        }
+
+        /// M == 1 -> decode matvec; M > 1 -> the GEMM of route( M ) (CudaLinearOp.ixx:535-827)
         void forward( const TensorType& in, TensorType& out ) const
         {
             if ( !built_ ) throw std::runtime_error( "RocmLinearOp::forward: not built" );
@@ -146,68 +197,51 @@ namespace Mila::Dnn::Compute
             }
             auto* y = static_cast<uint16_t*>( out.rawData() );
             auto* x = static_cast<const uint16_t*>( in.rawData() );
-            if ( M == 1 )
+            if ( M == 1 ) { matvec( y, x ); return; }
+            const auto* w8 = static_cast<const uint8_t*>( weight_ );
+            const PrefillRoute r = route( M );
+            switch ( r )
             {
-                if constexpr ( kFmt == 0 ) rocmCheck( mila_cdna4_matvec_bf16( y, x, static_cast<const uint16_t*>( weight_ ), bias_, K, N, st ) );
-                else if constexpr ( kFmt == 1 ) rocmCheck( mila_cdna4_matvec_bf16_qfp8( y, x, static_cast<const uint8_t*>( weight_ ), scales_, bias_, K, N, st ) );
-                else rocmCheck( mila_cdna4_matvec_bf16_qfp4( y, x, static_cast<const uint8_t*>( weight_ ), scales_, bias_, K, N, kGroup, st ) );
-            }
-            else
+            case PrefillRoute::Bf16: gemmWithWorkspace( y, x, static_cast<const uint16_t*>( weight_ ), M, K, N, 0, st ); break;
+            // resident prefill weights: the staging pass was run once, at load (same values => same bits as the staged call)
+            case PrefillRoute::ResidentBf16: gemmWithWorkspace( y, x, resident_bf16_->data(), M, K, N, 0, st ); break;
+            case PrefillRoute::Staged:
             {
-                if constexpr ( kFmt == 0 ) gemmWithWorkspace( y, x, static_cast<const uint16_t*>( weight_ ), M, K, N, 0, st );
-                else
-                {
-                    if constexpr ( kFmt == 1 )
-                    {
-                        // W8A8 (opt-in, setFp8ActivationPrefill): the policy's own e4m3 weights + per-channel scales on the fp8 matrix cores, per-token e4m3 activations --
-                        // "FP8 matmul consumes weights and scales natively" (Quantization/Weight/Policies.ixx:39-40); no staging pass, no bf16 copy of the weights
-                        if ( use_fp8_activation_prefill_ && mila_cdna4_gemm_fp8_applicable( M, K, N ) )
-                        {
-                            uint8_t* x8; float* ts; void* ws;
-                            const size_t ws_bytes = mila_cdna4_gemm_fp8_workspace_bytes( M, K, N );
-                            activationScratch( M, K, x8, ts, ws_bytes, &ws );
-                            rocmCheck( mila_cdna4_quantize_fp8_per_token( x8, ts, x, M, K, st ) );
-                            recordTap( x8, ts, M, K, N );
-                            rocmCheck( mila_cdna4_gemm_fp8_w8a8_ws( y, x8, static_cast<const uint8_t*>( weight_ ), ts, scales_, bias_, M, K, N, ws, ws_bytes, st ) );
-                            return;
-                        }
-                        // resident prefill weights: the staging pass was run once, at load (same values => same bits as the staged call)
-                        if ( resident_bf16_ && mila_cdna4_gemm_staging_bytes( M, K, N ) != 0 )
-                        {
-                            gemmWithWorkspace( y, x, resident_bf16_->data(), M, K, N, 0, st );
-                            return;
-                        }
-                    }
-                    // 2-phase staging through context scratch when the LDS-DMA GEMM applies; scratch is fetched per
-                    // forward and never cached (reference rule, CudaLinearOp.ixx:603-614)
-                    if constexpr ( kFmt == 2 )
-                    {
-                        // W4A8: fp4 -> e4m3 weight staging + per-token e4m3 activations + fp8 x fp8 MFMA GEMM, the reference's default
-                        // prefill for this policy (kUseFp8ActivationPrefillPath, CudaLinearOp.ixx:646-715), when an fp8 kernel serves the shape
-                        if ( use_fp8_activation_prefill_ && weight_fp8_scale_ && resident_e4m3_ && mila_cdna4_gemm_fp8_applicable( M, K, N ) )
-                        {
-                            uint8_t* x8; float* ts; void* ws;
-                            const size_t ws_bytes = mila_cdna4_gemm_fp8_workspace_bytes( M, K, N );
-                            activationScratch( M, K, x8, ts, ws_bytes, &ws );
-                            rocmCheck( mila_cdna4_quantize_fp8_per_token( x8, ts, x, M, K, st ) );
-                            recordTap( x8, ts, M, K, N );
-                            rocmCheck( mila_cdna4_gemm_fp8_scaled_ws( y, x8, resident_e4m3_->data(), ts, weight_fp8_scale_->data(), bias_, M, K, N, ws, ws_bytes, st ) );
-                            return;
-                        }
-                        if ( use_fp8_activation_prefill_ && weight_fp8_scale_ && mila_cdna4_gemm_fp8_applicable( M, K, N ) )
-                        {
-                            const size_t need8 = mila_cdna4_gemm_w4a8_scratch_bytes( M, K, N );
-                            void* scratch8 = this->context_->getScratch( need8 );
-                            rocmCheck( mila_cdna4_gemm_bf16_w4a8( y, x, static_cast<const uint8_t*>( weight_ ), scales_, weight_fp8_scale_->data(), bias_, M, K, N, kGroup, scratch8, need8, st ) );
-                            return;
-                        }
-                    }
-                    const size_t need = mila_cdna4_gemm_staging_bytes( M, K, N );
-                    void* scratch = need ? this->context_->getScratch( need ) : nullptr;
-                    if constexpr ( kFmt == 1 ) rocmCheck( mila_cdna4_gemm_bf16_w8a16_staged( y, x, static_cast<const uint8_t*>( weight_ ), scales_, bias_, M, K, N, scratch, need, st ) );
-                    else rocmCheck( mila_cdna4_gemm_bf16_w4a16_staged( y, x, static_cast<const uint8_t*>( weight_ ), scales_, bias_, M, K, N, kGroup, scratch, need, st ) );
-                }
+                // 2-phase staging through context scratch when the LDS-DMA GEMM applies; scratch is fetched per forward and never cached (reference rule,
+                // CudaLinearOp.ixx:603-614)
+                const size_t need = scratchBytes( r, M );
+                void* scratch = need ? this->context_->getScratch( need ) : nullptr;
+                if constexpr ( kFmt == 1 ) rocmCheck( mila_cdna4_gemm_bf16_w8a16_staged( y, x, w8, scales_, bias_, M, K, N, scratch, need, st ) );
+                else rocmCheck( mila_cdna4_gemm_bf16_w4a16_staged( y, x, w8, scales_, bias_, M, K, N, kGroup, scratch, need, st ) );
+                break;
             }
+            case PrefillRoute::Fp8Rows:
+            {
+                // per-token e4m3 activations + the fp8 x fp8 MFMA GEMM: no staging pass, no bf16 copy of the weights
+                uint8_t* x8; float* ts; void* ws;
+                const size_t ws_bytes = mila_cdna4_gemm_fp8_workspace_bytes( M, K, N );
+                activationScratch( M, K, x8, ts, ws_bytes, &ws );
+                rocmCheck( mila_cdna4_quantize_fp8_per_token( x8, ts, x, M, K, st ) );
+                recordTap( x8, ts, M, K, N );
+                gemmFp8Rows( y, x8, ts, M, K, N, ws, ws_bytes, st );
+                break;
+            }
+            case PrefillRoute::W4a8OneCall:
+            {
+                const size_t need = scratchBytes( r, M );
+                rocmCheck( mila_cdna4_gemm_bf16_w4a8( y, x, w8, scales_, weight_fp8_scale_->data(), bias_, M, K, N, kGroup, this->context_->getScratch( need ), need, st ) );
+                break;
+            }
+            }
+        }
+        /// the decode matvec of this op's weights: y[N] = W x[K] (+ bias); forward()'s M == 1 branch, and the o_proj / fc_down launches of the fused decode step
+        void matvec( uint16_t* y, const uint16_t* x ) const
+        {
+            const int K = (int)cfg_.in_features, N = (int)cfg_.out_features;
+            mila_stream_t st = this->context_->getStream();
+            if constexpr ( kFmt == 0 ) rocmCheck( mila_cdna4_matvec_bf16( y, x, static_cast<const uint16_t*>( weight_ ), bias_, K, N, st ) );
+            else if constexpr ( kFmt == 1 ) rocmCheck( mila_cdna4_matvec_bf16_qfp8( y, x, static_cast<const uint8_t*>( weight_ ), scales_, bias_, K, N, st ) );
+            else rocmCheck( mila_cdna4_matvec_bf16_qfp4( y, x, static_cast<const uint8_t*>( weight_ ), scales_, bias_, K, N, kGroup, st ) );
         }
 
         /// true when forwardGelu() serves this op and row count: unquantized weights on the GEMM branch
@@ -227,6 +261,85 @@ namespace Mila::Dnn::Compute
             else if constexpr ( kFmt == 0 )
                 gemmWithWorkspace( static_cast<uint16_t*>( out.rawData() ), static_cast<const uint16_t*>( in.rawData() ), static_cast<const uint16_t*>( weight_ ), M, K, N, 1,
                                    this->context_->getStream() );
+        }
+
+        /// The one decision of Linear + GeGLU over M > 1 rows of a [2F, K] = [gate | up] weight.  Two things are not what the Linear's own route would suggest:
+        /// once the fp8 x fp8 path serves the shape no bf16 fused form is taken, even where the fp8 GeGLU kernel does not apply (the plain fp8 GEMM would split K) --
+        /// the pair runs, and forward() takes the fp8 path; and under the fp4 policy that holds without the per-tensor weight scale too, where forward() then stages W4A16.
+        GegluRoute gegluRoute( int M ) const
+        {
+            const int K = (int)cfg_.in_features, F = (int)cfg_.out_features / 2;
+            if ( kFmt != 0 && fp8Serves( M ) )
+            {
+                if ( !mila_cdna4_gemm_geglu_w4a8_applicable( M, K, F ) || !( kFmt == 1 || weight_fp8_scale_ ) ) return GegluRoute::Pair;
+                return ( kFmt == 1 || resident_e4m3_ ) ? GegluRoute::FusedFp8Rows : GegluRoute::FusedW4a8OneCall;
+            }
+            // the fused bf16 forms where they are also the faster choice for a caller that holds the split-K workspace, as forward() does
+            if ( !mila_cdna4_gemm_geglu_preferred( M, K, F ) ) return GegluRoute::Pair;
+            if constexpr ( kFmt == 0 ) return GegluRoute::FusedBf16;
+            return resident_bf16_ ? GegluRoute::FusedResidentBf16 : GegluRoute::FusedStaged;
+        }
+        /// true when forwardGeglu() of M rows wants them quantized per token by their producer (x8 / ts): the quantization launch is then skipped, same bits
+        bool gegluWantsFp8Rows( int M ) const { return gegluRoute( M ) == GegluRoute::FusedFp8Rows; }
+        /// usesContextScratch() for forwardGeglu() (the fp8 x fp8 form counted as quantizing its rows itself)
+        bool gegluUsesContextScratch( int M ) const
+        {
+            const GegluRoute r = gegluRoute( M );
+            return r == GegluRoute::Pair ? usesContextScratch( M ) : r != GegluRoute::FusedBf16 && r != GegluRoute::FusedResidentBf16;
+        }
+
+        /// act[M, F] = GeGLU( forward( in ) ) (the FFN's fc_gate_up -> geglu): one kernel where gegluRoute() names a fused form -- the [M, 2F] gate | up rows then never
+        /// reach memory --, else forward() into `gate_up` + geglu_bf16.  The bits of the pair either way.  x8 / ts: `in`'s rows as the producing kernel quantized them
+        /// (caller-owned, only where gegluWantsFp8Rows()).
+        void forwardGeglu( const TensorType& in, TensorType& act, TensorType& gate_up, const uint8_t* x8 = nullptr, const float* ts = nullptr ) const requires ( !kFp32 )
+        {
+            if ( !built_ ) throw std::runtime_error( "RocmLinearOp::forwardGeglu: not built" );
+            const int K = narrowToKernelIndex( cfg_.in_features, "in_features" ), F = narrowToKernelIndex( cfg_.out_features / 2, "half of out_features" );
+            const int M = narrowToKernelIndex( static_cast<dim_t>( in.size() ) / cfg_.in_features, "outer size" );
+            mila_stream_t st = this->context_->getStream();
+            auto* y = act.data();
+            const auto* x = in.data();
+            const auto* w8 = static_cast<const uint8_t*>( weight_ );
+            const GegluRoute r = gegluRoute( M );
+            if ( ( x8 || ts ) && ( r != GegluRoute::FusedFp8Rows || !x8 || !ts ) ) throw std::logic_error( "RocmLinearOp::forwardGeglu: quantized rows handed to a call that does not consume them" );
+            if ( bias_ && r != GegluRoute::Pair ) throw std::logic_error( "RocmLinearOp::forwardGeglu: the fused Linear + GeGLU kernels take no bias" );
+            if ( cfg_.out_features % 2 != 0 || act.size() < static_cast<size_t>( M ) * F || ( r == GegluRoute::Pair && gate_up.size() < static_cast<size_t>( M ) * 2 * F ) )
+                throw std::invalid_argument( "RocmLinearOp::forwardGeglu: act must hold [M, F] and gate_up [M, 2F] elements of an even out_features" );
+            switch ( r )
+            {
+            case GegluRoute::FusedBf16: rocmCheck( mila_cdna4_gemm_geglu_bf16( y, x, static_cast<const uint16_t*>( weight_ ), M, K, F, st ) ); break;
+            case GegluRoute::FusedResidentBf16: rocmCheck( mila_cdna4_gemm_geglu_bf16( y, x, resident_bf16_->data(), M, K, F, st ) ); break;
+            case GegluRoute::FusedStaged:
+            {
+                const size_t need = (size_t)2 * F * K * 2;
+                void* scratch = this->context_->getScratch( need );
+                if constexpr ( kFmt == 1 ) rocmCheck( mila_cdna4_gemm_geglu_bf16_w8a16_staged( y, x, w8, scales_, M, K, F, scratch, need, st ) );
+                else rocmCheck( mila_cdna4_gemm_geglu_bf16_w4a16_staged( y, x, w8, scales_, M, K, F, kGroup, scratch, need, st ) );
+                break;
+            }
+            case GegluRoute::FusedFp8Rows:
+                if ( !x8 )
+                {
+                    uint8_t* q; float* s;
+                    activationScratch( M, K, q, s );
+                    rocmCheck( mila_cdna4_quantize_fp8_per_token( q, s, x, M, K, st ) );
+                    x8 = q; ts = s;
+                }
+                // W8A8: the policy's e4m3 [2F, K] weights and per-channel scales; W4A8: the resident e4m3 copy and the per-tensor scale
+                if constexpr ( kFmt == 1 ) rocmCheck( mila_cdna4_gemm_geglu_fp8_w8a8( y, x8, w8, ts, scales_, M, K, F, st ) );
+                else rocmCheck( mila_cdna4_gemm_geglu_fp8_scaled( y, x8, resident_e4m3_->data(), ts, weight_fp8_scale_->data(), M, K, F, st ) );
+                break;
+            case GegluRoute::FusedW4a8OneCall:
+            {
+                const size_t need = mila_cdna4_gemm_w4a8_scratch_bytes( M, K, 2 * F );
+                rocmCheck( mila_cdna4_gemm_geglu_bf16_w4a8( y, x, w8, scales_, weight_fp8_scale_->data(), M, K, F, kGroup, this->context_->getScratch( need ), need, st ) );
+                break;
+            }
+            case GegluRoute::Pair:
+                forward( in, gate_up );
+                rocmCheck( mila_cdna4_geglu_bf16( y, gate_up.data(), M, F, st ) );
+                break;
+            }
         }
 
         /// the bf16 GEMM with the context's scratch as its workspace, as CudaLinearOp hands context_->getCublasLtWorkspace() to every plan (CudaLinearOp.ixx:637-638,
@@ -280,48 +393,18 @@ namespace Mila::Dnn::Compute
             else refreshResident();
         }
         bool residentPrefillWeights() const noexcept { return resident_; }
-        const uint16_t* residentBf16() const noexcept { return resident_bf16_ ? resident_bf16_->data() : nullptr; }
-        const uint8_t* residentE4m3() const noexcept { return resident_e4m3_ ? resident_e4m3_->data() : nullptr; }
-        /// true when forward() of M rows would take the resident W4A8 path (fp8 x fp8 GEMM on weights staged at load): a producer may then hand over its
-        /// output already quantized per token (forwardFp8Activations) instead of as bf16
-        bool acceptsFp8Activations( int M ) const
-        {
-            if constexpr ( kFmt == 0 ) return false;
-            else if constexpr ( kFmt == 1 ) return use_fp8_activation_prefill_ && mila_cdna4_gemm_fp8_applicable( M, (int)cfg_.in_features, (int)cfg_.out_features ) != 0;
-            else return use_fp8_activation_prefill_ && weight_fp8_scale_ && resident_e4m3_ && mila_cdna4_gemm_fp8_applicable( M, (int)cfg_.in_features, (int)cfg_.out_features ) != 0;
-        }
-        /// the W4A8 forward on activations the caller quantized (x8 [M, K] e4m3, ts [M] per-token scales -- exactly what quantize_fp8_per_token gives): the same
-        /// GEMM call forward() makes, so the output carries the same bits
+        /// true when forward() of M rows runs fp8 x fp8 on per-token e4m3 rows: a producer may then hand over its output already quantized per token
+        /// (forwardFp8Activations) instead of as bf16
+        bool acceptsFp8Activations( int M ) const { return route( M ) == PrefillRoute::Fp8Rows; }
+        /// forward() on activations the caller quantized (x8 [M, K] e4m3, ts [M] per-token scales -- exactly what quantize_fp8_per_token gives): the same GEMM call
+        /// forward() makes, so the output carries the same bits
         /// (x8 / ts are the caller's own buffers, NOT context scratch: the GEMM's split-K workspace is taken from there)
-        void forwardFp8Activations( const uint8_t* x8, const float* ts, uint16_t* y, int M )
+        void forwardFp8Activations( const uint8_t* x8, const float* ts, uint16_t* y, int M ) const
         {
             if ( !acceptsFp8Activations( M ) ) throw std::logic_error( "RocmLinearOp::forwardFp8Activations: the fp8 x fp8 path does not serve this call" );
             const int K = (int)cfg_.in_features, N = (int)cfg_.out_features;
             const size_t ws_bytes = mila_cdna4_gemm_fp8_workspace_bytes( M, K, N );
-            void* ws = ws_bytes ? this->context_->getScratch( ws_bytes ) : nullptr;
-            if constexpr ( kFmt == 1 )
-                rocmCheck( mila_cdna4_gemm_fp8_w8a8_ws( y, x8, static_cast<const uint8_t*>( weight_ ), ts, scales_, bias_, M, K, N, ws, ws_bytes, this->context_->getStream() ) );
-            else
-                rocmCheck( mila_cdna4_gemm_fp8_scaled_ws( y, x8, resident_e4m3_->data(), ts, weight_fp8_scale_->data(), bias_, M, K, N, ws, ws_bytes, this->context_->getStream() ) );
-        }
-        /// the test instrument above: copy this call's e4m3 activations and scales to the host when a tap is installed
-        void recordTap( const uint8_t* x8, const float* ts, int M, int K, int N ) const
-        {
-            ActivationTap* tap = activationTap();
-            if ( !tap ) return;
-            ActivationTap::Record r{ M, K, N, std::vector<uint8_t>( static_cast<size_t>( M ) * K ), std::vector<float>( static_cast<size_t>( M ) ) };
-            rocmCheck( mila_cdna4_memcpy_d2h( r.x8.data(), x8, r.x8.size(), this->context_->getStream() ) );
-            rocmCheck( mila_cdna4_memcpy_d2h( r.ts.data(), ts, r.ts.size() * 4, this->context_->getStream() ) );
-            this->context_->synchronize();
-            tap->records.push_back( std::move( r ) );
-        }
-        /// scratch for the per-token e4m3 activations + their scales (+ `extra` bytes behind them, 16-byte aligned: the GEMM's workspace) -- fetched per forward, never cached
-        void activationScratch( int M, int K, uint8_t*& x8, float*& ts, size_t extra = 0, void** extra_out = nullptr ) const
-        {
-            const size_t xb = ( (size_t)M * K + 15 ) & ~(size_t)15, tb = ( (size_t)M * 4 + 15 ) & ~(size_t)15;
-            auto* base = static_cast<uint8_t*>( this->context_->getScratch( xb + tb + extra ) );
-            x8 = base; ts = reinterpret_cast<float*>( base + xb );
-            if ( extra_out ) *extra_out = extra ? base + xb + tb : nullptr;
+            gemmFp8Rows( y, x8, ts, M, K, N, ws_bytes ? this->context_->getScratch( ws_bytes ) : nullptr, ws_bytes, this->context_->getStream() );
         }
         /// fp4 policy: W4A8 prefill (default on, as in the reference) or the dequantize -> bf16 GEMM fallback.
         /// fp8 policy: W8A8 prefill (default OFF: the reference's arithmetic for PerChannelFp8<> is W8A16, CudaLinearOp.ixx:597-644) -- the policy's e4m3 weights and
@@ -336,7 +419,6 @@ namespace Mila::Dnn::Compute
             }
         }
         bool fp8ActivationPrefill() const noexcept { return use_fp8_activation_prefill_; }
-        const float* weightFp8Scale() const noexcept { return weight_fp8_scale_ ? weight_fp8_scale_->data() : nullptr; }
 
         /// bytes of the op-owned resident staging (0 when off, when W8A8 is on, or for unquantized weights)
         size_t residentBytes() const noexcept { return ( resident_bf16_ ? resident_bf16_->size() * 2 : 0 ) + ( resident_e4m3_ ? resident_e4m3_->size() : 0 ); }
@@ -365,6 +447,37 @@ namespace Mila::Dnn::Compute
         std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> weight_fp8_scale_;
         std::unique_ptr<RocmBf16Tensor> resident_bf16_;      // (quantized policies exist for BF16 activations only)
         std::unique_ptr<Tensor<TensorDataType::FP8_E4M3, RocmDeviceMemoryResource>> resident_e4m3_;
+
+        /// the fp8 x fp8 prefill is switched on and an fp8 MFMA kernel serves M rows of this [N, K] weight
+        bool fp8Serves( int M ) const { return use_fp8_activation_prefill_ && mila_cdna4_gemm_fp8_applicable( M, (int)cfg_.in_features, (int)cfg_.out_features ) != 0; }
+        /// the fp8 x fp8 GEMM of the Fp8Rows route on per-token e4m3 rows -- forward()'s own or the caller's: W8A8 on the policy's e4m3 weights and per-channel scales
+        /// (fp8 policy), the per-tensor-scaled form on the resident e4m3 copy (fp4 policy)
+        void gemmFp8Rows( uint16_t* y, const uint8_t* x8, const float* ts, int M, int K, int N, void* ws, size_t ws_bytes, mila_stream_t st ) const
+        {
+            if constexpr ( kFmt == 1 ) rocmCheck( mila_cdna4_gemm_fp8_w8a8_ws( y, x8, static_cast<const uint8_t*>( weight_ ), ts, scales_, bias_, M, K, N, ws, ws_bytes, st ) );
+            else rocmCheck( mila_cdna4_gemm_fp8_scaled_ws( y, x8, resident_e4m3_->data(), ts, weight_fp8_scale_->data(), bias_, M, K, N, ws, ws_bytes, st ) );
+        }
+        /// the test instrument above: copy this call's e4m3 activations and scales to the host when a tap is installed
+        void recordTap( const uint8_t* x8, const float* ts, int M, int K, int N ) const
+        {
+            ActivationTap* tap = activationTap();
+            if ( !tap ) return;
+            ActivationTap::Record r{ M, K, N, std::vector<uint8_t>( static_cast<size_t>( M ) * K ), std::vector<float>( static_cast<size_t>( M ) ) };
+            rocmCheck( mila_cdna4_memcpy_d2h( r.x8.data(), x8, r.x8.size(), this->context_->getStream() ) );
+            rocmCheck( mila_cdna4_memcpy_d2h( r.ts.data(), ts, r.ts.size() * 4, this->context_->getStream() ) );
+            this->context_->synchronize();
+            tap->records.push_back( std::move( r ) );
+        }
+        /// bytes of the per-token e4m3 activations [M, K] + their scales [M], each rounded up to 16
+        static size_t activationBytes( int M, int K ) { return ( ( (size_t)M * K + 15 ) & ~(size_t)15 ) + ( ( (size_t)M * 4 + 15 ) & ~(size_t)15 ); }
+        /// scratch for them (+ `extra` bytes behind them, 16-byte aligned: the GEMM's workspace) -- fetched per forward, never cached
+        void activationScratch( int M, int K, uint8_t*& x8, float*& ts, size_t extra = 0, void** extra_out = nullptr ) const
+        {
+            const size_t xb = ( (size_t)M * K + 15 ) & ~(size_t)15, all = activationBytes( M, K );
+            auto* base = static_cast<uint8_t*>( this->context_->getScratch( all + extra ) );
+            x8 = base; ts = reinterpret_cast<float*>( base + xb );
+            if ( extra_out ) *extra_out = extra ? base + all : nullptr;
+        }
 
         void refreshResident()
         {

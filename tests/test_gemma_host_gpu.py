@@ -5,6 +5,9 @@
     path vs decode matvec path; the reference's cross-path bar is 1e-1 * absmax, Linear.Cuda.cpp:760-774);
   * logits agree with the oracle composition (tests/ref_gemma.py) on a small Gemma-shaped config with
     one global layer, for all three weight policies."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -649,3 +652,52 @@ def test_w8a8_opt_in_prefill_of_the_fp8_policy(cfg_name, T):
         err = float(np.abs(got.astype(np.float64) - exp.astype(np.float64)).max() / np.abs(exp).max())
         print("W8A8 prefill T=%d on the conditioned %s model vs the oracle composition: %.2e of max|logit|" % (T, cfg_name, err))
         assert err <= BAR_W4A8_PREFILL, err
+
+
+# what host.Gemma switch each case of the route test flips, per policy: "staged" = set_resident_prefill_weights(False), "flipped" = set_fp8_activation_prefill away
+# from the policy's default (fp8: W8A8 on; fp4: W4A8 off, the exact-weight bf16 path), "unfused" = set_fused_prefill(False)
+ROUTE_SWITCHES = {"bf16": ("default", "unfused"), "fp8": ("default", "staged", "flipped", "unfused"), "fp4": ("default", "staged", "flipped", "unfused")}
+ROUTE_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "prefill_routes.json")
+
+
+def prefill_route_forms():
+    """{case: the '+'-joined kernel forms of ONE prefill of a one-layer model}: T = 24 on MEDIUM (few-row / unfused-pair routes), T = 1024 on WIDE_FFN (LDS-DMA GEMMs,
+    the fused fp8 x fp8 Linear + GeGLU; its 200 bf16 GeGLU tiles fill 78 % of a round of CUs, short of the fused bf16 forms' 80 %, so those policies run the pair) and on
+    WIDE_FFN with F = 6656 (208 tiles: the fused bf16 / resident / staged GeGLU forms), the layer global (sliding_window_pattern 1) or local (6), every policy under
+    every switch of ROUTE_SWITCHES"""
+    from mila_amd import capi
+    out = {}
+    for geo, base, T in (("medium_T24", MEDIUM, 24), ("wide_ffn_T1024", WIDE_FFN, 1024), ("wide_ffn_F6656_T1024", dict(WIDE_FFN, hidden_dim=6656), 1024)):
+        toks = [(13 * i + 5) % 2048 for i in range(T)]
+        for kind, pattern in (("global", 1), ("local", 6)):
+            cfg = dict(base, num_layers=1, sliding_window_pattern=pattern)
+            for policy, switches in ROUTE_SWITCHES.items():
+                for sw in switches:
+                    m = host.Gemma(policy, cfg, max_seq=T + 8, max_prefill=T, seed=3)
+                    try:
+                        if sw == "staged":
+                            m.set_resident_prefill_weights(False)
+                        elif sw == "flipped":
+                            m.set_fp8_activation_prefill(policy == "fp8")
+                        elif sw == "unfused":
+                            m.set_fused_prefill(False)
+                        capi.last_form()
+                        m.prefill(toks)
+                        out["%s/%s/%s/%s" % (geo, kind, policy, sw)] = "+".join(capi.last_form())
+                    finally:
+                        m.close()
+    return out
+
+
+def test_every_prefill_route_launches_the_recorded_kernel_forms():
+    """Most routes of a policy are bit-identical by design (resident vs per-forward staging, fused Linear + GeGLU vs the pair), so a Linear call that takes the wrong
+    route shows in no logit, only as lost speed.  The kernel forms one prefill launches (mila_cdna4_last_form), case by case, against tests/golden/prefill_routes.json.
+    The form buffer holds 256 characters and drops what does not fit, so every recorded string stays below 250.  The forms name the GEMM and attention kernels, not the
+    launches around them: a resident copy and the same GEMM behind a staging pass, or caller-quantized rows and a quantize launch, read alike here."""
+    with open(ROUTE_FIXTURE) as f:
+        want = json.load(f)
+    assert want and all(0 < len(v) < 250 for v in want.values()), {k: len(v) for k, v in want.items() if not 0 < len(v) < 250}
+    got = prefill_route_forms()
+    assert sorted(got) == sorted(want)
+    wrong = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not wrong, wrong
