@@ -179,13 +179,39 @@ __device__ __forceinline__ void warm_lines(const uint8_t* __restrict__ base, int
     if (acc == 0x12345679u && never != nullptr) never[0] = 1.0f;   // keeps the loads alive; never true in practice
 }
 
+// Diagnostic build only (-DMILA_ATTN_STAMPS, never the product library; tools/experiments/attn_stamps.sh): lane 0 of workgroup (0, 0, 0) of attn_decode_kernel adds the
+// shader cycles from its first instruction to the issue of its first K/V row requests to g_attn_stamps[0] and counts the launch in [1]; a buffer of its own, no output
+// is touched.  Read back with mila_dbg_attn_stamps().
+#ifdef MILA_ATTN_STAMPS
+__device__ unsigned long long g_attn_stamps[2];
+#endif
+
 // HS = 64 * EPL (EPL in {2,4,8}) or HS = 64 handled as EPL = 2 on 32 active lanes.
 // GH = query heads per workgroup; grid = (splits, NKV * GS/GH, B); 8 waves, wave w owns positions
 // begin + w + 8 j of the split.  FUSED: the q/k/v post-processing of the token is done in the prologue,
 // overlapped with the first K/V round trip; the new K/V row is appended to the cache by the split that owns it.
-template <int HS, int GH, bool FUSED>
-__global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(const AttnParams p)
+//
+// Arguments: the head of the kernel's latency chain is kernel arguments -> *pos_dev -> band and row addresses -> the first K/V round trip.  What that chain reads comes
+// as leading plain parameters (14 dwords), which the dispatcher preloads into SGPRs before the first instruction (kernarg preload, build.py), so the load of *pos_dev is
+// the first thing a wave does; the parameter block follows as a by-value tail that is fetched from the kernarg segment under that load.  The tail is the launcher's
+// whole AttnParams: its copies of the leading fields are never read, the leading parameters replace them below.
+#define MILA_ATTN_LEAD_PARAMS const int32_t* pos_dev, uint16_t* K, uint16_t* V, const uint16_t* q_raw, int NH, int NKV, int capacity, int window, int splits, int flat
+#define MILA_ATTN_LEAD_ARGS(p) (p).pos_dev, (p).K, (p).V, (p).q_raw, (p).NH, (p).NKV, (p).capacity, (p).window, (p).splits, (p).flat
+__device__ __forceinline__ AttnParams attn_params(MILA_ATTN_LEAD_PARAMS, const AttnParams& tail)
 {
+    AttnParams p = tail;
+    p.pos_dev = pos_dev; p.K = K; p.V = V; p.q_raw = q_raw;
+    p.NH = NH; p.NKV = NKV; p.capacity = capacity; p.window = window; p.splits = splits; p.flat = flat;
+    return p;
+}
+
+template <int HS, int GH, bool FUSED>
+__global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATTN_LEAD_PARAMS, const AttnParams tail)
+{
+#ifdef MILA_ATTN_STAMPS
+    const unsigned long long entry_ = __builtin_amdgcn_s_memtime();
+#endif
+    const AttnParams p = attn_params(pos_dev, K, V, q_raw, NH, NKV, capacity, window, splits, flat, tail);
     using Row = DecodeGeomBf16<HS>;
     constexpr int NW = kDecodeWaves, EPL = Row::EPL, NPAIR = Row::NPAIR, ACTIVE = Row::ACTIVE, PG = Row::PG, STR = HS + 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -243,6 +269,13 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(const At
     int base = begin + wave;
     KVG ga, gb;
     if (base < end) load_group(ga, base);                  // in flight during the prologue
+#ifdef MILA_ATTN_STAMPS
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
+    {
+        g_attn_stamps[0] += __builtin_amdgcn_s_memtime() - entry_;
+        g_attn_stamps[1] += 1;
+    }
+#endif
 
     // ---- q (and the new K/V row) ----
     uint32_t q[GH][NPAIR];
@@ -415,9 +448,10 @@ __global__ __launch_bounds__(64) void attn_combine_kernel(uint16_t* __restrict__
 // rounded to bf16 for the PV product (as the flash kernels do): within 1 bf16 ulp of the double-precision oracle like them, NOT bit-identical to the scalar kernel --
 // the choice depends on (window, capacity) only, so every path of a model (reference order, fused, graph replay) takes the same kernel.
 template <int HS>
-__global__ __launch_bounds__(256) void attn_decode_mfma_kernel(const AttnParams p)
+__global__ __launch_bounds__(256) void attn_decode_mfma_kernel(MILA_ATTN_LEAD_PARAMS, const AttnParams tail)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_mfma[];
+    const AttnParams p = attn_params(pos_dev, K, V, q_raw, NH, NKV, capacity, window, splits, flat, tail);
     const int pos = p.pos_dev ? *p.pos_dev : p.position;
     const MfmaDecodeArgs a{p.Q, p.q_b_stride, p.scratch, p.NH, p.NKV, p.capacity, pos + 1, p.window, p.splits, p.scale};
     attn_decode_mfma_body<HS>(a, MfmaStageBf16<HS>{p.K, p.V}, smem_mfma);
@@ -601,7 +635,7 @@ static int launch_decode_mfma(const AttnParams& p, int B, hipStream_t s)
         attr_set = true;
     }
     const int n16 = (p.NH / p.NKV) / 16;
-    hipLaunchKernelGGL((attn_decode_mfma_kernel<HS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((attn_decode_mfma_kernel<HS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
     int rc = check_hip(hipGetLastError(), "attn_decode_mfma");
     if (rc) return rc;
     return launch_attn_combine_many(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
@@ -617,13 +651,13 @@ static int launch_decode(const AttnParams& p, int B, hipStream_t s)
     if (p.flat)
     {
         // (only taken without warm blocks, tickets or a caller-side combine: plan_decode)
-        hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED>), dim3(p.NKV * hgroups * p.splits, 1, B), dim3(kDecodeWaves * 64), lds, s, p);
+        hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED>), dim3(p.NKV * hgroups * p.splits, 1, B), dim3(kDecodeWaves * 64), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
         int rc = check_hip(hipGetLastError(), "attn_decode (xcd-local)");
         if (rc || p.splits <= 1) return rc;
         hipLaunchKernelGGL(attn_combine_kernel, dim3(p.NH * (HS / 64), B, 1), dim3(64), 0, s, p.Y, p.scratch, p.NH, HS, p.splits, nullptr, 0, 0, GH);
         return check_hip(hipGetLastError(), "attn_combine (xcd-local)");
     }
-    hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED>), dim3(p.splits + wa, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, p);
+    hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED>), dim3(p.splits + wa, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
     int rc = check_hip(hipGetLastError(), "attn_decode");
     if (rc) return rc;
     if (p.splits > 1 && !p.no_combine && !p.tickets)
@@ -804,6 +838,13 @@ __global__ __launch_bounds__(256) void mha_kv_write_vec_kernel(uint16_t* __restr
 using namespace mila;
 
 extern "C" {
+
+#ifdef MILA_ATTN_STAMPS
+MILA_API int mila_dbg_attn_stamps(unsigned long long* out2)
+{
+    return (int)hipMemcpyFromSymbol(out2, HIP_SYMBOL(mila::g_attn_stamps), 2 * sizeof(unsigned long long));
+}
+#endif
 
 int mila_cdna4_kv_write_bf16(uint16_t* Kc, uint16_t* Vc, const uint16_t* k, const uint16_t* v, int B, int chunk, int NKV,
                              int HS, int start_pos, int capacity, mila_stream_t stream)

@@ -31,10 +31,11 @@ namespace mila {
 // ---- quantizing KV append ---------------------------------------------------------------------------------------------------------------------------------------
 // one wave per (K | V, batch, token, KV head) row: lanes below HS / EPL own EPL consecutive elements, the absmax is a wave reduction (exact, any order)
 template <int HS>
-__global__ __launch_bounds__(256) void kv_write_fp8_kernel(uint8_t* __restrict__ K8, uint8_t* __restrict__ V8, float* __restrict__ Ks, float* __restrict__ Vs,
-                                                           const uint16_t* __restrict__ k, const uint16_t* __restrict__ v, int64_t rows, int chunk, int NKV,
-                                                           int start_pos, const int32_t* __restrict__ pos_dev, int capacity)
+__global__ __launch_bounds__(256) void kv_write_fp8_kernel(const int32_t* __restrict__ pos_dev, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
+                                                           uint8_t* __restrict__ K8, uint8_t* __restrict__ V8, int chunk, int NKV, int capacity, int start_pos,
+                                                           int64_t rows, float* __restrict__ Ks, float* __restrict__ Vs)
 {
+    // (argument order: the position word, the source rows and what the row addresses derive from lead -- the 14 dwords the dispatcher preloads into SGPRs, build.py)
     constexpr int EPL = HS >= 512 ? 8 : 4, ACTIVE = HS / EPL;
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // wave-uniform
@@ -124,9 +125,23 @@ struct KvFp8DecodeParams
 };
 
 // GH = query heads per workgroup; grid = (splits, NKV * GS/GH, B).  Wave w, lane segment s own positions begin + (w * RPW + s) + 8 * RPW * j of the split.
-template <int HS, int GH>
-__global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kvfp8_kernel(const KvFp8DecodeParams p)
+//
+// Arguments, as attn_decode_kernel's (attention.hip): what the chain kernel arguments -> *pos_dev -> band and row addresses -> first K/V request reads comes as leading
+// plain parameters (13 dwords, preloaded into SGPRs by the dispatcher); the tail is the launcher's whole parameter block, whose copies of those fields are never read.
+#define MILA_KVFP8_LEAD_PARAMS const int32_t* pos_dev, const uint8_t* K8, const uint8_t* V8, const float* Ks, int NH, int NKV, int capacity, int window, int splits
+#define MILA_KVFP8_LEAD_ARGS(p) (p).pos_dev, (p).K8, (p).V8, (p).Ks, (p).NH, (p).NKV, (p).capacity, (p).window, (p).splits
+__device__ __forceinline__ KvFp8DecodeParams kvfp8_params(MILA_KVFP8_LEAD_PARAMS, const KvFp8DecodeParams& tail)
 {
+    KvFp8DecodeParams p = tail;
+    p.pos_dev = pos_dev; p.K8 = K8; p.V8 = V8; p.Ks = Ks;
+    p.NH = NH; p.NKV = NKV; p.capacity = capacity; p.window = window; p.splits = splits;
+    return p;
+}
+
+template <int HS, int GH>
+__global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kvfp8_kernel(MILA_KVFP8_LEAD_PARAMS, const KvFp8DecodeParams tail)
+{
+    const KvFp8DecodeParams p = kvfp8_params(pos_dev, K8, V8, Ks, NH, NKV, capacity, window, splits, tail);
     using Row = DecodeGeomKvFp8<HS>;
     constexpr int NW = kDecodeWaves, EPL = Row::EPL, ND = Row::ND, NPAIR = Row::NPAIR, LPR = Row::LPR, RPW = Row::RPW, PG = Row::PG;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_kvfp8[];
@@ -264,7 +279,7 @@ static int launch_decode_kvfp8(const KvFp8DecodeParams& p, int B, int hgroups, h
 {
     note_form("attn_decode_kvfp8");
     const size_t lds = (size_t)kDecodeWaves * GH * (HS + 2) * sizeof(float);      // <= 33 KB (HS 256 x 4 heads, HS 512 x 2)
-    hipLaunchKernelGGL((attn_decode_kvfp8_kernel<HS, GH>), dim3(p.splits, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, p);
+    hipLaunchKernelGGL((attn_decode_kvfp8_kernel<HS, GH>), dim3(p.splits, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, MILA_KVFP8_LEAD_ARGS(p), p);
     int rc = check_hip(hipGetLastError(), "attn_decode_kvfp8");
     if (rc || p.splits <= 1) return rc;
     return launch_attn_combine(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
@@ -272,9 +287,10 @@ static int launch_decode_kvfp8(const KvFp8DecodeParams& p, int B, int hgroups, h
 
 // ---- the matrix-core decode (attention_decode_mfma.h): grid (splits, NKV * GS / 16, B), 256 threads ----
 template <int HS>
-__global__ __launch_bounds__(256) void attn_decode_kvfp8_mfma_kernel(const KvFp8DecodeParams p)
+__global__ __launch_bounds__(256) void attn_decode_kvfp8_mfma_kernel(MILA_KVFP8_LEAD_PARAMS, const KvFp8DecodeParams tail)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_kvfp8_mfma[];
+    const KvFp8DecodeParams p = kvfp8_params(pos_dev, K8, V8, Ks, NH, NKV, capacity, window, splits, tail);
     const int len = p.pos_dev ? *p.pos_dev + 1 : p.len;
     const MfmaDecodeArgs a{p.Q, 0, p.scratch, p.NH, p.NKV, p.capacity, len, p.window, p.splits, p.scale};
     attn_decode_mfma_body<HS>(a, MfmaStageKvFp8<HS>{p.K8, p.V8, p.Ks, p.Vs}, smem_kvfp8_mfma);
@@ -293,7 +309,7 @@ static int launch_decode_kvfp8_mfma(const KvFp8DecodeParams& p, int B, hipStream
         attr_set = true;
     }
     const int n16 = (p.NH / p.NKV) / 16;
-    hipLaunchKernelGGL((attn_decode_kvfp8_mfma_kernel<HS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((attn_decode_kvfp8_mfma_kernel<HS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, MILA_KVFP8_LEAD_ARGS(p), p);
     int rc = check_hip(hipGetLastError(), "attn_decode_kvfp8_mfma");
     if (rc) return rc;
     return launch_attn_combine_many(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
@@ -317,10 +333,10 @@ static int launch_kv_write_fp8(const char* who, uint8_t* K8, uint8_t* V8, float*
     hipStream_t s = as_stream(stream);
     switch (HS)
     {
-        case 64: hipLaunchKernelGGL(kv_write_fp8_kernel<64>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, pos_dev, capacity); break;
-        case 128: hipLaunchKernelGGL(kv_write_fp8_kernel<128>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, pos_dev, capacity); break;
-        case 256: hipLaunchKernelGGL(kv_write_fp8_kernel<256>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, pos_dev, capacity); break;
-        default: hipLaunchKernelGGL(kv_write_fp8_kernel<512>, grid, dim3(256), 0, s, K8, V8, Ks, Vs, k, v, rows, chunk, NKV, start_pos, pos_dev, capacity); break;
+        case 64: hipLaunchKernelGGL(kv_write_fp8_kernel<64>, grid, dim3(256), 0, s, pos_dev, k, v, K8, V8, chunk, NKV, capacity, start_pos, rows, Ks, Vs); break;
+        case 128: hipLaunchKernelGGL(kv_write_fp8_kernel<128>, grid, dim3(256), 0, s, pos_dev, k, v, K8, V8, chunk, NKV, capacity, start_pos, rows, Ks, Vs); break;
+        case 256: hipLaunchKernelGGL(kv_write_fp8_kernel<256>, grid, dim3(256), 0, s, pos_dev, k, v, K8, V8, chunk, NKV, capacity, start_pos, rows, Ks, Vs); break;
+        default: hipLaunchKernelGGL(kv_write_fp8_kernel<512>, grid, dim3(256), 0, s, pos_dev, k, v, K8, V8, chunk, NKV, capacity, start_pos, rows, Ks, Vs); break;
     }
     return check_hip(hipGetLastError(), who);
 }

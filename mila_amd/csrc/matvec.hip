@@ -37,14 +37,37 @@ namespace mila {
 //     buffer with step t + 2; the last <= 3 steps are peeled so the loop body needs no validity test.
 // One 1024-thread workgroup (16 waves) per CU: x is staged (and the prologue computed) once per CU, so the
 // L2 -> LDS staging traffic is 256 * 2K bytes whatever the weight format.
+//
+// Arguments: what the first memory instructions need (the weight, x and prologue-operand addresses, the two sizes and the grid size every index derives from) comes as
+// leading plain parameters, 11 dwords, which the dispatcher preloads into SGPRs before the first instruction (kernarg preload, build.py: PRELOAD_FLAGS); the rest stays in
+// a by-value tail that is fetched from the kernarg segment when it is first used.  matvec_body keeps its MatvecParams: it is rebuilt in registers here.
+struct MatvecTail
+{
+    void* y;
+    const float* scales;
+    const uint16_t* bias;
+    const uint16_t* post_w;
+    uint16_t* res_out;
+    float post_scale, eps;
+    int group, comb_splits, comb_heads;
+    float* amax_v;
+    int* amax_i;
+};
+static MatvecTail matvec_tail(const MatvecParams& p)
+{
+    return MatvecTail{p.y, p.scales, p.bias, p.post_w, p.res_out, p.post_scale, p.eps, p.group, p.comb_splits, p.comb_heads, p.amax_v, p.amax_i};
+}
+
 template <int FMT, int R, int U, int PRO, bool GEGLU, bool F32OUT, int XC, int XSRC = X_PLAIN>
-__global__ __launch_bounds__(1024) void matvec_kernel(const MatvecParams p)
+__global__ __launch_bounds__(1024) void matvec_kernel(const uint8_t* W, const uint16_t* x, const uint16_t* norm_w, const uint16_t* res, int K, int N, int nblocks,
+                                                      const MatvecTail t)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ float red_a[16 * XC], red_b[16 * XC];
     u32x4 rkeep[XC];
+    const MatvecParams p{t.y, x, W, t.scales, t.bias, norm_w, t.post_w, res, t.res_out, t.post_scale, t.eps, K, N, t.group, t.comb_splits, t.comb_heads, t.amax_v, t.amax_i};
     matvec_body<FMT, R, U, PRO, GEGLU, F32OUT ? Y_F32 : Y_BF16, XC, XSRC, RES_MEM>(
-        p, reinterpret_cast<u32x4*>(smem_raw), red_a, red_b, (int)blockIdx.x, (int)gridDim.x, rkeep, NoWait{});
+        p, reinterpret_cast<u32x4*>(smem_raw), red_a, red_b, (int)blockIdx.x, nblocks, rkeep, NoWait{});
 }
 
 // ---- host side ------------------------------------------------------------------------------
@@ -68,7 +91,8 @@ static int launch_xc(const MatvecParams& p, int max_blocks, hipStream_t s)
     if (blocks < 1) blocks = 1;
     t_last_matvec_blocks = blocks;
     note_form("matvec");
-    hipLaunchKernelGGL((matvec_kernel<FMT, R, U, PRO, GEGLU, F32OUT, XC>), dim3(blocks), dim3(64 * kMatvecWaves), lds, s, p);
+    hipLaunchKernelGGL((matvec_kernel<FMT, R, U, PRO, GEGLU, F32OUT, XC>), dim3(blocks), dim3(64 * kMatvecWaves), lds, s, p.W, p.x, p.norm_w, p.res, p.K, p.N, blocks,
+                       matvec_tail(p));
     MILA_LAUNCH_CHECK("matvec");
 }
 
@@ -149,7 +173,8 @@ static int launch_combine_t(const MatvecParams& p, hipStream_t s)
     MILA_REQUIRE(lds <= 65536, "matvec_attn_combine: K=%d needs %zu bytes of LDS for x (limit 65536)", p.K, lds);
     int blocks = (p.N + kMatvecWaves - 1) / kMatvecWaves;
     if (blocks > kNumCU) blocks = kNumCU;
-    hipLaunchKernelGGL((matvec_kernel<FMT, 1, U, 0, false, false, 1, XSRC>), dim3(blocks), dim3(64 * kMatvecWaves), lds, s, p);
+    hipLaunchKernelGGL((matvec_kernel<FMT, 1, U, 0, false, false, 1, XSRC>), dim3(blocks), dim3(64 * kMatvecWaves), lds, s, p.W, p.x, p.norm_w, p.res, p.K, p.N, blocks,
+                       matvec_tail(p));
     MILA_LAUNCH_CHECK("matvec_attn_combine");
 }
 template <int XSRC>
