@@ -610,6 +610,48 @@ MILA_API int mila_cdna4_fused_attn_decode_batch_bf16(uint16_t* Y, uint16_t* Kc, 
                                                      size_t scratch_bytes, int B, int NH, int NKV, int HS, int capacity, int position,
                                                      const int32_t* position_dev, int window, float scale, float eps, mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched decode, 2 .. 4 rows per step, each row an independent sequence (ABI 4, additive).  The reference runs CudaLinearOp at M = B
+ * (Linear/Kernels/MatVec/CudaMatVecBias.Bf16.cu, one weight pass per row); here the weights are streamed ONCE for all rows.
+ * BATCH INVARIANCE: row b of every entry below has the bits the one-row entry gives on that row alone, whatever the other rows hold.
+ * ------------------------------------------------------------------------------------------- */
+/* The decode Linear on `rows` input vectors: everything matvec_bf16 / _qfp8 / _qfp4 / matvec_f32out (a.norm_w == NULL; `bias` optional, bf16 out only) and
+ * fused_norm_matvec (a.norm_w != NULL: norm prologue, sandwich tail, GeGLU, fp32 out, the sampler's first stage) compute, row by row.  `a` holds row 0's pointers;
+ * row b reads x + b * x_stride (and res + b * res_stride) and writes y + b * y_stride (and res_out + b * res_out_stride), strides in ELEMENTS of the respective type,
+ * at least the row's width, x / res / res_out strides multiples of 8.  With a.argmax_scratch, row b's partials go to argmax_scratch + b * sample_scratch_bytes()
+ * (argmax_scratch_bytes >= rows * sample_scratch_bytes()), every row has *a.argmax_blocks of them, and sample_argmax_rows_final_advance picks the tokens.
+ * rows outside 2 .. 4, or an x image that does not fit the 160 KiB of LDS: MILA_E_UNSUPPORTED. */
+typedef struct mila_matvec_rows_args {
+    mila_fused_matvec_args a;
+    const uint16_t* bias;     /* [N] bf16 or NULL; the plain form only                            */
+    int rows;
+    int64_t x_stride, y_stride, res_stride, res_out_stride;
+} mila_matvec_rows_args;
+MILA_API int mila_cdna4_matvec_rows(const mila_matvec_rows_args* host_args, mila_stream_t stream);
+
+/* fused_attn_decode_batch_bf16 for B INDEPENDENT sequences: row b decodes at positions_dev[b] (device memory, always: this is the graph-replay form) on its own caches
+ * [b] -- a different prompt length per row, rows that finish at different times (the reference's decode kernels take the batch in their grid at ONE position,
+ * Gqa.Decode.Bf16.cu:379-387).  max_len is the live-length bound the launch is captured for (0 = the capacity), as `position` is beside a position_dev in
+ * fused_attn_decode_bf16; the caller passes the bound of its LONGEST row.  The splits are planned for ONE row at that bound and used for every row, so row b's Y and
+ * cache rows are bit-identical to fused_attn_decode_bf16 in its device-position form at positions_dev[b] with the same max_len, whatever the other rows hold; a row
+ * whose band is shorter leaves (m = -inf, l = 0) partials in its idle splits.  THE ONE LIMIT of that invariance: on an unwindowed layer the plan follows the live-length
+ * bucket of max_len (attn_decode_band_bucket), so a row that would sit ALONE in a lower bucket than the batch's longest row is reduced over the higher bucket's splits
+ * here -- equal to the alone run captured for that bound, not to one captured for the row's own lower bucket.  Head sizes 64, 128, 256, 512; scratch from
+ * attn_decode_scratch_bytes(B, NH, HS). */
+MILA_API int mila_cdna4_fused_attn_decode_rows_bf16(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, const uint16_t* q_raw, const uint16_t* k_raw,
+                                                    const uint16_t* v_raw, int64_t raw_b_stride, const uint16_t* qw, const uint16_t* kw,
+                                                    const uint16_t* vw, const float* cos_cache, const float* sin_cache, void* scratch,
+                                                    size_t scratch_bytes, int B, int NH, int NKV, int HS, int capacity, const int32_t* positions_dev,
+                                                    int max_len, int window, float scale, float eps, mila_stream_t stream);
+
+/* The tail of a captured greedy step for B rows (the rows twin of sample_argmax_final_advance; Sampling.cu:23-75 once per row): token b = the argmax over the `blocks`
+ * partials a matvec_rows launch left at scratch + b * sample_scratch_bytes() -- the token sample_argmax_fp32 gives on row b's logits, ties to the lowest index.  Only
+ * where active_dev[b] != 0 is token_out[b] stored and positions_dev[b] += 1: a retired row keeps its token and its position.
+ * advance_positions_rows is the position bump alone (the stochastic path samples on its own). */
+MILA_API int mila_cdna4_sample_argmax_rows_final_advance(int32_t* token_out, const void* scratch, size_t scratch_bytes, int blocks, int32_t* positions_dev,
+                                                         const int32_t* active_dev, int B, mila_stream_t stream);
+MILA_API int mila_cdna4_advance_positions_rows(int32_t* positions_dev, const int32_t* active_dev, int B, mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

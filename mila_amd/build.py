@@ -25,10 +25,10 @@ KERNEL_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisib
                 "-Wall", "-Wno-unused-function"]
 # Kernarg preload (gfx950): the dispatcher writes a kernel's leading plain arguments into user SGPRs before the wave's first instruction, so the first loads do not
 # wait for a fetch from the kernarg segment.  Only leading scalar / pointer parameters are preloaded (a by-value struct never is): the decode step's kernels are
-# written that way (matvec.hip, attention.hip, attention_kvfp8.hip).  Set for the translation units of the captured decode step; the prefill GEMM / flash files are
+# written that way (matvec.hip, matvec_rows.hip, attention.hip, attention_kvfp8.hip).  Set for the translation units of the captured decode step; the prefill GEMM / flash files are
 # built as before.  16 = all user SGPRs; the compiler preloads what fits beside the kernarg pointer.
 PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
-PRELOAD_SOURCES = {"matvec.hip", "attention.hip", "attention_kvfp8.hip", "sampling.hip", "fused.hip"}
+PRELOAD_SOURCES = {"matvec.hip", "matvec_rows.hip", "attention.hip", "attention_kvfp8.hip", "sampling.hip", "fused.hip"}
 # host mirror: plain C++23 (no device code), HIP runtime API only for graphs/events
 HOST_FLAGS = ["-O2", "-std=c++23", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(os.path.dirname(ROOT), "include"),

@@ -119,6 +119,12 @@ class fused_matvec_args(C.Structure):
                 ("argmax_scratch", C.c_void_p), ("argmax_scratch_bytes", C.c_size_t), ("argmax_blocks", C.POINTER(C.c_int))]
 
 
+class matvec_rows_args(C.Structure):
+    """mila_matvec_rows_args: `a` holds row 0's pointers, row b is b strides (in elements) further"""
+    _fields_ = [("a", fused_matvec_args), ("bias", C.c_void_p), ("rows", C.c_int),
+                ("x_stride", C.c_int64), ("y_stride", C.c_int64), ("res_stride", C.c_int64), ("res_out_stride", C.c_int64)]
+
+
 class decode_chain_args(C.Structure):
     _fields_ = [("attn", C.c_void_p), ("res", C.c_void_p), ("res_out", C.c_void_p), ("y", C.c_void_p),
                 ("W_o", C.c_void_p), ("s_o", C.c_void_p), ("W_gate_up", C.c_void_p), ("s_gate_up", C.c_void_p),
@@ -214,6 +220,22 @@ def attn_prefill_plan(HS, NH, NKV, chunk, pos_offset=0, window=0):
     return dict(zip(PREFILL_PLAN_FIELDS, [f[0]] + [int(v) for v in f[1:]]))
 
 
+MATVEC_ROWS_PLAN_FIELDS = ("R", "U", "xc", "lds_bytes", "workgroups")
+
+
+def matvec_rows_plan(fmt, K, N, geglu=False, f32_out=False, rows=1):
+    """the launch of a decode Linear on `rows` input vectors (csrc/matvec_rows.hip: plan_rows; rows = 1: the one-row kernels of csrc/matvec.hip) as a dict of
+    MATVEC_ROWS_PLAN_FIELDS, or None for what the entry refuses.  Needs no GPU."""
+    lib = load()
+    lib.mila_cdna4_matvec_rows_plan_describe.restype = C.c_size_t
+    buf = C.create_string_buffer(128)
+    need = lib.mila_cdna4_matvec_rows_plan_describe(int(fmt), int(K), int(N), int(bool(geglu)), int(bool(f32_out)), int(rows), buf, C.c_size_t(len(buf)))
+    if not need:
+        return None
+    assert need <= len(buf), "plan text of %d bytes" % need
+    return dict(zip(MATVEC_ROWS_PLAN_FIELDS, [int(v) for v in buf.value.decode().split(":")]))
+
+
 RADIX_PLAN_FIELDS = ("launches", "k_passes", "p_passes", "scratch_need")
 
 
@@ -301,11 +323,12 @@ EXPORTED = [
     "kv_write_fp8", "attn_decode_kvfp8", "kv_dequant_fp8_bf16", "attn_prefill_kvfp8_scratch_bytes", "attn_prefill_kvfp8",
     "kv_write_fp8_devpos", "attn_decode_kvfp8_devpos", "attn_decode_kvfp8_plan_describe",
     "fused_qkv_post_kvfp8", "fused_qkv_post_kvfp8_prefill", "fused_qkv_post_kvfp8_devpos",
+    "matvec_rows", "fused_attn_decode_rows_bf16", "sample_argmax_rows_final_advance", "advance_positions_rows",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI
 INTERNAL = [
-    "tune", "tune_get", "tune_reset", "tune_list", "last_form", "gemm_plan_describe", "attn_decode_plan_describe",
+    "tune", "tune_get", "tune_reset", "tune_list", "last_form", "gemm_plan_describe", "attn_decode_plan_describe", "matvec_rows_plan_describe",
     "decode_engine_debug",
     "selftest_decode", "selftest_wave_reduce", "selftest_mfma_fp8", "stream_copy", "stream_read",
     "attn_decode_split_count", "fused_attn_decode_partials_bf16", "matvec_attn_combine",

@@ -86,6 +86,8 @@ struct AttnParams
     const float* cos_cache;
     const float* sin_cache;
     float eps;
+    int pos_stride;           // elements between two batch rows' position words at pos_dev: 0 = every row at *pos_dev (every entry but fused_attn_decode_rows_bf16), 1 = row b
+                              // at pos_dev[b].  It reaches the kernels as bit 1 of the leading `flat` argument, not through this tail copy (attn_params below)
 };
 
 // norm (+ RoPE) of one head row by one wave, canonical helpers => bit-identical to the standalone
@@ -194,14 +196,18 @@ __device__ unsigned long long g_attn_stamps[2];
 // Arguments: the head of the kernel's latency chain is kernel arguments -> *pos_dev -> band and row addresses -> the first K/V round trip.  What that chain reads comes
 // as leading plain parameters (14 dwords), which the dispatcher preloads into SGPRs before the first instruction (kernarg preload, build.py), so the load of *pos_dev is
 // the first thing a wave does; the parameter block follows as a by-value tail that is fetched from the kernarg segment under that load.  The tail is the launcher's
-// whole AttnParams: its copies of the leading fields are never read, the leading parameters replace them below.
+// whole AttnParams: its copies of the leading fields are never read, the leading parameters replace them below.  The per-row position stride (0 or 1) is on that chain
+// too -- it is part of the address of the position word -- so it travels in the leading block, as bit 1 of `flat`: read from the tail, the first load of every decode
+// launch would wait for the kernarg fetch again.
+// NEVER read the leading `flat` argument raw: it carries two flags (bit 0: the XCD-local grid, bit 1: per-row position words).  Kernels go through attn_params(),
+// which splits it into AttnParams::flat (0 / 1) and AttnParams::pos_stride (0 / 1); a kernel that tested the raw value would see 2 and 3 under the rows entry.
 #define MILA_ATTN_LEAD_PARAMS const int32_t* pos_dev, uint16_t* K, uint16_t* V, const uint16_t* q_raw, int NH, int NKV, int capacity, int window, int splits, int flat
-#define MILA_ATTN_LEAD_ARGS(p) (p).pos_dev, (p).K, (p).V, (p).q_raw, (p).NH, (p).NKV, (p).capacity, (p).window, (p).splits, (p).flat
+#define MILA_ATTN_LEAD_ARGS(p) (p).pos_dev, (p).K, (p).V, (p).q_raw, (p).NH, (p).NKV, (p).capacity, (p).window, (p).splits, ((p).flat | ((p).pos_stride ? 2 : 0))
 __device__ __forceinline__ AttnParams attn_params(MILA_ATTN_LEAD_PARAMS, const AttnParams& tail)
 {
     AttnParams p = tail;
     p.pos_dev = pos_dev; p.K = K; p.V = V; p.q_raw = q_raw;
-    p.NH = NH; p.NKV = NKV; p.capacity = capacity; p.window = window; p.splits = splits; p.flat = flat;
+    p.NH = NH; p.NKV = NKV; p.capacity = capacity; p.window = window; p.splits = splits; p.flat = flat & 1; p.pos_stride = (flat >> 1) & 1;
     return p;
 }
 
@@ -233,7 +239,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATT
     const int kvh = grp / hgroups, hg = grp % hgroups;
     const int h0 = kvh * GS + hg * GH;                     // first query head of this workgroup
     const int b = blockIdx.z;
-    const int pos = p.pos_dev ? *p.pos_dev : p.position;
+    const int pos = p.pos_dev ? p.pos_dev[b * p.pos_stride] : p.position;
     const int len = pos + 1;
     const int band_begin = (p.window > 0) ? max(0, len - p.window) : 0;
     const int band = len - band_begin;
@@ -452,7 +458,7 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(MILA_ATTN_LEAD_PA
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_mfma[];
     const AttnParams p = attn_params(pos_dev, K, V, q_raw, NH, NKV, capacity, window, splits, flat, tail);
-    const int pos = p.pos_dev ? *p.pos_dev : p.position;
+    const int pos = p.pos_dev ? p.pos_dev[(int)blockIdx.z * p.pos_stride] : p.position;      // blockIdx.z: the batch row (attention_decode_mfma.h)
     const MfmaDecodeArgs a{p.Q, p.q_b_stride, p.scratch, p.NH, p.NKV, p.capacity, pos + 1, p.window, p.splits, p.scale};
     attn_decode_mfma_body<HS>(a, MfmaStageBf16<HS>{p.K, p.V}, smem_mfma);
 }
@@ -713,7 +719,8 @@ static int run_decode(const DecodePlan& d, AttnParams p, int B, int HS, size_t s
             uint16_t* vc = p.V + (size_t)b * p.NKV * p.capacity * HS;
             const size_t ro = (size_t)b * p.raw_b_stride;
             const int rc = p.pos_dev ? mila_cdna4_fused_qkv_post_devpos(q_tmp + (size_t)b * p.NH * HS, kc, vc, p.q_raw + ro, p.k_raw + ro, p.v_raw + ro, p.qw, p.kw, p.vw, p.cos_cache,
-                                                                        p.sin_cache, p.NH, p.NKV, HS, p.pos_dev, p.capacity, p.eps, reinterpret_cast<mila_stream_t>(stream))
+                                                                        p.sin_cache, p.NH, p.NKV, HS, p.pos_dev + (size_t)b * p.pos_stride, p.capacity, p.eps,
+                                                                        reinterpret_cast<mila_stream_t>(stream))
                                      : mila_cdna4_fused_qkv_post(q_tmp + (size_t)b * p.NH * HS, kc, vc, p.q_raw + ro, p.k_raw + ro, p.v_raw + ro, p.qw, p.kw, p.vw, p.cos_cache,
                                                                  p.sin_cache, p.NH, p.NKV, HS, p.position, p.capacity, p.eps, reinterpret_cast<mila_stream_t>(stream));
             if (rc) return rc;
@@ -736,7 +743,8 @@ static int unfused_decode(const char* who, uint16_t* Y, const uint16_t* Q, int64
 
 // What the fused entry points share: the checks (`who` names the entry in the messages), the prologue fields of AttnParams, the plan and its launch.  The argument
 // block is fused_attn_decode_ex's; the other entries fill it from their parameter lists.
-enum { FD_BATCH = 1, FD_TICKETS = 2, FD_PARTIALS = 4 };      // the batch entry's B / raw_b_stride checks | tickets are required | no Y: the partials stay in scratch
+// the batch entry's B / raw_b_stride checks | tickets are required | no Y: the partials stay in scratch | row b at position_dev[b], planned as ONE row
+enum { FD_BATCH = 1, FD_TICKETS = 2, FD_PARTIALS = 4, FD_ROWS = 8 };
 static int fused_decode(const char* who, const mila_fused_attn_args& a, int B, int64_t raw_b_stride, int flags, hipStream_t stream)
 {
     MILA_REQUIRE((a.Y || (flags & FD_PARTIALS)) && a.Kc && a.Vc && a.q_raw && a.k_raw && a.v_raw && a.qw && a.kw && a.cos_cache && a.sin_cache &&
@@ -761,11 +769,19 @@ static int fused_decode(const char* who, const mila_fused_attn_args& a, int B, i
     p.cos_cache = a.cos_cache; p.sin_cache = a.sin_cache; p.eps = a.eps;
     p.tickets = a.tickets;
     p.no_combine = (flags & FD_PARTIALS) ? 1 : 0;
+    p.pos_stride = (flags & FD_ROWS) ? 1 : 0;
     if (a.warm_a && a.warm_a_bytes >= 128 && a.warm_a_blocks > 0) { p.warm_a = (const uint8_t*)a.warm_a; p.warm_a_lines = (int64_t)(a.warm_a_bytes / 128); p.warm_a_blocks = a.warm_a_blocks; }
     if (a.warm_b && a.warm_b_bytes >= 128 && a.warm_b_blocks > 0) { p.warm_b = (const uint8_t*)a.warm_b; p.warm_b_lines = (int64_t)(a.warm_b_bytes / 128); p.warm_b_blocks = a.warm_b_blocks; p.warm_b_pair = (int64_t)a.warm_b_pair_offset; }
     // under position_dev, `position` carries the live-length bound the launch is captured for (0 = the capacity)
-    const DecodePlan d = plan_decode(B, a.NH, a.NKV, a.HS, a.capacity, a.window, a.position_dev ? a.position : a.position + 1, true,
-                                     p.tickets || p.no_combine || p.warm_a || p.warm_b);
+    // FD_ROWS: rows are independent sequences, and a row must have the bits it has decoded alone -- the splits are planned for ONE row and used for every row (a B-row
+    // plan would share the chip between the rows and reduce each row over fewer, longer splits); only the scratch is sized for all of them
+    DecodePlan d = plan_decode((flags & FD_ROWS) ? 1 : B, a.NH, a.NKV, a.HS, a.capacity, a.window, a.position_dev ? a.position : a.position + 1, true,
+                               p.tickets || p.no_combine || p.warm_a || p.warm_b);
+    if ((flags & FD_ROWS) && B > 1)
+    {
+        d.partial_floats *= (size_t)B;
+        if (d.scratch_need) d.scratch_need = decode_scratch_bytes(B, a.NH, a.HS, d.splits, d.prologue);
+    }
     if (flags & FD_PARTIALS) MILA_REQUIRE(d.splits > 1, "%s: this (window, capacity) runs unsplit; use fused_attn_decode_bf16", who);
     if (!a.position_dev)
     {
@@ -920,6 +936,20 @@ int mila_cdna4_fused_attn_decode_batch_bf16(uint16_t* Y, uint16_t* Kc, uint16_t*
     return fused_decode("fused_attn_decode_batch_bf16", fused_args(Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, nullptr, 0, NH, NKV,
                                                                    HS, capacity, position, position_dev, window, scale, eps), B, raw_b_stride, FD_BATCH, as_stream(stream));
 }
+// B independent sequences, row b at positions_dev[b]: see mila_cdna4.h for the invariance this entry keeps
+int mila_cdna4_fused_attn_decode_rows_bf16(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, const uint16_t* q_raw, const uint16_t* k_raw, const uint16_t* v_raw, int64_t raw_b_stride,
+                                           const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache, void* scratch,
+                                           size_t scratch_bytes, int B, int NH, int NKV, int HS, int capacity, const int32_t* positions_dev, int max_len, int window, float scale,
+                                           float eps, mila_stream_t stream)
+{
+    MILA_REQUIRE(positions_dev != nullptr, "fused_attn_decode_rows_bf16: positions_dev is required (the rows' positions live on the device)");
+    MILA_REQUIRE(max_len >= 0 && max_len <= capacity, "fused_attn_decode_rows_bf16: max_len %d outside 0 .. the capacity %d", max_len, capacity);
+    MILA_REQUIRE(decode_scalar_head_size(HS), "fused_attn_decode_rows_bf16: head size %d must be 64, 128, 256 or 512", HS);
+    return fused_decode("fused_attn_decode_rows_bf16", fused_args(Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, nullptr, 0, NH, NKV,
+                                                                  HS, capacity, max_len, positions_dev, window, scale, eps),
+                        B, raw_b_stride, FD_BATCH | FD_ROWS, as_stream(stream));
+}
+
 // ---- GPT-2 multi-head attention over a KV cache (CudaMhaOp.ixx:137-380: prefill / decode of IPositionalUnaryOp + IKvCacheLifecycle) ----
 // The cache is [B, NH, capacity, HS] like the GQA one (NKV = NH); K / V come from the packed [B, T, 3C] projection.
 int mila_cdna4_mha_kv_write_bf16(uint16_t* Kc, uint16_t* Vc, const uint16_t* QKV, int B, int T, int C, int NH, int start_pos, int capacity,

@@ -27,6 +27,11 @@ MILA_API size_t mila_cdna4_gemm_plan_describe(int entry, int M, int K, int N, ch
  * capacity), fused = a fused entry, hooks = the entry uses tickets, no_combine or warm ranges.  Writes "form:splits:band_max:heads_per_group:head_groups:flat:prologue:
  * partial_floats:scratch_need" (form: attn_decode | attn_decode_mfma | attn_generic); returns the text's size, 0 for a bad shape. */
 MILA_API size_t mila_cdna4_attn_decode_plan_describe(int B, int NH, int NKV, int HS, int capacity, int window, int len_hint, int fused, int hooks, char* buf, size_t cap);
+/* the launch of a decode Linear on `rows` input vectors (csrc/matvec_rows.hip: plan_rows) as text, without running device code: "R:U:xc:lds_bytes:workgroups" -- output
+ * columns per wave step, chunk positions in flight, 16-byte x chunks per thread, dynamic LDS, grid.  rows = 1 describes the one-row launch of matvec_* / fused_norm_matvec
+ * (csrc/matvec.hip); f32_out = the lm_head launch with the sampler's first stage.  U is the same for every row count: it is part of a row's arithmetic.  Returns the
+ * text's size, 0 for what is refused (rows outside 1 .. 4, K beyond 16384 or no multiple of the format's chunk). */
+MILA_API size_t mila_cdna4_matvec_rows_plan_describe(int fmt, int K, int N, int geglu, int f32_out, int rows, char* buf, size_t cap);
 /* The names (tune_list prints them with their values and defaults; each is documented where it is registered):
  *   matvec.rows_per_wave, matvec.chunks_in_flight, matvec.max_workgroups                 0 = the default rule                                         (csrc/matvec.hip)
  *   gemm.force128          1 = always the 128 x 128 register-staged GEMM (A/B against the LDS-DMA kernels)                                           (csrc/gemm_plan.hip)

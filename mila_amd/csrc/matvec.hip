@@ -123,36 +123,49 @@ static ShapeOverrides parse_shape_overrides()
     return o;
 }
 
-template <int FMT, int PRO, bool GEGLU, bool F32OUT>
-static int dispatch_RU(const MatvecParams& p, hipStream_t s)
+// The launch shape of a decode Linear, in ONE place: the one-row kernels launch from it, and the multi-row kernel (matvec_rows.hip) takes its U from it -- U fixes which
+// chunks a lane sums, so it is part of the arithmetic a row of a batched step must share with the same row decoded alone.
+MatvecShape matvec_launch_shape(int fmt, bool geglu, int N, bool argmax)
 {
     // Launch shape (measured on MI355X with tools/bench_matvec.py): weight rows per wave step
     // `rows_per_step` and chunk positions per step U by weight format and matrix height.  Small matrices want
     // the most waves (1 row each) and, for bf16, the deepest per-wave stream; tall ones amortise the LDS x
     // reads over more rows and take two workgroups per CU so the hardware balances the tail.
-    const int rows = GEGLU ? 2 * p.N : p.N;
+    const int rows = geglu ? 2 * N : N;
     const bool tall = rows >= 16384, huge = rows >= 100000;
     int rows_per_step, U;
-    if (FMT == FMT_BF16) { rows_per_step = huge ? 4 : (tall ? 2 : 1); U = tall ? 2 : 4; }
-    else if (FMT == FMT_FP8) { rows_per_step = huge ? 4 : (tall ? 2 : 1); U = 2; }
+    if (fmt == FMT_BF16) { rows_per_step = huge ? 4 : (tall ? 2 : 1); U = tall ? 2 : 4; }
+    else if (fmt == FMT_FP8) { rows_per_step = huge ? 4 : (tall ? 2 : 1); U = 2; }
     else { rows_per_step = tall ? 2 : 1; U = huge ? 2 : 1; }
     // two workgroups per CU (dynamic tail balance) pay for the bf16 matrices and for the lm_head; the quantized
     // tall matrices (fc_gate_up) are faster with one resident workgroup per CU (in-situ sweep, tools/tune_shapes.sh)
-    int max_blocks = (huge || (tall && FMT == FMT_BF16)) ? 2 * kNumCU : kNumCU;
+    int max_blocks = (huge || (tall && fmt == FMT_BF16)) ? 2 * kNumCU : kNumCU;
     {
         // tuning hook (tools/, never set by the product path): MILA_MATVEC_SHAPE="f<fmt>t<0 short|1 tall|2 huge>=rows,U,blocks;..."
         static const ShapeOverrides ov = parse_shape_overrides();
-        const ShapeOverrides::E& e = ov.e[FMT][huge ? 2 : (tall ? 1 : 0)];
+        const ShapeOverrides::E& e = ov.e[fmt][huge ? 2 : (tall ? 1 : 0)];
         if (e.set) { rows_per_step = e.rows; U = e.U; max_blocks = e.blocks; }
     }
-    int R = GEGLU ? (rows_per_step >= 2 ? rows_per_step / 2 : 1) : rows_per_step;
+    int R = geglu ? (rows_per_step >= 2 ? rows_per_step / 2 : 1) : rows_per_step;
     if (g_tune_R > 0) R = g_tune_R;
     if (g_tune_U > 0) U = g_tune_U;
     if (g_tune_blocks > 0) max_blocks = g_tune_blocks;
     // the argmax epilogue writes one (value, index) partial per WORKGROUP into the sampler's scratch of kArgmaxPartials slots: the grid is capped BEFORE the launch
     // (the count was only checked afterwards -- a tuned or future workgroup rule beyond 512 would have overrun the scratch first)
-    if (p.amax_v && max_blocks > kArgmaxPartials) max_blocks = kArgmaxPartials;
-    if (GEGLU && R > 2) R = 2;
+    if (argmax && max_blocks > kArgmaxPartials) max_blocks = kArgmaxPartials;
+    if (geglu && R > 2) R = 2;
+    // the instantiated (R, U) pairs: (1, 1) (1, 2) (1, 4) (2, 1) (2, 2) (4, 2); anything else goes to its neighbour, as the ladder in dispatch_RU always did
+    if (R == 1) U = (U == 1 || U == 2) ? U : 4;
+    else if (R == 2) U = (U == 1) ? 1 : 2;
+    else { R = geglu ? 2 : 4; U = 2; }
+    return MatvecShape{R, U, max_blocks};
+}
+
+template <int FMT, int PRO, bool GEGLU, bool F32OUT>
+static int dispatch_RU(const MatvecParams& p, hipStream_t s)
+{
+    const MatvecShape shape = matvec_launch_shape(FMT, GEGLU, p.N, p.amax_v != nullptr);
+    const int R = shape.R, U = shape.U, max_blocks = shape.max_blocks;
     if (R == 1 && U == 1) return launch<FMT, 1, 1, PRO, GEGLU, F32OUT>(p, max_blocks, s);
     if (R == 1 && U == 2) return launch<FMT, 1, 2, PRO, GEGLU, F32OUT>(p, max_blocks, s);
     if (R == 1) return launch<FMT, 1, 4, PRO, GEGLU, F32OUT>(p, max_blocks, s);

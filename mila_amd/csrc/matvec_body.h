@@ -79,6 +79,10 @@ __device__ __forceinline__ void argmax_better(float& bv, int& bi, float v, int i
 
 constexpr int kMatvecWaves = 16;   // 1024 threads
 
+// the launch shape of a decode Linear (matvec.hip: matvec_launch_shape, host): output columns per wave step R, chunk positions in flight U, the largest grid
+struct MatvecShape { int R, U, max_blocks; };
+MatvecShape matvec_launch_shape(int fmt, bool geglu, int N, bool argmax);
+
 template <int FMT, int U, int NR>
 struct WBuf
 {

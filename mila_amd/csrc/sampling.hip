@@ -98,6 +98,37 @@ __global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* 
     }
 }
 
+// argmax_final_advance_kernel for B independent rows, one workgroup per row: row b reduces the n partials at pv + b * row_floats (values, then kArgmaxBlocks floats on
+// the indices); a row whose active word is 0 keeps its token and its position
+__global__ __launch_bounds__(256) void argmax_rows_final_advance_kernel(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
+                                                                        const int32_t* __restrict__ active, int n, int row_floats)
+{
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const int b = blockIdx.x;
+    const float* pv = pv0 + (size_t)b * row_floats;
+    const int* pi = reinterpret_cast<const int*>(pv + kArgmaxBlocks);
+    float bv = -FLT_MAX;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += 256) better(bv, bi, pv[i], pi[i]);
+    wave_argmax(bv, bi);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0 && active[b] != 0)
+    {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
+        token_out[b] = (bi == 0x7fffffff) ? 0 : bi;
+        pos[b] += 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void advance_positions_rows_kernel(int32_t* __restrict__ pos, const int32_t* __restrict__ active, int B)
+{
+    const int b = threadIdx.x;
+    if (b < B && active[b] != 0) pos[b] += 1;
+}
+
 template <typename T>
 static int run_argmax(const T* logits, int32_t* token_out, int vocab, void* scratch, size_t scratch_bytes, hipStream_t s, const char* who)
 {
@@ -867,6 +898,28 @@ int mila_cdna4_sample_argmax_final_advance(int32_t* token_out, const void* scrat
     const int* pi = reinterpret_cast<const int*>(pv + kArgmaxBlocks);
     hipLaunchKernelGGL(argmax_final_advance_kernel, dim3(1), dim3(256), 0, as_stream(stream), pv, pi, blocks, token_out, position_dev, seq_dev, ring, ring_size);
     MILA_LAUNCH_CHECK("sample_argmax_final_advance");
+}
+
+// the rows twin: row b's partials at scratch + b * sample_scratch_bytes() (a matvec_rows lm_head launch with argmax_scratch), tokens and positions of the active rows only
+int mila_cdna4_sample_argmax_rows_final_advance(int32_t* token_out, const void* scratch, size_t scratch_bytes, int blocks, int32_t* positions_dev,
+                                                const int32_t* active_dev, int B, mila_stream_t stream)
+{
+    MILA_REQUIRE(token_out && scratch && positions_dev && active_dev, "sample_argmax_rows_final_advance: null pointer");
+    MILA_REQUIRE(B >= 1 && B <= 64, "sample_argmax_rows_final_advance: B=%d out of range (1 .. 64)", B);
+    MILA_REQUIRE(blocks > 0 && blocks <= kArgmaxBlocks, "sample_argmax_rows_final_advance: blocks %d out of range (1 .. %d)", blocks, kArgmaxBlocks);
+    const size_t per_row = (size_t)kArgmaxBlocks * 8;
+    if (scratch_bytes < per_row * B) return set_error(MILA_E_SCRATCH_TOO_SMALL, "sample_argmax_rows_final_advance: scratch %zu bytes < required %zu", scratch_bytes, per_row * B);
+    hipLaunchKernelGGL(argmax_rows_final_advance_kernel, dim3(B), dim3(256), 0, as_stream(stream), reinterpret_cast<const float*>(scratch), token_out, positions_dev, active_dev,
+                       blocks, (int)(per_row / sizeof(float)));
+    MILA_LAUNCH_CHECK("sample_argmax_rows_final_advance");
+}
+
+int mila_cdna4_advance_positions_rows(int32_t* positions_dev, const int32_t* active_dev, int B, mila_stream_t stream)
+{
+    MILA_REQUIRE(positions_dev && active_dev, "advance_positions_rows: null pointer");
+    MILA_REQUIRE(B >= 1 && B <= 64, "advance_positions_rows: B=%d out of range (1 .. 64)", B);
+    hipLaunchKernelGGL(advance_positions_rows_kernel, dim3(1), dim3(64), 0, as_stream(stream), positions_dev, active_dev, B);
+    MILA_LAUNCH_CHECK("advance_positions_rows");
 }
 
 int mila_cdna4_sample_argmax_bf16(const uint16_t* logits, int32_t* token_out, int vocab, void* scratch, size_t scratch_bytes,

@@ -84,11 +84,13 @@ class Gemma:
 
     MODES = {"reference": 0, "fused": 1, "graph": 2}
 
-    def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None, kv_fp8=False):
+    def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None, kv_fp8=False, max_batch=None):
         """device: HIP device ordinal; default = this process's LOCAL_RANK (one replica per GPU under torch.distributed.run).
         profile: synthetic-parameter multipliers {linear_gain, qk_norm_center, post_norm_center, layer_scalar, table_gain}
         (GemmaTransformer::SyntheticProfile; None = the unit-scale generator of SURVEY.md section 8d)
-        kv_fp8: PerChannelKvFp8<> on every layer -- e4m3 K / V + one fp32 scale per KV head per cached token (also: config["kv_fp8"] = 1)"""
+        kv_fp8: PerChannelKvFp8<> on every layer -- e4m3 K / V + one fp32 scale per KV head per cached token (also: config["kv_fp8"] = 1)
+        max_batch: GemmaConfig::max_batch (1 .. 4) through mila_gemma_create_rows -- independent sequences per decode step (prefill_row / decode_rows); None = the
+        one-sequence model of mila_gemma_create"""
         lib = load()
         if device is None:
             from .replicas import local_device
@@ -101,7 +103,13 @@ class Gemma:
             self.cfg["kv_fp8"] = 1
         c = GemmaConfigC(**self.cfg)
         self.vocab = self.cfg["vocab_size"]
-        self.h = lib.mila_gemma_create(POLICIES[policy], C.byref(c), max_seq, max_prefill, seed, device)
+        self.max_batch = 1 if max_batch is None else int(max_batch)
+        if max_batch is None:
+            self.h = lib.mila_gemma_create(POLICIES[policy], C.byref(c), max_seq, max_prefill, seed, device)
+        else:
+            lib.mila_gemma_create_rows.restype = C.c_void_p
+            lib.mila_gemma_create_rows.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int]
+            self.h = lib.mila_gemma_create_rows(POLICIES[policy], C.byref(c), max_seq, max_prefill, self.max_batch, seed, device)
         if not self.h:
             text = lib.mila_host_last_error().decode()
             raise (ValueError if text.startswith("invalid_argument") else RuntimeError)("mila_gemma_create: " + text)
@@ -236,6 +244,53 @@ class Gemma:
                                                      float(temperature), int(top_k), float(top_p), int(seed), out.ctypes.data))
         return out
 
+    # ---- batched decode: rows of independent sequences (max_batch > 1) ----
+    def prefill_row(self, b, tokens, offset=0):
+        """prefill `tokens` at positions offset .. into row b's KV caches (the B = 1 prefill on the selected cache row); the last position's logits"""
+        lib = load()
+        lib.mila_gemma_prefill_row.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        out = np.empty(self.vocab, dtype=np.float32)
+        _check(lib.mila_gemma_prefill_row(self.h, int(b), t.ctypes.data, t.size, int(offset), out.ctypes.data))
+        return out
+
+    def set_active(self, b, active, token=None):
+        """row b's active word (an inactive row keeps its token, its position and its caches through every step) and, when given, the token its next step embeds"""
+        lib = load()
+        lib.mila_gemma_set_active.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int32]
+        _check(lib.mila_gemma_set_active(self.h, int(b), int(bool(active)), -1 if token is None else int(token)))
+
+    def reset_row(self, b):
+        """forget row b: position 0, inactive"""
+        lib = load()
+        lib.mila_gemma_reset_row.argtypes = [C.c_void_p, C.c_int]
+        _check(lib.mila_gemma_reset_row(self.h, int(b)))
+
+    def decode_rows(self, B, max_position, mode="graph", greedy=True):
+        """one step over rows 0 .. B - 1, eager ("fused") or as a graph replay; greedy: the step ends with the rows sampler tail.  max_position: the largest
+        position among the active rows.  Returns (logits [B, vocab], tokens [B], positions [B]) as they stand AFTER the step."""
+        lib = load()
+        lib.mila_gemma_decode_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        logits, toks, pos = np.empty((B, self.vocab), dtype=np.float32), np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        _check(lib.mila_gemma_decode_rows(self.h, int(B), int(max_position), {"fused": 1, "graph": 2}[mode], int(bool(greedy)), logits.ctypes.data, toks.ctypes.data, pos.ctypes.data))
+        return logits, toks, pos
+
+    def rows_graph_info(self):
+        """{"captures": captures of the rows graph so far, "nodes": kernel nodes of the captured rows step}"""
+        lib = load()
+        lib.mila_gemma_rows_graph_info.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_int64 * 2)()
+        _check(lib.mila_gemma_rows_graph_info(self.h, out))
+        return {"captures": out[0], "nodes": out[1]}
+
+    def time_decode_rows(self, B, start_position, steps, warmup):
+        """`steps` greedy graph replays of a B-row step, every row active from start_position"""
+        lib = load()
+        lib.mila_gemma_time_decode_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        out = (C.c_double * 2)()
+        _check(lib.mila_gemma_time_decode_rows(self.h, int(B), int(start_position), int(steps), int(warmup), out))
+        return {"wall_ms_per_step": out[0], "device_ms_per_step": out[1]}
+
     def time_decode(self, start_position, steps, warmup, mode="graph"):
         out = (C.c_double * 2)()
         _check(load().mila_gemma_time_decode(self.h, start_position, steps, warmup, self.MODES[mode], out))
@@ -316,7 +371,7 @@ class GemmaModel:
         return cls(h, device)
 
     @classmethod
-    def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0, kv_fp8=False):
+    def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0, kv_fp8=False, max_batch=None):
         lib = cls._bind()
         cfg = dict(GEMMA4_12B if config is None else config)
         cfg.setdefault("bounded_local_kv", 0)
@@ -327,7 +382,12 @@ class GemmaModel:
         p = None
         if profile is not None:
             p = (C.c_float * 5)(*[float(profile[k]) for k in ("linear_gain", "qk_norm_center", "post_norm_center", "layer_scalar", "table_gain")])
-        h = lib.mila_gemma_model_synthetic(POLICIES[policy], C.byref(c), context, prefill_chunk, seed, p, device)
+        if max_batch is None:
+            h = lib.mila_gemma_model_synthetic(POLICIES[policy], C.byref(c), context, prefill_chunk, seed, p, device)
+        else:      # GemmaModelConfig::withMaxBatch: a model generate_batch() can run on
+            lib.mila_gemma_model_synthetic_rows.restype = C.c_void_p
+            lib.mila_gemma_model_synthetic_rows.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_int]
+            h = lib.mila_gemma_model_synthetic_rows(POLICIES[policy], C.byref(c), context, prefill_chunk, int(max_batch), seed, p, device)
         if not h:
             cls._raise(lib, "GemmaModel.synthetic")
         return cls(h, device)
@@ -346,6 +406,23 @@ class GemmaModel:
                                              float(temperature), int(top_k), float(top_p), -1 if seed is None else int(seed), out.ctypes.data, len(out), C.byref(n), C.byref(status),
                                              C.byref(reused), -1 if cancel_after is None else int(cancel_after)))
         return out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], reused.value
+
+    def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0):
+        """GemmaModel::generateBatch: up to max_batch prompts at once, prompt b in row b -> [(tokens, finish reason)] per prompt, by generate()'s rules.  Row b samples
+        from its own generator seeded seed + b."""
+        lib = load()
+        lib.mila_gemma_model_generate_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64,
+                                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if len(prompts) else np.zeros(0), dtype=np.int32)
+        offs = np.ascontiguousarray(np.cumsum([0] + [len(p) for p in prompts]), dtype=np.int64)
+        st = np.ascontiguousarray(list(stop_tokens), dtype=np.int32)
+        cap = int(max_new_tokens) if max_new_tokens is not None else 1 << 16
+        out = np.zeros((max(len(prompts), 1), max(cap, 1)), dtype=np.int32)
+        counts, status = np.zeros(max(len(prompts), 1), dtype=np.int64), np.zeros(max(len(prompts), 1), dtype=np.int32)
+        _check(lib.mila_gemma_model_generate_rows(self.h, flat.ctypes.data, offs.ctypes.data, len(prompts), -1 if max_new_tokens is None else int(max_new_tokens),
+                                                  st.ctypes.data if len(st) else None, len(st), float(temperature), int(top_k), float(top_p), int(seed), out.ctypes.data,
+                                                  out.shape[1], counts.ctypes.data, status.ctypes.data))
+        return [(out[b, :min(int(counts[b]), out.shape[1])].tolist(), GENERATE_STATUS[int(status[b])]) for b in range(len(prompts))]
 
     def close(self):
         if self.h:

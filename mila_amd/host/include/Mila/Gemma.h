@@ -36,6 +36,7 @@ namespace Mila::Dnn
         float rms_norm_eps = 1e-6f, rope_theta_local = 10000.0f, rope_theta_global = 1000000.0f, final_logit_softcapping = 30.0f;
         bool bounded_local_kv = false;   ///< SlidingWindowKvCache on the sliding-window layers (ring of window + chunk - 1 rows)
         bool kv_fp8 = false;             ///< PerChannelKvFp8<> on every layer: e4m3 K / V + one fp32 scale per KV head per cached token, (HS + 4) / (2 HS) of the bf16 bytes
+        dim_t max_batch = 1;             ///< independent sequences a decode step can carry (1 .. 4): KV caches, decode buffers, logits and position words per row
 
         bool isGlobalLayer( dim_t i ) const { return ( i + 1 ) % sliding_window_pattern == 0; }   // Gemma.Config.ixx:504-507
         dim_t headDim( bool g ) const { return g ? global_head_dim : head_dim; }
@@ -54,6 +55,10 @@ namespace Mila::Dnn
                 throw std::invalid_argument( "GemmaConfig: num_heads must be a multiple of the KV head counts" );
             if ( embedding_dim % 128 != 0 || hidden_dim % 128 != 0 || qWidth( false ) % 128 != 0 || qWidth( true ) % 128 != 0 )
                 throw std::invalid_argument( "GemmaConfig: feature widths must be multiples of 128 (FP4 group size)" );
+            if ( max_batch < 1 || max_batch > 4 )
+                throw std::invalid_argument( "GemmaConfig: max_batch " + std::to_string( max_batch ) + " outside 1 .. 4 (the rows kernels keep every row's x in LDS)" );
+            if ( max_batch > 1 && kv_fp8 ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with kv_fp8 (the FP8 KV cache's fused append is B = 1)" );
+            if ( max_batch > 1 && bounded_local_kv ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with bounded_local_kv (the ring needs a rewind rule per row)" );
             if ( kv_fp8 )
             {
                 if ( bounded_local_kv ) throw std::invalid_argument( "GemmaConfig: kv_fp8 cannot be combined with bounded_local_kv (the FP8 KV cache is unbounded)" );
@@ -138,6 +143,7 @@ namespace Mila::Dnn
         ~GemmaTransformer()
         {
             destroyGraph();
+            destroyGraphRows();
             for ( auto& e : ov_ev_ ) if ( e ) (void)hipEventDestroy( e );
             if ( ov_stream_ ) (void)hipStreamDestroy( ov_stream_ );
         }
@@ -159,6 +165,7 @@ namespace Mila::Dnn
         void initSynthetic( uint64_t seed, const SyntheticProfile& pr = SyntheticProfile{} )
         {
             destroyGraph();   // layer scalars are baked into the captured launches
+            destroyGraphRows();
             // the staging buffer holds the largest matrix of the model: the table, fc_gate_up, or -- on geometries whose attention is wider than the stream -- a packed qkv
             const dim_t attn_w = cfg_.num_heads * std::max( cfg_.head_dim, cfg_.global_head_dim );
             const dim_t qkv_w = attn_w + 2 * std::max( cfg_.num_kv_heads * cfg_.head_dim, cfg_.num_global_kv_heads * cfg_.global_head_dim );
@@ -337,6 +344,115 @@ namespace Mila::Dnn
             hipCheck( hipGraphLaunch( graph_exec_, reinterpret_cast<hipStream_t>( ctx_->getStream() ) ), "hipGraphLaunch" );
         }
         LogitsTensor& logits() { return *logits_; }
+
+        // ------------------------------------------------------------------------------------
+        // batched decode (GemmaConfig::max_batch > 1): up to four INDEPENDENT sequences per step, row b at its own position rows_->pos[ b ], on its own KV caches.
+        // A step is enqueueFusedStep's launch sequence on the rows entries (matvec_rows, fused_attn_decode_rows_bf16): six launches per layer, the weights streamed
+        // once for all rows, always in the device-position form.  Row b's logits are bit-identical to the same sequence run alone through decodeFused(), as long as
+        // both runs are in the same live-length bucket (mila_cdna4.h: fused_attn_decode_rows_bf16).
+        // ------------------------------------------------------------------------------------
+        dim_t maxBatch() const noexcept { return cfg_.max_batch; }
+        /// prefill `n` tokens at positions offset .. into row b's caches through the B = 1 prefill (cache-row selection; no prefill kernel knows about rows); row b's
+        /// logits and position word follow.  The row's first decode token is the caller's to set (setRowToken).
+        LogitsTensor& prefillRow( int b, const TokenTensor& tokens, dim_t n, dim_t offset = 0 )
+        {
+            requireRows( b );
+            for ( auto& L : layers_ ) L.selectCacheRow( b );
+            if ( n <= 0 ) throw std::invalid_argument( "GemmaTransformer::prefillRow: empty prompt" );
+            try
+            {
+                for ( dim_t p0 = 0; p0 < n; p0 += max_prefill_ )      // chunks of the built prefill size, as prefillFrom() does
+                {
+                    const dim_t c = std::min( max_prefill_, n - p0 );
+                    prefill( tokens.slice( static_cast<size_t>( p0 ), shape_t{ 1, c } ), c, offset + p0 );
+                }
+            }
+            catch ( ... ) { for ( auto& L : layers_ ) L.selectCacheRow( 0 ); throw; }
+            for ( auto& L : layers_ ) L.selectCacheRow( 0 );
+            Compute::rocmCheck( mila_cdna4_memcpy_d2d( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, logits_->data(), static_cast<size_t>( cfg_.vocab_size ) * 4, ctx_->getStream() ) );
+            setRowWord( rows_->pos->data(), b, static_cast<int32_t>( offset + n ) );
+            return *logits_;
+        }
+        /// forget row b: position 0, inactive (its caches are overwritten positionally by the next prefillRow)
+        void resetRow( int b ) { requireRows( b ); setRowWord( rows_->pos->data(), b, 0 ); setRowWord( rows_->active->data(), b, 0 ); }
+        /// rewindKvCache for one row: row b goes on from `position`, given that `written` positions were appended to it; its caches are overwritten positionally.
+        /// false when the request is out of range (rows live on unbounded caches: no ring to refuse)
+        bool rewindKvCacheRow( int b, dim_t position, dim_t written )
+        {
+            requireRows( b );
+            if ( position < 0 || position > written || written > max_seq_ ) return false;
+            setRowWord( rows_->pos->data(), b, static_cast<int32_t>( position ) );
+            return true;
+        }
+        void setRowActive( int b, bool on ) { requireRows( b ); setRowWord( rows_->active->data(), b, on ? 1 : 0 ); }
+        void setRowToken( int b, int32_t token ) { requireRows( b ); setRowWord( rows_->tok->data(), b, token ); }
+        void setRowPosition( int b, dim_t position ) { requireRows( b ); checkPosition( position, 1 ); setRowWord( rows_->pos->data(), b, static_cast<int32_t>( position ) ); }
+        /// row b's next token from row b's logits, into the rows token buffer: the greedy sampler, or the radix pipeline at the caller's draw r (the sampler
+        /// generate() uses, on the model-owned one-row workspaces)
+        void sampleRowGreedy( int b )
+        {
+            requireRows( b );
+            Compute::rocmCheck( mila_cdna4_sample_argmax_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
+                                                               sample_scratch_->data(), sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
+        }
+        void sampleRowStochastic( int b, const SamplingParams& sp, float r )
+        {
+            if ( sp.temperature <= 0.0f ) { sampleRowGreedy( b ); return; }
+            requireRows( b );
+            Compute::rocmCheck( mila_cdna4_sample_radix_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
+                                                              cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r, radix_scratch_->data(), radix_scratch_->sizeInBytes(),
+                                                              ctx_->getStream() ) );
+        }
+        LogitsTensor& rowsLogits() { requireRows( 0 ); return *rows_->logits; }
+        TokenTensor& rowsTokens() { requireRows( 0 ); return *rows_->tok; }
+        TokenTensor& rowsPositions() { requireRows( 0 ); return *rows_->pos; }
+
+        /// one eager step over rows 0 .. B - 1 (2 <= B <= max_batch): the launches a captured rows step holds.  max_position: the largest position among the active
+        /// rows (its live-length bucket shapes the attention launches).  greedy: the step ends with the rows sampler tail (next token and position bump of every
+        /// active row); otherwise it ends at the logits and the position bump alone.
+        void decodeRows( int B, dim_t max_position, bool greedy )
+        {
+            checkRowsStep( B, max_position );
+            enqueueRowsStepAndTail( B, bandBucket( max_position ), greedy );
+        }
+        void captureGraphRows( int B, dim_t max_position, bool greedy )
+        {
+            checkRowsStep( B, max_position );
+            Compute::TraceRange tr( "gemma.captureGraphRows" );
+            destroyGraphRows();
+            hipStream_t s = reinterpret_cast<hipStream_t>( ctx_->getStream() );
+            ctx_->synchronize();
+            hipCheck( hipStreamBeginCapture( s, hipStreamCaptureModeThreadLocal ), "hipStreamBeginCapture" );
+            hipGraph_t g = nullptr;
+            const dim_t band = bandBucket( max_position );
+            try { enqueueRowsStepAndTail( B, band, greedy ); }      // one linear chain on one stream, like the one-row graph
+            catch ( ... ) { (void)hipStreamEndCapture( s, &g ); if ( g ) (void)hipGraphDestroy( g ); throw; }
+            hipCheck( hipStreamEndCapture( s, &g ), "hipStreamEndCapture" );
+            rows_graph_ = g;
+            const hipError_t e = hipGraphInstantiate( &rows_graph_exec_, rows_graph_, nullptr, nullptr, 0 );
+            if ( e != hipSuccess ) { rows_graph_exec_ = nullptr; destroyGraphRows(); hipCheck( e, "hipGraphInstantiate" ); }
+            rows_captured_B_ = B; rows_captured_greedy_ = greedy; rows_captured_band_ = band;
+            ++rows_graph_captures_;
+        }
+        /// capture on first use and whenever the step changes: another row count, sampler tail, or the live-length bucket of the largest active row
+        void ensureGraphRows( int B, dim_t max_position, bool greedy )
+        {
+            if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) )
+                captureGraphRows( B, max_position, greedy );
+        }
+        void replayGraphRows()
+        {
+            if ( !rows_graph_exec_ ) throw std::runtime_error( "GemmaTransformer::replayGraphRows: captureGraphRows() first" );
+            hipCheck( hipGraphLaunch( rows_graph_exec_, reinterpret_cast<hipStream_t>( ctx_->getStream() ) ), "hipGraphLaunch" );
+        }
+        size_t graphRowsCaptureCount() const noexcept { return rows_graph_captures_; }
+        size_t graphRowsNodeCount() const
+        {
+            if ( !rows_graph_ ) return 0;
+            size_t n = 0;
+            hipCheck( hipGraphGetNodes( rows_graph_, nullptr, &n ), "hipGraphGetNodes" );
+            return n;
+        }
 
         /// greedy device sampler: token <- argmax(logits); the token never leaves the device
         /// (GemmaModel::enqueueSampleNext, Models/GemmaModel.ixx:568)
@@ -579,6 +695,7 @@ namespace Mila::Dnn
             attn_partials_ = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( ( attnScratchBytes() + 3 ) / 4 ) } );
             // the radix sampler's workspace: model-owned for the same reason (a captured stochastic step's nodes point into it)
             radix_scratch_ = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( ( mila_cdna4_sample_radix_scratch_bytes( (int)cfg_.vocab_size ) + 3 ) / 4 ) } );
+            if ( cfg_.max_batch > 1 ) buildRows();
             ctx_->synchronize();
         }
 
@@ -879,6 +996,159 @@ namespace Mila::Dnn
             }
         }
 
+
+        // ---- rows step ------------------------------------------------------------------------------------
+        mila_matvec_rows_args rowsArgs( const mila_fused_matvec_args& a, int B, dim_t x_stride, dim_t y_stride, dim_t res_stride = 0, dim_t res_out_stride = 0 ) const
+        {
+            mila_matvec_rows_args r{};
+            r.a = a; r.bias = nullptr; r.rows = B;
+            r.x_stride = x_stride; r.y_stride = y_stride; r.res_stride = res_stride; r.res_out_stride = res_out_stride;
+            return r;
+        }
+        /// enqueueFusedStep for rows 0 .. B - 1: the same launches on the rows entries.  max_len: the live-length bound of the captured band bucket
+        void enqueueFusedStepRows( int B, int max_len, int* sampler_partials )
+        {
+            mila_stream_t st = ctx_->getStream();
+            auto& R = *rows_;
+            const dim_t D = cfg_.embedding_dim, F = cfg_.hidden_dim, PK = std::max( cfg_.packedQkvWidth( false ), cfg_.packedQkvWidth( true ) );
+            embed( R.tok->data(), B, *R.hidden[ 0 ] );
+            const uint16_t* cur = R.hidden[ 0 ]->data();
+            int next = 1;
+            const Layer* prev = nullptr;
+            for ( auto& L : layers_ )
+            {
+                const bool g = L.global;
+                const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.numKvHeads( g ), HD = (int)cfg_.headDim( g );
+                // 1. [tail of previous layer] + input_norm + qkv projection; the rows of the packed projection are PK elements apart
+                auto a = baseArgs( *L.qkv_proj, R.qkv->data(), prev ? R.down->data() : cur );
+                a.norm_w = L.input_norm->getWeight()->data();
+                if ( prev ) { a.post_w = prev->post_ffn_norm->getWeight()->data(); a.res = R.res1->data(); a.res_out = R.hidden[ next ]->data(); a.post_scale = prev->layer_scalar; }
+                auto r = rowsArgs( a, B, D, PK, D, D );
+                Compute::rocmCheck( mila_cdna4_matvec_rows( &r, st ) );
+                if ( prev ) { cur = R.hidden[ next ]->data(); next = ( next == 1 ) ? 2 : 1; }
+                // 2+3. q/k/v norms + RoPE + KV append + flash-decode, row b at pos[ b ] on its own caches (+ combine); output rows NH * HD apart
+                const uint16_t* qp = R.qkv->data();
+                const uint16_t* kp = qp + (size_t)NH * HD;
+                const uint16_t* vp = g ? kp : kp + (size_t)NKV * HD;
+                Compute::rocmCheck( mila_cdna4_fused_attn_decode_rows_bf16( R.attn->data(), L.keyCacheRows(), L.valueCacheRows(), qp, kp, vp, (int64_t)PK, L.q_norm->getWeight()->data(),
+                                                                            L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(),
+                                                                            R.attn_partials->data(), R.attn_partials->sizeInBytes(), B, NH, NKV, HD, (int)L.cacheCapacity(), R.pos->data(),
+                                                                            max_len, (int)cfg_.windowFor( g ), L.attentionScale(), cfg_.rms_norm_eps, st ) );
+                // 4. o_proj
+                L.o_proj->getOperation().matvecRows( R.o->data(), R.attn->data(), B, (int64_t)NH * HD, D );
+                // 5. post_attn_norm + residual + pre_ffn_norm + gate_up + GeGLU
+                a = baseArgs( *L.fc_gate_up, R.act->data(), R.o->data() );
+                a.N = (int)F; a.geglu = 1;
+                a.norm_w = L.pre_ffn_norm->getWeight()->data(); a.post_w = L.post_attn_norm->getWeight()->data();
+                a.res = cur; a.res_out = R.res1->data();
+                r = rowsArgs( a, B, D, F, D, D );
+                Compute::rocmCheck( mila_cdna4_matvec_rows( &r, st ) );
+                // 6. fc_down
+                L.fc_down->getOperation().matvecRows( R.down->data(), R.act->data(), B, F, D );
+                prev = &L;
+            }
+            // tail of the last layer + final norm + lm_head (fp32 logits, one set of sampler partials per row) in one launch
+            mila_fused_matvec_args a{};
+            a.y = reinterpret_cast<uint16_t*>( R.logits->data() ); a.x = R.down->data(); a.W = lm_head_->getWeight().rawData();
+            a.scales = nullptr;
+            if constexpr ( kTableFmt != 0 ) a.scales = lm_head_->getWeightScale()->data();
+            a.norm_w = final_norm_->getWeight()->data(); a.post_w = prev->post_ffn_norm->getWeight()->data();
+            a.res = R.res1->data(); a.res_out = R.hidden[ next ]->data(); a.post_scale = prev->layer_scalar; a.eps = cfg_.rms_norm_eps;
+            a.fmt = kTableFmt; a.K = (int)D; a.N = (int)cfg_.vocab_size; a.group = 0; a.geglu = 0; a.f32_out = 1;
+            if ( sampler_partials ) { a.argmax_scratch = R.sample_scratch->data(); a.argmax_scratch_bytes = R.sample_scratch->sizeInBytes(); a.argmax_blocks = sampler_partials; }
+            auto r = rowsArgs( a, B, D, cfg_.vocab_size, D, D );
+            Compute::rocmCheck( mila_cdna4_matvec_rows( &r, st ) );
+        }
+        void enqueueRowsStepAndTail( int B, dim_t band, bool greedy )
+        {
+            int partials = 0;
+            enqueueFusedStepRows( B, static_cast<int>( band ), greedy ? &partials : nullptr );
+            auto& R = *rows_;
+            if ( greedy )
+                Compute::rocmCheck( mila_cdna4_sample_argmax_rows_final_advance( R.tok->data(), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(), partials, R.pos->data(),
+                                                                                 R.active->data(), B, ctx_->getStream() ) );
+            else
+                Compute::rocmCheck( mila_cdna4_advance_positions_rows( R.pos->data(), R.active->data(), B, ctx_->getStream() ) );
+        }
+        void requireRows( int b ) const
+        {
+            if ( !rows_ ) throw std::logic_error( "GemmaTransformer: the rows interface needs GemmaConfig::max_batch > 1" );
+            if ( b < 0 || b >= cfg_.max_batch ) throw std::invalid_argument( "GemmaTransformer: row " + std::to_string( b ) + " outside max_batch " + std::to_string( cfg_.max_batch ) );
+        }
+        void checkRowsStep( int B, dim_t max_position ) const
+        {
+            requireRows( 0 );
+            if ( B < 2 || B > cfg_.max_batch ) throw std::invalid_argument( "GemmaTransformer: a rows step takes 2 .. max_batch rows (got " + std::to_string( B ) + ")" );
+            checkPosition( max_position, 1 );
+        }
+        void setRowWord( int32_t* words, int b, int32_t v )
+        {
+            Compute::rocmCheck( mila_cdna4_memcpy_h2d( words + b, &v, 4, ctx_->getStream() ) );
+            ctx_->synchronize();
+        }
+        void destroyGraphRows()
+        {
+            if ( rows_graph_exec_ ) { (void)hipGraphExecDestroy( rows_graph_exec_ ); rows_graph_exec_ = nullptr; }
+            if ( rows_graph_ ) { (void)hipGraphDestroy( rows_graph_ ); rows_graph_ = nullptr; }
+        }
+        /// the decode-role buffers of a rows step, [max_batch, width] each; allocated only when max_batch > 1, so a max_batch == 1 model is byte for byte what it was
+        struct RowsState
+        {
+            std::unique_ptr<TensorType> qkv, attn, o, down, act, res1, hidden[ 3 ];
+            std::unique_ptr<LogitsTensor> logits, sample_scratch, attn_partials;
+            std::unique_ptr<TokenTensor> pos, tok, active;
+        };
+        void buildRows()
+        {
+            const dim_t B = cfg_.max_batch, D = cfg_.embedding_dim;
+            const auto dev = ctx_->getDeviceId();
+            for ( auto& L : layers_ ) L.setCacheRows( static_cast<int>( B ) );
+            rows_ = std::make_unique<RowsState>();
+            auto& R = *rows_;
+            R.qkv = std::make_unique<TensorType>( dev, shape_t{ B, std::max( cfg_.packedQkvWidth( false ), cfg_.packedQkvWidth( true ) ) } );
+            R.attn = std::make_unique<TensorType>( dev, shape_t{ B, std::max( cfg_.qWidth( false ), cfg_.qWidth( true ) ) } );
+            R.o = std::make_unique<TensorType>( dev, shape_t{ B, D } );
+            R.down = std::make_unique<TensorType>( dev, shape_t{ B, D } );
+            R.act = std::make_unique<TensorType>( dev, shape_t{ B, cfg_.hidden_dim } );
+            R.res1 = std::make_unique<TensorType>( dev, shape_t{ B, D } );
+            for ( auto& h : R.hidden ) h = std::make_unique<TensorType>( dev, shape_t{ B, 1, D } );
+            R.logits = std::make_unique<LogitsTensor>( dev, shape_t{ B, 1, cfg_.vocab_size } );
+            R.sample_scratch = std::make_unique<LogitsTensor>( dev, shape_t{ B, static_cast<dim_t>( mila_cdna4_sample_scratch_bytes() / 4 ) } );
+            R.attn_partials = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( ( rowsAttnScratchBytes() + 3 ) / 4 ) } );
+            R.pos = std::make_unique<TokenTensor>( dev, shape_t{ B } );
+            R.tok = std::make_unique<TokenTensor>( dev, shape_t{ B } );
+            R.active = std::make_unique<TokenTensor>( dev, shape_t{ B } );
+            // every row starts as a valid, inactive sequence at position 0 with token 0: a row that was never admitted still rides through a step's launches
+            for ( auto* t : { R.pos.get(), R.tok.get(), R.active.get() } ) Compute::rocmCheck( mila_cdna4_memset_zero( t->data(), t->sizeInBytes(), ctx_->getStream() ) );
+            for ( auto* t : { R.qkv.get(), R.attn.get(), R.o.get(), R.down.get(), R.act.get(), R.res1.get() } ) Compute::rocmCheck( mila_cdna4_memset_zero( t->data(), t->sizeInBytes(), ctx_->getStream() ) );
+        }
+        size_t rowsAttnScratchBytes() const
+        {
+            const int B = static_cast<int>( cfg_.max_batch );
+            return std::max( mila_cdna4_attn_decode_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.head_dim ), mila_cdna4_attn_decode_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.global_head_dim ) );
+        }
+        size_t rowsStateBytes() const
+        {
+            if ( !rows_ ) return 0;
+            size_t b = 0;
+            auto& R = *rows_;
+            for ( const auto* t : { R.qkv.get(), R.attn.get(), R.o.get(), R.down.get(), R.act.get(), R.res1.get(), R.hidden[ 0 ].get(), R.hidden[ 1 ].get(), R.hidden[ 2 ].get() } ) b += tensorBytes( t );
+            for ( const auto* t : { R.logits.get(), R.sample_scratch.get(), R.attn_partials.get() } ) b += tensorBytes( t );
+            for ( const auto* t : { R.pos.get(), R.tok.get(), R.active.get() } ) b += tensorBytes( t );
+            return b;
+        }
+        /// the same from the configuration alone, plus the cache rows beyond the first of every layer
+        size_t requiredRowsStateBytes() const
+        {
+            if ( cfg_.max_batch <= 1 ) return 0;
+            const size_t B = static_cast<size_t>( cfg_.max_batch ), D = static_cast<size_t>( cfg_.embedding_dim );
+            const size_t maxq = static_cast<size_t>( std::max( cfg_.qWidth( false ), cfg_.qWidth( true ) ) ), maxpacked = static_cast<size_t>( std::max( cfg_.packedQkvWidth( false ), cfg_.packedQkvWidth( true ) ) );
+            size_t b = B * ( maxpacked + maxq + 3 * D + static_cast<size_t>( cfg_.hidden_dim ) + 3 * D ) * 2;
+            b += B * static_cast<size_t>( cfg_.vocab_size ) * 4 + B * ( ( mila_cdna4_sample_scratch_bytes() / 4 ) * 4 ) + ( ( rowsAttnScratchBytes() + 3 ) / 4 ) * 4 + 3 * B * 4;
+            for ( auto& L : layers_ ) b += ( B - 1 ) * 2 * static_cast<size_t>( cfg_.kvWidth( L.global ) ) * static_cast<size_t>( L.cacheCapacity() ) * 2;
+            return b;
+        }
+
     public:
         // ------------------------------------------------------------------------------------
         // weight ingestion.  Tensor vocabulary = the reference's flat names (the root's own name dropped,
@@ -1140,6 +1410,7 @@ namespace Mila::Dnn
                                     pf_q8_[ 1 ].get(), f_qkv_.get(), f_q_.get(), f_o_.get(), f_down_.get(), f_act_.get(), ov_qkv_.get(), ov_o_.get(), ov_gate_up_.get() } ) b += tensorBytes( t );
             for ( const auto* t : { logits_.get(), sample_scratch_.get(), attn_partials_.get(), radix_scratch_.get(), pf_ts_[ 0 ].get(), pf_ts_[ 1 ].get() } ) b += tensorBytes( t );
             b += tensorBytes( pos_dev_.get() );
+            b += rowsStateBytes();
             return b;
         }
         size_t requiredOwnStateBytes() const
@@ -1159,6 +1430,7 @@ namespace Mila::Dnn
             b += ( ( mila_cdna4_sample_radix_scratch_bytes( (int)cfg_.vocab_size ) + 3 ) / 4 ) * 4;      // the radix sampler's workspace
             if ( kFmt != 0 ) b += 2 * P * 4;
             b += 4;                                                                                          // the device position word
+            b += requiredRowsStateBytes();
             return b;
         }
     public:
@@ -1200,6 +1472,13 @@ namespace Mila::Dnn
         std::unique_ptr<TensorType> pf_q8_[ 2 ];          // [1, P, D / 2] bf16 elements = P * D bytes of e4m3
         std::unique_ptr<LogitsTensor> pf_ts_[ 2 ];        // [P] fp32 per-token scales
         const uint16_t* cur_hidden_{ nullptr };
+        std::unique_ptr<RowsState> rows_;               // max_batch > 1 only
+        hipGraph_t rows_graph_{ nullptr };
+        hipGraphExec_t rows_graph_exec_{ nullptr };
+        int rows_captured_B_{ 0 };
+        bool rows_captured_greedy_{ false };
+        dim_t rows_captured_band_{ 0 };
+        size_t rows_graph_captures_{ 0 };
         hipGraph_t graph_{ nullptr };
         hipGraphExec_t graph_exec_{ nullptr };
         const int32_t* captured_token_{ nullptr };      // what the captured graph was built for: ensureGraph() re-captures on a mismatch

@@ -71,6 +71,8 @@ namespace Mila::Dnn
         /// MI355X deployment knobs (no reference counterpart: a 12 GB card always chunks and always bounds the ring)
         GemmaModelConfig& withPrefillChunk( dim_t chunk ) { prefill_chunk_ = chunk; return *this; }          ///< 0 = min(context, 2048)
         GemmaModelConfig& withBoundedLocalKv( bool on ) { bounded_local_kv_ = on; return *this; }            ///< SlidingWindowKvCache on the sliding-window layers
+        GemmaModelConfig& withMaxBatch( dim_t n ) { max_batch_ = n; return *this; }                           ///< GemmaConfig::max_batch: sequences per decode step (generateBatch), 1 .. 4
+        dim_t maxBatch() const noexcept { return max_batch_; }
         GemmaModelConfig& withKvFp8( bool on ) { kv_fp8_ = on; return *this; }                               ///< PerChannelKvFp8<> on every layer (GemmaConfig::kv_fp8), under any weight policy
         dim_t getContextLength() const noexcept { return context_length_; }
         WeightQuantization getWeightQuantization() const noexcept { return weight_quantization_; }
@@ -79,7 +81,7 @@ namespace Mila::Dnn
         bool boundedLocalKv() const noexcept { return bounded_local_kv_; }
         bool kvFp8() const noexcept { return kv_fp8_; }
     private:
-        dim_t context_length_{ 0 }, prefill_chunk_{ 0 };
+        dim_t context_length_{ 0 }, prefill_chunk_{ 0 }, max_batch_{ 1 };
         WeightQuantization weight_quantization_{ WeightQuantization::None };
         KvCacheCompression kv_cache_compression_{ KvCacheCompression::None };
         bool bounded_local_kv_{ false }, kv_fp8_{ false };
@@ -140,6 +142,7 @@ namespace Mila::Dnn
                         throw std::invalid_argument( "GemmaModel::fromPretrained: context_length " + std::to_string( model_config.getContextLength() ) + " exceeds trained max_seq_len " + std::to_string( md.max_seq_length ) );
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
                     cfg.kv_fp8 = model_config.kvFp8();
+                    cfg.max_batch = model_config.maxBatch();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
                     net->loadPretrained( path );
                     return std::unique_ptr<GemmaModel>( new GemmaModel( Network( std::move( net ) ), cfg, model_config, md ) );
@@ -155,6 +158,7 @@ namespace Mila::Dnn
                     GemmaConfig cfg = network_config;
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
                     cfg.kv_fp8 = model_config.kvFp8();
+                    cfg.max_batch = model_config.maxBatch();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
                     typename Net<TWeightQuantization>::SyntheticProfile p;
                     p.linear_gain = profile.linear_gain; p.qk_norm_center = profile.qk_norm_center; p.post_norm_center = profile.post_norm_center; p.layer_scalar = profile.layer_scalar; p.table_gain = profile.table_gain;
@@ -211,7 +215,105 @@ namespace Mila::Dnn
             }, network_ );
         }
 
+        /// generate() for up to max_batch independent requests at once (GemmaModelConfig::withMaxBatch > 1): prompt b runs in row b, each at its own position, the
+        /// weights streamed once per step for all of them.  on_token( row, token ) as generate()'s on_token; one GenerateStatus per prompt, by generate()'s rules (stop
+        /// token, max_new_tokens, context limit -- the parameters are shared by the rows).  A plain step loop: every step replays the rows graph, reads the rows' tokens
+        /// back and retires finished rows by clearing their active word (a retired row stays frozen); no decode-ahead yet.  Greedy: the tokens generate() gives for each
+        /// prompt alone.  Stochastic: row b samples with the radix sampler from its own generator seeded seed + b, so a one-prompt batch with seed s gives generate()'s
+        /// tokens after seedSampler( s ).  The prompt-prefix reuse of generate() is dropped: the history is cleared.
+        [[nodiscard]] std::vector<GenerateStatus> generateBatch( std::span<const std::vector<int32_t>> prompts, const std::function<void( int, int32_t )>& on_token,
+                                                                 const GenerateParams& params = {}, uint64_t seed = 0 )
+        {
+            return std::visit( [&]( auto& net )
+            {
+                kv_token_history_.clear();      // row 0's caches are overwritten; whatever happens below, nothing is left to reuse
+                last_reuse_ = 0;
+                try { return onGeneratingBatch( *net, prompts, on_token, params, seed ); }
+                catch ( const std::invalid_argument& ) { throw; }
+                catch ( ... ) { try { net->context()->synchronize(); } catch ( ... ) {} throw; }
+            }, network_ );
+        }
+
     private:
+        template<typename TNet>
+        std::vector<GenerateStatus> onGeneratingBatch( TNet& net, std::span<const std::vector<int32_t>> prompts, const std::function<void( int, int32_t )>& on_token,
+                                                       const GenerateParams& params, uint64_t seed )
+        {
+            Compute::TraceRange tr( "GemmaModel.generateBatch" );
+            const int n = static_cast<int>( prompts.size() );
+            if ( net.maxBatch() < 2 ) throw std::invalid_argument( "GemmaModel::generateBatch: the model was built for one sequence (GemmaModelConfig::withMaxBatch)" );
+            if ( n < 1 || n > net.maxBatch() ) throw std::invalid_argument( "GemmaModel::generateBatch: " + std::to_string( n ) + " prompts for max_batch " + std::to_string( net.maxBatch() ) );
+            for ( auto& prompt : prompts )
+            {
+                if ( prompt.empty() ) throw std::invalid_argument( "GemmaModel::generateBatch: empty prompt" );
+                if ( prompt.size() > static_cast<size_t>( contextLength() ) ) throw std::invalid_argument( "GemmaModel::generateBatch: a prompt exceeds the deployment context length" );
+                for ( int32_t t : prompt )
+                    if ( t < 0 || t >= vocabSize() ) throw std::invalid_argument( "GemmaModel::generateBatch: token id " + std::to_string( t ) + " outside the vocabulary" );
+            }
+            std::unordered_set<int32_t> stop_ids;
+            if ( params.stop_tokens.empty() ) stop_ids = stopTokens();
+            else stop_ids.insert( params.stop_tokens.begin(), params.stop_tokens.end() );
+            const bool greedy = isGreedy( params.sampling );
+            typename TNet::SamplingParams sp; sp.temperature = params.sampling.temperature; sp.top_k = params.sampling.top_k; sp.top_p = params.sampling.top_p;
+            std::vector<std::mt19937_64> rng;
+            for ( int b = 0; b < n; ++b ) rng.emplace_back( seed + static_cast<uint64_t>( b ) );
+            auto draw = [&]( int b ) { return std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng[ static_cast<size_t>( b ) ] ); };
+            auto sampleRow = [&]( int b ) { if ( greedy ) net.sampleRowGreedy( b ); else net.sampleRowStochastic( b, sp, draw( b ) ); };
+            auto* ctx = net.context();
+            const int B = std::max( 2, n );      // a rows step carries at least two rows; a row without a prompt stays inactive
+            for ( int b = 0; b < static_cast<int>( net.maxBatch() ); ++b ) net.resetRow( b );
+            std::vector<dim_t> position( static_cast<size_t>( n ) );
+            std::vector<int> emitted( static_cast<size_t>( n ), 0 );
+            std::vector<char> active( static_cast<size_t>( n ), 1 );
+            std::vector<GenerateStatus> status( static_cast<size_t>( n ), GenerateStatus::Success );
+            for ( int b = 0; b < n; ++b )
+            {
+                const auto& prompt = prompts[ static_cast<size_t>( b ) ];
+                const dim_t len = static_cast<dim_t>( prompt.size() );
+                TokenTensor toks( ctx->getDeviceId(), shape_t{ 1, len } );
+                Compute::rocmCheck( mila_cdna4_memcpy_h2d( toks.rawData(), prompt.data(), static_cast<size_t>( len ) * 4, ctx->getStream() ) );
+                net.prefillRow( b, toks, len, 0 );
+                ctx->synchronize();
+                position[ static_cast<size_t>( b ) ] = len;
+                sampleRow( b );      // the first token, from the prefill's logits
+                net.setRowActive( b, true );
+            }
+            const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
+            std::vector<int32_t> tokens( static_cast<size_t>( B ) );
+            int live = n;
+            while ( true )
+            {
+                Compute::rocmCheck( mila_cdna4_memcpy_d2h( tokens.data(), net.rowsTokens().data(), static_cast<size_t>( B ) * 4, ctx->getStream() ) );
+                ctx->synchronize();
+                for ( int b = 0; b < n; ++b )
+                {
+                    const size_t i = static_cast<size_t>( b );
+                    if ( !active[ i ] ) continue;
+                    const int32_t token = tokens[ i ];
+                    bool retire = true;
+                    if ( stop_ids.contains( token ) ) status[ i ] = GenerateStatus::Success;
+                    else
+                    {
+                        on_token( b, token );
+                        ++emitted[ i ];
+                        if ( emitted[ i ] >= max_new ) status[ i ] = GenerateStatus::MaxNewTokensReached;
+                        else if ( position[ i ] >= contextLength() ) status[ i ] = GenerateStatus::ContextOverflow;
+                        else retire = false;
+                    }
+                    if ( retire ) { active[ i ] = 0; net.setRowActive( b, false ); --live; }
+                }
+                if ( live == 0 ) break;
+                dim_t max_position = 0;
+                for ( int b = 0; b < n; ++b ) if ( active[ static_cast<size_t>( b ) ] ) max_position = std::max( max_position, position[ static_cast<size_t>( b ) ] );
+                net.ensureGraphRows( B, max_position, greedy );      // (re-captures only when the largest active row leaves the captured live-length bucket)
+                net.replayGraphRows();
+                for ( int b = 0; b < n; ++b )
+                    if ( active[ static_cast<size_t>( b ) ] ) { ++position[ static_cast<size_t>( b ) ]; if ( !greedy ) sampleRow( b ); }
+            }
+            ctx->synchronize();
+            return status;
+        }
+
         GemmaModel( Network net, const GemmaConfig& cfg, const GemmaModelConfig& mc, Serialization::PretrainedMetadata md )
             : network_( std::move( net ) ), network_config_( cfg ), model_config_( mc ), source_metadata_( std::move( md ) )
         {

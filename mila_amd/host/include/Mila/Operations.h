@@ -244,6 +244,17 @@ namespace Mila::Dnn::Compute
             else rocmCheck( mila_cdna4_matvec_bf16_qfp4( y, x, static_cast<const uint8_t*>( weight_ ), scales_, bias_, K, N, kGroup, st ) );
         }
 
+        /// matvec() for `rows` (2 .. 4) independent input vectors from ONE pass over the weights (mila_cdna4_matvec_rows): row b reads x + b * x_stride and writes
+        /// y + b * y_stride (elements); row b has the bits matvec() gives on that row alone.  The o_proj / fc_down launches of the rows decode step
+        void matvecRows( uint16_t* y, const uint16_t* x, int rows, int64_t x_stride, int64_t y_stride ) const
+        {
+            mila_matvec_rows_args r{};
+            r.a.y = y; r.a.x = x; r.a.W = weight_; r.a.scales = scales_; r.a.post_scale = 1.0f; r.a.fmt = kFmt;
+            r.a.K = (int)cfg_.in_features; r.a.N = (int)cfg_.out_features; r.a.group = kFmt == 2 ? kGroup : 0;
+            r.bias = bias_; r.rows = rows; r.x_stride = x_stride; r.y_stride = y_stride;
+            rocmCheck( mila_cdna4_matvec_rows( &r, this->context_->getStream() ) );
+        }
+
         /// true when forwardGelu() serves this op and row count: unquantized weights on the GEMM branch
         bool fusesGelu( dim_t rows ) const noexcept { return kFmt == 0 && rows > 1; }
 
@@ -844,7 +855,29 @@ namespace Mila::Dnn::Compute
             k_cache_ = std::make_unique<TensorType>( context_->getDeviceId(), s );
             v_cache_ = std::make_unique<TensorType>( context_->getDeviceId(), s );
             length_ = 0;
+            rows_ = 1; row_ = 0;
         }
+        /// Batched decode of independent sequences: `rows` caches [rows, NKV, capacity, HS] behind this B = 1 op, one per sequence.  selectCacheRow( b ) makes row b
+        /// the cache every B = 1 call of this op (prefill, decode, keyCache() / valueCache()) works on, so the existing prefill writes row b unchanged; the rows decode
+        /// entry takes keyCacheRows() / valueCacheRows(), all rows.  Call after initializeKvCache(); rows == 1 leaves the op as it was built.
+        void setCacheRows( int rows )
+        {
+            requireCache();
+            if ( rows < 1 ) throw std::invalid_argument( "RocmGqaOp::setCacheRows: rows must be positive" );
+            if ( rows == rows_ ) return;
+            const shape_t s{ rows, cfg_.num_kv_heads, capacity_, cfg_.head_dim };
+            k_cache_ = std::make_unique<TensorType>( context_->getDeviceId(), s );
+            v_cache_ = std::make_unique<TensorType>( context_->getDeviceId(), s );
+            rows_ = rows; row_ = 0; length_ = 0;
+        }
+        void selectCacheRow( int b )
+        {
+            if ( b < 0 || b >= rows_ ) throw std::invalid_argument( "RocmGqaOp::selectCacheRow: row " + std::to_string( b ) + " outside the " + std::to_string( rows_ ) + " cache rows" );
+            row_ = b;
+        }
+        int cacheRows() const noexcept { return rows_; }
+        uint16_t* keyCacheRows() noexcept { return k_cache_ ? k_cache_->data() : nullptr; }
+        uint16_t* valueCacheRows() noexcept { return v_cache_ ? v_cache_->data() : nullptr; }
         void resetKvCache() noexcept { length_ = 0; }
         void rewindKvCache( dim_t length )
         {
@@ -865,8 +898,8 @@ namespace Mila::Dnn::Compute
             requireCache();
             mila_stream_t st = context_->getStream();
             const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
-            rocmCheck( mila_cdna4_kv_write_bf16( k_cache_->data(), v_cache_->data(), q_cast( k ), q_cast( v ), batch_, chunk, NKV, HS, position, cap, st ) );
-            rocmCheck( mila_cdna4_attn_prefill_bf16( out.data(), q_cast( q ), k_cache_->data(), v_cache_->data(), batch_, chunk, NH, NKV, HS, cap,
+            rocmCheck( mila_cdna4_kv_write_bf16( keyCache(), valueCache(), q_cast( k ), q_cast( v ), batch_, chunk, NKV, HS, position, cap, st ) );
+            rocmCheck( mila_cdna4_attn_prefill_bf16( out.data(), q_cast( q ), keyCache(), valueCache(), batch_, chunk, NH, NKV, HS, cap,
                                                      position, (int)cfg_.window, scale(), st ) );
             length_ = position + chunk;
         }
@@ -877,7 +910,7 @@ namespace Mila::Dnn::Compute
         {
             requireCache();
             const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
-            rocmCheck( mila_cdna4_attn_prefill_bf16( out.data(), q_cast( q ), k_cache_->data(), v_cache_->data(), batch_, chunk, NH, NKV, HS, cap,
+            rocmCheck( mila_cdna4_attn_prefill_bf16( out.data(), q_cast( q ), keyCache(), valueCache(), batch_, chunk, NH, NKV, HS, cap,
                                                      position, (int)cfg_.window, scale(), context_->getStream() ) );
             length_ = position + chunk;
         }
@@ -888,7 +921,7 @@ namespace Mila::Dnn::Compute
             requireCache();
             mila_stream_t st = context_->getStream();
             const int NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
-            rocmCheck( mila_cdna4_kv_write_bf16( k_cache_->data(), v_cache_->data(), q_cast( k ), q_cast( v ), batch_, 1, NKV, HS, position, cap, st ) );
+            rocmCheck( mila_cdna4_kv_write_bf16( keyCache(), valueCache(), q_cast( k ), q_cast( v ), batch_, 1, NKV, HS, position, cap, st ) );
             attendDecode( q, out, position );
         }
 
@@ -899,7 +932,7 @@ namespace Mila::Dnn::Compute
             const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
             const size_t need = mila_cdna4_attn_decode_scratch_bytes( batch_, NH, HS );
             void* scratch = context_->getScratch( need );   // fetched per forward, never cached
-            rocmCheck( mila_cdna4_attn_decode_bf16( out.data(), q_cast( q ), k_cache_->data(), v_cache_->data(), scratch, need, batch_, NH, NKV, HS, cap,
+            rocmCheck( mila_cdna4_attn_decode_bf16( out.data(), q_cast( q ), keyCache(), valueCache(), scratch, need, batch_, NH, NKV, HS, cap,
                                                     position + 1, (int)cfg_.window, scale(), context_->getStream() ) );
             length_ = position + 1;
         }
@@ -910,8 +943,9 @@ namespace Mila::Dnn::Compute
             return 2 * static_cast<size_t>( batch ) * static_cast<size_t>( cfg_.num_kv_heads ) * static_cast<size_t>( resolveCacheCapacity( max_seq, cfg_.window, prefill_chunk ) ) *
                    static_cast<size_t>( cfg_.head_dim ) * 2;
         }
-        uint16_t* keyCache() noexcept { return k_cache_ ? k_cache_->data() : nullptr; }
-        uint16_t* valueCache() noexcept { return v_cache_ ? v_cache_->data() : nullptr; }
+        /// the selected row's caches (row 0 unless selectCacheRow() said otherwise)
+        uint16_t* keyCache() noexcept { return k_cache_ ? k_cache_->data() + rowElems() * static_cast<size_t>( row_ ) : nullptr; }
+        uint16_t* valueCache() noexcept { return v_cache_ ? v_cache_->data() + rowElems() * static_cast<size_t>( row_ ) : nullptr; }
         const GqaOpConfig& config() const noexcept { return cfg_; }
 
     private:
@@ -920,7 +954,9 @@ namespace Mila::Dnn::Compute
         GqaOpConfig cfg_;
         const bool kBoundedRing;
         std::unique_ptr<TensorType> k_cache_, v_cache_;
+        size_t rowElems() const noexcept { return static_cast<size_t>( batch_ ) * static_cast<size_t>( cfg_.num_kv_heads ) * static_cast<size_t>( capacity_ ) * static_cast<size_t>( cfg_.head_dim ); }
         int batch_{ 1 };
+        int rows_{ 1 }, row_{ 0 };      ///< independent caches behind the op, and the one its B = 1 calls work on
         dim_t capacity_{ 0 }, length_{ 0 };
     };
     /// counterpart of CudaGqaOp<Prec, kBounded>: the KV policy as a compile-time axis, as in the reference

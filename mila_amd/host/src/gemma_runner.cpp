@@ -117,6 +117,43 @@ HOST_API void* mila_gemma_create( int policy, const mila_gemma_config* c, int64_
     return rc == 0 ? r : nullptr;
 }
 
+/// mila_gemma_create with GemmaConfig::max_batch: up to max_batch (1 .. 4) independent sequences per decode step.  mila_gemma_config itself is unchanged.
+HOST_API void* mila_gemma_create_rows( int policy, const mila_gemma_config* c, int64_t max_seq, int64_t max_prefill, int64_t max_batch, uint64_t seed, int device )
+{
+    Runner* r = nullptr;
+    int rc = guarded( [&]
+    {
+        GemmaConfig cfg;
+        if ( c )
+        {
+            cfg.vocab_size = c->vocab_size; cfg.embedding_dim = c->embedding_dim; cfg.num_layers = c->num_layers; cfg.num_heads = c->num_heads;
+            cfg.num_kv_heads = c->num_kv_heads; cfg.head_dim = c->head_dim; cfg.hidden_dim = c->hidden_dim; cfg.global_head_dim = c->global_head_dim;
+            cfg.num_global_kv_heads = c->num_global_kv_heads; cfg.window = c->window; cfg.sliding_window_pattern = c->sliding_window_pattern;
+            cfg.global_rotary_dim = c->global_rotary_dim;
+            cfg.bounded_local_kv = c->bounded_local_kv != 0;
+            cfg.kv_fp8 = c->kv_fp8 != 0;
+        }
+        cfg.max_batch = max_batch;
+        auto rr = std::make_unique<Runner>();
+        rr->max_prefill = max_prefill;
+        switch ( policy )
+        {
+            case 0: rr->model = std::make_unique<GemmaTransformer<NoWeightQuant>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            case 1: rr->model = std::make_unique<GemmaTransformer<PerChannelFp8<>>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            case 2: rr->model = std::make_unique<GemmaTransformer<PerGroupFp4<128>>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            default: throw std::invalid_argument( "unknown weight policy" );
+        }
+        std::visit( [&]( auto& m )
+        {
+            m->initSynthetic( seed );
+            rr->tokens = std::make_unique<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>>(
+                m->context()->getDeviceId(), shape_t{ std::max<dim_t>( max_prefill, 1 ) } );
+        }, rr->model );
+        r = rr.release();
+    } );
+    return rc == 0 ? r : nullptr;
+}
+
 /// regenerate the synthetic parameters under a profile: p = { linear_gain, qk_norm_center, post_norm_center, layer_scalar, table_gain }
 HOST_API int mila_gemma_init_synthetic( void* h, uint64_t seed, const float* p )
 {
@@ -346,6 +383,92 @@ HOST_API int mila_gemma_decode( void* h, int32_t token, int64_t position, int mo
 
 /// Timed decode: `warmup` untimed steps then `steps` timed ones from `start_position`, token ids
 /// cycling through a fixed pattern (the sampler is outside the measured path).
+
+// ---- batched decode: rows of independent sequences (GemmaConfig::max_batch > 1) ------------------------------------------------------------------------
+/// prefill T tokens at positions offset .. into row b's caches; host_logits (may be NULL): the last position's [vocab] logits
+HOST_API int mila_gemma_prefill_row( void* h, int b, const int32_t* host_tokens, int64_t T, int64_t offset, float* host_logits )
+{
+    auto* r = static_cast<Runner*>( h );
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( T <= 0 ) throw std::invalid_argument( "prefill_row: empty prompt" );
+            Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource> toks( m->context()->getDeviceId(), shape_t{ 1, T } );
+            Compute::rocmCheck( mila_cdna4_memcpy_h2d( toks.rawData(), host_tokens, static_cast<size_t>( T ) * 4, m->context()->getStream() ) );
+            m->prefillRow( b, toks, T, offset );
+            m->context()->synchronize();
+        }, r->model );
+        download_logits( r, host_logits );
+    } );
+}
+/// row b's active word, and (token >= 0) the token its next step embeds
+HOST_API int mila_gemma_set_active( void* h, int b, int active, int32_t token )
+{
+    return guarded( [&] { std::visit( [&]( auto& m ) { m->setRowActive( b, active != 0 ); if ( token >= 0 ) m->setRowToken( b, token ); }, static_cast<Runner*>( h )->model ); } );
+}
+HOST_API int mila_gemma_reset_row( void* h, int b )
+{
+    return guarded( [&] { std::visit( [&]( auto& m ) { m->resetRow( b ); }, static_cast<Runner*>( h )->model ); } );
+}
+/// one step over rows 0 .. B - 1.  mode 1: eager launches, 2: graph replay (captured on first use and when B, the sampler tail or the live-length bucket change).
+/// greedy != 0: the step ends with the rows sampler tail (next token + position bump of every active row); 0: it ends at the logits, positions bumped.
+/// max_position: the largest position among the active rows.  Outputs (each may be NULL): logits [B, vocab], tokens [B], positions [B] AFTER the step.
+HOST_API int mila_gemma_decode_rows( void* h, int B, int64_t max_position, int mode, int greedy, float* host_logits, int32_t* host_tokens, int32_t* host_positions )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( mode != 1 && mode != 2 ) throw std::invalid_argument( "decode_rows: mode must be 1 (eager) or 2 (graph)" );
+            if ( mode == 1 ) m->decodeRows( B, max_position, greedy != 0 );
+            else { m->ensureGraphRows( B, max_position, greedy != 0 ); m->replayGraphRows(); }
+            auto st = m->context()->getStream();
+            if ( host_logits ) Compute::rocmCheck( mila_cdna4_memcpy_d2h( host_logits, m->rowsLogits().data(), static_cast<size_t>( B ) * m->config().vocab_size * 4, st ) );
+            if ( host_tokens ) Compute::rocmCheck( mila_cdna4_memcpy_d2h( host_tokens, m->rowsTokens().data(), static_cast<size_t>( B ) * 4, st ) );
+            if ( host_positions ) Compute::rocmCheck( mila_cdna4_memcpy_d2h( host_positions, m->rowsPositions().data(), static_cast<size_t>( B ) * 4, st ) );
+            m->context()->synchronize();
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
+/// out[0] = captures of the rows graph so far, out[1] = kernel nodes of the captured rows step
+HOST_API int mila_gemma_rows_graph_info( void* h, int64_t* out )
+{
+    return guarded( [&] { std::visit( [&]( auto& m ) { out[ 0 ] = (int64_t)m->graphRowsCaptureCount(); out[ 1 ] = (int64_t)m->graphRowsNodeCount(); }, static_cast<Runner*>( h )->model ); } );
+}
+/// `steps` greedy graph replays of a B-row step with every row active from `start_position` (the caches hold whatever they hold: a timing loop), after `warmup`:
+/// out[0] = wall ms per step, out[1] = device ms per step
+HOST_API int mila_gemma_time_decode_rows( void* h, int B, int64_t start_position, int steps, int warmup, double* out )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            auto* ctx = m->context();
+            hipStream_t s = reinterpret_cast<hipStream_t>( ctx->getStream() );
+            for ( int b = 0; b < B; ++b ) { m->setRowPosition( b, start_position ); m->setRowToken( b, 17 + b ); m->setRowActive( b, true ); }
+            int64_t pos = start_position;
+            auto step = [&] { m->ensureGraphRows( B, pos, true ); m->replayGraphRows(); ++pos; };
+            for ( int i = 0; i < warmup; ++i ) step();
+            ctx->synchronize();
+            hipEvent_t e0, e1;
+            hipCheck( hipEventCreate( &e0 ), "hipEventCreate" );
+            hipCheck( hipEventCreate( &e1 ), "hipEventCreate" );
+            const auto t0 = std::chrono::steady_clock::now();
+            hipCheck( hipEventRecord( e0, s ), "hipEventRecord" );
+            for ( int i = 0; i < steps; ++i ) step();
+            hipCheck( hipEventRecord( e1, s ), "hipEventRecord" );
+            ctx->synchronize();
+            const auto t1 = std::chrono::steady_clock::now();
+            float ms = 0;
+            hipCheck( hipEventElapsedTime( &ms, e0, e1 ), "hipEventElapsedTime" );
+            (void)hipEventDestroy( e0 ); (void)hipEventDestroy( e1 );
+            out[ 0 ] = std::chrono::duration<double, std::milli>( t1 - t0 ).count() / steps;
+            out[ 1 ] = static_cast<double>( ms ) / steps;
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
+
 /// out[0] = wall ms per step (host clock around the timed region, stream synchronised both sides)
 /// out[1] = device ms per step (HIP events on the model stream)
 HOST_API int mila_gemma_time_decode( void* h, int64_t start_position, int steps, int warmup, int mode, double* out )
@@ -960,6 +1083,30 @@ HOST_API void* mila_gemma_model_synthetic( int policy, const mila_gemma_config* 
     return rc == 0 ? m : nullptr;
 }
 
+/// mila_gemma_model_synthetic with GemmaModelConfig::withMaxBatch( max_batch ): a model generate_rows can run on
+HOST_API void* mila_gemma_model_synthetic_rows( int policy, const mila_gemma_config* c, int64_t context, int64_t prefill_chunk, int64_t max_batch, uint64_t seed, const float* p, int device )
+{
+    RocmGemmaModel* m = nullptr;
+    int rc = guarded( [&]
+    {
+        GemmaConfig cfg;
+        int bounded = 0, kv_fp8 = 0;
+        if ( c )
+        {
+            cfg.vocab_size = c->vocab_size; cfg.embedding_dim = c->embedding_dim; cfg.num_layers = c->num_layers; cfg.num_heads = c->num_heads;
+            cfg.num_kv_heads = c->num_kv_heads; cfg.head_dim = c->head_dim; cfg.hidden_dim = c->hidden_dim; cfg.global_head_dim = c->global_head_dim;
+            cfg.num_global_kv_heads = c->num_global_kv_heads; cfg.window = c->window; cfg.sliding_window_pattern = c->sliding_window_pattern;
+            cfg.global_rotary_dim = c->global_rotary_dim;
+            bounded = c->bounded_local_kv != 0;
+            kv_fp8 = c->kv_fp8 != 0;
+        }
+        GemmaTransformer<NoWeightQuant>::SyntheticProfile pr;
+        if ( p ) { pr.linear_gain = p[ 0 ]; pr.qk_norm_center = p[ 1 ]; pr.post_norm_center = p[ 2 ]; pr.layer_scalar = p[ 3 ]; pr.table_gain = p[ 4 ]; }
+        m = RocmGemmaModel::fromSynthetic( cfg, model_config_of( policy, context, prefill_chunk, bounded, kv_fp8 ).withMaxBatch( max_batch ), seed, pr, Compute::Device::Rocm( device ) ).release();
+    } );
+    return rc == 0 ? m : nullptr;
+}
+
 HOST_API void mila_gemma_model_destroy( void* h ) { delete static_cast<RocmGemmaModel*>( h ); }
 
 /// generate(): max_new < 0 = no budget (run to a stop token or the context bound); n_stop == 0 = the model's default stop set; the callback's tokens
@@ -985,6 +1132,27 @@ HOST_API int mila_gemma_model_generate( void* h, const int32_t* prompt, int64_t 
         *out_count = n;
         *out_status = static_cast<int32_t>( st );
         if ( out_reused ) *out_reused = m->lastReusedPrefix();
+    } );
+}
+
+/// GemmaModel::generateBatch: n_prompts prompts, prompt b = prompts[ offsets[b] .. offsets[b + 1] ); parameters as mila_gemma_model_generate (shared by the rows); seed: row b's
+/// generator is seeded seed + b.  Row b's tokens go to out_tokens[ b * cap .. ] (at most cap), their number to out_counts[ b ], its GenerateStatus to out_status[ b ]
+HOST_API int mila_gemma_model_generate_rows( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                             int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m || !prompts || !offsets || !out_counts || !out_status || n_prompts < 0 ) throw std::invalid_argument( "gemma_model_generate_rows: null argument" );
+        GenerateParams gp;
+        if ( max_new >= 0 ) gp.max_new_tokens = max_new;
+        gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
+        for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
+        std::vector<std::vector<int32_t>> ps;
+        for ( int b = 0; b < n_prompts; ++b ) ps.emplace_back( prompts + offsets[ b ], prompts + offsets[ b + 1 ] );
+        std::vector<int64_t> counts( static_cast<size_t>( n_prompts ), 0 );
+        const auto st = m->generateBatch( ps, [&]( int b, int32_t t ) { int64_t& c = counts[ static_cast<size_t>( b ) ]; if ( out_tokens && c < cap ) out_tokens[ b * cap + c ] = t; ++c; }, gp, seed );
+        for ( int b = 0; b < n_prompts; ++b ) { out_counts[ b ] = counts[ static_cast<size_t>( b ) ]; out_status[ b ] = static_cast<int32_t>( st[ static_cast<size_t>( b ) ] ); }
     } );
 }
 
