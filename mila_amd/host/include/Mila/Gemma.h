@@ -909,12 +909,41 @@ namespace Mila::Dnn
             a.N = (int)lin.getConfig().getOutputFeatures(); a.group = Quant::Weight::groupSizeOf<TWeightQuant>(); a.geglu = 0;
             return a;
         }
-        void fusedGateUp( Layer& L )
+        // The three fused argument blocks of a decode step, for the one-row step and the rows step alike (the rows step adds its row strides: rowsArgs).
+        /// [sandwich tail of the previous layer: post_ffn_norm, residual, layer scalar] + input_norm + qkv projection
+        mila_fused_matvec_args qkvArgs( Layer& L, const Layer* prev, uint16_t* y, const uint16_t* x, const uint16_t* res, uint16_t* res_out ) const
         {
-            auto a = baseArgs( *L.fc_gate_up, f_act_->data(), f_o_->data() );
+            auto a = baseArgs( *L.qkv_proj, y, x );
+            a.norm_w = L.input_norm->getWeight()->data();
+            if ( prev ) { a.post_w = prev->post_ffn_norm->getWeight()->data(); a.res = res; a.res_out = res_out; a.post_scale = prev->layer_scalar; }
+            return a;
+        }
+        /// post_attn_norm + residual + pre_ffn_norm + gate_up + GeGLU
+        mila_fused_matvec_args gateUpArgs( Layer& L, uint16_t* y, const uint16_t* x, const uint16_t* res, uint16_t* res_out ) const
+        {
+            auto a = baseArgs( *L.fc_gate_up, y, x );
             a.N = (int)cfg_.hidden_dim; a.geglu = 1;
             a.norm_w = L.pre_ffn_norm->getWeight()->data(); a.post_w = L.post_attn_norm->getWeight()->data();
-            a.res = cur_hidden_; a.res_out = res1_->data();
+            a.res = res; a.res_out = res_out;
+            return a;
+        }
+        /// tail of the last layer + final norm + lm_head (fp32 logits); sampler_partials != nullptr: with the greedy sampler's first stage into `scratch`
+        template <typename TScratch>
+        mila_fused_matvec_args headArgs( const Layer& last, float* logits, const uint16_t* x, const uint16_t* res, uint16_t* res_out, TScratch& scratch, int* sampler_partials ) const
+        {
+            mila_fused_matvec_args a{};
+            a.y = reinterpret_cast<uint16_t*>( logits ); a.x = x; a.W = lm_head_->getWeight().rawData();
+            a.scales = nullptr;
+            if constexpr ( kTableFmt != 0 ) a.scales = lm_head_->getWeightScale()->data();
+            a.norm_w = final_norm_->getWeight()->data(); a.post_w = last.post_ffn_norm->getWeight()->data();
+            a.res = res; a.res_out = res_out; a.post_scale = last.layer_scalar; a.eps = cfg_.rms_norm_eps;
+            a.fmt = kTableFmt; a.K = (int)cfg_.embedding_dim; a.N = (int)cfg_.vocab_size; a.group = 0; a.geglu = 0; a.f32_out = 1;
+            if ( sampler_partials ) { a.argmax_scratch = scratch.data(); a.argmax_scratch_bytes = scratch.sizeInBytes(); a.argmax_blocks = sampler_partials; }
+            return a;
+        }
+        void fusedGateUp( Layer& L )
+        {
+            auto a = gateUpArgs( L, f_act_->data(), f_o_->data(), cur_hidden_, res1_->data() );
             Compute::rocmCheck( mila_cdna4_fused_norm_matvec( &a, ctx_->getStream() ) );
         }
 
@@ -933,12 +962,7 @@ namespace Mila::Dnn
                 const bool g = L.global;
                 const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.numKvHeads( g ), HD = (int)cfg_.headDim( g );
                 // 1. [tail of previous layer] + input_norm + qkv projection
-                auto a = baseArgs( *L.qkv_proj, f_qkv_->data(), prev ? f_down_->data() : cur_hidden_ );
-                a.norm_w = L.input_norm->getWeight()->data();
-                if ( prev )
-                {
-                    a.post_w = prev->post_ffn_norm->getWeight()->data(); a.res = res1_->data(); a.res_out = hidden_[ next ]->data(); a.post_scale = prev->layer_scalar;
-                }
+                auto a = qkvArgs( L, prev, f_qkv_->data(), prev ? f_down_->data() : cur_hidden_, res1_->data(), hidden_[ next ]->data() );
                 Compute::rocmCheck( mila_cdna4_fused_norm_matvec( &a, st ) );
                 if ( prev ) { cur_hidden_ = hidden_[ next ]->data(); next = ( next == 1 ) ? 2 : 1; }
                 // 2+3. q/k/v norms + RoPE + KV append + flash-decode in one launch (+ combine).
@@ -983,17 +1007,8 @@ namespace Mila::Dnn
                 prev = &L;
             }
             // tail of the last layer + final norm + lm_head (fp32 logits) in one launch
-            {
-                mila_fused_matvec_args a{};
-                a.y = reinterpret_cast<uint16_t*>( logits_->data() ); a.x = f_down_->data(); a.W = lm_head_->getWeight().rawData();
-                a.scales = nullptr;
-                if constexpr ( kTableFmt != 0 ) a.scales = lm_head_->getWeightScale()->data();
-                a.norm_w = final_norm_->getWeight()->data(); a.post_w = prev->post_ffn_norm->getWeight()->data();
-                a.res = res1_->data(); a.res_out = hidden_[ next ]->data(); a.post_scale = prev->layer_scalar; a.eps = cfg_.rms_norm_eps;
-                a.fmt = kTableFmt; a.K = (int)cfg_.embedding_dim; a.N = (int)cfg_.vocab_size; a.group = 0; a.geglu = 0; a.f32_out = 1;
-                if ( sampler_partials ) { a.argmax_scratch = sample_scratch_->data(); a.argmax_scratch_bytes = sample_scratch_->sizeInBytes(); a.argmax_blocks = sampler_partials; }
-                Compute::rocmCheck( mila_cdna4_fused_norm_matvec( &a, st ) );
-            }
+            auto a = headArgs( *prev, logits_->data(), f_down_->data(), res1_->data(), hidden_[ next ]->data(), *sample_scratch_, sampler_partials );
+            Compute::rocmCheck( mila_cdna4_fused_norm_matvec( &a, st ) );
         }
 
 
@@ -1020,9 +1035,7 @@ namespace Mila::Dnn
                 const bool g = L.global;
                 const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.numKvHeads( g ), HD = (int)cfg_.headDim( g );
                 // 1. [tail of previous layer] + input_norm + qkv projection; the rows of the packed projection are PK elements apart
-                auto a = baseArgs( *L.qkv_proj, R.qkv->data(), prev ? R.down->data() : cur );
-                a.norm_w = L.input_norm->getWeight()->data();
-                if ( prev ) { a.post_w = prev->post_ffn_norm->getWeight()->data(); a.res = R.res1->data(); a.res_out = R.hidden[ next ]->data(); a.post_scale = prev->layer_scalar; }
+                auto a = qkvArgs( L, prev, R.qkv->data(), prev ? R.down->data() : cur, R.res1->data(), R.hidden[ next ]->data() );
                 auto r = rowsArgs( a, B, D, PK, D, D );
                 Compute::rocmCheck( mila_cdna4_matvec_rows( &r, st ) );
                 if ( prev ) { cur = R.hidden[ next ]->data(); next = ( next == 1 ) ? 2 : 1; }
@@ -1037,10 +1050,7 @@ namespace Mila::Dnn
                 // 4. o_proj
                 L.o_proj->getOperation().matvecRows( R.o->data(), R.attn->data(), B, (int64_t)NH * HD, D );
                 // 5. post_attn_norm + residual + pre_ffn_norm + gate_up + GeGLU
-                a = baseArgs( *L.fc_gate_up, R.act->data(), R.o->data() );
-                a.N = (int)F; a.geglu = 1;
-                a.norm_w = L.pre_ffn_norm->getWeight()->data(); a.post_w = L.post_attn_norm->getWeight()->data();
-                a.res = cur; a.res_out = R.res1->data();
+                a = gateUpArgs( L, R.act->data(), R.o->data(), cur, R.res1->data() );
                 r = rowsArgs( a, B, D, F, D, D );
                 Compute::rocmCheck( mila_cdna4_matvec_rows( &r, st ) );
                 // 6. fc_down
@@ -1048,14 +1058,7 @@ namespace Mila::Dnn
                 prev = &L;
             }
             // tail of the last layer + final norm + lm_head (fp32 logits, one set of sampler partials per row) in one launch
-            mila_fused_matvec_args a{};
-            a.y = reinterpret_cast<uint16_t*>( R.logits->data() ); a.x = R.down->data(); a.W = lm_head_->getWeight().rawData();
-            a.scales = nullptr;
-            if constexpr ( kTableFmt != 0 ) a.scales = lm_head_->getWeightScale()->data();
-            a.norm_w = final_norm_->getWeight()->data(); a.post_w = prev->post_ffn_norm->getWeight()->data();
-            a.res = R.res1->data(); a.res_out = R.hidden[ next ]->data(); a.post_scale = prev->layer_scalar; a.eps = cfg_.rms_norm_eps;
-            a.fmt = kTableFmt; a.K = (int)D; a.N = (int)cfg_.vocab_size; a.group = 0; a.geglu = 0; a.f32_out = 1;
-            if ( sampler_partials ) { a.argmax_scratch = R.sample_scratch->data(); a.argmax_scratch_bytes = R.sample_scratch->sizeInBytes(); a.argmax_blocks = sampler_partials; }
+            auto a = headArgs( *prev, R.logits->data(), R.down->data(), R.res1->data(), R.hidden[ next ]->data(), *R.sample_scratch, sampler_partials );
             auto r = rowsArgs( a, B, D, cfg_.vocab_size, D, D );
             Compute::rocmCheck( mila_cdna4_matvec_rows( &r, st ) );
         }
