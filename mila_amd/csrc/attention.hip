@@ -27,6 +27,7 @@
 #include "attention_decode_mfma.h"
 #include "attention_decode_plan.h"
 #include "attention_decode_scalar.h"
+#include "split_div.h"
 
 namespace mila {
 
@@ -88,33 +89,8 @@ struct AttnParams
     float eps;
     int pos_stride;           // elements between two batch rows' position words at pos_dev: 0 = every row at *pos_dev (every entry but fused_attn_decode_rows_bf16), 1 = row b
                               // at pos_dev[b].  It reaches the kernels as bit 1 of the leading `flat` argument, not through this tail copy (attn_params below)
+    uint32_t split_mul, split_shift;      // split_div_make(splits), set by launch_decode: the kernel's ceil(band / splits) without a divide (split_div.h)
 };
-
-// norm (+ RoPE) of one head row by one wave, canonical helpers => bit-identical to the standalone
-// rmsnorm / rope kernels and to qkv_post_kernel.  dst_lds / dst_glb may be NULL.
-template <int HS>
-__device__ __forceinline__ void head_row_post(const uint16_t* __restrict__ src, const uint16_t* __restrict__ w, bool rotate,
-                                              const float* cos_row, const float* sin_row, float eps,
-                                              uint16_t* dst_lds, uint16_t* dst_glb)
-{
-    constexpr int hv = HS / 16;
-    const int lane = threadIdx.x & 63;
-    const bool act = lane < hv;
-    const int l2 = act ? lane : 0;
-    const u32x4 xlo = ld16(src + (size_t)l2 * 8), xhi = ld16(src + (size_t)(l2 + hv) * 8);
-    u32x4 wlo = u32x4{0u, 0u, 0u, 0u}, whi = wlo;
-    if (w) { wlo = ld16(w + (size_t)l2 * 8); whi = ld16(w + (size_t)(l2 + hv) * 8); }
-    const float rstd = rms_rstd_wave(src, HS, eps);
-    if (act)
-    {
-        u32x4 lo, hi;
-        if (w) { lo = rms_apply8(xlo, wlo, rstd, 0.0f); hi = rms_apply8(xhi, whi, rstd, 0.0f); }
-        else { lo = rms_apply8_now(xlo, rstd); hi = rms_apply8_now(xhi, rstd); }
-        if (rotate) rope_rotate8_vals(lo, hi, cos_row, sin_row, lane * 8);
-        if (dst_lds) { st16(dst_lds + (size_t)lane * 8, lo); st16(dst_lds + (size_t)(lane + hv) * 8, hi); }
-        if (dst_glb) { st16(dst_glb + (size_t)lane * 8, lo); st16(dst_glb + (size_t)(lane + hv) * 8, hi); }
-    }
-}
 
 // Combine of one head's split partials for output dim d by the lane that owns it: the arithmetic of attn_combine_kernel, shared by
 // the standalone kernel (plain loads behind a kernel boundary) and the one-pass tail of attn_decode_kernel (SC1 = agent-coherent
@@ -182,16 +158,21 @@ __device__ __forceinline__ void warm_lines(const uint8_t* __restrict__ base, int
 }
 
 // Diagnostic build only (-DMILA_ATTN_STAMPS, never the product library; tools/experiments/attn_stamps.sh): lane 0 of workgroup (0, 0, 0) of attn_decode_kernel adds the
-// shader cycles from its first instruction to the issue of its first K/V row requests to g_attn_stamps[0] and counts the launch in [1]; a buffer of its own, no output
-// is touched.  Read back with mila_dbg_attn_stamps().
+// shader cycles from its first instruction to the issue of its first K/V row requests to g_attn_stamps[0], those to the first score of its first group to [2], and
+// counts the launch in [1]; a buffer of its own, no output is touched.  Read back with mila_dbg_attn_stamps().
 #ifdef MILA_ATTN_STAMPS
-__device__ unsigned long long g_attn_stamps[2];
+__device__ unsigned long long g_attn_stamps[3];
 #endif
 
 // HS = 64 * EPL (EPL in {2,4,8}) or HS = 64 handled as EPL = 2 on 32 active lanes.
 // GH = query heads per workgroup; grid = (splits, NKV * GS/GH, B); 8 waves, wave w owns positions
-// begin + w + 8 j of the split.  FUSED: the q/k/v post-processing of the token is done in the prologue,
-// overlapped with the first K/V round trip; the new K/V row is appended to the cache by the split that owns it.
+// begin + w + 8 j of the split.  FUSED: the q/k/v post-processing of the token is done in the prologue; the new K/V row is appended to the cache by the split that
+// owns it.  Canonical helpers (rms_rstd_wave, rms_apply8, rope_rotate8_regs) => bit-identical to the standalone rmsnorm / rope kernels and to qkv_post_kernel.
+//
+// Order of issue (EXPERIMENTS.md section 19): the position word (a vector load) -> the by-value tail -> the prologue's rows and norm weights, their sums of squares, rstd
+// and weights, V parked in LDS: none of it needs the position -> position -> cos/sin row -> the K/V rows of the first group (both groups at HS 512), every request
+// unconditional so that the waits behind them are counts -> rotation, LDS, barrier, q read-back under the K/V round trip -> append.  No integer division stands between
+// the position word and a K/V request unless the band wraps a ring whose length is no power of two (one remainder per wave then).
 //
 // Arguments: the head of the kernel's latency chain is kernel arguments -> *pos_dev -> band and row addresses -> the first K/V round trip.  What that chain reads comes
 // as leading plain parameters (14 dwords), which the dispatcher preloads into SGPRs before the first instruction (kernarg preload, build.py), so the load of *pos_dev is
@@ -217,16 +198,29 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATT
 #ifdef MILA_ATTN_STAMPS
     const unsigned long long entry_ = __builtin_amdgcn_s_memtime();
 #endif
-    const AttnParams p = attn_params(pos_dev, K, V, q_raw, NH, NKV, capacity, window, splits, flat, tail);
     using Row = DecodeGeomBf16<HS>;
     constexpr int NW = kDecodeWaves, EPL = Row::EPL, NPAIR = Row::NPAIR, ACTIVE = Row::ACTIVE, PG = Row::PG, STR = HS + 2;
+    constexpr int GH_LOG2 = GH == 4 ? 2 : (GH == 2 ? 1 : 0);
+    constexpr bool PRE2 = PG < 8;                          // HS 512: both register groups are requested before the prologue
+    static_assert(GH == 1 || GH == 2 || GH == 4, "heads per workgroup: 1, 2 or 4");
+    static_assert(GH + 2 <= NW, "one prologue row per wave");
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (scalar: the row walk and the prologue's roles are wave-uniform)
+    const bool owner = lane < ACTIVE;
+    const int b = blockIdx.z;
+
+    // ---- the position word: the first request of the kernel, from the preloaded pointer.  A VECTOR load (every lane the same word, read back with readfirstlane):
+    // scalar loads return out of order, so a wait for the by-value tail would wait for a scalar load of the position beside it, and everything below that needs the
+    // tail but not the position -- the prologue's rows -- would stand behind the position.  Without a device position the word is read from the head of K and dropped.
+    int lane_zero;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(lane_zero));      // a zero the compiler cannot see through: keeps the address per-lane, hence the load a vector one
+    const int32_t* pos_at = pos_dev ? pos_dev + b * ((flat >> 1) & 1) : reinterpret_cast<const int32_t*>(K);
+    const int pos_word = pos_at[lane_zero];
+
+    const AttnParams p = attn_params(pos_dev, K, V, q_raw, NH, NKV, capacity, window, splits, flat, tail);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float* sm = reinterpret_cast<float*>(smem_raw);        // [NW][GH][HS + 2]
     uint16_t* qs = reinterpret_cast<uint16_t*>(smem_raw + (size_t)NW * GH * STR * sizeof(float));   // [GH][HS], then k_new, v_new
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool owner = lane < ACTIVE;
-    const int GS = p.NH / p.NKV, hgroups = GS / GH;
     if (!p.flat && (int)blockIdx.x >= p.splits)             // a warm block (block-uniform): no barrier is shared with the others
     {
         const int64_t wb = ((int64_t)(blockIdx.x - p.splits) * gridDim.y + blockIdx.y) * gridDim.z + blockIdx.z;
@@ -234,83 +228,46 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATT
                    p.scratch);
         return;
     }
-    const int ngrp = p.NKV * hgroups;
-    const int split = p.flat ? (int)blockIdx.x / ngrp : (int)blockIdx.x, grp = p.flat ? (int)blockIdx.x % ngrp : (int)blockIdx.y;
-    const int kvh = grp / hgroups, hg = grp % hgroups;
-    const int h0 = kvh * GS + hg * GH;                     // first query head of this workgroup
-    const int b = blockIdx.z;
-    const int pos = p.pos_dev ? p.pos_dev[b * p.pos_stride] : p.position;
-    const int len = pos + 1;
-    const int band_begin = (p.window > 0) ? max(0, len - p.window) : 0;
-    const int band = len - band_begin;
-    const int chunk = (band + p.splits - 1) / p.splits;
-    const int begin = band_begin + split * chunk;
-    const int end = min(begin + chunk, len);
-    const bool owns_new = FUSED && pos >= begin && pos < end;   // this split appends (and consumes) the new K/V row
-
+    // Head geometry without a division: NH = NKV * GS with GS a power of two (decode_group_size_ok, which every launcher checks) and GH a power of two that divides GS
+    // (heads_per_group), so GS is a shift, a KV head's workgroups are a mask, and kvh * GS + hg * GH is grp * GH
+    const int gs_log2 = __builtin_clz((unsigned)p.NKV) - __builtin_clz((unsigned)p.NH), hg_log2 = gs_log2 - GH_LOG2;
+    int split = (int)blockIdx.x, grp = (int)blockIdx.y;
+    if (p.flat)
+    {
+        const int ngrp = p.NKV << hg_log2;
+        split = (int)blockIdx.x / ngrp;
+        grp = (int)blockIdx.x % ngrp;
+    }
+    const int kvh = grp >> hg_log2, hg = grp & ((1 << hg_log2) - 1);
+    const int h0 = grp * GH;                               // first query head of this workgroup
     uint16_t* kbase = p.K + ((size_t)b * p.NKV + kvh) * p.capacity * HS;
     uint16_t* vbase = p.V + ((size_t)b * p.NKV + kvh) * p.capacity * HS;
 
-    struct KVG { uint32_t k[PG][NPAIR], v[PG][NPAIR]; };
-    auto load_group = [&](KVG& gbuf, int base) {
-#pragma unroll
-        for (int j = 0; j < PG; ++j)
-        {
-            const int pp = base + NW * j;
-            // in the fused form row `pos` is not in the cache yet: it is patched in from LDS below
-            if (owner && pp < end && !(FUSED && pp == pos))
-            {
-                const size_t r = (size_t)(pp % p.capacity) * HS + lane * EPL;
-                load_row<EPL>(gbuf.k[j], kbase + r);
-                load_row<EPL>(gbuf.v[j], vbase + r);
-            }
-            else
-            {
-#pragma unroll
-                for (int e = 0; e < NPAIR; ++e) { gbuf.k[j][e] = 0u; gbuf.v[j][e] = 0u; }
-            }
-        }
-    };
-
-    int base = begin + wave;
-    KVG ga, gb;
-    if (base < end) load_group(ga, base);                  // in flight during the prologue
-#ifdef MILA_ATTN_STAMPS
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
-    {
-        g_attn_stamps[0] += __builtin_amdgcn_s_memtime() - entry_;
-        g_attn_stamps[1] += 1;
-    }
-#endif
-
-    // ---- q (and the new K/V row) ----
+    // ---- what does not need the position: q (unfused), or the prologue's rows up to the rotation (fused) ----
+    // Fused: wave r < GH takes query head h0 + r, wave GH the token's K row, wave GH + 1 its V row, in EVERY workgroup (whether this split owns the new row is known
+    // only with the position; the LDS slots exist anyway).  Loads, sum of squares, rstd and the weights are done here; V is finished and parked in LDS.
+    constexpr int hv = HS / 16;
+    const bool act = lane < hv;                            // a lane holds chunks lane and lane + hv of the row (fused.hip's qkv_post_kernel assigns them the same way)
+    const int l2 = act ? lane : 0;
+    const bool has_row = FUSED && wave < GH + 2, rotates = FUSED && wave <= GH;
     uint32_t q[GH][NPAIR];
+    u32x4 lo = u32x4{0u, 0u, 0u, 0u}, hi = lo;
     if constexpr (FUSED)
     {
-        const int half = HS / 2;
-        const float* cos_row = p.cos_cache + (size_t)pos * half;
-        const float* sin_row = p.sin_cache + (size_t)pos * half;
-        const int nrows = GH + (owns_new ? 2 : 0);
-        for (int r = wave; r < nrows; r += NW)
+        if (has_row)
         {
-            if (r < GH)
-                head_row_post<HS>(p.q_raw + (size_t)b * p.raw_b_stride + (size_t)(h0 + r) * HS, p.qw, true, cos_row, sin_row, p.eps, qs + (size_t)r * HS, nullptr);
-            else if (r == GH)
-                head_row_post<HS>(p.k_raw + (size_t)b * p.raw_b_stride + (size_t)kvh * HS, p.kw, true, cos_row, sin_row, p.eps, qs + (size_t)GH * HS,
-                                  (hg == 0) ? kbase + (size_t)(pos % p.capacity) * HS : nullptr);
-            else
-                head_row_post<HS>(p.v_raw + (size_t)b * p.raw_b_stride + (size_t)kvh * HS, p.vw, false, cos_row, sin_row, p.eps, qs + (size_t)(GH + 1) * HS,
-                                  (hg == 0) ? vbase + (size_t)(pos % p.capacity) * HS : nullptr);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int g = 0; g < GH; ++g)
-        {
-            if (owner) load_row<EPL>(q[g], qs + (size_t)g * HS + lane * EPL);
-            else
+            const uint16_t* src = (wave < GH ? p.q_raw + (size_t)(h0 + wave) * HS : (wave == GH ? p.k_raw : p.v_raw) + (size_t)kvh * HS) + (size_t)b * p.raw_b_stride;
+            const uint16_t* w = wave < GH ? p.qw : (wave == GH ? p.kw : p.vw);
+            const u32x4 xlo = ld16(src + (size_t)l2 * 8), xhi = ld16(src + (size_t)(l2 + hv) * 8);
+            u32x4 wlo = u32x4{0u, 0u, 0u, 0u}, whi = wlo;
+            if (w) { wlo = ld16(w + (size_t)l2 * 8); whi = ld16(w + (size_t)(l2 + hv) * 8); }
+            const float rstd = rms_rstd_wave(src, HS, p.eps);
+            if (w) { lo = rms_apply8(xlo, wlo, rstd, 0.0f); hi = rms_apply8(xhi, whi, rstd, 0.0f); }
+            else { lo = rms_apply8_now(xlo, rstd); hi = rms_apply8_now(xhi, rstd); }
+            if (wave == GH + 1 && act)
             {
-#pragma unroll
-                for (int e = 0; e < NPAIR; ++e) q[g][e] = 0u;
+                st16(qs + (size_t)(GH + 1) * HS + (size_t)lane * 8, lo);
+                st16(qs + (size_t)(GH + 1) * HS + (size_t)(lane + hv) * 8, hi);
             }
         }
     }
@@ -326,6 +283,106 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATT
 #pragma unroll
                 for (int e = 0; e < NPAIR; ++e) q[g][e] = 0u;
             }
+        }
+    }
+
+    // the cache row of a wave's next position is the last one stepped by NW and wrapped once; a ring shorter than the step (NW % capacity: the one division, and it
+    // does not wait for the position) wraps once too
+    const uint32_t cap = (uint32_t)p.capacity;
+    const uint32_t row_step = cap >= (uint32_t)NW ? (uint32_t)NW : (uint32_t)NW % cap;
+
+    // ---- behind the position: no division up to the K/V requests on a cache the band does not wrap in, one remainder per wave on a ring ----
+    const int pos_read = __builtin_amdgcn_readfirstlane(pos_word);     // (unconditional: a request left pending on one path would make every later wait a full drain)
+    const int pos = p.pos_dev ? pos_read : p.position;
+    const int len = pos + 1;
+    const int band_begin = (p.window > 0) ? max(0, len - p.window) : 0;
+    const int band = len - band_begin;
+    const int chunk = (int)split_div((uint32_t)(band + p.splits - 1), SplitDiv{p.split_mul, p.split_shift});      // (band + splits - 1) / splits
+    const int begin = band_begin + split * chunk;
+    const int end = min(begin + chunk, len);
+    const bool owns_new = FUSED && pos >= begin && pos < end;   // this split appends (and consumes) the new K/V row
+
+    // the cache row of a position: the position itself while nothing has wrapped (len <= capacity: every flat cache), else its remainder
+    const bool wrapped = (uint32_t)len > cap;
+    auto ring_row = [&](int pp) -> uint32_t {
+        if (!wrapped) return (uint32_t)pp;
+        return (cap & (cap - 1u)) == 0u ? (uint32_t)pp & (cap - 1u) : (uint32_t)pp % cap;
+    };
+    // the first cos/sin request goes out before the K/V rows: vector memory returns in order, and the rotation is what the barrier below waits for
+    f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0, s0 = c0, s1 = c0;
+    if constexpr (FUSED)
+    {
+        if (rotates)
+        {
+            const float* cos_row = p.cos_cache + (size_t)pos * (HS / 2) + l2 * 8;
+            const float* sin_row = p.sin_cache + (size_t)pos * (HS / 2) + l2 * 8;
+            c0 = *reinterpret_cast<const f32x4*>(cos_row); c1 = *reinterpret_cast<const f32x4*>(cos_row + 4);
+            s0 = *reinterpret_cast<const f32x4*>(sin_row); s1 = *reinterpret_cast<const f32x4*>(sin_row + 4);
+        }
+    }
+
+    // A group's row requests are unconditional, so that the waits behind them are counted, not drained: a slot past the split's end (or row `pos` of the fused form,
+    // which is not in the cache yet and is patched in from LDS below) reads row 0 of its KV head and is zeroed on arrival.  `row` walks with the positions
+    struct KVG { uint32_t k[PG][NPAIR], v[PG][NPAIR]; };
+    int base = begin + wave;
+    uint32_t row = ring_row(base);
+    const uint32_t lane_el = owner ? (uint32_t)lane * EPL : 0u;      // (a row's address is a scalar base plus this: nothing per-lane is computed per row)
+    auto load_group = [&](KVG& gbuf, int base_) {
+#pragma unroll
+        for (int j = 0; j < PG; ++j)
+        {
+            const int pp = base_ + NW * j;
+            const bool valid = pp < end && !(FUSED && pp == pos);
+            const size_t r = (size_t)(valid ? row : 0u) * HS;
+            const uint32_t keep = (valid && owner) ? ~0u : 0u;      // (a mask, not a select: a select becomes a branch with a full drain on its zero side)
+            uint32_t kk[NPAIR], vv[NPAIR];
+            load_row<EPL>(kk, (kbase + r) + lane_el);
+            load_row<EPL>(vv, (vbase + r) + lane_el);
+            __builtin_amdgcn_sched_barrier(0);              // a row is requested as soon as its address exists, not behind the addresses of the whole group
+#pragma unroll
+            for (int e = 0; e < NPAIR; ++e) { gbuf.k[j][e] = kk[e] & keep; gbuf.v[j][e] = vv[e] & keep; }
+            row += row_step;
+            if (row >= cap) row -= cap;
+        }
+    };
+    KVG ga, gb;
+    load_group(ga, base);                                  // in flight while the prologue finishes
+#ifdef MILA_ATTN_STAMPS
+    const bool stamps_ = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0;
+    bool stamp_score_ = true;
+    if (stamps_)
+    {
+        g_attn_stamps[0] += __builtin_amdgcn_s_memtime() - entry_;
+        g_attn_stamps[1] += 1;
+    }
+#endif
+    if constexpr (PRE2) load_group(gb, base + NW * PG);
+
+    // ---- the rest of the prologue, under the K/V round trip: rotation, LDS, barrier, q read-back; then the append by the owner ----
+    if constexpr (FUSED)
+    {
+        if (rotates && act)
+        {
+            rope_rotate8_regs(lo, hi, c0, c1, s0, s1);
+            st16(qs + (size_t)wave * HS + (size_t)lane * 8, lo);
+            st16(qs + (size_t)wave * HS + (size_t)(lane + hv) * 8, hi);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int g = 0; g < GH; ++g)
+        {
+            if (owner) load_row<EPL>(q[g], qs + (size_t)g * HS + lane * EPL);
+            else
+            {
+#pragma unroll
+                for (int e = 0; e < NPAIR; ++e) q[g][e] = 0u;
+            }
+        }
+        if (has_row && wave >= GH && owns_new && hg == 0 && act)
+        {
+            uint16_t* dst = (wave == GH ? kbase : vbase) + (size_t)ring_row(pos) * HS;
+            st16(dst + (size_t)lane * 8, lo);
+            st16(dst + (size_t)(lane + hv) * 8, hi);
         }
     }
 
@@ -366,23 +423,28 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATT
                 for (int e = 0; e < NPAIR; ++e) a = dot2_bf16(as_bf16x2(q[g][e]), as_bf16x2(gbuf.k[j][e]), a);
                 sc[j][g] = a;
             }
+#ifdef MILA_ATTN_STAMPS
+        if (stamp_score_)
+        {
+            asm volatile("" :: "v"(sc[0][0]));             // the stamp stands behind the first score
+            if (stamps_) g_attn_stamps[2] += __builtin_amdgcn_s_memtime() - entry_;
+            stamp_score_ = false;
+        }
+#endif
         decode_softmax_step<GH, Row>(sc, gbuf.v, m, l, o, base_, end, p.scale);
     };
-    for (;;)
-    {
-        if (base >= end) break;
-        int nb = base + NW * PG;
-        if (nb < end) load_group(gb, nb);
-        patch_new(ga, base);
-        compute_group(ga, base);
+    // one step: request the group after `cur` into `nxt` (unless it is in flight already), then score `cur`
+    auto step = [&](KVG& cur, KVG& nxt, bool nxt_in_flight) -> bool {
+        if (base >= end) return false;
+        const int nb = base + NW * PG;
+        if (!nxt_in_flight && nb < end) load_group(nxt, nb);
+        patch_new(cur, base);
+        compute_group(cur, base);
         base = nb;
-        if (base >= end) break;
-        nb = base + NW * PG;
-        if (nb < end) load_group(ga, nb);
-        patch_new(gb, base);
-        compute_group(gb, base);
-        base = nb;
-    }
+        return true;
+    };
+    if (step(ga, gb, PRE2))
+        while (step(gb, ga, false) && step(ga, gb, false)) {}
 
     const DecodeFinishArgs a{p.Y, p.scratch, p.NH, p.splits, split, b, h0, p.tickets != nullptr};
     decode_finish<HS, GH, Row>(a, m, l, o, sm);
@@ -648,8 +710,12 @@ static int launch_decode_mfma(const AttnParams& p, int B, hipStream_t s)
 }
 
 template <int HS, int GH, bool FUSED>
-static int launch_decode(const AttnParams& p, int B, hipStream_t s)
+static int launch_decode(const AttnParams& params, int B, hipStream_t s)
 {
+    AttnParams p = params;
+    const SplitDiv sd = split_div_make((uint32_t)p.splits);
+    p.split_mul = sd.mul;
+    p.split_shift = sd.shift;
     const int hgroups = (p.NH / p.NKV) / GH;
     note_form("attn_decode");
     const size_t lds = (size_t)kDecodeWaves * GH * (HS + 2) * sizeof(float) + (size_t)(GH + 2) * HS * 2;
@@ -856,9 +922,9 @@ using namespace mila;
 extern "C" {
 
 #ifdef MILA_ATTN_STAMPS
-MILA_API int mila_dbg_attn_stamps(unsigned long long* out2)
+MILA_API int mila_dbg_attn_stamps(unsigned long long* out3)
 {
-    return (int)hipMemcpyFromSymbol(out2, HIP_SYMBOL(mila::g_attn_stamps), 2 * sizeof(unsigned long long));
+    return (int)hipMemcpyFromSymbol(out3, HIP_SYMBOL(mila::g_attn_stamps), 3 * sizeof(unsigned long long));
 }
 #endif
 

@@ -1,5 +1,5 @@
-"""Launch -> first K/V request of the fused decode-attention kernel, in shader cycles, from diagnostic libraries built by attn_stamps.sh (lane 0 of workgroup (0, 0, 0) stamps
-its first instruction and the issue of its first K/V row loads): Gemma's sliding-window and global layer shapes at position 2100, position read from device memory, hot
+"""Launch -> first K/V request and launch -> first score of the fused decode-attention kernel, in shader cycles, from diagnostic libraries built by attn_stamps.sh
+(lane 0 of workgroup (0, 0, 0) stamps its first instruction, the issue of its first K/V row loads and the first score of its first group): Gemma's sliding-window and global layer shapes at position 2100, position read from device memory, hot
 (launches back to back) and cold (an untimed 1 GiB read-only pass before every launch, as the weight stream leaves the caches in a decode step).
     python tools/experiments/attn_stamps.py after=<lib> before=<lib>"""
 import ctypes as C
@@ -47,23 +47,25 @@ def main():
 
             def read():
                 torch.cuda.synchronize()
-                out = (C.c_ulonglong * 2)()
+                out = (C.c_ulonglong * 3)()
                 assert lib.mila_dbg_attn_stamps(out) == 0
-                return out[0], out[1]
+                return out[0], out[1], out[2]
             for mode in ("hot", "cold"):
-                per_pass = []
+                per_pass, per_pass_score = [], []
                 for _ in range(5):
                     for _ in range(3):
                         launch()
-                    c0, n0 = read()
+                    c0, n0, s0 = read()
                     for _ in range(20):
                         if mode == "cold":
                             assert lib.mila_cdna4_stream_read(P(sink), P(flush_src), C.c_size_t(FLUSH_BYTES), st) == 0
                         launch()
-                    c1, n1 = read()
+                    c1, n1, s1 = read()
                     per_pass.append((c1 - c0) / (n1 - n0))
+                    per_pass_score.append((s1 - s0) / (n1 - n0))
                 print(json.dumps({"shape": shape, "build": name, "mode": mode, "cycles_launch_to_first_kv_request": round(sorted(per_pass)[2]),
-                                  "passes": [round(x) for x in per_pass]}), flush=True)
+                                  "cycles_launch_to_first_score": round(sorted(per_pass_score)[2]),
+                                  "passes": [round(x) for x in per_pass], "passes_score": [round(x) for x in per_pass_score]}), flush=True)
 
 
 if __name__ == "__main__":
