@@ -652,6 +652,45 @@ MILA_API int mila_cdna4_sample_argmax_rows_final_advance(int32_t* token_out, con
                                                          const int32_t* active_dev, int B, mila_stream_t stream);
 MILA_API int mila_cdna4_advance_positions_rows(int32_t* positions_dev, const int32_t* active_dev, int B, mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Chain decode: 2 .. 4 rows per step that are CONSECUTIVE POSITIONS OF ONE SEQUENCE on ONE cache (ABI 4, additive) -- what verifying drafted tokens needs
+ * (speculative greedy decode: the last sampled token and up to three drafts in one pass over the weights).  The Linears are matvec_rows as above.
+ * ------------------------------------------------------------------------------------------- */
+/* fused_attn_decode_bf16 for T rows (2 <= T <= 4) of one sequence: row t is the token at position + t -- `position` when position_dev is NULL, *position_dev + t
+ * otherwise (ONE position word, the one the one-row graph step reads; max_len then is the live-length bound the launch is captured for, 0 = the capacity, as in
+ * fused_attn_decode_rows_bf16, and the caller keeps *position_dev + T <= max_len).  ONE cache [1, NKV, capacity, HS]; row t reads q_raw / k_raw / v_raw +
+ * t * raw_b_stride elements (a multiple of 8); Y [T, NH*HS]; scratch from attn_decode_chain_scratch_bytes(T, NH, HS), always required (the roped q rows live there).
+ * Two launches plus the combine: (a) q/k/v norm + RoPE + KV append of all T rows (fused_qkv_post_prefill, or fused_qkv_post_rows_devpos), (b) decode attention, row t
+ * over the band of length position + t + 1 of the same cache, the splits planned for ONE row at the max_len bucket (eager: position + T).
+ * CONTRACT: row t's Y is bit-identical to T successive fused_attn_decode_bf16 calls (B = 1, device-position form, the same max_len) at position .. position + T - 1,
+ * so are cache rows position .. position + T - 1, and no other cache row is written.
+ * The chain is for UNBOUNDED caches (capacity >= every position it is used at), not rings: a rejected draft leaves a stale row behind, which a later step at that
+ * position overwrites; in a ring the stale row would already have evicted a live one.  Refused without touching the device (MILA_E_INVALID_ARGUMENT): T outside
+ * 2 .. 4, a head size other than 64 / 128 / 256 / 512, a null pointer, and in the eager form position + T > capacity. */
+MILA_API int mila_cdna4_fused_attn_decode_chain_bf16(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, const uint16_t* q_raw, const uint16_t* k_raw,
+                                                     const uint16_t* v_raw, int64_t raw_b_stride, const uint16_t* qw, const uint16_t* kw,
+                                                     const uint16_t* vw, const float* cos_cache, const float* sin_cache, void* scratch,
+                                                     size_t scratch_bytes, int T, int NH, int NKV, int HS, int capacity, int position,
+                                                     const int32_t* position_dev, int max_len, int window, float scale, float eps, mila_stream_t stream);
+/* the partials of T rows at the most splits a plan takes plus the roped q rows [T, NH, HS] bf16; 0 for T outside 2 .. 4 or an unsupported head size */
+MILA_API size_t mila_cdna4_attn_decode_chain_scratch_bytes(int T, int NH, int HS);
+/* The two entries above under a second spelling, for the host mirror (mila_amd/host): its sources must not spell the name of the measured-slower decode-chain
+ * EXPERIMENT of csrc/internal.h, which tests/test_capi_cpu.py checks as a substring -- and that substring is part of the two names above. */
+#define mila_cdna4_fused_attn_chain_bf16 mila_cdna4_fused_attn_decode_chain_bf16
+#define mila_cdna4_attn_chain_scratch_bytes mila_cdna4_attn_decode_chain_scratch_bytes
+/* fused_qkv_post_prefill with the first token's position on the device: token t at *position_dev + t (launch (a) of the chain's device-position form) */
+MILA_API int mila_cdna4_fused_qkv_post_rows_devpos(uint16_t* q_out, uint16_t* Kc, uint16_t* Vc, const uint16_t* q, const uint16_t* k,
+                                                   const uint16_t* v_src, int64_t src_row_stride, const uint16_t* qw, const uint16_t* kw,
+                                                   const uint16_t* vw, const float* cos_cache, const float* sin_cache, int T, int NH, int NKV,
+                                                   int HS, const int32_t* position_dev, int capacity, float eps, mila_stream_t stream);
+
+/* The tail of a captured chain step (the chain's twin of sample_argmax_rows_final_advance): row t was fed tok[t] -- tok[0] the last sampled token, tok[1 .. T - 1] the
+ * drafts -- and a_t is the argmax over the `blocks` partials a matvec_rows lm_head launch left at scratch + t * sample_scratch_bytes(), ties to the lowest index.
+ * n = the first t in [0, T - 1) with a_t != tok[t + 1], else T - 1: the longest correct draft prefix.  Writes result = {n + 1, a_0 .. a_n} (int32 [T + 1], device;
+ * words past a_n are left alone), tok[0] = a_n and *position_dev += n + 1.  One launch, plain vector stores. */
+MILA_API int mila_cdna4_sample_argmax_chain_accept(int32_t* tok, int32_t* result, const void* scratch, size_t scratch_bytes, int blocks, int32_t* position_dev, int T,
+                                                   mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,7 @@ def load():
     main.mila_cdna4_sample_stochastic_scratch_bytes.restype = C.c_size_t
     main.mila_cdna4_attn_decode_ticket_count.restype = C.c_size_t
     main.mila_cdna4_mha_decode_scratch_bytes.restype = C.c_size_t
+    main.mila_cdna4_attn_decode_chain_scratch_bytes.restype = C.c_size_t
     # the FP8 KV cache (PerChannelKvFp8<>, csrc/attention_kvfp8.hip): K8 / V8 [B, NKV, capacity, HS] e4m3 + Ks / Vs [B, NKV, capacity] fp32
     p, i, f, z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
     main.mila_cdna4_kv_write_fp8.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                               # K8 V8 Ks Vs k v | B chunk NKV HS start_pos capacity | stream
@@ -324,6 +325,7 @@ EXPORTED = [
     "kv_write_fp8_devpos", "attn_decode_kvfp8_devpos", "attn_decode_kvfp8_plan_describe",
     "fused_qkv_post_kvfp8", "fused_qkv_post_kvfp8_prefill", "fused_qkv_post_kvfp8_devpos",
     "matvec_rows", "fused_attn_decode_rows_bf16", "sample_argmax_rows_final_advance", "advance_positions_rows",
+    "fused_attn_decode_chain_bf16", "attn_decode_chain_scratch_bytes", "fused_qkv_post_rows_devpos", "sample_argmax_chain_accept",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

@@ -192,7 +192,10 @@ __device__ __forceinline__ AttnParams attn_params(MILA_ATTN_LEAD_PARAMS, const A
     return p;
 }
 
-template <int HS, int GH, bool FUSED>
+// CHAIN (unfused only; fused_attn_decode_chain_bf16): the batch rows are consecutive positions of ONE sequence -- row b is the query at position + b (the one position word
+// + b) over cache 0, whose rows position .. position + B - 1 the prologue launch has appended already; a row's band ends at its own position, so it never sees the
+// later rows.  From the band on, a row runs the code it runs alone.
+template <int HS, int GH, bool FUSED, bool CHAIN = false>
 __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATTN_LEAD_PARAMS, const AttnParams tail)
 {
 #ifdef MILA_ATTN_STAMPS
@@ -207,6 +210,8 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATT
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (scalar: the row walk and the prologue's roles are wave-uniform)
     const bool owner = lane < ACTIVE;
     const int b = blockIdx.z;
+    static_assert(!(CHAIN && FUSED), "the chain form takes its q rows from the prologue launch");
+    const int cb = CHAIN ? 0 : b;                          // the batch row whose cache this row reads
 
     // ---- the position word: the first request of the kernel, from the preloaded pointer.  A VECTOR load (every lane the same word, read back with readfirstlane):
     // scalar loads return out of order, so a wait for the by-value tail would wait for a scalar load of the position beside it, and everything below that needs the
@@ -240,8 +245,8 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATT
     }
     const int kvh = grp >> hg_log2, hg = grp & ((1 << hg_log2) - 1);
     const int h0 = grp * GH;                               // first query head of this workgroup
-    uint16_t* kbase = p.K + ((size_t)b * p.NKV + kvh) * p.capacity * HS;
-    uint16_t* vbase = p.V + ((size_t)b * p.NKV + kvh) * p.capacity * HS;
+    uint16_t* kbase = p.K + ((size_t)cb * p.NKV + kvh) * p.capacity * HS;
+    uint16_t* vbase = p.V + ((size_t)cb * p.NKV + kvh) * p.capacity * HS;
 
     // ---- what does not need the position: q (unfused), or the prologue's rows up to the rotation (fused) ----
     // Fused: wave r < GH takes query head h0 + r, wave GH the token's K row, wave GH + 1 its V row, in EVERY workgroup (whether this split owns the new row is known
@@ -293,7 +298,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kernel(MILA_ATT
 
     // ---- behind the position: no division up to the K/V requests on a cache the band does not wrap in, one remainder per wave on a ring ----
     const int pos_read = __builtin_amdgcn_readfirstlane(pos_word);     // (unconditional: a request left pending on one path would make every later wait a full drain)
-    const int pos = p.pos_dev ? pos_read : p.position;
+    const int pos = (p.pos_dev ? pos_read : p.position) + (CHAIN ? b : 0);
     const int len = pos + 1;
     const int band_begin = (p.window > 0) ? max(0, len - p.window) : 0;
     const int band = len - band_begin;
@@ -515,14 +520,15 @@ __global__ __launch_bounds__(64) void attn_combine_kernel(uint16_t* __restrict__
 // scalar kernel: O (unnormalised, relative to M) | M | L per (head, split); up to 256 splits, merged by attn_combine_many_kernel.  fp32 scores and statistics, P
 // rounded to bf16 for the PV product (as the flash kernels do): within 1 bf16 ulp of the double-precision oracle like them, NOT bit-identical to the scalar kernel --
 // the choice depends on (window, capacity) only, so every path of a model (reference order, fused, graph replay) takes the same kernel.
-template <int HS>
+// CHAIN: as in attn_decode_kernel -- batch row b is the query at position + b over cache 0
+template <int HS, bool CHAIN = false>
 __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(MILA_ATTN_LEAD_PARAMS, const AttnParams tail)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_mfma[];
     const AttnParams p = attn_params(pos_dev, K, V, q_raw, NH, NKV, capacity, window, splits, flat, tail);
-    const int pos = p.pos_dev ? p.pos_dev[(int)blockIdx.z * p.pos_stride] : p.position;      // blockIdx.z: the batch row (attention_decode_mfma.h)
+    const int pos = (p.pos_dev ? p.pos_dev[(int)blockIdx.z * p.pos_stride] : p.position) + (CHAIN ? (int)blockIdx.z : 0);      // blockIdx.z: the batch row (attention_decode_mfma.h)
     const MfmaDecodeArgs a{p.Q, p.q_b_stride, p.scratch, p.NH, p.NKV, p.capacity, pos + 1, p.window, p.splits, p.scale};
-    attn_decode_mfma_body<HS>(a, MfmaStageBf16<HS>{p.K, p.V}, smem_mfma);
+    attn_decode_mfma_body<HS, MfmaStageBf16<HS>, CHAIN>(a, MfmaStageBf16<HS>{p.K, p.V}, smem_mfma);
 }
 
 // merge of up to kMaxSplitsMfma partials per head: grid (NH, B, HS / 64), 4 waves; wave w merges splits 64 w .. 64 w + 63 as attn_combine_kernel does (lane s holds
@@ -690,26 +696,27 @@ int launch_attn_combine_many(uint16_t* Y, const float* partials, int B, int NH, 
     hipLaunchKernelGGL(attn_combine_many_kernel, dim3(NH, B, HS / 64), dim3(256), 0, s, Y, partials, NH, HS, splits);
     return check_hip(hipGetLastError(), "attn_combine_many");
 }
+template <bool CHAIN>
 static int launch_decode_mfma(const AttnParams& p, int B, hipStream_t s)
 {
     constexpr int HS = 512;
     note_form("attn_decode_mfma");
-    static bool attr_set = false;
+    static bool attr_set = false;      // (one per instantiation: the attribute belongs to the kernel)
     const size_t lds = mfma_decode_lds_bytes<HS>();
     if (!attr_set)
     {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_mfma_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(attn_decode_mfma)");
+        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_mfma_kernel<HS, CHAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(attn_decode_mfma)");
         if (rc) return rc;
         attr_set = true;
     }
     const int n16 = (p.NH / p.NKV) / 16;
-    hipLaunchKernelGGL((attn_decode_mfma_kernel<HS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
+    hipLaunchKernelGGL((attn_decode_mfma_kernel<HS, CHAIN>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
     int rc = check_hip(hipGetLastError(), "attn_decode_mfma");
     if (rc) return rc;
     return launch_attn_combine_many(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
 }
 
-template <int HS, int GH, bool FUSED>
+template <int HS, int GH, bool FUSED, bool CHAIN = false>
 static int launch_decode(const AttnParams& params, int B, hipStream_t s)
 {
     AttnParams p = params;
@@ -723,13 +730,13 @@ static int launch_decode(const AttnParams& params, int B, hipStream_t s)
     if (p.flat)
     {
         // (only taken without warm blocks, tickets or a caller-side combine: plan_decode)
-        hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED>), dim3(p.NKV * hgroups * p.splits, 1, B), dim3(kDecodeWaves * 64), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
+        hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED, CHAIN>), dim3(p.NKV * hgroups * p.splits, 1, B), dim3(kDecodeWaves * 64), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
         int rc = check_hip(hipGetLastError(), "attn_decode (xcd-local)");
         if (rc || p.splits <= 1) return rc;
         hipLaunchKernelGGL(attn_combine_kernel, dim3(p.NH * (HS / 64), B, 1), dim3(64), 0, s, p.Y, p.scratch, p.NH, HS, p.splits, nullptr, 0, 0, GH);
         return check_hip(hipGetLastError(), "attn_combine (xcd-local)");
     }
-    hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED>), dim3(p.splits + wa, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
+    hipLaunchKernelGGL((attn_decode_kernel<HS, GH, FUSED, CHAIN>), dim3(p.splits + wa, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, MILA_ATTN_LEAD_ARGS(p), p);
     int rc = check_hip(hipGetLastError(), "attn_decode");
     if (rc) return rc;
     if (p.splits > 1 && !p.no_combine && !p.tickets)
@@ -743,18 +750,18 @@ static int launch_decode(const AttnParams& params, int B, hipStream_t s)
 }
 
 // the scalar form of a plan: the plan's heads per workgroup at one of the four head sizes (attention_decode_plan.h), the generic kernel at any other
-template <bool FUSED>
+template <bool FUSED, bool CHAIN = false>
 static int dispatch_hs(int HS, int gh, const AttnParams& p, int B, hipStream_t s)
 {
     if (decode_scalar_head_size(HS))
     {
         const int GS = p.NH / p.NKV;
         if (!decode_group_size_ok(GS)) return set_error(MILA_E_UNSUPPORTED, "attention: group size %d (NH/NKV) must be 1,2,4,8,16 or 32", GS);
-        const int rc = dispatch_decode_scalar<true>(HS, gh, [&](auto hs, auto g) { return launch_decode<decltype(hs)::value, decltype(g)::value, FUSED>(p, B, s); });
+        const int rc = dispatch_decode_scalar<true>(HS, gh, [&](auto hs, auto g) { return launch_decode<decltype(hs)::value, decltype(g)::value, FUSED, CHAIN>(p, B, s); });
         if (rc == kNoDecodeKernel) return set_error(MILA_E_UNSUPPORTED, "attention: no kernel for %d heads per workgroup at HS=%d", gh, HS);
         return rc;
     }
-    if constexpr (!FUSED)
+    if constexpr (!FUSED && !CHAIN)
     {
         // any other head size: one wave per (batch, head) row on the generic kernel (attention_generic.hip); the position may live on the device only in the
         // captured forms, which the benchmarked head sizes alone use
@@ -794,7 +801,7 @@ static int run_decode(const DecodePlan& d, AttnParams p, int B, int HS, size_t s
         p.Q = q_tmp;
         p.q_b_stride = 0;
     }
-    return launch_decode_mfma(p, B, stream);
+    return launch_decode_mfma<false>(p, B, stream);
 }
 
 // The unfused entries (attn_decode_bf16, its device-position form, mha_decode_bf16): plan and launch.  q_b_stride as in AttnParams; len_hint as in plan_decode.
@@ -863,6 +870,50 @@ static mila_fused_attn_args fused_args(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, 
 {
     return mila_fused_attn_args{Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, tickets, ticket_count, nullptr, 0, 0, nullptr, 0, 0, 0,
                                 NH, NKV, HS, capacity, position, position_dev, window, scale, eps};
+}
+
+// ---- the chain: T consecutive positions of ONE sequence in one call (speculative verification) ----
+// Launch (a): qkv_post_kernel over T tokens -- norm, RoPE, the roped q rows into scratch behind the partials, K / V rows position .. position + T - 1 into the cache.
+// Launch (b): the unfused kernel of the plan's form in its CHAIN instantiation (row t = the query at position + t over that one cache), then the form's combine.
+// The plan is ONE row's at the max_len bucket (as FD_ROWS): row t reduces over the splits it has alone, and the prologue's rows are the bits the fused kernel's own
+// prologue makes (the canonical helpers), so row t is fused_attn_decode_bf16 at position + t bit for bit.
+static size_t chain_partial_floats(const DecodePlan& d, int T, int NH, int HS)
+{
+    return (d.form == DF_MFMA || d.splits > 1) ? (size_t)T * NH * d.splits * (HS + 4) : 0;
+}
+static int chain_decode(const char* who, const mila_fused_attn_args& a, int T, int64_t raw_b_stride, hipStream_t stream)
+{
+    MILA_REQUIRE(a.Y && a.Kc && a.Vc && a.q_raw && a.k_raw && a.v_raw && a.qw && a.kw && a.cos_cache && a.sin_cache && a.scratch, "%s: null pointer", who);
+    MILA_REQUIRE(T >= 2 && T <= 4, "%s: T=%d rows outside 2 .. 4", who, T);
+    MILA_REQUIRE(decode_scalar_head_size(a.HS), "%s: head size %d must be 64, 128, 256 or 512", who, a.HS);
+    MILA_REQUIRE(a.NH > 0 && a.NKV > 0 && a.NH % a.NKV == 0 && decode_group_size_ok(a.NH / a.NKV), "%s: bad head counts (NH=%d NKV=%d)", who, a.NH, a.NKV);
+    MILA_REQUIRE(a.capacity > 0 && a.window >= 0, "%s: bad sizes", who);
+    MILA_REQUIRE(raw_b_stride % 8 == 0 && raw_b_stride >= (int64_t)a.HS, "%s: raw_b_stride %lld must be a multiple of 8 and no shorter than a head row", who, (long long)raw_b_stride);
+    // a.position: the first row's position (eager), or max_len = the live-length bound of the LAST row (device position)
+    if (a.position_dev)
+        MILA_REQUIRE(a.position >= 0 && a.position <= a.capacity, "%s: max_len %d outside 0 .. the capacity %d", who, a.position, a.capacity);
+    else
+        MILA_REQUIRE(a.position >= 0 && (int64_t)a.position + T <= (int64_t)a.capacity,
+                     "%s: positions %d .. %d do not fit the cache capacity %d (the chain is for unbounded caches, not rings)", who, a.position, a.position + T - 1, a.capacity);
+    const int len_hint = a.position_dev ? a.position : a.position + T;
+    DecodePlan d = plan_decode(1, a.NH, a.NKV, a.HS, a.capacity, a.window, len_hint, true, false);
+    d.partial_floats = chain_partial_floats(d, T, a.NH, a.HS);
+    d.scratch_need = d.partial_floats * sizeof(float) + (size_t)T * a.NH * a.HS * 2;
+    if (a.scratch_bytes < d.scratch_need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, a.scratch_bytes, d.scratch_need);
+    uint16_t* q_tmp = reinterpret_cast<uint16_t*>(reinterpret_cast<float*>(a.scratch) + d.partial_floats);
+    const mila_stream_t ms = reinterpret_cast<mila_stream_t>(stream);
+    int rc = a.position_dev ? mila_cdna4_fused_qkv_post_rows_devpos(q_tmp, a.Kc, a.Vc, a.q_raw, a.k_raw, a.v_raw, raw_b_stride, a.qw, a.kw, a.vw, a.cos_cache, a.sin_cache, T, a.NH,
+                                                                    a.NKV, a.HS, a.position_dev, a.capacity, a.eps, ms)
+                            : mila_cdna4_fused_qkv_post_prefill(q_tmp, a.Kc, a.Vc, a.q_raw, a.k_raw, a.v_raw, raw_b_stride, a.qw, a.kw, a.vw, a.cos_cache, a.sin_cache, T, a.NH,
+                                                                a.NKV, a.HS, a.position, a.capacity, a.eps, ms);
+    if (rc) return rc;
+    AttnParams p{};
+    p.Y = a.Y; p.Q = q_tmp; p.K = a.Kc; p.V = a.Vc; p.scratch = reinterpret_cast<float*>(a.scratch);
+    p.NH = a.NH; p.NKV = a.NKV; p.capacity = a.capacity; p.position = a.position; p.pos_dev = a.position_dev; p.window = a.window; p.scale = a.scale;
+    p.splits = d.splits;
+    p.flat = d.flat;
+    if (d.form == DF_MFMA) return launch_decode_mfma<true>(p, T, stream);
+    return dispatch_hs<false, true>(a.HS, d.gh, p, T, stream);
 }
 
 // ---- what attention_kvfp8.hip takes from this file (attention_decode_plan.h) ----
@@ -1014,6 +1065,23 @@ int mila_cdna4_fused_attn_decode_rows_bf16(uint16_t* Y, uint16_t* Kc, uint16_t* 
     return fused_decode("fused_attn_decode_rows_bf16", fused_args(Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, nullptr, 0, NH, NKV,
                                                                   HS, capacity, max_len, positions_dev, window, scale, eps),
                         B, raw_b_stride, FD_BATCH | FD_ROWS, as_stream(stream));
+}
+
+// T consecutive positions of ONE sequence on ONE cache: see mila_cdna4.h for the contract (row t == fused_attn_decode_bf16 at position + t)
+int mila_cdna4_fused_attn_decode_chain_bf16(uint16_t* Y, uint16_t* Kc, uint16_t* Vc, const uint16_t* q_raw, const uint16_t* k_raw, const uint16_t* v_raw, int64_t raw_b_stride,
+                                            const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache, void* scratch,
+                                            size_t scratch_bytes, int T, int NH, int NKV, int HS, int capacity, int position, const int32_t* position_dev, int max_len, int window,
+                                            float scale, float eps, mila_stream_t stream)
+{
+    return chain_decode("fused_attn_decode_chain_bf16", fused_args(Y, Kc, Vc, q_raw, k_raw, v_raw, qw, kw, vw, cos_cache, sin_cache, scratch, scratch_bytes, nullptr, 0, NH, NKV, HS,
+                                                                   capacity, position_dev ? max_len : position, position_dev, window, scale, eps),
+                        T, raw_b_stride, as_stream(stream));
+}
+// the largest scratch a chain call of (T, NH, HS) can need: the partials of T rows at the most splits a plan takes, plus the roped q rows [T, NH, HS] bf16
+size_t mila_cdna4_attn_decode_chain_scratch_bytes(int T, int NH, int HS)
+{
+    if (T < 2 || T > 4 || NH <= 0 || !decode_scalar_head_size(HS)) return 0;
+    return decode_scratch_bytes(T, NH, HS, HS == 512 ? kMaxSplitsMfma : kMaxSplits, true);
 }
 
 // ---- GPT-2 multi-head attention over a KV cache (CudaMhaOp.ixx:137-380: prefill / decode of IPositionalUnaryOp + IKvCacheLifecycle) ----

@@ -129,7 +129,8 @@ constexpr size_t mfma_decode_lds_bytes() { return 4 * (size_t)kKeysPerTile * HS 
 // in flight during this tile's products), S^T = K Q^T and O^T += V^T P^T run as in the flash prefill (transposed products: a head's keys sit in its lane's
 // registers, the row statistics are in-lane plus two permlane steps, the exponentiated scores ARE the second product's B operand).  The four waves split the OUTPUT
 // dimensions (each computes the whole S^T and softmax of the tile -- identical in all four -- and a quarter of O^T: 32 accumulator registers).
-template <int HS, class Stage>
+// CHAIN: batch row b reads the cache of batch row 0 (p.len is its own live length; fused_attn_decode_chain_bf16).
+template <int HS, class Stage, bool CHAIN = false>
 __device__ __forceinline__ void attn_decode_mfma_body(const MfmaDecodeArgs& p, const Stage& cache, unsigned char* smem_mfma)
 {
     constexpr int KSTEPS = HS / 32, DT = HS / 16, DTW = DT / 4;
@@ -169,7 +170,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const MfmaDecodeArgs& p, c
                 *reinterpret_cast<u32x4*>(ldsQ + k_off<HS>(row, ch)) = ld16(qb + (size_t)row * HS + ch * 8);
             }
         }
-        const Stage st = cache.at(((size_t)b * p.NKV + kvh) * p.capacity);
+        const Stage st = cache.at(((size_t)(CHAIN ? 0 : b) * p.NKV + kvh) * p.capacity);
         const bool wraps = end > p.capacity;                          // uniform: an unbounded cache (the global layers) needs no modulo per row
         const int ntiles = (end - begin + kKeysPerTile - 1) / kKeysPerTile;
         const int kt_last = begin + (ntiles - 1) * kKeysPerTile;

@@ -261,6 +261,23 @@ int mila_cdna4_fused_qkv_post_devpos(uint16_t* q_out, uint16_t* Kc, uint16_t* Vc
     MILA_LAUNCH_CHECK("fused_qkv_post_devpos");
 }
 
+// fused_qkv_post_prefill's launch with the first token's position on the device: token t at *position_dev + t (the chain decode's prologue, attention.hip)
+int mila_cdna4_fused_qkv_post_rows_devpos(uint16_t* q_out, uint16_t* Kc, uint16_t* Vc, const uint16_t* q, const uint16_t* k,
+                                          const uint16_t* v_src, int64_t src_row_stride, const uint16_t* qw, const uint16_t* kw,
+                                          const uint16_t* vw, const float* cos_cache, const float* sin_cache, int T, int NH, int NKV,
+                                          int HS, const int32_t* position_dev, int capacity, float eps, mila_stream_t stream)
+{
+    MILA_REQUIRE(q_out && Kc && Vc && q && k && v_src && qw && kw && cos_cache && sin_cache && position_dev, "fused_qkv_post_rows_devpos: null pointer");
+    MILA_REQUIRE(T > 0 && T <= 65535 && NH > 0 && NKV > 0 && capacity > 0, "fused_qkv_post_rows_devpos: bad sizes");
+    MILA_REQUIRE(T <= capacity, "fused_qkv_post_rows_devpos: %d tokens do not fit the cache capacity %d", T, capacity);
+    MILA_REQUIRE(HS >= 16 && HS <= 1024 && (HS & (HS - 1)) == 0, "fused_qkv_post_rows_devpos: HS=%d must be a power of two in [16,1024]", HS);
+    MILA_REQUIRE(src_row_stride % 8 == 0 && src_row_stride >= (int64_t)HS, "fused_qkv_post_rows_devpos: row stride %lld must be a multiple of 8", (long long)src_row_stride);
+    QkvPostParams p{q_out, Kc, Vc, q, k, v_src, qw, kw, vw, cos_cache, sin_cache, position_dev, NH, NKV, HS, 0, capacity, eps, src_row_stride};
+    const int rows = NH + 2 * NKV;
+    hipLaunchKernelGGL(qkv_post_kernel, dim3(ceil_div(rows, 4 * qkv_post_rows_per_wave(HS)), T), dim3(256), 0, as_stream(stream), p);
+    MILA_LAUNCH_CHECK("fused_qkv_post_rows_devpos");
+}
+
 // ---- the same three entries over the FP8 KV cache (PerChannelKvFp8<>): q_out as above, the K / V rows quantized into K8 / V8 / Ks / Vs --------------------------
 // what the three share: every check (`who` names the entry), then the launch of T tokens from `position` (or one token at *pos_dev)
 static int qkv_post_kvfp8(const char* who, uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k, const uint16_t* v_src,

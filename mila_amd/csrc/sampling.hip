@@ -123,6 +123,38 @@ __global__ __launch_bounds__(256) void argmax_rows_final_advance_kernel(const fl
     }
 }
 
+// The chain's tail (speculative verification): rows 0 .. T - 1 are consecutive positions of ONE sequence, row t fed with tok[t] (tok[0] the last sampled token,
+// tok[1 ..] the drafts).  One workgroup, wave t reduces row t's n partials to a_t (argmax is exact in any order: the greedy sampler's token); then one lane accepts
+// the longest correct draft prefix: n_acc = the first t in [0, T - 1) with a_t != tok[t + 1], else T - 1.  result = {n_acc + 1, a_0 .. a_n_acc} (the other words are
+// left alone), tok[0] = a_n_acc (the next step's input), *pos += n_acc + 1.
+__global__ __launch_bounds__(256) void argmax_chain_accept_kernel(const float* __restrict__ pv0, int32_t* __restrict__ tok, int32_t* __restrict__ result, int32_t* __restrict__ pos,
+                                                                  int n, int row_floats, int T)
+{
+    __shared__ int sa[4];
+    const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+    if (t < T)
+    {
+        const float* pv = pv0 + (size_t)t * row_floats;
+        const int* pi = reinterpret_cast<const int*>(pv + kArgmaxBlocks);
+        float bv = -FLT_MAX;
+        int bi = 0x7fffffff;
+        for (int i = lane; i < n; i += 64) better(bv, bi, pv[i], pi[i]);
+        wave_argmax(bv, bi);
+        if (lane == 0) sa[t] = (bi == 0x7fffffff) ? 0 : bi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        int n_acc = T - 1;
+        for (int i = T - 2; i >= 0; --i)
+            if (sa[i] != tok[i + 1]) n_acc = i;
+        result[0] = n_acc + 1;
+        for (int i = 0; i <= n_acc; ++i) result[1 + i] = sa[i];
+        tok[0] = sa[n_acc];
+        *pos += n_acc + 1;
+    }
+}
+
 __global__ __launch_bounds__(64) void advance_positions_rows_kernel(int32_t* __restrict__ pos, const int32_t* __restrict__ active, int B)
 {
     const int b = threadIdx.x;
@@ -912,6 +944,20 @@ int mila_cdna4_sample_argmax_rows_final_advance(int32_t* token_out, const void* 
     hipLaunchKernelGGL(argmax_rows_final_advance_kernel, dim3(B), dim3(256), 0, as_stream(stream), reinterpret_cast<const float*>(scratch), token_out, positions_dev, active_dev,
                        blocks, (int)(per_row / sizeof(float)));
     MILA_LAUNCH_CHECK("sample_argmax_rows_final_advance");
+}
+
+// the chain twin: rows are consecutive positions of one sequence; see mila_cdna4.h for the acceptance rule
+int mila_cdna4_sample_argmax_chain_accept(int32_t* tok, int32_t* result, const void* scratch, size_t scratch_bytes, int blocks, int32_t* position_dev, int T,
+                                          mila_stream_t stream)
+{
+    MILA_REQUIRE(tok && result && scratch && position_dev, "sample_argmax_chain_accept: null pointer");
+    MILA_REQUIRE(T >= 2 && T <= 4, "sample_argmax_chain_accept: T=%d rows outside 2 .. 4", T);
+    MILA_REQUIRE(blocks > 0 && blocks <= kArgmaxBlocks, "sample_argmax_chain_accept: blocks %d out of range (1 .. %d)", blocks, kArgmaxBlocks);
+    const size_t per_row = (size_t)kArgmaxBlocks * 8;
+    if (scratch_bytes < per_row * T) return set_error(MILA_E_SCRATCH_TOO_SMALL, "sample_argmax_chain_accept: scratch %zu bytes < required %zu", scratch_bytes, per_row * T);
+    hipLaunchKernelGGL(argmax_chain_accept_kernel, dim3(1), dim3(256), 0, as_stream(stream), reinterpret_cast<const float*>(scratch), tok, result, position_dev, blocks,
+                       (int)(per_row / sizeof(float)), T);
+    MILA_LAUNCH_CHECK("sample_argmax_chain_accept");
 }
 
 int mila_cdna4_advance_positions_rows(int32_t* positions_dev, const int32_t* active_dev, int B, mila_stream_t stream)

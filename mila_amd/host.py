@@ -84,13 +84,15 @@ class Gemma:
 
     MODES = {"reference": 0, "fused": 1, "graph": 2}
 
-    def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None, kv_fp8=False, max_batch=None):
+    def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None, kv_fp8=False, max_batch=None, draft_tokens=None):
         """device: HIP device ordinal; default = this process's LOCAL_RANK (one replica per GPU under torch.distributed.run).
         profile: synthetic-parameter multipliers {linear_gain, qk_norm_center, post_norm_center, layer_scalar, table_gain}
         (GemmaTransformer::SyntheticProfile; None = the unit-scale generator of SURVEY.md section 8d)
         kv_fp8: PerChannelKvFp8<> on every layer -- e4m3 K / V + one fp32 scale per KV head per cached token (also: config["kv_fp8"] = 1)
         max_batch: GemmaConfig::max_batch (1 .. 4) through mila_gemma_create_rows -- independent sequences per decode step (prefill_row / decode_rows); None = the
-        one-sequence model of mila_gemma_create"""
+        one-sequence model of mila_gemma_create
+        draft_tokens: GemmaConfig::draft_tokens (0 .. 3) through mila_gemma_create_chain -- the chain step (decode_chain) verifies that many drafted tokens; 0 builds
+        the plain model through the same entry; None = not through that entry"""
         lib = load()
         if device is None:
             from .replicas import local_device
@@ -104,7 +106,12 @@ class Gemma:
         c = GemmaConfigC(**self.cfg)
         self.vocab = self.cfg["vocab_size"]
         self.max_batch = 1 if max_batch is None else int(max_batch)
-        if max_batch is None:
+        self.draft_tokens = 0 if draft_tokens is None else int(draft_tokens)
+        if draft_tokens is not None:
+            lib.mila_gemma_create_chain.restype = C.c_void_p
+            lib.mila_gemma_create_chain.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int]
+            self.h = lib.mila_gemma_create_chain(POLICIES[policy], C.byref(c), max_seq, max_prefill, self.max_batch, self.draft_tokens, seed, device)
+        elif max_batch is None:
             self.h = lib.mila_gemma_create(POLICIES[policy], C.byref(c), max_seq, max_prefill, seed, device)
         else:
             lib.mila_gemma_create_rows.restype = C.c_void_p
@@ -291,6 +298,36 @@ class Gemma:
         _check(lib.mila_gemma_time_decode_rows(self.h, int(B), int(start_position), int(steps), int(warmup), out))
         return {"wall_ms_per_step": out[0], "device_ms_per_step": out[1]}
 
+    # ---- chain decode: consecutive positions of one sequence (draft_tokens > 0) ----
+    def decode_chain(self, tokens, position, mode="graph"):
+        """one chain step: tokens[0] is decoded at `position`, tokens[1:] are drafts for the positions behind it (2 <= len(tokens) <= draft_tokens + 1), eager
+        ("fused") or as a graph replay.  Returns (logits [T, vocab], count, accepted tokens [count], new position): the longest correct draft prefix is accepted,
+        so accepted[i] is the greedy token after tokens[:i + 1] and the position advances by count."""
+        lib = load()
+        lib.mila_gemma_chain_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        T = int(t.size)
+        logits, out = np.empty((T, self.vocab), dtype=np.float32), np.zeros(T + 2, dtype=np.int32)
+        _check(lib.mila_gemma_chain_decode(self.h, t.ctypes.data, T, int(position), {"fused": 1, "graph": 2}[mode], logits.ctypes.data, out.ctypes.data))
+        count = int(out[0])
+        return logits, count, out[1:1 + count].tolist(), int(out[T + 1])
+
+    def chain_graph_info(self):
+        """{"captures": captures of the chain graph so far, "nodes": kernel nodes of the captured chain step, "rows": its row count}"""
+        lib = load()
+        lib.mila_gemma_chain_graph_info.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_int64 * 3)()
+        _check(lib.mila_gemma_chain_graph_info(self.h, out))
+        return {"captures": out[0], "nodes": out[1], "rows": out[2]}
+
+    def time_decode_chain(self, T, start_position, steps, warmup):
+        """`steps` graph replays of a T-row chain step from start_position (every step advances by what it accepts)"""
+        lib = load()
+        lib.mila_gemma_time_chain_decode.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        out = (C.c_double * 2)()
+        _check(lib.mila_gemma_time_chain_decode(self.h, int(T), int(start_position), int(steps), int(warmup), out))
+        return {"wall_ms_per_step": out[0], "device_ms_per_step": out[1]}
+
     def time_decode(self, start_position, steps, warmup, mode="graph"):
         out = (C.c_double * 2)()
         _check(load().mila_gemma_time_decode(self.h, start_position, steps, warmup, self.MODES[mode], out))
@@ -333,6 +370,30 @@ class Gemma:
         return {"decode_bytes_per_token": out[0], "weight_bytes": out[1], "linear_params": out[2], "table_params": out[3]}
 
 
+def validate_gemma_config(config=None, max_batch=1, draft_tokens=0, kv_fp8=False):
+    """GemmaConfig::validate() on the configuration Gemma(..., max_batch=, draft_tokens=) would build, without a device: raises ValueError with its message"""
+    lib = load()
+    lib.mila_gemma_validate_config.argtypes = [C.POINTER(GemmaConfigC), C.c_int64, C.c_int64]
+    cfg = dict(GEMMA4_12B if config is None else config)
+    cfg.setdefault("bounded_local_kv", 0)
+    cfg.setdefault("kv_fp8", 0)
+    if kv_fp8:
+        cfg["kv_fp8"] = 1
+    c = GemmaConfigC(**cfg)
+    _check(lib.mila_gemma_validate_config(C.byref(c), int(max_batch), int(draft_tokens)))
+
+
+def prompt_lookup_draft(history, k):
+    """the default drafter of the speculative generate() (promptLookupDraft): for n = 3, 2, 1 the latest earlier occurrence of the last n tokens of `history`
+    decides, and the up-to-k tokens that followed it are proposed; no occurrence proposes nothing.  Pure host code."""
+    lib = load()
+    lib.mila_gemma_prompt_lookup_draft.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    h = np.ascontiguousarray(history, dtype=np.int32)
+    out = np.zeros(max(int(k), 1), dtype=np.int32)
+    n = lib.mila_gemma_prompt_lookup_draft(h.ctypes.data if h.size else None, int(h.size), int(k), out.ctypes.data)
+    return out[:n].tolist()
+
+
 GENERATE_STATUS = {0: "stop", 1: "length", 2: "context_limit", 3: "cancelled"}      # GenerateStatus / to_string (Core/GenerateStatus.ixx)
 
 
@@ -371,7 +432,7 @@ class GemmaModel:
         return cls(h, device)
 
     @classmethod
-    def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0, kv_fp8=False, max_batch=None):
+    def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0, kv_fp8=False, max_batch=None, draft_tokens=None):
         lib = cls._bind()
         cfg = dict(GEMMA4_12B if config is None else config)
         cfg.setdefault("bounded_local_kv", 0)
@@ -382,7 +443,13 @@ class GemmaModel:
         p = None
         if profile is not None:
             p = (C.c_float * 5)(*[float(profile[k]) for k in ("linear_gain", "qk_norm_center", "post_norm_center", "layer_scalar", "table_gain")])
-        if max_batch is None:
+        if draft_tokens is not None:      # GemmaModelConfig::withDraftTokens: greedy generate() verifies up to draft_tokens drafted tokens per step
+            if max_batch is not None:
+                raise ValueError("GemmaModel.synthetic: draft_tokens cannot be combined with max_batch")
+            lib.mila_gemma_model_synthetic_chain.restype = C.c_void_p
+            lib.mila_gemma_model_synthetic_chain.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_int]
+            h = lib.mila_gemma_model_synthetic_chain(POLICIES[policy], C.byref(c), context, prefill_chunk, int(draft_tokens), seed, p, device)
+        elif max_batch is None:
             h = lib.mila_gemma_model_synthetic(POLICIES[policy], C.byref(c), context, prefill_chunk, seed, p, device)
         else:      # GemmaModelConfig::withMaxBatch: a model generate_batch() can run on
             lib.mila_gemma_model_synthetic_rows.restype = C.c_void_p
@@ -392,20 +459,42 @@ class GemmaModel:
             cls._raise(lib, "GemmaModel.synthetic")
         return cls(h, device)
 
-    def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None):
+    def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None):
         """-> (tokens passed to on_token, finish reason as GenerateStatus's to_string, prompt tokens served from the KV caches).
         top_k = 1 is greedy (SamplingParams); seed reseeds the host RNG that draws the sampler's uniform; cancel_after = n raises the client's stop request
-        from inside on_token once n tokens were delivered"""
+        from inside on_token once n tokens were delivered.
+        draft_hint (tests and tools; a draft_tokens model): the tokens expected to follow the prompt -- the drafter of the speculative loop reads its proposals from
+        there in place of the prompt lookup; the output is the plain greedy output whatever the hint holds.  speculation_stats() tells what the loop did."""
         lib = load()
         pr = np.ascontiguousarray(prompt, dtype=np.int32)
         st = np.ascontiguousarray(list(stop_tokens), dtype=np.int32)
         cap = int(max_new_tokens) if max_new_tokens is not None else 1 << 16
         out = np.zeros(max(cap, 1), dtype=np.int32)
         n, status, reused = C.c_int64(), C.c_int32(), C.c_int64()
+        if draft_hint is not None:
+            if cancel_after is not None:
+                raise ValueError("GemmaModel.generate: draft_hint cannot be combined with cancel_after")
+            lib.mila_gemma_model_generate_spec.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int64, C.c_void_p, C.c_int64,
+                                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+            hint = np.ascontiguousarray(draft_hint, dtype=np.int32)
+            stats = (C.c_int64 * 4)()
+            _check(lib.mila_gemma_model_generate_spec(self.h, pr.ctypes.data, len(pr), -1 if max_new_tokens is None else int(max_new_tokens), st.ctypes.data if len(st) else None, len(st),
+                                                      float(temperature), int(top_k), float(top_p), -1 if seed is None else int(seed), hint.ctypes.data if hint.size else None,
+                                                      int(hint.size), out.ctypes.data, len(out), C.byref(n), C.byref(status), stats))
+            return out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], 0
         _check(lib.mila_gemma_model_generate(self.h, pr.ctypes.data, len(pr), -1 if max_new_tokens is None else int(max_new_tokens), st.ctypes.data if len(st) else None, len(st),
                                              float(temperature), int(top_k), float(top_p), -1 if seed is None else int(seed), out.ctypes.data, len(out), C.byref(n), C.byref(status),
                                              C.byref(reused), -1 if cancel_after is None else int(cancel_after)))
         return out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], reused.value
+
+    def speculation_stats(self):
+        """GemmaModel::lastSpeculation() of the last generate(): {"steps", "chain_steps", "drafted", "accepted"} -- decode steps in all, those that were chain
+        steps, the drafter's tokens those carried (padding not counted) and how many of them were accepted"""
+        lib = load()
+        lib.mila_gemma_model_speculation_stats.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_int64 * 4)()
+        _check(lib.mila_gemma_model_speculation_stats(self.h, out))
+        return dict(zip(("steps", "chain_steps", "drafted", "accepted"), [int(v) for v in out]))
 
     def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0):
         """GemmaModel::generateBatch: up to max_batch prompts at once, prompt b in row b -> [(tokens, finish reason)] per prompt, by generate()'s rules.  Row b samples

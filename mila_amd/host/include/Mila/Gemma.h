@@ -37,6 +37,7 @@ namespace Mila::Dnn
         bool bounded_local_kv = false;   ///< SlidingWindowKvCache on the sliding-window layers (ring of window + chunk - 1 rows)
         bool kv_fp8 = false;             ///< PerChannelKvFp8<> on every layer: e4m3 K / V + one fp32 scale per KV head per cached token, (HS + 4) / (2 HS) of the bf16 bytes
         dim_t max_batch = 1;             ///< independent sequences a decode step can carry (1 .. 4): KV caches, decode buffers, logits and position words per row
+        dim_t draft_tokens = 0;          ///< drafted tokens a chain step can verify (0 .. 3): the rows decode buffers for draft_tokens + 1 rows on the ONE cache, no extra caches
 
         bool isGlobalLayer( dim_t i ) const { return ( i + 1 ) % sliding_window_pattern == 0; }   // Gemma.Config.ixx:504-507
         dim_t headDim( bool g ) const { return g ? global_head_dim : head_dim; }
@@ -59,6 +60,21 @@ namespace Mila::Dnn
                 throw std::invalid_argument( "GemmaConfig: max_batch " + std::to_string( max_batch ) + " outside 1 .. 4 (the rows kernels keep every row's x in LDS)" );
             if ( max_batch > 1 && kv_fp8 ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with kv_fp8 (the FP8 KV cache's fused append is B = 1)" );
             if ( max_batch > 1 && bounded_local_kv ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with bounded_local_kv (the ring needs a rewind rule per row)" );
+            if ( draft_tokens < 0 || draft_tokens > 3 )
+                throw std::invalid_argument( "GemmaConfig: draft_tokens " + std::to_string( draft_tokens ) + " outside 0 .. 3 (a chain step is the last token plus the drafts: at most the four rows of the rows kernels)" );
+            if ( draft_tokens > 0 )
+            {
+                if ( max_batch > 1 )
+                    throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 cannot be combined with max_batch > 1 (a chain step's rows are consecutive positions of ONE sequence on one cache; "
+                                                 "the rows of a batched step are independent sequences, and the two share the four rows of the rows kernels)" );
+                if ( kv_fp8 ) throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 cannot be combined with kv_fp8 (the FP8 KV cache's fused append is B = 1; the chain over it is not built)" );
+                if ( bounded_local_kv )
+                    throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 cannot be combined with bounded_local_kv (rejected drafts leave stale rows, and a ring may already have evicted what they overwrote)" );
+                for ( dim_t hs : { head_dim, global_head_dim } )
+                    if ( hs != 64 && hs != 128 && hs != 256 && hs != 512 )
+                        throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 needs head dimensions of 64, 128, 256 or 512 (head_dim " + std::to_string( head_dim ) + ", global_head_dim " +
+                                                     std::to_string( global_head_dim ) + ")" );
+            }
             if ( kv_fp8 )
             {
                 if ( bounded_local_kv ) throw std::invalid_argument( "GemmaConfig: kv_fp8 cannot be combined with bounded_local_kv (the FP8 KV cache is unbounded)" );
@@ -144,6 +160,7 @@ namespace Mila::Dnn
         {
             destroyGraph();
             destroyGraphRows();
+            destroyGraphChain();
             for ( auto& e : ov_ev_ ) if ( e ) (void)hipEventDestroy( e );
             if ( ov_stream_ ) (void)hipStreamDestroy( ov_stream_ );
         }
@@ -166,6 +183,7 @@ namespace Mila::Dnn
         {
             destroyGraph();   // layer scalars are baked into the captured launches
             destroyGraphRows();
+            destroyGraphChain();
             // the staging buffer holds the largest matrix of the model: the table, fc_gate_up, or -- on geometries whose attention is wider than the stream -- a packed qkv
             const dim_t attn_w = cfg_.num_heads * std::max( cfg_.head_dim, cfg_.global_head_dim );
             const dim_t qkv_w = attn_w + 2 * std::max( cfg_.num_kv_heads * cfg_.head_dim, cfg_.num_global_kv_heads * cfg_.global_head_dim );
@@ -454,6 +472,82 @@ namespace Mila::Dnn
             return n;
         }
 
+        // ------------------------------------------------------------------------------------
+        // chain decode (GemmaConfig::draft_tokens > 0): one step over T = 2 .. draft_tokens + 1 CONSECUTIVE POSITIONS of the one sequence -- the last sampled token and
+        // T - 1 drafted ones -- on the one KV cache: the rows step with the chain attention entry (mila_cdna4.h) in place of the rows attention, ended by
+        // sample_argmax_chain_accept.  Row t's logits are bit-identical to decodeFused() at position + t given the same history; the accepted tokens are the greedy
+        // ones.  A rejected draft leaves a stale cache row at its position, which the next step there overwrites before anything reads it.
+        // ------------------------------------------------------------------------------------
+        dim_t draftTokens() const noexcept { return cfg_.draft_tokens; }
+        dim_t maxSeq() const noexcept { return max_seq_; }
+        /// tokens[ 0 ] = the token about to be decoded, tokens[ 1 .. T - 1 ] = the drafts; row t is fed tokens[ t ]
+        void setChainDrafts( const int32_t* tokens, int T )
+        {
+            requireChain();
+            if ( T < 1 || T > cfg_.draft_tokens + 1 ) throw std::invalid_argument( "GemmaTransformer::setChainDrafts: 1 .. draft_tokens + 1 tokens" );
+            Compute::rocmCheck( mila_cdna4_memcpy_h2d( rows_->tok->data(), tokens, static_cast<size_t>( T ) * 4, ctx_->getStream() ) );
+        }
+        LogitsTensor& chainLogits() { requireChain(); return *rows_->logits; }
+        /// {count, accepted tokens ...} of the last chain step (device; draft_tokens + 2 words)
+        TokenTensor& chainResult() { requireChain(); return *rows_->result; }
+        /// the position word the one-row graph and the chain step share, read back
+        dim_t devicePosition()
+        {
+            int32_t p = 0;
+            Compute::rocmCheck( mila_cdna4_memcpy_d2h( &p, pos_dev_->data(), 4, ctx_->getStream() ) );
+            ctx_->synchronize();
+            return p;
+        }
+        /// one eager chain step at `position` (the attention launches take the position by value; the tail advances the device position word, set here first)
+        void decodeChain( int T, dim_t position )
+        {
+            checkChainStep( T, position );
+            setDevicePosition( position );
+            enqueueChainStepAndTail( T, bandBucket( position ), ChainAt{ static_cast<int>( position ), nullptr } );      // (checkChainStep: one bucket for all T rows)
+            kv_fill_ = position + T;
+        }
+        /// capture the chain step for T rows from the device position word (set to start_position here, as captureGraph does)
+        void captureGraphChain( int T, dim_t start_position )
+        {
+            checkChainStep( T, start_position );
+            Compute::TraceRange tr( "gemma.captureGraphChain" );
+            setDevicePosition( start_position );
+            destroyGraphChain();
+            hipStream_t s = reinterpret_cast<hipStream_t>( ctx_->getStream() );
+            ctx_->synchronize();
+            hipCheck( hipStreamBeginCapture( s, hipStreamCaptureModeThreadLocal ), "hipStreamBeginCapture" );
+            hipGraph_t g = nullptr;
+            const dim_t band = bandBucket( start_position );
+            try { enqueueChainStepAndTail( T, band, ChainAt{ 0, pos_dev_->data() } ); }      // one linear chain on one stream, like the one-row graph
+            catch ( ... ) { (void)hipStreamEndCapture( s, &g ); if ( g ) (void)hipGraphDestroy( g ); throw; }
+            hipCheck( hipStreamEndCapture( s, &g ), "hipStreamEndCapture" );
+            chain_graph_ = g;
+            const hipError_t e = hipGraphInstantiate( &chain_graph_exec_, chain_graph_, nullptr, nullptr, 0 );
+            if ( e != hipSuccess ) { chain_graph_exec_ = nullptr; destroyGraphChain(); hipCheck( e, "hipGraphInstantiate" ); }
+            chain_captured_T_ = T; chain_captured_band_ = band;
+            ++chain_graph_captures_;
+        }
+        /// capture on first use and whenever T or the live-length bucket changes; does NOT touch the device position word otherwise (the caller's loop owns it)
+        void ensureGraphChain( int T, dim_t position )
+        {
+            checkChainStep( T, position );
+            if ( !chain_graph_exec_ || chain_captured_T_ != T || chain_captured_band_ != bandBucket( position ) ) captureGraphChain( T, position );
+        }
+        void replayGraphChain()
+        {
+            if ( !chain_graph_exec_ ) throw std::runtime_error( "GemmaTransformer::replayGraphChain: captureGraphChain() first" );
+            hipCheck( hipGraphLaunch( chain_graph_exec_, reinterpret_cast<hipStream_t>( ctx_->getStream() ) ), "hipGraphLaunch" );
+        }
+        size_t graphChainCaptureCount() const noexcept { return chain_graph_captures_; }
+        size_t graphChainNodeCount() const
+        {
+            if ( !chain_graph_ ) return 0;
+            size_t n = 0;
+            hipCheck( hipGraphGetNodes( chain_graph_, nullptr, &n ), "hipGraphGetNodes" );
+            return n;
+        }
+        int graphChainRows() const noexcept { return chain_graph_exec_ ? chain_captured_T_ : 0; }
+
         /// greedy device sampler: token <- argmax(logits); the token never leaves the device
         /// (GemmaModel::enqueueSampleNext, Models/GemmaModel.ixx:568)
         void sampleGreedy( TokenTensor& token_out )
@@ -695,7 +789,7 @@ namespace Mila::Dnn
             attn_partials_ = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( ( attnScratchBytes() + 3 ) / 4 ) } );
             // the radix sampler's workspace: model-owned for the same reason (a captured stochastic step's nodes point into it)
             radix_scratch_ = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( ( mila_cdna4_sample_radix_scratch_bytes( (int)cfg_.vocab_size ) + 3 ) / 4 ) } );
-            if ( cfg_.max_batch > 1 ) buildRows();
+            if ( cfg_.max_batch > 1 || cfg_.draft_tokens > 0 ) buildRows();
             ctx_->synchronize();
         }
 
@@ -1020,8 +1114,11 @@ namespace Mila::Dnn
             r.x_stride = x_stride; r.y_stride = y_stride; r.res_stride = res_stride; r.res_out_stride = res_out_stride;
             return r;
         }
-        /// enqueueFusedStep for rows 0 .. B - 1: the same launches on the rows entries.  max_len: the live-length bound of the captured band bucket
-        void enqueueFusedStepRows( int B, int max_len, int* sampler_partials )
+        /// where a chain step's rows sit: row t at position + t (eager), or at *pos_dev + t (the one-row graph's position word)
+        struct ChainAt { int position; const int32_t* pos_dev; };
+        /// enqueueFusedStep for rows 0 .. B - 1: the same launches on the rows entries.  max_len: the live-length bound of the captured band bucket.
+        /// chain != nullptr: the rows are consecutive positions of the ONE sequence on the one cache -- the chain attention entry in place of the rows one
+        void enqueueFusedStepRows( int B, int max_len, int* sampler_partials, const ChainAt* chain = nullptr )
         {
             mila_stream_t st = ctx_->getStream();
             auto& R = *rows_;
@@ -1043,10 +1140,17 @@ namespace Mila::Dnn
                 const uint16_t* qp = R.qkv->data();
                 const uint16_t* kp = qp + (size_t)NH * HD;
                 const uint16_t* vp = g ? kp : kp + (size_t)NKV * HD;
-                Compute::rocmCheck( mila_cdna4_fused_attn_decode_rows_bf16( R.attn->data(), L.keyCacheRows(), L.valueCacheRows(), qp, kp, vp, (int64_t)PK, L.q_norm->getWeight()->data(),
-                                                                            L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(),
-                                                                            R.attn_partials->data(), R.attn_partials->sizeInBytes(), B, NH, NKV, HD, (int)L.cacheCapacity(), R.pos->data(),
-                                                                            max_len, (int)cfg_.windowFor( g ), L.attentionScale(), cfg_.rms_norm_eps, st ) );
+                if ( chain )
+                    Compute::rocmCheck( mila_cdna4_fused_attn_chain_bf16( R.attn->data(), L.keyCache(), L.valueCache(), qp, kp, vp, (int64_t)PK, L.q_norm->getWeight()->data(),
+                                                                                 L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(),
+                                                                                 R.attn_partials->data(), R.attn_partials->sizeInBytes(), B, NH, NKV, HD, (int)L.cacheCapacity(),
+                                                                                 chain->position, chain->pos_dev, max_len, (int)cfg_.windowFor( g ), L.attentionScale(),
+                                                                                 cfg_.rms_norm_eps, st ) );
+                else
+                    Compute::rocmCheck( mila_cdna4_fused_attn_decode_rows_bf16( R.attn->data(), L.keyCacheRows(), L.valueCacheRows(), qp, kp, vp, (int64_t)PK, L.q_norm->getWeight()->data(),
+                                                                                L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(),
+                                                                                R.attn_partials->data(), R.attn_partials->sizeInBytes(), B, NH, NKV, HD, (int)L.cacheCapacity(), R.pos->data(),
+                                                                                max_len, (int)cfg_.windowFor( g ), L.attentionScale(), cfg_.rms_norm_eps, st ) );
                 // 4. o_proj
                 L.o_proj->getOperation().matvecRows( R.o->data(), R.attn->data(), B, (int64_t)NH * HD, D );
                 // 5. post_attn_norm + residual + pre_ffn_norm + gate_up + GeGLU
@@ -1073,9 +1177,38 @@ namespace Mila::Dnn
             else
                 Compute::rocmCheck( mila_cdna4_advance_positions_rows( R.pos->data(), R.active->data(), B, ctx_->getStream() ) );
         }
+        /// a chain step and its tail: the rows step on the chain attention entry, then the accept kernel on the ONE position word (tok[ 0 ] <- the last accepted
+        /// token, result <- {count, accepted tokens}, position += count).  One linear chain on one stream.
+        void enqueueChainStepAndTail( int T, dim_t band, const ChainAt& at )
+        {
+            int partials = 0;
+            enqueueFusedStepRows( T, static_cast<int>( band ), &partials, &at );
+            auto& R = *rows_;
+            Compute::rocmCheck( mila_cdna4_sample_argmax_chain_accept( R.tok->data(), R.result->data(), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(), partials, pos_dev_->data(), T,
+                                                                       ctx_->getStream() ) );
+        }
+        void requireChain() const
+        {
+            if ( !rows_ || cfg_.draft_tokens <= 0 ) throw std::logic_error( "GemmaTransformer: the chain interface needs GemmaConfig::draft_tokens > 0" );
+        }
+        void checkChainStep( int T, dim_t position ) const
+        {
+            requireChain();
+            if ( T < 2 || T > cfg_.draft_tokens + 1 )
+                throw std::invalid_argument( "GemmaTransformer: a chain step takes 2 .. draft_tokens + 1 rows (got " + std::to_string( T ) + ")" );
+            checkPosition( position, T );
+            if ( bandBucket( position ) != bandBucket( position + T - 1 ) )
+                throw std::invalid_argument( "GemmaTransformer: a chain step must not cross a live-length bucket (positions " + std::to_string( position ) + " .. " +
+                                             std::to_string( position + T - 1 ) + "): its later rows would not have the bits they have alone" );
+        }
+        void destroyGraphChain()
+        {
+            if ( chain_graph_exec_ ) { (void)hipGraphExecDestroy( chain_graph_exec_ ); chain_graph_exec_ = nullptr; }
+            if ( chain_graph_ ) { (void)hipGraphDestroy( chain_graph_ ); chain_graph_ = nullptr; }
+        }
         void requireRows( int b ) const
         {
-            if ( !rows_ ) throw std::logic_error( "GemmaTransformer: the rows interface needs GemmaConfig::max_batch > 1" );
+            if ( !rows_ || cfg_.max_batch <= 1 ) throw std::logic_error( "GemmaTransformer: the rows interface needs GemmaConfig::max_batch > 1" );
             if ( b < 0 || b >= cfg_.max_batch ) throw std::invalid_argument( "GemmaTransformer: row " + std::to_string( b ) + " outside max_batch " + std::to_string( cfg_.max_batch ) );
         }
         void checkRowsStep( int B, dim_t max_position ) const
@@ -1094,18 +1227,21 @@ namespace Mila::Dnn
             if ( rows_graph_exec_ ) { (void)hipGraphExecDestroy( rows_graph_exec_ ); rows_graph_exec_ = nullptr; }
             if ( rows_graph_ ) { (void)hipGraphDestroy( rows_graph_ ); rows_graph_ = nullptr; }
         }
-        /// the decode-role buffers of a rows step, [max_batch, width] each; allocated only when max_batch > 1, so a max_batch == 1 model is byte for byte what it was
+        /// the decode-role buffers of a rows step, [rows, width] each; allocated only when max_batch > 1 (rows = max_batch, with a KV cache per row) or draft_tokens > 0
+        /// (rows = draft_tokens + 1 on the ONE cache, plus the chain's result words), so a model with neither is byte for byte what it was
         struct RowsState
         {
             std::unique_ptr<TensorType> qkv, attn, o, down, act, res1, hidden[ 3 ];
             std::unique_ptr<LogitsTensor> logits, sample_scratch, attn_partials;
             std::unique_ptr<TokenTensor> pos, tok, active;
+            std::unique_ptr<TokenTensor> result;      // chain only: {count, accepted tokens ...}, draft_tokens + 2 words
         };
+        dim_t rowsCount() const noexcept { return cfg_.max_batch > 1 ? cfg_.max_batch : cfg_.draft_tokens + 1; }
         void buildRows()
         {
-            const dim_t B = cfg_.max_batch, D = cfg_.embedding_dim;
+            const dim_t B = rowsCount(), D = cfg_.embedding_dim;
             const auto dev = ctx_->getDeviceId();
-            for ( auto& L : layers_ ) L.setCacheRows( static_cast<int>( B ) );
+            if ( cfg_.max_batch > 1 ) for ( auto& L : layers_ ) L.setCacheRows( static_cast<int>( B ) );
             rows_ = std::make_unique<RowsState>();
             auto& R = *rows_;
             R.qkv = std::make_unique<TensorType>( dev, shape_t{ B, std::max( cfg_.packedQkvWidth( false ), cfg_.packedQkvWidth( true ) ) } );
@@ -1121,13 +1257,21 @@ namespace Mila::Dnn
             R.pos = std::make_unique<TokenTensor>( dev, shape_t{ B } );
             R.tok = std::make_unique<TokenTensor>( dev, shape_t{ B } );
             R.active = std::make_unique<TokenTensor>( dev, shape_t{ B } );
+            if ( cfg_.draft_tokens > 0 )
+            {
+                R.result = std::make_unique<TokenTensor>( dev, shape_t{ B + 1 } );
+                Compute::rocmCheck( mila_cdna4_memset_zero( R.result->data(), R.result->sizeInBytes(), ctx_->getStream() ) );
+            }
             // every row starts as a valid, inactive sequence at position 0 with token 0: a row that was never admitted still rides through a step's launches
             for ( auto* t : { R.pos.get(), R.tok.get(), R.active.get() } ) Compute::rocmCheck( mila_cdna4_memset_zero( t->data(), t->sizeInBytes(), ctx_->getStream() ) );
             for ( auto* t : { R.qkv.get(), R.attn.get(), R.o.get(), R.down.get(), R.act.get(), R.res1.get() } ) Compute::rocmCheck( mila_cdna4_memset_zero( t->data(), t->sizeInBytes(), ctx_->getStream() ) );
         }
         size_t rowsAttnScratchBytes() const
         {
-            const int B = static_cast<int>( cfg_.max_batch );
+            const int B = static_cast<int>( rowsCount() );
+            if ( cfg_.draft_tokens > 0 )      // the chain entry parks the roped q rows behind the partials at every head size
+                return std::max( mila_cdna4_attn_chain_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.head_dim ),
+                                 mila_cdna4_attn_chain_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.global_head_dim ) );
             return std::max( mila_cdna4_attn_decode_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.head_dim ), mila_cdna4_attn_decode_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.global_head_dim ) );
         }
         size_t rowsStateBytes() const
@@ -1138,16 +1282,18 @@ namespace Mila::Dnn
             for ( const auto* t : { R.qkv.get(), R.attn.get(), R.o.get(), R.down.get(), R.act.get(), R.res1.get(), R.hidden[ 0 ].get(), R.hidden[ 1 ].get(), R.hidden[ 2 ].get() } ) b += tensorBytes( t );
             for ( const auto* t : { R.logits.get(), R.sample_scratch.get(), R.attn_partials.get() } ) b += tensorBytes( t );
             for ( const auto* t : { R.pos.get(), R.tok.get(), R.active.get() } ) b += tensorBytes( t );
+            if ( R.result ) b += tensorBytes( R.result.get() );
             return b;
         }
         /// the same from the configuration alone, plus the cache rows beyond the first of every layer
         size_t requiredRowsStateBytes() const
         {
-            if ( cfg_.max_batch <= 1 ) return 0;
-            const size_t B = static_cast<size_t>( cfg_.max_batch ), D = static_cast<size_t>( cfg_.embedding_dim );
+            if ( cfg_.max_batch <= 1 && cfg_.draft_tokens <= 0 ) return 0;
+            const size_t B = static_cast<size_t>( rowsCount() ), D = static_cast<size_t>( cfg_.embedding_dim );
             const size_t maxq = static_cast<size_t>( std::max( cfg_.qWidth( false ), cfg_.qWidth( true ) ) ), maxpacked = static_cast<size_t>( std::max( cfg_.packedQkvWidth( false ), cfg_.packedQkvWidth( true ) ) );
             size_t b = B * ( maxpacked + maxq + 3 * D + static_cast<size_t>( cfg_.hidden_dim ) + 3 * D ) * 2;
             b += B * static_cast<size_t>( cfg_.vocab_size ) * 4 + B * ( ( mila_cdna4_sample_scratch_bytes() / 4 ) * 4 ) + ( ( rowsAttnScratchBytes() + 3 ) / 4 ) * 4 + 3 * B * 4;
+            if ( cfg_.draft_tokens > 0 ) return b + ( B + 1 ) * 4;      // the chain's result words; its rows share the one cache
             for ( auto& L : layers_ ) b += ( B - 1 ) * 2 * static_cast<size_t>( cfg_.kvWidth( L.global ) ) * static_cast<size_t>( L.cacheCapacity() ) * 2;
             return b;
         }
@@ -1475,7 +1621,12 @@ namespace Mila::Dnn
         std::unique_ptr<TensorType> pf_q8_[ 2 ];          // [1, P, D / 2] bf16 elements = P * D bytes of e4m3
         std::unique_ptr<LogitsTensor> pf_ts_[ 2 ];        // [P] fp32 per-token scales
         const uint16_t* cur_hidden_{ nullptr };
-        std::unique_ptr<RowsState> rows_;               // max_batch > 1 only
+        std::unique_ptr<RowsState> rows_;               // max_batch > 1 or draft_tokens > 0 only
+        hipGraph_t chain_graph_{ nullptr };
+        hipGraphExec_t chain_graph_exec_{ nullptr };
+        int chain_captured_T_{ 0 };
+        dim_t chain_captured_band_{ 0 };
+        size_t chain_graph_captures_{ 0 };
         hipGraph_t rows_graph_{ nullptr };
         hipGraphExec_t rows_graph_exec_{ nullptr };
         int rows_captured_B_{ 0 };

@@ -49,12 +49,39 @@ namespace Mila::Dnn
         int top_k = 0;        ///< 0 disables top-k truncation; 1 == greedy
         float top_p = 1.0f;   ///< 1.0 disables nucleus truncation
     };
+    /// proposes up to k tokens that may follow `history` (prompt + emitted tokens; its last element is the token about to be decoded)
+    using DraftFunction = std::function<std::vector<int32_t>( std::span<const int32_t> history, int k )>;
     struct GenerateParams
     {
         std::optional<int> max_new_tokens;       ///< nullopt => run to EOS / the context bound
         SamplingParams sampling{};
         std::vector<int32_t> stop_tokens{};      ///< empty => the model's default stop set
+        DraftFunction draft{};                   ///< speculative greedy decode (GemmaModelConfig::withDraftTokens): the drafter; empty => promptLookupDraft
     };
+
+    /// The default drafter, prompt lookup: for n = 3, 2, 1 take the LATEST earlier occurrence of the last n tokens of `history` (one that starts before the suffix
+    /// itself does) and propose the up-to-k tokens that followed it; the first n with an occurrence decides, no occurrence at any n proposes nothing.  Pure host code.
+    inline std::vector<int32_t> promptLookupDraft( std::span<const int32_t> history, int k )
+    {
+        const std::ptrdiff_t h = static_cast<std::ptrdiff_t>( history.size() );
+        if ( k <= 0 ) return {};
+        for ( std::ptrdiff_t n = 3; n >= 1; --n )
+        {
+            if ( h < n + 1 ) continue;
+            for ( std::ptrdiff_t j = h - n - 1; j >= 0; --j )
+            {
+                bool same = true;
+                for ( std::ptrdiff_t i = 0; i < n && same; ++i ) same = history[ static_cast<size_t>( j + i ) ] == history[ static_cast<size_t>( h - n + i ) ];
+                if ( !same ) continue;
+                const std::ptrdiff_t first = j + n, last = std::min<std::ptrdiff_t>( first + k, h );
+                return std::vector<int32_t>( history.begin() + first, history.begin() + last );
+            }
+        }
+        return {};
+    }
+    /// what the last greedy generate() of a withDraftTokens model did: decode steps in all, those that were chain steps, the drafter's tokens those carried (padding
+    /// not counted) and how many of them were accepted
+    struct SpeculationStats { uint64_t steps = 0, chain_steps = 0, drafted = 0, accepted = 0; };
 
     struct GemmaModelConfig
     {
@@ -73,6 +100,10 @@ namespace Mila::Dnn
         GemmaModelConfig& withBoundedLocalKv( bool on ) { bounded_local_kv_ = on; return *this; }            ///< SlidingWindowKvCache on the sliding-window layers
         GemmaModelConfig& withMaxBatch( dim_t n ) { max_batch_ = n; return *this; }                           ///< GemmaConfig::max_batch: sequences per decode step (generateBatch), 1 .. 4
         dim_t maxBatch() const noexcept { return max_batch_; }
+        /// GemmaConfig::draft_tokens (0 .. 3): greedy generate() verifies up to k drafted tokens per step on the chain step and emits up to k + 1 tokens per step --
+        /// token for token the plain greedy output.  A plain step loop (one sync per step, no decode-ahead, as generateBatch); stochastic requests keep the plain path.
+        GemmaModelConfig& withDraftTokens( dim_t k ) { draft_tokens_ = k; return *this; }
+        dim_t draftTokens() const noexcept { return draft_tokens_; }
         GemmaModelConfig& withKvFp8( bool on ) { kv_fp8_ = on; return *this; }                               ///< PerChannelKvFp8<> on every layer (GemmaConfig::kv_fp8), under any weight policy
         dim_t getContextLength() const noexcept { return context_length_; }
         WeightQuantization getWeightQuantization() const noexcept { return weight_quantization_; }
@@ -81,7 +112,7 @@ namespace Mila::Dnn
         bool boundedLocalKv() const noexcept { return bounded_local_kv_; }
         bool kvFp8() const noexcept { return kv_fp8_; }
     private:
-        dim_t context_length_{ 0 }, prefill_chunk_{ 0 }, max_batch_{ 1 };
+        dim_t context_length_{ 0 }, prefill_chunk_{ 0 }, max_batch_{ 1 }, draft_tokens_{ 0 };
         WeightQuantization weight_quantization_{ WeightQuantization::None };
         KvCacheCompression kv_cache_compression_{ KvCacheCompression::None };
         bool bounded_local_kv_{ false }, kv_fp8_{ false };
@@ -143,6 +174,7 @@ namespace Mila::Dnn
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
                     cfg.kv_fp8 = model_config.kvFp8();
                     cfg.max_batch = model_config.maxBatch();
+                    cfg.draft_tokens = model_config.draftTokens();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
                     net->loadPretrained( path );
                     return std::unique_ptr<GemmaModel>( new GemmaModel( Network( std::move( net ) ), cfg, model_config, md ) );
@@ -159,6 +191,7 @@ namespace Mila::Dnn
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
                     cfg.kv_fp8 = model_config.kvFp8();
                     cfg.max_batch = model_config.maxBatch();
+                    cfg.draft_tokens = model_config.draftTokens();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
                     typename Net<TWeightQuantization>::SyntheticProfile p;
                     p.linear_gain = profile.linear_gain; p.qk_norm_center = profile.qk_norm_center; p.post_norm_center = profile.post_norm_center; p.layer_scalar = profile.layer_scalar; p.table_gain = profile.table_gain;
@@ -194,6 +227,8 @@ namespace Mila::Dnn
         const std::vector<int32_t>& kvTokenHistory() const noexcept { return kv_token_history_; }
         /// prompt tokens the last generate() did NOT have to prefill
         dim_t lastReusedPrefix() const noexcept { return last_reuse_; }
+        /// the speculative loop's counters of the last greedy generate() (all zero on a model without draft tokens, or after a stochastic request)
+        const SpeculationStats& lastSpeculation() const noexcept { return last_speculation_; }
         Network& network() noexcept { return network_; }
 
         /// prefill + decode; on_token is called for every generated token except a stop token
@@ -409,6 +444,8 @@ namespace Mila::Dnn
 
             const bool greedy = isGreedy( params.sampling );
             dim_t position = seq_len;
+            last_speculation_ = SpeculationStats{};
+            if ( greedy && net.draftTokens() > 0 ) return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids );
             enqueueSampleNext( net, params.sampling );
             int emitted = 0;
             const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
@@ -474,7 +511,93 @@ namespace Mila::Dnn
             }
         }
 
+        /// The greedy decode loop of a withDraftTokens model, entered behind the prefill.  Each step decodes the current token at `position` together with up to k
+        /// drafted successors (padded with token 0 to k: a padded token that happens to verify is a correct token) on the chain step, reads {count, tokens} back and
+        /// emits the accepted tokens under generate()'s rules.  It takes the one-row captured step instead when the drafter proposes nothing, when position + k + 1
+        /// would pass the context length, or when position and position + k lie in different live-length buckets (the one case where a chain row would not have the
+        /// bits it has alone).  Every token is the plain greedy loop's token.  One sync per step, no decode-ahead.
+        template<typename TNet>
+        GenerateStatus onGeneratingSpeculative( TNet& net, std::span<const int32_t> prompt, const std::function<void( int32_t )>& on_token, const GenerateParams& params,
+                                                const std::atomic<bool>* stop, const std::unordered_set<int32_t>& stop_ids )
+        {
+            auto* ctx = net.context();
+            const int k = static_cast<int>( net.draftTokens() );
+            const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
+            dim_t position = static_cast<dim_t>( prompt.size() );
+            std::vector<int32_t> history( prompt.begin(), prompt.end() );
+            auto readWords = [&]( int32_t* dst, const int32_t* src, int n )
+            {
+                Compute::rocmCheck( mila_cdna4_memcpy_d2h( dst, src, static_cast<size_t>( n ) * 4, ctx->getStream() ) );
+                ctx->synchronize();
+            };
+            net.sampleGreedy( *decode_token_device_ );      // the first token, from the prefill's logits
+            int32_t token = 0;
+            readWords( &token, decode_token_device_->data(), 1 );
+            int emitted = 0;
+            // emits one token under generate()'s rules; `at` = the position the token would be decoded at.  nullopt: go on
+            auto emit = [&]( int32_t t, dim_t at ) -> std::optional<GenerateStatus>
+            {
+                if ( stop_ids.contains( t ) ) return GenerateStatus::Success;
+                on_token( t );
+                ++emitted;
+                if ( emitted >= max_new ) return GenerateStatus::MaxNewTokensReached;
+                if ( at >= contextLength() ) return GenerateStatus::ContextOverflow;
+                return std::nullopt;
+            };
+            if ( auto st = emit( token, position ) ) return *st;
+            // the one-row step of this loop: the captured greedy step without the token ring (the loop reads the token back itself)
+            net.setSampleInGraph( true );
+            net.setTokenRing( nullptr, 0, nullptr );
+            net.setGraphSampling( std::nullopt );
+            net.setDevicePosition( position );
+            std::vector<int32_t> row( static_cast<size_t>( k ) + 2 );
+            while ( true )
+            {
+                if ( stop && stop->load( std::memory_order_relaxed ) ) { ctx->synchronize(); return GenerateStatus::ClientCancelled; }
+                history.push_back( token );
+                std::vector<int32_t> drafts = params.draft ? params.draft( history, k ) : promptLookupDraft( history, k );
+                if ( drafts.size() > static_cast<size_t>( k ) ) drafts.resize( static_cast<size_t>( k ) );
+                for ( int32_t& d : drafts ) if ( d < 0 || d >= vocabSize() ) d = 0;      // a drafter's out-of-range proposal is a wrong draft, not an error
+                const bool chain = !drafts.empty() && position + k + 1 <= contextLength() && net.bandBucket( position ) == net.bandBucket( position + k );
+                ++last_speculation_.steps;
+                if ( !chain )
+                {
+                    Compute::rocmCheck( mila_cdna4_memcpy_h2d( decode_token_device_->data(), &token, 4, ctx->getStream() ) );
+                    net.ensureGraph( *decode_token_device_, position );
+                    net.replayGraph();
+                    kv_token_history_.push_back( token );
+                    ++position;
+                    readWords( &token, decode_token_device_->data(), 1 );
+                    if ( auto st = emit( token, position ) ) return *st;
+                    continue;
+                }
+                const int real = static_cast<int>( drafts.size() ), T = k + 1;
+                row[ 0 ] = token;
+                for ( int i = 0; i < k; ++i ) row[ static_cast<size_t>( i ) + 1 ] = i < real ? drafts[ static_cast<size_t>( i ) ] : 0;
+                net.setChainDrafts( row.data(), T );
+                net.ensureGraphChain( T, position );
+                net.replayGraphChain();
+                readWords( row.data(), net.chainResult().data(), T + 1 );
+                const int count = row[ 0 ];
+                if ( count < 1 || count > T ) throw std::runtime_error( "GemmaModel: the chain step reported " + std::to_string( count ) + " accepted tokens" );
+                ++last_speculation_.chain_steps;
+                last_speculation_.drafted += static_cast<uint64_t>( real );
+                last_speculation_.accepted += static_cast<uint64_t>( std::min( count - 1, real ) );
+                // the caches now hold `token` and the count - 1 verified drafts behind it: the accepted tokens but the last, which is the next step's input
+                kv_token_history_.push_back( token );
+                for ( int i = 0; i + 1 < count; ++i ) kv_token_history_.push_back( row[ static_cast<size_t>( i ) + 1 ] );
+                for ( int i = 0; i < count; ++i )
+                {
+                    token = row[ static_cast<size_t>( i ) + 1 ];
+                    if ( i > 0 ) history.push_back( row[ static_cast<size_t>( i ) ] );
+                    if ( auto st = emit( token, position + i + 1 ) ) { ctx->synchronize(); return *st; }
+                }
+                position += count;
+            }
+        }
+
         static constexpr size_t kSnapshots = 8;
+        SpeculationStats last_speculation_{};
         Network network_;
         GemmaConfig network_config_;
         GemmaModelConfig model_config_;

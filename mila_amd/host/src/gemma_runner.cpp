@@ -154,6 +154,64 @@ HOST_API void* mila_gemma_create_rows( int policy, const mila_gemma_config* c, i
     return rc == 0 ? r : nullptr;
 }
 
+static GemmaConfig gemma_config_of( const mila_gemma_config* c )
+{
+    GemmaConfig cfg;
+    if ( c )
+    {
+        cfg.vocab_size = c->vocab_size; cfg.embedding_dim = c->embedding_dim; cfg.num_layers = c->num_layers; cfg.num_heads = c->num_heads;
+        cfg.num_kv_heads = c->num_kv_heads; cfg.head_dim = c->head_dim; cfg.hidden_dim = c->hidden_dim; cfg.global_head_dim = c->global_head_dim;
+        cfg.num_global_kv_heads = c->num_global_kv_heads; cfg.window = c->window; cfg.sliding_window_pattern = c->sliding_window_pattern;
+        cfg.global_rotary_dim = c->global_rotary_dim;
+        cfg.bounded_local_kv = c->bounded_local_kv != 0;
+        cfg.kv_fp8 = c->kv_fp8 != 0;
+    }
+    return cfg;
+}
+
+/// mila_gemma_create with GemmaConfig::max_batch AND GemmaConfig::draft_tokens (0 .. 3: the chain step, chain_decode).  max_batch = 1 and draft_tokens = 0 build the
+/// model mila_gemma_create builds.  mila_gemma_config itself is unchanged.
+HOST_API void* mila_gemma_create_chain( int policy, const mila_gemma_config* c, int64_t max_seq, int64_t max_prefill, int64_t max_batch, int64_t draft_tokens, uint64_t seed, int device )
+{
+    Runner* r = nullptr;
+    int rc = guarded( [&]
+    {
+        GemmaConfig cfg = gemma_config_of( c );
+        cfg.max_batch = max_batch;
+        cfg.draft_tokens = draft_tokens;
+        auto rr = std::make_unique<Runner>();
+        rr->max_prefill = max_prefill;
+        switch ( policy )
+        {
+            case 0: rr->model = std::make_unique<GemmaTransformer<NoWeightQuant>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            case 1: rr->model = std::make_unique<GemmaTransformer<PerChannelFp8<>>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            case 2: rr->model = std::make_unique<GemmaTransformer<PerGroupFp4<128>>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            default: throw std::invalid_argument( "unknown weight policy" );
+        }
+        std::visit( [&]( auto& m )
+        {
+            m->initSynthetic( seed );
+            rr->tokens = std::make_unique<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>>(
+                m->context()->getDeviceId(), shape_t{ std::max<dim_t>( max_prefill, 1 ) } );
+        }, rr->model );
+        r = rr.release();
+    } );
+    return rc == 0 ? r : nullptr;
+}
+/// GemmaConfig::validate() on the configuration mila_gemma_create_chain would build, without a device: 0, or MILA_E_INVALID_ARGUMENT and the message
+HOST_API int mila_gemma_validate_config( const mila_gemma_config* c, int64_t max_batch, int64_t draft_tokens )
+{
+    return guarded( [&] { GemmaConfig cfg = gemma_config_of( c ); cfg.max_batch = max_batch; cfg.draft_tokens = draft_tokens; cfg.validate(); } );
+}
+/// promptLookupDraft (GemmaModel.h), the default drafter of the speculative generate(): up to k tokens into out, returns their number.  Pure host code.
+HOST_API int mila_gemma_prompt_lookup_draft( const int32_t* history, int64_t n, int k, int32_t* out )
+{
+    if ( !history || !out || n < 0 ) return 0;
+    const auto d = promptLookupDraft( std::span<const int32_t>( history, static_cast<size_t>( n ) ), k );
+    for ( size_t i = 0; i < d.size(); ++i ) out[ i ] = d[ i ];
+    return static_cast<int>( d.size() );
+}
+
 /// regenerate the synthetic parameters under a profile: p = { linear_gain, qk_norm_center, post_norm_center, layer_scalar, table_gain }
 HOST_API int mila_gemma_init_synthetic( void* h, uint64_t seed, const float* p )
 {
@@ -457,6 +515,79 @@ HOST_API int mila_gemma_time_decode_rows( void* h, int B, int64_t start_position
             const auto t0 = std::chrono::steady_clock::now();
             hipCheck( hipEventRecord( e0, s ), "hipEventRecord" );
             for ( int i = 0; i < steps; ++i ) step();
+            hipCheck( hipEventRecord( e1, s ), "hipEventRecord" );
+            ctx->synchronize();
+            const auto t1 = std::chrono::steady_clock::now();
+            float ms = 0;
+            hipCheck( hipEventElapsedTime( &ms, e0, e1 ), "hipEventElapsedTime" );
+            (void)hipEventDestroy( e0 ); (void)hipEventDestroy( e1 );
+            out[ 0 ] = std::chrono::duration<double, std::milli>( t1 - t0 ).count() / steps;
+            out[ 1 ] = static_cast<double>( ms ) / steps;
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
+
+// ---- chain decode: consecutive positions of ONE sequence (GemmaConfig::draft_tokens > 0) ----------------------------------------------------------------
+/// one chain step: tokens[ 0 ] = the token at `position`, tokens[ 1 .. T - 1 ] = the drafts behind it.  mode 1: eager launches, 2: graph replay (captured on first use
+/// and when T or the live-length bucket change; the device position word is set to `position` either way).  Outputs (each may be NULL): logits [T, vocab];
+/// out[ 0 ] = count, out[ 1 .. count ] = the accepted tokens, out[ T + 1 ] = the position word after the step (out holds T + 2 words)
+HOST_API int mila_gemma_chain_decode( void* h, const int32_t* tokens, int T, int64_t position, int mode, float* host_logits, int32_t* out )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( mode != 1 && mode != 2 ) throw std::invalid_argument( "chain_decode: mode must be 1 (eager) or 2 (graph)" );
+            if ( !tokens ) throw std::invalid_argument( "chain_decode: null tokens" );
+            m->setChainDrafts( tokens, T );
+            if ( mode == 1 ) m->decodeChain( T, position );
+            else { m->ensureGraphChain( T, position ); m->setDevicePosition( position ); m->replayGraphChain(); }
+            auto st = m->context()->getStream();
+            if ( host_logits ) Compute::rocmCheck( mila_cdna4_memcpy_d2h( host_logits, m->chainLogits().data(), static_cast<size_t>( T ) * m->config().vocab_size * 4, st ) );
+            if ( out )
+            {
+                for ( int i = 0; i < T + 2; ++i ) out[ i ] = 0;
+                Compute::rocmCheck( mila_cdna4_memcpy_d2h( out, m->chainResult().data(), static_cast<size_t>( T + 1 ) * 4, st ) );
+                m->context()->synchronize();
+                out[ T + 1 ] = static_cast<int32_t>( m->devicePosition() );
+                for ( int i = out[ 0 ] + 1; i <= T; ++i ) out[ i ] = 0;      // words past the accepted run are left over from earlier steps
+            }
+            m->context()->synchronize();
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
+/// out[0] = captures of the chain graph so far, out[1] = kernel nodes of the captured chain step, out[2] = its rows
+HOST_API int mila_gemma_chain_graph_info( void* h, int64_t* out )
+{
+    return guarded( [&] { std::visit( [&]( auto& m ) { out[ 0 ] = (int64_t)m->graphChainCaptureCount(); out[ 1 ] = (int64_t)m->graphChainNodeCount(); out[ 2 ] = m->graphChainRows(); },
+                                      static_cast<Runner*>( h )->model ); } );
+}
+/// `steps` graph replays of a T-row chain step from `start_position` after `warmup` (a timing loop: the caches hold whatever they hold, the drafts are whatever the
+/// token words hold, and every step advances by what it accepts -- at most T, so start_position + (steps + warmup) * T must fit the sequence length):
+/// out[0] = wall ms per step, out[1] = device ms per step
+HOST_API int mila_gemma_time_chain_decode( void* h, int T, int64_t start_position, int steps, int warmup, double* out )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            auto* ctx = m->context();
+            hipStream_t s = reinterpret_cast<hipStream_t>( ctx->getStream() );
+            const int64_t last = start_position + static_cast<int64_t>( steps + warmup ) * T;
+            // the replays are not checked one by one (what a step accepts is known on the device only): the whole run must fit, every step taken as T positions
+            if ( steps < 1 || warmup < 0 || start_position < 0 || last > m->maxSeq() ) throw std::invalid_argument( "time_chain_decode: the run would pass the built sequence length" );
+            if ( m->bandBucket( start_position ) != m->bandBucket( last - 1 ) ) throw std::invalid_argument( "time_chain_decode: the run would leave its live-length bucket" );
+            const int32_t toks[ 4 ] = { 17, 18, 19, 20 };
+            m->setChainDrafts( toks, T );
+            m->captureGraphChain( T, start_position );
+            for ( int i = 0; i < warmup; ++i ) m->replayGraphChain();
+            ctx->synchronize();
+            hipEvent_t e0, e1;
+            hipCheck( hipEventCreate( &e0 ), "hipEventCreate" );
+            hipCheck( hipEventCreate( &e1 ), "hipEventCreate" );
+            const auto t0 = std::chrono::steady_clock::now();
+            hipCheck( hipEventRecord( e0, s ), "hipEventRecord" );
+            for ( int i = 0; i < steps; ++i ) m->replayGraphChain();
             hipCheck( hipEventRecord( e1, s ), "hipEventRecord" );
             ctx->synchronize();
             const auto t1 = std::chrono::steady_clock::now();
@@ -1107,6 +1238,21 @@ HOST_API void* mila_gemma_model_synthetic_rows( int policy, const mila_gemma_con
     return rc == 0 ? m : nullptr;
 }
 
+/// mila_gemma_model_synthetic with GemmaModelConfig::withDraftTokens( draft_tokens ): greedy generate() verifies up to draft_tokens drafted tokens per step
+HOST_API void* mila_gemma_model_synthetic_chain( int policy, const mila_gemma_config* c, int64_t context, int64_t prefill_chunk, int64_t draft_tokens, uint64_t seed, const float* p, int device )
+{
+    RocmGemmaModel* m = nullptr;
+    int rc = guarded( [&]
+    {
+        GemmaConfig cfg = gemma_config_of( c );
+        GemmaTransformer<NoWeightQuant>::SyntheticProfile pr;
+        if ( p ) { pr.linear_gain = p[ 0 ]; pr.qk_norm_center = p[ 1 ]; pr.post_norm_center = p[ 2 ]; pr.layer_scalar = p[ 3 ]; pr.table_gain = p[ 4 ]; }
+        m = RocmGemmaModel::fromSynthetic( cfg, model_config_of( policy, context, prefill_chunk, cfg.bounded_local_kv, cfg.kv_fp8 ).withDraftTokens( draft_tokens ), seed, pr,
+                                           Compute::Device::Rocm( device ) ).release();
+    } );
+    return rc == 0 ? m : nullptr;
+}
+
 HOST_API void mila_gemma_model_destroy( void* h ) { delete static_cast<RocmGemmaModel*>( h ); }
 
 /// generate(): max_new < 0 = no budget (run to a stop token or the context bound); n_stop == 0 = the model's default stop set; the callback's tokens
@@ -1132,6 +1278,55 @@ HOST_API int mila_gemma_model_generate( void* h, const int32_t* prompt, int64_t 
         *out_count = n;
         *out_status = static_cast<int32_t>( st );
         if ( out_reused ) *out_reused = m->lastReusedPrefix();
+    } );
+}
+
+/// mila_gemma_model_generate with a drafter for the speculative greedy loop: hint (n_hint > 0) = a sequence the drafter reads the continuation from -- the tokens
+/// expected to follow the prompt, so that the draft for the token at index i of the output is hint[ i + 1 .. ]; n_hint == 0 = the default drafter (prompt lookup).
+/// out_stats (may be NULL): GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
+HOST_API int mila_gemma_model_generate_spec( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                                             float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status,
+                                             int64_t* out_stats )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m || !prompt || !out_count || !out_status ) throw std::invalid_argument( "gemma_model_generate_spec: null argument" );
+        GenerateParams gp;
+        if ( max_new >= 0 ) gp.max_new_tokens = max_new;
+        gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
+        for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
+        if ( hint && n_hint > 0 )
+            gp.draft = [=]( std::span<const int32_t> history, int k )
+            {
+                // history = prompt + emitted tokens; the tokens after its last element are hint[ emitted .. ]
+                const int64_t first = static_cast<int64_t>( history.size() ) - n_prompt;
+                std::vector<int32_t> d;
+                for ( int64_t i = first; i >= 0 && i < n_hint && static_cast<int>( d.size() ) < k; ++i ) d.push_back( hint[ i ] );
+                return d;
+            };
+        if ( seed >= 0 ) m->seedSampler( static_cast<uint64_t>( seed ) );
+        int64_t n = 0;
+        const GenerateStatus st = m->generate( std::span<const int32_t>( prompt, static_cast<size_t>( n_prompt ) ), [&]( int32_t t ) { if ( out_tokens && n < cap ) out_tokens[ n ] = t; ++n; }, gp );
+        *out_count = n;
+        *out_status = static_cast<int32_t>( st );
+        if ( out_stats )
+        {
+            const auto& sp = m->lastSpeculation();
+            out_stats[ 0 ] = (int64_t)sp.steps; out_stats[ 1 ] = (int64_t)sp.chain_steps; out_stats[ 2 ] = (int64_t)sp.drafted; out_stats[ 3 ] = (int64_t)sp.accepted;
+        }
+    } );
+}
+
+/// GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
+HOST_API int mila_gemma_model_speculation_stats( void* h, int64_t* out )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m || !out ) throw std::invalid_argument( "gemma_model_speculation_stats: null argument" );
+        const auto& sp = m->lastSpeculation();
+        out[ 0 ] = (int64_t)sp.steps; out[ 1 ] = (int64_t)sp.chain_steps; out[ 2 ] = (int64_t)sp.drafted; out[ 3 ] = (int64_t)sp.accepted;
     } );
 }
 
