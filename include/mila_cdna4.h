@@ -691,6 +691,33 @@ MILA_API int mila_cdna4_fused_qkv_post_rows_devpos(uint16_t* q_out, uint16_t* Kc
 MILA_API int mila_cdna4_sample_argmax_chain_accept(int32_t* tok, int32_t* result, const void* scratch, size_t scratch_bytes, int blocks, int32_t* position_dev, int T,
                                                    mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The radix sampler over 1 .. 4 rows in ONE pipeline (ABI 4, additive): the stochastic twins of the two greedy tails above.  Row b reads logits + b * logits_stride
+ * floats (logits_stride >= vocab) and samples at its own draw draws[b] (one float in [0, 1] per row; device or host-visible memory, read with one system-scope load, so
+ * a host may rewrite the draws between replays of a captured call).  A call launches what sample_radix_plan_describe reports for ONE row -- the rows ride in the grid.
+ * ROW INVARIANCE: row b's token is the token sample_radix_fp32 returns on row b's logits with r = draws[b], for every input and every draw, whatever the other rows
+ * hold (a NaN included): per row every launch extent, chunk and float summation order is the one-row entry's.
+ *   scratch: sample_radix_rows_scratch_bytes(rows, vocab) = rows x (sample_radix_scratch_bytes(vocab) rounded up to 8) bytes, 8-byte aligned; 0 for rows outside 1 .. 4
+ *     or vocab <= 0.
+ *   sample_radix_rows_fp32: token_out[b] = row b's sample, b < rows; nothing is advanced.
+ *   sample_radix_rows_advance_fp32: the tail of a captured rows step -- where active_dev[b] != 0, token_out[b] = row b's sample and positions_dev[b] += 1; an inactive
+ *     row's token and position words are not touched.
+ *   sample_radix_chain_accept_fp32: the tail of a captured chain step, sample_argmax_chain_accept's rule with the samples s_t in the place of the argmaxes a_t: row t was
+ *     fed tok[t]; n = the first t in [0, T - 1) with s_t != tok[t + 1], else T - 1; result = {n + 1, s_0 .. s_n} (words past s_n are left alone), tok[0] = s_n,
+ *     *position_dev += n + 1.  With draws[t] the draw the one-row loop would use for that token, the emitted tokens ARE the one-row loop's tokens (coupled draws): a
+ *     deterministic draft d is accepted exactly when the plain sampler would have drawn d, i.e. with probability p(d).
+ * Refused before any device work: rows outside 1 .. 4 (T outside 2 .. 4), vocab <= 0, logits_stride < vocab, temperature <= 0, top_k < 0, top_p <= 0, a null
+ * pointer, a misaligned scratch (MILA_E_INVALID_ARGUMENT); a scratch that is too small (MILA_E_SCRATCH_TOO_SMALL). */
+MILA_API size_t mila_cdna4_sample_radix_rows_scratch_bytes(int rows, int vocab);
+MILA_API int mila_cdna4_sample_radix_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature,
+                                               int top_k, float top_p, const float* draws, void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                       float temperature, int top_k, float top_p, const float* draws, void* scratch, size_t scratch_bytes,
+                                                       int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_chain_accept_fp32(int32_t* tok, int32_t* result, const float* logits, size_t logits_stride, int T, int vocab, float softcap,
+                                                       float temperature, int top_k, float top_p, const float* draws, void* scratch, size_t scratch_bytes,
+                                                       int32_t* position_dev, mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

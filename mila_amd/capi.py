@@ -100,6 +100,11 @@ def load():
     main.mila_cdna4_sample_radix_advance_fp32.argtypes = [p, p, i, f, f, i, f, p, i, p, z, p, p, p, i, p]         # ... top_p | draws draws_size | scratch bytes | position_dev seq_dev ring ring_size
     main.mila_cdna4_sample_radix_plan_describe.argtypes = [i, i, f, p, z]                                         # vocab top_k top_p | buf cap
     main.mila_cdna4_sample_radix_plan_describe.restype = z
+    main.mila_cdna4_sample_radix_rows_scratch_bytes.argtypes = [i, i]                                             # rows vocab
+    main.mila_cdna4_sample_radix_rows_scratch_bytes.restype = z
+    main.mila_cdna4_sample_radix_rows_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, z, p]                     # logits logits_stride token_out | rows vocab softcap temperature top_k top_p | draws | scratch bytes
+    main.mila_cdna4_sample_radix_rows_advance_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, z, p, p, p]       # ... | scratch bytes | positions_dev active_dev
+    main.mila_cdna4_sample_radix_chain_accept_fp32.argtypes = [p, p, p, z, i, i, f, f, i, f, p, p, z, p, p]       # tok result logits logits_stride | T vocab softcap temperature top_k top_p | draws | scratch bytes | position_dev
     main.mila_cdna4_kv_dequant_fp8_bf16.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                        # Kc Vc K8 V8 Ks Vs | B NKV HS capacity first_pos count
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.argtypes = [i, i, i, i]                                      # B NKV HS capacity
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.restype = z
@@ -265,6 +270,37 @@ def sample_radix_advance(logits, token_out, softcap, temperature, top_k, top_p, 
          scratch, C.c_size_t(scratch.numel() * scratch.element_size()), position_dev, seq_dev, ring, 0 if ring is None else int(ring.numel()))
 
 
+def sample_radix_rows_scratch_bytes(rows, vocab):
+    return int(load().mila_cdna4_sample_radix_rows_scratch_bytes(int(rows), int(vocab)))
+
+
+def _radix_rows_head(logits, vocab):
+    """(logits_stride, vocab) of a [rows, stride] fp32 tensor whose rows hold `vocab` logits each (default: all of the row)"""
+    assert logits.dim() == 2
+    return C.c_size_t(int(logits.shape[1])), int(logits.shape[1] if vocab is None else vocab)
+
+
+def sample_radix_rows(logits, token_out, softcap, temperature, top_k, top_p, draws, scratch, vocab=None):
+    """token_out[b] <- the radix pipeline's sample from row b of `logits` [rows, stride] (fp32) at the draw draws[b]; nothing is advanced"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_rows_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), float(temperature), int(top_k), float(top_p), draws,
+         scratch, C.c_size_t(scratch.numel() * scratch.element_size()))
+
+
+def sample_radix_rows_advance(logits, token_out, softcap, temperature, top_k, top_p, draws, scratch, positions_dev, active_dev, vocab=None):
+    """the rows step's stochastic tail: token and position bump of every row whose active word is not 0"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_rows_advance_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), float(temperature), int(top_k), float(top_p), draws,
+         scratch, C.c_size_t(scratch.numel() * scratch.element_size()), positions_dev, active_dev)
+
+
+def sample_radix_chain_accept(tok, result, logits, softcap, temperature, top_k, top_p, draws, scratch, position_dev, vocab=None):
+    """the chain step's stochastic tail: accept the longest prefix of the drafts tok[1 ..] that the samples s_t (row t at draws[t]) confirm"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_chain_accept_fp32", tok, result, logits, stride, int(logits.shape[0]), V, float(softcap), float(temperature), int(top_k), float(top_p), draws,
+         scratch, C.c_size_t(scratch.numel() * scratch.element_size()), position_dev)
+
+
 def prefill_form_name(plan, HS):
     """what last_form() reports for a launch from this plan: the form and its instantiation"""
     return plan["form"] if plan["form"] == "attn_generic" else "%s_hs%d_hb%d_ds%d_nw%d" % (plan["form"], HS, plan["HB"], plan["DS"], plan["NW"])
@@ -326,6 +362,7 @@ EXPORTED = [
     "fused_qkv_post_kvfp8", "fused_qkv_post_kvfp8_prefill", "fused_qkv_post_kvfp8_devpos",
     "matvec_rows", "fused_attn_decode_rows_bf16", "sample_argmax_rows_final_advance", "advance_positions_rows",
     "fused_attn_decode_chain_bf16", "attn_decode_chain_scratch_bytes", "fused_qkv_post_rows_devpos", "sample_argmax_chain_accept",
+    "sample_radix_rows_scratch_bytes", "sample_radix_rows_fp32", "sample_radix_rows_advance_fp32", "sample_radix_chain_accept_fp32",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

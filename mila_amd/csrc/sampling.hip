@@ -574,7 +574,7 @@ __device__ __forceinline__ void radix_walk(const float* w, int first, int stride
 
 // launch 1: x = softcap / temperature, per-workgroup max; clears the header and both histograms for the launches behind it
 template <typename T>
-__global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ logits, const RadixParams p, int clear_words)
+__device__ __forceinline__ void radix_scale_body(const T* __restrict__ logits, const RadixParams& p, int clear_words)
 {
     __shared__ float sv[4];
     uint32_t* z = reinterpret_cast<uint32_t*>(p.hdr);
@@ -595,7 +595,7 @@ __global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ 
 }
 
 // top-k digit pass: pick the previous pass's digit, then count this pass's digit over the keys that share the prefix
-__global__ __launch_bounds__(256) void radix_kpass_kernel(const RadixParams p, int pass)
+__device__ __forceinline__ void radix_kpass_body(const RadixParams& p, int pass)
 {
     __shared__ uint32_t lh[kRadixBins];
     __shared__ unsigned long long sh[8];
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(256) void radix_kpass_kernel(const RadixParams p, i
 }
 
 // probabilities of the top-k survivors (samp_prob_kernel's expression), their fixed-point total, and the first digit pass of the nucleus search over bits(e)
-__global__ __launch_bounds__(256) void radix_prob_kernel(const RadixParams p, int use_k, int use_p, int nblocks_scale)
+__device__ __forceinline__ void radix_prob_body(const RadixParams& p, int use_k, int use_p, int nblocks_scale)
 {
     __shared__ unsigned long long lh[kRadixBins];
     __shared__ unsigned long long sh[8];
@@ -682,7 +682,7 @@ __device__ __forceinline__ unsigned long long radix_mass_target(float top_p, uns
 }
 
 // nucleus digit pass 1 / 2: pick the previous pass's digit, then sum this pass's digit over the probabilities that share the prefix
-__global__ __launch_bounds__(256) void radix_ppass_kernel(const RadixParams p, int pass)
+__device__ __forceinline__ void radix_ppass_body(const RadixParams& p, int pass)
 {
     __shared__ unsigned long long lh[kRadixBins];
     __shared__ unsigned long long sh[8];
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(256) void radix_ppass_kernel(const RadixParams p, i
 }
 
 // nucleus mask + contiguous-chunk sums for the index-order CDF (samp_mask_kernel with the radix search's threshold)
-__global__ __launch_bounds__(256) void radix_mask_kernel(const RadixParams p, int use_p, int chunk)
+__device__ __forceinline__ void radix_mask_body(const RadixParams& p, int use_p, int chunk)
 {
     __shared__ unsigned long long sh[8];
     __shared__ float sv[4];
@@ -749,20 +749,9 @@ __device__ __forceinline__ float lane_value(float v, int l) { return __int_as_fl
 
 // inverse CDF in token-index order: samp_cdf_kernel's sums and walk, value for value (the same additions in the same order), by one wave that holds the chunk sums in
 // registers and steps over the zeros of the walk: adding 0 leaves the cumulative sum as it is, and after the truncations nearly every entry is 0.
-// ADVANCE: the stochastic twin of argmax_final_advance_kernel -- the draw is slot (*seq_dev + 1) % draws_size of a host-written ring (system-scope load: the host
-// rewrites the slots between replays), and the tail bumps the position, stores the sequence number and (ring != NULL) publishes seq << 32 | token.
-template <bool ADVANCE>
-__global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int nchunks, int chunk)
+// radix_cdf_walk is the walk itself, by ONE wave (`lane` its lane) at the draw r; every lane returns the token.
+__device__ __forceinline__ int radix_cdf_walk(const RadixParams& p, float r, int nchunks, int chunk, int lane)
 {
-    const int lane = threadIdx.x;
-    float r = p.r;
-    unsigned long long seq = 0ull;
-    if (ADVANCE)
-    {
-        seq = *p.seq_dev + 1ull;
-        const uint32_t* slot = reinterpret_cast<const uint32_t*>(p.draws) + (seq % (unsigned long long)p.draws_size);
-        r = __uint_as_float(__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-    }
     const float* cs = p.red + kSampBlocks;
     float c[4];      // chunk sums: lane l holds chunks l, 64 + l, 128 + l, 192 + l
 #pragma unroll
@@ -808,6 +797,24 @@ __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int 
             }
         }
     }
+    return result;
+}
+
+// the one-row tail.  ADVANCE: the stochastic twin of argmax_final_advance_kernel -- the draw is slot (*seq_dev + 1) % draws_size of a host-written ring (system-scope
+// load: the host rewrites the slots between replays), and the tail bumps the position, stores the sequence number and (ring != NULL) publishes seq << 32 | token.
+template <bool ADVANCE>
+__global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int nchunks, int chunk)
+{
+    const int lane = threadIdx.x;
+    float r = p.r;
+    unsigned long long seq = 0ull;
+    if (ADVANCE)
+    {
+        seq = *p.seq_dev + 1ull;
+        const uint32_t* slot = reinterpret_cast<const uint32_t*>(p.draws) + (seq % (unsigned long long)p.draws_size);
+        r = __uint_as_float(__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+    }
+    const int result = radix_cdf_walk(p, r, nchunks, chunk, lane);
     if (lane == 0)
     {
         p.token_out[0] = result;
@@ -818,6 +825,99 @@ __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int 
             if (p.ring != nullptr)
                 __hip_atomic_store(p.ring + (seq % (unsigned long long)p.ring_size), (seq << 32) | (unsigned long long)(uint32_t)result, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
+    }
+}
+
+// the one-row launches
+template <typename T>
+__global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ logits, const RadixParams p, int clear_words) { radix_scale_body(logits, p, clear_words); }
+__global__ __launch_bounds__(256) void radix_kpass_kernel(const RadixParams p, int pass) { radix_kpass_body(p, pass); }
+__global__ __launch_bounds__(256) void radix_prob_kernel(const RadixParams p, int use_k, int use_p, int nblocks_scale) { radix_prob_body(p, use_k, use_p, nblocks_scale); }
+__global__ __launch_bounds__(256) void radix_ppass_kernel(const RadixParams p, int pass) { radix_ppass_body(p, pass); }
+__global__ __launch_bounds__(256) void radix_mask_kernel(const RadixParams p, int use_p, int chunk) { radix_mask_body(p, use_p, chunk); }
+
+// The rows forms: the same bodies with a row dimension in the grid.  blockIdx.y = b picks row b's logits (logits + b * logits_stride) and row b's scratch region
+// (header, histograms, red, w at scratch + b * row_stride bytes); blockIdx.x / gridDim.x are what the one-row launch has, so every walk, every chunk and every float
+// sum of row b is the one-row kernel's on that row: row b's token is sample_radix_fp32's on row b's logits with row b's draw, whatever the other rows hold.
+struct RadixRows
+{
+    RadixParams p;                  // row 0's pointers; p.draws = one draw per row, p.pos = the position word(s) of the tail
+    size_t row_stride;              // bytes between the scratch regions of two rows (a multiple of 8)
+    size_t logits_stride;           // floats between the logits of two rows
+};
+__device__ __forceinline__ RadixParams radix_row(const RadixRows& r, int b)
+{
+    RadixParams p = r.p;
+    const size_t off = (size_t)b * r.row_stride;
+    p.hdr = reinterpret_cast<RadixHeader*>(reinterpret_cast<char*>(r.p.hdr) + off);
+    p.khist = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(r.p.khist) + off);
+    p.phist = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(r.p.phist) + off);
+    p.red = reinterpret_cast<float*>(reinterpret_cast<char*>(r.p.red) + off);
+    p.w = reinterpret_cast<float*>(reinterpret_cast<char*>(r.p.w) + off);
+    return p;
+}
+__global__ __launch_bounds__(256) void radix_scale_rows_kernel(const float* __restrict__ logits, const RadixRows r, int clear_words)
+{
+    const RadixParams p = radix_row(r, blockIdx.y);
+    radix_scale_body(logits + (size_t)blockIdx.y * r.logits_stride, p, clear_words);
+}
+__global__ __launch_bounds__(256) void radix_kpass_rows_kernel(const RadixRows r, int pass)
+{
+    const RadixParams p = radix_row(r, blockIdx.y);
+    radix_kpass_body(p, pass);
+}
+__global__ __launch_bounds__(256) void radix_prob_rows_kernel(const RadixRows r, int use_k, int use_p, int nblocks_scale)
+{
+    const RadixParams p = radix_row(r, blockIdx.y);
+    radix_prob_body(p, use_k, use_p, nblocks_scale);
+}
+__global__ __launch_bounds__(256) void radix_ppass_rows_kernel(const RadixRows r, int pass)
+{
+    const RadixParams p = radix_row(r, blockIdx.y);
+    radix_ppass_body(p, pass);
+}
+__global__ __launch_bounds__(256) void radix_mask_rows_kernel(const RadixRows r, int use_p, int chunk)
+{
+    const RadixParams p = radix_row(r, blockIdx.y);
+    radix_mask_body(p, use_p, chunk);
+}
+
+// The rows tail, one workgroup: wave t walks row t's CDF (radix_cdf_walk: radix_cdf_kernel's additions in its order) at the draw draws[t] -- a system-scope load, the
+// host rewrites the draws between replays -- and the samples s_t meet in LDS; then one lane does the bookkeeping in plain stores.
+//   kRowsTokens:  token_out[b] = s_b, nothing advanced.
+//   kRowsAdvance: where active[b] != 0, token_out[b] = s_b and pos[b] += 1; an inactive row's words are not touched.
+//   kRowsChain:   argmax_chain_accept_kernel's rule with s_t in the place of a_t (token_out is tok[], pos the ONE position word).
+enum { kRowsTokens = 0, kRowsAdvance = 1, kRowsChain = 2 };
+template <int MODE>
+__global__ __launch_bounds__(256) void radix_rows_tail_kernel(const RadixRows r, int rows, int nchunks, int chunk, const int32_t* __restrict__ active, int32_t* __restrict__ result)
+{
+    __shared__ int ss[4];
+    const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+    if (t < rows)
+    {
+        const RadixParams p = radix_row(r, t);
+        const float draw = __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t*>(r.p.draws) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+        const int s = radix_cdf_walk(p, draw, nchunks, chunk, lane);
+        if (lane == 0) ss[t] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int32_t* tok = r.p.token_out;
+    int32_t* pos = r.p.pos;
+    if (MODE == kRowsTokens)
+        for (int b = 0; b < rows; ++b) tok[b] = ss[b];
+    if (MODE == kRowsAdvance)
+        for (int b = 0; b < rows; ++b)
+            if (active[b] != 0) { tok[b] = ss[b]; pos[b] += 1; }
+    if (MODE == kRowsChain)
+    {
+        int n_acc = rows - 1;
+        for (int i = rows - 2; i >= 0; --i)
+            if (ss[i] != tok[i + 1]) n_acc = i;
+        result[0] = n_acc + 1;
+        for (int i = 0; i <= n_acc; ++i) result[1 + i] = ss[i];
+        tok[0] = ss[n_acc];
+        *pos += n_acc + 1;
     }
 }
 
@@ -882,6 +982,53 @@ static int run_radix(const T* logits, int32_t* token_out, int vocab, float softc
     hipLaunchKernelGGL(radix_mask_kernel, dim3(d.nchunks), dim3(256), 0, s, p, d.p_passes ? 1 : 0, d.chunk);
     if (adv) hipLaunchKernelGGL(radix_cdf_kernel<true>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
     else hipLaunchKernelGGL(radix_cdf_kernel<false>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
+    return check_hip(hipGetLastError(), who);
+}
+
+// row stride of the rows scratch: the one-row need, rounded up so that every row's RadixHeader (and its 64-bit histogram) stays 8-byte aligned
+static size_t radix_row_stride(int vocab) { return (plan_radix(vocab, 0, 1.0f).scratch_need + 7) & ~(size_t)7; }
+
+// The radix pipeline over `rows` rows in ONE pipeline: plan_radix's launches for one row, each with the rows in grid.y, and the rows tail in the place of the cdf
+// launch.  mode kRowsTokens: pos / active / result unused; kRowsAdvance: pos[rows], active[rows]; kRowsChain: token_out is tok[rows], pos the one position word.
+static int run_radix_rows(int mode, const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k, float top_p,
+                          const float* draws, void* scratch, size_t scratch_bytes, int32_t* pos, const int32_t* active, int32_t* result, hipStream_t s, const char* who)
+{
+    MILA_REQUIRE(logits && token_out && draws, "%s: null pointer", who);
+    MILA_REQUIRE(mode == kRowsTokens || pos, "%s: null pointer", who);
+    MILA_REQUIRE(mode != kRowsAdvance || active, "%s: null pointer", who);
+    MILA_REQUIRE(mode != kRowsChain || result, "%s: null pointer", who);
+    if (mode == kRowsChain) MILA_REQUIRE(rows >= 2 && rows <= 4, "%s: T=%d rows outside 2 .. 4", who, rows);
+    else MILA_REQUIRE(rows >= 1 && rows <= 4, "%s: rows=%d outside 1 .. 4", who, rows);
+    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
+    MILA_REQUIRE(logits_stride >= (size_t)vocab, "%s: logits_stride %zu < vocab %d", who, logits_stride, vocab);
+    MILA_REQUIRE(temperature > 0.0f, "%s: temperature must be > 0 (temperature <= 0 is the greedy sampler: sample_argmax)", who);
+    MILA_REQUIRE(top_k >= 0 && top_p > 0.0f, "%s: need top_k >= 0, top_p > 0", who);
+    const RadixPlan d = plan_radix(vocab, top_k, top_p);
+    const size_t row_stride = radix_row_stride(vocab), need = row_stride * (size_t)rows;
+    if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, "%s: scratch must be 8-byte aligned", who);
+    RadixRows r{};
+    RadixParams& p = r.p;
+    char* base = reinterpret_cast<char*>(scratch);
+    p.hdr = reinterpret_cast<RadixHeader*>(base);
+    p.khist = reinterpret_cast<uint32_t*>(base + sizeof(RadixHeader));
+    p.phist = reinterpret_cast<unsigned long long*>(p.khist + (size_t)kRadixPasses * kRadixBins);
+    p.red = reinterpret_cast<float*>(base + sizeof(RadixHeader) + kRadixHistBytes);
+    p.w = p.red + 2 * kSampBlocks;
+    p.token_out = token_out; p.vocab = vocab; p.top_k = top_k;
+    p.softcap = softcap; p.temperature = temperature; p.top_p = top_p;
+    p.draws = draws; p.pos = pos;
+    r.row_stride = row_stride; r.logits_stride = logits_stride;
+    const int clear_words = (int)((sizeof(RadixHeader) + kRadixHistBytes) / 4);
+    const unsigned R = (unsigned)rows;
+    hipLaunchKernelGGL(radix_scale_rows_kernel, dim3(d.scale_blocks, R), dim3(256), 0, s, logits, r, clear_words);
+    for (int pass = 0; pass < d.k_passes; ++pass) hipLaunchKernelGGL(radix_kpass_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, pass);
+    hipLaunchKernelGGL(radix_prob_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, d.k_passes ? 1 : 0, d.p_passes ? 1 : 0, d.scale_blocks);
+    for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, pass);
+    hipLaunchKernelGGL(radix_mask_rows_kernel, dim3(d.nchunks, R), dim3(256), 0, s, r, d.p_passes ? 1 : 0, d.chunk);
+    if (mode == kRowsTokens) hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsTokens>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
+    else if (mode == kRowsAdvance) hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsAdvance>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
+    else hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsChain>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
     return check_hip(hipGetLastError(), who);
 }
 
@@ -1011,6 +1158,30 @@ int mila_cdna4_sample_radix_advance_fp32(const float* logits, int32_t* token_out
     const RadixAdvance adv{draws, draws_size, position_dev, seq_dev, ring, ring_size};
     return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream),
                             "sample_radix_advance_fp32");
+}
+
+size_t mila_cdna4_sample_radix_rows_scratch_bytes(int rows, int vocab) { return (rows >= 1 && rows <= 4 && vocab > 0) ? radix_row_stride(vocab) * (size_t)rows : 0; }
+
+int mila_cdna4_sample_radix_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k,
+                                      float top_p, const float* draws, void* scratch, size_t scratch_bytes, mila_stream_t stream)
+{
+    return run_radix_rows(kRowsTokens, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, nullptr, nullptr, nullptr,
+                          as_stream(stream), "sample_radix_rows_fp32");
+}
+
+int mila_cdna4_sample_radix_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k,
+                                              float top_p, const float* draws, void* scratch, size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev,
+                                              mila_stream_t stream)
+{
+    return run_radix_rows(kRowsAdvance, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, positions_dev, active_dev,
+                          nullptr, as_stream(stream), "sample_radix_rows_advance_fp32");
+}
+
+int mila_cdna4_sample_radix_chain_accept_fp32(int32_t* tok, int32_t* result, const float* logits, size_t logits_stride, int T, int vocab, float softcap, float temperature,
+                                              int top_k, float top_p, const float* draws, void* scratch, size_t scratch_bytes, int32_t* position_dev, mila_stream_t stream)
+{
+    return run_radix_rows(kRowsChain, logits, logits_stride, tok, T, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, position_dev, nullptr, result,
+                          as_stream(stream), "sample_radix_chain_accept_fp32");
 }
 
 size_t mila_cdna4_sample_radix_plan_describe(int vocab, int top_k, float top_p, char* buf, size_t cap)

@@ -273,12 +273,25 @@ class Gemma:
         lib.mila_gemma_reset_row.argtypes = [C.c_void_p, C.c_int]
         _check(lib.mila_gemma_reset_row(self.h, int(b)))
 
-    def decode_rows(self, B, max_position, mode="graph", greedy=True):
+    def decode_rows(self, B, max_position, mode="graph", greedy=True, sampling=None, draws=None):
         """one step over rows 0 .. B - 1, eager ("fused") or as a graph replay; greedy: the step ends with the rows sampler tail.  max_position: the largest
-        position among the active rows.  Returns (logits [B, vocab], tokens [B], positions [B]) as they stand AFTER the step."""
+        position among the active rows.  Returns (logits [B, vocab], tokens [B], positions [B]) as they stand AFTER the step.
+        sampling = (temperature, top_k, top_p) with draws = B uniform draws (greedy is then ignored): the step ends with the radix sampler over the rows, row b
+        sampling at draws[b] -- next token and position bump of every active row."""
         lib = load()
         lib.mila_gemma_decode_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         logits, toks, pos = np.empty((B, self.vocab), dtype=np.float32), np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        if (sampling is None) != (draws is None):
+            raise ValueError("Gemma.decode_rows: sampling and draws go together")
+        if sampling is not None:
+            lib.mila_gemma_decode_rows_sampled.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            d = np.ascontiguousarray(draws, dtype=np.float32)
+            if d.size != B:
+                raise ValueError("Gemma.decode_rows: one draw per row")
+            t, k, p = sampling
+            _check(lib.mila_gemma_decode_rows_sampled(self.h, int(B), int(max_position), {"fused": 1, "graph": 2}[mode], float(t), int(k), float(p), d.ctypes.data,
+                                                      logits.ctypes.data, toks.ctypes.data, pos.ctypes.data))
+            return logits, toks, pos
         _check(lib.mila_gemma_decode_rows(self.h, int(B), int(max_position), {"fused": 1, "graph": 2}[mode], int(bool(greedy)), logits.ctypes.data, toks.ctypes.data, pos.ctypes.data))
         return logits, toks, pos
 
@@ -290,24 +303,55 @@ class Gemma:
         _check(lib.mila_gemma_rows_graph_info(self.h, out))
         return {"captures": out[0], "nodes": out[1]}
 
-    def time_decode_rows(self, B, start_position, steps, warmup):
-        """`steps` greedy graph replays of a B-row step, every row active from start_position"""
+    def set_step_sampling(self, which, sampling=None, draws=None):
+        """the sampler tail of the "rows" or the "chain" step for the timing loops that follow: sampling = (temperature, top_k, top_p) with one uniform draw per row;
+        None clears it.  (decode_rows / decode_chain set it per call from their own arguments.)"""
+        lib = load()
+        lib.mila_gemma_set_step_sampling.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_int]
+        if sampling is None:
+            _check(lib.mila_gemma_set_step_sampling(self.h, {"rows": 0, "chain": 1}[which], 1.0, 0, 1.0, None, 0))
+            return
+        d = np.ascontiguousarray(draws, dtype=np.float32)
+        t, k, p = sampling
+        _check(lib.mila_gemma_set_step_sampling(self.h, {"rows": 0, "chain": 1}[which], float(t), int(k), float(p), d.ctypes.data, int(d.size)))
+
+    def time_decode_rows(self, B, start_position, steps, warmup, greedy=True):
+        """`steps` graph replays of a B-row step, every row active from start_position: the greedy step, or (greedy=False) the one that ends in the stochastic tail
+        set_step_sampling("rows", ...) chose -- at the logits and the position bump when none is set"""
         lib = load()
         lib.mila_gemma_time_decode_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        lib.mila_gemma_time_decode_rows_stochastic.argtypes = lib.mila_gemma_time_decode_rows.argtypes
         out = (C.c_double * 2)()
+        if not greedy:
+            _check(lib.mila_gemma_time_decode_rows_stochastic(self.h, int(B), int(start_position), int(steps), int(warmup), out))
+            return {"wall_ms_per_step": out[0], "device_ms_per_step": out[1]}
         _check(lib.mila_gemma_time_decode_rows(self.h, int(B), int(start_position), int(steps), int(warmup), out))
         return {"wall_ms_per_step": out[0], "device_ms_per_step": out[1]}
 
     # ---- chain decode: consecutive positions of one sequence (draft_tokens > 0) ----
-    def decode_chain(self, tokens, position, mode="graph"):
+    def decode_chain(self, tokens, position, mode="graph", sampling=None, draws=None):
         """one chain step: tokens[0] is decoded at `position`, tokens[1:] are drafts for the positions behind it (2 <= len(tokens) <= draft_tokens + 1), eager
         ("fused") or as a graph replay.  Returns (logits [T, vocab], count, accepted tokens [count], new position): the longest correct draft prefix is accepted,
-        so accepted[i] is the greedy token after tokens[:i + 1] and the position advances by count."""
+        so accepted[i] is the greedy token after tokens[:i + 1] and the position advances by count.
+        sampling = (temperature, top_k, top_p) with draws = T uniform draws: the drafts are verified against SAMPLES -- accepted[i] is the radix sampler's token from
+        row i's logits at draws[i], and a draft is accepted exactly when it equals that sample."""
         lib = load()
         lib.mila_gemma_chain_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         t = np.ascontiguousarray(tokens, dtype=np.int32)
         T = int(t.size)
         logits, out = np.empty((T, self.vocab), dtype=np.float32), np.zeros(T + 2, dtype=np.int32)
+        if (sampling is None) != (draws is None):
+            raise ValueError("Gemma.decode_chain: sampling and draws go together")
+        if sampling is not None:
+            lib.mila_gemma_chain_decode_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+            d = np.ascontiguousarray(draws, dtype=np.float32)
+            if d.size != T:
+                raise ValueError("Gemma.decode_chain: one draw per row")
+            tt, k, p = sampling
+            _check(lib.mila_gemma_chain_decode_sampled(self.h, t.ctypes.data, T, int(position), {"fused": 1, "graph": 2}[mode], float(tt), int(k), float(p), d.ctypes.data,
+                                                       logits.ctypes.data, out.ctypes.data))
+            count = int(out[0])
+            return logits, count, out[1:1 + count].tolist(), int(out[T + 1])
         _check(lib.mila_gemma_chain_decode(self.h, t.ctypes.data, T, int(position), {"fused": 1, "graph": 2}[mode], logits.ctypes.data, out.ctypes.data))
         count = int(out[0])
         return logits, count, out[1:1 + count].tolist(), int(out[T + 1])
@@ -320,7 +364,7 @@ class Gemma:
         _check(lib.mila_gemma_chain_graph_info(self.h, out))
         return {"captures": out[0], "nodes": out[1], "rows": out[2]}
 
-    def time_decode_chain(self, T, start_position, steps, warmup):
+    def time_decode_chain(self, T, start_position, steps, warmup):      # (the tail follows set_step_sampling("chain", ...))
         """`steps` graph replays of a T-row chain step from start_position (every step advances by what it accepts)"""
         lib = load()
         lib.mila_gemma_time_chain_decode.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]
@@ -459,18 +503,33 @@ class GemmaModel:
             cls._raise(lib, "GemmaModel.synthetic")
         return cls(h, device)
 
-    def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None):
+    def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
+                 speculative_sampling=False):
         """-> (tokens passed to on_token, finish reason as GenerateStatus's to_string, prompt tokens served from the KV caches).
         top_k = 1 is greedy (SamplingParams); seed reseeds the host RNG that draws the sampler's uniform; cancel_after = n raises the client's stop request
         from inside on_token once n tokens were delivered.
         draft_hint (tests and tools; a draft_tokens model): the tokens expected to follow the prompt -- the drafter of the speculative loop reads its proposals from
-        there in place of the prompt lookup; the output is the plain greedy output whatever the hint holds.  speculation_stats() tells what the loop did."""
+        there in place of the prompt lookup; the output is the plain greedy output whatever the hint holds.  speculation_stats() tells what the loop did.
+        speculative_sampling (GenerateParams::speculative_sampling; a draft_tokens model): a stochastic request takes the speculative loop too, each draft
+        verified against the sample the plain loop would take at that token -- the output is the plain stochastic output for the same seed."""
         lib = load()
         pr = np.ascontiguousarray(prompt, dtype=np.int32)
         st = np.ascontiguousarray(list(stop_tokens), dtype=np.int32)
         cap = int(max_new_tokens) if max_new_tokens is not None else 1 << 16
         out = np.zeros(max(cap, 1), dtype=np.int32)
         n, status, reused = C.c_int64(), C.c_int32(), C.c_int64()
+        if speculative_sampling:
+            if cancel_after is not None:
+                raise ValueError("GemmaModel.generate: speculative_sampling cannot be combined with cancel_after")
+            lib.mila_gemma_model_generate_spec_sampling.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int64,
+                                                                    C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+            hint = np.ascontiguousarray([] if draft_hint is None else draft_hint, dtype=np.int32)
+            stats = (C.c_int64 * 4)()
+            _check(lib.mila_gemma_model_generate_spec_sampling(self.h, pr.ctypes.data, len(pr), -1 if max_new_tokens is None else int(max_new_tokens),
+                                                               st.ctypes.data if len(st) else None, len(st), float(temperature), int(top_k), float(top_p),
+                                                               -1 if seed is None else int(seed), hint.ctypes.data if hint.size else None, int(hint.size), 1,
+                                                               out.ctypes.data, len(out), C.byref(n), C.byref(status), stats))
+            return out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], 0
         if draft_hint is not None:
             if cancel_after is not None:
                 raise ValueError("GemmaModel.generate: draft_hint cannot be combined with cancel_after")

@@ -450,13 +450,26 @@ namespace Mila::Dnn
             const hipError_t e = hipGraphInstantiate( &rows_graph_exec_, rows_graph_, nullptr, nullptr, 0 );
             if ( e != hipSuccess ) { rows_graph_exec_ = nullptr; destroyGraphRows(); hipCheck( e, "hipGraphInstantiate" ); }
             rows_captured_B_ = B; rows_captured_greedy_ = greedy; rows_captured_band_ = band;
+            rows_captured_sampling_ = rows_sampling_; rows_captured_draws_ = rows_draws_;
             ++rows_graph_captures_;
         }
         /// capture on first use and whenever the step changes: another row count, sampler tail, or the live-length bucket of the largest active row
         void ensureGraphRows( int B, dim_t max_position, bool greedy )
         {
-            if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) )
+            if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) ||
+                 ( !greedy && ( !sameSampling( rows_captured_sampling_, rows_sampling_ ) || rows_captured_draws_ != rows_draws_ ) ) )
                 captureGraphRows( B, max_position, greedy );
+        }
+        /// the stochastic sampler as the tail of a non-greedy rows step (mila_cdna4_sample_radix_rows_advance_fp32): with `sp` and `draws` set, decodeRows /
+        /// captureGraphRows with greedy == false run the radix pipeline over the B rows behind the logits, and its tail -- token and position bump of every active
+        /// row -- takes the place of advance_positions_rows.  draws: device address of max_batch floats of host-visible memory, row b's draw at [ b ], which the
+        /// host writes before each step.  Both optional: nullopt / nullptr = the step ends at the logits and the position bump, as before.  ensureGraphRows()
+        /// re-captures when either changes.
+        void setRowsSampling( const std::optional<SamplingParams>& sp, const float* draws )
+        {
+            requireRows( 0 );
+            if ( sp && !( sp->temperature > 0.0f ) ) throw std::invalid_argument( "GemmaTransformer::setRowsSampling: temperature must be > 0 (greedy: the greedy rows step)" );
+            rows_sampling_ = sp; rows_draws_ = draws;
         }
         void replayGraphRows()
         {
@@ -525,13 +538,27 @@ namespace Mila::Dnn
             const hipError_t e = hipGraphInstantiate( &chain_graph_exec_, chain_graph_, nullptr, nullptr, 0 );
             if ( e != hipSuccess ) { chain_graph_exec_ = nullptr; destroyGraphChain(); hipCheck( e, "hipGraphInstantiate" ); }
             chain_captured_T_ = T; chain_captured_band_ = band;
+            chain_captured_sampling_ = chain_sampling_; chain_captured_draws_ = chain_draws_;
             ++chain_graph_captures_;
         }
         /// capture on first use and whenever T or the live-length bucket changes; does NOT touch the device position word otherwise (the caller's loop owns it)
         void ensureGraphChain( int T, dim_t position )
         {
             checkChainStep( T, position );
-            if ( !chain_graph_exec_ || chain_captured_T_ != T || chain_captured_band_ != bandBucket( position ) ) captureGraphChain( T, position );
+            if ( !chain_graph_exec_ || chain_captured_T_ != T || chain_captured_band_ != bandBucket( position ) ||
+                 !sameSampling( chain_captured_sampling_, chain_sampling_ ) || chain_captured_draws_ != chain_draws_ )
+                captureGraphChain( T, position );
+        }
+        /// speculative SAMPLING: with `sp` and `draws` set, a chain step verifies the drafts against SAMPLES instead of argmaxes -- the lm_head leaves the logits
+        /// only, and the tail is mila_cdna4_sample_radix_chain_accept_fp32: row t samples s_t from its own logits at draws[ t ], and a draft is accepted exactly
+        /// when it equals s_t.  With draws[ t ] the draw the one-row loop would use for that token, the emitted tokens are the one-row loop's (coupled draws).
+        /// draws: device address of draft_tokens + 1 floats of host-visible memory.  nullopt / nullptr = the greedy chain step.  Eager decodeChain follows the
+        /// setter at once; ensureGraphChain() re-captures when either changes.
+        void setChainSampling( const std::optional<SamplingParams>& sp, const float* draws )
+        {
+            requireChain();
+            if ( sp && !( sp->temperature > 0.0f ) ) throw std::invalid_argument( "GemmaTransformer::setChainSampling: temperature must be > 0 (greedy: the greedy chain step)" );
+            chain_sampling_ = sp; chain_draws_ = draws;
         }
         void replayGraphChain()
         {
@@ -1171,7 +1198,12 @@ namespace Mila::Dnn
             int partials = 0;
             enqueueFusedStepRows( B, static_cast<int>( band ), greedy ? &partials : nullptr );
             auto& R = *rows_;
-            if ( greedy )
+            if ( !greedy && rowsSamplesInStep() )      // the radix pipeline over the B rows behind the logits; its tail takes the place of the position bump
+                Compute::rocmCheck( mila_cdna4_sample_radix_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
+                                                                               cfg_.final_logit_softcapping, rows_sampling_->temperature, rows_sampling_->top_k, rows_sampling_->top_p,
+                                                                               rows_draws_, R.radix_scratch->data(), R.radix_scratch->sizeInBytes(), R.pos->data(), R.active->data(),
+                                                                               ctx_->getStream() ) );
+            else if ( greedy )
                 Compute::rocmCheck( mila_cdna4_sample_argmax_rows_final_advance( R.tok->data(), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(), partials, R.pos->data(),
                                                                                  R.active->data(), B, ctx_->getStream() ) );
             else
@@ -1182,11 +1214,20 @@ namespace Mila::Dnn
         void enqueueChainStepAndTail( int T, dim_t band, const ChainAt& at )
         {
             int partials = 0;
-            enqueueFusedStepRows( T, static_cast<int>( band ), &partials, &at );
+            const bool stochastic = chainSamples();
+            enqueueFusedStepRows( T, static_cast<int>( band ), stochastic ? nullptr : &partials, &at );      // stochastic: the lm_head leaves the logits only
             auto& R = *rows_;
-            Compute::rocmCheck( mila_cdna4_sample_argmax_chain_accept( R.tok->data(), R.result->data(), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(), partials, pos_dev_->data(), T,
+            if ( stochastic )
+                Compute::rocmCheck( mila_cdna4_sample_radix_chain_accept_fp32( R.tok->data(), R.result->data(), R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), T,
+                                                                               (int)cfg_.vocab_size, cfg_.final_logit_softcapping, chain_sampling_->temperature, chain_sampling_->top_k,
+                                                                               chain_sampling_->top_p, chain_draws_, R.radix_scratch->data(), R.radix_scratch->sizeInBytes(),
+                                                                               pos_dev_->data(), ctx_->getStream() ) );
+            else
+                Compute::rocmCheck( mila_cdna4_sample_argmax_chain_accept( R.tok->data(), R.result->data(), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(), partials, pos_dev_->data(), T,
                                                                        ctx_->getStream() ) );
         }
+        bool rowsSamplesInStep() const noexcept { return rows_sampling_.has_value() && rows_draws_ != nullptr; }
+        bool chainSamples() const noexcept { return chain_sampling_.has_value() && chain_draws_ != nullptr; }
         void requireChain() const
         {
             if ( !rows_ || cfg_.draft_tokens <= 0 ) throw std::logic_error( "GemmaTransformer: the chain interface needs GemmaConfig::draft_tokens > 0" );
@@ -1233,6 +1274,7 @@ namespace Mila::Dnn
         {
             std::unique_ptr<TensorType> qkv, attn, o, down, act, res1, hidden[ 3 ];
             std::unique_ptr<LogitsTensor> logits, sample_scratch, attn_partials;
+            std::unique_ptr<LogitsTensor> radix_scratch;      // the rows radix sampler's workspace, one region per row
             std::unique_ptr<TokenTensor> pos, tok, active;
             std::unique_ptr<TokenTensor> result;      // chain only: {count, accepted tokens ...}, draft_tokens + 2 words
         };
@@ -1254,6 +1296,7 @@ namespace Mila::Dnn
             R.logits = std::make_unique<LogitsTensor>( dev, shape_t{ B, 1, cfg_.vocab_size } );
             R.sample_scratch = std::make_unique<LogitsTensor>( dev, shape_t{ B, static_cast<dim_t>( mila_cdna4_sample_scratch_bytes() / 4 ) } );
             R.attn_partials = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( ( rowsAttnScratchBytes() + 3 ) / 4 ) } );
+            R.radix_scratch = std::make_unique<LogitsTensor>( dev, shape_t{ static_cast<dim_t>( rowsRadixScratchBytes() / 4 ) } );
             R.pos = std::make_unique<TokenTensor>( dev, shape_t{ B } );
             R.tok = std::make_unique<TokenTensor>( dev, shape_t{ B } );
             R.active = std::make_unique<TokenTensor>( dev, shape_t{ B } );
@@ -1274,13 +1317,15 @@ namespace Mila::Dnn
                                  mila_cdna4_attn_chain_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.global_head_dim ) );
             return std::max( mila_cdna4_attn_decode_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.head_dim ), mila_cdna4_attn_decode_scratch_bytes( B, (int)cfg_.num_heads, (int)cfg_.global_head_dim ) );
         }
+        /// the rows radix sampler's workspace for rowsCount() rows (a multiple of 8)
+        size_t rowsRadixScratchBytes() const { return mila_cdna4_sample_radix_rows_scratch_bytes( static_cast<int>( rowsCount() ), (int)cfg_.vocab_size ); }
         size_t rowsStateBytes() const
         {
             if ( !rows_ ) return 0;
             size_t b = 0;
             auto& R = *rows_;
             for ( const auto* t : { R.qkv.get(), R.attn.get(), R.o.get(), R.down.get(), R.act.get(), R.res1.get(), R.hidden[ 0 ].get(), R.hidden[ 1 ].get(), R.hidden[ 2 ].get() } ) b += tensorBytes( t );
-            for ( const auto* t : { R.logits.get(), R.sample_scratch.get(), R.attn_partials.get() } ) b += tensorBytes( t );
+            for ( const auto* t : { R.logits.get(), R.sample_scratch.get(), R.attn_partials.get(), R.radix_scratch.get() } ) b += tensorBytes( t );
             for ( const auto* t : { R.pos.get(), R.tok.get(), R.active.get() } ) b += tensorBytes( t );
             if ( R.result ) b += tensorBytes( R.result.get() );
             return b;
@@ -1293,6 +1338,7 @@ namespace Mila::Dnn
             const size_t maxq = static_cast<size_t>( std::max( cfg_.qWidth( false ), cfg_.qWidth( true ) ) ), maxpacked = static_cast<size_t>( std::max( cfg_.packedQkvWidth( false ), cfg_.packedQkvWidth( true ) ) );
             size_t b = B * ( maxpacked + maxq + 3 * D + static_cast<size_t>( cfg_.hidden_dim ) + 3 * D ) * 2;
             b += B * static_cast<size_t>( cfg_.vocab_size ) * 4 + B * ( ( mila_cdna4_sample_scratch_bytes() / 4 ) * 4 ) + ( ( rowsAttnScratchBytes() + 3 ) / 4 ) * 4 + 3 * B * 4;
+            b += rowsRadixScratchBytes();
             if ( cfg_.draft_tokens > 0 ) return b + ( B + 1 ) * 4;      // the chain's result words; its rows share the one cache
             for ( auto& L : layers_ ) b += ( B - 1 ) * 2 * static_cast<size_t>( cfg_.kvWidth( L.global ) ) * static_cast<size_t>( L.cacheCapacity() ) * 2;
             return b;
@@ -1633,6 +1679,12 @@ namespace Mila::Dnn
         bool rows_captured_greedy_{ false };
         dim_t rows_captured_band_{ 0 };
         size_t rows_graph_captures_{ 0 };
+        // the stochastic tails of the rows / chain step: parameters + the device address of one draw per row, asked for and captured (nullopt / nullptr: none)
+        std::optional<SamplingParams> rows_sampling_, rows_captured_sampling_, chain_sampling_, chain_captured_sampling_;
+        const float* rows_draws_{ nullptr };
+        const float* rows_captured_draws_{ nullptr };
+        const float* chain_draws_{ nullptr };
+        const float* chain_captured_draws_{ nullptr };
         hipGraph_t graph_{ nullptr };
         hipGraphExec_t graph_exec_{ nullptr };
         const int32_t* captured_token_{ nullptr };      // what the captured graph was built for: ensureGraph() re-captures on a mismatch

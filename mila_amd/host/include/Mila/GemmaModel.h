@@ -7,6 +7,8 @@
 // token never leaves the device) and publishes it into a host-visible ring (sequence number << 32 | token, one system-scope store); the host
 // polls its slot while the next step is already running: no event, no copy, no stream wait on the decode path.  A stochastic request runs the same loop: its captured
 // step ends with the radix sampler (mila_cdna4_sample_radix_advance_fp32), whose uniform draw the host writes into a second host-visible ring before each replay.
+// The rows step of generateBatch and the chain step of speculative sampling end in the same sampler run over their rows (mila_cdna4_sample_radix_rows_advance_fp32,
+// mila_cdna4_sample_radix_chain_accept_fp32), one host-written draw per row.
 #pragma once
 
 #include <atomic>
@@ -56,8 +58,23 @@ namespace Mila::Dnn
         std::optional<int> max_new_tokens;       ///< nullopt => run to EOS / the context bound
         SamplingParams sampling{};
         std::vector<int32_t> stop_tokens{};      ///< empty => the model's default stop set
-        DraftFunction draft{};                   ///< speculative greedy decode (GemmaModelConfig::withDraftTokens): the drafter; empty => promptLookupDraft
+        DraftFunction draft{};                   ///< speculative decode (GemmaModelConfig::withDraftTokens): the drafter; empty => promptLookupDraft
+        bool speculative_sampling = false;       ///< a STOCHASTIC request on a withDraftTokens model takes the speculative loop too (coupled draws: the plain tokens)
     };
+
+    /// The draw bookkeeping of speculative sampling, host only.  The plain stochastic loop takes one uniform per sampled token from the model's generator.  A chain
+    /// step of T rows that starts after e sampled tokens verifies its drafts against the samples the plain loop would have taken for tokens e .. e + T - 1, so it
+    /// needs the NEXT T uniforms without taking them: peekDraws.  Afterwards only the tokens that were really emitted count: consumeDraws( n ) leaves the generator
+    /// where n plain draws leave it.
+    inline float nextDraw( std::mt19937_64& rng ) { return std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng ); }
+    inline std::vector<float> peekDraws( const std::mt19937_64& rng, int n )
+    {
+        std::mt19937_64 ahead = rng;
+        std::vector<float> r;
+        for ( int i = 0; i < n; ++i ) r.push_back( nextDraw( ahead ) );
+        return r;
+    }
+    inline void consumeDraws( std::mt19937_64& rng, int n ) { for ( int i = 0; i < n; ++i ) (void)nextDraw( rng ); }
 
     /// The default drafter, prompt lookup: for n = 3, 2, 1 take the LATEST earlier occurrence of the last n tokens of `history` (one that starts before the suffix
     /// itself does) and propose the up-to-k tokens that followed it; the first n with an occurrence decides, no occurrence at any n proposes nothing.  Pure host code.
@@ -79,8 +96,8 @@ namespace Mila::Dnn
         }
         return {};
     }
-    /// what the last greedy generate() of a withDraftTokens model did: decode steps in all, those that were chain steps, the drafter's tokens those carried (padding
-    /// not counted) and how many of them were accepted
+    /// what the last speculative generate() of a withDraftTokens model did (greedy, or stochastic with GenerateParams::speculative_sampling): decode steps in all,
+    /// those that were chain steps, the drafter's tokens those carried (padding not counted) and how many of them were accepted
     struct SpeculationStats { uint64_t steps = 0, chain_steps = 0, drafted = 0, accepted = 0; };
 
     struct GemmaModelConfig
@@ -101,7 +118,10 @@ namespace Mila::Dnn
         GemmaModelConfig& withMaxBatch( dim_t n ) { max_batch_ = n; return *this; }                           ///< GemmaConfig::max_batch: sequences per decode step (generateBatch), 1 .. 4
         dim_t maxBatch() const noexcept { return max_batch_; }
         /// GemmaConfig::draft_tokens (0 .. 3): greedy generate() verifies up to k drafted tokens per step on the chain step and emits up to k + 1 tokens per step --
-        /// token for token the plain greedy output.  A plain step loop (one sync per step, no decode-ahead, as generateBatch); stochastic requests keep the plain path.
+        /// token for token the plain greedy output.  A plain step loop (one sync per step, no decode-ahead, as generateBatch).  Stochastic requests keep the plain
+        /// path unless GenerateParams::speculative_sampling is set: then a draft is verified against the SAMPLE the plain loop would have taken at that token (the
+        /// same uniform draw), so the output is token for token the plain stochastic output for the same seed, and a deterministic draft d is accepted with
+        /// probability p( d ).
         GemmaModelConfig& withDraftTokens( dim_t k ) { draft_tokens_ = k; return *this; }
         dim_t draftTokens() const noexcept { return draft_tokens_; }
         GemmaModelConfig& withKvFp8( bool on ) { kv_fp8_ = on; return *this; }                               ///< PerChannelKvFp8<> on every layer (GemmaConfig::kv_fp8), under any weight policy
@@ -151,6 +171,7 @@ namespace Mila::Dnn
         {
             if ( ring_host_ ) (void)hipHostFree( ring_host_ );
             if ( draws_host_ ) (void)hipHostFree( draws_host_ );
+            if ( row_draws_host_ ) (void)hipHostFree( row_draws_host_ );
         }
 
         /// every architectural parameter comes from the artifact's metadata; `model_config` carries the deployment decisions
@@ -227,7 +248,8 @@ namespace Mila::Dnn
         const std::vector<int32_t>& kvTokenHistory() const noexcept { return kv_token_history_; }
         /// prompt tokens the last generate() did NOT have to prefill
         dim_t lastReusedPrefix() const noexcept { return last_reuse_; }
-        /// the speculative loop's counters of the last greedy generate() (all zero on a model without draft tokens, or after a stochastic request)
+        /// the speculative loop's counters of the last generate() (all zero on a model without draft tokens, or after a stochastic request without
+        /// GenerateParams::speculative_sampling)
         const SpeculationStats& lastSpeculation() const noexcept { return last_speculation_; }
         Network& network() noexcept { return network_; }
 
@@ -255,7 +277,8 @@ namespace Mila::Dnn
         /// token, max_new_tokens, context limit -- the parameters are shared by the rows).  A plain step loop: every step replays the rows graph, reads the rows' tokens
         /// back and retires finished rows by clearing their active word (a retired row stays frozen); no decode-ahead yet.  Greedy: the tokens generate() gives for each
         /// prompt alone.  Stochastic: row b samples with the radix sampler from its own generator seeded seed + b, so a one-prompt batch with seed s gives generate()'s
-        /// tokens after seedSampler( s ).  The prompt-prefix reuse of generate() is dropped: the history is cleared.
+        /// tokens after seedSampler( s ); the sampler runs inside the rows graph, over all rows in one pipeline, at the draws the host writes before each replay.
+        /// The prompt-prefix reuse of generate() is dropped: the history is cleared.
         [[nodiscard]] std::vector<GenerateStatus> generateBatch( std::span<const std::vector<int32_t>> prompts, const std::function<void( int, int32_t )>& on_token,
                                                                  const GenerateParams& params = {}, uint64_t seed = 0 )
         {
@@ -297,6 +320,8 @@ namespace Mila::Dnn
             auto* ctx = net.context();
             const int B = std::max( 2, n );      // a rows step carries at least two rows; a row without a prompt stays inactive
             for ( int b = 0; b < static_cast<int>( net.maxBatch() ); ++b ) net.resetRow( b );
+            if ( greedy ) net.setRowsSampling( std::nullopt, nullptr );
+            else net.setRowsSampling( sp, row_draws_dev_ );      // the rows graph ends in the sampler: token and position bump of every active row
             std::vector<dim_t> position( static_cast<size_t>( n ) );
             std::vector<int> emitted( static_cast<size_t>( n ), 0 );
             std::vector<char> active( static_cast<size_t>( n ), 1 );
@@ -341,9 +366,13 @@ namespace Mila::Dnn
                 dim_t max_position = 0;
                 for ( int b = 0; b < n; ++b ) if ( active[ static_cast<size_t>( b ) ] ) max_position = std::max( max_position, position[ static_cast<size_t>( b ) ] );
                 net.ensureGraphRows( B, max_position, greedy );      // (re-captures only when the largest active row leaves the captured live-length bucket)
+                // stochastic: one draw per active row, from that row's generator in the order the per-row sampler calls took them; the previous replay was drained above
+                if ( !greedy )
+                    for ( int b = 0; b < n; ++b )
+                        if ( active[ static_cast<size_t>( b ) ] ) writeRowDraw( b, draw( b ) );
                 net.replayGraphRows();
                 for ( int b = 0; b < n; ++b )
-                    if ( active[ static_cast<size_t>( b ) ] ) { ++position[ static_cast<size_t>( b ) ]; if ( !greedy ) sampleRow( b ); }
+                    if ( active[ static_cast<size_t>( b ) ] ) ++position[ static_cast<size_t>( b ) ];
             }
             ctx->synchronize();
             return status;
@@ -368,9 +397,24 @@ namespace Mila::Dnn
             std::memset( draws_host_, 0, kSnapshots * sizeof( float ) );
             hipCheck( hipHostGetDevicePointer( &dptr, draws_host_, 0 ), "hipHostGetDevicePointer" );
             draws_dev_ = static_cast<const float*>( dptr );
+            // one draw per row of a rows / chain step with the sampler in it; only a model that has such steps
+            if ( cfg.max_batch > 1 || cfg.draft_tokens > 0 )
+            {
+                hipCheck( hipHostMalloc( reinterpret_cast<void**>( &row_draws_host_ ), kRowDraws * sizeof( float ), hipHostMallocMapped | hipHostMallocCoherent ), "hipHostMalloc (mapped, coherent row draws)" );
+                std::memset( row_draws_host_, 0, kRowDraws * sizeof( float ) );
+                hipCheck( hipHostGetDevicePointer( &dptr, row_draws_host_, 0 ), "hipHostGetDevicePointer" );
+                row_draws_dev_ = static_cast<const float*>( dptr );
+            }
             ctx->synchronize();
         }
 
+        /// row b's draw of the next rows / chain step (the step's tail reads it with a system-scope load; no step is in flight when the host writes)
+        void writeRowDraw( int b, float r )
+        {
+            uint32_t bits;
+            std::memcpy( &bits, &r, 4 );
+            __atomic_store_n( reinterpret_cast<uint32_t*>( row_draws_host_ ) + b, bits, __ATOMIC_RELEASE );
+        }
         static bool isGreedy( const SamplingParams& sp ) noexcept { return sp.top_k == 1 || sp.temperature <= 0.0f; }
 
         // Every sample -- the eager sampler's or the captured step's -- takes the next sequence number on the device and lands in ring slot seq % kSnapshots of
@@ -445,7 +489,7 @@ namespace Mila::Dnn
             const bool greedy = isGreedy( params.sampling );
             dim_t position = seq_len;
             last_speculation_ = SpeculationStats{};
-            if ( greedy && net.draftTokens() > 0 ) return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids );
+            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 ) return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids, greedy );
             enqueueSampleNext( net, params.sampling );
             int emitted = 0;
             const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
@@ -511,17 +555,22 @@ namespace Mila::Dnn
             }
         }
 
-        /// The greedy decode loop of a withDraftTokens model, entered behind the prefill.  Each step decodes the current token at `position` together with up to k
+        /// The decode loop of a withDraftTokens model, entered behind the prefill: greedy, or stochastic with GenerateParams::speculative_sampling.
+        /// Each step decodes the current token at `position` together with up to k
         /// drafted successors (padded with token 0 to k: a padded token that happens to verify is a correct token) on the chain step, reads {count, tokens} back and
         /// emits the accepted tokens under generate()'s rules.  It takes the one-row captured step instead when the drafter proposes nothing, when position + k + 1
         /// would pass the context length, or when position and position + k lie in different live-length buckets (the one case where a chain row would not have the
         /// bits it has alone).  Every token is the plain greedy loop's token.  One sync per step, no decode-ahead.
+        /// Stochastic: the tail of the chain step samples row t at the draw the plain loop would take for that token (peekDraws) and accepts a draft exactly when it
+        /// equals that sample, so every token is the plain stochastic loop's token for the same generator state; only the draws of the tokens that were emitted are
+        /// taken (consumeDraws), and the request leaves rng_ where the plain loop leaves it.  The one-row steps are the captured stochastic step of the plain path.
         template<typename TNet>
         GenerateStatus onGeneratingSpeculative( TNet& net, std::span<const int32_t> prompt, const std::function<void( int32_t )>& on_token, const GenerateParams& params,
-                                                const std::atomic<bool>* stop, const std::unordered_set<int32_t>& stop_ids )
+                                                const std::atomic<bool>* stop, const std::unordered_set<int32_t>& stop_ids, bool greedy )
         {
             auto* ctx = net.context();
             const int k = static_cast<int>( net.draftTokens() );
+            typename TNet::SamplingParams sp; sp.temperature = params.sampling.temperature; sp.top_k = params.sampling.top_k; sp.top_p = params.sampling.top_p;
             const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
             dim_t position = static_cast<dim_t>( prompt.size() );
             std::vector<int32_t> history( prompt.begin(), prompt.end() );
@@ -530,7 +579,9 @@ namespace Mila::Dnn
                 Compute::rocmCheck( mila_cdna4_memcpy_d2h( dst, src, static_cast<size_t>( n ) * 4, ctx->getStream() ) );
                 ctx->synchronize();
             };
-            net.sampleGreedy( *decode_token_device_ );      // the first token, from the prefill's logits
+            // the first token, from the prefill's logits (stochastic: the plain path's call -- one draw, one sequence number)
+            if ( greedy ) net.sampleGreedy( *decode_token_device_ );
+            else enqueueSampleNext( net, params.sampling );
             int32_t token = 0;
             readWords( &token, decode_token_device_->data(), 1 );
             int emitted = 0;
@@ -545,10 +596,23 @@ namespace Mila::Dnn
                 return std::nullopt;
             };
             if ( auto st = emit( token, position ) ) return *st;
-            // the one-row step of this loop: the captured greedy step without the token ring (the loop reads the token back itself)
-            net.setSampleInGraph( true );
-            net.setTokenRing( nullptr, 0, nullptr );
-            net.setGraphSampling( std::nullopt );
+            // the one-row step of this loop: the captured greedy step without the token ring (the loop reads the token back itself), or the plain path's captured
+            // stochastic step (its draw slot follows the sequence counter, which comes with the token ring)
+            if ( greedy )
+            {
+                net.setSampleInGraph( true );
+                net.setTokenRing( nullptr, 0, nullptr );
+                net.setGraphSampling( std::nullopt );
+                net.setChainSampling( std::nullopt, nullptr );
+            }
+            else
+            {
+                net.setSampleInGraph( false );
+                net.setTokenRing( ring_dev_, static_cast<int>( kSnapshots ), seqCounter() );
+                net.setGraphSampling( sp );
+                net.setDrawRing( draws_dev_, static_cast<int>( kSnapshots ) );
+                net.setChainSampling( sp, row_draws_dev_ );
+            }
             net.setDevicePosition( position );
             std::vector<int32_t> row( static_cast<size_t>( k ) + 2 );
             while ( true )
@@ -564,6 +628,14 @@ namespace Mila::Dnn
                 {
                     Compute::rocmCheck( mila_cdna4_memcpy_h2d( decode_token_device_->data(), &token, 4, ctx->getStream() ) );
                     net.ensureGraph( *decode_token_device_, position );
+                    if ( !greedy )      // the sample's draw, into the slot its sequence number reads
+                    {
+                        const float r = nextDraw( rng_ );
+                        uint32_t bits;
+                        std::memcpy( &bits, &r, 4 );
+                        __atomic_store_n( reinterpret_cast<uint32_t*>( draws_host_ ) + ( ( published_ + 1 ) % kSnapshots ), bits, __ATOMIC_RELEASE );
+                        ++published_;
+                    }
                     net.replayGraph();
                     kv_token_history_.push_back( token );
                     ++position;
@@ -575,6 +647,11 @@ namespace Mila::Dnn
                 row[ 0 ] = token;
                 for ( int i = 0; i < k; ++i ) row[ static_cast<size_t>( i ) + 1 ] = i < real ? drafts[ static_cast<size_t>( i ) ] : 0;
                 net.setChainDrafts( row.data(), T );
+                if ( !greedy )      // row t samples at the draw of token emitted + t of the plain loop
+                {
+                    const std::vector<float> draws = peekDraws( rng_, T );
+                    for ( int t = 0; t < T; ++t ) writeRowDraw( t, draws[ static_cast<size_t>( t ) ] );
+                }
                 net.ensureGraphChain( T, position );
                 net.replayGraphChain();
                 readWords( row.data(), net.chainResult().data(), T + 1 );
@@ -590,6 +667,7 @@ namespace Mila::Dnn
                 {
                     token = row[ static_cast<size_t>( i ) + 1 ];
                     if ( i > 0 ) history.push_back( row[ static_cast<size_t>( i ) ] );
+                    if ( !greedy ) consumeDraws( rng_, 1 );      // the plain loop sampled this token: its draw is taken; a token behind the request's end never was
                     if ( auto st = emit( token, position + i + 1 ) ) { ctx->synchronize(); return *st; }
                 }
                 position += count;
@@ -597,6 +675,7 @@ namespace Mila::Dnn
         }
 
         static constexpr size_t kSnapshots = 8;
+        static constexpr size_t kRowDraws = 4;          // rows of a rows / chain step
         SpeculationStats last_speculation_{};
         Network network_;
         GemmaConfig network_config_;
@@ -610,6 +689,8 @@ namespace Mila::Dnn
         unsigned long long* ring_dev_{ nullptr };       // the same memory through its device address
         float* draws_host_{ nullptr };                  // pinned + mapped: the host writes a draw, the captured stochastic step's last node reads it
         const float* draws_dev_{ nullptr };
+        float* row_draws_host_{ nullptr };              // pinned + mapped: one draw per row of a rows / chain step that samples
+        const float* row_draws_dev_{ nullptr };
         uint64_t published_{ 0 };                       // samples enqueued so far (their sequence numbers are 1 .. published_)
     };
 }

@@ -36,8 +36,33 @@ namespace
         unsigned long long* ring_dev{ nullptr };
         std::unique_ptr<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>> seq_dev;      // one 64-bit counter
         uint64_t samples{ 0 };                                                                       // its value
+        // decode_rows / chain_decode with a sampler tail: one draw per row, host-visible, allocated at the first such call
+        static constexpr int kStepDraws = 4;
+        float* step_draws_host{ nullptr };
+        const float* step_draws_dev{ nullptr };
+        /// the device address of the step draws, holding draws[ 0 .. n )
+        const float* stepDraws( const float* draws, int n )
+        {
+            if ( !draws || n < 1 || n > kStepDraws ) throw std::invalid_argument( "a sampled step takes 1 .. 4 draws" );
+            if ( !step_draws_host )
+            {
+                hipCheck( hipHostMalloc( reinterpret_cast<void**>( &step_draws_host ), kStepDraws * sizeof( float ), hipHostMallocMapped | hipHostMallocCoherent ), "hipHostMalloc (mapped, coherent step draws)" );
+                void* dptr = nullptr;
+                hipCheck( hipHostGetDevicePointer( &dptr, step_draws_host, 0 ), "hipHostGetDevicePointer" );
+                step_draws_dev = static_cast<const float*>( dptr );
+            }
+            for ( int i = 0; i < kStepDraws; ++i )
+            {
+                const float v = i < n ? draws[ i ] : 0.0f;
+                uint32_t bits;
+                std::memcpy( &bits, &v, 4 );
+                __atomic_store_n( reinterpret_cast<uint32_t*>( step_draws_host ) + i, bits, __ATOMIC_RELEASE );
+            }
+            return step_draws_dev;
+        }
         ~Runner()
         {
+            if ( step_draws_host ) (void)hipHostFree( step_draws_host );
             if ( draws_host ) (void)hipHostFree( draws_host );
             if ( ring_host ) (void)hipHostFree( ring_host );
         }
@@ -472,13 +497,23 @@ HOST_API int mila_gemma_reset_row( void* h, int b )
 /// one step over rows 0 .. B - 1.  mode 1: eager launches, 2: graph replay (captured on first use and when B, the sampler tail or the live-length bucket change).
 /// greedy != 0: the step ends with the rows sampler tail (next token + position bump of every active row); 0: it ends at the logits, positions bumped.
 /// max_position: the largest position among the active rows.  Outputs (each may be NULL): logits [B, vocab], tokens [B], positions [B] AFTER the step.
-HOST_API int mila_gemma_decode_rows( void* h, int B, int64_t max_position, int mode, int greedy, float* host_logits, int32_t* host_tokens, int32_t* host_positions )
+/// draws != NULL (greedy == 0 only): B uniform draws, one per row -- the step ends with the radix sampler over the rows at (temperature, top_k, top_p): next token
+/// and position bump of every active row (GemmaTransformer::setRowsSampling); NULL: no sampler in the step
+static int decode_rows_impl( void* h, int B, int64_t max_position, int mode, int greedy, float temperature, int top_k, float top_p, const float* draws, float* host_logits,
+                             int32_t* host_tokens, int32_t* host_positions )
 {
     return guarded( [&]
     {
+        auto* r = static_cast<Runner*>( h );
         std::visit( [&]( auto& m )
         {
             if ( mode != 1 && mode != 2 ) throw std::invalid_argument( "decode_rows: mode must be 1 (eager) or 2 (graph)" );
+            if ( draws && !greedy )
+            {
+                typename std::remove_reference_t<decltype( *m )>::SamplingParams sp; sp.temperature = temperature; sp.top_k = top_k; sp.top_p = top_p;
+                m->setRowsSampling( sp, r->stepDraws( draws, B ) );
+            }
+            else m->setRowsSampling( std::nullopt, nullptr );
             if ( mode == 1 ) m->decodeRows( B, max_position, greedy != 0 );
             else { m->ensureGraphRows( B, max_position, greedy != 0 ); m->replayGraphRows(); }
             auto st = m->context()->getStream();
@@ -486,17 +521,54 @@ HOST_API int mila_gemma_decode_rows( void* h, int B, int64_t max_position, int m
             if ( host_tokens ) Compute::rocmCheck( mila_cdna4_memcpy_d2h( host_tokens, m->rowsTokens().data(), static_cast<size_t>( B ) * 4, st ) );
             if ( host_positions ) Compute::rocmCheck( mila_cdna4_memcpy_d2h( host_positions, m->rowsPositions().data(), static_cast<size_t>( B ) * 4, st ) );
             m->context()->synchronize();
-        }, static_cast<Runner*>( h )->model );
+        }, r->model );
     } );
+}
+HOST_API int mila_gemma_decode_rows( void* h, int B, int64_t max_position, int mode, int greedy, float* host_logits, int32_t* host_tokens, int32_t* host_positions )
+{
+    return decode_rows_impl( h, B, max_position, mode, greedy, 1.0f, 0, 1.0f, nullptr, host_logits, host_tokens, host_positions );
+}
+/// mila_gemma_decode_rows ending in the stochastic rows tail: draws[ b ] is row b's uniform draw
+HOST_API int mila_gemma_decode_rows_sampled( void* h, int B, int64_t max_position, int mode, float temperature, int top_k, float top_p, const float* draws, float* host_logits,
+                                             int32_t* host_tokens, int32_t* host_positions )
+{
+    if ( !draws ) { g_err = "invalid_argument: decode_rows_sampled: null draws"; return MILA_E_INVALID_ARGUMENT; }
+    return decode_rows_impl( h, B, max_position, mode, 0, temperature, top_k, top_p, draws, host_logits, host_tokens, host_positions );
 }
 /// out[0] = captures of the rows graph so far, out[1] = kernel nodes of the captured rows step
 HOST_API int mila_gemma_rows_graph_info( void* h, int64_t* out )
 {
     return guarded( [&] { std::visit( [&]( auto& m ) { out[ 0 ] = (int64_t)m->graphRowsCaptureCount(); out[ 1 ] = (int64_t)m->graphRowsNodeCount(); }, static_cast<Runner*>( h )->model ); } );
 }
+/// the sampler tail of the rows step (which = 0) or of the chain step (which = 1) for the calls that follow -- the timing loops among them: draws = n uniform draws,
+/// one per row, kept in the runner's host-visible words; draws == NULL clears it (mila_gemma_decode_rows / mila_gemma_chain_decode set it per call themselves)
+HOST_API int mila_gemma_set_step_sampling( void* h, int which, float temperature, int top_k, float top_p, const float* draws, int n )
+{
+    return guarded( [&]
+    {
+        auto* r = static_cast<Runner*>( h );
+        std::visit( [&]( auto& m )
+        {
+            std::optional<typename std::remove_reference_t<decltype( *m )>::SamplingParams> sp;
+            const float* dev = nullptr;
+            if ( draws ) { sp.emplace(); sp->temperature = temperature; sp->top_k = top_k; sp->top_p = top_p; dev = r->stepDraws( draws, n ); }
+            if ( which == 0 ) m->setRowsSampling( sp, dev ); else m->setChainSampling( sp, dev );
+        }, r->model );
+    } );
+}
+static int time_decode_rows_impl( void* h, int B, int64_t start_position, int steps, int warmup, bool greedy, double* out );
 /// `steps` greedy graph replays of a B-row step with every row active from `start_position` (the caches hold whatever they hold: a timing loop), after `warmup`:
 /// out[0] = wall ms per step, out[1] = device ms per step
 HOST_API int mila_gemma_time_decode_rows( void* h, int B, int64_t start_position, int steps, int warmup, double* out )
+{
+    return time_decode_rows_impl( h, B, start_position, steps, warmup, true, out );
+}
+/// the same loop over the NON-greedy step: it ends in the stochastic rows tail when mila_gemma_set_step_sampling set one, at the logits and the position bump otherwise
+HOST_API int mila_gemma_time_decode_rows_stochastic( void* h, int B, int64_t start_position, int steps, int warmup, double* out )
+{
+    return time_decode_rows_impl( h, B, start_position, steps, warmup, false, out );
+}
+static int time_decode_rows_impl( void* h, int B, int64_t start_position, int steps, int warmup, bool greedy, double* out )
 {
     return guarded( [&]
     {
@@ -506,7 +578,7 @@ HOST_API int mila_gemma_time_decode_rows( void* h, int B, int64_t start_position
             hipStream_t s = reinterpret_cast<hipStream_t>( ctx->getStream() );
             for ( int b = 0; b < B; ++b ) { m->setRowPosition( b, start_position ); m->setRowToken( b, 17 + b ); m->setRowActive( b, true ); }
             int64_t pos = start_position;
-            auto step = [&] { m->ensureGraphRows( B, pos, true ); m->replayGraphRows(); ++pos; };
+            auto step = [&] { m->ensureGraphRows( B, pos, greedy ); m->replayGraphRows(); ++pos; };
             for ( int i = 0; i < warmup; ++i ) step();
             ctx->synchronize();
             hipEvent_t e0, e1;
@@ -531,14 +603,23 @@ HOST_API int mila_gemma_time_decode_rows( void* h, int B, int64_t start_position
 /// one chain step: tokens[ 0 ] = the token at `position`, tokens[ 1 .. T - 1 ] = the drafts behind it.  mode 1: eager launches, 2: graph replay (captured on first use
 /// and when T or the live-length bucket change; the device position word is set to `position` either way).  Outputs (each may be NULL): logits [T, vocab];
 /// out[ 0 ] = count, out[ 1 .. count ] = the accepted tokens, out[ T + 1 ] = the position word after the step (out holds T + 2 words)
-HOST_API int mila_gemma_chain_decode( void* h, const int32_t* tokens, int T, int64_t position, int mode, float* host_logits, int32_t* out )
+/// draws != NULL: T uniform draws -- the step verifies the drafts against samples (GemmaTransformer::setChainSampling); NULL: the greedy chain step
+static int chain_decode_impl( void* h, const int32_t* tokens, int T, int64_t position, int mode, float temperature, int top_k, float top_p, const float* draws, float* host_logits,
+                              int32_t* out )
 {
     return guarded( [&]
     {
+        auto* r = static_cast<Runner*>( h );
         std::visit( [&]( auto& m )
         {
             if ( mode != 1 && mode != 2 ) throw std::invalid_argument( "chain_decode: mode must be 1 (eager) or 2 (graph)" );
             if ( !tokens ) throw std::invalid_argument( "chain_decode: null tokens" );
+            if ( draws )
+            {
+                typename std::remove_reference_t<decltype( *m )>::SamplingParams sp; sp.temperature = temperature; sp.top_k = top_k; sp.top_p = top_p;
+                m->setChainSampling( sp, r->stepDraws( draws, T ) );
+            }
+            else m->setChainSampling( std::nullopt, nullptr );
             m->setChainDrafts( tokens, T );
             if ( mode == 1 ) m->decodeChain( T, position );
             else { m->ensureGraphChain( T, position ); m->setDevicePosition( position ); m->replayGraphChain(); }
@@ -553,8 +634,19 @@ HOST_API int mila_gemma_chain_decode( void* h, const int32_t* tokens, int T, int
                 for ( int i = out[ 0 ] + 1; i <= T; ++i ) out[ i ] = 0;      // words past the accepted run are left over from earlier steps
             }
             m->context()->synchronize();
-        }, static_cast<Runner*>( h )->model );
+        }, r->model );
     } );
+}
+HOST_API int mila_gemma_chain_decode( void* h, const int32_t* tokens, int T, int64_t position, int mode, float* host_logits, int32_t* out )
+{
+    return chain_decode_impl( h, tokens, T, position, mode, 1.0f, 0, 1.0f, nullptr, host_logits, out );
+}
+/// mila_gemma_chain_decode verifying against samples: draws[ t ] is row t's uniform draw
+HOST_API int mila_gemma_chain_decode_sampled( void* h, const int32_t* tokens, int T, int64_t position, int mode, float temperature, int top_k, float top_p, const float* draws,
+                                              float* host_logits, int32_t* out )
+{
+    if ( !draws ) { g_err = "invalid_argument: chain_decode_sampled: null draws"; return MILA_E_INVALID_ARGUMENT; }
+    return chain_decode_impl( h, tokens, T, position, mode, temperature, top_k, top_p, draws, host_logits, out );
 }
 /// out[0] = captures of the chain graph so far, out[1] = kernel nodes of the captured chain step, out[2] = its rows
 HOST_API int mila_gemma_chain_graph_info( void* h, int64_t* out )
@@ -563,7 +655,8 @@ HOST_API int mila_gemma_chain_graph_info( void* h, int64_t* out )
                                       static_cast<Runner*>( h )->model ); } );
 }
 /// `steps` graph replays of a T-row chain step from `start_position` after `warmup` (a timing loop: the caches hold whatever they hold, the drafts are whatever the
-/// token words hold, and every step advances by what it accepts -- at most T, so start_position + (steps + warmup) * T must fit the sequence length):
+/// token words hold, and every step advances by what it accepts -- at most T, so start_position + (steps + warmup) * T must fit the sequence length; the step's tail is
+/// the greedy one unless mila_gemma_set_step_sampling set the sampling one):
 /// out[0] = wall ms per step, out[1] = device ms per step
 HOST_API int mila_gemma_time_chain_decode( void* h, int T, int64_t start_position, int steps, int warmup, double* out )
 {
@@ -1284,15 +1377,16 @@ HOST_API int mila_gemma_model_generate( void* h, const int32_t* prompt, int64_t 
 /// mila_gemma_model_generate with a drafter for the speculative greedy loop: hint (n_hint > 0) = a sequence the drafter reads the continuation from -- the tokens
 /// expected to follow the prompt, so that the draft for the token at index i of the output is hint[ i + 1 .. ]; n_hint == 0 = the default drafter (prompt lookup).
 /// out_stats (may be NULL): GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
-HOST_API int mila_gemma_model_generate_spec( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
-                                             float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status,
-                                             int64_t* out_stats )
+static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                               float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens, int64_t cap, int64_t* out_count,
+                               int32_t* out_status, int64_t* out_stats )
 {
     return guarded( [&]
     {
         auto* m = static_cast<RocmGemmaModel*>( h );
         if ( !m || !prompt || !out_count || !out_status ) throw std::invalid_argument( "gemma_model_generate_spec: null argument" );
         GenerateParams gp;
+        gp.speculative_sampling = speculative_sampling != 0;
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
@@ -1316,6 +1410,21 @@ HOST_API int mila_gemma_model_generate_spec( void* h, const int32_t* prompt, int
             out_stats[ 0 ] = (int64_t)sp.steps; out_stats[ 1 ] = (int64_t)sp.chain_steps; out_stats[ 2 ] = (int64_t)sp.drafted; out_stats[ 3 ] = (int64_t)sp.accepted;
         }
     } );
+}
+
+HOST_API int mila_gemma_model_generate_spec( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                                             float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status,
+                                             int64_t* out_stats )
+{
+    return generate_spec_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, hint, n_hint, 0, out_tokens, cap, out_count, out_status, out_stats );
+}
+/// mila_gemma_model_generate_spec with GenerateParams::speculative_sampling: a stochastic request takes the speculative loop too (coupled draws)
+HOST_API int mila_gemma_model_generate_spec_sampling( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                                      int top_k, float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens,
+                                                      int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_stats )
+{
+    return generate_spec_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, hint, n_hint, speculative_sampling, out_tokens, cap, out_count,
+                               out_status, out_stats );
 }
 
 /// GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
