@@ -718,6 +718,35 @@ MILA_API int mila_cdna4_sample_radix_chain_accept_fp32(int32_t* tok, int32_t* re
                                                        float temperature, int top_k, float top_p, const float* draws, void* scratch, size_t scratch_bytes,
                                                        int32_t* position_dev, mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Token log-probabilities of a decode step (ABI 4, additive; csrc/logprobs.hip): how probable the chosen token was, and the top-n alternatives, from the fp32 logits on
+ * the device -- no logits readback.  With z_i = softcap > 0 ? softcap * tanhf(x_i / softcap) : x_i, m = max z and S = sum expf(z_i - m):
+ *     logprob_i = (z_i - m) - logf(S)
+ * the model's distribution, independent of temperature, top-k and top-p.  "Top-n" = the n largest z, value descending, then LOWER index first (the greedy sampler's tie
+ * rule: on a greedy step top_ids[0] is the emitted token).  top_n = 0 .. min(20, vocab); 0 = the chosen token's log-probability only.
+ * A call is two launches: per row <= 256 workgroups leave (max, sum, local top-n) partials in scratch, then one workgroup per row merges them in a fixed order (ascending
+ * workgroup index) and reads the token from a DEVICE word.  No floating-point atomics: the same bits run to run.
+ *   scratch: token_logprobs_scratch_bytes(rows, vocab, top_n) bytes, 4-byte aligned; 0 for rows outside 1 .. 4, vocab <= 0 or top_n outside 0 .. min(20, vocab).
+ *   token_logprobs_rows_fp32: row b reads logits + b * logits_stride floats (logits_stride >= vocab; the pad is never read) and reports the token tokens_dev[b]:
+ *     logprob_out[b], top_ids_out[b * top_n ..], top_logprobs_out[b * top_n ..] (the two lists may be NULL when top_n = 0).  A row is LEFT UNTOUCHED when active_dev is
+ *     given and active_dev[b] == 0 (a rows step: the active words), or when count_dev is given and b >= *count_dev (a chain step: tokens_dev = result + 1, count_dev =
+ *     result -- only the accepted rows have a token).  ROW INVARIANCE: row b's outputs are, bit for bit, those of a rows = 1 call on that row alone, whatever the other
+ *     rows hold.  A token outside [0, vocab) reports NaN and reads nothing; when the token is one of the top ids its logprob has that entry's bits.
+ *   token_logprobs_publish_fp32: the one-row form for a decode-ahead loop, the same pair of launches.  The final reads s = *seq_dev -- which the step's tail or
+ *     snapshot_token has already bumped for this sample -- and writes one record of token_logprobs_record_words() = 44 32-bit words at ring + (s % ring_size) * 44
+ *     (host-visible memory): [0] tag = the low 32 bits of s, stored LAST by the lane that wrote the payload (release, system scope), [1] token, [2] logprob bits,
+ *     [3] top_n, [4 .. 24) ids, [24 .. 44) logprob bits (only the first top_n of each are written).
+ * Refused before any device work: a null pointer, rows outside 1 .. 4, vocab <= 0, top_n out of range, logits_stride < vocab, ring_size <= 0, a misaligned scratch or
+ * ring (MILA_E_INVALID_ARGUMENT); a scratch that is too small (MILA_E_SCRATCH_TOO_SMALL). */
+MILA_API int mila_cdna4_token_logprobs_record_words(void);
+MILA_API size_t mila_cdna4_token_logprobs_scratch_bytes(int rows, int vocab, int top_n);
+MILA_API int mila_cdna4_token_logprobs_rows_fp32(const float* logits, size_t logits_stride, const int32_t* tokens_dev, int rows, int vocab, float softcap, int top_n,
+                                                 const int32_t* active_dev, const int32_t* count_dev, float* logprob_out, int32_t* top_ids_out,
+                                                 float* top_logprobs_out, void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_token_logprobs_publish_fp32(const float* logits, const int32_t* token_dev, int vocab, float softcap, int top_n,
+                                                    const unsigned long long* seq_dev, uint32_t* ring, int ring_size, void* scratch, size_t scratch_bytes,
+                                                    mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

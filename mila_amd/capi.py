@@ -105,6 +105,11 @@ def load():
     main.mila_cdna4_sample_radix_rows_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, z, p]                     # logits logits_stride token_out | rows vocab softcap temperature top_k top_p | draws | scratch bytes
     main.mila_cdna4_sample_radix_rows_advance_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, z, p, p, p]       # ... | scratch bytes | positions_dev active_dev
     main.mila_cdna4_sample_radix_chain_accept_fp32.argtypes = [p, p, p, z, i, i, f, f, i, f, p, p, z, p, p]       # tok result logits logits_stride | T vocab softcap temperature top_k top_p | draws | scratch bytes | position_dev
+    # token log-probabilities (csrc/logprobs.hip)
+    main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
+    main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
+    main.mila_cdna4_token_logprobs_rows_fp32.argtypes = [p, z, p, i, i, f, i, p, p, p, p, p, p, z, p]             # logits logits_stride tokens_dev | rows vocab softcap top_n | active_dev count_dev | logprob_out top_ids_out top_logprobs_out | scratch bytes
+    main.mila_cdna4_token_logprobs_publish_fp32.argtypes = [p, p, i, f, i, p, p, i, p, z, p]                      # logits token_dev | vocab softcap top_n | seq_dev ring ring_size | scratch bytes
     main.mila_cdna4_kv_dequant_fp8_bf16.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                        # Kc Vc K8 V8 Ks Vs | B NKV HS capacity first_pos count
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.argtypes = [i, i, i, i]                                      # B NKV HS capacity
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.restype = z
@@ -301,6 +306,32 @@ def sample_radix_chain_accept(tok, result, logits, softcap, temperature, top_k, 
          scratch, C.c_size_t(scratch.numel() * scratch.element_size()), position_dev)
 
 
+TOKEN_LOGPROBS_MAX_TOP = 20
+
+
+def token_logprobs_record_words():
+    return int(load().mila_cdna4_token_logprobs_record_words())
+
+
+def token_logprobs_scratch_bytes(rows, vocab, top_n):
+    return int(load().mila_cdna4_token_logprobs_scratch_bytes(int(rows), int(vocab), int(top_n)))
+
+
+def token_logprobs_rows(logits, tokens_dev, softcap, top_n, logprob_out, top_ids_out, top_logprobs_out, scratch, active_dev=None, count_dev=None, vocab=None):
+    """logprob_out[b] <- the log-probability of tokens_dev[b] under row b of `logits` [rows, stride] (fp32), top_ids_out / top_logprobs_out [rows, top_n] <- the top_n
+    alternatives (None when top_n == 0); a row whose active word is 0, or whose index is >= *count_dev, is left untouched"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("token_logprobs_rows_fp32", logits, stride, tokens_dev, int(logits.shape[0]), V, float(softcap), int(top_n), active_dev, count_dev, logprob_out, top_ids_out,
+         top_logprobs_out, scratch, C.c_size_t(scratch.numel() * scratch.element_size()))
+
+
+def token_logprobs_publish(logits, token_dev, softcap, top_n, seq_dev, ring, scratch, ring_size=None):
+    """the one-row form: one record of token_logprobs_record_words() 32-bit words into slot *seq_dev % ring_size of the host-visible `ring`, the tag word last"""
+    words = token_logprobs_record_words()
+    call("token_logprobs_publish_fp32", logits, token_dev, int(logits.numel()), float(softcap), int(top_n), seq_dev, ring,
+         int(ring.numel() // words) if ring_size is None else int(ring_size), scratch, C.c_size_t(scratch.numel() * scratch.element_size()))
+
+
 def prefill_form_name(plan, HS):
     """what last_form() reports for a launch from this plan: the form and its instantiation"""
     return plan["form"] if plan["form"] == "attn_generic" else "%s_hs%d_hb%d_ds%d_nw%d" % (plan["form"], HS, plan["HB"], plan["DS"], plan["NW"])
@@ -363,6 +394,7 @@ EXPORTED = [
     "matvec_rows", "fused_attn_decode_rows_bf16", "sample_argmax_rows_final_advance", "advance_positions_rows",
     "fused_attn_decode_chain_bf16", "attn_decode_chain_scratch_bytes", "fused_qkv_post_rows_devpos", "sample_argmax_chain_accept",
     "sample_radix_rows_scratch_bytes", "sample_radix_rows_fp32", "sample_radix_rows_advance_fp32", "sample_radix_chain_accept_fp32",
+    "token_logprobs_record_words", "token_logprobs_scratch_bytes", "token_logprobs_rows_fp32", "token_logprobs_publish_fp32",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

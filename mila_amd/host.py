@@ -79,6 +79,14 @@ def _check(rc):
         raise RuntimeError(text)
 
 
+def _logprobs_n(n):
+    """the top-n of a logprobs argument: 0 .. 20 (0 = the chosen token's log-probability only)"""
+    n = int(n)
+    if n < 0 or n > capi.TOKEN_LOGPROBS_MAX_TOP:
+        raise ValueError("logprobs must be 0 .. %d (got %d)" % (capi.TOKEN_LOGPROBS_MAX_TOP, n))
+    return n
+
+
 class Gemma:
     """GemmaTransformer<policy> with synthetic weights on cuda:0."""
 
@@ -230,10 +238,28 @@ class Gemma:
         _check(load().mila_gemma_prefill(self.h, t.ctypes.data, t.size, position_offset, out.ctypes.data))
         return out
 
-    def decode(self, token, position, mode="fused"):
+    def decode(self, token, position, mode="fused", logprobs=None):
+        """one decode step; the logits.  logprobs = n (0 .. 20): the step is followed by the greedy sampler and the token log-probability launches (in graph mode
+        they are the captured step's tail), and the call returns (logits, token, logprob, top_ids [n], top_logprobs [n]) -- the greedy token of these logits, its
+        log-probability under the model's distribution and the n most probable tokens"""
         out = np.empty(self.vocab, dtype=np.float32)
+        if logprobs is not None:
+            lib = load()
+            lib.mila_gemma_decode_logprobs.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 5
+            n = _logprobs_n(logprobs)
+            tok, lp, ids, tlp = C.c_int32(), C.c_float(), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+            _check(lib.mila_gemma_decode_logprobs(self.h, int(token), int(position), self.MODES[mode], n, out.ctypes.data, C.addressof(tok), C.addressof(lp),
+                                                  ids.ctypes.data, tlp.ctypes.data))
+            return out, tok.value, np.float32(lp.value), ids, tlp
         _check(load().mila_gemma_decode(self.h, int(token), int(position), self.MODES[mode], out.ctypes.data))
         return out
+
+    def set_step_logprobs(self, n=None):
+        """token log-probabilities (top n, 0 .. 20) in every step that follows -- the timing loops time_decode / time_decode_rows / time_decode_chain among them;
+        None turns them off.  (decode / decode_rows / decode_chain set them per call from their logprobs argument.)"""
+        lib = load()
+        lib.mila_gemma_set_step_logprobs.argtypes = [C.c_void_p, C.c_int]
+        _check(lib.mila_gemma_set_step_logprobs(self.h, -1 if n is None else _logprobs_n(n)))
 
     def generate(self, first_token, start_position, n_tokens, mode="graph"):
         """greedy autoregressive generation with the device sampler; returns the sampled token ids"""
@@ -273,7 +299,7 @@ class Gemma:
         lib.mila_gemma_reset_row.argtypes = [C.c_void_p, C.c_int]
         _check(lib.mila_gemma_reset_row(self.h, int(b)))
 
-    def decode_rows(self, B, max_position, mode="graph", greedy=True, sampling=None, draws=None):
+    def decode_rows(self, B, max_position, mode="graph", greedy=True, sampling=None, draws=None, logprobs=None):
         """one step over rows 0 .. B - 1, eager ("fused") or as a graph replay; greedy: the step ends with the rows sampler tail.  max_position: the largest
         position among the active rows.  Returns (logits [B, vocab], tokens [B], positions [B]) as they stand AFTER the step.
         sampling = (temperature, top_k, top_p) with draws = B uniform draws (greedy is then ignored): the step ends with the radix sampler over the rows, row b
@@ -283,6 +309,19 @@ class Gemma:
         logits, toks, pos = np.empty((B, self.vocab), dtype=np.float32), np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
         if (sampling is None) != (draws is None):
             raise ValueError("Gemma.decode_rows: sampling and draws go together")
+        if logprobs is not None:
+            # ... additionally (logprob [B], top_ids [B, n], top_logprobs [B, n]) of the tokens the tail chose; an inactive row's entries are stale
+            lib.mila_gemma_decode_rows_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+            n = _logprobs_n(logprobs)
+            d = None if draws is None else np.ascontiguousarray(draws, dtype=np.float32)
+            if d is not None and d.size != B:
+                raise ValueError("Gemma.decode_rows: one draw per row")
+            t, k, p = (1.0, 0, 1.0) if sampling is None else sampling
+            lp, ids, tlp = np.empty(B, dtype=np.float32), np.empty((B, n), dtype=np.int32), np.empty((B, n), dtype=np.float32)
+            _check(lib.mila_gemma_decode_rows_logprobs(self.h, int(B), int(max_position), {"fused": 1, "graph": 2}[mode], int(bool(greedy)), float(t), int(k), float(p),
+                                                       None if d is None else d.ctypes.data, n, logits.ctypes.data, toks.ctypes.data, pos.ctypes.data,
+                                                       lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data))
+            return logits, toks, pos, lp, ids, tlp
         if sampling is not None:
             lib.mila_gemma_decode_rows_sampled.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             d = np.ascontiguousarray(draws, dtype=np.float32)
@@ -329,7 +368,7 @@ class Gemma:
         return {"wall_ms_per_step": out[0], "device_ms_per_step": out[1]}
 
     # ---- chain decode: consecutive positions of one sequence (draft_tokens > 0) ----
-    def decode_chain(self, tokens, position, mode="graph", sampling=None, draws=None):
+    def decode_chain(self, tokens, position, mode="graph", sampling=None, draws=None, logprobs=None):
         """one chain step: tokens[0] is decoded at `position`, tokens[1:] are drafts for the positions behind it (2 <= len(tokens) <= draft_tokens + 1), eager
         ("fused") or as a graph replay.  Returns (logits [T, vocab], count, accepted tokens [count], new position): the longest correct draft prefix is accepted,
         so accepted[i] is the greedy token after tokens[:i + 1] and the position advances by count.
@@ -342,6 +381,19 @@ class Gemma:
         logits, out = np.empty((T, self.vocab), dtype=np.float32), np.zeros(T + 2, dtype=np.int32)
         if (sampling is None) != (draws is None):
             raise ValueError("Gemma.decode_chain: sampling and draws go together")
+        if logprobs is not None:
+            # ... additionally (logprob [count], top_ids [count, n], top_logprobs [count, n]) of the accepted tokens
+            lib.mila_gemma_chain_decode_logprobs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+            n = _logprobs_n(logprobs)
+            d = None if draws is None else np.ascontiguousarray(draws, dtype=np.float32)
+            if d is not None and d.size != T:
+                raise ValueError("Gemma.decode_chain: one draw per row")
+            tt, k, p = (1.0, 0, 1.0) if sampling is None else sampling
+            lp, ids, tlp = np.empty(T, dtype=np.float32), np.empty((T, n), dtype=np.int32), np.empty((T, n), dtype=np.float32)
+            _check(lib.mila_gemma_chain_decode_logprobs(self.h, t.ctypes.data, T, int(position), {"fused": 1, "graph": 2}[mode], float(tt), int(k), float(p),
+                                                        None if d is None else d.ctypes.data, n, logits.ctypes.data, out.ctypes.data, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data))
+            count = int(out[0])
+            return logits, count, out[1:1 + count].tolist(), int(out[T + 1]), lp[:count], ids[:count], tlp[:count]
         if sampling is not None:
             lib.mila_gemma_chain_decode_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
             d = np.ascontiguousarray(draws, dtype=np.float32)
@@ -504,8 +556,10 @@ class GemmaModel:
         return cls(h, device)
 
     def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
-                 speculative_sampling=False):
+                 speculative_sampling=False, logprobs=None):
         """-> (tokens passed to on_token, finish reason as GenerateStatus's to_string, prompt tokens served from the KV caches).
+        logprobs = n (0 .. 20; GenerateParams::logprobs): a fourth element, a list of (logprob, top_ids [n], top_logprobs [n]) per emitted token -- its
+        log-probability under the model's distribution (no temperature, no truncation) and the n most probable tokens, computed on the device inside the step.
         top_k = 1 is greedy (SamplingParams); seed reseeds the host RNG that draws the sampler's uniform; cancel_after = n raises the client's stop request
         from inside on_token once n tokens were delivered.
         draft_hint (tests and tools; a draft_tokens model): the tokens expected to follow the prompt -- the drafter of the speculative loop reads its proposals from
@@ -518,6 +572,30 @@ class GemmaModel:
         cap = int(max_new_tokens) if max_new_tokens is not None else 1 << 16
         out = np.zeros(max(cap, 1), dtype=np.int32)
         n, status, reused = C.c_int64(), C.c_int32(), C.c_int64()
+        if logprobs is not None:
+            # GenerateParams::logprobs: the return tuple gains a list of (logprob, top_ids, top_logprobs), one entry per emitted token
+            top_n = _logprobs_n(logprobs)
+            lp, ids, tlp = np.zeros(len(out), dtype=np.float32), np.zeros((len(out), top_n), dtype=np.int32), np.zeros((len(out), top_n), dtype=np.float32)
+            n_lp = C.c_int64()
+            tail = [top_n, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data, C.byref(n_lp)]
+            tail_types = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            head = [self.h, pr.ctypes.data, len(pr), -1 if max_new_tokens is None else int(max_new_tokens), st.ctypes.data if len(st) else None, len(st), float(temperature),
+                    int(top_k), float(top_p), -1 if seed is None else int(seed)]
+            head_types = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int64]
+            if speculative_sampling or draft_hint is not None:
+                if cancel_after is not None:
+                    raise ValueError("GemmaModel.generate: draft_hint / speculative_sampling cannot be combined with cancel_after")
+                hint = np.ascontiguousarray([] if draft_hint is None else draft_hint, dtype=np.int32)
+                stats = (C.c_int64 * 4)()
+                lib.mila_gemma_model_generate_spec_logprobs.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types
+                _check(lib.mila_gemma_model_generate_spec_logprobs(*head, hint.ctypes.data if hint.size else None, int(hint.size), int(bool(speculative_sampling)), out.ctypes.data,
+                                                                   len(out), C.byref(n), C.byref(status), stats, *tail))
+            else:
+                lib.mila_gemma_model_generate_logprobs.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + tail_types
+                _check(lib.mila_gemma_model_generate_logprobs(*head, out.ctypes.data, len(out), C.byref(n), C.byref(status), C.byref(reused),
+                                                              -1 if cancel_after is None else int(cancel_after), *tail))
+            entries = [(np.float32(lp[i]), ids[i].copy(), tlp[i].copy()) for i in range(min(n_lp.value, len(out)))]
+            return out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], reused.value, entries
         if speculative_sampling:
             if cancel_after is not None:
                 raise ValueError("GemmaModel.generate: speculative_sampling cannot be combined with cancel_after")
@@ -555,7 +633,7 @@ class GemmaModel:
         _check(lib.mila_gemma_model_speculation_stats(self.h, out))
         return dict(zip(("steps", "chain_steps", "drafted", "accepted"), [int(v) for v in out]))
 
-    def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0):
+    def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0, logprobs=None):
         """GemmaModel::generateBatch: up to max_batch prompts at once, prompt b in row b -> [(tokens, finish reason)] per prompt, by generate()'s rules.  Row b samples
         from its own generator seeded seed + b."""
         lib = load()
@@ -567,6 +645,18 @@ class GemmaModel:
         cap = int(max_new_tokens) if max_new_tokens is not None else 1 << 16
         out = np.zeros((max(len(prompts), 1), max(cap, 1)), dtype=np.int32)
         counts, status = np.zeros(max(len(prompts), 1), dtype=np.int64), np.zeros(max(len(prompts), 1), dtype=np.int32)
+        if logprobs is not None:
+            # ... with a list of (logprob, top_ids, top_logprobs) per emitted token as a third element of every prompt's tuple
+            top_n = _logprobs_n(logprobs)
+            lib.mila_gemma_model_generate_rows_logprobs.argtypes = lib.mila_gemma_model_generate_rows.argtypes + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lp, ids, tlp = np.zeros(out.shape, dtype=np.float32), np.zeros(out.shape + (top_n,), dtype=np.int32), np.zeros(out.shape + (top_n,), dtype=np.float32)
+            lp_counts = np.zeros(max(len(prompts), 1), dtype=np.int64)
+            _check(lib.mila_gemma_model_generate_rows_logprobs(self.h, flat.ctypes.data, offs.ctypes.data, len(prompts), -1 if max_new_tokens is None else int(max_new_tokens),
+                                                               st.ctypes.data if len(st) else None, len(st), float(temperature), int(top_k), float(top_p), int(seed), out.ctypes.data,
+                                                               out.shape[1], counts.ctypes.data, status.ctypes.data, top_n, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data,
+                                                               lp_counts.ctypes.data))
+            return [(out[b, :min(int(counts[b]), out.shape[1])].tolist(), GENERATE_STATUS[int(status[b])],
+                     [(np.float32(lp[b, i]), ids[b, i].copy(), tlp[b, i].copy()) for i in range(min(int(lp_counts[b]), out.shape[1]))]) for b in range(len(prompts))]
         _check(lib.mila_gemma_model_generate_rows(self.h, flat.ctypes.data, offs.ctypes.data, len(prompts), -1 if max_new_tokens is None else int(max_new_tokens),
                                                   st.ctypes.data if len(st) else None, len(st), float(temperature), int(top_k), float(top_p), int(seed), out.ctypes.data,
                                                   out.shape[1], counts.ctypes.data, status.ctypes.data))

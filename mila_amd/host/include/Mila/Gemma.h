@@ -267,6 +267,8 @@ namespace Mila::Dnn
                 const bool stochastic = graph_sampling_.has_value();
                 if ( stochastic && ( !draw_ring_ || !token_seq_ ) )
                     throw std::invalid_argument( "GemmaTransformer::captureGraph: a stochastic step needs setDrawRing() and the sequence counter of setTokenRing()" );
+                if ( step_lp_ && !stochastic && !sample_in_graph_ )
+                    throw std::invalid_argument( "GemmaTransformer::captureGraph: token log-probabilities need a sampler in the step (setSampleInGraph / setGraphSampling)" );
                 enqueueFusedStep( token.data(), static_cast<int>( captured_band_end_ ), pos_dev_->data(), ( sample_in_graph_ && !stochastic ) ? &sampler_partials : nullptr );
                 // stochastic: the step ends at the logits like the sampler-less one, then the radix pipeline on the model-owned workspace; its last node draws from the
                 // ring, writes the next token, bumps the position and publishes -- in the place of the advance_position node.  One linear chain on one stream.
@@ -281,6 +283,8 @@ namespace Mila::Dnn
                                                                                 ctx_->getStream() ) );
                 else
                     Compute::rocmCheck( mila_cdna4_advance_position( pos_dev_->data(), ctx_->getStream() ) );
+                // the tail has written the next token (and bumped the sequence counter): its log-probability and the alternatives, two more nodes
+                if ( step_lp_ ) enqueueStepLogprobs( token.data() );
             }
             catch ( ... ) { (void)hipStreamEndCapture( s, &g ); if ( g ) (void)hipGraphDestroy( g ); throw; }
             hipCheck( hipStreamEndCapture( s, &g ), "hipStreamEndCapture" );
@@ -292,6 +296,7 @@ namespace Mila::Dnn
             captured_ring_ = token_ring_;
             captured_sampling_ = graph_sampling_;
             captured_draw_ring_ = graph_sampling_ ? draw_ring_ : nullptr;
+            captured_lp_ = step_lp_;
             ++graph_captures_;
         }
         /// capture on first use, and again whenever the captured graph no longer matches what a replay must do: another token
@@ -301,7 +306,7 @@ namespace Mila::Dnn
         void ensureGraph( const TokenTensor& token, dim_t start_position )
         {
             if ( !graph_exec_ || captured_token_ != token.data() || captured_sample_in_graph_ != sample_in_graph_ || captured_ring_ != token_ring_ ||
-                 !sameSampling( captured_sampling_, graph_sampling_ ) || ( graph_sampling_ && captured_draw_ring_ != draw_ring_ ) ||
+                 !sameSampling( captured_sampling_, graph_sampling_ ) || ( graph_sampling_ && captured_draw_ring_ != draw_ring_ ) || captured_lp_ != step_lp_ ||
                  bandBucket( start_position ) != captured_band_end_ )
                 captureGraph( token, start_position );
         }
@@ -348,6 +353,55 @@ namespace Mila::Dnn
             if ( draws && size <= 0 ) throw std::invalid_argument( "GemmaTransformer::setDrawRing: a ring needs a positive size" );
             draw_ring_ = draws; draw_ring_size_ = draws ? size : 0;
         }
+        /// token log-probabilities as part of every step (mila_cdna4_token_logprobs_*): with top_n set (0 .. 20; 0 = the chosen token's only), the one-row step, the
+        /// rows step and the chain step run the two log-probability launches behind their sampler tail -- the tail decides the token, and a captured step is one
+        /// linear chain, so nothing is gained by placing the partials launch earlier.  The one-row step publishes a record into `ring` (device address of ring_size
+        /// records of RocmTokenLogprobsOp::recordWords() host-visible 32-bit words, slot = the sequence counter of setTokenRing(), which the tail has already bumped)
+        /// or, without a ring, writes the op's device outputs; the rows step reports the active rows, the chain step the accepted ones, both into the device outputs
+        /// (tokenLogprobs().read()).  A step without a sampler tail has no token to report: capturing or running one with the setting on is an invalid_argument.
+        /// The scratch and the outputs are allocated by the first call that turns the setting on, and counted in the memory statistics from then on; with the
+        /// setting off a step is launch for launch what it is without this interface.  ensureGraph*() re-capture when the setting changes.
+        void setStepLogprobs( std::optional<int> top_n, uint32_t* ring = nullptr, int ring_size = 0 )
+        {
+            if ( !top_n ) { step_lp_.reset(); return; }
+            if ( ring ? ring_size <= 0 : ring_size != 0 ) throw std::invalid_argument( "GemmaTransformer::setStepLogprobs: a ring and a positive ring size go together" );
+            if ( *top_n < 0 || *top_n > std::min<dim_t>( Compute::RocmTokenLogprobsOp::kMaxTop, cfg_.vocab_size ) )
+                throw std::invalid_argument( "GemmaTransformer::setStepLogprobs: top_n " + std::to_string( *top_n ) + " outside 0 .. min(20, vocabulary)" );
+            if ( !lp_op_ )
+                lp_op_ = std::make_unique<Compute::RocmTokenLogprobsOp>( ctx_, Compute::TokenLogprobsOpConfig{ cfg_.vocab_size, cfg_.final_logit_softcapping,
+                                                                                                                   static_cast<int>( rows_ ? rowsCount() : 1 ) } );
+            step_lp_ = StepLogprobs{ *top_n, ring, ring_size };
+        }
+        std::optional<int> stepLogprobs() const noexcept { return step_lp_ ? std::optional<int>( step_lp_->top_n ) : std::nullopt; }
+        /// the op behind setStepLogprobs() (its device outputs); only after the setting was turned on once
+        Compute::RocmTokenLogprobsOp& tokenLogprobs()
+        {
+            if ( !lp_op_ ) throw std::logic_error( "GemmaTransformer::tokenLogprobs: setStepLogprobs() first" );
+            return *lp_op_;
+        }
+        /// the one-row step's two launches for an EAGER step: `token_dev` holds the token a sampler just chose from logits() (and, in the ring form, snapshot_token or
+        /// the tail has bumped the sequence counter for it).  A captured one-row step runs them itself.
+        void enqueueStepLogprobs( const int32_t* token_dev )
+        {
+            if ( !step_lp_ ) throw std::logic_error( "GemmaTransformer::enqueueStepLogprobs: setStepLogprobs() first" );
+            if ( step_lp_->ring )
+            {
+                if ( !token_seq_ ) throw std::invalid_argument( "GemmaTransformer: the log-probability ring needs the sequence counter of setTokenRing()" );
+                lp_op_->publish( logits_->data(), token_dev, step_lp_->top_n, token_seq_, step_lp_->ring, step_lp_->ring_size );
+            }
+            else
+                lp_op_->forward( logits_->data(), static_cast<size_t>( cfg_.vocab_size ), token_dev, 1, step_lp_->top_n, nullptr, nullptr );
+        }
+        /// the same for row b of the rows interface alone, behind sampleRowGreedy / sampleRowStochastic (a row's first token, from its prefill's logits): the
+        /// outputs land in row 0 of the op's
+        void enqueueRowLogprobs( int b )
+        {
+            requireRows( b );
+            if ( !step_lp_ ) throw std::logic_error( "GemmaTransformer::enqueueRowLogprobs: setStepLogprobs() first" );
+            lp_op_->forward( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, static_cast<size_t>( cfg_.vocab_size ), rows_->tok->data() + b, 1, step_lp_->top_n,
+                             nullptr, nullptr );
+        }
+        bool sampleInGraph() const noexcept { return sample_in_graph_; }
         void setDevicePosition( dim_t position )
         {
             checkPosition( position, 1 );
@@ -451,12 +505,13 @@ namespace Mila::Dnn
             if ( e != hipSuccess ) { rows_graph_exec_ = nullptr; destroyGraphRows(); hipCheck( e, "hipGraphInstantiate" ); }
             rows_captured_B_ = B; rows_captured_greedy_ = greedy; rows_captured_band_ = band;
             rows_captured_sampling_ = rows_sampling_; rows_captured_draws_ = rows_draws_;
+            rows_captured_lp_ = step_lp_;
             ++rows_graph_captures_;
         }
         /// capture on first use and whenever the step changes: another row count, sampler tail, or the live-length bucket of the largest active row
         void ensureGraphRows( int B, dim_t max_position, bool greedy )
         {
-            if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) ||
+            if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) || rows_captured_lp_ != step_lp_ ||
                  ( !greedy && ( !sameSampling( rows_captured_sampling_, rows_sampling_ ) || rows_captured_draws_ != rows_draws_ ) ) )
                 captureGraphRows( B, max_position, greedy );
         }
@@ -539,13 +594,14 @@ namespace Mila::Dnn
             if ( e != hipSuccess ) { chain_graph_exec_ = nullptr; destroyGraphChain(); hipCheck( e, "hipGraphInstantiate" ); }
             chain_captured_T_ = T; chain_captured_band_ = band;
             chain_captured_sampling_ = chain_sampling_; chain_captured_draws_ = chain_draws_;
+            chain_captured_lp_ = step_lp_;
             ++chain_graph_captures_;
         }
         /// capture on first use and whenever T or the live-length bucket changes; does NOT touch the device position word otherwise (the caller's loop owns it)
         void ensureGraphChain( int T, dim_t position )
         {
             checkChainStep( T, position );
-            if ( !chain_graph_exec_ || chain_captured_T_ != T || chain_captured_band_ != bandBucket( position ) ||
+            if ( !chain_graph_exec_ || chain_captured_T_ != T || chain_captured_band_ != bandBucket( position ) || chain_captured_lp_ != step_lp_ ||
                  !sameSampling( chain_captured_sampling_, chain_sampling_ ) || chain_captured_draws_ != chain_draws_ )
                 captureGraphChain( T, position );
         }
@@ -1196,6 +1252,8 @@ namespace Mila::Dnn
         void enqueueRowsStepAndTail( int B, dim_t band, bool greedy )
         {
             int partials = 0;
+            if ( step_lp_ && !greedy && !rowsSamplesInStep() )
+                throw std::invalid_argument( "GemmaTransformer: token log-probabilities need a sampler tail in the rows step (greedy, or setRowsSampling)" );
             enqueueFusedStepRows( B, static_cast<int>( band ), greedy ? &partials : nullptr );
             auto& R = *rows_;
             if ( !greedy && rowsSamplesInStep() )      // the radix pipeline over the B rows behind the logits; its tail takes the place of the position bump
@@ -1208,6 +1266,8 @@ namespace Mila::Dnn
                                                                                  R.active->data(), B, ctx_->getStream() ) );
             else
                 Compute::rocmCheck( mila_cdna4_advance_positions_rows( R.pos->data(), R.active->data(), B, ctx_->getStream() ) );
+            // the tail wrote the active rows' tokens: their log-probabilities; an inactive row's outputs stay as they are
+            if ( step_lp_ ) lp_op_->forward( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, step_lp_->top_n, R.active->data(), nullptr );
         }
         /// a chain step and its tail: the rows step on the chain attention entry, then the accept kernel on the ONE position word (tok[ 0 ] <- the last accepted
         /// token, result <- {count, accepted tokens}, position += count).  One linear chain on one stream.
@@ -1225,6 +1285,8 @@ namespace Mila::Dnn
             else
                 Compute::rocmCheck( mila_cdna4_sample_argmax_chain_accept( R.tok->data(), R.result->data(), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(), partials, pos_dev_->data(), T,
                                                                        ctx_->getStream() ) );
+            // result = {count, accepted tokens}: row t < count reports result[ 1 + t ] under row t's logits; the rejected rows have no token
+            if ( step_lp_ ) lp_op_->forward( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.result->data() + 1, T, step_lp_->top_n, nullptr, R.result->data() );
         }
         bool rowsSamplesInStep() const noexcept { return rows_sampling_.has_value() && rows_draws_ != nullptr; }
         bool chainSamples() const noexcept { return chain_sampling_.has_value() && chain_draws_ != nullptr; }
@@ -1606,6 +1668,7 @@ namespace Mila::Dnn
             for ( const auto* t : { logits_.get(), sample_scratch_.get(), attn_partials_.get(), radix_scratch_.get(), pf_ts_[ 0 ].get(), pf_ts_[ 1 ].get() } ) b += tensorBytes( t );
             b += tensorBytes( pos_dev_.get() );
             b += rowsStateBytes();
+            if ( lp_op_ ) b += lp_op_->stateBytes();
             return b;
         }
         size_t requiredOwnStateBytes() const
@@ -1626,6 +1689,7 @@ namespace Mila::Dnn
             if ( kFmt != 0 ) b += 2 * P * 4;
             b += 4;                                                                                          // the device position word
             b += requiredRowsStateBytes();
+            if ( lp_op_ ) b += lp_op_->stateBytes();                                                         // token log-probabilities, once setStepLogprobs() turned them on
             return b;
         }
     public:
@@ -1699,6 +1763,14 @@ namespace Mila::Dnn
         const float* draw_ring_{ nullptr };
         const float* captured_draw_ring_{ nullptr };
         int draw_ring_size_{ 0 };
+        // token log-probabilities in the step: the setting asked for and what each of the three graphs was captured with; the op exists from the first enable on
+        struct StepLogprobs
+        {
+            int top_n; uint32_t* ring; int ring_size;
+            bool operator==( const StepLogprobs& ) const = default;
+        };
+        std::optional<StepLogprobs> step_lp_, captured_lp_, rows_captured_lp_, chain_captured_lp_;
+        std::unique_ptr<Compute::RocmTokenLogprobsOp> lp_op_;
         static bool sameSampling( const std::optional<SamplingParams>& a, const std::optional<SamplingParams>& b ) noexcept
         {
             if ( a.has_value() != b.has_value() ) return false;

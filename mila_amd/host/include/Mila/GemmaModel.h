@@ -53,6 +53,16 @@ namespace Mila::Dnn
     };
     /// proposes up to k tokens that may follow `history` (prompt + emitted tokens; its last element is the token about to be decoded)
     using DraftFunction = std::function<std::vector<int32_t>( std::span<const int32_t> history, int k )>;
+    /// GenerateParams::on_logprobs: the log-probability of an emitted token under the model's distribution (softmax of the soft-capped logits: no temperature, no
+    /// top-k / top-p) and the top_n most probable tokens, most probable first, ties to the lower id.  The spans are valid during the call only.
+    struct TokenLogprobs
+    {
+        int row;                                 ///< generateBatch: the prompt's row; 0 otherwise
+        int32_t token;
+        float logprob;
+        std::span<const int32_t> top_ids;
+        std::span<const float> top_logprobs;
+    };
     struct GenerateParams
     {
         std::optional<int> max_new_tokens;       ///< nullopt => run to EOS / the context bound
@@ -60,6 +70,38 @@ namespace Mila::Dnn
         std::vector<int32_t> stop_tokens{};      ///< empty => the model's default stop set
         DraftFunction draft{};                   ///< speculative decode (GemmaModelConfig::withDraftTokens): the drafter; empty => promptLookupDraft
         bool speculative_sampling = false;       ///< a STOCHASTIC request on a withDraftTokens model takes the speculative loop too (coupled draws: the plain tokens)
+        /// token log-probabilities: the top-n to report (0 .. 20, 0 = the emitted token's alone); on_logprobs is then called immediately before on_token, for exactly
+        /// the tokens on_token sees.  Computed on the device inside the decode step; tokens, status, generator state and prefix reuse are what they are without it.
+        std::optional<int> logprobs;
+        std::function<void( const TokenLogprobs& )> on_logprobs{};
+    };
+    /// throws invalid_argument for a GenerateParams::logprobs outside 0 .. min(20, vocabulary)
+    inline void checkLogprobsRequest( const GenerateParams& params, dim_t vocab )
+    {
+        if ( params.logprobs && ( *params.logprobs < 0 || *params.logprobs > std::min<dim_t>( Compute::RocmTokenLogprobsOp::kMaxTop, vocab ) ) )
+            throw std::invalid_argument( "GenerateParams::logprobs must be 0 .. min(20, vocabulary) (got " + std::to_string( *params.logprobs ) + ")" );
+    }
+    /// host copies of the log-probabilities of up to four rows, and the callback over one of them
+    struct TokenLogprobsRows
+    {
+        static constexpr int kMaxTop = Compute::RocmTokenLogprobsOp::kMaxTop;
+        int top_n = 0;
+        float logprob[ 4 ]{};
+        int32_t top_ids[ 4 * kMaxTop ]{};
+        float top_logprobs[ 4 * kMaxTop ]{};
+        /// rows 0 .. rows - 1 of the op's device outputs (synchronizes)
+        void read( const Compute::RocmTokenLogprobsOp& op, int rows ) { op.read( rows, top_n, logprob, top_ids, top_logprobs ); }
+        /// one row of the op's outputs (row 0 there) into row `b` here
+        void readInto( const Compute::RocmTokenLogprobsOp& op, int b )
+        {
+            op.read( 1, top_n, logprob + b, top_ids + static_cast<size_t>( b ) * top_n, top_logprobs + static_cast<size_t>( b ) * top_n );
+        }
+        void report( const std::function<void( const TokenLogprobs& )>& cb, int out_row, int b, int32_t token ) const
+        {
+            if ( !cb ) return;
+            const size_t n = static_cast<size_t>( top_n );
+            cb( TokenLogprobs{ out_row, token, logprob[ b ], std::span<const int32_t>( top_ids + b * n, n ), std::span<const float>( top_logprobs + b * n, n ) } );
+        }
     };
 
     /// The draw bookkeeping of speculative sampling, host only.  The plain stochastic loop takes one uniform per sampled token from the model's generator.  A chain
@@ -171,6 +213,7 @@ namespace Mila::Dnn
         {
             if ( ring_host_ ) (void)hipHostFree( ring_host_ );
             if ( draws_host_ ) (void)hipHostFree( draws_host_ );
+            if ( lp_ring_host_ ) (void)hipHostFree( lp_ring_host_ );
             if ( row_draws_host_ ) (void)hipHostFree( row_draws_host_ );
         }
 
@@ -308,6 +351,7 @@ namespace Mila::Dnn
                 for ( int32_t t : prompt )
                     if ( t < 0 || t >= vocabSize() ) throw std::invalid_argument( "GemmaModel::generateBatch: token id " + std::to_string( t ) + " outside the vocabulary" );
             }
+            checkLogprobsRequest( params, vocabSize() );
             std::unordered_set<int32_t> stop_ids;
             if ( params.stop_tokens.empty() ) stop_ids = stopTokens();
             else stop_ids.insert( params.stop_tokens.begin(), params.stop_tokens.end() );
@@ -322,6 +366,10 @@ namespace Mila::Dnn
             for ( int b = 0; b < static_cast<int>( net.maxBatch() ); ++b ) net.resetRow( b );
             if ( greedy ) net.setRowsSampling( std::nullopt, nullptr );
             else net.setRowsSampling( sp, row_draws_dev_ );      // the rows graph ends in the sampler: token and position bump of every active row
+            // log-probabilities: the rows step reports its active rows into the op's device outputs, read back with the tokens; a row's first token is reported alone
+            net.setStepLogprobs( params.logprobs );
+            TokenLogprobsRows lp;
+            lp.top_n = params.logprobs.value_or( 0 );
             std::vector<dim_t> position( static_cast<size_t>( n ) );
             std::vector<int> emitted( static_cast<size_t>( n ), 0 );
             std::vector<char> active( static_cast<size_t>( n ), 1 );
@@ -336,15 +384,18 @@ namespace Mila::Dnn
                 ctx->synchronize();
                 position[ static_cast<size_t>( b ) ] = len;
                 sampleRow( b );      // the first token, from the prefill's logits
+                if ( params.logprobs ) { net.enqueueRowLogprobs( b ); lp.readInto( net.tokenLogprobs(), b ); }
                 net.setRowActive( b, true );
             }
             const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
             std::vector<int32_t> tokens( static_cast<size_t>( B ) );
             int live = n;
+            bool stepped = false;
             while ( true )
             {
                 Compute::rocmCheck( mila_cdna4_memcpy_d2h( tokens.data(), net.rowsTokens().data(), static_cast<size_t>( B ) * 4, ctx->getStream() ) );
                 ctx->synchronize();
+                if ( params.logprobs && stepped ) lp.read( net.tokenLogprobs(), B );      // (a retired row's entries are stale: never reported)
                 for ( int b = 0; b < n; ++b )
                 {
                     const size_t i = static_cast<size_t>( b );
@@ -354,6 +405,7 @@ namespace Mila::Dnn
                     if ( stop_ids.contains( token ) ) status[ i ] = GenerateStatus::Success;
                     else
                     {
+                        if ( params.logprobs ) lp.report( params.on_logprobs, b, b, token );
                         on_token( b, token );
                         ++emitted[ i ];
                         if ( emitted[ i ] >= max_new ) status[ i ] = GenerateStatus::MaxNewTokensReached;
@@ -371,6 +423,7 @@ namespace Mila::Dnn
                     for ( int b = 0; b < n; ++b )
                         if ( active[ static_cast<size_t>( b ) ] ) writeRowDraw( b, draw( b ) );
                 net.replayGraphRows();
+                stepped = true;
                 for ( int b = 0; b < n; ++b )
                     if ( active[ static_cast<size_t>( b ) ] ) ++position[ static_cast<size_t>( b ) ];
             }
@@ -450,6 +503,34 @@ namespace Mila::Dnn
             }
         }
 
+        void ensureLogprobRing()
+        {
+            if ( lp_ring_host_ ) return;
+            const size_t bytes = kSnapshots * static_cast<size_t>( Compute::RocmTokenLogprobsOp::recordWords() ) * sizeof( uint32_t );
+            hipCheck( hipHostMalloc( reinterpret_cast<void**>( &lp_ring_host_ ), bytes, hipHostMallocMapped | hipHostMallocCoherent ), "hipHostMalloc (mapped, coherent log-probability ring)" );
+            std::memset( lp_ring_host_, 0, bytes );
+            void* dptr = nullptr;
+            hipCheck( hipHostGetDevicePointer( &dptr, lp_ring_host_, 0 ), "hipHostGetDevicePointer" );
+            lp_ring_dev_ = static_cast<uint32_t*>( dptr );
+        }
+        /// awaitSampledToken for the log-probability record of sample `seq` (its tag is stored last): row 0 of `lp` <- the record
+        void awaitLogprobRecord( uint64_t seq, int32_t token, TokenLogprobsRows& lp )
+        {
+            const size_t words = static_cast<size_t>( Compute::RocmTokenLogprobsOp::recordWords() );
+            uint32_t* rec = lp_ring_host_ + ( seq % kSnapshots ) * words;
+            const auto t0 = std::chrono::steady_clock::now();
+            for ( uint64_t spins = 0; __atomic_load_n( rec, __ATOMIC_ACQUIRE ) != static_cast<uint32_t>( seq & 0xffffffffull ); ++spins )
+                if ( ( spins & 1023 ) == 1023 )
+                {
+                    if ( std::chrono::steady_clock::now() - t0 > std::chrono::seconds( 20 ) ) throw std::runtime_error( "GemmaModel::awaitLogprobRecord: the device did not publish a record within 20 s" );
+                    std::this_thread::yield();
+                }
+            if ( static_cast<int32_t>( rec[ 1 ] ) != token || static_cast<int>( rec[ 3 ] ) != lp.top_n ) throw std::runtime_error( "GemmaModel::awaitLogprobRecord: the record is not this sample's" );
+            std::memcpy( lp.logprob, rec + 2, 4 );
+            std::memcpy( lp.top_ids, rec + 4, static_cast<size_t>( lp.top_n ) * 4 );
+            std::memcpy( lp.top_logprobs, rec + 4 + TokenLogprobsRows::kMaxTop, static_cast<size_t>( lp.top_n ) * 4 );
+        }
+
         template<typename TNet>
         GenerateStatus onGenerating( TNet& net, std::span<const int32_t> prompt, const std::function<void( int32_t )>& on_token, const GenerateParams& params, const std::atomic<bool>* stop )
         {
@@ -459,6 +540,7 @@ namespace Mila::Dnn
                 throw std::invalid_argument( "GemmaModel::onGenerating: prompt length " + std::to_string( prompt.size() ) + " exceeds deployment context length " + std::to_string( contextLength() ) );
             for ( int32_t t : prompt )
                 if ( t < 0 || t >= vocabSize() ) throw std::invalid_argument( "GemmaModel::onGenerating: token id " + std::to_string( t ) + " outside the vocabulary" );
+            checkLogprobsRequest( params, vocabSize() );
             std::unordered_set<int32_t> stop_ids;
             if ( params.stop_tokens.empty() ) stop_ids = stopTokens();
             else stop_ids.insert( params.stop_tokens.begin(), params.stop_tokens.end() );
@@ -490,7 +572,19 @@ namespace Mila::Dnn
             dim_t position = seq_len;
             last_speculation_ = SpeculationStats{};
             if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 ) return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids, greedy );
+            // log-probabilities travel like the tokens: every sample's record lands in slot seq % kSnapshots of a second host-visible ring, written by the two launches
+            // behind the sampler -- eagerly for the first token, as the captured step's last nodes afterwards
+            if ( params.logprobs )
+            {
+                ensureLogprobRing();
+                net.setTokenRing( ring_dev_, static_cast<int>( kSnapshots ), seqCounter() );      // (its sequence counter; the graph setup below repeats the call)
+                net.setStepLogprobs( params.logprobs, lp_ring_dev_, static_cast<int>( kSnapshots ) );
+            }
+            else net.setStepLogprobs( std::nullopt );
+            TokenLogprobsRows lp;
+            lp.top_n = params.logprobs.value_or( 0 );
             enqueueSampleNext( net, params.sampling );
+            if ( params.logprobs ) net.enqueueStepLogprobs( decode_token_device_->data() );
             int emitted = 0;
             const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
             if ( position < contextLength() )
@@ -544,7 +638,11 @@ namespace Mila::Dnn
                     ctx->synchronize();
                     return GenerateStatus::Success;
                 }
-                try { on_token( token ); }
+                try
+                {
+                    if ( params.logprobs ) { awaitLogprobRecord( mine, token, lp ); lp.report( params.on_logprobs, 0, 0, token ); }
+                    on_token( token );
+                }
                 catch ( ... )
                 {
                     if ( ahead && !greedy ) rng_ = rng_before_ahead;      // the eager loop drew only after on_token returned
@@ -579,16 +677,24 @@ namespace Mila::Dnn
                 Compute::rocmCheck( mila_cdna4_memcpy_d2h( dst, src, static_cast<size_t>( n ) * 4, ctx->getStream() ) );
                 ctx->synchronize();
             };
+            // log-probabilities: every step of this loop reads its tokens back, and reads the op's device outputs with them (no ring): the one-row step reports row 0,
+            // the chain step its accepted rows
+            net.setStepLogprobs( params.logprobs );
+            TokenLogprobsRows lp;
+            lp.top_n = params.logprobs.value_or( 0 );
             // the first token, from the prefill's logits (stochastic: the plain path's call -- one draw, one sequence number)
             if ( greedy ) net.sampleGreedy( *decode_token_device_ );
             else enqueueSampleNext( net, params.sampling );
+            if ( params.logprobs ) net.enqueueStepLogprobs( decode_token_device_->data() );
             int32_t token = 0;
             readWords( &token, decode_token_device_->data(), 1 );
+            if ( params.logprobs ) lp.read( net.tokenLogprobs(), 1 );
             int emitted = 0;
-            // emits one token under generate()'s rules; `at` = the position the token would be decoded at.  nullopt: go on
-            auto emit = [&]( int32_t t, dim_t at ) -> std::optional<GenerateStatus>
+            // emits one token under generate()'s rules; `at` = the position the token would be decoded at, `b` = its row in lp.  nullopt: go on
+            auto emit = [&]( int32_t t, dim_t at, int b = 0 ) -> std::optional<GenerateStatus>
             {
                 if ( stop_ids.contains( t ) ) return GenerateStatus::Success;
+                if ( params.logprobs ) lp.report( params.on_logprobs, 0, b, t );
                 on_token( t );
                 ++emitted;
                 if ( emitted >= max_new ) return GenerateStatus::MaxNewTokensReached;
@@ -640,6 +746,7 @@ namespace Mila::Dnn
                     kv_token_history_.push_back( token );
                     ++position;
                     readWords( &token, decode_token_device_->data(), 1 );
+                    if ( params.logprobs ) lp.read( net.tokenLogprobs(), 1 );
                     if ( auto st = emit( token, position ) ) return *st;
                     continue;
                 }
@@ -657,6 +764,7 @@ namespace Mila::Dnn
                 readWords( row.data(), net.chainResult().data(), T + 1 );
                 const int count = row[ 0 ];
                 if ( count < 1 || count > T ) throw std::runtime_error( "GemmaModel: the chain step reported " + std::to_string( count ) + " accepted tokens" );
+                if ( params.logprobs ) lp.read( net.tokenLogprobs(), count );
                 ++last_speculation_.chain_steps;
                 last_speculation_.drafted += static_cast<uint64_t>( real );
                 last_speculation_.accepted += static_cast<uint64_t>( std::min( count - 1, real ) );
@@ -668,7 +776,7 @@ namespace Mila::Dnn
                     token = row[ static_cast<size_t>( i ) + 1 ];
                     if ( i > 0 ) history.push_back( row[ static_cast<size_t>( i ) ] );
                     if ( !greedy ) consumeDraws( rng_, 1 );      // the plain loop sampled this token: its draw is taken; a token behind the request's end never was
-                    if ( auto st = emit( token, position + i + 1 ) ) { ctx->synchronize(); return *st; }
+                    if ( auto st = emit( token, position + i + 1, i ) ) { ctx->synchronize(); return *st; }
                 }
                 position += count;
             }
@@ -691,6 +799,8 @@ namespace Mila::Dnn
         const float* draws_dev_{ nullptr };
         float* row_draws_host_{ nullptr };              // pinned + mapped: one draw per row of a rows / chain step that samples
         const float* row_draws_dev_{ nullptr };
+        uint32_t* lp_ring_host_{ nullptr };             // pinned + mapped, from the first request with log-probabilities on: kSnapshots records the device writes, the host polls
+        uint32_t* lp_ring_dev_{ nullptr };
         uint64_t published_{ 0 };                       // samples enqueued so far (their sequence numbers are 1 .. published_)
     };
 }

@@ -1212,6 +1212,72 @@ namespace Mila::Dnn::Compute
     };
     template<> struct OperationTraits<OperationType::SamplingOp, DeviceType::Rocm, TensorDataType::FP32> { using type = RocmSamplingOp; };
 
+    // ---------------------------------------------------------------------------------------
+    // Token log-probabilities (mila_cdna4_token_logprobs_*, csrc/logprobs.hip): the log-probability of the token a step chose and of the top-n alternatives, from the
+    // fp32 logits on the device.  The op owns the kernels' scratch (max_rows regions at the widest list) and the device outputs of the rows form; the publish form
+    // writes a record into a caller-owned host-visible ring instead.  Both are two launches on the context's stream; nothing synchronizes.
+    // ---------------------------------------------------------------------------------------
+    struct TokenLogprobsOpConfig { dim_t vocab_size{ 0 }; float final_logit_softcap{ 0.0f }; int max_rows{ 1 }; };
+
+    class RocmTokenLogprobsOp : public Operation<DeviceType::Rocm, TensorDataType::FP32>
+    {
+    public:
+        static constexpr int kMaxTop = 20;
+        RocmTokenLogprobsOp( IExecutionContext* ctx, const TokenLogprobsOpConfig& cfg ) : Operation( ctx ), cfg_( cfg )
+        {
+            if ( cfg.vocab_size <= 0 ) throw std::invalid_argument( "RocmTokenLogprobsOp: vocabulary size must be positive" );
+            if ( cfg.max_rows < 1 || cfg.max_rows > 4 ) throw std::invalid_argument( "RocmTokenLogprobsOp: 1 .. 4 rows" );
+            const int V = narrowToKernelIndex( cfg.vocab_size, "vocab" );
+            scratch_bytes_ = mila_cdna4_token_logprobs_scratch_bytes( cfg.max_rows, V, maxTop() );
+            const auto dev = context_->getDeviceId();
+            scratch_ = std::make_unique<Tensor<TensorDataType::UINT8, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( scratch_bytes_ ) } );
+            logprob_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ cfg.max_rows } );
+            top_ids_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ cfg.max_rows, kMaxTop } );
+            top_logprobs_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ cfg.max_rows, kMaxTop } );
+        }
+        /// the longest list this vocabulary allows
+        int maxTop() const { return static_cast<int>( std::min<dim_t>( kMaxTop, cfg_.vocab_size ) ); }
+        void checkTop( int top_n ) const
+        {
+            if ( top_n < 0 || top_n > maxTop() ) throw std::invalid_argument( "token log-probabilities: top_n " + std::to_string( top_n ) + " outside 0 .. " + std::to_string( maxTop() ) );
+        }
+        /// rows 0 .. rows - 1 of `logits` (logits_stride floats apart) report tokens_dev[ b ] into the op's outputs: logprob [ b ], ids / logprobs [ b * top_n .. ).  A row
+        /// whose active word is 0, or whose index is >= *count_dev, keeps what it held (either pointer may be null)
+        void forward( const float* logits, size_t logits_stride, const int32_t* tokens_dev, int rows, int top_n, const int32_t* active_dev, const int32_t* count_dev )
+        {
+            checkTop( top_n );
+            if ( rows < 1 || rows > cfg_.max_rows ) throw std::invalid_argument( "RocmTokenLogprobsOp::forward: rows outside 1 .. max_rows" );
+            rocmCheck( mila_cdna4_token_logprobs_rows_fp32( logits, logits_stride, tokens_dev, rows, narrowToKernelIndex( cfg_.vocab_size, "vocab" ), cfg_.final_logit_softcap, top_n,
+                                                            active_dev, count_dev, logprob_->data(), top_ids_->data(), top_logprobs_->data(), scratch_->rawData(), scratch_bytes_,
+                                                            context_->getStream() ) );
+        }
+        /// the one-row form of a decode-ahead loop: one record of recordWords() 32-bit words into slot *seq_dev % ring_size of the host-visible ring, the tag last
+        void publish( const float* logits, const int32_t* token_dev, int top_n, const unsigned long long* seq_dev, uint32_t* ring, int ring_size )
+        {
+            checkTop( top_n );
+            rocmCheck( mila_cdna4_token_logprobs_publish_fp32( logits, token_dev, narrowToKernelIndex( cfg_.vocab_size, "vocab" ), cfg_.final_logit_softcap, top_n, seq_dev, ring,
+                                                               ring_size, scratch_->rawData(), scratch_bytes_, context_->getStream() ) );
+        }
+        static int recordWords() { return mila_cdna4_token_logprobs_record_words(); }
+        /// the outputs of the last forward( .., rows, top_n, .. ) to the host (synchronizes): logprob [rows], ids / logprobs [rows * top_n]; null pointers are skipped
+        void read( int rows, int top_n, float* logprob, int32_t* top_ids, float* top_logprobs ) const
+        {
+            const size_t list = static_cast<size_t>( rows ) * static_cast<size_t>( top_n );
+            if ( logprob ) rocmCheck( mila_cdna4_memcpy_d2h( logprob, logprob_->data(), static_cast<size_t>( rows ) * 4, context_->getStream() ) );
+            if ( top_ids && list ) rocmCheck( mila_cdna4_memcpy_d2h( top_ids, top_ids_->data(), list * 4, context_->getStream() ) );
+            if ( top_logprobs && list ) rocmCheck( mila_cdna4_memcpy_d2h( top_logprobs, top_logprobs_->data(), list * 4, context_->getStream() ) );
+            context_->synchronize();
+        }
+        /// device bytes the op holds
+        size_t stateBytes() const { return scratch_->sizeInBytes() + logprob_->sizeInBytes() + top_ids_->sizeInBytes() + top_logprobs_->sizeInBytes(); }
+    private:
+        TokenLogprobsOpConfig cfg_;
+        size_t scratch_bytes_{ 0 };
+        std::unique_ptr<Tensor<TensorDataType::UINT8, RocmDeviceMemoryResource>> scratch_;
+        std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> logprob_, top_logprobs_;
+        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> top_ids_;
+    };
+
     /// GPT-2 attention on packed QKV (new BF16 row; the reference's CUDA MHA is FP32-only, OPS/OperationTraits.Cuda.ixx:274-282) with the KV-cache
     /// interface of CudaMultiHeadAttentionOp (OPS/Attention/MHA/CudaMhaOp.ixx:107-380: IPositionalUnaryOp::prefill / decode + IKvCacheLifecycle)
     template<TensorDataType TPrecision> requires RocmPrecision<TPrecision>

@@ -464,6 +464,57 @@ HOST_API int mila_gemma_decode( void* h, int32_t token, int64_t position, int mo
     } );
 }
 
+/// token log-probabilities in every step that follows, the timing loops among them (GemmaTransformer::setStepLogprobs, the device-output form): top_n = 0 .. 20, < 0 = off
+HOST_API int mila_gemma_set_step_logprobs( void* h, int top_n )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m ) { if ( top_n < 0 ) m->setStepLogprobs( std::nullopt ); else m->setStepLogprobs( top_n ); }, static_cast<Runner*>( h )->model );
+    } );
+}
+/// the outputs of the last step with log-probabilities: logprob [rows], ids / logprobs [rows * top_n]
+static void read_logprobs( Runner* r, int rows, int top_n, float* out_logprob, int32_t* out_ids, float* out_logprobs )
+{
+    std::visit( [&]( auto& m ) { m->tokenLogprobs().read( rows, top_n, out_logprob, out_ids, out_logprobs ); }, r->model );
+}
+/// mila_gemma_decode, then the greedy sampler and the token's log-probabilities: *out_token = the greedy token of the step's logits, *out_logprob its log-probability,
+/// out_ids / out_logprobs [top_n] the alternatives.  Modes 0 / 1 sample and report eagerly behind the step; mode 2 replays a graph captured with the greedy sampler
+/// and the two log-probability nodes as its tail.  The setting is off again when the call returns (a later graph-mode step re-captures).
+HOST_API int mila_gemma_decode_logprobs( void* h, int32_t token, int64_t position, int mode, int top_n, float* host_logits, int32_t* out_token, float* out_logprob,
+                                         int32_t* out_ids, float* out_logprobs )
+{
+    auto* r = static_cast<Runner*>( h );
+    return guarded( [&]
+    {
+        upload_tokens( r, &token, 1 );
+        std::visit( [&]( auto& m )
+        {
+            if ( top_n < 0 ) throw std::invalid_argument( "decode_logprobs: top_n must be 0 .. 20" );
+            m->setStepLogprobs( top_n );
+            const bool was = m->sampleInGraph();
+            try
+            {
+                if ( mode == 0 ) { m->decode( *r->tokens, position ); m->sampleGreedy( *r->tokens ); m->enqueueStepLogprobs( r->tokens->data() ); }
+                else if ( mode == 1 ) { m->decodeFused( *r->tokens, position ); m->sampleGreedy( *r->tokens ); m->enqueueStepLogprobs( r->tokens->data() ); }
+                else
+                {
+                    m->setSampleInGraph( true );
+                    m->ensureGraph( *r->tokens, position );
+                    m->setDevicePosition( position );
+                    m->replayGraph();
+                }
+                m->context()->synchronize();
+            }
+            catch ( ... ) { m->setSampleInGraph( was ); m->setStepLogprobs( std::nullopt ); throw; }
+            m->setSampleInGraph( was );
+            m->setStepLogprobs( std::nullopt );
+            if ( out_token ) Compute::rocmCheck( mila_cdna4_memcpy_d2h( out_token, r->tokens->data(), 4, m->context()->getStream() ) );
+            m->tokenLogprobs().read( 1, top_n, out_logprob, out_ids, out_logprobs );
+        }, r->model );
+        download_logits( r, host_logits );
+    } );
+}
+
 /// Timed decode: `warmup` untimed steps then `steps` timed ones from `start_position`, token ids
 /// cycling through a fixed pattern (the sampler is outside the measured path).
 
@@ -534,6 +585,21 @@ HOST_API int mila_gemma_decode_rows_sampled( void* h, int B, int64_t max_positio
 {
     if ( !draws ) { g_err = "invalid_argument: decode_rows_sampled: null draws"; return MILA_E_INVALID_ARGUMENT; }
     return decode_rows_impl( h, B, max_position, mode, 0, temperature, top_k, top_p, draws, host_logits, host_tokens, host_positions );
+}
+/// mila_gemma_decode_rows (draws == NULL) or mila_gemma_decode_rows_sampled (draws != NULL) with token log-probabilities in the step: out_logprob [B] and
+/// out_ids / out_logprobs [B, top_n] of the tokens the tail chose.  An inactive row's entries are whatever an earlier step left there.  The setting is off again on return.
+HOST_API int mila_gemma_decode_rows_logprobs( void* h, int B, int64_t max_position, int mode, int greedy, float temperature, int top_k, float top_p, const float* draws, int top_n,
+                                              float* host_logits, int32_t* host_tokens, int32_t* host_positions, float* out_logprob, int32_t* out_ids, float* out_logprobs )
+{
+    if ( top_n < 0 ) { g_err = "invalid_argument: decode_rows_logprobs: top_n must be 0 .. 20"; return MILA_E_INVALID_ARGUMENT; }
+    int rc = mila_gemma_set_step_logprobs( h, top_n );
+    if ( rc ) return rc;
+    rc = decode_rows_impl( h, B, max_position, mode, draws ? 0 : greedy, temperature, top_k, top_p, draws, host_logits, host_tokens, host_positions );
+    if ( !rc ) rc = guarded( [&] { read_logprobs( static_cast<Runner*>( h ), B, top_n, out_logprob, out_ids, out_logprobs ); } );
+    const std::string err = g_err;
+    (void)mila_gemma_set_step_logprobs( h, -1 );
+    g_err = err;
+    return rc;
 }
 /// out[0] = captures of the rows graph so far, out[1] = kernel nodes of the captured rows step
 HOST_API int mila_gemma_rows_graph_info( void* h, int64_t* out )
@@ -648,6 +714,21 @@ HOST_API int mila_gemma_chain_decode_sampled( void* h, const int32_t* tokens, in
     if ( !draws ) { g_err = "invalid_argument: chain_decode_sampled: null draws"; return MILA_E_INVALID_ARGUMENT; }
     return chain_decode_impl( h, tokens, T, position, mode, temperature, top_k, top_p, draws, host_logits, out );
 }
+/// mila_gemma_chain_decode (draws == NULL) or mila_gemma_chain_decode_sampled with token log-probabilities in the step: out_logprob [T] and out_ids / out_logprobs
+/// [T, top_n]; rows 0 .. count - 1 (the accepted tokens, count = out[ 0 ]) are this step's, the others are whatever an earlier step left there.  Off again on return.
+HOST_API int mila_gemma_chain_decode_logprobs( void* h, const int32_t* tokens, int T, int64_t position, int mode, float temperature, int top_k, float top_p, const float* draws,
+                                               int top_n, float* host_logits, int32_t* out, float* out_logprob, int32_t* out_ids, float* out_logprobs )
+{
+    if ( top_n < 0 ) { g_err = "invalid_argument: chain_decode_logprobs: top_n must be 0 .. 20"; return MILA_E_INVALID_ARGUMENT; }
+    int rc = mila_gemma_set_step_logprobs( h, top_n );
+    if ( rc ) return rc;
+    rc = chain_decode_impl( h, tokens, T, position, mode, temperature, top_k, top_p, draws, host_logits, out );
+    if ( !rc ) rc = guarded( [&] { read_logprobs( static_cast<Runner*>( h ), T, top_n, out_logprob, out_ids, out_logprobs ); } );
+    const std::string err = g_err;
+    (void)mila_gemma_set_step_logprobs( h, -1 );
+    g_err = err;
+    return rc;
+}
 /// out[0] = captures of the chain graph so far, out[1] = kernel nodes of the captured chain step, out[2] = its rows
 HOST_API int mila_gemma_chain_graph_info( void* h, int64_t* out )
 {
@@ -715,6 +796,7 @@ HOST_API int mila_gemma_time_decode( void* h, int64_t start_position, int steps,
                 if ( mode == 0 ) { m->decode( *r->tokens, pos ); m->sampleGreedy( *r->tokens ); }
                 else if ( mode == 1 ) { m->decodeFused( *r->tokens, pos ); m->sampleGreedy( *r->tokens ); }
                 else { m->ensureGraph( *r->tokens, pos ); m->replayGraph(); }
+                if ( mode != 2 && m->stepLogprobs() ) m->enqueueStepLogprobs( r->tokens->data() );      // (the captured step runs them itself)
             };
             int64_t pos = start_position;
             for ( int i = 0; i < warmup; ++i ) step( pos++ );
@@ -1351,15 +1433,69 @@ HOST_API void mila_gemma_model_destroy( void* h ) { delete static_cast<RocmGemma
 /// generate(): max_new < 0 = no budget (run to a stop token or the context bound); n_stop == 0 = the model's default stop set; the callback's tokens
 /// are appended to out_tokens (at most cap).  *out_status = GenerateStatus; *out_reused = prompt tokens served from the KV caches; cancel_after >= 0: the
 /// client's stop request is raised from inside on_token once that many tokens were delivered (the std::stop_token of the reference's generate)
+/// where the *_logprobs entries collect GenerateParams::on_logprobs: entry i (of one row) goes to logprob[ i ], ids / logprobs[ i * top_n .. ), at most cap entries;
+/// top_n < 0 = the request carries no log-probabilities
+struct LogprobSink
+{
+    int top_n{ -1 };
+    float* logprob{ nullptr };
+    int32_t* ids{ nullptr };
+    float* logprobs{ nullptr };
+    int64_t cap{ 0 };
+    /// sets the request's fields; `count` = entries of this row so far, advanced by the callback
+    void attach( GenerateParams& gp, std::function<int64_t&( int )> count )
+    {
+        if ( top_n < 0 ) return;
+        gp.logprobs = top_n;
+        gp.on_logprobs = [this, count]( const TokenLogprobs& t )
+        {
+            int64_t& c = count( t.row );
+            const int64_t at = static_cast<int64_t>( t.row ) * cap + c;
+            if ( c < cap )
+            {
+                if ( logprob ) logprob[ at ] = t.logprob;
+                for ( size_t i = 0; i < t.top_ids.size(); ++i )
+                {
+                    if ( ids ) ids[ at * top_n + static_cast<int64_t>( i ) ] = t.top_ids[ i ];
+                    if ( logprobs ) logprobs[ at * top_n + static_cast<int64_t>( i ) ] = t.top_logprobs[ i ];
+                }
+            }
+            ++c;
+        };
+    }
+};
+
+static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                                float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
+                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count );
 HOST_API int mila_gemma_model_generate( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                         float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
                                         int64_t cancel_after )
+{
+    return model_generate_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_count, out_status, out_reused, cancel_after,
+                                LogprobSink{}, nullptr );
+}
+/// mila_gemma_model_generate with GenerateParams::logprobs = top_n: entry i of on_logprobs goes to out_logprob[ i ] and out_ids / out_logprobs[ i * top_n .. ) (at most
+/// cap entries), their number to *out_logprob_count
+HOST_API int mila_gemma_model_generate_logprobs( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                                                 float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
+                                                 int64_t cancel_after, int top_n, float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_count )
+{
+    return model_generate_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_count, out_status, out_reused, cancel_after,
+                                LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count );
+}
+static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                                float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
+                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count )
 {
     return guarded( [&]
     {
         auto* m = static_cast<RocmGemmaModel*>( h );
         if ( !m || !prompt || !out_count || !out_status ) throw std::invalid_argument( "gemma_model_generate: null argument" );
         GenerateParams gp;
+        int64_t n_lp = 0;
+        sink.attach( gp, [&]( int ) -> int64_t& { return n_lp; } );
+        struct Report { int64_t* out; int64_t& n; ~Report() { if ( out ) *out = n; } } report{ out_logprob_count, n_lp };
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
@@ -1379,13 +1515,16 @@ HOST_API int mila_gemma_model_generate( void* h, const int32_t* prompt, int64_t 
 /// out_stats (may be NULL): GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
 static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens, int64_t cap, int64_t* out_count,
-                               int32_t* out_status, int64_t* out_stats )
+                               int32_t* out_status, int64_t* out_stats, LogprobSink sink = LogprobSink{}, int64_t* out_logprob_count = nullptr )
 {
     return guarded( [&]
     {
         auto* m = static_cast<RocmGemmaModel*>( h );
         if ( !m || !prompt || !out_count || !out_status ) throw std::invalid_argument( "gemma_model_generate_spec: null argument" );
         GenerateParams gp;
+        int64_t n_lp = 0;
+        sink.attach( gp, [&]( int ) -> int64_t& { return n_lp; } );
+        struct Report { int64_t* out; int64_t& n; ~Report() { if ( out ) *out = n; } } report{ out_logprob_count, n_lp };
         gp.speculative_sampling = speculative_sampling != 0;
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
@@ -1427,6 +1566,16 @@ HOST_API int mila_gemma_model_generate_spec_sampling( void* h, const int32_t* pr
                                out_status, out_stats );
 }
 
+/// mila_gemma_model_generate_spec_sampling with GenerateParams::logprobs = top_n; the outputs as in mila_gemma_model_generate_logprobs
+HOST_API int mila_gemma_model_generate_spec_logprobs( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                                      int top_k, float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens,
+                                                      int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_stats, int top_n, float* out_logprob, int32_t* out_ids,
+                                                      float* out_logprobs, int64_t* out_logprob_count )
+{
+    return generate_spec_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, hint, n_hint, speculative_sampling, out_tokens, cap, out_count,
+                               out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count );
+}
+
 /// GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
 HOST_API int mila_gemma_model_speculation_stats( void* h, int64_t* out )
 {
@@ -1441,14 +1590,35 @@ HOST_API int mila_gemma_model_speculation_stats( void* h, int64_t* out )
 
 /// GemmaModel::generateBatch: n_prompts prompts, prompt b = prompts[ offsets[b] .. offsets[b + 1] ); parameters as mila_gemma_model_generate (shared by the rows); seed: row b's
 /// generator is seeded seed + b.  Row b's tokens go to out_tokens[ b * cap .. ] (at most cap), their number to out_counts[ b ], its GenerateStatus to out_status[ b ]
+static int model_generate_rows_impl( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                     int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status, LogprobSink sink,
+                                     int64_t* out_logprob_counts );
 HOST_API int mila_gemma_model_generate_rows( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
                                              int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status )
+{
+    return model_generate_rows_impl( h, prompts, offsets, n_prompts, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_counts, out_status, LogprobSink{},
+                                     nullptr );
+}
+/// mila_gemma_model_generate_rows with GenerateParams::logprobs = top_n: row b's entry i goes to out_logprob[ b * cap + i ] and out_ids / out_logprobs[ (b * cap + i) * top_n .. ),
+/// their number to out_logprob_counts[ b ]
+HOST_API int mila_gemma_model_generate_rows_logprobs( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop,
+                                                      float temperature, int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status,
+                                                      int top_n, float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts )
+{
+    return model_generate_rows_impl( h, prompts, offsets, n_prompts, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_counts, out_status,
+                                     LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_counts );
+}
+static int model_generate_rows_impl( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                     int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status, LogprobSink sink,
+                                     int64_t* out_logprob_counts )
 {
     return guarded( [&]
     {
         auto* m = static_cast<RocmGemmaModel*>( h );
         if ( !m || !prompts || !offsets || !out_counts || !out_status || n_prompts < 0 ) throw std::invalid_argument( "gemma_model_generate_rows: null argument" );
         GenerateParams gp;
+        std::vector<int64_t> lp_counts( static_cast<size_t>( std::max( n_prompts, 1 ) ), 0 );
+        sink.attach( gp, [&]( int b ) -> int64_t& { return lp_counts.at( static_cast<size_t>( b ) ); } );
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
@@ -1457,6 +1627,7 @@ HOST_API int mila_gemma_model_generate_rows( void* h, const int32_t* prompts, co
         std::vector<int64_t> counts( static_cast<size_t>( n_prompts ), 0 );
         const auto st = m->generateBatch( ps, [&]( int b, int32_t t ) { int64_t& c = counts[ static_cast<size_t>( b ) ]; if ( out_tokens && c < cap ) out_tokens[ b * cap + c ] = t; ++c; }, gp, seed );
         for ( int b = 0; b < n_prompts; ++b ) { out_counts[ b ] = counts[ static_cast<size_t>( b ) ]; out_status[ b ] = static_cast<int32_t>( st[ static_cast<size_t>( b ) ] ); }
+        if ( out_logprob_counts ) for ( int b = 0; b < n_prompts; ++b ) out_logprob_counts[ b ] = lp_counts[ static_cast<size_t>( b ) ];
     } );
 }
 

@@ -3,7 +3,8 @@
 tool.  Prints one JSON line per (policy, B) and a closing line that says, per policy, whether the B = 2 aggregate exceeds B = 1.
 --stochastic: the step time of a stochastic GemmaModel.generate_batch at B = 2 .. max-batch instead -- (wall time of a batch of --steps tokens per row minus that of one
 token per row) / (steps - 1), per repeat and as a median, at --temperature / --top-k / --top-p (default: Gemma's 1.0 / 64 / 0.95); it uses nothing but generate_batch,
-so the same file measures a commit from before the sampler moved into the rows graph.  Not part of the product path."""
+so the same file measures a commit from before the sampler moved into the rows graph.
+--logprobs N: the same measurements with token log-probabilities (top N) in every step.  Not part of the product path."""
 import argparse
 import json
 import os
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-k", type=int, default=64)
     ap.add_argument("--top-p", type=float, default=0.95)
+    ap.add_argument("--logprobs", type=int, default=None, help="token log-probabilities (top N, 0 .. 20) in every step")
     a = ap.parse_args()
     if a.stochastic:
         return stochastic(a)
@@ -37,6 +39,7 @@ def main():
         rng = np.random.default_rng(0)
         for b in range(a.max_batch):
             g.prefill_row(b, rng.integers(0, g.vocab, a.context))
+        g.set_step_logprobs(a.logprobs)
         agg = {}
         for B in range(1, a.max_batch + 1):
             ms = []
@@ -46,7 +49,7 @@ def main():
             med = statistics.median(ms)
             agg[B] = B * 1000.0 / med
             print(json.dumps({"policy": policy, "B": B, "ms_per_step": [round(v, 4) for v in ms], "median_ms_per_step": round(med, 4), "aggregate_tok_s": round(agg[B], 1),
-                              "vs_B1": round(agg[B] / agg[1], 3), "context": a.context, "steps": a.steps}), flush=True)
+                              "vs_B1": round(agg[B] / agg[1], 3), "context": a.context, "steps": a.steps, "logprobs": a.logprobs}), flush=True)
         verdict[policy] = {"B2_exceeds_B1": agg.get(2, 0) > agg[1], "best_B": max(agg, key=agg.get)}
         g.close()
     print(json.dumps({"rows_worth_dispatching": verdict}), flush=True)
@@ -62,8 +65,8 @@ def stochastic(a):
         for B in range(2, a.max_batch + 1):
             def run(n, seed):
                 t0 = time.perf_counter()
-                got = m.generate_batch(prompts[:B], max_new_tokens=n, seed=seed, **req)
-                return time.perf_counter() - t0, min(len(t) for t, _ in got)
+                got = m.generate_batch(prompts[:B], max_new_tokens=n, seed=seed, logprobs=a.logprobs, **req)
+                return time.perf_counter() - t0, min(len(g[0]) for g in got)
             run(a.warmup + 1, 1)
             ms = []
             for i in range(a.repeats):
@@ -74,7 +77,7 @@ def stochastic(a):
             med = statistics.median(ms)
             print(json.dumps({"policy": policy, "mode": "stochastic generate_batch", "B": B, "ms_per_step": [round(v, 4) for v in ms], "median_ms_per_step": round(med, 4),
                               "spread_us": round(1000 * (max(ms) - min(ms)), 1), "aggregate_tok_s": round(B * 1000.0 / med, 1), "context": a.context, "steps": a.steps,
-                              "sampling": [a.temperature, a.top_k, a.top_p]}), flush=True)
+                              "sampling": [a.temperature, a.top_k, a.top_p], "logprobs": a.logprobs}), flush=True)
         m.close()
 
 

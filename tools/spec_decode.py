@@ -4,6 +4,7 @@ step and tok/s with the default drafter (prompt lookup) on a repetitive prompt, 
 --stochastic: the same for speculative SAMPLING (GenerateParams::speculative_sampling) at --temperature / --top-k / --top-p (default: Gemma's 1.0 / 64 / 0.95) -- the
 chain step with the sampling tail against the greedy chain step and against the one-row stochastic graph step, and generate() against the plain stochastic generate()
 of the same model.  --baseline-only stops after the one-row figures (they need nothing this mode added).
+--logprobs N: every step and every request with token log-probabilities (top N, 0 .. 20) on.
 Not part of the product path."""
 import argparse
 import json
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-k", type=int, default=64)
     ap.add_argument("--top-p", type=float, default=0.95)
+    ap.add_argument("--logprobs", type=int, default=None, help="token log-probabilities (top N, 0 .. 20) in every step and request")
     a = ap.parse_args()
     if a.stochastic:
         return stochastic(a)
@@ -44,19 +46,21 @@ def main():
     K = a.draft_tokens
     max_seq = a.context + (a.steps + a.warmup) * (K + 1) + 8
     for policy in a.policies.split(","):
-        out = {"policy": policy, "context": a.context, "steps": a.steps, "draft_tokens": K}
+        out = {"policy": policy, "context": a.context, "steps": a.steps, "draft_tokens": K, "logprobs": a.logprobs}
         rng = np.random.default_rng(0)
         prompt = rng.integers(0, 1000, a.context)
         # the yardstick: one row, and T independent rows, on a max_batch model
         g = host.Gemma(policy, cfg, max_seq=max_seq, max_prefill=a.context, seed=1234, max_batch=K + 1)
         for b in range(K + 1):
             g.prefill_row(b, prompt)
+        g.set_step_logprobs(a.logprobs)
         out["one_row_ms"] = round(_median(lambda: g.time_decode(a.context, a.steps, a.warmup, "graph"), a.repeats), 4)
         out["rows_ms"] = {T: round(_median(lambda: g.time_decode_rows(T, a.context, a.steps, a.warmup), a.repeats), 4) for T in range(2, K + 2)}
         g.close()
         # the chain step on a draft_tokens model (the drafts are whatever the token words hold: the step's cost does not depend on what it accepts)
         g = host.Gemma(policy, cfg, max_seq=max_seq, max_prefill=a.context, seed=1234, draft_tokens=K)
         g.prefill(prompt)
+        g.set_step_logprobs(a.logprobs)
         out["chain_ms"] = {T: round(_median(lambda: g.time_decode_chain(T, a.context, a.steps, a.warmup), a.repeats), 4) for T in range(2, K + 2)}
         out["chain_graph_nodes"] = g.chain_graph_info()["nodes"]
         g.close()
@@ -71,7 +75,7 @@ def main():
 
         def timed(n, hint=None):
             t0 = time.perf_counter()
-            toks, status, _ = m.generate(rep, max_new_tokens=n, stop_tokens=[cfg["vocab_size"] - 1 if cfg else 262143], draft_hint=hint)
+            toks = m.generate(rep, max_new_tokens=n, stop_tokens=[cfg["vocab_size"] - 1 if cfg else 262143], draft_hint=hint, logprobs=a.logprobs)[0]
             return toks, time.perf_counter() - t0, m.speculation_stats()
 
         timed(2)                                   # the prompt's prefill; every later request reuses it but for the last position
@@ -107,7 +111,7 @@ def stochastic(a):
 
         def plain(n, seed):
             t0 = time.perf_counter()
-            toks = m.generate(rep, max_new_tokens=n, stop_tokens=stop, seed=seed, **req)[0]
+            toks = m.generate(rep, max_new_tokens=n, stop_tokens=stop, seed=seed, logprobs=a.logprobs, **req)[0]
             return toks, time.perf_counter() - t0
 
         plain(2, 1)
@@ -126,6 +130,7 @@ def stochastic(a):
         # the chain step: greedy tail, then the sampling tail (the drafts are whatever the token words hold: the step's cost does not depend on what it accepts)
         g = host.Gemma(policy, cfg, max_seq=max_seq, max_prefill=a.context, seed=1234, draft_tokens=K)
         g.prefill(prompt)
+        g.set_step_logprobs(a.logprobs)
         out["one_row_greedy_ms"] = round(_median(lambda: g.time_decode(a.context, a.steps, a.warmup, "graph"), a.repeats), 4)
         out["chain_greedy_ms"] = {T: round(_median(lambda: g.time_decode_chain(T, a.context, a.steps, a.warmup), a.repeats), 4) for T in range(2, K + 2)}
         greedy_nodes = g.chain_graph_info()["nodes"]
@@ -141,7 +146,7 @@ def stochastic(a):
 
         def timed(n, hint=None, seed=10):
             t0 = time.perf_counter()
-            toks = m.generate(rep, max_new_tokens=n, stop_tokens=stop, seed=seed, draft_hint=hint, speculative_sampling=True, **req)[0]
+            toks = m.generate(rep, max_new_tokens=n, stop_tokens=stop, seed=seed, draft_hint=hint, speculative_sampling=True, logprobs=a.logprobs, **req)[0]
             return toks, time.perf_counter() - t0, m.speculation_stats()
 
         timed(2)
