@@ -747,6 +747,76 @@ MILA_API int mila_cdna4_token_logprobs_publish_fp32(const float* logits, const i
                                                     const unsigned long long* seq_dev, uint32_t* ring, int ring_size, void* scratch, size_t scratch_bytes,
                                                     mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sampling filters (ABI 4, additive; csrc/sampling.hip): repetition, presence and frequency penalties and min-p, as filters over the samplers above.  The reference's
+ * sampling specification (Specifications/TokenSampling.md 3.3, 4.2) names "top-k, top-p, min-p, and repetition penalty" as composable filters over one sampler and
+ * pencils them into GenerateParams; the reference has NO kernel for them yet, so these entries anticipate that surface and replace no launcher.
+ *
+ * THE TABLE.  The state of one sequence is a table of `vocab` 32-bit words on the device (token_table_bytes(vocab) bytes): bit 31 = the token occurs in the prompt,
+ * bits 0 .. 30 = c, the number of times the token has been generated in this request.  token_table_clear zeroes row `row` of a table (table + row * table_stride
+ * words); token_table_mark_prompt sets bit 31 of the words of n token ids held in DEVICE memory -- into a cleared table, before the first sample (it stores the flag
+ * with c = 0); repeats are fine, ids outside [0, vocab) are skipped.
+ *
+ * THE ADJUSTED LOGIT of a logit l whose table word is w, all in fp32, every operation rounded on its own (no fused multiply-add), so that a host can restate it bit
+ * for bit:
+ *     x0 = softcap > 0 ? softcap * tanhf(l / softcap) : l                    (as in sample_radix_*)
+ *     x1 = w != 0 ? (x0 > 0 ? x0 * inv_rep : x0 * rep) : x0                  inv_rep = 1.0f / rep, divided once on the host
+ *     x2 = x1 - (freq * (float)c)
+ *     x3 = c > 0 ? x2 - pres : x2
+ *     x  = x3 / temperature                                                  (as in sample_radix_*)
+ * The repetition penalty covers prompt and generated tokens (the HF / vLLM convention); presence and frequency cover generated tokens only (the OpenAI / vLLM
+ * convention).  Penalties come after the softcap (HF applies them to Gemma's already capped logits) and before the temperature.
+ * MIN-P.  After the nucleus cut (top-k, then top-p, then min-p) a surviving entry with e = expf(x - max) < min_p is dropped: the tokens whose probability is at least
+ * min_p times the top token's stay.
+ * GREEDY.  sample_argmax_filtered_* take argmax(x3), ties to the lower id (the softcap first: the penalty touches only some tokens).  min_p does not change a greedy
+ * request.
+ * THE UPDATE.  Every entry that is given a table adds 1 to table[s] after choosing token s: one lane, a plain load and a plain store, before the token is stored or
+ * published; the rows advance forms touch the active rows only.  The next call reads the table across a kernel boundary.
+ * The samplers write their scaled copy into scratch and never touch `logits`: log-probabilities (token_logprobs_*) stay those of the capped, UNPENALIZED logits.
+ *
+ * filters: read on the host at enqueue; NULL = the neutral values {min_p 0, repetition 1, presence 0, frequency 0}.  table: NULL = no penalties and no update (min_p
+ * still holds in the stochastic entries; the greedy entries are then sample_argmax_* on the logits as they are).  table_stride: words between the tables of two rows.
+ * A filtered call launches exactly what sample_radix_plan_describe reports for the unfiltered call (the table rides in the scale launch, min-p in the mask launch, the
+ * update in the tail); with a NULL table and min_p = 0 it launches the unfiltered kernels themselves.  The greedy entries are the two launches of sample_argmax_*.
+ *   sample_filters_describe: "launches:k_passes:p_passes:scratch_need:scale_filtered:mask_filtered" -- sample_radix_plan_describe's text and whether the scale / the mask
+ *     launch is the filtered instantiation (with_table: a table would be given).  0 for arguments the entries refuse.  No device work.
+ *   scratch: as for the entry each one mirrors (sample_radix_scratch_bytes, sample_radix_rows_scratch_bytes, sample_scratch_bytes; the rows greedy entry rows x
+ *     sample_scratch_bytes()).
+ * Refused before any device work, beside what the mirrored entry refuses: repetition_penalty <= 0, a non-finite filter value, min_p outside [0, 1), table_stride < vocab
+ * with more than one row (MILA_E_INVALID_ARGUMENT). */
+typedef struct mila_sample_filters
+{
+    float min_p;                  /* [0, 1); 0 = off */
+    float repetition_penalty;     /* > 0; 1 = off */
+    float presence_penalty;       /* 0 = off */
+    float frequency_penalty;      /* 0 = off */
+} mila_sample_filters;
+MILA_API size_t mila_cdna4_token_table_bytes(int vocab);
+MILA_API int mila_cdna4_token_table_clear(uint32_t* table, size_t table_stride, int row, int vocab, mila_stream_t stream);
+MILA_API int mila_cdna4_token_table_mark_prompt(uint32_t* table, size_t table_stride, int row, int vocab, const int32_t* tokens_dev, int n, mila_stream_t stream);
+MILA_API size_t mila_cdna4_sample_filters_describe(int vocab, int top_k, float top_p, const mila_sample_filters* filters, int with_table, char* buf, size_t cap);
+MILA_API int mila_cdna4_sample_radix_filtered_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                                   const mila_sample_filters* filters, uint32_t* table, void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
+                                                           const float* draws, int draws_size, const mila_sample_filters* filters, uint32_t* table, void* scratch,
+                                                           size_t scratch_bytes, int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring,
+                                                           int ring_size, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_filtered_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                        float temperature, int top_k, float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table,
+                                                        size_t table_stride, void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_filtered_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                                float temperature, int top_k, float top_p, const float* draws, const mila_sample_filters* filters,
+                                                                uint32_t* table, size_t table_stride, void* scratch, size_t scratch_bytes, int32_t* positions_dev,
+                                                                const int32_t* active_dev, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_filtered_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
+                                                    void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters,
+                                                            uint32_t* table, void* scratch, size_t scratch_bytes, int32_t* position_dev, unsigned long long* seq_dev,
+                                                            unsigned long long* ring, int ring_size, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_filtered_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                                 const mila_sample_filters* filters, uint32_t* table, size_t table_stride, void* scratch,
+                                                                 size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,20 @@ def load():
     main.mila_cdna4_sample_radix_rows_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, z, p]                     # logits logits_stride token_out | rows vocab softcap temperature top_k top_p | draws | scratch bytes
     main.mila_cdna4_sample_radix_rows_advance_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, z, p, p, p]       # ... | scratch bytes | positions_dev active_dev
     main.mila_cdna4_sample_radix_chain_accept_fp32.argtypes = [p, p, p, z, i, i, f, f, i, f, p, p, z, p, p]       # tok result logits logits_stride | T vocab softcap temperature top_k top_p | draws | scratch bytes | position_dev
+    # sampling filters (csrc/sampling.hip: the filtered instantiations and the token table)
+    main.mila_cdna4_token_table_bytes.argtypes = [i]
+    main.mila_cdna4_token_table_bytes.restype = z
+    main.mila_cdna4_token_table_clear.argtypes = [p, z, i, i, p]                                                  # table table_stride row vocab
+    main.mila_cdna4_token_table_mark_prompt.argtypes = [p, z, i, i, p, i, p]                                      # table table_stride row vocab | tokens_dev n
+    main.mila_cdna4_sample_filters_describe.argtypes = [i, i, f, p, i, p, z]                                      # vocab top_k top_p | filters with_table | buf cap
+    main.mila_cdna4_sample_filters_describe.restype = z
+    main.mila_cdna4_sample_radix_filtered_fp32.argtypes = [p, p, i, f, f, i, f, f, p, p, p, z, p]                 # ... top_p r | filters table | scratch bytes
+    main.mila_cdna4_sample_radix_filtered_advance_fp32.argtypes = [p, p, i, f, f, i, f, p, i, p, p, p, z, p, p, p, i, p]     # ... draws draws_size | filters table | scratch bytes | position_dev seq_dev ring ring_size
+    main.mila_cdna4_sample_radix_filtered_rows_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, p, z, p, z, p]   # ... draws | filters table table_stride | scratch bytes
+    main.mila_cdna4_sample_radix_filtered_rows_advance_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, p, z, p, z, p, p, p]        # ... | positions_dev active_dev
+    main.mila_cdna4_sample_argmax_filtered_fp32.argtypes = [p, p, i, f, p, p, p, z, p]                            # logits token_out | vocab softcap | filters table | scratch bytes
+    main.mila_cdna4_sample_argmax_filtered_advance_fp32.argtypes = [p, p, i, f, p, p, p, z, p, p, p, i, p]        # ... | position_dev seq_dev ring ring_size
+    main.mila_cdna4_sample_argmax_filtered_rows_advance_fp32.argtypes = [p, z, p, i, i, f, p, p, z, p, z, p, p, p]       # logits logits_stride token_out | rows vocab softcap | filters table table_stride | scratch bytes | positions_dev active_dev
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -306,6 +320,104 @@ def sample_radix_chain_accept(tok, result, logits, softcap, temperature, top_k, 
          scratch, C.c_size_t(scratch.numel() * scratch.element_size()), position_dev)
 
 
+class sample_filters(C.Structure):
+    """mila_sample_filters: read on the host at enqueue"""
+    _fields_ = [("min_p", C.c_float), ("repetition_penalty", C.c_float), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float)]
+
+
+def _filters_arg(filters):
+    """None (neutral), a sample_filters, or (min_p, repetition_penalty, presence_penalty, frequency_penalty) -> what ctypes passes for `const mila_sample_filters*`"""
+    if filters is None:
+        return None
+    if not isinstance(filters, sample_filters):
+        filters = sample_filters(*[float(v) for v in filters])
+    return C.byref(filters)
+
+
+def _nbytes(t):
+    return C.c_size_t(t.numel() * t.element_size())
+
+
+SAMPLE_FILTERS_FIELDS = RADIX_PLAN_FIELDS + ("scale_filtered", "mask_filtered")
+
+
+def sample_filters_plan(vocab, top_k, top_p, filters=None, with_table=False):
+    """what a sample_radix_filtered_* call launches (csrc/sampling.hip: plan_radix) as a dict of SAMPLE_FILTERS_FIELDS: sample_radix_plan's fields and whether the scale
+    / the mask launch is the filtered instantiation; None for filters the entries refuse.  Needs no GPU."""
+    buf = C.create_string_buffer(128)
+    need = load().mila_cdna4_sample_filters_describe(int(vocab), int(top_k), float(top_p), _filters_arg(filters), int(bool(with_table)), buf, C.c_size_t(len(buf)))
+    if not need:
+        return None
+    assert need <= len(buf), "plan text of %d bytes" % need
+    return dict(zip(SAMPLE_FILTERS_FIELDS, [int(v) for v in buf.value.decode().split(":")]))
+
+
+def token_table_bytes(vocab):
+    return int(load().mila_cdna4_token_table_bytes(int(vocab)))
+
+
+def _table_head(table, row):
+    """(table_stride, vocab) of a [rows, vocab] or [vocab] int32 table tensor"""
+    assert table.dim() in (1, 2) and table.element_size() == 4
+    assert 0 <= row < (table.shape[0] if table.dim() == 2 else 1)
+    return C.c_size_t(int(table.shape[-1])), int(table.shape[-1])
+
+
+def token_table_clear(table, row=0):
+    stride, V = _table_head(table, row)
+    call("token_table_clear", table, stride, int(row), V)
+
+
+def token_table_mark_prompt(table, tokens_dev, row=0, n=None):
+    """bit 31 of row `row`'s words of the ids in tokens_dev (int32, on the device): into a cleared table"""
+    stride, V = _table_head(table, row)
+    call("token_table_mark_prompt", table, stride, int(row), V, tokens_dev, int(tokens_dev.numel() if n is None else n))
+
+
+def sample_radix_filtered(logits, token_out, softcap, temperature, top_k, top_p, r, filters, table, scratch):
+    """sample_radix with the filters (None / sample_filters / 4-tuple) and the token table (int32 [vocab] or None): the table word of the sample goes up by one"""
+    call("sample_radix_filtered_fp32", logits, token_out, int(logits.numel()), float(softcap), float(temperature), int(top_k), float(top_p), float(r),
+         _filters_arg(filters), table, scratch, _nbytes(scratch))
+
+
+def sample_radix_filtered_advance(logits, token_out, softcap, temperature, top_k, top_p, draws, filters, table, scratch, position_dev, seq_dev, ring=None):
+    call("sample_radix_filtered_advance_fp32", logits, token_out, int(logits.numel()), float(softcap), float(temperature), int(top_k), float(top_p), draws, int(draws.numel()),
+         _filters_arg(filters), table, scratch, _nbytes(scratch), position_dev, seq_dev, ring, 0 if ring is None else int(ring.numel()))
+
+
+def _tables_stride(table):
+    return C.c_size_t(0 if table is None else int(table.shape[-1]))
+
+
+def sample_radix_filtered_rows(logits, token_out, softcap, temperature, top_k, top_p, draws, filters, table, scratch, vocab=None):
+    """sample_radix_rows with the filters and the tables [rows, vocab] (row b's table is table[b])"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_filtered_rows_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), float(temperature), int(top_k), float(top_p), draws,
+         _filters_arg(filters), table, _tables_stride(table), scratch, _nbytes(scratch))
+
+
+def sample_radix_filtered_rows_advance(logits, token_out, softcap, temperature, top_k, top_p, draws, filters, table, scratch, positions_dev, active_dev, vocab=None):
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_filtered_rows_advance_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), float(temperature), int(top_k), float(top_p), draws,
+         _filters_arg(filters), table, _tables_stride(table), scratch, _nbytes(scratch), positions_dev, active_dev)
+
+
+def sample_argmax_filtered(logits, token_out, softcap, filters, table, scratch):
+    """the penalized greedy sampler: argmax of the adjusted logits x3, ties to the lower id; the table word of the token goes up by one"""
+    call("sample_argmax_filtered_fp32", logits, token_out, int(logits.numel()), float(softcap), _filters_arg(filters), table, scratch, _nbytes(scratch))
+
+
+def sample_argmax_filtered_advance(logits, token_out, softcap, filters, table, scratch, position_dev, seq_dev=None, ring=None):
+    call("sample_argmax_filtered_advance_fp32", logits, token_out, int(logits.numel()), float(softcap), _filters_arg(filters), table, scratch, _nbytes(scratch),
+         position_dev, seq_dev, ring, 0 if ring is None else int(ring.numel()))
+
+
+def sample_argmax_filtered_rows_advance(logits, token_out, softcap, filters, table, scratch, positions_dev, active_dev, vocab=None):
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_argmax_filtered_rows_advance_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), _filters_arg(filters), table, _tables_stride(table),
+         scratch, _nbytes(scratch), positions_dev, active_dev)
+
+
 TOKEN_LOGPROBS_MAX_TOP = 20
 
 
@@ -395,6 +507,9 @@ EXPORTED = [
     "fused_attn_decode_chain_bf16", "attn_decode_chain_scratch_bytes", "fused_qkv_post_rows_devpos", "sample_argmax_chain_accept",
     "sample_radix_rows_scratch_bytes", "sample_radix_rows_fp32", "sample_radix_rows_advance_fp32", "sample_radix_chain_accept_fp32",
     "token_logprobs_record_words", "token_logprobs_scratch_bytes", "token_logprobs_rows_fp32", "token_logprobs_publish_fp32",
+    "token_table_bytes", "token_table_clear", "token_table_mark_prompt", "sample_filters_describe",
+    "sample_radix_filtered_fp32", "sample_radix_filtered_advance_fp32", "sample_radix_filtered_rows_fp32", "sample_radix_filtered_rows_advance_fp32",
+    "sample_argmax_filtered_fp32", "sample_argmax_filtered_advance_fp32", "sample_argmax_filtered_rows_advance_fp32",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

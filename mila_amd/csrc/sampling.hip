@@ -2,6 +2,8 @@
 // (OPS/Sampling/Kernels/Sampling.cu:23-75: strict '>' while scanning in index order, lower index wins the reduction).
 // Integer output => bit-exact.  Two stages so that 1 MB of logits is read by the whole chip, not by one CU.
 #include <cfloat>
+#include <cmath>
+#include <type_traits>
 
 #include "common.h"
 
@@ -29,6 +31,30 @@ __device__ __forceinline__ void wave_argmax(float& bv, int& bi)
     }
 }
 
+// ---- sampling filters (TokenSampling.md 3.3: repetition penalty, presence / frequency penalty, min-p).  The per-sequence state is a table of `vocab` 32-bit words:
+// bit 31 = the token occurs in the prompt, bits 0..30 = c, the times it has been generated.  The sampler that is given a table reads table[i] beside logits[i] and its
+// tail adds 1 to the word of the token it chose.
+struct SampleFilter
+{
+    uint32_t* table;              // row 0's table (nullptr: no penalties, no update)
+    size_t table_stride;          // words between the tables of two rows
+    float rep, inv_rep;           // repetition penalty and 1.0f / rep (divided once, on the host)
+    float pres, freq, min_p;
+};
+
+// the adjusted logit x3 of a soft-capped logit x0 whose table word is w: every operation rounded on its own (no contraction into a fused multiply-add), so that a host
+// can restate it bit for bit
+__device__ __forceinline__ float penalized_logit(float x0, uint32_t w, const SampleFilter& f)
+{
+    const float x1 = w != 0u ? (x0 > 0.0f ? __fmul_rn(x0, f.inv_rep) : __fmul_rn(x0, f.rep)) : x0;
+    const uint32_t c = w & 0x7fffffffu;
+    const float x2 = __fsub_rn(x1, __fmul_rn(f.freq, (float)c));
+    return c > 0u ? __fsub_rn(x2, f.pres) : x2;
+}
+
+// one lane, after choosing token s and before publishing it: a plain load and a plain store (the next step's first launch reads the table across a kernel boundary)
+__device__ __forceinline__ void table_count(uint32_t* table, int s) { table[s] = table[s] + 1u; }
+
 template <typename T>
 __global__ __launch_bounds__(256) void argmax_partial_kernel(const T* __restrict__ logits, float* __restrict__ pv, int* __restrict__ pi,
                                                              int vocab)
@@ -50,8 +76,39 @@ __global__ __launch_bounds__(256) void argmax_partial_kernel(const T* __restrict
     }
 }
 
-__global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n,
-                                                           int32_t* __restrict__ token_out)
+// the greedy sampler's first stage over the ADJUSTED logits x3 (softcap first: the penalty touches only some tokens, so the capped values decide); blockIdx.y = row b:
+// logits + b * logits_stride, table + b * table_stride, partials at pv0 + b * row_floats (values, then kArgmaxBlocks floats on the indices)
+__global__ __launch_bounds__(256) void argmax_partial_filtered_kernel(const float* __restrict__ logits0, size_t logits_stride, float softcap, const SampleFilter f,
+                                                                      float* __restrict__ pv0, int row_floats, int vocab)
+{
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const float* logits = logits0 + (size_t)blockIdx.y * logits_stride;
+    const uint32_t* table = f.table + (size_t)blockIdx.y * f.table_stride;
+    float* pv = pv0 + (size_t)blockIdx.y * row_floats;
+    int* pi = reinterpret_cast<int*>(pv + kArgmaxBlocks);
+    float bv = -FLT_MAX;
+    int bi = 0x7fffffff;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256)
+    {
+        float x = logits[i];
+        if (softcap > 0.0f) x = softcap * tanhf(x / softcap);
+        better(bv, bi, penalized_logit(x, table[i], f), i);
+    }
+    wave_argmax(bv, bi);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
+        pv[blockIdx.x] = bv;
+        pi[blockIdx.x] = bi;
+    }
+}
+
+template <bool TABLE>
+__device__ __forceinline__ void argmax_final_body(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out, uint32_t* table)
 {
     __shared__ float sv[4];
     __shared__ int si[4];
@@ -65,14 +122,25 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
     {
 #pragma unroll
         for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-        token_out[0] = (bi == 0x7fffffff) ? 0 : bi;      // all -FLT_MAX / NaN: the reference leaves index 0
+        const int tok = (bi == 0x7fffffff) ? 0 : bi;     // all -FLT_MAX / NaN: the reference leaves index 0
+        if (TABLE) table_count(table, tok);
+        token_out[0] = tok;
     }
+}
+__global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out)
+{
+    argmax_final_body<false>(pv, pi, n, token_out, nullptr);
+}
+__global__ __launch_bounds__(256) void argmax_final_table_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out, uint32_t* table)
+{
+    argmax_final_body<true>(pv, pi, n, token_out, table);
 }
 
 // the last node of a captured decode step: the final reduction of the greedy sampler, the position bump of the next step and (ring != NULL) the publication
 // of the sampled token to the host -- what argmax_final + advance_position[_snapshot] did in two launches (round 3: one launch fewer per token)
-__global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out,
-                                                                   int32_t* __restrict__ pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size)
+template <bool TABLE>
+__device__ __forceinline__ void argmax_final_advance_body(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out,
+                                                          int32_t* __restrict__ pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size, uint32_t* table)
 {
     __shared__ float sv[4];
     __shared__ int si[4];
@@ -87,6 +155,7 @@ __global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* 
 #pragma unroll
         for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
         const int tok = (bi == 0x7fffffff) ? 0 : bi;
+        if (TABLE) table_count(table, tok);
         token_out[0] = tok;
         *pos += 1;
         if (ring != nullptr)
@@ -97,11 +166,23 @@ __global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* 
         }
     }
 }
+__global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out,
+                                                                   int32_t* __restrict__ pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size)
+{
+    argmax_final_advance_body<false>(pv, pi, n, token_out, pos, seq_dev, ring, ring_size, nullptr);
+}
+__global__ __launch_bounds__(256) void argmax_final_advance_table_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out,
+                                                                         int32_t* __restrict__ pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size,
+                                                                         uint32_t* table)
+{
+    argmax_final_advance_body<true>(pv, pi, n, token_out, pos, seq_dev, ring, ring_size, table);
+}
 
 // argmax_final_advance_kernel for B independent rows, one workgroup per row: row b reduces the n partials at pv + b * row_floats (values, then kArgmaxBlocks floats on
 // the indices); a row whose active word is 0 keeps its token and its position
-__global__ __launch_bounds__(256) void argmax_rows_final_advance_kernel(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
-                                                                        const int32_t* __restrict__ active, int n, int row_floats)
+template <bool TABLE>
+__device__ __forceinline__ void argmax_rows_final_advance_body(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
+                                                               const int32_t* __restrict__ active, int n, int row_floats, uint32_t* table0, size_t table_stride)
 {
     __shared__ float sv[4];
     __shared__ int si[4];
@@ -118,8 +199,32 @@ __global__ __launch_bounds__(256) void argmax_rows_final_advance_kernel(const fl
     {
 #pragma unroll
         for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-        token_out[b] = (bi == 0x7fffffff) ? 0 : bi;
+        const int tok = (bi == 0x7fffffff) ? 0 : bi;
+        if (TABLE) table_count(table0 + (size_t)b * table_stride, tok);
+        token_out[b] = tok;
         pos[b] += 1;
+    }
+}
+__global__ __launch_bounds__(256) void argmax_rows_final_advance_kernel(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
+                                                                        const int32_t* __restrict__ active, int n, int row_floats)
+{
+    argmax_rows_final_advance_body<false>(pv0, token_out, pos, active, n, row_floats, nullptr, 0);
+}
+// (the active rows only: an inactive row's table, like its token and its position, is not touched)
+__global__ __launch_bounds__(256) void argmax_rows_final_advance_table_kernel(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
+                                                                              const int32_t* __restrict__ active, int n, int row_floats, uint32_t* table0, size_t table_stride)
+{
+    argmax_rows_final_advance_body<true>(pv0, token_out, pos, active, n, row_floats, table0, table_stride);
+}
+
+// table maintenance: bit 31 of the words of n token ids in device memory.  Every writer stores the SAME value into a cleared table (counts are zero before the first
+// sample), so plain vector stores are enough: repeats race on equal bits.  An id outside [0, vocab) is skipped.
+__global__ __launch_bounds__(256) void token_table_mark_prompt_kernel(uint32_t* __restrict__ table, int vocab, const int32_t* __restrict__ tokens, int n)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    {
+        const int id = tokens[i];
+        if (id >= 0 && id < vocab) table[id] = 0x80000000u;
     }
 }
 
@@ -573,8 +678,11 @@ __device__ __forceinline__ void radix_walk(const float* w, int first, int stride
 }
 
 // launch 1: x = softcap / temperature, per-workgroup max; clears the header and both histograms for the launches behind it
-template <typename T>
-__device__ __forceinline__ void radix_scale_body(const T* __restrict__ logits, const RadixParams& p, int clear_words)
+// FILT: the adjusted logit (penalized_logit on the capped value, then the temperature) with the table word read beside the logit in the same coalesced walk; the
+// copy goes to p.w as ever -- the logits are never written (the log-probabilities stay those of the unpenalized logits)
+template <typename T, bool FILT = false>
+__device__ __forceinline__ void radix_scale_body(const T* __restrict__ logits, const RadixParams& p, int clear_words, const SampleFilter* f = nullptr,
+                                                 const uint32_t* __restrict__ table = nullptr)
 {
     __shared__ float sv[4];
     uint32_t* z = reinterpret_cast<uint32_t*>(p.hdr);
@@ -584,6 +692,7 @@ __device__ __forceinline__ void radix_scale_body(const T* __restrict__ logits, c
     {
         float x = to_f32(logits[i]);
         if (p.softcap > 0.0f) x = p.softcap * tanhf(x / p.softcap);
+        if (FILT) x = penalized_logit(x, table[i], *f);
         x = x / p.temperature;
         p.w[i] = x;
         mx = fmaxf(mx, x);
@@ -714,7 +823,10 @@ __device__ __forceinline__ void radix_ppass_body(const RadixParams& p, int pass)
 }
 
 // nucleus mask + contiguous-chunk sums for the index-order CDF (samp_mask_kernel with the radix search's threshold)
-__device__ __forceinline__ void radix_mask_body(const RadixParams& p, int use_p, int chunk)
+// MINP: after the nucleus cut a surviving entry with e = expf(x - max) < min_p is dropped (the largest entry has e = 1: the tokens whose probability is at least
+// min_p times the top token's stay)
+template <bool MINP = false>
+__device__ __forceinline__ void radix_mask_body(const RadixParams& p, int use_p, int chunk, float min_p = 0.0f)
 {
     __shared__ unsigned long long sh[8];
     __shared__ float sv[4];
@@ -737,6 +849,7 @@ __device__ __forceinline__ void radix_mask_body(const RadixParams& p, int use_p,
     radix_walk(p.w, i0 + threadIdx.x, 256, i1, pre, [&](int i, float e)
     {
         if (use_p && __float_as_uint(e) < pthr) { e = 0.0f; p.w[i] = 0.0f; }
+        if (MINP && e > 0.0f && e < min_p) { e = 0.0f; p.w[i] = 0.0f; }
         sum += e;
     });
     sum = wave_sum(sum);
@@ -802,8 +915,9 @@ __device__ __forceinline__ int radix_cdf_walk(const RadixParams& p, float r, int
 
 // the one-row tail.  ADVANCE: the stochastic twin of argmax_final_advance_kernel -- the draw is slot (*seq_dev + 1) % draws_size of a host-written ring (system-scope
 // load: the host rewrites the slots between replays), and the tail bumps the position, stores the sequence number and (ring != NULL) publishes seq << 32 | token.
-template <bool ADVANCE>
-__global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int nchunks, int chunk)
+// TABLE: lane 0 counts the sample in the table before it stores / publishes the token.
+template <bool ADVANCE, bool TABLE>
+__device__ __forceinline__ void radix_cdf_body(const RadixParams& p, int nchunks, int chunk, uint32_t* table)
 {
     const int lane = threadIdx.x;
     float r = p.r;
@@ -817,6 +931,7 @@ __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int 
     const int result = radix_cdf_walk(p, r, nchunks, chunk, lane);
     if (lane == 0)
     {
+        if (TABLE) table_count(table, result);
         p.token_out[0] = result;
         if (ADVANCE)
         {
@@ -828,6 +943,11 @@ __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int 
     }
 }
 
+template <bool ADVANCE>
+__global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int nchunks, int chunk) { radix_cdf_body<ADVANCE, false>(p, nchunks, chunk, nullptr); }
+template <bool ADVANCE>
+__global__ __launch_bounds__(64) void radix_cdf_table_kernel(const RadixParams p, int nchunks, int chunk, uint32_t* table) { radix_cdf_body<ADVANCE, true>(p, nchunks, chunk, table); }
+
 // the one-row launches
 template <typename T>
 __global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ logits, const RadixParams p, int clear_words) { radix_scale_body(logits, p, clear_words); }
@@ -835,6 +955,12 @@ __global__ __launch_bounds__(256) void radix_kpass_kernel(const RadixParams p, i
 __global__ __launch_bounds__(256) void radix_prob_kernel(const RadixParams p, int use_k, int use_p, int nblocks_scale) { radix_prob_body(p, use_k, use_p, nblocks_scale); }
 __global__ __launch_bounds__(256) void radix_ppass_kernel(const RadixParams p, int pass) { radix_ppass_body(p, pass); }
 __global__ __launch_bounds__(256) void radix_mask_kernel(const RadixParams p, int use_p, int chunk) { radix_mask_body(p, use_p, chunk); }
+// ... and their filtered instantiations: the scale launch with the table, the mask launch with min-p
+__global__ __launch_bounds__(256) void radix_scale_filtered_kernel(const float* __restrict__ logits, const RadixParams p, int clear_words, const SampleFilter f)
+{
+    radix_scale_body<float, true>(logits, p, clear_words, &f, f.table);
+}
+__global__ __launch_bounds__(256) void radix_mask_minp_kernel(const RadixParams p, int use_p, int chunk, float min_p) { radix_mask_body<true>(p, use_p, chunk, min_p); }
 
 // The rows forms: the same bodies with a row dimension in the grid.  blockIdx.y = b picks row b's logits (logits + b * logits_stride) and row b's scratch region
 // (header, histograms, red, w at scratch + b * row_stride bytes); blockIdx.x / gridDim.x are what the one-row launch has, so every walk, every chunk and every float
@@ -881,6 +1007,17 @@ __global__ __launch_bounds__(256) void radix_mask_rows_kernel(const RadixRows r,
     const RadixParams p = radix_row(r, blockIdx.y);
     radix_mask_body(p, use_p, chunk);
 }
+// the filtered rows launches: row b's table is f.table + b * f.table_stride
+__global__ __launch_bounds__(256) void radix_scale_rows_filtered_kernel(const float* __restrict__ logits, const RadixRows r, int clear_words, const SampleFilter f)
+{
+    const RadixParams p = radix_row(r, blockIdx.y);
+    radix_scale_body<float, true>(logits + (size_t)blockIdx.y * r.logits_stride, p, clear_words, &f, f.table + (size_t)blockIdx.y * f.table_stride);
+}
+__global__ __launch_bounds__(256) void radix_mask_rows_minp_kernel(const RadixRows r, int use_p, int chunk, float min_p)
+{
+    const RadixParams p = radix_row(r, blockIdx.y);
+    radix_mask_body<true>(p, use_p, chunk, min_p);
+}
 
 // The rows tail, one workgroup: wave t walks row t's CDF (radix_cdf_walk: radix_cdf_kernel's additions in its order) at the draw draws[t] -- a system-scope load, the
 // host rewrites the draws between replays -- and the samples s_t meet in LDS; then one lane does the bookkeeping in plain stores.
@@ -921,6 +1058,36 @@ __global__ __launch_bounds__(256) void radix_rows_tail_kernel(const RadixRows r,
     }
 }
 
+// The rows tail with token tables (kRowsTokens / kRowsAdvance; a launch of its own so that the tail above stays as it is): the same walks, and the lane counts row b's
+// sample in row b's table (table0 + b * table_stride) before it stores the token -- in kRowsAdvance for the active rows only.  The chain tail takes no table: row t would
+// need the table plus the drafts 1 .. t.
+template <int MODE>
+__global__ __launch_bounds__(256) void radix_rows_tail_table_kernel(const RadixRows r, int rows, int nchunks, int chunk, const int32_t* __restrict__ active, uint32_t* table0,
+                                                                    size_t table_stride)
+{
+    static_assert(MODE == kRowsTokens || MODE == kRowsAdvance, "the chain tail takes no table");
+    __shared__ int ss[4];
+    const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+    if (t < rows)
+    {
+        const RadixParams p = radix_row(r, t);
+        const float draw = __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t*>(r.p.draws) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+        const int s = radix_cdf_walk(p, draw, nchunks, chunk, lane);
+        if (lane == 0) ss[t] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int32_t* tok = r.p.token_out;
+    int32_t* pos = r.p.pos;
+    for (int b = 0; b < rows; ++b)
+    {
+        if (MODE == kRowsAdvance && active[b] == 0) continue;
+        table_count(table0 + (size_t)b * table_stride, ss[b]);
+        tok[b] = ss[b];
+        if (MODE == kRowsAdvance) pos[b] += 1;
+    }
+}
+
 // the one place that decides what a radix call launches: the entries below and sample_radix_plan_describe read it
 struct RadixPlan
 {
@@ -930,11 +1097,16 @@ struct RadixPlan
     int blocks;              // workgroups of the pass / prob launches
     int chunk, nchunks;      // the mask launch's contiguous chunks
     size_t scratch_need;
+    int scale_filtered;      // the scale launch is the instantiation that reads the token table (a table was given)
+    int mask_filtered;       // the mask launch is the instantiation with the min-p test (min_p > 0)
 };
 constexpr size_t kRadixHistBytes = (size_t)kRadixPasses * kRadixBins * (sizeof(uint32_t) + sizeof(unsigned long long));
-static RadixPlan plan_radix(int vocab, int top_k, float top_p)
+// with_table / min_p choose INSTANTIATIONS of launches the plan already has: a filtered call launches what the unfiltered call launches
+static RadixPlan plan_radix(int vocab, int top_k, float top_p, bool with_table = false, float min_p = 0.0f)
 {
     RadixPlan d{};
+    d.scale_filtered = with_table ? 1 : 0;
+    d.mask_filtered = min_p > 0.0f ? 1 : 0;
     d.k_passes = (top_k > 0 && top_k < vocab) ? kRadixPasses : 0;
     d.p_passes = top_p < 1.0f ? kRadixPasses : 0;
     d.launches = 1 + d.k_passes + 1 + (d.p_passes ? d.p_passes - 1 : 0) + 2;
@@ -947,12 +1119,28 @@ static RadixPlan plan_radix(int vocab, int top_k, float top_p)
     return d;
 }
 
+// the filters of a call as the kernels take them.  flt == nullptr: neutral.  table == nullptr: no penalties and no update (min_p still holds).
+static int make_filter(const mila_sample_filters* flt, uint32_t* table, size_t table_stride, int rows, int vocab, SampleFilter& f, const char* who)
+{
+    const mila_sample_filters n = flt ? *flt : mila_sample_filters{0.0f, 1.0f, 0.0f, 0.0f};
+    MILA_REQUIRE(std::isfinite(n.min_p) && std::isfinite(n.repetition_penalty) && std::isfinite(n.presence_penalty) && std::isfinite(n.frequency_penalty),
+                 "%s: a sampling filter is not finite", who);
+    MILA_REQUIRE(n.repetition_penalty > 0.0f, "%s: repetition_penalty must be > 0", who);
+    MILA_REQUIRE(n.min_p >= 0.0f && n.min_p < 1.0f, "%s: min_p outside [0, 1)", who);
+    MILA_REQUIRE(!table || rows == 1 || table_stride >= (size_t)vocab, "%s: table_stride %zu < vocab %d", who, table_stride, vocab);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(table) & 3u) == 0, "%s: table must be 4-byte aligned", who);
+    f.table = table; f.table_stride = table_stride;
+    f.rep = n.repetition_penalty; f.inv_rep = 1.0f / n.repetition_penalty;
+    f.pres = n.presence_penalty; f.freq = n.frequency_penalty; f.min_p = n.min_p;
+    return MILA_OK;
+}
+
 struct RadixAdvance { const float* draws; int draws_size; int32_t* pos; unsigned long long* seq_dev; unsigned long long* ring; int ring_size; };
 
 // adv == nullptr: the draw is `r` and nothing is advanced
 template <typename T>
 static int run_radix(const T* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r, const RadixAdvance* adv,
-                     void* scratch, size_t scratch_bytes, hipStream_t s, const char* who)
+                     void* scratch, size_t scratch_bytes, hipStream_t s, const char* who, const SampleFilter* flt = nullptr)
 {
     MILA_REQUIRE(logits && token_out, "%s: null pointer", who);
     MILA_REQUIRE(!adv || (adv->draws && adv->pos && adv->seq_dev), "%s: null pointer", who);
@@ -961,7 +1149,7 @@ static int run_radix(const T* logits, int32_t* token_out, int vocab, float softc
     MILA_REQUIRE(top_k >= 0 && top_p > 0.0f && r >= 0.0f && r <= 1.0f, "%s: need top_k >= 0, top_p > 0, 0 <= r <= 1", who);
     MILA_REQUIRE(!adv || adv->draws_size > 0, "%s: draws_size must be positive", who);
     MILA_REQUIRE(!adv || (adv->ring ? adv->ring_size > 0 : adv->ring_size == 0), "%s: ring and ring_size go together", who);
-    const RadixPlan d = plan_radix(vocab, top_k, top_p);
+    const RadixPlan d = plan_radix(vocab, top_k, top_p, flt && flt->table, flt ? flt->min_p : 0.0f);
     if (!scratch || scratch_bytes < d.scratch_need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, d.scratch_need);
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, "%s: scratch must be 8-byte aligned", who);
     RadixParams p{};
@@ -975,12 +1163,23 @@ static int run_radix(const T* logits, int32_t* token_out, int vocab, float softc
     p.softcap = softcap; p.temperature = temperature; p.top_p = top_p; p.r = r;
     if (adv) { p.draws = adv->draws; p.draws_size = adv->draws_size; p.pos = adv->pos; p.seq_dev = adv->seq_dev; p.ring = adv->ring; p.ring_size = adv->ring_size; }
     const int clear_words = (int)((sizeof(RadixHeader) + kRadixHistBytes) / 4);
-    hipLaunchKernelGGL(radix_scale_kernel<T>, dim3(d.scale_blocks), dim3(256), 0, s, logits, p, clear_words);
+    if constexpr (std::is_same<T, float>::value)
+    {
+        if (d.scale_filtered) hipLaunchKernelGGL(radix_scale_filtered_kernel, dim3(d.scale_blocks), dim3(256), 0, s, logits, p, clear_words, *flt);
+        else hipLaunchKernelGGL(radix_scale_kernel<T>, dim3(d.scale_blocks), dim3(256), 0, s, logits, p, clear_words);
+    }
+    else hipLaunchKernelGGL(radix_scale_kernel<T>, dim3(d.scale_blocks), dim3(256), 0, s, logits, p, clear_words);
     for (int pass = 0; pass < d.k_passes; ++pass) hipLaunchKernelGGL(radix_kpass_kernel, dim3(d.blocks), dim3(256), 0, s, p, pass);
     hipLaunchKernelGGL(radix_prob_kernel, dim3(d.blocks), dim3(256), 0, s, p, d.k_passes ? 1 : 0, d.p_passes ? 1 : 0, d.scale_blocks);
     for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_kernel, dim3(d.blocks), dim3(256), 0, s, p, pass);
-    hipLaunchKernelGGL(radix_mask_kernel, dim3(d.nchunks), dim3(256), 0, s, p, d.p_passes ? 1 : 0, d.chunk);
-    if (adv) hipLaunchKernelGGL(radix_cdf_kernel<true>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
+    if (d.mask_filtered) hipLaunchKernelGGL(radix_mask_minp_kernel, dim3(d.nchunks), dim3(256), 0, s, p, d.p_passes ? 1 : 0, d.chunk, flt->min_p);
+    else hipLaunchKernelGGL(radix_mask_kernel, dim3(d.nchunks), dim3(256), 0, s, p, d.p_passes ? 1 : 0, d.chunk);
+    if (d.scale_filtered)
+    {
+        if (adv) hipLaunchKernelGGL(radix_cdf_table_kernel<true>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk, flt->table);
+        else hipLaunchKernelGGL(radix_cdf_table_kernel<false>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk, flt->table);
+    }
+    else if (adv) hipLaunchKernelGGL(radix_cdf_kernel<true>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
     else hipLaunchKernelGGL(radix_cdf_kernel<false>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
     return check_hip(hipGetLastError(), who);
 }
@@ -991,7 +1190,8 @@ static size_t radix_row_stride(int vocab) { return (plan_radix(vocab, 0, 1.0f).s
 // The radix pipeline over `rows` rows in ONE pipeline: plan_radix's launches for one row, each with the rows in grid.y, and the rows tail in the place of the cdf
 // launch.  mode kRowsTokens: pos / active / result unused; kRowsAdvance: pos[rows], active[rows]; kRowsChain: token_out is tok[rows], pos the one position word.
 static int run_radix_rows(int mode, const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k, float top_p,
-                          const float* draws, void* scratch, size_t scratch_bytes, int32_t* pos, const int32_t* active, int32_t* result, hipStream_t s, const char* who)
+                          const float* draws, void* scratch, size_t scratch_bytes, int32_t* pos, const int32_t* active, int32_t* result, hipStream_t s, const char* who,
+                          const SampleFilter* flt = nullptr)
 {
     MILA_REQUIRE(logits && token_out && draws, "%s: null pointer", who);
     MILA_REQUIRE(mode == kRowsTokens || pos, "%s: null pointer", who);
@@ -1003,7 +1203,8 @@ static int run_radix_rows(int mode, const float* logits, size_t logits_stride, i
     MILA_REQUIRE(logits_stride >= (size_t)vocab, "%s: logits_stride %zu < vocab %d", who, logits_stride, vocab);
     MILA_REQUIRE(temperature > 0.0f, "%s: temperature must be > 0 (temperature <= 0 is the greedy sampler: sample_argmax)", who);
     MILA_REQUIRE(top_k >= 0 && top_p > 0.0f, "%s: need top_k >= 0, top_p > 0", who);
-    const RadixPlan d = plan_radix(vocab, top_k, top_p);
+    MILA_REQUIRE(mode != kRowsChain || !flt, "%s: the chain tail takes no filters", who);
+    const RadixPlan d = plan_radix(vocab, top_k, top_p, flt && flt->table, flt ? flt->min_p : 0.0f);
     const size_t row_stride = radix_row_stride(vocab), need = row_stride * (size_t)rows;
     if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, "%s: scratch must be 8-byte aligned", who);
@@ -1021,14 +1222,44 @@ static int run_radix_rows(int mode, const float* logits, size_t logits_stride, i
     r.row_stride = row_stride; r.logits_stride = logits_stride;
     const int clear_words = (int)((sizeof(RadixHeader) + kRadixHistBytes) / 4);
     const unsigned R = (unsigned)rows;
-    hipLaunchKernelGGL(radix_scale_rows_kernel, dim3(d.scale_blocks, R), dim3(256), 0, s, logits, r, clear_words);
+    if (d.scale_filtered) hipLaunchKernelGGL(radix_scale_rows_filtered_kernel, dim3(d.scale_blocks, R), dim3(256), 0, s, logits, r, clear_words, *flt);
+    else hipLaunchKernelGGL(radix_scale_rows_kernel, dim3(d.scale_blocks, R), dim3(256), 0, s, logits, r, clear_words);
     for (int pass = 0; pass < d.k_passes; ++pass) hipLaunchKernelGGL(radix_kpass_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, pass);
     hipLaunchKernelGGL(radix_prob_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, d.k_passes ? 1 : 0, d.p_passes ? 1 : 0, d.scale_blocks);
     for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, pass);
-    hipLaunchKernelGGL(radix_mask_rows_kernel, dim3(d.nchunks, R), dim3(256), 0, s, r, d.p_passes ? 1 : 0, d.chunk);
-    if (mode == kRowsTokens) hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsTokens>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
+    if (d.mask_filtered) hipLaunchKernelGGL(radix_mask_rows_minp_kernel, dim3(d.nchunks, R), dim3(256), 0, s, r, d.p_passes ? 1 : 0, d.chunk, flt->min_p);
+    else hipLaunchKernelGGL(radix_mask_rows_kernel, dim3(d.nchunks, R), dim3(256), 0, s, r, d.p_passes ? 1 : 0, d.chunk);
+    if (d.scale_filtered && mode == kRowsTokens)
+        hipLaunchKernelGGL(radix_rows_tail_table_kernel<kRowsTokens>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, flt->table, flt->table_stride);
+    else if (d.scale_filtered && mode == kRowsAdvance)
+        hipLaunchKernelGGL(radix_rows_tail_table_kernel<kRowsAdvance>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, flt->table, flt->table_stride);
+    else if (mode == kRowsTokens) hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsTokens>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
     else if (mode == kRowsAdvance) hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsAdvance>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
     else hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsChain>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
+    return check_hip(hipGetLastError(), who);
+}
+
+// The penalized greedy sampler over `rows` rows: argmax(x3), ties to the lower id, in the two launches of sample_argmax_*: the partial stage computes x3 from logits,
+// table and softcap, the final stage counts the token in the table.  adv: the one-row advance tail; pos + active: the rows advance tail; neither: token only.
+static int run_argmax_filtered(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, const SampleFilter& f, void* scratch,
+                               size_t scratch_bytes, const RadixAdvance* adv, int32_t* positions, const int32_t* active, hipStream_t s, const char* who)
+{
+    const size_t per_row = (size_t)kArgmaxBlocks * 8, need = per_row * (size_t)rows;
+    if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
+    float* pv = reinterpret_cast<float*>(scratch);
+    int* pi = reinterpret_cast<int*>(pv + kArgmaxBlocks);
+    int blocks = (vocab + 255) / 256;
+    if (blocks > kArgmaxBlocks) blocks = kArgmaxBlocks;
+    const int row_floats = (int)(per_row / sizeof(float));
+    hipLaunchKernelGGL(argmax_partial_filtered_kernel, dim3(blocks, (unsigned)rows), dim3(256), 0, s, logits, logits_stride, softcap, f, pv, row_floats, vocab);
+    int rc = check_hip(hipGetLastError(), who);
+    if (rc) return rc;
+    if (positions)
+        hipLaunchKernelGGL(argmax_rows_final_advance_table_kernel, dim3(rows), dim3(256), 0, s, pv, token_out, positions, active, blocks, row_floats, f.table, f.table_stride);
+    else if (adv)
+        hipLaunchKernelGGL(argmax_final_advance_table_kernel, dim3(1), dim3(256), 0, s, pv, pi, blocks, token_out, adv->pos, adv->seq_dev, adv->ring, adv->ring_size, f.table);
+    else
+        hipLaunchKernelGGL(argmax_final_table_kernel, dim3(1), dim3(256), 0, s, pv, pi, blocks, token_out, f.table);
     return check_hip(hipGetLastError(), who);
 }
 
@@ -1182,6 +1413,126 @@ int mila_cdna4_sample_radix_chain_accept_fp32(int32_t* tok, int32_t* result, con
 {
     return run_radix_rows(kRowsChain, logits, logits_stride, tok, T, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, position_dev, nullptr, result,
                           as_stream(stream), "sample_radix_chain_accept_fp32");
+}
+
+// ---- the filtered entries (mila_cdna4.h: sampling filters)
+size_t mila_cdna4_token_table_bytes(int vocab) { return vocab > 0 ? (size_t)vocab * sizeof(uint32_t) : 0; }
+
+int mila_cdna4_token_table_clear(uint32_t* table, size_t table_stride, int row, int vocab, mila_stream_t stream)
+{
+    MILA_REQUIRE(table, "token_table_clear: null pointer");
+    MILA_REQUIRE(vocab > 0 && row >= 0 && (row == 0 || table_stride >= (size_t)vocab), "token_table_clear: need vocab > 0, row >= 0, table_stride >= vocab");
+    return check_hip(hipMemsetAsync(table + (size_t)row * table_stride, 0, (size_t)vocab * sizeof(uint32_t), as_stream(stream)), "token_table_clear");
+}
+
+int mila_cdna4_token_table_mark_prompt(uint32_t* table, size_t table_stride, int row, int vocab, const int32_t* tokens_dev, int n, mila_stream_t stream)
+{
+    MILA_REQUIRE(table && (tokens_dev || n == 0), "token_table_mark_prompt: null pointer");
+    MILA_REQUIRE(vocab > 0 && row >= 0 && n >= 0 && (row == 0 || table_stride >= (size_t)vocab), "token_table_mark_prompt: need vocab > 0, row >= 0, n >= 0, table_stride >= vocab");
+    if (n == 0) return MILA_OK;
+    int blocks = (n + 255) / 256;
+    if (blocks > 256) blocks = 256;
+    hipLaunchKernelGGL(token_table_mark_prompt_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), table + (size_t)row * table_stride, vocab, tokens_dev, n);
+    MILA_LAUNCH_CHECK("token_table_mark_prompt");
+}
+
+int mila_cdna4_sample_radix_filtered_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                          const mila_sample_filters* filters, uint32_t* table, void* scratch, size_t scratch_bytes, mila_stream_t stream)
+{
+    SampleFilter f{};
+    const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_radix_filtered_fp32");
+    if (rc) return rc;
+    return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_filtered_fp32", &f);
+}
+
+int mila_cdna4_sample_radix_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
+                                                  const float* draws, int draws_size, const mila_sample_filters* filters, uint32_t* table, void* scratch, size_t scratch_bytes,
+                                                  int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring, int ring_size, mila_stream_t stream)
+{
+    SampleFilter f{};
+    const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_radix_filtered_advance_fp32");
+    if (rc) return rc;
+    const RadixAdvance adv{draws, draws_size, position_dev, seq_dev, ring, ring_size};
+    return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream),
+                            "sample_radix_filtered_advance_fp32", &f);
+}
+
+int mila_cdna4_sample_radix_filtered_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k,
+                                               float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table, size_t table_stride, void* scratch,
+                                               size_t scratch_bytes, mila_stream_t stream)
+{
+    SampleFilter f{};
+    const int rc = make_filter(filters, table, table_stride, rows, vocab, f, "sample_radix_filtered_rows_fp32");
+    if (rc) return rc;
+    return run_radix_rows(kRowsTokens, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, nullptr, nullptr, nullptr,
+                          as_stream(stream), "sample_radix_filtered_rows_fp32", &f);
+}
+
+int mila_cdna4_sample_radix_filtered_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature,
+                                                       int top_k, float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table, size_t table_stride,
+                                                       void* scratch, size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream)
+{
+    SampleFilter f{};
+    const int rc = make_filter(filters, table, table_stride, rows, vocab, f, "sample_radix_filtered_rows_advance_fp32");
+    if (rc) return rc;
+    return run_radix_rows(kRowsAdvance, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, positions_dev, active_dev,
+                          nullptr, as_stream(stream), "sample_radix_filtered_rows_advance_fp32", &f);
+}
+
+// table == NULL: no penalties, and min_p does not change a greedy request -- today's greedy sampler on the logits as they are
+int mila_cdna4_sample_argmax_filtered_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
+                                           void* scratch, size_t scratch_bytes, mila_stream_t stream)
+{
+    SampleFilter f{};
+    const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_argmax_filtered_fp32");
+    if (rc) return rc;
+    if (!table) return run_argmax<float>(logits, token_out, vocab, scratch, scratch_bytes, as_stream(stream), "sample_argmax_filtered_fp32");
+    MILA_REQUIRE(logits && token_out, "sample_argmax_filtered_fp32: null pointer");
+    MILA_REQUIRE(vocab > 0, "sample_argmax_filtered_fp32: vocab must be positive");
+    return run_argmax_filtered(logits, 0, token_out, 1, vocab, softcap, f, scratch, scratch_bytes, nullptr, nullptr, nullptr, as_stream(stream), "sample_argmax_filtered_fp32");
+}
+
+int mila_cdna4_sample_argmax_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
+                                                   void* scratch, size_t scratch_bytes, int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring,
+                                                   int ring_size, mila_stream_t stream)
+{
+    SampleFilter f{};
+    const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_argmax_filtered_advance_fp32");
+    if (rc) return rc;
+    if (!table) return mila_cdna4_sample_argmax_advance_fp32(logits, token_out, vocab, scratch, scratch_bytes, position_dev, seq_dev, ring, ring_size, stream);
+    MILA_REQUIRE(logits && token_out && position_dev, "sample_argmax_filtered_advance_fp32: null pointer");
+    MILA_REQUIRE(vocab > 0, "sample_argmax_filtered_advance_fp32: vocab must be positive");
+    MILA_REQUIRE((ring == nullptr) == (seq_dev == nullptr) && (ring == nullptr || ring_size > 0), "sample_argmax_filtered_advance_fp32: ring, seq_dev and ring_size go together");
+    const RadixAdvance adv{nullptr, 0, position_dev, seq_dev, ring, ring_size};
+    return run_argmax_filtered(logits, 0, token_out, 1, vocab, softcap, f, scratch, scratch_bytes, &adv, nullptr, nullptr, as_stream(stream), "sample_argmax_filtered_advance_fp32");
+}
+
+// the rows greedy tail with penalties: both launches (the lm_head epilogue cannot compute x3), tokens, positions and tables of the active rows only
+int mila_cdna4_sample_argmax_filtered_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                        const mila_sample_filters* filters, uint32_t* table, size_t table_stride, void* scratch, size_t scratch_bytes,
+                                                        int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream)
+{
+    const char* who = "sample_argmax_filtered_rows_advance_fp32";
+    MILA_REQUIRE(logits && token_out && positions_dev && active_dev && table, "%s: null pointer", who);
+    MILA_REQUIRE(rows >= 1 && rows <= 4, "%s: rows=%d outside 1 .. 4", who, rows);
+    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
+    MILA_REQUIRE(logits_stride >= (size_t)vocab, "%s: logits_stride %zu < vocab %d", who, logits_stride, vocab);
+    SampleFilter f{};
+    const int rc = make_filter(filters, table, table_stride, rows, vocab, f, who);
+    if (rc) return rc;
+    return run_argmax_filtered(logits, logits_stride, token_out, rows, vocab, softcap, f, scratch, scratch_bytes, nullptr, positions_dev, active_dev, as_stream(stream), who);
+}
+
+// "launches:k_passes:p_passes:scratch_need:scale_filtered:mask_filtered" of a filtered call (plan_radix, the function the entries launch from); 0 for arguments the
+// entries refuse
+size_t mila_cdna4_sample_filters_describe(int vocab, int top_k, float top_p, const mila_sample_filters* filters, int with_table, char* buf, size_t cap)
+{
+    if (buf && cap) buf[0] = 0;
+    if (vocab <= 0 || top_k < 0 || !(top_p > 0.0f)) return 0;
+    SampleFilter f{};
+    if (make_filter(filters, nullptr, 0, 1, vocab, f, "sample_filters_describe")) return 0;
+    const RadixPlan d = plan_radix(vocab, top_k, top_p, with_table != 0, f.min_p);
+    return 1 + snprintf(buf, buf ? cap : 0, "%d:%d:%d:%zu:%d:%d", d.launches, d.k_passes, d.p_passes, d.scratch_need, d.scale_filtered, d.mask_filtered);
 }
 
 size_t mila_cdna4_sample_radix_plan_describe(int vocab, int top_k, float top_p, char* buf, size_t cap)

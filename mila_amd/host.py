@@ -87,6 +87,19 @@ def _logprobs_n(n):
     return n
 
 
+def _filters(min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+    """the sampling filters as (min_p, repetition_penalty, presence_penalty, frequency_penalty) floats; ValueError for what the C ABI refuses with
+    MILA_E_INVALID_ARGUMENT (include/mila_cdna4.h: sampling filters): a non-finite value, repetition_penalty <= 0, min_p outside [0, 1)"""
+    f = tuple(float(v) for v in (min_p, repetition_penalty, presence_penalty, frequency_penalty))
+    if not all(np.isfinite(v) for v in f):
+        raise ValueError("sampling filters must be finite (got min_p=%g repetition_penalty=%g presence_penalty=%g frequency_penalty=%g)" % f)
+    if f[1] <= 0.0:
+        raise ValueError("repetition_penalty must be > 0 (got %g)" % f[1])
+    if not 0.0 <= f[0] < 1.0:
+        raise ValueError("min_p must be in [0, 1) (got %g)" % f[0])
+    return f
+
+
 class Gemma:
     """GemmaTransformer<policy> with synthetic weights on cuda:0."""
 
@@ -261,20 +274,58 @@ class Gemma:
         lib.mila_gemma_set_step_logprobs.argtypes = [C.c_void_p, C.c_int]
         _check(lib.mila_gemma_set_step_logprobs(self.h, -1 if n is None else _logprobs_n(n)))
 
-    def generate(self, first_token, start_position, n_tokens, mode="graph"):
-        """greedy autoregressive generation with the device sampler; returns the sampled token ids"""
+    def set_sampling_filters(self, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+        """the sampling filters of the step-level calls that follow (GemmaTransformer::setSamplingFilters for the greedy samplers; the stochastic ones get them with
+        their parameters): decode_rows, the timing loops, generate / generate_sampled without filter keywords.  No arguments = neutral.  Penalties act on the token
+        table of set_token_table()."""
+        lib = load()
+        lib.mila_gemma_set_sampling_filters.argtypes = [C.c_void_p, C.c_void_p]
+        f = (C.c_float * 4)(*_filters(min_p, repetition_penalty, presence_penalty, frequency_penalty))
+        _check(lib.mila_gemma_set_sampling_filters(self.h, f))
+
+    def set_token_table(self, row, prompt):
+        """a new request on row `row` (0: the one-sequence interface): counts to zero, the prompt tokens' flags set"""
+        lib = load()
+        lib.mila_gemma_set_token_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+        ids = np.ascontiguousarray(prompt, dtype=np.int32)
+        _check(lib.mila_gemma_set_token_table(self.h, int(row), ids.ctypes.data if ids.size else None, ids.size))
+
+    def token_table(self, row=0):
+        """row `row`'s table words (uint32 [vocab]): bit 31 = in the prompt, bits 0 .. 30 = times generated"""
+        lib = load()
+        lib.mila_gemma_read_token_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        out = np.zeros(self.vocab, dtype=np.uint32)
+        _check(lib.mila_gemma_read_token_table(self.h, int(row), out.ctypes.data))
+        return out
+
+    def _with_filters(self, filters, fn):
+        """fn() under the given filter keywords, neutral again afterwards; no keywords: whatever set_sampling_filters() left"""
+        if not filters:
+            return fn()
+        self.set_sampling_filters(**filters)
+        try:
+            return fn()
+        finally:
+            self.set_sampling_filters()
+
+    def generate(self, first_token, start_position, n_tokens, mode="graph", **penalties):
+        """greedy autoregressive generation with the device sampler; returns the sampled token ids.  penalties: repetition_penalty, presence_penalty,
+        frequency_penalty -- argmax of the adjusted logits, from and into the token table of set_token_table(0, prompt)"""
+        if "min_p" in penalties:
+            raise TypeError("Gemma.generate: min_p does not change a greedy request")
         out = np.empty(n_tokens, dtype=np.int32)
-        _check(load().mila_gemma_generate(self.h, int(first_token), int(start_position), int(n_tokens), self.MODES[mode], out.ctypes.data))
+        self._with_filters(penalties, lambda: _check(load().mila_gemma_generate(self.h, int(first_token), int(start_position), int(n_tokens), self.MODES[mode], out.ctypes.data)))
         return out
 
     PIPELINES = {"search": 0, "radix": 1}
 
-    def generate_sampled(self, first_token, start_position, n_tokens, temperature=1.0, top_k=0, top_p=1.0, seed=0, mode="fused", pipeline="search"):
+    def generate_sampled(self, first_token, start_position, n_tokens, temperature=1.0, top_k=0, top_p=1.0, seed=0, mode="fused", pipeline="search", **filters):
         """multinomial generation (softcap + temperature + top-k + top-p on the device, uniform draws from a host mt19937).  pipeline: "search" = sample_stochastic_*,
-        "radix" = sample_radix_*; mode "graph" (radix only) runs the sampler as the tail of the captured step, its draws and tokens travelling through host-visible rings"""
+        "radix" = sample_radix_*; mode "graph" (radix only) runs the sampler as the tail of the captured step, its draws and tokens travelling through host-visible rings.
+        filters (radix only): min_p, repetition_penalty, presence_penalty, frequency_penalty; the penalties read and update the token table of set_token_table(0, prompt)"""
         out = np.empty(n_tokens, dtype=np.int32)
-        _check(load().mila_gemma_generate_sampled(self.h, int(first_token), int(start_position), int(n_tokens), self.MODES[mode], self.PIPELINES[pipeline],
-                                                     float(temperature), int(top_k), float(top_p), int(seed), out.ctypes.data))
+        self._with_filters(filters, lambda: _check(load().mila_gemma_generate_sampled(self.h, int(first_token), int(start_position), int(n_tokens), self.MODES[mode],
+                                                                                      self.PIPELINES[pipeline], float(temperature), int(top_k), float(top_p), int(seed), out.ctypes.data)))
         return out
 
     # ---- batched decode: rows of independent sequences (max_batch > 1) ----
@@ -556,7 +607,48 @@ class GemmaModel:
         return cls(h, device)
 
     def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
-                 speculative_sampling=False, logprobs=None):
+                 speculative_sampling=False, logprobs=None, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+        """_generate() with the sampling filters (GenerateParams::sampling.min_p / .repetition_penalty / .presence_penalty / .frequency_penalty): the penalties read a
+        token table on the device that starts from the whole prompt and counts every generated token; greedy with a penalty = argmax of the adjusted logits; a request
+        with any filter set takes the plain loop on a draft_tokens model too.  Log-probabilities are those of the unpenalized logits.  With every filter neutral this
+        is _generate(), entry for entry."""
+        f = _filters(min_p, repetition_penalty, presence_penalty, frequency_penalty)
+        if f == _filters():
+            return self._generate(prompt, max_new_tokens, stop_tokens, temperature, top_k, top_p, seed, cancel_after, draft_hint, speculative_sampling, logprobs)
+        lib = load()
+        pr = np.ascontiguousarray(prompt, dtype=np.int32)
+        st = np.ascontiguousarray(list(stop_tokens), dtype=np.int32)
+        cap = int(max_new_tokens) if max_new_tokens is not None else 1 << 16
+        out = np.zeros(max(cap, 1), dtype=np.int32)
+        n, status, reused, n_lp = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64()
+        top_n = -1 if logprobs is None else _logprobs_n(logprobs)
+        width = max(top_n, 1)
+        lp, ids, tlp = np.zeros(len(out), dtype=np.float32), np.zeros((len(out), width), dtype=np.int32), np.zeros((len(out), width), dtype=np.float32)
+        fl = (C.c_float * 4)(*f)
+        head = [self.h, pr.ctypes.data, len(pr), -1 if max_new_tokens is None else int(max_new_tokens), st.ctypes.data if len(st) else None, len(st), float(temperature),
+                int(top_k), float(top_p), -1 if seed is None else int(seed)]
+        head_types = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int64]
+        tail = [top_n, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data, C.byref(n_lp), fl]
+        tail_types = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if speculative_sampling or draft_hint is not None:
+            if cancel_after is not None:
+                raise ValueError("GemmaModel.generate: draft_hint / speculative_sampling cannot be combined with cancel_after")
+            hint = np.ascontiguousarray([] if draft_hint is None else draft_hint, dtype=np.int32)
+            stats = (C.c_int64 * 4)()
+            lib.mila_gemma_model_generate_spec_filtered.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types
+            _check(lib.mila_gemma_model_generate_spec_filtered(*head, hint.ctypes.data if hint.size else None, int(hint.size), int(bool(speculative_sampling)), out.ctypes.data,
+                                                               len(out), C.byref(n), C.byref(status), stats, *tail))
+        else:
+            lib.mila_gemma_model_generate_filtered.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + tail_types
+            _check(lib.mila_gemma_model_generate_filtered(*head, out.ctypes.data, len(out), C.byref(n), C.byref(status), C.byref(reused),
+                                                          -1 if cancel_after is None else int(cancel_after), *tail))
+        res = (out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], reused.value)
+        if logprobs is None:
+            return res
+        return res + ([(np.float32(lp[i]), ids[i, :top_n].copy(), tlp[i, :top_n].copy()) for i in range(min(n_lp.value, len(out)))],)
+
+    def _generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
+                  speculative_sampling=False, logprobs=None):
         """-> (tokens passed to on_token, finish reason as GenerateStatus's to_string, prompt tokens served from the KV caches).
         logprobs = n (0 .. 20; GenerateParams::logprobs): a fourth element, a list of (logprob, top_ids [n], top_logprobs [n]) per emitted token -- its
         log-probability under the model's distribution (no temperature, no truncation) and the n most probable tokens, computed on the device inside the step.
@@ -633,7 +725,35 @@ class GemmaModel:
         _check(lib.mila_gemma_model_speculation_stats(self.h, out))
         return dict(zip(("steps", "chain_steps", "drafted", "accepted"), [int(v) for v in out]))
 
-    def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0, logprobs=None):
+    def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0, logprobs=None, min_p=0.0, repetition_penalty=1.0,
+                       presence_penalty=0.0, frequency_penalty=0.0):
+        """_generate_batch() with the sampling filters of generate(), shared by the rows; every row has its own token table"""
+        f = _filters(min_p, repetition_penalty, presence_penalty, frequency_penalty)
+        if f == _filters():
+            return self._generate_batch(prompts, max_new_tokens, stop_tokens, temperature, top_k, top_p, seed, logprobs)
+        lib = load()
+        lib.mila_gemma_model_generate_rows_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64,
+                                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if len(prompts) else np.zeros(0), dtype=np.int32)
+        offs = np.ascontiguousarray(np.cumsum([0] + [len(p) for p in prompts]), dtype=np.int64)
+        st = np.ascontiguousarray(list(stop_tokens), dtype=np.int32)
+        cap = int(max_new_tokens) if max_new_tokens is not None else 1 << 16
+        out = np.zeros((max(len(prompts), 1), max(cap, 1)), dtype=np.int32)
+        counts, status, lp_counts = (np.zeros(max(len(prompts), 1), dtype=t) for t in (np.int64, np.int32, np.int64))
+        top_n = -1 if logprobs is None else _logprobs_n(logprobs)
+        width = max(top_n, 1)
+        lp, ids, tlp = np.zeros(out.shape, dtype=np.float32), np.zeros(out.shape + (width,), dtype=np.int32), np.zeros(out.shape + (width,), dtype=np.float32)
+        fl = (C.c_float * 4)(*f)
+        _check(lib.mila_gemma_model_generate_rows_filtered(self.h, flat.ctypes.data, offs.ctypes.data, len(prompts), -1 if max_new_tokens is None else int(max_new_tokens),
+                                                           st.ctypes.data if len(st) else None, len(st), float(temperature), int(top_k), float(top_p), int(seed), out.ctypes.data,
+                                                           out.shape[1], counts.ctypes.data, status.ctypes.data, top_n, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data,
+                                                           lp_counts.ctypes.data, fl))
+        rows = [(out[b, :min(int(counts[b]), out.shape[1])].tolist(), GENERATE_STATUS[int(status[b])]) for b in range(len(prompts))]
+        if logprobs is None:
+            return rows
+        return [rows[b] + ([(np.float32(lp[b, i]), ids[b, i, :top_n].copy(), tlp[b, i, :top_n].copy()) for i in range(min(int(lp_counts[b]), out.shape[1]))],) for b in range(len(prompts))]
+
+    def _generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0, logprobs=None):
         """GemmaModel::generateBatch: up to max_batch prompts at once, prompt b in row b -> [(tokens, finish reason)] per prompt, by generate()'s rules.  Row b samples
         from its own generator seeded seed + b."""
         lib = load()
@@ -918,6 +1038,9 @@ class Sampler:
         lib.mila_sampler_destroy.argtypes = [C.c_void_p]
         lib.mila_sampler_set_logits.argtypes = [C.c_void_p, C.c_void_p]
         lib.mila_sampler_sample.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_void_p]
+        lib.mila_sampler_sample_filtered.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+        lib.mila_sampler_set_token_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.mila_sampler_read_token_table.argtypes = [C.c_void_p, C.c_void_p]
         lib.mila_linear_last_error.restype = C.c_char_p
         self.vocab = vocab
         self.h = lib.mila_sampler_create(vocab, softcap, device)
@@ -931,19 +1054,43 @@ class Sampler:
         if load().mila_sampler_set_logits(self.h, lg.ctypes.data):
             raise RuntimeError(load().mila_linear_last_error().decode())
 
-    def _run(self, mode, temperature, top_k, top_p, r):
+    @staticmethod
+    def _raise(rc):
+        text = load().mila_linear_last_error().decode()
+        raise (TypeError if rc == capi.MILA_E_UNSUPPORTED else (ValueError if rc == capi.MILA_E_INVALID_ARGUMENT else RuntimeError))(text)
+
+    def _run(self, mode, temperature, top_k, top_p, r, filters=None):
         tok = C.c_int32()
-        rc = load().mila_sampler_sample(self.h, mode, temperature, top_k, top_p, r, C.byref(tok))
+        if filters is None or filters == _filters():
+            rc = load().mila_sampler_sample(self.h, mode, temperature, top_k, top_p, r, C.byref(tok))
+        else:
+            f = (C.c_float * 4)(*filters)
+            rc = load().mila_sampler_sample_filtered(self.h, mode, temperature, top_k, top_p, r, f, C.byref(tok))
         if rc:
-            text = load().mila_linear_last_error().decode()
-            raise (TypeError if rc == capi.MILA_E_UNSUPPORTED else (ValueError if rc == capi.MILA_E_INVALID_ARGUMENT else RuntimeError))(text)
+            self._raise(rc)
         return tok.value
 
-    def sample(self, temperature=1.0, top_k=0, top_p=1.0, r=0.5):
-        return self._run(0, temperature, top_k, top_p, r)
+    def sample(self, temperature=1.0, top_k=0, top_p=1.0, r=0.5, **filters):
+        """filters: min_p, repetition_penalty, presence_penalty, frequency_penalty (penalties need set_token_table() first; the sampled token is counted there)"""
+        return self._run(0, temperature, top_k, top_p, r, _filters(**filters))
 
-    def sample_enqueued(self, temperature=1.0, top_k=0, top_p=1.0, r=0.5):
-        return self._run(1, temperature, top_k, top_p, r)
+    def sample_enqueued(self, temperature=1.0, top_k=0, top_p=1.0, r=0.5, **filters):
+        return self._run(1, temperature, top_k, top_p, r, _filters(**filters))
+
+    def set_token_table(self, prompt):
+        """a new request: counts to zero, the prompt tokens' flags set"""
+        ids = np.ascontiguousarray(prompt, dtype=np.int32)
+        rc = load().mila_sampler_set_token_table(self.h, ids.ctypes.data, ids.size)
+        if rc:
+            self._raise(rc)
+
+    def token_table(self):
+        """the table's words (uint32 [vocab]): bit 31 = in the prompt, bits 0 .. 30 = times generated"""
+        out = np.zeros(self.vocab, dtype=np.uint32)
+        rc = load().mila_sampler_read_token_table(self.h, out.ctypes.data)
+        if rc:
+            self._raise(rc)
+        return out
 
     def await_token(self):
         return self._run(2, 0.0, 0, 1.0, 0.0)

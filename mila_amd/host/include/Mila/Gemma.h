@@ -242,7 +242,35 @@ namespace Mila::Dnn
 
         /// SamplingParams (Components/Transformers/SamplingParams.ixx): temperature <= 0 is greedy; top_k 0 / top_p >= 1 disable
         /// the truncations.  The uniform r in [0, 1) is drawn by the caller, as in the reference (host RNG, GemmaModel.ixx:568).
-        struct SamplingParams { float temperature = 1.0f; int top_k = 0; float top_p = 1.0f; };
+        /// The four sampling filters (min_p, repetition / presence / frequency penalty; Operations.h, mila_cdna4.h: sampling filters) ride in the same struct, neutral
+        /// by default.  The stochastic samplers take them from the SamplingParams they are given; the greedy samplers, which take none, from setSamplingFilters().
+        /// The penalties depend on the tokens sampled so far, so their state -- one token table per row -- lives on the device and is updated by every filtered
+        /// sampler, eager or captured: resetTokenTable() starts a request.  Log-probabilities are unchanged by all four: the samplers write their scaled copy into
+        /// their own workspace and never touch the logits, so setStepLogprobs() keeps reporting the softmax of the soft-capped, UNPENALIZED logits.
+        using SamplingParams = Compute::SamplingParams;
+
+        /// the filters of the greedy samplers (sampleGreedy, sampleRowGreedy, the greedy captured steps); only the four filter fields of `f` are read.  With a penalty
+        /// set, a greedy token is argmax of the adjusted logits (softcap first), ties to the lower id: the captured greedy step then ends at the logits, like the
+        /// stochastic one, and runs the penalized sampler's two launches behind them.  min_p alone leaves a greedy request on today's path.  A change re-captures
+        /// once, as a change of temperature does.  The token tables are allocated by the first call that sets a penalty, and counted in the memory statistics from
+        /// then on; a model that never saw a penalty allocates nothing.
+        void setSamplingFilters( const SamplingParams& f )
+        {
+            f.checkFilters( "GemmaTransformer::setSamplingFilters" );
+            if ( f.penalized() ) ensureTokenTable();
+            filters_ = onlyFilters( f );
+        }
+        const SamplingParams& samplingFilters() const noexcept { return filters_; }
+        /// a new request on row `row` (0 for the one-sequence interface): every count to zero, the flag of each of the n prompt tokens set -- the WHOLE prompt, a
+        /// KV-reused prefix included.  Stream-ordered; the ids are consumed before the call returns.
+        void resetTokenTable( int row, const int32_t* prompt_host, size_t n )
+        {
+            ensureTokenTable();
+            token_table_->reset( row, prompt_host, n );
+            ctx_->synchronize();
+        }
+        /// the tables (nullptr before the first penalty or resetTokenTable())
+        Compute::RocmTokenTable* tokenTable() noexcept { return token_table_.get(); }
 
         /// capture the fused step once; afterwards replayGraph() advances one token per call.
         /// The token is read from `token` (device) and the position from an internal device counter.
@@ -265,18 +293,36 @@ namespace Mila::Dnn
                 int sampler_partials = 0;
                 captured_band_end_ = bandBucket( start_position );
                 const bool stochastic = graph_sampling_.has_value();
+                const bool penalized_greedy = sample_in_graph_ && !stochastic && filters_.penalized();      // ends at the logits; the penalized sampler's two launches follow
                 if ( stochastic && ( !draw_ring_ || !token_seq_ ) )
                     throw std::invalid_argument( "GemmaTransformer::captureGraph: a stochastic step needs setDrawRing() and the sequence counter of setTokenRing()" );
                 if ( step_lp_ && !stochastic && !sample_in_graph_ )
                     throw std::invalid_argument( "GemmaTransformer::captureGraph: token log-probabilities need a sampler in the step (setSampleInGraph / setGraphSampling)" );
-                enqueueFusedStep( token.data(), static_cast<int>( captured_band_end_ ), pos_dev_->data(), ( sample_in_graph_ && !stochastic ) ? &sampler_partials : nullptr );
+                enqueueFusedStep( token.data(), static_cast<int>( captured_band_end_ ), pos_dev_->data(), ( sample_in_graph_ && !stochastic && !penalized_greedy ) ? &sampler_partials : nullptr );
                 // stochastic: the step ends at the logits like the sampler-less one, then the radix pipeline on the model-owned workspace; its last node draws from the
                 // ring, writes the next token, bumps the position and publishes -- in the place of the advance_position node.  One linear chain on one stream.
-                if ( stochastic )
+                if ( stochastic && graph_sampling_->filtered() )      // the same launches, in their filtered instantiations: the node count does not move
+                {
+                    const mila_sample_filters f = graph_sampling_->filters();
+                    Compute::rocmCheck( mila_cdna4_sample_radix_filtered_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size,
+                                                                                       cfg_.final_logit_softcapping, graph_sampling_->temperature, graph_sampling_->top_k,
+                                                                                       graph_sampling_->top_p, draw_ring_, draw_ring_size_, &f, tableWords( *graph_sampling_, 0, false ),
+                                                                                       radix_scratch_->data(), radix_scratch_->sizeInBytes(), pos_dev_->data(), token_seq_, token_ring_,
+                                                                                       token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
+                }
+                else if ( stochastic )
                     Compute::rocmCheck( mila_cdna4_sample_radix_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping,
                                                                               graph_sampling_->temperature, graph_sampling_->top_k, graph_sampling_->top_p, draw_ring_, draw_ring_size_,
                                                                               radix_scratch_->data(), radix_scratch_->sizeInBytes(), pos_dev_->data(), token_seq_, token_ring_,
                                                                               token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
+                else if ( penalized_greedy )
+                {
+                    const mila_sample_filters f = filters_.filters();
+                    Compute::rocmCheck( mila_cdna4_sample_argmax_filtered_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size,
+                                                                                        cfg_.final_logit_softcapping, &f, tableWords( filters_, 0, false ), sample_scratch_->data(),
+                                                                                        sample_scratch_->sizeInBytes(), pos_dev_->data(), token_ring_ ? token_seq_ : nullptr, token_ring_,
+                                                                                        token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
+                }
                 else if ( sample_in_graph_ )
                     Compute::rocmCheck( mila_cdna4_sample_argmax_final_advance( const_cast<TokenTensor&>( token ).data(), sample_scratch_->data(), sample_scratch_->sizeInBytes(), sampler_partials,
                                                                                 pos_dev_->data(), token_ring_ ? token_seq_ : nullptr, token_ring_, token_ring_ ? token_ring_size_ : 0,
@@ -295,6 +341,7 @@ namespace Mila::Dnn
             captured_sample_in_graph_ = sample_in_graph_;
             captured_ring_ = token_ring_;
             captured_sampling_ = graph_sampling_;
+            captured_filters_ = filters_;
             captured_draw_ring_ = graph_sampling_ ? draw_ring_ : nullptr;
             captured_lp_ = step_lp_;
             ++graph_captures_;
@@ -307,6 +354,7 @@ namespace Mila::Dnn
         {
             if ( !graph_exec_ || captured_token_ != token.data() || captured_sample_in_graph_ != sample_in_graph_ || captured_ring_ != token_ring_ ||
                  !sameSampling( captured_sampling_, graph_sampling_ ) || ( graph_sampling_ && captured_draw_ring_ != draw_ring_ ) || captured_lp_ != step_lp_ ||
+                 ( sample_in_graph_ && !graph_sampling_ && !samePenalties( captured_filters_, filters_ ) ) ||
                  bandBucket( start_position ) != captured_band_end_ )
                 captureGraph( token, start_position );
         }
@@ -344,6 +392,8 @@ namespace Mila::Dnn
         void setGraphSampling( const std::optional<SamplingParams>& sp )
         {
             if ( sp && !( sp->temperature > 0.0f ) ) throw std::invalid_argument( "GemmaTransformer::setGraphSampling: temperature must be > 0 (greedy: setSampleInGraph)" );
+            if ( sp ) sp->checkFilters( "GemmaTransformer::setGraphSampling" );
+            if ( sp && sp->penalized() ) ensureTokenTable();      // (never inside a capture)
             graph_sampling_ = sp;
         }
         /// the uniform draws of the captured stochastic step: `size` floats of host-visible memory (device address); sample number n (the sequence counter's value after
@@ -461,16 +511,34 @@ namespace Mila::Dnn
         void setRowPosition( int b, dim_t position ) { requireRows( b ); checkPosition( position, 1 ); setRowWord( rows_->pos->data(), b, static_cast<int32_t>( position ) ); }
         /// row b's next token from row b's logits, into the rows token buffer: the greedy sampler, or the radix pipeline at the caller's draw r (the sampler
         /// generate() uses, on the model-owned one-row workspaces)
-        void sampleRowGreedy( int b )
+        void sampleRowGreedy( int b ) { sampleRowGreedyWith( b, filters_ ); }
+        void sampleRowGreedyWith( int b, const SamplingParams& fl )
         {
             requireRows( b );
+            if ( fl.penalized() )
+            {
+                const mila_sample_filters f = fl.filters();
+                Compute::rocmCheck( mila_cdna4_sample_argmax_filtered_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
+                                                                            cfg_.final_logit_softcapping, &f, tableWords( fl, b, true ), sample_scratch_->data(),
+                                                                            sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
+                return;
+            }
             Compute::rocmCheck( mila_cdna4_sample_argmax_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
                                                                sample_scratch_->data(), sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
         }
         void sampleRowStochastic( int b, const SamplingParams& sp, float r )
         {
-            if ( sp.temperature <= 0.0f ) { sampleRowGreedy( b ); return; }
+            if ( sp.temperature <= 0.0f ) { sampleRowGreedyWith( b, sp.filtered() ? sp : filters_ ); return; }
             requireRows( b );
+            if ( sp.filtered() )
+            {
+                sp.checkFilters( "GemmaTransformer::sampleRowStochastic" );
+                const mila_sample_filters f = sp.filters();
+                Compute::rocmCheck( mila_cdna4_sample_radix_filtered_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
+                                                                           cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r, &f, tableWords( sp, b, true ),
+                                                                           radix_scratch_->data(), radix_scratch_->sizeInBytes(), ctx_->getStream() ) );
+                return;
+            }
             Compute::rocmCheck( mila_cdna4_sample_radix_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
                                                               cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r, radix_scratch_->data(), radix_scratch_->sizeInBytes(),
                                                               ctx_->getStream() ) );
@@ -505,6 +573,7 @@ namespace Mila::Dnn
             if ( e != hipSuccess ) { rows_graph_exec_ = nullptr; destroyGraphRows(); hipCheck( e, "hipGraphInstantiate" ); }
             rows_captured_B_ = B; rows_captured_greedy_ = greedy; rows_captured_band_ = band;
             rows_captured_sampling_ = rows_sampling_; rows_captured_draws_ = rows_draws_;
+            rows_captured_filters_ = filters_;
             rows_captured_lp_ = step_lp_;
             ++rows_graph_captures_;
         }
@@ -512,7 +581,8 @@ namespace Mila::Dnn
         void ensureGraphRows( int B, dim_t max_position, bool greedy )
         {
             if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) || rows_captured_lp_ != step_lp_ ||
-                 ( !greedy && ( !sameSampling( rows_captured_sampling_, rows_sampling_ ) || rows_captured_draws_ != rows_draws_ ) ) )
+                 ( !greedy && ( !sameSampling( rows_captured_sampling_, rows_sampling_ ) || rows_captured_draws_ != rows_draws_ ) ) ||
+                 ( greedy && !samePenalties( rows_captured_filters_, filters_ ) ) )
                 captureGraphRows( B, max_position, greedy );
         }
         /// the stochastic sampler as the tail of a non-greedy rows step (mila_cdna4_sample_radix_rows_advance_fp32): with `sp` and `draws` set, decodeRows /
@@ -524,6 +594,8 @@ namespace Mila::Dnn
         {
             requireRows( 0 );
             if ( sp && !( sp->temperature > 0.0f ) ) throw std::invalid_argument( "GemmaTransformer::setRowsSampling: temperature must be > 0 (greedy: the greedy rows step)" );
+            if ( sp ) sp->checkFilters( "GemmaTransformer::setRowsSampling" );
+            if ( sp && sp->penalized() ) ensureTokenTable();
             rows_sampling_ = sp; rows_draws_ = draws;
         }
         void replayGraphRows()
@@ -614,6 +686,8 @@ namespace Mila::Dnn
         {
             requireChain();
             if ( sp && !( sp->temperature > 0.0f ) ) throw std::invalid_argument( "GemmaTransformer::setChainSampling: temperature must be > 0 (greedy: the greedy chain step)" );
+            // row t of a chain step would need the token table plus the drafts 1 .. t: not built; refused rather than silently unfiltered
+            if ( sp && sp->filtered() ) throw std::invalid_argument( "GemmaTransformer::setChainSampling: the chain step takes no sampling filters" );
             chain_sampling_ = sp; chain_draws_ = draws;
         }
         void replayGraphChain()
@@ -633,9 +707,18 @@ namespace Mila::Dnn
 
         /// greedy device sampler: token <- argmax(logits); the token never leaves the device
         /// (GemmaModel::enqueueSampleNext, Models/GemmaModel.ixx:568)
-        void sampleGreedy( TokenTensor& token_out )
+        void sampleGreedy( TokenTensor& token_out ) { sampleGreedyWith( token_out, filters_ ); }
+        /// ... with the penalties of `fl` (setSamplingFilters()'s by default): argmax of the adjusted logits, counted in row 0 of the token table
+        void sampleGreedyWith( TokenTensor& token_out, const SamplingParams& fl )
         {
             Compute::TraceRange tr( "gemma.sample(greedy)" );
+            if ( fl.penalized() )
+            {
+                const mila_sample_filters f = fl.filters();
+                Compute::rocmCheck( mila_cdna4_sample_argmax_filtered_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, &f,
+                                                                            tableWords( fl, 0, true ), sample_scratch_->data(), sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
+                return;
+            }
             Compute::rocmCheck( mila_cdna4_sample_argmax_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, sample_scratch_->data(),
                                                                sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
         }
@@ -655,8 +738,17 @@ namespace Mila::Dnn
         /// sampleStochastic through the radix pipeline (fewer launches, a model-owned workspace): the eager form of what a stochastic captured step ends with
         void sampleStochasticRadix( TokenTensor& token_out, const SamplingParams& sp, float r )
         {
-            if ( sp.temperature <= 0.0f ) { sampleGreedy( token_out ); return; }
+            if ( sp.temperature <= 0.0f ) { sampleGreedyWith( token_out, sp.filtered() ? sp : filters_ ); return; }
             Compute::TraceRange tr( "gemma.sample(stochastic, radix)" );
+            if ( sp.filtered() )      // the eager form of what a filtered captured step ends with
+            {
+                sp.checkFilters( "GemmaTransformer::sampleStochasticRadix" );
+                const mila_sample_filters f = sp.filters();
+                Compute::rocmCheck( mila_cdna4_sample_radix_filtered_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature, sp.top_k,
+                                                                           sp.top_p, r, &f, tableWords( sp, 0, true ), radix_scratch_->data(), radix_scratch_->sizeInBytes(),
+                                                                           ctx_->getStream() ) );
+                return;
+            }
             Compute::rocmCheck( mila_cdna4_sample_radix_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r,
                                                               radix_scratch_->data(), radix_scratch_->sizeInBytes(), ctx_->getStream() ) );
         }
@@ -1254,9 +1346,27 @@ namespace Mila::Dnn
             int partials = 0;
             if ( step_lp_ && !greedy && !rowsSamplesInStep() )
                 throw std::invalid_argument( "GemmaTransformer: token log-probabilities need a sampler tail in the rows step (greedy, or setRowsSampling)" );
-            enqueueFusedStepRows( B, static_cast<int>( band ), greedy ? &partials : nullptr );
+            const bool penalized_greedy = greedy && filters_.penalized();      // the lm_head epilogue cannot compute the adjusted logits: the step ends at the logits
+            enqueueFusedStepRows( B, static_cast<int>( band ), ( greedy && !penalized_greedy ) ? &partials : nullptr );
             auto& R = *rows_;
-            if ( !greedy && rowsSamplesInStep() )      // the radix pipeline over the B rows behind the logits; its tail takes the place of the position bump
+            if ( !greedy && rowsSamplesInStep() && rows_sampling_->filtered() )
+            {
+                const mila_sample_filters f = rows_sampling_->filters();
+                Compute::rocmCheck( mila_cdna4_sample_radix_filtered_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
+                                                                                        cfg_.final_logit_softcapping, rows_sampling_->temperature, rows_sampling_->top_k,
+                                                                                        rows_sampling_->top_p, rows_draws_, &f, tableWords( *rows_sampling_, 0, false ),
+                                                                                        static_cast<size_t>( cfg_.vocab_size ), R.radix_scratch->data(), R.radix_scratch->sizeInBytes(),
+                                                                                        R.pos->data(), R.active->data(), ctx_->getStream() ) );
+            }
+            else if ( penalized_greedy )
+            {
+                const mila_sample_filters f = filters_.filters();
+                Compute::rocmCheck( mila_cdna4_sample_argmax_filtered_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
+                                                                                         cfg_.final_logit_softcapping, &f, tableWords( filters_, 0, false ),
+                                                                                         static_cast<size_t>( cfg_.vocab_size ), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(),
+                                                                                         R.pos->data(), R.active->data(), ctx_->getStream() ) );
+            }
+            else if ( !greedy && rowsSamplesInStep() )      // the radix pipeline over the B rows behind the logits; its tail takes the place of the position bump
                 Compute::rocmCheck( mila_cdna4_sample_radix_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
                                                                                cfg_.final_logit_softcapping, rows_sampling_->temperature, rows_sampling_->top_k, rows_sampling_->top_p,
                                                                                rows_draws_, R.radix_scratch->data(), R.radix_scratch->sizeInBytes(), R.pos->data(), R.active->data(),
@@ -1274,6 +1384,7 @@ namespace Mila::Dnn
         void enqueueChainStepAndTail( int T, dim_t band, const ChainAt& at )
         {
             int partials = 0;
+            if ( filters_.penalized() ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no penalties (setSamplingFilters)" );
             const bool stochastic = chainSamples();
             enqueueFusedStepRows( T, static_cast<int>( band ), stochastic ? nullptr : &partials, &at );      // stochastic: the lm_head leaves the logits only
             auto& R = *rows_;
@@ -1669,6 +1780,7 @@ namespace Mila::Dnn
             b += tensorBytes( pos_dev_.get() );
             b += rowsStateBytes();
             if ( lp_op_ ) b += lp_op_->stateBytes();
+            if ( token_table_ ) b += token_table_->stateBytes();
             return b;
         }
         size_t requiredOwnStateBytes() const
@@ -1690,6 +1802,7 @@ namespace Mila::Dnn
             b += 4;                                                                                          // the device position word
             b += requiredRowsStateBytes();
             if ( lp_op_ ) b += lp_op_->stateBytes();                                                         // token log-probabilities, once setStepLogprobs() turned them on
+            if ( token_table_ ) b += Compute::RocmTokenTable::requiredBytes( cfg_.vocab_size, token_table_->rows() );      // the token tables, once a penalty was set
             return b;
         }
     public:
@@ -1771,10 +1884,41 @@ namespace Mila::Dnn
         };
         std::optional<StepLogprobs> step_lp_, captured_lp_, rows_captured_lp_, chain_captured_lp_;
         std::unique_ptr<Compute::RocmTokenLogprobsOp> lp_op_;
+        // sampling filters: the greedy samplers' setting, what the one-row and the rows graph were captured with, and the token tables (from the first penalty on)
+        SamplingParams filters_{}, captured_filters_{}, rows_captured_filters_{};
+        std::unique_ptr<Compute::RocmTokenTable> token_table_;
+        static SamplingParams onlyFilters( const SamplingParams& f ) noexcept
+        {
+            SamplingParams o{};
+            o.min_p = f.min_p; o.repetition_penalty = f.repetition_penalty; o.presence_penalty = f.presence_penalty; o.frequency_penalty = f.frequency_penalty;
+            return o;
+        }
+        void ensureTokenTable()
+        {
+            // one table per batch row; a draft-token model's rows are positions of ONE sequence and its chain step takes no table: row 0 alone
+            if ( !token_table_ ) token_table_ = std::make_unique<Compute::RocmTokenTable>( ctx_, cfg_.vocab_size, static_cast<int>( cfg_.max_batch > 1 ? cfg_.max_batch : 1 ) );
+        }
+        /// row `row`'s table words for a sampler with the filters `f`: nullptr without a penalty (min_p needs no table).  A capture never allocates: the setters did.
+        uint32_t* tableWords( const SamplingParams& f, int row, bool may_allocate )
+        {
+            if ( !f.penalized() ) return nullptr;
+            if ( may_allocate ) ensureTokenTable();
+            if ( !token_table_ ) throw std::logic_error( "GemmaTransformer: penalties without a token table (setSamplingFilters / setGraphSampling / setRowsSampling allocate it)" );
+            return token_table_->row( row );
+        }
+        /// what a GREEDY graph was captured for: min_p does not enter a greedy step
+        static bool samePenalties( const SamplingParams& a, const SamplingParams& b ) noexcept
+        {
+            return a.repetition_penalty == b.repetition_penalty && a.presence_penalty == b.presence_penalty && a.frequency_penalty == b.frequency_penalty;
+        }
+        static bool sameFilters( const SamplingParams& a, const SamplingParams& b ) noexcept
+        {
+            return a.min_p == b.min_p && a.repetition_penalty == b.repetition_penalty && a.presence_penalty == b.presence_penalty && a.frequency_penalty == b.frequency_penalty;
+        }
         static bool sameSampling( const std::optional<SamplingParams>& a, const std::optional<SamplingParams>& b ) noexcept
         {
             if ( a.has_value() != b.has_value() ) return false;
-            return !a || ( a->temperature == b->temperature && a->top_k == b->top_k && a->top_p == b->top_p );
+            return !a || ( a->temperature == b->temperature && a->top_k == b->top_k && a->top_p == b->top_p && sameFilters( *a, *b ) );
         }
     };
 }

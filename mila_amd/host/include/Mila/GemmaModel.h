@@ -50,7 +50,25 @@ namespace Mila::Dnn
         float temperature = 1.0f;
         int top_k = 0;        ///< 0 disables top-k truncation; 1 == greedy
         float top_p = 1.0f;   ///< 1.0 disables nucleus truncation
+        // The sampling filters (Specifications/TokenSampling.md 3.3; include/mila_cdna4.h: sampling filters), neutral by default.  The penalties read a per-request
+        // token table on the device (bit 31: the token occurs in the prompt, bits 0 .. 30: times generated) that every sampler of the request updates -- the eager
+        // first sample and the captured step alike -- so the decode-ahead loop needs no host round trip.  Greedy with a penalty = argmax of the adjusted logits.
+        float min_p = 0.0f;                 ///< [0, 1): after top-k and top-p, drop the tokens less probable than min_p x the top token's probability; 0 = off
+        float repetition_penalty = 1.0f;    ///< > 0: logits of prompt AND generated tokens divided (positive) or multiplied (negative) by it; 1 = off
+        float presence_penalty = 0.0f;      ///< subtracted from the logit of every token generated so far in this request; 0 = off
+        float frequency_penalty = 0.0f;     ///< times the number of times the token was generated, subtracted; 0 = off
+        bool penalized() const noexcept { return repetition_penalty != 1.0f || presence_penalty != 0.0f || frequency_penalty != 0.0f; }
+        bool filtered() const noexcept { return penalized() || min_p != 0.0f; }
     };
+    /// the network's SamplingParams of a request's (the same fields); throws invalid_argument for filters the device library refuses
+    template<typename TNet> typename TNet::SamplingParams networkSampling( const SamplingParams& s )
+    {
+        typename TNet::SamplingParams p;
+        p.temperature = s.temperature; p.top_k = s.top_k; p.top_p = s.top_p;
+        p.min_p = s.min_p; p.repetition_penalty = s.repetition_penalty; p.presence_penalty = s.presence_penalty; p.frequency_penalty = s.frequency_penalty;
+        p.checkFilters( "GenerateParams::sampling" );
+        return p;
+    }
     /// proposes up to k tokens that may follow `history` (prompt + emitted tokens; its last element is the token about to be decoded)
     using DraftFunction = std::function<std::vector<int32_t>( std::span<const int32_t> history, int k )>;
     /// GenerateParams::on_logprobs: the log-probability of an emitted token under the model's distribution (softmax of the soft-capped logits: no temperature, no
@@ -70,6 +88,9 @@ namespace Mila::Dnn
         std::vector<int32_t> stop_tokens{};      ///< empty => the model's default stop set
         DraftFunction draft{};                   ///< speculative decode (GemmaModelConfig::withDraftTokens): the drafter; empty => promptLookupDraft
         bool speculative_sampling = false;       ///< a STOCHASTIC request on a withDraftTokens model takes the speculative loop too (coupled draws: the plain tokens)
+        /// Sampling filters (sampling.min_p / .repetition_penalty / .presence_penalty / .frequency_penalty): a request with any of them set takes the plain loop, also
+        /// on a withDraftTokens model and whatever speculative_sampling says (row t of a chain step would need the table plus the drafts 1 .. t: a follow-up);
+        /// lastSpeculation() then reports zero chain steps.  They do not change the log-probabilities below: the samplers never touch the logits.
         /// token log-probabilities: the top-n to report (0 .. 20, 0 = the emitted token's alone); on_logprobs is then called immediately before on_token, for exactly
         /// the tokens on_token sees.  Computed on the device inside the decode step; tokens, status, generator state and prefix reuse are what they are without it.
         std::optional<int> logprobs;
@@ -356,7 +377,8 @@ namespace Mila::Dnn
             if ( params.stop_tokens.empty() ) stop_ids = stopTokens();
             else stop_ids.insert( params.stop_tokens.begin(), params.stop_tokens.end() );
             const bool greedy = isGreedy( params.sampling );
-            typename TNet::SamplingParams sp; sp.temperature = params.sampling.temperature; sp.top_k = params.sampling.top_k; sp.top_p = params.sampling.top_p;
+            const typename TNet::SamplingParams sp = networkSampling<TNet>( params.sampling );
+            net.setSamplingFilters( sp );      // the greedy rows samplers' filters: this request's, neutral ones included
             std::vector<std::mt19937_64> rng;
             for ( int b = 0; b < n; ++b ) rng.emplace_back( seed + static_cast<uint64_t>( b ) );
             auto draw = [&]( int b ) { return std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng[ static_cast<size_t>( b ) ] ); };
@@ -383,6 +405,7 @@ namespace Mila::Dnn
                 net.prefillRow( b, toks, len, 0 );
                 ctx->synchronize();
                 position[ static_cast<size_t>( b ) ] = len;
+                if ( sp.penalized() ) net.resetTokenTable( b, prompt.data(), prompt.size() );      // before the row's first sample
                 sampleRow( b );      // the first token, from the prefill's logits
                 if ( params.logprobs ) { net.enqueueRowLogprobs( b ); lp.readInto( net.tokenLogprobs(), b ); }
                 net.setRowActive( b, true );
@@ -479,8 +502,7 @@ namespace Mila::Dnn
             if ( isGreedy( sp ) ) net.sampleGreedy( *decode_token_device_ );
             else
             {
-                typename TNet::SamplingParams p; p.temperature = sp.temperature; p.top_k = sp.top_k; p.top_p = sp.top_p;
-                net.sampleStochasticRadix( *decode_token_device_, p, std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng_ ) );
+                net.sampleStochasticRadix( *decode_token_device_, networkSampling<TNet>( sp ), std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng_ ) );
             }
             Compute::rocmCheck( mila_cdna4_snapshot_token( decode_token_device_->data(), seqCounter(), ring_dev_, static_cast<int>( kSnapshots ), net.context()->getStream() ) );
             ++published_;
@@ -541,6 +563,7 @@ namespace Mila::Dnn
             for ( int32_t t : prompt )
                 if ( t < 0 || t >= vocabSize() ) throw std::invalid_argument( "GemmaModel::onGenerating: token id " + std::to_string( t ) + " outside the vocabulary" );
             checkLogprobsRequest( params, vocabSize() );
+            const typename TNet::SamplingParams net_sampling = networkSampling<TNet>( params.sampling );      // (validates the filters: nothing was enqueued yet)
             std::unordered_set<int32_t> stop_ids;
             if ( params.stop_tokens.empty() ) stop_ids = stopTokens();
             else stop_ids.insert( params.stop_tokens.begin(), params.stop_tokens.end() );
@@ -571,7 +594,12 @@ namespace Mila::Dnn
             const bool greedy = isGreedy( params.sampling );
             dim_t position = seq_len;
             last_speculation_ = SpeculationStats{};
-            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 ) return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids, greedy );
+            // the filters of this request, neutral ones included (the greedy samplers keep no other request's); with a penalty the token table starts from the WHOLE
+            // prompt -- a KV-reused prefix, whose chunks were not uploaded above, included -- before the first sample
+            net.setSamplingFilters( net_sampling );
+            if ( net_sampling.penalized() ) net.resetTokenTable( 0, prompt.data(), prompt.size() );
+            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 && !net_sampling.filtered() )
+                return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids, greedy );
             // log-probabilities travel like the tokens: every sample's record lands in slot seq % kSnapshots of a second host-visible ring, written by the two launches
             // behind the sampler -- eagerly for the first token, as the captured step's last nodes afterwards
             if ( params.logprobs )
@@ -596,8 +624,7 @@ namespace Mila::Dnn
                 if ( greedy ) net.setGraphSampling( std::nullopt );
                 else
                 {
-                    typename TNet::SamplingParams p; p.temperature = params.sampling.temperature; p.top_k = params.sampling.top_k; p.top_p = params.sampling.top_p;
-                    net.setGraphSampling( p );
+                    net.setGraphSampling( net_sampling );
                     net.setDrawRing( draws_dev_, static_cast<int>( kSnapshots ) );
                 }
                 net.ensureGraph( *decode_token_device_, position );
@@ -668,7 +695,7 @@ namespace Mila::Dnn
         {
             auto* ctx = net.context();
             const int k = static_cast<int>( net.draftTokens() );
-            typename TNet::SamplingParams sp; sp.temperature = params.sampling.temperature; sp.top_k = params.sampling.top_k; sp.top_p = params.sampling.top_p;
+            const typename TNet::SamplingParams sp = networkSampling<TNet>( params.sampling );      // (never filtered here: onGenerating sends such requests to the plain loop)
             const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
             dim_t position = static_cast<dim_t>( prompt.size() );
             std::vector<int32_t> history( prompt.begin(), prompt.end() );

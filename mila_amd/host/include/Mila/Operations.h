@@ -1148,7 +1148,77 @@ namespace Mila::Dnn::Compute
     // there; awaitToken() without an outstanding enqueueForward() is a caller bug: std::logic_error, not UB (Sampling.Cuda.cpp:503-509).
     // ---------------------------------------------------------------------------------------
     struct SamplingOpConfig { dim_t vocab_size{ 0 }; float final_logit_softcap{ 0.0f }; };
-    struct SamplingParams { float temperature{ 1.0f }; int top_k{ 0 }; float top_p{ 1.0f }; };      ///< Components/Transformers/SamplingParams.ixx: temperature <= 0 = greedy
+    /// Components/Transformers/SamplingParams.ixx: temperature <= 0 = greedy.  The four filters (Specifications/TokenSampling.md 3.3; mila_cdna4.h: sampling filters) are
+    /// neutral by default: min_p in [0, 1), repetition_penalty > 0 (1 = off), presence / frequency penalties (0 = off)
+    struct SamplingParams
+    {
+        float temperature{ 1.0f }; int top_k{ 0 }; float top_p{ 1.0f };
+        float min_p{ 0.0f }; float repetition_penalty{ 1.0f }; float presence_penalty{ 0.0f }; float frequency_penalty{ 0.0f };
+        /// any penalty set: the sampler reads and updates a token table
+        bool penalized() const noexcept { return repetition_penalty != 1.0f || presence_penalty != 0.0f || frequency_penalty != 0.0f; }
+        bool filtered() const noexcept { return penalized() || min_p != 0.0f; }
+        mila_sample_filters filters() const noexcept { return mila_sample_filters{ min_p, repetition_penalty, presence_penalty, frequency_penalty }; }
+        /// std::invalid_argument for what the device library refuses: a non-finite value, repetition_penalty <= 0, min_p outside [0, 1)
+        void checkFilters( const char* who ) const
+        {
+            if ( !std::isfinite( min_p ) || !std::isfinite( repetition_penalty ) || !std::isfinite( presence_penalty ) || !std::isfinite( frequency_penalty ) )
+                throw std::invalid_argument( std::string( who ) + ": a sampling filter is not finite" );
+            if ( !( repetition_penalty > 0.0f ) ) throw std::invalid_argument( std::string( who ) + ": repetition_penalty must be > 0" );
+            if ( !( min_p >= 0.0f && min_p < 1.0f ) ) throw std::invalid_argument( std::string( who ) + ": min_p outside [0, 1)" );
+        }
+    };
+
+    /// The token tables of 1 .. max_rows sequences (mila_cdna4.h: sampling filters -- `vocab` 32-bit words per row: bit 31 = the token occurs in the prompt, bits
+    /// 0 .. 30 = the times it has been generated).  The filtered samplers read row b's table beside the logits and count the token they choose; reset() starts a
+    /// request.  Everything runs on the context's stream; nothing synchronizes but read().
+    class RocmTokenTable
+    {
+    public:
+        RocmTokenTable( IExecutionContext* ctx, dim_t vocab, int max_rows ) : context_( cast_context<DeviceType::Rocm>( ctx ) ), vocab_( vocab ), rows_( max_rows )
+        {
+            if ( vocab <= 0 || max_rows < 1 ) throw std::invalid_argument( "RocmTokenTable: need a positive vocabulary and at least one row" );
+            (void)narrowToKernelIndex( vocab, "vocab" );
+            const auto dev = context_->getDeviceId();
+            table_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( max_rows ), vocab } );
+            stage_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( kStage ) } );
+            for ( int b = 0; b < max_rows; ++b ) clear( b );
+        }
+        uint32_t* data() { return reinterpret_cast<uint32_t*>( table_->data() ); }
+        uint32_t* row( int b ) { checkRow( b ); return data() + static_cast<size_t>( b ) * stride(); }
+        size_t stride() const noexcept { return static_cast<size_t>( vocab_ ); }
+        int rows() const noexcept { return rows_; }
+        void clear( int b )
+        {
+            checkRow( b );
+            rocmCheck( mila_cdna4_token_table_clear( data(), stride(), b, static_cast<int>( vocab_ ), context_->getStream() ) );
+        }
+        /// a new request on row b: every count to zero, the flag of every prompt token set.  The ids travel through a small device staging buffer in stream order.
+        void reset( int b, const int32_t* prompt_host, size_t n )
+        {
+            clear( b );
+            for ( size_t i0 = 0; i0 < n; i0 += kStage )
+            {
+                const size_t c = std::min<size_t>( kStage, n - i0 );
+                rocmCheck( mila_cdna4_memcpy_h2d( stage_->data(), prompt_host + i0, c * 4, context_->getStream() ) );
+                rocmCheck( mila_cdna4_token_table_mark_prompt( data(), stride(), b, static_cast<int>( vocab_ ), stage_->data(), static_cast<int>( c ), context_->getStream() ) );
+            }
+        }
+        /// row b to the host (synchronizes)
+        void read( int b, uint32_t* out )
+        {
+            rocmCheck( mila_cdna4_memcpy_d2h( out, row( b ), stride() * 4, context_->getStream() ) );
+            context_->synchronize();
+        }
+        size_t stateBytes() const { return table_->sizeInBytes() + stage_->sizeInBytes(); }
+        static size_t requiredBytes( dim_t vocab, int max_rows ) { return ( static_cast<size_t>( max_rows ) * static_cast<size_t>( vocab ) + kStage ) * 4; }
+    private:
+        static constexpr size_t kStage = 1024;
+        void checkRow( int b ) const { if ( b < 0 || b >= rows_ ) throw std::invalid_argument( "RocmTokenTable: row " + std::to_string( b ) + " outside 0 .. " + std::to_string( rows_ - 1 ) ); }
+        ExecutionContext<DeviceType::Rocm>* context_;
+        dim_t vocab_;
+        int rows_;
+        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> table_, stage_;
+    };
 
     class RocmSamplingOp : public Operation<DeviceType::Rocm, TensorDataType::FP32>
     {
@@ -1170,20 +1240,42 @@ namespace Mila::Dnn::Compute
         }
         ~RocmSamplingOp() override { if ( ring_ ) mila_cdna4_host_free_pinned( ring_ ); }
 
-        /// logits [.., vocab] -> token_out[0]; r in [0, 1) is drawn by the caller (the reference injects it the same way)
-        void forward( const LogitsTensor& logits, TokenTensor& token_out, const SamplingParams& sp, float r ) const
+        /// logits [.., vocab] -> token_out[0]; r in [0, 1) is drawn by the caller (the reference injects it the same way).  With any filter of `sp` set the call goes to
+        /// the filtered entries (mila_cdna4_sample_radix_filtered_fp32 / _sample_argmax_filtered_fp32): penalties read row `row` of `table` and the chosen token is
+        /// counted there (penalties without a table: std::invalid_argument); min_p alone needs none and leaves a greedy request as it is.
+        void forward( const LogitsTensor& logits, TokenTensor& token_out, const SamplingParams& sp, float r, RocmTokenTable* table = nullptr, int row = 0 ) const
         {
             const int V = narrowToKernelIndex( cfg_.vocab_size, "vocab" );
             if ( static_cast<dim_t>( logits.size() ) < cfg_.vocab_size ) throw std::invalid_argument( "RocmSamplingOp::forward: logits are shorter than the vocabulary" );
+            if ( sp.filtered() )
+            {
+                sp.checkFilters( "RocmSamplingOp::forward" );
+                if ( sp.penalized() && !table ) throw std::invalid_argument( "RocmSamplingOp::forward: penalties need a token table" );
+                if ( table && static_cast<dim_t>( table->stride() ) != cfg_.vocab_size ) throw std::invalid_argument( "RocmSamplingOp::forward: the token table is of another vocabulary" );
+                const mila_sample_filters f = sp.filters();
+                uint32_t* words = sp.penalized() ? table->row( row ) : nullptr;
+                if ( sp.temperature <= 0.0f || sp.top_k == 1 )
+                    rocmCheck( mila_cdna4_sample_argmax_filtered_fp32( logits.data(), token_out.data(), V, cfg_.final_logit_softcap, &f, words, scratch_->rawData(), scratch_bytes_,
+                                                                       context_->getStream() ) );
+                else
+                {
+                    // the radix pipeline's workspace: allocated by the first filtered stochastic call, so an op that never sees a filter holds what it always held
+                    if ( !radix_scratch_ )
+                        radix_scratch_ = std::make_unique<Tensor<TensorDataType::UINT8, RocmDeviceMemoryResource>>( context_->getDeviceId(), shape_t{ static_cast<dim_t>( mila_cdna4_sample_radix_scratch_bytes( V ) ) } );
+                    rocmCheck( mila_cdna4_sample_radix_filtered_fp32( logits.data(), token_out.data(), V, cfg_.final_logit_softcap, sp.temperature, sp.top_k, sp.top_p, r, &f, words,
+                                                                      radix_scratch_->rawData(), radix_scratch_->sizeInBytes(), context_->getStream() ) );
+                }
+                return;
+            }
             if ( sp.temperature <= 0.0f || sp.top_k == 1 )
                 rocmCheck( mila_cdna4_sample_argmax_fp32( logits.data(), token_out.data(), V, scratch_->rawData(), scratch_bytes_, context_->getStream() ) );
             else
                 rocmCheck( mila_cdna4_sample_stochastic_fp32( logits.data(), token_out.data(), V, cfg_.final_logit_softcap, sp.temperature, sp.top_k, sp.top_p, r, scratch_->rawData(),
                                                               scratch_bytes_, context_->getStream() ) );
         }
-        void enqueueForward( const LogitsTensor& logits, TokenTensor& token_out, const SamplingParams& sp, float r )
+        void enqueueForward( const LogitsTensor& logits, TokenTensor& token_out, const SamplingParams& sp, float r, RocmTokenTable* table = nullptr, int row = 0 )
         {
-            forward( logits, token_out, sp, r );
+            forward( logits, token_out, sp, r, table, row );
             rocmCheck( mila_cdna4_snapshot_token( token_out.data(), reinterpret_cast<unsigned long long*>( seq_dev_->rawData() ), ring_, kSlots, context_->getStream() ) );
             ++enqueued_;
         }
@@ -1206,6 +1298,7 @@ namespace Mila::Dnn::Compute
         SamplingOpConfig cfg_;
         size_t scratch_bytes_{ 0 };
         std::unique_ptr<Tensor<TensorDataType::UINT8, RocmDeviceMemoryResource>> scratch_;
+        mutable std::unique_ptr<Tensor<TensorDataType::UINT8, RocmDeviceMemoryResource>> radix_scratch_;      // filtered stochastic calls only
         std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> seq_dev_;
         unsigned long long* ring_{ nullptr };
         uint64_t enqueued_{ 0 }, awaited_{ 0 };

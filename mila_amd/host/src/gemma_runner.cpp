@@ -37,6 +37,12 @@ namespace
         std::unique_ptr<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>> seq_dev;      // one 64-bit counter
         uint64_t samples{ 0 };                                                                       // its value
         // decode_rows / chain_decode with a sampler tail: one draw per row, host-visible, allocated at the first such call
+        // the sampling filters of the step-level calls (mila_gemma_set_sampling_filters): min_p, repetition_penalty, presence_penalty, frequency_penalty
+        float filters[ 4 ]{ 0.0f, 1.0f, 0.0f, 0.0f };
+        template<typename TSp> void applyFilters( TSp& sp ) const
+        {
+            sp.min_p = filters[ 0 ]; sp.repetition_penalty = filters[ 1 ]; sp.presence_penalty = filters[ 2 ]; sp.frequency_penalty = filters[ 3 ];
+        }
         static constexpr int kStepDraws = 4;
         float* step_draws_host{ nullptr };
         const float* step_draws_dev{ nullptr };
@@ -537,6 +543,46 @@ HOST_API int mila_gemma_prefill_row( void* h, int b, const int32_t* host_tokens,
     } );
 }
 /// row b's active word, and (token >= 0) the token its next step embeds
+/// The sampling filters of the step-level calls that follow (filters[4] = min_p, repetition_penalty, presence_penalty, frequency_penalty; NULL = neutral): the greedy
+/// samplers read them from the network (GemmaTransformer::setSamplingFilters), the stochastic ones get them with their SamplingParams (generate_sampled, decode_rows_sampled,
+/// set_step_sampling for the rows step)
+HOST_API int mila_gemma_set_sampling_filters( void* h, const float* filters )
+{
+    return guarded( [&]
+    {
+        auto* r = static_cast<Runner*>( h );
+        const float neutral[ 4 ] = { 0.0f, 1.0f, 0.0f, 0.0f };
+        const float* f = filters ? filters : neutral;
+        std::visit( [&]( auto& m )
+        {
+            typename std::remove_reference_t<decltype( *m )>::SamplingParams sp;
+            sp.min_p = f[ 0 ]; sp.repetition_penalty = f[ 1 ]; sp.presence_penalty = f[ 2 ]; sp.frequency_penalty = f[ 3 ];
+            m->setSamplingFilters( sp );      // (validates; throws before the runner's copy changes)
+        }, r->model );
+        for ( int i = 0; i < 4; ++i ) r->filters[ i ] = f[ i ];
+    } );
+}
+/// a new request on row `row` (0: the one-sequence interface): the token table cleared, the flags of the n prompt tokens set
+HOST_API int mila_gemma_set_token_table( void* h, int row, const int32_t* prompt, int64_t n )
+{
+    return guarded( [&]
+    {
+        if ( n < 0 || ( n > 0 && !prompt ) ) throw std::invalid_argument( "set_token_table: null prompt" );
+        std::visit( [&]( auto& m ) { m->resetTokenTable( row, prompt, static_cast<size_t>( n ) ); }, static_cast<Runner*>( h )->model );
+    } );
+}
+/// row `row`'s table words [vocab] to the host
+HOST_API int mila_gemma_read_token_table( void* h, int row, uint32_t* out )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( !m->tokenTable() ) throw std::logic_error( "read_token_table: no token table yet (set_token_table / a penalty first)" );
+            m->tokenTable()->read( row, out );
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
 HOST_API int mila_gemma_set_active( void* h, int b, int active, int32_t token )
 {
     return guarded( [&] { std::visit( [&]( auto& m ) { m->setRowActive( b, active != 0 ); if ( token >= 0 ) m->setRowToken( b, token ); }, static_cast<Runner*>( h )->model ); } );
@@ -562,6 +608,7 @@ static int decode_rows_impl( void* h, int B, int64_t max_position, int mode, int
             if ( draws && !greedy )
             {
                 typename std::remove_reference_t<decltype( *m )>::SamplingParams sp; sp.temperature = temperature; sp.top_k = top_k; sp.top_p = top_p;
+                r->applyFilters( sp );
                 m->setRowsSampling( sp, r->stepDraws( draws, B ) );
             }
             else m->setRowsSampling( std::nullopt, nullptr );
@@ -618,6 +665,7 @@ HOST_API int mila_gemma_set_step_sampling( void* h, int which, float temperature
             std::optional<typename std::remove_reference_t<decltype( *m )>::SamplingParams> sp;
             const float* dev = nullptr;
             if ( draws ) { sp.emplace(); sp->temperature = temperature; sp->top_k = top_k; sp->top_p = top_p; dev = r->stepDraws( draws, n ); }
+            if ( sp && which == 0 ) r->applyFilters( *sp );      // (the chain step takes none)
             if ( which == 0 ) m->setRowsSampling( sp, dev ); else m->setChainSampling( sp, dev );
         }, r->model );
     } );
@@ -963,6 +1011,8 @@ HOST_API int mila_gemma_generate_sampled( void* h, int32_t first_token, int64_t 
             auto* ctx = m->context();
             typename std::remove_reference_t<decltype( *m )>::SamplingParams sp;
             sp.temperature = temperature; sp.top_k = top_k; sp.top_p = top_p;
+            r->applyFilters( sp );
+            if ( sp.filtered() && pipeline != 1 ) throw std::invalid_argument( "generate_sampled: the sampling filters need the radix pipeline" );
             if ( mode != 2 )
             {
                 for ( int i = 0; i < n_tokens; ++i )
@@ -1435,6 +1485,13 @@ HOST_API void mila_gemma_model_destroy( void* h ) { delete static_cast<RocmGemma
 /// client's stop request is raised from inside on_token once that many tokens were delivered (the std::stop_token of the reference's generate)
 /// where the *_logprobs entries collect GenerateParams::on_logprobs: entry i (of one row) goes to logprob[ i ], ids / logprobs[ i * top_n .. ), at most cap entries;
 /// top_n < 0 = the request carries no log-probabilities
+/// GenerateParams::sampling's filters from filters[4] = min_p, repetition_penalty, presence_penalty, frequency_penalty (NULL: neutral) -- the *_filtered entries below
+static void apply_request_filters( decltype( GenerateParams::sampling )& sp, const float* filters )
+{
+    if ( !filters ) return;
+    sp.min_p = filters[ 0 ]; sp.repetition_penalty = filters[ 1 ]; sp.presence_penalty = filters[ 2 ]; sp.frequency_penalty = filters[ 3 ];
+}
+
 struct LogprobSink
 {
     int top_n{ -1 };
@@ -1467,7 +1524,7 @@ struct LogprobSink
 
 static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                 float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
-                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count );
+                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters = nullptr );
 HOST_API int mila_gemma_model_generate( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                         float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
                                         int64_t cancel_after )
@@ -1484,9 +1541,19 @@ HOST_API int mila_gemma_model_generate_logprobs( void* h, const int32_t* prompt,
     return model_generate_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_count, out_status, out_reused, cancel_after,
                                 LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count );
 }
+/// mila_gemma_model_generate_logprobs with the sampling filters: filters[4] = min_p, repetition_penalty, presence_penalty, frequency_penalty; top_n < 0 = no log-probabilities
+HOST_API int mila_gemma_model_generate_filtered( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                                                 float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
+                                                 int64_t cancel_after, int top_n, float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_count,
+                                                 const float* filters )
+{
+    if ( !filters ) { g_err = "invalid_argument: gemma_model_generate_filtered: null filters"; return MILA_E_INVALID_ARGUMENT; }
+    return model_generate_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_count, out_status, out_reused, cancel_after,
+                                LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters );
+}
 static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                 float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
-                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count )
+                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters )
 {
     return guarded( [&]
     {
@@ -1498,6 +1565,7 @@ static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt
         struct Report { int64_t* out; int64_t& n; ~Report() { if ( out ) *out = n; } } report{ out_logprob_count, n_lp };
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
+        apply_request_filters( gp.sampling, filters );
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
         if ( seed >= 0 ) m->seedSampler( static_cast<uint64_t>( seed ) );
         int64_t n = 0;
@@ -1515,7 +1583,7 @@ static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt
 /// out_stats (may be NULL): GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
 static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens, int64_t cap, int64_t* out_count,
-                               int32_t* out_status, int64_t* out_stats, LogprobSink sink = LogprobSink{}, int64_t* out_logprob_count = nullptr )
+                               int32_t* out_status, int64_t* out_stats, LogprobSink sink = LogprobSink{}, int64_t* out_logprob_count = nullptr, const float* filters = nullptr )
 {
     return guarded( [&]
     {
@@ -1528,6 +1596,7 @@ static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt,
         gp.speculative_sampling = speculative_sampling != 0;
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
+        apply_request_filters( gp.sampling, filters );
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
         if ( hint && n_hint > 0 )
             gp.draft = [=]( std::span<const int32_t> history, int k )
@@ -1576,6 +1645,17 @@ HOST_API int mila_gemma_model_generate_spec_logprobs( void* h, const int32_t* pr
                                out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count );
 }
 
+/// mila_gemma_model_generate_spec_logprobs with the sampling filters (as mila_gemma_model_generate_filtered): a request with any of them set takes the plain loop
+HOST_API int mila_gemma_model_generate_spec_filtered( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                                      int top_k, float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens,
+                                                      int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_stats, int top_n, float* out_logprob, int32_t* out_ids,
+                                                      float* out_logprobs, int64_t* out_logprob_count, const float* filters )
+{
+    if ( !filters ) { g_err = "invalid_argument: gemma_model_generate_spec_filtered: null filters"; return MILA_E_INVALID_ARGUMENT; }
+    return generate_spec_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, hint, n_hint, speculative_sampling, out_tokens, cap, out_count,
+                               out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters );
+}
+
 /// GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
 HOST_API int mila_gemma_model_speculation_stats( void* h, int64_t* out )
 {
@@ -1592,7 +1672,7 @@ HOST_API int mila_gemma_model_speculation_stats( void* h, int64_t* out )
 /// generator is seeded seed + b.  Row b's tokens go to out_tokens[ b * cap .. ] (at most cap), their number to out_counts[ b ], its GenerateStatus to out_status[ b ]
 static int model_generate_rows_impl( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
                                      int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status, LogprobSink sink,
-                                     int64_t* out_logprob_counts );
+                                     int64_t* out_logprob_counts, const float* filters = nullptr );
 HOST_API int mila_gemma_model_generate_rows( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
                                              int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status )
 {
@@ -1608,9 +1688,18 @@ HOST_API int mila_gemma_model_generate_rows_logprobs( void* h, const int32_t* pr
     return model_generate_rows_impl( h, prompts, offsets, n_prompts, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_counts, out_status,
                                      LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_counts );
 }
+/// mila_gemma_model_generate_rows_logprobs with the sampling filters (as mila_gemma_model_generate_filtered), shared by the rows
+HOST_API int mila_gemma_model_generate_rows_filtered( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop,
+                                                      float temperature, int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status,
+                                                      int top_n, float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts, const float* filters )
+{
+    if ( !filters ) { g_err = "invalid_argument: gemma_model_generate_rows_filtered: null filters"; return MILA_E_INVALID_ARGUMENT; }
+    return model_generate_rows_impl( h, prompts, offsets, n_prompts, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_counts, out_status,
+                                     LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_counts, filters );
+}
 static int model_generate_rows_impl( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
                                      int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status, LogprobSink sink,
-                                     int64_t* out_logprob_counts )
+                                     int64_t* out_logprob_counts, const float* filters )
 {
     return guarded( [&]
     {
@@ -1621,6 +1710,7 @@ static int model_generate_rows_impl( void* h, const int32_t* prompts, const int6
         sink.attach( gp, [&]( int b ) -> int64_t& { return lp_counts.at( static_cast<size_t>( b ) ); } );
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
+        apply_request_filters( gp.sampling, filters );
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
         std::vector<std::vector<int32_t>> ps;
         for ( int b = 0; b < n_prompts; ++b ) ps.emplace_back( prompts + offsets[ b ], prompts + offsets[ b + 1 ] );

@@ -127,6 +127,7 @@ namespace
         std::unique_ptr<Compute::RocmSamplingOp> op;
         std::unique_ptr<Compute::RocmSamplingOp::LogitsTensor> logits;
         std::unique_ptr<Compute::RocmSamplingOp::TokenTensor> token;
+        std::unique_ptr<Compute::RocmTokenTable> table;      // from the first mila_sampler_set_token_table on
         dim_t vocab;
     };
 }
@@ -163,6 +164,45 @@ HOST_API int mila_sampler_sample( void* h, int enqueued, float temperature, int 
         if ( enqueued == 2 ) { *token_out = r->op->awaitToken(); return; }
         if ( enqueued == 1 ) { r->op->enqueueForward( *r->logits, *r->token, sp, rnd ); *token_out = r->op->awaitToken(); return; }
         r->op->forward( *r->logits, *r->token, sp, rnd );
+        Compute::rocmCheck( mila_cdna4_memcpy_d2h( token_out, r->token->rawData(), 4, ctx->getStream() ) );
+        ctx->synchronize();
+    } );
+}
+
+/// a new request: the sampler's token table cleared and the flags of the n prompt tokens set (the table is allocated by the first call)
+HOST_API int mila_sampler_set_token_table( void* h, const int32_t* prompt, int64_t n )
+{
+    auto* r = static_cast<SamplerRunner*>( h );
+    return guarded( [&]
+    {
+        if ( n < 0 || ( n > 0 && !prompt ) ) throw std::invalid_argument( "mila_sampler_set_token_table: null prompt" );
+        if ( !r->table ) r->table = std::make_unique<Compute::RocmTokenTable>( r->ctx.get(), r->vocab, 1 );
+        r->table->reset( 0, prompt, static_cast<size_t>( n ) );
+        r->ctx->synchronize();      // the prompt is the caller's buffer
+    } );
+}
+/// the table's `vocab` words to the host
+HOST_API int mila_sampler_read_token_table( void* h, uint32_t* out )
+{
+    auto* r = static_cast<SamplerRunner*>( h );
+    return guarded( [&]
+    {
+        if ( !r->table ) throw std::logic_error( "mila_sampler_read_token_table: mila_sampler_set_token_table() first" );
+        r->table->read( 0, out );
+    } );
+}
+/// mila_sampler_sample with the four filters (filters[4] = min_p, repetition_penalty, presence_penalty, frequency_penalty); penalties use the sampler's token table
+HOST_API int mila_sampler_sample_filtered( void* h, int enqueued, float temperature, int top_k, float top_p, float rnd, const float* filters, int32_t* token_out )
+{
+    auto* r = static_cast<SamplerRunner*>( h );
+    return guarded( [&]
+    {
+        Compute::SamplingParams sp{ temperature, top_k, top_p };
+        sp.min_p = filters[ 0 ]; sp.repetition_penalty = filters[ 1 ]; sp.presence_penalty = filters[ 2 ]; sp.frequency_penalty = filters[ 3 ];
+        sp.checkFilters( "mila_sampler_sample_filtered" );
+        auto* ctx = Compute::cast_context<DeviceType::Rocm>( r->ctx.get() );
+        if ( enqueued == 1 ) { r->op->enqueueForward( *r->logits, *r->token, sp, rnd, r->table.get(), 0 ); *token_out = r->op->awaitToken(); return; }
+        r->op->forward( *r->logits, *r->token, sp, rnd, r->table.get(), 0 );
         Compute::rocmCheck( mila_cdna4_memcpy_d2h( token_out, r->token->rawData(), 4, ctx->getStream() ) );
         ctx->synchronize();
     } );

@@ -30,7 +30,12 @@ def main():
     ap.add_argument("--top-k", type=int, default=64)
     ap.add_argument("--top-p", type=float, default=0.95)
     ap.add_argument("--logprobs", type=int, default=None, help="token log-probabilities (top N, 0 .. 20) in every step")
+    ap.add_argument("--min-p", type=float, default=0.0, help="sampling filter: min-p (stochastic steps)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="sampling filter: repetition penalty (every row gets a token table marked with its prompt)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0)
+    ap.add_argument("--frequency-penalty", type=float, default=0.0)
     a = ap.parse_args()
+    a.filters = dict(min_p=a.min_p, repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty, frequency_penalty=a.frequency_penalty)
     if a.stochastic:
         return stochastic(a)
     verdict = {}
@@ -38,7 +43,11 @@ def main():
         g = host.Gemma(policy, None, max_seq=a.context + a.warmup + a.steps + 8, max_prefill=a.context, seed=1234, max_batch=a.max_batch)
         rng = np.random.default_rng(0)
         for b in range(a.max_batch):
-            g.prefill_row(b, rng.integers(0, g.vocab, a.context))
+            prompt = rng.integers(0, g.vocab, a.context)
+            g.prefill_row(b, prompt)
+            if host._filters(**a.filters)[1:] != host._filters()[1:]:
+                g.set_token_table(b, prompt)
+        g.set_sampling_filters(**a.filters)      # the greedy steps below: argmax of the adjusted logits when a penalty is set
         g.set_step_logprobs(a.logprobs)
         agg = {}
         for B in range(1, a.max_batch + 1):
@@ -49,7 +58,7 @@ def main():
             med = statistics.median(ms)
             agg[B] = B * 1000.0 / med
             print(json.dumps({"policy": policy, "B": B, "ms_per_step": [round(v, 4) for v in ms], "median_ms_per_step": round(med, 4), "aggregate_tok_s": round(agg[B], 1),
-                              "vs_B1": round(agg[B] / agg[1], 3), "context": a.context, "steps": a.steps, "logprobs": a.logprobs}), flush=True)
+                              "vs_B1": round(agg[B] / agg[1], 3), "context": a.context, "steps": a.steps, "logprobs": a.logprobs, "filters": a.filters}), flush=True)
         verdict[policy] = {"B2_exceeds_B1": agg.get(2, 0) > agg[1], "best_B": max(agg, key=agg.get)}
         g.close()
     print(json.dumps({"rows_worth_dispatching": verdict}), flush=True)
@@ -65,7 +74,7 @@ def stochastic(a):
         for B in range(2, a.max_batch + 1):
             def run(n, seed):
                 t0 = time.perf_counter()
-                got = m.generate_batch(prompts[:B], max_new_tokens=n, seed=seed, logprobs=a.logprobs, **req)
+                got = m.generate_batch(prompts[:B], max_new_tokens=n, seed=seed, logprobs=a.logprobs, **req, **a.filters)
                 return time.perf_counter() - t0, min(len(g[0]) for g in got)
             run(a.warmup + 1, 1)
             ms = []
@@ -77,7 +86,7 @@ def stochastic(a):
             med = statistics.median(ms)
             print(json.dumps({"policy": policy, "mode": "stochastic generate_batch", "B": B, "ms_per_step": [round(v, 4) for v in ms], "median_ms_per_step": round(med, 4),
                               "spread_us": round(1000 * (max(ms) - min(ms)), 1), "aggregate_tok_s": round(B * 1000.0 / med, 1), "context": a.context, "steps": a.steps,
-                              "sampling": [a.temperature, a.top_k, a.top_p], "logprobs": a.logprobs}), flush=True)
+                              "sampling": [a.temperature, a.top_k, a.top_p], "logprobs": a.logprobs, "filters": a.filters}), flush=True)
         m.close()
 
 
