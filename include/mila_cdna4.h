@@ -748,6 +748,33 @@ MILA_API int mila_cdna4_token_logprobs_publish_fp32(const float* logits, const i
                                                     mila_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Prompt log-probabilities (ABI 4, additive; csrc/lm_head_score.hip): the lm_head over MANY rows -- a prefill chunk -- as a matrix-core GEMM whose epilogue keeps the
+ * softmax statistics and never stores a logit (fp32 logits of a 2048-row chunk would be 2 GB).  For row r, with t = targets_dev[r]:
+ *     y_i = sum_k x[r,k] * W[i,k]     accumulated in fp32 on the matrix cores.  fmt 1: the e4m3 byte enters as its exact bf16 value and scales[i] multiplies ONCE after
+ *                                     the reduction -- matvec_f32out's arithmetic, so a prompt position scores with the arithmetic the decode head would have used
+ *                                     (not the prefill GEMM's bf16(decode * scale))
+ *     z_i = softcap > 0 ? softcap * tanhf(y_i / softcap) : y_i,   m = max z,   S = sum expf(z_i - m)
+ *     logprob_out[r] = (z_t - m) - logf(S); a target outside [0, vocab) reports NaN and reads nothing (-1 = "no target")
+ *     argmax_out[r] = the index of the largest z, the LOWEST index among equals (the greedy sampler's tie rule); argmax_logprob_out[r] = its log-probability.  The two
+ *     may both be NULL.  When the target is the argmax the two log-probabilities carry the same bits.
+ *   x: `rows` normed hidden rows, bf16, x_stride elements apart.  W: the [vocab, K] table; fmt 0 = bf16, 1 = e4m3 with scales[vocab].
+ * Two launches.  Partials: one workgroup owns a block of 128 rows and a SLAB of the vocabulary, walks it 128 columns at a time through a 128 x 128 x 64 K loop, and
+ * leaves one 32-byte record per (row, slab) in scratch: (max, sum exp rescaled to that max, best z, best index, the target's z).  Final: one wave per row merges the
+ * records in ascending slab order, rescaled to the global max.  No floating-point atomics, every sum has a fixed order: the same bits run to run.
+ * THE SLAB RULE looks at vocab alone: with tiles = ceil(vocab / 128), a slab is ceil(tiles / 256) tiles, so there are at most 256 slabs -- 262144 entries: 1024 columns
+ * per slab, 256 slabs, so a call of a few rows still occupies every CU and scratch stays at 32 bytes per (row, slab).
+ * ROW INVARIANCE: row r's three outputs are, bit for bit, those of a rows = 1 call on that row alone, whatever the other rows hold, however many there are and wherever
+ * r sits in the call (padded rows are zero-filled; neither the tile shape nor the slab rule looks at rows).
+ *   scratch: lm_head_score_scratch_bytes(rows, vocab) = rows * slabs * 32 bytes, 16-byte aligned; 0 for rows < 1 or vocab < 1.
+ * Refused before any device work: a null x, W, targets_dev or logprob_out, exactly one of the two argmax pointers, fmt outside {0, 1}, fmt 1 without scales, rows < 1,
+ * vocab < 1, K no multiple of 8 (bf16) or 16 (e4m3), x_stride < K, a misaligned scratch (MILA_E_INVALID_ARGUMENT); a scratch that is too small
+ * (MILA_E_SCRATCH_TOO_SMALL). */
+MILA_API size_t mila_cdna4_lm_head_score_scratch_bytes(int rows, int vocab);
+MILA_API int mila_cdna4_lm_head_score_bf16(const uint16_t* x, size_t x_stride, const void* W, const float* scales, int fmt, int K, int vocab,
+                                           const int32_t* targets_dev, int rows, float softcap, float* logprob_out, int32_t* argmax_out,
+                                           float* argmax_logprob_out, void* scratch, size_t scratch_bytes, mila_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sampling filters (ABI 4, additive; csrc/sampling.hip): repetition, presence and frequency penalties and min-p, as filters over the samplers above.  The reference's
  * sampling specification (Specifications/TokenSampling.md 3.3, 4.2) names "top-k, top-p, min-p, and repetition penalty" as composable filters over one sampler and
  * pencils them into GenerateParams; the reference has NO kernel for them yet, so these entries anticipate that surface and replace no launcher.

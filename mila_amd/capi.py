@@ -124,6 +124,10 @@ def load():
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
     main.mila_cdna4_token_logprobs_rows_fp32.argtypes = [p, z, p, i, i, f, i, p, p, p, p, p, p, z, p]             # logits logits_stride tokens_dev | rows vocab softcap top_n | active_dev count_dev | logprob_out top_ids_out top_logprobs_out | scratch bytes
     main.mila_cdna4_token_logprobs_publish_fp32.argtypes = [p, p, i, f, i, p, p, i, p, z, p]                      # logits token_dev | vocab softcap top_n | seq_dev ring ring_size | scratch bytes
+    # prompt log-probabilities (csrc/lm_head_score.hip)
+    main.mila_cdna4_lm_head_score_scratch_bytes.argtypes = [i, i]                                                 # rows vocab
+    main.mila_cdna4_lm_head_score_scratch_bytes.restype = z
+    main.mila_cdna4_lm_head_score_bf16.argtypes = [p, z, p, p, i, i, i, p, i, f, p, p, p, p, z, p]                # x x_stride W scales fmt | K vocab | targets_dev rows softcap | logprob_out argmax_out argmax_logprob_out | scratch bytes
     main.mila_cdna4_kv_dequant_fp8_bf16.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, p]                        # Kc Vc K8 V8 Ks Vs | B NKV HS capacity first_pos count
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.argtypes = [i, i, i, i]                                      # B NKV HS capacity
     main.mila_cdna4_attn_prefill_kvfp8_scratch_bytes.restype = z
@@ -444,6 +448,33 @@ def token_logprobs_publish(logits, token_dev, softcap, top_n, seq_dev, ring, scr
          int(ring.numel() // words) if ring_size is None else int(ring_size), scratch, C.c_size_t(scratch.numel() * scratch.element_size()))
 
 
+LM_HEAD_SCORE_TILE = 128
+LM_HEAD_SCORE_MAX_SLABS = 256
+
+
+def lm_head_score_slab(vocab):
+    """the slab rule of lm_head_score (include/mila_cdna4.h), restated: vocabulary columns per slab -- a function of vocab alone"""
+    tiles = -(-int(vocab) // LM_HEAD_SCORE_TILE)
+    return LM_HEAD_SCORE_TILE * -(-tiles // LM_HEAD_SCORE_MAX_SLABS)
+
+
+def lm_head_score_scratch_bytes(rows, vocab):
+    return int(load().mila_cdna4_lm_head_score_scratch_bytes(int(rows), int(vocab)))
+
+
+def lm_head_score(x, W, scales, targets_dev, softcap, logprob_out, argmax_out=None, argmax_logprob_out=None, scratch=None, rows=None):
+    """logprob_out[r] <- log-probability of targets_dev[r] under softmax(softcap(x[r] @ W^T)); x [rows, K] bf16 (any row stride), W [vocab, K] bf16, or e4m3 bytes with
+    per-row `scales`; argmax_out / argmax_logprob_out (both or neither) <- the greedy token and its log-probability.  No logits are stored."""
+    rows = int(x.shape[0]) if rows is None else int(rows)
+    K, V = int(x.shape[1]), int(W.shape[0])
+    if scratch is None:
+        import torch
+        scratch = torch.empty(max(lm_head_score_scratch_bytes(rows, V), 16), dtype=torch.uint8, device=x.device)
+    assert x.stride(1) == 1
+    call("lm_head_score_bf16", C.c_void_p(x.data_ptr()), C.c_size_t(int(x.stride(0))), W, scales, 0 if scales is None else 1, K, V, targets_dev, rows, float(softcap), logprob_out, argmax_out,
+         argmax_logprob_out, scratch, C.c_size_t(scratch.numel() * scratch.element_size()))
+
+
 def prefill_form_name(plan, HS):
     """what last_form() reports for a launch from this plan: the form and its instantiation"""
     return plan["form"] if plan["form"] == "attn_generic" else "%s_hs%d_hb%d_ds%d_nw%d" % (plan["form"], HS, plan["HB"], plan["DS"], plan["NW"])
@@ -507,6 +538,7 @@ EXPORTED = [
     "fused_attn_decode_chain_bf16", "attn_decode_chain_scratch_bytes", "fused_qkv_post_rows_devpos", "sample_argmax_chain_accept",
     "sample_radix_rows_scratch_bytes", "sample_radix_rows_fp32", "sample_radix_rows_advance_fp32", "sample_radix_chain_accept_fp32",
     "token_logprobs_record_words", "token_logprobs_scratch_bytes", "token_logprobs_rows_fp32", "token_logprobs_publish_fp32",
+    "lm_head_score_scratch_bytes", "lm_head_score_bf16",
     "token_table_bytes", "token_table_clear", "token_table_mark_prompt", "sample_filters_describe",
     "sample_radix_filtered_fp32", "sample_radix_filtered_advance_fp32", "sample_radix_filtered_rows_fp32", "sample_radix_filtered_rows_advance_fp32",
     "sample_argmax_filtered_fp32", "sample_argmax_filtered_advance_fp32", "sample_argmax_filtered_rows_advance_fp32",

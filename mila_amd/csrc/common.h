@@ -159,6 +159,23 @@ __device__ __forceinline__ float wave_max(float v)
     }
     return v;
 }
+// integer 64-lane minimum by the same butterfly (all lanes get the result; all 64 lanes must be active)
+__device__ __forceinline__ int wave_min_i32(int v)
+{
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true));     // quad_perm [1,0,3,2]
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true));     // quad_perm [2,3,0,1]
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, true));    // row_half_mirror
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, true));    // row_mirror
+    {
+        const auto r = __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false);
+        v = min((int)r[0], (int)r[1]);
+    }
+    {
+        const auto r = __builtin_amdgcn_permlane32_swap((uint32_t)v, (uint32_t)v, false, false);
+        v = min((int)r[0], (int)r[1]);
+    }
+    return v;
+}
 // reference implementation through the LDS crossbar (tests compare the two)
 __device__ __forceinline__ float wave_sum_shfl(float v)
 {

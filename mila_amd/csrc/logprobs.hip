@@ -54,26 +54,10 @@ __device__ __forceinline__ bool lp_behind(float v, int i, float pv, int pi) { re
 
 // the best (z, index) pair of a wave, on every lane: the largest value, then the lowest index among the lanes that hold it -- two register-only butterflies
 // (wave_max's DPP / permlane steps) instead of twelve LDS-crossbar shuffles.  All 64 lanes must be active.
-__device__ __forceinline__ int lp_wave_min_i32(int v)
-{
-    v = min(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true));     // quad_perm [1,0,3,2]
-    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true));     // quad_perm [2,3,0,1]
-    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, true));    // row_half_mirror
-    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, true));    // row_mirror
-    {
-        const auto r = __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false);
-        v = min((int)r[0], (int)r[1]);
-    }
-    {
-        const auto r = __builtin_amdgcn_permlane32_swap((uint32_t)v, (uint32_t)v, false, false);
-        v = min((int)r[0], (int)r[1]);
-    }
-    return v;
-}
 __device__ __forceinline__ void lp_wave_argmax(float& bv, int& bi)
 {
     const float m = wave_max(bv);
-    bi = lp_wave_min_i32(bv == m ? bi : kLpNone);
+    bi = wave_min_i32(bv == m ? bi : kLpNone);
     bv = m;
 }
 

@@ -251,6 +251,37 @@ class Gemma:
         _check(load().mila_gemma_prefill(self.h, t.ctypes.data, t.size, position_offset, out.ctypes.data))
         return out
 
+    def prefill_scored(self, tokens, targets, position_offset=0, first_row=0, argmax=True):
+        """prefill() that also scores the chunk (GemmaTransformer::prefillScored): targets[r] = the token whose log-probability row r reports (one per row of the
+        chunk, the last included; -1 = none: NaN).  Returns (logits of the last row as prefill() returns them, logprob [T - first_row], argmax, argmax_logprob) --
+        the last two None without argmax.  The logits of the scored rows are never formed."""
+        lib = load()
+        lib.mila_gemma_prefill_scored.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        if tg.size != t.size:
+            raise ValueError("prefill_scored: one target per token of the chunk")
+        n = max(int(t.size) - int(first_row), 0)
+        out = np.empty(self.vocab, dtype=np.float32)
+        lp = np.empty(n, dtype=np.float32)
+        am = np.empty(n, dtype=np.int32) if argmax else None
+        alp = np.empty(n, dtype=np.float32) if argmax else None
+        _check(lib.mila_gemma_prefill_scored(self.h, t.ctypes.data, t.size, int(position_offset), tg.ctypes.data, int(first_row), lp.ctypes.data,
+                                             am.ctypes.data if argmax else None, alp.ctypes.data if argmax else None, out.ctypes.data))
+        return out, lp, am, alp
+
+    def time_score(self, T, reps=1, first_row=0):
+        """device ms of one prefillScored() of T tokens with rows [first_row, T) scored (time_prefill's shape)"""
+        lib = load()
+        lib.mila_gemma_time_score.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+        lib.mila_gemma_time_score_from.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+        out = C.c_double()
+        if first_row:
+            _check(lib.mila_gemma_time_score_from(self.h, int(T), int(first_row), int(reps), C.byref(out)))
+        else:
+            _check(lib.mila_gemma_time_score(self.h, int(T), int(reps), C.byref(out)))
+        return out.value
+
     def decode(self, token, position, mode="fused", logprobs=None):
         """one decode step; the logits.  logprobs = n (0 .. 20): the step is followed by the greedy sampler and the token log-probability launches (in graph mode
         they are the captured step's tail), and the call returns (logits, token, logprob, top_ids [n], top_logprobs [n]) -- the greedy token of these logits, its
@@ -605,6 +636,26 @@ class GemmaModel:
         if not h:
             cls._raise(lib, "GemmaModel.synthetic")
         return cls(h, device)
+
+    def score(self, tokens, first=1, argmax=False):
+        """GemmaModel::score: the log-probability of every token first .. n - 1 given the tokens before it, from the prefill (chunked by the model's prefill chunk,
+        with KV prefix reuse up to first - 1).  Returns a dict: logprob [n - first] float32, sum (float64, summed on the host), reused_prefix, and with argmax the
+        greedy token of every scored position and its log-probability (argmax, argmax_logprob).  ValueError for what the model refuses before anything is enqueued."""
+        lib = load()
+        lib.mila_gemma_model_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        n = max(int(t.size) - int(first), 0) if int(first) >= 1 else 0
+        lp = np.empty(n, dtype=np.float32)
+        am = np.empty(n, dtype=np.int32) if argmax else None
+        alp = np.empty(n, dtype=np.float32) if argmax else None
+        total, reused = C.c_double(), C.c_int64()
+        if lib.mila_gemma_model_score(self.h, t.ctypes.data, t.size, int(first), lp.ctypes.data, am.ctypes.data if argmax else None, alp.ctypes.data if argmax else None,
+                                      C.byref(total), C.byref(reused)) != 0:
+            self._raise(lib, "GemmaModel.score")
+        out = {"logprob": lp, "sum": total.value, "reused_prefix": int(reused.value)}
+        if argmax:
+            out["argmax"], out["argmax_logprob"] = am, alp
+        return out
 
     def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
                  speculative_sampling=False, logprobs=None, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):

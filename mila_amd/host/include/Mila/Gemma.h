@@ -762,6 +762,50 @@ namespace Mila::Dnn
             if ( T <= 0 || T > max_prefill_ ) throw std::invalid_argument( "GemmaTransformer::prefill: chunk length out of range" );
             Compute::TraceRange tr( "gemma.prefill" );
             checkPosition( position_offset, T );
+            return prefillTail( *prefillBlocks( tokens, T, position_offset ), T );
+        }
+
+        /// prefill() that also SCORES the chunk: after the same blocks (every route, the FP8 KV cache, the bounded local KV, any cache row) the final norm runs over
+        /// rows [first_row, T) of the last block's output and the scoring lm_head (RocmLmHeadScoreOp) over them: row r reports the log-probability of targets_dev[ r ]
+        /// (one device word per row of the chunk, -1 = none) and, with argmax, the greedy token and its log-probability; read them with scoreOp().read( T - first_row, .. ).
+        /// The last row's logits are left in logits() as prefill() leaves them.  Nothing synchronizes.
+        LogitsTensor& prefillScored( const TokenTensor& tokens, dim_t T, dim_t position_offset, const int32_t* targets_dev, dim_t first_row = 0, bool argmax = true )
+        {
+            if ( T <= 0 || T > max_prefill_ ) throw std::invalid_argument( "GemmaTransformer::prefillScored: chunk length out of range" );
+            if ( first_row < 0 || first_row >= T ) throw std::invalid_argument( "GemmaTransformer::prefillScored: first_row outside the chunk" );
+            if ( !targets_dev ) throw std::invalid_argument( "GemmaTransformer::prefillScored: targets are required" );
+            Compute::TraceRange tr( "gemma.prefill_scored" );
+            checkPosition( position_offset, T );
+            TensorType& x = *prefillBlocks( tokens, T, position_offset );
+            const dim_t D = cfg_.embedding_dim, rows = T - first_row;
+            if ( !score_op_ )
+                score_op_ = std::make_unique<Compute::RocmLmHeadScoreOp>( ctx_, Compute::LmHeadScoreOpConfig{ cfg_.vocab_size, D, cfg_.final_logit_softcapping, max_prefill_ } );
+            // pf_norm_ is free once the last block has run (the tails write the NEXT block's input norm there)
+            final_norm_->getOperation().forwardRows( x.data() + static_cast<size_t>( first_row * D ), pf_norm_->data(), static_cast<int>( rows ) );
+            const float* sc = nullptr;
+            if constexpr ( kTableFmt != 0 ) sc = lm_head_->getWeightScale()->data();
+            score_op_->forward( pf_norm_->data(), static_cast<size_t>( D ), lm_head_->getWeight().rawData(), sc, kTableFmt, targets_dev + first_row, rows, argmax );
+            return prefillTail( x, T );
+        }
+        Compute::RocmLmHeadScoreOp& scoreOp()
+        {
+            if ( !score_op_ ) throw std::logic_error( "GemmaTransformer::scoreOp: prefillScored() first" );
+            return *score_op_;
+        }
+
+    private:
+        /// the tail every prefill route shares: the final norm of the chunk's last row and the lm_head on it
+        LogitsTensor& prefillTail( TensorType& x, dim_t T )
+        {
+            const dim_t D = cfg_.embedding_dim;
+            auto last = x.slice( static_cast<size_t>( ( T - 1 ) * D ), shape_t{ 1, 1, D } );
+            auto& normed = final_norm_->forward( last );
+            head( normed.data() );
+            return *logits_;
+        }
+        /// the blocks of a prefill chunk by the route prefill() takes; the last block's output [T, D]
+        TensorType* prefillBlocks( const TokenTensor& tokens, dim_t T, dim_t position_offset )
+        {
             kv_fill_ = position_offset + T;
             const dim_t D = cfg_.embedding_dim;
             embed( tokens.data(), static_cast<int>( T ), *pf_x_[ 0 ] );
@@ -782,11 +826,9 @@ namespace Mila::Dnn
                 x = r.out;
                 flip = 1 - flip;
             }
-            auto last = x->slice( static_cast<size_t>( ( T - 1 ) * D ), shape_t{ 1, 1, D } );
-            auto& normed = final_norm_->forward( last );
-            head( normed.data() );
-            return *logits_;
+            return x;
         }
+    public:
 
         /// algorithmic bytes one decode token must read: weights + scales + norm weights + KV band
         double decodeBytesPerToken( dim_t context ) const
@@ -1094,7 +1136,7 @@ namespace Mila::Dnn
                         return false;
             return true;
         }
-        LogitsTensor& prefillOverlapped( const TokenTensor& tokens, dim_t T, dim_t position_offset )
+        TensorType* prefillOverlapped( const TokenTensor& tokens, dim_t T, dim_t position_offset )
         {
             const dim_t D = cfg_.embedding_dim;
             const int H = static_cast<int>( T / 2 );
@@ -1134,10 +1176,7 @@ namespace Mila::Dnn
             }
             hipCheck( hipEventRecord( ov_ev_[ 7 ], ov_stream_ ), "hipEventRecord" );
             hipCheck( hipStreamWaitEvent( main, ov_ev_[ 7 ], 0 ), "hipStreamWaitEvent" );
-            auto last = pf_x_[ flip ]->slice( static_cast<size_t>( ( T - 1 ) * D ), shape_t{ 1, 1, D } );
-            auto& normed = final_norm_->forward( last );
-            head( normed.data() );
-            return *logits_;
+            return pf_x_[ flip ].get();
         }
 
     public:
@@ -1780,6 +1819,7 @@ namespace Mila::Dnn
             b += tensorBytes( pos_dev_.get() );
             b += rowsStateBytes();
             if ( lp_op_ ) b += lp_op_->stateBytes();
+            if ( score_op_ ) b += score_op_->stateBytes();
             if ( token_table_ ) b += token_table_->stateBytes();
             return b;
         }
@@ -1802,6 +1842,7 @@ namespace Mila::Dnn
             b += 4;                                                                                          // the device position word
             b += requiredRowsStateBytes();
             if ( lp_op_ ) b += lp_op_->stateBytes();                                                         // token log-probabilities, once setStepLogprobs() turned them on
+            if ( score_op_ ) b += score_op_->stateBytes();                                                   // prompt log-probabilities, once prefillScored() has run
             if ( token_table_ ) b += Compute::RocmTokenTable::requiredBytes( cfg_.vocab_size, token_table_->rows() );      // the token tables, once a penalty was set
             return b;
         }
@@ -1884,6 +1925,7 @@ namespace Mila::Dnn
         };
         std::optional<StepLogprobs> step_lp_, captured_lp_, rows_captured_lp_, chain_captured_lp_;
         std::unique_ptr<Compute::RocmTokenLogprobsOp> lp_op_;
+        std::unique_ptr<Compute::RocmLmHeadScoreOp> score_op_;
         // sampling filters: the greedy samplers' setting, what the one-row and the rows graph were captured with, and the token tables (from the first penalty on)
         SamplingParams filters_{}, captured_filters_{}, rows_captured_filters_{};
         std::unique_ptr<Compute::RocmTokenTable> token_table_;

@@ -159,6 +159,13 @@ namespace Mila::Dnn
         }
         return {};
     }
+    /// score(): `first` = the first token that is scored (1 .. n - 1; positions below first - 1 need no head); argmax = also report the greedy token of every scored
+    /// position and its log-probability
+    struct ScoreParams { dim_t first{ 1 }; bool argmax{ false }; };
+    /// one entry per scored token first .. n - 1: entry j = log P( token first + j | tokens before it ); argmax / argmax_logprob are empty without ScoreParams::argmax;
+    /// sum = the float64 sum of logprob on the host
+    struct ScoreResult { std::vector<float> logprob; std::vector<int32_t> argmax; std::vector<float> argmax_logprob; double sum{ 0.0 }; };
+
     /// what the last speculative generate() of a withDraftTokens model did (greedy, or stochastic with GenerateParams::speculative_sampling): decode steps in all,
     /// those that were chain steps, the drafter's tokens those carried (padding not counted) and how many of them were accepted
     struct SpeculationStats { uint64_t steps = 0, chain_steps = 0, drafted = 0, accepted = 0; };
@@ -329,6 +336,28 @@ namespace Mila::Dnn
                 {
                     // a replay may still be in flight (awaitSampledToken's timeout, a throwing on_token): drain it before the caller sees the exception,
                     // and drop the reuse key -- what the in-flight step wrote is not in the history
+                    try { net->context()->synchronize(); } catch ( ... ) {}
+                    kv_token_history_.clear();
+                    throw;
+                }
+            }, network_ );
+        }
+
+        /// Score a token sequence: the log-probability of every token first .. n - 1 given the tokens before it, from the prefill itself (GemmaTransformer::
+        /// prefillScored: the logits are never formed).  Chunked by the model's prefill chunk: the target of a chunk's last row is the next chunk's first token; the
+        /// sequence's last row has no target and is not scored.  KV prefix reuse as generate()'s, except that positions below first - 1 need no head, so
+        /// reuse = min( common prefix with kvTokenHistory(), first - 1 ): scoring many continuations of one context prefills the context once.  Afterwards the history
+        /// holds all n tokens: a generate() on the same tokens re-prefills only the last position (echo = score() + generate() at the cost of one prefill).
+        /// Failures as generate()'s: invalid_argument before anything is enqueued (n < 2, n beyond the context length, first outside 1 .. n - 1, a token id outside
+        /// the vocabulary); anything else drains the stream and clears the history.
+        [[nodiscard]] ScoreResult score( std::span<const int32_t> tokens, const ScoreParams& params = {} )
+        {
+            return std::visit( [&]( auto& net )
+            {
+                try { return onScoring( *net, tokens, params ); }
+                catch ( const std::invalid_argument& ) { throw; }
+                catch ( ... )
+                {
                     try { net->context()->synchronize(); } catch ( ... ) {}
                     kv_token_history_.clear();
                     throw;
@@ -551,6 +580,61 @@ namespace Mila::Dnn
             std::memcpy( lp.logprob, rec + 2, 4 );
             std::memcpy( lp.top_ids, rec + 4, static_cast<size_t>( lp.top_n ) * 4 );
             std::memcpy( lp.top_logprobs, rec + 4 + TokenLogprobsRows::kMaxTop, static_cast<size_t>( lp.top_n ) * 4 );
+        }
+
+        template<typename TNet>
+        ScoreResult onScoring( TNet& net, std::span<const int32_t> tokens, const ScoreParams& params )
+        {
+            Compute::TraceRange tr( "GemmaModel.score" );
+            const dim_t n = static_cast<dim_t>( tokens.size() );
+            if ( n < 2 ) throw std::invalid_argument( "GemmaModel::score: at least two tokens (a context and a token to score)" );
+            if ( n > contextLength() ) throw std::invalid_argument( "GemmaModel::score: " + std::to_string( n ) + " tokens exceed deployment context length " + std::to_string( contextLength() ) );
+            if ( params.first < 1 || params.first > n - 1 ) throw std::invalid_argument( "GemmaModel::score: first " + std::to_string( params.first ) + " outside 1 .. " + std::to_string( n - 1 ) );
+            for ( int32_t t : tokens )
+                if ( t < 0 || t >= vocabSize() ) throw std::invalid_argument( "GemmaModel::score: token id " + std::to_string( t ) + " outside the vocabulary" );
+
+            dim_t common = 0;
+            const dim_t comparable = std::min<dim_t>( n, static_cast<dim_t>( kv_token_history_.size() ) );
+            while ( common < comparable && kv_token_history_[ static_cast<size_t>( common ) ] == tokens[ static_cast<size_t>( common ) ] ) ++common;
+            dim_t reuse = std::min( common, params.first - 1 );      // position first - 1 is the first one whose head is needed
+            if ( reuse > 0 && !net.rewindKvCache( reuse, static_cast<dim_t>( kv_token_history_.size() ) ) ) reuse = 0;
+            last_reuse_ = reuse;
+            const dim_t chunk = model_config_.getPrefillChunk();
+            auto* ctx = net.context();
+            if ( !score_targets_dev_ ) score_targets_dev_ = std::make_unique<TokenTensor>( ctx->getDeviceId(), shape_t{ 1, chunk } );
+            ScoreResult out;
+            const size_t entries = static_cast<size_t>( n - params.first );
+            out.logprob.reserve( entries );
+            if ( params.argmax ) { out.argmax.reserve( entries ); out.argmax_logprob.reserve( entries ); }
+            std::vector<int32_t> targets( static_cast<size_t>( chunk ) );
+            kv_token_history_.resize( static_cast<size_t>( reuse ) );
+            for ( dim_t p0 = reuse; p0 < n; p0 += chunk )
+            {
+                const dim_t c = std::min( chunk, n - p0 );
+                Compute::rocmCheck( mila_cdna4_memcpy_h2d( prompt_dev_->rawData(), tokens.data() + p0, static_cast<size_t>( c ) * 4, ctx->getStream() ) );
+                // positions lo .. hi - 1 of this chunk are scored: position p reports token p + 1
+                const dim_t lo = std::max( p0, params.first - 1 ), hi = std::min( p0 + c, n - 1 );
+                if ( lo >= hi ) net.prefill( *prompt_dev_, c, p0 );
+                else
+                {
+                    for ( dim_t r = 0; r < c; ++r ) targets[ static_cast<size_t>( r ) ] = p0 + r + 1 < n ? tokens[ static_cast<size_t>( p0 + r + 1 ) ] : -1;
+                    Compute::rocmCheck( mila_cdna4_memcpy_h2d( score_targets_dev_->rawData(), targets.data(), static_cast<size_t>( c ) * 4, ctx->getStream() ) );
+                    net.prefillScored( *prompt_dev_, c, p0, score_targets_dev_->data(), lo - p0, params.argmax );
+                    const size_t at = out.logprob.size(), m = static_cast<size_t>( hi - lo );
+                    // rows lo - p0 .. of the chunk were scored; the sequence's last row (no target) is read into the spare slot and dropped
+                    const size_t rows = static_cast<size_t>( p0 + c - lo );
+                    out.logprob.resize( at + rows );
+                    if ( params.argmax ) { out.argmax.resize( at + rows ); out.argmax_logprob.resize( at + rows ); }
+                    net.scoreOp().read( static_cast<dim_t>( rows ), out.logprob.data() + at, params.argmax ? out.argmax.data() + at : nullptr,
+                                        params.argmax ? out.argmax_logprob.data() + at : nullptr );
+                    out.logprob.resize( at + m );
+                    if ( params.argmax ) { out.argmax.resize( at + m ); out.argmax_logprob.resize( at + m ); }
+                }
+                ctx->synchronize();       // prompt_dev_ and the targets are reused by the next chunk
+                kv_token_history_.insert( kv_token_history_.end(), tokens.begin() + p0, tokens.begin() + p0 + c );
+            }
+            for ( float v : out.logprob ) out.sum += static_cast<double>( v );
+            return out;
         }
 
         template<typename TNet>
@@ -817,6 +901,7 @@ namespace Mila::Dnn
         GemmaModelConfig model_config_;
         Serialization::PretrainedMetadata source_metadata_;
         std::unique_ptr<TokenTensor> prompt_dev_, decode_token_device_, seq_dev_;
+        std::unique_ptr<TokenTensor> score_targets_dev_;      // the targets of a scored chunk, from the first score() on
         std::vector<int32_t> kv_token_history_;
         dim_t last_reuse_{ 0 };
         std::mt19937_64 rng_{ 0x4d494c41ull };

@@ -580,6 +580,11 @@ namespace Mila::Dnn::Compute
             rocmCheck( mila_cdna4_rmsnorm_bf16( static_cast<uint16_t*>( out.rawData() ), rstd_->data(), static_cast<const uint16_t*>( in.rawData() ), w_, b_,
                                                 outer, 1, dim, cfg_.epsilon, cfg_.weight_offset, context_->getStream() ) );
         }
+        /// `outer` rows of caller-owned memory, any count, no rstd kept: the same kernel and bits per row as forward()
+        void forwardRows( const uint16_t* in, uint16_t* out, int outer ) const
+        {
+            rocmCheck( mila_cdna4_rmsnorm_bf16( out, nullptr, in, w_, b_, outer, 1, narrowToKernelIndex( cfg_.dim, "dim" ), cfg_.epsilon, cfg_.weight_offset, context_->getStream() ) );
+        }
         const TensorType* rstd() const noexcept { return rstd_.get(); }
         size_t stateBytes() const noexcept { return rstd_ ? rstd_->sizeInBytes() : 0; }
         const uint16_t* weightPtr() const noexcept { return w_; }
@@ -1369,6 +1374,63 @@ namespace Mila::Dnn::Compute
         std::unique_ptr<Tensor<TensorDataType::UINT8, RocmDeviceMemoryResource>> scratch_;
         std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> logprob_, top_logprobs_;
         std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> top_ids_;
+    };
+
+    // ---------------------------------------------------------------------------------------
+    // Prompt log-probabilities (mila_cdna4_lm_head_score_bf16, csrc/lm_head_score.hip): the lm_head over the rows of a prefill chunk as a GEMM that keeps the softmax
+    // statistics and stores no logit.  The op owns the kernel's scratch and its device outputs; they are allocated on FIRST use (a model that never scores holds
+    // none of them) and counted in stateBytes() from then on.  Two launches on the context's stream; nothing synchronizes.
+    // ---------------------------------------------------------------------------------------
+    struct LmHeadScoreOpConfig { dim_t vocab_size{ 0 }; dim_t input_features{ 0 }; float final_logit_softcap{ 0.0f }; dim_t max_rows{ 1 }; };
+
+    class RocmLmHeadScoreOp : public Operation<DeviceType::Rocm, TensorDataType::FP32>
+    {
+    public:
+        RocmLmHeadScoreOp( IExecutionContext* ctx, const LmHeadScoreOpConfig& cfg ) : Operation( ctx ), cfg_( cfg )
+        {
+            if ( cfg.vocab_size <= 0 || cfg.input_features <= 0 ) throw std::invalid_argument( "RocmLmHeadScoreOp: vocabulary size and input features must be positive" );
+            if ( cfg.max_rows < 1 ) throw std::invalid_argument( "RocmLmHeadScoreOp: max_rows must be positive" );
+        }
+        /// rows 0 .. rows - 1 of x (bf16, x_stride elements apart, already normed) against the table W [vocab, K] in `fmt` (0 bf16, 1 e4m3 + scales): the log-probability
+        /// of targets_dev[ r ] (-1 = none: NaN) and, with argmax, the greedy token and its log-probability, into the op's outputs
+        void forward( const uint16_t* x, size_t x_stride, const void* W, const float* scales, int fmt, const int32_t* targets_dev, dim_t rows, bool argmax )
+        {
+            if ( rows < 1 || rows > cfg_.max_rows ) throw std::invalid_argument( "RocmLmHeadScoreOp::forward: rows outside 1 .. max_rows" );
+            ensure();
+            rocmCheck( mila_cdna4_lm_head_score_bf16( x, x_stride, W, scales, fmt, narrowToKernelIndex( cfg_.input_features, "K" ), narrowToKernelIndex( cfg_.vocab_size, "vocab" ),
+                                                      targets_dev, narrowToKernelIndex( rows, "rows" ), cfg_.final_logit_softcap, logprob_->data(),
+                                                      argmax ? argmax_->data() : nullptr, argmax ? argmax_logprob_->data() : nullptr, scratch_->rawData(), scratch_bytes_,
+                                                      context_->getStream() ) );
+        }
+        /// the outputs of the last forward( .., rows, .. ) to the host (synchronizes); null pointers are skipped
+        void read( dim_t rows, float* logprob, int32_t* argmax, float* argmax_logprob ) const
+        {
+            const size_t n = static_cast<size_t>( rows ) * 4;
+            if ( logprob ) rocmCheck( mila_cdna4_memcpy_d2h( logprob, logprob_->data(), n, context_->getStream() ) );
+            if ( argmax ) rocmCheck( mila_cdna4_memcpy_d2h( argmax, argmax_->data(), n, context_->getStream() ) );
+            if ( argmax_logprob ) rocmCheck( mila_cdna4_memcpy_d2h( argmax_logprob, argmax_logprob_->data(), n, context_->getStream() ) );
+            context_->synchronize();
+        }
+        /// device bytes the op holds: 0 until the first forward
+        size_t stateBytes() const { return scratch_ ? scratch_->sizeInBytes() + logprob_->sizeInBytes() + argmax_->sizeInBytes() + argmax_logprob_->sizeInBytes() : 0; }
+        size_t scratchBytes() const { return scratch_bytes_; }
+    private:
+        void ensure()
+        {
+            if ( scratch_ ) return;
+            scratch_bytes_ = mila_cdna4_lm_head_score_scratch_bytes( narrowToKernelIndex( cfg_.max_rows, "rows" ), narrowToKernelIndex( cfg_.vocab_size, "vocab" ) );
+            const auto dev = context_->getDeviceId();
+            auto scratch = std::make_unique<Tensor<TensorDataType::UINT8, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( scratch_bytes_ ) } );
+            logprob_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ cfg_.max_rows } );
+            argmax_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ cfg_.max_rows } );
+            argmax_logprob_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ cfg_.max_rows } );
+            scratch_ = std::move( scratch );
+        }
+        LmHeadScoreOpConfig cfg_;
+        size_t scratch_bytes_{ 0 };
+        std::unique_ptr<Tensor<TensorDataType::UINT8, RocmDeviceMemoryResource>> scratch_;
+        std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> logprob_, argmax_logprob_;
+        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> argmax_;
     };
 
     /// GPT-2 attention on packed QKV (new BF16 row; the reference's CUDA MHA is FP32-only, OPS/OperationTraits.Cuda.ixx:274-282) with the KV-cache

@@ -293,6 +293,30 @@ HOST_API int mila_gemma_prefill( void* h, const int32_t* host_tokens, int64_t T,
     } );
 }
 
+/// GemmaTransformer::prefillScored: mila_gemma_prefill that also scores rows [first_row, T) of the chunk.  host_targets[T]: the token whose log-probability row r
+/// reports (the last row included; -1 = none: NaN).  out_logprob / out_argmax / out_argmax_logprob [T - first_row] (the two argmax outputs may both be NULL);
+/// host_logits: the last row's logits as mila_gemma_prefill returns them (may be NULL)
+HOST_API int mila_gemma_prefill_scored( void* h, const int32_t* host_tokens, int64_t T, int64_t position_offset, const int32_t* host_targets, int64_t first_row,
+                                        float* out_logprob, int32_t* out_argmax, float* out_argmax_logprob, float* host_logits )
+{
+    auto* r = static_cast<Runner*>( h );
+    return guarded( [&]
+    {
+        if ( T <= 0 || T > r->max_prefill ) throw std::invalid_argument( "GemmaTransformer::prefillScored: chunk length out of range" );
+        if ( !host_targets || !out_logprob ) throw std::invalid_argument( "prefill_scored: targets and out_logprob are required" );
+        if ( ( out_argmax == nullptr ) != ( out_argmax_logprob == nullptr ) ) throw std::invalid_argument( "prefill_scored: the two argmax outputs go together" );
+        upload_tokens( r, host_tokens, T );
+        std::visit( [&]( auto& m )
+        {
+            Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource> targets( m->context()->getDeviceId(), shape_t{ T } );
+            Compute::rocmCheck( mila_cdna4_memcpy_h2d( targets.rawData(), host_targets, static_cast<size_t>( T ) * 4, m->context()->getStream() ) );
+            m->prefillScored( *r->tokens, T, position_offset, targets.data(), first_row, out_argmax != nullptr );
+            m->scoreOp().read( T - first_row, out_logprob, out_argmax, out_argmax_logprob );
+        }, r->model );
+        download_logits( r, host_logits );
+    } );
+}
+
 /// on != 0 (default): prefill runs the fused glue kernels when the configuration fits; 0: one launch per reference op
 HOST_API int mila_gemma_set_fused_prefill( void* h, int on )
 {
@@ -963,6 +987,43 @@ HOST_API int mila_gemma_time_prefill( void* h, int64_t T, int reps, double* out_
     } );
 }
 
+/// mila_gemma_time_prefill for prefillScored: rows [first_row, T) are scored (argmax on), each row's target the chunk's next token
+HOST_API int mila_gemma_time_score_from( void* h, int64_t T, int64_t first_row, int reps, double* out_ms )
+{
+    auto* r = static_cast<Runner*>( h );
+    return guarded( [&]
+    {
+        if ( T <= 0 || T > r->max_prefill ) throw std::invalid_argument( "time_score: chunk length out of range" );
+        if ( reps < 1 ) throw std::invalid_argument( "time_score: reps must be positive" );
+        std::vector<int32_t> toks( static_cast<size_t>( T ) ), tg( static_cast<size_t>( T ) );
+        for ( int64_t i = 0; i < T; ++i ) toks[ i ] = static_cast<int32_t>( ( i * 7919 + 13 ) % 1000 );
+        for ( int64_t i = 0; i < T; ++i ) tg[ i ] = i + 1 < T ? toks[ i + 1 ] : -1;
+        upload_tokens( r, toks.data(), T );
+        std::visit( [&]( auto& m )
+        {
+            auto* ctx = m->context();
+            hipStream_t s = reinterpret_cast<hipStream_t>( ctx->getStream() );
+            Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource> targets( ctx->getDeviceId(), shape_t{ T } );
+            Compute::rocmCheck( mila_cdna4_memcpy_h2d( targets.rawData(), tg.data(), static_cast<size_t>( T ) * 4, ctx->getStream() ) );
+            m->prefillScored( *r->tokens, T, 0, targets.data(), first_row, true );
+            ctx->synchronize();
+            hipEvent_t e0, e1;
+            hipCheck( hipEventCreate( &e0 ), "hipEventCreate" );
+            hipCheck( hipEventCreate( &e1 ), "hipEventCreate" );
+            hipCheck( hipEventRecord( e0, s ), "hipEventRecord" );
+            for ( int i = 0; i < reps; ++i ) m->prefillScored( *r->tokens, T, 0, targets.data(), first_row, true );
+            hipCheck( hipEventRecord( e1, s ), "hipEventRecord" );
+            ctx->synchronize();
+            float ms = 0;
+            hipCheck( hipEventElapsedTime( &ms, e0, e1 ), "hipEventElapsedTime" );
+            (void)hipEventDestroy( e0 ); (void)hipEventDestroy( e1 );
+            *out_ms = static_cast<double>( ms ) / reps;
+        }, r->model );
+    } );
+}
+/// every row of the chunk scored
+HOST_API int mila_gemma_time_score( void* h, int64_t T, int reps, double* out_ms ) { return mila_gemma_time_score_from( h, T, 0, reps, out_ms ); }
+
 /// greedy generation: feeds `first_token` at `start_position`, then n_tokens - 1 more steps, each consuming the
 /// token the device sampler produced; returns the sampled ids (host) -- mode as in mila_gemma_decode
 HOST_API int mila_gemma_generate( void* h, int32_t first_token, int64_t start_position, int n_tokens, int mode, int32_t* host_out )
@@ -1479,6 +1540,27 @@ HOST_API void* mila_gemma_model_synthetic_chain( int policy, const mila_gemma_co
 }
 
 HOST_API void mila_gemma_model_destroy( void* h ) { delete static_cast<RocmGemmaModel*>( h ); }
+
+/// GemmaModel::score: out_logprob [n - first]; out_argmax / out_argmax_logprob [n - first] or both NULL (ScoreParams::argmax off); *out_sum = the float64 sum;
+/// *out_reused = tokens served from the KV caches
+HOST_API int mila_gemma_model_score( void* h, const int32_t* tokens, int64_t n, int64_t first, float* out_logprob, int32_t* out_argmax, float* out_argmax_logprob,
+                                     double* out_sum, int64_t* out_reused )
+{
+    auto* m = static_cast<RocmGemmaModel*>( h );
+    return guarded( [&]
+    {
+        if ( n < 0 || ( n > 0 && !tokens ) ) throw std::invalid_argument( "model_score: tokens are required" );
+        if ( ( out_argmax == nullptr ) != ( out_argmax_logprob == nullptr ) ) throw std::invalid_argument( "model_score: the two argmax outputs go together" );
+        ScoreParams sp;
+        sp.first = first;
+        sp.argmax = out_argmax != nullptr;
+        const ScoreResult res = m->score( std::span<const int32_t>( tokens, static_cast<size_t>( n ) ), sp );
+        if ( out_logprob ) std::copy( res.logprob.begin(), res.logprob.end(), out_logprob );
+        if ( out_argmax ) { std::copy( res.argmax.begin(), res.argmax.end(), out_argmax ); std::copy( res.argmax_logprob.begin(), res.argmax_logprob.end(), out_argmax_logprob ); }
+        if ( out_sum ) *out_sum = res.sum;
+        if ( out_reused ) *out_reused = m->lastReusedPrefix();
+    } );
+}
 
 /// generate(): max_new < 0 = no budget (run to a stop token or the context bound); n_stop == 0 = the model's default stop set; the callback's tokens
 /// are appended to out_tokens (at most cap).  *out_status = GenerateStatus; *out_reused = prompt tokens served from the KV caches; cancel_after >= 0: the
