@@ -213,6 +213,16 @@ __device__ __forceinline__ float block_max(float v, float* red)
     return t;
 }
 
+// ---- what the samplers, the log-probabilities and the lm_head epilogues share ---------------------
+// the (value, index) order of every argmax here: strictly larger wins, equal values go to the lower index, NaN never wins (the reference's semantics,
+// OPS/Sampling/Kernels/Sampling.cu:23-75)
+__device__ __forceinline__ void argmax_better(float& bv, int& bi, float v, int i)
+{
+    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+}
+// the final-logit soft cap (softcap <= 0: off)
+__device__ __forceinline__ float soft_cap(float x, float softcap) { return softcap > 0.0f ? softcap * tanhf(x / softcap) : x; }
+
 // ---- 16-byte global accesses -------------------------------------------------------------------
 __device__ __forceinline__ u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p); }
 // streamed-once data (weights in decode): non-temporal so it does not evict x / KV from L2

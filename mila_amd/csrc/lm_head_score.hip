@@ -1,7 +1,7 @@
 // Prompt log-probabilities: the lm_head GEMM over many rows whose epilogue keeps the softmax statistics and never stores a logit.
 //   y_i = sum_k x[r,k] * W[i,k]      fp32 on the matrix cores; an e4m3 table enters as its exact bf16 values and the per-row scale multiplies ONCE after the reduction
 //                                    (matvec_f32out's arithmetic -- what the decode head computes -- not gemm.hip's bf16(decode * scale))
-//   z_i = softcap > 0 ? softcap * tanhf(y_i / softcap) : y_i                                            (lp_z of logprobs.hip)
+//   z_i = softcap > 0 ? softcap * tanhf(y_i / softcap) : y_i                                            (soft_cap of common.h)
 //   m = max z,  S = sum expf(z_i - m),  logprob_t = (z_t - m) - logf(S);  argmax = the largest z, the LOWEST index among equals (the greedy sampler's tie rule)
 // Two launches:
 //   partials: one workgroup owns a block of 128 rows and a SLAB of the vocabulary and walks the slab 128 columns at a time through the K loop of gemm.hip's gemm_kernel
@@ -49,7 +49,6 @@ struct LsParams
 };
 
 __device__ __forceinline__ int ls_swz(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ float ls_z(float x, float softcap) { return softcap > 0.0f ? softcap * tanhf(x / softcap) : x; }
 // a 16-byte load from an address that is only 2-byte aligned (x rows at any stride); st16_a2's counterpart
 __device__ __forceinline__ u32x4 ls_ld16_a2(const void* p)
 {
@@ -230,7 +229,7 @@ __global__ __launch_bounds__(256) void lm_head_score_partial_kernel(const LsPara
                         const bool in = n < p.vocab;
                         float y = acc[a][b][e];
                         if constexpr (FMT == 1) y = (in ? p.scales[n] : 0.0f) * y;
-                        const float v = in ? ls_z(y, p.softcap) : -INFINITY;
+                        const float v = in ? soft_cap(y, p.softcap) : -INFINITY;
                         z[a][e] = v;
                         mt = fmaxf(mt, v);
                         if (v > st[b].bz) { st[b].bz = v; st[b].bi = n; }          // ascending n: the first of equals stays

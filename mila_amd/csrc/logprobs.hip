@@ -1,5 +1,5 @@
 // Token log-probabilities of a decode step: the chosen token's and the top-n alternatives', from the fp32 logits the lm_head left on the device.
-//   z_i = softcap > 0 ? softcap * tanhf(x_i / softcap) : x_i      (radix_scale_body's expression in sampling.hip, without the temperature)
+//   z_i = softcap > 0 ? softcap * tanhf(x_i / softcap) : x_i      (soft_cap of common.h: the samplers' expression, without the temperature)
 //   m = max z,  S = sum expf(z_i - m),  logprob_i = (z_i - m) - logf(S)
 // the model's distribution: no temperature, no top-k / top-p.  "Top-n" = the n largest z, value descending, then LOWER index first -- the greedy sampler's tie rule, so
 // on a greedy step top_ids[0] is the emitted token.
@@ -43,12 +43,6 @@ struct LpParams
 
 static size_t lp_row_floats(int top_n) { return (size_t)2 * kLpBlocks + (size_t)2 * kLpBlocks * top_n; }
 
-__device__ __forceinline__ float lp_z(float x, float softcap) { return softcap > 0.0f ? softcap * tanhf(x / softcap) : x; }
-
-__device__ __forceinline__ void lp_better(float& bv, int& bi, float v, int i)
-{
-    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
 // (v, i) comes strictly behind (pv, pi) in the top-n order
 __device__ __forceinline__ bool lp_behind(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
 
@@ -100,15 +94,15 @@ __global__ __launch_bounds__(256) void logprobs_partial_kernel(const LpParams p)
 #pragma unroll
     for (int j = 0; j < kLpPre; ++j)
     {
-        if (ix[j] != kLpNone) z[j] = lp_z(z[j], p.softcap);
+        if (ix[j] != kLpNone) z[j] = soft_cap(z[j], p.softcap);
         mx = fmaxf(mx, z[j]);
     }
-    for (int i = tail0; i < p.vocab; i += stride) mx = fmaxf(mx, lp_z(x[i], p.softcap));      // beyond 2^19 entries: recomputed in every walk
+    for (int i = tail0; i < p.vocab; i += stride) mx = fmaxf(mx, soft_cap(x[i], p.softcap));      // beyond 2^19 entries: recomputed in every walk
     mx = block_max<4>(mx, red);
     float sum = 0.0f;
 #pragma unroll
     for (int j = 0; j < kLpPre; ++j) sum += expf(z[j] - mx);                                   // an empty slot is -inf: adds 0
-    for (int i = tail0; i < p.vocab; i += stride) sum += expf(lp_z(x[i], p.softcap) - mx);
+    for (int i = tail0; i < p.vocab; i += stride) sum += expf(soft_cap(x[i], p.softcap) - mx);
     sum = block_sum<4>(sum, red);
     if (threadIdx.x == 0) { pm[blockIdx.x] = mx; ps[blockIdx.x] = sum; }
     const int n = p.top_n;
@@ -123,11 +117,11 @@ __global__ __launch_bounds__(256) void logprobs_partial_kernel(const LpParams p)
             int bi = kLpNone;
 #pragma unroll
             for (int j = 0; j < kLpPre; ++j)
-                if (lp_behind(z[j], ix[j], pv, pi)) lp_better(bv, bi, z[j], ix[j]);
+                if (lp_behind(z[j], ix[j], pv, pi)) argmax_better(bv, bi, z[j], ix[j]);
             for (int i = tail0; i < p.vocab; i += stride)
             {
-                const float v = lp_z(x[i], p.softcap);
-                if (lp_behind(v, i, pv, pi)) lp_better(bv, bi, v, i);
+                const float v = soft_cap(x[i], p.softcap);
+                if (lp_behind(v, i, pv, pi)) argmax_better(bv, bi, v, i);
             }
             lp_wave_argmax(bv, bi);
             if (lane == 0) { wv[wave * kLpMaxTop + r] = bv; wi[wave * kLpMaxTop + r] = bi; }
@@ -204,7 +198,7 @@ __global__ __launch_bounds__(256) void logprobs_final_kernel(const LpParams p)
     bool listed = false;
     for (int r = 0; r < n; ++r)
         if (ti[r] == tok) { lp = (tv[r] - mx) - lse; listed = true; }
-    if (!listed && tok >= 0 && tok < p.vocab) lp = (lp_z(p.logits[(size_t)row * p.logits_stride + tok], p.softcap) - mx) - lse;
+    if (!listed && tok >= 0 && tok < p.vocab) lp = (soft_cap(p.logits[(size_t)row * p.logits_stride + tok], p.softcap) - mx) - lse;
     if (PUBLISH)
     {
         const unsigned long long s = p.seq_dev[0];

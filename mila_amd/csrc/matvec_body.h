@@ -71,12 +71,6 @@ struct MatvecParams
     int* amax_i = nullptr;
 };
 
-// the sampler's order: strictly larger wins, equal values go to the lower index, NaN never wins (csrc/sampling.hip: better)
-__device__ __forceinline__ void argmax_better(float& bv, int& bi, float v, int i)
-{
-    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
-
 constexpr int kMatvecWaves = 16;   // 1024 threads
 
 // the launch shape of a decode Linear (matvec.hip: matvec_launch_shape, host): output columns per wave step R, chunk positions in flight U, the largest grid

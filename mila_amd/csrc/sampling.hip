@@ -15,11 +15,7 @@ template <typename T> __device__ __forceinline__ float to_f32(T v);
 template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ float to_f32<uint16_t>(uint16_t v) { return bf16_bits_to_f32(v); }
 
-__device__ __forceinline__ void better(float& bv, int& bi, float v, int i)
-{
-    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
-
+// (the (value, index) order is argmax_better of common.h)
 __device__ __forceinline__ void wave_argmax(float& bv, int& bi)
 {
 #pragma unroll
@@ -27,9 +23,28 @@ __device__ __forceinline__ void wave_argmax(float& bv, int& bi)
     {
         const float ov = __shfl_xor(bv, off, 64);
         const int oi = __shfl_xor(bi, off, 64);
-        better(bv, bi, ov, oi);
+        argmax_better(bv, bi, ov, oi);
     }
 }
+
+// the reduction of a 256-thread workgroup: each wave's butterfly, four LDS slots, and thread 0 folds the other three waves into its pair.  Only thread 0 holds the
+// result.  One barrier: every thread of the workgroup calls it.
+__device__ __forceinline__ void block_argmax(float& bv, int& bi)
+{
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    wave_argmax(bv, bi);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) argmax_better(bv, bi, sv[w], si[w]);
+    }
+}
+
+// the token of a finished reduction that started from (-FLT_MAX, 0x7fffffff).  All -FLT_MAX / NaN: the reference leaves index 0
+__device__ __forceinline__ int argmax_token(int bi) { return (bi == 0x7fffffff) ? 0 : bi; }
 
 // ---- sampling filters (TokenSampling.md 3.3: repetition penalty, presence / frequency penalty, min-p).  The per-sequence state is a table of `vocab` 32-bit words:
 // bit 31 = the token occurs in the prompt, bits 0..30 = c, the times it has been generated.  The sampler that is given a table reads table[i] beside logits[i] and its
@@ -59,21 +74,11 @@ template <typename T>
 __global__ __launch_bounds__(256) void argmax_partial_kernel(const T* __restrict__ logits, float* __restrict__ pv, int* __restrict__ pi,
                                                              int vocab)
 {
-    __shared__ float sv[4];
-    __shared__ int si[4];
     float bv = -FLT_MAX;
     int bi = 0x7fffffff;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) better(bv, bi, to_f32(logits[i]), i);
-    wave_argmax(bv, bi);
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-#pragma unroll
-        for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-        pv[blockIdx.x] = bv;
-        pi[blockIdx.x] = bi;
-    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) argmax_better(bv, bi, to_f32(logits[i]), i);
+    block_argmax(bv, bi);
+    if (threadIdx.x == 0) { pv[blockIdx.x] = bv; pi[blockIdx.x] = bi; }
 }
 
 // the greedy sampler's first stage over the ADJUSTED logits x3 (softcap first: the penalty touches only some tokens, so the capped values decide); blockIdx.y = row b:
@@ -81,8 +86,6 @@ __global__ __launch_bounds__(256) void argmax_partial_kernel(const T* __restrict
 __global__ __launch_bounds__(256) void argmax_partial_filtered_kernel(const float* __restrict__ logits0, size_t logits_stride, float softcap, const SampleFilter f,
                                                                       float* __restrict__ pv0, int row_floats, int vocab)
 {
-    __shared__ float sv[4];
-    __shared__ int si[4];
     const float* logits = logits0 + (size_t)blockIdx.y * logits_stride;
     const uint32_t* table = f.table + (size_t)blockIdx.y * f.table_stride;
     float* pv = pv0 + (size_t)blockIdx.y * row_floats;
@@ -90,131 +93,78 @@ __global__ __launch_bounds__(256) void argmax_partial_filtered_kernel(const floa
     float bv = -FLT_MAX;
     int bi = 0x7fffffff;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256)
-    {
-        float x = logits[i];
-        if (softcap > 0.0f) x = softcap * tanhf(x / softcap);
-        better(bv, bi, penalized_logit(x, table[i], f), i);
-    }
-    wave_argmax(bv, bi);
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-#pragma unroll
-        for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-        pv[blockIdx.x] = bv;
-        pi[blockIdx.x] = bi;
-    }
+        argmax_better(bv, bi, penalized_logit(soft_cap(logits[i], softcap), table[i], f), i);
+    block_argmax(bv, bi);
+    if (threadIdx.x == 0) { pv[blockIdx.x] = bv; pi[blockIdx.x] = bi; }
 }
 
+// the second stage: one workgroup reduces the n partials.  TABLE: thread 0 counts the token in the table before it stores it (`table` is not read otherwise)
 template <bool TABLE>
-__device__ __forceinline__ void argmax_final_body(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out, uint32_t* table)
+__global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out, uint32_t* table)
 {
-    __shared__ float sv[4];
-    __shared__ int si[4];
     float bv = -FLT_MAX;
     int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += 256) better(bv, bi, pv[i], pi[i]);
-    wave_argmax(bv, bi);
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256) argmax_better(bv, bi, pv[i], pi[i]);
+    block_argmax(bv, bi);
     if (threadIdx.x == 0)
     {
-#pragma unroll
-        for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-        const int tok = (bi == 0x7fffffff) ? 0 : bi;     // all -FLT_MAX / NaN: the reference leaves index 0
+        const int tok = argmax_token(bi);
         if (TABLE) table_count(table, tok);
         token_out[0] = tok;
     }
 }
-__global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out)
+
+// what one lane does behind the token of a one-row advance step: the position bump of the next step, the sequence number `seq` of this token (seq_dev != NULL) and
+// (ring != NULL) the publication of seq << 32 | token to the host
+__device__ __forceinline__ void publish_token(int tok, unsigned long long seq, int32_t* pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size)
 {
-    argmax_final_body<false>(pv, pi, n, token_out, nullptr);
-}
-__global__ __launch_bounds__(256) void argmax_final_table_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out, uint32_t* table)
-{
-    argmax_final_body<true>(pv, pi, n, token_out, table);
+    *pos += 1;
+    if (seq_dev != nullptr) *seq_dev = seq;
+    if (ring != nullptr)
+        __hip_atomic_store(ring + (seq % (unsigned long long)ring_size), (seq << 32) | (unsigned long long)(uint32_t)tok, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// the last node of a captured decode step: the final reduction of the greedy sampler, the position bump of the next step and (ring != NULL) the publication
-// of the sampled token to the host -- what argmax_final + advance_position[_snapshot] did in two launches (round 3: one launch fewer per token)
+// the last node of a captured decode step: the final reduction of the greedy sampler, the position bump of the next step and (ring != NULL; seq_dev goes with it) the
+// publication of the sampled token to the host -- what argmax_final + advance_position[_snapshot] did in two launches (round 3: one launch fewer per token).  The
+// leading parameters are plain pointers / integers (kernarg preload), the table comes last.
 template <bool TABLE>
-__device__ __forceinline__ void argmax_final_advance_body(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out,
-                                                          int32_t* __restrict__ pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size, uint32_t* table)
-{
-    __shared__ float sv[4];
-    __shared__ int si[4];
-    float bv = -FLT_MAX;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += 256) better(bv, bi, pv[i], pi[i]);
-    wave_argmax(bv, bi);
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-#pragma unroll
-        for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-        const int tok = (bi == 0x7fffffff) ? 0 : bi;
-        if (TABLE) table_count(table, tok);
-        token_out[0] = tok;
-        *pos += 1;
-        if (ring != nullptr)
-        {
-            const unsigned long long seq = *seq_dev + 1ull;
-            *seq_dev = seq;
-            __hip_atomic_store(ring + (seq % (unsigned long long)ring_size), (seq << 32) | (unsigned long long)(uint32_t)tok, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
 __global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out,
-                                                                   int32_t* __restrict__ pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size)
+                                                                   int32_t* __restrict__ pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size,
+                                                                   uint32_t* table)
 {
-    argmax_final_advance_body<false>(pv, pi, n, token_out, pos, seq_dev, ring, ring_size, nullptr);
-}
-__global__ __launch_bounds__(256) void argmax_final_advance_table_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int32_t* __restrict__ token_out,
-                                                                         int32_t* __restrict__ pos, unsigned long long* seq_dev, unsigned long long* ring, int ring_size,
-                                                                         uint32_t* table)
-{
-    argmax_final_advance_body<true>(pv, pi, n, token_out, pos, seq_dev, ring, ring_size, table);
+    float bv = -FLT_MAX;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += 256) argmax_better(bv, bi, pv[i], pi[i]);
+    block_argmax(bv, bi);
+    if (threadIdx.x == 0)
+    {
+        const int tok = argmax_token(bi);
+        if (TABLE) table_count(table, tok);
+        token_out[0] = tok;
+        publish_token(tok, seq_dev != nullptr ? *seq_dev + 1ull : 0ull, pos, seq_dev, ring, ring_size);
+    }
 }
 
 // argmax_final_advance_kernel for B independent rows, one workgroup per row: row b reduces the n partials at pv + b * row_floats (values, then kArgmaxBlocks floats on
-// the indices); a row whose active word is 0 keeps its token and its position
+// the indices); a row whose active word is 0 keeps its token, its position and (TABLE) its table
 template <bool TABLE>
-__device__ __forceinline__ void argmax_rows_final_advance_body(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
-                                                               const int32_t* __restrict__ active, int n, int row_floats, uint32_t* table0, size_t table_stride)
+__global__ __launch_bounds__(256) void argmax_rows_final_advance_kernel(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
+                                                                        const int32_t* __restrict__ active, int n, int row_floats, uint32_t* table0, size_t table_stride)
 {
-    __shared__ float sv[4];
-    __shared__ int si[4];
     const int b = blockIdx.x;
     const float* pv = pv0 + (size_t)b * row_floats;
     const int* pi = reinterpret_cast<const int*>(pv + kArgmaxBlocks);
     float bv = -FLT_MAX;
     int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += 256) better(bv, bi, pv[i], pi[i]);
-    wave_argmax(bv, bi);
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256) argmax_better(bv, bi, pv[i], pi[i]);
+    block_argmax(bv, bi);
     if (threadIdx.x == 0 && active[b] != 0)
     {
-#pragma unroll
-        for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-        const int tok = (bi == 0x7fffffff) ? 0 : bi;
+        const int tok = argmax_token(bi);
         if (TABLE) table_count(table0 + (size_t)b * table_stride, tok);
         token_out[b] = tok;
         pos[b] += 1;
     }
-}
-__global__ __launch_bounds__(256) void argmax_rows_final_advance_kernel(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
-                                                                        const int32_t* __restrict__ active, int n, int row_floats)
-{
-    argmax_rows_final_advance_body<false>(pv0, token_out, pos, active, n, row_floats, nullptr, 0);
-}
-// (the active rows only: an inactive row's table, like its token and its position, is not touched)
-__global__ __launch_bounds__(256) void argmax_rows_final_advance_table_kernel(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
-                                                                              const int32_t* __restrict__ active, int n, int row_floats, uint32_t* table0, size_t table_stride)
-{
-    argmax_rows_final_advance_body<true>(pv0, token_out, pos, active, n, row_floats, table0, table_stride);
 }
 
 // table maintenance: bit 31 of the words of n token ids in device memory.  Every writer stores the SAME value into a cleared table (counts are zero before the first
@@ -228,10 +178,21 @@ __global__ __launch_bounds__(256) void token_table_mark_prompt_kernel(uint32_t* 
     }
 }
 
-// The chain's tail (speculative verification): rows 0 .. T - 1 are consecutive positions of ONE sequence, row t fed with tok[t] (tok[0] the last sampled token,
-// tok[1 ..] the drafts).  One workgroup, wave t reduces row t's n partials to a_t (argmax is exact in any order: the greedy sampler's token); then one lane accepts
-// the longest correct draft prefix: n_acc = the first t in [0, T - 1) with a_t != tok[t + 1], else T - 1.  result = {n_acc + 1, a_0 .. a_n_acc} (the other words are
-// left alone), tok[0] = a_n_acc (the next step's input), *pos += n_acc + 1.
+// The acceptance rule of a chain (speculative verification), by one lane: rows 0 .. T - 1 are consecutive positions of ONE sequence, row t fed with tok[t] (tok[0] the
+// last sampled token, tok[1 ..] the drafts), and s[t] is row t's sample.  The longest correct draft prefix is accepted: n_acc = the first t in [0, T - 1) with
+// s[t] != tok[t + 1], else T - 1.  result = {n_acc + 1, s[0] .. s[n_acc]} (the other words are left alone), tok[0] = s[n_acc] (the next step's input), *pos += n_acc + 1.
+__device__ __forceinline__ void chain_accept(const int* s, int T, int32_t* __restrict__ tok, int32_t* __restrict__ result, int32_t* __restrict__ pos)
+{
+    int n_acc = T - 1;
+    for (int i = T - 2; i >= 0; --i)
+        if (s[i] != tok[i + 1]) n_acc = i;
+    result[0] = n_acc + 1;
+    for (int i = 0; i <= n_acc; ++i) result[1 + i] = s[i];
+    tok[0] = s[n_acc];
+    *pos += n_acc + 1;
+}
+
+// The greedy chain's tail.  One workgroup, wave t reduces row t's n partials to a_t (argmax is exact in any order: the greedy sampler's token); then chain_accept.
 __global__ __launch_bounds__(256) void argmax_chain_accept_kernel(const float* __restrict__ pv0, int32_t* __restrict__ tok, int32_t* __restrict__ result, int32_t* __restrict__ pos,
                                                                   int n, int row_floats, int T)
 {
@@ -243,21 +204,12 @@ __global__ __launch_bounds__(256) void argmax_chain_accept_kernel(const float* _
         const int* pi = reinterpret_cast<const int*>(pv + kArgmaxBlocks);
         float bv = -FLT_MAX;
         int bi = 0x7fffffff;
-        for (int i = lane; i < n; i += 64) better(bv, bi, pv[i], pi[i]);
+        for (int i = lane; i < n; i += 64) argmax_better(bv, bi, pv[i], pi[i]);
         wave_argmax(bv, bi);
-        if (lane == 0) sa[t] = (bi == 0x7fffffff) ? 0 : bi;
+        if (lane == 0) sa[t] = argmax_token(bi);
     }
     __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        int n_acc = T - 1;
-        for (int i = T - 2; i >= 0; --i)
-            if (sa[i] != tok[i + 1]) n_acc = i;
-        result[0] = n_acc + 1;
-        for (int i = 0; i <= n_acc; ++i) result[1 + i] = sa[i];
-        tok[0] = sa[n_acc];
-        *pos += n_acc + 1;
-    }
+    if (threadIdx.x == 0) chain_accept(sa, T, tok, result, pos);
 }
 
 __global__ __launch_bounds__(64) void advance_positions_rows_kernel(int32_t* __restrict__ pos, const int32_t* __restrict__ active, int B)
@@ -266,21 +218,39 @@ __global__ __launch_bounds__(64) void advance_positions_rows_kernel(int32_t* __r
     if (b < B && active[b] != 0) pos[b] += 1;
 }
 
+// The first stage of the two-launch greedy entries, written once: the scratch check, the split of a row's partials into values and indices, the workgroup count and
+// the partial launch.  f == nullptr: the logits as they are, one row; else x3 of `rows` rows (softcap first), row b's partials at pv + b * row_floats.
+struct ArgmaxPartials { float* pv; int* pi; int blocks, row_floats; };
+constexpr size_t kArgmaxRowBytes = (size_t)kArgmaxBlocks * 8;
+template <typename T>
+static int launch_argmax_partials(const T* logits, size_t logits_stride, int rows, int vocab, float softcap, const SampleFilter* f, void* scratch, size_t scratch_bytes,
+                                  hipStream_t s, const char* who, ArgmaxPartials& a)
+{
+    const size_t need = kArgmaxRowBytes * (size_t)rows;
+    if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
+    a.pv = reinterpret_cast<float*>(scratch);
+    a.pi = reinterpret_cast<int*>(a.pv + kArgmaxBlocks);
+    a.blocks = (vocab + 255) / 256;
+    if (a.blocks > kArgmaxBlocks) a.blocks = kArgmaxBlocks;
+    a.row_floats = (int)(kArgmaxRowBytes / sizeof(float));
+    if constexpr (std::is_same<T, float>::value)
+    {
+        if (f) hipLaunchKernelGGL(argmax_partial_filtered_kernel, dim3(a.blocks, (unsigned)rows), dim3(256), 0, s, logits, logits_stride, softcap, *f, a.pv, a.row_floats, vocab);
+        else hipLaunchKernelGGL(argmax_partial_kernel<T>, dim3(a.blocks), dim3(256), 0, s, logits, a.pv, a.pi, vocab);
+    }
+    else hipLaunchKernelGGL(argmax_partial_kernel<T>, dim3(a.blocks), dim3(256), 0, s, logits, a.pv, a.pi, vocab);
+    return check_hip(hipGetLastError(), who);
+}
+
 template <typename T>
 static int run_argmax(const T* logits, int32_t* token_out, int vocab, void* scratch, size_t scratch_bytes, hipStream_t s, const char* who)
 {
     MILA_REQUIRE(logits && token_out, "%s: null pointer", who);
     MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
-    const size_t need = (size_t)kArgmaxBlocks * 8;
-    if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
-    float* pv = reinterpret_cast<float*>(scratch);
-    int* pi = reinterpret_cast<int*>(pv + kArgmaxBlocks);
-    int blocks = (vocab + 255) / 256;
-    if (blocks > kArgmaxBlocks) blocks = kArgmaxBlocks;
-    hipLaunchKernelGGL(argmax_partial_kernel<T>, dim3(blocks), dim3(256), 0, s, logits, pv, pi, vocab);
-    int rc = check_hip(hipGetLastError(), who);
+    ArgmaxPartials a;
+    const int rc = launch_argmax_partials(logits, 0, 1, vocab, 0.0f, nullptr, scratch, scratch_bytes, s, who, a);
     if (rc) return rc;
-    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, s, pv, pi, blocks, token_out);
+    hipLaunchKernelGGL(argmax_final_kernel<false>, dim3(1), dim3(256), 0, s, a.pv, a.pi, a.blocks, token_out, (uint32_t*)nullptr);
     return check_hip(hipGetLastError(), who);
 }
 
@@ -368,8 +338,7 @@ __global__ __launch_bounds__(256) void samp_scale_kernel(const T* __restrict__ l
     float mx = -FLT_MAX;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < p.vocab; i += gridDim.x * 256)
     {
-        float x = to_f32(logits[i]);
-        if (p.softcap > 0.0f) x = p.softcap * tanhf(x / p.softcap);
+        float x = soft_cap(to_f32(logits[i]), p.softcap);
         x = x / p.temperature;
         p.w[i] = x;
         mx = fmaxf(mx, x);
@@ -603,7 +572,7 @@ struct RadixParams
     int32_t* token_out;
     int vocab, top_k;
     float softcap, temperature, top_p, r;
-    // the graph form's tail (radix_cdf_kernel<true>)
+    // the one-row advance tail (radix_cdf_kernel<true, *>)
     const float* draws;
     int draws_size, ring_size;
     int32_t* pos;
@@ -690,8 +659,7 @@ __device__ __forceinline__ void radix_scale_body(const T* __restrict__ logits, c
     float mx = -FLT_MAX;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < p.vocab; i += gridDim.x * 256)
     {
-        float x = to_f32(logits[i]);
-        if (p.softcap > 0.0f) x = p.softcap * tanhf(x / p.softcap);
+        float x = soft_cap(to_f32(logits[i]), p.softcap);
         if (FILT) x = penalized_logit(x, table[i], *f);
         x = x / p.temperature;
         p.w[i] = x;
@@ -913,63 +881,16 @@ __device__ __forceinline__ int radix_cdf_walk(const RadixParams& p, float r, int
     return result;
 }
 
-// the one-row tail.  ADVANCE: the stochastic twin of argmax_final_advance_kernel -- the draw is slot (*seq_dev + 1) % draws_size of a host-written ring (system-scope
-// load: the host rewrites the slots between replays), and the tail bumps the position, stores the sequence number and (ring != NULL) publishes seq << 32 | token.
-// TABLE: lane 0 counts the sample in the table before it stores / publishes the token.
-template <bool ADVANCE, bool TABLE>
-__device__ __forceinline__ void radix_cdf_body(const RadixParams& p, int nchunks, int chunk, uint32_t* table)
-{
-    const int lane = threadIdx.x;
-    float r = p.r;
-    unsigned long long seq = 0ull;
-    if (ADVANCE)
-    {
-        seq = *p.seq_dev + 1ull;
-        const uint32_t* slot = reinterpret_cast<const uint32_t*>(p.draws) + (seq % (unsigned long long)p.draws_size);
-        r = __uint_as_float(__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-    }
-    const int result = radix_cdf_walk(p, r, nchunks, chunk, lane);
-    if (lane == 0)
-    {
-        if (TABLE) table_count(table, result);
-        p.token_out[0] = result;
-        if (ADVANCE)
-        {
-            *p.pos += 1;
-            *p.seq_dev = seq;
-            if (p.ring != nullptr)
-                __hip_atomic_store(p.ring + (seq % (unsigned long long)p.ring_size), (seq << 32) | (unsigned long long)(uint32_t)result, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
-
-template <bool ADVANCE>
-__global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixParams p, int nchunks, int chunk) { radix_cdf_body<ADVANCE, false>(p, nchunks, chunk, nullptr); }
-template <bool ADVANCE>
-__global__ __launch_bounds__(64) void radix_cdf_table_kernel(const RadixParams p, int nchunks, int chunk, uint32_t* table) { radix_cdf_body<ADVANCE, true>(p, nchunks, chunk, table); }
-
-// the one-row launches
-template <typename T>
-__global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ logits, const RadixParams p, int clear_words) { radix_scale_body(logits, p, clear_words); }
-__global__ __launch_bounds__(256) void radix_kpass_kernel(const RadixParams p, int pass) { radix_kpass_body(p, pass); }
-__global__ __launch_bounds__(256) void radix_prob_kernel(const RadixParams p, int use_k, int use_p, int nblocks_scale) { radix_prob_body(p, use_k, use_p, nblocks_scale); }
-__global__ __launch_bounds__(256) void radix_ppass_kernel(const RadixParams p, int pass) { radix_ppass_body(p, pass); }
-__global__ __launch_bounds__(256) void radix_mask_kernel(const RadixParams p, int use_p, int chunk) { radix_mask_body(p, use_p, chunk); }
-// ... and their filtered instantiations: the scale launch with the table, the mask launch with min-p
-__global__ __launch_bounds__(256) void radix_scale_filtered_kernel(const float* __restrict__ logits, const RadixParams p, int clear_words, const SampleFilter f)
-{
-    radix_scale_body<float, true>(logits, p, clear_words, &f, f.table);
-}
-__global__ __launch_bounds__(256) void radix_mask_minp_kernel(const RadixParams p, int use_p, int chunk, float min_p) { radix_mask_body<true>(p, use_p, chunk, min_p); }
-
-// The rows forms: the same bodies with a row dimension in the grid.  blockIdx.y = b picks row b's logits (logits + b * logits_stride) and row b's scratch region
-// (header, histograms, red, w at scratch + b * row_stride bytes); blockIdx.x / gridDim.x are what the one-row launch has, so every walk, every chunk and every float
-// sum of row b is the one-row kernel's on that row: row b's token is sample_radix_fp32's on row b's logits with row b's draw, whatever the other rows hold.
+// The rows of a call: the stage kernels take a row dimension in the grid.  blockIdx.y = b picks row b's logits (logits + b * logits_stride), row b's table
+// (f.table + b * f.table_stride) and row b's scratch region (header, histograms, red, w at scratch + b * row_stride bytes); blockIdx.x / gridDim.x are what a one-row
+// launch has, so every walk, every chunk and every float sum of row b is the one-row call's on that row: row b's token is sample_radix_fp32's on row b's logits with row
+// b's draw, whatever the other rows hold.  A one-row call is rows = 1, gridDim.y = 1 (row_stride is never multiplied by anything but 0).
 struct RadixRows
 {
-    RadixParams p;                  // row 0's pointers; p.draws = one draw per row, p.pos = the position word(s) of the tail
+    RadixParams p;                  // row 0's pointers; in a rows call p.draws = one draw per row, p.pos = the position word(s) of the tail
     size_t row_stride;              // bytes between the scratch regions of two rows (a multiple of 8)
     size_t logits_stride;           // floats between the logits of two rows
+    SampleFilter f;                 // read by the FILT / TABLE instantiations only (min_p is an argument of the mask launch)
 };
 __device__ __forceinline__ RadixParams radix_row(const RadixRows& r, int b)
 {
@@ -982,52 +903,73 @@ __device__ __forceinline__ RadixParams radix_row(const RadixRows& r, int b)
     p.w = reinterpret_cast<float*>(reinterpret_cast<char*>(r.p.w) + off);
     return p;
 }
-__global__ __launch_bounds__(256) void radix_scale_rows_kernel(const float* __restrict__ logits, const RadixRows r, int clear_words)
+
+// the stage launches (`logits` leads: it is preloaded)
+template <typename T, bool FILT>
+__global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ logits, const RadixRows r, int clear_words)
 {
     const RadixParams p = radix_row(r, blockIdx.y);
-    radix_scale_body(logits + (size_t)blockIdx.y * r.logits_stride, p, clear_words);
+    radix_scale_body<T, FILT>(logits + (size_t)blockIdx.y * r.logits_stride, p, clear_words, &r.f, FILT ? r.f.table + (size_t)blockIdx.y * r.f.table_stride : nullptr);
 }
-__global__ __launch_bounds__(256) void radix_kpass_rows_kernel(const RadixRows r, int pass)
+__global__ __launch_bounds__(256) void radix_kpass_kernel(const RadixRows r, int pass)
 {
     const RadixParams p = radix_row(r, blockIdx.y);
     radix_kpass_body(p, pass);
 }
-__global__ __launch_bounds__(256) void radix_prob_rows_kernel(const RadixRows r, int use_k, int use_p, int nblocks_scale)
+__global__ __launch_bounds__(256) void radix_prob_kernel(const RadixRows r, int use_k, int use_p, int nblocks_scale)
 {
     const RadixParams p = radix_row(r, blockIdx.y);
     radix_prob_body(p, use_k, use_p, nblocks_scale);
 }
-__global__ __launch_bounds__(256) void radix_ppass_rows_kernel(const RadixRows r, int pass)
+__global__ __launch_bounds__(256) void radix_ppass_kernel(const RadixRows r, int pass)
 {
     const RadixParams p = radix_row(r, blockIdx.y);
     radix_ppass_body(p, pass);
 }
-__global__ __launch_bounds__(256) void radix_mask_rows_kernel(const RadixRows r, int use_p, int chunk)
+template <bool MINP>
+__global__ __launch_bounds__(256) void radix_mask_kernel(const RadixRows r, int use_p, int chunk, float min_p)
 {
     const RadixParams p = radix_row(r, blockIdx.y);
-    radix_mask_body(p, use_p, chunk);
+    radix_mask_body<MINP>(p, use_p, chunk, min_p);
 }
-// the filtered rows launches: row b's table is f.table + b * f.table_stride
-__global__ __launch_bounds__(256) void radix_scale_rows_filtered_kernel(const float* __restrict__ logits, const RadixRows r, int clear_words, const SampleFilter f)
+
+// The one-row tail, one wave over row 0.  ADVANCE: the stochastic twin of argmax_final_advance_kernel -- the draw is slot (*seq_dev + 1) % draws_size of a host-written
+// ring (system-scope load: the host rewrites the slots between replays), and the tail bumps the position, stores the sequence number and (ring != NULL) publishes
+// seq << 32 | token; else the draw is p.r.  TABLE: lane 0 counts the sample in the table before it stores / publishes the token.
+template <bool ADVANCE, bool TABLE>
+__global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixRows rr, int nchunks, int chunk)
 {
-    const RadixParams p = radix_row(r, blockIdx.y);
-    radix_scale_body<float, true>(logits + (size_t)blockIdx.y * r.logits_stride, p, clear_words, &f, f.table + (size_t)blockIdx.y * f.table_stride);
-}
-__global__ __launch_bounds__(256) void radix_mask_rows_minp_kernel(const RadixRows r, int use_p, int chunk, float min_p)
-{
-    const RadixParams p = radix_row(r, blockIdx.y);
-    radix_mask_body<true>(p, use_p, chunk, min_p);
+    const RadixParams& p = rr.p;
+    const int lane = threadIdx.x;
+    float r = p.r;
+    unsigned long long seq = 0ull;
+    if (ADVANCE)
+    {
+        seq = *p.seq_dev + 1ull;
+        const uint32_t* slot = reinterpret_cast<const uint32_t*>(p.draws) + (seq % (unsigned long long)p.draws_size);
+        r = __uint_as_float(__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+    }
+    const int result = radix_cdf_walk(p, r, nchunks, chunk, lane);
+    if (lane == 0)
+    {
+        if (TABLE) table_count(rr.f.table, result);
+        p.token_out[0] = result;
+        if (ADVANCE) publish_token(result, seq, p.pos, p.seq_dev, p.ring, p.ring_size);
+    }
 }
 
 // The rows tail, one workgroup: wave t walks row t's CDF (radix_cdf_walk: radix_cdf_kernel's additions in its order) at the draw draws[t] -- a system-scope load, the
 // host rewrites the draws between replays -- and the samples s_t meet in LDS; then one lane does the bookkeeping in plain stores.
 //   kRowsTokens:  token_out[b] = s_b, nothing advanced.
 //   kRowsAdvance: where active[b] != 0, token_out[b] = s_b and pos[b] += 1; an inactive row's words are not touched.
-//   kRowsChain:   argmax_chain_accept_kernel's rule with s_t in the place of a_t (token_out is tok[], pos the ONE position word).
+//   kRowsChain:   chain_accept with the samples (token_out is tok[], pos the ONE position word).
+// TABLE (kRowsTokens / kRowsAdvance): the lane counts row b's sample in row b's table before it stores the token -- in kRowsAdvance for the active rows only.  The chain
+// tail takes no table: row t would need the table plus the drafts 1 .. t.
 enum { kRowsTokens = 0, kRowsAdvance = 1, kRowsChain = 2 };
-template <int MODE>
+template <int MODE, bool TABLE>
 __global__ __launch_bounds__(256) void radix_rows_tail_kernel(const RadixRows r, int rows, int nchunks, int chunk, const int32_t* __restrict__ active, int32_t* __restrict__ result)
 {
+    static_assert(!TABLE || MODE == kRowsTokens || MODE == kRowsAdvance, "the chain tail takes no table");
     __shared__ int ss[4];
     const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
     if (t < rows)
@@ -1041,51 +983,15 @@ __global__ __launch_bounds__(256) void radix_rows_tail_kernel(const RadixRows r,
     if (threadIdx.x != 0) return;
     int32_t* tok = r.p.token_out;
     int32_t* pos = r.p.pos;
-    if (MODE == kRowsTokens)
-        for (int b = 0; b < rows; ++b) tok[b] = ss[b];
-    if (MODE == kRowsAdvance)
+    if (MODE == kRowsChain) chain_accept(ss, rows, tok, result, pos);
+    else
         for (int b = 0; b < rows; ++b)
-            if (active[b] != 0) { tok[b] = ss[b]; pos[b] += 1; }
-    if (MODE == kRowsChain)
-    {
-        int n_acc = rows - 1;
-        for (int i = rows - 2; i >= 0; --i)
-            if (ss[i] != tok[i + 1]) n_acc = i;
-        result[0] = n_acc + 1;
-        for (int i = 0; i <= n_acc; ++i) result[1 + i] = ss[i];
-        tok[0] = ss[n_acc];
-        *pos += n_acc + 1;
-    }
-}
-
-// The rows tail with token tables (kRowsTokens / kRowsAdvance; a launch of its own so that the tail above stays as it is): the same walks, and the lane counts row b's
-// sample in row b's table (table0 + b * table_stride) before it stores the token -- in kRowsAdvance for the active rows only.  The chain tail takes no table: row t would
-// need the table plus the drafts 1 .. t.
-template <int MODE>
-__global__ __launch_bounds__(256) void radix_rows_tail_table_kernel(const RadixRows r, int rows, int nchunks, int chunk, const int32_t* __restrict__ active, uint32_t* table0,
-                                                                    size_t table_stride)
-{
-    static_assert(MODE == kRowsTokens || MODE == kRowsAdvance, "the chain tail takes no table");
-    __shared__ int ss[4];
-    const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
-    if (t < rows)
-    {
-        const RadixParams p = radix_row(r, t);
-        const float draw = __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t*>(r.p.draws) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-        const int s = radix_cdf_walk(p, draw, nchunks, chunk, lane);
-        if (lane == 0) ss[t] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    int32_t* tok = r.p.token_out;
-    int32_t* pos = r.p.pos;
-    for (int b = 0; b < rows; ++b)
-    {
-        if (MODE == kRowsAdvance && active[b] == 0) continue;
-        table_count(table0 + (size_t)b * table_stride, ss[b]);
-        tok[b] = ss[b];
-        if (MODE == kRowsAdvance) pos[b] += 1;
-    }
+        {
+            if (MODE == kRowsAdvance && active[b] == 0) continue;
+            if (TABLE) table_count(r.f.table + (size_t)b * r.f.table_stride, ss[b]);
+            tok[b] = ss[b];
+            if (MODE == kRowsAdvance) pos[b] += 1;
+        }
 }
 
 // the one place that decides what a radix call launches: the entries below and sample_radix_plan_describe read it
@@ -1137,75 +1043,57 @@ static int make_filter(const mila_sample_filters* flt, uint32_t* table, size_t t
 
 struct RadixAdvance { const float* draws; int draws_size; int32_t* pos; unsigned long long* seq_dev; unsigned long long* ring; int ring_size; };
 
-// adv == nullptr: the draw is `r` and nothing is advanced
-template <typename T>
-static int run_radix(const T* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r, const RadixAdvance* adv,
-                     void* scratch, size_t scratch_bytes, hipStream_t s, const char* who, const SampleFilter* flt = nullptr)
-{
-    MILA_REQUIRE(logits && token_out, "%s: null pointer", who);
-    MILA_REQUIRE(!adv || (adv->draws && adv->pos && adv->seq_dev), "%s: null pointer", who);
-    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
-    MILA_REQUIRE(temperature > 0.0f, "%s: temperature must be > 0 (temperature <= 0 is the greedy sampler: sample_argmax)", who);
-    MILA_REQUIRE(top_k >= 0 && top_p > 0.0f && r >= 0.0f && r <= 1.0f, "%s: need top_k >= 0, top_p > 0, 0 <= r <= 1", who);
-    MILA_REQUIRE(!adv || adv->draws_size > 0, "%s: draws_size must be positive", who);
-    MILA_REQUIRE(!adv || (adv->ring ? adv->ring_size > 0 : adv->ring_size == 0), "%s: ring and ring_size go together", who);
-    const RadixPlan d = plan_radix(vocab, top_k, top_p, flt && flt->table, flt ? flt->min_p : 0.0f);
-    if (!scratch || scratch_bytes < d.scratch_need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, d.scratch_need);
-    MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, "%s: scratch must be 8-byte aligned", who);
-    RadixParams p{};
-    char* base = reinterpret_cast<char*>(scratch);
-    p.hdr = reinterpret_cast<RadixHeader*>(base);
-    p.khist = reinterpret_cast<uint32_t*>(base + sizeof(RadixHeader));
-    p.phist = reinterpret_cast<unsigned long long*>(p.khist + (size_t)kRadixPasses * kRadixBins);
-    p.red = reinterpret_cast<float*>(base + sizeof(RadixHeader) + kRadixHistBytes);
-    p.w = p.red + 2 * kSampBlocks;
-    p.token_out = token_out; p.vocab = vocab; p.top_k = top_k;
-    p.softcap = softcap; p.temperature = temperature; p.top_p = top_p; p.r = r;
-    if (adv) { p.draws = adv->draws; p.draws_size = adv->draws_size; p.pos = adv->pos; p.seq_dev = adv->seq_dev; p.ring = adv->ring; p.ring_size = adv->ring_size; }
-    const int clear_words = (int)((sizeof(RadixHeader) + kRadixHistBytes) / 4);
-    if constexpr (std::is_same<T, float>::value)
-    {
-        if (d.scale_filtered) hipLaunchKernelGGL(radix_scale_filtered_kernel, dim3(d.scale_blocks), dim3(256), 0, s, logits, p, clear_words, *flt);
-        else hipLaunchKernelGGL(radix_scale_kernel<T>, dim3(d.scale_blocks), dim3(256), 0, s, logits, p, clear_words);
-    }
-    else hipLaunchKernelGGL(radix_scale_kernel<T>, dim3(d.scale_blocks), dim3(256), 0, s, logits, p, clear_words);
-    for (int pass = 0; pass < d.k_passes; ++pass) hipLaunchKernelGGL(radix_kpass_kernel, dim3(d.blocks), dim3(256), 0, s, p, pass);
-    hipLaunchKernelGGL(radix_prob_kernel, dim3(d.blocks), dim3(256), 0, s, p, d.k_passes ? 1 : 0, d.p_passes ? 1 : 0, d.scale_blocks);
-    for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_kernel, dim3(d.blocks), dim3(256), 0, s, p, pass);
-    if (d.mask_filtered) hipLaunchKernelGGL(radix_mask_minp_kernel, dim3(d.nchunks), dim3(256), 0, s, p, d.p_passes ? 1 : 0, d.chunk, flt->min_p);
-    else hipLaunchKernelGGL(radix_mask_kernel, dim3(d.nchunks), dim3(256), 0, s, p, d.p_passes ? 1 : 0, d.chunk);
-    if (d.scale_filtered)
-    {
-        if (adv) hipLaunchKernelGGL(radix_cdf_table_kernel<true>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk, flt->table);
-        else hipLaunchKernelGGL(radix_cdf_table_kernel<false>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk, flt->table);
-    }
-    else if (adv) hipLaunchKernelGGL(radix_cdf_kernel<true>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
-    else hipLaunchKernelGGL(radix_cdf_kernel<false>, dim3(1), dim3(64), 0, s, p, d.nchunks, d.chunk);
-    return check_hip(hipGetLastError(), who);
-}
-
 // row stride of the rows scratch: the one-row need, rounded up so that every row's RadixHeader (and its 64-bit histogram) stays 8-byte aligned
 static size_t radix_row_stride(int vocab) { return (plan_radix(vocab, 0, 1.0f).scratch_need + 7) & ~(size_t)7; }
 
-// The radix pipeline over `rows` rows in ONE pipeline: plan_radix's launches for one row, each with the rows in grid.y, and the rows tail in the place of the cdf
-// launch.  mode kRowsTokens: pos / active / result unused; kRowsAdvance: pos[rows], active[rows]; kRowsChain: token_out is tok[rows], pos the one position word.
-static int run_radix_rows(int mode, const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k, float top_p,
-                          const float* draws, void* scratch, size_t scratch_bytes, int32_t* pos, const int32_t* active, int32_t* result, hipStream_t s, const char* who,
-                          const SampleFilter* flt = nullptr)
+// What an entry asks of the pipeline.  kOneRow is the one-row call (radix_cdf_kernel behind the stages): the draw is `r`, or with `adv` the draw ring at the sequence
+// number, and the scratch need is plan_radix's for one row, not rounded up to the row stride.  The kRows* modes end in radix_rows_tail_kernel<mode> with one draw per
+// row in `draws`: kRowsTokens leaves pos / active / result unused; kRowsAdvance takes pos[rows], active[rows]; kRowsChain takes token_out = tok[rows], pos = the one
+// position word, result.
+constexpr int kOneRow = -1;
+template <typename T>
+struct RadixCall
 {
-    MILA_REQUIRE(logits && token_out && draws, "%s: null pointer", who);
-    MILA_REQUIRE(mode == kRowsTokens || pos, "%s: null pointer", who);
-    MILA_REQUIRE(mode != kRowsAdvance || active, "%s: null pointer", who);
-    MILA_REQUIRE(mode != kRowsChain || result, "%s: null pointer", who);
-    if (mode == kRowsChain) MILA_REQUIRE(rows >= 2 && rows <= 4, "%s: T=%d rows outside 2 .. 4", who, rows);
-    else MILA_REQUIRE(rows >= 1 && rows <= 4, "%s: rows=%d outside 1 .. 4", who, rows);
-    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
-    MILA_REQUIRE(logits_stride >= (size_t)vocab, "%s: logits_stride %zu < vocab %d", who, logits_stride, vocab);
-    MILA_REQUIRE(temperature > 0.0f, "%s: temperature must be > 0 (temperature <= 0 is the greedy sampler: sample_argmax)", who);
-    MILA_REQUIRE(top_k >= 0 && top_p > 0.0f, "%s: need top_k >= 0, top_p > 0", who);
-    MILA_REQUIRE(mode != kRowsChain || !flt, "%s: the chain tail takes no filters", who);
-    const RadixPlan d = plan_radix(vocab, top_k, top_p, flt && flt->table, flt ? flt->min_p : 0.0f);
-    const size_t row_stride = radix_row_stride(vocab), need = row_stride * (size_t)rows;
+    int mode;
+    const T* logits;
+    size_t logits_stride;
+    int32_t* token_out;
+    int rows, vocab;
+    float softcap, temperature;
+    int top_k;
+    float top_p, r;
+    const RadixAdvance* adv;
+    const float* draws;
+    int32_t* pos;
+    const int32_t* active;
+    int32_t* result;
+    const SampleFilter* flt;
+};
+
+// The radix pipeline of every entry: plan_radix's launches for one row, each with the rows in grid.y, and the mode's tail.
+template <typename T>
+static int run_radix(const RadixCall<T>& c, void* scratch, size_t scratch_bytes, hipStream_t s, const char* who)
+{
+    const bool one = c.mode == kOneRow;
+    const RadixAdvance* adv = c.adv;
+    const SampleFilter* flt = c.flt;
+    MILA_REQUIRE(c.logits && c.token_out && (one || c.draws), "%s: null pointer", who);
+    MILA_REQUIRE(!adv || (adv->draws && adv->pos && adv->seq_dev), "%s: null pointer", who);
+    MILA_REQUIRE(one || c.mode == kRowsTokens || c.pos, "%s: null pointer", who);
+    MILA_REQUIRE(c.mode != kRowsAdvance || c.active, "%s: null pointer", who);
+    MILA_REQUIRE(c.mode != kRowsChain || c.result, "%s: null pointer", who);
+    if (c.mode == kRowsChain) MILA_REQUIRE(c.rows >= 2 && c.rows <= 4, "%s: T=%d rows outside 2 .. 4", who, c.rows);
+    else MILA_REQUIRE(c.rows >= 1 && c.rows <= 4, "%s: rows=%d outside 1 .. 4", who, c.rows);
+    MILA_REQUIRE(c.vocab > 0, "%s: vocab must be positive", who);
+    MILA_REQUIRE(one || c.logits_stride >= (size_t)c.vocab, "%s: logits_stride %zu < vocab %d", who, c.logits_stride, c.vocab);
+    MILA_REQUIRE(c.temperature > 0.0f, "%s: temperature must be > 0 (temperature <= 0 is the greedy sampler: sample_argmax)", who);
+    if (one) MILA_REQUIRE(c.top_k >= 0 && c.top_p > 0.0f && c.r >= 0.0f && c.r <= 1.0f, "%s: need top_k >= 0, top_p > 0, 0 <= r <= 1", who);
+    else MILA_REQUIRE(c.top_k >= 0 && c.top_p > 0.0f, "%s: need top_k >= 0, top_p > 0", who);
+    MILA_REQUIRE(!adv || adv->draws_size > 0, "%s: draws_size must be positive", who);
+    MILA_REQUIRE(!adv || (adv->ring ? adv->ring_size > 0 : adv->ring_size == 0), "%s: ring and ring_size go together", who);
+    MILA_REQUIRE(c.mode != kRowsChain || !flt, "%s: the chain tail takes no filters", who);
+    const RadixPlan d = plan_radix(c.vocab, c.top_k, c.top_p, flt && flt->table, flt ? flt->min_p : 0.0f);
+    const size_t row_stride = radix_row_stride(c.vocab), need = one ? d.scratch_need : row_stride * (size_t)c.rows;
     if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, "%s: scratch must be 8-byte aligned", who);
     RadixRows r{};
@@ -1216,27 +1104,54 @@ static int run_radix_rows(int mode, const float* logits, size_t logits_stride, i
     p.phist = reinterpret_cast<unsigned long long*>(p.khist + (size_t)kRadixPasses * kRadixBins);
     p.red = reinterpret_cast<float*>(base + sizeof(RadixHeader) + kRadixHistBytes);
     p.w = p.red + 2 * kSampBlocks;
-    p.token_out = token_out; p.vocab = vocab; p.top_k = top_k;
-    p.softcap = softcap; p.temperature = temperature; p.top_p = top_p;
-    p.draws = draws; p.pos = pos;
-    r.row_stride = row_stride; r.logits_stride = logits_stride;
+    p.token_out = c.token_out; p.vocab = c.vocab; p.top_k = c.top_k;
+    p.softcap = c.softcap; p.temperature = c.temperature; p.top_p = c.top_p; p.r = c.r;
+    p.draws = c.draws; p.pos = c.pos;
+    if (adv) { p.draws = adv->draws; p.draws_size = adv->draws_size; p.pos = adv->pos; p.seq_dev = adv->seq_dev; p.ring = adv->ring; p.ring_size = adv->ring_size; }
+    r.row_stride = row_stride; r.logits_stride = c.logits_stride;
+    if (flt) r.f = *flt;
     const int clear_words = (int)((sizeof(RadixHeader) + kRadixHistBytes) / 4);
-    const unsigned R = (unsigned)rows;
-    if (d.scale_filtered) hipLaunchKernelGGL(radix_scale_rows_filtered_kernel, dim3(d.scale_blocks, R), dim3(256), 0, s, logits, r, clear_words, *flt);
-    else hipLaunchKernelGGL(radix_scale_rows_kernel, dim3(d.scale_blocks, R), dim3(256), 0, s, logits, r, clear_words);
-    for (int pass = 0; pass < d.k_passes; ++pass) hipLaunchKernelGGL(radix_kpass_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, pass);
-    hipLaunchKernelGGL(radix_prob_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, d.k_passes ? 1 : 0, d.p_passes ? 1 : 0, d.scale_blocks);
-    for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_rows_kernel, dim3(d.blocks, R), dim3(256), 0, s, r, pass);
-    if (d.mask_filtered) hipLaunchKernelGGL(radix_mask_rows_minp_kernel, dim3(d.nchunks, R), dim3(256), 0, s, r, d.p_passes ? 1 : 0, d.chunk, flt->min_p);
-    else hipLaunchKernelGGL(radix_mask_rows_kernel, dim3(d.nchunks, R), dim3(256), 0, s, r, d.p_passes ? 1 : 0, d.chunk);
-    if (d.scale_filtered && mode == kRowsTokens)
-        hipLaunchKernelGGL(radix_rows_tail_table_kernel<kRowsTokens>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, flt->table, flt->table_stride);
-    else if (d.scale_filtered && mode == kRowsAdvance)
-        hipLaunchKernelGGL(radix_rows_tail_table_kernel<kRowsAdvance>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, flt->table, flt->table_stride);
-    else if (mode == kRowsTokens) hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsTokens>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
-    else if (mode == kRowsAdvance) hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsAdvance>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
-    else hipLaunchKernelGGL(radix_rows_tail_kernel<kRowsChain>, dim3(1), dim3(256), 0, s, r, rows, d.nchunks, d.chunk, active, result);
+    const int use_k = d.k_passes ? 1 : 0, use_p = d.p_passes ? 1 : 0;
+    const unsigned R = (unsigned)c.rows;
+    const dim3 wg(256);
+    if constexpr (std::is_same<T, float>::value)
+    {
+        if (d.scale_filtered) hipLaunchKernelGGL((radix_scale_kernel<float, true>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
+        else hipLaunchKernelGGL((radix_scale_kernel<float, false>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
+    }
+    else hipLaunchKernelGGL((radix_scale_kernel<T, false>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
+    for (int pass = 0; pass < d.k_passes; ++pass) hipLaunchKernelGGL(radix_kpass_kernel, dim3(d.blocks, R), wg, 0, s, r, pass);
+    hipLaunchKernelGGL(radix_prob_kernel, dim3(d.blocks, R), wg, 0, s, r, use_k, use_p, d.scale_blocks);
+    for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_kernel, dim3(d.blocks, R), wg, 0, s, r, pass);
+    if (d.mask_filtered) hipLaunchKernelGGL(radix_mask_kernel<true>, dim3(d.nchunks, R), wg, 0, s, r, use_p, d.chunk, flt->min_p);
+    else hipLaunchKernelGGL(radix_mask_kernel<false>, dim3(d.nchunks, R), wg, 0, s, r, use_p, d.chunk, 0.0f);
+    // the tail: <mode, table> picks the instantiation
+    const bool tab = d.scale_filtered != 0;
+    auto cdf = [&](auto k) { hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, s, r, d.nchunks, d.chunk); };
+    auto tail = [&](auto k) { hipLaunchKernelGGL(k, dim3(1), wg, 0, s, r, c.rows, d.nchunks, d.chunk, c.active, c.result); };
+    if (one && adv) { if (tab) cdf(radix_cdf_kernel<true, true>); else cdf(radix_cdf_kernel<true, false>); }
+    else if (one) { if (tab) cdf(radix_cdf_kernel<false, true>); else cdf(radix_cdf_kernel<false, false>); }
+    else if (c.mode == kRowsTokens) { if (tab) tail(radix_rows_tail_kernel<kRowsTokens, true>); else tail(radix_rows_tail_kernel<kRowsTokens, false>); }
+    else if (c.mode == kRowsAdvance) { if (tab) tail(radix_rows_tail_kernel<kRowsAdvance, true>); else tail(radix_rows_tail_kernel<kRowsAdvance, false>); }
+    else tail(radix_rows_tail_kernel<kRowsChain, false>);
     return check_hip(hipGetLastError(), who);
+}
+
+// the one-row entries: the draw `r`, or with `adv` the draw ring
+template <typename T>
+static int call_radix_one(const T* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r, const RadixAdvance* adv,
+                         void* scratch, size_t scratch_bytes, hipStream_t s, const char* who, const SampleFilter* flt = nullptr)
+{
+    const RadixCall<T> c{kOneRow, logits, 0, token_out, 1, vocab, softcap, temperature, top_k, top_p, r, adv, nullptr, nullptr, nullptr, nullptr, flt};
+    return run_radix(c, scratch, scratch_bytes, s, who);
+}
+// the rows entries: one draw per row in `draws`
+static int call_radix_rows(int mode, const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k, float top_p,
+                          const float* draws, void* scratch, size_t scratch_bytes, int32_t* pos, const int32_t* active, int32_t* result, hipStream_t s, const char* who,
+                          const SampleFilter* flt = nullptr)
+{
+    const RadixCall<float> c{mode, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, 0.0f, nullptr, draws, pos, active, result, flt};
+    return run_radix(c, scratch, scratch_bytes, s, who);
 }
 
 // The penalized greedy sampler over `rows` rows: argmax(x3), ties to the lower id, in the two launches of sample_argmax_*: the partial stage computes x3 from logits,
@@ -1244,22 +1159,15 @@ static int run_radix_rows(int mode, const float* logits, size_t logits_stride, i
 static int run_argmax_filtered(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, const SampleFilter& f, void* scratch,
                                size_t scratch_bytes, const RadixAdvance* adv, int32_t* positions, const int32_t* active, hipStream_t s, const char* who)
 {
-    const size_t per_row = (size_t)kArgmaxBlocks * 8, need = per_row * (size_t)rows;
-    if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
-    float* pv = reinterpret_cast<float*>(scratch);
-    int* pi = reinterpret_cast<int*>(pv + kArgmaxBlocks);
-    int blocks = (vocab + 255) / 256;
-    if (blocks > kArgmaxBlocks) blocks = kArgmaxBlocks;
-    const int row_floats = (int)(per_row / sizeof(float));
-    hipLaunchKernelGGL(argmax_partial_filtered_kernel, dim3(blocks, (unsigned)rows), dim3(256), 0, s, logits, logits_stride, softcap, f, pv, row_floats, vocab);
-    int rc = check_hip(hipGetLastError(), who);
+    ArgmaxPartials a;
+    const int rc = launch_argmax_partials(logits, logits_stride, rows, vocab, softcap, &f, scratch, scratch_bytes, s, who, a);
     if (rc) return rc;
     if (positions)
-        hipLaunchKernelGGL(argmax_rows_final_advance_table_kernel, dim3(rows), dim3(256), 0, s, pv, token_out, positions, active, blocks, row_floats, f.table, f.table_stride);
+        hipLaunchKernelGGL(argmax_rows_final_advance_kernel<true>, dim3(rows), dim3(256), 0, s, a.pv, token_out, positions, active, a.blocks, a.row_floats, f.table, f.table_stride);
     else if (adv)
-        hipLaunchKernelGGL(argmax_final_advance_table_kernel, dim3(1), dim3(256), 0, s, pv, pi, blocks, token_out, adv->pos, adv->seq_dev, adv->ring, adv->ring_size, f.table);
+        hipLaunchKernelGGL(argmax_final_advance_kernel<true>, dim3(1), dim3(256), 0, s, a.pv, a.pi, a.blocks, token_out, adv->pos, adv->seq_dev, adv->ring, adv->ring_size, f.table);
     else
-        hipLaunchKernelGGL(argmax_final_table_kernel, dim3(1), dim3(256), 0, s, pv, pi, blocks, token_out, f.table);
+        hipLaunchKernelGGL(argmax_final_kernel<true>, dim3(1), dim3(256), 0, s, a.pv, a.pi, a.blocks, token_out, f.table);
     return check_hip(hipGetLastError(), who);
 }
 
@@ -1283,16 +1191,11 @@ int mila_cdna4_sample_argmax_advance_fp32(const float* logits, int32_t* token_ou
     MILA_REQUIRE(logits && token_out && position_dev, "sample_argmax_advance_fp32: null pointer");
     MILA_REQUIRE(vocab > 0, "sample_argmax_advance_fp32: vocab must be positive");
     MILA_REQUIRE((ring == nullptr) == (seq_dev == nullptr) && (ring == nullptr || ring_size > 0), "sample_argmax_advance_fp32: ring, seq_dev and ring_size go together");
-    const size_t need = (size_t)kArgmaxBlocks * 8;
-    if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "sample_argmax_advance_fp32: scratch %zu bytes < required %zu", scratch_bytes, need);
-    float* pv = reinterpret_cast<float*>(scratch);
-    int* pi = reinterpret_cast<int*>(pv + kArgmaxBlocks);
-    int blocks = (vocab + 255) / 256;
-    if (blocks > kArgmaxBlocks) blocks = kArgmaxBlocks;
-    hipLaunchKernelGGL(argmax_partial_kernel<float>, dim3(blocks), dim3(256), 0, as_stream(stream), logits, pv, pi, vocab);
-    int rc = check_hip(hipGetLastError(), "sample_argmax_advance_fp32");
+    ArgmaxPartials a;
+    const int rc = launch_argmax_partials(logits, 0, 1, vocab, 0.0f, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_argmax_advance_fp32", a);
     if (rc) return rc;
-    hipLaunchKernelGGL(argmax_final_advance_kernel, dim3(1), dim3(256), 0, as_stream(stream), pv, pi, blocks, token_out, position_dev, seq_dev, ring, ring_size);
+    hipLaunchKernelGGL(argmax_final_advance_kernel<false>, dim3(1), dim3(256), 0, as_stream(stream), a.pv, a.pi, a.blocks, token_out, position_dev, seq_dev, ring, ring_size,
+                       (uint32_t*)nullptr);
     MILA_LAUNCH_CHECK("sample_argmax_advance_fp32");
 }
 
@@ -1306,7 +1209,8 @@ int mila_cdna4_sample_argmax_final_advance(int32_t* token_out, const void* scrat
     if (scratch_bytes < (size_t)kArgmaxBlocks * 8) return set_error(MILA_E_SCRATCH_TOO_SMALL, "sample_argmax_final_advance: scratch %zu bytes < required %zu", scratch_bytes, (size_t)kArgmaxBlocks * 8);
     const float* pv = reinterpret_cast<const float*>(scratch);
     const int* pi = reinterpret_cast<const int*>(pv + kArgmaxBlocks);
-    hipLaunchKernelGGL(argmax_final_advance_kernel, dim3(1), dim3(256), 0, as_stream(stream), pv, pi, blocks, token_out, position_dev, seq_dev, ring, ring_size);
+    hipLaunchKernelGGL(argmax_final_advance_kernel<false>, dim3(1), dim3(256), 0, as_stream(stream), pv, pi, blocks, token_out, position_dev, seq_dev, ring, ring_size,
+                       (uint32_t*)nullptr);
     MILA_LAUNCH_CHECK("sample_argmax_final_advance");
 }
 
@@ -1319,8 +1223,8 @@ int mila_cdna4_sample_argmax_rows_final_advance(int32_t* token_out, const void* 
     MILA_REQUIRE(blocks > 0 && blocks <= kArgmaxBlocks, "sample_argmax_rows_final_advance: blocks %d out of range (1 .. %d)", blocks, kArgmaxBlocks);
     const size_t per_row = (size_t)kArgmaxBlocks * 8;
     if (scratch_bytes < per_row * B) return set_error(MILA_E_SCRATCH_TOO_SMALL, "sample_argmax_rows_final_advance: scratch %zu bytes < required %zu", scratch_bytes, per_row * B);
-    hipLaunchKernelGGL(argmax_rows_final_advance_kernel, dim3(B), dim3(256), 0, as_stream(stream), reinterpret_cast<const float*>(scratch), token_out, positions_dev, active_dev,
-                       blocks, (int)(per_row / sizeof(float)));
+    hipLaunchKernelGGL(argmax_rows_final_advance_kernel<false>, dim3(B), dim3(256), 0, as_stream(stream), reinterpret_cast<const float*>(scratch), token_out, positions_dev,
+                       active_dev, blocks, (int)(per_row / sizeof(float)), (uint32_t*)nullptr, (size_t)0);
     MILA_LAUNCH_CHECK("sample_argmax_rows_final_advance");
 }
 
@@ -1373,13 +1277,13 @@ size_t mila_cdna4_sample_radix_scratch_bytes(int vocab) { return vocab > 0 ? pla
 int mila_cdna4_sample_radix_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
                                  void* scratch, size_t scratch_bytes, mila_stream_t stream)
 {
-    return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_fp32");
+    return call_radix_one<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_fp32");
 }
 
 int mila_cdna4_sample_radix_bf16(const uint16_t* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
                                  void* scratch, size_t scratch_bytes, mila_stream_t stream)
 {
-    return run_radix<uint16_t>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_bf16");
+    return call_radix_one<uint16_t>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_bf16");
 }
 
 int mila_cdna4_sample_radix_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
@@ -1387,7 +1291,7 @@ int mila_cdna4_sample_radix_advance_fp32(const float* logits, int32_t* token_out
                                          unsigned long long* seq_dev, unsigned long long* ring, int ring_size, mila_stream_t stream)
 {
     const RadixAdvance adv{draws, draws_size, position_dev, seq_dev, ring, ring_size};
-    return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream),
+    return call_radix_one<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream),
                             "sample_radix_advance_fp32");
 }
 
@@ -1396,7 +1300,7 @@ size_t mila_cdna4_sample_radix_rows_scratch_bytes(int rows, int vocab) { return 
 int mila_cdna4_sample_radix_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k,
                                       float top_p, const float* draws, void* scratch, size_t scratch_bytes, mila_stream_t stream)
 {
-    return run_radix_rows(kRowsTokens, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, nullptr, nullptr, nullptr,
+    return call_radix_rows(kRowsTokens, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, nullptr, nullptr, nullptr,
                           as_stream(stream), "sample_radix_rows_fp32");
 }
 
@@ -1404,14 +1308,14 @@ int mila_cdna4_sample_radix_rows_advance_fp32(const float* logits, size_t logits
                                               float top_p, const float* draws, void* scratch, size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev,
                                               mila_stream_t stream)
 {
-    return run_radix_rows(kRowsAdvance, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, positions_dev, active_dev,
+    return call_radix_rows(kRowsAdvance, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, positions_dev, active_dev,
                           nullptr, as_stream(stream), "sample_radix_rows_advance_fp32");
 }
 
 int mila_cdna4_sample_radix_chain_accept_fp32(int32_t* tok, int32_t* result, const float* logits, size_t logits_stride, int T, int vocab, float softcap, float temperature,
                                               int top_k, float top_p, const float* draws, void* scratch, size_t scratch_bytes, int32_t* position_dev, mila_stream_t stream)
 {
-    return run_radix_rows(kRowsChain, logits, logits_stride, tok, T, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, position_dev, nullptr, result,
+    return call_radix_rows(kRowsChain, logits, logits_stride, tok, T, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, position_dev, nullptr, result,
                           as_stream(stream), "sample_radix_chain_accept_fp32");
 }
 
@@ -1442,7 +1346,7 @@ int mila_cdna4_sample_radix_filtered_fp32(const float* logits, int32_t* token_ou
     SampleFilter f{};
     const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_radix_filtered_fp32");
     if (rc) return rc;
-    return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_filtered_fp32", &f);
+    return call_radix_one<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_filtered_fp32", &f);
 }
 
 int mila_cdna4_sample_radix_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
@@ -1453,7 +1357,7 @@ int mila_cdna4_sample_radix_filtered_advance_fp32(const float* logits, int32_t* 
     const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_radix_filtered_advance_fp32");
     if (rc) return rc;
     const RadixAdvance adv{draws, draws_size, position_dev, seq_dev, ring, ring_size};
-    return run_radix<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream),
+    return call_radix_one<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream),
                             "sample_radix_filtered_advance_fp32", &f);
 }
 
@@ -1464,7 +1368,7 @@ int mila_cdna4_sample_radix_filtered_rows_fp32(const float* logits, size_t logit
     SampleFilter f{};
     const int rc = make_filter(filters, table, table_stride, rows, vocab, f, "sample_radix_filtered_rows_fp32");
     if (rc) return rc;
-    return run_radix_rows(kRowsTokens, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, nullptr, nullptr, nullptr,
+    return call_radix_rows(kRowsTokens, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, nullptr, nullptr, nullptr,
                           as_stream(stream), "sample_radix_filtered_rows_fp32", &f);
 }
 
@@ -1475,7 +1379,7 @@ int mila_cdna4_sample_radix_filtered_rows_advance_fp32(const float* logits, size
     SampleFilter f{};
     const int rc = make_filter(filters, table, table_stride, rows, vocab, f, "sample_radix_filtered_rows_advance_fp32");
     if (rc) return rc;
-    return run_radix_rows(kRowsAdvance, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, positions_dev, active_dev,
+    return call_radix_rows(kRowsAdvance, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, positions_dev, active_dev,
                           nullptr, as_stream(stream), "sample_radix_filtered_rows_advance_fp32", &f);
 }
 
