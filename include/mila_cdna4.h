@@ -844,6 +844,68 @@ MILA_API int mila_cdna4_sample_argmax_filtered_rows_advance_fp32(const float* lo
                                                                  const mila_sample_filters* filters, uint32_t* table, size_t table_stride, void* scratch,
                                                                  size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Logit bias (ABI 4, additive; csrc/sampling.hip): an additive bias per token, and through it banned tokens, a closed answer set (allowed tokens) and min_tokens (the
+ * stop tokens banned until the n-th sample) -- the `logit_bias`, `bad_words_ids`, `allowed_token_ids` and `min_tokens` of the HF / OpenAI / vLLM front ends.  All four
+ * are ONE mechanism: a dense table of fp32 values, read beside the logits in the sampler's first launch.  The reference names composable filters over one sampler
+ * (Specifications/TokenSampling.md 3.3) and ships an OpenAI-compatible server, but has no kernel for any of this: these entries anticipate that surface and replace no
+ * launcher.  Mila/TokenBias.h (host only) composes a request's four controls into a table.
+ *
+ * THE TABLE.  `vocab` fp32 values per row on the device (token_bias_bytes(vocab) bytes), each finite or -inf.  token_bias_fill sets row `row` of a table
+ * (bias + row * bias_stride floats) to one value; token_bias_set scatters n values to n token ids, both held in DEVICE memory: ids outside [0, vocab) are skipped,
+ * duplicate ids in one call are the caller's to avoid (two plain stores race).  Both run in stream order: a table may be updated between two replays of a captured step
+ * that reads it (the pointer is what is captured).
+ *
+ * THE ADJUSTED LOGIT gains one step between the softcap and the penalties of the sampling-filters section:
+ *     x0 = softcap > 0 ? softcap * tanhf(l / softcap) : l
+ *     xb = x0 + bias[i]                                                      one fp32 addition, rounded to nearest; only where a bias table is given
+ *     x1 .. x3 = the penalties, on xb in the place of x0
+ *     x  = x3 / temperature
+ * The bias comes before the penalties (vLLM's order: the repetition penalty's sign test sees the biased value) and after the softcap (the capped logits are the
+ * model's logits).  -inf stays -inf through every later step: x1 is a product with rep or 1 / rep > 0, x2 and x3 subtract finite values, the temperature is positive.
+ * A TOKEN WHOSE BIAS IS -inf IS NEVER RETURNED, at any draw in [0, 1] and under any top-k / top-p / min-p: its e = expf(-inf - max) is 0, the walk of the inverse CDF
+ * visits only e > 0, and where the running sum never reaches r * total (the two are added in different orders, so next to r = 1 they can differ) a biased call returns
+ * the LAST entry with nonzero mass, not vocab - 1 as the unbiased samplers do.  Caller's contract: at least one token of a row has a finite bias.
+ * GREEDY.  sample_argmax_biased_* take argmax(x3), ties to the lower id, in the two launches of sample_argmax_filtered_*; the table may be NULL (a bias without
+ * penalties).
+ * The samplers never write `logits`: log-probabilities (token_logprobs_*, the scoring entries) stay those of the capped, UNBIASED logits.
+ *
+ * Each sample_*_biased_* entry is the sample_*_filtered_* entry of the same name plus `bias, bias_stride`, and the filtered entries are calls of them.  bias: row 0's
+ * table; NULL = exactly the filtered entry, including its NULL-table behaviour, launching the kernels it launched.  bias_stride: floats between the tables of two rows;
+ * 0 = one table shared by all rows; with more than one row a stride from 1 to vocab - 1 is refused.  A biased call launches exactly what sample_radix_plan_describe
+ * reports for the unfiltered call: the bias rides in the scale launch (four instantiations: none, table, bias, table + bias), and the tail is the instantiation with the
+ * fallback above.  Scratch: as for the mirrored entry.
+ * Refused before any device work, beside what the mirrored entry refuses (MILA_E_INVALID_ARGUMENT): a NaN or +inf fill value; n < 0; a null table, id or value pointer with
+ * n > 0; the stride rule above. */
+MILA_API size_t mila_cdna4_token_bias_bytes(int vocab);
+MILA_API int mila_cdna4_token_bias_fill(float* bias, size_t bias_stride, int row, int vocab, float value, mila_stream_t stream);
+MILA_API int mila_cdna4_token_bias_set(float* bias, size_t bias_stride, int row, int vocab, const int32_t* ids_dev, const float* values_dev, int n, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_biased_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                                 const mila_sample_filters* filters, uint32_t* table, const float* bias, size_t bias_stride, void* scratch,
+                                                 size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_biased_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
+                                                         const float* draws, int draws_size, const mila_sample_filters* filters, uint32_t* table, const float* bias,
+                                                         size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* position_dev, unsigned long long* seq_dev,
+                                                         unsigned long long* ring, int ring_size, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_biased_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                      float temperature, int top_k, float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table,
+                                                      size_t table_stride, const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes,
+                                                      mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_biased_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                              float temperature, int top_k, float top_p, const float* draws, const mila_sample_filters* filters,
+                                                              uint32_t* table, size_t table_stride, const float* bias, size_t bias_stride, void* scratch,
+                                                              size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_biased_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
+                                                  const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_biased_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters,
+                                                          uint32_t* table, const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes,
+                                                          int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring, int ring_size,
+                                                          mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_biased_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                               const mila_sample_filters* filters, uint32_t* table, size_t table_stride, const float* bias,
+                                                               size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* positions_dev,
+                                                               const int32_t* active_dev, mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,18 @@ def load():
     main.mila_cdna4_sample_argmax_filtered_fp32.argtypes = [p, p, i, f, p, p, p, z, p]                            # logits token_out | vocab softcap | filters table | scratch bytes
     main.mila_cdna4_sample_argmax_filtered_advance_fp32.argtypes = [p, p, i, f, p, p, p, z, p, p, p, i, p]        # ... | position_dev seq_dev ring ring_size
     main.mila_cdna4_sample_argmax_filtered_rows_advance_fp32.argtypes = [p, z, p, i, i, f, p, p, z, p, z, p, p, p]       # logits logits_stride token_out | rows vocab softcap | filters table table_stride | scratch bytes | positions_dev active_dev
+    # logit bias (csrc/sampling.hip: the bias table and the biased siblings of the filtered entries: `bias bias_stride` behind the table arguments)
+    main.mila_cdna4_token_bias_bytes.argtypes = [i]
+    main.mila_cdna4_token_bias_bytes.restype = z
+    main.mila_cdna4_token_bias_fill.argtypes = [p, z, i, i, f, p]                                                 # bias bias_stride row vocab | value
+    main.mila_cdna4_token_bias_set.argtypes = [p, z, i, i, p, p, i, p]                                            # bias bias_stride row vocab | ids_dev values_dev n
+    main.mila_cdna4_sample_radix_biased_fp32.argtypes = [p, p, i, f, f, i, f, f, p, p, p, z, p, z, p]             # ... top_p r | filters table | bias bias_stride | scratch bytes
+    main.mila_cdna4_sample_radix_biased_advance_fp32.argtypes = [p, p, i, f, f, i, f, p, i, p, p, p, z, p, z, p, p, p, i, p]
+    main.mila_cdna4_sample_radix_biased_rows_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, p, z, p, z, p, z, p]
+    main.mila_cdna4_sample_radix_biased_rows_advance_fp32.argtypes = [p, z, p, i, i, f, f, i, f, p, p, p, z, p, z, p, z, p, p, p]
+    main.mila_cdna4_sample_argmax_biased_fp32.argtypes = [p, p, i, f, p, p, p, z, p, z, p]
+    main.mila_cdna4_sample_argmax_biased_advance_fp32.argtypes = [p, p, i, f, p, p, p, z, p, z, p, p, p, i, p]
+    main.mila_cdna4_sample_argmax_biased_rows_advance_fp32.argtypes = [p, z, p, i, i, f, p, p, z, p, z, p, z, p, p, p]
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -422,6 +434,72 @@ def sample_argmax_filtered_rows_advance(logits, token_out, softcap, filters, tab
          scratch, _nbytes(scratch), positions_dev, active_dev)
 
 
+# ---- logit bias: a float32 table [vocab] or [rows, vocab] on the device; the biased entries take `bias` (None: the filtered entry) and `bias_stride` (None: 0 for a
+# one-dimensional table, which every row then shares, else the row length)
+def token_bias_bytes(vocab):
+    return int(load().mila_cdna4_token_bias_bytes(int(vocab)))
+
+
+def token_bias_fill(bias, value, row=0):
+    """every value of row `row` of the bias table becomes `value` (finite or -inf)"""
+    stride, V = _table_head(bias, row)
+    call("token_bias_fill", bias, stride, int(row), V, float(value))
+
+
+def token_bias_set(bias, ids_dev, values_dev, row=0, n=None):
+    """bias[row][ids[j]] = values[j] for n ids / values on the device (int32 / float32); ids outside the vocabulary are skipped"""
+    stride, V = _table_head(bias, row)
+    call("token_bias_set", bias, stride, int(row), V, ids_dev, values_dev, int(ids_dev.numel() if n is None else n))
+
+
+def _bias_stride(bias, bias_stride):
+    if bias_stride is None:
+        bias_stride = 0 if bias is None or bias.dim() == 1 else int(bias.shape[-1])
+    return C.c_size_t(int(bias_stride))
+
+
+def sample_radix_biased(logits, token_out, softcap, temperature, top_k, top_p, r, filters, table, bias, scratch, bias_stride=None):
+    """sample_radix_filtered with the bias table (float32 [vocab], or None: the filtered entry)"""
+    call("sample_radix_biased_fp32", logits, token_out, int(logits.numel()), float(softcap), float(temperature), int(top_k), float(top_p), float(r),
+         _filters_arg(filters), table, bias, _bias_stride(bias, bias_stride), scratch, _nbytes(scratch))
+
+
+def sample_radix_biased_advance(logits, token_out, softcap, temperature, top_k, top_p, draws, filters, table, bias, scratch, position_dev, seq_dev, ring=None, bias_stride=None):
+    call("sample_radix_biased_advance_fp32", logits, token_out, int(logits.numel()), float(softcap), float(temperature), int(top_k), float(top_p), draws, int(draws.numel()),
+         _filters_arg(filters), table, bias, _bias_stride(bias, bias_stride), scratch, _nbytes(scratch), position_dev, seq_dev, ring, 0 if ring is None else int(ring.numel()))
+
+
+def sample_radix_biased_rows(logits, token_out, softcap, temperature, top_k, top_p, draws, filters, table, bias, scratch, vocab=None, bias_stride=None):
+    """sample_radix_filtered_rows with the bias tables: [rows, vocab] (row b's is bias[b]) or [vocab] (shared: bias_stride 0)"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_biased_rows_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), float(temperature), int(top_k), float(top_p), draws,
+         _filters_arg(filters), table, _tables_stride(table), bias, _bias_stride(bias, bias_stride), scratch, _nbytes(scratch))
+
+
+def sample_radix_biased_rows_advance(logits, token_out, softcap, temperature, top_k, top_p, draws, filters, table, bias, scratch, positions_dev, active_dev, vocab=None,
+                                     bias_stride=None):
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_biased_rows_advance_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), float(temperature), int(top_k), float(top_p), draws,
+         _filters_arg(filters), table, _tables_stride(table), bias, _bias_stride(bias, bias_stride), scratch, _nbytes(scratch), positions_dev, active_dev)
+
+
+def sample_argmax_biased(logits, token_out, softcap, filters, table, bias, scratch, bias_stride=None):
+    """the greedy sampler over the biased and penalized logits x3, ties to the lower id (table None: no penalties, no update)"""
+    call("sample_argmax_biased_fp32", logits, token_out, int(logits.numel()), float(softcap), _filters_arg(filters), table, bias, _bias_stride(bias, bias_stride), scratch,
+         _nbytes(scratch))
+
+
+def sample_argmax_biased_advance(logits, token_out, softcap, filters, table, bias, scratch, position_dev, seq_dev=None, ring=None, bias_stride=None):
+    call("sample_argmax_biased_advance_fp32", logits, token_out, int(logits.numel()), float(softcap), _filters_arg(filters), table, bias, _bias_stride(bias, bias_stride),
+         scratch, _nbytes(scratch), position_dev, seq_dev, ring, 0 if ring is None else int(ring.numel()))
+
+
+def sample_argmax_biased_rows_advance(logits, token_out, softcap, filters, table, bias, scratch, positions_dev, active_dev, vocab=None, bias_stride=None):
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_argmax_biased_rows_advance_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), _filters_arg(filters), table, _tables_stride(table),
+         bias, _bias_stride(bias, bias_stride), scratch, _nbytes(scratch), positions_dev, active_dev)
+
+
 TOKEN_LOGPROBS_MAX_TOP = 20
 
 
@@ -542,6 +620,9 @@ EXPORTED = [
     "token_table_bytes", "token_table_clear", "token_table_mark_prompt", "sample_filters_describe",
     "sample_radix_filtered_fp32", "sample_radix_filtered_advance_fp32", "sample_radix_filtered_rows_fp32", "sample_radix_filtered_rows_advance_fp32",
     "sample_argmax_filtered_fp32", "sample_argmax_filtered_advance_fp32", "sample_argmax_filtered_rows_advance_fp32",
+    "token_bias_bytes", "token_bias_fill", "token_bias_set",
+    "sample_radix_biased_fp32", "sample_radix_biased_advance_fp32", "sample_radix_biased_rows_fp32", "sample_radix_biased_rows_advance_fp32",
+    "sample_argmax_biased_fp32", "sample_argmax_biased_advance_fp32", "sample_argmax_biased_rows_advance_fp32",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

@@ -81,19 +81,35 @@ __global__ __launch_bounds__(256) void argmax_partial_kernel(const T* __restrict
     if (threadIdx.x == 0) { pv[blockIdx.x] = bv; pi[blockIdx.x] = bi; }
 }
 
+// Row b's bias table from the trailing kernel arguments of a BIAS instantiation (bias0, bias_stride).  The arguments are a parameter pack, empty in the instantiations
+// without a bias: those keep the parent's kernel signature, and with it the offsets of their hidden arguments -- their instruction streams do not move.
+__device__ __forceinline__ const float* bias_row(int) { return nullptr; }
+__device__ __forceinline__ const float* bias_row(int b, const float* bias0, size_t bias_stride) { return bias0 + (size_t)b * bias_stride; }
+
 // the greedy sampler's first stage over the ADJUSTED logits x3 (softcap first: the penalty touches only some tokens, so the capped values decide); blockIdx.y = row b:
 // logits + b * logits_stride, table + b * table_stride, partials at pv0 + b * row_floats (values, then kArgmaxBlocks floats on the indices)
+// TABLE: the penalties from the token table.  BIAS: xb = x0 + bias[i] (row b's bias table at bias0 + b * bias_stride, the two trailing arguments B of the BIAS
+// instantiations) between the softcap and the penalties.  A -inf entry never beats the start value -FLT_MAX.
+template <bool TABLE, bool BIAS, typename... B>
 __global__ __launch_bounds__(256) void argmax_partial_filtered_kernel(const float* __restrict__ logits0, size_t logits_stride, float softcap, const SampleFilter f,
-                                                                      float* __restrict__ pv0, int row_floats, int vocab)
+                                                                      float* __restrict__ pv0, int row_floats, int vocab, B... bias_args)
 {
+    static_assert(TABLE || BIAS, "the unfiltered first stage is argmax_partial_kernel");
+    static_assert(sizeof...(B) == (BIAS ? 2 : 0), "bias0 and bias_stride go with BIAS");
     const float* logits = logits0 + (size_t)blockIdx.y * logits_stride;
     const uint32_t* table = f.table + (size_t)blockIdx.y * f.table_stride;
+    const float* __restrict__ bias = bias_row(blockIdx.y, bias_args...);
     float* pv = pv0 + (size_t)blockIdx.y * row_floats;
     int* pi = reinterpret_cast<int*>(pv + kArgmaxBlocks);
     float bv = -FLT_MAX;
     int bi = 0x7fffffff;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256)
-        argmax_better(bv, bi, penalized_logit(soft_cap(logits[i], softcap), table[i], f), i);
+    {
+        float x = soft_cap(logits[i], softcap);
+        if (BIAS) x = __fadd_rn(x, bias[i]);
+        if (TABLE) x = penalized_logit(x, table[i], f);
+        argmax_better(bv, bi, x, i);
+    }
     block_argmax(bv, bi);
     if (threadIdx.x == 0) { pv[blockIdx.x] = bv; pi[blockIdx.x] = bi; }
 }
@@ -178,6 +194,22 @@ __global__ __launch_bounds__(256) void token_table_mark_prompt_kernel(uint32_t* 
     }
 }
 
+// ---- the bias table (mila_cdna4.h: logit bias): `vocab` fp32 values per row, finite or -inf, added to the capped logit by the BIAS instantiations.  Maintenance in
+// plain vector stores: a whole row to one value, and n values scattered to n ids held in device memory (an id outside [0, vocab) is skipped; two writers of one id
+// race, so duplicates are the caller's to avoid).
+__global__ __launch_bounds__(256) void token_bias_fill_kernel(float* __restrict__ bias, int vocab, float value)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) bias[i] = value;
+}
+__global__ __launch_bounds__(256) void token_bias_set_kernel(float* __restrict__ bias, int vocab, const int32_t* __restrict__ ids, const float* __restrict__ values, int n)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    {
+        const int id = ids[i];
+        if (id >= 0 && id < vocab) bias[id] = values[i];
+    }
+}
+
 // The acceptance rule of a chain (speculative verification), by one lane: rows 0 .. T - 1 are consecutive positions of ONE sequence, row t fed with tok[t] (tok[0] the
 // last sampled token, tok[1 ..] the drafts), and s[t] is row t's sample.  The longest correct draft prefix is accepted: n_acc = the first t in [0, T - 1) with
 // s[t] != tok[t + 1], else T - 1.  result = {n_acc + 1, s[0] .. s[n_acc]} (the other words are left alone), tok[0] = s[n_acc] (the next step's input), *pos += n_acc + 1.
@@ -219,12 +251,13 @@ __global__ __launch_bounds__(64) void advance_positions_rows_kernel(int32_t* __r
 }
 
 // The first stage of the two-launch greedy entries, written once: the scratch check, the split of a row's partials into values and indices, the workgroup count and
-// the partial launch.  f == nullptr: the logits as they are, one row; else x3 of `rows` rows (softcap first), row b's partials at pv + b * row_floats.
+// the partial launch.  f == nullptr: the logits as they are, one row; else x3 of `rows` rows (softcap first), row b's partials at pv + b * row_floats: the penalties
+// where f->table is set, the bias where `bias` is set (at least one of the two).
 struct ArgmaxPartials { float* pv; int* pi; int blocks, row_floats; };
 constexpr size_t kArgmaxRowBytes = (size_t)kArgmaxBlocks * 8;
 template <typename T>
 static int launch_argmax_partials(const T* logits, size_t logits_stride, int rows, int vocab, float softcap, const SampleFilter* f, void* scratch, size_t scratch_bytes,
-                                  hipStream_t s, const char* who, ArgmaxPartials& a)
+                                  hipStream_t s, const char* who, ArgmaxPartials& a, const float* bias = nullptr, size_t bias_stride = 0)
 {
     const size_t need = kArgmaxRowBytes * (size_t)rows;
     if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
@@ -235,7 +268,10 @@ static int launch_argmax_partials(const T* logits, size_t logits_stride, int row
     a.row_floats = (int)(kArgmaxRowBytes / sizeof(float));
     if constexpr (std::is_same<T, float>::value)
     {
-        if (f) hipLaunchKernelGGL(argmax_partial_filtered_kernel, dim3(a.blocks, (unsigned)rows), dim3(256), 0, s, logits, logits_stride, softcap, *f, a.pv, a.row_floats, vocab);
+        auto biased = [&](auto k) { hipLaunchKernelGGL(k, dim3(a.blocks, (unsigned)rows), dim3(256), 0, s, logits, logits_stride, softcap, *f, a.pv, a.row_floats, vocab, bias, bias_stride); };
+        if (f && f->table && bias) biased(argmax_partial_filtered_kernel<true, true, const float*, size_t>);
+        else if (f && bias) biased(argmax_partial_filtered_kernel<false, true, const float*, size_t>);
+        else if (f) hipLaunchKernelGGL((argmax_partial_filtered_kernel<true, false>), dim3(a.blocks, (unsigned)rows), dim3(256), 0, s, logits, logits_stride, softcap, *f, a.pv, a.row_floats, vocab);
         else hipLaunchKernelGGL(argmax_partial_kernel<T>, dim3(a.blocks), dim3(256), 0, s, logits, a.pv, a.pi, vocab);
     }
     else hipLaunchKernelGGL(argmax_partial_kernel<T>, dim3(a.blocks), dim3(256), 0, s, logits, a.pv, a.pi, vocab);
@@ -649,9 +685,11 @@ __device__ __forceinline__ void radix_walk(const float* w, int first, int stride
 // launch 1: x = softcap / temperature, per-workgroup max; clears the header and both histograms for the launches behind it
 // FILT: the adjusted logit (penalized_logit on the capped value, then the temperature) with the table word read beside the logit in the same coalesced walk; the
 // copy goes to p.w as ever -- the logits are never written (the log-probabilities stay those of the unpenalized logits)
-template <typename T, bool FILT = false>
+// BIAS: xb = x0 + bias[i], one more value read beside the logit, between the softcap and the penalties.  A -inf bias stays -inf through penalized_logit (a product with
+// rep > 0, differences with finite values) and the division by a positive temperature; the maximum is over the finite entries (one exists: the caller's contract).
+template <typename T, bool FILT = false, bool BIAS = false>
 __device__ __forceinline__ void radix_scale_body(const T* __restrict__ logits, const RadixParams& p, int clear_words, const SampleFilter* f = nullptr,
-                                                 const uint32_t* __restrict__ table = nullptr)
+                                                 const uint32_t* __restrict__ table = nullptr, const float* __restrict__ bias = nullptr)
 {
     __shared__ float sv[4];
     uint32_t* z = reinterpret_cast<uint32_t*>(p.hdr);
@@ -660,6 +698,7 @@ __device__ __forceinline__ void radix_scale_body(const T* __restrict__ logits, c
     for (int i = blockIdx.x * 256 + threadIdx.x; i < p.vocab; i += gridDim.x * 256)
     {
         float x = soft_cap(to_f32(logits[i]), p.softcap);
+        if (BIAS) x = __fadd_rn(x, bias[i]);
         if (FILT) x = penalized_logit(x, table[i], *f);
         x = x / p.temperature;
         p.w[i] = x;
@@ -831,6 +870,9 @@ __device__ __forceinline__ float lane_value(float v, int l) { return __int_as_fl
 // inverse CDF in token-index order: samp_cdf_kernel's sums and walk, value for value (the same additions in the same order), by one wave that holds the chunk sums in
 // registers and steps over the zeros of the walk: adding 0 leaves the cumulative sum as it is, and after the truncations nearly every entry is 0.
 // radix_cdf_walk is the walk itself, by ONE wave (`lane` its lane) at the draw r; every lane returns the token.
+// LAST (the instantiations of a call with a bias table): when the running sum never reaches r * total -- the two are added in different orders, so next to r = 1 they
+// can differ -- the token is the LAST entry with nonzero mass, found by a scan of the whole vector, instead of vocab - 1, which a -inf bias may forbid.
+template <bool LAST = false>
 __device__ __forceinline__ int radix_cdf_walk(const RadixParams& p, float r, int nchunks, int chunk, int lane)
 {
     const float* cs = p.red + kSampBlocks;
@@ -878,6 +920,15 @@ __device__ __forceinline__ int radix_cdf_walk(const RadixParams& p, float r, int
             }
         }
     }
+    if (LAST && !found)
+    {
+        int last = -1;
+        for (int i = lane; i < p.vocab; i += 64)
+            if (p.w[i] > 0.0f) last = i;      // ascending: the lane's largest
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
+        if (last >= 0) result = last;
+    }
     return result;
 }
 
@@ -905,11 +956,14 @@ __device__ __forceinline__ RadixParams radix_row(const RadixRows& r, int b)
 }
 
 // the stage launches (`logits` leads: it is preloaded)
-template <typename T, bool FILT>
-__global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ logits, const RadixRows r, int clear_words)
+// (BIAS: bias0 and bias_stride trail the arguments -- the pack B, empty otherwise: row b's bias table is bias0 + b * bias_stride)
+template <typename T, bool FILT, bool BIAS, typename... B>
+__global__ __launch_bounds__(256) void radix_scale_kernel(const T* __restrict__ logits, const RadixRows r, int clear_words, B... bias_args)
 {
+    static_assert(sizeof...(B) == (BIAS ? 2 : 0), "bias0 and bias_stride go with BIAS");
     const RadixParams p = radix_row(r, blockIdx.y);
-    radix_scale_body<T, FILT>(logits + (size_t)blockIdx.y * r.logits_stride, p, clear_words, &r.f, FILT ? r.f.table + (size_t)blockIdx.y * r.f.table_stride : nullptr);
+    radix_scale_body<T, FILT, BIAS>(logits + (size_t)blockIdx.y * r.logits_stride, p, clear_words, &r.f, FILT ? r.f.table + (size_t)blockIdx.y * r.f.table_stride : nullptr,
+                                    bias_row(blockIdx.y, bias_args...));
 }
 __global__ __launch_bounds__(256) void radix_kpass_kernel(const RadixRows r, int pass)
 {
@@ -936,7 +990,8 @@ __global__ __launch_bounds__(256) void radix_mask_kernel(const RadixRows r, int 
 // The one-row tail, one wave over row 0.  ADVANCE: the stochastic twin of argmax_final_advance_kernel -- the draw is slot (*seq_dev + 1) % draws_size of a host-written
 // ring (system-scope load: the host rewrites the slots between replays), and the tail bumps the position, stores the sequence number and (ring != NULL) publishes
 // seq << 32 | token; else the draw is p.r.  TABLE: lane 0 counts the sample in the table before it stores / publishes the token.
-template <bool ADVANCE, bool TABLE>
+// LAST: radix_cdf_walk<true>, for a call with a bias table.
+template <bool ADVANCE, bool TABLE, bool LAST = false>
 __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixRows rr, int nchunks, int chunk)
 {
     const RadixParams& p = rr.p;
@@ -949,7 +1004,7 @@ __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixRows rr, int n
         const uint32_t* slot = reinterpret_cast<const uint32_t*>(p.draws) + (seq % (unsigned long long)p.draws_size);
         r = __uint_as_float(__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
     }
-    const int result = radix_cdf_walk(p, r, nchunks, chunk, lane);
+    const int result = radix_cdf_walk<LAST>(p, r, nchunks, chunk, lane);
     if (lane == 0)
     {
         if (TABLE) table_count(rr.f.table, result);
@@ -964,9 +1019,9 @@ __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixRows rr, int n
 //   kRowsAdvance: where active[b] != 0, token_out[b] = s_b and pos[b] += 1; an inactive row's words are not touched.
 //   kRowsChain:   chain_accept with the samples (token_out is tok[], pos the ONE position word).
 // TABLE (kRowsTokens / kRowsAdvance): the lane counts row b's sample in row b's table before it stores the token -- in kRowsAdvance for the active rows only.  The chain
-// tail takes no table: row t would need the table plus the drafts 1 .. t.
+// tail takes no table: row t would need the table plus the drafts 1 .. t.  LAST: radix_cdf_walk<true>, for a call with a bias table (never the chain tail).
 enum { kRowsTokens = 0, kRowsAdvance = 1, kRowsChain = 2 };
-template <int MODE, bool TABLE>
+template <int MODE, bool TABLE, bool LAST = false>
 __global__ __launch_bounds__(256) void radix_rows_tail_kernel(const RadixRows r, int rows, int nchunks, int chunk, const int32_t* __restrict__ active, int32_t* __restrict__ result)
 {
     static_assert(!TABLE || MODE == kRowsTokens || MODE == kRowsAdvance, "the chain tail takes no table");
@@ -976,7 +1031,7 @@ __global__ __launch_bounds__(256) void radix_rows_tail_kernel(const RadixRows r,
     {
         const RadixParams p = radix_row(r, t);
         const float draw = __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t*>(r.p.draws) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-        const int s = radix_cdf_walk(p, draw, nchunks, chunk, lane);
+        const int s = radix_cdf_walk<LAST>(p, draw, nchunks, chunk, lane);
         if (lane == 0) ss[t] = s;
     }
     __syncthreads();
@@ -1005,12 +1060,14 @@ struct RadixPlan
     size_t scratch_need;
     int scale_filtered;      // the scale launch is the instantiation that reads the token table (a table was given)
     int mask_filtered;       // the mask launch is the instantiation with the min-p test (min_p > 0)
+    int scale_biased;        // the scale launch reads a bias table, and the tail is the instantiation whose fallback is the last entry with mass
 };
 constexpr size_t kRadixHistBytes = (size_t)kRadixPasses * kRadixBins * (sizeof(uint32_t) + sizeof(unsigned long long));
-// with_table / min_p choose INSTANTIATIONS of launches the plan already has: a filtered call launches what the unfiltered call launches
-static RadixPlan plan_radix(int vocab, int top_k, float top_p, bool with_table = false, float min_p = 0.0f)
+// with_table / min_p / with_bias choose INSTANTIATIONS of launches the plan already has: a filtered or biased call launches what the unfiltered call launches
+static RadixPlan plan_radix(int vocab, int top_k, float top_p, bool with_table = false, float min_p = 0.0f, bool with_bias = false)
 {
     RadixPlan d{};
+    d.scale_biased = with_bias ? 1 : 0;
     d.scale_filtered = with_table ? 1 : 0;
     d.mask_filtered = min_p > 0.0f ? 1 : 0;
     d.k_passes = (top_k > 0 && top_k < vocab) ? kRadixPasses : 0;
@@ -1068,7 +1125,17 @@ struct RadixCall
     const int32_t* active;
     int32_t* result;
     const SampleFilter* flt;
+    const float* bias;              // row 0's bias table (nullptr: none)
+    size_t bias_stride;             // floats between the bias tables of two rows; 0 = one table for every row
 };
+
+// the bias table of a call: any stride with one row; with more, 0 (shared) or at least vocab
+static int check_bias(const float* bias, size_t bias_stride, int rows, int vocab, const char* who)
+{
+    MILA_REQUIRE(!bias || rows <= 1 || bias_stride == 0 || bias_stride >= (size_t)vocab, "%s: bias_stride %zu is neither 0 nor >= vocab %d", who, bias_stride, vocab);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(bias) & 3u) == 0, "%s: bias must be 4-byte aligned", who);
+    return MILA_OK;
+}
 
 // The radix pipeline of every entry: plan_radix's launches for one row, each with the rows in grid.y, and the mode's tail.
 template <typename T>
@@ -1092,7 +1159,9 @@ static int run_radix(const RadixCall<T>& c, void* scratch, size_t scratch_bytes,
     MILA_REQUIRE(!adv || adv->draws_size > 0, "%s: draws_size must be positive", who);
     MILA_REQUIRE(!adv || (adv->ring ? adv->ring_size > 0 : adv->ring_size == 0), "%s: ring and ring_size go together", who);
     MILA_REQUIRE(c.mode != kRowsChain || !flt, "%s: the chain tail takes no filters", who);
-    const RadixPlan d = plan_radix(c.vocab, c.top_k, c.top_p, flt && flt->table, flt ? flt->min_p : 0.0f);
+    MILA_REQUIRE(c.mode != kRowsChain || !c.bias, "%s: the chain tail takes no bias", who);
+    if (const int rc = check_bias(c.bias, c.bias_stride, c.rows, c.vocab, who)) return rc;
+    const RadixPlan d = plan_radix(c.vocab, c.top_k, c.top_p, flt && flt->table, flt ? flt->min_p : 0.0f, c.bias != nullptr);
     const size_t row_stride = radix_row_stride(c.vocab), need = one ? d.scratch_need : row_stride * (size_t)c.rows;
     if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
     MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, "%s: scratch must be 8-byte aligned", who);
@@ -1116,22 +1185,33 @@ static int run_radix(const RadixCall<T>& c, void* scratch, size_t scratch_bytes,
     const dim3 wg(256);
     if constexpr (std::is_same<T, float>::value)
     {
-        if (d.scale_filtered) hipLaunchKernelGGL((radix_scale_kernel<float, true>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
-        else hipLaunchKernelGGL((radix_scale_kernel<float, false>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
+        auto biased = [&](auto k) { hipLaunchKernelGGL(k, dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words, c.bias, c.bias_stride); };
+        if (d.scale_filtered && d.scale_biased) biased(radix_scale_kernel<float, true, true, const float*, size_t>);
+        else if (d.scale_biased) biased(radix_scale_kernel<float, false, true, const float*, size_t>);
+        else if (d.scale_filtered) hipLaunchKernelGGL((radix_scale_kernel<float, true, false>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
+        else hipLaunchKernelGGL((radix_scale_kernel<float, false, false>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
     }
-    else hipLaunchKernelGGL((radix_scale_kernel<T, false>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
+    else
+    {
+        MILA_REQUIRE(!c.bias, "%s: the bias table goes with fp32 logits", who);
+        hipLaunchKernelGGL((radix_scale_kernel<T, false, false>), dim3(d.scale_blocks, R), wg, 0, s, c.logits, r, clear_words);
+    }
     for (int pass = 0; pass < d.k_passes; ++pass) hipLaunchKernelGGL(radix_kpass_kernel, dim3(d.blocks, R), wg, 0, s, r, pass);
     hipLaunchKernelGGL(radix_prob_kernel, dim3(d.blocks, R), wg, 0, s, r, use_k, use_p, d.scale_blocks);
     for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_kernel, dim3(d.blocks, R), wg, 0, s, r, pass);
     if (d.mask_filtered) hipLaunchKernelGGL(radix_mask_kernel<true>, dim3(d.nchunks, R), wg, 0, s, r, use_p, d.chunk, flt->min_p);
     else hipLaunchKernelGGL(radix_mask_kernel<false>, dim3(d.nchunks, R), wg, 0, s, r, use_p, d.chunk, 0.0f);
-    // the tail: <mode, table> picks the instantiation
-    const bool tab = d.scale_filtered != 0;
+    // the tail: <mode, table, last> picks the instantiation
+    const bool tab = d.scale_filtered != 0, last = d.scale_biased != 0;
     auto cdf = [&](auto k) { hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, s, r, d.nchunks, d.chunk); };
     auto tail = [&](auto k) { hipLaunchKernelGGL(k, dim3(1), wg, 0, s, r, c.rows, d.nchunks, d.chunk, c.active, c.result); };
-    if (one && adv) { if (tab) cdf(radix_cdf_kernel<true, true>); else cdf(radix_cdf_kernel<true, false>); }
+    if (one && adv && last) { if (tab) cdf(radix_cdf_kernel<true, true, true>); else cdf(radix_cdf_kernel<true, false, true>); }
+    else if (one && adv) { if (tab) cdf(radix_cdf_kernel<true, true>); else cdf(radix_cdf_kernel<true, false>); }
+    else if (one && last) { if (tab) cdf(radix_cdf_kernel<false, true, true>); else cdf(radix_cdf_kernel<false, false, true>); }
     else if (one) { if (tab) cdf(radix_cdf_kernel<false, true>); else cdf(radix_cdf_kernel<false, false>); }
+    else if (c.mode == kRowsTokens && last) { if (tab) tail(radix_rows_tail_kernel<kRowsTokens, true, true>); else tail(radix_rows_tail_kernel<kRowsTokens, false, true>); }
     else if (c.mode == kRowsTokens) { if (tab) tail(radix_rows_tail_kernel<kRowsTokens, true>); else tail(radix_rows_tail_kernel<kRowsTokens, false>); }
+    else if (c.mode == kRowsAdvance && last) { if (tab) tail(radix_rows_tail_kernel<kRowsAdvance, true, true>); else tail(radix_rows_tail_kernel<kRowsAdvance, false, true>); }
     else if (c.mode == kRowsAdvance) { if (tab) tail(radix_rows_tail_kernel<kRowsAdvance, true>); else tail(radix_rows_tail_kernel<kRowsAdvance, false>); }
     else tail(radix_rows_tail_kernel<kRowsChain, false>);
     return check_hip(hipGetLastError(), who);
@@ -1140,34 +1220,49 @@ static int run_radix(const RadixCall<T>& c, void* scratch, size_t scratch_bytes,
 // the one-row entries: the draw `r`, or with `adv` the draw ring
 template <typename T>
 static int call_radix_one(const T* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r, const RadixAdvance* adv,
-                         void* scratch, size_t scratch_bytes, hipStream_t s, const char* who, const SampleFilter* flt = nullptr)
+                         void* scratch, size_t scratch_bytes, hipStream_t s, const char* who, const SampleFilter* flt = nullptr, const float* bias = nullptr,
+                         size_t bias_stride = 0)
 {
-    const RadixCall<T> c{kOneRow, logits, 0, token_out, 1, vocab, softcap, temperature, top_k, top_p, r, adv, nullptr, nullptr, nullptr, nullptr, flt};
+    const RadixCall<T> c{kOneRow, logits, 0, token_out, 1, vocab, softcap, temperature, top_k, top_p, r, adv, nullptr, nullptr, nullptr, nullptr, flt, bias, bias_stride};
     return run_radix(c, scratch, scratch_bytes, s, who);
 }
 // the rows entries: one draw per row in `draws`
 static int call_radix_rows(int mode, const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k, float top_p,
                           const float* draws, void* scratch, size_t scratch_bytes, int32_t* pos, const int32_t* active, int32_t* result, hipStream_t s, const char* who,
-                          const SampleFilter* flt = nullptr)
+                          const SampleFilter* flt = nullptr, const float* bias = nullptr, size_t bias_stride = 0)
 {
-    const RadixCall<float> c{mode, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, 0.0f, nullptr, draws, pos, active, result, flt};
+    const RadixCall<float> c{mode, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, 0.0f, nullptr, draws, pos, active, result, flt, bias,
+                             bias_stride};
     return run_radix(c, scratch, scratch_bytes, s, who);
 }
 
 // The penalized greedy sampler over `rows` rows: argmax(x3), ties to the lower id, in the two launches of sample_argmax_*: the partial stage computes x3 from logits,
 // table and softcap, the final stage counts the token in the table.  adv: the one-row advance tail; pos + active: the rows advance tail; neither: token only.
+// With a bias table the first stage adds it; f.table may then be null (a bias without penalties: the final stage is the one that counts nothing).
 static int run_argmax_filtered(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, const SampleFilter& f, void* scratch,
-                               size_t scratch_bytes, const RadixAdvance* adv, int32_t* positions, const int32_t* active, hipStream_t s, const char* who)
+                               size_t scratch_bytes, const RadixAdvance* adv, int32_t* positions, const int32_t* active, hipStream_t s, const char* who,
+                               const float* bias = nullptr, size_t bias_stride = 0)
 {
+    if (const int rc = check_bias(bias, bias_stride, rows, vocab, who)) return rc;
     ArgmaxPartials a;
-    const int rc = launch_argmax_partials(logits, logits_stride, rows, vocab, softcap, &f, scratch, scratch_bytes, s, who, a);
+    const int rc = launch_argmax_partials(logits, logits_stride, rows, vocab, softcap, &f, scratch, scratch_bytes, s, who, a, bias, bias_stride);
     if (rc) return rc;
+    const bool tab = f.table != nullptr;
     if (positions)
-        hipLaunchKernelGGL(argmax_rows_final_advance_kernel<true>, dim3(rows), dim3(256), 0, s, a.pv, token_out, positions, active, a.blocks, a.row_floats, f.table, f.table_stride);
+    {
+        auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(rows), dim3(256), 0, s, a.pv, token_out, positions, active, a.blocks, a.row_floats, f.table, f.table_stride); };
+        if (tab) go(argmax_rows_final_advance_kernel<true>); else go(argmax_rows_final_advance_kernel<false>);
+    }
     else if (adv)
-        hipLaunchKernelGGL(argmax_final_advance_kernel<true>, dim3(1), dim3(256), 0, s, a.pv, a.pi, a.blocks, token_out, adv->pos, adv->seq_dev, adv->ring, adv->ring_size, f.table);
+    {
+        auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(1), dim3(256), 0, s, a.pv, a.pi, a.blocks, token_out, adv->pos, adv->seq_dev, adv->ring, adv->ring_size, f.table); };
+        if (tab) go(argmax_final_advance_kernel<true>); else go(argmax_final_advance_kernel<false>);
+    }
     else
-        hipLaunchKernelGGL(argmax_final_kernel<true>, dim3(1), dim3(256), 0, s, a.pv, a.pi, a.blocks, token_out, f.table);
+    {
+        auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(1), dim3(256), 0, s, a.pv, a.pi, a.blocks, token_out, f.table); };
+        if (tab) go(argmax_final_kernel<true>); else go(argmax_final_kernel<false>);
+    }
     return check_hip(hipGetLastError(), who);
 }
 
@@ -1340,91 +1435,181 @@ int mila_cdna4_token_table_mark_prompt(uint32_t* table, size_t table_stride, int
     MILA_LAUNCH_CHECK("token_table_mark_prompt");
 }
 
-int mila_cdna4_sample_radix_filtered_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
-                                          const mila_sample_filters* filters, uint32_t* table, void* scratch, size_t scratch_bytes, mila_stream_t stream)
+// ---- the bias table and the biased entries (mila_cdna4.h: logit bias).  Each biased entry is the filtered entry plus `bias, bias_stride`; bias == NULL is the filtered
+// entry itself, which is now a call of its biased sibling.
+size_t mila_cdna4_token_bias_bytes(int vocab) { return vocab > 0 ? (size_t)vocab * sizeof(float) : 0; }
+
+int mila_cdna4_token_bias_fill(float* bias, size_t bias_stride, int row, int vocab, float value, mila_stream_t stream)
 {
-    SampleFilter f{};
-    const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_radix_filtered_fp32");
-    if (rc) return rc;
-    return call_radix_one<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), "sample_radix_filtered_fp32", &f);
+    MILA_REQUIRE(bias, "token_bias_fill: null pointer");
+    MILA_REQUIRE(vocab > 0 && row >= 0 && (row == 0 || bias_stride >= (size_t)vocab), "token_bias_fill: need vocab > 0, row >= 0, bias_stride >= vocab");
+    MILA_REQUIRE(!std::isnan(value) && !(std::isinf(value) && value > 0.0f), "token_bias_fill: the value must be finite or -inf");
+    int blocks = (vocab + 255) / 256;
+    if (blocks > 256) blocks = 256;
+    hipLaunchKernelGGL(token_bias_fill_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), bias + (size_t)row * bias_stride, vocab, value);
+    MILA_LAUNCH_CHECK("token_bias_fill");
 }
 
-int mila_cdna4_sample_radix_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
-                                                  const float* draws, int draws_size, const mila_sample_filters* filters, uint32_t* table, void* scratch, size_t scratch_bytes,
-                                                  int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring, int ring_size, mila_stream_t stream)
+int mila_cdna4_token_bias_set(float* bias, size_t bias_stride, int row, int vocab, const int32_t* ids_dev, const float* values_dev, int n, mila_stream_t stream)
 {
+    MILA_REQUIRE(n >= 0, "token_bias_set: n must not be negative");
+    MILA_REQUIRE(n == 0 || (bias && ids_dev && values_dev), "token_bias_set: null pointer");
+    MILA_REQUIRE(vocab > 0 && row >= 0 && (row == 0 || bias_stride >= (size_t)vocab), "token_bias_set: need vocab > 0, row >= 0, bias_stride >= vocab");
+    if (n == 0) return MILA_OK;
+    int blocks = (n + 255) / 256;
+    if (blocks > 256) blocks = 256;
+    hipLaunchKernelGGL(token_bias_set_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), bias + (size_t)row * bias_stride, vocab, ids_dev, values_dev, n);
+    MILA_LAUNCH_CHECK("token_bias_set");
+}
+
+int mila_cdna4_sample_radix_biased_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                        const mila_sample_filters* filters, uint32_t* table, const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes,
+                                        mila_stream_t stream)
+{
+    const char* who = bias ? "sample_radix_biased_fp32" : "sample_radix_filtered_fp32";
     SampleFilter f{};
-    const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_radix_filtered_advance_fp32");
+    const int rc = make_filter(filters, table, 0, 1, vocab, f, who);
+    if (rc) return rc;
+    return call_radix_one<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, nullptr, scratch, scratch_bytes, as_stream(stream), who, &f, bias, bias_stride);
+}
+
+int mila_cdna4_sample_radix_biased_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
+                                                const float* draws, int draws_size, const mila_sample_filters* filters, uint32_t* table, const float* bias, size_t bias_stride,
+                                                void* scratch, size_t scratch_bytes, int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring, int ring_size,
+                                                mila_stream_t stream)
+{
+    const char* who = bias ? "sample_radix_biased_advance_fp32" : "sample_radix_filtered_advance_fp32";
+    SampleFilter f{};
+    const int rc = make_filter(filters, table, 0, 1, vocab, f, who);
     if (rc) return rc;
     const RadixAdvance adv{draws, draws_size, position_dev, seq_dev, ring, ring_size};
-    return call_radix_one<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream),
-                            "sample_radix_filtered_advance_fp32", &f);
+    return call_radix_one<float>(logits, token_out, vocab, softcap, temperature, top_k, top_p, 0.0f, &adv, scratch, scratch_bytes, as_stream(stream), who, &f, bias, bias_stride);
 }
 
-int mila_cdna4_sample_radix_filtered_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k,
-                                               float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table, size_t table_stride, void* scratch,
-                                               size_t scratch_bytes, mila_stream_t stream)
+int mila_cdna4_sample_radix_biased_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k,
+                                             float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table, size_t table_stride, const float* bias,
+                                             size_t bias_stride, void* scratch, size_t scratch_bytes, mila_stream_t stream)
 {
+    const char* who = bias ? "sample_radix_biased_rows_fp32" : "sample_radix_filtered_rows_fp32";
     SampleFilter f{};
-    const int rc = make_filter(filters, table, table_stride, rows, vocab, f, "sample_radix_filtered_rows_fp32");
+    const int rc = make_filter(filters, table, table_stride, rows, vocab, f, who);
     if (rc) return rc;
     return call_radix_rows(kRowsTokens, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, nullptr, nullptr, nullptr,
-                          as_stream(stream), "sample_radix_filtered_rows_fp32", &f);
+                          as_stream(stream), who, &f, bias, bias_stride);
 }
 
-int mila_cdna4_sample_radix_filtered_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature,
-                                                       int top_k, float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table, size_t table_stride,
-                                                       void* scratch, size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream)
+int mila_cdna4_sample_radix_biased_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature,
+                                                     int top_k, float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table, size_t table_stride,
+                                                     const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* positions_dev,
+                                                     const int32_t* active_dev, mila_stream_t stream)
 {
+    const char* who = bias ? "sample_radix_biased_rows_advance_fp32" : "sample_radix_filtered_rows_advance_fp32";
     SampleFilter f{};
-    const int rc = make_filter(filters, table, table_stride, rows, vocab, f, "sample_radix_filtered_rows_advance_fp32");
+    const int rc = make_filter(filters, table, table_stride, rows, vocab, f, who);
     if (rc) return rc;
     return call_radix_rows(kRowsAdvance, logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, positions_dev, active_dev,
-                          nullptr, as_stream(stream), "sample_radix_filtered_rows_advance_fp32", &f);
+                          nullptr, as_stream(stream), who, &f, bias, bias_stride);
 }
 
-// table == NULL: no penalties, and min_p does not change a greedy request -- today's greedy sampler on the logits as they are
-int mila_cdna4_sample_argmax_filtered_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
-                                           void* scratch, size_t scratch_bytes, mila_stream_t stream)
+// table == NULL and bias == NULL: no penalties, and min_p does not change a greedy request -- today's greedy sampler on the logits as they are
+int mila_cdna4_sample_argmax_biased_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
+                                         const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, mila_stream_t stream)
 {
+    const char* who = bias ? "sample_argmax_biased_fp32" : "sample_argmax_filtered_fp32";
     SampleFilter f{};
-    const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_argmax_filtered_fp32");
+    const int rc = make_filter(filters, table, 0, 1, vocab, f, who);
     if (rc) return rc;
-    if (!table) return run_argmax<float>(logits, token_out, vocab, scratch, scratch_bytes, as_stream(stream), "sample_argmax_filtered_fp32");
-    MILA_REQUIRE(logits && token_out, "sample_argmax_filtered_fp32: null pointer");
-    MILA_REQUIRE(vocab > 0, "sample_argmax_filtered_fp32: vocab must be positive");
-    return run_argmax_filtered(logits, 0, token_out, 1, vocab, softcap, f, scratch, scratch_bytes, nullptr, nullptr, nullptr, as_stream(stream), "sample_argmax_filtered_fp32");
+    if (!table && !bias) return run_argmax<float>(logits, token_out, vocab, scratch, scratch_bytes, as_stream(stream), who);
+    MILA_REQUIRE(logits && token_out, "%s: null pointer", who);
+    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
+    return run_argmax_filtered(logits, 0, token_out, 1, vocab, softcap, f, scratch, scratch_bytes, nullptr, nullptr, nullptr, as_stream(stream), who, bias, bias_stride);
 }
 
-int mila_cdna4_sample_argmax_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
-                                                   void* scratch, size_t scratch_bytes, int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring,
-                                                   int ring_size, mila_stream_t stream)
+int mila_cdna4_sample_argmax_biased_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
+                                                 const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* position_dev,
+                                                 unsigned long long* seq_dev, unsigned long long* ring, int ring_size, mila_stream_t stream)
 {
+    const char* who = bias ? "sample_argmax_biased_advance_fp32" : "sample_argmax_filtered_advance_fp32";
     SampleFilter f{};
-    const int rc = make_filter(filters, table, 0, 1, vocab, f, "sample_argmax_filtered_advance_fp32");
+    const int rc = make_filter(filters, table, 0, 1, vocab, f, who);
     if (rc) return rc;
-    if (!table) return mila_cdna4_sample_argmax_advance_fp32(logits, token_out, vocab, scratch, scratch_bytes, position_dev, seq_dev, ring, ring_size, stream);
-    MILA_REQUIRE(logits && token_out && position_dev, "sample_argmax_filtered_advance_fp32: null pointer");
-    MILA_REQUIRE(vocab > 0, "sample_argmax_filtered_advance_fp32: vocab must be positive");
-    MILA_REQUIRE((ring == nullptr) == (seq_dev == nullptr) && (ring == nullptr || ring_size > 0), "sample_argmax_filtered_advance_fp32: ring, seq_dev and ring_size go together");
+    if (!table && !bias) return mila_cdna4_sample_argmax_advance_fp32(logits, token_out, vocab, scratch, scratch_bytes, position_dev, seq_dev, ring, ring_size, stream);
+    MILA_REQUIRE(logits && token_out && position_dev, "%s: null pointer", who);
+    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
+    MILA_REQUIRE((ring == nullptr) == (seq_dev == nullptr) && (ring == nullptr || ring_size > 0), "%s: ring, seq_dev and ring_size go together", who);
     const RadixAdvance adv{nullptr, 0, position_dev, seq_dev, ring, ring_size};
-    return run_argmax_filtered(logits, 0, token_out, 1, vocab, softcap, f, scratch, scratch_bytes, &adv, nullptr, nullptr, as_stream(stream), "sample_argmax_filtered_advance_fp32");
+    return run_argmax_filtered(logits, 0, token_out, 1, vocab, softcap, f, scratch, scratch_bytes, &adv, nullptr, nullptr, as_stream(stream), who, bias, bias_stride);
 }
 
-// the rows greedy tail with penalties: both launches (the lm_head epilogue cannot compute x3), tokens, positions and tables of the active rows only
-int mila_cdna4_sample_argmax_filtered_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
-                                                        const mila_sample_filters* filters, uint32_t* table, size_t table_stride, void* scratch, size_t scratch_bytes,
-                                                        int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream)
+// the rows greedy tail with penalties and / or a bias: both launches (the lm_head epilogue cannot compute x3), tokens, positions and tables of the active rows only.
+// Without a bias the table is required, as it always was; with one it may be NULL.
+int mila_cdna4_sample_argmax_biased_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                      const mila_sample_filters* filters, uint32_t* table, size_t table_stride, const float* bias, size_t bias_stride,
+                                                      void* scratch, size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream)
 {
-    const char* who = "sample_argmax_filtered_rows_advance_fp32";
-    MILA_REQUIRE(logits && token_out && positions_dev && active_dev && table, "%s: null pointer", who);
+    const char* who = bias ? "sample_argmax_biased_rows_advance_fp32" : "sample_argmax_filtered_rows_advance_fp32";
+    MILA_REQUIRE(logits && token_out && positions_dev && active_dev && (table || bias), "%s: null pointer", who);
     MILA_REQUIRE(rows >= 1 && rows <= 4, "%s: rows=%d outside 1 .. 4", who, rows);
     MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
     MILA_REQUIRE(logits_stride >= (size_t)vocab, "%s: logits_stride %zu < vocab %d", who, logits_stride, vocab);
     SampleFilter f{};
     const int rc = make_filter(filters, table, table_stride, rows, vocab, f, who);
     if (rc) return rc;
-    return run_argmax_filtered(logits, logits_stride, token_out, rows, vocab, softcap, f, scratch, scratch_bytes, nullptr, positions_dev, active_dev, as_stream(stream), who);
+    return run_argmax_filtered(logits, logits_stride, token_out, rows, vocab, softcap, f, scratch, scratch_bytes, nullptr, positions_dev, active_dev, as_stream(stream), who, bias,
+                               bias_stride);
+}
+
+// the filtered entries: their biased siblings without a bias table
+int mila_cdna4_sample_radix_filtered_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,
+                                          const mila_sample_filters* filters, uint32_t* table, void* scratch, size_t scratch_bytes, mila_stream_t stream)
+{
+    return mila_cdna4_sample_radix_biased_fp32(logits, token_out, vocab, softcap, temperature, top_k, top_p, r, filters, table, nullptr, 0, scratch, scratch_bytes, stream);
+}
+
+int mila_cdna4_sample_radix_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p,
+                                                  const float* draws, int draws_size, const mila_sample_filters* filters, uint32_t* table, void* scratch, size_t scratch_bytes,
+                                                  int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring, int ring_size, mila_stream_t stream)
+{
+    return mila_cdna4_sample_radix_biased_advance_fp32(logits, token_out, vocab, softcap, temperature, top_k, top_p, draws, draws_size, filters, table, nullptr, 0, scratch,
+                                                       scratch_bytes, position_dev, seq_dev, ring, ring_size, stream);
+}
+
+int mila_cdna4_sample_radix_filtered_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature, int top_k,
+                                               float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table, size_t table_stride, void* scratch,
+                                               size_t scratch_bytes, mila_stream_t stream)
+{
+    return mila_cdna4_sample_radix_biased_rows_fp32(logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, filters, table, table_stride, nullptr,
+                                                    0, scratch, scratch_bytes, stream);
+}
+
+int mila_cdna4_sample_radix_filtered_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, float temperature,
+                                                       int top_k, float top_p, const float* draws, const mila_sample_filters* filters, uint32_t* table, size_t table_stride,
+                                                       void* scratch, size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream)
+{
+    return mila_cdna4_sample_radix_biased_rows_advance_fp32(logits, logits_stride, token_out, rows, vocab, softcap, temperature, top_k, top_p, draws, filters, table, table_stride,
+                                                            nullptr, 0, scratch, scratch_bytes, positions_dev, active_dev, stream);
+}
+
+int mila_cdna4_sample_argmax_filtered_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
+                                           void* scratch, size_t scratch_bytes, mila_stream_t stream)
+{
+    return mila_cdna4_sample_argmax_biased_fp32(logits, token_out, vocab, softcap, filters, table, nullptr, 0, scratch, scratch_bytes, stream);
+}
+
+int mila_cdna4_sample_argmax_filtered_advance_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, const mila_sample_filters* filters, uint32_t* table,
+                                                   void* scratch, size_t scratch_bytes, int32_t* position_dev, unsigned long long* seq_dev, unsigned long long* ring,
+                                                   int ring_size, mila_stream_t stream)
+{
+    return mila_cdna4_sample_argmax_biased_advance_fp32(logits, token_out, vocab, softcap, filters, table, nullptr, 0, scratch, scratch_bytes, position_dev, seq_dev, ring,
+                                                        ring_size, stream);
+}
+
+int mila_cdna4_sample_argmax_filtered_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                        const mila_sample_filters* filters, uint32_t* table, size_t table_stride, void* scratch, size_t scratch_bytes,
+                                                        int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream)
+{
+    return mila_cdna4_sample_argmax_biased_rows_advance_fp32(logits, logits_stride, token_out, rows, vocab, softcap, filters, table, table_stride, nullptr, 0, scratch,
+                                                             scratch_bytes, positions_dev, active_dev, stream);
 }
 
 // "launches:k_passes:p_passes:scratch_need:scale_filtered:mask_filtered" of a filtered call (plan_radix, the function the entries launch from); 0 for arguments the

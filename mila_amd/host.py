@@ -100,6 +100,59 @@ def _filters(min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_
     return f
 
 
+class TokenBiasRequestC(C.Structure):
+    """mila_token_bias_request (host/src/gemma_runner.cpp): the four bias controls of a generate request, by pointer"""
+    _fields_ = [("bias_ids", C.c_void_p), ("bias_values", C.c_void_p), ("n_bias", C.c_int64), ("banned", C.c_void_p), ("n_banned", C.c_int64),
+                ("allowed", C.c_void_p), ("n_allowed", C.c_int64), ("min_tokens", C.c_int32)]
+
+
+def _id_list(ids, what, vocab):
+    out = []
+    for t in ids:
+        if isinstance(t, (bool, float)) or int(t) != t:
+            raise ValueError("%s: token id %r is not an integer" % (what, t))
+        t = int(t)
+        if t < 0 or (vocab is not None and t >= vocab):
+            raise ValueError("%s: token id %d outside the vocabulary" % (what, t))
+        out.append(t)
+    return out
+
+
+def _bias_request(logit_bias=None, banned_tokens=(), allowed_tokens=(), min_tokens=0, stop_tokens=(), max_new_tokens=None, vocab=None):
+    """the bias controls of a request, checked as Mila/TokenBias.h: composeTokenBias checks them (ValueError before any call): an id outside the vocabulary, a NaN or
+    infinite logit_bias value, an id twice in logit_bias, no token left with a finite value (with an explicit stop set: before the min_tokens restore too),
+    min_tokens < 0 or above max_new_tokens.  -> None when the request has none of them, else (TokenBiasRequestC, the arrays it points into)."""
+    items = list(logit_bias.items()) if hasattr(logit_bias, "items") else list(logit_bias or ())
+    ids = _id_list([k for k, _ in items], "logit_bias", vocab)
+    if len(set(ids)) != len(ids):
+        raise ValueError("logit_bias: an id occurs twice")
+    vals = [float(v) for _, v in items]
+    for t, v in zip(ids, vals):
+        if not np.isfinite(v):
+            raise ValueError("logit_bias: the value of id %d is not finite" % t)
+    banned = _id_list(banned_tokens, "banned_tokens", vocab)
+    allowed = _id_list(allowed_tokens, "allowed_tokens", vocab)
+    if isinstance(min_tokens, (bool, float)) or int(min_tokens) != min_tokens or int(min_tokens) < 0:
+        raise ValueError("min_tokens must be an integer >= 0 (got %r)" % (min_tokens,))
+    min_tokens = int(min_tokens)
+    if max_new_tokens is not None and min_tokens > int(max_new_tokens):
+        raise ValueError("min_tokens %d exceeds max_new_tokens %d" % (min_tokens, int(max_new_tokens)))
+    held = set(_id_list(stop_tokens, "stop_tokens", vocab)) if min_tokens > 0 else set()
+    for forbidden, when in ((set(banned), ""), (set(banned) | held, " before the min_tokens restore")):
+        if allowed:
+            left = len(set(allowed) - forbidden)
+        else:
+            left = None if vocab is None else vocab - len(forbidden)
+        if left is not None and left <= 0:
+            raise ValueError("no token is left with a finite bias%s" % when)
+    if not (ids or banned or allowed or min_tokens):
+        return None
+    arrays = (np.ascontiguousarray(ids, dtype=np.int32), np.ascontiguousarray(vals, dtype=np.float32), np.ascontiguousarray(banned, dtype=np.int32),
+              np.ascontiguousarray(allowed, dtype=np.int32))
+    ptr = [a.ctypes.data if a.size else None for a in arrays]
+    return TokenBiasRequestC(ptr[0], ptr[1], arrays[0].size, ptr[2], arrays[2].size, ptr[3], arrays[3].size, min_tokens), arrays
+
+
 class Gemma:
     """GemmaTransformer<policy> with synthetic weights on cuda:0."""
 
@@ -328,6 +381,34 @@ class Gemma:
         out = np.zeros(self.vocab, dtype=np.uint32)
         _check(lib.mila_gemma_read_token_table(self.h, int(row), out.ctypes.data))
         return out
+
+    def set_token_bias(self, bias=None, fill=0.0, update=False):
+        """the bias table of every sampler of the step-level calls that follow (GemmaTransformer::setTokenBias; include/mila_cdna4.h: logit bias): every value
+        `fill` (finite or -inf), then bias[id] (finite or -inf) at each id of the dict / (id, value) list.  update=True changes the listed entries of a table that is
+        on and leaves the rest.  bias=None turns the bias off.  Turning it on or off re-captures a graph once; changing the contents never does."""
+        lib = load()
+        lib.mila_gemma_set_token_bias.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+        if bias is None:
+            _check(lib.mila_gemma_set_token_bias(self.h, 0.0, None, None, -1, 1))
+            return
+        items = list(bias.items()) if hasattr(bias, "items") else list(bias)
+        ids = _id_list([k for k, _ in items], "set_token_bias", self.vocab)
+        if len(set(ids)) != len(ids):
+            raise ValueError("set_token_bias: an id occurs twice")
+        vals = [float(v) for _, v in items]
+        for v in vals + [float(fill)]:
+            if np.isnan(v) or v == float("inf"):
+                raise ValueError("set_token_bias: a bias value must be finite or -inf (got %g)" % v)
+        i32, f32 = np.ascontiguousarray(ids, dtype=np.int32), np.ascontiguousarray(vals, dtype=np.float32)
+        _check(lib.mila_gemma_set_token_bias(self.h, float(fill), i32.ctypes.data if i32.size else None, f32.ctypes.data if f32.size else None, i32.size, 0 if update else 1))
+
+    def token_bias(self):
+        """-> (the bias table, float32 [vocab]; whether the bias is on)"""
+        lib = load()
+        lib.mila_gemma_read_token_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        out, on = np.zeros(self.vocab, dtype=np.float32), C.c_int32()
+        _check(lib.mila_gemma_read_token_bias(self.h, out.ctypes.data, C.byref(on)))
+        return out, bool(on.value)
 
     def _with_filters(self, filters, fn):
         """fn() under the given filter keywords, neutral again afterwards; no keywords: whatever set_sampling_filters() left"""
@@ -658,13 +739,18 @@ class GemmaModel:
         return out
 
     def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
-                 speculative_sampling=False, logprobs=None, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+                 speculative_sampling=False, logprobs=None, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None,
+                 banned_tokens=(), allowed_tokens=(), min_tokens=0):
         """_generate() with the sampling filters (GenerateParams::sampling.min_p / .repetition_penalty / .presence_penalty / .frequency_penalty): the penalties read a
         token table on the device that starts from the whole prompt and counts every generated token; greedy with a penalty = argmax of the adjusted logits; a request
         with any filter set takes the plain loop on a draft_tokens model too.  Log-probabilities are those of the unpenalized logits.  With every filter neutral this
-        is _generate(), entry for entry."""
+        is _generate(), entry for entry.
+        logit_bias ({id: finite value}), banned_tokens, allowed_tokens (a closed answer set; a ban wins) and min_tokens (no stop token among the first min_tokens
+        samples) are GenerateParams' fields of those names: one bias table on the device, added to the capped logit by every sampler of the request; a request with
+        any of them takes the plain loop on a draft_tokens model.  Log-probabilities stay those of the unbiased logits."""
         f = _filters(min_p, repetition_penalty, presence_penalty, frequency_penalty)
-        if f == _filters():
+        bias = _bias_request(logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_tokens, max_new_tokens, self.vocab_size())
+        if f == _filters() and bias is None:
             return self._generate(prompt, max_new_tokens, stop_tokens, temperature, top_k, top_p, seed, cancel_after, draft_hint, speculative_sampling, logprobs)
         lib = load()
         pr = np.ascontiguousarray(prompt, dtype=np.int32)
@@ -679,19 +765,19 @@ class GemmaModel:
         head = [self.h, pr.ctypes.data, len(pr), -1 if max_new_tokens is None else int(max_new_tokens), st.ctypes.data if len(st) else None, len(st), float(temperature),
                 int(top_k), float(top_p), -1 if seed is None else int(seed)]
         head_types = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int64]
-        tail = [top_n, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data, C.byref(n_lp), fl]
-        tail_types = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        tail = [top_n, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data, C.byref(n_lp), fl, None if bias is None else C.byref(bias[0])]
+        tail_types = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if speculative_sampling or draft_hint is not None:
             if cancel_after is not None:
                 raise ValueError("GemmaModel.generate: draft_hint / speculative_sampling cannot be combined with cancel_after")
             hint = np.ascontiguousarray([] if draft_hint is None else draft_hint, dtype=np.int32)
             stats = (C.c_int64 * 4)()
-            lib.mila_gemma_model_generate_spec_filtered.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types
-            _check(lib.mila_gemma_model_generate_spec_filtered(*head, hint.ctypes.data if hint.size else None, int(hint.size), int(bool(speculative_sampling)), out.ctypes.data,
+            lib.mila_gemma_model_generate_spec_biased.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types
+            _check(lib.mila_gemma_model_generate_spec_biased(*head, hint.ctypes.data if hint.size else None, int(hint.size), int(bool(speculative_sampling)), out.ctypes.data,
                                                                len(out), C.byref(n), C.byref(status), stats, *tail))
         else:
-            lib.mila_gemma_model_generate_filtered.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + tail_types
-            _check(lib.mila_gemma_model_generate_filtered(*head, out.ctypes.data, len(out), C.byref(n), C.byref(status), C.byref(reused),
+            lib.mila_gemma_model_generate_biased.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + tail_types
+            _check(lib.mila_gemma_model_generate_biased(*head, out.ctypes.data, len(out), C.byref(n), C.byref(status), C.byref(reused),
                                                           -1 if cancel_after is None else int(cancel_after), *tail))
         res = (out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], reused.value)
         if logprobs is None:
@@ -767,6 +853,12 @@ class GemmaModel:
                                              C.byref(reused), -1 if cancel_after is None else int(cancel_after)))
         return out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], reused.value
 
+    def vocab_size(self):
+        lib = load()
+        lib.mila_gemma_model_vocab_size.restype = C.c_int64
+        lib.mila_gemma_model_vocab_size.argtypes = [C.c_void_p]
+        return int(lib.mila_gemma_model_vocab_size(self.h))
+
     def speculation_stats(self):
         """GemmaModel::lastSpeculation() of the last generate(): {"steps", "chain_steps", "drafted", "accepted"} -- decode steps in all, those that were chain
         steps, the drafter's tokens those carried (padding not counted) and how many of them were accepted"""
@@ -777,14 +869,17 @@ class GemmaModel:
         return dict(zip(("steps", "chain_steps", "drafted", "accepted"), [int(v) for v in out]))
 
     def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0, logprobs=None, min_p=0.0, repetition_penalty=1.0,
-                       presence_penalty=0.0, frequency_penalty=0.0):
-        """_generate_batch() with the sampling filters of generate(), shared by the rows; every row has its own token table"""
+                       presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, banned_tokens=(), allowed_tokens=(), min_tokens=0):
+        """_generate_batch() with the sampling filters of generate(), shared by the rows; every row has its own token table.  logit_bias / banned_tokens /
+        allowed_tokens / min_tokens as in generate(): one bias table shared by the rows, which step in lockstep."""
         f = _filters(min_p, repetition_penalty, presence_penalty, frequency_penalty)
-        if f == _filters():
+        bias = _bias_request(logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_tokens, max_new_tokens, self.vocab_size())
+        if f == _filters() and bias is None:
             return self._generate_batch(prompts, max_new_tokens, stop_tokens, temperature, top_k, top_p, seed, logprobs)
         lib = load()
-        lib.mila_gemma_model_generate_rows_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64,
-                                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mila_gemma_model_generate_rows_biased.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64,
+                                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                              C.c_void_p]
         flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if len(prompts) else np.zeros(0), dtype=np.int32)
         offs = np.ascontiguousarray(np.cumsum([0] + [len(p) for p in prompts]), dtype=np.int64)
         st = np.ascontiguousarray(list(stop_tokens), dtype=np.int32)
@@ -795,10 +890,10 @@ class GemmaModel:
         width = max(top_n, 1)
         lp, ids, tlp = np.zeros(out.shape, dtype=np.float32), np.zeros(out.shape + (width,), dtype=np.int32), np.zeros(out.shape + (width,), dtype=np.float32)
         fl = (C.c_float * 4)(*f)
-        _check(lib.mila_gemma_model_generate_rows_filtered(self.h, flat.ctypes.data, offs.ctypes.data, len(prompts), -1 if max_new_tokens is None else int(max_new_tokens),
+        _check(lib.mila_gemma_model_generate_rows_biased(self.h, flat.ctypes.data, offs.ctypes.data, len(prompts), -1 if max_new_tokens is None else int(max_new_tokens),
                                                            st.ctypes.data if len(st) else None, len(st), float(temperature), int(top_k), float(top_p), int(seed), out.ctypes.data,
                                                            out.shape[1], counts.ctypes.data, status.ctypes.data, top_n, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data,
-                                                           lp_counts.ctypes.data, fl))
+                                                           lp_counts.ctypes.data, fl, None if bias is None else C.byref(bias[0])))
         rows = [(out[b, :min(int(counts[b]), out.shape[1])].tolist(), GENERATE_STATUS[int(status[b])]) for b in range(len(prompts))]
         if logprobs is None:
             return rows

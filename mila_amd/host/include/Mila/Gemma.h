@@ -272,6 +272,46 @@ namespace Mila::Dnn
         /// the tables (nullptr before the first penalty or resetTokenTable())
         Compute::RocmTokenTable* tokenTable() noexcept { return token_table_.get(); }
 
+        /// Logit bias (mila_cdna4.h: logit bias; Mila/TokenBias.h composes a request's logit_bias / banned / allowed / min_tokens into one): a table of vocab fp32
+        /// values, finite or -inf, added to the capped logit ahead of the penalties by every sampler of this network but the chain step's -- the eager samplers, the
+        /// one-row captured step and the rows step (one table for every row), greedy and stochastic.  setTokenBias() writes the whole table (every value `fill`, then
+        /// values[j] at ids[j]) and turns the bias on; updateTokenBias() changes entries of a table that is on; clearTokenBias() turns it off.  Whether a bias is on
+        /// belongs to what each graph was captured for, as the filters do: turning it on or off re-captures once; changing the table's contents never does, because
+        /// the table's address is what is captured.  With a bias a greedy token is argmax of the adjusted logits: the greedy steps then end at the logits and run the
+        /// penalized greedy sampler's two launches.  Log-probabilities stay those of the unbiased logits.  The table is allocated by the first setTokenBias() and
+        /// counted in the memory statistics from then on.  The caller keeps at least one token finite.
+        void setTokenBias( float fill, const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            if ( std::isnan( fill ) || ( std::isinf( fill ) && fill > 0.0f ) ) throw std::invalid_argument( "GemmaTransformer::setTokenBias: the fill value must be finite or -inf" );
+            checkBiasEntries( ids_host, values_host, n, "GemmaTransformer::setTokenBias" );
+            if ( !token_bias_ ) token_bias_ = std::make_unique<Compute::RocmTokenBias>( ctx_, cfg_.vocab_size );
+            token_bias_->apply( fill, ids_host, values_host, n );
+            bias_on_ = true;
+        }
+        void updateTokenBias( const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            if ( !bias_on_ ) throw std::logic_error( "GemmaTransformer::updateTokenBias: no bias is set (setTokenBias)" );
+            checkBiasEntries( ids_host, values_host, n, "GemmaTransformer::updateTokenBias" );
+            token_bias_->update( ids_host, values_host, n );
+        }
+        /// an update uploaded now and enqueued later: commitTokenBiasUpdate() is one small launch in stream order that reads no host memory -- what a decode-ahead
+        /// loop puts between two replays (GemmaModel: the min_tokens restore)
+        void stageTokenBiasUpdate( const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            if ( !bias_on_ ) throw std::logic_error( "GemmaTransformer::stageTokenBiasUpdate: no bias is set (setTokenBias)" );
+            checkBiasEntries( ids_host, values_host, n, "GemmaTransformer::stageTokenBiasUpdate" );
+            token_bias_->stage( ids_host, values_host, n );
+        }
+        void commitTokenBiasUpdate()
+        {
+            if ( !bias_on_ ) throw std::logic_error( "GemmaTransformer::commitTokenBiasUpdate: no bias is set (setTokenBias)" );
+            token_bias_->commit();
+        }
+        void clearTokenBias() noexcept { bias_on_ = false; }
+        bool tokenBiasOn() const noexcept { return bias_on_; }
+        /// the table (nullptr before the first setTokenBias())
+        Compute::RocmTokenBias* tokenBias() noexcept { return token_bias_.get(); }
+
         /// capture the fused step once; afterwards replayGraph() advances one token per call.
         /// The token is read from `token` (device) and the position from an internal device counter.
         /// Every device pointer the captured nodes hold is model-owned and fixed for the model's lifetime (the split-attention partials
@@ -293,7 +333,7 @@ namespace Mila::Dnn
                 int sampler_partials = 0;
                 captured_band_end_ = bandBucket( start_position );
                 const bool stochastic = graph_sampling_.has_value();
-                const bool penalized_greedy = sample_in_graph_ && !stochastic && filters_.penalized();      // ends at the logits; the penalized sampler's two launches follow
+                const bool penalized_greedy = sample_in_graph_ && !stochastic && ( filters_.penalized() || bias_on_ );      // ends at the logits; the penalized sampler's two launches follow
                 if ( stochastic && ( !draw_ring_ || !token_seq_ ) )
                     throw std::invalid_argument( "GemmaTransformer::captureGraph: a stochastic step needs setDrawRing() and the sequence counter of setTokenRing()" );
                 if ( step_lp_ && !stochastic && !sample_in_graph_ )
@@ -301,14 +341,14 @@ namespace Mila::Dnn
                 enqueueFusedStep( token.data(), static_cast<int>( captured_band_end_ ), pos_dev_->data(), ( sample_in_graph_ && !stochastic && !penalized_greedy ) ? &sampler_partials : nullptr );
                 // stochastic: the step ends at the logits like the sampler-less one, then the radix pipeline on the model-owned workspace; its last node draws from the
                 // ring, writes the next token, bumps the position and publishes -- in the place of the advance_position node.  One linear chain on one stream.
-                if ( stochastic && graph_sampling_->filtered() )      // the same launches, in their filtered instantiations: the node count does not move
+                if ( stochastic && ( graph_sampling_->filtered() || bias_on_ ) )      // the same launches, in their filtered / biased instantiations: the node count does not move
                 {
                     const mila_sample_filters f = graph_sampling_->filters();
-                    Compute::rocmCheck( mila_cdna4_sample_radix_filtered_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size,
-                                                                                       cfg_.final_logit_softcapping, graph_sampling_->temperature, graph_sampling_->top_k,
-                                                                                       graph_sampling_->top_p, draw_ring_, draw_ring_size_, &f, tableWords( *graph_sampling_, 0, false ),
-                                                                                       radix_scratch_->data(), radix_scratch_->sizeInBytes(), pos_dev_->data(), token_seq_, token_ring_,
-                                                                                       token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
+                    Compute::rocmCheck( mila_cdna4_sample_radix_biased_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size,
+                                                                                     cfg_.final_logit_softcapping, graph_sampling_->temperature, graph_sampling_->top_k,
+                                                                                     graph_sampling_->top_p, draw_ring_, draw_ring_size_, &f, tableWords( *graph_sampling_, 0, false ),
+                                                                                     biasValues(), 0, radix_scratch_->data(), radix_scratch_->sizeInBytes(), pos_dev_->data(), token_seq_,
+                                                                                     token_ring_, token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
                 }
                 else if ( stochastic )
                     Compute::rocmCheck( mila_cdna4_sample_radix_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping,
@@ -318,10 +358,10 @@ namespace Mila::Dnn
                 else if ( penalized_greedy )
                 {
                     const mila_sample_filters f = filters_.filters();
-                    Compute::rocmCheck( mila_cdna4_sample_argmax_filtered_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size,
-                                                                                        cfg_.final_logit_softcapping, &f, tableWords( filters_, 0, false ), sample_scratch_->data(),
-                                                                                        sample_scratch_->sizeInBytes(), pos_dev_->data(), token_ring_ ? token_seq_ : nullptr, token_ring_,
-                                                                                        token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
+                    Compute::rocmCheck( mila_cdna4_sample_argmax_biased_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size,
+                                                                                      cfg_.final_logit_softcapping, &f, tableWords( filters_, 0, false ), biasValues(), 0,
+                                                                                      sample_scratch_->data(), sample_scratch_->sizeInBytes(), pos_dev_->data(),
+                                                                                      token_ring_ ? token_seq_ : nullptr, token_ring_, token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
                 }
                 else if ( sample_in_graph_ )
                     Compute::rocmCheck( mila_cdna4_sample_argmax_final_advance( const_cast<TokenTensor&>( token ).data(), sample_scratch_->data(), sample_scratch_->sizeInBytes(), sampler_partials,
@@ -342,6 +382,7 @@ namespace Mila::Dnn
             captured_ring_ = token_ring_;
             captured_sampling_ = graph_sampling_;
             captured_filters_ = filters_;
+            captured_bias_ = bias_on_;
             captured_draw_ring_ = graph_sampling_ ? draw_ring_ : nullptr;
             captured_lp_ = step_lp_;
             ++graph_captures_;
@@ -355,6 +396,7 @@ namespace Mila::Dnn
             if ( !graph_exec_ || captured_token_ != token.data() || captured_sample_in_graph_ != sample_in_graph_ || captured_ring_ != token_ring_ ||
                  !sameSampling( captured_sampling_, graph_sampling_ ) || ( graph_sampling_ && captured_draw_ring_ != draw_ring_ ) || captured_lp_ != step_lp_ ||
                  ( sample_in_graph_ && !graph_sampling_ && !samePenalties( captured_filters_, filters_ ) ) ||
+                 ( ( sample_in_graph_ || graph_sampling_ ) && captured_bias_ != bias_on_ ) ||
                  bandBucket( start_position ) != captured_band_end_ )
                 captureGraph( token, start_position );
         }
@@ -515,12 +557,12 @@ namespace Mila::Dnn
         void sampleRowGreedyWith( int b, const SamplingParams& fl )
         {
             requireRows( b );
-            if ( fl.penalized() )
+            if ( fl.penalized() || bias_on_ )
             {
                 const mila_sample_filters f = fl.filters();
-                Compute::rocmCheck( mila_cdna4_sample_argmax_filtered_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
-                                                                            cfg_.final_logit_softcapping, &f, tableWords( fl, b, true ), sample_scratch_->data(),
-                                                                            sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
+                Compute::rocmCheck( mila_cdna4_sample_argmax_biased_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
+                                                                          cfg_.final_logit_softcapping, &f, tableWords( fl, b, true ), biasValues(), 0, sample_scratch_->data(),
+                                                                          sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
                 return;
             }
             Compute::rocmCheck( mila_cdna4_sample_argmax_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
@@ -530,13 +572,13 @@ namespace Mila::Dnn
         {
             if ( sp.temperature <= 0.0f ) { sampleRowGreedyWith( b, sp.filtered() ? sp : filters_ ); return; }
             requireRows( b );
-            if ( sp.filtered() )
+            if ( sp.filtered() || bias_on_ )
             {
                 sp.checkFilters( "GemmaTransformer::sampleRowStochastic" );
                 const mila_sample_filters f = sp.filters();
-                Compute::rocmCheck( mila_cdna4_sample_radix_filtered_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
-                                                                           cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r, &f, tableWords( sp, b, true ),
-                                                                           radix_scratch_->data(), radix_scratch_->sizeInBytes(), ctx_->getStream() ) );
+                Compute::rocmCheck( mila_cdna4_sample_radix_biased_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
+                                                                         cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r, &f, tableWords( sp, b, true ), biasValues(), 0,
+                                                                         radix_scratch_->data(), radix_scratch_->sizeInBytes(), ctx_->getStream() ) );
                 return;
             }
             Compute::rocmCheck( mila_cdna4_sample_radix_fp32( rows_->logits->data() + static_cast<size_t>( b ) * cfg_.vocab_size, rows_->tok->data() + b, (int)cfg_.vocab_size,
@@ -574,6 +616,7 @@ namespace Mila::Dnn
             rows_captured_B_ = B; rows_captured_greedy_ = greedy; rows_captured_band_ = band;
             rows_captured_sampling_ = rows_sampling_; rows_captured_draws_ = rows_draws_;
             rows_captured_filters_ = filters_;
+            rows_captured_bias_ = bias_on_;
             rows_captured_lp_ = step_lp_;
             ++rows_graph_captures_;
         }
@@ -582,7 +625,7 @@ namespace Mila::Dnn
         {
             if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) || rows_captured_lp_ != step_lp_ ||
                  ( !greedy && ( !sameSampling( rows_captured_sampling_, rows_sampling_ ) || rows_captured_draws_ != rows_draws_ ) ) ||
-                 ( greedy && !samePenalties( rows_captured_filters_, filters_ ) ) )
+                 ( greedy && !samePenalties( rows_captured_filters_, filters_ ) ) || ( ( greedy || rowsSamplesInStep() ) && rows_captured_bias_ != bias_on_ ) )
                 captureGraphRows( B, max_position, greedy );
         }
         /// the stochastic sampler as the tail of a non-greedy rows step (mila_cdna4_sample_radix_rows_advance_fp32): with `sp` and `draws` set, decodeRows /
@@ -712,11 +755,12 @@ namespace Mila::Dnn
         void sampleGreedyWith( TokenTensor& token_out, const SamplingParams& fl )
         {
             Compute::TraceRange tr( "gemma.sample(greedy)" );
-            if ( fl.penalized() )
+            if ( fl.penalized() || bias_on_ )
             {
                 const mila_sample_filters f = fl.filters();
-                Compute::rocmCheck( mila_cdna4_sample_argmax_filtered_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, &f,
-                                                                            tableWords( fl, 0, true ), sample_scratch_->data(), sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
+                Compute::rocmCheck( mila_cdna4_sample_argmax_biased_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, &f,
+                                                                          tableWords( fl, 0, true ), biasValues(), 0, sample_scratch_->data(), sample_scratch_->sizeInBytes(),
+                                                                          ctx_->getStream() ) );
                 return;
             }
             Compute::rocmCheck( mila_cdna4_sample_argmax_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, sample_scratch_->data(),
@@ -729,6 +773,7 @@ namespace Mila::Dnn
         {
             if ( sp.temperature <= 0.0f ) { sampleGreedy( token_out ); return; }
             Compute::TraceRange tr( "gemma.sample(stochastic)" );
+            if ( bias_on_ ) throw std::invalid_argument( "GemmaTransformer::sampleStochastic: the search pipeline takes no bias table (sampleStochasticRadix)" );
             const size_t need = mila_cdna4_sample_stochastic_scratch_bytes( (int)cfg_.vocab_size );
             void* scratch = ctx_->getScratch( need );
             Compute::rocmCheck( mila_cdna4_sample_stochastic_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature,
@@ -740,13 +785,13 @@ namespace Mila::Dnn
         {
             if ( sp.temperature <= 0.0f ) { sampleGreedyWith( token_out, sp.filtered() ? sp : filters_ ); return; }
             Compute::TraceRange tr( "gemma.sample(stochastic, radix)" );
-            if ( sp.filtered() )      // the eager form of what a filtered captured step ends with
+            if ( sp.filtered() || bias_on_ )      // the eager form of what a filtered / biased captured step ends with
             {
                 sp.checkFilters( "GemmaTransformer::sampleStochasticRadix" );
                 const mila_sample_filters f = sp.filters();
-                Compute::rocmCheck( mila_cdna4_sample_radix_filtered_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature, sp.top_k,
-                                                                           sp.top_p, r, &f, tableWords( sp, 0, true ), radix_scratch_->data(), radix_scratch_->sizeInBytes(),
-                                                                           ctx_->getStream() ) );
+                Compute::rocmCheck( mila_cdna4_sample_radix_biased_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature, sp.top_k,
+                                                                         sp.top_p, r, &f, tableWords( sp, 0, true ), biasValues(), 0, radix_scratch_->data(), radix_scratch_->sizeInBytes(),
+                                                                         ctx_->getStream() ) );
                 return;
             }
             Compute::rocmCheck( mila_cdna4_sample_radix_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r,
@@ -1385,25 +1430,25 @@ namespace Mila::Dnn
             int partials = 0;
             if ( step_lp_ && !greedy && !rowsSamplesInStep() )
                 throw std::invalid_argument( "GemmaTransformer: token log-probabilities need a sampler tail in the rows step (greedy, or setRowsSampling)" );
-            const bool penalized_greedy = greedy && filters_.penalized();      // the lm_head epilogue cannot compute the adjusted logits: the step ends at the logits
+            const bool penalized_greedy = greedy && ( filters_.penalized() || bias_on_ );      // the lm_head epilogue cannot compute the adjusted logits: the step ends at the logits
             enqueueFusedStepRows( B, static_cast<int>( band ), ( greedy && !penalized_greedy ) ? &partials : nullptr );
             auto& R = *rows_;
-            if ( !greedy && rowsSamplesInStep() && rows_sampling_->filtered() )
+            if ( !greedy && rowsSamplesInStep() && ( rows_sampling_->filtered() || bias_on_ ) )      // (one bias table for every row: stride 0)
             {
                 const mila_sample_filters f = rows_sampling_->filters();
-                Compute::rocmCheck( mila_cdna4_sample_radix_filtered_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
-                                                                                        cfg_.final_logit_softcapping, rows_sampling_->temperature, rows_sampling_->top_k,
-                                                                                        rows_sampling_->top_p, rows_draws_, &f, tableWords( *rows_sampling_, 0, false ),
-                                                                                        static_cast<size_t>( cfg_.vocab_size ), R.radix_scratch->data(), R.radix_scratch->sizeInBytes(),
-                                                                                        R.pos->data(), R.active->data(), ctx_->getStream() ) );
+                Compute::rocmCheck( mila_cdna4_sample_radix_biased_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
+                                                                                      cfg_.final_logit_softcapping, rows_sampling_->temperature, rows_sampling_->top_k,
+                                                                                      rows_sampling_->top_p, rows_draws_, &f, tableWords( *rows_sampling_, 0, false ),
+                                                                                      static_cast<size_t>( cfg_.vocab_size ), biasValues(), 0, R.radix_scratch->data(),
+                                                                                      R.radix_scratch->sizeInBytes(), R.pos->data(), R.active->data(), ctx_->getStream() ) );
             }
             else if ( penalized_greedy )
             {
                 const mila_sample_filters f = filters_.filters();
-                Compute::rocmCheck( mila_cdna4_sample_argmax_filtered_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
-                                                                                         cfg_.final_logit_softcapping, &f, tableWords( filters_, 0, false ),
-                                                                                         static_cast<size_t>( cfg_.vocab_size ), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(),
-                                                                                         R.pos->data(), R.active->data(), ctx_->getStream() ) );
+                Compute::rocmCheck( mila_cdna4_sample_argmax_biased_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
+                                                                                       cfg_.final_logit_softcapping, &f, tableWords( filters_, 0, false ),
+                                                                                       static_cast<size_t>( cfg_.vocab_size ), biasValues(), 0, R.sample_scratch->data(),
+                                                                                       R.sample_scratch->sizeInBytes(), R.pos->data(), R.active->data(), ctx_->getStream() ) );
             }
             else if ( !greedy && rowsSamplesInStep() )      // the radix pipeline over the B rows behind the logits; its tail takes the place of the position bump
                 Compute::rocmCheck( mila_cdna4_sample_radix_rows_advance_fp32( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, (int)cfg_.vocab_size,
@@ -1424,6 +1469,7 @@ namespace Mila::Dnn
         {
             int partials = 0;
             if ( filters_.penalized() ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no penalties (setSamplingFilters)" );
+            if ( bias_on_ ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no bias table (clearTokenBias)" );      // refused rather than silently unbiased
             const bool stochastic = chainSamples();
             enqueueFusedStepRows( T, static_cast<int>( band ), stochastic ? nullptr : &partials, &at );      // stochastic: the lm_head leaves the logits only
             auto& R = *rows_;
@@ -1821,6 +1867,7 @@ namespace Mila::Dnn
             if ( lp_op_ ) b += lp_op_->stateBytes();
             if ( score_op_ ) b += score_op_->stateBytes();
             if ( token_table_ ) b += token_table_->stateBytes();
+            if ( token_bias_ ) b += token_bias_->stateBytes();
             return b;
         }
         size_t requiredOwnStateBytes() const
@@ -1844,6 +1891,7 @@ namespace Mila::Dnn
             if ( lp_op_ ) b += lp_op_->stateBytes();                                                         // token log-probabilities, once setStepLogprobs() turned them on
             if ( score_op_ ) b += score_op_->stateBytes();                                                   // prompt log-probabilities, once prefillScored() has run
             if ( token_table_ ) b += Compute::RocmTokenTable::requiredBytes( cfg_.vocab_size, token_table_->rows() );      // the token tables, once a penalty was set
+            if ( token_bias_ ) b += Compute::RocmTokenBias::requiredBytes( cfg_.vocab_size );                              // the bias table and its staging, once a bias was set
             return b;
         }
     public:
@@ -1929,6 +1977,20 @@ namespace Mila::Dnn
         // sampling filters: the greedy samplers' setting, what the one-row and the rows graph were captured with, and the token tables (from the first penalty on)
         SamplingParams filters_{}, captured_filters_{}, rows_captured_filters_{};
         std::unique_ptr<Compute::RocmTokenTable> token_table_;
+        // logit bias: the table (from the first setTokenBias() on), whether it is on, and what the one-row and the rows graph were captured with
+        std::unique_ptr<Compute::RocmTokenBias> token_bias_;
+        bool bias_on_ = false, captured_bias_ = false, rows_captured_bias_ = false;
+        const float* biasValues() noexcept { return bias_on_ ? token_bias_->data() : nullptr; }
+        void checkBiasEntries( const int32_t* ids, const float* values, size_t n, const char* who ) const
+        {
+            if ( n && ( !ids || !values ) ) throw std::invalid_argument( std::string( who ) + ": null pointer" );
+            for ( size_t i = 0; i < n; ++i )
+            {
+                if ( ids[ i ] < 0 || ids[ i ] >= cfg_.vocab_size ) throw std::invalid_argument( std::string( who ) + ": token id " + std::to_string( ids[ i ] ) + " outside the vocabulary" );
+                if ( std::isnan( values[ i ] ) || ( std::isinf( values[ i ] ) && values[ i ] > 0.0f ) )
+                    throw std::invalid_argument( std::string( who ) + ": the value of id " + std::to_string( ids[ i ] ) + " must be finite or -inf" );
+            }
+        }
         static SamplingParams onlyFilters( const SamplingParams& f ) noexcept
         {
             SamplingParams o{};

@@ -22,6 +22,7 @@
 #include <variant>
 
 #include "Gemma.h"
+#include "TokenBias.h"
 
 namespace Mila::Dnn
 {
@@ -95,7 +96,35 @@ namespace Mila::Dnn
         /// the tokens on_token sees.  Computed on the device inside the decode step; tokens, status, generator state and prefix reuse are what they are without it.
         std::optional<int> logprobs;
         std::function<void( const TokenLogprobs& )> on_logprobs{};
+        /// Logit bias, banned tokens, a closed answer set and min_tokens (Mila/TokenBias.h composes the four into ONE device table of vocab fp32 values that the
+        /// samplers add to the capped logit; include/mila_cdna4.h: logit bias), all empty / 0 by default.  The table is written before the first sample; with
+        /// min_tokens > 0 the stop tokens are forbidden until the step that produces sample index min_tokens (the first sampled token is index 0), in front of which
+        /// the loop enqueues the restore in stream order -- one small launch, no host round trip, the captured step unchanged.  A request with any of them set takes
+        /// the plain loop on a withDraftTokens model, as the sampling filters do.  generateBatch shares one table among its rows.  Log-probabilities are those of the
+        /// unbiased logits.  A request without them clears the network's bias.
+        std::vector<std::pair<int32_t, float>> logit_bias{};      ///< id -> finite additive bias, an id at most once
+        std::vector<int32_t> banned_tokens{};                     ///< never sampled (a ban wins over an allow)
+        std::vector<int32_t> allowed_tokens{};                    ///< non-empty: only these may be sampled
+        int min_tokens = 0;                                       ///< no stop token among the first min_tokens samples
     };
+    /// the bias table of a request (throws invalid_argument for what composeTokenBias refuses); stop_ids: the request's effective stop set
+    inline TokenBiasPlan composeRequestBias( const GenerateParams& params, const std::unordered_set<int32_t>& stop_ids, dim_t vocab )
+    {
+        TokenBiasRequest rq;
+        rq.logit_bias = params.logit_bias; rq.banned_tokens = params.banned_tokens; rq.allowed_tokens = params.allowed_tokens;
+        rq.min_tokens = params.min_tokens; rq.max_new_tokens = params.max_new_tokens;
+        if ( params.min_tokens > 0 ) rq.stop_tokens.assign( stop_ids.begin(), stop_ids.end() );
+        TokenBiasPlan plan = composeTokenBias( rq, vocab );
+        if ( plan.restore_ids.size() > Compute::RocmTokenBias::kStage ) throw std::invalid_argument( "GenerateParams::min_tokens: a stop set of more than 1024 tokens" );
+        return plan;
+    }
+    /// the request's table onto the network before the first sample (the restore list staged for commitTokenBiasUpdate()); a request without one clears the bias
+    template<typename TNet> void applyRequestBias( TNet& net, const TokenBiasPlan& plan )
+    {
+        if ( !plan.active ) { net.clearTokenBias(); return; }
+        net.setTokenBias( plan.fill, plan.ids.data(), plan.values.data(), plan.ids.size() );
+        if ( plan.hasRestore() ) net.stageTokenBiasUpdate( plan.restore_ids.data(), plan.restore_values.data(), plan.restore_ids.size() );
+    }
     /// throws invalid_argument for a GenerateParams::logprobs outside 0 .. min(20, vocabulary)
     inline void checkLogprobsRequest( const GenerateParams& params, dim_t vocab )
     {
@@ -407,7 +436,9 @@ namespace Mila::Dnn
             else stop_ids.insert( params.stop_tokens.begin(), params.stop_tokens.end() );
             const bool greedy = isGreedy( params.sampling );
             const typename TNet::SamplingParams sp = networkSampling<TNet>( params.sampling );
+            const TokenBiasPlan bias_plan = composeRequestBias( params, stop_ids, vocabSize() );      // (nothing was enqueued yet)
             net.setSamplingFilters( sp );      // the greedy rows samplers' filters: this request's, neutral ones included
+            applyRequestBias( net, bias_plan );      // one table for every row, before the first sample
             std::vector<std::mt19937_64> rng;
             for ( int b = 0; b < n; ++b ) rng.emplace_back( seed + static_cast<uint64_t>( b ) );
             auto draw = [&]( int b ) { return std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng[ static_cast<size_t>( b ) ] ); };
@@ -443,6 +474,7 @@ namespace Mila::Dnn
             std::vector<int32_t> tokens( static_cast<size_t>( B ) );
             int live = n;
             bool stepped = false;
+            int next_sample = 1;      // the sample index the next rows step produces (every row's index 0 was sampled behind its prefill)
             while ( true )
             {
                 Compute::rocmCheck( mila_cdna4_memcpy_d2h( tokens.data(), net.rowsTokens().data(), static_cast<size_t>( B ) * 4, ctx->getStream() ) );
@@ -474,7 +506,9 @@ namespace Mila::Dnn
                 if ( !greedy )
                     for ( int b = 0; b < n; ++b )
                         if ( active[ static_cast<size_t>( b ) ] ) writeRowDraw( b, draw( b ) );
+                if ( bias_plan.hasRestore() && next_sample == bias_plan.restore_index ) net.commitTokenBiasUpdate();      // min_tokens: the stop tokens are back from this step on
                 net.replayGraphRows();
+                ++next_sample;
                 stepped = true;
                 for ( int b = 0; b < n; ++b )
                     if ( active[ static_cast<size_t>( b ) ] ) ++position[ static_cast<size_t>( b ) ];
@@ -651,6 +685,7 @@ namespace Mila::Dnn
             std::unordered_set<int32_t> stop_ids;
             if ( params.stop_tokens.empty() ) stop_ids = stopTokens();
             else stop_ids.insert( params.stop_tokens.begin(), params.stop_tokens.end() );
+            const TokenBiasPlan bias_plan = composeRequestBias( params, stop_ids, vocabSize() );      // (composed and checked before anything is enqueued)
 
             // transparent KV prefix reuse: cache positions [0, n) are a function of the first n tokens only, so token equality against what the
             // caches hold is the whole validity test; at least the last prompt position is always prefilled (fresh logits)
@@ -682,7 +717,8 @@ namespace Mila::Dnn
             // prompt -- a KV-reused prefix, whose chunks were not uploaded above, included -- before the first sample
             net.setSamplingFilters( net_sampling );
             if ( net_sampling.penalized() ) net.resetTokenTable( 0, prompt.data(), prompt.size() );
-            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 && !net_sampling.filtered() )
+            applyRequestBias( net, bias_plan );      // the bias table of this request, or none: before the first sample
+            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 && !net_sampling.filtered() && !bias_plan.active )
                 return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids, greedy );
             // log-probabilities travel like the tokens: every sample's record lands in slot seq % kSnapshots of a second host-visible ring, written by the two launches
             // behind the sampler -- eagerly for the first token, as the captured step's last nodes afterwards
@@ -715,6 +751,7 @@ namespace Mila::Dnn
                 net.setDevicePosition( position );
             }
             std::mt19937_64 rng_before_ahead = rng_;
+            int next_sample = 1;      // the sample index the next replay produces (index 0 was sampled eagerly above)
             while ( true )
             {
                 // (a cancel seen here needs no draw put back: the replay of the previous iteration drew for the sample the eager loop drew at that iteration's end --
@@ -738,7 +775,10 @@ namespace Mila::Dnn
                         std::memcpy( &bits, &r, 4 );
                         __atomic_store_n( reinterpret_cast<uint32_t*>( draws_host_ ) + ( ( published_ + 1 ) % kSnapshots ), bits, __ATOMIC_RELEASE );
                     }
+                    // min_tokens: the stop tokens get their values back in stream order immediately before the replay that produces sample index min_tokens
+                    if ( bias_plan.hasRestore() && next_sample == bias_plan.restore_index ) net.commitTokenBiasUpdate();
                     net.replayGraph();
+                    ++next_sample;
                     ++published_;      // the captured step ends with sampler + publish: the NEXT token
                 }
                 const int32_t token = awaitSampledToken( mine );

@@ -1225,6 +1225,78 @@ namespace Mila::Dnn::Compute
         std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> table_, stage_;
     };
 
+    /// One bias table row (mila_cdna4.h: logit bias -- `vocab` fp32 values, finite or -inf, that the biased samplers add to the capped logit) plus a staging buffer.
+    /// The table's address never changes, so a captured step that reads it sees every later update.  Everything runs on the context's stream.  apply() / update()
+    /// upload through the staging buffer and return once the ids are consumed (they synchronize); stage() uploads a list ahead of time and commit() enqueues it
+    /// later as one small launch without touching the host again -- what a decode-ahead loop puts between two replays.
+    class RocmTokenBias
+    {
+    public:
+        RocmTokenBias( IExecutionContext* ctx, dim_t vocab ) : context_( cast_context<DeviceType::Rocm>( ctx ) ), vocab_( vocab )
+        {
+            if ( vocab <= 0 ) throw std::invalid_argument( "RocmTokenBias: need a positive vocabulary" );
+            (void)narrowToKernelIndex( vocab, "vocab" );
+            const auto dev = context_->getDeviceId();
+            table_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ vocab } );
+            stage_ids_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( 2 * kStage ) } );
+            stage_values_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( 2 * kStage ) } );
+            rocmCheck( mila_cdna4_token_bias_fill( data(), 0, 0, static_cast<int>( vocab_ ), 0.0f, context_->getStream() ) );
+        }
+        float* data() { return table_->data(); }
+        dim_t vocab() const noexcept { return vocab_; }
+        /// the whole table: every value `fill`, then values[j] at ids[j]
+        void apply( float fill, const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            rocmCheck( mila_cdna4_token_bias_fill( data(), 0, 0, static_cast<int>( vocab_ ), fill, context_->getStream() ) );
+            update( ids_host, values_host, n );
+        }
+        /// values[j] at ids[j]; the other entries stay
+        void update( const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            for ( size_t i0 = 0; i0 < n; i0 += kStage )
+            {
+                const size_t c = std::min<size_t>( kStage, n - i0 );
+                rocmCheck( mila_cdna4_memcpy_h2d( stage_ids_->data(), ids_host + i0, c * 4, context_->getStream() ) );
+                rocmCheck( mila_cdna4_memcpy_h2d( stage_values_->data(), values_host + i0, c * 4, context_->getStream() ) );
+                rocmCheck( mila_cdna4_token_bias_set( data(), 0, 0, static_cast<int>( vocab_ ), stage_ids_->data(), stage_values_->data(), static_cast<int>( c ), context_->getStream() ) );
+            }
+            context_->synchronize();
+        }
+        /// upload an update of at most kStage entries into the second half of the staging buffer (synchronizes) ...
+        void stage( const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            if ( n > kStage ) throw std::invalid_argument( "RocmTokenBias::stage: more than " + std::to_string( kStage ) + " entries" );
+            if ( n )
+            {
+                rocmCheck( mila_cdna4_memcpy_h2d( stage_ids_->data() + kStage, ids_host, n * 4, context_->getStream() ) );
+                rocmCheck( mila_cdna4_memcpy_h2d( stage_values_->data() + kStage, values_host, n * 4, context_->getStream() ) );
+                context_->synchronize();
+            }
+            staged_ = n;
+        }
+        /// ... and enqueue it: one launch in stream order, no host data
+        void commit()
+        {
+            rocmCheck( mila_cdna4_token_bias_set( data(), 0, 0, static_cast<int>( vocab_ ), stage_ids_->data() + kStage, stage_values_->data() + kStage, static_cast<int>( staged_ ),
+                                                  context_->getStream() ) );
+        }
+        /// the table to the host (synchronizes)
+        void read( float* out )
+        {
+            rocmCheck( mila_cdna4_memcpy_d2h( out, data(), static_cast<size_t>( vocab_ ) * 4, context_->getStream() ) );
+            context_->synchronize();
+        }
+        size_t stateBytes() const { return table_->sizeInBytes() + stage_ids_->sizeInBytes() + stage_values_->sizeInBytes(); }
+        static size_t requiredBytes( dim_t vocab ) { return ( static_cast<size_t>( vocab ) + 4 * kStage ) * 4; }
+        static constexpr size_t kStage = 1024;
+    private:
+        ExecutionContext<DeviceType::Rocm>* context_;
+        dim_t vocab_;
+        size_t staged_{ 0 };
+        std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> table_, stage_values_;
+        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> stage_ids_;
+    };
+
     class RocmSamplingOp : public Operation<DeviceType::Rocm, TensorDataType::FP32>
     {
     public:

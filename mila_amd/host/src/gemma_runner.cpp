@@ -607,6 +607,34 @@ HOST_API int mila_gemma_read_token_table( void* h, int row, uint32_t* out )
         }, static_cast<Runner*>( h )->model );
     } );
 }
+/// The bias table of the step-level calls that follow (Gemma.h: setTokenBias): every value `fill`, then values[j] at ids[j]; n < 0 turns the bias off.  replace == 0
+/// updates entries of a table that is on and leaves the rest (fill is not read).
+HOST_API int mila_gemma_set_token_bias( void* h, float fill, const int32_t* ids, const float* values, int64_t n, int replace )
+{
+    return guarded( [&]
+    {
+        if ( n > 0 && ( !ids || !values ) ) throw std::invalid_argument( "set_token_bias: null ids / values" );
+        std::visit( [&]( auto& m )
+        {
+            if ( n < 0 ) m->clearTokenBias();
+            else if ( replace ) m->setTokenBias( fill, ids, values, static_cast<size_t>( n ) );
+            else m->updateTokenBias( ids, values, static_cast<size_t>( n ) );
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
+/// the bias table [vocab] to the host; *out_on = whether the bias is on
+HOST_API int mila_gemma_read_token_bias( void* h, float* out, int32_t* out_on )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( !m->tokenBias() ) throw std::logic_error( "read_token_bias: no bias table yet (set_token_bias first)" );
+            if ( out ) m->tokenBias()->read( out );
+            if ( out_on ) *out_on = m->tokenBiasOn() ? 1 : 0;
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
 HOST_API int mila_gemma_set_active( void* h, int b, int active, int32_t token )
 {
     return guarded( [&] { std::visit( [&]( auto& m ) { m->setRowActive( b, active != 0 ); if ( token >= 0 ) m->setRowToken( b, token ); }, static_cast<Runner*>( h )->model ); } );
@@ -1574,6 +1602,25 @@ static void apply_request_filters( decltype( GenerateParams::sampling )& sp, con
     sp.min_p = filters[ 0 ]; sp.repetition_penalty = filters[ 1 ]; sp.presence_penalty = filters[ 2 ]; sp.frequency_penalty = filters[ 3 ];
 }
 
+/// GenerateParams::logit_bias / banned_tokens / allowed_tokens / min_tokens of the *_biased entries below, by pointer (NULL: none of them)
+struct mila_token_bias_request
+{
+    const int32_t* bias_ids; const float* bias_values; int64_t n_bias;      ///< logit_bias: id -> value
+    const int32_t* banned; int64_t n_banned;
+    const int32_t* allowed; int64_t n_allowed;
+    int32_t min_tokens;
+};
+static void apply_request_bias( GenerateParams& gp, const mila_token_bias_request* b )
+{
+    if ( !b ) return;
+    if ( b->n_bias < 0 || b->n_banned < 0 || b->n_allowed < 0 || ( b->n_bias && ( !b->bias_ids || !b->bias_values ) ) || ( b->n_banned && !b->banned ) || ( b->n_allowed && !b->allowed ) )
+        throw std::invalid_argument( "token bias request: null list" );
+    for ( int64_t i = 0; i < b->n_bias; ++i ) gp.logit_bias.emplace_back( b->bias_ids[ i ], b->bias_values[ i ] );
+    gp.banned_tokens.assign( b->banned, b->banned + b->n_banned );
+    gp.allowed_tokens.assign( b->allowed, b->allowed + b->n_allowed );
+    gp.min_tokens = b->min_tokens;
+}
+
 struct LogprobSink
 {
     int top_n{ -1 };
@@ -1606,7 +1653,7 @@ struct LogprobSink
 
 static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                 float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
-                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters = nullptr );
+                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters = nullptr, const mila_token_bias_request* bias = nullptr );
 HOST_API int mila_gemma_model_generate( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                         float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
                                         int64_t cancel_after )
@@ -1633,9 +1680,18 @@ HOST_API int mila_gemma_model_generate_filtered( void* h, const int32_t* prompt,
     return model_generate_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_count, out_status, out_reused, cancel_after,
                                 LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters );
 }
+/// mila_gemma_model_generate_filtered (filters may be NULL: neutral) with the bias request (NULL: none)
+HOST_API int mila_gemma_model_generate_biased( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                                               float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
+                                               int64_t cancel_after, int top_n, float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_count,
+                                               const float* filters, const mila_token_bias_request* bias )
+{
+    return model_generate_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_count, out_status, out_reused, cancel_after,
+                                LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters, bias );
+}
 static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                 float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
-                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters )
+                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters, const mila_token_bias_request* bias )
 {
     return guarded( [&]
     {
@@ -1648,6 +1704,7 @@ static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         apply_request_filters( gp.sampling, filters );
+        apply_request_bias( gp, bias );
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
         if ( seed >= 0 ) m->seedSampler( static_cast<uint64_t>( seed ) );
         int64_t n = 0;
@@ -1665,7 +1722,8 @@ static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt
 /// out_stats (may be NULL): GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
 static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens, int64_t cap, int64_t* out_count,
-                               int32_t* out_status, int64_t* out_stats, LogprobSink sink = LogprobSink{}, int64_t* out_logprob_count = nullptr, const float* filters = nullptr )
+                               int32_t* out_status, int64_t* out_stats, LogprobSink sink = LogprobSink{}, int64_t* out_logprob_count = nullptr, const float* filters = nullptr,
+                               const mila_token_bias_request* bias = nullptr )
 {
     return guarded( [&]
     {
@@ -1679,6 +1737,7 @@ static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt,
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         apply_request_filters( gp.sampling, filters );
+        apply_request_bias( gp, bias );
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
         if ( hint && n_hint > 0 )
             gp.draft = [=]( std::span<const int32_t> history, int k )
@@ -1738,6 +1797,23 @@ HOST_API int mila_gemma_model_generate_spec_filtered( void* h, const int32_t* pr
                                out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters );
 }
 
+/// mila_gemma_model_generate_spec_filtered (filters may be NULL) with the bias request (NULL: none): a request with a bias takes the plain loop
+HOST_API int mila_gemma_model_generate_spec_biased( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                                    int top_k, float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens,
+                                                    int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_stats, int top_n, float* out_logprob, int32_t* out_ids,
+                                                    float* out_logprobs, int64_t* out_logprob_count, const float* filters, const mila_token_bias_request* bias )
+{
+    return generate_spec_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, hint, n_hint, speculative_sampling, out_tokens, cap, out_count,
+                               out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters, bias );
+}
+
+/// the vocabulary size of the model (what the ids of a bias request are checked against)
+HOST_API int64_t mila_gemma_model_vocab_size( void* h )
+{
+    auto* m = static_cast<RocmGemmaModel*>( h );
+    return m ? static_cast<int64_t>( m->vocabSize() ) : 0;
+}
+
 /// GemmaModel::lastSpeculation() as { steps, chain_steps, drafted, accepted }
 HOST_API int mila_gemma_model_speculation_stats( void* h, int64_t* out )
 {
@@ -1754,7 +1830,7 @@ HOST_API int mila_gemma_model_speculation_stats( void* h, int64_t* out )
 /// generator is seeded seed + b.  Row b's tokens go to out_tokens[ b * cap .. ] (at most cap), their number to out_counts[ b ], its GenerateStatus to out_status[ b ]
 static int model_generate_rows_impl( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
                                      int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status, LogprobSink sink,
-                                     int64_t* out_logprob_counts, const float* filters = nullptr );
+                                     int64_t* out_logprob_counts, const float* filters = nullptr, const mila_token_bias_request* bias = nullptr );
 HOST_API int mila_gemma_model_generate_rows( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
                                              int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status )
 {
@@ -1779,9 +1855,18 @@ HOST_API int mila_gemma_model_generate_rows_filtered( void* h, const int32_t* pr
     return model_generate_rows_impl( h, prompts, offsets, n_prompts, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_counts, out_status,
                                      LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_counts, filters );
 }
+/// mila_gemma_model_generate_rows_filtered (filters may be NULL) with the bias request (NULL: none), shared by the rows
+HOST_API int mila_gemma_model_generate_rows_biased( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop,
+                                                    float temperature, int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status,
+                                                    int top_n, float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts, const float* filters,
+                                                    const mila_token_bias_request* bias )
+{
+    return model_generate_rows_impl( h, prompts, offsets, n_prompts, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_counts, out_status,
+                                     LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_counts, filters, bias );
+}
 static int model_generate_rows_impl( void* h, const int32_t* prompts, const int64_t* offsets, int n_prompts, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
                                      int top_k, float top_p, uint64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status, LogprobSink sink,
-                                     int64_t* out_logprob_counts, const float* filters )
+                                     int64_t* out_logprob_counts, const float* filters, const mila_token_bias_request* bias )
 {
     return guarded( [&]
     {
@@ -1793,6 +1878,7 @@ static int model_generate_rows_impl( void* h, const int32_t* prompts, const int6
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         apply_request_filters( gp.sampling, filters );
+        apply_request_bias( gp, bias );
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
         std::vector<std::vector<int32_t>> ps;
         for ( int b = 0; b < n_prompts; ++b ) ps.emplace_back( prompts + offsets[ b ], prompts + offsets[ b + 1 ] );
