@@ -448,7 +448,10 @@ MILA_API int mila_cdna4_sample_argmax_bf16(const uint16_t* logits, int32_t* toke
 /* Stochastic sampler: x = (softcap > 0 ? softcap * tanh(l / softcap) : l) / temperature;
  * top-k (0 = off) keeps the values strictly above the (k+1)-th largest; top-p (>= 1 = off) keeps the smallest set of
  * highest-probability survivors whose mass exceeds top_p * total; token = first index, in token order, with
- * probability > 0 and cumulative >= r * total (vocab - 1 otherwise); r in [0, 1] is drawn by the caller.
+ * probability > 0 and cumulative >= r * total; r in [0, 1] is drawn by the caller.  Where rounding leaves the running
+ * sum short of r * total (next to r = 1) the token is the LAST index with probability > 0, so a token that top-k or
+ * top-p removed is never returned; vocab - 1 only when no token has mass (every value tied under top-k).  -0.0 and
+ * +0.0 are one value: a tie group enters or leaves top-k as a whole.
  * replaces Sampling/Kernels/Sampling.cuh: cuda_sample_stochastic_fp32 / _bf16 (Sampling.cu:655-714; semantics of the
  * single-block kernel :760-905).  temperature <= 0 is the greedy sampler above.  Deterministic for fixed arguments. */
 MILA_API size_t mila_cdna4_sample_stochastic_scratch_bytes(int vocab);
@@ -560,7 +563,7 @@ MILA_API int mila_cdna4_sample_argmax_final_advance(int32_t* token_out, const vo
 
 /* The stochastic sampler as a pipeline that can sit in a captured decode step ("radix"): the semantics of sample_stochastic_* above, in the same order (softcap, then
  * temperature; top-k survivors strictly above the (k+1)-th largest; the smallest nucleus whose mass exceeds top_p * total, a tie entering whole; the first index with
- * e > 0 and cumulative >= r * total, else vocab - 1), from at most 9 launches over fixed buffers instead of 21.  replaces Sampling/Kernels/Sampling.cuh:
+ * e > 0 and cumulative >= r * total, else the last index with e > 0, else vocab - 1), from at most 9 launches over fixed buffers instead of 21.  replaces Sampling/Kernels/Sampling.cuh:
  * cuda_sample_stochastic_fp32 / _bf16 (Sampling.cu:655-714; semantics of the single-block kernel :760-905).  Both thresholds come from digit selection over the 32-bit
  * key (11 + 11 + 10 bits): integer counts for top-k (the threshold of sample_stochastic_* exactly), 64-bit fixed-point masses (scale 2^40) for top-p, summed with integer
  * atomics, so a call is deterministic run to run.  The nucleus may differ from sample_stochastic_*'s where top_p * total lies within float rounding of a boundary, and
@@ -864,8 +867,8 @@ MILA_API int mila_cdna4_sample_argmax_filtered_rows_advance_fp32(const float* lo
  * The bias comes before the penalties (vLLM's order: the repetition penalty's sign test sees the biased value) and after the softcap (the capped logits are the
  * model's logits).  -inf stays -inf through every later step: x1 is a product with rep or 1 / rep > 0, x2 and x3 subtract finite values, the temperature is positive.
  * A TOKEN WHOSE BIAS IS -inf IS NEVER RETURNED, at any draw in [0, 1] and under any top-k / top-p / min-p: its e = expf(-inf - max) is 0, the walk of the inverse CDF
- * visits only e > 0, and where the running sum never reaches r * total (the two are added in different orders, so next to r = 1 they can differ) a biased call returns
- * the LAST entry with nonzero mass, not vocab - 1 as the unbiased samplers do.  Caller's contract: at least one token of a row has a finite bias.
+ * visits only e > 0, and where the running sum never reaches r * total (the two are added in different orders, so next to r = 1 they can differ) every stochastic
+ * entry, biased or not, returns the LAST entry with nonzero mass, never vocab - 1 for its own sake.  Caller's contract: at least one token of a row has a finite bias.
  * GREEDY.  sample_argmax_biased_* take argmax(x3), ties to the lower id, in the two launches of sample_argmax_filtered_*; the table may be NULL (a bias without
  * penalties).
  * The samplers never write `logits`: log-probabilities (token_logprobs_*, the scoring entries) stay those of the capped, UNBIASED logits.
@@ -873,8 +876,8 @@ MILA_API int mila_cdna4_sample_argmax_filtered_rows_advance_fp32(const float* lo
  * Each sample_*_biased_* entry is the sample_*_filtered_* entry of the same name plus `bias, bias_stride`, and the filtered entries are calls of them.  bias: row 0's
  * table; NULL = exactly the filtered entry, including its NULL-table behaviour, launching the kernels it launched.  bias_stride: floats between the tables of two rows;
  * 0 = one table shared by all rows; with more than one row a stride from 1 to vocab - 1 is refused.  A biased call launches exactly what sample_radix_plan_describe
- * reports for the unfiltered call: the bias rides in the scale launch (four instantiations: none, table, bias, table + bias), and the tail is the instantiation with the
- * fallback above.  Scratch: as for the mirrored entry.
+ * reports for the unfiltered call: the bias rides in the scale launch (four instantiations: none, table, bias, table + bias), and the tail is the
+ * unbiased call's.  Scratch: as for the mirrored entry.
  * Refused before any device work, beside what the mirrored entry refuses (MILA_E_INVALID_ARGUMENT): a NaN or +inf fill value; n < 0; a null table, id or value pointer with
  * n > 0; the stride rule above. */
 MILA_API size_t mila_cdna4_token_bias_bytes(int vocab);

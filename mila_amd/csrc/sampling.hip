@@ -318,10 +318,28 @@ struct SampParams
     float softcap, temperature, top_p, r;
 };
 
-__device__ __forceinline__ uint32_t ordered_key(float x)      // monotone: x < y  <=>  key(x) < key(y)
+// the order of the keys is the order of the floats with ONE exception: key(-0.0f) = 0x7FFFFFFF < key(+0.0f) = 0x80000000 while -0.0f == +0.0f.  For every other pair of
+// non-NaN values x < y <=> key(x) < key(y) and x == y <=> key(x) == key(y).  The samplers compare keys where the stated semantics compare floats, so the scale launches
+// never store -0.0f (canonical_zero below): over what they store the two orders are one.
+__device__ __forceinline__ uint32_t ordered_key(float x)
 {
     const uint32_t b = __float_as_uint(x);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// x with -0.0f replaced by +0.0f and every other value (NaN, infinities, denormals) as it is: one IEEE addition, which the compiler may not fold (-0 + +0 = +0)
+__device__ __forceinline__ float canonical_zero(float x) { return __fadd_rn(x, 0.0f); }
+
+// the LAST index whose masked probability w[i] is nonzero, -1 when there is none: one wave scans the whole vector (`lane` its lane), every lane returns the index.
+// The inverse-CDF walks take it when their running sum never reached r * total.
+__device__ __forceinline__ int last_with_mass(const float* w, int vocab, int lane)
+{
+    int last = -1;
+    for (int i = lane; i < vocab; i += 64)
+        if (w[i] > 0.0f) last = i;      // ascending: the lane's largest
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
+    return last;
 }
 
 // fixed-order sum of n <= 256 per-workgroup partials by one wave: lane l adds entries 4l .. 4l+3, then the butterfly
@@ -375,7 +393,7 @@ __global__ __launch_bounds__(256) void samp_scale_kernel(const T* __restrict__ l
     for (int i = blockIdx.x * 256 + threadIdx.x; i < p.vocab; i += gridDim.x * 256)
     {
         float x = soft_cap(to_f32(logits[i]), p.softcap);
-        x = x / p.temperature;
+        x = canonical_zero(x / p.temperature);
         p.w[i] = x;
         mx = fmaxf(mx, x);
     }
@@ -498,30 +516,39 @@ __global__ __launch_bounds__(256) void samp_mask_kernel(const SampParams p, int 
 }
 
 // inverse CDF in token-index order: chunk sums locate the chunk, one lane walks it (and, if rounding left the target just
-// beyond it, the following ones) with the reference's guard e > 0 && cumulative >= target; vocab - 1 otherwise
+// beyond it, the following ones) with the reference's guard e > 0 && cumulative >= target.  Where the running sum never reaches the target -- the total is the chunk
+// sums added in chunk order, the walk adds entry by entry, so next to r = 1 the two can differ in the last bits -- the wave scans for the LAST entry with mass, which
+// is where an exact walk ends at r = 1; vocab - 1 only when nothing has mass (what the reference's walk leaves then)
 __global__ __launch_bounds__(64) void samp_cdf_kernel(const SampParams p, int nchunks, int chunk)
 {
-    if (threadIdx.x != 0) return;
-    float total = 0.0f;
-    for (int b = 0; b < nchunks; ++b) total += p.red[b];
-    const float target = p.r * total;
-    float before = 0.0f;
-    int b = 0;
-    while (b < nchunks - 1 && before + p.red[b] < target) { before += p.red[b]; ++b; }
     int result = p.vocab - 1;
-    float cum = before;
     bool found = false;
-    for (; b < nchunks && !found; ++b)
+    if (threadIdx.x == 0)
     {
-        const int i1 = min(p.vocab, (b + 1) * chunk);
-        for (int i = b * chunk; i < i1; ++i)
+        float total = 0.0f;
+        for (int b = 0; b < nchunks; ++b) total += p.red[b];
+        const float target = p.r * total;
+        float before = 0.0f;
+        int b = 0;
+        while (b < nchunks - 1 && before + p.red[b] < target) { before += p.red[b]; ++b; }
+        float cum = before;
+        for (; b < nchunks && !found; ++b)
         {
-            const float e = p.w[i];
-            cum += e;
-            if (e > 0.0f && cum >= target) { result = i; found = true; break; }
+            const int i1 = min(p.vocab, (b + 1) * chunk);
+            for (int i = b * chunk; i < i1; ++i)
+            {
+                const float e = p.w[i];
+                cum += e;
+                if (e > 0.0f && cum >= target) { result = i; found = true; break; }
+            }
         }
     }
-    p.token_out[0] = result;
+    if (!__shfl((int)found, 0, 64))
+    {
+        const int last = last_with_mass(p.w, p.vocab, threadIdx.x);
+        if (last >= 0) result = last;
+    }
+    if (threadIdx.x == 0) p.token_out[0] = result;
 }
 
 constexpr size_t kSampHeaderFloats = 64;
@@ -700,7 +727,7 @@ __device__ __forceinline__ void radix_scale_body(const T* __restrict__ logits, c
         float x = soft_cap(to_f32(logits[i]), p.softcap);
         if (BIAS) x = __fadd_rn(x, bias[i]);
         if (FILT) x = penalized_logit(x, table[i], *f);
-        x = x / p.temperature;
+        x = canonical_zero(x / p.temperature);
         p.w[i] = x;
         mx = fmaxf(mx, x);
     }
@@ -870,9 +897,9 @@ __device__ __forceinline__ float lane_value(float v, int l) { return __int_as_fl
 // inverse CDF in token-index order: samp_cdf_kernel's sums and walk, value for value (the same additions in the same order), by one wave that holds the chunk sums in
 // registers and steps over the zeros of the walk: adding 0 leaves the cumulative sum as it is, and after the truncations nearly every entry is 0.
 // radix_cdf_walk is the walk itself, by ONE wave (`lane` its lane) at the draw r; every lane returns the token.
-// LAST (the instantiations of a call with a bias table): when the running sum never reaches r * total -- the two are added in different orders, so next to r = 1 they
-// can differ -- the token is the LAST entry with nonzero mass, found by a scan of the whole vector, instead of vocab - 1, which a -inf bias may forbid.
-template <bool LAST = false>
+// When the running sum never reaches r * total -- the two are added in different orders, so next to r = 1 they can differ -- the token is the LAST entry with nonzero
+// mass, found by a scan of the whole vector (taken only then): where an exact walk ends at r = 1, and never a token that top-k / top-p / min-p or a -inf bias removed.
+// vocab - 1 only when nothing has mass.
 __device__ __forceinline__ int radix_cdf_walk(const RadixParams& p, float r, int nchunks, int chunk, int lane)
 {
     const float* cs = p.red + kSampBlocks;
@@ -920,13 +947,9 @@ __device__ __forceinline__ int radix_cdf_walk(const RadixParams& p, float r, int
             }
         }
     }
-    if (LAST && !found)
+    if (!found)
     {
-        int last = -1;
-        for (int i = lane; i < p.vocab; i += 64)
-            if (p.w[i] > 0.0f) last = i;      // ascending: the lane's largest
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
+        const int last = last_with_mass(p.w, p.vocab, lane);
         if (last >= 0) result = last;
     }
     return result;
@@ -990,8 +1013,7 @@ __global__ __launch_bounds__(256) void radix_mask_kernel(const RadixRows r, int 
 // The one-row tail, one wave over row 0.  ADVANCE: the stochastic twin of argmax_final_advance_kernel -- the draw is slot (*seq_dev + 1) % draws_size of a host-written
 // ring (system-scope load: the host rewrites the slots between replays), and the tail bumps the position, stores the sequence number and (ring != NULL) publishes
 // seq << 32 | token; else the draw is p.r.  TABLE: lane 0 counts the sample in the table before it stores / publishes the token.
-// LAST: radix_cdf_walk<true>, for a call with a bias table.
-template <bool ADVANCE, bool TABLE, bool LAST = false>
+template <bool ADVANCE, bool TABLE>
 __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixRows rr, int nchunks, int chunk)
 {
     const RadixParams& p = rr.p;
@@ -1004,7 +1026,7 @@ __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixRows rr, int n
         const uint32_t* slot = reinterpret_cast<const uint32_t*>(p.draws) + (seq % (unsigned long long)p.draws_size);
         r = __uint_as_float(__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
     }
-    const int result = radix_cdf_walk<LAST>(p, r, nchunks, chunk, lane);
+    const int result = radix_cdf_walk(p, r, nchunks, chunk, lane);
     if (lane == 0)
     {
         if (TABLE) table_count(rr.f.table, result);
@@ -1019,9 +1041,9 @@ __global__ __launch_bounds__(64) void radix_cdf_kernel(const RadixRows rr, int n
 //   kRowsAdvance: where active[b] != 0, token_out[b] = s_b and pos[b] += 1; an inactive row's words are not touched.
 //   kRowsChain:   chain_accept with the samples (token_out is tok[], pos the ONE position word).
 // TABLE (kRowsTokens / kRowsAdvance): the lane counts row b's sample in row b's table before it stores the token -- in kRowsAdvance for the active rows only.  The chain
-// tail takes no table: row t would need the table plus the drafts 1 .. t.  LAST: radix_cdf_walk<true>, for a call with a bias table (never the chain tail).
+// tail takes no table: row t would need the table plus the drafts 1 .. t.
 enum { kRowsTokens = 0, kRowsAdvance = 1, kRowsChain = 2 };
-template <int MODE, bool TABLE, bool LAST = false>
+template <int MODE, bool TABLE>
 __global__ __launch_bounds__(256) void radix_rows_tail_kernel(const RadixRows r, int rows, int nchunks, int chunk, const int32_t* __restrict__ active, int32_t* __restrict__ result)
 {
     static_assert(!TABLE || MODE == kRowsTokens || MODE == kRowsAdvance, "the chain tail takes no table");
@@ -1031,7 +1053,7 @@ __global__ __launch_bounds__(256) void radix_rows_tail_kernel(const RadixRows r,
     {
         const RadixParams p = radix_row(r, t);
         const float draw = __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t*>(r.p.draws) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-        const int s = radix_cdf_walk<LAST>(p, draw, nchunks, chunk, lane);
+        const int s = radix_cdf_walk(p, draw, nchunks, chunk, lane);
         if (lane == 0) ss[t] = s;
     }
     __syncthreads();
@@ -1060,7 +1082,7 @@ struct RadixPlan
     size_t scratch_need;
     int scale_filtered;      // the scale launch is the instantiation that reads the token table (a table was given)
     int mask_filtered;       // the mask launch is the instantiation with the min-p test (min_p > 0)
-    int scale_biased;        // the scale launch reads a bias table, and the tail is the instantiation whose fallback is the last entry with mass
+    int scale_biased;        // the scale launch is the instantiation that reads a bias table
 };
 constexpr size_t kRadixHistBytes = (size_t)kRadixPasses * kRadixBins * (sizeof(uint32_t) + sizeof(unsigned long long));
 // with_table / min_p / with_bias choose INSTANTIATIONS of launches the plan already has: a filtered or biased call launches what the unfiltered call launches
@@ -1201,17 +1223,13 @@ static int run_radix(const RadixCall<T>& c, void* scratch, size_t scratch_bytes,
     for (int pass = 1; pass < d.p_passes; ++pass) hipLaunchKernelGGL(radix_ppass_kernel, dim3(d.blocks, R), wg, 0, s, r, pass);
     if (d.mask_filtered) hipLaunchKernelGGL(radix_mask_kernel<true>, dim3(d.nchunks, R), wg, 0, s, r, use_p, d.chunk, flt->min_p);
     else hipLaunchKernelGGL(radix_mask_kernel<false>, dim3(d.nchunks, R), wg, 0, s, r, use_p, d.chunk, 0.0f);
-    // the tail: <mode, table, last> picks the instantiation
-    const bool tab = d.scale_filtered != 0, last = d.scale_biased != 0;
+    // the tail: <mode, table> picks the instantiation
+    const bool tab = d.scale_filtered != 0;
     auto cdf = [&](auto k) { hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, s, r, d.nchunks, d.chunk); };
     auto tail = [&](auto k) { hipLaunchKernelGGL(k, dim3(1), wg, 0, s, r, c.rows, d.nchunks, d.chunk, c.active, c.result); };
-    if (one && adv && last) { if (tab) cdf(radix_cdf_kernel<true, true, true>); else cdf(radix_cdf_kernel<true, false, true>); }
-    else if (one && adv) { if (tab) cdf(radix_cdf_kernel<true, true>); else cdf(radix_cdf_kernel<true, false>); }
-    else if (one && last) { if (tab) cdf(radix_cdf_kernel<false, true, true>); else cdf(radix_cdf_kernel<false, false, true>); }
+    if (one && adv) { if (tab) cdf(radix_cdf_kernel<true, true>); else cdf(radix_cdf_kernel<true, false>); }
     else if (one) { if (tab) cdf(radix_cdf_kernel<false, true>); else cdf(radix_cdf_kernel<false, false>); }
-    else if (c.mode == kRowsTokens && last) { if (tab) tail(radix_rows_tail_kernel<kRowsTokens, true, true>); else tail(radix_rows_tail_kernel<kRowsTokens, false, true>); }
     else if (c.mode == kRowsTokens) { if (tab) tail(radix_rows_tail_kernel<kRowsTokens, true>); else tail(radix_rows_tail_kernel<kRowsTokens, false>); }
-    else if (c.mode == kRowsAdvance && last) { if (tab) tail(radix_rows_tail_kernel<kRowsAdvance, true, true>); else tail(radix_rows_tail_kernel<kRowsAdvance, false, true>); }
     else if (c.mode == kRowsAdvance) { if (tab) tail(radix_rows_tail_kernel<kRowsAdvance, true>); else tail(radix_rows_tail_kernel<kRowsAdvance, false>); }
     else tail(radix_rows_tail_kernel<kRowsChain, false>);
     return check_hip(hipGetLastError(), who);
