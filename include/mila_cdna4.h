@@ -909,6 +909,36 @@ MILA_API int mila_cdna4_sample_argmax_biased_rows_advance_fp32(const float* logi
                                                                size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* positions_dev,
                                                                const int32_t* active_dev, mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Token automaton (ABI 4, additive; csrc/sampling.hip): grammar-constrained decoding -- the set of tokens a request may emit changes with every token it emits.  The
+ * constraint is a deterministic automaton over token ids, brought by the caller (tokenizers and the regex / JSON-schema compilers that produce one stay outside this
+ * library): what vLLM, TGI and llama.cpp reach through a per-step logits mask built on the host.  Here the state and the mask live on the device, so a step that samples
+ * token n + 1 before the host has seen token n stays closed.  The samplers are untouched: they already honour a dense fp32 table of "finite or -inf" exactly (logit
+ * bias, above); these entries maintain such a table, `eff`, and the sample_*_biased_* entries read it in the place of the bias table.  The reference re-parses what the
+ * model emitted (Gemma.Protocol.ixx) and has no kernel for any of this.  Mila/TokenAutomaton.h (host only) holds, checks and compresses an automaton.
+ *
+ * THE IMAGE.  token_automaton_bytes(vocab, S, C) bytes on the device: class_of[vocab] uint16 (token id -> class, < C), then next[S * C] uint16 (state x class -> next
+ * state, < S, or 0xFFFF = FORBIDDEN: the token may not be emitted in that state).  1 <= S, C <= 65535 and S * C * 2 bytes <= 256 MiB (bytes returns 0 otherwise).
+ * THE STATE.  One int32 word per row (state_dev[rows]) and, for step, one uint32 ticket word per row that is 0 between launches (ticket_dev[rows]).
+ *
+ * compose: for row b with s = state_dev[b]:   eff[b * eff_stride + i] = next[s * C + class_of[i]] != FORBIDDEN ? base[b * base_stride + i] : -inf   for every i.
+ *     base == NULL: 0.0f in the place of base; base_stride == 0: one base table shared by the rows.  The base value passes through bit for bit.  The state stays.
+ * step: for every row b whose active_dev[b] != 0 (active_dev == NULL: every row): s' = next[s * C + class_of[token_dev[b]]]; FORBIDDEN (only a token the mask forbade)
+ *     or a token outside [0, vocab) leaves s' = s; then eff[b] is composed for s' and state_dev[b] = s'.  An inactive row keeps its state and its table bytes.
+ * Both are ONE launch for all rows (the row in blockIdx.y, as the radix stages), in stream order: step goes behind the sampler tail that wrote token_dev, the next
+ * step's sampler reads eff.  Every workgroup of a step launch reads the state word and one stores it; a ticket (one agent-scope atomic add per workgroup, taken after
+ * the reads) makes the workgroup that draws the last one the writer, so no workgroup can read the advanced state -- no grid barrier, no second launch.  A state word
+ * outside [0, S) is read as 0.  The walk uses 16-byte accesses where eff and base are 16-byte aligned with strides that are multiples of 4 and class_of is 8-byte
+ * aligned, scalar ones otherwise.
+ * Refused before any device work (MILA_E_INVALID_ARGUMENT): a null eff, class_of, next or state_dev (step: token_dev, ticket_dev); rows outside 1 .. 4; vocab <= 0, S
+ * or C outside the limits above; with more than one row an eff_stride below vocab; a base_stride from 1 to vocab - 1. */
+MILA_API size_t mila_cdna4_token_automaton_bytes(int vocab, int S, int C);
+MILA_API int mila_cdna4_token_automaton_compose(float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next,
+                                                int S, int C, int32_t* state_dev, int rows, int vocab, mila_stream_t stream);
+MILA_API int mila_cdna4_token_automaton_step(float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next, int S,
+                                             int C, int32_t* state_dev, const int32_t* token_dev, const int32_t* active_dev, uint32_t* ticket_dev, int rows, int vocab,
+                                             mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

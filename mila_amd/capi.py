@@ -131,6 +131,11 @@ def load():
     main.mila_cdna4_sample_argmax_biased_fp32.argtypes = [p, p, i, f, p, p, p, z, p, z, p]
     main.mila_cdna4_sample_argmax_biased_advance_fp32.argtypes = [p, p, i, f, p, p, p, z, p, z, p, p, p, i, p]
     main.mila_cdna4_sample_argmax_biased_rows_advance_fp32.argtypes = [p, z, p, i, i, f, p, p, z, p, z, p, z, p, p, p]
+    # token automaton (csrc/sampling.hip: the effective table of a grammar-constrained row and the state step behind the sampler tail)
+    main.mila_cdna4_token_automaton_bytes.argtypes = [i, i, i]                                                    # vocab S C
+    main.mila_cdna4_token_automaton_bytes.restype = z
+    main.mila_cdna4_token_automaton_compose.argtypes = [p, z, p, z, p, p, i, i, p, i, i, p]                       # eff eff_stride base base_stride | class_of next S C | state_dev | rows vocab
+    main.mila_cdna4_token_automaton_step.argtypes = [p, z, p, z, p, p, i, i, p, p, p, p, i, i, p]                 # ... state_dev token_dev active_dev ticket_dev | rows vocab
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -500,6 +505,35 @@ def sample_argmax_biased_rows_advance(logits, token_out, softcap, filters, table
          bias, _bias_stride(bias, bias_stride), scratch, _nbytes(scratch), positions_dev, active_dev)
 
 
+# ---- token automaton: class_of [vocab] and next [S, C] are 16-bit tensors on the device, state / token / active int32 [rows], ticket int32 [rows] (zero between
+# launches); eff float32 [rows, vocab] (or [vocab] for one row); base None (zeros), [vocab] (shared: base_stride 0) or [rows, vocab]
+TOKEN_AUTOMATON_FORBIDDEN = 0xFFFF
+
+
+def token_automaton_bytes(vocab, num_states, num_classes):
+    return int(load().mila_cdna4_token_automaton_bytes(int(vocab), int(num_states), int(num_classes)))
+
+
+def _automaton_head(eff, base, class_of, next_table):
+    assert class_of.element_size() == 2 and next_table.element_size() == 2 and next_table.dim() == 2
+    rows, V = (1, int(eff.shape[0])) if eff.dim() == 1 else (int(eff.shape[0]), int(eff.shape[1]))
+    assert int(class_of.numel()) == V
+    base_stride = 0 if base is None or base.dim() == 1 else int(base.shape[-1])
+    return rows, V, C.c_size_t(V), C.c_size_t(base_stride), int(next_table.shape[0]), int(next_table.shape[1])
+
+
+def token_automaton_compose(eff, base, class_of, next_table, state_dev):
+    """eff[b][i] = base[b][i] where next[state[b], class_of[i]] is not FORBIDDEN, else -inf; the state stays"""
+    rows, V, es, bs, S, Cn = _automaton_head(eff, base, class_of, next_table)
+    call("token_automaton_compose", eff, es, base, bs, class_of, next_table, S, Cn, state_dev, rows, V)
+
+
+def token_automaton_step(eff, base, class_of, next_table, state_dev, token_dev, ticket_dev, active_dev=None):
+    """every active row's state advanced by token_dev[b] (a forbidden token leaves it), eff[b] composed for the new state: one launch"""
+    rows, V, es, bs, S, Cn = _automaton_head(eff, base, class_of, next_table)
+    call("token_automaton_step", eff, es, base, bs, class_of, next_table, S, Cn, state_dev, token_dev, active_dev, ticket_dev, rows, V)
+
+
 TOKEN_LOGPROBS_MAX_TOP = 20
 
 
@@ -623,6 +657,7 @@ EXPORTED = [
     "token_bias_bytes", "token_bias_fill", "token_bias_set",
     "sample_radix_biased_fp32", "sample_radix_biased_advance_fp32", "sample_radix_biased_rows_fp32", "sample_radix_biased_rows_advance_fp32",
     "sample_argmax_biased_fp32", "sample_argmax_biased_advance_fp32", "sample_argmax_biased_rows_advance_fp32",
+    "token_automaton_bytes", "token_automaton_compose", "token_automaton_step",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

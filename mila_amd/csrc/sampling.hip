@@ -210,6 +210,78 @@ __global__ __launch_bounds__(256) void token_bias_set_kernel(float* __restrict__
     }
 }
 
+// ---- the token automaton (mila_cdna4.h: token automaton): the effective table of a row is its base table with -inf wherever the row's state forbids the token,
+// eff[i] = next[s * C + class_of[i]] != FORBIDDEN ? base[i] : -inf.  One kernel, two forms.  COMPOSE writes the table of the state the word holds.  STEP first advances
+// the state by the token the sampler tail just wrote, s' = next[s * C + class_of[token]] (FORBIDDEN: s stays), then writes the table of s' and leaves s' in the word.
+// THE STATE WORD is read by every workgroup of the launch and stored by one of them, and a workgroup that starts late must not read the advanced value.  So lane 0 of
+// every workgroup reads the word and the token, and only then takes a ticket with an agent-scope atomic add whose release ordering keeps the two loads (and the two
+// dependent loads of s') in front of it: the ticket that completes the row's count, gridDim.x - 1, is drawn after every workgroup of the row has read, and its holder
+// stores s' and zeroes the ticket for the next launch, which the kernel boundary orders behind both stores.  Every workgroup computes the same s' from the same words.
+// The walk: four tokens per lane where the pointers allow (VEC: one 8-byte load of class_of, one 16-byte load of base, one 16-byte store), a scalar loop for the
+// vocab % 4 tail or for everything when a pointer or stride is not aligned; the state's row of `next` (at most 128 KB) is gathered through the cache.
+constexpr uint16_t kAutomatonForbidden = 0xFFFFu;
+
+template <bool STEP>
+__global__ __launch_bounds__(256) void token_automaton_kernel(float* __restrict__ eff, size_t eff_stride, const float* __restrict__ base, size_t base_stride,
+                                                              const uint16_t* __restrict__ class_of, const uint16_t* __restrict__ next, int S, int C, int32_t* state_dev,
+                                                              const int32_t* __restrict__ token_dev, const int32_t* __restrict__ active_dev, uint32_t* ticket_dev, int vocab,
+                                                              int vec)
+{
+    const int b = blockIdx.y;
+    if (STEP && active_dev && active_dev[b] == 0) return;      // (uniform over the row's workgroups: none of them takes a ticket)
+    __shared__ int s_state;
+    if (threadIdx.x == 0)
+    {
+        int s = __hip_atomic_load(state_dev + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)s >= (unsigned)S) s = 0;      // (never with a state the host set: keeps every read of `next` inside the image)
+        if (STEP)
+        {
+            const int t = token_dev[b];
+            int s2 = s;
+            if (t >= 0 && t < vocab)
+            {
+                const unsigned c = class_of[t];
+                const uint16_t n = c < (unsigned)C ? next[(size_t)s * C + c] : kAutomatonForbidden;
+                if (n != kAutomatonForbidden && n < S) s2 = n;
+            }
+            const unsigned ticket = __hip_atomic_fetch_add(ticket_dev + b, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            if (ticket == gridDim.x - 1)
+            {
+                __hip_atomic_store(state_dev + b, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(ticket_dev + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            s = s2;
+        }
+        s_state = s;
+    }
+    __syncthreads();
+    const uint16_t* __restrict__ row = next + (size_t)s_state * C;
+    float* __restrict__ e = eff + (size_t)b * eff_stride;
+    const float* __restrict__ x = base ? base + (size_t)b * base_stride : nullptr;
+    // (a class outside [0, C) -- never from a validated image -- reads entry 0 and is forbidden: no branch in front of the gathers, so the four of a lane fly together)
+    auto entry = [&](unsigned c) { return row[c < (unsigned)C ? c : 0u]; };
+    auto keep = [&](unsigned c, uint16_t n) { return c < (unsigned)C && n != kAutomatonForbidden; };
+    const int nvec = vec ? (vocab >> 2) : 0;
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < nvec; v += gridDim.x * 256)
+    {
+        const uint2 cw = reinterpret_cast<const uint2*>(class_of)[v];
+        float4 o = x ? reinterpret_cast<const float4*>(x)[v] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const unsigned c0 = cw.x & 0xFFFFu, c1 = cw.x >> 16, c2 = cw.y & 0xFFFFu, c3 = cw.y >> 16;
+        const uint16_t n0 = entry(c0), n1 = entry(c1), n2 = entry(c2), n3 = entry(c3);
+        o.x = keep(c0, n0) ? o.x : -INFINITY;
+        o.y = keep(c1, n1) ? o.y : -INFINITY;
+        o.z = keep(c2, n2) ? o.z : -INFINITY;
+        o.w = keep(c3, n3) ? o.w : -INFINITY;
+        reinterpret_cast<float4*>(e)[v] = o;
+    }
+    for (int i = nvec * 4 + blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256)
+    {
+        const unsigned c = class_of[i];
+        const float xi = x ? x[i] : 0.0f;
+        e[i] = keep(c, entry(c)) ? xi : -INFINITY;
+    }
+}
+
 // The acceptance rule of a chain (speculative verification), by one lane: rows 0 .. T - 1 are consecutive positions of ONE sequence, row t fed with tok[t] (tok[0] the
 // last sampled token, tok[1 ..] the drafts), and s[t] is row t's sample.  The longest correct draft prefix is accepted: n_acc = the first t in [0, T - 1) with
 // s[t] != tok[t + 1], else T - 1.  result = {n_acc + 1, s[0] .. s[n_acc]} (the other words are left alone), tok[0] = s[n_acc] (the next step's input), *pos += n_acc + 1.
@@ -1478,6 +1550,53 @@ int mila_cdna4_token_bias_set(float* bias, size_t bias_stride, int row, int voca
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(token_bias_set_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), bias + (size_t)row * bias_stride, vocab, ids_dev, values_dev, n);
     MILA_LAUNCH_CHECK("token_bias_set");
+}
+
+// ---- the token automaton (mila_cdna4.h: token automaton).  One launch each, the row in blockIdx.y; at most 256 workgroups per row walk the table.
+static bool automaton_shape_ok(int vocab, int S, int C)
+{
+    return vocab > 0 && S >= 1 && S <= 65535 && C >= 1 && C <= 65535 && (size_t)S * (size_t)C * sizeof(uint16_t) <= ((size_t)256 << 20);
+}
+
+size_t mila_cdna4_token_automaton_bytes(int vocab, int S, int C)
+{
+    return automaton_shape_ok(vocab, S, C) ? ((size_t)vocab + (size_t)S * (size_t)C) * sizeof(uint16_t) : 0;
+}
+
+static int launch_token_automaton(bool step, float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next, int S,
+                                  int C, int32_t* state_dev, const int32_t* token_dev, const int32_t* active_dev, uint32_t* ticket_dev, int rows, int vocab,
+                                  mila_stream_t stream, const char* who)
+{
+    MILA_REQUIRE(eff && class_of && next && state_dev && (!step || (token_dev && ticket_dev)), "token_automaton: null pointer");
+    MILA_REQUIRE(rows >= 1 && rows <= 4, "token_automaton: rows must be 1 .. 4");
+    MILA_REQUIRE(automaton_shape_ok(vocab, S, C), "token_automaton: need vocab > 0, 1 <= S, C <= 65535 and S * C * 2 bytes <= 256 MiB");
+    MILA_REQUIRE(rows == 1 || eff_stride >= (size_t)vocab, "token_automaton: eff_stride must be at least vocab");
+    MILA_REQUIRE(!base || base_stride == 0 || base_stride >= (size_t)vocab, "token_automaton: base_stride must be 0 (shared) or at least vocab");
+    auto aligned = [](const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    const int vec = aligned(eff, 16) && eff_stride % 4 == 0 && aligned(class_of, 8) && (!base || (aligned(base, 16) && base_stride % 4 == 0));
+    int blocks = (vocab + 1023) / 1024;
+    if (blocks > 256) blocks = 256;
+    if (step)
+        hipLaunchKernelGGL(token_automaton_kernel<true>, dim3(blocks, rows), dim3(256), 0, as_stream(stream), eff, eff_stride, base, base_stride, class_of, next, S, C, state_dev,
+                           token_dev, active_dev, ticket_dev, vocab, vec);
+    else
+        hipLaunchKernelGGL(token_automaton_kernel<false>, dim3(blocks, rows), dim3(256), 0, as_stream(stream), eff, eff_stride, base, base_stride, class_of, next, S, C, state_dev,
+                           nullptr, nullptr, nullptr, vocab, vec);
+    MILA_LAUNCH_CHECK(who);
+}
+
+int mila_cdna4_token_automaton_compose(float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next, int S, int C,
+                                       int32_t* state_dev, int rows, int vocab, mila_stream_t stream)
+{
+    return launch_token_automaton(false, eff, eff_stride, base, base_stride, class_of, next, S, C, state_dev, nullptr, nullptr, nullptr, rows, vocab, stream,
+                                  "token_automaton_compose");
+}
+
+int mila_cdna4_token_automaton_step(float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next, int S, int C,
+                                    int32_t* state_dev, const int32_t* token_dev, const int32_t* active_dev, uint32_t* ticket_dev, int rows, int vocab, mila_stream_t stream)
+{
+    return launch_token_automaton(true, eff, eff_stride, base, base_stride, class_of, next, S, C, state_dev, token_dev, active_dev, ticket_dev, rows, vocab, stream,
+                                  "token_automaton_step");
 }
 
 int mila_cdna4_sample_radix_biased_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,

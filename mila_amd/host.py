@@ -153,6 +153,91 @@ def _bias_request(logit_bias=None, banned_tokens=(), allowed_tokens=(), min_toke
     return TokenBiasRequestC(ptr[0], ptr[1], arrays[0].size, ptr[2], arrays[2].size, ptr[3], arrays[3].size, min_tokens), arrays
 
 
+class TokenAutomatonRequestC(C.Structure):
+    """mila_token_automaton_request (host/src/gemma_runner.cpp): GenerateParams::automaton by pointer"""
+    _fields_ = [("class_of", C.c_void_p), ("vocab", C.c_int64), ("next", C.c_void_p), ("num_states", C.c_int32), ("num_classes", C.c_int32), ("start", C.c_int32)]
+
+
+class TokenAutomaton:
+    """Mila/TokenAutomaton.h: a deterministic automaton over token ids in the compressed form the device reads -- class_of [vocab] uint16 (token id -> class) and
+    next [num_states, num_classes] uint16 (state x class -> next state, FORBIDDEN = 0xFFFF: the token may not be emitted in that state).  The constructor checks
+    what TokenAutomaton::validate checks (ValueError); the dead-end check needs the request's bias table and runs in generate()."""
+    FORBIDDEN = 0xFFFF
+    MAX_NEXT_BYTES = 256 << 20
+
+    def __init__(self, class_of, next_table, start=0):
+        class_of, next_table = np.asarray(class_of), np.asarray(next_table)
+        if class_of.ndim != 1 or next_table.ndim != 2 or class_of.size < 1:
+            raise ValueError("TokenAutomaton: class_of must be [vocab] and next [num_states, num_classes]")
+        S, Cn = (int(d) for d in next_table.shape)
+        if not 1 <= S <= 65535:
+            raise ValueError("TokenAutomaton: num_states %d outside 1 .. 65535" % S)
+        if not 1 <= Cn <= 65535:
+            raise ValueError("TokenAutomaton: num_classes %d outside 1 .. 65535" % Cn)
+        if S * Cn * 2 > self.MAX_NEXT_BYTES:
+            raise ValueError("TokenAutomaton: the transition table exceeds 256 MiB")
+        if isinstance(start, (bool, float)) or int(start) != start or not 0 <= int(start) < S:
+            raise ValueError("TokenAutomaton: start %r is not a state" % (start,))
+        if class_of.dtype.kind not in "iu" or next_table.dtype.kind not in "iu":
+            raise ValueError("TokenAutomaton: class_of and next must be integer arrays")
+        if class_of.min() < 0 or class_of.max() >= Cn:
+            raise ValueError("TokenAutomaton: a class_of entry is not a class (0 .. %d)" % (Cn - 1))
+        nt = next_table.astype(np.int64)
+        if ((nt != self.FORBIDDEN) & ((nt < 0) | (nt >= S))).any():
+            raise ValueError("TokenAutomaton: a next entry is neither a state (0 .. %d) nor FORBIDDEN" % (S - 1))
+        self.class_of = np.ascontiguousarray(class_of, dtype=np.uint16)
+        self.next = np.ascontiguousarray(next_table, dtype=np.uint16)
+        self.start = int(start)
+
+    vocab = property(lambda self: int(self.class_of.size))
+    num_states = property(lambda self: int(self.next.shape[0]))
+    num_classes = property(lambda self: int(self.next.shape[1]))
+
+    @classmethod
+    def from_transitions(cls, vocab, num_states, transitions, start=0):
+        """{state: {token: next state}} (what is not listed is forbidden) -> the compressed form: tokens whose columns of the dense [num_states, vocab] table are
+        identical share a class, numbered in the order of their first token"""
+        vocab, num_states = int(vocab), int(num_states)
+        if vocab < 1 or not 1 <= num_states <= 65535:
+            raise ValueError("TokenAutomaton.from_transitions: vocab %d / num_states %d out of range" % (vocab, num_states))
+        dense = np.full((num_states, vocab), cls.FORBIDDEN, dtype=np.uint16)
+        for s_, row in transitions.items():
+            if not 0 <= int(s_) < num_states:
+                raise ValueError("TokenAutomaton.from_transitions: state %r is not a state" % (s_,))
+            for t, n in row.items():
+                if not 0 <= int(t) < vocab:
+                    raise ValueError("TokenAutomaton.from_transitions: token id %r outside the vocabulary" % (t,))
+                if not 0 <= int(n) < num_states:
+                    raise ValueError("TokenAutomaton.from_transitions: next state %r is not a state" % (n,))
+                dense[int(s_), int(t)] = int(n)
+        return cls.from_dense(dense, start)
+
+    @classmethod
+    def from_dense(cls, dense, start=0):
+        """a dense [num_states, vocab] table of next states / FORBIDDEN -> the compressed form"""
+        dense = np.ascontiguousarray(dense, dtype=np.uint16)
+        cols, first, inverse = np.unique(dense.T, axis=0, return_index=True, return_inverse=True)
+        order = np.argsort(first, kind="stable")              # classes in the order of their first token
+        rank = np.empty(len(order), dtype=np.int64)
+        rank[order] = np.arange(len(order))
+        return cls(rank[np.asarray(inverse).reshape(-1)], cols[order].T, start)
+
+    def dense(self):
+        """-> the [num_states, vocab] table this automaton compresses"""
+        return self.next[:, self.class_of]
+
+    def step(self, state, token):
+        n = int(self.next[state, self.class_of[token]])
+        return state if n == self.FORBIDDEN else n
+
+    def allowed(self, state):
+        """-> bool [vocab]: the tokens the automaton allows in `state`"""
+        return self.next[state, self.class_of] != self.FORBIDDEN
+
+    def _request(self):
+        return TokenAutomatonRequestC(self.class_of.ctypes.data, self.vocab, self.next.ctypes.data, self.num_states, self.num_classes, self.start)
+
+
 class Gemma:
     """GemmaTransformer<policy> with synthetic weights on cuda:0."""
 
@@ -409,6 +494,33 @@ class Gemma:
         out, on = np.zeros(self.vocab, dtype=np.float32), C.c_int32()
         _check(lib.mila_gemma_read_token_bias(self.h, out.ctypes.data, C.byref(on)))
         return out, bool(on.value)
+
+    def set_token_automaton(self, automaton):
+        """the token automaton of every one-row sampler of the step-level calls that follow (GemmaTransformer::setTokenAutomaton; include/mila_cdna4.h: token
+        automaton): validated, uploaded, turned on and reset to its start state.  None turns it off.  Turning it on or off re-captures a graph once; replacing one by
+        another of the same size, or resetting it, never does."""
+        lib = load()
+        lib.mila_gemma_set_token_automaton.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        if automaton is None:
+            _check(lib.mila_gemma_set_token_automaton(self.h, None, 0, None, 0, 0, 0))
+            return
+        a = automaton
+        _check(lib.mila_gemma_set_token_automaton(self.h, a.class_of.ctypes.data, a.vocab, a.next.ctypes.data, a.num_states, a.num_classes, a.start))
+
+    def reset_token_automaton(self):
+        """the state back to the automaton's start state, the effective table composed for it (GemmaTransformer::resetTokenAutomaton)"""
+        lib = load()
+        lib.mila_gemma_reset_token_automaton.argtypes = [C.c_void_p]
+        _check(lib.mila_gemma_reset_token_automaton(self.h))
+
+    def token_automaton_state(self, table=False):
+        """-> the automaton's state word, read synchronously; table=True: (state, the effective table float32 [vocab])"""
+        lib = load()
+        lib.mila_gemma_token_automaton_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        st, on = C.c_int32(), C.c_int32()
+        eff = np.zeros(self.vocab, dtype=np.float32) if table else None
+        _check(lib.mila_gemma_token_automaton_state(self.h, C.byref(st), C.byref(on), eff.ctypes.data if table else None))
+        return (int(st.value), eff) if table else int(st.value)
 
     def _with_filters(self, filters, fn):
         """fn() under the given filter keywords, neutral again afterwards; no keywords: whatever set_sampling_filters() left"""
@@ -740,17 +852,23 @@ class GemmaModel:
 
     def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
                  speculative_sampling=False, logprobs=None, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None,
-                 banned_tokens=(), allowed_tokens=(), min_tokens=0):
+                 banned_tokens=(), allowed_tokens=(), min_tokens=0, automaton=None):
         """_generate() with the sampling filters (GenerateParams::sampling.min_p / .repetition_penalty / .presence_penalty / .frequency_penalty): the penalties read a
         token table on the device that starts from the whole prompt and counts every generated token; greedy with a penalty = argmax of the adjusted logits; a request
         with any filter set takes the plain loop on a draft_tokens model too.  Log-probabilities are those of the unpenalized logits.  With every filter neutral this
         is _generate(), entry for entry.
         logit_bias ({id: finite value}), banned_tokens, allowed_tokens (a closed answer set; a ban wins) and min_tokens (no stop token among the first min_tokens
         samples) are GenerateParams' fields of those names: one bias table on the device, added to the capped logit by every sampler of the request; a request with
-        any of them takes the plain loop on a draft_tokens model.  Log-probabilities stay those of the unbiased logits."""
+        any of them takes the plain loop on a draft_tokens model.  Log-probabilities stay those of the unbiased logits.
+        automaton (a TokenAutomaton; GenerateParams::automaton): grammar-constrained decoding -- the state advances on the device with every sampled token and the
+        samplers see -inf wherever the state forbids a token.  Refused (ValueError, before anything runs): a reachable state with no token that has both a transition
+        and a finite bias, and min_tokens > 0 beside an automaton.  The return value gains a last element: the state the request ended in (the state after its last
+        sample, a stop token included)."""
         f = _filters(min_p, repetition_penalty, presence_penalty, frequency_penalty)
         bias = _bias_request(logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_tokens, max_new_tokens, self.vocab_size())
-        if f == _filters() and bias is None:
+        if automaton is not None and not isinstance(automaton, TokenAutomaton):
+            raise ValueError("GemmaModel.generate: automaton must be a host.TokenAutomaton")
+        if f == _filters() and bias is None and automaton is None:
             return self._generate(prompt, max_new_tokens, stop_tokens, temperature, top_k, top_p, seed, cancel_after, draft_hint, speculative_sampling, logprobs)
         lib = load()
         pr = np.ascontiguousarray(prompt, dtype=np.int32)
@@ -767,22 +885,35 @@ class GemmaModel:
         head_types = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int64]
         tail = [top_n, lp.ctypes.data, ids.ctypes.data, tlp.ctypes.data, C.byref(n_lp), fl, None if bias is None else C.byref(bias[0])]
         tail_types = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        spec_entry, plain_entry = lib.mila_gemma_model_generate_spec_biased, lib.mila_gemma_model_generate_biased
+        if automaton is not None:      # the entries with the automaton request behind the bias request
+            areq = automaton._request()
+            tail, tail_types = tail + [C.byref(areq)], tail_types + [C.c_void_p]
+            spec_entry, plain_entry = lib.mila_gemma_model_generate_spec_automaton, lib.mila_gemma_model_generate_automaton
         if speculative_sampling or draft_hint is not None:
             if cancel_after is not None:
                 raise ValueError("GemmaModel.generate: draft_hint / speculative_sampling cannot be combined with cancel_after")
             hint = np.ascontiguousarray([] if draft_hint is None else draft_hint, dtype=np.int32)
             stats = (C.c_int64 * 4)()
-            lib.mila_gemma_model_generate_spec_biased.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types
-            _check(lib.mila_gemma_model_generate_spec_biased(*head, hint.ctypes.data if hint.size else None, int(hint.size), int(bool(speculative_sampling)), out.ctypes.data,
+            spec_entry.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types
+            _check(spec_entry(*head, hint.ctypes.data if hint.size else None, int(hint.size), int(bool(speculative_sampling)), out.ctypes.data,
                                                                len(out), C.byref(n), C.byref(status), stats, *tail))
         else:
-            lib.mila_gemma_model_generate_biased.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + tail_types
-            _check(lib.mila_gemma_model_generate_biased(*head, out.ctypes.data, len(out), C.byref(n), C.byref(status), C.byref(reused),
+            plain_entry.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + tail_types
+            _check(plain_entry(*head, out.ctypes.data, len(out), C.byref(n), C.byref(status), C.byref(reused),
                                                           -1 if cancel_after is None else int(cancel_after), *tail))
         res = (out[:min(n.value, len(out))].tolist(), GENERATE_STATUS[status.value], reused.value)
-        if logprobs is None:
-            return res
-        return res + ([(np.float32(lp[i]), ids[i, :top_n].copy(), tlp[i, :top_n].copy()) for i in range(min(n_lp.value, len(out)))],)
+        if logprobs is not None:
+            res = res + ([(np.float32(lp[i]), ids[i, :top_n].copy(), tlp[i, :top_n].copy()) for i in range(min(n_lp.value, len(out)))],)
+        return res if automaton is None else res + (self.last_automaton_state(),)
+
+    def last_automaton_state(self):
+        """GemmaModel::lastAutomatonState(): the automaton state the last generate() ended in, None when that request had no automaton"""
+        lib = load()
+        lib.mila_gemma_model_last_automaton_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        st, has = C.c_int32(), C.c_int32()
+        _check(lib.mila_gemma_model_last_automaton_state(self.h, C.byref(st), C.byref(has)))
+        return int(st.value) if has.value else None
 
     def _generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
                   speculative_sampling=False, logprobs=None):
@@ -869,9 +1000,11 @@ class GemmaModel:
         return dict(zip(("steps", "chain_steps", "drafted", "accepted"), [int(v) for v in out]))
 
     def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0, logprobs=None, min_p=0.0, repetition_penalty=1.0,
-                       presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, banned_tokens=(), allowed_tokens=(), min_tokens=0):
+                       presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, banned_tokens=(), allowed_tokens=(), min_tokens=0, automaton=None):
         """_generate_batch() with the sampling filters of generate(), shared by the rows; every row has its own token table.  logit_bias / banned_tokens /
-        allowed_tokens / min_tokens as in generate(): one bias table shared by the rows, which step in lockstep."""
+        allowed_tokens / min_tokens as in generate(): one bias table shared by the rows, which step in lockstep.  automaton: refused (GemmaModel::generateBatch)."""
+        if automaton is not None:
+            raise ValueError("GemmaModel.generate_batch: automaton is not built: one state per row in generateBatch")
         f = _filters(min_p, repetition_penalty, presence_penalty, frequency_penalty)
         bias = _bias_request(logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_tokens, max_new_tokens, self.vocab_size())
         if f == _filters() and bias is None:

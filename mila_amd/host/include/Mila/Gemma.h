@@ -24,6 +24,7 @@
 
 #include "GemmaBlock.h"
 #include "Serialization.h"
+#include "TokenAutomaton.h"
 
 namespace Mila::Dnn
 {
@@ -287,12 +288,14 @@ namespace Mila::Dnn
             if ( !token_bias_ ) token_bias_ = std::make_unique<Compute::RocmTokenBias>( ctx_, cfg_.vocab_size );
             token_bias_->apply( fill, ids_host, values_host, n );
             bias_on_ = true;
+            if ( automaton_on_ ) token_automaton_->compose( biasValues() );      // the effective table follows its base
         }
         void updateTokenBias( const int32_t* ids_host, const float* values_host, size_t n )
         {
             if ( !bias_on_ ) throw std::logic_error( "GemmaTransformer::updateTokenBias: no bias is set (setTokenBias)" );
             checkBiasEntries( ids_host, values_host, n, "GemmaTransformer::updateTokenBias" );
             token_bias_->update( ids_host, values_host, n );
+            if ( automaton_on_ ) token_automaton_->compose( biasValues() );
         }
         /// an update uploaded now and enqueued later: commitTokenBiasUpdate() is one small launch in stream order that reads no host memory -- what a decode-ahead
         /// loop puts between two replays (GemmaModel: the min_tokens restore)
@@ -306,11 +309,50 @@ namespace Mila::Dnn
         {
             if ( !bias_on_ ) throw std::logic_error( "GemmaTransformer::commitTokenBiasUpdate: no bias is set (setTokenBias)" );
             token_bias_->commit();
+            if ( automaton_on_ ) token_automaton_->compose( biasValues() );
         }
-        void clearTokenBias() noexcept { bias_on_ = false; }
+        void clearTokenBias()
+        {
+            const bool was = bias_on_;
+            bias_on_ = false;
+            if ( was && automaton_on_ ) token_automaton_->compose( nullptr );
+        }
         bool tokenBiasOn() const noexcept { return bias_on_; }
         /// the table (nullptr before the first setTokenBias())
         Compute::RocmTokenBias* tokenBias() noexcept { return token_bias_.get(); }
+
+        /// Token automaton (mila_cdna4.h: token automaton; Mila/TokenAutomaton.h): grammar-constrained decoding on the one-row interface.  While one is on, every one-row
+        /// sampler of this network -- sampleGreedy / sampleStochasticRadix and the tail of the captured step -- reads the automaton's effective table (the bias table, or
+        /// zeros, with -inf wherever the current state forbids the token) in the place of the bias table and is followed by ONE launch that advances the state by the
+        /// token just chosen and rewrites the table: a node behind the tail of a captured step, the same launch behind an eager sampler.  A greedy step then ends at
+        /// the logits and takes the biased greedy sampler's two launches.  setTokenAutomaton() validates, uploads, turns it on and resets; resetTokenAutomaton() puts
+        /// the state back to `start` and composes the table; clearTokenAutomaton() turns it off.  Whether one is on belongs to what the one-row graph was captured
+        /// for, with the image's address and (S, C), which the step node holds by value: on / off re-captures once, as does an automaton of another size; replacing
+        /// the contents of one of the same size, or resetting, never does.  The rows step and the chain step refuse while one is on.  Log-probabilities stay those
+        /// of the unconstrained logits.  Allocated by the first setTokenAutomaton() and counted in the memory statistics from then on.
+        void setTokenAutomaton( const TokenAutomaton& a )
+        {
+            a.validate( cfg_.vocab_size );
+            if ( !token_automaton_ ) token_automaton_ = std::make_unique<Compute::RocmTokenAutomaton>( ctx_, cfg_.vocab_size );
+            token_automaton_->upload( a.class_of.data(), a.next.data(), a.num_states, a.num_classes, a.start );
+            automaton_on_ = true;
+            token_automaton_->reset( biasValues() );
+        }
+        void resetTokenAutomaton()
+        {
+            if ( !automaton_on_ ) throw std::logic_error( "GemmaTransformer::resetTokenAutomaton: no automaton is set (setTokenAutomaton)" );
+            token_automaton_->reset( biasValues() );
+        }
+        void clearTokenAutomaton() noexcept { automaton_on_ = false; }
+        bool tokenAutomatonOn() const noexcept { return automaton_on_; }
+        /// the state word, read synchronously: for tests, and for a caller that asks whether the final state is accepting
+        int32_t tokenAutomatonState()
+        {
+            if ( !token_automaton_ || !token_automaton_->loaded() ) throw std::logic_error( "GemmaTransformer::tokenAutomatonState: no automaton was set (setTokenAutomaton)" );
+            return token_automaton_->readState();
+        }
+        /// the device side (nullptr before the first setTokenAutomaton())
+        Compute::RocmTokenAutomaton* tokenAutomaton() noexcept { return token_automaton_.get(); }
 
         /// capture the fused step once; afterwards replayGraph() advances one token per call.
         /// The token is read from `token` (device) and the position from an internal device counter.
@@ -333,7 +375,7 @@ namespace Mila::Dnn
                 int sampler_partials = 0;
                 captured_band_end_ = bandBucket( start_position );
                 const bool stochastic = graph_sampling_.has_value();
-                const bool penalized_greedy = sample_in_graph_ && !stochastic && ( filters_.penalized() || bias_on_ );      // ends at the logits; the penalized sampler's two launches follow
+                const bool penalized_greedy = sample_in_graph_ && !stochastic && ( filters_.penalized() || bias_on_ || automaton_on_ );      // ends at the logits; the penalized sampler's two launches follow
                 if ( stochastic && ( !draw_ring_ || !token_seq_ ) )
                     throw std::invalid_argument( "GemmaTransformer::captureGraph: a stochastic step needs setDrawRing() and the sequence counter of setTokenRing()" );
                 if ( step_lp_ && !stochastic && !sample_in_graph_ )
@@ -341,13 +383,13 @@ namespace Mila::Dnn
                 enqueueFusedStep( token.data(), static_cast<int>( captured_band_end_ ), pos_dev_->data(), ( sample_in_graph_ && !stochastic && !penalized_greedy ) ? &sampler_partials : nullptr );
                 // stochastic: the step ends at the logits like the sampler-less one, then the radix pipeline on the model-owned workspace; its last node draws from the
                 // ring, writes the next token, bumps the position and publishes -- in the place of the advance_position node.  One linear chain on one stream.
-                if ( stochastic && ( graph_sampling_->filtered() || bias_on_ ) )      // the same launches, in their filtered / biased instantiations: the node count does not move
+                if ( stochastic && ( graph_sampling_->filtered() || bias_on_ || automaton_on_ ) )      // the same launches, in their filtered / biased instantiations: the node count does not move
                 {
                     const mila_sample_filters f = graph_sampling_->filters();
                     Compute::rocmCheck( mila_cdna4_sample_radix_biased_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size,
                                                                                      cfg_.final_logit_softcapping, graph_sampling_->temperature, graph_sampling_->top_k,
                                                                                      graph_sampling_->top_p, draw_ring_, draw_ring_size_, &f, tableWords( *graph_sampling_, 0, false ),
-                                                                                     biasValues(), 0, radix_scratch_->data(), radix_scratch_->sizeInBytes(), pos_dev_->data(), token_seq_,
+                                                                                     samplerBias(), 0, radix_scratch_->data(), radix_scratch_->sizeInBytes(), pos_dev_->data(), token_seq_,
                                                                                      token_ring_, token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
                 }
                 else if ( stochastic )
@@ -359,7 +401,7 @@ namespace Mila::Dnn
                 {
                     const mila_sample_filters f = filters_.filters();
                     Compute::rocmCheck( mila_cdna4_sample_argmax_biased_advance_fp32( logits_->data(), const_cast<TokenTensor&>( token ).data(), (int)cfg_.vocab_size,
-                                                                                      cfg_.final_logit_softcapping, &f, tableWords( filters_, 0, false ), biasValues(), 0,
+                                                                                      cfg_.final_logit_softcapping, &f, tableWords( filters_, 0, false ), samplerBias(), 0,
                                                                                       sample_scratch_->data(), sample_scratch_->sizeInBytes(), pos_dev_->data(),
                                                                                       token_ring_ ? token_seq_ : nullptr, token_ring_, token_ring_ ? token_ring_size_ : 0, ctx_->getStream() ) );
                 }
@@ -369,6 +411,9 @@ namespace Mila::Dnn
                                                                                 ctx_->getStream() ) );
                 else
                     Compute::rocmCheck( mila_cdna4_advance_position( pos_dev_->data(), ctx_->getStream() ) );
+                // a token automaton: one more node behind the tail, which reads the token word the tail wrote, advances the state and rewrites the effective table the
+                // next replay's sampler reads
+                if ( automaton_on_ && ( sample_in_graph_ || stochastic ) ) token_automaton_->step( biasValues(), token.data() );
                 // the tail has written the next token (and bumped the sequence counter): its log-probability and the alternatives, two more nodes
                 if ( step_lp_ ) enqueueStepLogprobs( token.data() );
             }
@@ -383,6 +428,7 @@ namespace Mila::Dnn
             captured_sampling_ = graph_sampling_;
             captured_filters_ = filters_;
             captured_bias_ = bias_on_;
+            captured_automaton_ = automatonKey();
             captured_draw_ring_ = graph_sampling_ ? draw_ring_ : nullptr;
             captured_lp_ = step_lp_;
             ++graph_captures_;
@@ -397,6 +443,7 @@ namespace Mila::Dnn
                  !sameSampling( captured_sampling_, graph_sampling_ ) || ( graph_sampling_ && captured_draw_ring_ != draw_ring_ ) || captured_lp_ != step_lp_ ||
                  ( sample_in_graph_ && !graph_sampling_ && !samePenalties( captured_filters_, filters_ ) ) ||
                  ( ( sample_in_graph_ || graph_sampling_ ) && captured_bias_ != bias_on_ ) ||
+                 ( ( sample_in_graph_ || graph_sampling_ ) && captured_automaton_ != automatonKey() ) ||
                  bandBucket( start_position ) != captured_band_end_ )
                 captureGraph( token, start_position );
         }
@@ -755,12 +802,13 @@ namespace Mila::Dnn
         void sampleGreedyWith( TokenTensor& token_out, const SamplingParams& fl )
         {
             Compute::TraceRange tr( "gemma.sample(greedy)" );
-            if ( fl.penalized() || bias_on_ )
+            if ( fl.penalized() || bias_on_ || automaton_on_ )
             {
                 const mila_sample_filters f = fl.filters();
                 Compute::rocmCheck( mila_cdna4_sample_argmax_biased_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, &f,
-                                                                          tableWords( fl, 0, true ), biasValues(), 0, sample_scratch_->data(), sample_scratch_->sizeInBytes(),
+                                                                          tableWords( fl, 0, true ), samplerBias(), 0, sample_scratch_->data(), sample_scratch_->sizeInBytes(),
                                                                           ctx_->getStream() ) );
+                if ( automaton_on_ ) token_automaton_->step( biasValues(), token_out.data() );      // the launch a captured step holds behind its tail
                 return;
             }
             Compute::rocmCheck( mila_cdna4_sample_argmax_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, sample_scratch_->data(),
@@ -773,7 +821,7 @@ namespace Mila::Dnn
         {
             if ( sp.temperature <= 0.0f ) { sampleGreedy( token_out ); return; }
             Compute::TraceRange tr( "gemma.sample(stochastic)" );
-            if ( bias_on_ ) throw std::invalid_argument( "GemmaTransformer::sampleStochastic: the search pipeline takes no bias table (sampleStochasticRadix)" );
+            if ( bias_on_ || automaton_on_ ) throw std::invalid_argument( "GemmaTransformer::sampleStochastic: the search pipeline takes no bias table (sampleStochasticRadix)" );
             const size_t need = mila_cdna4_sample_stochastic_scratch_bytes( (int)cfg_.vocab_size );
             void* scratch = ctx_->getScratch( need );
             Compute::rocmCheck( mila_cdna4_sample_stochastic_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature,
@@ -785,13 +833,14 @@ namespace Mila::Dnn
         {
             if ( sp.temperature <= 0.0f ) { sampleGreedyWith( token_out, sp.filtered() ? sp : filters_ ); return; }
             Compute::TraceRange tr( "gemma.sample(stochastic, radix)" );
-            if ( sp.filtered() || bias_on_ )      // the eager form of what a filtered / biased captured step ends with
+            if ( sp.filtered() || bias_on_ || automaton_on_ )      // the eager form of what a filtered / biased / constrained captured step ends with
             {
                 sp.checkFilters( "GemmaTransformer::sampleStochasticRadix" );
                 const mila_sample_filters f = sp.filters();
                 Compute::rocmCheck( mila_cdna4_sample_radix_biased_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature, sp.top_k,
-                                                                         sp.top_p, r, &f, tableWords( sp, 0, true ), biasValues(), 0, radix_scratch_->data(), radix_scratch_->sizeInBytes(),
+                                                                         sp.top_p, r, &f, tableWords( sp, 0, true ), samplerBias(), 0, radix_scratch_->data(), radix_scratch_->sizeInBytes(),
                                                                          ctx_->getStream() ) );
+                if ( automaton_on_ ) token_automaton_->step( biasValues(), token_out.data() );
                 return;
             }
             Compute::rocmCheck( mila_cdna4_sample_radix_fp32( logits_->data(), token_out.data(), (int)cfg_.vocab_size, cfg_.final_logit_softcapping, sp.temperature, sp.top_k, sp.top_p, r,
@@ -1430,6 +1479,7 @@ namespace Mila::Dnn
             int partials = 0;
             if ( step_lp_ && !greedy && !rowsSamplesInStep() )
                 throw std::invalid_argument( "GemmaTransformer: token log-probabilities need a sampler tail in the rows step (greedy, or setRowsSampling)" );
+            if ( automaton_on_ ) throw std::invalid_argument( "GemmaTransformer: the rows step takes no token automaton: one state per row is not built (clearTokenAutomaton)" );
             const bool penalized_greedy = greedy && ( filters_.penalized() || bias_on_ );      // the lm_head epilogue cannot compute the adjusted logits: the step ends at the logits
             enqueueFusedStepRows( B, static_cast<int>( band ), ( greedy && !penalized_greedy ) ? &partials : nullptr );
             auto& R = *rows_;
@@ -1470,6 +1520,7 @@ namespace Mila::Dnn
             int partials = 0;
             if ( filters_.penalized() ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no penalties (setSamplingFilters)" );
             if ( bias_on_ ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no bias table (clearTokenBias)" );      // refused rather than silently unbiased
+            if ( automaton_on_ ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no token automaton (clearTokenAutomaton)" );
             const bool stochastic = chainSamples();
             enqueueFusedStepRows( T, static_cast<int>( band ), stochastic ? nullptr : &partials, &at );      // stochastic: the lm_head leaves the logits only
             auto& R = *rows_;
@@ -1868,6 +1919,7 @@ namespace Mila::Dnn
             if ( score_op_ ) b += score_op_->stateBytes();
             if ( token_table_ ) b += token_table_->stateBytes();
             if ( token_bias_ ) b += token_bias_->stateBytes();
+            if ( token_automaton_ ) b += token_automaton_->stateBytes();
             return b;
         }
         size_t requiredOwnStateBytes() const
@@ -1892,6 +1944,7 @@ namespace Mila::Dnn
             if ( score_op_ ) b += score_op_->stateBytes();                                                   // prompt log-probabilities, once prefillScored() has run
             if ( token_table_ ) b += Compute::RocmTokenTable::requiredBytes( cfg_.vocab_size, token_table_->rows() );      // the token tables, once a penalty was set
             if ( token_bias_ ) b += Compute::RocmTokenBias::requiredBytes( cfg_.vocab_size );                              // the bias table and its staging, once a bias was set
+            if ( token_automaton_ ) b += token_automaton_->requiredBytes();                                              // the automaton's image, words and effective table, once one was set
             return b;
         }
     public:
@@ -1981,6 +2034,13 @@ namespace Mila::Dnn
         std::unique_ptr<Compute::RocmTokenBias> token_bias_;
         bool bias_on_ = false, captured_bias_ = false, rows_captured_bias_ = false;
         const float* biasValues() noexcept { return bias_on_ ? token_bias_->data() : nullptr; }
+        // token automaton: the device side (from the first setTokenAutomaton() on), whether it is on, and what the one-row graph's step node was captured with
+        std::unique_ptr<Compute::RocmTokenAutomaton> token_automaton_;
+        bool automaton_on_ = false;
+        std::optional<Compute::RocmTokenAutomaton::Key> captured_automaton_{};
+        std::optional<Compute::RocmTokenAutomaton::Key> automatonKey() const { return automaton_on_ ? std::optional( token_automaton_->key() ) : std::nullopt; }
+        /// what the one-row samplers read as their bias table: the automaton's effective table (composed over the bias table) while one is on
+        const float* samplerBias() noexcept { return automaton_on_ ? token_automaton_->eff() : biasValues(); }
         void checkBiasEntries( const int32_t* ids, const float* values, size_t n, const char* who ) const
         {
             if ( n && ( !ids || !values ) ) throw std::invalid_argument( std::string( who ) + ": null pointer" );

@@ -19,9 +19,11 @@
 #include <random>
 #include <span>
 #include <unordered_set>
+#include <memory>
 #include <variant>
 
 #include "Gemma.h"
+#include "TokenAutomaton.h"
 #include "TokenBias.h"
 
 namespace Mila::Dnn
@@ -106,7 +108,23 @@ namespace Mila::Dnn
         std::vector<int32_t> banned_tokens{};                     ///< never sampled (a ban wins over an allow)
         std::vector<int32_t> allowed_tokens{};                    ///< non-empty: only these may be sampled
         int min_tokens = 0;                                       ///< no stop token among the first min_tokens samples
+        /// Grammar-constrained decoding (Mila/TokenAutomaton.h; include/mila_cdna4.h: token automaton): a deterministic automaton over token ids that says, state by
+        /// state, which tokens may come next.  generate() validates it against the request's bias table (a reachable state that keeps no token with a transition and a
+        /// finite bias is refused, with its number), uploads it and resets the state before the first sample; every step then ends with one launch that advances the
+        /// state by the sampled token and rewrites the table the next sampler reads -- no logits readback, the captured step and the decode-ahead loop stay.  Stop
+        /// tokens are ordinary tokens of the automaton.  min_tokens > 0 beside an automaton is refused (a chain of states says the same).  A constrained request takes
+        /// the plain loop on a withDraftTokens model; generateBatch refuses one.  Log-probabilities stay those of the unconstrained logits.  A request without one
+        /// clears the network's.  lastAutomatonState() reports where the request ended.
+        std::shared_ptr<const TokenAutomaton> automaton{};
     };
+    /// the automaton of a request against its composed bias table (throws invalid_argument; touches no device)
+    inline void checkRequestAutomaton( const GenerateParams& params, const TokenBiasPlan& bias_plan, dim_t vocab )
+    {
+        if ( !params.automaton ) return;
+        if ( params.min_tokens > 0 ) throw std::invalid_argument( "GenerateParams: min_tokens > 0 together with an automaton (a chain of states expresses it)" );
+        params.automaton->validate( vocab );
+        params.automaton->checkLive( bias_plan );
+    }
     /// the bias table of a request (throws invalid_argument for what composeTokenBias refuses); stop_ids: the request's effective stop set
     inline TokenBiasPlan composeRequestBias( const GenerateParams& params, const std::unordered_set<int32_t>& stop_ids, dim_t vocab )
     {
@@ -351,6 +369,8 @@ namespace Mila::Dnn
         /// the speculative loop's counters of the last generate() (all zero on a model without draft tokens, or after a stochastic request without
         /// GenerateParams::speculative_sampling)
         const SpeculationStats& lastSpeculation() const noexcept { return last_speculation_; }
+        /// the automaton state the last generate() ended in: the state after its last sample, a stop token included (nullopt: the request had no automaton)
+        std::optional<int32_t> lastAutomatonState() const noexcept { return last_automaton_state_; }
         Network& network() noexcept { return network_; }
 
         /// prefill + decode; on_token is called for every generated token except a stop token
@@ -437,6 +457,8 @@ namespace Mila::Dnn
             const bool greedy = isGreedy( params.sampling );
             const typename TNet::SamplingParams sp = networkSampling<TNet>( params.sampling );
             const TokenBiasPlan bias_plan = composeRequestBias( params, stop_ids, vocabSize() );      // (nothing was enqueued yet)
+            if ( params.automaton ) throw std::invalid_argument( "GemmaModel::generateBatch: GenerateParams::automaton is not built: one state per row in generateBatch" );
+            net.clearTokenAutomaton();
             net.setSamplingFilters( sp );      // the greedy rows samplers' filters: this request's, neutral ones included
             applyRequestBias( net, bias_plan );      // one table for every row, before the first sample
             std::vector<std::mt19937_64> rng;
@@ -686,6 +708,8 @@ namespace Mila::Dnn
             if ( params.stop_tokens.empty() ) stop_ids = stopTokens();
             else stop_ids.insert( params.stop_tokens.begin(), params.stop_tokens.end() );
             const TokenBiasPlan bias_plan = composeRequestBias( params, stop_ids, vocabSize() );      // (composed and checked before anything is enqueued)
+            checkRequestAutomaton( params, bias_plan, vocabSize() );
+            last_automaton_state_.reset();
 
             // transparent KV prefix reuse: cache positions [0, n) are a function of the first n tokens only, so token equality against what the
             // caches hold is the whole validity test; at least the last prompt position is always prefilled (fresh logits)
@@ -718,7 +742,11 @@ namespace Mila::Dnn
             net.setSamplingFilters( net_sampling );
             if ( net_sampling.penalized() ) net.resetTokenTable( 0, prompt.data(), prompt.size() );
             applyRequestBias( net, bias_plan );      // the bias table of this request, or none: before the first sample
-            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 && !net_sampling.filtered() && !bias_plan.active )
+            // the automaton of this request, or none: uploaded and reset to its start state before the first sample, as the penalties' table is reset above.  The
+            // state is followed on the host from the tokens the loop sees (the device word may be one decode-ahead sample further when the request ends)
+            if ( params.automaton ) { net.setTokenAutomaton( *params.automaton ); last_automaton_state_ = params.automaton->start; }
+            else net.clearTokenAutomaton();
+            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 && !net_sampling.filtered() && !bias_plan.active && !params.automaton )
                 return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids, greedy );
             // log-probabilities travel like the tokens: every sample's record lands in slot seq % kSnapshots of a second host-visible ring, written by the two launches
             // behind the sampler -- eagerly for the first token, as the captured step's last nodes afterwards
@@ -783,6 +811,7 @@ namespace Mila::Dnn
                 }
                 const int32_t token = awaitSampledToken( mine );
                 if ( ahead ) { kv_token_history_.push_back( token ); ++position; }     // the ahead-decode entered it into the caches, whatever it is
+                if ( params.automaton ) last_automaton_state_ = params.automaton->step( *last_automaton_state_, token );
                 if ( stop_ids.contains( token ) )
                 {
                     if ( ahead && !greedy ) rng_ = rng_before_ahead;
@@ -936,6 +965,7 @@ namespace Mila::Dnn
         static constexpr size_t kSnapshots = 8;
         static constexpr size_t kRowDraws = 4;          // rows of a rows / chain step
         SpeculationStats last_speculation_{};
+        std::optional<int32_t> last_automaton_state_{};
         Network network_;
         GemmaConfig network_config_;
         GemmaModelConfig model_config_;

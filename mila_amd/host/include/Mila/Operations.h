@@ -1297,6 +1297,90 @@ namespace Mila::Dnn::Compute
         std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> stage_ids_;
     };
 
+    /// The device side of a token automaton for one row (mila_cdna4.h: token automaton): the image (class_of, then next), the state word and the ticket word, and the
+    /// effective table `eff` that the biased samplers read in the place of the bias table.  eff, the state and the ticket never move, so a captured step that holds
+    /// them sees every later reset; the image is re-allocated only when its size changes, and key() names what a captured step kernel node holds by value (the image
+    /// address, S, C).  Everything runs on the context's stream.  upload() and reset() synchronize (they read host memory); compose() and step() are one launch each.
+    class RocmTokenAutomaton
+    {
+    public:
+        struct Key { const void* image = nullptr; int S = 0, C = 0; bool operator==( const Key& ) const = default; };
+        RocmTokenAutomaton( IExecutionContext* ctx, dim_t vocab ) : context_( cast_context<DeviceType::Rocm>( ctx ) ), vocab_( vocab )
+        {
+            if ( vocab <= 0 ) throw std::invalid_argument( "RocmTokenAutomaton: need a positive vocabulary" );
+            (void)narrowToKernelIndex( vocab, "vocab" );
+            const auto dev = context_->getDeviceId();
+            eff_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ vocab } );
+            words_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ 2 } );
+            rocmCheck( mila_cdna4_memset_zero( words_->rawData(), 8, context_->getStream() ) );
+            rocmCheck( mila_cdna4_token_bias_fill( eff_->data(), 0, 0, static_cast<int>( vocab_ ), 0.0f, context_->getStream() ) );
+            context_->synchronize();
+        }
+        /// the image of a validated automaton (TokenAutomaton::validate) onto the device; the state is whatever it was: reset() follows
+        void upload( const uint16_t* class_of, const uint16_t* next, int S, int C, int start )
+        {
+            const size_t bytes = mila_cdna4_token_automaton_bytes( static_cast<int>( vocab_ ), S, C );
+            if ( !bytes || !class_of || !next || start < 0 || start >= S ) throw std::invalid_argument( "RocmTokenAutomaton::upload: an automaton outside the limits of mila_cdna4.h" );
+            const dim_t words = static_cast<dim_t>( ( bytes + 3 ) / 4 );
+            context_->synchronize();      // (no step in flight reads the image that is replaced)
+            if ( !image_ || image_->shape()[ 0 ] != words ) image_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( context_->getDeviceId(), shape_t{ words } );
+            rocmCheck( mila_cdna4_memcpy_h2d( image_->rawData(), class_of, static_cast<size_t>( vocab_ ) * 2, context_->getStream() ) );
+            rocmCheck( mila_cdna4_memcpy_h2d( nextDev(), next, static_cast<size_t>( S ) * static_cast<size_t>( C ) * 2, context_->getStream() ) );
+            context_->synchronize();
+            S_ = S; C_ = C; start_ = start;
+        }
+        bool loaded() const noexcept { return image_ != nullptr; }
+        Key key() const noexcept { return Key{ image_ ? image_->rawData() : nullptr, S_, C_ }; }
+        const float* eff() { return eff_->data(); }
+        /// state = start, ticket = 0, eff composed over `base` (nullptr: zeros)
+        void reset( const float* base )
+        {
+            const int32_t w[ 2 ] = { start_, 0 };
+            rocmCheck( mila_cdna4_memcpy_h2d( words_->rawData(), w, 8, context_->getStream() ) );
+            context_->synchronize();
+            compose( base );
+        }
+        /// eff for the state the word holds: one launch in stream order
+        void compose( const float* base )
+        {
+            requireLoaded();
+            rocmCheck( mila_cdna4_token_automaton_compose( eff_->data(), 0, base, 0, classDev(), nextDev(), S_, C_, words_->data(), 1, static_cast<int>( vocab_ ), context_->getStream() ) );
+        }
+        /// the state advanced by *token_dev and eff composed for it: one launch in stream order (what a captured step holds as a node)
+        void step( const float* base, const int32_t* token_dev )
+        {
+            requireLoaded();
+            rocmCheck( mila_cdna4_token_automaton_step( eff_->data(), 0, base, 0, classDev(), nextDev(), S_, C_, words_->data(), token_dev, nullptr,
+                                                        reinterpret_cast<uint32_t*>( words_->data() + 1 ), 1, static_cast<int>( vocab_ ), context_->getStream() ) );
+        }
+        /// the state word (synchronizes)
+        int32_t readState()
+        {
+            int32_t s = 0;
+            rocmCheck( mila_cdna4_memcpy_d2h( &s, words_->rawData(), 4, context_->getStream() ) );
+            context_->synchronize();
+            return s;
+        }
+        /// the effective table to the host (synchronizes)
+        void read( float* out )
+        {
+            rocmCheck( mila_cdna4_memcpy_d2h( out, eff_->data(), static_cast<size_t>( vocab_ ) * 4, context_->getStream() ) );
+            context_->synchronize();
+        }
+        size_t stateBytes() const { return eff_->sizeInBytes() + words_->sizeInBytes() + ( image_ ? image_->sizeInBytes() : 0 ); }
+        /// eff + the two words + the image rounded up to whole 32-bit words
+        size_t requiredBytes() const { return static_cast<size_t>( vocab_ ) * 4 + 8 + ( image_ ? ( ( mila_cdna4_token_automaton_bytes( static_cast<int>( vocab_ ), S_, C_ ) + 3 ) / 4 ) * 4 : 0 ); }
+    private:
+        void requireLoaded() const { if ( !image_ ) throw std::logic_error( "RocmTokenAutomaton: no automaton was uploaded" ); }
+        const uint16_t* classDev() { return reinterpret_cast<const uint16_t*>( image_->rawData() ); }
+        uint16_t* nextDev() { return reinterpret_cast<uint16_t*>( image_->rawData() ) + vocab_; }
+        ExecutionContext<DeviceType::Rocm>* context_;
+        dim_t vocab_;
+        int S_{ 0 }, C_{ 0 }, start_{ 0 };
+        std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> eff_;
+        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> words_, image_;
+    };
+
     class RocmSamplingOp : public Operation<DeviceType::Rocm, TensorDataType::FP32>
     {
     public:

@@ -635,6 +635,42 @@ HOST_API int mila_gemma_read_token_bias( void* h, float* out, int32_t* out_on )
         }, static_cast<Runner*>( h )->model );
     } );
 }
+/// The token automaton of the step-level calls that follow (Gemma.h: setTokenAutomaton): class_of [vocab], next [S * C]; validated, uploaded, turned on and reset to
+/// `start`.  class_of == NULL turns it off.
+HOST_API int mila_gemma_set_token_automaton( void* h, const uint16_t* class_of, int64_t vocab, const uint16_t* next, int S, int C, int start )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( !class_of ) { m->clearTokenAutomaton(); return; }
+            if ( !next || vocab < 0 || S < 0 || C < 0 ) throw std::invalid_argument( "set_token_automaton: null table or negative size" );
+            TokenAutomaton a;
+            a.num_states = S; a.num_classes = C; a.start = start;
+            a.class_of.assign( class_of, class_of + vocab );
+            a.next.assign( next, next + static_cast<size_t>( S ) * static_cast<size_t>( C ) );
+            m->setTokenAutomaton( a );
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
+/// the state back to `start` and the effective table composed for it
+HOST_API int mila_gemma_reset_token_automaton( void* h )
+{
+    return guarded( [&] { std::visit( [&]( auto& m ) { m->resetTokenAutomaton(); }, static_cast<Runner*>( h )->model ); } );
+}
+/// *out_state = the state word (a synchronous read), *out_on = whether an automaton is on; out_eff (may be NULL): the effective table [vocab]
+HOST_API int mila_gemma_token_automaton_state( void* h, int32_t* out_state, int32_t* out_on, float* out_eff )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( out_state ) *out_state = m->tokenAutomatonState();
+            if ( out_on ) *out_on = m->tokenAutomatonOn() ? 1 : 0;
+            if ( out_eff ) m->tokenAutomaton()->read( out_eff );
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
 HOST_API int mila_gemma_set_active( void* h, int b, int active, int32_t token )
 {
     return guarded( [&] { std::visit( [&]( auto& m ) { m->setRowActive( b, active != 0 ); if ( token >= 0 ) m->setRowToken( b, token ); }, static_cast<Runner*>( h )->model ); } );
@@ -1621,6 +1657,24 @@ static void apply_request_bias( GenerateParams& gp, const mila_token_bias_reques
     gp.min_tokens = b->min_tokens;
 }
 
+/// GenerateParams::automaton of the *_automaton entries below, by pointer (NULL: none)
+struct mila_token_automaton_request
+{
+    const uint16_t* class_of; int64_t vocab;      ///< token id -> class
+    const uint16_t* next;                         ///< [num_states * num_classes], 0xFFFF = forbidden
+    int32_t num_states, num_classes, start;
+};
+static void apply_request_automaton( GenerateParams& gp, const mila_token_automaton_request* a )
+{
+    if ( !a ) return;
+    if ( !a->class_of || !a->next || a->vocab < 0 || a->num_states < 0 || a->num_classes < 0 ) throw std::invalid_argument( "token automaton request: null table or negative size" );
+    auto t = std::make_shared<TokenAutomaton>();
+    t->num_states = a->num_states; t->num_classes = a->num_classes; t->start = a->start;
+    t->class_of.assign( a->class_of, a->class_of + a->vocab );
+    t->next.assign( a->next, a->next + static_cast<size_t>( a->num_states ) * static_cast<size_t>( a->num_classes ) );
+    gp.automaton = std::move( t );
+}
+
 struct LogprobSink
 {
     int top_n{ -1 };
@@ -1653,7 +1707,8 @@ struct LogprobSink
 
 static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                 float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
-                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters = nullptr, const mila_token_bias_request* bias = nullptr );
+                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters = nullptr, const mila_token_bias_request* bias = nullptr,
+                                const mila_token_automaton_request* automaton = nullptr );
 HOST_API int mila_gemma_model_generate( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                         float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
                                         int64_t cancel_after )
@@ -1689,9 +1744,31 @@ HOST_API int mila_gemma_model_generate_biased( void* h, const int32_t* prompt, i
     return model_generate_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_count, out_status, out_reused, cancel_after,
                                 LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters, bias );
 }
+/// mila_gemma_model_generate_biased (filters and bias may be NULL) with the automaton request (NULL: none)
+HOST_API int mila_gemma_model_generate_automaton( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
+                                                  float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
+                                                  int64_t cancel_after, int top_n, float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_count,
+                                                  const float* filters, const mila_token_bias_request* bias, const mila_token_automaton_request* automaton )
+{
+    return model_generate_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, out_tokens, cap, out_count, out_status, out_reused, cancel_after,
+                                LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters, bias, automaton );
+}
+/// GemmaModel::lastAutomatonState(): *out_has = whether the last generate() had an automaton, *out_state = the state it ended in
+HOST_API int mila_gemma_model_last_automaton_state( void* h, int32_t* out_state, int32_t* out_has )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m ) throw std::invalid_argument( "null model" );
+        const auto st = m->lastAutomatonState();
+        if ( out_has ) *out_has = st ? 1 : 0;
+        if ( out_state ) *out_state = st.value_or( -1 );
+    } );
+}
 static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                 float top_p, int64_t seed, int32_t* out_tokens, int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_reused,
-                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters, const mila_token_bias_request* bias )
+                                int64_t cancel_after, LogprobSink sink, int64_t* out_logprob_count, const float* filters, const mila_token_bias_request* bias,
+                                const mila_token_automaton_request* automaton )
 {
     return guarded( [&]
     {
@@ -1705,6 +1782,7 @@ static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         apply_request_filters( gp.sampling, filters );
         apply_request_bias( gp, bias );
+        apply_request_automaton( gp, automaton );
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
         if ( seed >= 0 ) m->seedSampler( static_cast<uint64_t>( seed ) );
         int64_t n = 0;
@@ -1723,7 +1801,7 @@ static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt
 static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens, int64_t cap, int64_t* out_count,
                                int32_t* out_status, int64_t* out_stats, LogprobSink sink = LogprobSink{}, int64_t* out_logprob_count = nullptr, const float* filters = nullptr,
-                               const mila_token_bias_request* bias = nullptr )
+                               const mila_token_bias_request* bias = nullptr, const mila_token_automaton_request* automaton = nullptr )
 {
     return guarded( [&]
     {
@@ -1738,6 +1816,7 @@ static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt,
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         apply_request_filters( gp.sampling, filters );
         apply_request_bias( gp, bias );
+        apply_request_automaton( gp, automaton );
         for ( int i = 0; i < n_stop; ++i ) gp.stop_tokens.push_back( stop_tokens[ i ] );
         if ( hint && n_hint > 0 )
             gp.draft = [=]( std::span<const int32_t> history, int k )
@@ -1805,6 +1884,17 @@ HOST_API int mila_gemma_model_generate_spec_biased( void* h, const int32_t* prom
 {
     return generate_spec_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, hint, n_hint, speculative_sampling, out_tokens, cap, out_count,
                                out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters, bias );
+}
+
+/// mila_gemma_model_generate_spec_biased with the automaton request (NULL: none): a constrained request takes the plain loop
+HOST_API int mila_gemma_model_generate_spec_automaton( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                                       int top_k, float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens,
+                                                       int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_stats, int top_n, float* out_logprob, int32_t* out_ids,
+                                                       float* out_logprobs, int64_t* out_logprob_count, const float* filters, const mila_token_bias_request* bias,
+                                                       const mila_token_automaton_request* automaton )
+{
+    return generate_spec_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, hint, n_hint, speculative_sampling, out_tokens, cap, out_count,
+                               out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters, bias, automaton );
 }
 
 /// the vocabulary size of the model (what the ids of a bias request are checked against)
