@@ -282,6 +282,29 @@ def matvec_rows_plan(fmt, K, N, geglu=False, f32_out=False, rows=1):
     return dict(zip(MATVEC_ROWS_PLAN_FIELDS, [int(v) for v in buf.value.decode().split(":")]))
 
 
+def row_kernel_form(op, outer, dim, inner=1):
+    """the kernel a row entry launches at a shape (csrc/row_kernel_plan.h), e.g. row_kernel_form("rmsnorm_bf16", 4, 3840) == "rmsnorm_block"; dim = K of
+    quantize_fp8_per_token, HS of rope_forward_bf16 and the fused_qkv_post entries.  None for an unknown entry or a shape it refuses.  Needs no GPU."""
+    lib = load()
+    lib.mila_cdna4_row_kernel_form.restype = C.c_size_t
+    buf = C.create_string_buffer(64)
+    need = lib.mila_cdna4_row_kernel_form(op.encode(), int(outer), int(dim), int(inner), buf, C.c_size_t(len(buf)))
+    if not need:
+        return None
+    assert need <= len(buf), "form name of %d bytes" % need
+    return buf.value.decode()
+
+
+def row_kernel_forms():
+    """every name row_kernel_form can return"""
+    lib = load()
+    lib.mila_cdna4_row_kernel_forms.restype = C.c_size_t
+    buf = C.create_string_buffer(2048)
+    need = lib.mila_cdna4_row_kernel_forms(buf, C.c_size_t(len(buf)))
+    assert 0 < need <= len(buf), "form list of %d bytes" % need
+    return buf.value.decode().split("+")
+
+
 RADIX_PLAN_FIELDS = ("launches", "k_passes", "p_passes", "scratch_need")
 
 
@@ -663,6 +686,7 @@ EXPORTED = [
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI
 INTERNAL = [
     "tune", "tune_get", "tune_reset", "tune_list", "last_form", "gemm_plan_describe", "attn_decode_plan_describe", "matvec_rows_plan_describe",
+    "row_kernel_form", "row_kernel_forms",
     "decode_engine_debug",
     "selftest_decode", "selftest_wave_reduce", "selftest_mfma_fp8", "stream_copy", "stream_read",
     "attn_decode_split_count", "fused_attn_decode_partials_bf16", "matvec_attn_combine",

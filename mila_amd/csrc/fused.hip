@@ -9,6 +9,7 @@
 #include "fp8_quant.h"
 #include "rms_common.h"
 #include "rope_common.h"
+#include "row_kernel_plan.h"
 
 namespace mila {
 
@@ -203,12 +204,6 @@ __device__ __forceinline__ void qkv_post_body(const QkvPostParams& p, const KvFp
 __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostParams p) { qkv_post_body<false>(p, KvFp8Rows{}); }
 // the same launch shape; Kc / Vc of `p` are unused
 __global__ __launch_bounds__(256) void qkv_post_kvfp8_kernel(const QkvPostParams p, const KvFp8Rows d) { qkv_post_body<true>(p, d); }
-
-static int qkv_post_rows_per_wave(int HS)
-{
-    const int hv = HS / 16;
-    return hv <= 32 ? 64 / hv : 1;
-}
 
 }  // namespace mila
 

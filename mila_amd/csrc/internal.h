@@ -32,6 +32,13 @@ MILA_API size_t mila_cdna4_attn_decode_plan_describe(int B, int NH, int NKV, int
  * (csrc/matvec.hip); f32_out = the lm_head launch with the sampler's first stage.  U is the same for every row count: it is part of a row's arithmetic.  Returns the
  * text's size, 0 for what is refused (rows outside 1 .. 4, K beyond 16384 or no multiple of the format's chunk). */
 MILA_API size_t mila_cdna4_matvec_rows_plan_describe(int fmt, int K, int N, int geglu, int f32_out, int rows, char* buf, size_t cap);
+/* which kernel a row entry launches (csrc/row_kernel_plan.h: the host functions the entries switch on), as a name, without running device code.  op = the entry's name
+ * without the prefix: rmsnorm_bf16, rmsnorm_fp32, layernorm_bf16, layernorm_fp32, softmax_fp32, softmax_bf16, fused_tail_norm_bf16, fused_tail_norm_quant_bf16,
+ * quantize_fp8_per_token (dim = K), rope_forward_bf16 (dim = HS), fused_qkv_post[_prefill | _devpos] and fused_qkv_post_kvfp8[_prefill | _devpos] (dim = HS); inner = 1
+ * for the entries that have no inner axis.  Writes e.g. "rmsnorm_block", "layernorm_wave_nv4", "tail_norm_nch3_quant", "quant_token_reread", "qkv_post_hv8"; returns the
+ * text's size, 0 for an unknown entry or a shape the entry refuses.  row_kernel_forms writes every name the first can return, joined by '+'. */
+MILA_API size_t mila_cdna4_row_kernel_form(const char* op, int outer, int dim, int inner, char* buf, size_t cap);
+MILA_API size_t mila_cdna4_row_kernel_forms(char* buf, size_t cap);
 /* The names (tune_list prints them with their values and defaults; each is documented where it is registered):
  *   matvec.rows_per_wave, matvec.chunks_in_flight, matvec.max_workgroups                 0 = the default rule                                         (csrc/matvec.hip)
  *   gemm.force128          1 = always the 128 x 128 register-staged GEMM (A/B against the LDS-DMA kernels)                                           (csrc/gemm_plan.hip)

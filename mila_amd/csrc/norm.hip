@@ -7,12 +7,12 @@
 //              (thread per row there; a wave per row here, online max+sum in one pass).
 #include "common.h"
 #include "rms_common.h"
+#include "row_kernel_plan.h"
+#include "internal.h"
 
 namespace mila {
 
 // ---- RMSNorm ----------------------------------------------------------------------------------
-constexpr int kRmsBlockMaxGroups = 256;   // rows up to 131072 elements through the workgroup-per-row kernel
-
 __global__ __launch_bounds__(256) void rmsnorm_block_kernel(uint16_t* __restrict__ Y, uint16_t* __restrict__ rstd_out,
                                                             const uint16_t* __restrict__ X,
                                                             const uint16_t* __restrict__ w,
@@ -41,8 +41,7 @@ __global__ __launch_bounds__(256) void rmsnorm_block_kernel(uint16_t* __restrict
 //   xn = bf16(rmsnorm(r; next_w))                                         -> XN (when next_w != NULL)
 // replaces RmsNorm + Residual (+ scale) + RmsNorm of Gemma.Block.ixx:339-356 / :287-289; same canonical reductions
 // (rms_rstd_block) and element functions, so the outputs carry the same bits as the unfused launches.
-// One workgroup per row, dim <= 8 * 256 * kTailChunks.
-constexpr int kTailChunks = 4;
+// One workgroup per row, dim <= 8 * 256 * kTailChunks (row_kernel_plan.h).
 // NCH = 16-byte chunks per thread actually needed (ceil(dim / 8 / 256)): a row of 3840 takes 2, not kTailChunks -- the groups a
 // smaller NCH leaves out are exactly the empty ones (g >= G), so the sums and their order do not change
 // QUANT: XN's row is also written as per-token e4m3 (XQ) with its scale (XS) -- the arithmetic of quantize_fp8_per_token_kernel (csrc/quantize.hip) on the values
@@ -400,7 +399,106 @@ __global__ __launch_bounds__(256) void rmsnorm_fp32_kernel(float* __restrict__ Y
 
 using namespace mila;
 
+// ---- which kernel a row entry launches (csrc/internal.h: row_kernel_form) -------------------------------------------------------------
+// every name row_form can return, in the order of the entries; row_kernel_forms lists them
+static const char* const kRowForms[] = {
+    "rmsnorm_wave", "rmsnorm_block", "rmsnorm_strided", "rmsnorm_fp32_vec", "rmsnorm_fp32_scalar",
+    "layernorm_wave_nv1", "layernorm_wave_nv2", "layernorm_wave_nv4", "layernorm_wave_nv8", "layernorm_block", "layernorm_block_fp32",
+    "softmax_wave_fp32", "softmax_wave_bf16",
+    "tail_norm_nch1", "tail_norm_nch2", "tail_norm_nch3", "tail_norm_nch4",
+    "tail_norm_nch1_quant", "tail_norm_nch2_quant", "tail_norm_nch3_quant", "tail_norm_nch4_quant",
+    "quant_token_nch2", "quant_token_nch4", "quant_token_nch8", "quant_token_reread",
+    "rope_vec", "rope_pair",
+    "qkv_post_hv1", "qkv_post_hv2", "qkv_post_hv4", "qkv_post_hv8", "qkv_post_hv16", "qkv_post_hv32", "qkv_post_wave",
+    "qkv_post_kvfp8_hv4", "qkv_post_kvfp8_hv8", "qkv_post_kvfp8_hv16", "qkv_post_kvfp8_hv32",
+};
+
+// the form of entry `op` at a shape, from the plan functions the entries launch from (row_kernel_plan.h); false = no such entry, or a shape the entry refuses
+static bool row_form(const char* op, int outer, int dim, int inner, char* out, size_t n)
+{
+    if (outer <= 0 || dim <= 0 || inner <= 0) return false;
+    const bool pow2 = (dim & (dim - 1)) == 0;
+    if (!strcmp(op, "rmsnorm_bf16"))
+    {
+        const RmsForm f = plan_rmsnorm_bf16(dim, inner);
+        snprintf(out, n, "%s", f == RmsForm::Wave ? "rmsnorm_wave" : f == RmsForm::Block ? "rmsnorm_block" : "rmsnorm_strided");
+    }
+    else if (!strcmp(op, "rmsnorm_fp32")) snprintf(out, n, "%s", plan_rmsnorm_fp32_vec(dim, inner) ? "rmsnorm_fp32_vec" : "rmsnorm_fp32_scalar");
+    else if (!strcmp(op, "layernorm_bf16"))
+    {
+        if (inner != 1) return false;
+        const int nv = plan_layernorm_bf16(dim);
+        if (nv) snprintf(out, n, "layernorm_wave_nv%d", nv);
+        else snprintf(out, n, "layernorm_block");
+    }
+    else if (!strcmp(op, "layernorm_fp32"))
+    {
+        if (inner != 1) return false;
+        snprintf(out, n, "layernorm_block_fp32");
+    }
+    else if (!strcmp(op, "softmax_fp32")) snprintf(out, n, "softmax_wave_fp32");
+    else if (!strcmp(op, "softmax_bf16")) snprintf(out, n, "softmax_wave_bf16");
+    else if (!strcmp(op, "fused_tail_norm_bf16") || !strcmp(op, "fused_tail_norm_quant_bf16"))
+    {
+        if (inner != 1 || dim % 8 != 0 || dim <= 1024 || dim > 8 * 256 * kTailChunks) return false;
+        snprintf(out, n, "tail_norm_nch%d%s", plan_tail_norm(dim), strstr(op, "quant") ? "_quant" : "");
+    }
+    else if (!strcmp(op, "quantize_fp8_per_token"))
+    {
+        if (inner != 1 || dim % 8 != 0) return false;
+        const int nch = plan_quantize_per_token(dim);
+        if (nch) snprintf(out, n, "quant_token_nch%d", nch);
+        else snprintf(out, n, "quant_token_reread");
+    }
+    else if (!strcmp(op, "rope_forward_bf16"))
+    {
+        if (inner != 1 || dim % 2 != 0) return false;
+        snprintf(out, n, "%s", plan_rope_vec(dim) ? "rope_vec" : "rope_pair");
+    }
+    else if (!strcmp(op, "fused_qkv_post") || !strcmp(op, "fused_qkv_post_prefill") || !strcmp(op, "fused_qkv_post_devpos"))
+    {
+        if (inner != 1 || !pow2 || dim < 16 || dim > 1024) return false;
+        const int hv = plan_qkv_post_hv(dim);
+        if (hv) snprintf(out, n, "qkv_post_hv%d", hv);
+        else snprintf(out, n, "qkv_post_wave");
+    }
+    else if (!strcmp(op, "fused_qkv_post_kvfp8") || !strcmp(op, "fused_qkv_post_kvfp8_prefill") || !strcmp(op, "fused_qkv_post_kvfp8_devpos"))
+    {
+        if (inner != 1 || !pow2 || dim < 64 || dim > 512) return false;
+        snprintf(out, n, "qkv_post_kvfp8_hv%d", plan_qkv_post_hv(dim));
+    }
+    else return false;
+    return true;
+}
+
+static size_t copy_text(const char* text, char* buf, size_t cap)
+{
+    const size_t need = strlen(text) + 1;
+    if (buf && cap)
+    {
+        const size_t k = need <= cap ? need - 1 : cap - 1;
+        memcpy(buf, text, k);
+        buf[k] = 0;
+    }
+    return need;
+}
+
 extern "C" {
+
+size_t mila_cdna4_row_kernel_form(const char* op, int outer, int dim, int inner, char* buf, size_t cap)
+{
+    char name[64];
+    if (!op || !row_form(op, outer, dim, inner, name, sizeof(name))) return 0;
+    return copy_text(name, buf, cap);
+}
+
+size_t mila_cdna4_row_kernel_forms(char* buf, size_t cap)
+{
+    char text[1024];
+    size_t at = 0;
+    for (const char* f : kRowForms) at += (size_t)snprintf(text + at, sizeof(text) - at, "%s%s", at ? "+" : "", f);
+    return copy_text(text, buf, cap);
+}
 
 int mila_cdna4_rmsnorm_bf16(uint16_t* Y, uint16_t* rstd, const uint16_t* X, const uint16_t* w, const uint16_t* b,
                             int outer, int inner, int dim, float eps, float w_offset, mila_stream_t stream)
@@ -409,14 +507,12 @@ int mila_cdna4_rmsnorm_bf16(uint16_t* Y, uint16_t* rstd, const uint16_t* X, cons
     MILA_REQUIRE(outer > 0 && dim > 0 && inner > 0, "rmsnorm_bf16: outer/inner/dim must be positive (%d,%d,%d)", outer, inner, dim);
     MILA_REQUIRE(!(b && !w), "rmsnorm_bf16: bias without weight is not a reference configuration");
     hipStream_t s = as_stream(stream);
-    if (inner == 1 && dim % 8 == 0)
-    {
-        if (dim > 1024 && dim <= kRmsBlockMaxGroups * 512)
-            hipLaunchKernelGGL(rmsnorm_block_kernel, dim3(outer), dim3(256), 0, s, Y, rstd, X, w, b, dim, eps, w_offset);
-        else
-            hipLaunchKernelGGL(rmsnorm_wave_kernel, dim3(ceil_div(outer, 4)), dim3(256), 0, s, Y, rstd, X, w, b, outer,
-                               dim, eps, w_offset);
-    }
+    const RmsForm form = plan_rmsnorm_bf16(dim, inner);
+    if (form == RmsForm::Block)
+        hipLaunchKernelGGL(rmsnorm_block_kernel, dim3(outer), dim3(256), 0, s, Y, rstd, X, w, b, dim, eps, w_offset);
+    else if (form == RmsForm::Wave)
+        hipLaunchKernelGGL(rmsnorm_wave_kernel, dim3(ceil_div(outer, 4)), dim3(256), 0, s, Y, rstd, X, w, b, outer,
+                           dim, eps, w_offset);
     else
     {
         const int64_t slices = (int64_t)outer * inner;
@@ -436,7 +532,7 @@ int mila_cdna4_rmsnorm_fp32(float* Y, float* rstd, const float* X, const float* 
     const int64_t slices = (int64_t)outer * inner;
     MILA_REQUIRE(slices < (1ll << 31), "rmsnorm_fp32: too many slices");
     hipStream_t s = as_stream(stream);
-    if (inner == 1 && dim % 4 == 0)
+    if (plan_rmsnorm_fp32_vec(dim, inner))
         hipLaunchKernelGGL(rmsnorm_fp32_kernel<true>, dim3(ceil_div(slices, 4)), dim3(256), 0, s, Y, rstd, X, w, b, (int)slices, dim, inner, eps, w_offset);
     else
         hipLaunchKernelGGL(rmsnorm_fp32_kernel<false>, dim3(ceil_div(slices, 4)), dim3(256), 0, s, Y, rstd, X, w, b, (int)slices, dim, inner, eps, w_offset);
@@ -449,8 +545,8 @@ int mila_cdna4_fused_tail_norm_quant_bf16(uint16_t* R, uint16_t* XN, uint8_t* XQ
     MILA_REQUIRE(R && XN && XQ && XS && A && RES && post_w && next_w, "fused_tail_norm_quant_bf16: null pointer");
     MILA_REQUIRE(rows > 0 && dim > 0, "fused_tail_norm_quant_bf16: rows/dim must be positive (%d,%d)", rows, dim);
     MILA_REQUIRE(dim % 8 == 0 && dim > 1024 && dim <= 8 * 256 * kTailChunks, "fused_tail_norm_quant_bf16: dim=%d must be a multiple of 8 in (1024, %d]", dim, 8 * 256 * kTailChunks);
-    const int nch = (dim / 8 + 255) / 256;
-    if (nch <= 1) hipLaunchKernelGGL((tail_norm_kernel<1, true>), dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, XQ, XS);
+    const int nch = plan_tail_norm(dim);
+    if (nch == 1) hipLaunchKernelGGL((tail_norm_kernel<1, true>), dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, XQ, XS);
     else if (nch == 2) hipLaunchKernelGGL((tail_norm_kernel<2, true>), dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, XQ, XS);
     else if (nch == 3) hipLaunchKernelGGL((tail_norm_kernel<3, true>), dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, XQ, XS);
     else hipLaunchKernelGGL((tail_norm_kernel<4, true>), dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, XQ, XS);
@@ -464,8 +560,8 @@ int mila_cdna4_fused_tail_norm_bf16(uint16_t* R, uint16_t* XN, const uint16_t* A
     MILA_REQUIRE((XN == nullptr) == (next_w == nullptr), "fused_tail_norm_bf16: XN and next_w go together");
     MILA_REQUIRE(rows > 0 && dim > 0, "fused_tail_norm_bf16: rows/dim must be positive (%d,%d)", rows, dim);
     MILA_REQUIRE(dim % 8 == 0 && dim > 1024 && dim <= 8 * 256 * kTailChunks, "fused_tail_norm_bf16: dim=%d must be a multiple of 8 in (1024, %d]", dim, 8 * 256 * kTailChunks);
-    const int nch = (dim / 8 + 255) / 256;
-    if (nch <= 1) hipLaunchKernelGGL(tail_norm_kernel<1>, dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, (uint8_t*)nullptr, (float*)nullptr);
+    const int nch = plan_tail_norm(dim);
+    if (nch == 1) hipLaunchKernelGGL(tail_norm_kernel<1>, dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, (uint8_t*)nullptr, (float*)nullptr);
     else if (nch == 2) hipLaunchKernelGGL(tail_norm_kernel<2>, dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, (uint8_t*)nullptr, (float*)nullptr);
     else if (nch == 3) hipLaunchKernelGGL(tail_norm_kernel<3>, dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, (uint8_t*)nullptr, (float*)nullptr);
     else hipLaunchKernelGGL(tail_norm_kernel<4>, dim3(rows), dim3(256), 0, as_stream(stream), R, XN, A, RES, post_w, next_w, dim, post_scale, eps, (uint8_t*)nullptr, (float*)nullptr);
@@ -477,13 +573,13 @@ int mila_cdna4_layernorm_bf16(uint16_t* Y, float* mean, float* rstd, const uint1
 {
     MILA_REQUIRE(Y && X, "layernorm_bf16: null pointer");
     MILA_REQUIRE(outer > 0 && dim > 0, "layernorm_bf16: outer/dim must be positive (%d,%d)", outer, dim);
-    if (dim % 8 == 0 && dim <= 4096)
+    if (const int nv = plan_layernorm_bf16(dim))
     {
-        const int nv = (dim / 8 + 63) / 64, blocks = ceil_div(outer, 4);
+        const int blocks = ceil_div(outer, 4);
         hipStream_t s = as_stream(stream);
-        if (nv <= 1) hipLaunchKernelGGL(layernorm_wave_bf16_kernel<1>, dim3(blocks), dim3(256), 0, s, Y, mean, rstd, X, w, b, outer, dim, eps);
+        if (nv == 1) hipLaunchKernelGGL(layernorm_wave_bf16_kernel<1>, dim3(blocks), dim3(256), 0, s, Y, mean, rstd, X, w, b, outer, dim, eps);
         else if (nv == 2) hipLaunchKernelGGL(layernorm_wave_bf16_kernel<2>, dim3(blocks), dim3(256), 0, s, Y, mean, rstd, X, w, b, outer, dim, eps);
-        else if (nv <= 4) hipLaunchKernelGGL(layernorm_wave_bf16_kernel<4>, dim3(blocks), dim3(256), 0, s, Y, mean, rstd, X, w, b, outer, dim, eps);
+        else if (nv == 4) hipLaunchKernelGGL(layernorm_wave_bf16_kernel<4>, dim3(blocks), dim3(256), 0, s, Y, mean, rstd, X, w, b, outer, dim, eps);
         else hipLaunchKernelGGL(layernorm_wave_bf16_kernel<8>, dim3(blocks), dim3(256), 0, s, Y, mean, rstd, X, w, b, outer, dim, eps);
         MILA_LAUNCH_CHECK("layernorm_bf16");
     }

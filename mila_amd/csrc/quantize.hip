@@ -9,6 +9,7 @@
 // arithmetic on the fp32 bits (RNE at mantissa bit 20, saturate to 0x7e) so it does not depend on
 // the FP8 hardware-convert overflow mode.
 #include "gemm_plan.h"
+#include "row_kernel_plan.h"
 #include "fp8_quant.h"      // the e4m3 encoders and the row-scale rule (shared with the quantizing KV-cache append)
 
 namespace mila {
@@ -284,10 +285,10 @@ int mila_cdna4_quantize_fp8_per_token(uint8_t* dst, float* scales, const uint16_
 {
     MILA_REQUIRE(dst && scales && src, "quantize_fp8_per_token: null pointer");
     MILA_REQUIRE(M > 0 && K > 0 && K % 8 == 0, "quantize_fp8_per_token: bad sizes (M=%d K=%d)", M, K);
-    const int nch = (K / 8 + 255) / 256;
-    if (nch <= 2) hipLaunchKernelGGL(quantize_fp8_per_token_kernel<2>, dim3(M), dim3(256), 0, as_stream(stream), dst, scales, src, K);
-    else if (nch <= 4) hipLaunchKernelGGL(quantize_fp8_per_token_kernel<4>, dim3(M), dim3(256), 0, as_stream(stream), dst, scales, src, K);
-    else if (nch <= 8) hipLaunchKernelGGL(quantize_fp8_per_token_kernel<8>, dim3(M), dim3(256), 0, as_stream(stream), dst, scales, src, K);
+    const int nch = plan_quantize_per_token(K);
+    if (nch == 2) hipLaunchKernelGGL(quantize_fp8_per_token_kernel<2>, dim3(M), dim3(256), 0, as_stream(stream), dst, scales, src, K);
+    else if (nch == 4) hipLaunchKernelGGL(quantize_fp8_per_token_kernel<4>, dim3(M), dim3(256), 0, as_stream(stream), dst, scales, src, K);
+    else if (nch == 8) hipLaunchKernelGGL(quantize_fp8_per_token_kernel<8>, dim3(M), dim3(256), 0, as_stream(stream), dst, scales, src, K);
     else hipLaunchKernelGGL(quantize_fp8_per_token_kernel<0>, dim3(M), dim3(256), 0, as_stream(stream), dst, scales, src, K);
     MILA_LAUNCH_CHECK("quantize_fp8_per_token");
 }

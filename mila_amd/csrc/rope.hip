@@ -9,6 +9,7 @@
 //   rotation: OPS/Encodings/Rope/Kernels/Rope.Bf16.cu:28-118: r0 = x0 c - x1 s, r1 = x0 s + x1 c.
 #include "common.h"
 #include "rope_common.h"
+#include "row_kernel_plan.h"
 
 namespace mila {
 
@@ -102,7 +103,7 @@ int mila_cdna4_rope_forward_bf16(uint16_t* Qout, uint16_t* Kout, const uint16_t*
                  "rope_forward_bf16: positions [%d,%d) exceed the cache length %d", pos_offset, pos_offset + T, max_seq);
     const int half = HS / 2;
     hipStream_t s = as_stream(stream);
-    if (HS % 16 != 0)
+    if (!plan_rope_vec(HS))
     {
         for (int which = 0; which < 2; ++which)
         {
