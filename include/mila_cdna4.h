@@ -939,6 +939,51 @@ MILA_API int mila_cdna4_token_automaton_step(float* eff, size_t eff_stride, cons
                                              int C, int32_t* state_dev, const int32_t* token_dev, const int32_t* active_dev, uint32_t* ticket_dev, int rows, int vocab,
                                              mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The constrained chain step (ABI 4, additive; csrc/sampling.hip): the bias table and the automaton in a chain step (sample_*_chain_accept above), so that a constrained
+ * request can verify drafts -- in particular the tokens its automaton FORCES (a state that allows one token: the successor is known before the model runs).
+ *
+ * STATE SEMANTICS IN A CHAIN STEP.  state_dev[0] is the state after every token sampled so far, tok[0] included, as in the one-row step.  Row t was fed tok[t]; its
+ * sample obeys q_t:  q_0 = state_dev[0],  q_t = next[q_{t-1} * C + class_of[tok[t]]],  and a draft that is FORBIDDEN in q_{t-1} or lies outside [0, vocab) leaves
+ * q_t = q_{t-1} (the step entry's rule).  Such a draft is never accepted -- row t - 1 never samples it -- so the rows behind it only need a well-defined table.
+ *
+ * token_automaton_chain_compose: ONE launch, the first node of the step.  For t = 1 .. T - 1 (the row in blockIdx.y) eff[t * eff_stride + i] is composed for q_t by
+ *     compose's rule from base[t * base_stride + i] (base == NULL: 0.0f; base_stride == 0: one shared table), and q_0 .. q_{T-1} are stored to chain_states[0 .. T - 1]
+ *     (int32, device).  Row 0 of eff is NOT touched: every step leaves it composed for state_dev[0] (compose at the start of a request, step / chain_step behind every
+ *     tail).  Every workgroup walks its row's at most 3 dependent lookups itself; the launch stores nothing that it reads (state_dev and tok_dev are read only), so it
+ *     takes no ticket.  The walk is compose's, 16-byte path and scalar fallback included.
+ * token_automaton_chain_step: ONE launch behind the accept tail, which left result[0] = n (the accepted count, 1 .. T; any other value is read as 1) and tok[0] = the
+ *     last accepted sample.  It is step on row 0 with the state read from chain_states[n - 1] and the token from tok[0]: state_dev[0] = s', eff row 0 composed for s'
+ *     from base row 0.  ticket_dev: one uint32 word, 0 between launches, step's discipline (every workgroup reads before it draws; the last ticket's holder stores).
+ *     It touches row 0 only: eff_stride and base_stride are the chain's (checked as chain_compose checks them) and decide no more than the 16-byte path.
+ * Refused before any device work (MILA_E_INVALID_ARGUMENT): a null eff, class_of, next, state_dev, tok_dev or chain_states (chain_step: result_dev, ticket_dev); T
+ * outside 2 .. 4; the shape limits of the image; an eff_stride below vocab; a base_stride from 1 to vocab - 1.
+ *
+ * sample_radix_biased_chain_accept_fp32 is sample_radix_chain_accept_fp32 plus `bias, bias_stride`; sample_argmax_biased_chain_accept_fp32 is the greedy chain tail from
+ * the LOGITS: the two launches of sample_argmax_biased_rows_advance_fp32 (the biased first stage over T rows, one final), the final being sample_argmax_chain_accept's.
+ * Row t's sample is the token the one-row biased entry (sample_radix_biased_fp32 with r = draws[t]; sample_argmax_biased_fp32) returns on row t's logits with the table
+ * bias + t * bias_stride; the acceptance rule, result, tok[0] and the position word are the unbiased chain entry's.  bias_stride 0 = one table shared by all rows (a
+ * request's bias table); bias_stride >= vocab = one per row (the automaton's eff rows); 1 .. vocab - 1 is refused.  A token whose entry is -inf is never returned;
+ * caller's contract: every row's table has a finite entry.  The bias rides in the scale launch (radix) or the first stage (greedy): only the tail differs from the rows
+ * entries, and it is the unbiased chain tail.  radix: bias == NULL launches exactly sample_radix_chain_accept_fp32.  greedy: bias is required -- without one the chain's
+ * partials come from the lm_head launch and sample_argmax_chain_accept is the whole tail.  scratch: sample_radix_rows_scratch_bytes(T, vocab) / T *
+ * sample_scratch_bytes().  NO PENALTIES AND NO MIN-P IN A CHAIN: row t would need the token table plus the drafts 1 .. t, so these entries take no filters and no
+ * table, and a request with such settings stays on the one-row step.  Neither entry writes logits or bias.
+ * Refused before any device work: what the unbiased chain entry refuses (greedy: a null tok, result, logits, bias or position_dev; T outside 2 .. 4; vocab <= 0;
+ * logits_stride < vocab; a short scratch, MILA_E_SCRATCH_TOO_SMALL), the stride rule, a bias pointer that is not 4-byte aligned. */
+MILA_API int mila_cdna4_token_automaton_chain_compose(float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of,
+                                                      const uint16_t* next, int S, int C, const int32_t* state_dev, const int32_t* tok_dev, int32_t* chain_states, int T,
+                                                      int vocab, mila_stream_t stream);
+MILA_API int mila_cdna4_token_automaton_chain_step(float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next,
+                                                   int S, int C, int32_t* state_dev, const int32_t* tok_dev, const int32_t* chain_states, const int32_t* result_dev, int T,
+                                                   uint32_t* ticket_dev, int vocab, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_biased_chain_accept_fp32(int32_t* tok, int32_t* result, const float* logits, size_t logits_stride, int T, int vocab, float softcap,
+                                                              float temperature, int top_k, float top_p, const float* draws, const float* bias, size_t bias_stride,
+                                                              void* scratch, size_t scratch_bytes, int32_t* position_dev, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_biased_chain_accept_fp32(int32_t* tok, int32_t* result, const float* logits, size_t logits_stride, int T, int vocab, float softcap,
+                                                               const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* position_dev,
+                                                               mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

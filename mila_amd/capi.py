@@ -136,6 +136,11 @@ def load():
     main.mila_cdna4_token_automaton_bytes.restype = z
     main.mila_cdna4_token_automaton_compose.argtypes = [p, z, p, z, p, p, i, i, p, i, i, p]                       # eff eff_stride base base_stride | class_of next S C | state_dev | rows vocab
     main.mila_cdna4_token_automaton_step.argtypes = [p, z, p, z, p, p, i, i, p, p, p, p, i, i, p]                 # ... state_dev token_dev active_dev ticket_dev | rows vocab
+    # the constrained chain step: the automaton's chain forms and the chain tails with a bias
+    main.mila_cdna4_token_automaton_chain_compose.argtypes = [p, z, p, z, p, p, i, i, p, p, p, i, i, p]           # ... state_dev tok_dev chain_states | T vocab
+    main.mila_cdna4_token_automaton_chain_step.argtypes = [p, z, p, z, p, p, i, i, p, p, p, p, i, p, i, p]        # ... state_dev tok_dev chain_states result_dev T ticket_dev | vocab
+    main.mila_cdna4_sample_radix_biased_chain_accept_fp32.argtypes = [p, p, p, z, i, i, f, f, i, f, p, p, z, p, z, p, p]   # ... top_p | draws | bias bias_stride | scratch bytes | position_dev
+    main.mila_cdna4_sample_argmax_biased_chain_accept_fp32.argtypes = [p, p, p, z, i, i, f, p, z, p, z, p, p]     # tok result logits logits_stride | T vocab softcap | bias bias_stride | scratch bytes | position_dev
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -557,6 +562,39 @@ def token_automaton_step(eff, base, class_of, next_table, state_dev, token_dev, 
     call("token_automaton_step", eff, es, base, bs, class_of, next_table, S, Cn, state_dev, token_dev, active_dev, ticket_dev, rows, V)
 
 
+def _automaton_chain_head(eff, base, class_of, next_table):
+    """the chain forms: eff float32 [rows >= T, eff_stride] (the first class_of.numel() floats of a row are its table), base None, [vocab] or [rows, base_stride]"""
+    assert class_of.element_size() == 2 and next_table.element_size() == 2 and next_table.dim() == 2 and eff.dim() == 2
+    base_stride = 0 if base is None or base.dim() == 1 else int(base.shape[-1])
+    return int(class_of.numel()), C.c_size_t(int(eff.shape[1])), C.c_size_t(base_stride), int(next_table.shape[0]), int(next_table.shape[1])
+
+
+def token_automaton_chain_compose(eff, base, class_of, next_table, state_dev, tok_dev, chain_states, T):
+    """rows 1 .. T - 1 of eff composed for the states behind the drafts tok[1 ..], the states q_0 .. q_{T-1} to chain_states; row 0 and the state word stay"""
+    V, es, bs, S, Cn = _automaton_chain_head(eff, base, class_of, next_table)
+    call("token_automaton_chain_compose", eff, es, base, bs, class_of, next_table, S, Cn, state_dev, tok_dev, chain_states, int(T), V)
+
+
+def token_automaton_chain_step(eff, base, class_of, next_table, state_dev, tok_dev, chain_states, result_dev, T, ticket_dev):
+    """behind the accept tail: the state word = chain_states[result[0] - 1] advanced by tok[0], eff row 0 composed for it"""
+    V, es, bs, S, Cn = _automaton_chain_head(eff, base, class_of, next_table)
+    call("token_automaton_chain_step", eff, es, base, bs, class_of, next_table, S, Cn, state_dev, tok_dev, chain_states, result_dev, int(T), ticket_dev, V)
+
+
+def sample_radix_biased_chain_accept(tok, result, logits, softcap, temperature, top_k, top_p, draws, bias, scratch, position_dev, vocab=None, bias_stride=None):
+    """sample_radix_chain_accept with the bias tables: [T, stride] (row t's is bias[t]), [vocab] (shared: bias_stride 0) or None (the unbiased entry)"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_biased_chain_accept_fp32", tok, result, logits, stride, int(logits.shape[0]), V, float(softcap), float(temperature), int(top_k), float(top_p), draws,
+         bias, _bias_stride(bias, bias_stride), scratch, _nbytes(scratch), position_dev)
+
+
+def sample_argmax_biased_chain_accept(tok, result, logits, softcap, bias, scratch, position_dev, vocab=None, bias_stride=None):
+    """the greedy chain tail from the logits: row t's argmax over the capped logits plus its bias table, then the chain's acceptance rule"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_argmax_biased_chain_accept_fp32", tok, result, logits, stride, int(logits.shape[0]), V, float(softcap), bias, _bias_stride(bias, bias_stride), scratch,
+         _nbytes(scratch), position_dev)
+
+
 TOKEN_LOGPROBS_MAX_TOP = 20
 
 
@@ -681,6 +719,7 @@ EXPORTED = [
     "sample_radix_biased_fp32", "sample_radix_biased_advance_fp32", "sample_radix_biased_rows_fp32", "sample_radix_biased_rows_advance_fp32",
     "sample_argmax_biased_fp32", "sample_argmax_biased_advance_fp32", "sample_argmax_biased_rows_advance_fp32",
     "token_automaton_bytes", "token_automaton_compose", "token_automaton_step",
+    "token_automaton_chain_compose", "token_automaton_chain_step", "sample_radix_biased_chain_accept_fp32", "sample_argmax_biased_chain_accept_fp32",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

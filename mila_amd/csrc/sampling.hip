@@ -221,41 +221,24 @@ __global__ __launch_bounds__(256) void token_bias_set_kernel(float* __restrict__
 // vocab % 4 tail or for everything when a pointer or stride is not aligned; the state's row of `next` (at most 128 KB) is gathered through the cache.
 constexpr uint16_t kAutomatonForbidden = 0xFFFFu;
 
-template <bool STEP>
-__global__ __launch_bounds__(256) void token_automaton_kernel(float* __restrict__ eff, size_t eff_stride, const float* __restrict__ base, size_t base_stride,
-                                                              const uint16_t* __restrict__ class_of, const uint16_t* __restrict__ next, int S, int C, int32_t* state_dev,
-                                                              const int32_t* __restrict__ token_dev, const int32_t* __restrict__ active_dev, uint32_t* ticket_dev, int vocab,
-                                                              int vec)
+// the state behind token t in state s: next[s * C + class_of[t]], and s itself where that is FORBIDDEN or t lies outside [0, vocab)
+__device__ __forceinline__ int automaton_advance(int s, int t, const uint16_t* __restrict__ class_of, const uint16_t* __restrict__ next, int S, int C, int vocab)
 {
-    const int b = blockIdx.y;
-    if (STEP && active_dev && active_dev[b] == 0) return;      // (uniform over the row's workgroups: none of them takes a ticket)
-    __shared__ int s_state;
-    if (threadIdx.x == 0)
+    int s2 = s;
+    if (t >= 0 && t < vocab)
     {
-        int s = __hip_atomic_load(state_dev + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)s >= (unsigned)S) s = 0;      // (never with a state the host set: keeps every read of `next` inside the image)
-        if (STEP)
-        {
-            const int t = token_dev[b];
-            int s2 = s;
-            if (t >= 0 && t < vocab)
-            {
-                const unsigned c = class_of[t];
-                const uint16_t n = c < (unsigned)C ? next[(size_t)s * C + c] : kAutomatonForbidden;
-                if (n != kAutomatonForbidden && n < S) s2 = n;
-            }
-            const unsigned ticket = __hip_atomic_fetch_add(ticket_dev + b, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            if (ticket == gridDim.x - 1)
-            {
-                __hip_atomic_store(state_dev + b, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(ticket_dev + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            s = s2;
-        }
-        s_state = s;
+        const unsigned c = class_of[t];
+        const uint16_t n = c < (unsigned)C ? next[(size_t)s * C + c] : kAutomatonForbidden;
+        if (n != kAutomatonForbidden && n < S) s2 = n;
     }
-    __syncthreads();
-    const uint16_t* __restrict__ row = next + (size_t)s_state * C;
+    return s2;
+}
+
+// the walk of row b by the workgroups blockIdx.x of gridDim.x: e[i] = x[i] (0 without a base table) where row `state` of `next` allows token i, else -inf
+__device__ __forceinline__ void automaton_walk(float* __restrict__ eff, size_t eff_stride, const float* __restrict__ base, size_t base_stride, int b,
+                                               const uint16_t* __restrict__ class_of, const uint16_t* __restrict__ next, int state, int C, int vocab, int vec)
+{
+    const uint16_t* __restrict__ row = next + (size_t)state * C;
     float* __restrict__ e = eff + (size_t)b * eff_stride;
     const float* __restrict__ x = base ? base + (size_t)b * base_stride : nullptr;
     // (a class outside [0, C) -- never from a validated image -- reads entry 0 and is forbidden: no branch in front of the gathers, so the four of a lane fly together)
@@ -280,6 +263,89 @@ __global__ __launch_bounds__(256) void token_automaton_kernel(float* __restrict_
         const float xi = x ? x[i] : 0.0f;
         e[i] = keep(c, entry(c)) ? xi : -INFINITY;
     }
+}
+
+template <bool STEP>
+__global__ __launch_bounds__(256) void token_automaton_kernel(float* __restrict__ eff, size_t eff_stride, const float* __restrict__ base, size_t base_stride,
+                                                              const uint16_t* __restrict__ class_of, const uint16_t* __restrict__ next, int S, int C, int32_t* state_dev,
+                                                              const int32_t* __restrict__ token_dev, const int32_t* __restrict__ active_dev, uint32_t* ticket_dev, int vocab,
+                                                              int vec)
+{
+    const int b = blockIdx.y;
+    if (STEP && active_dev && active_dev[b] == 0) return;      // (uniform over the row's workgroups: none of them takes a ticket)
+    __shared__ int s_state;
+    if (threadIdx.x == 0)
+    {
+        int s = __hip_atomic_load(state_dev + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)s >= (unsigned)S) s = 0;      // (never with a state the host set: keeps every read of `next` inside the image)
+        if (STEP)
+        {
+            const int t = token_dev[b];
+            const int s2 = automaton_advance(s, t, class_of, next, S, C, vocab);
+            const unsigned ticket = __hip_atomic_fetch_add(ticket_dev + b, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            if (ticket == gridDim.x - 1)
+            {
+                __hip_atomic_store(state_dev + b, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(ticket_dev + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            s = s2;
+        }
+        s_state = s;
+    }
+    __syncthreads();
+    automaton_walk(eff, eff_stride, base, base_stride, b, class_of, next, s_state, C, vocab, vec);
+}
+
+// ---- the automaton in a chain step (mila_cdna4.h: token automaton, chain forms).  Row t of a chain was fed tok[t], so its sample obeys q_t: q_0 the state word,
+// q_t = automaton_advance(q_{t-1}, tok[t]).  CHAIN COMPOSE, the first node of the step: blockIdx.y + 1 = t in 1 .. T - 1; lane 0 of every workgroup walks the t
+// dependent lookups from the state word itself (the launch stores no word another workgroup reads: no ticket), workgroup 0 of row t stores q_t into chain_states[t]
+// (that of row 1 also q_0 into chain_states[0]), and the row's workgroups write eff row t for q_t.  Row 0 holds the table of q_0 from the launch before.
+__global__ __launch_bounds__(256) void token_automaton_chain_compose_kernel(float* __restrict__ eff, size_t eff_stride, const float* __restrict__ base, size_t base_stride,
+                                                                            const uint16_t* __restrict__ class_of, const uint16_t* __restrict__ next, int S, int C,
+                                                                            const int32_t* __restrict__ state_dev, const int32_t* __restrict__ tok,
+                                                                            int32_t* __restrict__ chain_states, int vocab, int vec)
+{
+    const int t = blockIdx.y + 1;
+    __shared__ int s_state;
+    if (threadIdx.x == 0)
+    {
+        int s = state_dev[0];
+        if ((unsigned)s >= (unsigned)S) s = 0;
+        if (blockIdx.x == 0 && t == 1) chain_states[0] = s;
+        for (int j = 1; j <= t; ++j) s = automaton_advance(s, tok[j], class_of, next, S, C, vocab);
+        if (blockIdx.x == 0) chain_states[t] = s;
+        s_state = s;
+    }
+    __syncthreads();
+    automaton_walk(eff, eff_stride, base, base_stride, t, class_of, next, s_state, C, vocab, vec);
+}
+
+// CHAIN STEP, behind the accept tail: token_automaton_kernel<true> on row 0 with the state q_{n - 1} = chain_states[n - 1] of the last accepted row (n = result[0], the
+// accepted count; outside 1 .. T it reads as 1) and the token tok[0] the accept tail left.  The ticket as in the step kernel: every workgroup reads its words before it
+// draws, the holder of the last ticket stores the state word and zeroes the ticket.
+__global__ __launch_bounds__(256) void token_automaton_chain_step_kernel(float* __restrict__ eff, const float* __restrict__ base, const uint16_t* __restrict__ class_of,
+                                                                         const uint16_t* __restrict__ next, int S, int C, int32_t* state_dev,
+                                                                         const int32_t* __restrict__ tok, const int32_t* __restrict__ chain_states,
+                                                                         const int32_t* __restrict__ result, int T, uint32_t* ticket_dev, int vocab, int vec)
+{
+    __shared__ int s_state;
+    if (threadIdx.x == 0)
+    {
+        int n = result[0];
+        if (n < 1 || n > T) n = 1;
+        int s = chain_states[n - 1];
+        if ((unsigned)s >= (unsigned)S) s = 0;
+        const int s2 = automaton_advance(s, tok[0], class_of, next, S, C, vocab);
+        const unsigned ticket = __hip_atomic_fetch_add(ticket_dev, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket == gridDim.x - 1)
+        {
+            __hip_atomic_store(state_dev, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ticket_dev, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        s_state = s2;
+    }
+    __syncthreads();
+    automaton_walk(eff, 0, base, 0, 0, class_of, next, s_state, C, vocab, vec);
 }
 
 // The acceptance rule of a chain (speculative verification), by one lane: rows 0 .. T - 1 are consecutive positions of ONE sequence, row t fed with tok[t] (tok[0] the
@@ -1253,7 +1319,6 @@ static int run_radix(const RadixCall<T>& c, void* scratch, size_t scratch_bytes,
     MILA_REQUIRE(!adv || adv->draws_size > 0, "%s: draws_size must be positive", who);
     MILA_REQUIRE(!adv || (adv->ring ? adv->ring_size > 0 : adv->ring_size == 0), "%s: ring and ring_size go together", who);
     MILA_REQUIRE(c.mode != kRowsChain || !flt, "%s: the chain tail takes no filters", who);
-    MILA_REQUIRE(c.mode != kRowsChain || !c.bias, "%s: the chain tail takes no bias", who);
     if (const int rc = check_bias(c.bias, c.bias_stride, c.rows, c.vocab, who)) return rc;
     const RadixPlan d = plan_radix(c.vocab, c.top_k, c.top_p, flt && flt->table, flt ? flt->min_p : 0.0f, c.bias != nullptr);
     const size_t row_stride = radix_row_stride(c.vocab), need = one ? d.scratch_need : row_stride * (size_t)c.rows;
@@ -1597,6 +1662,75 @@ int mila_cdna4_token_automaton_step(float* eff, size_t eff_stride, const float* 
 {
     return launch_token_automaton(true, eff, eff_stride, base, base_stride, class_of, next, S, C, state_dev, token_dev, active_dev, ticket_dev, rows, vocab, stream,
                                   "token_automaton_step");
+}
+
+// the chain forms: what both check, the 16-byte path's condition (launch_token_automaton's) and the workgroups of a row
+static int chain_automaton_args(const float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next, int S, int C,
+                                int T, int vocab, const char* who, int& vec, int& blocks)
+{
+    MILA_REQUIRE(eff && class_of && next, "%s: null pointer", who);
+    MILA_REQUIRE(T >= 2 && T <= 4, "%s: T=%d rows outside 2 .. 4", who, T);
+    MILA_REQUIRE(automaton_shape_ok(vocab, S, C), "%s: need vocab > 0, 1 <= S, C <= 65535 and S * C * 2 bytes <= 256 MiB", who);
+    MILA_REQUIRE(eff_stride >= (size_t)vocab, "%s: eff_stride must be at least vocab", who);
+    MILA_REQUIRE(!base || base_stride == 0 || base_stride >= (size_t)vocab, "%s: base_stride must be 0 (shared) or at least vocab", who);
+    auto aligned = [](const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    vec = aligned(eff, 16) && eff_stride % 4 == 0 && aligned(class_of, 8) && (!base || (aligned(base, 16) && base_stride % 4 == 0));
+    blocks = (vocab + 1023) / 1024;
+    if (blocks > 256) blocks = 256;
+    return MILA_OK;
+}
+
+int mila_cdna4_token_automaton_chain_compose(float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next, int S,
+                                             int C, const int32_t* state_dev, const int32_t* tok_dev, int32_t* chain_states, int T, int vocab, mila_stream_t stream)
+{
+    const char* who = "token_automaton_chain_compose";
+    int vec = 0, blocks = 0;
+    if (const int rc = chain_automaton_args(eff, eff_stride, base, base_stride, class_of, next, S, C, T, vocab, who, vec, blocks)) return rc;
+    MILA_REQUIRE(state_dev && tok_dev && chain_states, "%s: null pointer", who);
+    hipLaunchKernelGGL(token_automaton_chain_compose_kernel, dim3(blocks, T - 1), dim3(256), 0, as_stream(stream), eff, eff_stride, base, base_stride, class_of, next, S, C,
+                       state_dev, tok_dev, chain_states, vocab, vec);
+    MILA_LAUNCH_CHECK(who);
+}
+
+int mila_cdna4_token_automaton_chain_step(float* eff, size_t eff_stride, const float* base, size_t base_stride, const uint16_t* class_of, const uint16_t* next, int S, int C,
+                                          int32_t* state_dev, const int32_t* tok_dev, const int32_t* chain_states, const int32_t* result_dev, int T,
+                                          uint32_t* ticket_dev, int vocab, mila_stream_t stream)
+{
+    const char* who = "token_automaton_chain_step";
+    int vec = 0, blocks = 0;
+    if (const int rc = chain_automaton_args(eff, eff_stride, base, base_stride, class_of, next, S, C, T, vocab, who, vec, blocks)) return rc;
+    MILA_REQUIRE(state_dev && tok_dev && chain_states && result_dev && ticket_dev, "%s: null pointer", who);
+    hipLaunchKernelGGL(token_automaton_chain_step_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), eff, base, class_of, next, S, C, state_dev, tok_dev, chain_states,
+                       result_dev, T, ticket_dev, vocab, vec);
+    MILA_LAUNCH_CHECK(who);
+}
+
+// the chain tails with a bias (mila_cdna4.h: logit bias, chain forms): row t's table is bias + t * bias_stride
+int mila_cdna4_sample_radix_biased_chain_accept_fp32(int32_t* tok, int32_t* result, const float* logits, size_t logits_stride, int T, int vocab, float softcap,
+                                                     float temperature, int top_k, float top_p, const float* draws, const float* bias, size_t bias_stride, void* scratch,
+                                                     size_t scratch_bytes, int32_t* position_dev, mila_stream_t stream)
+{
+    return call_radix_rows(kRowsChain, logits, logits_stride, tok, T, vocab, softcap, temperature, top_k, top_p, draws, scratch, scratch_bytes, position_dev, nullptr, result,
+                          as_stream(stream), bias ? "sample_radix_biased_chain_accept_fp32" : "sample_radix_chain_accept_fp32", nullptr, bias, bias_stride);
+}
+
+// the greedy chain from the logits: the biased first stage over T rows, then the chain's final.  Without a bias the greedy chain has no first stage of its own (the
+// lm_head launch leaves the partials: sample_argmax_chain_accept), so a bias table is required here, as a table or a bias is in the rows entry.
+int mila_cdna4_sample_argmax_biased_chain_accept_fp32(int32_t* tok, int32_t* result, const float* logits, size_t logits_stride, int T, int vocab, float softcap,
+                                                      const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* position_dev, mila_stream_t stream)
+{
+    const char* who = "sample_argmax_biased_chain_accept_fp32";
+    MILA_REQUIRE(tok && result && logits && bias && position_dev, "%s: null pointer", who);
+    MILA_REQUIRE(T >= 2 && T <= 4, "%s: T=%d rows outside 2 .. 4", who, T);
+    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
+    MILA_REQUIRE(logits_stride >= (size_t)vocab, "%s: logits_stride %zu < vocab %d", who, logits_stride, vocab);
+    if (const int rc = check_bias(bias, bias_stride, T, vocab, who)) return rc;
+    SampleFilter f{};
+    if (const int rc = make_filter(nullptr, nullptr, 0, T, vocab, f, who)) return rc;
+    ArgmaxPartials a;
+    if (const int rc = launch_argmax_partials(logits, logits_stride, T, vocab, softcap, &f, scratch, scratch_bytes, as_stream(stream), who, a, bias, bias_stride)) return rc;
+    hipLaunchKernelGGL(argmax_chain_accept_kernel, dim3(1), dim3(256), 0, as_stream(stream), a.pv, tok, result, position_dev, a.blocks, a.row_floats, T);
+    MILA_LAUNCH_CHECK(who);
 }
 
 int mila_cdna4_sample_radix_biased_fp32(const float* logits, int32_t* token_out, int vocab, float softcap, float temperature, int top_k, float top_p, float r,

@@ -234,6 +234,17 @@ class TokenAutomaton:
         """-> bool [vocab]: the tokens the automaton allows in `state`"""
         return self.next[state, self.class_of] != self.FORBIDDEN
 
+    def forced_tokens(self, banned=()):
+        """TokenAutomaton::forcedTokens -> int32 [num_states]: the ONE token a state allows (a transition, and not in `banned`), else -1.  Such a token is known
+        before the model runs: the speculative loop of generate(speculate_constrained=True) drafts it for free.  Host only."""
+        lib = load()
+        lib.mila_token_automaton_forced_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        ban = np.ascontiguousarray(list(banned), dtype=np.int32)
+        out = np.zeros(self.num_states, dtype=np.int32)
+        areq = self._request()
+        _check(lib.mila_token_automaton_forced_tokens(C.byref(areq), ban.ctypes.data if ban.size else None, int(ban.size), out.ctypes.data))
+        return out
+
     def _request(self):
         return TokenAutomatonRequestC(self.class_of.ctypes.data, self.vocab, self.next.ctypes.data, self.num_states, self.num_classes, self.start)
 
@@ -852,18 +863,21 @@ class GemmaModel:
 
     def generate(self, prompt, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=None, cancel_after=None, draft_hint=None,
                  speculative_sampling=False, logprobs=None, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None,
-                 banned_tokens=(), allowed_tokens=(), min_tokens=0, automaton=None):
+                 banned_tokens=(), allowed_tokens=(), min_tokens=0, automaton=None, speculate_constrained=False):
         """_generate() with the sampling filters (GenerateParams::sampling.min_p / .repetition_penalty / .presence_penalty / .frequency_penalty): the penalties read a
         token table on the device that starts from the whole prompt and counts every generated token; greedy with a penalty = argmax of the adjusted logits; a request
         with any filter set takes the plain loop on a draft_tokens model too.  Log-probabilities are those of the unpenalized logits.  With every filter neutral this
         is _generate(), entry for entry.
         logit_bias ({id: finite value}), banned_tokens, allowed_tokens (a closed answer set; a ban wins) and min_tokens (no stop token among the first min_tokens
         samples) are GenerateParams' fields of those names: one bias table on the device, added to the capped logit by every sampler of the request; a request with
-        any of them takes the plain loop on a draft_tokens model.  Log-probabilities stay those of the unbiased logits.
+        any of them takes the plain loop on a draft_tokens model (unless speculate_constrained is set, below).  Log-probabilities stay those of the unbiased logits.
         automaton (a TokenAutomaton; GenerateParams::automaton): grammar-constrained decoding -- the state advances on the device with every sampled token and the
         samplers see -inf wherever the state forbids a token.  Refused (ValueError, before anything runs): a reachable state with no token that has both a transition
         and a finite bias, and min_tokens > 0 beside an automaton.  The return value gains a last element: the state the request ended in (the state after its last
-        sample, a stop token included)."""
+        sample, a stop token included).
+        speculate_constrained (GenerateParams::speculate_constrained; a draft_tokens model, greedy or speculative_sampling, no penalties / min-p): a request with a bias
+        and / or an automaton takes the speculative loop -- the tokens its automaton forces are drafted for free, the rest by draft_hint / the prompt lookup.  Tokens,
+        finish reason, final state and generator state are the plain loop's; speculation_stats_forced() reports the forced tokens.  Not with cancel_after."""
         f = _filters(min_p, repetition_penalty, presence_penalty, frequency_penalty)
         bias = _bias_request(logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_tokens, max_new_tokens, self.vocab_size())
         if automaton is not None and not isinstance(automaton, TokenAutomaton):
@@ -890,9 +904,14 @@ class GemmaModel:
             areq = automaton._request()
             tail, tail_types = tail + [C.byref(areq)], tail_types + [C.c_void_p]
             spec_entry, plain_entry = lib.mila_gemma_model_generate_spec_automaton, lib.mila_gemma_model_generate_automaton
-        if speculative_sampling or draft_hint is not None:
+        if speculate_constrained:      # the entry with the flag behind the automaton request (None: none)
+            if automaton is None:
+                tail, tail_types = tail + [None], tail_types + [C.c_void_p]
+            tail, tail_types = tail + [1], tail_types + [C.c_int]
+            spec_entry = lib.mila_gemma_model_generate_spec_constrained
+        if speculative_sampling or draft_hint is not None or speculate_constrained:
             if cancel_after is not None:
-                raise ValueError("GemmaModel.generate: draft_hint / speculative_sampling cannot be combined with cancel_after")
+                raise ValueError("GemmaModel.generate: draft_hint / speculative_sampling / speculate_constrained cannot be combined with cancel_after")
             hint = np.ascontiguousarray([] if draft_hint is None else draft_hint, dtype=np.int32)
             stats = (C.c_int64 * 4)()
             spec_entry.argtypes = head_types + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types
@@ -998,6 +1017,15 @@ class GemmaModel:
         out = (C.c_int64 * 4)()
         _check(lib.mila_gemma_model_speculation_stats(self.h, out))
         return dict(zip(("steps", "chain_steps", "drafted", "accepted"), [int(v) for v in out]))
+
+    def speculation_stats_forced(self):
+        """speculation_stats() plus "forced" and "forced_accepted": the drafted tokens that the automaton forced (generate(speculate_constrained=True)) and how many
+        of those were accepted"""
+        lib = load()
+        lib.mila_gemma_model_speculation_stats_forced.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_int64 * 6)()
+        _check(lib.mila_gemma_model_speculation_stats_forced(self.h, out))
+        return dict(zip(("steps", "chain_steps", "drafted", "accepted", "forced", "forced_accepted"), [int(v) for v in out]))
 
     def generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0, logprobs=None, min_p=0.0, repetition_penalty=1.0,
                        presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, banned_tokens=(), allowed_tokens=(), min_tokens=0, automaton=None):

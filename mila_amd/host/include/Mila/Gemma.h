@@ -333,7 +333,7 @@ namespace Mila::Dnn
         void setTokenAutomaton( const TokenAutomaton& a )
         {
             a.validate( cfg_.vocab_size );
-            if ( !token_automaton_ ) token_automaton_ = std::make_unique<Compute::RocmTokenAutomaton>( ctx_, cfg_.vocab_size );
+            if ( !token_automaton_ ) token_automaton_ = std::make_unique<Compute::RocmTokenAutomaton>( ctx_, cfg_.vocab_size, cfg_.draft_tokens );
             token_automaton_->upload( a.class_of.data(), a.next.data(), a.num_states, a.num_classes, a.start );
             automaton_on_ = true;
             token_automaton_->reset( biasValues() );
@@ -707,6 +707,9 @@ namespace Mila::Dnn
         // T - 1 drafted ones -- on the one KV cache: the rows step with the chain attention entry (mila_cdna4.h) in place of the rows attention, ended by
         // sample_argmax_chain_accept.  Row t's logits are bit-identical to decodeFused() at position + t given the same history; the accepted tokens are the greedy
         // ones.  A rejected draft leaves a stale cache row at its position, which the next step there overwrites before anything reads it.
+        // With a bias table and / or a token automaton on (setTokenBias, setTokenAutomaton) the step is the constrained chain step: chain_compose as the first node
+        // (an automaton), the layers, the biased chain tail over the logits (one table at stride 0, or the automaton's rows at stride vocab), chain_step as the last
+        // node ahead of the log-probability launches.  One linear chain on one stream; the graph re-captures once per bias / automaton key.
         // ------------------------------------------------------------------------------------
         dim_t draftTokens() const noexcept { return cfg_.draft_tokens; }
         dim_t maxSeq() const noexcept { return max_seq_; }
@@ -757,6 +760,7 @@ namespace Mila::Dnn
             chain_captured_T_ = T; chain_captured_band_ = band;
             chain_captured_sampling_ = chain_sampling_; chain_captured_draws_ = chain_draws_;
             chain_captured_lp_ = step_lp_;
+            chain_captured_bias_ = bias_on_; chain_captured_automaton_ = automatonKey();
             ++chain_graph_captures_;
         }
         /// capture on first use and whenever T or the live-length bucket changes; does NOT touch the device position word otherwise (the caller's loop owns it)
@@ -764,7 +768,8 @@ namespace Mila::Dnn
         {
             checkChainStep( T, position );
             if ( !chain_graph_exec_ || chain_captured_T_ != T || chain_captured_band_ != bandBucket( position ) || chain_captured_lp_ != step_lp_ ||
-                 !sameSampling( chain_captured_sampling_, chain_sampling_ ) || chain_captured_draws_ != chain_draws_ )
+                 !sameSampling( chain_captured_sampling_, chain_sampling_ ) || chain_captured_draws_ != chain_draws_ ||
+                 chain_captured_bias_ != bias_on_ || chain_captured_automaton_ != automatonKey() )      // (a reset, a table update or an automaton of the same size: the same nodes)
                 captureGraphChain( T, position );
         }
         /// speculative SAMPLING: with `sp` and `draws` set, a chain step verifies the drafts against SAMPLES instead of argmaxes -- the lm_head leaves the logits
@@ -1519,12 +1524,24 @@ namespace Mila::Dnn
         {
             int partials = 0;
             if ( filters_.penalized() ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no penalties (setSamplingFilters)" );
-            if ( bias_on_ ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no bias table (clearTokenBias)" );      // refused rather than silently unbiased
-            if ( automaton_on_ ) throw std::invalid_argument( "GemmaTransformer: the chain step takes no token automaton (clearTokenAutomaton)" );
-            const bool stochastic = chainSamples();
-            enqueueFusedStepRows( T, static_cast<int>( band ), stochastic ? nullptr : &partials, &at );      // stochastic: the lm_head leaves the logits only
+            const bool stochastic = chainSamples(), constrained = bias_on_ || automaton_on_;
             auto& R = *rows_;
-            if ( stochastic )
+            // the constrained chain step (mila_cdna4.h): row t's table is row t of the automaton's effective table, composed here for the state behind the drafts
+            // 1 .. t (row 0 holds the table of the state word from the step before), or the ONE bias table for every row (stride 0)
+            if ( automaton_on_ ) token_automaton_->chainCompose( biasValues(), R.tok->data(), T );
+            const float* tables = samplerBias();
+            const size_t tables_stride = automaton_on_ ? static_cast<size_t>( cfg_.vocab_size ) : 0;
+            enqueueFusedStepRows( T, static_cast<int>( band ), stochastic || constrained ? nullptr : &partials, &at );      // stochastic / constrained: the lm_head leaves the logits only
+            if ( stochastic && constrained )
+                Compute::rocmCheck( mila_cdna4_sample_radix_biased_chain_accept_fp32( R.tok->data(), R.result->data(), R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), T,
+                                                                                      (int)cfg_.vocab_size, cfg_.final_logit_softcapping, chain_sampling_->temperature,
+                                                                                      chain_sampling_->top_k, chain_sampling_->top_p, chain_draws_, tables, tables_stride,
+                                                                                      R.radix_scratch->data(), R.radix_scratch->sizeInBytes(), pos_dev_->data(), ctx_->getStream() ) );
+            else if ( constrained )
+                Compute::rocmCheck( mila_cdna4_sample_argmax_biased_chain_accept_fp32( R.tok->data(), R.result->data(), R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), T,
+                                                                                       (int)cfg_.vocab_size, cfg_.final_logit_softcapping, tables, tables_stride,
+                                                                                       R.sample_scratch->data(), R.sample_scratch->sizeInBytes(), pos_dev_->data(), ctx_->getStream() ) );
+            else if ( stochastic )
                 Compute::rocmCheck( mila_cdna4_sample_radix_chain_accept_fp32( R.tok->data(), R.result->data(), R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), T,
                                                                                (int)cfg_.vocab_size, cfg_.final_logit_softcapping, chain_sampling_->temperature, chain_sampling_->top_k,
                                                                                chain_sampling_->top_p, chain_draws_, R.radix_scratch->data(), R.radix_scratch->sizeInBytes(),
@@ -1532,6 +1549,7 @@ namespace Mila::Dnn
             else
                 Compute::rocmCheck( mila_cdna4_sample_argmax_chain_accept( R.tok->data(), R.result->data(), R.sample_scratch->data(), R.sample_scratch->sizeInBytes(), partials, pos_dev_->data(), T,
                                                                        ctx_->getStream() ) );
+            if ( automaton_on_ ) token_automaton_->chainStep( biasValues(), R.tok->data(), R.result->data(), T );      // the state word and row 0 for the next step, of either kind
             // result = {count, accepted tokens}: row t < count reports result[ 1 + t ] under row t's logits; the rejected rows have no token
             if ( step_lp_ ) lp_op_->forward( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.result->data() + 1, T, step_lp_->top_n, nullptr, R.result->data() );
         }
@@ -2032,12 +2050,12 @@ namespace Mila::Dnn
         std::unique_ptr<Compute::RocmTokenTable> token_table_;
         // logit bias: the table (from the first setTokenBias() on), whether it is on, and what the one-row and the rows graph were captured with
         std::unique_ptr<Compute::RocmTokenBias> token_bias_;
-        bool bias_on_ = false, captured_bias_ = false, rows_captured_bias_ = false;
+        bool bias_on_ = false, captured_bias_ = false, rows_captured_bias_ = false, chain_captured_bias_ = false;
         const float* biasValues() noexcept { return bias_on_ ? token_bias_->data() : nullptr; }
         // token automaton: the device side (from the first setTokenAutomaton() on), whether it is on, and what the one-row graph's step node was captured with
         std::unique_ptr<Compute::RocmTokenAutomaton> token_automaton_;
         bool automaton_on_ = false;
-        std::optional<Compute::RocmTokenAutomaton::Key> captured_automaton_{};
+        std::optional<Compute::RocmTokenAutomaton::Key> captured_automaton_{}, chain_captured_automaton_{};
         std::optional<Compute::RocmTokenAutomaton::Key> automatonKey() const { return automaton_on_ ? std::optional( token_automaton_->key() ) : std::nullopt; }
         /// what the one-row samplers read as their bias table: the automaton's effective table (composed over the bias table) while one is on
         const float* samplerBias() noexcept { return automaton_on_ ? token_automaton_->eff() : biasValues(); }

@@ -18,6 +18,7 @@
 #include <optional>
 #include <random>
 #include <span>
+#include <unordered_map>
 #include <unordered_set>
 #include <memory>
 #include <variant>
@@ -102,7 +103,7 @@ namespace Mila::Dnn
         /// samplers add to the capped logit; include/mila_cdna4.h: logit bias), all empty / 0 by default.  The table is written before the first sample; with
         /// min_tokens > 0 the stop tokens are forbidden until the step that produces sample index min_tokens (the first sampled token is index 0), in front of which
         /// the loop enqueues the restore in stream order -- one small launch, no host round trip, the captured step unchanged.  A request with any of them set takes
-        /// the plain loop on a withDraftTokens model, as the sampling filters do.  generateBatch shares one table among its rows.  Log-probabilities are those of the
+        /// the plain loop on a withDraftTokens model, as the sampling filters do, unless speculate_constrained (below) is set.  generateBatch shares one table among its rows.  Log-probabilities are those of the
         /// unbiased logits.  A request without them clears the network's bias.
         std::vector<std::pair<int32_t, float>> logit_bias{};      ///< id -> finite additive bias, an id at most once
         std::vector<int32_t> banned_tokens{};                     ///< never sampled (a ban wins over an allow)
@@ -113,9 +114,16 @@ namespace Mila::Dnn
         /// finite bias is refused, with its number), uploads it and resets the state before the first sample; every step then ends with one launch that advances the
         /// state by the sampled token and rewrites the table the next sampler reads -- no logits readback, the captured step and the decode-ahead loop stay.  Stop
         /// tokens are ordinary tokens of the automaton.  min_tokens > 0 beside an automaton is refused (a chain of states says the same).  A constrained request takes
-        /// the plain loop on a withDraftTokens model; generateBatch refuses one.  Log-probabilities stay those of the unconstrained logits.  A request without one
+        /// the plain loop on a withDraftTokens model unless speculate_constrained (below) is set; generateBatch refuses one.  Log-probabilities stay those of the unconstrained logits.  A request without one
         /// clears the network's.  lastAutomatonState() reports where the request ended.
         std::shared_ptr<const TokenAutomaton> automaton{};
+        /// Constrained speculative decode (a withDraftTokens model; greedy, or stochastic with speculative_sampling; no penalties and no min-p): a request with a bias
+        /// table and / or an automaton takes the speculative loop instead of the plain one.  The chain step's tail reads row t's table (include/mila_cdna4.h: the
+        /// constrained chain step), and the drafter starts with the tokens the automaton FORCES from the current state (TokenAutomaton::forcedTokens: states that
+        /// allow one token -- drafted at no cost and accepted with certainty), then asks `draft` / the prompt lookup for the rest, cut at the first proposal the
+        /// automaton forbids or whose bias is -inf.  The emitted tokens, the finish reason, the final state and the generator state are the plain loop's.
+        /// Off by default: with it off such a request takes the plain loop, as it always did.
+        bool speculate_constrained = false;
     };
     /// the automaton of a request against its composed bias table (throws invalid_argument; touches no device)
     inline void checkRequestAutomaton( const GenerateParams& params, const TokenBiasPlan& bias_plan, dim_t vocab )
@@ -215,7 +223,8 @@ namespace Mila::Dnn
 
     /// what the last speculative generate() of a withDraftTokens model did (greedy, or stochastic with GenerateParams::speculative_sampling): decode steps in all,
     /// those that were chain steps, the drafter's tokens those carried (padding not counted) and how many of them were accepted
-    struct SpeculationStats { uint64_t steps = 0, chain_steps = 0, drafted = 0, accepted = 0; };
+    /// forced / forced_accepted (GenerateParams::speculate_constrained): the drafted tokens that the automaton forced, and how many of those were accepted
+    struct SpeculationStats { uint64_t steps = 0, chain_steps = 0, drafted = 0, accepted = 0, forced = 0, forced_accepted = 0; };
 
     struct GemmaModelConfig
     {
@@ -746,8 +755,9 @@ namespace Mila::Dnn
             // state is followed on the host from the tokens the loop sees (the device word may be one decode-ahead sample further when the request ends)
             if ( params.automaton ) { net.setTokenAutomaton( *params.automaton ); last_automaton_state_ = params.automaton->start; }
             else net.clearTokenAutomaton();
-            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 && !net_sampling.filtered() && !bias_plan.active && !params.automaton )
-                return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids, greedy );
+            const bool constrained = bias_plan.active || params.automaton;
+            if ( ( greedy || params.speculative_sampling ) && net.draftTokens() > 0 && !net_sampling.filtered() && ( !constrained || params.speculate_constrained ) )
+                return onGeneratingSpeculative( net, prompt, on_token, params, stop, stop_ids, greedy, bias_plan );
             // log-probabilities travel like the tokens: every sample's record lands in slot seq % kSnapshots of a second host-visible ring, written by the two launches
             // behind the sampler -- eagerly for the first token, as the captured step's last nodes afterwards
             if ( params.logprobs )
@@ -842,11 +852,33 @@ namespace Mila::Dnn
         /// Stochastic: the tail of the chain step samples row t at the draw the plain loop would take for that token (peekDraws) and accepts a draft exactly when it
         /// equals that sample, so every token is the plain stochastic loop's token for the same generator state; only the draws of the tokens that were emitted are
         /// taken (consumeDraws), and the request leaves rng_ where the plain loop leaves it.  The one-row steps are the captured stochastic step of the plain path.
+        /// Constrained (GenerateParams::speculate_constrained; bias_plan and the automaton are on the network already): the chain step and the one-row step read the
+        /// request's table, the drafts start with the automaton's forced run, and the sample index decides where min_tokens lets a chain step be taken.
         template<typename TNet>
         GenerateStatus onGeneratingSpeculative( TNet& net, std::span<const int32_t> prompt, const std::function<void( int32_t )>& on_token, const GenerateParams& params,
-                                                const std::atomic<bool>* stop, const std::unordered_set<int32_t>& stop_ids, bool greedy )
+                                                const std::atomic<bool>* stop, const std::unordered_set<int32_t>& stop_ids, bool greedy, const TokenBiasPlan& bias_plan )
         {
             auto* ctx = net.context();
+            // A constrained request (speculate_constrained: a bias table and / or an automaton, set on the network by onGenerating).  The host follows the state from
+            // the tokens it reads back -- this loop has no decode-ahead, so the device word is never behind it, and is ahead of it only where the request ends inside
+            // a chain step's accepted run.  forced[ s ]: the one token state s allows under the request's table (no min_tokens beside an automaton: one table).
+            const TokenAutomaton* automaton = params.automaton.get();
+            const std::vector<int32_t> forced = automaton ? automaton->forcedTokens( bias_plan ) : std::vector<int32_t>{};
+            std::unordered_map<int32_t, float> bias_listed, bias_restored;
+            if ( bias_plan.active )
+            {
+                for ( size_t j = 0; j < bias_plan.ids.size(); ++j ) bias_listed[ bias_plan.ids[ j ] ] = bias_plan.values[ j ];
+                for ( size_t j = 0; j < bias_plan.restore_ids.size(); ++j ) bias_restored[ bias_plan.restore_ids[ j ] ] = bias_plan.restore_values[ j ];
+            }
+            // whether the table lets `t` be sample number `index` of the request (min_tokens: the stop tokens have their values back from restore_index on)
+            auto biasFinite = [&]( int32_t t, int index )
+            {
+                if ( !bias_plan.active ) return true;
+                if ( bias_plan.hasRestore() && index >= bias_plan.restore_index )
+                    if ( const auto it = bias_restored.find( t ); it != bias_restored.end() ) return std::isfinite( it->second );
+                const auto it = bias_listed.find( t );
+                return std::isfinite( it != bias_listed.end() ? it->second : bias_plan.fill );
+            };
             const int k = static_cast<int>( net.draftTokens() );
             const typename TNet::SamplingParams sp = networkSampling<TNet>( params.sampling );      // (never filtered here: onGenerating sends such requests to the plain loop)
             const int max_new = params.max_new_tokens.value_or( static_cast<int>( contextLength() ) );
@@ -873,6 +905,7 @@ namespace Mila::Dnn
             // emits one token under generate()'s rules; `at` = the position the token would be decoded at, `b` = its row in lp.  nullopt: go on
             auto emit = [&]( int32_t t, dim_t at, int b = 0 ) -> std::optional<GenerateStatus>
             {
+                if ( automaton ) last_automaton_state_ = automaton->step( *last_automaton_state_, t );
                 if ( stop_ids.contains( t ) ) return GenerateStatus::Success;
                 if ( params.logprobs ) lp.report( params.on_logprobs, 0, b, t );
                 on_token( t );
@@ -905,10 +938,49 @@ namespace Mila::Dnn
             {
                 if ( stop && stop->load( std::memory_order_relaxed ) ) { ctx->synchronize(); return GenerateStatus::ClientCancelled; }
                 history.push_back( token );
-                std::vector<int32_t> drafts = params.draft ? params.draft( history, k ) : promptLookupDraft( history, k );
-                if ( drafts.size() > static_cast<size_t>( k ) ) drafts.resize( static_cast<size_t>( k ) );
-                for ( int32_t& d : drafts ) if ( d < 0 || d >= vocabSize() ) d = 0;      // a drafter's out-of-range proposal is a wrong draft, not an error
-                const bool chain = !drafts.empty() && position + k + 1 <= contextLength() && net.bandBucket( position ) == net.bandBucket( position + k );
+                std::vector<int32_t> drafts;
+                int n_forced = 0;
+                if ( !automaton && !bias_plan.active )
+                {
+                    drafts = params.draft ? params.draft( history, k ) : promptLookupDraft( history, k );
+                    if ( drafts.size() > static_cast<size_t>( k ) ) drafts.resize( static_cast<size_t>( k ) );
+                    for ( int32_t& d : drafts ) if ( d < 0 || d >= vocabSize() ) d = 0;      // a drafter's out-of-range proposal is a wrong draft, not an error
+                }
+                else
+                {
+                    // the forced run from the current state, then the drafter on the history extended by it; nothing is drafted behind a stop token, and the
+                    // drafter's proposals end at the first one this request can never sample (draft i is sample emitted + i)
+                    int q = automaton ? *last_automaton_state_ : 0;
+                    bool ended = false;
+                    while ( automaton && !ended && static_cast<int>( drafts.size() ) < k && forced[ static_cast<size_t>( q ) ] >= 0 )
+                    {
+                        const int32_t f = forced[ static_cast<size_t>( q ) ];
+                        drafts.push_back( f );
+                        q = automaton->step( q, f );
+                        ended = stop_ids.contains( f );
+                    }
+                    n_forced = static_cast<int>( drafts.size() );
+                    if ( !ended && n_forced < k )
+                    {
+                        std::vector<int32_t> extended( history );
+                        extended.insert( extended.end(), drafts.begin(), drafts.end() );
+                        const std::vector<int32_t> more = params.draft ? params.draft( extended, k - n_forced ) : promptLookupDraft( extended, k - n_forced );
+                        for ( int32_t d : more )
+                        {
+                            if ( ended || static_cast<int>( drafts.size() ) >= k || d < 0 || d >= vocabSize() ) break;
+                            if ( ( automaton && !automaton->allows( q, d ) ) || !biasFinite( d, emitted + static_cast<int>( drafts.size() ) ) ) break;
+                            drafts.push_back( d );
+                            if ( automaton ) q = automaton->step( q, d );
+                            ended = stop_ids.contains( d );
+                        }
+                    }
+                }
+                // min_tokens: this step's row 0 produces sample `emitted`; the restore goes in front of the step that produces sample restore_index, and a chain step
+                // is taken only when its k + 1 samples lie on one side of it (its rows share the ONE table)
+                const bool restores = bias_plan.hasRestore();
+                if ( restores && emitted == bias_plan.restore_index ) net.commitTokenBiasUpdate();
+                const bool one_side = !restores || emitted >= bias_plan.restore_index || emitted + k < bias_plan.restore_index;
+                const bool chain = !drafts.empty() && one_side && position + k + 1 <= contextLength() && net.bandBucket( position ) == net.bandBucket( position + k );
                 ++last_speculation_.steps;
                 if ( !chain )
                 {
@@ -948,6 +1020,8 @@ namespace Mila::Dnn
                 ++last_speculation_.chain_steps;
                 last_speculation_.drafted += static_cast<uint64_t>( real );
                 last_speculation_.accepted += static_cast<uint64_t>( std::min( count - 1, real ) );
+                last_speculation_.forced += static_cast<uint64_t>( n_forced );
+                last_speculation_.forced_accepted += static_cast<uint64_t>( std::min( count - 1, n_forced ) );
                 // the caches now hold `token` and the count - 1 verified drafts behind it: the accepted tokens but the last, which is the next step's input
                 kv_token_history_.push_back( token );
                 for ( int i = 0; i + 1 < count; ++i ) kv_token_history_.push_back( row[ static_cast<size_t>( i ) + 1 ] );

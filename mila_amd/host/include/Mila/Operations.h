@@ -1301,19 +1301,30 @@ namespace Mila::Dnn::Compute
     /// effective table `eff` that the biased samplers read in the place of the bias table.  eff, the state and the ticket never move, so a captured step that holds
     /// them sees every later reset; the image is re-allocated only when its size changes, and key() names what a captured step kernel node holds by value (the image
     /// address, S, C).  Everything runs on the context's stream.  upload() and reset() synchronize (they read host memory); compose() and step() are one launch each.
+    /// On a draft_tokens network (drafts > 0) eff has one row per chain row and chain_states one word per row: chainCompose() / chainStep() are the two launches
+    /// around the tail of a constrained chain step (mila_cdna4.h: the constrained chain step); row 0 and the state word are the one-row step's.
     class RocmTokenAutomaton
     {
     public:
         struct Key { const void* image = nullptr; int S = 0, C = 0; bool operator==( const Key& ) const = default; };
-        RocmTokenAutomaton( IExecutionContext* ctx, dim_t vocab ) : context_( cast_context<DeviceType::Rocm>( ctx ) ), vocab_( vocab )
+        /// drafts > 0 (a draft_tokens network): eff has drafts + 1 rows of `vocab` floats -- row t the table of chain row t -- and chain_states drafts + 1 words;
+        /// drafts == 0 allocates exactly what it always did
+        RocmTokenAutomaton( IExecutionContext* ctx, dim_t vocab, dim_t drafts = 0 ) : context_( cast_context<DeviceType::Rocm>( ctx ) ), vocab_( vocab ), drafts_( drafts )
         {
             if ( vocab <= 0 ) throw std::invalid_argument( "RocmTokenAutomaton: need a positive vocabulary" );
+            if ( drafts < 0 || drafts > 3 ) throw std::invalid_argument( "RocmTokenAutomaton: 0 .. 3 drafts" );
             (void)narrowToKernelIndex( vocab, "vocab" );
             const auto dev = context_->getDeviceId();
-            eff_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ vocab } );
+            eff_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ vocab * ( drafts + 1 ) } );
             words_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ 2 } );
             rocmCheck( mila_cdna4_memset_zero( words_->rawData(), 8, context_->getStream() ) );
-            rocmCheck( mila_cdna4_token_bias_fill( eff_->data(), 0, 0, static_cast<int>( vocab_ ), 0.0f, context_->getStream() ) );
+            for ( dim_t t = 0; t <= drafts; ++t )
+                rocmCheck( mila_cdna4_token_bias_fill( eff_->data(), static_cast<size_t>( vocab_ ), static_cast<int>( t ), static_cast<int>( vocab_ ), 0.0f, context_->getStream() ) );
+            if ( drafts > 0 )
+            {
+                chain_states_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ drafts + 1 } );
+                rocmCheck( mila_cdna4_memset_zero( chain_states_->rawData(), chain_states_->sizeInBytes(), context_->getStream() ) );
+            }
             context_->synchronize();
         }
         /// the image of a validated automaton (TokenAutomaton::validate) onto the device; the state is whatever it was: reset() follows
@@ -1353,6 +1364,22 @@ namespace Mila::Dnn::Compute
             rocmCheck( mila_cdna4_token_automaton_step( eff_->data(), 0, base, 0, classDev(), nextDev(), S_, C_, words_->data(), token_dev, nullptr,
                                                         reinterpret_cast<uint32_t*>( words_->data() + 1 ), 1, static_cast<int>( vocab_ ), context_->getStream() ) );
         }
+        /// the first node of a constrained chain step of T rows fed tok_dev[ 0 .. T - 1 ]: eff rows 1 .. T - 1 and chain_states, one launch
+        void chainCompose( const float* base, const int32_t* tok_dev, int T )
+        {
+            requireChain( T );
+            rocmCheck( mila_cdna4_token_automaton_chain_compose( eff_->data(), static_cast<size_t>( vocab_ ), base, 0, classDev(), nextDev(), S_, C_, words_->data(), tok_dev,
+                                                                 chain_states_->data(), T, static_cast<int>( vocab_ ), context_->getStream() ) );
+        }
+        /// behind the accept tail that left result_dev = {count, ...} and tok_dev[ 0 ]: the state word and eff row 0, one launch
+        void chainStep( const float* base, const int32_t* tok_dev, const int32_t* result_dev, int T )
+        {
+            requireChain( T );
+            rocmCheck( mila_cdna4_token_automaton_chain_step( eff_->data(), static_cast<size_t>( vocab_ ), base, 0, classDev(), nextDev(), S_, C_, words_->data(), tok_dev,
+                                                              chain_states_->data(), result_dev, T, reinterpret_cast<uint32_t*>( words_->data() + 1 ),
+                                                              static_cast<int>( vocab_ ), context_->getStream() ) );
+        }
+        dim_t drafts() const noexcept { return drafts_; }
         /// the state word (synchronizes)
         int32_t readState()
         {
@@ -1367,18 +1394,28 @@ namespace Mila::Dnn::Compute
             rocmCheck( mila_cdna4_memcpy_d2h( out, eff_->data(), static_cast<size_t>( vocab_ ) * 4, context_->getStream() ) );
             context_->synchronize();
         }
-        size_t stateBytes() const { return eff_->sizeInBytes() + words_->sizeInBytes() + ( image_ ? image_->sizeInBytes() : 0 ); }
-        /// eff + the two words + the image rounded up to whole 32-bit words
-        size_t requiredBytes() const { return static_cast<size_t>( vocab_ ) * 4 + 8 + ( image_ ? ( ( mila_cdna4_token_automaton_bytes( static_cast<int>( vocab_ ), S_, C_ ) + 3 ) / 4 ) * 4 : 0 ); }
+        size_t stateBytes() const { return eff_->sizeInBytes() + words_->sizeInBytes() + ( chain_states_ ? chain_states_->sizeInBytes() : 0 ) + ( image_ ? image_->sizeInBytes() : 0 ); }
+        /// eff (one row, and one per draft) + the two words (and the chain's state words) + the image rounded up to whole 32-bit words
+        size_t requiredBytes() const
+        {
+            const size_t rows = static_cast<size_t>( drafts_ ) + 1;
+            return rows * static_cast<size_t>( vocab_ ) * 4 + 8 + ( drafts_ > 0 ? rows * 4 : 0 ) +
+                   ( image_ ? ( ( mila_cdna4_token_automaton_bytes( static_cast<int>( vocab_ ), S_, C_ ) + 3 ) / 4 ) * 4 : 0 );
+        }
     private:
         void requireLoaded() const { if ( !image_ ) throw std::logic_error( "RocmTokenAutomaton: no automaton was uploaded" ); }
+        void requireChain( int T ) const
+        {
+            requireLoaded();
+            if ( T < 2 || T > drafts_ + 1 ) throw std::invalid_argument( "RocmTokenAutomaton: a chain step takes 2 .. drafts + 1 rows" );
+        }
         const uint16_t* classDev() { return reinterpret_cast<const uint16_t*>( image_->rawData() ); }
         uint16_t* nextDev() { return reinterpret_cast<uint16_t*>( image_->rawData() ) + vocab_; }
         ExecutionContext<DeviceType::Rocm>* context_;
-        dim_t vocab_;
+        dim_t vocab_, drafts_;
         int S_{ 0 }, C_{ 0 }, start_{ 0 };
         std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> eff_;
-        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> words_, image_;
+        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> words_, image_, chain_states_;
     };
 
     class RocmSamplingOp : public Operation<DeviceType::Rocm, TensorDataType::FP32>

@@ -59,6 +59,36 @@ namespace Mila::Dnn
         }
         bool allows( int state, int32_t token ) const { return next[ static_cast<size_t>( state ) * num_classes + class_of[ static_cast<size_t>( token ) ] ] != FORBIDDEN; }
 
+        /// forced[s] = the ONE token id that has both a transition and a finite bias in state s, else -1 (no such token, or more than one).  A forced token is known
+        /// before the model runs: the masked distribution of state s has one atom, so every sampler returns it.  `bias` as for checkLive (its initial table: a plan
+        /// with a restore gives the forced tokens before the restore).  validate() first.  Per class: the count of finite tokens and the sum of their ids, which is
+        /// the id where the count is 1.
+        std::vector<int32_t> forcedTokens( const TokenBiasPlan& bias ) const
+        {
+            const size_t C = static_cast<size_t>( num_classes );
+            std::vector<int64_t> finite( C, 0 ), id_sum( C, 0 );
+            const bool fill_finite = !bias.active || std::isfinite( bias.fill );
+            if ( fill_finite )
+                for ( size_t i = 0; i < class_of.size(); ++i ) { ++finite[ class_of[ i ] ]; id_sum[ class_of[ i ] ] += static_cast<int64_t>( i ); }
+            if ( bias.active )
+                for ( size_t j = 0; j < bias.ids.size(); ++j )
+                {
+                    const uint16_t c = class_of[ static_cast<size_t>( bias.ids[ j ] ) ];
+                    const bool f = std::isfinite( bias.values[ j ] );
+                    if ( fill_finite && !f ) { --finite[ c ]; id_sum[ c ] -= bias.ids[ j ]; }
+                    else if ( !fill_finite && f ) { ++finite[ c ]; id_sum[ c ] += bias.ids[ j ]; }
+                }
+            std::vector<int32_t> forced( static_cast<size_t>( num_states ), -1 );
+            for ( size_t s = 0; s < forced.size(); ++s )
+            {
+                int64_t count = 0, sum = 0;
+                for ( size_t c = 0; c < C && count <= 1; ++c )
+                    if ( next[ s * C + c ] != FORBIDDEN && finite[ c ] > 0 ) { count += finite[ c ]; sum += id_sum[ c ]; }
+                if ( count == 1 ) forced[ s ] = static_cast<int32_t>( sum );
+            }
+            return forced;
+        }
+
         /// throws invalid_argument naming the first reachable state (in breadth-first order from start) that keeps no token with a transition and a finite bias;
         /// `bias` is the request's composed table (inactive: every token finite).  validate() first.
         void checkLive( const TokenBiasPlan& bias ) const

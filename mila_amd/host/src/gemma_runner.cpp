@@ -1801,7 +1801,7 @@ static int model_generate_impl( void* h, const int32_t* prompt, int64_t n_prompt
 static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature, int top_k,
                                float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens, int64_t cap, int64_t* out_count,
                                int32_t* out_status, int64_t* out_stats, LogprobSink sink = LogprobSink{}, int64_t* out_logprob_count = nullptr, const float* filters = nullptr,
-                               const mila_token_bias_request* bias = nullptr, const mila_token_automaton_request* automaton = nullptr )
+                               const mila_token_bias_request* bias = nullptr, const mila_token_automaton_request* automaton = nullptr, int speculate_constrained = 0 )
 {
     return guarded( [&]
     {
@@ -1812,6 +1812,7 @@ static int generate_spec_impl( void* h, const int32_t* prompt, int64_t n_prompt,
         sink.attach( gp, [&]( int ) -> int64_t& { return n_lp; } );
         struct Report { int64_t* out; int64_t& n; ~Report() { if ( out ) *out = n; } } report{ out_logprob_count, n_lp };
         gp.speculative_sampling = speculative_sampling != 0;
+        gp.speculate_constrained = speculate_constrained != 0;
         if ( max_new >= 0 ) gp.max_new_tokens = max_new;
         gp.sampling.temperature = temperature; gp.sampling.top_k = top_k; gp.sampling.top_p = top_p;
         apply_request_filters( gp.sampling, filters );
@@ -1897,6 +1898,34 @@ HOST_API int mila_gemma_model_generate_spec_automaton( void* h, const int32_t* p
                                out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters, bias, automaton );
 }
 
+/// mila_gemma_model_generate_spec_automaton with GenerateParams::speculate_constrained: with it set, a request with a bias and / or an automaton takes the speculative loop
+HOST_API int mila_gemma_model_generate_spec_constrained( void* h, const int32_t* prompt, int64_t n_prompt, int max_new, const int32_t* stop_tokens, int n_stop, float temperature,
+                                                         int top_k, float top_p, int64_t seed, const int32_t* hint, int64_t n_hint, int speculative_sampling, int32_t* out_tokens,
+                                                         int64_t cap, int64_t* out_count, int32_t* out_status, int64_t* out_stats, int top_n, float* out_logprob, int32_t* out_ids,
+                                                         float* out_logprobs, int64_t* out_logprob_count, const float* filters, const mila_token_bias_request* bias,
+                                                         const mila_token_automaton_request* automaton, int speculate_constrained )
+{
+    return generate_spec_impl( h, prompt, n_prompt, max_new, stop_tokens, n_stop, temperature, top_k, top_p, seed, hint, n_hint, speculative_sampling, out_tokens, cap, out_count,
+                               out_status, out_stats, LogprobSink{ top_n, out_logprob, out_ids, out_logprobs, cap }, out_logprob_count, filters, bias, automaton,
+                               speculate_constrained );
+}
+
+/// TokenAutomaton::forcedTokens under a table that bans `banned` (n_banned may be 0): out[ num_states ] = the one token a state allows, else -1.  Host only.
+HOST_API int mila_token_automaton_forced_tokens( const mila_token_automaton_request* automaton, const int32_t* banned, int64_t n_banned, int32_t* out )
+{
+    return guarded( [&]
+    {
+        if ( !automaton || !out || n_banned < 0 || ( n_banned && !banned ) ) throw std::invalid_argument( "token_automaton_forced_tokens: null argument" );
+        GenerateParams gp;
+        apply_request_automaton( gp, automaton );
+        gp.automaton->validate( automaton->vocab );
+        TokenBiasRequest rq;
+        rq.banned_tokens.assign( banned, banned + n_banned );
+        const std::vector<int32_t> forced = gp.automaton->forcedTokens( composeTokenBias( rq, automaton->vocab ) );
+        std::copy( forced.begin(), forced.end(), out );
+    } );
+}
+
 /// the vocabulary size of the model (what the ids of a bias request are checked against)
 HOST_API int64_t mila_gemma_model_vocab_size( void* h )
 {
@@ -1913,6 +1942,19 @@ HOST_API int mila_gemma_model_speculation_stats( void* h, int64_t* out )
         if ( !m || !out ) throw std::invalid_argument( "gemma_model_speculation_stats: null argument" );
         const auto& sp = m->lastSpeculation();
         out[ 0 ] = (int64_t)sp.steps; out[ 1 ] = (int64_t)sp.chain_steps; out[ 2 ] = (int64_t)sp.drafted; out[ 3 ] = (int64_t)sp.accepted;
+    } );
+}
+
+/// GemmaModel::lastSpeculation() in full: { steps, chain_steps, drafted, accepted, forced, forced_accepted }
+HOST_API int mila_gemma_model_speculation_stats_forced( void* h, int64_t* out )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m || !out ) throw std::invalid_argument( "gemma_model_speculation_stats_forced: null argument" );
+        const auto& sp = m->lastSpeculation();
+        out[ 0 ] = (int64_t)sp.steps; out[ 1 ] = (int64_t)sp.chain_steps; out[ 2 ] = (int64_t)sp.drafted; out[ 3 ] = (int64_t)sp.accepted;
+        out[ 4 ] = (int64_t)sp.forced; out[ 5 ] = (int64_t)sp.forced_accepted;
     } );
 }
 
