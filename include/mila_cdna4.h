@@ -984,6 +984,94 @@ MILA_API int mila_cdna4_sample_argmax_biased_chain_accept_fp32(int32_t* tok, int
                                                                const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* position_dev,
                                                                mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Row requests (ABI 4, additive; csrc/sampling.hip): a rows call whose rows each carry their OWN request -- a greedy constrained row next to a temperature-0.9 row
+ * next to a penalized one.  The entries above take one temperature / top_k / top_p / filters for every row as launch arguments; here they live in DEVICE memory, one
+ * record per row, so that a captured rows step serves a new set of requests without being captured again (the rule the bias tables and the automaton already keep).
+ *
+ * THE RECORD.  mila_sample_row_params, 32 bytes per row, sample_row_params_bytes(rows) = rows x 32 (0 for rows outside 1 .. 4).  temperature <= 0 makes the row GREEDY.
+ * inv_rep is an output of the setter (1.0f / repetition_penalty, divided once on the host as the filtered entries do); what a caller puts there is ignored.
+ * sample_row_params_set validates ONE row's record on the host and stores it into params_dev[row] in stream order (one lane, plain vector stores): behind the steps
+ * enqueued before it, in front of those enqueued after.  Refused before any device work (MILA_E_INVALID_ARGUMENT): a null pointer, a misaligned params_dev, row outside
+ * 0 .. 3, a temperature that is not finite, top_k < 0, top_p <= 0 or NaN, and what the filtered entries refuse (a non-finite filter, repetition_penalty <= 0, min_p
+ * outside [0, 1)).
+ *
+ * THE STOCHASTIC ROWS.  sample_radix_requests_rows_fp32 / _advance_fp32 launch the FULL radix plan (scale, 3 top-k passes, prob, 2 further nucleus passes, mask, tail:
+ * 9 launches, what top_k and top_p both on launch today) with the rows in the grid.  Every stage reads its row's record: a row with top-k off (top_k = 0 or >= vocab)
+ * returns from the top-k passes at once, a row with top-p off (top_p >= 1) from the nucleus passes; a GREEDY or (advance form) INACTIVE row returns from every stage.
+ * Row b reads logits + b * logits_stride, draws[b] (as in sample_radix_rows_fp32), its bias row bias + b * bias_stride (bias NULL: none; bias_stride 0: shared) and,
+ * only where its record has a penalty (repetition_penalty != 1 or presence / frequency != 0), its table table + b * table_stride.
+ * ROW INVARIANCE: row b's token is the token sample_radix_biased_fp32 / sample_radix_filtered_fp32 returns on row b's logits with row b's parameters, table (NULL where
+ * the record has no penalty), bias row and r = draws[b], for every input and every draw, whatever the other rows hold (a NaN included) and whatever their records say:
+ * the stages run the one-row entry's bodies, so per row every launch extent, chunk, walk order and float summation is the one-row entry's.
+ * The tail (one wave per row, then one lane's plain stores) acts on the rows that are active and stochastic ONLY: token_out[b] = the sample, (advance)
+ * positions_dev[b] += 1, and table[b][sample] += 1 where the row has a penalty.  Every other row's token, position and table words are not touched.
+ *
+ * THE GREEDY ROWS.  sample_argmax_requests_rows_fp32 / _advance_fp32 are the two launches of sample_argmax_biased_rows_advance_fp32 reading the record: argmax(x3) over
+ * the capped logit, the row's bias and (where the record has a penalty) the row's table, ties to the LOWEST id; a row with neither bias nor penalty takes the logits
+ * as they are (sample_argmax_fp32).  A greedy row's logit is never divided by a temperature.  The tail acts on the rows that are active and greedy ONLY.
+ * Row b's token is sample_argmax_biased_fp32's on row b alone.  The soft cap is monotone but can merge two neighbouring logits into a tie, so a greedy row WITHOUT a
+ * bias must not be given a row of zeros where it is to keep the token of the uncapped logits: a caller whose batch holds both kinds of greedy row calls the entry twice,
+ * once with the tables and once with bias = NULL, each with an active mask that selects its rows (Mila/Gemma.h keeps the two masks on the device).
+ * Enqueued one behind the other, the two advance entries advance each active row exactly once; a step without greedy (stochastic) rows may leave the greedy
+ * (stochastic) entry out.
+ *   scratch: radix -- sample_radix_rows_scratch_bytes(rows, vocab), 8-byte aligned; argmax -- rows x sample_scratch_bytes(), 4-byte aligned.
+ * Refused before any device work: a null logits, token_out, params_dev (radix: draws; advance: positions_dev, active_dev), rows outside 1 .. 4, vocab <= 0,
+ * logits_stride < vocab, with more than one row a table_stride below vocab or a bias_stride from 1 to vocab - 1, a misaligned pointer or scratch
+ * (MILA_E_INVALID_ARGUMENT); a scratch that is too small (MILA_E_SCRATCH_TOO_SMALL).
+ *
+ * THE AUTOMATON PER ROW.  token_automaton_rows_compose / _rows_step are token_automaton_compose / _step with the image of row b taken from a descriptor in device
+ * memory: mila_token_automaton_row {class_of, next, S, C}, 24 bytes per row, token_automaton_rows_bytes(rows).  token_automaton_rows_set validates one row's image
+ * shape on the host and stores the descriptor in stream order; class_of = next = NULL stores a NULL DESCRIPTOR: the row has no automaton -- its eff row is not
+ * written, its state word not read and it takes no ticket.  State word, ticket word and active word per row as in token_automaton_step, with its ordering argument:
+ * every workgroup reads state and token before it draws its ticket, and the holder of the row's last ticket stores the state and zeroes the ticket.  Row b's state
+ * sequence and eff row are token_automaton_step's on that row alone.  The 16-byte walk needs, beside the one-row entry's conditions on eff and base, row b's class_of
+ * 8-byte aligned (tested per row on the device).
+ * Refused before any device work (MILA_E_INVALID_ARGUMENT): a null or misaligned desc_dev, row outside 0 .. 3, exactly one of class_of / next, the shape limits of the
+ * image; compose / step: a null eff or state_dev (step: token_dev, ticket_dev), rows outside 1 .. 4, vocab <= 0, with more than one row an eff_stride below vocab, a
+ * base_stride from 1 to vocab - 1. */
+typedef struct mila_sample_row_params
+{
+    float temperature;            /* > 0: stochastic; <= 0: greedy */
+    int32_t top_k;                /* 0 or >= vocab = off */
+    float top_p;                  /* (0, 1); >= 1 = off */
+    float min_p;                  /* [0, 1); 0 = off */
+    float repetition_penalty;     /* > 0; 1 = off */
+    float inv_rep;                /* written by the setter */
+    float presence_penalty;       /* 0 = off */
+    float frequency_penalty;      /* 0 = off */
+} mila_sample_row_params;
+typedef struct mila_token_automaton_row
+{
+    const uint16_t* class_of;     /* NULL: the row has no automaton */
+    const uint16_t* next;
+    int32_t S, C;
+} mila_token_automaton_row;
+MILA_API size_t mila_cdna4_sample_row_params_bytes(int rows);
+MILA_API int mila_cdna4_sample_row_params_set(void* params_dev, int row, const mila_sample_row_params* params, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_requests_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                        const void* params_dev, const float* draws, uint32_t* table, size_t table_stride, const float* bias,
+                                                        size_t bias_stride, void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_radix_requests_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                                const void* params_dev, const float* draws, uint32_t* table, size_t table_stride, const float* bias,
+                                                                size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* positions_dev,
+                                                                const int32_t* active_dev, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_requests_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                         const void* params_dev, uint32_t* table, size_t table_stride, const float* bias, size_t bias_stride,
+                                                         void* scratch, size_t scratch_bytes, mila_stream_t stream);
+MILA_API int mila_cdna4_sample_argmax_requests_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                                 const void* params_dev, uint32_t* table, size_t table_stride, const float* bias, size_t bias_stride,
+                                                                 void* scratch, size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev,
+                                                                 mila_stream_t stream);
+MILA_API size_t mila_cdna4_token_automaton_rows_bytes(int rows);
+MILA_API int mila_cdna4_token_automaton_rows_set(void* desc_dev, int row, const uint16_t* class_of, const uint16_t* next, int S, int C, int vocab,
+                                                 mila_stream_t stream);
+MILA_API int mila_cdna4_token_automaton_rows_compose(float* eff, size_t eff_stride, const float* base, size_t base_stride, const void* desc_dev, int32_t* state_dev,
+                                                     int rows, int vocab, mila_stream_t stream);
+MILA_API int mila_cdna4_token_automaton_rows_step(float* eff, size_t eff_stride, const float* base, size_t base_stride, const void* desc_dev, int32_t* state_dev,
+                                                  const int32_t* token_dev, const int32_t* active_dev, uint32_t* ticket_dev, int rows, int vocab,
+                                                  mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,19 @@ def load():
     main.mila_cdna4_token_automaton_chain_step.argtypes = [p, z, p, z, p, p, i, i, p, p, p, p, i, p, i, p]        # ... state_dev tok_dev chain_states result_dev T ticket_dev | vocab
     main.mila_cdna4_sample_radix_biased_chain_accept_fp32.argtypes = [p, p, p, z, i, i, f, f, i, f, p, p, z, p, z, p, p]   # ... top_p | draws | bias bias_stride | scratch bytes | position_dev
     main.mila_cdna4_sample_argmax_biased_chain_accept_fp32.argtypes = [p, p, p, z, i, i, f, p, z, p, z, p, p]     # tok result logits logits_stride | T vocab softcap | bias bias_stride | scratch bytes | position_dev
+    # row requests (csrc/sampling.hip: the sampler parameters and the automaton image of each row in device memory)
+    main.mila_cdna4_sample_row_params_bytes.argtypes = [i]                                                        # rows
+    main.mila_cdna4_sample_row_params_bytes.restype = z
+    main.mila_cdna4_sample_row_params_set.argtypes = [p, i, p, p]                                                 # params_dev row params
+    main.mila_cdna4_sample_radix_requests_rows_fp32.argtypes = [p, z, p, i, i, f, p, p, p, z, p, z, p, z, p]      # logits logits_stride token_out | rows vocab softcap | params_dev draws | table table_stride | bias bias_stride | scratch bytes
+    main.mila_cdna4_sample_radix_requests_rows_advance_fp32.argtypes = [p, z, p, i, i, f, p, p, p, z, p, z, p, z, p, p, p]   # ... | positions_dev active_dev
+    main.mila_cdna4_sample_argmax_requests_rows_fp32.argtypes = [p, z, p, i, i, f, p, p, z, p, z, p, z, p]        # logits logits_stride token_out | rows vocab softcap | params_dev | table table_stride | bias bias_stride | scratch bytes
+    main.mila_cdna4_sample_argmax_requests_rows_advance_fp32.argtypes = [p, z, p, i, i, f, p, p, z, p, z, p, z, p, p, p]
+    main.mila_cdna4_token_automaton_rows_bytes.argtypes = [i]
+    main.mila_cdna4_token_automaton_rows_bytes.restype = z
+    main.mila_cdna4_token_automaton_rows_set.argtypes = [p, i, p, p, i, i, i, p]                                  # desc_dev row | class_of next S C vocab
+    main.mila_cdna4_token_automaton_rows_compose.argtypes = [p, z, p, z, p, p, i, i, p]                           # eff eff_stride base base_stride | desc_dev state_dev | rows vocab
+    main.mila_cdna4_token_automaton_rows_step.argtypes = [p, z, p, z, p, p, p, p, p, i, i, p]                     # ... desc_dev state_dev token_dev active_dev ticket_dev | rows vocab
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -595,6 +608,87 @@ def sample_argmax_biased_chain_accept(tok, result, logits, softcap, bias, scratc
          _nbytes(scratch), position_dev)
 
 
+# ---- row requests: the sampler parameters of each row as a 32-byte record in device memory (params_dev: a uint8 / int32 tensor of sample_row_params_bytes(rows)
+# bytes), written by a host-validated setter; the requests entries read row b's record, table[b] (only where the record has a penalty) and bias[b]
+class sample_row_params(C.Structure):
+    """mila_sample_row_params: temperature <= 0 = greedy; inv_rep is the setter's to write"""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float), ("repetition_penalty", C.c_float), ("inv_rep", C.c_float),
+                ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float)]
+
+
+class token_automaton_row(C.Structure):
+    """mila_token_automaton_row: the image of one row; class_of NULL = the row has no automaton"""
+    _fields_ = [("class_of", C.c_void_p), ("next", C.c_void_p), ("S", C.c_int32), ("C", C.c_int32)]
+
+
+def sample_row_params_bytes(rows):
+    return int(load().mila_cdna4_sample_row_params_bytes(int(rows)))
+
+
+def sample_row_params_set(params_dev, row, temperature=0.0, top_k=0, top_p=1.0, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+    """params_dev[row] <- the validated record, in stream order"""
+    rec = sample_row_params(float(temperature), int(top_k), float(top_p), float(min_p), float(repetition_penalty), 0.0, float(presence_penalty), float(frequency_penalty))
+    call("sample_row_params_set", params_dev, int(row), C.byref(rec))
+
+
+def sample_radix_requests_rows(logits, token_out, softcap, params_dev, draws, table, bias, scratch, vocab=None, bias_stride=None):
+    """the stochastic rows of a requests call: token_out[b] <- row b's sample under ITS record at draws[b]; a greedy row's word is not touched"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_requests_rows_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), params_dev, draws, table, _tables_stride(table), bias,
+         _bias_stride(bias, bias_stride), scratch, _nbytes(scratch))
+
+
+def sample_radix_requests_rows_advance(logits, token_out, softcap, params_dev, draws, table, bias, scratch, positions_dev, active_dev, vocab=None, bias_stride=None):
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_radix_requests_rows_advance_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), params_dev, draws, table, _tables_stride(table), bias,
+         _bias_stride(bias, bias_stride), scratch, _nbytes(scratch), positions_dev, active_dev)
+
+
+def sample_argmax_requests_rows(logits, token_out, softcap, params_dev, table, bias, scratch, vocab=None, bias_stride=None):
+    """the greedy rows of a requests call: token_out[b] <- argmax of row b's adjusted logits, ties to the lower id; a stochastic row's word is not touched"""
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_argmax_requests_rows_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), params_dev, table, _tables_stride(table), bias,
+         _bias_stride(bias, bias_stride), scratch, _nbytes(scratch))
+
+
+def sample_argmax_requests_rows_advance(logits, token_out, softcap, params_dev, table, bias, scratch, positions_dev, active_dev, vocab=None, bias_stride=None):
+    stride, V = _radix_rows_head(logits, vocab)
+    call("sample_argmax_requests_rows_advance_fp32", logits, stride, token_out, int(logits.shape[0]), V, float(softcap), params_dev, table, _tables_stride(table), bias,
+         _bias_stride(bias, bias_stride), scratch, _nbytes(scratch), positions_dev, active_dev)
+
+
+def token_automaton_rows_bytes(rows):
+    return int(load().mila_cdna4_token_automaton_rows_bytes(int(rows)))
+
+
+def token_automaton_rows_set(desc_dev, row, class_of, next_table, vocab=None):
+    """desc_dev[row] <- the image (class_of [vocab], next [S, C], 16-bit tensors on the device), or the null descriptor when both are None; in stream order"""
+    if class_of is None and next_table is None:
+        call("token_automaton_rows_set", desc_dev, int(row), None, None, 0, 0, 0)
+        return
+    assert class_of.element_size() == 2 and next_table.element_size() == 2 and next_table.dim() == 2
+    call("token_automaton_rows_set", desc_dev, int(row), class_of, next_table, int(next_table.shape[0]), int(next_table.shape[1]),
+         int(class_of.numel() if vocab is None else vocab))
+
+
+def _automaton_rows_head(eff, base, vocab):
+    assert eff.dim() == 2
+    base_stride = 0 if base is None or base.dim() == 1 else int(base.shape[-1])
+    return int(eff.shape[0]), int(eff.shape[1] if vocab is None else vocab), C.c_size_t(int(eff.shape[1])), C.c_size_t(base_stride)
+
+
+def token_automaton_rows_compose(eff, base, desc_dev, state_dev, vocab=None):
+    """token_automaton_compose with row b's image from desc_dev[b]; a row with the null descriptor is not touched"""
+    rows, V, es, bs = _automaton_rows_head(eff, base, vocab)
+    call("token_automaton_rows_compose", eff, es, base, bs, desc_dev, state_dev, rows, V)
+
+
+def token_automaton_rows_step(eff, base, desc_dev, state_dev, token_dev, ticket_dev, active_dev=None, vocab=None):
+    """token_automaton_step with row b's image from desc_dev[b]; a row with the null descriptor or a zero active word is not touched"""
+    rows, V, es, bs = _automaton_rows_head(eff, base, vocab)
+    call("token_automaton_rows_step", eff, es, base, bs, desc_dev, state_dev, token_dev, active_dev, ticket_dev, rows, V)
+
+
 TOKEN_LOGPROBS_MAX_TOP = 20
 
 
@@ -720,6 +814,9 @@ EXPORTED = [
     "sample_argmax_biased_fp32", "sample_argmax_biased_advance_fp32", "sample_argmax_biased_rows_advance_fp32",
     "token_automaton_bytes", "token_automaton_compose", "token_automaton_step",
     "token_automaton_chain_compose", "token_automaton_chain_step", "sample_radix_biased_chain_accept_fp32", "sample_argmax_biased_chain_accept_fp32",
+    "sample_row_params_bytes", "sample_row_params_set", "sample_radix_requests_rows_fp32", "sample_radix_requests_rows_advance_fp32",
+    "sample_argmax_requests_rows_fp32", "sample_argmax_requests_rows_advance_fp32",
+    "token_automaton_rows_bytes", "token_automaton_rows_set", "token_automaton_rows_compose", "token_automaton_rows_step",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

@@ -1421,6 +1421,317 @@ static int run_argmax_filtered(const float* logits, size_t logits_stride, int32_
     return check_hip(hipGetLastError(), who);
 }
 
+// ================================================================================================
+// Row requests (mila_cdna4.h: row requests): every row of a rows call samples under its OWN parameters, read from a record in device memory, so that a new set of
+// requests changes words, not launch arguments -- a captured rows step is not captured again.  The stage kernels are the rows kernels above with the row's record in
+// the place of the launch arguments: each builds row b's RadixParams / SampleFilter from the record and runs the SAME stage body (radix_scale_body, radix_kpass_body,
+// radix_prob_body, radix_ppass_body, radix_mask_body, radix_cdf_walk), so per row every launch extent, chunk, walk order and float summation is the one-row entry's.
+// A call launches the full plan (scale, 3 k-passes, prob, 2 p-passes, mask, tail); a row whose truncation is off returns from that search's launches at once, a greedy
+// or inactive row from every stage.  Every branch on the record is uniform over the row's workgroups.
+struct RowParams                    // = mila_sample_row_params
+{
+    float temperature;              // <= 0: the row is greedy
+    int32_t top_k;
+    float top_p, min_p, rep, inv_rep, pres, freq;
+};
+static_assert(sizeof(RowParams) == sizeof(mila_sample_row_params) && sizeof(RowParams) == 32, "RowParams");
+
+__device__ __forceinline__ bool row_stochastic(const RowParams& q) { return q.temperature > 0.0f; }
+__device__ __forceinline__ bool row_penalized(const RowParams& q) { return q.rep != 1.0f || q.pres != 0.0f || q.freq != 0.0f; }
+__device__ __forceinline__ bool row_use_k(const RowParams& q, int vocab) { return q.top_k > 0 && q.top_k < vocab; }
+__device__ __forceinline__ bool row_use_p(const RowParams& q) { return q.top_p < 1.0f; }
+__device__ __forceinline__ bool row_active(const int32_t* active, int b) { return active == nullptr || active[b] != 0; }
+
+// what the request kernels share beside RadixRows (r.f holds table and table_stride only; r.p no temperature, top_k, top_p)
+struct RowRequests
+{
+    const RowParams* params;        // [rows] on the device
+    const int32_t* active;          // [rows] or nullptr (every row)
+    const float* bias;              // row 0's bias table or nullptr; row b's at bias + b * bias_stride
+    size_t bias_stride;
+};
+
+// row b's stage parameters; false: the row takes no part in the radix stages
+__device__ __forceinline__ bool request_row(const RadixRows& r, const RowRequests& q, int b, RadixParams& p, RowParams& rp)
+{
+    rp = q.params[b];
+    if (!row_stochastic(rp) || !row_active(q.active, b)) return false;
+    p = radix_row(r, b);
+    p.temperature = rp.temperature; p.top_k = rp.top_k; p.top_p = rp.top_p;
+    return true;
+}
+__device__ __forceinline__ SampleFilter request_filter(const RadixRows& r, const RowParams& rp)
+{
+    return SampleFilter{r.f.table, r.f.table_stride, rp.rep, rp.inv_rep, rp.pres, rp.freq, rp.min_p};
+}
+
+__global__ __launch_bounds__(256) void radix_requests_scale_kernel(const float* __restrict__ logits0, const RadixRows r, const RowRequests q, int clear_words)
+{
+    const int b = blockIdx.y;
+    RadixParams p;
+    RowParams rp;
+    if (!request_row(r, q, b, p, rp)) return;
+    const SampleFilter f = request_filter(r, rp);
+    const float* logits = logits0 + (size_t)b * r.logits_stride;
+    const uint32_t* table = (f.table && row_penalized(rp)) ? f.table + (size_t)b * f.table_stride : nullptr;
+    const float* bias = q.bias ? q.bias + (size_t)b * q.bias_stride : nullptr;
+    if (table && bias) radix_scale_body<float, true, true>(logits, p, clear_words, &f, table, bias);
+    else if (bias) radix_scale_body<float, false, true>(logits, p, clear_words, &f, nullptr, bias);
+    else if (table) radix_scale_body<float, true, false>(logits, p, clear_words, &f, table, nullptr);
+    else radix_scale_body<float, false, false>(logits, p, clear_words);
+}
+__global__ __launch_bounds__(256) void radix_requests_kpass_kernel(const RadixRows r, const RowRequests q, int pass)
+{
+    RadixParams p;
+    RowParams rp;
+    if (!request_row(r, q, blockIdx.y, p, rp) || !row_use_k(rp, p.vocab)) return;
+    radix_kpass_body(p, pass);
+}
+__global__ __launch_bounds__(256) void radix_requests_prob_kernel(const RadixRows r, const RowRequests q, int nblocks_scale)
+{
+    RadixParams p;
+    RowParams rp;
+    if (!request_row(r, q, blockIdx.y, p, rp)) return;
+    radix_prob_body(p, row_use_k(rp, p.vocab) ? 1 : 0, row_use_p(rp) ? 1 : 0, nblocks_scale);
+}
+__global__ __launch_bounds__(256) void radix_requests_ppass_kernel(const RadixRows r, const RowRequests q, int pass)
+{
+    RadixParams p;
+    RowParams rp;
+    if (!request_row(r, q, blockIdx.y, p, rp) || !row_use_p(rp)) return;
+    radix_ppass_body(p, pass);
+}
+// (the min-p test with min_p = 0 drops nothing: e > 0 && e < 0 never holds -- one instantiation serves every row)
+__global__ __launch_bounds__(256) void radix_requests_mask_kernel(const RadixRows r, const RowRequests q, int chunk)
+{
+    RadixParams p;
+    RowParams rp;
+    if (!request_row(r, q, blockIdx.y, p, rp)) return;
+    radix_mask_body<true>(p, row_use_p(rp) ? 1 : 0, chunk, rp.min_p);
+}
+
+// The requests tail: radix_rows_tail_kernel's shape (wave t walks row t's CDF at draws[t], then one lane's plain stores) over the rows that are active and stochastic.
+// The lane counts the sample in row b's table only where row b has penalties.  ADVANCE: pos[b] += 1 behind the token.
+template <bool ADVANCE>
+__global__ __launch_bounds__(256) void radix_requests_tail_kernel(const RadixRows r, const RowRequests q, int rows, int nchunks, int chunk)
+{
+    __shared__ int ss[4];
+    __shared__ int take[4];
+    const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+    if (t < rows)
+    {
+        RadixParams p;
+        RowParams rp;
+        const bool mine = request_row(r, q, t, p, rp);
+        int s = 0;
+        if (mine)
+        {
+            const float draw = __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t*>(r.p.draws) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+            s = radix_cdf_walk(p, draw, nchunks, chunk, lane);
+        }
+        if (lane == 0) { ss[t] = s; take[t] = mine ? (r.f.table && row_penalized(rp) ? 2 : 1) : 0; }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int b = 0; b < rows; ++b)
+    {
+        if (take[b] == 0) continue;
+        if (take[b] == 2) table_count(r.f.table + (size_t)b * r.f.table_stride, ss[b]);
+        r.p.token_out[b] = ss[b];
+        if (ADVANCE) r.p.pos[b] += 1;
+    }
+}
+
+// The greedy rows of the same step.  First stage: argmax_partial_filtered_kernel with the row's record -- x3 over the capped logit, the row's bias and (where the row
+// has penalties) the row's table; a row with neither bias nor penalties takes the logits AS THEY ARE, as sample_argmax_fp32 does (the cap is monotone but can merge
+// neighbours into a tie).  A greedy row's logit is never divided by a temperature.  A stochastic or inactive row returns at once and leaves its partials alone.
+template <bool TABLE, bool BIAS>
+__device__ __forceinline__ void argmax_request_walk(const float* __restrict__ logits, const uint32_t* __restrict__ table, const float* __restrict__ bias, float softcap,
+                                                    const SampleFilter& f, int vocab, float& bv, int& bi)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256)
+    {
+        float x = logits[i];
+        if (TABLE || BIAS) x = soft_cap(x, softcap);
+        if (BIAS) x = __fadd_rn(x, bias[i]);
+        if (TABLE) x = penalized_logit(x, table[i], f);
+        argmax_better(bv, bi, x, i);
+    }
+}
+__global__ __launch_bounds__(256) void argmax_requests_partial_kernel(const float* __restrict__ logits0, size_t logits_stride, float softcap, const RowRequests q,
+                                                                      const uint32_t* table0, size_t table_stride, float* __restrict__ pv0, int row_floats, int vocab)
+{
+    const int b = blockIdx.y;
+    const RowParams rp = q.params[b];
+    if (row_stochastic(rp) || !row_active(q.active, b)) return;
+    const float* logits = logits0 + (size_t)b * logits_stride;
+    const uint32_t* table = (table0 && row_penalized(rp)) ? table0 + (size_t)b * table_stride : nullptr;
+    const float* bias = q.bias ? q.bias + (size_t)b * q.bias_stride : nullptr;
+    const SampleFilter f{nullptr, 0, rp.rep, rp.inv_rep, rp.pres, rp.freq, rp.min_p};
+    float* pv = pv0 + (size_t)b * row_floats;
+    int* pi = reinterpret_cast<int*>(pv + kArgmaxBlocks);
+    float bv = -FLT_MAX;
+    int bi = 0x7fffffff;
+    if (table && bias) argmax_request_walk<true, true>(logits, table, bias, softcap, f, vocab, bv, bi);
+    else if (bias) argmax_request_walk<false, true>(logits, table, bias, softcap, f, vocab, bv, bi);
+    else if (table) argmax_request_walk<true, false>(logits, table, bias, softcap, f, vocab, bv, bi);
+    else argmax_request_walk<false, false>(logits, table, bias, softcap, f, vocab, bv, bi);
+    block_argmax(bv, bi);
+    if (threadIdx.x == 0) { pv[blockIdx.x] = bv; pi[blockIdx.x] = bi; }
+}
+
+// second stage: argmax_rows_final_advance_kernel over the rows that are active and greedy, the count in the row's table only where the row has penalties
+template <bool ADVANCE>
+__global__ __launch_bounds__(256) void argmax_requests_final_kernel(const float* __restrict__ pv0, int32_t* __restrict__ token_out, int32_t* __restrict__ pos,
+                                                                    const RowRequests q, int n, int row_floats, uint32_t* table0, size_t table_stride)
+{
+    const int b = blockIdx.x;
+    const RowParams rp = q.params[b];
+    if (row_stochastic(rp) || !row_active(q.active, b)) return;
+    const float* pv = pv0 + (size_t)b * row_floats;
+    const int* pi = reinterpret_cast<const int*>(pv + kArgmaxBlocks);
+    float bv = -FLT_MAX;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += 256) argmax_better(bv, bi, pv[i], pi[i]);
+    block_argmax(bv, bi);
+    if (threadIdx.x == 0)
+    {
+        const int tok = argmax_token(bi);
+        if (table0 && row_penalized(rp)) table_count(table0 + (size_t)b * table_stride, tok);
+        token_out[b] = tok;
+        if (ADVANCE) pos[b] += 1;
+    }
+}
+
+// the record of one row, stored by one lane in plain vector stores (stream order: behind the steps that read the old record, in front of those that read the new)
+__global__ __launch_bounds__(64) void sample_row_params_set_kernel(RowParams* __restrict__ dst, const RowParams v)
+{
+    if (threadIdx.x == 0) *dst = v;
+}
+
+// what the requests entries check before any launch
+static int check_requests(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, const void* params_dev, uint32_t* table, size_t table_stride,
+                          const float* bias, size_t bias_stride, bool advance, int32_t* positions_dev, const int32_t* active_dev, const char* who)
+{
+    MILA_REQUIRE(logits && token_out && params_dev, "%s: null pointer", who);
+    MILA_REQUIRE(!advance || (positions_dev && active_dev), "%s: null pointer", who);
+    MILA_REQUIRE(rows >= 1 && rows <= 4, "%s: rows=%d outside 1 .. 4", who, rows);
+    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
+    MILA_REQUIRE(logits_stride >= (size_t)vocab, "%s: logits_stride %zu < vocab %d", who, logits_stride, vocab);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(params_dev) & 3u) == 0, "%s: params_dev must be 4-byte aligned", who);
+    MILA_REQUIRE(!table || rows == 1 || table_stride >= (size_t)vocab, "%s: table_stride %zu < vocab %d", who, table_stride, vocab);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(table) & 3u) == 0, "%s: table must be 4-byte aligned", who);
+    return check_bias(bias, bias_stride, rows, vocab, who);
+}
+
+static int run_radix_requests(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, const void* params_dev, const float* draws,
+                              uint32_t* table, size_t table_stride, const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, bool advance,
+                              int32_t* positions_dev, const int32_t* active_dev, hipStream_t s, const char* who)
+{
+    if (const int rc = check_requests(logits, logits_stride, token_out, rows, vocab, params_dev, table, table_stride, bias, bias_stride, advance, positions_dev, active_dev, who))
+        return rc;
+    MILA_REQUIRE(draws, "%s: null pointer", who);
+    const RadixPlan d = plan_radix(vocab, 1, 0.5f);      // the extents of a row; every pass is launched, the rows decide on the device which they run
+    const size_t row_stride = radix_row_stride(vocab), need = row_stride * (size_t)rows;
+    if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, "%s: scratch must be 8-byte aligned", who);
+    RadixRows r{};
+    RadixParams& p = r.p;
+    char* base = reinterpret_cast<char*>(scratch);
+    p.hdr = reinterpret_cast<RadixHeader*>(base);
+    p.khist = reinterpret_cast<uint32_t*>(base + sizeof(RadixHeader));
+    p.phist = reinterpret_cast<unsigned long long*>(p.khist + (size_t)kRadixPasses * kRadixBins);
+    p.red = reinterpret_cast<float*>(base + sizeof(RadixHeader) + kRadixHistBytes);
+    p.w = p.red + 2 * kSampBlocks;
+    p.token_out = token_out; p.vocab = vocab; p.softcap = softcap;
+    p.draws = draws; p.pos = positions_dev;
+    r.row_stride = row_stride; r.logits_stride = logits_stride;
+    r.f.table = table; r.f.table_stride = table_stride;
+    const RowRequests q{reinterpret_cast<const RowParams*>(params_dev), advance ? active_dev : nullptr, bias, bias_stride};
+    const int clear_words = (int)((sizeof(RadixHeader) + kRadixHistBytes) / 4);
+    const unsigned R = (unsigned)rows;
+    const dim3 wg(256);
+    hipLaunchKernelGGL(radix_requests_scale_kernel, dim3(d.scale_blocks, R), wg, 0, s, logits, r, q, clear_words);
+    for (int pass = 0; pass < kRadixPasses; ++pass) hipLaunchKernelGGL(radix_requests_kpass_kernel, dim3(d.blocks, R), wg, 0, s, r, q, pass);
+    hipLaunchKernelGGL(radix_requests_prob_kernel, dim3(d.blocks, R), wg, 0, s, r, q, d.scale_blocks);
+    for (int pass = 1; pass < kRadixPasses; ++pass) hipLaunchKernelGGL(radix_requests_ppass_kernel, dim3(d.blocks, R), wg, 0, s, r, q, pass);
+    hipLaunchKernelGGL(radix_requests_mask_kernel, dim3(d.nchunks, R), wg, 0, s, r, q, d.chunk);
+    if (advance) hipLaunchKernelGGL(radix_requests_tail_kernel<true>, dim3(1), wg, 0, s, r, q, rows, d.nchunks, d.chunk);
+    else hipLaunchKernelGGL(radix_requests_tail_kernel<false>, dim3(1), wg, 0, s, r, q, rows, d.nchunks, d.chunk);
+    return check_hip(hipGetLastError(), who);
+}
+
+static int run_argmax_requests(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, const void* params_dev, uint32_t* table,
+                               size_t table_stride, const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes, bool advance, int32_t* positions_dev,
+                               const int32_t* active_dev, hipStream_t s, const char* who)
+{
+    if (const int rc = check_requests(logits, logits_stride, token_out, rows, vocab, params_dev, table, table_stride, bias, bias_stride, advance, positions_dev, active_dev, who))
+        return rc;
+    const size_t need = kArgmaxRowBytes * (size_t)rows;
+    if (!scratch || scratch_bytes < need) return set_error(MILA_E_SCRATCH_TOO_SMALL, "%s: scratch %zu bytes < required %zu", who, scratch_bytes, need);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 3u) == 0, "%s: scratch must be 4-byte aligned", who);
+    float* pv = reinterpret_cast<float*>(scratch);
+    int blocks = (vocab + 255) / 256;
+    if (blocks > kArgmaxBlocks) blocks = kArgmaxBlocks;
+    const int row_floats = (int)(kArgmaxRowBytes / sizeof(float));
+    const RowRequests q{reinterpret_cast<const RowParams*>(params_dev), advance ? active_dev : nullptr, bias, bias_stride};
+    hipLaunchKernelGGL(argmax_requests_partial_kernel, dim3(blocks, (unsigned)rows), dim3(256), 0, s, logits, logits_stride, softcap, q, table, table_stride, pv, row_floats, vocab);
+    if (advance) hipLaunchKernelGGL(argmax_requests_final_kernel<true>, dim3(rows), dim3(256), 0, s, pv, token_out, positions_dev, q, blocks, row_floats, table, table_stride);
+    else hipLaunchKernelGGL(argmax_requests_final_kernel<false>, dim3(rows), dim3(256), 0, s, pv, token_out, positions_dev, q, blocks, row_floats, table, table_stride);
+    return check_hip(hipGetLastError(), who);
+}
+
+// ---- the automaton per row (mila_cdna4.h: row requests): token_automaton_kernel with the image of row b taken from a descriptor in device memory.  A null descriptor
+// (class_of == nullptr): the row has no automaton -- its workgroups return before they read a word, write nothing and take no ticket.  The state word, the ticket and the
+// ordering argument are token_automaton_kernel's: lane 0 of every workgroup reads state and token before it draws, the holder of the row's last ticket stores.
+struct AutomatonRow                 // = mila_token_automaton_row
+{
+    const uint16_t* class_of;
+    const uint16_t* next;
+    int32_t S, C;
+};
+static_assert(sizeof(AutomatonRow) == sizeof(mila_token_automaton_row) && sizeof(AutomatonRow) == 24, "AutomatonRow");
+
+template <bool STEP>
+__global__ __launch_bounds__(256) void token_automaton_rows_kernel(float* __restrict__ eff, size_t eff_stride, const float* __restrict__ base, size_t base_stride,
+                                                                   const AutomatonRow* __restrict__ desc, int32_t* state_dev, const int32_t* __restrict__ token_dev,
+                                                                   const int32_t* __restrict__ active_dev, uint32_t* ticket_dev, int vocab, int vec)
+{
+    const int b = blockIdx.y;
+    const AutomatonRow a = desc[b];
+    if (a.class_of == nullptr) return;
+    if (STEP && active_dev && active_dev[b] == 0) return;      // (both uniform over the row's workgroups: none of them takes a ticket)
+    const uint16_t* __restrict__ class_of = a.class_of;
+    const uint16_t* __restrict__ next = a.next;
+    const int S = a.S, C = a.C;
+    __shared__ int s_state;
+    if (threadIdx.x == 0)
+    {
+        int s = __hip_atomic_load(state_dev + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)s >= (unsigned)S) s = 0;
+        if (STEP)
+        {
+            const int t = token_dev[b];
+            const int s2 = automaton_advance(s, t, class_of, next, S, C, vocab);
+            const unsigned ticket = __hip_atomic_fetch_add(ticket_dev + b, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            if (ticket == gridDim.x - 1)
+            {
+                __hip_atomic_store(state_dev + b, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(ticket_dev + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            s = s2;
+        }
+        s_state = s;
+    }
+    __syncthreads();
+    automaton_walk(eff, eff_stride, base, base_stride, b, class_of, next, s_state, C, vocab, vec && (reinterpret_cast<uintptr_t>(class_of) & 7u) == 0);
+}
+
+__global__ __launch_bounds__(64) void token_automaton_row_set_kernel(AutomatonRow* __restrict__ dst, const AutomatonRow v)
+{
+    if (threadIdx.x == 0) *dst = v;
+}
+
 }  // namespace mila
 
 using namespace mila;
@@ -1901,6 +2212,116 @@ size_t mila_cdna4_sample_radix_plan_describe(int vocab, int top_k, float top_p, 
     if (vocab <= 0 || top_k < 0 || !(top_p > 0.0f)) return 0;
     const RadixPlan d = plan_radix(vocab, top_k, top_p);
     return 1 + snprintf(buf, buf ? cap : 0, "%d:%d:%d:%zu", d.launches, d.k_passes, d.p_passes, d.scratch_need);
+}
+
+// ---- row requests (mila_cdna4.h: row requests)
+size_t mila_cdna4_sample_row_params_bytes(int rows) { return (rows >= 1 && rows <= 4) ? (size_t)rows * sizeof(RowParams) : 0; }
+
+int mila_cdna4_sample_row_params_set(void* params_dev, int row, const mila_sample_row_params* params, mila_stream_t stream)
+{
+    const char* who = "sample_row_params_set";
+    MILA_REQUIRE(params_dev && params, "%s: null pointer", who);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(params_dev) & 3u) == 0, "%s: params_dev must be 4-byte aligned", who);
+    MILA_REQUIRE(row >= 0 && row < 4, "%s: row=%d outside 0 .. 3", who, row);
+    MILA_REQUIRE(std::isfinite(params->temperature), "%s: temperature is not finite", who);
+    MILA_REQUIRE(params->top_k >= 0 && params->top_p > 0.0f, "%s: need top_k >= 0, top_p > 0", who);
+    const mila_sample_filters flt{params->min_p, params->repetition_penalty, params->presence_penalty, params->frequency_penalty};
+    SampleFilter f{};
+    if (const int rc = make_filter(&flt, nullptr, 0, 1, 1, f, who)) return rc;
+    const RowParams v{params->temperature, params->top_k, params->top_p, f.min_p, f.rep, f.inv_rep, f.pres, f.freq};      // (inv_rep: divided here, as make_filter does)
+    hipLaunchKernelGGL(sample_row_params_set_kernel, dim3(1), dim3(64), 0, as_stream(stream), reinterpret_cast<RowParams*>(params_dev) + row, v);
+    MILA_LAUNCH_CHECK(who);
+}
+
+int mila_cdna4_sample_radix_requests_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, const void* params_dev,
+                                               const float* draws, uint32_t* table, size_t table_stride, const float* bias, size_t bias_stride, void* scratch,
+                                               size_t scratch_bytes, mila_stream_t stream)
+{
+    return run_radix_requests(logits, logits_stride, token_out, rows, vocab, softcap, params_dev, draws, table, table_stride, bias, bias_stride, scratch, scratch_bytes, false,
+                              nullptr, nullptr, as_stream(stream), "sample_radix_requests_rows_fp32");
+}
+
+int mila_cdna4_sample_radix_requests_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                       const void* params_dev, const float* draws, uint32_t* table, size_t table_stride, const float* bias,
+                                                       size_t bias_stride, void* scratch, size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev,
+                                                       mila_stream_t stream)
+{
+    return run_radix_requests(logits, logits_stride, token_out, rows, vocab, softcap, params_dev, draws, table, table_stride, bias, bias_stride, scratch, scratch_bytes, true,
+                              positions_dev, active_dev, as_stream(stream), "sample_radix_requests_rows_advance_fp32");
+}
+
+int mila_cdna4_sample_argmax_requests_rows_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap, const void* params_dev,
+                                                uint32_t* table, size_t table_stride, const float* bias, size_t bias_stride, void* scratch, size_t scratch_bytes,
+                                                mila_stream_t stream)
+{
+    return run_argmax_requests(logits, logits_stride, token_out, rows, vocab, softcap, params_dev, table, table_stride, bias, bias_stride, scratch, scratch_bytes, false, nullptr,
+                               nullptr, as_stream(stream), "sample_argmax_requests_rows_fp32");
+}
+
+int mila_cdna4_sample_argmax_requests_rows_advance_fp32(const float* logits, size_t logits_stride, int32_t* token_out, int rows, int vocab, float softcap,
+                                                        const void* params_dev, uint32_t* table, size_t table_stride, const float* bias, size_t bias_stride, void* scratch,
+                                                        size_t scratch_bytes, int32_t* positions_dev, const int32_t* active_dev, mila_stream_t stream)
+{
+    return run_argmax_requests(logits, logits_stride, token_out, rows, vocab, softcap, params_dev, table, table_stride, bias, bias_stride, scratch, scratch_bytes, true,
+                               positions_dev, active_dev, as_stream(stream), "sample_argmax_requests_rows_advance_fp32");
+}
+
+size_t mila_cdna4_token_automaton_rows_bytes(int rows) { return (rows >= 1 && rows <= 4) ? (size_t)rows * sizeof(AutomatonRow) : 0; }
+
+int mila_cdna4_token_automaton_rows_set(void* desc_dev, int row, const uint16_t* class_of, const uint16_t* next, int S, int C, int vocab, mila_stream_t stream)
+{
+    const char* who = "token_automaton_rows_set";
+    MILA_REQUIRE(desc_dev, "%s: null pointer", who);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(desc_dev) & 7u) == 0, "%s: desc_dev must be 8-byte aligned", who);
+    MILA_REQUIRE(row >= 0 && row < 4, "%s: row=%d outside 0 .. 3", who, row);
+    AutomatonRow v{nullptr, nullptr, 0, 0};
+    if (class_of || next)
+    {
+        MILA_REQUIRE(class_of && next, "%s: class_of and next go together", who);
+        MILA_REQUIRE(automaton_shape_ok(vocab, S, C), "%s: need vocab > 0, 1 <= S, C <= 65535 and S * C * 2 bytes <= 256 MiB", who);
+        MILA_REQUIRE(((reinterpret_cast<uintptr_t>(class_of) | reinterpret_cast<uintptr_t>(next)) & 1u) == 0, "%s: class_of and next must be 2-byte aligned", who);
+        v = AutomatonRow{class_of, next, S, C};
+    }
+    hipLaunchKernelGGL(token_automaton_row_set_kernel, dim3(1), dim3(64), 0, as_stream(stream), reinterpret_cast<AutomatonRow*>(desc_dev) + row, v);
+    MILA_LAUNCH_CHECK(who);
+}
+
+static int launch_token_automaton_rows(bool step, float* eff, size_t eff_stride, const float* base, size_t base_stride, const void* desc_dev, int32_t* state_dev,
+                                       const int32_t* token_dev, const int32_t* active_dev, uint32_t* ticket_dev, int rows, int vocab, mila_stream_t stream, const char* who)
+{
+    MILA_REQUIRE(eff && desc_dev && state_dev && (!step || (token_dev && ticket_dev)), "%s: null pointer", who);
+    MILA_REQUIRE((reinterpret_cast<uintptr_t>(desc_dev) & 7u) == 0, "%s: desc_dev must be 8-byte aligned", who);
+    MILA_REQUIRE(rows >= 1 && rows <= 4, "%s: rows must be 1 .. 4", who);
+    MILA_REQUIRE(vocab > 0, "%s: vocab must be positive", who);
+    MILA_REQUIRE(rows == 1 || eff_stride >= (size_t)vocab, "%s: eff_stride must be at least vocab", who);
+    MILA_REQUIRE(!base || base_stride == 0 || base_stride >= (size_t)vocab, "%s: base_stride must be 0 (shared) or at least vocab", who);
+    auto aligned = [](const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    MILA_REQUIRE(aligned(eff, 4) && aligned(base, 4), "%s: eff and base must be 4-byte aligned", who);
+    const int vec = aligned(eff, 16) && eff_stride % 4 == 0 && (!base || (aligned(base, 16) && base_stride % 4 == 0));      // (class_of: per row, on the device)
+    int blocks = (vocab + 1023) / 1024;
+    if (blocks > 256) blocks = 256;
+    const AutomatonRow* desc = reinterpret_cast<const AutomatonRow*>(desc_dev);
+    if (step)
+        hipLaunchKernelGGL(token_automaton_rows_kernel<true>, dim3(blocks, rows), dim3(256), 0, as_stream(stream), eff, eff_stride, base, base_stride, desc, state_dev, token_dev,
+                           active_dev, ticket_dev, vocab, vec);
+    else
+        hipLaunchKernelGGL(token_automaton_rows_kernel<false>, dim3(blocks, rows), dim3(256), 0, as_stream(stream), eff, eff_stride, base, base_stride, desc, state_dev, nullptr,
+                           nullptr, nullptr, vocab, vec);
+    MILA_LAUNCH_CHECK(who);
+}
+
+int mila_cdna4_token_automaton_rows_compose(float* eff, size_t eff_stride, const float* base, size_t base_stride, const void* desc_dev, int32_t* state_dev, int rows,
+                                            int vocab, mila_stream_t stream)
+{
+    return launch_token_automaton_rows(false, eff, eff_stride, base, base_stride, desc_dev, state_dev, nullptr, nullptr, nullptr, rows, vocab, stream,
+                                       "token_automaton_rows_compose");
+}
+
+int mila_cdna4_token_automaton_rows_step(float* eff, size_t eff_stride, const float* base, size_t base_stride, const void* desc_dev, int32_t* state_dev,
+                                         const int32_t* token_dev, const int32_t* active_dev, uint32_t* ticket_dev, int rows, int vocab, mila_stream_t stream)
+{
+    return launch_token_automaton_rows(true, eff, eff_stride, base, base_stride, desc_dev, state_dev, token_dev, active_dev, ticket_dev, rows, vocab, stream,
+                                       "token_automaton_rows_step");
 }
 
 }  // extern "C"

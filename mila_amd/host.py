@@ -249,6 +249,17 @@ class TokenAutomaton:
         return TokenAutomatonRequestC(self.class_of.ctypes.data, self.vocab, self.next.ctypes.data, self.num_states, self.num_classes, self.start)
 
 
+class GemmaRowRequestC(C.Structure):
+    """mila_gemma_row_request (host/src/gemma_runner.cpp): one row of GemmaModel::generateRequests"""
+    _fields_ = [("prompt", C.c_void_p), ("n_prompt", C.c_int64), ("stop_tokens", C.c_void_p), ("n_stop", C.c_int64), ("bias", C.c_void_p), ("automaton", C.c_void_p),
+                ("seed", C.c_uint64), ("temperature", C.c_float), ("top_p", C.c_float), ("filters", C.c_float * 4), ("top_k", C.c_int32), ("max_new", C.c_int32),
+                ("logprobs", C.c_int32), ("speculative", C.c_int32)]
+
+
+ROW_REQUEST_KEYS = ("prompt", "seed", "max_new_tokens", "stop_tokens", "temperature", "top_k", "top_p", "logprobs", "min_p", "repetition_penalty", "presence_penalty",
+                    "frequency_penalty", "logit_bias", "banned_tokens", "allowed_tokens", "min_tokens", "automaton", "speculative_sampling", "speculate_constrained", "draft_hint")
+
+
 class Gemma:
     """GemmaTransformer<policy> with synthetic weights on cuda:0."""
 
@@ -619,6 +630,64 @@ class Gemma:
             return logits, toks, pos
         _check(lib.mila_gemma_decode_rows(self.h, int(B), int(max_position), {"fused": 1, "graph": 2}[mode], int(bool(greedy)), logits.ctypes.data, toks.ctypes.data, pos.ctypes.data))
         return logits, toks, pos
+
+    def set_rows_requests(self, requests=None, draws=None):
+        """ROW REQUESTS for the rows steps that follow (GemmaTransformer::setRowsRequests; include/mila_cdna4.h: row requests): requests = one dict per row with any of
+        temperature (<= 0: greedy; default 0), top_k, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty.  The parameters go into records in device
+        memory: decode_rows / time_decode_rows then end in the requests tails whatever their greedy / sampling arguments say (decode_rows(sampling=(1, 0, 1),
+        draws=...) still delivers one draw per row), and rows_graph_info()["captures"] moves only when a CLASS fact changes -- whether there are greedy rows,
+        stochastic rows, a constrained row, a row with an automaton, a penalized row.  None clears the requests."""
+        lib = load()
+        lib.mila_gemma_set_rows_requests.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        if not requests:
+            _check(lib.mila_gemma_set_rows_requests(self.h, None, 0, None))
+            return
+        rows = []
+        for q in requests:
+            unknown = set(q) - {"temperature", "top_k", "top_p", "min_p", "repetition_penalty", "presence_penalty", "frequency_penalty"}
+            if unknown:
+                raise ValueError("set_rows_requests: unknown keys %s" % sorted(unknown))
+            rows.append([q.get("temperature", 0.0), q.get("top_k", 0), q.get("top_p", 1.0), q.get("min_p", 0.0), q.get("repetition_penalty", 1.0), q.get("presence_penalty", 0.0),
+                         q.get("frequency_penalty", 0.0)])
+        p = np.ascontiguousarray(rows, dtype=np.float32)
+        d = None if draws is None else np.ascontiguousarray(draws, dtype=np.float32)
+        if d is not None and d.size != len(rows):
+            raise ValueError("set_rows_requests: one draw per row")
+        _check(lib.mila_gemma_set_rows_requests(self.h, p.ctypes.data, len(rows), None if d is None else d.ctypes.data))
+
+    def set_row_token_bias(self, row, bias=None, fill=0.0):
+        """row `row`'s bias table for the requests samplers (set_token_bias's arguments, per row); None: no bias.  A row with an automaton: set the automaton first."""
+        lib = load()
+        lib.mila_gemma_set_row_token_bias.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int64]
+        if bias is None:
+            _check(lib.mila_gemma_set_row_token_bias(self.h, int(row), 0.0, None, None, -1))
+            return
+        items = list(bias.items()) if hasattr(bias, "items") else list(bias)
+        ids = np.ascontiguousarray(_id_list([k for k, _ in items], "set_row_token_bias", self.vocab), dtype=np.int32)
+        if len(set(ids.tolist())) != ids.size:
+            raise ValueError("set_row_token_bias: an id occurs twice")
+        vals = np.ascontiguousarray([v for _, v in items], dtype=np.float32)
+        _check(lib.mila_gemma_set_row_token_bias(self.h, int(row), float(fill), ids.ctypes.data if ids.size else None, vals.ctypes.data if ids.size else None, int(ids.size)))
+
+    def set_row_token_automaton(self, row, automaton):
+        """row `row`'s automaton for the requests step (set_token_automaton's, per row): validated, uploaded, at its start state; None: the row has none"""
+        lib = load()
+        lib.mila_gemma_set_row_token_automaton.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        if automaton is None:
+            _check(lib.mila_gemma_set_row_token_automaton(self.h, int(row), None, 0, None, 0, 0, 0))
+            return
+        a = automaton
+        _check(lib.mila_gemma_set_row_token_automaton(self.h, int(row), a.class_of.ctypes.data, a.vocab, a.next.ctypes.data, a.num_states, a.num_classes, a.start))
+
+    def row_token_automaton_state(self, row, table=False):
+        """-> row `row`'s automaton state (None: the row has no automaton), read synchronously; table=True: (state, the row's effective table float32 [vocab])"""
+        lib = load()
+        lib.mila_gemma_row_token_automaton_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        st, on = C.c_int32(), C.c_int32()
+        eff = np.zeros(self.vocab, dtype=np.float32) if table else None
+        _check(lib.mila_gemma_row_token_automaton_state(self.h, int(row), C.byref(st), C.byref(on), eff.ctypes.data if table else None))
+        state = int(st.value) if on.value else None
+        return (state, eff) if table else state
 
     def rows_graph_info(self):
         """{"captures": captures of the rows graph so far, "nodes": kernel nodes of the captured rows step}"""
@@ -1059,6 +1128,79 @@ class GemmaModel:
         if logprobs is None:
             return rows
         return [rows[b] + ([(np.float32(lp[b, i]), ids[b, i, :top_n].copy(), tlp[b, i, :top_n].copy()) for i in range(min(int(lp_counts[b]), out.shape[1]))],) for b in range(len(prompts))]
+
+    def generate_requests(self, requests, logprobs=None):
+        """GemmaModel::generateRequests: up to max_batch requests that need NOT agree, request b in row b.  requests: a list of dicts with generate()'s keyword names
+        (max_new_tokens, stop_tokens, temperature, top_k, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, banned_tokens,
+        allowed_tokens, min_tokens, automaton) plus "prompt" and "seed" (the row's generator; default 0).  Row b gives what generate() gives for request b alone on
+        a one-sequence model after the same seed.  logprobs: ONE n for the call; a row's own "logprobs" key that differs is refused, as are the speculative keys
+        (speculative_sampling, speculate_constrained, draft_hint).  -> per row what generate_batch returns -- (tokens, finish reason[, log-probability entries]) --
+        plus, for a row with an automaton, the state it ended in as a last element."""
+        lib = load()
+        n = len(requests)
+        keep, rq = [], (GemmaRowRequestC * max(n, 1))()
+        vocab = self.vocab_size()
+        top_n = -1 if logprobs is None else _logprobs_n(logprobs)
+        for b, q in enumerate(requests):
+            unknown = set(q) - set(ROW_REQUEST_KEYS)
+            if unknown:
+                raise ValueError("GemmaModel.generate_requests: row %d: unknown keys %s" % (b, sorted(unknown)))
+            try:
+                f = _filters(q.get("min_p", 0.0), q.get("repetition_penalty", 1.0), q.get("presence_penalty", 0.0), q.get("frequency_penalty", 0.0))
+                bias = _bias_request(q.get("logit_bias"), q.get("banned_tokens", ()), q.get("allowed_tokens", ()), q.get("min_tokens", 0), q.get("stop_tokens", ()),
+                                     q.get("max_new_tokens"), vocab)
+                own = q.get("logprobs", logprobs)
+                own = -1 if own is None else _logprobs_n(own)
+            except ValueError as e:
+                raise ValueError("GemmaModel.generate_requests: row %d: %s" % (b, e)) from None
+            automaton = q.get("automaton")
+            if automaton is not None and not isinstance(automaton, TokenAutomaton):
+                raise ValueError("GemmaModel.generate_requests: row %d: automaton must be a host.TokenAutomaton" % b)
+            pr = np.ascontiguousarray(q.get("prompt", ()), dtype=np.int32)
+            st = np.ascontiguousarray(list(q.get("stop_tokens", ())), dtype=np.int32)
+            areq = None if automaton is None else automaton._request()
+            keep.append((pr, st, bias, areq, automaton))
+            r = rq[b]
+            r.prompt, r.n_prompt = pr.ctypes.data if pr.size else None, int(pr.size)
+            r.stop_tokens, r.n_stop = st.ctypes.data if st.size else None, int(st.size)
+            r.bias = None if bias is None else C.addressof(bias[0])
+            r.automaton = None if areq is None else C.addressof(areq)
+            r.seed = int(q.get("seed", 0))
+            r.temperature, r.top_k, r.top_p = float(q.get("temperature", 1.0)), int(q.get("top_k", 1)), float(q.get("top_p", 1.0))
+            r.filters = (C.c_float * 4)(*f)
+            mx = q.get("max_new_tokens")
+            r.max_new = -1 if mx is None else int(mx)
+            r.logprobs = own
+            r.speculative = (1 if q.get("speculative_sampling") else 0) | (2 if q.get("speculate_constrained") else 0) | (4 if q.get("draft_hint") is not None else 0)
+        caps = [int(q["max_new_tokens"]) if q.get("max_new_tokens") is not None else 1 << 16 for q in requests]
+        cap = max(caps + [1])
+        out = np.zeros((max(n, 1), cap), dtype=np.int32)
+        counts, status, lp_counts, states, has_state = (np.zeros(max(n, 1), dtype=t) for t in (np.int64, np.int32, np.int64, np.int32, np.int32))
+        width = max(top_n, 1)
+        with_lp = top_n >= 0
+        lp, ids, tlp = (np.zeros(out.shape if with_lp else (1, 1), dtype=np.float32), np.zeros((out.shape if with_lp else (1, 1)) + (width,), dtype=np.int32),
+                        np.zeros((out.shape if with_lp else (1, 1)) + (width,), dtype=np.float32))
+        lib.mila_gemma_model_generate_requests.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 8
+        _check(lib.mila_gemma_model_generate_requests(self.h, C.addressof(rq), n, out.ctypes.data, cap, counts.ctypes.data, status.ctypes.data,
+                                                      lp.ctypes.data if with_lp else None, ids.ctypes.data if with_lp else None, tlp.ctypes.data if with_lp else None,
+                                                      lp_counts.ctypes.data, states.ctypes.data, has_state.ctypes.data))
+        rows = []
+        for b in range(n):
+            row = (out[b, :min(int(counts[b]), cap)].tolist(), GENERATE_STATUS[int(status[b])])
+            if with_lp:
+                row = row + ([(np.float32(lp[b, i]), ids[b, i, :top_n].copy(), tlp[b, i, :top_n].copy()) for i in range(min(int(lp_counts[b]), cap))],)
+            if requests[b].get("automaton") is not None:
+                row = row + (int(states[b]) if has_state[b] else None,)
+            rows.append(row)
+        return rows
+
+    def rows_graph_info(self):
+        """{"captures": captures of the model's rows graph so far, "nodes": kernel nodes of the captured rows step}"""
+        lib = load()
+        lib.mila_gemma_model_rows_graph_info.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_int64 * 2)()
+        _check(lib.mila_gemma_model_rows_graph_info(self.h, out))
+        return {"captures": int(out[0]), "nodes": int(out[1])}
 
     def _generate_batch(self, prompts, max_new_tokens=None, stop_tokens=(), temperature=1.0, top_k=1, top_p=1.0, seed=0, logprobs=None):
         """GemmaModel::generateBatch: up to max_batch prompts at once, prompt b in row b -> [(tokens, finish reason)] per prompt, by generate()'s rules.  Row b samples

@@ -16,6 +16,7 @@
 #include <functional>
 #include <map>
 #include <optional>
+#include <span>
 
 #include <hip/hip_runtime_api.h>
 
@@ -585,7 +586,7 @@ namespace Mila::Dnn
             return *logits_;
         }
         /// forget row b: position 0, inactive (its caches are overwritten positionally by the next prefillRow)
-        void resetRow( int b ) { requireRows( b ); setRowWord( rows_->pos->data(), b, 0 ); setRowWord( rows_->active->data(), b, 0 ); }
+        void resetRow( int b ) { requireRows( b ); setRowWord( rows_->pos->data(), b, 0 ); setRowWord( rows_->active->data(), b, 0 ); noteRowActive( b, false ); }
         /// rewindKvCache for one row: row b goes on from `position`, given that `written` positions were appended to it; its caches are overwritten positionally.
         /// false when the request is out of range (rows live on unbounded caches: no ring to refuse)
         bool rewindKvCacheRow( int b, dim_t position, dim_t written )
@@ -595,7 +596,7 @@ namespace Mila::Dnn
             setRowWord( rows_->pos->data(), b, static_cast<int32_t>( position ) );
             return true;
         }
-        void setRowActive( int b, bool on ) { requireRows( b ); setRowWord( rows_->active->data(), b, on ? 1 : 0 ); }
+        void setRowActive( int b, bool on ) { requireRows( b ); setRowWord( rows_->active->data(), b, on ? 1 : 0 ); noteRowActive( b, on ); }
         void setRowToken( int b, int32_t token ) { requireRows( b ); setRowWord( rows_->tok->data(), b, token ); }
         void setRowPosition( int b, dim_t position ) { requireRows( b ); checkPosition( position, 1 ); setRowWord( rows_->pos->data(), b, static_cast<int32_t>( position ) ); }
         /// row b's next token from row b's logits, into the rows token buffer: the greedy sampler, or the radix pipeline at the caller's draw r (the sampler
@@ -661,16 +662,24 @@ namespace Mila::Dnn
             const hipError_t e = hipGraphInstantiate( &rows_graph_exec_, rows_graph_, nullptr, nullptr, 0 );
             if ( e != hipSuccess ) { rows_graph_exec_ = nullptr; destroyGraphRows(); hipCheck( e, "hipGraphInstantiate" ); }
             rows_captured_B_ = B; rows_captured_greedy_ = greedy; rows_captured_band_ = band;
-            rows_captured_sampling_ = rows_sampling_; rows_captured_draws_ = rows_draws_;
+            rows_captured_sampling_ = rows_sampling_; rows_captured_draws_ = row_requests_.empty() ? rows_draws_ : row_request_draws_;
             rows_captured_filters_ = filters_;
             rows_captured_bias_ = bias_on_;
             rows_captured_lp_ = step_lp_;
+            rows_captured_key_ = rowsRequestKey();
             ++rows_graph_captures_;
         }
         /// capture on first use and whenever the step changes: another row count, sampler tail, or the live-length bucket of the largest active row
         void ensureGraphRows( int B, dim_t max_position, bool greedy )
         {
-            if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) || rows_captured_lp_ != step_lp_ ||
+            if ( !row_requests_.empty() )      // row requests: the class facts, the row count, the bucket and the log-probability setting -- no parameter of any row
+            {
+                if ( !rows_graph_exec_ || rows_captured_B_ != B || rows_captured_band_ != bandBucket( max_position ) || rows_captured_lp_ != step_lp_ || rows_captured_key_ != rowsRequestKey() ||
+                     rows_captured_draws_ != row_request_draws_ )
+                    captureGraphRows( B, max_position, greedy );
+                return;
+            }
+            if ( !rows_graph_exec_ || rows_captured_key_.on || rows_captured_B_ != B || rows_captured_greedy_ != greedy || rows_captured_band_ != bandBucket( max_position ) || rows_captured_lp_ != step_lp_ ||
                  ( !greedy && ( !sameSampling( rows_captured_sampling_, rows_sampling_ ) || rows_captured_draws_ != rows_draws_ ) ) ||
                  ( greedy && !samePenalties( rows_captured_filters_, filters_ ) ) || ( ( greedy || rowsSamplesInStep() ) && rows_captured_bias_ != bias_on_ ) )
                 captureGraphRows( B, max_position, greedy );
@@ -687,6 +696,134 @@ namespace Mila::Dnn
             if ( sp ) sp->checkFilters( "GemmaTransformer::setRowsSampling" );
             if ( sp && sp->penalized() ) ensureTokenTable();
             rows_sampling_ = sp; rows_draws_ = draws;
+        }
+        /// ROW REQUESTS (mila_cdna4.h: row requests): rows 0 .. n - 1 of the rows step each sample under their OWN parameters -- temperature <= 0 makes a row greedy --
+        /// from records in device memory, written here in stream order.  While requests are installed decodeRows / captureGraphRows / ensureGraphRows ignore their
+        /// `greedy` argument and setRowsSampling's setting: the step ends in the requests tails (enqueueRowsRequestsStepAndTail).  draws: device address of max_batch
+        /// floats of host-visible memory, row b's draw at [ b ] (needed when a row is stochastic).  The rows graph is captured again only when a CLASS fact changes
+        /// (whether there are greedy rows, stochastic rows, a constrained row, a row with an automaton, a penalized row), never for other parameters of the same class.
+        /// Every record is validated before anything is written.  clearRowsRequests() returns the rows step to the shared parameters.
+        void setRowsRequests( std::span<const SamplingParams> requests, const float* draws )
+        {
+            requireRows( 0 );
+            if ( requests.empty() || static_cast<dim_t>( requests.size() ) > cfg_.max_batch )
+                throw std::invalid_argument( "GemmaTransformer::setRowsRequests: " + std::to_string( requests.size() ) + " requests for max_batch " + std::to_string( cfg_.max_batch ) );
+            bool penalized = false;
+            for ( size_t b = 0; b < requests.size(); ++b )
+            {
+                const auto& q = requests[ b ];
+                const std::string who = "GemmaTransformer::setRowsRequests: row " + std::to_string( b );
+                if ( !std::isfinite( q.temperature ) ) throw std::invalid_argument( who + ": temperature is not finite" );
+                if ( q.top_k < 0 || !( q.top_p > 0.0f ) ) throw std::invalid_argument( who + ": need top_k >= 0, top_p > 0" );
+                q.checkFilters( who.c_str() );
+                penalized = penalized || q.penalized();
+            }
+            if ( penalized ) ensureTokenTable();
+            if ( !row_params_ )
+            {
+                row_params_ = std::make_unique<TokenTensor>( ctx_->getDeviceId(), shape_t{ static_cast<dim_t>( mila_cdna4_sample_row_params_bytes( static_cast<int>( cfg_.max_batch ) ) / 4 ) } );
+                Compute::rocmCheck( mila_cdna4_memset_zero( row_params_->rawData(), row_params_->sizeInBytes(), ctx_->getStream() ) );
+            }
+            for ( int b = 0; b < static_cast<int>( cfg_.max_batch ); ++b )      // a row without a request: greedy and neutral (it stays inactive)
+            {
+                const SamplingParams q = static_cast<size_t>( b ) < requests.size() ? requests[ static_cast<size_t>( b ) ] : SamplingParams{};
+                mila_sample_row_params rec{};
+                rec.temperature = static_cast<size_t>( b ) < requests.size() ? q.temperature : 0.0f;
+                rec.top_k = q.top_k; rec.top_p = q.top_p; rec.min_p = q.min_p;
+                rec.repetition_penalty = q.repetition_penalty; rec.presence_penalty = q.presence_penalty; rec.frequency_penalty = q.frequency_penalty;
+                Compute::rocmCheck( mila_cdna4_sample_row_params_set( row_params_->rawData(), b, &rec, ctx_->getStream() ) );
+            }
+            row_requests_.assign( requests.begin(), requests.end() );
+            row_request_draws_ = draws;
+            if ( !row_masks_ )
+            {
+                row_masks_ = std::make_unique<TokenTensor>( ctx_->getDeviceId(), shape_t{ 2 * cfg_.max_batch } );
+                for ( int b = 0; b < static_cast<int>( cfg_.max_batch ); ++b ) refreshRowMasks( b );
+            }
+        }
+        void clearRowsRequests() noexcept { row_requests_.clear(); row_request_draws_ = nullptr; }
+        bool rowsRequestsOn() const noexcept { return !row_requests_.empty(); }
+        /// row b's bias table for the requests samplers (setTokenBias's arguments): written into the row's effective table, or -- when the row has an automaton --
+        /// into the table its automaton composes from (set the automaton FIRST).  clearRowTokenBias: zeros.  stage / commit: the min_tokens restore of that row.
+        void setRowTokenBias( int b, float fill, const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            requireRows( b );
+            if ( std::isnan( fill ) || ( std::isinf( fill ) && fill > 0.0f ) ) throw std::invalid_argument( "GemmaTransformer::setRowTokenBias: the fill value must be finite or -inf" );
+            checkBiasEntries( ids_host, values_host, n, "GemmaTransformer::setRowTokenBias" );
+            ensureRowBias();
+            const bool automaton = row_automata_ && row_automata_->on( b );
+            row_bias_->apply( b, automaton, fill, ids_host, values_host, n );
+            if ( automaton ) row_automata_->compose( *row_bias_ );
+            refreshRowMasks( b );
+        }
+        void clearRowTokenBias( int b )
+        {
+            requireRows( b );
+            if ( !row_bias_ ) return;
+            row_bias_->clear( b );
+            if ( row_automata_ && row_automata_->on( b ) ) row_automata_->compose( *row_bias_ );
+            refreshRowMasks( b );
+        }
+        void stageRowTokenBiasUpdate( int b, const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            requireRows( b );
+            if ( !row_bias_ || !row_bias_->on( b ) ) throw std::logic_error( "GemmaTransformer::stageRowTokenBiasUpdate: the row has no bias (setRowTokenBias)" );
+            checkBiasEntries( ids_host, values_host, n, "GemmaTransformer::stageRowTokenBiasUpdate" );
+            row_bias_->stage( b, ids_host, values_host, n );
+        }
+        void commitRowTokenBiasUpdate( int b )
+        {
+            requireRows( b );
+            if ( !row_bias_ || !row_bias_->on( b ) ) throw std::logic_error( "GemmaTransformer::commitRowTokenBiasUpdate: the row has no bias (setRowTokenBias)" );
+            row_bias_->commit( b );
+            if ( row_automata_ && row_automata_->on( b ) ) row_automata_->compose( *row_bias_ );
+        }
+        /// row b's automaton: validated, uploaded, the state at its start, the row's effective table composed over zeros (a bias set afterwards composes again)
+        void setRowTokenAutomaton( int b, const TokenAutomaton& a )
+        {
+            requireRows( b );
+            a.validate( cfg_.vocab_size );
+            ensureRowBias();
+            if ( !row_automata_ ) row_automata_ = std::make_unique<Compute::RocmTokenAutomatonRows>( ctx_, cfg_.vocab_size, static_cast<int>( cfg_.max_batch ) );
+            row_bias_->clear( b );
+            row_automata_->set( b, a.class_of.data(), a.next.data(), a.num_states, a.num_classes, a.start );
+            row_automata_->compose( *row_bias_ );
+            refreshRowMasks( b );
+        }
+        void clearRowTokenAutomaton( int b )
+        {
+            requireRows( b );
+            if ( !row_automata_ || !row_automata_->on( b ) ) return;
+            row_automata_->clear( b );
+            row_bias_->clear( b );
+            refreshRowMasks( b );
+        }
+        std::optional<int32_t> rowTokenAutomatonState( int b )
+        {
+            requireRows( b );
+            if ( !row_automata_ || !row_automata_->on( b ) ) return std::nullopt;
+            return row_automata_->readState( b );
+        }
+        Compute::RocmTokenBiasRows* rowTokenBias() noexcept { return row_bias_.get(); }
+        /// row b's next token from row b's logits through the ONE-ROW samplers with the row's request (a row's first token, from its prefill's logits; r: the row's
+        /// draw, unused by a greedy row), then the row's automaton advanced by it
+        void sampleRowRequest( int b, float r )
+        {
+            requireRows( b );
+            if ( static_cast<size_t>( b ) >= row_requests_.size() ) throw std::invalid_argument( "GemmaTransformer::sampleRowRequest: row " + std::to_string( b ) + " has no request (setRowsRequests)" );
+            const SamplingParams& q = row_requests_[ static_cast<size_t>( b ) ];
+            const size_t V = static_cast<size_t>( cfg_.vocab_size );
+            const float* logits = rows_->logits->data() + static_cast<size_t>( b ) * V;
+            const float* bias = rowConstrained( b ) ? row_bias_->eff() + static_cast<size_t>( b ) * V : nullptr;
+            const mila_sample_filters f = q.filters();
+            uint32_t* words = tableWords( q, b, true );
+            if ( q.temperature > 0.0f )
+                Compute::rocmCheck( mila_cdna4_sample_radix_biased_fp32( logits, rows_->tok->data() + b, (int)cfg_.vocab_size, cfg_.final_logit_softcapping, q.temperature, q.top_k, q.top_p, r, &f,
+                                                                         words, bias, 0, radix_scratch_->data(), radix_scratch_->sizeInBytes(), ctx_->getStream() ) );
+            else
+                Compute::rocmCheck( mila_cdna4_sample_argmax_biased_fp32( logits, rows_->tok->data() + b, (int)cfg_.vocab_size, cfg_.final_logit_softcapping, &f, words, bias, 0,
+                                                                          sample_scratch_->data(), sample_scratch_->sizeInBytes(), ctx_->getStream() ) );
+            if ( row_automata_ ) row_automata_->stepRow( *row_bias_, b, rows_->tok->data() + b );
         }
         void replayGraphRows()
         {
@@ -1482,6 +1619,7 @@ namespace Mila::Dnn
         void enqueueRowsStepAndTail( int B, dim_t band, bool greedy )
         {
             int partials = 0;
+            if ( !row_requests_.empty() ) { enqueueRowsRequestsStepAndTail( B, band ); return; }
             if ( step_lp_ && !greedy && !rowsSamplesInStep() )
                 throw std::invalid_argument( "GemmaTransformer: token log-probabilities need a sampler tail in the rows step (greedy, or setRowsSampling)" );
             if ( automaton_on_ ) throw std::invalid_argument( "GemmaTransformer: the rows step takes no token automaton: one state per row is not built (clearTokenAutomaton)" );
@@ -1517,6 +1655,36 @@ namespace Mila::Dnn
                 Compute::rocmCheck( mila_cdna4_advance_positions_rows( R.pos->data(), R.active->data(), B, ctx_->getStream() ) );
             // the tail wrote the active rows' tokens: their log-probabilities; an inactive row's outputs stay as they are
             if ( step_lp_ ) lp_op_->forward( R.logits->data(), static_cast<size_t>( cfg_.vocab_size ), R.tok->data(), B, step_lp_->top_n, R.active->data(), nullptr );
+        }
+        /// The rows step of row requests (setRowsRequests): the layers, then the stochastic rows' radix pipeline and the greedy rows' argmax pair, each reading its row's
+        /// record -- the two tails together advance every active row exactly once -- then the automaton rows step and the log-probability launches.  A batch without
+        /// greedy (stochastic) rows holds no argmax (radix) launches.  One linear chain on one stream.
+        void enqueueRowsRequestsStepAndTail( int B, dim_t band )
+        {
+            const RowsRequestKey k = rowsRequestKey();
+            if ( k.stochastic && !row_request_draws_ ) throw std::invalid_argument( "GemmaTransformer: a stochastic row request needs the rows' draws (setRowsRequests)" );
+            if ( k.table && !token_table_ ) throw std::logic_error( "GemmaTransformer: penalties without a token table (setRowsRequests allocates it)" );
+            enqueueFusedStepRows( B, static_cast<int>( band ), nullptr );
+            auto& R = *rows_;
+            const size_t V = static_cast<size_t>( cfg_.vocab_size );
+            uint32_t* table = k.table ? token_table_->data() : nullptr;
+            const float* bias = k.constrained ? row_bias_->eff() : nullptr;
+            if ( k.stochastic )
+                Compute::rocmCheck( mila_cdna4_sample_radix_requests_rows_advance_fp32( R.logits->data(), V, R.tok->data(), B, (int)cfg_.vocab_size, cfg_.final_logit_softcapping,
+                                                                                        row_params_->rawData(), row_request_draws_, table, V, bias, V, R.radix_scratch->data(),
+                                                                                        R.radix_scratch->sizeInBytes(), R.pos->data(), R.active->data(), ctx_->getStream() ) );
+            // (a stochastic row's zero table adds +0.0 in front of a value whose sign of zero the scale launch canonicalizes anyway: one radix call serves both kinds)
+            if ( k.greedy_constrained )
+                Compute::rocmCheck( mila_cdna4_sample_argmax_requests_rows_advance_fp32( R.logits->data(), V, R.tok->data(), B, (int)cfg_.vocab_size, cfg_.final_logit_softcapping,
+                                                                                         row_params_->rawData(), table, V, bias, V, R.sample_scratch->data(),
+                                                                                         R.sample_scratch->sizeInBytes(), R.pos->data(), row_masks_->data(), ctx_->getStream() ) );
+            if ( k.greedy_plain )
+                Compute::rocmCheck( mila_cdna4_sample_argmax_requests_rows_advance_fp32( R.logits->data(), V, R.tok->data(), B, (int)cfg_.vocab_size, cfg_.final_logit_softcapping,
+                                                                                         row_params_->rawData(), table, V, nullptr, 0, R.sample_scratch->data(),
+                                                                                         R.sample_scratch->sizeInBytes(), R.pos->data(), row_masks_->data() + cfg_.max_batch,
+                                                                                         ctx_->getStream() ) );
+            if ( k.automaton ) row_automata_->step( *row_bias_, R.tok->data(), R.active->data(), B );
+            if ( step_lp_ ) lp_op_->forward( R.logits->data(), V, R.tok->data(), B, step_lp_->top_n, R.active->data(), nullptr );
         }
         /// a chain step and its tail: the rows step on the chain attention entry, then the accept kernel on the ONE position word (tok[ 0 ] <- the last accepted
         /// token, result <- {count, accepted tokens}, position += count).  One linear chain on one stream.
@@ -1938,6 +2106,10 @@ namespace Mila::Dnn
             if ( token_table_ ) b += token_table_->stateBytes();
             if ( token_bias_ ) b += token_bias_->stateBytes();
             if ( token_automaton_ ) b += token_automaton_->stateBytes();
+            if ( row_bias_ ) b += row_bias_->stateBytes();
+            if ( row_automata_ ) b += row_automata_->stateBytes();
+            if ( row_params_ ) b += row_params_->sizeInBytes();
+            if ( row_masks_ ) b += row_masks_->sizeInBytes();
             return b;
         }
         size_t requiredOwnStateBytes() const
@@ -1963,6 +2135,10 @@ namespace Mila::Dnn
             if ( token_table_ ) b += Compute::RocmTokenTable::requiredBytes( cfg_.vocab_size, token_table_->rows() );      // the token tables, once a penalty was set
             if ( token_bias_ ) b += Compute::RocmTokenBias::requiredBytes( cfg_.vocab_size );                              // the bias table and its staging, once a bias was set
             if ( token_automaton_ ) b += token_automaton_->requiredBytes();                                              // the automaton's image, words and effective table, once one was set
+            if ( row_bias_ ) b += Compute::RocmTokenBiasRows::requiredBytes( cfg_.vocab_size, static_cast<int>( cfg_.max_batch ) );      // row requests: the rows' tables, once one was set
+            if ( row_automata_ ) b += row_automata_->requiredBytes();                                                    // ... the rows' images, words and descriptors
+            if ( row_params_ ) b += mila_cdna4_sample_row_params_bytes( static_cast<int>( cfg_.max_batch ) );            // ... the rows' sampler records
+            if ( row_masks_ ) b += 2 * static_cast<size_t>( cfg_.max_batch ) * 4;                                        // ... and the two masks per row
             return b;
         }
     public:
@@ -2057,6 +2233,63 @@ namespace Mila::Dnn
         bool automaton_on_ = false;
         std::optional<Compute::RocmTokenAutomaton::Key> captured_automaton_{}, chain_captured_automaton_{};
         std::optional<Compute::RocmTokenAutomaton::Key> automatonKey() const { return automaton_on_ ? std::optional( token_automaton_->key() ) : std::nullopt; }
+        // row requests (mila_cdna4.h: row requests): the rows' sampler records on the device and their host mirror, the rows forms of the bias table and the
+        // automaton (each from its first use on), and the class facts a rows graph was captured with -- parameters WITHIN a class are device words, not graph nodes
+        struct RowsRequestKey
+        {
+            bool on = false, greedy_plain = false, greedy_constrained = false, stochastic = false, constrained = false, automaton = false, table = false;
+            bool operator==( const RowsRequestKey& ) const = default;
+        };
+        // Two masks per row on the device, derived from the active word and the row's class: [ b ] = active and constrained (a bias or an automaton), [ max_batch + b ]
+        // = active and unconstrained.  The greedy pair runs once per mask that has greedy rows: the constrained rows read their table over the CAPPED logits, the
+        // plain rows take the logits as they are, as each does alone (the cap is monotone but can merge neighbours into a tie).  Updated wherever the active word or
+        // a row's constraints change; allocated by the first setRowsRequests().
+        std::unique_ptr<TokenTensor> row_masks_;
+        std::vector<char> row_active_host_;
+        void refreshRowMasks( int b )
+        {
+            if ( !row_masks_ ) return;
+            if ( row_active_host_.empty() ) row_active_host_.assign( static_cast<size_t>( cfg_.max_batch ), 0 );      // (no row was ever activated: buildRows() left them inactive)
+            const bool on = row_active_host_[ static_cast<size_t>( b ) ] != 0, c = rowConstrained( b );
+            const int32_t w[ 2 ] = { on && c ? 1 : 0, on && !c ? 1 : 0 };
+            Compute::rocmCheck( mila_cdna4_memcpy_h2d( row_masks_->data() + b, &w[ 0 ], 4, ctx_->getStream() ) );
+            Compute::rocmCheck( mila_cdna4_memcpy_h2d( row_masks_->data() + cfg_.max_batch + b, &w[ 1 ], 4, ctx_->getStream() ) );
+            ctx_->synchronize();
+        }
+        std::unique_ptr<TokenTensor> row_params_;
+        std::vector<SamplingParams> row_requests_;      // empty: the rows step takes the shared parameters, as ever
+        const float* row_request_draws_{ nullptr };
+        std::unique_ptr<Compute::RocmTokenBiasRows> row_bias_;
+        std::unique_ptr<Compute::RocmTokenAutomatonRows> row_automata_;
+        RowsRequestKey rows_captured_key_{};
+        bool rowConstrained( int b ) const { return ( row_bias_ && row_bias_->on( b ) ) || ( row_automata_ && row_automata_->on( b ) ); }
+        RowsRequestKey rowsRequestKey() const
+        {
+            RowsRequestKey k{};
+            if ( row_requests_.empty() ) return k;
+            k.on = true;
+            for ( size_t b = 0; b < row_requests_.size(); ++b )
+            {
+                const bool greedy = !( row_requests_[ b ].temperature > 0.0f ), c = rowConstrained( static_cast<int>( b ) );
+                if ( !greedy ) k.stochastic = true;
+                else ( c ? k.greedy_constrained : k.greedy_plain ) = true;
+                k.constrained = k.constrained || c;
+                k.automaton = k.automaton || ( row_automata_ && row_automata_->on( static_cast<int>( b ) ) );
+                k.table = k.table || row_requests_[ b ].penalized();
+            }
+            return k;
+        }
+        void noteRowActive( int b, bool on )
+        {
+            if ( row_active_host_.empty() ) row_active_host_.assign( static_cast<size_t>( cfg_.max_batch ), 0 );
+            row_active_host_[ static_cast<size_t>( b ) ] = on ? 1 : 0;
+            refreshRowMasks( b );
+        }
+        void ensureRowBias()
+        {
+            requireRows( 0 );
+            if ( !row_bias_ ) row_bias_ = std::make_unique<Compute::RocmTokenBiasRows>( ctx_, cfg_.vocab_size, static_cast<int>( cfg_.max_batch ) );
+        }
         /// what the one-row samplers read as their bias table: the automaton's effective table (composed over the bias table) while one is on
         const float* samplerBias() noexcept { return automaton_on_ ? token_automaton_->eff() : biasValues(); }
         void checkBiasEntries( const int32_t* ids, const float* values, size_t n, const char* who ) const

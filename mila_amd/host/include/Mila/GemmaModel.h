@@ -125,6 +125,13 @@ namespace Mila::Dnn
         /// Off by default: with it off such a request takes the plain loop, as it always did.
         bool speculate_constrained = false;
     };
+    /// One row of GemmaModel::generateRequests: a prompt, its request and the seed of the row's generator
+    struct BatchRequest
+    {
+        std::vector<int32_t> prompt;
+        GenerateParams params{};
+        uint64_t seed = 0;
+    };
     /// the automaton of a request against its composed bias table (throws invalid_argument; touches no device)
     inline void checkRequestAutomaton( const GenerateParams& params, const TokenBiasPlan& bias_plan, dim_t vocab )
     {
@@ -156,6 +163,51 @@ namespace Mila::Dnn
     {
         if ( params.logprobs && ( *params.logprobs < 0 || *params.logprobs > std::min<dim_t>( Compute::RocmTokenLogprobsOp::kMaxTop, vocab ) ) )
             throw std::invalid_argument( "GenerateParams::logprobs must be 0 .. min(20, vocabulary) (got " + std::to_string( *params.logprobs ) + ")" );
+    }
+    /// What generateRequests checks and composes for ONE row before anything is enqueued (host only: no device, no model).  sampling: the row's record -- a greedy
+    /// request (top_k == 1 or temperature <= 0, generate()'s rule) is temperature 0 with the truncations off.
+    struct RowRequestPlan
+    {
+        std::unordered_set<int32_t> stop_ids;
+        TokenBiasPlan bias;
+        SamplingParams sampling{};
+        bool greedy = true;
+        int max_new = 0;
+    };
+    /// every check generate() makes for the request, plus the rows rules (no speculative field; `logprobs` = the call's ONE top_n); throws invalid_argument with the
+    /// row's number in the message.  default_stops: the model's stop set, taken when the request names none.
+    inline RowRequestPlan planRowRequest( const BatchRequest& rq, const std::optional<int>& logprobs, int row, dim_t vocab, dim_t context, const std::unordered_set<int32_t>& default_stops )
+    {
+        try
+        {
+            if ( rq.prompt.empty() ) throw std::invalid_argument( "empty prompt" );
+            if ( rq.prompt.size() > static_cast<size_t>( context ) ) throw std::invalid_argument( "the prompt exceeds the deployment context length" );
+            for ( int32_t t : rq.prompt )
+                if ( t < 0 || t >= vocab ) throw std::invalid_argument( "token id " + std::to_string( t ) + " outside the vocabulary" );
+            const GenerateParams& p = rq.params;
+            if ( p.speculative_sampling || p.speculate_constrained || p.draft )
+                throw std::invalid_argument( "the speculative fields (speculative_sampling, speculate_constrained, draft) are not for a rows model: it has no chain" );
+            if ( p.logprobs != logprobs ) throw std::invalid_argument( "logprobs differs from the call's: the step's log-probability launches have one top_n" );
+            checkLogprobsRequest( p, vocab );
+            RowRequestPlan pl;
+            if ( p.stop_tokens.empty() ) pl.stop_ids = default_stops;
+            else pl.stop_ids.insert( p.stop_tokens.begin(), p.stop_tokens.end() );
+            pl.sampling = p.sampling;
+            const SamplingParams& s = p.sampling;
+            if ( !std::isfinite( s.temperature ) ) throw std::invalid_argument( "temperature is not finite" );
+            if ( !std::isfinite( s.min_p ) || !std::isfinite( s.repetition_penalty ) || !std::isfinite( s.presence_penalty ) || !std::isfinite( s.frequency_penalty ) )
+                throw std::invalid_argument( "a sampling filter is not finite" );
+            if ( !( s.repetition_penalty > 0.0f ) ) throw std::invalid_argument( "repetition_penalty must be > 0" );
+            if ( !( s.min_p >= 0.0f && s.min_p < 1.0f ) ) throw std::invalid_argument( "min_p outside [0, 1)" );
+            pl.greedy = s.top_k == 1 || s.temperature <= 0.0f;
+            if ( pl.greedy ) { pl.sampling.temperature = 0.0f; pl.sampling.top_k = 0; pl.sampling.top_p = 1.0f; }
+            else if ( s.top_k < 0 || !( s.top_p > 0.0f ) ) throw std::invalid_argument( "need top_k >= 0, top_p > 0" );
+            pl.max_new = p.max_new_tokens.value_or( static_cast<int>( context ) );
+            pl.bias = composeRequestBias( p, pl.stop_ids, vocab );
+            checkRequestAutomaton( p, pl.bias, vocab );
+            return pl;
+        }
+        catch ( const std::invalid_argument& e ) { throw std::invalid_argument( "GemmaModel::generateRequests: row " + std::to_string( row ) + ": " + e.what() ); }
     }
     /// host copies of the log-probabilities of up to four rows, and the callback over one of them
     struct TokenLogprobsRows
@@ -443,7 +495,146 @@ namespace Mila::Dnn
             }, network_ );
         }
 
+        /// generateBatch for requests that do NOT agree: row b runs requests[ b ] -- its own sampling (all seven fields; greedy and stochastic rows mix), stop set,
+        /// max_new_tokens, logit_bias / banned_tokens / allowed_tokens / min_tokens and automaton -- with its own generator seeded requests[ b ].seed.  THE CONTRACT:
+        /// row b gives, token for token, what generate() gives for request b alone on a one-sequence model of the same weights after seedSampler( seed_b ) -- tokens,
+        /// finish reason, log-probability bits and the final automaton state -- whatever the other rows carry (the rows step's invariance, with its one documented
+        /// limit: the unwindowed layers' live-length bucket follows the batch's longest row).  logprobs / on_logprobs: ONE n for the call (the step's two
+        /// log-probability launches have one top_n), so differing values are refused; the callback reported is each row's own.  The speculative fields
+        /// (speculative_sampling, speculate_constrained, draft) are refused: a rows model has no chain.  Every request check happens before anything is enqueued, with
+        /// the row's number in the message.  final_states (may be null): row b's automaton state after its last sample, nullopt for a row without one.
+        /// The sampler parameters live in device memory (GemmaTransformer::setRowsRequests): a second call with other parameters of the same classes replays the
+        /// captured rows graph.  generateBatch keeps its contract; this is an entry beside it.
+        [[nodiscard]] std::vector<GenerateStatus> generateRequests( std::span<const BatchRequest> requests, const std::function<void( int, int32_t )>& on_token,
+                                                                    std::vector<std::optional<int32_t>>* final_states = nullptr )
+        {
+            return std::visit( [&]( auto& net )
+            {
+                try
+                {
+                    auto status = onGeneratingRequests( *net, requests, on_token, final_states );
+                    net->clearRowsRequests();
+                    return status;
+                }
+                catch ( const std::invalid_argument& ) { net->clearRowsRequests(); throw; }
+                catch ( ... ) { try { net->context()->synchronize(); } catch ( ... ) {} net->clearRowsRequests(); kv_token_history_.clear(); throw; }
+            }, network_ );
+        }
+
     private:
+        template<typename TNet>
+        std::vector<GenerateStatus> onGeneratingRequests( TNet& net, std::span<const BatchRequest> requests, const std::function<void( int, int32_t )>& on_token,
+                                                          std::vector<std::optional<int32_t>>* final_states )
+        {
+            Compute::TraceRange tr( "GemmaModel.generateRequests" );
+            const int n = static_cast<int>( requests.size() );
+            if ( net.maxBatch() < 2 ) throw std::invalid_argument( "GemmaModel::generateRequests: the model was built for one sequence (GemmaModelConfig::withMaxBatch)" );
+            if ( n < 1 || n > net.maxBatch() ) throw std::invalid_argument( "GemmaModel::generateRequests: " + std::to_string( n ) + " requests for max_batch " + std::to_string( net.maxBatch() ) );
+            std::vector<RowRequestPlan> plan;
+            std::vector<typename TNet::SamplingParams> sp;
+            for ( int b = 0; b < n; ++b )
+            {
+                plan.push_back( planRowRequest( requests[ static_cast<size_t>( b ) ], requests[ 0 ].params.logprobs, b, vocabSize(), contextLength(), stopTokens() ) );
+                sp.push_back( networkSampling<TNet>( plan.back().sampling ) );
+            }
+            // ---- nothing was enqueued so far
+            kv_token_history_.clear();      // row 0's caches are overwritten: nothing is left to reuse
+            last_reuse_ = 0;
+            const std::optional<int> logprobs = requests[ 0 ].params.logprobs;
+            auto* ctx = net.context();
+            const int B = std::max( 2, n );
+            net.clearTokenAutomaton();
+            for ( int b = 0; b < static_cast<int>( net.maxBatch() ); ++b )
+            {
+                net.resetRow( b );
+                const GenerateParams* p = b < n ? &requests[ static_cast<size_t>( b ) ].params : nullptr;
+                // the automaton first: a row with one keeps its bias in the table the automaton composes from
+                if ( p && p->automaton ) net.setRowTokenAutomaton( b, *p->automaton ); else net.clearRowTokenAutomaton( b );
+                const TokenBiasPlan* bp = b < n ? &plan[ static_cast<size_t>( b ) ].bias : nullptr;
+                if ( bp && bp->active )
+                {
+                    net.setRowTokenBias( b, bp->fill, bp->ids.data(), bp->values.data(), bp->ids.size() );
+                    if ( bp->hasRestore() ) net.stageRowTokenBiasUpdate( b, bp->restore_ids.data(), bp->restore_values.data(), bp->restore_ids.size() );
+                }
+                else net.clearRowTokenBias( b );
+            }
+            net.setRowsRequests( std::span<const typename TNet::SamplingParams>( sp ), row_draws_dev_ );
+            net.setStepLogprobs( logprobs );
+            std::vector<std::mt19937_64> rng;
+            for ( int b = 0; b < n; ++b ) rng.emplace_back( requests[ static_cast<size_t>( b ) ].seed );
+            auto draw = [&]( int b ) { return std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng[ static_cast<size_t>( b ) ] ); };
+            TokenLogprobsRows lp;
+            lp.top_n = logprobs.value_or( 0 );
+            std::vector<dim_t> position( static_cast<size_t>( n ) );
+            std::vector<int> emitted( static_cast<size_t>( n ), 0 );
+            std::vector<char> active( static_cast<size_t>( n ), 1 );
+            std::vector<GenerateStatus> status( static_cast<size_t>( n ), GenerateStatus::Success );
+            for ( int b = 0; b < n; ++b )
+            {
+                const auto& prompt = requests[ static_cast<size_t>( b ) ].prompt;
+                const dim_t len = static_cast<dim_t>( prompt.size() );
+                TokenTensor toks( ctx->getDeviceId(), shape_t{ 1, len } );
+                Compute::rocmCheck( mila_cdna4_memcpy_h2d( toks.rawData(), prompt.data(), static_cast<size_t>( len ) * 4, ctx->getStream() ) );
+                net.prefillRow( b, toks, len, 0 );
+                ctx->synchronize();
+                position[ static_cast<size_t>( b ) ] = len;
+                if ( sp[ static_cast<size_t>( b ) ].penalized() ) net.resetTokenTable( b, prompt.data(), prompt.size() );      // before the row's first sample
+                net.sampleRowRequest( b, plan[ static_cast<size_t>( b ) ].greedy ? 0.0f : draw( b ) );      // the first token, from the prefill's logits, then the row's automaton
+                if ( logprobs ) { net.enqueueRowLogprobs( b ); lp.readInto( net.tokenLogprobs(), b ); }
+                net.setRowActive( b, true );
+            }
+            std::vector<int32_t> tokens( static_cast<size_t>( B ) );
+            int live = n;
+            bool stepped = false;
+            int next_sample = 1;      // the sample index the next rows step produces: the rows step in lockstep, every row's index 0 came behind its prefill
+            while ( true )
+            {
+                Compute::rocmCheck( mila_cdna4_memcpy_d2h( tokens.data(), net.rowsTokens().data(), static_cast<size_t>( B ) * 4, ctx->getStream() ) );
+                ctx->synchronize();
+                if ( logprobs && stepped ) lp.read( net.tokenLogprobs(), B );      // (a retired row's entries are stale: never reported)
+                for ( int b = 0; b < n; ++b )
+                {
+                    const size_t i = static_cast<size_t>( b );
+                    if ( !active[ i ] ) continue;
+                    const int32_t token = tokens[ i ];
+                    bool retire = true;
+                    if ( plan[ i ].stop_ids.contains( token ) ) status[ i ] = GenerateStatus::Success;
+                    else
+                    {
+                        if ( logprobs ) lp.report( requests[ i ].params.on_logprobs, b, b, token );
+                        on_token( b, token );
+                        ++emitted[ i ];
+                        if ( emitted[ i ] >= plan[ i ].max_new ) status[ i ] = GenerateStatus::MaxNewTokensReached;
+                        else if ( position[ i ] >= contextLength() ) status[ i ] = GenerateStatus::ContextOverflow;
+                        else retire = false;
+                    }
+                    if ( retire ) { active[ i ] = 0; net.setRowActive( b, false ); --live; }
+                }
+                if ( live == 0 ) break;
+                dim_t max_position = 0;
+                for ( int b = 0; b < n; ++b ) if ( active[ static_cast<size_t>( b ) ] ) max_position = std::max( max_position, position[ static_cast<size_t>( b ) ] );
+                net.ensureGraphRows( B, max_position, false );      // (the class facts, the row count and the bucket: never a row's parameters)
+                for ( int b = 0; b < n; ++b )
+                {
+                    const size_t i = static_cast<size_t>( b );
+                    if ( !active[ i ] ) continue;
+                    if ( !plan[ i ].greedy ) writeRowDraw( b, draw( b ) );      // one draw per active stochastic row, from that row's generator
+                    if ( plan[ i ].bias.hasRestore() && next_sample == plan[ i ].bias.restore_index ) net.commitRowTokenBiasUpdate( b );      // min_tokens_b: the row's stop tokens are back from this step on
+                }
+                net.replayGraphRows();
+                ++next_sample;
+                stepped = true;
+                for ( int b = 0; b < n; ++b )
+                    if ( active[ static_cast<size_t>( b ) ] ) ++position[ static_cast<size_t>( b ) ];
+            }
+            ctx->synchronize();
+            if ( final_states )
+            {
+                final_states->assign( static_cast<size_t>( n ), std::nullopt );
+                for ( int b = 0; b < n; ++b ) ( *final_states )[ static_cast<size_t>( b ) ] = net.rowTokenAutomatonState( b );
+            }
+            return status;
+        }
         template<typename TNet>
         std::vector<GenerateStatus> onGeneratingBatch( TNet& net, std::span<const std::vector<int32_t>> prompts, const std::function<void( int, int32_t )>& on_token,
                                                        const GenerateParams& params, uint64_t seed )

@@ -1418,6 +1418,205 @@ namespace Mila::Dnn::Compute
         std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> words_, image_, chain_states_;
     };
 
+    /// The rows form of RocmTokenBias (mila_cdna4.h: row requests): one table per row of a rows step and one staging area per row.  `eff` [rows, vocab] is what the
+    /// requests samplers read as row b's bias row; `base` [rows, vocab] is what row b's automaton composes eff FROM.  A row WITHOUT an automaton keeps its table in eff
+    /// itself (nothing else writes that row); a row WITH one keeps it in base, and RocmTokenAutomatonRows rewrites eff behind every sample.  Both start as zeros (no
+    /// bias).  The addresses never move: a captured rows step sees every later update.  apply() synchronizes (it reads host memory); stage() uploads a restore list
+    /// ahead of time and commit() enqueues it as one small launch in stream order.
+    class RocmTokenBiasRows
+    {
+    public:
+        static constexpr size_t kStage = RocmTokenBias::kStage;
+        RocmTokenBiasRows( IExecutionContext* ctx, dim_t vocab, int rows ) : context_( cast_context<DeviceType::Rocm>( ctx ) ), vocab_( vocab ), rows_( rows )
+        {
+            if ( vocab <= 0 || rows < 1 || rows > 4 ) throw std::invalid_argument( "RocmTokenBiasRows: need a positive vocabulary and 1 .. 4 rows" );
+            (void)narrowToKernelIndex( vocab, "vocab" );
+            const auto dev = context_->getDeviceId();
+            eff_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( rows ), vocab } );
+            base_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( rows ), vocab } );
+            stage_ids_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( rows ), static_cast<dim_t>( 2 * kStage ) } );
+            stage_values_ = std::make_unique<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( rows ), static_cast<dim_t>( 2 * kStage ) } );
+            for ( int b = 0; b < rows; ++b ) { fill( eff_->data(), b, 0.0f ); fill( base_->data(), b, 0.0f ); }
+            staged_.assign( static_cast<size_t>( rows ), 0 );
+            on_.assign( static_cast<size_t>( rows ), 0 );
+            to_base_.assign( static_cast<size_t>( rows ), 0 );
+            context_->synchronize();
+        }
+        float* eff() { return eff_->data(); }
+        float* base() { return base_->data(); }
+        size_t stride() const noexcept { return static_cast<size_t>( vocab_ ); }
+        int rows() const noexcept { return rows_; }
+        bool on( int b ) const { checkRow( b ); return on_[ static_cast<size_t>( b ) ] != 0; }
+        bool any() const noexcept { for ( char c : on_ ) if ( c ) return true; return false; }
+        /// row b's whole table: every value `fill`, then values[j] at ids[j]; into base when the row has an automaton (`to_base`), else into eff
+        void apply( int b, bool to_base, float fill_value, const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            checkRow( b );
+            float* t = to_base ? base() : eff();
+            fill( t, b, fill_value );
+            int32_t* ids = stage_ids_->data() + static_cast<size_t>( b ) * 2 * kStage;
+            float* values = stage_values_->data() + static_cast<size_t>( b ) * 2 * kStage;
+            for ( size_t i0 = 0; i0 < n; i0 += kStage )
+            {
+                const size_t c = std::min<size_t>( kStage, n - i0 );
+                rocmCheck( mila_cdna4_memcpy_h2d( ids, ids_host + i0, c * 4, context_->getStream() ) );
+                rocmCheck( mila_cdna4_memcpy_h2d( values, values_host + i0, c * 4, context_->getStream() ) );
+                rocmCheck( mila_cdna4_token_bias_set( t, stride(), b, static_cast<int>( vocab_ ), ids, values, static_cast<int>( c ), context_->getStream() ) );
+                context_->synchronize();
+            }
+            on_[ static_cast<size_t>( b ) ] = 1; to_base_[ static_cast<size_t>( b ) ] = to_base ? 1 : 0; staged_[ static_cast<size_t>( b ) ] = 0;
+        }
+        /// row b without a bias: zeros in both tables
+        void clear( int b )
+        {
+            checkRow( b );
+            fill( eff(), b, 0.0f ); fill( base(), b, 0.0f );
+            on_[ static_cast<size_t>( b ) ] = 0; to_base_[ static_cast<size_t>( b ) ] = 0; staged_[ static_cast<size_t>( b ) ] = 0;
+        }
+        /// row b's restore list (at most kStage entries) into the second half of its staging area (synchronizes) ...
+        void stage( int b, const int32_t* ids_host, const float* values_host, size_t n )
+        {
+            checkRow( b );
+            if ( n > kStage ) throw std::invalid_argument( "RocmTokenBiasRows::stage: more than " + std::to_string( kStage ) + " entries" );
+            if ( n )
+            {
+                rocmCheck( mila_cdna4_memcpy_h2d( stage_ids_->data() + static_cast<size_t>( b ) * 2 * kStage + kStage, ids_host, n * 4, context_->getStream() ) );
+                rocmCheck( mila_cdna4_memcpy_h2d( stage_values_->data() + static_cast<size_t>( b ) * 2 * kStage + kStage, values_host, n * 4, context_->getStream() ) );
+                context_->synchronize();
+            }
+            staged_[ static_cast<size_t>( b ) ] = n;
+        }
+        /// ... and enqueue it on the table apply() wrote: one launch in stream order, no host data
+        void commit( int b )
+        {
+            checkRow( b );
+            rocmCheck( mila_cdna4_token_bias_set( to_base_[ static_cast<size_t>( b ) ] ? base() : eff(), stride(), b, static_cast<int>( vocab_ ),
+                                                  stage_ids_->data() + static_cast<size_t>( b ) * 2 * kStage + kStage, stage_values_->data() + static_cast<size_t>( b ) * 2 * kStage + kStage,
+                                                  static_cast<int>( staged_[ static_cast<size_t>( b ) ] ), context_->getStream() ) );
+        }
+        /// row b of eff to the host (synchronizes)
+        void read( int b, float* out )
+        {
+            checkRow( b );
+            rocmCheck( mila_cdna4_memcpy_d2h( out, eff() + static_cast<size_t>( b ) * stride(), stride() * 4, context_->getStream() ) );
+            context_->synchronize();
+        }
+        size_t stateBytes() const { return eff_->sizeInBytes() + base_->sizeInBytes() + stage_ids_->sizeInBytes() + stage_values_->sizeInBytes(); }
+        static size_t requiredBytes( dim_t vocab, int rows ) { return static_cast<size_t>( rows ) * ( 2 * static_cast<size_t>( vocab ) + 4 * kStage ) * 4; }
+    private:
+        void checkRow( int b ) const { if ( b < 0 || b >= rows_ ) throw std::invalid_argument( "RocmTokenBiasRows: row " + std::to_string( b ) + " outside 0 .. " + std::to_string( rows_ - 1 ) ); }
+        void fill( float* t, int b, float v ) { rocmCheck( mila_cdna4_token_bias_fill( t, stride(), b, static_cast<int>( vocab_ ), v, context_->getStream() ) ); }
+        ExecutionContext<DeviceType::Rocm>* context_;
+        dim_t vocab_;
+        int rows_;
+        std::vector<size_t> staged_;
+        std::vector<char> on_, to_base_;
+        std::unique_ptr<Tensor<TensorDataType::FP32, RocmDeviceMemoryResource>> eff_, base_, stage_values_;
+        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> stage_ids_;
+    };
+
+    /// The rows form of RocmTokenAutomaton (mila_cdna4.h: row requests): one image, one state word and one ticket word per row, and the descriptor array the rows
+    /// step reads.  It owns no table: eff and base are RocmTokenBiasRows'.  set() uploads a validated image, stores the row's descriptor in stream order and puts the
+    /// state word to `start`; clear() stores the null descriptor (the row has no automaton: the step does not touch it).  compose() / step() are one launch for all
+    /// rows; stepRow() is the one-row entry on row b alone (behind a row's first token).  set() and readState() synchronize.
+    class RocmTokenAutomatonRows
+    {
+    public:
+        RocmTokenAutomatonRows( IExecutionContext* ctx, dim_t vocab, int rows ) : context_( cast_context<DeviceType::Rocm>( ctx ) ), vocab_( vocab ), rows_( rows )
+        {
+            if ( vocab <= 0 || rows < 1 || rows > 4 ) throw std::invalid_argument( "RocmTokenAutomatonRows: need a positive vocabulary and 1 .. 4 rows" );
+            (void)narrowToKernelIndex( vocab, "vocab" );
+            const auto dev = context_->getDeviceId();
+            words_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( 2 * rows ) } );      // states, then tickets
+            desc_ = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( dev, shape_t{ static_cast<dim_t>( mila_cdna4_token_automaton_rows_bytes( rows ) / 4 ) } );
+            rocmCheck( mila_cdna4_memset_zero( words_->rawData(), words_->sizeInBytes(), context_->getStream() ) );
+            rocmCheck( mila_cdna4_memset_zero( desc_->rawData(), desc_->sizeInBytes(), context_->getStream() ) );      // null descriptors
+            images_.resize( static_cast<size_t>( rows ) );
+            shape_.assign( static_cast<size_t>( rows ), Shape{} );
+            context_->synchronize();
+        }
+        bool on( int b ) const { checkRow( b ); return shape_[ static_cast<size_t>( b ) ].S > 0; }
+        bool any() const noexcept { for ( auto& s : shape_ ) if ( s.S > 0 ) return true; return false; }
+        void set( int b, const uint16_t* class_of, const uint16_t* next, int S, int C, int start )
+        {
+            checkRow( b );
+            const size_t bytes = mila_cdna4_token_automaton_bytes( static_cast<int>( vocab_ ), S, C );
+            if ( !bytes || !class_of || !next || start < 0 || start >= S ) throw std::invalid_argument( "RocmTokenAutomatonRows::set: an automaton outside the limits of mila_cdna4.h" );
+            const dim_t words = static_cast<dim_t>( ( bytes + 3 ) / 4 );
+            context_->synchronize();      // (no step in flight reads the image that is replaced)
+            auto& image = images_[ static_cast<size_t>( b ) ];
+            if ( !image || image->shape()[ 0 ] != words ) image = std::make_unique<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>( context_->getDeviceId(), shape_t{ words } );
+            uint16_t* cls = reinterpret_cast<uint16_t*>( image->rawData() );
+            rocmCheck( mila_cdna4_memcpy_h2d( cls, class_of, static_cast<size_t>( vocab_ ) * 2, context_->getStream() ) );
+            rocmCheck( mila_cdna4_memcpy_h2d( cls + vocab_, next, static_cast<size_t>( S ) * static_cast<size_t>( C ) * 2, context_->getStream() ) );
+            const int32_t w = start, zero = 0;
+            rocmCheck( mila_cdna4_memcpy_h2d( words_->data() + b, &w, 4, context_->getStream() ) );
+            rocmCheck( mila_cdna4_memcpy_h2d( words_->data() + rows_ + b, &zero, 4, context_->getStream() ) );
+            rocmCheck( mila_cdna4_token_automaton_rows_set( desc_->rawData(), b, cls, cls + vocab_, S, C, static_cast<int>( vocab_ ), context_->getStream() ) );
+            context_->synchronize();
+            shape_[ static_cast<size_t>( b ) ] = Shape{ S, C };
+        }
+        void clear( int b )
+        {
+            checkRow( b );
+            rocmCheck( mila_cdna4_token_automaton_rows_set( desc_->rawData(), b, nullptr, nullptr, 0, 0, 0, context_->getStream() ) );
+            shape_[ static_cast<size_t>( b ) ] = Shape{};
+        }
+        /// every row's eff row for the state its word holds (rows without an automaton are not touched): one launch
+        void compose( RocmTokenBiasRows& t )
+        {
+            rocmCheck( mila_cdna4_token_automaton_rows_compose( t.eff(), t.stride(), t.base(), t.stride(), desc_->rawData(), words_->data(), rows_, static_cast<int>( vocab_ ), context_->getStream() ) );
+        }
+        /// behind the sampler tails of a rows step over rows 0 .. B - 1: the active rows' states advanced by tok_dev[b], their eff rows rewritten; one launch
+        void step( RocmTokenBiasRows& t, const int32_t* tok_dev, const int32_t* active_dev, int B )
+        {
+            rocmCheck( mila_cdna4_token_automaton_rows_step( t.eff(), t.stride(), t.base(), t.stride(), desc_->rawData(), words_->data(), tok_dev, active_dev,
+                                                             reinterpret_cast<uint32_t*>( words_->data() + rows_ ), B, static_cast<int>( vocab_ ), context_->getStream() ) );
+        }
+        /// the one-row step on row b alone, by the token at tok_dev (behind the row's first sample)
+        void stepRow( RocmTokenBiasRows& t, int b, const int32_t* tok_dev )
+        {
+            if ( !on( b ) ) return;
+            const uint16_t* cls = reinterpret_cast<const uint16_t*>( images_[ static_cast<size_t>( b ) ]->rawData() );
+            const size_t off = static_cast<size_t>( b ) * t.stride();
+            rocmCheck( mila_cdna4_token_automaton_step( t.eff() + off, 0, t.base() + off, 0, cls, cls + vocab_, shape_[ static_cast<size_t>( b ) ].S, shape_[ static_cast<size_t>( b ) ].C,
+                                                        words_->data() + b, tok_dev, nullptr, reinterpret_cast<uint32_t*>( words_->data() + rows_ + b ), 1, static_cast<int>( vocab_ ),
+                                                        context_->getStream() ) );
+        }
+        /// row b's state word (synchronizes)
+        int32_t readState( int b )
+        {
+            checkRow( b );
+            int32_t s = 0;
+            rocmCheck( mila_cdna4_memcpy_d2h( &s, words_->data() + b, 4, context_->getStream() ) );
+            context_->synchronize();
+            return s;
+        }
+        size_t stateBytes() const
+        {
+            size_t n = words_->sizeInBytes() + desc_->sizeInBytes();
+            for ( auto& i : images_ ) if ( i ) n += i->sizeInBytes();
+            return n;
+        }
+        /// the words and descriptors, plus every uploaded image rounded up to whole 32-bit words
+        size_t requiredBytes() const
+        {
+            size_t n = static_cast<size_t>( rows_ ) * 8 + mila_cdna4_token_automaton_rows_bytes( rows_ );
+            for ( size_t b = 0; b < images_.size(); ++b )
+                if ( images_[ b ] ) n += static_cast<size_t>( images_[ b ]->shape()[ 0 ] ) * 4;
+            return n;
+        }
+    private:
+        struct Shape { int S = 0, C = 0; };
+        void checkRow( int b ) const { if ( b < 0 || b >= rows_ ) throw std::invalid_argument( "RocmTokenAutomatonRows: row " + std::to_string( b ) + " outside 0 .. " + std::to_string( rows_ - 1 ) ); }
+        ExecutionContext<DeviceType::Rocm>* context_;
+        dim_t vocab_;
+        int rows_;
+        std::vector<Shape> shape_;
+        std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>> words_, desc_;
+        std::vector<std::unique_ptr<Tensor<TensorDataType::INT32, RocmDeviceMemoryResource>>> images_;
+    };
+
     class RocmSamplingOp : public Operation<DeviceType::Rocm, TensorDataType::FP32>
     {
     public:

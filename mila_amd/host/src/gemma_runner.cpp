@@ -741,6 +741,74 @@ HOST_API int mila_gemma_rows_graph_info( void* h, int64_t* out )
 {
     return guarded( [&] { std::visit( [&]( auto& m ) { out[ 0 ] = (int64_t)m->graphRowsCaptureCount(); out[ 1 ] = (int64_t)m->graphRowsNodeCount(); }, static_cast<Runner*>( h )->model ); } );
 }
+/// ROW REQUESTS for the rows steps that follow (GemmaTransformer::setRowsRequests): params = n x 7 floats, row b's temperature (<= 0: greedy), top_k, top_p, min_p,
+/// repetition_penalty, presence_penalty, frequency_penalty; draws = one uniform draw per row (NULL: zeros), kept in the runner's host-visible words, which
+/// mila_gemma_decode_rows_sampled rewrites per call.  n == 0 clears the requests: the rows step takes the shared parameters again.
+HOST_API int mila_gemma_set_rows_requests( void* h, const float* params, int n, const float* draws )
+{
+    return guarded( [&]
+    {
+        auto* r = static_cast<Runner*>( h );
+        std::visit( [&]( auto& m )
+        {
+            if ( n == 0 ) { m->clearRowsRequests(); return; }
+            if ( !params || n < 0 || n > Runner::kStepDraws ) throw std::invalid_argument( "set_rows_requests: 1 .. 4 requests of 7 values" );
+            std::vector<typename std::remove_reference_t<decltype( *m )>::SamplingParams> sp( static_cast<size_t>( n ) );
+            for ( int b = 0; b < n; ++b )
+            {
+                const float* q = params + 7 * b;
+                auto& s = sp[ static_cast<size_t>( b ) ];
+                s.temperature = q[ 0 ]; s.top_k = static_cast<int>( q[ 1 ] ); s.top_p = q[ 2 ];
+                s.min_p = q[ 3 ]; s.repetition_penalty = q[ 4 ]; s.presence_penalty = q[ 5 ]; s.frequency_penalty = q[ 6 ];
+            }
+            const float zeros[ Runner::kStepDraws ] = { 0.0f, 0.0f, 0.0f, 0.0f };
+            m->setRowsRequests( sp, r->stepDraws( draws ? draws : zeros, n ) );
+        }, r->model );
+    } );
+}
+/// row b's bias table for the requests samplers: every value `fill`, then values[ j ] at ids[ j ]; n < 0 clears the row's bias
+HOST_API int mila_gemma_set_row_token_bias( void* h, int b, float fill, const int32_t* ids, const float* values, int64_t n )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m ) { if ( n < 0 ) m->clearRowTokenBias( b ); else m->setRowTokenBias( b, fill, ids, values, static_cast<size_t>( n ) ); }, static_cast<Runner*>( h )->model );
+    } );
+}
+/// row b's automaton for the requests step (mila_gemma_set_token_automaton's arguments); class_of == NULL clears it.  Set it BEFORE the row's bias.
+HOST_API int mila_gemma_set_row_token_automaton( void* h, int b, const uint16_t* class_of, int64_t vocab, const uint16_t* next, int S, int C, int start )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( !class_of ) { m->clearRowTokenAutomaton( b ); return; }
+            if ( !next || vocab < 0 || S < 0 || C < 0 ) throw std::invalid_argument( "set_row_token_automaton: null table or negative size" );
+            TokenAutomaton a;
+            a.num_states = S; a.num_classes = C; a.start = start;
+            a.class_of.assign( class_of, class_of + vocab );
+            a.next.assign( next, next + static_cast<size_t>( S ) * static_cast<size_t>( C ) );
+            m->setRowTokenAutomaton( b, a );
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
+/// *out_state = row b's state word (a synchronous read), *out_on = whether the row has an automaton; out_eff (may be NULL): the row's effective table [vocab]
+HOST_API int mila_gemma_row_token_automaton_state( void* h, int b, int32_t* out_state, int32_t* out_on, float* out_eff )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            const auto s = m->rowTokenAutomatonState( b );
+            if ( out_state ) *out_state = s.value_or( 0 );
+            if ( out_on ) *out_on = s ? 1 : 0;
+            if ( out_eff )
+            {
+                if ( !m->rowTokenBias() ) throw std::logic_error( "row_token_automaton_state: no row table was set" );
+                m->rowTokenBias()->read( b, out_eff );
+            }
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
 /// the sampler tail of the rows step (which = 0) or of the chain step (which = 1) for the calls that follow -- the timing loops among them: draws = n uniform draws,
 /// one per row, kept in the runner's host-visible words; draws == NULL clears it (mila_gemma_decode_rows / mila_gemma_chain_decode set it per call themselves)
 HOST_API int mila_gemma_set_step_sampling( void* h, int which, float temperature, int top_k, float top_p, const float* draws, int n )
@@ -2018,6 +2086,77 @@ static int model_generate_rows_impl( void* h, const int32_t* prompts, const int6
         const auto st = m->generateBatch( ps, [&]( int b, int32_t t ) { int64_t& c = counts[ static_cast<size_t>( b ) ]; if ( out_tokens && c < cap ) out_tokens[ b * cap + c ] = t; ++c; }, gp, seed );
         for ( int b = 0; b < n_prompts; ++b ) { out_counts[ b ] = counts[ static_cast<size_t>( b ) ]; out_status[ b ] = static_cast<int32_t>( st[ static_cast<size_t>( b ) ] ); }
         if ( out_logprob_counts ) for ( int b = 0; b < n_prompts; ++b ) out_logprob_counts[ b ] = lp_counts[ static_cast<size_t>( b ) ];
+    } );
+}
+
+/// out[0] = captures of the model's rows graph so far, out[1] = kernel nodes of the captured rows step
+HOST_API int mila_gemma_model_rows_graph_info( void* h, int64_t* out )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m || !out ) throw std::invalid_argument( "gemma_model_rows_graph_info: null argument" );
+        std::visit( [&]( auto& net ) { out[ 0 ] = (int64_t)net->graphRowsCaptureCount(); out[ 1 ] = (int64_t)net->graphRowsNodeCount(); }, m->network() );
+    } );
+}
+/// One row of mila_gemma_model_generate_requests: generate()'s arguments by value and by pointer
+struct mila_gemma_row_request
+{
+    const int32_t* prompt; int64_t n_prompt;
+    const int32_t* stop_tokens; int64_t n_stop;
+    const mila_token_bias_request* bias;                 ///< NULL: none
+    const mila_token_automaton_request* automaton;       ///< NULL: none
+    uint64_t seed;
+    float temperature, top_p;
+    float filters[ 4 ];                                  ///< min_p, repetition_penalty, presence_penalty, frequency_penalty
+    int32_t top_k;
+    int32_t max_new;                                     ///< < 0: none
+    int32_t logprobs;                                    ///< < 0: none
+    int32_t speculative;                                 ///< bit 0 speculative_sampling, bit 1 speculate_constrained, bit 2 a drafter: all refused
+};
+/// GemmaModel::generateRequests: row b runs requests[ b ].  out_tokens [n, cap], out_counts / out_status [n]; the log-probability entries of row b at
+/// out_logprob[ b * cap .. ) and out_ids / out_logprobs[ ( b * cap + i ) * top_n .. ) with top_n = requests[ 0 ].logprobs (the arrays may be NULL without
+/// log-probabilities), their numbers to out_logprob_counts [n]; out_states / out_has_state [n]: the final automaton state of a row that had one
+HOST_API int mila_gemma_model_generate_requests( void* h, const mila_gemma_row_request* requests, int n, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status,
+                                                 float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts, int32_t* out_states, int32_t* out_has_state )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m || !requests || !out_counts || !out_status || n < 0 ) throw std::invalid_argument( "gemma_model_generate_requests: null argument" );
+        std::vector<BatchRequest> rq( static_cast<size_t>( n ) );
+        std::vector<int64_t> lp_counts( static_cast<size_t>( std::max( n, 1 ) ), 0 );
+        LogprobSink sink{ n > 0 ? requests[ 0 ].logprobs : -1, out_logprob, out_ids, out_logprobs, cap };
+        for ( int b = 0; b < n; ++b )
+        {
+            const auto& q = requests[ b ];
+            auto& r = rq[ static_cast<size_t>( b ) ];
+            if ( q.n_prompt < 0 || q.n_stop < 0 || ( q.n_prompt && !q.prompt ) || ( q.n_stop && !q.stop_tokens ) ) throw std::invalid_argument( "gemma_model_generate_requests: null list" );
+            r.prompt.assign( q.prompt, q.prompt + q.n_prompt );
+            r.seed = q.seed;
+            GenerateParams& gp = r.params;
+            sink.attach( gp, [&lp_counts]( int row ) -> int64_t& { return lp_counts.at( static_cast<size_t>( row ) ); } );
+            if ( q.logprobs >= 0 ) gp.logprobs = q.logprobs; else gp.logprobs.reset();      // each row's own value: the model refuses rows that differ
+            if ( q.max_new >= 0 ) gp.max_new_tokens = q.max_new;
+            gp.sampling.temperature = q.temperature; gp.sampling.top_k = q.top_k; gp.sampling.top_p = q.top_p;
+            apply_request_filters( gp.sampling, q.filters );
+            apply_request_bias( gp, q.bias );
+            apply_request_automaton( gp, q.automaton );
+            gp.stop_tokens.assign( q.stop_tokens, q.stop_tokens + q.n_stop );
+            gp.speculative_sampling = ( q.speculative & 1 ) != 0;
+            gp.speculate_constrained = ( q.speculative & 2 ) != 0;
+            if ( q.speculative & 4 ) gp.draft = []( std::span<const int32_t>, int ) { return std::vector<int32_t>{}; };
+        }
+        std::vector<int64_t> counts( static_cast<size_t>( n ), 0 );
+        std::vector<std::optional<int32_t>> states;
+        const auto st = m->generateRequests( rq, [&]( int b, int32_t t ) { int64_t& c = counts[ static_cast<size_t>( b ) ]; if ( out_tokens && c < cap ) out_tokens[ b * cap + c ] = t; ++c; }, &states );
+        for ( int b = 0; b < n; ++b )
+        {
+            out_counts[ b ] = counts[ static_cast<size_t>( b ) ]; out_status[ b ] = static_cast<int32_t>( st[ static_cast<size_t>( b ) ] );
+            if ( out_logprob_counts ) out_logprob_counts[ b ] = lp_counts[ static_cast<size_t>( b ) ];
+            if ( out_states ) out_states[ b ] = states[ static_cast<size_t>( b ) ].value_or( 0 );
+            if ( out_has_state ) out_has_state[ b ] = states[ static_cast<size_t>( b ) ] ? 1 : 0;
+        }
     } );
 }
 
