@@ -1072,6 +1072,19 @@ MILA_API int mila_cdna4_token_automaton_rows_step(float* eff, size_t eff_stride,
                                                   const int32_t* token_dev, const int32_t* active_dev, uint32_t* ticket_dev, int rows, int vocab,
                                                   mila_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fork a row's KV prefix (ABI 4, additive; csrc/kv_rows_fork.hip): the device primitive of a shared prefill.  A rows model keeps, per layer, K and V as
+ * [rows, NKV, capacity, HS] bf16 on UNBOUNDED caches (position p at cache index p of its row), so two requests with the same prompt hold the same bits at [0, len) of
+ * their rows after their prefills.  kv_rows_fork_bf16 copies, for every KV head, for K and for V, positions [0, len) of cache row `src` into every cache row whose
+ * bit is set in dst_mask (bit r = row r): ONE launch that reads the source once and stores each destination, 16 bytes per lane, a flat grid-stride walk over the
+ * 16-byte units with every element offset in 64 bits.  The copy is bitwise (NaN patterns and signed zeros pass through).  Nothing is written outside [0, len) of the
+ * destination rows, and nothing in `src` or in a row the mask does not name.  Stream-ordered: behind the prefill that wrote `src`, in front of the steps that read
+ * the destinations.  One call per layer.
+ * Refused before any device work (MILA_E_INVALID_ARGUMENT): a null or misaligned (16 bytes) K or V, rows outside 2 .. 4, NKV / capacity / HS <= 0, HS no multiple
+ * of 8, src outside the rows, a dst_mask that is empty, names src or names a row >= rows, len outside 1 .. capacity. */
+MILA_API int mila_cdna4_kv_rows_fork_bf16(uint16_t* K, uint16_t* V, int rows, int NKV, int capacity, int HS, int src, unsigned dst_mask, int len,
+                                          mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,8 @@ def load():
     main.mila_cdna4_token_automaton_rows_set.argtypes = [p, i, p, p, i, i, i, p]                                  # desc_dev row | class_of next S C vocab
     main.mila_cdna4_token_automaton_rows_compose.argtypes = [p, z, p, z, p, p, i, i, p]                           # eff eff_stride base base_stride | desc_dev state_dev | rows vocab
     main.mila_cdna4_token_automaton_rows_step.argtypes = [p, z, p, z, p, p, p, p, p, i, i, p]                     # ... desc_dev state_dev token_dev active_dev ticket_dev | rows vocab
+    # a shared prefill's device primitive (csrc/kv_rows_fork.hip)
+    main.mila_cdna4_kv_rows_fork_bf16.argtypes = [p, p, i, i, i, i, i, i, i, p]                                   # K V | rows NKV capacity HS | src dst_mask len
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -817,6 +819,7 @@ EXPORTED = [
     "sample_row_params_bytes", "sample_row_params_set", "sample_radix_requests_rows_fp32", "sample_radix_requests_rows_advance_fp32",
     "sample_argmax_requests_rows_fp32", "sample_argmax_requests_rows_advance_fp32",
     "token_automaton_rows_bytes", "token_automaton_rows_set", "token_automaton_rows_compose", "token_automaton_rows_step",
+    "kv_rows_fork_bf16",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

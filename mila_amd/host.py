@@ -1129,14 +1129,8 @@ class GemmaModel:
             return rows
         return [rows[b] + ([(np.float32(lp[b, i]), ids[b, i, :top_n].copy(), tlp[b, i, :top_n].copy()) for i in range(min(int(lp_counts[b]), out.shape[1]))],) for b in range(len(prompts))]
 
-    def generate_requests(self, requests, logprobs=None):
-        """GemmaModel::generateRequests: up to max_batch requests that need NOT agree, request b in row b.  requests: a list of dicts with generate()'s keyword names
-        (max_new_tokens, stop_tokens, temperature, top_k, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, banned_tokens,
-        allowed_tokens, min_tokens, automaton) plus "prompt" and "seed" (the row's generator; default 0).  Row b gives what generate() gives for request b alone on
-        a one-sequence model after the same seed.  logprobs: ONE n for the call; a row's own "logprobs" key that differs is refused, as are the speculative keys
-        (speculative_sampling, speculate_constrained, draft_hint).  -> per row what generate_batch returns -- (tokens, finish reason[, log-probability entries]) --
-        plus, for a row with an automaton, the state it ended in as a last element."""
-        lib = load()
+    def _row_requests(self, requests, logprobs, who):
+        """the GemmaRowRequestC array of generate_requests / serve_requests (who: what the refusals call a request, with its number) -> (array, what it points into, top_n)"""
         n = len(requests)
         keep, rq = [], (GemmaRowRequestC * max(n, 1))()
         vocab = self.vocab_size()
@@ -1144,7 +1138,7 @@ class GemmaModel:
         for b, q in enumerate(requests):
             unknown = set(q) - set(ROW_REQUEST_KEYS)
             if unknown:
-                raise ValueError("GemmaModel.generate_requests: row %d: unknown keys %s" % (b, sorted(unknown)))
+                raise ValueError("%s %d: unknown keys %s" % (who, b, sorted(unknown)))
             try:
                 f = _filters(q.get("min_p", 0.0), q.get("repetition_penalty", 1.0), q.get("presence_penalty", 0.0), q.get("frequency_penalty", 0.0))
                 bias = _bias_request(q.get("logit_bias"), q.get("banned_tokens", ()), q.get("allowed_tokens", ()), q.get("min_tokens", 0), q.get("stop_tokens", ()),
@@ -1152,10 +1146,10 @@ class GemmaModel:
                 own = q.get("logprobs", logprobs)
                 own = -1 if own is None else _logprobs_n(own)
             except ValueError as e:
-                raise ValueError("GemmaModel.generate_requests: row %d: %s" % (b, e)) from None
+                raise ValueError("%s %d: %s" % (who, b, e)) from None
             automaton = q.get("automaton")
             if automaton is not None and not isinstance(automaton, TokenAutomaton):
-                raise ValueError("GemmaModel.generate_requests: row %d: automaton must be a host.TokenAutomaton" % b)
+                raise ValueError("%s %d: automaton must be a host.TokenAutomaton" % (who, b))
             pr = np.ascontiguousarray(q.get("prompt", ()), dtype=np.int32)
             st = np.ascontiguousarray(list(q.get("stop_tokens", ())), dtype=np.int32)
             areq = None if automaton is None else automaton._request()
@@ -1172,6 +1166,18 @@ class GemmaModel:
             r.max_new = -1 if mx is None else int(mx)
             r.logprobs = own
             r.speculative = (1 if q.get("speculative_sampling") else 0) | (2 if q.get("speculate_constrained") else 0) | (4 if q.get("draft_hint") is not None else 0)
+        return rq, keep, top_n
+
+    def generate_requests(self, requests, logprobs=None):
+        """GemmaModel::generateRequests: up to max_batch requests that need NOT agree, request b in row b.  requests: a list of dicts with generate()'s keyword names
+        (max_new_tokens, stop_tokens, temperature, top_k, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, banned_tokens,
+        allowed_tokens, min_tokens, automaton) plus "prompt" and "seed" (the row's generator; default 0).  Row b gives what generate() gives for request b alone on
+        a one-sequence model after the same seed.  logprobs: ONE n for the call; a row's own "logprobs" key that differs is refused, as are the speculative keys
+        (speculative_sampling, speculate_constrained, draft_hint).  -> per row what generate_batch returns -- (tokens, finish reason[, log-probability entries]) --
+        plus, for a row with an automaton, the state it ended in as a last element."""
+        lib = load()
+        n = len(requests)
+        rq, keep, top_n = self._row_requests(requests, logprobs, "GemmaModel.generate_requests: row")
         caps = [int(q["max_new_tokens"]) if q.get("max_new_tokens") is not None else 1 << 16 for q in requests]
         cap = max(caps + [1])
         out = np.zeros((max(n, 1), cap), dtype=np.int32)
@@ -1193,6 +1199,55 @@ class GemmaModel:
                 row = row + (int(states[b]) if has_state[b] else None,)
             rows.append(row)
         return rows
+
+    def serve_requests(self, requests, logprobs=None):
+        """GemmaModel::serveRequests: generate_requests for ANY number of requests (>= 1) on a max_batch > 1 model -- a FIFO queue in front of the rows step: a request
+        enters the lowest free row, a row whose request has ended goes to the next waiting one before the next step, and requests admitted together with an identical
+        prompt share one prefill (the others fork the first one's KV rows and logits).  requests: generate_requests' dicts; a dict may also carry "n": k (k >= 1),
+        expanded here into k consecutive requests with seeds seed, seed + 1, ..., seed + k - 1 (generate_batch's convention).  Request i gives what generate() gives
+        for it alone on a one-sequence model after its seed, wherever and whenever it ran.  Refusals number the requests AFTER the expansion, as the results do.
+        -> (rows, stats): rows[i] = what generate_requests returns for a row; stats = {"steps": rows steps replayed, "prefills", "prefill_tokens", "forks",
+        "captures": rows-graph captures during the call, "rows": the row each request ran in, "admitted_at": the steps replayed before each admission,
+        "finish_order": the position of each request's end among the call's, "admission_ms": host milliseconds the admissions spent in their
+        {"setters", "prefill", "fork", "first_sample"}}."""
+        lib = load()
+        flat = []
+        for q in requests:
+            q = dict(q)
+            k = q.pop("n", 1)
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+                raise ValueError("GemmaModel.serve_requests: request %d: n must be an integer >= 1 (got %r)" % (len(flat), k))
+            seed = int(q.get("seed", 0))
+            for j in range(int(k)):
+                flat.append(dict(q, seed=seed + j) if k > 1 else q)
+        n = len(flat)
+        rq, keep, top_n = self._row_requests(flat, logprobs, "GemmaModel.serve_requests: request")
+        caps = [int(q["max_new_tokens"]) if q.get("max_new_tokens") is not None else 1 << 16 for q in flat]
+        cap = max(caps + [1])
+        out = np.zeros((max(n, 1), cap), dtype=np.int32)
+        counts, status, lp_counts, states, has_state, rows_of, finish = (np.zeros(max(n, 1), dtype=t) for t in (np.int64, np.int32, np.int64, np.int32, np.int32, np.int32, np.int32))
+        admitted, totals, times = np.zeros(max(n, 1), dtype=np.int64), np.zeros(5, dtype=np.int64), np.zeros(4, dtype=np.float64)
+        width = max(top_n, 1)
+        with_lp = top_n >= 0
+        lp, ids, tlp = (np.zeros(out.shape if with_lp else (1, 1), dtype=np.float32), np.zeros((out.shape if with_lp else (1, 1)) + (width,), dtype=np.int32),
+                        np.zeros((out.shape if with_lp else (1, 1)) + (width,), dtype=np.float32))
+        lib.mila_gemma_model_serve_requests.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 13
+        _check(lib.mila_gemma_model_serve_requests(self.h, C.addressof(rq), n, out.ctypes.data, cap, counts.ctypes.data, status.ctypes.data,
+                                                   lp.ctypes.data if with_lp else None, ids.ctypes.data if with_lp else None, tlp.ctypes.data if with_lp else None,
+                                                   lp_counts.ctypes.data, states.ctypes.data, has_state.ctypes.data, rows_of.ctypes.data, admitted.ctypes.data,
+                                                   finish.ctypes.data, totals.ctypes.data, times.ctypes.data))
+        rows = []
+        for b in range(n):
+            row = (out[b, :min(int(counts[b]), cap)].tolist(), GENERATE_STATUS[int(status[b])])
+            if with_lp:
+                row = row + ([(np.float32(lp[b, i]), ids[b, i, :top_n].copy(), tlp[b, i, :top_n].copy()) for i in range(min(int(lp_counts[b]), cap))],)
+            if flat[b].get("automaton") is not None:
+                row = row + (int(states[b]) if has_state[b] else None,)
+            rows.append(row)
+        stats = {"steps": int(totals[0]), "prefills": int(totals[1]), "prefill_tokens": int(totals[2]), "forks": int(totals[3]), "captures": int(totals[4]),
+                 "rows": rows_of[:n].tolist(), "admitted_at": admitted[:n].tolist(), "finish_order": finish[:n].tolist(),
+                 "admission_ms": dict(zip(("setters", "prefill", "fork", "first_sample"), (float(t) for t in times)))}
+        return rows, stats
 
     def rows_graph_info(self):
         """{"captures": captures of the model's rows graph so far, "nodes": kernel nodes of the captured rows step}"""

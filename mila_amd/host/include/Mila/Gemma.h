@@ -734,6 +734,7 @@ namespace Mila::Dnn
                 Compute::rocmCheck( mila_cdna4_sample_row_params_set( row_params_->rawData(), b, &rec, ctx_->getStream() ) );
             }
             row_requests_.assign( requests.begin(), requests.end() );
+            row_request_vacant_.assign( requests.size(), 0 );
             row_request_draws_ = draws;
             if ( !row_masks_ )
             {
@@ -741,7 +742,80 @@ namespace Mila::Dnn
                 for ( int b = 0; b < static_cast<int>( cfg_.max_batch ); ++b ) refreshRowMasks( b );
             }
         }
-        void clearRowsRequests() noexcept { row_requests_.clear(); row_request_draws_ = nullptr; }
+        /// setRowsRequests for ONE row, between steps (a request admitted into a retired row): the same checks, one record written through
+        /// mila_cdna4_sample_row_params_set in stream order, the row's masks refreshed.  The first call after clearRowsRequests() turns the requests step on with
+        /// every other row VACANT -- greedy and neutral on the device, and no part of the class facts until it gets a request of its own -- so ensureGraphRows
+        /// re-captures only when the new record changes a class fact.  draws: as setRowsRequests' (kept when null).
+        void setRowRequest( int b, const SamplingParams& q, const float* draws = nullptr )
+        {
+            requireRows( b );
+            const std::string who = "GemmaTransformer::setRowRequest: row " + std::to_string( b );
+            if ( !std::isfinite( q.temperature ) ) throw std::invalid_argument( who + ": temperature is not finite" );
+            if ( q.top_k < 0 || !( q.top_p > 0.0f ) ) throw std::invalid_argument( who + ": need top_k >= 0, top_p > 0" );
+            q.checkFilters( who.c_str() );
+            if ( q.penalized() ) ensureTokenTable();
+            auto record = []( const SamplingParams& s, float temperature )
+            {
+                mila_sample_row_params rec{};
+                rec.temperature = temperature;
+                rec.top_k = s.top_k; rec.top_p = s.top_p; rec.min_p = s.min_p;
+                rec.repetition_penalty = s.repetition_penalty; rec.presence_penalty = s.presence_penalty; rec.frequency_penalty = s.frequency_penalty;
+                return rec;
+            };
+            if ( !row_params_ )
+            {
+                row_params_ = std::make_unique<TokenTensor>( ctx_->getDeviceId(), shape_t{ static_cast<dim_t>( mila_cdna4_sample_row_params_bytes( static_cast<int>( cfg_.max_batch ) ) / 4 ) } );
+                Compute::rocmCheck( mila_cdna4_memset_zero( row_params_->rawData(), row_params_->sizeInBytes(), ctx_->getStream() ) );
+            }
+            if ( row_requests_.empty() )      // the requests step turns on: every row vacant, as setRowsRequests leaves a row without a request
+            {
+                const mila_sample_row_params neutral = record( SamplingParams{}, 0.0f );
+                for ( int r = 0; r < static_cast<int>( cfg_.max_batch ); ++r )
+                    Compute::rocmCheck( mila_cdna4_sample_row_params_set( row_params_->rawData(), r, &neutral, ctx_->getStream() ) );
+            }
+            const mila_sample_row_params rec = record( q, q.temperature );
+            Compute::rocmCheck( mila_cdna4_sample_row_params_set( row_params_->rawData(), b, &rec, ctx_->getStream() ) );
+            if ( row_requests_.size() <= static_cast<size_t>( b ) )
+            {
+                row_requests_.resize( static_cast<size_t>( b ) + 1 );
+                row_request_vacant_.resize( static_cast<size_t>( b ) + 1, 1 );
+            }
+            row_requests_[ static_cast<size_t>( b ) ] = q;
+            row_request_vacant_[ static_cast<size_t>( b ) ] = 0;
+            if ( draws ) row_request_draws_ = draws;
+            if ( !row_masks_ )
+            {
+                row_masks_ = std::make_unique<TokenTensor>( ctx_->getDeviceId(), shape_t{ 2 * cfg_.max_batch } );
+                for ( int r = 0; r < static_cast<int>( cfg_.max_batch ); ++r ) refreshRowMasks( r );
+            }
+            else refreshRowMasks( b );
+        }
+        /// A SHARED PREFILL: row `src`, directly after prefillRow( src, tokens, len, 0 ) and before any step, into the rows of dst_mask (bit r = row r) -- every
+        /// layer's cache prefix [0, len) (one kv_rows_fork_bf16 launch per layer), the row's logits and the position word.  Afterwards a destination row is in
+        /// exactly the state prefillRow( dst, the same tokens ) would have left it in: the same cache bits, logits bits and position.  Throws invalid_argument when
+        /// row src's position word is not len (it was not prefilled with len tokens, or it has stepped: its logits are no longer the prefill's).
+        void forkRow( int src, unsigned dst_mask, dim_t len )
+        {
+            requireRows( src );
+            if ( dst_mask == 0 || ( dst_mask >> cfg_.max_batch ) != 0 || ( ( dst_mask >> src ) & 1u ) )
+                throw std::invalid_argument( "GemmaTransformer::forkRow: dst_mask " + std::to_string( dst_mask ) + " must name rows of the model other than the source row " + std::to_string( src ) );
+            if ( len < 1 || len > max_seq_ ) throw std::invalid_argument( "GemmaTransformer::forkRow: len " + std::to_string( len ) + " outside 1 .. " + std::to_string( max_seq_ ) );
+            int32_t at = -1;
+            Compute::rocmCheck( mila_cdna4_memcpy_d2h( &at, rows_->pos->data() + src, 4, ctx_->getStream() ) );
+            ctx_->synchronize();
+            if ( at != static_cast<int32_t>( len ) )
+                throw std::invalid_argument( "GemmaTransformer::forkRow: row " + std::to_string( src ) + " is at position " + std::to_string( at ) + ", not " + std::to_string( len ) +
+                                             " (a fork follows prefillRow( src, ..., len, 0 ) directly)" );
+            for ( auto& L : layers_ ) L.forkCacheRows( src, dst_mask, len );
+            const size_t V = static_cast<size_t>( cfg_.vocab_size );
+            for ( int r = 0; r < static_cast<int>( cfg_.max_batch ); ++r )
+            {
+                if ( !( ( dst_mask >> r ) & 1u ) ) continue;
+                Compute::rocmCheck( mila_cdna4_memcpy_d2d( rows_->logits->data() + static_cast<size_t>( r ) * V, rows_->logits->data() + static_cast<size_t>( src ) * V, V * 4, ctx_->getStream() ) );
+                setRowWord( rows_->pos->data(), r, static_cast<int32_t>( len ) );
+            }
+        }
+        void clearRowsRequests() noexcept { row_requests_.clear(); row_request_vacant_.clear(); row_request_draws_ = nullptr; }
         bool rowsRequestsOn() const noexcept { return !row_requests_.empty(); }
         /// row b's bias table for the requests samplers (setTokenBias's arguments): written into the row's effective table, or -- when the row has an automaton --
         /// into the table its automaton composes from (set the automaton FIRST).  clearRowTokenBias: zeros.  stage / commit: the min_tokens restore of that row.
@@ -810,7 +884,7 @@ namespace Mila::Dnn
         void sampleRowRequest( int b, float r )
         {
             requireRows( b );
-            if ( static_cast<size_t>( b ) >= row_requests_.size() ) throw std::invalid_argument( "GemmaTransformer::sampleRowRequest: row " + std::to_string( b ) + " has no request (setRowsRequests)" );
+            if ( static_cast<size_t>( b ) >= row_requests_.size() || row_request_vacant_[ static_cast<size_t>( b ) ] ) throw std::invalid_argument( "GemmaTransformer::sampleRowRequest: row " + std::to_string( b ) + " has no request (setRowsRequests)" );
             const SamplingParams& q = row_requests_[ static_cast<size_t>( b ) ];
             const size_t V = static_cast<size_t>( cfg_.vocab_size );
             const float* logits = rows_->logits->data() + static_cast<size_t>( b ) * V;
@@ -2258,6 +2332,7 @@ namespace Mila::Dnn
         }
         std::unique_ptr<TokenTensor> row_params_;
         std::vector<SamplingParams> row_requests_;      // empty: the rows step takes the shared parameters, as ever
+        std::vector<char> row_request_vacant_;          // beside row_requests_: 1 = a row below a setRowRequest row that has no request yet
         const float* row_request_draws_{ nullptr };
         std::unique_ptr<Compute::RocmTokenBiasRows> row_bias_;
         std::unique_ptr<Compute::RocmTokenAutomatonRows> row_automata_;
@@ -2270,6 +2345,7 @@ namespace Mila::Dnn
             k.on = true;
             for ( size_t b = 0; b < row_requests_.size(); ++b )
             {
+                if ( row_request_vacant_[ b ] ) continue;      // (setRowRequest: a row that never had a request carries no class)
                 const bool greedy = !( row_requests_[ b ].temperature > 0.0f ), c = rowConstrained( static_cast<int>( b ) );
                 if ( !greedy ) k.stochastic = true;
                 else ( c ? k.greedy_constrained : k.greedy_plain ) = true;

@@ -12,6 +12,7 @@
 #pragma once
 
 #include <atomic>
+#include <bit>
 #include <chrono>
 #include <cstring>
 #include <thread>
@@ -24,6 +25,7 @@
 #include <variant>
 
 #include "Gemma.h"
+#include "RequestQueue.h"
 #include "TokenAutomaton.h"
 #include "TokenBias.h"
 
@@ -175,8 +177,9 @@ namespace Mila::Dnn
         int max_new = 0;
     };
     /// every check generate() makes for the request, plus the rows rules (no speculative field; `logprobs` = the call's ONE top_n); throws invalid_argument with the
-    /// row's number in the message.  default_stops: the model's stop set, taken when the request names none.
-    inline RowRequestPlan planRowRequest( const BatchRequest& rq, const std::optional<int>& logprobs, int row, dim_t vocab, dim_t context, const std::unordered_set<int32_t>& default_stops )
+    /// row's number in the message.  default_stops: the model's stop set, taken when the request names none.  who: what the number counts (serveRequests: requests).
+    inline RowRequestPlan planRowRequest( const BatchRequest& rq, const std::optional<int>& logprobs, int row, dim_t vocab, dim_t context, const std::unordered_set<int32_t>& default_stops,
+                                          const char* who = "GemmaModel::generateRequests: row " )
     {
         try
         {
@@ -207,7 +210,7 @@ namespace Mila::Dnn
             checkRequestAutomaton( p, pl.bias, vocab );
             return pl;
         }
-        catch ( const std::invalid_argument& e ) { throw std::invalid_argument( "GemmaModel::generateRequests: row " + std::to_string( row ) + ": " + e.what() ); }
+        catch ( const std::invalid_argument& e ) { throw std::invalid_argument( who + std::to_string( row ) + ": " + e.what() ); }
     }
     /// host copies of the log-probabilities of up to four rows, and the callback over one of them
     struct TokenLogprobsRows
@@ -521,7 +524,232 @@ namespace Mila::Dnn
             }, network_ );
         }
 
+        /// What a serveRequests call did: the rows steps it replayed, the prefills it ran and their tokens, the rows that took a fork in place of a prefill, the
+        /// rows-graph captures during the call, and per request the row it ran in and the number of steps replayed before its admission.  The four times are host
+        /// wall-clock sums over the call's admissions (every phase ends in a synchronize of its own): the rows' setters, the prefills, the forks, and the first
+        /// samples with their readback
+        struct ServeStats
+        {
+            int64_t steps = 0, prefills = 0, prefill_tokens = 0, forks = 0, captures = 0;
+            double setters_ms = 0.0, prefill_ms = 0.0, fork_ms = 0.0, first_sample_ms = 0.0;
+            std::vector<int> row;
+            std::vector<int64_t> admitted_at;
+        };
+        /// generateRequests for ANY number of requests (>= 1) on a withMaxBatch( R > 1 ) model: a queue in front of the rows step.  Requests are admitted in FIFO
+        /// order, each into the lowest free row (Mila/RequestQueue.h holds the rule): the first min( n, R ) at the start, and after every step's readback each retired
+        /// row goes to the next waiting request before the next replay.  Admission runs what generateRequests runs per row, in its order -- resetRow, the automaton or
+        /// its clear, the bias table and its staged restore, setRowRequest, prefillRow, resetTokenTable, the first sample at the first draw of the request's OWN
+        /// generator (mt19937_64( seed )), its log-probability record, setRowActive -- and delivers the first token at once: a stop token there ends the request with
+        /// zero tokens and frees the row in the same round.  Requests admitted in the same round with an identical prompt share ONE prefill: the others take
+        /// GemmaTransformer::forkRow from that row, then their own table reset and first sample; nothing else is shared.  A row that has stepped is never forked from.
+        /// THE CONTRACT is generateRequests': request i gives, token for token, what generate() gives for it alone on a one-sequence model of the same weights after
+        /// seedSampler( seed_i ) -- tokens, finish reason, log-probability bits, final automaton state -- whatever the other requests are, whichever row it landed
+        /// in, whenever it was admitted, prefilled or forked (same limit: the unwindowed layers' live-length bucket follows the longest live row).
+        /// on_token( request, token ) / on_finish( request, status ) (once per request) / on_logprobs report the REQUEST's number.  logprobs: one n for the call.
+        /// Every request is checked before anything is enqueued, with its number in the message.  Not here: requests arriving during the call, cancellation,
+        /// priorities, prefixes shorter than a whole prompt, decode-ahead.
+        [[nodiscard]] std::vector<GenerateStatus> serveRequests( std::span<const BatchRequest> requests, const std::function<void( int, int32_t )>& on_token,
+                                                                 const std::function<void( int, GenerateStatus )>& on_finish = {},
+                                                                 std::vector<std::optional<int32_t>>* final_states = nullptr, ServeStats* stats = nullptr )
+        {
+            return std::visit( [&]( auto& net )
+            {
+                try
+                {
+                    auto status = onServingRequests( *net, requests, on_token, on_finish, final_states, stats );
+                    net->clearRowsRequests();
+                    return status;
+                }
+                catch ( const std::invalid_argument& ) { net->clearRowsRequests(); throw; }
+                catch ( ... ) { try { net->context()->synchronize(); } catch ( ... ) {} net->clearRowsRequests(); kv_token_history_.clear(); throw; }
+            }, network_ );
+        }
+
     private:
+        template<typename TNet>
+        std::vector<GenerateStatus> onServingRequests( TNet& net, std::span<const BatchRequest> requests, const std::function<void( int, int32_t )>& on_token,
+                                                       const std::function<void( int, GenerateStatus )>& on_finish, std::vector<std::optional<int32_t>>* final_states,
+                                                       ServeStats* stats )
+        {
+            Compute::TraceRange tr( "GemmaModel.serveRequests" );
+            const size_t n = requests.size();
+            const int R = static_cast<int>( net.maxBatch() );
+            if ( R < 2 ) throw std::invalid_argument( "GemmaModel::serveRequests: the model was built for one sequence (GemmaModelConfig::withMaxBatch)" );
+            if ( n < 1 ) throw std::invalid_argument( "GemmaModel::serveRequests: no request" );
+            std::vector<RowRequestPlan> plan;
+            std::vector<typename TNet::SamplingParams> sp;
+            std::vector<std::span<const int32_t>> prompts;
+            for ( size_t q = 0; q < n; ++q )
+            {
+                plan.push_back( planRowRequest( requests[ q ], requests[ 0 ].params.logprobs, static_cast<int>( q ), vocabSize(), contextLength(), stopTokens(), "GemmaModel::serveRequests: request " ) );
+                sp.push_back( networkSampling<TNet>( plan.back().sampling ) );
+                prompts.emplace_back( requests[ q ].prompt );
+            }
+            RequestQueue queue( R, promptClasses( prompts ) );
+            // ---- nothing was enqueued so far
+            kv_token_history_.clear();      // row 0's caches are overwritten: nothing is left to reuse
+            last_reuse_ = 0;
+            const std::optional<int> logprobs = requests[ 0 ].params.logprobs;
+            auto* ctx = net.context();
+            net.clearTokenAutomaton();
+            net.clearRowsRequests();      // every row vacant until its first admission (setRowRequest)
+            for ( int b = static_cast<int>( std::min<size_t>( n, static_cast<size_t>( R ) ) ); b < R; ++b )      // a row no request will enter at the start: as generateRequests leaves it
+            {
+                net.resetRow( b );
+                net.clearRowTokenAutomaton( b );
+                net.clearRowTokenBias( b );
+            }
+            net.setStepLogprobs( logprobs );
+            const size_t captures0 = net.graphRowsCaptureCount();
+            ServeStats st;
+            st.row.assign( n, -1 );
+            st.admitted_at.assign( n, -1 );
+            TokenLogprobsRows lp;
+            lp.top_n = logprobs.value_or( 0 );
+            std::vector<GenerateStatus> status( n, GenerateStatus::Success );
+            if ( final_states ) final_states->assign( n, std::nullopt );
+            // per ROW: the generator, position, emitted tokens and sample index of the request the row holds (rows are not in lockstep: all counted from the admission)
+            std::vector<std::mt19937_64> rng( static_cast<size_t>( R ) );
+            std::vector<dim_t> position( static_cast<size_t>( R ), 0 );
+            std::vector<int> emitted( static_cast<size_t>( R ), 0 ), samples( static_cast<size_t>( R ), 0 );
+            auto draw = [&]( int b ) { return std::uniform_real_distribution<float>( 0.0f, 1.0f )( rng[ static_cast<size_t>( b ) ] ); };
+            auto finish = [&]( int b, GenerateStatus s )
+            {
+                const int q = queue.requestOf( b );
+                status[ static_cast<size_t>( q ) ] = s;
+                if ( final_states ) ( *final_states )[ static_cast<size_t>( q ) ] = net.rowTokenAutomatonState( b );      // before the row is handed on
+                net.setRowActive( b, false );
+                queue.retire( b );
+                if ( on_finish ) on_finish( q, s );
+            };
+            // generateRequests' rules in its order: stop token, max_new_tokens, context.  true: the request has ended and its row is free
+            auto deliver = [&]( int b, int32_t token )
+            {
+                const int q = queue.requestOf( b );
+                const size_t i = static_cast<size_t>( q );
+                if ( plan[ i ].stop_ids.contains( token ) ) { finish( b, GenerateStatus::Success ); return true; }
+                if ( logprobs ) lp.report( requests[ i ].params.on_logprobs, q, b, token );
+                on_token( q, token );
+                ++emitted[ static_cast<size_t>( b ) ];
+                if ( emitted[ static_cast<size_t>( b ) ] >= plan[ i ].max_new ) { finish( b, GenerateStatus::MaxNewTokensReached ); return true; }
+                if ( position[ static_cast<size_t>( b ) ] >= contextLength() ) { finish( b, GenerateStatus::ContextOverflow ); return true; }
+                return false;
+            };
+            using Clock = std::chrono::steady_clock;
+            auto since = []( Clock::time_point t0 ) { return std::chrono::duration<double, std::milli>( Clock::now() - t0 ).count(); };
+            auto admitRound = [&]
+            {
+                for ( auto wave = queue.admit(); !wave.empty(); wave = queue.admit() )
+                {
+                    auto t0 = Clock::now();
+                    for ( const auto& a : wave )      // the row's setters, in generateRequests' order
+                    {
+                        const int b = a.row;
+                        const size_t i = static_cast<size_t>( a.request );
+                        net.resetRow( b );
+                        const GenerateParams& p = requests[ i ].params;
+                        // the automaton first: a row with one keeps its bias in the table the automaton composes from
+                        if ( p.automaton ) net.setRowTokenAutomaton( b, *p.automaton ); else net.clearRowTokenAutomaton( b );
+                        const TokenBiasPlan& bp = plan[ i ].bias;
+                        if ( bp.active )
+                        {
+                            net.setRowTokenBias( b, bp.fill, bp.ids.data(), bp.values.data(), bp.ids.size() );
+                            if ( bp.hasRestore() ) net.stageRowTokenBiasUpdate( b, bp.restore_ids.data(), bp.restore_values.data(), bp.restore_ids.size() );
+                        }
+                        else net.clearRowTokenBias( b );
+                        net.setRowRequest( b, sp[ i ], row_draws_dev_ );
+                        rng[ static_cast<size_t>( b ) ] = std::mt19937_64( requests[ i ].seed );
+                        emitted[ static_cast<size_t>( b ) ] = 0;
+                        samples[ static_cast<size_t>( b ) ] = 0;
+                        st.row[ i ] = b;
+                        st.admitted_at[ i ] = queue.steps();
+                    }
+                    st.setters_ms += since( t0 );
+                    unsigned filled = 0;      // rows of this wave whose caches, logits and position are in place
+                    auto forkFrom = [&]( int src, dim_t len )      // ONE fork for every row of the wave that shares row src's prefill
+                    {
+                        unsigned mask = 0;
+                        for ( const auto& m : wave ) if ( m.fork_from == src && !( ( filled >> m.row ) & 1u ) ) mask |= 1u << m.row;
+                        if ( !mask ) return;
+                        const auto f0 = Clock::now();
+                        net.forkRow( src, mask, len );
+                        ctx->synchronize();
+                        st.fork_ms += since( f0 );
+                        filled |= mask;
+                        st.forks += std::popcount( mask );
+                    };
+                    for ( const auto& a : wave )
+                    {
+                        const auto& prompt = requests[ static_cast<size_t>( a.request ) ].prompt;
+                        const dim_t len = static_cast<dim_t>( prompt.size() );
+                        if ( a.fork_from < 0 )
+                        {
+                            const auto p0 = Clock::now();
+                            TokenTensor toks( ctx->getDeviceId(), shape_t{ 1, len } );
+                            Compute::rocmCheck( mila_cdna4_memcpy_h2d( toks.rawData(), prompt.data(), static_cast<size_t>( len ) * 4, ctx->getStream() ) );
+                            net.prefillRow( a.row, toks, len, 0 );
+                            ctx->synchronize();
+                            st.prefill_ms += since( p0 );
+                            filled |= 1u << a.row;
+                            ++st.prefills;
+                            st.prefill_tokens += len;
+                        }
+                        else if ( !( ( filled >> a.row ) & 1u ) ) forkFrom( a.fork_from, len );      // (its source: a row of an earlier wave of this round, or filled above)
+                        forkFrom( a.row, len );
+                    }
+                    t0 = Clock::now();
+                    for ( const auto& a : wave )
+                    {
+                        const int b = a.row;
+                        const size_t i = static_cast<size_t>( a.request );
+                        const auto& prompt = requests[ i ].prompt;
+                        position[ static_cast<size_t>( b ) ] = static_cast<dim_t>( prompt.size() );
+                        if ( sp[ i ].penalized() ) net.resetTokenTable( b, prompt.data(), prompt.size() );      // before the row's first sample
+                        net.sampleRowRequest( b, plan[ i ].greedy ? 0.0f : draw( b ) );      // the first token, from the prefill's logits, then the row's automaton
+                        samples[ static_cast<size_t>( b ) ] = 1;
+                        if ( logprobs ) { net.enqueueRowLogprobs( b ); lp.readInto( net.tokenLogprobs(), b ); }
+                        int32_t token = 0;
+                        Compute::rocmCheck( mila_cdna4_memcpy_d2h( &token, net.rowsTokens().data() + b, 4, ctx->getStream() ) );
+                        ctx->synchronize();
+                        net.setRowActive( b, true );
+                        (void)deliver( b, token );      // a request that ends here frees its row for the next wave of this round
+                    }
+                    st.first_sample_ms += since( t0 );
+                }
+            };
+            admitRound();
+            std::vector<int32_t> tokens( static_cast<size_t>( R ) );
+            while ( queue.live() > 0 )
+            {
+                const int B = queue.rowsInStep();
+                dim_t max_position = 0;
+                for ( int b = 0; b < R; ++b ) if ( queue.requestOf( b ) >= 0 ) max_position = std::max( max_position, position[ static_cast<size_t>( b ) ] );
+                net.ensureGraphRows( B, max_position, false );      // (the class facts, the row count and the bucket: never a row's parameters)
+                for ( int b = 0; b < R; ++b )
+                {
+                    const int q = queue.requestOf( b );
+                    if ( q < 0 ) continue;
+                    const RowRequestPlan& pl = plan[ static_cast<size_t>( q ) ];
+                    if ( !pl.greedy ) writeRowDraw( b, draw( b ) );      // one draw per live stochastic row, from that request's generator
+                    if ( pl.bias.hasRestore() && samples[ static_cast<size_t>( b ) ] == pl.bias.restore_index ) net.commitRowTokenBiasUpdate( b );      // the row's OWN sample index
+                }
+                net.replayGraphRows();
+                queue.step();
+                ++st.steps;
+                for ( int b = 0; b < R; ++b )
+                    if ( queue.requestOf( b ) >= 0 ) { ++position[ static_cast<size_t>( b ) ]; ++samples[ static_cast<size_t>( b ) ]; }
+                Compute::rocmCheck( mila_cdna4_memcpy_d2h( tokens.data(), net.rowsTokens().data(), static_cast<size_t>( B ) * 4, ctx->getStream() ) );
+                ctx->synchronize();
+                if ( logprobs ) lp.read( net.tokenLogprobs(), B );
+                for ( int b = 0; b < B; ++b )
+                    if ( queue.requestOf( b ) >= 0 ) (void)deliver( b, tokens[ static_cast<size_t>( b ) ] );
+                admitRound();      // each retired row to the next waiting request, before the next replay
+            }
+            ctx->synchronize();
+            st.captures = static_cast<int64_t>( net.graphRowsCaptureCount() - captures0 );
+            if ( stats ) *stats = std::move( st );
+            return status;
+        }
         template<typename TNet>
         std::vector<GenerateStatus> onGeneratingRequests( TNet& net, std::span<const BatchRequest> requests, const std::function<void( int, int32_t )>& on_token,
                                                           std::vector<std::optional<int32_t>>* final_states )

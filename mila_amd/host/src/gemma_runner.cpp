@@ -2114,6 +2114,30 @@ struct mila_gemma_row_request
     int32_t logprobs;                                    ///< < 0: none
     int32_t speculative;                                 ///< bit 0 speculative_sampling, bit 1 speculate_constrained, bit 2 a drafter: all refused
 };
+/// the C rows of a requests call as BatchRequests (who: the entry's name for the refusals); the log-probability sink counts per request
+static void read_row_requests( const mila_gemma_row_request* requests, int n, std::vector<BatchRequest>& rq, LogprobSink& sink, std::vector<int64_t>& lp_counts, const char* who )
+{
+    for ( int b = 0; b < n; ++b )
+    {
+        const auto& q = requests[ b ];
+        auto& r = rq[ static_cast<size_t>( b ) ];
+        if ( q.n_prompt < 0 || q.n_stop < 0 || ( q.n_prompt && !q.prompt ) || ( q.n_stop && !q.stop_tokens ) ) throw std::invalid_argument( std::string( who ) + ": null list" );
+        r.prompt.assign( q.prompt, q.prompt + q.n_prompt );
+        r.seed = q.seed;
+        GenerateParams& gp = r.params;
+        sink.attach( gp, [&lp_counts]( int row ) -> int64_t& { return lp_counts.at( static_cast<size_t>( row ) ); } );
+        if ( q.logprobs >= 0 ) gp.logprobs = q.logprobs; else gp.logprobs.reset();      // each row's own value: the model refuses rows that differ
+        if ( q.max_new >= 0 ) gp.max_new_tokens = q.max_new;
+        gp.sampling.temperature = q.temperature; gp.sampling.top_k = q.top_k; gp.sampling.top_p = q.top_p;
+        apply_request_filters( gp.sampling, q.filters );
+        apply_request_bias( gp, q.bias );
+        apply_request_automaton( gp, q.automaton );
+        gp.stop_tokens.assign( q.stop_tokens, q.stop_tokens + q.n_stop );
+        gp.speculative_sampling = ( q.speculative & 1 ) != 0;
+        gp.speculate_constrained = ( q.speculative & 2 ) != 0;
+        if ( q.speculative & 4 ) gp.draft = []( std::span<const int32_t>, int ) { return std::vector<int32_t>{}; };
+    }
+}
 /// GemmaModel::generateRequests: row b runs requests[ b ].  out_tokens [n, cap], out_counts / out_status [n]; the log-probability entries of row b at
 /// out_logprob[ b * cap .. ) and out_ids / out_logprobs[ ( b * cap + i ) * top_n .. ) with top_n = requests[ 0 ].logprobs (the arrays may be NULL without
 /// log-probabilities), their numbers to out_logprob_counts [n]; out_states / out_has_state [n]: the final automaton state of a row that had one
@@ -2127,26 +2151,7 @@ HOST_API int mila_gemma_model_generate_requests( void* h, const mila_gemma_row_r
         std::vector<BatchRequest> rq( static_cast<size_t>( n ) );
         std::vector<int64_t> lp_counts( static_cast<size_t>( std::max( n, 1 ) ), 0 );
         LogprobSink sink{ n > 0 ? requests[ 0 ].logprobs : -1, out_logprob, out_ids, out_logprobs, cap };
-        for ( int b = 0; b < n; ++b )
-        {
-            const auto& q = requests[ b ];
-            auto& r = rq[ static_cast<size_t>( b ) ];
-            if ( q.n_prompt < 0 || q.n_stop < 0 || ( q.n_prompt && !q.prompt ) || ( q.n_stop && !q.stop_tokens ) ) throw std::invalid_argument( "gemma_model_generate_requests: null list" );
-            r.prompt.assign( q.prompt, q.prompt + q.n_prompt );
-            r.seed = q.seed;
-            GenerateParams& gp = r.params;
-            sink.attach( gp, [&lp_counts]( int row ) -> int64_t& { return lp_counts.at( static_cast<size_t>( row ) ); } );
-            if ( q.logprobs >= 0 ) gp.logprobs = q.logprobs; else gp.logprobs.reset();      // each row's own value: the model refuses rows that differ
-            if ( q.max_new >= 0 ) gp.max_new_tokens = q.max_new;
-            gp.sampling.temperature = q.temperature; gp.sampling.top_k = q.top_k; gp.sampling.top_p = q.top_p;
-            apply_request_filters( gp.sampling, q.filters );
-            apply_request_bias( gp, q.bias );
-            apply_request_automaton( gp, q.automaton );
-            gp.stop_tokens.assign( q.stop_tokens, q.stop_tokens + q.n_stop );
-            gp.speculative_sampling = ( q.speculative & 1 ) != 0;
-            gp.speculate_constrained = ( q.speculative & 2 ) != 0;
-            if ( q.speculative & 4 ) gp.draft = []( std::span<const int32_t>, int ) { return std::vector<int32_t>{}; };
-        }
+        read_row_requests( requests, n, rq, sink, lp_counts, "gemma_model_generate_requests" );
         std::vector<int64_t> counts( static_cast<size_t>( n ), 0 );
         std::vector<std::optional<int32_t>> states;
         const auto st = m->generateRequests( rq, [&]( int b, int32_t t ) { int64_t& c = counts[ static_cast<size_t>( b ) ]; if ( out_tokens && c < cap ) out_tokens[ b * cap + c ] = t; ++c; }, &states );
@@ -2157,6 +2162,48 @@ HOST_API int mila_gemma_model_generate_requests( void* h, const mila_gemma_row_r
             if ( out_states ) out_states[ b ] = states[ static_cast<size_t>( b ) ].value_or( 0 );
             if ( out_has_state ) out_has_state[ b ] = states[ static_cast<size_t>( b ) ] ? 1 : 0;
         }
+    } );
+}
+/// GemmaModel::serveRequests: mila_gemma_model_generate_requests for ANY n >= 1, the outputs indexed by REQUEST.  Beside them: out_rows [n] the row a request ran in,
+/// out_admitted_at [n] the rows steps replayed before its admission, out_finish_order [n] the position of its on_finish among the call's, and out_stats [5] =
+/// {rows steps, prefills, prefill tokens, forks, rows-graph captures during the call}, out_times [4] = the host milliseconds the call's admissions spent in
+/// {the rows' setters, prefills, forks, first samples}
+HOST_API int mila_gemma_model_serve_requests( void* h, const mila_gemma_row_request* requests, int n, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status,
+                                              float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts, int32_t* out_states, int32_t* out_has_state,
+                                              int32_t* out_rows, int64_t* out_admitted_at, int32_t* out_finish_order, int64_t* out_stats, double* out_times )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m || !requests || !out_counts || !out_status || n < 0 ) throw std::invalid_argument( "gemma_model_serve_requests: null argument" );
+        std::vector<BatchRequest> rq( static_cast<size_t>( n ) );
+        std::vector<int64_t> lp_counts( static_cast<size_t>( std::max( n, 1 ) ), 0 );
+        LogprobSink sink{ n > 0 ? requests[ 0 ].logprobs : -1, out_logprob, out_ids, out_logprobs, cap };
+        read_row_requests( requests, n, rq, sink, lp_counts, "gemma_model_serve_requests" );
+        std::vector<int64_t> counts( static_cast<size_t>( n ), 0 );
+        std::vector<int32_t> finished( static_cast<size_t>( n ), -1 );
+        int32_t finishes = 0;
+        std::vector<std::optional<int32_t>> states;
+        RocmGemmaModel::ServeStats stats;
+        const auto st = m->serveRequests( rq, [&]( int q, int32_t t ) { int64_t& c = counts[ static_cast<size_t>( q ) ]; if ( out_tokens && c < cap ) out_tokens[ q * cap + c ] = t; ++c; },
+                                          [&]( int q, GenerateStatus )
+                                          {
+                                              if ( finished.at( static_cast<size_t>( q ) ) >= 0 ) throw std::logic_error( "gemma_model_serve_requests: a request finished twice" );
+                                              finished[ static_cast<size_t>( q ) ] = finishes++;
+                                          }, &states, &stats );
+        for ( int q = 0; q < n; ++q )
+        {
+            const size_t i = static_cast<size_t>( q );
+            out_counts[ q ] = counts[ i ]; out_status[ q ] = static_cast<int32_t>( st[ i ] );
+            if ( out_logprob_counts ) out_logprob_counts[ q ] = lp_counts[ i ];
+            if ( out_states ) out_states[ q ] = states[ i ].value_or( 0 );
+            if ( out_has_state ) out_has_state[ q ] = states[ i ] ? 1 : 0;
+            if ( out_rows ) out_rows[ q ] = stats.row[ i ];
+            if ( out_admitted_at ) out_admitted_at[ q ] = stats.admitted_at[ i ];
+            if ( out_finish_order ) out_finish_order[ q ] = finished[ i ];
+        }
+        if ( out_stats ) { out_stats[ 0 ] = stats.steps; out_stats[ 1 ] = stats.prefills; out_stats[ 2 ] = stats.prefill_tokens; out_stats[ 3 ] = stats.forks; out_stats[ 4 ] = stats.captures; }
+        if ( out_times ) { out_times[ 0 ] = stats.setters_ms; out_times[ 1 ] = stats.prefill_ms; out_times[ 2 ] = stats.fork_ms; out_times[ 3 ] = stats.first_sample_ms; }
     } );
 }
 
