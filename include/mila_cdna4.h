@@ -1085,6 +1085,23 @@ MILA_API int mila_cdna4_token_automaton_rows_step(float* eff, size_t eff_stride,
 MILA_API int mila_cdna4_kv_rows_fork_bf16(uint16_t* K, uint16_t* V, int rows, int NKV, int capacity, int HS, int src, unsigned dst_mask, int len,
                                           mila_stream_t stream);
 
+/* kv_rows_fork_bf16 for n layers in ONE launch (ABI 4, additive; csrc/kv_rows_fork.hip): layer i has its own caches and its own (NKV, capacity, HS); the rows, src,
+ * dst_mask and len are shared.  `layers` is a HOST array of n_layers records -- the caller builds it once and keeps it; the entry passes the records to the kernel
+ * by value in its argument block, up to 64 layers per launch (more layers: further launches of the same call), so the call allocates nothing, copies nothing from
+ * host to device and reads nothing back.  The layer is the grid's y index; within a layer a grid-stride walk over its 16-byte units, each read once from row `src`
+ * and stored to every row of dst_mask, every element offset in 64 bits, plain vector loads and stores of bit patterns, no LDS, no atomics.  Byte for byte the
+ * result is n_layers calls of kv_rows_fork_bf16.
+ * Refused before any device work (MILA_E_INVALID_ARGUMENT), from host-known values alone, with the layer's number in the message: a null `layers`, n_layers <= 0,
+ * rows outside 2 .. 4, src outside the rows, a dst_mask that is empty, names src or names a row >= rows, len < 1, and per layer kv_rows_fork_bf16's own checks -- a
+ * null or misaligned K or V, NKV / capacity / HS <= 0, HS no multiple of 8, len above that layer's capacity.  A refusal launches nothing, for no layer. */
+typedef struct mila_kv_fork_layer {
+    uint16_t* K;            /* [rows, NKV, capacity, HS] bf16, device */
+    uint16_t* V;
+    int32_t NKV, capacity, HS;
+    int32_t reserved;       /* 0 */
+} mila_kv_fork_layer;
+MILA_API int mila_cdna4_kv_rows_fork_layers_bf16(const mila_kv_fork_layer* layers, int n_layers, int rows, int src, unsigned dst_mask, int len, mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,11 @@ class InvalidArgument(MilaError, ValueError):
     """reference: std::invalid_argument"""
 
 
+class KvForkLayer(C.Structure):
+    """mila_kv_fork_layer: one layer's record for kv_rows_fork_layers_bf16 (K and V: device addresses)"""
+    _fields_ = [("K", C.c_void_p), ("V", C.c_void_p), ("NKV", C.c_int32), ("capacity", C.c_int32), ("HS", C.c_int32), ("reserved", C.c_int32)]
+
+
 _lib = None
 EXPERIMENTS_PATH = os.path.join(_HERE, "lib", "libmila_cdna4_experiments.so")
 
@@ -156,6 +161,7 @@ def load():
     main.mila_cdna4_token_automaton_rows_step.argtypes = [p, z, p, z, p, p, p, p, p, i, i, p]                     # ... desc_dev state_dev token_dev active_dev ticket_dev | rows vocab
     # a shared prefill's device primitive (csrc/kv_rows_fork.hip)
     main.mila_cdna4_kv_rows_fork_bf16.argtypes = [p, p, i, i, i, i, i, i, i, p]                                   # K V | rows NKV capacity HS | src dst_mask len
+    main.mila_cdna4_kv_rows_fork_layers_bf16.argtypes = [p, i, i, i, i, i, p]                                     # layers (host records) n_layers | rows src dst_mask len
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -819,7 +825,7 @@ EXPORTED = [
     "sample_row_params_bytes", "sample_row_params_set", "sample_radix_requests_rows_fp32", "sample_radix_requests_rows_advance_fp32",
     "sample_argmax_requests_rows_fp32", "sample_argmax_requests_rows_advance_fp32",
     "token_automaton_rows_bytes", "token_automaton_rows_set", "token_automaton_rows_compose", "token_automaton_rows_step",
-    "kv_rows_fork_bf16",
+    "kv_rows_fork_bf16", "kv_rows_fork_layers_bf16",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

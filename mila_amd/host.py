@@ -596,6 +596,20 @@ class Gemma:
         lib.mila_gemma_reset_row.argtypes = [C.c_void_p, C.c_int]
         _check(lib.mila_gemma_reset_row(self.h, int(b)))
 
+    def fork_row(self, src, dst_mask, length):
+        """GemmaTransformer::forkRow: a shared prefill -- directly behind prefill_row(src, tokens of `length`), row src's cache prefix [0, length) of every layer, its
+        logits and its position into the rows of dst_mask (bit r = row r)"""
+        lib = load()
+        lib.mila_gemma_fork_row.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int64, C.c_int]
+        _check(lib.mila_gemma_fork_row(self.h, int(src), int(dst_mask), int(length), 1))
+
+    def fork_row_prefix(self, src, dst_mask, length):
+        """GemmaTransformer::forkRowPrefix: a shared prefix -- the caches only, [0, length) of every layer, from ANY row at a position >= length (it may have stepped)
+        into the rows of dst_mask; no logits, no position: prefill_row(dst, suffix, offset=length) follows.  One launch for all layers."""
+        lib = load()
+        lib.mila_gemma_fork_row.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int64, C.c_int]
+        _check(lib.mila_gemma_fork_row(self.h, int(src), int(dst_mask), int(length), 0))
+
     def decode_rows(self, B, max_position, mode="graph", greedy=True, sampling=None, draws=None, logprobs=None):
         """one step over rows 0 .. B - 1, eager ("fused") or as a graph replay; greedy: the step ends with the rows sampler tail.  max_position: the largest
         position among the active rows.  Returns (logits [B, vocab], tokens [B], positions [B]) as they stand AFTER the step.
@@ -1210,6 +1224,38 @@ class GemmaModel:
         "captures": rows-graph captures during the call, "rows": the row each request ran in, "admitted_at": the steps replayed before each admission,
         "finish_order": the position of each request's end among the call's, "admission_ms": host milliseconds the admissions spent in their
         {"setters", "prefill", "fork", "first_sample"}}."""
+        return self._serve(requests, logprobs, None)
+
+    def serve_requests_prefix(self, requests, logprobs=None, prefix_cache=True, min_prefix=1):
+        """GemmaModel::serveRequests( ..., ServeParams{ prefix_cache, min_prefix } ): serve_requests with THE PREFIX CACHE.  Every row keeps a claim -- the tokens whose
+        KV its caches hold -- beyond its request, until the row is written; an admission takes the longest prefix L <= len - 1 of its prompt that any row holds (a live
+        one, a retired one, its own) by one fork of that prefix (none in place) and prefills only prompt[L:].  The claims live in the model: a later call reuses them;
+        generate, generate_batch, generate_requests, score, a serve_requests without the cache and any failing serving call clear them (clear_prefix_cache(): by
+        hand; prefix_cache_lengths(): what is held).  Request i gives what generate() gives for it on a one-sequence model on which its donors' requests ran before
+        it, generate() itself reusing L positions.  min_prefix: the shortest prefix worth reusing (>= 1).  prefix_cache=False: serve_requests, the same stats dict.
+        With the cache on, stats gains "reused_tokens" and "donor_row" per request (-1: none; the own row: in place; a whole fork of an identical prompt: its length
+        and that row) and the totals "prefix_forks" and "prefix_in_place"; "prefill_tokens" counts the tokens actually prefilled.  (An entry of its own:
+        serve_requests keeps its signature.)"""
+        if isinstance(min_prefix, bool) or not isinstance(min_prefix, (int, np.integer)) or min_prefix < 1:
+            raise ValueError("GemmaModel.serve_requests_prefix: min_prefix must be an integer >= 1 (got %r)" % (min_prefix,))
+        return self._serve(requests, logprobs, (bool(prefix_cache), int(min_prefix)))
+
+    def clear_prefix_cache(self):
+        """GemmaModel::clearPrefixCache: forget what the rows hold"""
+        lib = load()
+        lib.mila_gemma_model_clear_prefix_cache.argtypes = [C.c_void_p]
+        _check(lib.mila_gemma_model_clear_prefix_cache(self.h))
+
+    def prefix_cache_lengths(self):
+        """GemmaModel::prefixCacheLengths: per row, the number of cache positions the prefix cache knows the tokens of"""
+        lib = load()
+        lib.mila_gemma_model_prefix_cache_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        out, rows = (C.c_int64 * 4)(), C.c_int32(0)
+        _check(lib.mila_gemma_model_prefix_cache_lengths(self.h, out, C.byref(rows)))
+        return [int(out[r]) for r in range(rows.value)]
+
+    def _serve(self, requests, logprobs, prefix):
+        """serve_requests (prefix None) / serve_requests_prefix (prefix = (prefix_cache, min_prefix))"""
         lib = load()
         flat = []
         for q in requests:
@@ -1231,11 +1277,16 @@ class GemmaModel:
         with_lp = top_n >= 0
         lp, ids, tlp = (np.zeros(out.shape if with_lp else (1, 1), dtype=np.float32), np.zeros((out.shape if with_lp else (1, 1)) + (width,), dtype=np.int32),
                         np.zeros((out.shape if with_lp else (1, 1)) + (width,), dtype=np.float32))
-        lib.mila_gemma_model_serve_requests.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 13
-        _check(lib.mila_gemma_model_serve_requests(self.h, C.addressof(rq), n, out.ctypes.data, cap, counts.ctypes.data, status.ctypes.data,
-                                                   lp.ctypes.data if with_lp else None, ids.ctypes.data if with_lp else None, tlp.ctypes.data if with_lp else None,
-                                                   lp_counts.ctypes.data, states.ctypes.data, has_state.ctypes.data, rows_of.ctypes.data, admitted.ctypes.data,
-                                                   finish.ctypes.data, totals.ctypes.data, times.ctypes.data))
+        args = (self.h, C.addressof(rq), n, out.ctypes.data, cap, counts.ctypes.data, status.ctypes.data, lp.ctypes.data if with_lp else None,
+                ids.ctypes.data if with_lp else None, tlp.ctypes.data if with_lp else None, lp_counts.ctypes.data, states.ctypes.data, has_state.ctypes.data,
+                rows_of.ctypes.data, admitted.ctypes.data, finish.ctypes.data, totals.ctypes.data, times.ctypes.data)
+        if prefix is None:
+            lib.mila_gemma_model_serve_requests.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 13
+            _check(lib.mila_gemma_model_serve_requests(*args))
+        else:
+            reused, donor, prefix_totals = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int32), np.zeros(2, dtype=np.int64)
+            lib.mila_gemma_model_serve_requests_prefix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 13 + [C.c_int, C.c_int] + [C.c_void_p] * 3
+            _check(lib.mila_gemma_model_serve_requests_prefix(*args, int(prefix[0]), prefix[1], reused.ctypes.data, donor.ctypes.data, prefix_totals.ctypes.data))
         rows = []
         for b in range(n):
             row = (out[b, :min(int(counts[b]), cap)].tolist(), GENERATE_STATUS[int(status[b])])
@@ -1247,6 +1298,8 @@ class GemmaModel:
         stats = {"steps": int(totals[0]), "prefills": int(totals[1]), "prefill_tokens": int(totals[2]), "forks": int(totals[3]), "captures": int(totals[4]),
                  "rows": rows_of[:n].tolist(), "admitted_at": admitted[:n].tolist(), "finish_order": finish[:n].tolist(),
                  "admission_ms": dict(zip(("setters", "prefill", "fork", "first_sample"), (float(t) for t in times)))}
+        if prefix is not None and prefix[0]:
+            stats.update(reused_tokens=reused[:n].tolist(), donor_row=donor[:n].tolist(), prefix_forks=int(prefix_totals[0]), prefix_in_place=int(prefix_totals[1]))
         return rows, stats
 
     def rows_graph_info(self):

@@ -791,7 +791,7 @@ namespace Mila::Dnn
             else refreshRowMasks( b );
         }
         /// A SHARED PREFILL: row `src`, directly after prefillRow( src, tokens, len, 0 ) and before any step, into the rows of dst_mask (bit r = row r) -- every
-        /// layer's cache prefix [0, len) (one kv_rows_fork_bf16 launch per layer), the row's logits and the position word.  Afterwards a destination row is in
+        /// layer's cache prefix [0, len) (one kv_rows_fork_layers_bf16 launch for all layers), the row's logits and the position word.  Afterwards a destination row is in
         /// exactly the state prefillRow( dst, the same tokens ) would have left it in: the same cache bits, logits bits and position.  Throws invalid_argument when
         /// row src's position word is not len (it was not prefilled with len tokens, or it has stepped: its logits are no longer the prefill's).
         void forkRow( int src, unsigned dst_mask, dim_t len )
@@ -806,7 +806,7 @@ namespace Mila::Dnn
             if ( at != static_cast<int32_t>( len ) )
                 throw std::invalid_argument( "GemmaTransformer::forkRow: row " + std::to_string( src ) + " is at position " + std::to_string( at ) + ", not " + std::to_string( len ) +
                                              " (a fork follows prefillRow( src, ..., len, 0 ) directly)" );
-            for ( auto& L : layers_ ) L.forkCacheRows( src, dst_mask, len );
+            forkLayers( src, dst_mask, len );
             const size_t V = static_cast<size_t>( cfg_.vocab_size );
             for ( int r = 0; r < static_cast<int>( cfg_.max_batch ); ++r )
             {
@@ -814,6 +814,25 @@ namespace Mila::Dnn
                 Compute::rocmCheck( mila_cdna4_memcpy_d2d( rows_->logits->data() + static_cast<size_t>( r ) * V, rows_->logits->data() + static_cast<size_t>( src ) * V, V * 4, ctx_->getStream() ) );
                 setRowWord( rows_->pos->data(), r, static_cast<int32_t>( len ) );
             }
+        }
+        /// A SHARED PREFIX: every layer's cache positions [0, len) of row `src` into the rows of dst_mask, and nothing else -- no logits, no position word: the
+        /// prefillRow( dst, suffix, n - len, len ) that follows sets both.  Row src may be live, retired, and may have stepped: whatever sits at [0, len) of its
+        /// caches is copied, and it must be at a position >= len (below it the caches hold nothing the row ever wrote).  One kv_rows_fork_layers_bf16 launch for all
+        /// layers.  Refused (invalid_argument) before anything is enqueued: a one-row model, a mask that is empty, names src or a row outside the model, len < 1 or
+        /// beyond the context; then the row's position word is read, and a len beyond it is refused as well.
+        void forkRowPrefix( int src, unsigned dst_mask, dim_t len )
+        {
+            if ( !rows_ || cfg_.max_batch <= 1 ) throw std::invalid_argument( "GemmaTransformer::forkRowPrefix: the model was built for one sequence (GemmaConfig::max_batch > 1)" );
+            if ( src < 0 || src >= cfg_.max_batch ) throw std::invalid_argument( "GemmaTransformer::forkRowPrefix: source row " + std::to_string( src ) + " outside max_batch " + std::to_string( cfg_.max_batch ) );
+            if ( dst_mask == 0 || ( dst_mask >> cfg_.max_batch ) != 0 || ( ( dst_mask >> src ) & 1u ) )
+                throw std::invalid_argument( "GemmaTransformer::forkRowPrefix: dst_mask " + std::to_string( dst_mask ) + " must name rows of the model other than the source row " + std::to_string( src ) );
+            if ( len < 1 || len > max_seq_ ) throw std::invalid_argument( "GemmaTransformer::forkRowPrefix: len " + std::to_string( len ) + " outside 1 .. " + std::to_string( max_seq_ ) );
+            int32_t at = -1;
+            Compute::rocmCheck( mila_cdna4_memcpy_d2h( &at, rows_->pos->data() + src, 4, ctx_->getStream() ) );
+            ctx_->synchronize();
+            if ( static_cast<int32_t>( len ) > at )
+                throw std::invalid_argument( "GemmaTransformer::forkRowPrefix: len " + std::to_string( len ) + " beyond row " + std::to_string( src ) + "'s position " + std::to_string( at ) );
+            forkLayers( src, dst_mask, len );
         }
         void clearRowsRequests() noexcept { row_requests_.clear(); row_request_vacant_.clear(); row_request_draws_ = nullptr; }
         bool rowsRequestsOn() const noexcept { return !row_requests_.empty(); }
@@ -1816,6 +1835,12 @@ namespace Mila::Dnn
             if ( chain_graph_exec_ ) { (void)hipGraphExecDestroy( chain_graph_exec_ ); chain_graph_exec_ = nullptr; }
             if ( chain_graph_ ) { (void)hipGraphDestroy( chain_graph_ ); chain_graph_ = nullptr; }
         }
+        /// every layer's cache prefix in one launch, from the table buildRows() made (mila_cdna4.h: kv_rows_fork_layers_bf16)
+        void forkLayers( int src, unsigned dst_mask, dim_t len )
+        {
+            Compute::rocmCheck( mila_cdna4_kv_rows_fork_layers_bf16( fork_layers_.data(), static_cast<int>( fork_layers_.size() ), static_cast<int>( cfg_.max_batch ), src, dst_mask,
+                                                                     static_cast<int>( len ), ctx_->getStream() ) );
+        }
         void requireRows( int b ) const
         {
             if ( !rows_ || cfg_.max_batch <= 1 ) throw std::logic_error( "GemmaTransformer: the rows interface needs GemmaConfig::max_batch > 1" );
@@ -1852,7 +1877,16 @@ namespace Mila::Dnn
         {
             const dim_t B = rowsCount(), D = cfg_.embedding_dim;
             const auto dev = ctx_->getDeviceId();
-            if ( cfg_.max_batch > 1 ) for ( auto& L : layers_ ) L.setCacheRows( static_cast<int>( B ) );
+            if ( cfg_.max_batch > 1 )
+            {
+                fork_layers_.clear();      // the layer table of forkRow / forkRowPrefix: built once, here
+                for ( auto& L : layers_ )
+                {
+                    L.setCacheRows( static_cast<int>( B ) );
+                    fork_layers_.push_back( mila_kv_fork_layer{ L.keyCacheRows(), L.valueCacheRows(), static_cast<int32_t>( cfg_.numKvHeads( L.global ) ),
+                                                                static_cast<int32_t>( L.cacheCapacity() ), static_cast<int32_t>( cfg_.headDim( L.global ) ), 0 } );
+                }
+            }
             rows_ = std::make_unique<RowsState>();
             auto& R = *rows_;
             R.qkv = std::make_unique<TensorType>( dev, shape_t{ B, std::max( cfg_.packedQkvWidth( false ), cfg_.packedQkvWidth( true ) ) } );
@@ -2231,6 +2265,7 @@ namespace Mila::Dnn
         std::unique_ptr<IExecutionContext> owned_ctx_;
         Compute::RocmExecutionContext* ctx_{ nullptr };
         LayerList layers_;
+        std::vector<mila_kv_fork_layer> fork_layers_;
         std::shared_ptr<RmsNormType> final_norm_;
         std::shared_ptr<LmHeadLinearType> lm_head_;
         std::unique_ptr<TensorType> hidden_[ 3 ], pf_x_[ 2 ], f_qkv_, f_q_, f_o_, f_down_, f_act_;

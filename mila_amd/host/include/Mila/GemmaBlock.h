@@ -619,8 +619,6 @@ namespace Mila::Dnn
         /// batched decode of independent sequences (bf16 caches only): `rows` caches behind the attention op, the one its B = 1 calls work on, and all of them
         virtual void setCacheRows( int rows ) = 0;
         virtual void selectCacheRow( int b ) = 0;
-        /// cache row `src`'s positions [0, len) into the cache rows of dst_mask (RocmGqaOp::forkCacheRows)
-        virtual void forkCacheRows( int src, unsigned dst_mask, dim_t len ) = 0;
         virtual uint16_t* keyCacheRows() = 0;
         virtual uint16_t* valueCacheRows() = 0;
 
@@ -776,11 +774,6 @@ namespace Mila::Dnn
         {
             if constexpr ( kKvFp8 ) { if ( b != 0 ) throw std::logic_error( this->getName() + ": the FP8 KV cache has one row" ); }
             else attn->getOperation().selectCacheRow( b );
-        }
-        void forkCacheRows( int src, unsigned dst_mask, dim_t len ) override
-        {
-            if constexpr ( kKvFp8 ) throw std::logic_error( this->getName() + ": the FP8 KV cache has one row" );
-            else attn->getOperation().forkCacheRows( src, dst_mask, len );
         }
         uint16_t* keyCacheRows() override { if constexpr ( kKvFp8 ) return nullptr; else return attn->getOperation().keyCacheRows(); }
         uint16_t* valueCacheRows() override { if constexpr ( kKvFp8 ) return nullptr; else return attn->getOperation().valueCacheRows(); }

@@ -25,6 +25,7 @@
 #include <variant>
 
 #include "Gemma.h"
+#include "PrefixCache.h"
 #include "RequestQueue.h"
 #include "TokenAutomaton.h"
 #include "TokenBias.h"
@@ -443,6 +444,7 @@ namespace Mila::Dnn
         {
             return std::visit( [&]( auto& net )
             {
+                prefix_cache_.clear();      // (row 0's caches are written: the rows' claims end here)
                 try { return onGenerating( *net, prompt_tokens, on_token, params, stop ); }
                 catch ( const std::invalid_argument& ) { throw; }      // the request checks: nothing was enqueued, the caches are untouched
                 catch ( ... )
@@ -467,6 +469,7 @@ namespace Mila::Dnn
         {
             return std::visit( [&]( auto& net )
             {
+                prefix_cache_.clear();
                 try { return onScoring( *net, tokens, params ); }
                 catch ( const std::invalid_argument& ) { throw; }
                 catch ( ... )
@@ -491,6 +494,7 @@ namespace Mila::Dnn
             return std::visit( [&]( auto& net )
             {
                 kv_token_history_.clear();      // row 0's caches are overwritten; whatever happens below, nothing is left to reuse
+                prefix_cache_.clear();
                 last_reuse_ = 0;
                 try { return onGeneratingBatch( *net, prompts, on_token, params, seed ); }
                 catch ( const std::invalid_argument& ) { throw; }
@@ -513,6 +517,7 @@ namespace Mila::Dnn
         {
             return std::visit( [&]( auto& net )
             {
+                prefix_cache_.clear();
                 try
                 {
                     auto status = onGeneratingRequests( *net, requests, on_token, final_states );
@@ -534,6 +539,18 @@ namespace Mila::Dnn
             double setters_ms = 0.0, prefill_ms = 0.0, fork_ms = 0.0, first_sample_ms = 0.0;
             std::vector<int> row;
             std::vector<int64_t> admitted_at;
+            // with ServeParams::prefix_cache (otherwise empty / zero).  Per request: the prompt positions it did not prefill and the row they came from (-1: none, its
+            // own row: in place; a request forked whole by the identical-prompt rule: its whole prompt and that row).  Totals: the forkRowPrefix calls and the
+            // admissions that reused their own row in place.  prefill_tokens counts the tokens actually prefilled
+            std::vector<int64_t> reused_tokens;
+            std::vector<int> donor_row;
+            int64_t prefix_forks = 0, prefix_in_place = 0;
+        };
+        /// serveRequests' options.  prefix_cache: reuse cached KV prefixes across requests and calls (below); min_prefix: the shortest prefix worth reusing (>= 1)
+        struct ServeParams
+        {
+            bool prefix_cache = false;
+            int min_prefix = 1;
         };
         /// generateRequests for ANY number of requests (>= 1) on a withMaxBatch( R > 1 ) model: a queue in front of the rows step.  Requests are admitted in FIFO
         /// order, each into the lowest free row (Mila/RequestQueue.h holds the rule): the first min( n, R ) at the start, and after every step's readback each retired
@@ -547,8 +564,26 @@ namespace Mila::Dnn
         /// in, whenever it was admitted, prefilled or forked (same limit: the unwindowed layers' live-length bucket follows the longest live row).
         /// on_token( request, token ) / on_finish( request, status ) (once per request) / on_logprobs report the REQUEST's number.  logprobs: one n for the call.
         /// Every request is checked before anything is enqueued, with its number in the message.  Not here: requests arriving during the call, cancellation,
-        /// priorities, prefixes shorter than a whole prompt, decode-ahead.
+        /// priorities, decode-ahead; prefixes shorter than a whole prompt are the ServeParams overload below.
         [[nodiscard]] std::vector<GenerateStatus> serveRequests( std::span<const BatchRequest> requests, const std::function<void( int, int32_t )>& on_token,
+                                                                 const std::function<void( int, GenerateStatus )>& on_finish = {},
+                                                                 std::vector<std::optional<int32_t>>* final_states = nullptr, ServeStats* stats = nullptr )
+        {
+            return serveRequests( requests, on_token, ServeParams{}, on_finish, final_states, stats );
+        }
+        /// serveRequests with options.  ServeParams{} is the call above, launch for launch.  prefix_cache = true: THE PREFIX CACHE (Mila/PrefixCache.h holds the rule).
+        /// Every row has a claim -- the tokens whose KV its caches hold at [0, n) -- that outlives its request: a retired row keeps it until the row is written.  The
+        /// cache work of a round runs admission by admission, in the queue's order: the identical-prompt rule first and unchanged (forkRow, logits and all, no
+        /// prefill); otherwise plan() finds the longest prefix L <= len - 1 of the prompt that any row holds -- live, retired, or the request's own row -- and the
+        /// admission is forkRowPrefix( donor, row, L ) (none when the donor is the own row: in place), then prefillRow( row, prompt[ L: ], len - L, L ), whose chunks
+        /// are the ones generate() cuts from its reuse.  After every step each live row's claim grows by the token it was fed.  The claims live in the model: a later
+        /// serveRequests( prefix_cache ) reuses them; generate, generateBatch, generateRequests, score and a serveRequests without the flag clear them on entry, and so
+        /// does any exception out of a serving call (clearPrefixCache(): by hand).
+        /// THE CONTRACT: request i, admitted with reuse L from a chain of donors, gives what generate() gives for it on a one-sequence model on which the requests of
+        /// that chain ran before it, in order, generate() itself reusing L positions -- a prefilled suffix takes another GEMM form than a whole prompt (fp8 weights:
+        /// other bits), so the reuse path is the oracle, not a cold prefill.  min_prefix < 1 is refused before anything is enqueued.  Not here: copying only a
+        /// windowed layer's live band, choosing the free row by best match, eviction beyond "a written row loses its claim".
+        [[nodiscard]] std::vector<GenerateStatus> serveRequests( std::span<const BatchRequest> requests, const std::function<void( int, int32_t )>& on_token, const ServeParams& serve,
                                                                  const std::function<void( int, GenerateStatus )>& on_finish = {},
                                                                  std::vector<std::optional<int32_t>>* final_states = nullptr, ServeStats* stats = nullptr )
         {
@@ -556,26 +591,38 @@ namespace Mila::Dnn
             {
                 try
                 {
-                    auto status = onServingRequests( *net, requests, on_token, on_finish, final_states, stats );
+                    auto status = onServingRequests( *net, requests, on_token, serve, on_finish, final_states, stats );
                     net->clearRowsRequests();
                     return status;
                 }
-                catch ( const std::invalid_argument& ) { net->clearRowsRequests(); throw; }
-                catch ( ... ) { try { net->context()->synchronize(); } catch ( ... ) {} net->clearRowsRequests(); kv_token_history_.clear(); throw; }
+                catch ( const std::invalid_argument& ) { net->clearRowsRequests(); prefix_cache_.clear(); throw; }
+                catch ( ... ) { try { net->context()->synchronize(); } catch ( ... ) {} net->clearRowsRequests(); kv_token_history_.clear(); prefix_cache_.clear(); throw; }
             }, network_ );
+        }
+        /// forget what the rows hold: the next serveRequests( prefix_cache ) prefills every prompt whole
+        void clearPrefixCache() noexcept { prefix_cache_.clear(); }
+        /// per row of the model: the number of cache positions the prefix cache knows the tokens of
+        std::vector<int64_t> prefixCacheLengths() const
+        {
+            const int R = std::visit( []( const auto& net ) { return static_cast<int>( net->maxBatch() ); }, network_ );
+            std::vector<int64_t> out;
+            for ( int r = 0; r < std::min( R, PrefixCache::kMaxRows ); ++r ) out.push_back( static_cast<int64_t>( prefix_cache_.claim( r ).size() ) );
+            return out;
         }
 
     private:
         template<typename TNet>
         std::vector<GenerateStatus> onServingRequests( TNet& net, std::span<const BatchRequest> requests, const std::function<void( int, int32_t )>& on_token,
-                                                       const std::function<void( int, GenerateStatus )>& on_finish, std::vector<std::optional<int32_t>>* final_states,
-                                                       ServeStats* stats )
+                                                       const ServeParams& serve, const std::function<void( int, GenerateStatus )>& on_finish,
+                                                       std::vector<std::optional<int32_t>>* final_states, ServeStats* stats )
         {
             Compute::TraceRange tr( "GemmaModel.serveRequests" );
             const size_t n = requests.size();
             const int R = static_cast<int>( net.maxBatch() );
             if ( R < 2 ) throw std::invalid_argument( "GemmaModel::serveRequests: the model was built for one sequence (GemmaModelConfig::withMaxBatch)" );
             if ( n < 1 ) throw std::invalid_argument( "GemmaModel::serveRequests: no request" );
+            if ( serve.min_prefix < 1 ) throw std::invalid_argument( "GemmaModel::serveRequests: min_prefix " + std::to_string( serve.min_prefix ) + " (>= 1)" );
+            const bool cached = serve.prefix_cache;
             std::vector<RowRequestPlan> plan;
             std::vector<typename TNet::SamplingParams> sp;
             std::vector<std::span<const int32_t>> prompts;
@@ -589,13 +636,17 @@ namespace Mila::Dnn
             // ---- nothing was enqueued so far
             kv_token_history_.clear();      // row 0's caches are overwritten: nothing is left to reuse
             last_reuse_ = 0;
+            if ( !cached ) prefix_cache_.clear();      // this call writes rows and keeps no account of it
             const std::optional<int> logprobs = requests[ 0 ].params.logprobs;
             auto* ctx = net.context();
             net.clearTokenAutomaton();
             net.clearRowsRequests();      // every row vacant until its first admission (setRowRequest)
+            // a row between requests: position 0 and inactive -- except that under the prefix cache a row keeps its position word until it is written (the word says
+            // how far its caches were written, which is what forkRowPrefix checks a donor against; an inactive row's position is read by nothing else)
+            auto vacate = [&]( int b ) { if ( cached ) net.setRowActive( b, false ); else net.resetRow( b ); };
             for ( int b = static_cast<int>( std::min<size_t>( n, static_cast<size_t>( R ) ) ); b < R; ++b )      // a row no request will enter at the start: as generateRequests leaves it
             {
-                net.resetRow( b );
+                vacate( b );
                 net.clearRowTokenAutomaton( b );
                 net.clearRowTokenBias( b );
             }
@@ -604,6 +655,8 @@ namespace Mila::Dnn
             ServeStats st;
             st.row.assign( n, -1 );
             st.admitted_at.assign( n, -1 );
+            if ( cached ) { st.reused_tokens.assign( n, 0 ); st.donor_row.assign( n, -1 ); }
+            std::vector<int32_t> last_token( static_cast<size_t>( R ), 0 );      // per row: its latest sample, which the next step feeds (the prefix cache's fed())
             TokenLogprobsRows lp;
             lp.top_n = logprobs.value_or( 0 );
             std::vector<GenerateStatus> status( n, GenerateStatus::Success );
@@ -646,7 +699,7 @@ namespace Mila::Dnn
                     {
                         const int b = a.row;
                         const size_t i = static_cast<size_t>( a.request );
-                        net.resetRow( b );
+                        vacate( b );
                         const GenerateParams& p = requests[ i ].params;
                         // the automaton first: a row with one keeps its bias in the table the automaton composes from
                         if ( p.automaton ) net.setRowTokenAutomaton( b, *p.automaton ); else net.clearRowTokenAutomaton( b );
@@ -682,6 +735,49 @@ namespace Mila::Dnn
                     {
                         const auto& prompt = requests[ static_cast<size_t>( a.request ) ].prompt;
                         const dim_t len = static_cast<dim_t>( prompt.size() );
+                        if ( cached )      // one admission after the other: each sees the claims as the ones before it left them (Mila/PrefixCache.h)
+                        {
+                            const size_t i = static_cast<size_t>( a.request );
+                            const std::span<const int32_t> whole( prompt );
+                            if ( a.fork_from >= 0 )      // the identical-prompt rule, unchanged: a whole fork, logits and position included
+                            {
+                                const auto f0 = Clock::now();
+                                prefix_cache_.beginWrite( a.row, 0 );
+                                net.forkRow( a.fork_from, 1u << a.row, len );
+                                ctx->synchronize();
+                                prefix_cache_.extend( a.row, whole );
+                                st.fork_ms += since( f0 );
+                                ++st.forks;
+                                st.reused_tokens[ i ] = len;
+                                st.donor_row[ i ] = a.fork_from;
+                                continue;
+                            }
+                            const PrefixCache::Plan pl = prefix_cache_.plan( a.row, whole, serve.min_prefix );
+                            const dim_t L = static_cast<dim_t>( pl.reuse );
+                            prefix_cache_.beginWrite( a.row, pl.donor == a.row ? static_cast<size_t>( L ) : 0 );      // before anything writes the row
+                            if ( L > 0 && pl.donor != a.row )
+                            {
+                                const auto f0 = Clock::now();
+                                net.forkRowPrefix( pl.donor, 1u << a.row, L );
+                                ctx->synchronize();
+                                prefix_cache_.extend( a.row, whole.first( static_cast<size_t>( L ) ) );
+                                st.fork_ms += since( f0 );
+                                ++st.prefix_forks;
+                            }
+                            else if ( L > 0 ) ++st.prefix_in_place;
+                            const auto p0 = Clock::now();
+                            TokenTensor toks( ctx->getDeviceId(), shape_t{ 1, len - L } );
+                            Compute::rocmCheck( mila_cdna4_memcpy_h2d( toks.rawData(), prompt.data() + L, static_cast<size_t>( len - L ) * 4, ctx->getStream() ) );
+                            net.prefillRow( a.row, toks, len - L, L );      // chunks of the prefill size from L on, as generate() cuts them from its reuse
+                            ctx->synchronize();
+                            prefix_cache_.extend( a.row, whole.subspan( static_cast<size_t>( L ) ) );
+                            st.prefill_ms += since( p0 );
+                            ++st.prefills;
+                            st.prefill_tokens += len - L;
+                            st.reused_tokens[ i ] = L;
+                            st.donor_row[ i ] = pl.donor;
+                            continue;
+                        }
                         if ( a.fork_from < 0 )
                         {
                             const auto p0 = Clock::now();
@@ -711,6 +807,7 @@ namespace Mila::Dnn
                         int32_t token = 0;
                         Compute::rocmCheck( mila_cdna4_memcpy_d2h( &token, net.rowsTokens().data() + b, 4, ctx->getStream() ) );
                         ctx->synchronize();
+                        last_token[ static_cast<size_t>( b ) ] = token;
                         net.setRowActive( b, true );
                         (void)deliver( b, token );      // a request that ends here frees its row for the next wave of this round
                     }
@@ -742,7 +839,17 @@ namespace Mila::Dnn
                 ctx->synchronize();
                 if ( logprobs ) lp.read( net.tokenLogprobs(), B );
                 for ( int b = 0; b < B; ++b )
-                    if ( queue.requestOf( b ) >= 0 ) (void)deliver( b, tokens[ static_cast<size_t>( b ) ] );
+                {
+                    if ( queue.requestOf( b ) < 0 ) continue;
+                    if ( cached )      // the step wrote the KV of the token it was fed -- the sample before this one -- at the row's position
+                    {
+                        if ( static_cast<dim_t>( prefix_cache_.claim( b ).size() ) + 1 != position[ static_cast<size_t>( b ) ] )
+                            throw std::logic_error( "GemmaModel::serveRequests: row " + std::to_string( b ) + "'s claim and position disagree" );
+                        prefix_cache_.fed( b, last_token[ static_cast<size_t>( b ) ] );
+                    }
+                    last_token[ static_cast<size_t>( b ) ] = tokens[ static_cast<size_t>( b ) ];
+                    (void)deliver( b, tokens[ static_cast<size_t>( b ) ] );
+                }
                 admitRound();      // each retired row to the next waiting request, before the next replay
             }
             ctx->synchronize();
@@ -1466,6 +1573,7 @@ namespace Mila::Dnn
         std::unique_ptr<TokenTensor> prompt_dev_, decode_token_device_, seq_dev_;
         std::unique_ptr<TokenTensor> score_targets_dev_;      // the targets of a scored chunk, from the first score() on
         std::vector<int32_t> kv_token_history_;
+        PrefixCache prefix_cache_;      // what the rows of a max_batch > 1 model hold (serveRequests with ServeParams::prefix_cache)
         dim_t last_reuse_{ 0 };
         std::mt19937_64 rng_{ 0x4d494c41ull };
         unsigned long long* ring_host_{ nullptr };      // pinned + mapped: the device writes, the host polls

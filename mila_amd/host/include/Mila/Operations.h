@@ -880,15 +880,6 @@ namespace Mila::Dnn::Compute
             if ( b < 0 || b >= rows_ ) throw std::invalid_argument( "RocmGqaOp::selectCacheRow: row " + std::to_string( b ) + " outside the " + std::to_string( rows_ ) + " cache rows" );
             row_ = b;
         }
-        /// positions [0, len) of cache row `src` into every cache row of dst_mask (bit r = row r), K and V, every head: one launch (mila_cdna4.h: kv_rows_fork_bf16).
-        /// The rows' caches are unbounded, so the prefix of a prompt prefilled at offset 0 is exactly that range.
-        void forkCacheRows( int src, unsigned dst_mask, dim_t len )
-        {
-            requireCache();
-            if ( rows_ < 2 ) throw std::logic_error( "RocmGqaOp::forkCacheRows: the op has one cache row (setCacheRows)" );
-            rocmCheck( mila_cdna4_kv_rows_fork_bf16( k_cache_->data(), v_cache_->data(), rows_, (int)cfg_.num_kv_heads, (int)capacity_, (int)cfg_.head_dim, src, dst_mask,
-                                                     (int)len, context_->getStream() ) );
-        }
         int cacheRows() const noexcept { return rows_; }
         uint16_t* keyCacheRows() noexcept { return k_cache_ ? k_cache_->data() : nullptr; }
         uint16_t* valueCacheRows() noexcept { return v_cache_ ? v_cache_->data() : nullptr; }

@@ -12,6 +12,8 @@
 //     gone, and one re-prefilled position takes another GEMM form), and neither is a row whose request has retired (the loop may hand it on);
 //   * after a step's readback the loop calls retire( row ) for every row that ended, then the next round.
 // Prompt identity is a class number per request: equal numbers = the same length and the same ids (promptClasses builds them).
+// A prefix shorter than a whole prompt, a source row that has stepped or retired, and reuse across rounds and calls are not this rule's: they are the prefix cache
+// (Mila/PrefixCache.h), which serveRequests applies, when asked to, to every admission this rule leaves with fork_from < 0.  Row choice and the rule above do not change.
 #include <algorithm>
 #include <cstdint>
 #include <map>

@@ -679,6 +679,19 @@ HOST_API int mila_gemma_reset_row( void* h, int b )
 {
     return guarded( [&] { std::visit( [&]( auto& m ) { m->resetRow( b ); }, static_cast<Runner*>( h )->model ); } );
 }
+/// GemmaTransformer::forkRow (whole != 0: caches [0, len), logits and position, directly behind row src's prefill of len tokens) or forkRowPrefix (caches only, from
+/// any row at a position >= len)
+HOST_API int mila_gemma_fork_row( void* h, int src, unsigned dst_mask, int64_t len, int whole )
+{
+    return guarded( [&]
+    {
+        std::visit( [&]( auto& m )
+        {
+            if ( whole ) m->forkRow( src, dst_mask, len ); else m->forkRowPrefix( src, dst_mask, len );
+            m->context()->synchronize();
+        }, static_cast<Runner*>( h )->model );
+    } );
+}
 /// one step over rows 0 .. B - 1.  mode 1: eager launches, 2: graph replay (captured on first use and when B, the sampler tail or the live-length bucket change).
 /// greedy != 0: the step ends with the rows sampler tail (next token + position bump of every active row); 0: it ends at the logits, positions bumped.
 /// max_position: the largest position among the active rows.  Outputs (each may be NULL): logits [B, vocab], tokens [B], positions [B] AFTER the step.
@@ -2168,9 +2181,10 @@ HOST_API int mila_gemma_model_generate_requests( void* h, const mila_gemma_row_r
 /// out_admitted_at [n] the rows steps replayed before its admission, out_finish_order [n] the position of its on_finish among the call's, and out_stats [5] =
 /// {rows steps, prefills, prefill tokens, forks, rows-graph captures during the call}, out_times [4] = the host milliseconds the call's admissions spent in
 /// {the rows' setters, prefills, forks, first samples}
-HOST_API int mila_gemma_model_serve_requests( void* h, const mila_gemma_row_request* requests, int n, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status,
-                                              float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts, int32_t* out_states, int32_t* out_has_state,
-                                              int32_t* out_rows, int64_t* out_admitted_at, int32_t* out_finish_order, int64_t* out_stats, double* out_times )
+static int serve_requests( void* h, const mila_gemma_row_request* requests, int n, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status,
+                           float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts, int32_t* out_states, int32_t* out_has_state,
+                           int32_t* out_rows, int64_t* out_admitted_at, int32_t* out_finish_order, int64_t* out_stats, double* out_times,
+                           const RocmGemmaModel::ServeParams& serve, int64_t* out_reused, int32_t* out_donor, int64_t* out_prefix_stats )
 {
     return guarded( [&]
     {
@@ -2186,7 +2200,7 @@ HOST_API int mila_gemma_model_serve_requests( void* h, const mila_gemma_row_requ
         std::vector<std::optional<int32_t>> states;
         RocmGemmaModel::ServeStats stats;
         const auto st = m->serveRequests( rq, [&]( int q, int32_t t ) { int64_t& c = counts[ static_cast<size_t>( q ) ]; if ( out_tokens && c < cap ) out_tokens[ q * cap + c ] = t; ++c; },
-                                          [&]( int q, GenerateStatus )
+                                          serve, [&]( int q, GenerateStatus )
                                           {
                                               if ( finished.at( static_cast<size_t>( q ) ) >= 0 ) throw std::logic_error( "gemma_model_serve_requests: a request finished twice" );
                                               finished[ static_cast<size_t>( q ) ] = finishes++;
@@ -2201,9 +2215,56 @@ HOST_API int mila_gemma_model_serve_requests( void* h, const mila_gemma_row_requ
             if ( out_rows ) out_rows[ q ] = stats.row[ i ];
             if ( out_admitted_at ) out_admitted_at[ q ] = stats.admitted_at[ i ];
             if ( out_finish_order ) out_finish_order[ q ] = finished[ i ];
+            if ( out_reused ) out_reused[ q ] = serve.prefix_cache ? stats.reused_tokens[ i ] : 0;
+            if ( out_donor ) out_donor[ q ] = serve.prefix_cache ? stats.donor_row[ i ] : -1;
         }
+        if ( out_prefix_stats ) { out_prefix_stats[ 0 ] = stats.prefix_forks; out_prefix_stats[ 1 ] = stats.prefix_in_place; }
         if ( out_stats ) { out_stats[ 0 ] = stats.steps; out_stats[ 1 ] = stats.prefills; out_stats[ 2 ] = stats.prefill_tokens; out_stats[ 3 ] = stats.forks; out_stats[ 4 ] = stats.captures; }
         if ( out_times ) { out_times[ 0 ] = stats.setters_ms; out_times[ 1 ] = stats.prefill_ms; out_times[ 2 ] = stats.fork_ms; out_times[ 3 ] = stats.first_sample_ms; }
+    } );
+}
+HOST_API int mila_gemma_model_serve_requests( void* h, const mila_gemma_row_request* requests, int n, int32_t* out_tokens, int64_t cap, int64_t* out_counts, int32_t* out_status,
+                                              float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts, int32_t* out_states, int32_t* out_has_state,
+                                              int32_t* out_rows, int64_t* out_admitted_at, int32_t* out_finish_order, int64_t* out_stats, double* out_times )
+{
+    return serve_requests( h, requests, n, out_tokens, cap, out_counts, out_status, out_logprob, out_ids, out_logprobs, out_logprob_counts, out_states, out_has_state, out_rows,
+                           out_admitted_at, out_finish_order, out_stats, out_times, RocmGemmaModel::ServeParams{}, nullptr, nullptr, nullptr );
+}
+/// mila_gemma_model_serve_requests with GemmaModel::ServeParams: prefix_cache != 0 turns the prefix cache on, min_prefix is its shortest reused prefix.  Beside the
+/// outputs above: out_reused [n] the prompt positions a request did not prefill, out_donor [n] the row they came from (-1: none), out_prefix_stats [2] =
+/// {forkRowPrefix calls, in-place reuses}
+HOST_API int mila_gemma_model_serve_requests_prefix( void* h, const mila_gemma_row_request* requests, int n, int32_t* out_tokens, int64_t cap, int64_t* out_counts,
+                                                     int32_t* out_status, float* out_logprob, int32_t* out_ids, float* out_logprobs, int64_t* out_logprob_counts,
+                                                     int32_t* out_states, int32_t* out_has_state, int32_t* out_rows, int64_t* out_admitted_at, int32_t* out_finish_order,
+                                                     int64_t* out_stats, double* out_times, int prefix_cache, int min_prefix, int64_t* out_reused, int32_t* out_donor,
+                                                     int64_t* out_prefix_stats )
+{
+    RocmGemmaModel::ServeParams serve;
+    serve.prefix_cache = prefix_cache != 0;
+    serve.min_prefix = min_prefix;
+    return serve_requests( h, requests, n, out_tokens, cap, out_counts, out_status, out_logprob, out_ids, out_logprobs, out_logprob_counts, out_states, out_has_state, out_rows,
+                           out_admitted_at, out_finish_order, out_stats, out_times, serve, out_reused, out_donor, out_prefix_stats );
+}
+/// GemmaModel::clearPrefixCache
+HOST_API int mila_gemma_model_clear_prefix_cache( void* h )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m ) throw std::invalid_argument( "gemma_model_clear_prefix_cache: null argument" );
+        m->clearPrefixCache();
+    } );
+}
+/// GemmaModel::prefixCacheLengths: out [4], one length per row of the model; *out_rows = the rows
+HOST_API int mila_gemma_model_prefix_cache_lengths( void* h, int64_t* out, int32_t* out_rows )
+{
+    return guarded( [&]
+    {
+        auto* m = static_cast<RocmGemmaModel*>( h );
+        if ( !m || !out || !out_rows ) throw std::invalid_argument( "gemma_model_prefix_cache_lengths: null argument" );
+        const auto lengths = m->prefixCacheLengths();
+        *out_rows = static_cast<int32_t>( lengths.size() );
+        for ( size_t r = 0; r < lengths.size() && r < 4; ++r ) out[ r ] = lengths[ r ];
     } );
 }
 
