@@ -333,7 +333,8 @@ template <int FMT, int U, int PRO, bool GEGLU, bool F32OUT, int XC, int NB>
 static int launch_rows_t(const MatvecRowsArgs& a, const MatvecRowsPlan& pl, hipStream_t s)
 {
     auto kernel = matvec_rows_kernel<FMT, U, PRO, GEGLU, F32OUT, XC, NB>;
-    // more than the 64 KiB a kernel gets by default (as attention_prefill.hip does for its LDS-DMA forms): once per instantiation and device
+    // more than the 64 KiB a kernel gets by default (as attention_prefill.hip does for its LDS-DMA forms): once per instantiation and device.  The 160 KiB hold the
+    // kernel's own reduction arrays as well (every form but the plain bf16 one keeps them): asking for all of it as dynamic LDS is refused with an invalid-value error
     static thread_local int raised_for = -1;
     int dev = 0;
     if (pl.lds > 65536)
@@ -342,7 +343,8 @@ static int launch_rows_t(const MatvecRowsArgs& a, const MatvecRowsPlan& pl, hipS
         if (rc) return rc;
         if (raised_for != dev)
         {
-            rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatvecRowsLdsLimit), "matvec_rows");
+            rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMatvecRowsLdsLimit - pl.lds_static)),
+                           "matvec_rows");
             if (rc) return rc;
             raised_for = dev;
         }
