@@ -334,6 +334,32 @@ MILA_API int mila_cdna4_fused_qkv_post_kvfp8_devpos(uint16_t* q_out, uint8_t* K8
                                                     const float* sin_cache, int NH, int NKV, int HS, const int32_t* position_dev, int capacity, float eps,
                                                     mila_stream_t stream);
 
+/* The FP8 KV cache under a rows step (ABI 4, additive): B INDEPENDENT sequences (2 <= B <= 4), row b at positions_dev[b] (device memory, always: these are graph-replay
+ * forms) on its own caches K8 / V8 + b * NKV * capacity * HS bytes and Ks / Vs + b * NKV * capacity floats -- the [B, NKV, capacity(, HS)] layout above, one sequence per
+ * batch index.  The two launches a rows step makes per layer where the bf16 cache has fused_attn_decode_rows_bf16.
+ *   fused_qkv_post_kvfp8_rows_devpos: fused_qkv_post_kvfp8_devpos for the B rows (csrc/fused.hip: the qkv_post_body<true> instantiation whose grid y is the row).  Row b
+ *     reads q / k / v_src at + b * raw_b_stride elements (a multiple of 8), takes its position from positions_dev[b] (NOT *positions_dev + b), writes q_out +
+ *     b * NH * HS and appends into its own caches at cache row positions_dev[b] % capacity; every offset is 64-bit.  Row b's q_out, bytes and scales are bit-identical
+ *     to fused_qkv_post_kvfp8_devpos on that row's slices with *position_dev = positions_dev[b]; no other cache row is written.  Refused before any device work: a null
+ *     pointer (vw may be null: ones), B outside 2 .. 4, HS outside {64, 128, 256, 512}, a stride that is no multiple of 8, a non-positive capacity.
+ *   attn_decode_kvfp8_rows: attn_decode_kvfp8_devpos for the B rows (csrc/attention_kvfp8.hip: the ROWS instantiations of both kernel forms).  Row b attends over
+ *     positions_dev[b] + 1 keys of its own caches.  max_len is the live-length bound the launch is captured for; the caller passes the bound of its LONGEST row.  The
+ *     splits are planned for ONE row at that bound (attn_decode_kvfp8_plan_describe(1, ...) describes the plan) and used for every row, so row b's Y is bit-identical
+ *     to attn_decode_kvfp8_devpos with B = 1 on that row's slices at positions_dev[b] with the same max_len, whatever the other rows hold; a row whose band is shorter
+ *     leaves (m = -inf, l = 0) partials in its idle splits.  THE ONE LIMIT of that invariance: on an unwindowed layer the plan follows the live-length bucket of max_len
+ *     (attn_decode_band_bucket), so a row that would sit ALONE in a lower bucket than the batch's longest row is reduced over the higher bucket's splits here -- equal
+ *     to the alone run captured for that bound, not to one captured for the row's own lower bucket.  Scratch from attn_decode_scratch_bytes(B, NH, HS).
+ * Neither entry can see the device values.  A positions_dev[b] outside [0, max_len) -- max_len at most the capacity and the length of the RoPE tables -- makes the
+ * append read the tables out of bounds and the attention run over cache rows the sequence never wrote: keeping every row inside is the CALLER's invariant
+ * (GemmaTransformer: checkRowsStep, checkPosition), as it is for the bf16 rows entry; there is no device-side check. */
+MILA_API int mila_cdna4_fused_qkv_post_kvfp8_rows_devpos(uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k,
+                                                         const uint16_t* v_src, int64_t raw_b_stride, const uint16_t* qw, const uint16_t* kw, const uint16_t* vw,
+                                                         const float* cos_cache, const float* sin_cache, int B, int NH, int NKV, int HS, const int32_t* positions_dev,
+                                                         int capacity, float eps, mila_stream_t stream);
+MILA_API int mila_cdna4_attn_decode_kvfp8_rows(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch,
+                                               size_t scratch_bytes, int B, int NH, int NKV, int HS, int capacity, const int32_t* positions_dev, int max_len, int window,
+                                               float scale, mila_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Normalisation / activations.
  * rmsnorm: y = x * rsqrt(mean(x^2) + eps) * (w + w_offset) + b over `dim` strided by `inner`;
@@ -1101,6 +1127,23 @@ typedef struct mila_kv_fork_layer {
     int32_t reserved;       /* 0 */
 } mila_kv_fork_layer;
 MILA_API int mila_cdna4_kv_rows_fork_layers_bf16(const mila_kv_fork_layer* layers, int n_layers, int rows, int src, unsigned dst_mask, int len, mila_stream_t stream);
+
+/* kv_rows_fork_layers_bf16 for the FP8 KV cache (ABI 4, additive; csrc/kv_rows_fork.hip): layer i keeps K8 / V8 [rows, NKV, capacity, HS] e4m3 bytes and Ks / Vs
+ * [rows, NKV, capacity] fp32 scales.  Per layer and KV head, positions [0, len) of cache row `src` are copied into every row of dst_mask: the bytes as 16-byte units (HS a
+ * multiple of 16), the scales as 4-byte WORDS -- a head's scale run starts capacity * 4 bytes after the one before it and is len * 4 bytes long, neither 16-byte aligned in
+ * general, so that copy is never widened.  Bitwise: a NaN, a -0.0 or a denormal scale passes as it is.  Nothing is written outside [0, len) of the named rows, nothing in
+ * `src`.  The interface is otherwise the bf16 entry's: a HOST array passed by value in the kernel arguments, the layer in the grid's y index, up to 64 layers per launch.
+ * Refused before any device work, with the layer's number in the message where one is at fault: the bf16 entry's refusals; K8 / V8 not 16-byte aligned, Ks / Vs not
+ * 4-byte aligned; HS no multiple of 16; len above a layer's capacity. */
+typedef struct mila_kv_fork_layer_fp8 {
+    uint8_t* K8;            /* device: [rows, NKV, capacity, HS] e4m3, 16-byte aligned */
+    uint8_t* V8;
+    float* Ks;              /* device: [rows, NKV, capacity] fp32 */
+    float* Vs;
+    int32_t NKV, capacity, HS;
+    int32_t reserved;       /* 0 */
+} mila_kv_fork_layer_fp8;
+MILA_API int mila_cdna4_kv_rows_fork_layers_kvfp8(const mila_kv_fork_layer_fp8* layers, int n_layers, int rows, int src, unsigned dst_mask, int len, mila_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,12 @@ class KvForkLayer(C.Structure):
     _fields_ = [("K", C.c_void_p), ("V", C.c_void_p), ("NKV", C.c_int32), ("capacity", C.c_int32), ("HS", C.c_int32), ("reserved", C.c_int32)]
 
 
+class KvForkLayerFp8(C.Structure):
+    """mila_kv_fork_layer_fp8: one layer's record for kv_rows_fork_layers_kvfp8 (K8 / V8 bytes and Ks / Vs scales: device addresses)"""
+    _fields_ = [("K8", C.c_void_p), ("V8", C.c_void_p), ("Ks", C.c_void_p), ("Vs", C.c_void_p), ("NKV", C.c_int32), ("capacity", C.c_int32), ("HS", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 _lib = None
 EXPERIMENTS_PATH = os.path.join(_HERE, "lib", "libmila_cdna4_experiments.so")
 
@@ -162,6 +168,7 @@ def load():
     # a shared prefill's device primitive (csrc/kv_rows_fork.hip)
     main.mila_cdna4_kv_rows_fork_bf16.argtypes = [p, p, i, i, i, i, i, i, i, p]                                   # K V | rows NKV capacity HS | src dst_mask len
     main.mila_cdna4_kv_rows_fork_layers_bf16.argtypes = [p, i, i, i, i, i, p]                                     # layers (host records) n_layers | rows src dst_mask len
+    main.mila_cdna4_kv_rows_fork_layers_kvfp8.argtypes = [p, i, i, i, i, i, p]                                    # layers (host fp8 records) n_layers | rows src dst_mask len
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -179,6 +186,9 @@ def load():
     main.mila_cdna4_fused_qkv_post_kvfp8.argtypes = [p] * 13 + [i, i, i, i, i, f, p]                              # q_out K8 V8 Ks Vs q k v_src qw kw vw cos sin | NH NKV HS position capacity | eps
     main.mila_cdna4_fused_qkv_post_kvfp8_prefill.argtypes = [p] * 8 + [i64] + [p] * 5 + [i, i, i, i, i, i, f, p]  # q_out K8 V8 Ks Vs q k v_src | stride | qw kw vw cos sin | T NH NKV HS pos_offset capacity | eps
     main.mila_cdna4_fused_qkv_post_kvfp8_devpos.argtypes = [p] * 13 + [i, i, i, p, i, f, p]                       # ... | NH NKV HS | position_dev | capacity | eps
+    # the FP8 KV cache under a rows step: row b at positions_dev[b] on its own caches
+    main.mila_cdna4_fused_qkv_post_kvfp8_rows_devpos.argtypes = [p] * 8 + [i64] + [p] * 5 + [i, i, i, i, p, i, f, p]   # q_out K8 V8 Ks Vs q k v_src | stride | qw kw vw cos sin | B NH NKV HS | positions_dev | capacity | eps
+    main.mila_cdna4_attn_decode_kvfp8_rows.argtypes = [p, p, p, p, p, p, p, z, i, i, i, i, i, p, i, i, f, p]      # Y Q K8 V8 Ks Vs scratch bytes | B NH NKV HS capacity | positions_dev | max_len window | scale
     _lib = _Libs(main)
     return _lib
 
@@ -826,6 +836,7 @@ EXPORTED = [
     "sample_argmax_requests_rows_fp32", "sample_argmax_requests_rows_advance_fp32",
     "token_automaton_rows_bytes", "token_automaton_rows_set", "token_automaton_rows_compose", "token_automaton_rows_step",
     "kv_rows_fork_bf16", "kv_rows_fork_layers_bf16",
+    "fused_qkv_post_kvfp8_rows_devpos", "attn_decode_kvfp8_rows", "kv_rows_fork_layers_kvfp8",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

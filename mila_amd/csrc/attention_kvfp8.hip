@@ -138,7 +138,9 @@ __device__ __forceinline__ KvFp8DecodeParams kvfp8_params(MILA_KVFP8_LEAD_PARAMS
     return p;
 }
 
-template <int HS, int GH>
+// ROWS (attn_decode_kvfp8_rows): the batch rows are independent sequences -- row b = blockIdx.z attends over pos_dev[b] + 1 keys of its own caches; everything else
+// (the band, the splits, the partial layout) is the one-row kernel's, so a row has the bits it has alone.
+template <int HS, int GH, bool ROWS = false>
 __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kvfp8_kernel(MILA_KVFP8_LEAD_PARAMS, const KvFp8DecodeParams tail)
 {
     const KvFp8DecodeParams p = kvfp8_params(pos_dev, K8, V8, Ks, NH, NKV, capacity, window, splits, tail);
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kvfp8_kernel(MI
     const int kvh = grp / hgroups, hg = grp % hgroups;
     const int h0 = kvh * GS + hg * GH;                     // first query head of this workgroup
     const int b = blockIdx.z;
-    const int len = p.pos_dev ? *p.pos_dev + 1 : p.len;
+    const int len = ROWS ? p.pos_dev[b] + 1 : (p.pos_dev ? *p.pos_dev + 1 : p.len);
     const int band_begin = (p.window > 0) ? max(0, len - p.window) : 0;
     const int band = len - band_begin;
     const int chunk = (band + p.splits - 1) / p.splits;
@@ -274,27 +276,28 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void attn_decode_kvfp8_kernel(MI
     decode_finish<HS, GH, Row>(a, m, l, o, sm);
 }
 
-template <int HS, int GH>
+template <int HS, int GH, bool ROWS = false>
 static int launch_decode_kvfp8(const KvFp8DecodeParams& p, int B, int hgroups, hipStream_t s)
 {
     note_form("attn_decode_kvfp8");
     const size_t lds = (size_t)kDecodeWaves * GH * (HS + 2) * sizeof(float);      // <= 33 KB (HS 256 x 4 heads, HS 512 x 2)
-    hipLaunchKernelGGL((attn_decode_kvfp8_kernel<HS, GH>), dim3(p.splits, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, MILA_KVFP8_LEAD_ARGS(p), p);
+    hipLaunchKernelGGL((attn_decode_kvfp8_kernel<HS, GH, ROWS>), dim3(p.splits, p.NKV * hgroups, B), dim3(kDecodeWaves * 64), lds, s, MILA_KVFP8_LEAD_ARGS(p), p);
     int rc = check_hip(hipGetLastError(), "attn_decode_kvfp8");
     if (rc || p.splits <= 1) return rc;
     return launch_attn_combine(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
 }
 
 // ---- the matrix-core decode (attention_decode_mfma.h): grid (splits, NKV * GS / 16, B), 256 threads ----
-template <int HS>
+template <int HS, bool ROWS = false>
 __global__ __launch_bounds__(256) void attn_decode_kvfp8_mfma_kernel(MILA_KVFP8_LEAD_PARAMS, const KvFp8DecodeParams tail)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_kvfp8_mfma[];
     const KvFp8DecodeParams p = kvfp8_params(pos_dev, K8, V8, Ks, NH, NKV, capacity, window, splits, tail);
-    const int len = p.pos_dev ? *p.pos_dev + 1 : p.len;
+    const int len = ROWS ? p.pos_dev[blockIdx.z] + 1 : (p.pos_dev ? *p.pos_dev + 1 : p.len);      // ROWS: row b = blockIdx.z of independent sequences, as above
     const MfmaDecodeArgs a{p.Q, 0, p.scratch, p.NH, p.NKV, p.capacity, len, p.window, p.splits, p.scale};
     attn_decode_mfma_body<HS>(a, MfmaStageKvFp8<HS>{p.K8, p.V8, p.Ks, p.Vs}, smem_kvfp8_mfma);
 }
+template <bool ROWS = false>
 static int launch_decode_kvfp8_mfma(const KvFp8DecodeParams& p, int B, hipStream_t s)
 {
     constexpr int HS = 512;
@@ -303,13 +306,13 @@ static int launch_decode_kvfp8_mfma(const KvFp8DecodeParams& p, int B, hipStream
     const size_t lds = mfma_decode_lds_bytes<HS>();      // what attn_decode_mfma_kernel asks for: the images are the same
     if (!attr_set)
     {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_kvfp8_mfma_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_kvfp8_mfma_kernel<HS, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
                            "hipFuncSetAttribute(attn_decode_kvfp8_mfma)");
         if (rc) return rc;
         attr_set = true;
     }
     const int n16 = (p.NH / p.NKV) / 16;
-    hipLaunchKernelGGL((attn_decode_kvfp8_mfma_kernel<HS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, MILA_KVFP8_LEAD_ARGS(p), p);
+    hipLaunchKernelGGL((attn_decode_kvfp8_mfma_kernel<HS, ROWS>), dim3(p.splits, p.NKV * n16, B), dim3(256), lds, s, MILA_KVFP8_LEAD_ARGS(p), p);
     int rc = check_hip(hipGetLastError(), "attn_decode_kvfp8_mfma");
     if (rc) return rc;
     return launch_attn_combine_many(p.Y, p.scratch, B, p.NH, HS, p.splits, s);
@@ -377,9 +380,10 @@ int mila_cdna4_kv_dequant_fp8_bf16(uint16_t* Kc_bf16, uint16_t* Vc_bf16, const u
 }
 
 // what the two decode entries share: the checks (`who` names the entry in the messages; `len` is the live length of the eager entry, the captured bound max_len of
-// the device-position one), the plan for that length's band bucket, the launch of the plan's form
+// the device-position one), the plan for that length's band bucket, the launch of the plan's form.  rows: pos_dev holds B words, row b's position at [b]; the plan
+// is ONE row's (as fused_attn_decode_rows_bf16 plans), only the partials are sized for all B
 static int kvfp8_decode(const char* who, uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
-                        int B, int NH, int NKV, int HS, int capacity, int len, const int32_t* pos_dev, int window, float scale, mila_stream_t stream)
+                        int B, int NH, int NKV, int HS, int capacity, int len, const int32_t* pos_dev, int window, float scale, mila_stream_t stream, bool rows = false)
 {
     MILA_REQUIRE(B > 0 && NH > 0 && NKV > 0 && NH % NKV == 0, "%s: bad head counts (NH=%d NKV=%d)", who, NH, NKV);
     MILA_REQUIRE(decode_scalar_head_size(HS), "%s: HS=%d must be 64, 128, 256 or 512", who, HS);
@@ -389,14 +393,18 @@ static int kvfp8_decode(const char* who, uint16_t* Y, const uint16_t* Q, const u
     MILA_REQUIRE(window >= 0, "%s: negative window", who);
     const int band = live_band(len, window);
     MILA_REQUIRE(band <= capacity, "%s: live band %d exceeds the cache capacity %d", who, band, capacity);
-    const KvFp8DecodeShape d = plan_decode_kvfp8(B, NH, NKV, HS, capacity, window, len);
+    KvFp8DecodeShape d = plan_decode_kvfp8(rows ? 1 : B, NH, NKV, HS, capacity, window, len);
+    if (rows) d.scratch_need *= (size_t)B;      // partials [B, NH, splits, HS + 4]: no q rows in this plan (an unfused entry)
     MILA_REQUIRE(!d.scratch_need || (scratch && scratch_bytes >= d.scratch_need), "%s: scratch %zu bytes < required %zu (ask attn_decode_scratch_bytes)", who, scratch_bytes,
                  d.scratch_need);
     KvFp8DecodeParams p{Y, Q, K8, V8, Ks, Vs, reinterpret_cast<float*>(scratch), NH, NKV, capacity, len, window, d.splits, scale, pos_dev};
     hipStream_t s = as_stream(stream);
-    if (d.mfma) return launch_decode_kvfp8_mfma(p, B, s);      // (HS 512 by the plan's rule)
+    if (d.mfma) return rows ? launch_decode_kvfp8_mfma<true>(p, B, s) : launch_decode_kvfp8_mfma<false>(p, B, s);      // (HS 512 by the plan's rule)
     // (<512, 4> runs only under the attn.heads_per_group_512 experiment, on the bf16 cache)
-    const int rc = dispatch_decode_scalar<false>(HS, d.gh, [&](auto hs, auto g) { return launch_decode_kvfp8<decltype(hs)::value, decltype(g)::value>(p, B, d.hgroups, s); });
+    const int rc = dispatch_decode_scalar<false>(HS, d.gh, [&](auto hs, auto g) {
+        return rows ? launch_decode_kvfp8<decltype(hs)::value, decltype(g)::value, true>(p, B, d.hgroups, s)
+                    : launch_decode_kvfp8<decltype(hs)::value, decltype(g)::value, false>(p, B, d.hgroups, s);
+    });
     if (rc == kNoDecodeKernel) return set_error(MILA_E_UNSUPPORTED, "attn_decode_kvfp8: no kernel for %d heads per workgroup at HS=%d", d.gh, HS);
     return rc;
 }
@@ -413,6 +421,17 @@ int mila_cdna4_attn_decode_kvfp8_devpos(uint16_t* Y, const uint16_t* Q, const ui
 {
     MILA_REQUIRE(Y && Q && K8 && V8 && Ks && Vs && position_dev, "attn_decode_kvfp8_devpos: null pointer");
     return kvfp8_decode("attn_decode_kvfp8_devpos", Y, Q, K8, V8, Ks, Vs, scratch, scratch_bytes, B, NH, NKV, HS, capacity, max_len, position_dev, window, scale, stream);
+}
+
+// attn_decode_kvfp8_devpos for B independent sequences (mila_cdna4.h).  The entry cannot see the device values: a positions_dev[b] outside [0, max_len) would read
+// out of bounds or take a plan it was not captured for -- the caller keeps that invariant (GemmaTransformer: checkRowsStep, checkPosition).
+int mila_cdna4_attn_decode_kvfp8_rows(uint16_t* Y, const uint16_t* Q, const uint8_t* K8, const uint8_t* V8, const float* Ks, const float* Vs, void* scratch, size_t scratch_bytes,
+                                      int B, int NH, int NKV, int HS, int capacity, const int32_t* positions_dev, int max_len, int window, float scale, mila_stream_t stream)
+{
+    MILA_REQUIRE(Y && Q && K8 && V8 && Ks && Vs && positions_dev, "attn_decode_kvfp8_rows: null pointer");
+    MILA_REQUIRE(B >= 2 && B <= 4, "attn_decode_kvfp8_rows: B=%d rows outside 2 .. 4", B);
+    MILA_REQUIRE(max_len <= capacity, "attn_decode_kvfp8_rows: max_len %d beyond the capacity %d (a row's cache is unbounded: position p lives at cache row p)", max_len, capacity);
+    return kvfp8_decode("attn_decode_kvfp8_rows", Y, Q, K8, V8, Ks, Vs, scratch, scratch_bytes, B, NH, NKV, HS, capacity, max_len, positions_dev, window, scale, stream, true);
 }
 
 size_t mila_cdna4_attn_prefill_kvfp8_scratch_bytes(int B, int NKV, int HS, int capacity)

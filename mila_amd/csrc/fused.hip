@@ -96,9 +96,12 @@ __device__ __forceinline__ float group_tree_max(float v, int hv)
 // computes for a row of 2 hv chunks (its remaining steps add zeros), so the bits match the standalone RMSNorm kernel.
 // kQuant: the K / V rows, rounded to bf16 as the bf16 cache would hold them, are quantized the way kv_write_fp8_kernel quantizes a row (row absmax over the row's hv
 // lanes -> fp8_row_scale -> bf16x4_to_e4m3x4) and go to the FP8 KV cache `d` (HS <= 512): two 8-byte e4m3 groups per lane, the scale from the row's first lane.
-template <bool kQuant>
+// kRows (with kQuant; fused_qkv_post_kvfp8_rows_devpos): blockIdx.y is not a token of one sequence but ROW b of B independent sequences -- its q / k / v at
+// + b * src_row_stride, its position pos_dev[b] (not *pos_dev + b), its q_out at + b * NH * HS, its own caches [NKV, capacity, HS] at + b * NKV * capacity rows.
+template <bool kQuant, bool kRows = false>
 __device__ __forceinline__ void qkv_post_body(const QkvPostParams& p, const KvFp8Rows& d)
 {
+    static_assert(kQuant || !kRows, "the rows form exists over the FP8 KV cache only");
     const int HS = p.HS, half = HS / 2, hv = half / 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rpw = (hv <= 32) ? 64 / hv : 1;                       // rows per wave
@@ -108,8 +111,9 @@ __device__ __forceinline__ void qkv_post_body(const QkvPostParams& p, const KvFp
     const bool valid = r < nrows;
     const int rr = valid ? r : nrows - 1;
     const int t = blockIdx.y;
-    const int position = (p.pos_dev ? *p.pos_dev : p.position) + t;
+    const int position = kRows ? p.pos_dev[t] : (p.pos_dev ? *p.pos_dev : p.position) + t;
     const int row = position % p.capacity;
+    const size_t cache_row0 = kRows ? (size_t)t * p.NKV * p.capacity : 0;      // the first cache row of this sequence's caches
     const size_t src_t = (size_t)t * p.src_row_stride;
     const float* cos_row = p.cos_cache + (size_t)position * half;
     const float* sin_row = p.sin_cache + (size_t)position * half;
@@ -126,7 +130,7 @@ __device__ __forceinline__ void qkv_post_body(const QkvPostParams& p, const KvFp
     else if (rr < p.NH + p.NKV)
     {
         const int n = rr - p.NH;
-        const size_t crow = (size_t)n * p.capacity + row;
+        const size_t crow = cache_row0 + (size_t)n * p.capacity + row;
         src = p.k + src_t + (size_t)n * HS; w = p.kw; rotate = true;
         if constexpr (kQuant) { dst8 = d.K8 + crow * HS; dsts = d.Ks + crow; }
         else dst = p.Kc + crow * HS;
@@ -134,7 +138,7 @@ __device__ __forceinline__ void qkv_post_body(const QkvPostParams& p, const KvFp
     else
     {
         const int n = rr - p.NH - p.NKV;
-        const size_t crow = (size_t)n * p.capacity + row;
+        const size_t crow = cache_row0 + (size_t)n * p.capacity + row;
         src = p.v_src + src_t + (size_t)n * HS; w = p.vw; rotate = false;
         if constexpr (kQuant) { dst8 = d.V8 + crow * HS; dsts = d.Vs + crow; }
         else dst = p.Vc + crow * HS;
@@ -204,6 +208,8 @@ __device__ __forceinline__ void qkv_post_body(const QkvPostParams& p, const KvFp
 __global__ __launch_bounds__(256) void qkv_post_kernel(const QkvPostParams p) { qkv_post_body<false>(p, KvFp8Rows{}); }
 // the same launch shape; Kc / Vc of `p` are unused
 __global__ __launch_bounds__(256) void qkv_post_kvfp8_kernel(const QkvPostParams p, const KvFp8Rows d) { qkv_post_body<true>(p, d); }
+// B independent sequences, row b = blockIdx.y at pos_dev[b] on its own caches
+__global__ __launch_bounds__(256) void qkv_post_kvfp8_rows_kernel(const QkvPostParams p, const KvFp8Rows d) { qkv_post_body<true, true>(p, d); }
 
 }  // namespace mila
 
@@ -312,6 +318,25 @@ int mila_cdna4_fused_qkv_post_kvfp8_devpos(uint16_t* q_out, uint8_t* K8, uint8_t
 {
     return qkv_post_kvfp8("fused_qkv_post_kvfp8_devpos", q_out, K8, V8, Ks, Vs, q, k, v_src, 0, qw, kw, vw, cos_cache, sin_cache, 1, NH, NKV, HS, 0, position_dev, true, false, capacity, eps,
                           stream);
+}
+
+// fused_qkv_post_kvfp8_devpos for B independent sequences (mila_cdna4.h): row b at positions_dev[b] into its own caches.  The entry cannot see the device values: a
+// positions_dev[b] outside [0, the RoPE tables' length) would read out of bounds -- the caller keeps that invariant (GemmaTransformer: checkRowsStep, checkPosition).
+int mila_cdna4_fused_qkv_post_kvfp8_rows_devpos(uint16_t* q_out, uint8_t* K8, uint8_t* V8, float* Ks, float* Vs, const uint16_t* q, const uint16_t* k, const uint16_t* v_src,
+                                                int64_t raw_b_stride, const uint16_t* qw, const uint16_t* kw, const uint16_t* vw, const float* cos_cache, const float* sin_cache,
+                                                int B, int NH, int NKV, int HS, const int32_t* positions_dev, int capacity, float eps, mila_stream_t stream)
+{
+    const char* who = "fused_qkv_post_kvfp8_rows_devpos";
+    MILA_REQUIRE(q_out && K8 && V8 && Ks && Vs && q && k && v_src && qw && kw && cos_cache && sin_cache && positions_dev, "%s: null pointer", who);
+    MILA_REQUIRE(B >= 2 && B <= 4, "%s: B=%d rows outside 2 .. 4", who, B);
+    MILA_REQUIRE(HS == 64 || HS == 128 || HS == 256 || HS == 512, "%s: HS=%d must be 64, 128, 256 or 512", who, HS);
+    MILA_REQUIRE(NH > 0 && NKV > 0, "%s: bad sizes (NH=%d NKV=%d)", who, NH, NKV);
+    MILA_REQUIRE(capacity > 0, "%s: capacity=%d must be positive", who, capacity);
+    MILA_REQUIRE(raw_b_stride % 8 == 0 && raw_b_stride >= (int64_t)HS, "%s: row stride %lld must be a multiple of 8", who, (long long)raw_b_stride);
+    QkvPostParams p{q_out, nullptr, nullptr, q, k, v_src, qw, kw, vw, cos_cache, sin_cache, positions_dev, NH, NKV, HS, 0, capacity, eps, raw_b_stride};
+    const int rows = NH + 2 * NKV;
+    hipLaunchKernelGGL(qkv_post_kvfp8_rows_kernel, dim3(ceil_div(rows, 4 * qkv_post_rows_per_wave(HS)), B), dim3(256), 0, as_stream(stream), p, KvFp8Rows{K8, V8, Ks, Vs});
+    return check_hip(hipGetLastError(), who);
 }
 
 int mila_cdna4_advance_position(int32_t* position_dev, mila_stream_t stream)

@@ -60,6 +60,53 @@ __global__ __launch_bounds__(kForkThreads) void kv_rows_fork_layers_bf16_kernel(
     }
 }
 
+// The same for the FP8 KV cache (kv_rows_fork_layers_kvfp8): per layer K8 / V8 [rows, NKV, capacity, HS] e4m3 and Ks / Vs [rows, NKV, capacity] fp32.  One flat walk per
+// layer over two kinds of unit: first the 16-byte units of the bytes (K8 then V8; per head len * HS / 16 of them, HS a multiple of 16), then the 4-byte words of the
+// scales (Ks then Vs; per head len of them).  A head's scale run starts capacity * 4 bytes after the one before and is len * 4 long: neither is 16-byte aligned in
+// general, so the scales go word by word, never wider.
+struct ForkLayerFp8 { uint8_t* K8; uint8_t* V8; float* Ks; float* Vs; int64_t seg_units, head_bytes; int32_t NKV, capacity; };      // seg_units = len * HS / 16, head_bytes = capacity * HS
+constexpr int kForkLayersFp8PerLaunch = 64;      // 64 x 56 bytes of records: 3.5 KiB of the 4 KiB argument block
+struct ForkLayersFp8 { ForkLayerFp8 l[kForkLayersFp8PerLaunch]; };
+
+__global__ __launch_bounds__(kForkThreads) void kv_rows_fork_layers_kvfp8_kernel(const ForkLayersFp8 layers, int src, unsigned dst_mask, int rows, int len)
+{
+    const ForkLayerFp8& L = layers.l[blockIdx.y];
+    uint8_t* const K8 = L.K8;
+    uint8_t* const V8 = L.V8;
+    float* const Ks = L.Ks;
+    float* const Vs = L.Vs;
+    const int64_t seg_units = L.seg_units, head_bytes = L.head_bytes, capacity = L.capacity;
+    const int64_t cache_units = (int64_t)L.NKV * seg_units, byte_units = 2 * cache_units, row_bytes = (int64_t)L.NKV * head_bytes;
+    const int64_t cache_words = (int64_t)L.NKV * len, total = byte_units + 2 * cache_words, row_words = (int64_t)L.NKV * capacity;
+    const int64_t stride = (int64_t)gridDim.x * kForkThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kForkThreads + threadIdx.x; i < total; i += stride)
+    {
+        if (i < byte_units)
+        {
+            const bool value = i >= cache_units;
+            const int64_t c = value ? i - cache_units : i;
+            const int64_t head = c / seg_units, u = c - head * seg_units;
+            uint8_t* base = value ? V8 : K8;
+            const int64_t in_row = head * head_bytes + u * 16;      // < row_bytes: head < NKV, u * 16 < len * HS <= capacity * HS
+            const u32x4 bits = *reinterpret_cast<const u32x4*>(base + (int64_t)src * row_bytes + in_row);
+            for (int r = 0; r < rows; ++r)
+                if ((dst_mask >> r) & 1u) *reinterpret_cast<u32x4*>(base + (int64_t)r * row_bytes + in_row) = bits;
+        }
+        else
+        {
+            const int64_t j = i - byte_units;
+            const bool value = j >= cache_words;
+            const int64_t c = value ? j - cache_words : j;
+            const int64_t head = c / len, u = c - head * len;
+            uint32_t* base = reinterpret_cast<uint32_t*>(value ? Vs : Ks);      // bit patterns: a NaN, a -0 or a denormal passes as it is
+            const int64_t in_row = head * capacity + u;             // < row_words: head < NKV, u < len <= capacity
+            const uint32_t bits = base[(int64_t)src * row_words + in_row];
+            for (int r = 0; r < rows; ++r)
+                if ((dst_mask >> r) & 1u) base[(int64_t)r * row_words + in_row] = bits;
+        }
+    }
+}
+
 }  // namespace mila
 
 using namespace mila;
@@ -126,6 +173,51 @@ int mila_cdna4_kv_rows_fork_layers_bf16(const mila_kv_fork_layer* layers, int n_
                            dst_mask, rows);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return ::mila::check_hip(e, "kv_rows_fork_layers_bf16");
+    }
+    return MILA_OK;
+}
+
+int mila_cdna4_kv_rows_fork_layers_kvfp8(const mila_kv_fork_layer_fp8* layers, int n_layers, int rows, int src, unsigned dst_mask, int len, mila_stream_t stream)
+{
+    MILA_REQUIRE(layers, "kv_rows_fork_layers_kvfp8: null layer table");
+    MILA_REQUIRE(n_layers > 0, "kv_rows_fork_layers_kvfp8: n_layers=%d must be positive", n_layers);
+    MILA_REQUIRE(rows >= 2 && rows <= 4, "kv_rows_fork_layers_kvfp8: rows=%d out of range (2 .. 4)", rows);
+    MILA_REQUIRE(src >= 0 && src < rows, "kv_rows_fork_layers_kvfp8: src=%d outside the %d rows", src, rows);
+    MILA_REQUIRE(dst_mask != 0, "kv_rows_fork_layers_kvfp8: empty dst_mask");
+    MILA_REQUIRE((dst_mask >> rows) == 0, "kv_rows_fork_layers_kvfp8: dst_mask=0x%x names a row outside the %d rows", dst_mask, rows);
+    MILA_REQUIRE(((dst_mask >> src) & 1u) == 0, "kv_rows_fork_layers_kvfp8: dst_mask=0x%x names the source row %d", dst_mask, src);
+    MILA_REQUIRE(len >= 1, "kv_rows_fork_layers_kvfp8: len=%d must be positive", len);
+    for (int i = 0; i < n_layers; ++i)      // every layer before the first launch: a refusal leaves every cache as it was
+    {
+        const mila_kv_fork_layer_fp8& L = layers[i];
+        MILA_REQUIRE(L.K8 && L.V8 && L.Ks && L.Vs, "kv_rows_fork_layers_kvfp8: layer %d: null pointer", i);
+        MILA_REQUIRE(L.NKV > 0 && L.capacity > 0 && L.HS > 0, "kv_rows_fork_layers_kvfp8: layer %d: bad sizes (NKV=%d capacity=%d HS=%d)", i, L.NKV, L.capacity, L.HS);
+        MILA_REQUIRE(L.HS % 16 == 0, "kv_rows_fork_layers_kvfp8: layer %d: HS=%d must be a multiple of 16", i, L.HS);
+        MILA_REQUIRE(len <= L.capacity, "kv_rows_fork_layers_kvfp8: layer %d: len=%d out of range (1 .. capacity %d)", i, len, L.capacity);
+        MILA_REQUIRE(((reinterpret_cast<uintptr_t>(L.K8) | reinterpret_cast<uintptr_t>(L.V8)) & 15) == 0, "kv_rows_fork_layers_kvfp8: layer %d: K8 and V8 must be 16-byte aligned", i);
+        MILA_REQUIRE(((reinterpret_cast<uintptr_t>(L.Ks) | reinterpret_cast<uintptr_t>(L.Vs)) & 3) == 0, "kv_rows_fork_layers_kvfp8: layer %d: Ks and Vs must be 4-byte aligned", i);
+    }
+    for (int first = 0; first < n_layers; first += kForkLayersFp8PerLaunch)
+    {
+        const int n = n_layers - first < kForkLayersFp8PerLaunch ? n_layers - first : kForkLayersFp8PerLaunch;
+        ForkLayersFp8 args{};
+        int64_t most = 0;      // the longest layer's units size the grid's x; a shorter layer's spare blocks fall through their loop
+        for (int i = 0; i < n; ++i)
+        {
+            const mila_kv_fork_layer_fp8& L = layers[first + i];
+            ForkLayerFp8& a = args.l[i];
+            a.K8 = L.K8; a.V8 = L.V8; a.Ks = L.Ks; a.Vs = L.Vs; a.NKV = L.NKV; a.capacity = L.capacity;
+            a.seg_units = (int64_t)len * (L.HS / 16);
+            a.head_bytes = (int64_t)L.capacity * L.HS;
+            const int64_t total = 2 * (int64_t)L.NKV * (a.seg_units + len);
+            most = total > most ? total : most;
+        }
+        const int64_t blocks = (most + kForkThreads - 1) / kForkThreads;
+        const int64_t cap = kForkMaxBlocks / n > kForkLayersMinBlocks ? kForkMaxBlocks / n : kForkLayersMinBlocks;
+        hipLaunchKernelGGL(kv_rows_fork_layers_kvfp8_kernel, dim3((unsigned)(blocks < cap ? blocks : cap), (unsigned)n), dim3(kForkThreads), 0, as_stream(stream), args, src,
+                           dst_mask, rows, len);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return ::mila::check_hip(e, "kv_rows_fork_layers_kvfp8");
     }
     return MILA_OK;
 }

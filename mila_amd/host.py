@@ -265,7 +265,8 @@ class Gemma:
 
     MODES = {"reference": 0, "fused": 1, "graph": 2}
 
-    def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None, kv_fp8=False, max_batch=None, draft_tokens=None):
+    def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None, kv_fp8=False, max_batch=None, draft_tokens=None,
+                 kv_fp8_rows=False):
         """device: HIP device ordinal; default = this process's LOCAL_RANK (one replica per GPU under torch.distributed.run).
         profile: synthetic-parameter multipliers {linear_gain, qk_norm_center, post_norm_center, layer_scalar, table_gain}
         (GemmaTransformer::SyntheticProfile; None = the unit-scale generator of SURVEY.md section 8d)
@@ -273,7 +274,9 @@ class Gemma:
         max_batch: GemmaConfig::max_batch (1 .. 4) through mila_gemma_create_rows -- independent sequences per decode step (prefill_row / decode_rows); None = the
         one-sequence model of mila_gemma_create
         draft_tokens: GemmaConfig::draft_tokens (0 .. 3) through mila_gemma_create_chain -- the chain step (decode_chain) verifies that many drafted tokens; 0 builds
-        the plain model through the same entry; None = not through that entry"""
+        the plain model through the same entry; None = not through that entry
+        kv_fp8_rows: GemmaConfig::kv_fp8_rows through mila_gemma_create_rows_kv -- the FP8 KV cache (implied) on a model of max_batch 1 .. 4, one cache per row; plain
+        kv_fp8 with max_batch > 1 stays refused"""
         lib = load()
         if device is None:
             from .replicas import local_device
@@ -288,7 +291,14 @@ class Gemma:
         self.vocab = self.cfg["vocab_size"]
         self.max_batch = 1 if max_batch is None else int(max_batch)
         self.draft_tokens = 0 if draft_tokens is None else int(draft_tokens)
-        if draft_tokens is not None:
+        self.kv_fp8_rows = bool(kv_fp8_rows)
+        if kv_fp8_rows:
+            if draft_tokens:
+                raise ValueError("Gemma: draft_tokens cannot be combined with kv_fp8_rows (the chain over the FP8 KV cache is not built)")
+            lib.mila_gemma_create_rows_kv.restype = C.c_void_p
+            lib.mila_gemma_create_rows_kv.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_int]
+            self.h = lib.mila_gemma_create_rows_kv(POLICIES[policy], C.byref(c), max_seq, max_prefill, self.max_batch, 1, seed, device)
+        elif draft_tokens is not None:
             lib.mila_gemma_create_chain.restype = C.c_void_p
             lib.mila_gemma_create_chain.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int]
             self.h = lib.mila_gemma_create_chain(POLICIES[policy], C.byref(c), max_seq, max_prefill, self.max_batch, self.draft_tokens, seed, device)
@@ -835,16 +845,20 @@ class Gemma:
         return {"decode_bytes_per_token": out[0], "weight_bytes": out[1], "linear_params": out[2], "table_params": out[3]}
 
 
-def validate_gemma_config(config=None, max_batch=1, draft_tokens=0, kv_fp8=False):
-    """GemmaConfig::validate() on the configuration Gemma(..., max_batch=, draft_tokens=) would build, without a device: raises ValueError with its message"""
+def validate_gemma_config(config=None, max_batch=1, draft_tokens=0, kv_fp8=False, kv_fp8_rows=False):
+    """GemmaConfig::validate() on the configuration Gemma(..., max_batch=, draft_tokens=, kv_fp8_rows=) would build, without a device: raises ValueError with its message"""
     lib = load()
     lib.mila_gemma_validate_config.argtypes = [C.POINTER(GemmaConfigC), C.c_int64, C.c_int64]
+    lib.mila_gemma_validate_config_kv.argtypes = [C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int]
     cfg = dict(GEMMA4_12B if config is None else config)
     cfg.setdefault("bounded_local_kv", 0)
     cfg.setdefault("kv_fp8", 0)
     if kv_fp8:
         cfg["kv_fp8"] = 1
     c = GemmaConfigC(**cfg)
+    if kv_fp8_rows:
+        _check(lib.mila_gemma_validate_config_kv(C.byref(c), int(max_batch), int(draft_tokens), 1))
+        return
     _check(lib.mila_gemma_validate_config(C.byref(c), int(max_batch), int(draft_tokens)))
 
 
@@ -897,7 +911,10 @@ class GemmaModel:
         return cls(h, device)
 
     @classmethod
-    def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0, kv_fp8=False, max_batch=None, draft_tokens=None):
+    def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0, kv_fp8=False, max_batch=None, draft_tokens=None,
+                  kv_fp8_rows=False):
+        """kv_fp8_rows: GemmaModelConfig::withKvFp8Rows -- the FP8 KV cache (implied) on a model of max_batch 1 .. 4 (generate_batch / generate_requests / serve_requests
+        over FP8 rows); plain kv_fp8 with max_batch > 1 stays refused"""
         lib = cls._bind()
         cfg = dict(GEMMA4_12B if config is None else config)
         cfg.setdefault("bounded_local_kv", 0)
@@ -908,7 +925,13 @@ class GemmaModel:
         p = None
         if profile is not None:
             p = (C.c_float * 5)(*[float(profile[k]) for k in ("linear_gain", "qk_norm_center", "post_norm_center", "layer_scalar", "table_gain")])
-        if draft_tokens is not None:      # GemmaModelConfig::withDraftTokens: greedy generate() verifies up to draft_tokens drafted tokens per step
+        if kv_fp8_rows:
+            if draft_tokens:
+                raise ValueError("GemmaModel.synthetic: draft_tokens cannot be combined with kv_fp8_rows")
+            lib.mila_gemma_model_synthetic_rows_kv.restype = C.c_void_p
+            lib.mila_gemma_model_synthetic_rows_kv.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_void_p, C.c_int]
+            h = lib.mila_gemma_model_synthetic_rows_kv(POLICIES[policy], C.byref(c), context, prefill_chunk, 1 if max_batch is None else int(max_batch), 1, seed, p, device)
+        elif draft_tokens is not None:      # GemmaModelConfig::withDraftTokens: greedy generate() verifies up to draft_tokens drafted tokens per step
             if max_batch is not None:
                 raise ValueError("GemmaModel.synthetic: draft_tokens cannot be combined with max_batch")
             lib.mila_gemma_model_synthetic_chain.restype = C.c_void_p

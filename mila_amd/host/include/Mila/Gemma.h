@@ -38,6 +38,7 @@ namespace Mila::Dnn
         float rms_norm_eps = 1e-6f, rope_theta_local = 10000.0f, rope_theta_global = 1000000.0f, final_logit_softcapping = 30.0f;
         bool bounded_local_kv = false;   ///< SlidingWindowKvCache on the sliding-window layers (ring of window + chunk - 1 rows)
         bool kv_fp8 = false;             ///< PerChannelKvFp8<> on every layer: e4m3 K / V + one fp32 scale per KV head per cached token, (HS + 4) / (2 HS) of the bf16 bytes
+        bool kv_fp8_rows = false;        ///< kv_fp8 (implied) that max_batch > 1 may be combined with: one FP8 KV cache per row, the rows step on the FP8 rows entries (two launches per layer)
         dim_t max_batch = 1;             ///< independent sequences a decode step can carry (1 .. 4): KV caches, decode buffers, logits and position words per row
         dim_t draft_tokens = 0;          ///< drafted tokens a chain step can verify (0 .. 3): the rows decode buffers for draft_tokens + 1 rows on the ONE cache, no extra caches
 
@@ -49,6 +50,7 @@ namespace Mila::Dnn
         dim_t packedQkvWidth( bool g ) const { return qWidth( g ) + ( g ? 1 : 2 ) * kvWidth( g ); }   // K=V on global layers
         dim_t windowFor( bool g ) const { return g ? 0 : window; }
         float embeddingScale() const { return std::sqrt( static_cast<float>( embedding_dim ) ); }
+        bool kvFp8() const noexcept { return kv_fp8 || kv_fp8_rows; }      // the FP8 KV cache on every layer, by either switch
 
         void validate() const
         {
@@ -60,7 +62,7 @@ namespace Mila::Dnn
                 throw std::invalid_argument( "GemmaConfig: feature widths must be multiples of 128 (FP4 group size)" );
             if ( max_batch < 1 || max_batch > 4 )
                 throw std::invalid_argument( "GemmaConfig: max_batch " + std::to_string( max_batch ) + " outside 1 .. 4 (the rows kernels keep every row's x in LDS)" );
-            if ( max_batch > 1 && kv_fp8 ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with kv_fp8 (the FP8 KV cache's fused append is B = 1)" );
+            if ( max_batch > 1 && kv_fp8 && !kv_fp8_rows ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with kv_fp8 (the FP8 KV cache's fused append is B = 1)" );
             if ( max_batch > 1 && bounded_local_kv ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with bounded_local_kv (the ring needs a rewind rule per row)" );
             if ( draft_tokens < 0 || draft_tokens > 3 )
                 throw std::invalid_argument( "GemmaConfig: draft_tokens " + std::to_string( draft_tokens ) + " outside 0 .. 3 (a chain step is the last token plus the drafts: at most the four rows of the rows kernels)" );
@@ -69,7 +71,7 @@ namespace Mila::Dnn
                 if ( max_batch > 1 )
                     throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 cannot be combined with max_batch > 1 (a chain step's rows are consecutive positions of ONE sequence on one cache; "
                                                  "the rows of a batched step are independent sequences, and the two share the four rows of the rows kernels)" );
-                if ( kv_fp8 ) throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 cannot be combined with kv_fp8 (the FP8 KV cache's fused append is B = 1; the chain over it is not built)" );
+                if ( kvFp8() ) throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 cannot be combined with kv_fp8 (the FP8 KV cache's fused append is B = 1; the chain over it is not built)" );
                 if ( bounded_local_kv )
                     throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 cannot be combined with bounded_local_kv (rejected drafts leave stale rows, and a ring may already have evicted what they overwrote)" );
                 for ( dim_t hs : { head_dim, global_head_dim } )
@@ -77,7 +79,7 @@ namespace Mila::Dnn
                         throw std::invalid_argument( "GemmaConfig: draft_tokens > 0 needs head dimensions of 64, 128, 256 or 512 (head_dim " + std::to_string( head_dim ) + ", global_head_dim " +
                                                      std::to_string( global_head_dim ) + ")" );
             }
-            if ( kv_fp8 )
+            if ( kvFp8() )
             {
                 if ( bounded_local_kv ) throw std::invalid_argument( "GemmaConfig: kv_fp8 cannot be combined with bounded_local_kv (the FP8 KV cache is unbounded)" );
                 for ( dim_t hs : { head_dim, global_head_dim } )
@@ -152,6 +154,7 @@ namespace Mila::Dnn
             : cfg_( cfg ), max_seq_( max_seq ), max_prefill_( std::max<dim_t>( max_prefill, 1 ) )
         {
             cfg_.validate();
+            if ( cfg_.kv_fp8_rows ) cfg_.kv_fp8 = true;      // the rows switch implies the cache policy; at max_batch 1 this IS the kv_fp8 model
             if ( max_seq <= 0 ) throw std::invalid_argument( "GemmaTransformer: max_seq must be positive" );
             owned_ctx_ = Compute::createExecutionContext( device );
             ctx_ = Compute::cast_context<kDevice>( owned_ctx_.get() );
@@ -561,7 +564,10 @@ namespace Mila::Dnn
         // batched decode (GemmaConfig::max_batch > 1): up to four INDEPENDENT sequences per step, row b at its own position rows_->pos[ b ], on its own KV caches.
         // A step is enqueueFusedStep's launch sequence on the rows entries (matvec_rows, fused_attn_decode_rows_bf16): six launches per layer, the weights streamed
         // once for all rows, always in the device-position form.  Row b's logits are bit-identical to the same sequence run alone through decodeFused(), as long as
-        // both runs are in the same live-length bucket (mila_cdna4.h: fused_attn_decode_rows_bf16).
+        // both runs are in the same live-length bucket (mila_cdna4.h: fused_attn_decode_rows_bf16).  With GemmaConfig::kv_fp8_rows every row has its own FP8 KV
+        // caches and the attention launch is two -- fused_qkv_post_kvfp8_rows_devpos into the rows q buffer, attn_decode_kvfp8_rows -- seven per layer, one linear
+        // chain; row b is then bit-identical to the same sequence alone on a kv_fp8 model.  prefillRow / forkRow / forkRowPrefix / rewindKvCacheRow / resetRow work on
+        // either cache: a row's state beside its caches is its position word, its token and its logits.
         // ------------------------------------------------------------------------------------
         dim_t maxBatch() const noexcept { return cfg_.max_batch; }
         /// prefill `n` tokens at positions offset .. into row b's caches through the B = 1 prefill (cache-row selection; no prefill kernel knows about rows); row b's
@@ -1689,6 +1695,18 @@ namespace Mila::Dnn
                                                                                  R.attn_partials->data(), R.attn_partials->sizeInBytes(), B, NH, NKV, HD, (int)L.cacheCapacity(),
                                                                                  chain->position, chain->pos_dev, max_len, (int)cfg_.windowFor( g ), L.attentionScale(),
                                                                                  cfg_.rms_norm_eps, st ) );
+                else if ( L.kvFp8() )
+                {
+                    // the FP8 KV cache: two launches (+ combine), as in the one-row step -- the quantizing append of every row into its own caches and the rows q
+                    // buffer, then the policy's decode attention, row b over pos[ b ] + 1 keys, on the rows partials
+                    const int cap = (int)L.cacheCapacity();
+                    Compute::rocmCheck( mila_cdna4_fused_qkv_post_kvfp8_rows_devpos( R.q->data(), L.keyCacheFp8Rows(), L.valueCacheFp8Rows(), L.keyScalesRows(), L.valueScalesRows(), qp, kp, vp,
+                                                                                     (int64_t)PK, L.q_norm->getWeight()->data(), L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(),
+                                                                                     L.rope->cosCache(), L.rope->sinCache(), B, NH, NKV, HD, R.pos->data(), cap, cfg_.rms_norm_eps, st ) );
+                    Compute::rocmCheck( mila_cdna4_attn_decode_kvfp8_rows( R.attn->data(), R.q->data(), L.keyCacheFp8Rows(), L.valueCacheFp8Rows(), L.keyScalesRows(), L.valueScalesRows(),
+                                                                           R.attn_partials->data(), R.attn_partials->sizeInBytes(), B, NH, NKV, HD, cap, R.pos->data(), max_len,
+                                                                           (int)cfg_.windowFor( g ), L.attentionScale(), st ) );
+                }
                 else
                     Compute::rocmCheck( mila_cdna4_fused_attn_decode_rows_bf16( R.attn->data(), L.keyCacheRows(), L.valueCacheRows(), qp, kp, vp, (int64_t)PK, L.q_norm->getWeight()->data(),
                                                                                 L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(),
@@ -1835,9 +1853,15 @@ namespace Mila::Dnn
             if ( chain_graph_exec_ ) { (void)hipGraphExecDestroy( chain_graph_exec_ ); chain_graph_exec_ = nullptr; }
             if ( chain_graph_ ) { (void)hipGraphDestroy( chain_graph_ ); chain_graph_ = nullptr; }
         }
-        /// every layer's cache prefix in one launch, from the table buildRows() made (mila_cdna4.h: kv_rows_fork_layers_bf16)
+        /// every layer's cache prefix in one launch, from the table buildRows() made (mila_cdna4.h: kv_rows_fork_layers_bf16, kv_rows_fork_layers_kvfp8)
         void forkLayers( int src, unsigned dst_mask, dim_t len )
         {
+            if ( !fork_layers_fp8_.empty() )
+            {
+                Compute::rocmCheck( mila_cdna4_kv_rows_fork_layers_kvfp8( fork_layers_fp8_.data(), static_cast<int>( fork_layers_fp8_.size() ), static_cast<int>( cfg_.max_batch ), src,
+                                                                          dst_mask, static_cast<int>( len ), ctx_->getStream() ) );
+                return;
+            }
             Compute::rocmCheck( mila_cdna4_kv_rows_fork_layers_bf16( fork_layers_.data(), static_cast<int>( fork_layers_.size() ), static_cast<int>( cfg_.max_batch ), src, dst_mask,
                                                                      static_cast<int>( len ), ctx_->getStream() ) );
         }
@@ -1867,6 +1891,7 @@ namespace Mila::Dnn
         struct RowsState
         {
             std::unique_ptr<TensorType> qkv, attn, o, down, act, res1, hidden[ 3 ];
+            std::unique_ptr<TensorType> q;      // FP8 KV rows only: [rows, NH * HD] roped q rows
             std::unique_ptr<LogitsTensor> logits, sample_scratch, attn_partials;
             std::unique_ptr<LogitsTensor> radix_scratch;      // the rows radix sampler's workspace, one region per row
             std::unique_ptr<TokenTensor> pos, tok, active;
@@ -1879,16 +1904,20 @@ namespace Mila::Dnn
             const auto dev = ctx_->getDeviceId();
             if ( cfg_.max_batch > 1 )
             {
-                fork_layers_.clear();      // the layer table of forkRow / forkRowPrefix: built once, here
+                fork_layers_.clear();      // the layer tables of forkRow / forkRowPrefix (one per cache policy; a model has layers of one): built once, here
+                fork_layers_fp8_.clear();
                 for ( auto& L : layers_ )
                 {
                     L.setCacheRows( static_cast<int>( B ) );
-                    fork_layers_.push_back( mila_kv_fork_layer{ L.keyCacheRows(), L.valueCacheRows(), static_cast<int32_t>( cfg_.numKvHeads( L.global ) ),
-                                                                static_cast<int32_t>( L.cacheCapacity() ), static_cast<int32_t>( cfg_.headDim( L.global ) ), 0 } );
+                    const auto NKV = static_cast<int32_t>( cfg_.numKvHeads( L.global ) ), cap = static_cast<int32_t>( L.cacheCapacity() ), HD = static_cast<int32_t>( cfg_.headDim( L.global ) );
+                    if ( L.kvFp8() ) fork_layers_fp8_.push_back( mila_kv_fork_layer_fp8{ L.keyCacheFp8Rows(), L.valueCacheFp8Rows(), L.keyScalesRows(), L.valueScalesRows(), NKV, cap, HD, 0 } );
+                    else fork_layers_.push_back( mila_kv_fork_layer{ L.keyCacheRows(), L.valueCacheRows(), NKV, cap, HD, 0 } );
                 }
             }
             rows_ = std::make_unique<RowsState>();
             auto& R = *rows_;
+            // the FP8 rows step's roped q rows, between its two launches per layer (a bf16 rows model allocates none: byte for byte what it was)
+            if ( cfg_.max_batch > 1 && cfg_.kv_fp8 ) R.q = std::make_unique<TensorType>( dev, shape_t{ B, std::max( cfg_.qWidth( false ), cfg_.qWidth( true ) ) } );
             R.qkv = std::make_unique<TensorType>( dev, shape_t{ B, std::max( cfg_.packedQkvWidth( false ), cfg_.packedQkvWidth( true ) ) } );
             R.attn = std::make_unique<TensorType>( dev, shape_t{ B, std::max( cfg_.qWidth( false ), cfg_.qWidth( true ) ) } );
             R.o = std::make_unique<TensorType>( dev, shape_t{ B, D } );
@@ -1931,6 +1960,7 @@ namespace Mila::Dnn
             for ( const auto* t : { R.logits.get(), R.sample_scratch.get(), R.attn_partials.get(), R.radix_scratch.get() } ) b += tensorBytes( t );
             for ( const auto* t : { R.pos.get(), R.tok.get(), R.active.get() } ) b += tensorBytes( t );
             if ( R.result ) b += tensorBytes( R.result.get() );
+            if ( R.q ) b += tensorBytes( R.q.get() );
             return b;
         }
         /// the same from the configuration alone, plus the cache rows beyond the first of every layer
@@ -1943,6 +1973,7 @@ namespace Mila::Dnn
             b += B * static_cast<size_t>( cfg_.vocab_size ) * 4 + B * ( ( mila_cdna4_sample_scratch_bytes() / 4 ) * 4 ) + ( ( rowsAttnScratchBytes() + 3 ) / 4 ) * 4 + 3 * B * 4;
             b += rowsRadixScratchBytes();
             if ( cfg_.draft_tokens > 0 ) return b + ( B + 1 ) * 4;      // the chain's result words; its rows share the one cache
+            if ( cfg_.kv_fp8 ) return b + B * maxq * 2;      // the rows q buffer; the FP8 KV op counts its cache rows itself (RocmGqaKvFp8Op::requiredStateBytes)
             for ( auto& L : layers_ ) b += ( B - 1 ) * 2 * static_cast<size_t>( cfg_.kvWidth( L.global ) ) * static_cast<size_t>( L.cacheCapacity() ) * 2;
             return b;
         }
@@ -2266,6 +2297,7 @@ namespace Mila::Dnn
         Compute::RocmExecutionContext* ctx_{ nullptr };
         LayerList layers_;
         std::vector<mila_kv_fork_layer> fork_layers_;
+        std::vector<mila_kv_fork_layer_fp8> fork_layers_fp8_;
         std::shared_ptr<RmsNormType> final_norm_;
         std::shared_ptr<LmHeadLinearType> lm_head_;
         std::unique_ptr<TensorType> hidden_[ 3 ], pf_x_[ 2 ], f_qkv_, f_q_, f_o_, f_down_, f_act_;

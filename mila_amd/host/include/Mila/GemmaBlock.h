@@ -616,11 +616,16 @@ namespace Mila::Dnn
         virtual float* valueScales() noexcept = 0;
         /// drop everything from `position` on, given that `written` positions were appended (the fused schedules append behind the op's back); false = refused
         virtual bool rewindKvCache( dim_t position, dim_t written ) = 0;
-        /// batched decode of independent sequences (bf16 caches only): `rows` caches behind the attention op, the one its B = 1 calls work on, and all of them
+        /// batched decode of independent sequences: `rows` caches behind the attention op, the one its B = 1 calls work on (keyCache() / keyCacheFp8() and their
+        /// siblings are then that row's), and all of them -- the bf16 arrays (null on an fp8 block) and the FP8 KV policy's four (null on a bf16 one)
         virtual void setCacheRows( int rows ) = 0;
         virtual void selectCacheRow( int b ) = 0;
         virtual uint16_t* keyCacheRows() = 0;
         virtual uint16_t* valueCacheRows() = 0;
+        virtual uint8_t* keyCacheFp8Rows() = 0;
+        virtual uint8_t* valueCacheFp8Rows() = 0;
+        virtual float* keyScalesRows() = 0;
+        virtual float* valueScalesRows() = 0;
 
         /// `layer_scalar` ([1] F32); children load through their own components
         void loadParameter( const std::string& n, const void* blob, size_t bytes ) override
@@ -765,18 +770,14 @@ namespace Mila::Dnn
         float* keyScales() noexcept override { if constexpr ( kKvFp8 ) return attn->getOperation().keyScaleData(); else return nullptr; }
         float* valueScales() noexcept override { if constexpr ( kKvFp8 ) return attn->getOperation().valueScaleData(); else return nullptr; }
         bool rewindKvCache( dim_t position, dim_t written ) override { attn->noteCacheLength( written ); return attn->rewindKvCache( position ); }
-        void setCacheRows( int rows ) override
-        {
-            if constexpr ( kKvFp8 ) { if ( rows != 1 ) throw std::logic_error( this->getName() + ": the FP8 KV cache has one row (its fused append is B = 1)" ); }
-            else attn->getOperation().setCacheRows( rows );
-        }
-        void selectCacheRow( int b ) override
-        {
-            if constexpr ( kKvFp8 ) { if ( b != 0 ) throw std::logic_error( this->getName() + ": the FP8 KV cache has one row" ); }
-            else attn->getOperation().selectCacheRow( b );
-        }
+        void setCacheRows( int rows ) override { attn->getOperation().setCacheRows( rows ); }
+        void selectCacheRow( int b ) override { attn->getOperation().selectCacheRow( b ); }
         uint16_t* keyCacheRows() override { if constexpr ( kKvFp8 ) return nullptr; else return attn->getOperation().keyCacheRows(); }
         uint16_t* valueCacheRows() override { if constexpr ( kKvFp8 ) return nullptr; else return attn->getOperation().valueCacheRows(); }
+        uint8_t* keyCacheFp8Rows() override { if constexpr ( kKvFp8 ) return attn->getOperation().keyBytesRows(); else return nullptr; }
+        uint8_t* valueCacheFp8Rows() override { if constexpr ( kKvFp8 ) return attn->getOperation().valueBytesRows(); else return nullptr; }
+        float* keyScalesRows() override { if constexpr ( kKvFp8 ) return attn->getOperation().keyScaleDataRows(); else return nullptr; }
+        float* valueScalesRows() override { if constexpr ( kKvFp8 ) return attn->getOperation().valueScaleDataRows(); else return nullptr; }
 
         /// Gemma.Block.ixx:433-440 / :464-490: the children's stats + the block's own workspace (unless the owner of a pooled one installed it)
         MemoryStats getMemoryStats() const override

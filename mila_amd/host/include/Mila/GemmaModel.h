@@ -307,6 +307,9 @@ namespace Mila::Dnn
         GemmaModelConfig& withDraftTokens( dim_t k ) { draft_tokens_ = k; return *this; }
         dim_t draftTokens() const noexcept { return draft_tokens_; }
         GemmaModelConfig& withKvFp8( bool on ) { kv_fp8_ = on; return *this; }                               ///< PerChannelKvFp8<> on every layer (GemmaConfig::kv_fp8), under any weight policy
+        /// GemmaConfig::kv_fp8_rows: the FP8 KV cache (implied) on a model of max_batch 1 .. 4 -- generateBatch / generateRequests / serveRequests over FP8 rows
+        GemmaModelConfig& withKvFp8Rows( bool on ) { kv_fp8_rows_ = on; return *this; }
+        bool kvFp8Rows() const noexcept { return kv_fp8_rows_; }
         dim_t getContextLength() const noexcept { return context_length_; }
         WeightQuantization getWeightQuantization() const noexcept { return weight_quantization_; }
         KvCacheCompression getKvCacheCompression() const noexcept { return kv_cache_compression_; }
@@ -317,7 +320,7 @@ namespace Mila::Dnn
         dim_t context_length_{ 0 }, prefill_chunk_{ 0 }, max_batch_{ 1 }, draft_tokens_{ 0 };
         WeightQuantization weight_quantization_{ WeightQuantization::None };
         KvCacheCompression kv_cache_compression_{ KvCacheCompression::None };
-        bool bounded_local_kv_{ false }, kv_fp8_{ false };
+        bool bounded_local_kv_{ false }, kv_fp8_{ false }, kv_fp8_rows_{ false };
     };
 
     /// Models/QuantizationDispatch.ixx: the runtime deployment choice picks the compile-time policy
@@ -377,6 +380,7 @@ namespace Mila::Dnn
                         throw std::invalid_argument( "GemmaModel::fromPretrained: context_length " + std::to_string( model_config.getContextLength() ) + " exceeds trained max_seq_len " + std::to_string( md.max_seq_length ) );
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
                     cfg.kv_fp8 = model_config.kvFp8();
+                    cfg.kv_fp8_rows = model_config.kvFp8Rows();
                     cfg.max_batch = model_config.maxBatch();
                     cfg.draft_tokens = model_config.draftTokens();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
@@ -394,6 +398,7 @@ namespace Mila::Dnn
                     GemmaConfig cfg = network_config;
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
                     cfg.kv_fp8 = model_config.kvFp8();
+                    cfg.kv_fp8_rows = model_config.kvFp8Rows();
                     cfg.max_batch = model_config.maxBatch();
                     cfg.draft_tokens = model_config.draftTokens();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );

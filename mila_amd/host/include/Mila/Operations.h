@@ -1011,7 +1011,30 @@ namespace Mila::Dnn::Compute
             ks_ = std::make_unique<ScaleTensor>( context_->getDeviceId(), ss );
             vs_ = std::make_unique<ScaleTensor>( context_->getDeviceId(), ss );
             length_ = 0;
+            rows_ = 1; row_ = 0;
         }
+        /// Batched decode of independent sequences, as RocmGqaOp::setCacheRows: `rows` caches [rows, NKV, capacity(, HS)] behind this B = 1 op, one per sequence.
+        /// selectCacheRow( b ) makes row b the cache every B = 1 call of this op (prefill, attendPrefill, decode*, keyBytes() and its siblings) works on, so the
+        /// existing prefill and the fused prefill append write row b unchanged; the rows entries (fused_qkv_post_kvfp8_rows_devpos, attn_decode_kvfp8_rows,
+        /// kv_rows_fork_layers_kvfp8) take keyBytesRows() and its siblings, all rows.  Call after initializeKvCache(); rows == 1 leaves the op as it was built.
+        void setCacheRows( int rows )
+        {
+            requireCache();
+            if ( rows < 1 ) throw std::invalid_argument( "RocmGqaKvFp8Op::setCacheRows: rows must be positive" );
+            if ( rows == rows_ ) return;
+            const shape_t s8{ rows, cfg_.num_kv_heads, capacity_, cfg_.head_dim }, ss{ rows, cfg_.num_kv_heads, capacity_ };
+            k8_ = std::make_unique<StorageTensor>( context_->getDeviceId(), s8 );
+            v8_ = std::make_unique<StorageTensor>( context_->getDeviceId(), s8 );
+            ks_ = std::make_unique<ScaleTensor>( context_->getDeviceId(), ss );
+            vs_ = std::make_unique<ScaleTensor>( context_->getDeviceId(), ss );
+            rows_ = rows; row_ = 0; length_ = 0;
+        }
+        void selectCacheRow( int b )
+        {
+            if ( b < 0 || b >= rows_ ) throw std::invalid_argument( "RocmGqaKvFp8Op::selectCacheRow: row " + std::to_string( b ) + " outside the " + std::to_string( rows_ ) + " cache rows" );
+            row_ = b;
+        }
+        int cacheRows() const noexcept { return rows_; }
         void resetKvCache() noexcept { length_ = 0; }
         void rewindKvCache( dim_t length )
         {
@@ -1034,10 +1057,10 @@ namespace Mila::Dnn::Compute
             requireCache();
             mila_stream_t st = context_->getStream();
             const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
-            rocmCheck( mila_cdna4_kv_write_fp8( k8_->data(), v8_->data(), ks_->data(), vs_->data(), q_cast( k ), q_cast( v ), batch_, chunk, NKV, HS, position, cap, st ) );
+            rocmCheck( mila_cdna4_kv_write_fp8( keyBytes(), valueBytes(), keyScaleData(), valueScaleData(), q_cast( k ), q_cast( v ), batch_, chunk, NKV, HS, position, cap, st ) );
             const size_t need = mila_cdna4_attn_prefill_kvfp8_scratch_bytes( batch_, NKV, HS, cap );
             void* scratch = context_->getScratch( need );   // fetched per call, never cached
-            rocmCheck( mila_cdna4_attn_prefill_kvfp8( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, chunk, NH, NKV, HS,
+            rocmCheck( mila_cdna4_attn_prefill_kvfp8( out.data(), q_cast( q ), keyBytes(), valueBytes(), keyScaleData(), valueScaleData(), scratch, need, batch_, chunk, NH, NKV, HS,
                                                       cap, position, (int)cfg_.window, scale(), st ) );
             length_ = position + chunk;
         }
@@ -1046,7 +1069,7 @@ namespace Mila::Dnn::Compute
         {
             requireCache();
             const int NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
-            rocmCheck( mila_cdna4_kv_write_fp8( k8_->data(), v8_->data(), ks_->data(), vs_->data(), q_cast( k ), q_cast( v ), batch_, 1, NKV, HS, position, cap,
+            rocmCheck( mila_cdna4_kv_write_fp8( keyBytes(), valueBytes(), keyScaleData(), valueScaleData(), q_cast( k ), q_cast( v ), batch_, 1, NKV, HS, position, cap,
                                                 context_->getStream() ) );
             attendDecode( q, out, position );
         }
@@ -1057,7 +1080,7 @@ namespace Mila::Dnn::Compute
             const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
             const size_t need = mila_cdna4_attn_decode_scratch_bytes( batch_, NH, HS );
             void* scratch = context_->getScratch( need );   // fetched per call, never cached
-            rocmCheck( mila_cdna4_attn_decode_kvfp8( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, NH, NKV, HS, cap,
+            rocmCheck( mila_cdna4_attn_decode_kvfp8( out.data(), q_cast( q ), keyBytes(), valueBytes(), keyScaleData(), valueScaleData(), scratch, need, batch_, NH, NKV, HS, cap,
                                                      position + 1, (int)cfg_.window, scale(), context_->getStream() ) );
             length_ = position + 1;
         }
@@ -1072,10 +1095,10 @@ namespace Mila::Dnn::Compute
             if ( !position_dev ) throw std::invalid_argument( "RocmGqaKvFp8Op::decodeAt: null device position" );
             mila_stream_t st = context_->getStream();
             const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
-            rocmCheck( mila_cdna4_kv_write_fp8_devpos( k8_->data(), v8_->data(), ks_->data(), vs_->data(), q_cast( k ), q_cast( v ), batch_, NKV, HS, position_dev, cap, st ) );
+            rocmCheck( mila_cdna4_kv_write_fp8_devpos( keyBytes(), valueBytes(), keyScaleData(), valueScaleData(), q_cast( k ), q_cast( v ), batch_, NKV, HS, position_dev, cap, st ) );
             const size_t need = mila_cdna4_attn_decode_scratch_bytes( batch_, NH, HS );
             void* scratch = context_->getScratch( need );   // fetched per call, never cached
-            rocmCheck( mila_cdna4_attn_decode_kvfp8_devpos( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, NH, NKV, HS, cap,
+            rocmCheck( mila_cdna4_attn_decode_kvfp8_devpos( out.data(), q_cast( q ), keyBytes(), valueBytes(), keyScaleData(), valueScaleData(), scratch, need, batch_, NH, NKV, HS, cap,
                                                             position_dev, max_len, (int)cfg_.window, scale(), st ) );
         }
 
@@ -1087,7 +1110,7 @@ namespace Mila::Dnn::Compute
             const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
             const size_t need = mila_cdna4_attn_prefill_kvfp8_scratch_bytes( batch_, NKV, HS, cap );
             void* scratch = context_->getScratch( need );   // fetched per call, never cached
-            rocmCheck( mila_cdna4_attn_prefill_kvfp8( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, chunk, NH, NKV, HS,
+            rocmCheck( mila_cdna4_attn_prefill_kvfp8( out.data(), q_cast( q ), keyBytes(), valueBytes(), keyScaleData(), valueScaleData(), scratch, need, batch_, chunk, NH, NKV, HS,
                                                       cap, position, (int)cfg_.window, scale(), context_->getStream() ) );
             length_ = position + chunk;
         }
@@ -1100,7 +1123,7 @@ namespace Mila::Dnn::Compute
             const int NH = (int)cfg_.num_heads, NKV = (int)cfg_.num_kv_heads, HS = (int)cfg_.head_dim, cap = (int)capacity_;
             const size_t need = mila_cdna4_attn_decode_scratch_bytes( batch_, NH, HS );
             void* scratch = context_->getScratch( need );   // fetched per call, never cached
-            rocmCheck( mila_cdna4_attn_decode_kvfp8_devpos( out.data(), q_cast( q ), k8_->data(), v8_->data(), ks_->data(), vs_->data(), scratch, need, batch_, NH, NKV, HS, cap,
+            rocmCheck( mila_cdna4_attn_decode_kvfp8_devpos( out.data(), q_cast( q ), keyBytes(), valueBytes(), keyScaleData(), valueScaleData(), scratch, need, batch_, NH, NKV, HS, cap,
                                                             position_dev, max_len, (int)cfg_.window, scale(), context_->getStream() ) );
         }
 
@@ -1109,22 +1132,31 @@ namespace Mila::Dnn::Compute
         uint16_t* keyCache() { throw std::logic_error( "RocmGqaKvFp8Op::keyCache: " + std::string( kFusedOnly ) ); }
         uint16_t* valueCache() { throw std::logic_error( "RocmGqaKvFp8Op::valueCache: " + std::string( kFusedOnly ) ); }
 
-        /// 2 * B * NKV * capacity * (HS + 4): one byte per element and one fp32 scale per row, K and V
+        /// 2 * rows * B * NKV * capacity * (HS + 4): one byte per element and one fp32 scale per cached token, K and V
         size_t stateBytes() const noexcept { return tensorBytes( k8_ ) + tensorBytes( v8_ ) + tensorBytes( ks_ ) + tensorBytes( vs_ ); }
+        /// (times the cache rows setCacheRows() asked for)
         size_t requiredStateBytes( int batch, dim_t max_seq, dim_t /*prefill_chunk*/ ) const
         {
-            return 2 * static_cast<size_t>( batch ) * static_cast<size_t>( cfg_.num_kv_heads ) * static_cast<size_t>( max_seq ) * ( static_cast<size_t>( cfg_.head_dim ) + 4 );
+            return 2 * static_cast<size_t>( rows_ ) * static_cast<size_t>( batch ) * static_cast<size_t>( cfg_.num_kv_heads ) * static_cast<size_t>( max_seq ) * ( static_cast<size_t>( cfg_.head_dim ) + 4 );
         }
-        /// the cache arrays (tests read them back): e4m3 bytes and fp32 scales
+        /// the cache arrays (tests read them back): e4m3 bytes and fp32 scales, all rows
         const StorageTensor* keyStorage() const noexcept { return k8_.get(); }
         const StorageTensor* valueStorage() const noexcept { return v8_.get(); }
         const ScaleTensor* keyScales() const noexcept { return ks_.get(); }
         const ScaleTensor* valueScales() const noexcept { return vs_.get(); }
-        /// ... and their device arrays, for the quantizing fused entries (fused_qkv_post_kvfp8*), which append through raw pointers; null before initializeKvCache()
-        uint8_t* keyBytes() noexcept { return k8_ ? static_cast<uint8_t*>( k8_->rawData() ) : nullptr; }
-        uint8_t* valueBytes() noexcept { return v8_ ? static_cast<uint8_t*>( v8_->rawData() ) : nullptr; }
-        float* keyScaleData() noexcept { return ks_ ? ks_->data() : nullptr; }
-        float* valueScaleData() noexcept { return vs_ ? vs_->data() : nullptr; }
+        /// where the selected row's slice starts in them: elements of the byte tensors | of the scale tensors (0 unless selectCacheRow() said otherwise)
+        size_t selectedRowByteOffset() const noexcept { return rowScales() * static_cast<size_t>( cfg_.head_dim ) * static_cast<size_t>( row_ ); }
+        size_t selectedRowScaleOffset() const noexcept { return rowScales() * static_cast<size_t>( row_ ); }
+        /// ... and the selected row's device arrays, for the quantizing fused entries (fused_qkv_post_kvfp8*), which append through raw pointers; null before initializeKvCache()
+        uint8_t* keyBytes() noexcept { return k8_ ? keyBytesRows() + selectedRowByteOffset() : nullptr; }
+        uint8_t* valueBytes() noexcept { return v8_ ? valueBytesRows() + selectedRowByteOffset() : nullptr; }
+        float* keyScaleData() noexcept { return ks_ ? keyScaleDataRows() + selectedRowScaleOffset() : nullptr; }
+        float* valueScaleData() noexcept { return vs_ ? valueScaleDataRows() + selectedRowScaleOffset() : nullptr; }
+        /// all rows: what the rows entries take
+        uint8_t* keyBytesRows() noexcept { return k8_ ? static_cast<uint8_t*>( k8_->rawData() ) : nullptr; }
+        uint8_t* valueBytesRows() noexcept { return v8_ ? static_cast<uint8_t*>( v8_->rawData() ) : nullptr; }
+        float* keyScaleDataRows() noexcept { return ks_ ? ks_->data() : nullptr; }
+        float* valueScaleDataRows() noexcept { return vs_ ? vs_->data() : nullptr; }
         const GqaOpConfig& config() const noexcept { return cfg_; }
 
     private:
@@ -1134,7 +1166,10 @@ namespace Mila::Dnn::Compute
         GqaOpConfig cfg_;
         std::unique_ptr<StorageTensor> k8_, v8_;
         std::unique_ptr<ScaleTensor> ks_, vs_;
+        /// scales (= cached K or V rows) of one cache row
+        size_t rowScales() const noexcept { return static_cast<size_t>( batch_ ) * static_cast<size_t>( cfg_.num_kv_heads ) * static_cast<size_t>( capacity_ ); }
         int batch_{ 1 };
+        int rows_{ 1 }, row_{ 0 };      ///< independent caches behind the op, and the one its B = 1 calls work on
         dim_t capacity_{ 0 }, length_{ 0 };
     };
     /// more specialised than the TKvPolicy row above; storage other than OCP e4m3 has no kernels

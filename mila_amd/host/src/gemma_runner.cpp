@@ -234,6 +234,40 @@ HOST_API int mila_gemma_validate_config( const mila_gemma_config* c, int64_t max
 {
     return guarded( [&] { GemmaConfig cfg = gemma_config_of( c ); cfg.max_batch = max_batch; cfg.draft_tokens = draft_tokens; cfg.validate(); } );
 }
+/// ... with GemmaConfig::kv_fp8_rows (kv_fp8_rows != 0): the FP8 KV cache that max_batch > 1 may be combined with.  mila_gemma_config itself is unchanged.
+HOST_API int mila_gemma_validate_config_kv( const mila_gemma_config* c, int64_t max_batch, int64_t draft_tokens, int kv_fp8_rows )
+{
+    return guarded( [&] { GemmaConfig cfg = gemma_config_of( c ); cfg.max_batch = max_batch; cfg.draft_tokens = draft_tokens; cfg.kv_fp8_rows = kv_fp8_rows != 0; cfg.validate(); } );
+}
+/// mila_gemma_create_rows with GemmaConfig::kv_fp8_rows: max_batch (1 .. 4) sequences per decode step, each on its own FP8 KV caches.  kv_fp8_rows = 0 builds the model
+/// mila_gemma_create_rows builds.
+HOST_API void* mila_gemma_create_rows_kv( int policy, const mila_gemma_config* c, int64_t max_seq, int64_t max_prefill, int64_t max_batch, int kv_fp8_rows, uint64_t seed, int device )
+{
+    Runner* r = nullptr;
+    int rc = guarded( [&]
+    {
+        GemmaConfig cfg = gemma_config_of( c );
+        cfg.max_batch = max_batch;
+        cfg.kv_fp8_rows = kv_fp8_rows != 0;
+        auto rr = std::make_unique<Runner>();
+        rr->max_prefill = max_prefill;
+        switch ( policy )
+        {
+            case 0: rr->model = std::make_unique<GemmaTransformer<NoWeightQuant>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            case 1: rr->model = std::make_unique<GemmaTransformer<PerChannelFp8<>>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            case 2: rr->model = std::make_unique<GemmaTransformer<PerGroupFp4<128>>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            default: throw std::invalid_argument( "unknown weight policy" );
+        }
+        std::visit( [&]( auto& m )
+        {
+            m->initSynthetic( seed );
+            rr->tokens = std::make_unique<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>>(
+                m->context()->getDeviceId(), shape_t{ std::max<dim_t>( max_prefill, 1 ) } );
+        }, rr->model );
+        r = rr.release();
+    } );
+    return rc == 0 ? r : nullptr;
+}
 /// promptLookupDraft (GemmaModel.h), the default drafter of the speculative generate(): up to k tokens into out, returns their number.  Pure host code.
 HOST_API int mila_gemma_prompt_lookup_draft( const int32_t* history, int64_t n, int k, int32_t* out )
 {
@@ -1665,6 +1699,22 @@ HOST_API void* mila_gemma_model_synthetic_rows( int policy, const mila_gemma_con
         GemmaTransformer<NoWeightQuant>::SyntheticProfile pr;
         if ( p ) { pr.linear_gain = p[ 0 ]; pr.qk_norm_center = p[ 1 ]; pr.post_norm_center = p[ 2 ]; pr.layer_scalar = p[ 3 ]; pr.table_gain = p[ 4 ]; }
         m = RocmGemmaModel::fromSynthetic( cfg, model_config_of( policy, context, prefill_chunk, bounded, kv_fp8 ).withMaxBatch( max_batch ), seed, pr, Compute::Device::Rocm( device ) ).release();
+    } );
+    return rc == 0 ? m : nullptr;
+}
+
+/// mila_gemma_model_synthetic_rows with GemmaModelConfig::withKvFp8Rows( kv_fp8_rows != 0 ): the rows model over FP8 KV caches
+HOST_API void* mila_gemma_model_synthetic_rows_kv( int policy, const mila_gemma_config* c, int64_t context, int64_t prefill_chunk, int64_t max_batch, int kv_fp8_rows, uint64_t seed,
+                                                   const float* p, int device )
+{
+    RocmGemmaModel* m = nullptr;
+    int rc = guarded( [&]
+    {
+        GemmaConfig cfg = gemma_config_of( c );
+        GemmaTransformer<NoWeightQuant>::SyntheticProfile pr;
+        if ( p ) { pr.linear_gain = p[ 0 ]; pr.qk_norm_center = p[ 1 ]; pr.post_norm_center = p[ 2 ]; pr.layer_scalar = p[ 3 ]; pr.table_gain = p[ 4 ]; }
+        m = RocmGemmaModel::fromSynthetic( cfg, model_config_of( policy, context, prefill_chunk, cfg.bounded_local_kv, cfg.kv_fp8 ).withMaxBatch( max_batch ).withKvFp8Rows( kv_fp8_rows != 0 ),
+                                           seed, pr, Compute::Device::Rocm( device ) ).release();
     } );
     return rc == 0 ? m : nullptr;
 }
