@@ -1145,6 +1145,23 @@ typedef struct mila_kv_fork_layer_fp8 {
 } mila_kv_fork_layer_fp8;
 MILA_API int mila_cdna4_kv_rows_fork_layers_kvfp8(const mila_kv_fork_layer_fp8* layers, int n_layers, int rows, int src, unsigned dst_mask, int len, mila_stream_t stream);
 
+/* kv_rows_fork_layers_bf16 for a rows model whose sliding-window layers sit on RINGS (ABI 4, additive; csrc/kv_rows_fork.hip): position p of a row lives at cache index
+ * p % capacity of its layer.  Per layer the entry copies the LIVE BAND, positions [begin, len) with begin = window > 0 ? max( 0, len - window ) : 0 -- what a continuation
+ * from `len` can read (a flat layer, window 0, is the whole prefix [0, len)) -- of cache row `src` into every row of dst_mask, for every KV head, K and V.  A band that
+ * crosses the ring's end is two runs of cache indices; the kernel folds a unit past the end back with one conditional subtract, the one remainder (begin % capacity) is
+ * taken on the host.  Bitwise; nothing is written outside the band's cache indices of the named rows, nothing in `src`.  The interface is otherwise the bf16 entry's: a
+ * HOST array passed by value in the kernel arguments, the layer in the grid's y index, up to 64 layers per launch, each unit read once, 16 bytes per lane, 64-bit offsets.
+ * Refused before any device work, with the layer's number in the message where one is at fault: the bf16 entry's refusals, except that len may exceed a capacity; a
+ * window < 0; a band len - begin above the layer's capacity (a flat layer with len > capacity, a ring whose window exceeds its capacity). */
+typedef struct mila_kv_fork_layer_band {
+    uint16_t* K;            /* [rows, NKV, capacity, HS] bf16, device */
+    uint16_t* V;
+    int32_t NKV, capacity, HS;
+    int32_t window;         /* > 0: a ring layer's sliding window; 0: a flat layer, the whole prefix */
+} mila_kv_fork_layer_band;
+MILA_API int mila_cdna4_kv_rows_fork_layers_band_bf16(const mila_kv_fork_layer_band* layers, int n_layers, int rows, int src, unsigned dst_mask, int len,
+                                                      mila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,11 @@ class KvForkLayerFp8(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class KvForkLayerBand(C.Structure):
+    """mila_kv_fork_layer_band: one layer's record for kv_rows_fork_layers_band_bf16 (window > 0: a ring layer; 0: a flat one)"""
+    _fields_ = [("K", C.c_void_p), ("V", C.c_void_p), ("NKV", C.c_int32), ("capacity", C.c_int32), ("HS", C.c_int32), ("window", C.c_int32)]
+
+
 _lib = None
 EXPERIMENTS_PATH = os.path.join(_HERE, "lib", "libmila_cdna4_experiments.so")
 
@@ -169,6 +174,7 @@ def load():
     main.mila_cdna4_kv_rows_fork_bf16.argtypes = [p, p, i, i, i, i, i, i, i, p]                                   # K V | rows NKV capacity HS | src dst_mask len
     main.mila_cdna4_kv_rows_fork_layers_bf16.argtypes = [p, i, i, i, i, i, p]                                     # layers (host records) n_layers | rows src dst_mask len
     main.mila_cdna4_kv_rows_fork_layers_kvfp8.argtypes = [p, i, i, i, i, i, p]                                    # layers (host fp8 records) n_layers | rows src dst_mask len
+    main.mila_cdna4_kv_rows_fork_layers_band_bf16.argtypes = [p, i, i, i, i, i, p]                                # layers (host band records) n_layers | rows src dst_mask len
     # token log-probabilities (csrc/logprobs.hip)
     main.mila_cdna4_token_logprobs_scratch_bytes.argtypes = [i, i, i]                                             # rows vocab top_n
     main.mila_cdna4_token_logprobs_scratch_bytes.restype = z
@@ -837,6 +843,7 @@ EXPORTED = [
     "token_automaton_rows_bytes", "token_automaton_rows_set", "token_automaton_rows_compose", "token_automaton_rows_step",
     "kv_rows_fork_bf16", "kv_rows_fork_layers_bf16",
     "fused_qkv_post_kvfp8_rows_devpos", "attn_decode_kvfp8_rows", "kv_rows_fork_layers_kvfp8",
+    "kv_rows_fork_layers_band_bf16",
 ]
 
 # csrc/internal.h: test / tuning hooks and the measured-slower experiments -- exported, but not part of the drop-in ABI

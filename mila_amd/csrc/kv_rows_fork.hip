@@ -107,6 +107,38 @@ __global__ __launch_bounds__(kForkThreads) void kv_rows_fork_layers_kvfp8_kernel
     }
 }
 
+// The LIVE BAND of every layer in one launch (kv_rows_fork_layers_band_bf16): a rows model whose sliding-window layers sit on rings (GemmaConfig::bounded_local_kv_rows).
+// Position p lives at cache index p % capacity, and a continuation from `len` reads no further back than len - window, so a layer's copy is positions [begin, len),
+// begin = window > 0 ? max( 0, len - window ) : 0 -- a flat layer (window 0) is the whole prefix, as above.  Per (K | V, head) that is band * HS / 8 16-byte units that
+// start at cache index begin % capacity and may run over the ring's end once (band <= capacity): unit u sits at start_elems + u * 8, less head_elems when that passes the
+// head's end -- one conditional subtract per unit, no remainder in the walk.  Otherwise the walk of the layers kernel above: read once, stored to every destination row.
+struct ForkLayerBand { uint16_t* K; uint16_t* V; int64_t seg_units, head_elems, start_elems; int32_t NKV, pad; };      // seg_units = band * HS / 8, head_elems = capacity * HS, start_elems = (begin % capacity) * HS
+constexpr int kForkLayersBandPerLaunch = 64;      // 64 x 48 bytes of records: 3 KiB of the 4 KiB argument block
+struct ForkLayersBand { ForkLayerBand l[kForkLayersBandPerLaunch]; };
+
+__global__ __launch_bounds__(kForkThreads) void kv_rows_fork_layers_band_bf16_kernel(const ForkLayersBand layers, int src, unsigned dst_mask, int rows)
+{
+    const ForkLayerBand& L = layers.l[blockIdx.y];
+    uint16_t* const K = L.K;
+    uint16_t* const V = L.V;
+    const int64_t seg_units = L.seg_units, head_elems = L.head_elems, start_elems = L.start_elems;
+    const int64_t cache_units = (int64_t)L.NKV * seg_units, total_units = 2 * cache_units, row_elems = (int64_t)L.NKV * head_elems;
+    const int64_t stride = (int64_t)gridDim.x * kForkThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kForkThreads + threadIdx.x; i < total_units; i += stride)
+    {
+        const bool value = i >= cache_units;
+        const int64_t c = value ? i - cache_units : i;
+        const int64_t head = c / seg_units, u = c - head * seg_units;
+        uint16_t* base = value ? V : K;
+        int64_t in_head = start_elems + u * 8;      // < 2 * head_elems: start_elems < head_elems, u * 8 < band * HS <= capacity * HS
+        if (in_head >= head_elems) in_head -= head_elems;      // the band's second run, from the ring's first index
+        const int64_t in_row = head * head_elems + in_head;      // < row_elems: head < NKV, in_head < head_elems
+        const u32x4 bits = ld16(base + (int64_t)src * row_elems + in_row);
+        for (int r = 0; r < rows; ++r)
+            if ((dst_mask >> r) & 1u) st16(base + (int64_t)r * row_elems + in_row, bits);
+    }
+}
+
 }  // namespace mila
 
 using namespace mila;
@@ -173,6 +205,54 @@ int mila_cdna4_kv_rows_fork_layers_bf16(const mila_kv_fork_layer* layers, int n_
                            dst_mask, rows);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return ::mila::check_hip(e, "kv_rows_fork_layers_bf16");
+    }
+    return MILA_OK;
+}
+
+int mila_cdna4_kv_rows_fork_layers_band_bf16(const mila_kv_fork_layer_band* layers, int n_layers, int rows, int src, unsigned dst_mask, int len, mila_stream_t stream)
+{
+    MILA_REQUIRE(layers, "kv_rows_fork_layers_band_bf16: null layer table");
+    MILA_REQUIRE(n_layers > 0, "kv_rows_fork_layers_band_bf16: n_layers=%d must be positive", n_layers);
+    MILA_REQUIRE(rows >= 2 && rows <= 4, "kv_rows_fork_layers_band_bf16: rows=%d out of range (2 .. 4)", rows);
+    MILA_REQUIRE(src >= 0 && src < rows, "kv_rows_fork_layers_band_bf16: src=%d outside the %d rows", src, rows);
+    MILA_REQUIRE(dst_mask != 0, "kv_rows_fork_layers_band_bf16: empty dst_mask");
+    MILA_REQUIRE((dst_mask >> rows) == 0, "kv_rows_fork_layers_band_bf16: dst_mask=0x%x names a row outside the %d rows", dst_mask, rows);
+    MILA_REQUIRE(((dst_mask >> src) & 1u) == 0, "kv_rows_fork_layers_band_bf16: dst_mask=0x%x names the source row %d", dst_mask, src);
+    MILA_REQUIRE(len >= 1, "kv_rows_fork_layers_band_bf16: len=%d must be positive", len);
+    for (int i = 0; i < n_layers; ++i)      // every layer before the first launch: a refusal leaves every cache as it was
+    {
+        const mila_kv_fork_layer_band& L = layers[i];
+        MILA_REQUIRE(L.K && L.V, "kv_rows_fork_layers_band_bf16: layer %d: null pointer", i);
+        MILA_REQUIRE(L.NKV > 0 && L.capacity > 0 && L.HS > 0, "kv_rows_fork_layers_band_bf16: layer %d: bad sizes (NKV=%d capacity=%d HS=%d)", i, L.NKV, L.capacity, L.HS);
+        MILA_REQUIRE(L.HS % 8 == 0, "kv_rows_fork_layers_band_bf16: layer %d: HS=%d must be a multiple of 8", i, L.HS);
+        MILA_REQUIRE(L.window >= 0, "kv_rows_fork_layers_band_bf16: layer %d: window=%d must not be negative", i, L.window);
+        const int begin = L.window > 0 && len > L.window ? len - L.window : 0;
+        MILA_REQUIRE(len - begin <= L.capacity, "kv_rows_fork_layers_band_bf16: layer %d: band=%d of len=%d (window %d) above capacity %d", i, len - begin, len, L.window, L.capacity);
+        MILA_REQUIRE(((reinterpret_cast<uintptr_t>(L.K) | reinterpret_cast<uintptr_t>(L.V)) & 15) == 0, "kv_rows_fork_layers_band_bf16: layer %d: K and V must be 16-byte aligned", i);
+    }
+    for (int first = 0; first < n_layers; first += kForkLayersBandPerLaunch)
+    {
+        const int n = n_layers - first < kForkLayersBandPerLaunch ? n_layers - first : kForkLayersBandPerLaunch;
+        ForkLayersBand args{};
+        int64_t most = 0;      // the longest layer's units size the grid's x; a shorter layer's spare blocks fall through their loop
+        for (int i = 0; i < n; ++i)
+        {
+            const mila_kv_fork_layer_band& L = layers[first + i];
+            ForkLayerBand& a = args.l[i];
+            const int begin = L.window > 0 && len > L.window ? len - L.window : 0;
+            a.K = L.K; a.V = L.V; a.NKV = L.NKV;
+            a.seg_units = (int64_t)(len - begin) * (L.HS / 8);
+            a.head_elems = (int64_t)L.capacity * L.HS;
+            a.start_elems = (int64_t)(begin % L.capacity) * L.HS;      // the one remainder of the call, on the host
+            const int64_t total_units = 2 * (int64_t)L.NKV * a.seg_units;
+            most = total_units > most ? total_units : most;
+        }
+        const int64_t blocks = (most + kForkThreads - 1) / kForkThreads;
+        const int64_t cap = kForkMaxBlocks / n > kForkLayersMinBlocks ? kForkMaxBlocks / n : kForkLayersMinBlocks;      // the grid cap of the one-layer kernel, shared by the layers
+        hipLaunchKernelGGL(kv_rows_fork_layers_band_bf16_kernel, dim3((unsigned)(blocks < cap ? blocks : cap), (unsigned)n), dim3(kForkThreads), 0, as_stream(stream), args, src,
+                           dst_mask, rows);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return ::mila::check_hip(e, "kv_rows_fork_layers_band_bf16");
     }
     return MILA_OK;
 }

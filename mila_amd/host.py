@@ -266,7 +266,7 @@ class Gemma:
     MODES = {"reference": 0, "fused": 1, "graph": 2}
 
     def __init__(self, policy="bf16", config=None, max_seq=4096, max_prefill=1, seed=1234, device=None, profile=None, kv_fp8=False, max_batch=None, draft_tokens=None,
-                 kv_fp8_rows=False):
+                 kv_fp8_rows=False, bounded_local_kv_rows=False):
         """device: HIP device ordinal; default = this process's LOCAL_RANK (one replica per GPU under torch.distributed.run).
         profile: synthetic-parameter multipliers {linear_gain, qk_norm_center, post_norm_center, layer_scalar, table_gain}
         (GemmaTransformer::SyntheticProfile; None = the unit-scale generator of SURVEY.md section 8d)
@@ -276,7 +276,9 @@ class Gemma:
         draft_tokens: GemmaConfig::draft_tokens (0 .. 3) through mila_gemma_create_chain -- the chain step (decode_chain) verifies that many drafted tokens; 0 builds
         the plain model through the same entry; None = not through that entry
         kv_fp8_rows: GemmaConfig::kv_fp8_rows through mila_gemma_create_rows_kv -- the FP8 KV cache (implied) on a model of max_batch 1 .. 4, one cache per row; plain
-        kv_fp8 with max_batch > 1 stays refused"""
+        kv_fp8 with max_batch > 1 stays refused
+        bounded_local_kv_rows: GemmaConfig::bounded_local_kv_rows through mila_gemma_create_rows_ring -- rings (bounded_local_kv, implied) on the sliding-window layers
+        of a model of max_batch 1 .. 4, one ring per row, forks of the live band; plain bounded_local_kv with max_batch > 1 stays refused"""
         lib = load()
         if device is None:
             from .replicas import local_device
@@ -292,7 +294,16 @@ class Gemma:
         self.max_batch = 1 if max_batch is None else int(max_batch)
         self.draft_tokens = 0 if draft_tokens is None else int(draft_tokens)
         self.kv_fp8_rows = bool(kv_fp8_rows)
-        if kv_fp8_rows:
+        self.bounded_local_kv_rows = bool(bounded_local_kv_rows)
+        if bounded_local_kv_rows:
+            if kv_fp8_rows or self.cfg["kv_fp8"]:
+                raise ValueError("Gemma: bounded_local_kv_rows cannot be combined with kv_fp8 / kv_fp8_rows (FP8 rings are not built)")
+            if draft_tokens:
+                raise ValueError("Gemma: draft_tokens cannot be combined with bounded_local_kv_rows (the chain over rings is not built)")
+            lib.mila_gemma_create_rows_ring.restype = C.c_void_p
+            lib.mila_gemma_create_rows_ring.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_int]
+            self.h = lib.mila_gemma_create_rows_ring(POLICIES[policy], C.byref(c), max_seq, max_prefill, self.max_batch, 1, seed, device)
+        elif kv_fp8_rows:
             if draft_tokens:
                 raise ValueError("Gemma: draft_tokens cannot be combined with kv_fp8_rows (the chain over the FP8 KV cache is not built)")
             lib.mila_gemma_create_rows_kv.restype = C.c_void_p
@@ -606,6 +617,15 @@ class Gemma:
         lib.mila_gemma_reset_row.argtypes = [C.c_void_p, C.c_int]
         _check(lib.mila_gemma_reset_row(self.h, int(b)))
 
+    def rewind_row(self, b, position, written):
+        """GemmaTransformer::rewindKvCacheRow: row b goes on from `position`, given that `written` positions were appended to it -> True; False when it is out of
+        range or, on a bounded_local_kv_rows model, when the row's rings no longer hold what a continuation from `position` reads (nothing changed: prefill from 0)"""
+        lib = load()
+        lib.mila_gemma_rewind_row.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+        ok = C.c_int(0)
+        _check(lib.mila_gemma_rewind_row(self.h, int(b), int(position), int(written), C.byref(ok)))
+        return bool(ok.value)
+
     def fork_row(self, src, dst_mask, length):
         """GemmaTransformer::forkRow: a shared prefill -- directly behind prefill_row(src, tokens of `length`), row src's cache prefix [0, length) of every layer, its
         logits and its position into the rows of dst_mask (bit r = row r)"""
@@ -845,8 +865,9 @@ class Gemma:
         return {"decode_bytes_per_token": out[0], "weight_bytes": out[1], "linear_params": out[2], "table_params": out[3]}
 
 
-def validate_gemma_config(config=None, max_batch=1, draft_tokens=0, kv_fp8=False, kv_fp8_rows=False):
-    """GemmaConfig::validate() on the configuration Gemma(..., max_batch=, draft_tokens=, kv_fp8_rows=) would build, without a device: raises ValueError with its message"""
+def validate_gemma_config(config=None, max_batch=1, draft_tokens=0, kv_fp8=False, kv_fp8_rows=False, bounded_local_kv_rows=False):
+    """GemmaConfig::validate() on the configuration Gemma(..., max_batch=, draft_tokens=, kv_fp8_rows=, bounded_local_kv_rows=) would build, without a device: raises
+    ValueError with its message"""
     lib = load()
     lib.mila_gemma_validate_config.argtypes = [C.POINTER(GemmaConfigC), C.c_int64, C.c_int64]
     lib.mila_gemma_validate_config_kv.argtypes = [C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int]
@@ -856,6 +877,10 @@ def validate_gemma_config(config=None, max_batch=1, draft_tokens=0, kv_fp8=False
     if kv_fp8:
         cfg["kv_fp8"] = 1
     c = GemmaConfigC(**cfg)
+    if bounded_local_kv_rows:
+        lib.mila_gemma_validate_config_ring.argtypes = [C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int, C.c_int]
+        _check(lib.mila_gemma_validate_config_ring(C.byref(c), int(max_batch), int(draft_tokens), int(bool(kv_fp8_rows)), 1))
+        return
     if kv_fp8_rows:
         _check(lib.mila_gemma_validate_config_kv(C.byref(c), int(max_batch), int(draft_tokens), 1))
         return
@@ -912,9 +937,11 @@ class GemmaModel:
 
     @classmethod
     def synthetic(cls, policy="bf16", config=None, context=4096, prefill_chunk=0, seed=1234, profile=None, device=0, kv_fp8=False, max_batch=None, draft_tokens=None,
-                  kv_fp8_rows=False):
+                  kv_fp8_rows=False, bounded_local_kv_rows=False):
         """kv_fp8_rows: GemmaModelConfig::withKvFp8Rows -- the FP8 KV cache (implied) on a model of max_batch 1 .. 4 (generate_batch / generate_requests / serve_requests
-        over FP8 rows); plain kv_fp8 with max_batch > 1 stays refused"""
+        over FP8 rows); plain kv_fp8 with max_batch > 1 stays refused
+        bounded_local_kv_rows: GemmaModelConfig::withBoundedLocalKvRows -- rings (bounded_local_kv, implied) on the sliding-window layers of a model of max_batch 1 .. 4:
+        the same calls over rows that keep window + prefill_chunk - 1 positions per sliding-window layer; plain bounded_local_kv with max_batch > 1 stays refused"""
         lib = cls._bind()
         cfg = dict(GEMMA4_12B if config is None else config)
         cfg.setdefault("bounded_local_kv", 0)
@@ -925,7 +952,15 @@ class GemmaModel:
         p = None
         if profile is not None:
             p = (C.c_float * 5)(*[float(profile[k]) for k in ("linear_gain", "qk_norm_center", "post_norm_center", "layer_scalar", "table_gain")])
-        if kv_fp8_rows:
+        if bounded_local_kv_rows:
+            if kv_fp8_rows or cfg["kv_fp8"]:
+                raise ValueError("GemmaModel.synthetic: bounded_local_kv_rows cannot be combined with kv_fp8 / kv_fp8_rows")
+            if draft_tokens:
+                raise ValueError("GemmaModel.synthetic: draft_tokens cannot be combined with bounded_local_kv_rows")
+            lib.mila_gemma_model_synthetic_rows_ring.restype = C.c_void_p
+            lib.mila_gemma_model_synthetic_rows_ring.argtypes = [C.c_int, C.POINTER(GemmaConfigC), C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_void_p, C.c_int]
+            h = lib.mila_gemma_model_synthetic_rows_ring(POLICIES[policy], C.byref(c), context, prefill_chunk, 1 if max_batch is None else int(max_batch), 1, seed, p, device)
+        elif kv_fp8_rows:
             if draft_tokens:
                 raise ValueError("GemmaModel.synthetic: draft_tokens cannot be combined with kv_fp8_rows")
             lib.mila_gemma_model_synthetic_rows_kv.restype = C.c_void_p

@@ -39,6 +39,7 @@ namespace Mila::Dnn
         bool bounded_local_kv = false;   ///< SlidingWindowKvCache on the sliding-window layers (ring of window + chunk - 1 rows)
         bool kv_fp8 = false;             ///< PerChannelKvFp8<> on every layer: e4m3 K / V + one fp32 scale per KV head per cached token, (HS + 4) / (2 HS) of the bf16 bytes
         bool kv_fp8_rows = false;        ///< kv_fp8 (implied) that max_batch > 1 may be combined with: one FP8 KV cache per row, the rows step on the FP8 rows entries (two launches per layer)
+        bool bounded_local_kv_rows = false;   ///< bounded_local_kv (implied) that max_batch > 1 may be combined with: one ring per row on the sliding-window layers, forks of the live band, a valid-from bound per row
         dim_t max_batch = 1;             ///< independent sequences a decode step can carry (1 .. 4): KV caches, decode buffers, logits and position words per row
         dim_t draft_tokens = 0;          ///< drafted tokens a chain step can verify (0 .. 3): the rows decode buffers for draft_tokens + 1 rows on the ONE cache, no extra caches
 
@@ -51,6 +52,7 @@ namespace Mila::Dnn
         dim_t windowFor( bool g ) const { return g ? 0 : window; }
         float embeddingScale() const { return std::sqrt( static_cast<float>( embedding_dim ) ); }
         bool kvFp8() const noexcept { return kv_fp8 || kv_fp8_rows; }      // the FP8 KV cache on every layer, by either switch
+        bool boundedLocalKv() const noexcept { return bounded_local_kv || bounded_local_kv_rows; }      // rings on the sliding-window layers, by either switch
 
         void validate() const
         {
@@ -63,7 +65,14 @@ namespace Mila::Dnn
             if ( max_batch < 1 || max_batch > 4 )
                 throw std::invalid_argument( "GemmaConfig: max_batch " + std::to_string( max_batch ) + " outside 1 .. 4 (the rows kernels keep every row's x in LDS)" );
             if ( max_batch > 1 && kv_fp8 && !kv_fp8_rows ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with kv_fp8 (the FP8 KV cache's fused append is B = 1)" );
-            if ( max_batch > 1 && bounded_local_kv ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with bounded_local_kv (the ring needs a rewind rule per row)" );
+            if ( max_batch > 1 && bounded_local_kv && !bounded_local_kv_rows ) throw std::invalid_argument( "GemmaConfig: max_batch > 1 cannot be combined with bounded_local_kv (the ring needs a rewind rule per row)" );
+            if ( bounded_local_kv_rows )
+            {
+                if ( kvFp8() ) throw std::invalid_argument( "GemmaConfig: bounded_local_kv_rows cannot be combined with kv_fp8 (the FP8 KV cache is unbounded; FP8 rings are not built)" );
+                if ( draft_tokens > 0 )
+                    throw std::invalid_argument( "GemmaConfig: bounded_local_kv_rows cannot be combined with draft_tokens > 0 (rejected drafts leave stale rows, and a ring may already have evicted what they overwrote)" );
+                if ( window <= 0 ) throw std::invalid_argument( "GemmaConfig: bounded_local_kv_rows needs a sliding window (window " + std::to_string( window ) + ")" );
+            }
             if ( draft_tokens < 0 || draft_tokens > 3 )
                 throw std::invalid_argument( "GemmaConfig: draft_tokens " + std::to_string( draft_tokens ) + " outside 0 .. 3 (a chain step is the last token plus the drafts: at most the four rows of the rows kernels)" );
             if ( draft_tokens > 0 )
@@ -155,6 +164,7 @@ namespace Mila::Dnn
         {
             cfg_.validate();
             if ( cfg_.kv_fp8_rows ) cfg_.kv_fp8 = true;      // the rows switch implies the cache policy; at max_batch 1 this IS the kv_fp8 model
+            if ( cfg_.bounded_local_kv_rows ) cfg_.bounded_local_kv = true;      // likewise: at max_batch 1 this IS the bounded_local_kv model
             if ( max_seq <= 0 ) throw std::invalid_argument( "GemmaTransformer: max_seq must be positive" );
             owned_ctx_ = Compute::createExecutionContext( device );
             ctx_ = Compute::cast_context<kDevice>( owned_ctx_.get() );
@@ -570,13 +580,24 @@ namespace Mila::Dnn
         // either cache: a row's state beside its caches is its position word, its token and its logits.
         // ------------------------------------------------------------------------------------
         dim_t maxBatch() const noexcept { return cfg_.max_batch; }
+        /// the capacity of the sliding-window layers' rings on a rows model built with GemmaConfig::bounded_local_kv_rows (0: every row on flat caches) -- with
+        /// config().window the geometry PrefixCache takes
+        dim_t rowsRingCapacity() const noexcept { return ring_capacity_; }
         /// prefill `n` tokens at positions offset .. into row b's caches through the B = 1 prefill (cache-row selection; no prefill kernel knows about rows); row b's
         /// logits and position word follow.  The row's first decode token is the caller's to set (setRowToken).
         LogitsTensor& prefillRow( int b, const TokenTensor& tokens, dim_t n, dim_t offset = 0 )
         {
             requireRows( b );
-            for ( auto& L : layers_ ) L.selectCacheRow( b );
             if ( n <= 0 ) throw std::invalid_argument( "GemmaTransformer::prefillRow: empty prompt" );
+            if ( ringRows() )      // (before the first chunk writes: a prefill that throws half way has still written)
+            {
+                if ( offset == 0 ) row_high_[ static_cast<size_t>( b ) ] = row_from_[ static_cast<size_t>( b ) ] = 0;
+                else if ( !rowHolds( b, offset ) )
+                    throw std::invalid_argument( "GemmaTransformer::prefillRow: row " + std::to_string( b ) + "'s rings no longer hold what a continuation from " + std::to_string( offset ) +
+                                                 " reads (valid from " + std::to_string( rowValidFrom( b ) ) + ", window " + std::to_string( cfg_.window ) + ")" );
+                row_high_[ static_cast<size_t>( b ) ] = std::max( row_high_[ static_cast<size_t>( b ) ], offset + n );
+            }
+            for ( auto& L : layers_ ) L.selectCacheRow( b );
             try
             {
                 for ( dim_t p0 = 0; p0 < n; p0 += max_prefill_ )      // chunks of the built prefill size, as prefillFrom() does
@@ -594,11 +615,18 @@ namespace Mila::Dnn
         /// forget row b: position 0, inactive (its caches are overwritten positionally by the next prefillRow)
         void resetRow( int b ) { requireRows( b ); setRowWord( rows_->pos->data(), b, 0 ); setRowWord( rows_->active->data(), b, 0 ); noteRowActive( b, false ); }
         /// rewindKvCache for one row: row b goes on from `position`, given that `written` positions were appended to it; its caches are overwritten positionally.
-        /// false when the request is out of range (rows live on unbounded caches: no ring to refuse)
+        /// false when the request is out of range; on a ring model (bounded_local_kv_rows) also by the ring rule of RocmGqaOpBase::rewindKvCache, per row: when
+        /// written - position > capacity - window, or when the row's valid-from bound (a band fork's, or the furthest the row was ever written less the capacity) lies
+        /// above position - window.  A refused row is prefilled from 0, which overwrites positionally.
         bool rewindKvCacheRow( int b, dim_t position, dim_t written )
         {
             requireRows( b );
             if ( position < 0 || position > written || written > max_seq_ ) return false;
+            if ( ringRows() )
+            {
+                row_high_[ static_cast<size_t>( b ) ] = std::max( row_high_[ static_cast<size_t>( b ) ], written );
+                if ( written - position > ring_capacity_ - cfg_.window || !rowHolds( b, position ) ) return false;
+            }
             setRowWord( rows_->pos->data(), b, static_cast<int32_t>( position ) );
             return true;
         }
@@ -800,6 +828,10 @@ namespace Mila::Dnn
         /// layer's cache prefix [0, len) (one kv_rows_fork_layers_bf16 launch for all layers), the row's logits and the position word.  Afterwards a destination row is in
         /// exactly the state prefillRow( dst, the same tokens ) would have left it in: the same cache bits, logits bits and position.  Throws invalid_argument when
         /// row src's position word is not len (it was not prefilled with len tokens, or it has stepped: its logits are no longer the prefill's).
+        /// On a ring model (GemmaConfig::bounded_local_kv_rows) the copy is every layer's LIVE BAND (one kv_rows_fork_layers_band_bf16 launch): afterwards a destination
+        /// row holds, on every layer, the bits of every position a continuation from len can read -- [max( 0, len - window ), len) on the ring layers, [0, len) on the
+        /// flat ones -- plus the logits and the position word; everything outside the band in the destination rows is left as it was, and the row's valid-from bound is
+        /// max( 0, len - window + 1 ): beyond the window it cannot donate a shorter prefix, nor be rewound below len.
         void forkRow( int src, unsigned dst_mask, dim_t len )
         {
             requireRows( src );
@@ -825,7 +857,9 @@ namespace Mila::Dnn
         /// prefillRow( dst, suffix, n - len, len ) that follows sets both.  Row src may be live, retired, and may have stepped: whatever sits at [0, len) of its
         /// caches is copied, and it must be at a position >= len (below it the caches hold nothing the row ever wrote).  One kv_rows_fork_layers_bf16 launch for all
         /// layers.  Refused (invalid_argument) before anything is enqueued: a one-row model, a mask that is empty, names src or a row outside the model, len < 1 or
-        /// beyond the context; then the row's position word is read, and a len beyond it is refused as well.
+        /// beyond the context; then the row's position word is read, and a len beyond it is refused as well.  On a ring model: the live band, as forkRow; refused as
+        /// well is a len whose band the donor has already overwritten -- donor position - len > capacity - window, or a donor whose own valid-from bound lies above
+        /// len - window (the rewind rule).
         void forkRowPrefix( int src, unsigned dst_mask, dim_t len )
         {
             if ( !rows_ || cfg_.max_batch <= 1 ) throw std::invalid_argument( "GemmaTransformer::forkRowPrefix: the model was built for one sequence (GemmaConfig::max_batch > 1)" );
@@ -838,6 +872,14 @@ namespace Mila::Dnn
             ctx_->synchronize();
             if ( static_cast<int32_t>( len ) > at )
                 throw std::invalid_argument( "GemmaTransformer::forkRowPrefix: len " + std::to_string( len ) + " beyond row " + std::to_string( src ) + "'s position " + std::to_string( at ) );
+            if ( ringRows() )      // the rewind rule, on the donor: its writes up to `at` (and whatever came before a cut) must not have reused the band's cells
+            {
+                row_high_[ static_cast<size_t>( src ) ] = std::max<dim_t>( row_high_[ static_cast<size_t>( src ) ], at );
+                if ( at - len > ring_capacity_ - cfg_.window || !rowHolds( src, len ) )
+                    throw std::invalid_argument( "GemmaTransformer::forkRowPrefix: row " + std::to_string( src ) + " at position " + std::to_string( at ) + " (valid from " +
+                                                 std::to_string( rowValidFrom( src ) ) + ") no longer holds the band of len " + std::to_string( len ) + " (ring capacity " +
+                                                 std::to_string( ring_capacity_ ) + ", window " + std::to_string( cfg_.window ) + ")" );
+            }
             forkLayers( src, dst_mask, len );
         }
         void clearRowsRequests() noexcept { row_requests_.clear(); row_request_vacant_.clear(); row_request_draws_ = nullptr; }
@@ -1711,7 +1753,8 @@ namespace Mila::Dnn
                     Compute::rocmCheck( mila_cdna4_fused_attn_decode_rows_bf16( R.attn->data(), L.keyCacheRows(), L.valueCacheRows(), qp, kp, vp, (int64_t)PK, L.q_norm->getWeight()->data(),
                                                                                 L.k_norm->getWeight()->data(), L.v_norm->getWeight()->data(), L.rope->cosCache(), L.rope->sinCache(),
                                                                                 R.attn_partials->data(), R.attn_partials->sizeInBytes(), B, NH, NKV, HD, (int)L.cacheCapacity(), R.pos->data(),
-                                                                                max_len, (int)cfg_.windowFor( g ), L.attentionScale(), cfg_.rms_norm_eps, st ) );
+                                                                                ringRows() && !g ? std::min( max_len, (int)L.cacheCapacity() ) : max_len, (int)cfg_.windowFor( g ),
+                                                                                L.attentionScale(), cfg_.rms_norm_eps, st ) );      // (a ring layer: the entry wants max_len <= capacity, and its plan is the window's anyway)
                 // 4. o_proj
                 L.o_proj->getOperation().matvecRows( R.o->data(), R.attn->data(), B, (int64_t)NH * HD, D );
                 // 5. post_attn_norm + residual + pre_ffn_norm + gate_up + GeGLU
@@ -1862,9 +1905,23 @@ namespace Mila::Dnn
                                                                           dst_mask, static_cast<int>( len ), ctx_->getStream() ) );
                 return;
             }
+            if ( !fork_layers_band_.empty() )      // a ring model: every layer's live band, and what the destination rows hold from now on
+            {
+                Compute::rocmCheck( mila_cdna4_kv_rows_fork_layers_band_bf16( fork_layers_band_.data(), static_cast<int>( fork_layers_band_.size() ), static_cast<int>( cfg_.max_batch ), src,
+                                                                              dst_mask, static_cast<int>( len ), ctx_->getStream() ) );
+                for ( size_t r = 0; r < row_high_.size(); ++r )
+                    if ( ( dst_mask >> r ) & 1u ) { row_high_[ r ] = len; row_from_[ r ] = std::max<dim_t>( 0, len - cfg_.window + 1 ); }
+                return;
+            }
             Compute::rocmCheck( mila_cdna4_kv_rows_fork_layers_bf16( fork_layers_.data(), static_cast<int>( fork_layers_.size() ), static_cast<int>( cfg_.max_batch ), src, dst_mask,
                                                                      static_cast<int>( len ), ctx_->getStream() ) );
         }
+        /// A ring model's account of row b (GemmaConfig::bounded_local_kv_rows; Mila/PrefixCache.h states the rule): row_high_ -- the furthest length written since the row
+        /// was last written from position 0, as far as prefillRow / forkRow / forkRowPrefix / rewindKvCacheRow were told (steps advance on the device: their callers pass
+        /// `written`); row_from_ -- the lowest position a band fork is known to have left intact.  Positions below max( row_from_, row_high_ - capacity + 1 ) count as gone.
+        bool ringRows() const noexcept { return ring_capacity_ > 0; }
+        dim_t rowValidFrom( int b ) const noexcept { return std::max<dim_t>( { 0, row_from_[ static_cast<size_t>( b ) ], row_high_[ static_cast<size_t>( b ) ] - ring_capacity_ + 1 } ); }
+        bool rowHolds( int b, dim_t position ) const noexcept { return std::max<dim_t>( 0, position - cfg_.window + 1 ) >= rowValidFrom( b ); }      // PrefixCache::usable, on this account
         void requireRows( int b ) const
         {
             if ( !rows_ || cfg_.max_batch <= 1 ) throw std::logic_error( "GemmaTransformer: the rows interface needs GemmaConfig::max_batch > 1" );
@@ -1906,11 +1963,20 @@ namespace Mila::Dnn
             {
                 fork_layers_.clear();      // the layer tables of forkRow / forkRowPrefix (one per cache policy; a model has layers of one): built once, here
                 fork_layers_fp8_.clear();
+                fork_layers_band_.clear();
+                ring_capacity_ = 0;
+                row_high_.assign( static_cast<size_t>( B ), 0 );
+                row_from_.assign( static_cast<size_t>( B ), 0 );
                 for ( auto& L : layers_ )
                 {
                     L.setCacheRows( static_cast<int>( B ) );
                     const auto NKV = static_cast<int32_t>( cfg_.numKvHeads( L.global ) ), cap = static_cast<int32_t>( L.cacheCapacity() ), HD = static_cast<int32_t>( cfg_.headDim( L.global ) );
                     if ( L.kvFp8() ) fork_layers_fp8_.push_back( mila_kv_fork_layer_fp8{ L.keyCacheFp8Rows(), L.valueCacheFp8Rows(), L.keyScalesRows(), L.valueScalesRows(), NKV, cap, HD, 0 } );
+                    else if ( cfg_.bounded_local_kv_rows )      // rings on the sliding-window layers: the live band of each (a global layer: window 0, the whole prefix)
+                    {
+                        fork_layers_band_.push_back( mila_kv_fork_layer_band{ L.keyCacheRows(), L.valueCacheRows(), NKV, cap, HD, static_cast<int32_t>( cfg_.windowFor( L.global ) ) } );
+                        if ( !L.global ) ring_capacity_ = cap;
+                    }
                     else fork_layers_.push_back( mila_kv_fork_layer{ L.keyCacheRows(), L.valueCacheRows(), NKV, cap, HD, 0 } );
                 }
             }
@@ -2298,6 +2364,9 @@ namespace Mila::Dnn
         LayerList layers_;
         std::vector<mila_kv_fork_layer> fork_layers_;
         std::vector<mila_kv_fork_layer_fp8> fork_layers_fp8_;
+        std::vector<mila_kv_fork_layer_band> fork_layers_band_;      // bounded_local_kv_rows: every layer, the sliding-window ones with their window
+        dim_t ring_capacity_{ 0 };                                    // ... the ring layers' capacity (0: no ring rows)
+        std::vector<dim_t> row_high_, row_from_;                      // ... per row (ringRows())
         std::shared_ptr<RmsNormType> final_norm_;
         std::shared_ptr<LmHeadLinearType> lm_head_;
         std::unique_ptr<TensorType> hidden_[ 3 ], pf_x_[ 2 ], f_qkv_, f_q_, f_o_, f_down_, f_act_;

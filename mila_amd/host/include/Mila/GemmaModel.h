@@ -310,6 +310,10 @@ namespace Mila::Dnn
         /// GemmaConfig::kv_fp8_rows: the FP8 KV cache (implied) on a model of max_batch 1 .. 4 -- generateBatch / generateRequests / serveRequests over FP8 rows
         GemmaModelConfig& withKvFp8Rows( bool on ) { kv_fp8_rows_ = on; return *this; }
         bool kvFp8Rows() const noexcept { return kv_fp8_rows_; }
+        /// GemmaConfig::bounded_local_kv_rows: rings on the sliding-window layers (bounded_local_kv, implied) on a model of max_batch 1 .. 4 -- generateBatch /
+        /// generateRequests / serveRequests over rows that keep window + chunk - 1 positions per sliding-window layer; forks copy the live band
+        GemmaModelConfig& withBoundedLocalKvRows( bool on ) { bounded_local_kv_rows_ = on; return *this; }
+        bool boundedLocalKvRows() const noexcept { return bounded_local_kv_rows_; }
         dim_t getContextLength() const noexcept { return context_length_; }
         WeightQuantization getWeightQuantization() const noexcept { return weight_quantization_; }
         KvCacheCompression getKvCacheCompression() const noexcept { return kv_cache_compression_; }
@@ -320,7 +324,7 @@ namespace Mila::Dnn
         dim_t context_length_{ 0 }, prefill_chunk_{ 0 }, max_batch_{ 1 }, draft_tokens_{ 0 };
         WeightQuantization weight_quantization_{ WeightQuantization::None };
         KvCacheCompression kv_cache_compression_{ KvCacheCompression::None };
-        bool bounded_local_kv_{ false }, kv_fp8_{ false }, kv_fp8_rows_{ false };
+        bool bounded_local_kv_{ false }, kv_fp8_{ false }, kv_fp8_rows_{ false }, bounded_local_kv_rows_{ false };
     };
 
     /// Models/QuantizationDispatch.ixx: the runtime deployment choice picks the compile-time policy
@@ -381,6 +385,7 @@ namespace Mila::Dnn
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
                     cfg.kv_fp8 = model_config.kvFp8();
                     cfg.kv_fp8_rows = model_config.kvFp8Rows();
+                    cfg.bounded_local_kv_rows = model_config.boundedLocalKvRows();
                     cfg.max_batch = model_config.maxBatch();
                     cfg.draft_tokens = model_config.draftTokens();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
@@ -399,6 +404,7 @@ namespace Mila::Dnn
                     cfg.bounded_local_kv = model_config.boundedLocalKv();
                     cfg.kv_fp8 = model_config.kvFp8();
                     cfg.kv_fp8_rows = model_config.kvFp8Rows();
+                    cfg.bounded_local_kv_rows = model_config.boundedLocalKvRows();
                     cfg.max_batch = model_config.maxBatch();
                     cfg.draft_tokens = model_config.draftTokens();
                     auto net = std::make_unique<Net<TWeightQuantization>>( cfg, model_config.getContextLength(), model_config.getPrefillChunk(), device_id );
@@ -750,7 +756,7 @@ namespace Mila::Dnn
                                 prefix_cache_.beginWrite( a.row, 0 );
                                 net.forkRow( a.fork_from, 1u << a.row, len );
                                 ctx->synchronize();
-                                prefix_cache_.extend( a.row, whole );
+                                prefix_cache_.adopt( a.row, whole );      // (a ring model's fork is the live band: the claim comes with its valid-from bound)
                                 st.fork_ms += since( f0 );
                                 ++st.forks;
                                 st.reused_tokens[ i ] = len;
@@ -765,7 +771,7 @@ namespace Mila::Dnn
                                 const auto f0 = Clock::now();
                                 net.forkRowPrefix( pl.donor, 1u << a.row, L );
                                 ctx->synchronize();
-                                prefix_cache_.extend( a.row, whole.first( static_cast<size_t>( L ) ) );
+                                prefix_cache_.adopt( a.row, whole.first( static_cast<size_t>( L ) ) );
                                 st.fork_ms += since( f0 );
                                 ++st.prefix_forks;
                             }
@@ -1083,6 +1089,8 @@ namespace Mila::Dnn
             : network_( std::move( net ) ), network_config_( cfg ), model_config_( mc ), source_metadata_( std::move( md ) )
         {
             const auto dev = std::visit( []( auto& n ) { return n->context()->getDeviceId(); }, network_ );
+            // a ring rows model (GemmaConfig::bounded_local_kv_rows): the prefix rule with the rings' geometry (Mila/PrefixCache.h); 0 / 0 otherwise, the flat rule
+            std::visit( [&]( auto& n ) { if ( n->rowsRingCapacity() > 0 ) prefix_cache_ = PrefixCache( PrefixCache::kMaxRows, n->config().window, n->rowsRingCapacity() ); }, network_ );
             prompt_dev_ = std::make_unique<TokenTensor>( dev, shape_t{ 1, mc.getPrefillChunk() } );
             decode_token_device_ = std::make_unique<TokenTensor>( dev, shape_t{ 1 } );
             seq_dev_ = std::make_unique<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>>( dev, shape_t{ 2 } );      // one 64-bit counter

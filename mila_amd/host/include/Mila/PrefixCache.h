@@ -21,8 +21,29 @@
 // admission k sees the claims as the admissions before it left them -- their fresh whole prompts included, and the claims they cut excluded.  Planning a whole wave up
 // front would let two admissions name each other's row as the donor after the first has already overwritten it.
 //
-// Not here: copying only a windowed layer's live band (a claim would need a valid-from bound), choosing the free row by best match, any eviction beyond "a written row
-// loses its claim", sharing with generate()'s row-0 history.
+// RINGS.  PrefixCache( rows, window, capacity ) with window > 0 is the rule of a model whose sliding-window layers sit on rings of `capacity` cells, position p at cell
+// p % capacity (GemmaConfig::bounded_local_kv_rows), and whose forks copy a ring layer's live band [max( 0, len - window ), len) only.  A claim then says less than "all of
+// [0, |H_r|)": on the ring layers only the positions from a VALID-FROM bound on are intact.  Beside H_r each row keeps
+//   high_r        the furthest length ever written since the row was last written from position 0 (a cut claim keeps it: the stale tail is still in the ring), and
+//   from_r        the lowest position a band fork is known to have left intact in the row (0 when the row was prefilled from 0);
+//   valid_from_r  = max( 0, from_r, high_r - capacity + 1 ): the writes up to high_r have reused the cells of every position below high_r - capacity, and the cell of
+//                   position high_r - capacity is the one the next write takes.  It counts as taken: a rows step also writes a row that is in the step but not live --
+//                   the K / V of a stale token at the row's position word, |H_r| <= high_r.
+// A continuation from `reuse` reads down to reuse - window + 1:
+//   usable( s, reuse ) = max( 0, reuse - window + 1 ) >= valid_from_s.
+// For reuse >= window that is reuse - window >= max( len_fork - window, high_s - capacity ) -- the ring rule of RocmGqaOp::rewindKvCache, high - reuse <= capacity - window,
+// and a forked row's bound max( 0, len - window ).  Below the window it is stricter than that form read with max( 0, . ): a row written up to exactly `capacity`, or forked
+// at exactly `window`, may have lost position 0, which a shorter prefix would read.
+// The bound is a LOWER bound, so a shorter prefix of the same row is never usable where a longer one is not: plan() counts an unusable row's match as 0 and nothing else
+// changes -- reuse = min( max over usable s of m_s, len - 1 ), where usable is asked at min( m_s, len - 1 ).
+//   adopt( r, tokens )     AFTER a band fork into row r: H_r = tokens, high_r = |tokens|, from_r = max( 0, |tokens| - window + 1 ) (the fork copies one position more,
+//                          |tokens| - window; the donor was not asked for it);
+//   beginWrite( r, 0 )     the row is about to be written from position 0: high_r = from_r = 0;   beginWrite( r, keep > 0 ) keeps both;
+//   extend / fed           raise high_r to |H_r|.
+// With window = capacity = 0 (the default) no bound exists and every answer is the one above.
+//
+// Not here: copying more than the live band to keep a forked row's donation range, choosing the free row by best match, any eviction beyond "a written row loses its
+// claim", sharing with generate()'s row-0 history.
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
@@ -45,9 +66,11 @@ namespace Mila::Dnn
             bool operator==( const Plan& ) const = default;
         };
 
-        explicit PrefixCache( int rows = kMaxRows ) : rows_( rows )
+        explicit PrefixCache( int rows = kMaxRows, int64_t window = 0, int64_t capacity = 0 ) : rows_( rows ), window_( window ), capacity_( capacity )
         {
             if ( rows < 1 || rows > kMaxRows ) throw std::invalid_argument( "PrefixCache: " + std::to_string( rows ) + " rows (1 .. 4)" );
+            if ( window < 0 || capacity < 0 || ( window > 0 ) != ( capacity > 0 ) || capacity < window )
+                throw std::invalid_argument( "PrefixCache: window " + std::to_string( window ) + " and ring capacity " + std::to_string( capacity ) + " (both 0, or 0 < window <= capacity)" );
         }
         Plan plan( int row, std::span<const int32_t> prompt, int64_t min_prefix = 1 ) const
         {
@@ -55,7 +78,13 @@ namespace Mila::Dnn
             if ( prompt.empty() ) throw std::invalid_argument( "PrefixCache::plan: empty prompt" );
             if ( min_prefix < 1 ) throw std::invalid_argument( "PrefixCache::plan: min_prefix " + std::to_string( min_prefix ) + " (>= 1)" );
             int64_t m[ kMaxRows ] = {}, best = 0;
-            for ( int s = 0; s < rows_; ++s ) { m[ s ] = common( claim_[ s ], prompt ); best = std::max( best, m[ s ] ); }
+            const int64_t last = static_cast<int64_t>( prompt.size() ) - 1;
+            for ( int s = 0; s < rows_; ++s )
+            {
+                m[ s ] = common( claim_[ s ], prompt );
+                if ( !usable( s, std::min( m[ s ], last ) ) ) m[ s ] = 0;      // (a shorter prefix of the same row is no better: the bound is a lower bound)
+                best = std::max( best, m[ s ] );
+            }
             const int64_t reuse = std::min<int64_t>( best, static_cast<int64_t>( prompt.size() ) - 1 );
             if ( reuse < min_prefix ) return {};
             if ( m[ row ] >= reuse ) return { row, reuse };
@@ -67,12 +96,27 @@ namespace Mila::Dnn
             auto& h = claim_[ checkedRow( row ) ];
             if ( keep > h.size() ) throw std::logic_error( "PrefixCache::beginWrite: row " + std::to_string( row ) + " keeps " + std::to_string( keep ) + " of " + std::to_string( h.size() ) + " claimed positions" );
             h.resize( keep );
+            if ( keep == 0 ) high_[ row ] = from_[ row ] = 0;      // written from position 0: whatever the ring held no longer counts
         }
-        void extend( int row, std::span<const int32_t> tokens ) { auto& h = claim_[ checkedRow( row ) ]; h.insert( h.end(), tokens.begin(), tokens.end() ); }
-        void fed( int row, int32_t token ) { claim_[ checkedRow( row ) ].push_back( token ); }
+        void extend( int row, std::span<const int32_t> tokens ) { auto& h = claim_[ checkedRow( row ) ]; h.insert( h.end(), tokens.begin(), tokens.end() ); wrote( row ); }
+        void fed( int row, int32_t token ) { claim_[ checkedRow( row ) ].push_back( token ); wrote( row ); }
+        /// after a band fork of `tokens` into the row: on the ring layers only [max( 0, len - window ), len) is there
+        void adopt( int row, std::span<const int32_t> tokens )
+        {
+            claim_[ checkedRow( row ) ].assign( tokens.begin(), tokens.end() );
+            high_[ row ] = static_cast<int64_t>( tokens.size() );
+            from_[ row ] = window_ > 0 ? std::max<int64_t>( 0, high_[ row ] - window_ + 1 ) : 0;
+        }
         void invalidate( int row ) { claim_[ checkedRow( row ) ].clear(); }
         void clear() noexcept { for ( auto& h : claim_ ) h.clear(); }
         int rows() const noexcept { return rows_; }
+        int64_t window() const noexcept { return window_; }
+        int64_t capacity() const noexcept { return capacity_; }
+        int64_t high( int row ) const { return high_[ checkedRow( row ) ]; }
+        /// the lowest position of row `row` whose ring contents are intact (0 without rings)
+        int64_t validFrom( int row ) const { checkedRow( row ); return window_ > 0 ? std::max<int64_t>( { 0, from_[ row ], high_[ row ] - capacity_ + 1 } ) : 0; }
+        /// may a continuation from `reuse` run on what row `row` holds (given that its claim matches that far)?
+        bool usable( int row, int64_t reuse ) const { return window_ <= 0 || std::max<int64_t>( 0, reuse - window_ + 1 ) >= validFrom( row ); }
         const std::vector<int32_t>& claim( int row ) const { return claim_[ checkedRow( row ) ]; }
 
     private:
@@ -88,7 +132,10 @@ namespace Mila::Dnn
             if ( row < 0 || row >= rows_ ) throw std::invalid_argument( "PrefixCache: row " + std::to_string( row ) + " outside the " + std::to_string( rows_ ) + " rows" );
             return row;
         }
+        void wrote( int row ) { high_[ row ] = std::max( high_[ row ], static_cast<int64_t>( claim_[ row ].size() ) ); }
         int rows_;
+        int64_t window_, capacity_;
+        int64_t high_[ kMaxRows ] = {}, from_[ kMaxRows ] = {};
         std::vector<int32_t> claim_[ kMaxRows ];
     };
 }

@@ -239,6 +239,45 @@ HOST_API int mila_gemma_validate_config_kv( const mila_gemma_config* c, int64_t 
 {
     return guarded( [&] { GemmaConfig cfg = gemma_config_of( c ); cfg.max_batch = max_batch; cfg.draft_tokens = draft_tokens; cfg.kv_fp8_rows = kv_fp8_rows != 0; cfg.validate(); } );
 }
+/// ... with GemmaConfig::bounded_local_kv_rows as well (bounded_local_kv_rows != 0): the rings that max_batch > 1 may be combined with
+HOST_API int mila_gemma_validate_config_ring( const mila_gemma_config* c, int64_t max_batch, int64_t draft_tokens, int kv_fp8_rows, int bounded_local_kv_rows )
+{
+    return guarded( [&]
+    {
+        GemmaConfig cfg = gemma_config_of( c );
+        cfg.max_batch = max_batch; cfg.draft_tokens = draft_tokens; cfg.kv_fp8_rows = kv_fp8_rows != 0; cfg.bounded_local_kv_rows = bounded_local_kv_rows != 0;
+        cfg.validate();
+    } );
+}
+/// mila_gemma_create_rows with GemmaConfig::bounded_local_kv_rows: max_batch (1 .. 4) sequences per decode step, each with its own rings on the sliding-window layers.
+/// bounded_local_kv_rows = 0 builds the model mila_gemma_create_rows builds.
+HOST_API void* mila_gemma_create_rows_ring( int policy, const mila_gemma_config* c, int64_t max_seq, int64_t max_prefill, int64_t max_batch, int bounded_local_kv_rows, uint64_t seed, int device )
+{
+    Runner* r = nullptr;
+    int rc = guarded( [&]
+    {
+        GemmaConfig cfg = gemma_config_of( c );
+        cfg.max_batch = max_batch;
+        cfg.bounded_local_kv_rows = bounded_local_kv_rows != 0;
+        auto rr = std::make_unique<Runner>();
+        rr->max_prefill = max_prefill;
+        switch ( policy )
+        {
+            case 0: rr->model = std::make_unique<GemmaTransformer<NoWeightQuant>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            case 1: rr->model = std::make_unique<GemmaTransformer<PerChannelFp8<>>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            case 2: rr->model = std::make_unique<GemmaTransformer<PerGroupFp4<128>>>( cfg, max_seq, max_prefill, Compute::Device::Rocm( device ) ); break;
+            default: throw std::invalid_argument( "unknown weight policy" );
+        }
+        std::visit( [&]( auto& m )
+        {
+            m->initSynthetic( seed );
+            rr->tokens = std::make_unique<Tensor<TensorDataType::INT32, Compute::RocmDeviceMemoryResource>>(
+                m->context()->getDeviceId(), shape_t{ std::max<dim_t>( max_prefill, 1 ) } );
+        }, rr->model );
+        r = rr.release();
+    } );
+    return rc == 0 ? r : nullptr;
+}
 /// mila_gemma_create_rows with GemmaConfig::kv_fp8_rows: max_batch (1 .. 4) sequences per decode step, each on its own FP8 KV caches.  kv_fp8_rows = 0 builds the model
 /// mila_gemma_create_rows builds.
 HOST_API void* mila_gemma_create_rows_kv( int policy, const mila_gemma_config* c, int64_t max_seq, int64_t max_prefill, int64_t max_batch, int kv_fp8_rows, uint64_t seed, int device )
@@ -712,6 +751,16 @@ HOST_API int mila_gemma_set_active( void* h, int b, int active, int32_t token )
 HOST_API int mila_gemma_reset_row( void* h, int b )
 {
     return guarded( [&] { std::visit( [&]( auto& m ) { m->resetRow( b ); }, static_cast<Runner*>( h )->model ); } );
+}
+/// GemmaTransformer::rewindKvCacheRow: *accepted = 1 and row b goes on from `position`, or 0 (out of range; on a ring model: the row's rings no longer hold what a
+/// continuation from `position` reads) and nothing changed
+HOST_API int mila_gemma_rewind_row( void* h, int b, int64_t position, int64_t written, int* accepted )
+{
+    return guarded( [&]
+    {
+        if ( !accepted ) throw std::invalid_argument( "mila_gemma_rewind_row: null result" );
+        std::visit( [&]( auto& m ) { *accepted = m->rewindKvCacheRow( b, position, written ) ? 1 : 0; }, static_cast<Runner*>( h )->model );
+    } );
 }
 /// GemmaTransformer::forkRow (whole != 0: caches [0, len), logits and position, directly behind row src's prefill of len tokens) or forkRowPrefix (caches only, from
 /// any row at a position >= len)
@@ -1715,6 +1764,22 @@ HOST_API void* mila_gemma_model_synthetic_rows_kv( int policy, const mila_gemma_
         if ( p ) { pr.linear_gain = p[ 0 ]; pr.qk_norm_center = p[ 1 ]; pr.post_norm_center = p[ 2 ]; pr.layer_scalar = p[ 3 ]; pr.table_gain = p[ 4 ]; }
         m = RocmGemmaModel::fromSynthetic( cfg, model_config_of( policy, context, prefill_chunk, cfg.bounded_local_kv, cfg.kv_fp8 ).withMaxBatch( max_batch ).withKvFp8Rows( kv_fp8_rows != 0 ),
                                            seed, pr, Compute::Device::Rocm( device ) ).release();
+    } );
+    return rc == 0 ? m : nullptr;
+}
+
+/// mila_gemma_model_synthetic_rows with GemmaModelConfig::withBoundedLocalKvRows( bounded_local_kv_rows != 0 ): the rows model with rings on the sliding-window layers
+HOST_API void* mila_gemma_model_synthetic_rows_ring( int policy, const mila_gemma_config* c, int64_t context, int64_t prefill_chunk, int64_t max_batch, int bounded_local_kv_rows,
+                                                     uint64_t seed, const float* p, int device )
+{
+    RocmGemmaModel* m = nullptr;
+    int rc = guarded( [&]
+    {
+        GemmaConfig cfg = gemma_config_of( c );
+        GemmaTransformer<NoWeightQuant>::SyntheticProfile pr;
+        if ( p ) { pr.linear_gain = p[ 0 ]; pr.qk_norm_center = p[ 1 ]; pr.post_norm_center = p[ 2 ]; pr.layer_scalar = p[ 3 ]; pr.table_gain = p[ 4 ]; }
+        m = RocmGemmaModel::fromSynthetic( cfg, model_config_of( policy, context, prefill_chunk, cfg.bounded_local_kv, cfg.kv_fp8 ).withMaxBatch( max_batch )
+                                                    .withBoundedLocalKvRows( bounded_local_kv_rows != 0 ), seed, pr, Compute::Device::Rocm( device ) ).release();
     } );
     return rc == 0 ? m : nullptr;
 }
